@@ -117,6 +117,25 @@ def test_bench_workload_text_and_spawn_command():
     assert cmd[cmd.index("--master-addr") + 1] == "127.0.0.1" and cmd[-4:] == ["--gpus", "4", "--steps", "20"]
 
 
+def test_bench_write_outputs_budget_and_sample(tmp_path):
+    """--dump-outputs: float32 arrays stay float32, others become float64; an array past the byte budget is written as a fixed (seeded) sample
+    of its rows, in order, so that two runs of the same build write the same files"""
+    b = _bench()
+    acc = np.arange(600 * 50 * 4, dtype=np.float32).reshape(600, 50, 4)
+    b.write_outputs(str(tmp_path / "whole"), {"accumulator": acc, "rays": np.array([7], np.int64)})
+    assert np.array_equal(np.load(str(tmp_path / "whole" / "accumulator.npy")), acc)
+    r = np.load(str(tmp_path / "whole" / "rays.npy"))
+    assert r.dtype == np.float64 and r.tolist() == [7.0]
+    for run in ("a", "b"):
+        b.write_outputs(str(tmp_path / run), {"accumulator": acc, "rays": np.array([7], np.int64)}, max_bytes=200000)
+        assert sorted(os.listdir(str(tmp_path / run))) == ["accumulator_sample.npy", "rays.npy"]
+        assert sum(os.path.getsize(str(tmp_path / run / f)) for f in os.listdir(str(tmp_path / run))) <= 200000
+    s1, s2 = np.load(str(tmp_path / "a" / "accumulator_sample.npy")), np.load(str(tmp_path / "b" / "accumulator_sample.npy"))
+    assert np.array_equal(s1, s2) and s1.dtype == np.float32 and s1.shape[1:] == (50, 4) and 0 < s1.shape[0] < 600
+    rows = s1[:, 0, 0].astype(np.int64) // 200
+    assert np.all(np.diff(rows) > 0) and np.array_equal(s1, acc[rows])
+
+
 def test_bench_spawns_its_own_ranks():
     """`bench.py --gpus 2` with no WORLD_SIZE in the environment starts its two ranks itself (gloo rendezvous on 127.0.0.1 here); without a GPU
     every rank stops at the product's "no CPU path" message — after the ranks have found each other — and the launcher hands the failure on"""

@@ -184,10 +184,10 @@ def test_config4_tower_1080p_256spp(crt, orc):
 
 
 def test_bench_json_contract():
-    """bench.py's one-line JSON: the driver's contract fields + the roofline and cpu_baseline objects (small run of the real script)"""
+    """bench.py --full's one-line JSON: the driver's contract fields + the roofline and cpu_baseline objects (small run of the real script)"""
     import json, os, subprocess, sys
     from conftest import REPO
-    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "3", "--warmup", "1", "--width", "320", "--height", "192"],
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--full", "--steps", "3", "--warmup", "1", "--width", "320", "--height", "192"],
                        capture_output=True, text=True, timeout=600, env=dict(os.environ, CRT_BENCH_CPU_BUDGET_S="1"))
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -214,11 +214,40 @@ def test_bench_starts_its_own_ranks_for_gpus_2():
     from conftest import REPO
     env = dict(os.environ, CRT_BENCH_BACKEND="gloo", CRT_BENCH_CPU_BUDGET_S="1")
     env.pop("WORLD_SIZE", None); env.pop("RANK", None)
-    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--width", "320", "--height", "192", "--no-single-render"],
+    r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--full", "--steps", "3", "--warmup", "1", "--width", "320", "--height", "192", "--no-single-render"],
                        capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
     d = json.loads(lines[0])
     assert d["n_gpus"] == 2 and d["scaling"] == "strong" and d["config"]["rccl_ranks"] == 2 and d["config"]["collective"] in ("reduce", "all_reduce")
-    assert "dealt round-robin over 2 ranks" in d["config"]["workload"] and d["value"] > 0 and "cpu_baseline" not in d
+    assert "dealt round-robin over 2 ranks" in d["config"]["workload"] and d["value"] > 0 and "cpu_baseline" not in d and "roofline" in d
+
+
+def test_bench_plain_line_and_dumped_outputs(orc, tmp_path):
+    """plain bench.py (no --full): the contract fields and none of what --full measures; --dump-outputs writes what the timed job computed —
+    the accumulator after its last step (float32, H x W x 4: the oracle's image of the same frames) and the ray count — identically in two runs"""
+    import json, os, subprocess, sys
+    from conftest import REPO
+    w, h, steps = 64, 32, 2
+    lines = []
+    for run in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", str(steps), "--warmup", "1", "--width", str(w), "--height", str(h),
+                            "--dump-outputs", str(tmp_path / run)], capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines += [json.loads(l) for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 2
+    for d in lines:
+        assert d["steps"] == steps and d["unit"] == "Mrays/s" and d["dtype"] == "f32" and d["higher_is_better"] is True and d["value"] > 0
+        assert d["ms_per_step"] > 0 and d["n_gpus"] == 1 and d["warmup"] == 1
+        assert "roofline" not in d and "cpu_baseline" not in d and d["single_render"] is None
+    acc = np.load(str(tmp_path / "a" / "accumulator.npy"))
+    rays = np.load(str(tmp_path / "a" / "rays.npy"))
+    assert acc.dtype == np.float32 and acc.shape == (h, w, 4) and rays.dtype == np.float64 and rays.shape == (1,)
+    assert np.array_equal(acc, np.load(str(tmp_path / "b" / "accumulator.npy"))) and np.array_equal(rays, np.load(str(tmp_path / "b" / "rays.npy")))
+    assert abs(rays[0] - lines[0]["config"]["rays_per_step_rank0"] * steps) <= steps
+    o, _ = orc.load_scene(scene_path("bunny_scene.xml"), 0, ASSETS)
+    o.renderer_init(w, h)
+    o.render(64 * steps, 2)
+    assert np.abs(acc - o.accumulator()).max() / (64 * steps) <= 1e-4
+    assert rays[0] == o.counters()["rays"]

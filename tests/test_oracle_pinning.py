@@ -1,5 +1,6 @@
 """CPU tests that pin the oracle:
-  * against the REAL reference compiled in place (oracle/_ref: infra/bvh.cpp, tinyobj, stb_image) — authoring container only;
+  * against the REAL reference compiled in place (oracle/_ref: infra/bvh.cpp, tinyobj, stb_image) where it can be built, and elsewhere
+    against the outputs it gave for the same inputs (tests/golden/ref_live*);
   * against the committed golden vectors those runs produced (tests/golden/ref_*) — everywhere, including the GPU box;
   * regression vectors for the parts with no executable reference (tests/golden/orc_*, "parity unpinned")."""
 import json
@@ -131,76 +132,154 @@ def test_oracle_refit_matches_reference_golden(orc, mesh):
 
 
 # ---------------------------------------------------------------------------------------------------------------
-# live comparison with the real reference (authoring container)
+# live comparison with the real reference: oracle/_ref where it is built, elsewhere the outputs it gave for the same inputs
+# (tests/golden/ref_live.json: shape + CRC32 per output; ref_live_masks.npz: the ray masks the comparisons are restricted to)
 # ---------------------------------------------------------------------------------------------------------------
-def test_oracle_camera_and_texture_vs_reference_live(orc, ref):
+LIVE_JSON = os.path.join(GOLDEN, "ref_live.json")
+LIVE_NPZ = os.path.join(GOLDEN, "ref_live_masks.npz")
+
+
+def _canon(a, nan_any=False):
+    """the bits an output is compared by: raw bytes of records, the bit patterns of floats (nan_any: every NaN as one pattern), the values of integers"""
+    a = np.ascontiguousarray(a)
+    if a.dtype.names:
+        return a.view(np.uint8)
+    if a.dtype.kind == "f":
+        a = a.view(np.uint32 if a.itemsize == 4 else np.uint64)
+        return np.where((a & 0x7fffffff) > 0x7f800000, np.uint32(0x7fc00000), a) if nan_any else a
+    return a.astype(np.int64)
+
+
+class LiveRef:
+    """`ref` is the real reference's library (oracle/_ref) where it is built, else None.  check() compares an output of the oracle with the
+    reference's bit for bit: live when the library is there (and then also with the recording, which must not go stale), otherwise with the
+    recorded shape + CRC32 of the reference's output for the same inputs.  CRT_RECORD_REF_LIVE=1 with oracle/_ref built re-records."""
+
+    def __init__(self, ref, recording):
+        self.ref, self.recording = ref, recording
+        self.crcs = json.load(open(LIVE_JSON)) if os.path.exists(LIVE_JSON) or not recording else {}
+        self.arrays = dict(np.load(LIVE_NPZ)) if os.path.exists(LIVE_NPZ) or not recording else {}
+
+    def _keep(self, store, key, value, same):
+        if self.recording:
+            store[key] = value
+        else:
+            assert same(store[key], value), "%s: tests/golden/ref_live* is stale (re-record with CRT_RECORD_REF_LIVE=1)" % key
+
+    def check(self, key, mine, theirs=None, nan_any=False):
+        m = _canon(mine, nan_any)
+        if self.ref is None:
+            assert self.crcs[key] == [list(m.shape), crc(m)], key
+            return
+        t = _canon(theirs, nan_any)
+        assert m.shape == t.shape and np.array_equal(m, t), key
+        self._keep(self.crcs, key, [list(t.shape), crc(t)], lambda x, y: x == y)
+
+    def mask(self, key, theirs=None):
+        """a boolean ray mask of the reference's (which rays hit the mesh): live, or as recorded"""
+        if self.ref is None:
+            return self.arrays[key]
+        self._keep(self.arrays, key, theirs, np.array_equal)
+        return theirs
+
+
+@pytest.fixture(scope="module")
+def live(orc):
+    try:
+        ref = orc.Ref()
+    except FileNotFoundError:
+        ref = None
+    lr = LiveRef(ref, ref is not None and os.environ.get("CRT_RECORD_REF_LIVE") == "1")
+    yield lr
+    if lr.recording:
+        with open(LIVE_JSON, "w") as f:
+            json.dump(lr.crcs, f, indent=1, sort_keys=True)
+        np.savez_compressed(LIVE_NPZ, **lr.arrays)
+
+
+def test_oracle_camera_and_texture_vs_reference_live(orc, live):
+    ref = live.ref
     rng = np.random.default_rng(3)
     xy = rng.uniform(-2, [1026, 642], (4000, 2)).astype(np.float32)
-    for pt in (None, ((0.5, 1.25, -3.0), (0.0, 0.0, 2.0)), ((-2.0, 3.0, 1.0), (0.0, -1.0, 2.5))):
-        corners, O, D = ref.camera_rays(xy, pt)
+    live.check("camera_xy", xy, xy)                 # (the inputs: the recorded outputs belong to these)
+    for i, pt in enumerate((None, ((0.5, 1.25, -3.0), (0.0, 0.0, 2.0)), ((-2.0, 3.0, 1.0), (0.0, -1.0, 2.5)))):
+        corners, O, D = ref.camera_rays(xy, pt) if ref else (None, None, None)
         o = camera_oracle(orc, pt)
-        assert np.array_equal(np.stack(o.camera()).view(np.uint32), corners.view(np.uint32))
+        live.check("camera%d_corners" % i, np.stack(o.camera()), corners)
         oO, oD = o.primary_rays(xy)
-        assert np.array_equal(oO.view(np.uint32), O.view(np.uint32)) and np.array_equal(oD.view(np.uint32), D.view(np.uint32))
+        live.check("camera%d_O" % i, oO, O)
+        live.check("camera%d_D" % i, oD, D)
     for f in ("textures/Stylized_Pavement_basecolor.png", "textures/Stylized_Wood_basecolor.tga", "textures/Defuse_wok.png"):
-        tex = ref.texture_load(os.path.join(ASSETS, f))
-        assert np.array_equal(tex, orc.pack_rgb(orc.read_image(os.path.join(ASSETS, f)))), f
+        live.check("texture_load " + f, orc.pack_rgb(orc.read_image(os.path.join(ASSETS, f))), ref.texture_load(os.path.join(ASSETS, f)) if ref else None)
     uv = rng.uniform(-0.5, 1.5, (20000, 2)).astype(np.float32)
     small = rng.integers(0, 1 << 24, (37, 53)).astype(np.uint32)
-    for tex in (ref.texture_load(os.path.join(ASSETS, "textures/Stylized_Pavement_basecolor.png")), small):
-        rgb, alb = ref.texture_sample(tex, uv)
-        assert np.array_equal(orc.texture_sample(tex, uv).view(np.uint32), rgb.view(np.uint32)) and np.array_equal(rgb, alb)
+    live.check("texture_uv", uv, uv)
+    live.check("texture_small", small, small)
+    pavement = orc.pack_rgb(orc.read_image(os.path.join(ASSETS, "textures/Stylized_Pavement_basecolor.png")))     # = Texture::LoadFromFile's texels (checked above)
+    for name, tex in (("pavement", pavement), ("small", small)):
+        rgb, alb = ref.texture_sample(tex, uv) if ref else (None, None)
+        mine = orc.texture_sample(tex, uv)
+        live.check("texture_sample %s rgb" % name, mine, rgb)
+        live.check("texture_sample %s albedo" % name, mine, alb)
 
 
 @pytest.mark.parametrize("mesh", ["bunny", "wok"])
-def test_oracle_refit_vs_reference_live(orc, ref, mesh):
+def test_oracle_refit_vs_reference_live(orc, live, mesh):
+    ref = live.ref
     o = simple_scene(orc, mesh)
     t = o.bvh(0)["tris"]
-    h, _ = ref.bvh_build(t)
-    try:
-        moved = deform(np.stack([t["vertex0"], t["vertex1"], t["vertex2"]], axis=1))
-        rn = ref.bvh_move_and_refit(h, moved)
-        o.move_and_refit(0, moved)
-        assert np.array_equal(rn.view(np.uint8), o.bvh(0)["nodes"].view(np.uint8))
-    finally:
-        ref.bvh_free(h)
-
+    live.check("refit %s tris" % mesh, t, t)
+    moved = deform(np.stack([t["vertex0"], t["vertex1"], t["vertex2"]], axis=1))
+    rn = None
+    if ref:
+        h, _ = ref.bvh_build(t)
+        try:
+            rn = ref.bvh_move_and_refit(h, moved)
+        finally:
+            ref.bvh_free(h)
+    o.move_and_refit(0, moved)
+    live.check("refit %s nodes" % mesh, o.bvh(0)["nodes"], rn)
 
 
 @pytest.mark.parametrize("mesh", ["bunny", "wok", "teapot"])
-def test_oracle_vs_reference_live(orc, ref, mesh):
+def test_oracle_vs_reference_live(orc, live, mesh):
+    ref = live.ref
     o = simple_scene(orc, mesh)
     b = o.bvh(0)
-    h, rb = ref.bvh_build(b["tris"])
-    try:
-        assert rb["nodesUsed"] == b["nodesUsed"] and rb["maxDepth"] == b["maxDepth"]
-        assert np.array_equal(rb["nodes"].view(np.uint8), b["nodes"].view(np.uint8))
-        assert np.array_equal(rb["triIndices"], b["triIndices"])
-        rng = np.random.default_rng(99)
-        n = 20000
-        O = rng.uniform(-3, 3, (n, 3)).astype(np.float32)
-        O[:, 1] = np.abs(O[:, 1]) + 0.2
-        T = rng.uniform(-1, 1, (n, 3)).astype(np.float32) + np.array([0, -0.3, 2], np.float32)
-        D = T - O
-        D = (D / np.linalg.norm(D, axis=1, keepdims=True)).astype(np.float32)
-        rh = ref.bvh_intersect(h, O, D)
-        oh = o.find_nearest(O, D)
-        both = (oh["objIdx"] >= 2) & (rh["objIdx"] >= 2)
-        assert both.sum() > 1000
-        for f in ("t", "u", "v"):
-            assert np.array_equal(oh[f][both].view(np.uint32), rh[f][both].view(np.uint32))
-        assert np.array_equal(oh["triIdx"][both], rh["triIdx"][both])
-    finally:
-        ref.bvh_free(h)
+    live.check("bvh %s tris" % mesh, b["tris"], b["tris"])
+    rng = np.random.default_rng(99)
+    n = 20000
+    O = rng.uniform(-3, 3, (n, 3)).astype(np.float32)
+    O[:, 1] = np.abs(O[:, 1]) + 0.2
+    T = rng.uniform(-1, 1, (n, 3)).astype(np.float32) + np.array([0, -0.3, 2], np.float32)
+    D = T - O
+    D = (D / np.linalg.norm(D, axis=1, keepdims=True)).astype(np.float32)
+    live.check("bvh %s rays" % mesh, np.concatenate([O, D], axis=1), np.concatenate([O, D], axis=1))
+    rb = rh = None
+    if ref:
+        h, rb = ref.bvh_build(b["tris"])
+        try:
+            rh = ref.bvh_intersect(h, O, D)
+        finally:
+            ref.bvh_free(h)
+    live.check("bvh %s nodesUsed maxDepth" % mesh, np.array([b["nodesUsed"], b["maxDepth"]]), np.array([rb["nodesUsed"], rb["maxDepth"]]) if rb else None)
+    live.check("bvh %s nodes" % mesh, b["nodes"], rb["nodes"] if rb else None)
+    live.check("bvh %s triIndices" % mesh, b["triIndices"], rb["triIndices"] if rb else None)
+    oh = o.find_nearest(O, D)
+    both = (oh["objIdx"] >= 2) & live.mask("bvh_%s_mesh_hits" % mesh, None if rh is None else rh["objIdx"] >= 2)
+    assert both.sum() > 1000
+    for f in ("t", "u", "v", "triIdx"):
+        live.check("bvh %s %s" % (mesh, f), oh[f][both], None if rh is None else rh[f][both])
 
 
-def test_python_readers_vs_reference_live(orc, ref):
+def test_python_readers_vs_reference_live(orc, live):
+    ref = live.ref
     for m in MESHES:
-        mine, theirs = orc.read_obj(os.path.join(ASSETS, m + ".obj")), ref.obj_load(os.path.join(ASSETS, m + ".obj"))
-        for a, b in zip(mine, theirs):
-            assert a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32)), m
+        p = os.path.join(ASSETS, m + ".obj")
+        for name, a, b in zip(("pos", "nrm", "uv"), orc.read_obj(p), ref.obj_load(p) if ref else (None, None, None)):
+            live.check("obj %s %s" % (m, name), a, b)
     for f in G["ref_img"]:
-        assert np.array_equal(orc.read_image(os.path.join(ASSETS, f)), ref.image_load(os.path.join(ASSETS, f))), f
+        live.check("image " + f, orc.read_image(os.path.join(ASSETS, f)), ref.image_load(os.path.join(ASSETS, f)) if ref else None)
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -340,19 +419,19 @@ def test_vertex_table_matches_reference_golden(orc, who):
     assert uniq.shape == z["unique"].shape and _same_bits(uniq, z["unique"])
 
 
-def test_tmplmath_and_vertex_live(orc):
-    """authoring container only: the same probes against oracle/_ref directly, on fresh random inputs"""
-    try:
-        ref = orc.Ref()
-    except FileNotFoundError:
-        pytest.skip("oracle/_ref is built only where /root/reference is mounted")
+def test_tmplmath_and_vertex_live(orc, live):
+    """the same probes against oracle/_ref (or what it gave, recorded) on fresh random inputs"""
+    ref = live.ref
     rng = np.random.default_rng(5)
     x = rng.uniform(-10, 10, (3000, 12)).astype(np.float32)
-    assert _same_bits(orc.math_probe(x), ref.math_probe(x))
+    live.check("math inputs", x, x)
+    live.check("math_probe", orc.math_probe(x), ref.math_probe(x) if ref else None, nan_any=True)
     v = np.round(rng.uniform(-1, 1, (4000, 8)) * 4).astype(np.float32) / 4          # many exact duplicates, +0 and -0
+    live.check("vertex inputs", v, v)
     i1, u1 = orc.vertex_dedup(v)
-    i2, u2, _ = ref.vertex_dedup(v)
-    assert np.array_equal(i1, i2) and _same_bits(u1, u2)
+    i2, u2 = ref.vertex_dedup(v)[:2] if ref else (None, None)
+    live.check("vertex_dedup idx", i1, i2)
+    live.check("vertex_dedup unique", u1, u2, nan_any=True)
 
 
 def test_sky_lookup_deviation_from_libm_is_bounded(orc):
@@ -417,22 +496,28 @@ def test_host_front_alt_accel_build_matches_reference_golden(tmp_path, mesh, kin
     assert _alt_matches(hs.build_alt(code), G["ref_alt"][mesh][kind], kind)
 
 
-def test_alt_accel_live(orc):
-    """authoring container only: oracle vs the real kdtree.cpp / grid.cpp on a mesh and rays the goldens do not cover"""
-    try:
-        ref = orc.Ref()
-    except FileNotFoundError:
-        pytest.skip("oracle/_ref is built only where /root/reference is mounted")
+def test_alt_accel_live(orc, live):
+    """oracle vs the real kdtree.cpp / grid.cpp (or what they gave, recorded) on a mesh and rays the goldens do not cover"""
+    ref = live.ref
     tris = simple_scene(orc, "log_fence").bvh(0)["tris"]
+    live.check("alt tris", tris, tris)
     rng = np.random.default_rng(9)
     O = rng.uniform(-3, 3, (2000, 3)).astype(np.float32); O[:, 1] = np.abs(O[:, 1]) + 0.1
     D = (np.array([0, -0.5, 2], np.float32) + rng.uniform(-1, 1, (2000, 3)).astype(np.float32)) - O
     D = (D / np.linalg.norm(D, axis=1, keepdims=True)).astype(np.float32)
     D[:20, 0] = 0; D[20:40, 1] = 0; D[40:60, 2] = 0                   # axis-parallel components: infinite reciprocal, NaN plane distances
+    live.check("alt rays", np.concatenate([O, D], axis=1), np.concatenate([O, D], axis=1))
     for kind in ("kd", "grid"):
-        a, b = ref.alt_accel(kind, tris), orc.alt_accel(kind, tris)
-        da, db = a.dump(), b.dump()
-        assert all(np.array_equal(da[k], db[k]) if isinstance(da[k], np.ndarray) else da[k] == db[k] for k in da)
-        ha, hb = a.intersect(O, D), b.intersect(O, D)
-        assert all(np.array_equal(ha[f].view(np.uint32), hb[f].view(np.uint32)) for f in ha.dtype.names), kind
-        a.close(); b.close()
+        b = orc.alt_accel(kind, tris)
+        db, hb = b.dump(), b.intersect(O, D)
+        b.close()
+        da = ha = None
+        if ref:
+            a = ref.alt_accel(kind, tris)
+            da, ha = a.dump(), a.intersect(O, D)
+            a.close()
+            assert sorted(da) == sorted(db)
+        for k in sorted(db):
+            live.check("alt %s %s" % (kind, k), np.asarray(db[k]), None if da is None else np.asarray(da[k]))
+        for f in hb.dtype.names:
+            live.check("alt %s hit %s" % (kind, f), hb[f], None if ha is None else ha[f])

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Prints the few numbers of a bench.py JSON line one usually wants (stdin or file argument)."""
+"""Prints the few numbers of a `bench.py --full` JSON line one usually wants (stdin or file argument)."""
 import json, sys
 src = open(sys.argv[1]) if len(sys.argv) > 1 else sys.stdin
 for l in src:

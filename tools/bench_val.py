@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""stdin: bench.py's JSON line -> value, ms per step, single render (short)"""
+"""stdin: bench.py's JSON line -> value, ms per step, single render (short; the single render is measured by `bench.py --full`)"""
 import json, sys
 for l in sys.stdin:
     if l.startswith("{"):
