@@ -2,8 +2,8 @@
 //   find_nearest_alt_kernel<1>   KDTree::Intersect   (infra/kdtree.cpp:143-207; the accelerator FileScene ships enabled, infra/scene/file_scene.h:10-12)
 //   find_nearest_alt_kernel<2>   Grid::Intersect     (infra/grid.cpp:89-161, 3D-DDA)
 // Both run FileScene::FindNearest's order (file_scene.cpp:170-175): light quad, floor plane, then the accelerator, and report Ray::traversed / Ray::tested as the
-// reference counts them.  Same interface as find_nearest_kernel.  The render path through these structures (crt_set_render_accel) is render_narrow.hip's full-wave
-// mode over alt_common.h's sequential kd_intersect / grid_intersect; the kernels here are the same traversals, step for step, in PERSISTENT-WAVE form (round 3):
+// reference counts them.  Same interface as find_nearest_kernel.  The render path through these structures (crt_set_render_accel) is render_seq.hip's sequential
+// Sample loop over alt_common.h's kd_intersect / grid_intersect; the kernels here are the same traversals, step for step, in PERSISTENT-WAVE form (round 3):
 //   * a ray is not tied to a lane for the launch: a wavefront draws rays from a launch-wide cursor, and a lane whose ray is finished takes the next one as soon as
 //     a quarter of the wavefront is idle, so lanes pay for their own ray's length, not for the longest ray among 64 (before: 10.5 % / 7.8 % of the lanes
 //     busy in an average VALU instruction, profiles/r02b_other_kernels.json);

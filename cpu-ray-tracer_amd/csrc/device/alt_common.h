@@ -1,5 +1,5 @@
 // alt_common.h — device-side traversal of FileScene's alternative acceleration structures, shared by the query kernels (alt_accel.hip), the render kernel that traces
-// Renderer::Sample through them (render_narrow.hip, MODE 2 / 3) and the Whitted kernel (kernels.hip):
+// Renderer::Sample through them (render_seq.hip, KdWorld / GridWorld) and the Whitted kernel (kernels.hip):
 //   kd_intersect     KDTree::Intersect   (infra/kdtree.cpp:143-207; the accelerator FileScene ships enabled, infra/scene/file_scene.h:10-12)
 //   grid_intersect   Grid::Intersect     (infra/grid.cpp:89-161, 3D-DDA)
 // Both report Ray::traversed / Ray::tested as the reference counts them.  Numerics as everywhere: -ffp-contract=off, IEEE + - * / only, std::min / std::max operand

@@ -1,6 +1,6 @@
 // render_prim.hip — PrimitiveScene (second half: infra/scene/primitive_scene.cpp + template/primitives.h Sphere :31, Cube :187, Quad :321, Torus :380)
 // behind the same two seams as the triangle scenes: scene.FindNearest for a ray buffer (find_nearest_prim_kernel) and Renderer::Sample per tile
-// (render_prim_kernel: the sequential form — one wavefront per (tile, 64-frame window), lane = frame, a plain per-lane path loop).
+// (render_seq_kernel<PrimWorld>: seq_sample.h's sequential form — one wavefront per (tile, 64-frame window), lane = frame, a plain per-lane path loop).
 // The scene is the reference's hard-coded demo room: six walls, the swinging light quad, the bouncing mirror ball, the "rounded corners" sphere, the spinning
 // glass cube and the glass torus, in the SPEEDTRIX / single-light configuration its headers select.  No acceleration structure: every ray tests all eleven.
 //
@@ -10,7 +10,7 @@
 // IEEE double + - * / sqrt), so oracle and kernel agree exactly; against a Windows build of the reference the torus' hit distances can differ in the last place.
 //
 // Numerics: -ffp-contract=off; fp32 as everywhere, fp64 only inside the torus test.  No MFMA.
-#include "dev_common.h"
+#include "seq_sample.h"
 
 namespace crt {
 
@@ -263,104 +263,25 @@ __global__ __launch_bounds__(64) void find_nearest_prim_kernel(const PrimDev p, 
     hits[i] = o;
 }
 
-// Renderer::ProcessTile + Sample (renderer.cpp:50-131) over the primitive scene: block = one wavefront = one (tile, 64-frame window), lane = frame
-__global__ __launch_bounds__(64) void render_prim_kernel(const Scene sc, const PrimDev p, float4* __restrict__ slab, Counters* __restrict__ counters,
-                                                          uint32_t tileFirst, uint32_t tileStride, uint32_t tileCount, uint32_t tilesX,
-                                                          uint32_t sppFirst, uint32_t frames, uint32_t passes)
-{
-    __shared__ float fstAll[15 * 64];
-    const uint32_t lane = threadIdx.x;
-    const uint32_t windows = (frames + 63u) / 64u;
-    const uint32_t tl = blockIdx.x / windows, win = blockIdx.x - tl * windows;
-    if (tl >= tileCount) return;
-    sppFirst += win * 64u * passes;
-    frames = (frames - win * 64u < 64u) ? frames - win * 64u : 64u;
-    if (lane >= frames) return;
-    slab += (size_t)win * ((size_t)tileCount * 256u * 64u * passes);
-    const uint32_t tile = tileFirst + tl * tileStride;
-    const uint32_t tx = tile % tilesX, ty = tile / tilesX;
-    float* fst = fstAll + lane;
-    uint32_t nRays = 0, nPrimary = 0;
-    const uint32_t items = 256u * passes;
-    uint32_t seed = init_seed(tx + ty * (uint32_t)sc.W + (sppFirst + lane * passes) * 1799u);   // renderer.cpp:120
-    const f3 camPos = mk3(sc.camPos[0], sc.camPos[1], sc.camPos[2]);
-    const f3 TL = mk3(sc.topLeft[0], sc.topLeft[1], sc.topLeft[2]), TR = mk3(sc.topRight[0], sc.topRight[1], sc.topRight[2]), BL = mk3(sc.bottomLeft[0], sc.bottomLeft[1], sc.bottomLeft[2]);
-    for (uint32_t item = 0; item < items; item++) {
-        const uint32_t pix = (passes == 1u) ? item : item / passes;
-        const int x = (int)(tx * 16u + (pix & 15u)), y = (int)(ty * 16u + (pix >> 4));
-        const float jy = rnd(seed);                                               // pinned: first draw is the y jitter
-        const float jx = rnd(seed);
-        const float u = ((float)x + jx) * sc.invW, vv = ((float)y + jy) * sc.invH;
-        const f3 P = TL + u * (TR - TL) + vv * (BL - TL);
-        const f3 v = P - camPos;
-        f3 O = camPos, D = v * rcp_exact(__builtin_sqrtf(dot3(v, v)));
-        bool inside = false; int depth = 0;
-        nPrimary++;
-        f3 L = mk3(0, 0, 0);
-        for (;;) {
-            const f3 rD = rcp_exact3(D);
-            float t = 1e34f; int obj = -1;
-            nRays++;
-            prim_find_nearest(p, O, D, rD, t, obj);
-            if (obj == -1) { L = mk3(0, 0, 0); break; }                            // PrimitiveScene::GetSkyColor
-            if (depth >= sc.depthLimit) { L = mk3(0, 0, 0); break; }
-            const f3 I = O + t * D;
-            f3 N = prim_normal(p, obj, I);
-            if (dot3(N, D) > 0) N = -N;
-            const f3 c = (obj >= 4 && obj <= 6) ? prim_albedo_override(p, obj, I) : mk3(1.0f, 1.0f, 1.0f);     // material->isAlbedoOverridden ? scene.GetAlbedo : material->albedo
-            if (obj == 0) { L = mk3(24, 24, 22); break; }                          // materials[0].isLight
-            f3 medium = mk3(1, 1, 1);
-            if (inside) {
-                const f3 ab = mk3(p.absorb[3 * obj], p.absorb[3 * obj + 1], p.absorb[3 * obj + 2]) * -t;
-                medium = mk3(crt_expf(ab.x), crt_expf(ab.y), crt_expf(ab.z));
-            }
-            const float refl = p.refl[obj], refr = p.refr[obj];
-            f3 nv, factor; bool newInside = false;
-            const float r = rnd(seed);
-            if (r < refl) {
-                nv = D - 2.0f * N * dot3(N, D);
-                factor = c * medium;
-            } else if (r < refl + refr) {
-                nv = D - 2.0f * N * dot3(N, D);
-                const float n1 = inside ? 1.2f : 1, n2 = inside ? 1 : 1.2f;
-                const float eta = n1 / n2, cosi = dot3(-D, N);
-                const float cost2 = 1.0f - eta * eta * (1 - cosi * cosi);
-                if (cost2 > 0) {
-                    const float a = n1 - n2, b2 = n1 + n2, R0 = (a * a) / (b2 * b2), cc = 1 - cosi;
-                    const float Fr = R0 + (1 - R0) * (cc * cc * cc * cc * cc);
-                    const f3 T = eta * D + ((eta * cosi - __builtin_sqrtf(__builtin_fabsf(cost2))) * N);
-                    if (rnd(seed) > Fr) { nv = T; newInside = !inside; }
-                }
-                factor = c * medium;
-            } else {
-                f3 Rr;
-                do {
-                    const float rz = rnd_pm1(seed);                                // draw order pinned z, y, x
-                    const float ry = rnd_pm1(seed);
-                    const float rx = rnd_pm1(seed);
-                    Rr = mk3(rx, ry, rz);
-                } while (dot3(Rr, Rr) > 1);
-                if (dot3(Rr, N) < 0) Rr = Rr * -1.0f;
-                nv = Rr * rcp_exact(__builtin_sqrtf(dot3(Rr, Rr)));
-                const f3 brdf = c * CRT_INVPI;
-                const f3 pre = medium * brdf * 2.0f * CRT_PI;
-                factor = pre * dot3(nv, N);
-            }
-            float* fd = fst + (uint32_t)(3 * depth) * 64u;
-            fd[0] = factor.x; fd[64] = factor.y; fd[128] = factor.z;
-            depth++;
-            O = I + nv * CRT_EPS; D = nv; inside = newInside;
-        }
-#pragma unroll
-        for (int k = 4; k >= 0; k--)
-            if (depth > k) { const float* fd = fst + (uint32_t)(3 * k) * 64u; L = mk3(fd[0], fd[64], fd[128]) * L; }
-        uint32_t pass = 0;
-        if (passes != 1u) pass = item - pix * passes;
-        slab[((size_t)tl * 256u + pix) * (64u * passes) + (lane * passes + pass)] = make_float4(L.x, L.y, L.z, 0.0f);
+// the PrimitiveScene as a world of render_seq_kernel (seq_sample.h): Renderer::ProcessTile + Sample (renderer.cpp:50-131) over the eleven primitives
+struct PrimWorld {
+    PrimDev p;
+    static constexpr bool kMeshHits = false;
+    __device__ __host__ uint32_t stack_words(const Scene&) const { return 0u; }
+    __device__ __forceinline__ uint32_t trace(const Scene&, f3 O, f3 D, f3 rD, Hit& h, uint32_t*) const { prim_find_nearest(p, O, D, rD, h.t, h.objIdx); return 0u; }
+    __device__ __forceinline__ f3 miss(const Scene&, f3) const { return mk3(0, 0, 0); }                      // PrimitiveScene::GetSkyColor
+    __device__ __forceinline__ Surf surface(const Scene&, const Hit& h, f3 I, f3 D) const
+    {
+        const int obj = h.objIdx;
+        Surf s;
+        s.N = prim_normal(p, obj, I);
+        if (dot3(s.N, D) > 0) s.N = -s.N;
+        s.c = (obj >= 4 && obj <= 6) ? prim_albedo_override(p, obj, I) : mk3(1.0f, 1.0f, 1.0f);     // material->isAlbedoOverridden ? scene.GetAlbedo : material->albedo
+        s.refl = p.refl[obj]; s.refr = p.refr[obj];
+        s.absorb = mk3(p.absorb[3 * obj], p.absorb[3 * obj + 1], p.absorb[3 * obj + 2]);
+        return s;
     }
-    atomicAdd(&counters->v[0], (unsigned long long)nRays);
-    atomicAdd(&counters->v[1], (unsigned long long)nPrimary);
-}
+};
 
 } // namespace crt
 
@@ -376,6 +297,5 @@ extern "C" hipError_t crt_launch_render_prim(const crt::Scene* sc, const crt::Pr
     if (tileCount == 0 || frames == 0) return hipSuccess;
     const uint32_t windows = (frames + 63u) / 64u;
     if ((unsigned long long)tileCount * windows > 0x7fffffffull) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(crt::render_prim_kernel, dim3(tileCount * windows), dim3(64), 0, stream, *sc, *p, (float4*)slab, counters, tileFirst, tileStride, tileCount, tilesX, sppFirst, frames, passes);
-    return hipGetLastError();
+    return crt::launch_render_seq(sc, crt::PrimWorld{*p}, slab, counters, tileFirst, tileStride, tileCount, tilesX, sppFirst, frames, passes, stream);
 }

@@ -1,0 +1,160 @@
+// seq_sample.h — render_seq_kernel: Renderer::ProcessTile + Sample ("3. PathTracer/renderer.cpp":117-131, Sample :50-100) as a plain per-lane path loop — the
+// SEQUENTIAL form: one wavefront per (tile, 64-frame window), lane = frame, no phases, no queues.  It serves everything that is not issue-bound:
+//   * the latency mode's cost probe (PROBE: render_seq.hip, abi.cpp probe_tile_costs);
+//   * Sample through FileScene's KD-tree / uniform grid (crt_set_render_accel; render_seq.hip);
+//   * Sample over the PrimitiveScene (render_prim.hip).
+// What differs between them is the "world" the loop runs in, a small policy class:
+//   uint32_t trace(sc, O, D, rD, h, stk)   scene.FindNearest into `h`; returns the traversal steps the probe counts (interior + triangle + TLAS steps; 0 where never probed)
+//   Surf surface(sc, h, I, D)              normal (already facing the ray), albedo, reflectivity, refractivity and absorption at the hit
+//   f3 miss(sc, D)                         scene.GetSkyColor
+//   kMeshHits                              hits of objects >= 2 are counted into Counters::v[7]
+//   stack_words(sc)                        dwords per lane of the LDS traversal stack `stk` (column layout: entry i at stk[i * 64])
+// Per stream everything is the reference's: the rnd draws in its order and every float expression as written there (-ffp-contract=off, dev_common.h), so the
+// samples are bit-identical to render_pool_kernel's, render_tiles_kernel's and the CPU oracle's.
+#pragma once
+#include "dev_common.h"
+
+namespace crt {
+
+struct Surf { f3 N, c; float refl, refr; f3 absorb; };
+
+constexpr uint32_t kSeqWaves = 4u;                         // wavefronts per workgroup, each an entry of its own
+constexpr uint32_t kProbeWaves = 8u;                       // cost probe: wavefronts (of 64 one-path lanes) per tile
+
+__device__ __host__ __forceinline__ uint32_t seq_lds_bytes(uint32_t stackWords) { return kSeqWaves * (stackWords + 15u) * 64u * 4u; }   // traversal stack + 15 throughput factors per lane
+
+// entry = tile rank * windows + window.  PROBE = true is the cost probe of the latency mode: kProbeWaves entries per tile, lane l of entry q traces ONE path through
+// pixel (4 l + q) % 256 of the tile with a seed of its own (256 paths per tile per four entries), nothing is stored, and every wavefront adds the number of traversal /
+// shading steps its 64 paths took to tileCost[tile] (zeroed by the host) — an estimate of what the tile's streams will cost (a stream = 256 such paths), available well
+// under a millisecond after a camera or scene change instead of after a first full render.
+template <class World, bool PROBE>
+__global__ __launch_bounds__(256, 4) void render_seq_kernel(const Scene sc, const World world, float4* __restrict__ slab, Counters* __restrict__ counters,
+                                                           uint32_t tileFirst, uint32_t tileStride, uint32_t tileCount, uint32_t tilesX,
+                                                           uint32_t sppFirst, uint32_t frames, uint32_t passes, uint32_t nEntries, uint32_t* __restrict__ tileCost)
+{
+    extern __shared__ uint32_t ldsAll[];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint32_t entry = blockIdx.x * kSeqWaves + wave;
+    if (entry >= nEntries) return;
+    const uint32_t windows = (frames + 63u) / 64u;
+    const uint32_t tl = PROBE ? entry / kProbeWaves : entry / windows, win = PROBE ? 0u : entry % windows;
+    if (tl >= tileCount) return;
+    sppFirst += win * 64u * passes;
+    frames = (frames - win * 64u < 64u) ? frames - win * 64u : 64u;               // frames of THIS window (the last one may be partial)
+    if (lane >= frames) return;
+    slab += (size_t)win * ((size_t)tileCount * 256u * 64u * passes);              // this window's region of the sample slab
+    const uint32_t tile = tileFirst + tl * tileStride;
+    const uint32_t tx = tile % tilesX, ty = tile / tilesX;
+    // this lane's LDS columns: the traversal stack, then the throughput factors
+    const uint32_t stackWords = world.stack_words(sc);
+    uint32_t* stk = ldsAll + wave * (stackWords + 15u) * 64u + lane;
+    float* fst = reinterpret_cast<float*>(stk + stackWords * 64u);
+
+    uint32_t nRays = 0, nPrimary = 0, nMesh = 0;
+    const uint32_t items = PROBE ? 1u : 256u * passes;                            // (pixel, pass) pairs in stream order
+    uint32_t seed = init_seed(tx + ty * (uint32_t)sc.W + (sppFirst + lane * passes) * 1799u);   // renderer.cpp:120
+    if (PROBE) seed = init_seed(0x9e3779b9u ^ ((tile * kProbeWaves + entry % kProbeWaves) * 64u + lane));
+    uint32_t steps = 0;                                                           // probe: traversal + weighted shading steps of this lane's path
+
+    const kernarg_f cam = scene_floats(offsetof(Scene, camPos));                  // camPos, topLeft, topRight, bottomLeft, invW, invH
+    const f3 camPos = mk3(cam[0], cam[1], cam[2]);
+    const f3 TL = mk3(cam[3], cam[4], cam[5]), TR = mk3(cam[6], cam[7], cam[8]), BL = mk3(cam[9], cam[10], cam[11]);
+    const float invW = cam[12], invH = cam[13];
+
+    for (uint32_t item = 0; item < items; item++) {
+        // ---------------- ProcessTile + Camera::GetPrimaryRay (renderer.cpp:125-126, camera.h:23-30) ----------------
+        const uint32_t pix = PROBE ? ((lane * 4u + entry % kProbeWaves) & 255u) : ((passes == 1u) ? item : item / passes);
+        const int x = (int)(tx * 16u + (pix & 15u)), y = (int)(ty * 16u + (pix >> 4));
+        const float jy = rnd(seed);                                               // pinned: first draw is the y jitter
+        const float jx = rnd(seed);
+        const float u = ((float)x + jx) * invW, vv = ((float)y + jy) * invH;
+        const f3 P = TL + u * (TR - TL) + vv * (BL - TL);
+        f3 v = P - camPos;
+        f3 O = camPos, D = v * rcp_exact(__builtin_sqrtf(dot3(v, v)));            // normalize()
+        bool inside = false; int depth = 0;
+        nPrimary++;
+        f3 L = mk3(0, 0, 0);
+        for (;;) {
+            const f3 rD = rcp_exact3(D);
+            Hit h; h.t = 1e34f; h.u = 0; h.v = 0; h.objIdx = -1; h.triIdx = -1;
+            nRays++;
+            const uint32_t traceSteps = world.trace(sc, O, D, rD, h, stk);
+            if (PROBE) steps += traceSteps + 3u;                                  // a shading step weighs about three traversal steps
+            if (World::kMeshHits && h.objIdx >= 2) nMesh++;
+            // ---------------- Renderer::Sample (renderer.cpp:50-100) ----------------
+            if (h.objIdx == -1) { L = world.miss(sc, D); break; }
+            if (depth >= sc.depthLimit) { L = mk3(0, 0, 0); break; }
+            if (h.objIdx == 0) { L = mk3(24, 24, 22); break; }                     // the light
+            const f3 I = O + h.t * D;
+            const Surf s = world.surface(sc, h, I, D);
+            const f3 N = s.N, c = s.c;
+            f3 medium = mk3(1, 1, 1);
+            if (inside) {
+                const f3 ab = s.absorb * -h.t;
+                medium = mk3(crt_expf(ab.x), crt_expf(ab.y), crt_expf(ab.z));
+            }
+            f3 nv, factor; bool newInside = false;
+            const float r = rnd(seed);
+            if (r < s.refl) {                                                      // HandleMirror, renderer.cpp:20-25
+                nv = D - 2.0f * N * dot3(N, D);
+                factor = c * medium;
+            } else if (r < s.refl + s.refr) {                                      // HandleDielectric, renderer.cpp:27-45
+                nv = D - 2.0f * N * dot3(N, D);
+                const float n1 = inside ? 1.2f : 1, n2 = inside ? 1 : 1.2f;
+                const float eta = n1 / n2, cosi = dot3(-D, N);
+                const float cost2 = 1.0f - eta * eta * (1 - cosi * cosi);
+                if (cost2 > 0) {
+                    const float a = n1 - n2, b2 = n1 + n2, R0 = (a * a) / (b2 * b2), cc = 1 - cosi;
+                    const float Fr = R0 + (1 - R0) * (cc * cc * cc * cc * cc);
+                    const f3 T = eta * D + ((eta * cosi - __builtin_sqrtf(__builtin_fabsf(cost2))) * N);
+                    if (rnd(seed) > Fr) { nv = T; newInside = !inside; }
+                }
+                factor = c * medium;
+            } else {                                                               // diffuse, renderer.cpp:93-99; diffusereflection tmplmath.h:535-544
+                f3 Rr;
+                do {
+                    const float rz = rnd_pm1(seed);                                // draw order pinned z, y, x
+                    const float ry = rnd_pm1(seed);
+                    const float rx = rnd_pm1(seed);
+                    Rr = mk3(rx, ry, rz);
+                } while (dot3(Rr, Rr) > 1);
+                if (dot3(Rr, N) < 0) Rr = Rr * -1.0f;
+                nv = Rr * rcp_exact(__builtin_sqrtf(dot3(Rr, Rr)));                // normalize(R)
+                const f3 brdf = c * CRT_INVPI;
+                const f3 pre = medium * brdf * 2.0f * CRT_PI;
+                factor = pre * dot3(nv, N);
+            }
+            // the bounce's throughput factor (albedo*medium*... multiplies on return: depth <= 4 here)
+            float* fd = fst + (uint32_t)(3 * depth) * 64u;
+            fd[0] = factor.x; fd[64] = factor.y; fd[128] = factor.z;
+            depth++;
+            O = I + nv * CRT_EPS; D = nv; inside = newInside;
+        }
+        // unwind the recursion (innermost factor first), store the sample
+#pragma unroll
+        for (int k = 4; k >= 0; k--)
+            if (depth > k) { const float* fd = fst + (uint32_t)(3 * k) * 64u; L = mk3(fd[0], fd[64], fd[128]) * L; }
+        if (!PROBE) {
+            uint32_t pass = 0;
+            if (passes != 1u) pass = item - pix * passes;
+            slab[((size_t)tl * 256u + pix) * (64u * passes) + (lane * passes + pass)] = make_float4(L.x, L.y, L.z, 0.0f);
+        } else if (L.x != L.x) steps++;                                            // (keeps the probe's shading arithmetic alive)
+    }
+    if (PROBE) { const uint32_t sum = wave_sum(steps); if (lane == 0) atomicAdd(&tileCost[tl], sum); return; }
+    atomicAdd(&counters->v[0], (unsigned long long)nRays);
+    atomicAdd(&counters->v[1], (unsigned long long)nPrimary);
+    if (nMesh) atomicAdd(&counters->v[7], (unsigned long long)nMesh);
+}
+
+// what a launch over every (owned tile, 64-frame window) needs (render_seq.hip / render_prim.hip: the callers check their own limits first)
+template <class World>
+hipError_t launch_render_seq(const Scene* sc, const World& world, void* slab, Counters* counters, uint32_t tileFirst, uint32_t tileStride, uint32_t tileCount, uint32_t tilesX,
+                             uint32_t sppFirst, uint32_t frames, uint32_t passes, hipStream_t stream)
+{
+    const uint32_t entries = tileCount * ((frames + 63u) / 64u);
+    hipLaunchKernelGGL((render_seq_kernel<World, false>), dim3((entries + kSeqWaves - 1u) / kSeqWaves), dim3(64u * kSeqWaves), seq_lds_bytes(world.stack_words(*sc)), stream,
+                       *sc, world, (float4*)slab, counters, tileFirst, tileStride, tileCount, tilesX, sppFirst, frames, passes, entries, (uint32_t*)nullptr);
+    return hipGetLastError();
+}
+
+} // namespace crt

@@ -18,10 +18,9 @@ policies = sys.argv[5].split(";") if len(sys.argv) > 5 else ["off", "default", "
 sc = crt.HostScene(os.path.join(A, "scenes", xml), kind, A)
 ref = None; watch = None
 for pol in policies:
-    for k in ("CRT_LAT_OFF", "CRT_LAT_POLICY", "CRT_LAT_AIM", "CRT_LAT_FORCE", "CRT_LAT_RECORD"): os.environ.pop(k, None)
+    for k in ("CRT_LAT_OFF", "CRT_LAT_POLICY", "CRT_LAT_FORCE", "CRT_LAT_RECORD"): os.environ.pop(k, None)
     os.environ["CRT_LAT_RECORD"] = "1"
     if pol == "off": os.environ["CRT_LAT_POLICY"] = "2:64"; os.environ["CRT_LAT_FORCE"] = "1"      # a table of one wave per tile
-    elif pol.startswith("aim="): os.environ["CRT_LAT_AIM"] = pol[4:]
     elif pol != "default": os.environ["CRT_LAT_POLICY"] = pol; os.environ["CRT_LAT_FORCE"] = "1"
     stride = int(os.environ.get("PROBE_TILE_STRIDE", "1")); tiles = (W // 16) * (H // 16)      # (stride > 1: how does the mode behave with a lighter load)
     ctx = crt.Context(W, H, tile_stride=stride, tile_count=(tiles + stride - 1) // stride if stride > 1 else -1); sc.upload(ctx)

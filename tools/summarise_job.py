@@ -32,7 +32,7 @@ for d in sorted(glob.glob(src + "/pmc_*")):
         for r in csv.DictReader(open(f)):
             k = r["Kernel_Name"].split("(")[0].strip()
             per.setdefault((int(r["Dispatch_Id"]), k), collections.defaultdict(float))[r["Counter_Name"]] += float(r["Counter_Value"])
-        render = [(did, k) for (did, k) in sorted(per) if ("render_pool_kernel" in k or "render_tiles_kernel" in k or "render_narrow_kernel" in k) and "true" not in k.split("<")[-1].split(",")[1:2][0]]
+        render = [(did, k) for (did, k) in sorted(per) if ("render_pool_kernel" in k or "render_tiles_kernel" in k or "render_seq_kernel" in k) and "true" not in k.split("<")[-1].split(",")[1:2][0]]
         for (did, k) in render[warm_kernels:]:
             for c, v in per[(did, k)].items(): job[k][c] += v
         for (did, k) in per:
