@@ -78,7 +78,7 @@ HIT_DTYPE = np.dtype([("t", "<f4"), ("u", "<f4"), ("v", "<f4"), ("objIdx", "<i4"
 
 # every symbol include/crt_abi.h and include/crt_host.h declare (tests check the library exports all of them)
 ABI_SYMBOLS = ["crt_upload_primitive_scene", "crt_set_render_accel", "crt_upload_alt_accel", "crt_find_nearest_alt", "crt_update_scene", "crt_abi_version", "crt_device_count", "crt_create", "crt_destroy", "crt_last_error", "crt_upload_scene", "crt_set_camera",
-               "crt_render", "crt_reserve", "crt_whitted_tick", "crt_sync", "crt_clear", "crt_read_accumulator", "crt_resolve_screen", "crt_find_nearest", "crt_get_counters",
+               "crt_render", "crt_tick", "crt_reserve", "crt_whitted_tick", "crt_sync", "crt_clear", "crt_read_accumulator", "crt_resolve_screen", "crt_find_nearest", "crt_get_counters",
                "crt_reset_counters", "crt_get_timing", "crt_get_tile_clocks", "crt_bind_accumulator", "crt_accumulator_device_ptr"]
 HOST_SYMBOLS = ["crt_host_primitive_scene_create", "crt_host_primitive_scene_free", "crt_host_primitive_scene_set_time", "crt_host_primitive_scene_desc", "crt_host_primitive_scene_upload", "crt_host_scene_build_alt", "crt_host_scene_upload_alt", "crt_host_scene_alt_info", "crt_host_scene_alt_copy", "crt_host_scene_set_transform", "crt_host_scene_update", "crt_host_math_probe", "crt_host_vertex_dedup", "crt_host_last_error", "crt_host_scene_load", "crt_host_scene_free", "crt_host_scene_upload", "crt_host_scene_kind",
                 "crt_host_scene_triangle_count", "crt_host_scene_bvh_count", "crt_host_scene_bvh_info", "crt_host_scene_bvh_copy",
@@ -192,6 +192,15 @@ class Context:
 
     def render(self, spp_first, frames, passes=1):
         self._ck(self.L.crt_render(self.h, C.c_uint32(spp_first), C.c_uint32(frames), C.c_uint32(passes)))
+
+    def tick(self, spp, passes=1, pixels=True, accumulator=True):
+        """crt_tick: one Renderer::Tick at `spp` (crt_render(spp, 1, passes) + read-back + resolve; frames after a run of still Ticks are rendered ahead).
+        Returns (pixels (H, W) uint32 or None, accumulator (H, W, 4) float32 or None, energy)."""
+        px = np.empty((self.H, self.W), np.uint32) if pixels else None
+        acc = np.empty((self.H, self.W, 4), np.float32) if accumulator else None
+        e = C.c_float()
+        self._ck(self.L.crt_tick(self.h, C.c_uint32(spp), C.c_uint32(passes), _p(px) if px is not None else None, _p(acc) if acc is not None else None, C.byref(e)))
+        return px, acc, e.value
 
     def reserve(self, frames, passes=1):
         self._ck(self.L.crt_reserve(self.h, C.c_uint32(frames), C.c_uint32(passes)))

@@ -31,6 +31,7 @@ namespace crt { struct AltAccelDev; }
 extern "C" hipError_t crt_launch_whitted(const crt::Scene*, int, const crt::AltAccelDev*, void*, uint32_t*, crt::Counters*, uint32_t, hipStream_t);
 extern "C" hipError_t crt_launch_render_alt(int, const crt::Scene*, const crt::AltAccelDev*, void*, crt::Counters*, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, hipStream_t);
 extern "C" hipError_t crt_launch_resolve(const void*, uint32_t*, float*, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, float, hipStream_t);
+extern "C" hipError_t crt_launch_commit_frame(const void*, uint32_t, uint32_t, void*, uint32_t*, float*, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, float, hipStream_t);
 
 static_assert(sizeof(crt_bvh_node) == 32 && sizeof(crt_tri) == 112 && sizeof(crt_tlas_node) == 32, "reference layouts");
 static_assert(sizeof(crt::NodePair) == 64 && sizeof(crt::LeafTri) == 48 && sizeof(crt::ShadeTri) == 64 && sizeof(crt::TlasNode) == 32 &&
@@ -83,12 +84,21 @@ struct crt_ctx {
     // the GPU; the ordered accumulate kernels run on the main stream behind events.  Their sample slabs are regions of ONE pool
     // handed out as a ring: launch order = accumulate order = release order, so the oldest region is always the next to free.
     std::vector<hipStream_t> streams; uint64_t launchSeq = 0;
-    struct Region { size_t off, bytes; hipEvent_t freed; };      // freed: recorded on the main stream behind the region's accumulate
+    // freed: recorded on the main stream behind the region's accumulate.  held: the region of a crt_tick render-ahead launch whose frames are not all committed
+    // or discarded yet — its `freed` is not recorded, so take_region must never wait on it
+    struct Region { size_t off, bytes; hipEvent_t freed; bool held = false; };
     std::deque<Region> inflight;
     char* pool = nullptr; size_t poolBytes = 0, poolHead = 0; bool poolCapped = false;   // capped: already as large as the HBM budget allows
     hipEvent_t mustWait = nullptr;                                // `freed` of the newest region whose space was handed out again
     std::vector<hipEvent_t> freeEvents;
-    std::vector<hipEvent_t> doneEvents;
+    std::vector<hipEvent_t> doneEvents;                           // recycled end events of render-ahead launches
+    // crt_tick's render-ahead queue (see crt_tick): launches of the frames after the last Tick, valid for one state epoch and the next (spp, passes)
+    struct Ahead { hipEvent_t end; size_t off; const char* slab; uint64_t epoch; uint32_t sppFirst, nf, passes, used; };   // used: frames committed so far
+    std::deque<Ahead> ahead;
+    uint64_t epoch = 1;                   // bumped by every change the samples depend on: camera, scene upload / update, render accelerator
+    uint64_t tickEpoch = 0; uint32_t tickNextSpp = 0, tickPasses = 0;   // the previous crt_tick: its epoch (0: none), spp + passes, passes
+    uint32_t aheadFrames = 0;             // frames of the newest render-ahead launch (doubles while Ticks hit)
+    hipStream_t aheadStream = nullptr;    // low-priority stream of the render-ahead launches
     crt::Scene hScene{};
     crt::Counters* dCounters = nullptr;
     uint32_t* dQueryCursor = nullptr;      // the ray cursor of the persistent query kernels (zeroed by each launch)
@@ -302,8 +312,11 @@ void crt_destroy(crt_ctx* c)
     if (!c) return;
     (void)hipSetDevice(c->cfg.device);
     for (auto st : c->streams) (void)hipStreamSynchronize(st);
+    if (c->aheadStream) (void)hipStreamSynchronize(c->aheadStream);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     c->freeScene();
+    for (auto& a : c->ahead) (void)hipEventDestroy(a.end);
+    if (c->aheadStream) (void)hipStreamDestroy(c->aheadStream);
     for (auto& ev : c->evPool) { (void)hipEventDestroy(ev.a); (void)hipEventDestroy(ev.b); }
     for (auto& ev : c->evRender) { (void)hipEventDestroy(ev.a); (void)hipEventDestroy(ev.b); }
     for (auto& ev : c->evAcc) { (void)hipEventDestroy(ev.a); (void)hipEventDestroy(ev.b); }
@@ -344,6 +357,7 @@ void crt_destroy(crt_ctx* c)
 int crt_upload_scene(crt_ctx* c, const crt_scene_desc* sd)
 {
     if (!c || !sd) return CRT_ERR_INVALID;
+    c->epoch++;                                                       // frames rendered ahead by crt_tick are of the old scene
     HIPCK(c, hipSetDevice(c->cfg.device));
     if (sd->kind != CRT_SCENE_FILE && sd->kind != CRT_SCENE_TLAS) return c->fail(CRT_ERR_INVALID, "unknown scene kind %d", sd->kind);
     if (!sd->bvhs || sd->bvhCount == 0) return c->fail(CRT_ERR_INVALID, "scene has no acceleration structure");
@@ -523,6 +537,7 @@ int crt_upload_scene(crt_ctx* c, const crt_scene_desc* sd)
 
     // launches still in flight read the previous scene's buffers (render streams first: the main stream's accumulates wait on them)
     for (auto st : c->streams) HIPCK(c, hipStreamSynchronize(st));
+    if (c->aheadStream) HIPCK(c, hipStreamSynchronize(c->aheadStream));
     HIPCK(c, hipStreamSynchronize(c->stream));
     c->freeScene();
     uint32_t* dTexels = nullptr;
@@ -602,6 +617,15 @@ int crt_upload_scene(crt_ctx* c, const crt_scene_desc* sd)
     }
     c->haveScene = true;
     return CRT_OK;
+}
+
+// Writes on the main stream of data the render kernels read (tile order, block tables, job plans, in-place scene updates) assume the main stream is ordered
+// behind every render launch submitted so far — true for crt_render's launches (each one's accumulate waits for it there), not for crt_tick's render-ahead
+// launches, which nothing on the main stream waits for until their frames are committed: the main stream waits for them here first.
+static int order_behind_ahead(crt_ctx* c)
+{
+    for (const auto& a : c->ahead) HIPCK(c, hipStreamWaitEvent(c->stream, a.end, 0));
+    return 0;
 }
 
 // fills the TLAS sections of a host geometry image from the reference's TLASBVHNode array: per-node records with both reference forms, and the child
@@ -691,6 +715,7 @@ int crt_update_scene(crt_ctx* c, const crt_scene_desc* sd, uint32_t what)
             return c->fail(CRT_ERR_UNSUPPORTED, "TLAS height %u needs %u bytes of LDS traversal stack per wave (> 64 KiB)", tlasHeight, (c->hScene.bvhStack + tlasHeight + 1) * 256u);
     }
     // ---- apply ----
+    c->epoch++;
     size_t lo = SIZE_MAX, hi = 0;                                         // byte range of the geometry buffer to rewrite
     auto touch = [&](size_t a, size_t b) { if (a < lo) lo = a; if (b > hi) hi = b; };
     if (what & CRT_UPDATE_BOUNDS) {
@@ -735,6 +760,7 @@ int crt_update_scene(crt_ctx* c, const crt_scene_desc* sd, uint32_t what)
         if (!c->stageCopied[k]) HIPCK(c, hipEventCreateWithFlags(&c->stageCopied[k], hipEventDisableTiming));
     } else HIPCK(c, hipEventSynchronize(c->stageCopied[k]));
     memcpy(c->hStage[k], f.geom.data() + lo, bytes);
+    { const int r = order_behind_ahead(c); if (r) return r; }
     HIPCK(c, hipMemcpyAsync(const_cast<char*>(c->hScene.geom) + lo, c->hStage[k], bytes, hipMemcpyHostToDevice, c->stream));
     HIPCK(c, hipEventRecord(c->stageCopied[k], c->stream));
     c->sceneReady = c->stageCopied[k];
@@ -751,7 +777,7 @@ int crt_set_camera(crt_ctx* c, const float camPos[3], const float tl[3], const f
     crt::Scene& s = c->hScene;
     if (!memcmp(s.camPos, camPos, 12) && !memcmp(s.topLeft, tl, 12) && !memcmp(s.topRight, tr, 12) && !memcmp(s.bottomLeft, bl, 12)) return CRT_OK;   // unchanged (a per-frame PushCamera)
     memcpy(s.camPos, camPos, 12); memcpy(s.topLeft, tl, 12); memcpy(s.topRight, tr, 12); memcpy(s.bottomLeft, bl, 12);
-    c->orderDirty = true;
+    c->orderDirty = true; c->epoch++;
     return CRT_OK;      // the Scene block travels by value in every launch's kernel arguments
 }
 
@@ -761,6 +787,7 @@ int crt_set_camera(crt_ctx* c, const float camPos[3], const float tl[3], const f
 static int upload_tile_order(crt_ctx* c, const std::vector<uint32_t>& order)
 {
     if (!c->dTileOrder) HIPCK(c, hipMalloc((void**)&c->dTileOrder, (size_t)c->tileCount * 4));
+    { const int r = order_behind_ahead(c); if (r) return r; }
     const int k = c->orderFlip ^= 1;
     if (!c->hTileOrder[k]) {
         HIPCK(c, hipHostMalloc((void**)&c->hTileOrder[k], (size_t)c->tileCount * 4, hipHostMallocDefault));
@@ -917,6 +944,7 @@ static int upload_block_table(crt_ctx* c, const std::vector<uint8_t>& lanes, con
     } else if (c->descReady) HIPCK(c, hipEventSynchronize(c->descReady));     // the staging buffer's previous copy (long done)
     if (!c->descReady) HIPCK(c, hipEventCreateWithFlags(&c->descReady, hipEventDisableTiming));
     memcpy(c->hBlockDesc, table.data(), table.size() * 4);
+    { const int r = order_behind_ahead(c); if (r) return r; }
     // on the main stream: ordered behind every launch submitted so far (each launch's accumulate waits for it there), so the previous table is no longer read
     HIPCK(c, hipMemcpyAsync(c->dBlockDesc, c->hBlockDesc, table.size() * 4, hipMemcpyHostToDevice, c->stream));
     HIPCK(c, hipEventRecord(c->descReady, c->stream));
@@ -1030,6 +1058,28 @@ static int take_event(crt_ctx* c, std::deque<EventPair>& list, EventPair* out)
 // grows to the high-water mark only (hipMalloc synchronises the device and takes seconds for tens of GB): room for the largest
 // launch — for two of them when a call needs several launches — and for at least eight windows (consecutive single-window calls
 // overlap on the streams), never more than half of the free HBM.
+// The region of render-ahead launch `a` is free once the main stream has passed `a`'s end (a committed launch: behind its last commit)
+static int release_ahead_region(crt_ctx* c, const crt_ctx::Ahead& a)
+{
+    for (auto& r : c->inflight)
+        if (r.held && r.off == a.off) { HIPCK(c, hipEventRecord(r.freed, c->stream)); r.held = false; return 0; }
+    return c->fail(CRT_ERR_DEVICE, "render-ahead region at %zu is not in the slab ring", a.off);
+}
+
+// Drops crt_tick's render-ahead queue.  Kernels of a discarded launch keep running, so the main stream waits for each launch's end before the region's
+// `freed` is recorded there (releases stay ordered on the main stream, which take_region's mustWait relies on).
+static int discard_ahead(crt_ctx* c)
+{
+    while (!c->ahead.empty()) {
+        const crt_ctx::Ahead a = c->ahead.front(); c->ahead.pop_front();
+        HIPCK(c, hipStreamWaitEvent(c->stream, a.end, 0));
+        c->doneEvents.push_back(a.end);
+        const int r = release_ahead_region(c, a); if (r) return r;
+    }
+    c->aheadFrames = 0;
+    return 0;
+}
+
 static int ensure_pool(crt_ctx* c, uint32_t frames, uint32_t passes, uint32_t* maxFOut)
 {
     const size_t windowBytes = window_bytes(c, passes);
@@ -1040,8 +1090,10 @@ static int ensure_pool(crt_ctx* c, uint32_t frames, uint32_t passes, uint32_t* m
     size_t want = (size_t)callW * windowBytes * (wantW > callW ? 2u : 1u);
     if (want < 8 * windowBytes) want = 8 * windowBytes;
     if (want > c->poolBytes && !(c->poolCapped && windowBytes <= c->poolBytes)) {
+        { const int r = discard_ahead(c); if (r) return r; }
         HIPCK(c, hipStreamSynchronize(c->stream));
         for (auto st : c->streams) HIPCK(c, hipStreamSynchronize(st));
+        if (c->aheadStream) HIPCK(c, hipStreamSynchronize(c->aheadStream));
         for (auto& r : c->inflight) c->freeEvents.push_back(r.freed);
         c->inflight.clear(); c->poolHead = 0;
         if (c->pool) { HIPCK(c, hipFree(c->pool)); c->pool = nullptr; c->poolBytes = 0; }
@@ -1070,12 +1122,14 @@ int crt_reserve(crt_ctx* c, uint32_t frames, uint32_t passes)
     if (!c) return CRT_ERR_INVALID;
     if (passes < 1 || passes > 4) return c->fail(CRT_ERR_INVALID, "passes must be 1..4");
     HIPCK(c, hipSetDevice(c->cfg.device));
+    { const int r = discard_ahead(c); if (r) return r; }
     if (c->tileCount == 0 || frames == 0) return CRT_OK;
     uint32_t maxF = 0;
     return ensure_pool(c, frames, passes, &maxF);
 }
 
-// a region of `need` bytes of the slab pool for a launch on stream `st`; regions still in use are waited for on the GPU (never on the host)
+// a region of `need` bytes of the slab pool for a launch on stream `st`; regions still in use are waited for on the GPU (never on the host).
+// Returns 1 (nothing taken) when the space would have to come from a held render-ahead region.
 static int take_region(crt_ctx* c, size_t need, hipStream_t st, size_t* offOut)
 {
     for (;;) {
@@ -1095,6 +1149,7 @@ static int take_region(crt_ctx* c, size_t need, hipStream_t st, size_t* offOut)
             return 0;
         }
         if (c->inflight.empty()) return c->fail(CRT_ERR_DEVICE, "slab pool of %zu bytes cannot hold a launch of %zu bytes", c->poolBytes, need);
+        if (c->inflight.front().held) return 1;
         if (c->mustWait) c->freeEvents.push_back(c->mustWait);
         c->mustWait = c->inflight.front().freed;
         c->inflight.pop_front();
@@ -1214,6 +1269,7 @@ static int install_job_plan(crt_ctx* c, uint32_t windows, uint32_t frames, bool 
     } else if (c->jobDescReady) HIPCK(c, hipEventSynchronize(c->jobDescReady));
     if (!c->jobDescReady) HIPCK(c, hipEventCreateWithFlags(&c->jobDescReady, hipEventDisableTiming));
     memcpy(c->hJobDesc, table.data(), table.size() * 4);
+    { const int r = order_behind_ahead(c); if (r) return r; }
     HIPCK(c, hipMemcpyAsync(c->dJobDesc, c->hJobDesc, table.size() * 4, hipMemcpyHostToDevice, c->stream));      // main stream: behind every launch submitted so far
     HIPCK(c, hipEventRecord(c->jobDescReady, c->stream));
     return 0;
@@ -1388,12 +1444,82 @@ static int probe_tile_costs(crt_ctx* c, hipStream_t st)
     return r;
 }
 
+// One render launch of frames [sppFirst, sppFirst + nf * passes) on stream `st`: a slab region, tuner_prepare, planner_prepare, launch_render_kernels.
+// ahead == nullptr: a launch of crt_render — the ordered accumulate follows on the main stream and the region is released behind it.  Otherwise a
+// render-ahead launch of crt_tick: no accumulate; the region stays held and *ahead describes the launch (its end event recorded on `st`).
+// Returns 1 (nothing launched) when a render-ahead launch finds no room in the ring short of a held region.
+static int launch_frames(crt_ctx* c, uint32_t sppFirst, uint32_t nf, uint32_t passes, hipStream_t st, crt_ctx::Ahead* ahead)
+{
+    const size_t windowBytes = window_bytes(c, passes);
+    size_t off = 0; int r;
+    if ((r = take_region(c, (size_t)((nf + 63u) / 64u) * windowBytes, st, &off))) return r;
+    if (c->orderReady) HIPCK(c, hipStreamWaitEvent(st, c->orderReady, 0));
+    if (c->sceneReady) HIPCK(c, hipStreamWaitEvent(st, c->sceneReady, 0));
+    void* slab = c->pool + off;
+    EventPair ev;
+    harvest_tuning(c);
+    fold_completed(c, c->evRender, &c->foldedRenderMs, &c->foldedLaunches); fold_completed(c, c->evAcc, &c->foldedAccMs, nullptr);
+    if ((r = take_event(c, c->evRender, &ev))) return r;
+    // the pair is in the timing list from here on; any error exit before its end event is recorded takes it back (a half-recorded pair would make every
+    // later crt_get_timing fail in hipEventElapsedTime)
+    struct PairGuard { crt_ctx* c; bool armed; ~PairGuard() { if (armed && !c->evRender.empty()) { c->evPool.push_back(c->evRender.back()); c->evRender.pop_back(); } } } pairGuard{c, true};
+    Launch L; L.st = st; L.ev = ev; L.slab = slab; L.sppFirst = sppFirst; L.nf = nf; L.passes = passes; L.windows = (nf + 63u) / 64u;
+    if ((r = tuner_prepare(c, L))) return r;                       // single-window launches: latency mode (block table, tile-cost measurement)
+    if ((r = planner_prepare(c, L))) return r;                     // jobs: tile-cost measurement, kernel choice, plan (block table + pool split) or plain launch
+    HIPCK(c, hipEventRecord(ev.a, st));
+    const bool pool = L.pool, wantCost = L.wantCost, wantJobCost = L.wantJobCost;
+    const hipError_t le = hook("CRT_DEBUG_FAIL_LAUNCH") ? hipErrorInvalidConfiguration /* tests: the runtime refuses the launch */ : launch_render_kernels(c, L);
+    if (le != hipSuccess) {
+        // a launch that failed has rendered nothing: its timing pair goes back (pairGuard), the accumulator and the region bookkeeping stay untouched —
+        // the frames before it are in, this one and the rest are not — and the error is reported
+        return c->hip(le, pool ? "launch of render_pool_kernel" : "launch of render_tiles_kernel");
+    }
+    if (pool) c->poolLaunches++;
+    HIPCK(c, hipEventRecord(ev.b, st));
+    pairGuard.armed = false;
+    c->lastRenderEnd = ev.b;
+    if (wantJobCost) {
+        HIPCK(c, hipMemcpyAsync(c->hJobCost, c->dJobCost, job_cost_bytes(c), hipMemcpyDeviceToHost, st));
+        HIPCK(c, hipEventRecord(c->jobCostCopied, st));
+        c->jobCostPending = true;
+    }
+    if (wantCost && !pool && !c->latDone) {                                                // the tile costs travel to the host behind the launch; looked at by a later crt_render
+        HIPCK(c, hipMemcpyAsync(c->hTileCost, c->dTileCost, (size_t)c->tileCount * 4, hipMemcpyDeviceToHost, st));
+        HIPCK(c, hipEventRecord(c->costCopied, st));
+        c->costPending = true;
+    }
+    crt_ctx::Region reg; reg.off = off; reg.bytes = (size_t)((nf + 63u) / 64u) * windowBytes;
+    if (c->freeEvents.empty()) HIPCK(c, hipEventCreateWithFlags(&reg.freed, hipEventDisableTiming));
+    else { reg.freed = c->freeEvents.back(); c->freeEvents.pop_back(); }
+    if (ahead) {                                                    // render-ahead: the frames are committed one by one by later crt_tick calls
+        hipEvent_t end = nullptr;
+        if (c->doneEvents.empty()) { const hipError_t e = hipEventCreateWithFlags(&end, hipEventDisableTiming); if (e != hipSuccess) { c->freeEvents.push_back(reg.freed); return c->hip(e, "hipEventCreate"); } }
+        else { end = c->doneEvents.back(); c->doneEvents.pop_back(); }
+        const hipError_t e = hipEventRecord(end, st);
+        if (e != hipSuccess) { c->doneEvents.push_back(end); c->freeEvents.push_back(reg.freed); return c->hip(e, "hipEventRecord"); }
+        reg.held = true;
+        c->inflight.push_back(reg);
+        *ahead = crt_ctx::Ahead{end, off, (const char*)slab, c->epoch, sppFirst, nf, passes, 0u};
+        return 0;
+    }
+    // ordered accumulation on the main stream (frame order = launch order), behind this launch
+    HIPCK(c, hipStreamWaitEvent(c->stream, ev.b, 0));
+    if ((r = take_event(c, c->evAcc, &ev))) return r;
+    HIPCK(c, hipEventRecord(ev.a, c->stream));
+    HIPCK(c, crt_launch_accumulate(slab, c->dAcc, c->tileFirst, c->tileStride, c->tileCount, (uint32_t)c->tilesX, (uint32_t)c->cfg.width, nf, passes, c->stream));
+    HIPCK(c, hipEventRecord(ev.b, c->stream));
+    HIPCK(c, hipEventRecord(reg.freed, c->stream));
+    c->inflight.push_back(reg);
+    return 0;
+}
+
 int crt_render(crt_ctx* c, uint32_t spp_first, uint32_t frames, uint32_t passes)
 {
     if (!c) return CRT_ERR_INVALID;
     if (!c->haveScene && !c->havePrim) return c->fail(CRT_ERR_STATE, "crt_render before crt_upload_scene");
     if (passes < 1 || passes > 4) return c->fail(CRT_ERR_INVALID, "passes must be 1..4 (the reference's UI range, renderer.cpp:178)");
     HIPCK(c, hipSetDevice(c->cfg.device));
+    { int r = discard_ahead(c); if (r) return r; }                 // (a held region must never be handed out again: see take_region)
     if (c->tileCount == 0 || frames == 0) return CRT_OK;
     { int r = update_tile_order(c); if (r) return r; }
     if (c->streams.empty()) {
@@ -1430,55 +1556,8 @@ int crt_render(crt_ctx* c, uint32_t spp_first, uint32_t frames, uint32_t passes)
     }
     for (uint32_t f0 = 0; f0 < frames; f0 += maxF) {
         const uint32_t nf = (frames - f0 < maxF) ? frames - f0 : maxF;
-        hipStream_t st = c->streams[(size_t)(c->launchSeq++ % c->streams.size())];
-        size_t off = 0; int r;
-        if ((r = take_region(c, (size_t)((nf + 63u) / 64u) * windowBytes, st, &off))) return r;
-        if (c->orderReady) HIPCK(c, hipStreamWaitEvent(st, c->orderReady, 0));
-        if (c->sceneReady) HIPCK(c, hipStreamWaitEvent(st, c->sceneReady, 0));
-        void* slab = c->pool + off;
-        EventPair ev;
-        harvest_tuning(c);
-        fold_completed(c, c->evRender, &c->foldedRenderMs, &c->foldedLaunches); fold_completed(c, c->evAcc, &c->foldedAccMs, nullptr);
-        if ((r = take_event(c, c->evRender, &ev))) return r;
-        // the pair is in the timing list from here on; any error exit before its end event is recorded takes it back (a half-recorded pair would make every
-        // later crt_get_timing fail in hipEventElapsedTime)
-        struct PairGuard { crt_ctx* c; bool armed; ~PairGuard() { if (armed && !c->evRender.empty()) { c->evPool.push_back(c->evRender.back()); c->evRender.pop_back(); } } } pairGuard{c, true};
-        Launch L; L.st = st; L.ev = ev; L.slab = slab; L.sppFirst = spp_first + f0 * passes; L.nf = nf; L.passes = passes; L.windows = (nf + 63u) / 64u;
-        if ((r = tuner_prepare(c, L))) return r;                       // single-window launches: latency mode (block table, tile-cost measurement)
-        if ((r = planner_prepare(c, L))) return r;                     // jobs: tile-cost measurement, kernel choice, plan (block table + pool split) or plain launch
-        HIPCK(c, hipEventRecord(ev.a, st));
-        const bool pool = L.pool, wantCost = L.wantCost, wantJobCost = L.wantJobCost;
-        const hipError_t le = hook("CRT_DEBUG_FAIL_LAUNCH") ? hipErrorInvalidConfiguration /* tests: the runtime refuses the launch */ : launch_render_kernels(c, L);
-        if (le != hipSuccess) {
-            // a launch that failed has rendered nothing: its timing pair goes back (pairGuard), the accumulator and the region bookkeeping stay untouched —
-            // the frames before it are in, this one and the rest are not — and the error is reported
-            return c->hip(le, pool ? "launch of render_pool_kernel" : "launch of render_tiles_kernel");
-        }
-        if (pool) c->poolLaunches++;
-        HIPCK(c, hipEventRecord(ev.b, st));
-        pairGuard.armed = false;
-        c->lastRenderEnd = ev.b;
-        if (wantJobCost) {
-            HIPCK(c, hipMemcpyAsync(c->hJobCost, c->dJobCost, job_cost_bytes(c), hipMemcpyDeviceToHost, st));
-            HIPCK(c, hipEventRecord(c->jobCostCopied, st));
-            c->jobCostPending = true;
-        }
-        if (wantCost && !pool && !c->latDone) {                                                // the tile costs travel to the host behind the launch; looked at by a later crt_render
-            HIPCK(c, hipMemcpyAsync(c->hTileCost, c->dTileCost, (size_t)c->tileCount * 4, hipMemcpyDeviceToHost, st));
-            HIPCK(c, hipEventRecord(c->costCopied, st));
-            c->costPending = true;
-        }
-        // ordered accumulation on the main stream (frame order = launch order), behind this launch
-        HIPCK(c, hipStreamWaitEvent(c->stream, ev.b, 0));
-        if ((r = take_event(c, c->evAcc, &ev))) return r;
-        HIPCK(c, hipEventRecord(ev.a, c->stream));
-        HIPCK(c, crt_launch_accumulate(slab, c->dAcc, c->tileFirst, c->tileStride, c->tileCount, (uint32_t)c->tilesX, (uint32_t)c->cfg.width, nf, passes, c->stream));
-        HIPCK(c, hipEventRecord(ev.b, c->stream));
-        crt_ctx::Region reg; reg.off = off; reg.bytes = (size_t)((nf + 63u) / 64u) * windowBytes;
-        if (c->freeEvents.empty()) HIPCK(c, hipEventCreateWithFlags(&reg.freed, hipEventDisableTiming));
-        else { reg.freed = c->freeEvents.back(); c->freeEvents.pop_back(); }
-        HIPCK(c, hipEventRecord(reg.freed, c->stream));
-        c->inflight.push_back(reg);
+        const int r = launch_frames(c, spp_first + f0 * passes, nf, passes, c->streams[(size_t)(c->launchSeq++ % c->streams.size())], nullptr);
+        if (r) return r > 0 ? c->fail(CRT_ERR_DEVICE, "slab ring blocked by a render-ahead region") : r;
     }
     return CRT_OK;
 }
@@ -1489,6 +1568,7 @@ int crt_sync(crt_ctx* c)
     HIPCK(c, hipSetDevice(c->cfg.device));
     HIPCK(c, hipStreamSynchronize(c->stream));          // every render launch is followed by its accumulate on this stream
     for (auto st : c->streams) HIPCK(c, hipStreamSynchronize(st));
+    if (c->aheadStream) HIPCK(c, hipStreamSynchronize(c->aheadStream));
     return CRT_OK;
 }
 
@@ -1509,17 +1589,97 @@ int crt_read_accumulator(crt_ctx* c, float* host)
     return CRT_OK;
 }
 
-int crt_resolve_screen(crt_ctx* c, float scale, uint32_t* hostPixels, float* energy)
+// the screen and the energy a resolve left on the device, to the host (waits for the main stream)
+static int read_screen(crt_ctx* c, uint32_t* hostPixels, float* energy)
 {
-    if (!c) return CRT_ERR_INVALID;
-    HIPCK(c, hipSetDevice(c->cfg.device));
     const int tiles = c->tilesX * c->tilesY;
-    HIPCK(c, crt_launch_resolve(c->dAcc, c->dPixels, c->dTileSums, c->tileFirst, c->tileStride, c->tileCount, (uint32_t)c->tilesX, (uint32_t)c->cfg.width, scale, c->stream));
     if (hostPixels) HIPCK(c, hipMemcpyAsync(hostPixels, c->dPixels, (size_t)c->cfg.width * c->cfg.height * 4, hipMemcpyDeviceToHost, c->stream));
     std::vector<float> sums(tiles);
     HIPCK(c, hipMemcpyAsync(sums.data(), c->dTileSums, (size_t)tiles * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCK(c, hipStreamSynchronize(c->stream));
     if (energy) { float e = 0; for (int i = 0; i < tiles; i++) e += sums[i]; *energy = e; }   // renderer.cpp:155-157, tile order
+    return CRT_OK;
+}
+
+int crt_resolve_screen(crt_ctx* c, float scale, uint32_t* hostPixels, float* energy)
+{
+    if (!c) return CRT_ERR_INVALID;
+    HIPCK(c, hipSetDevice(c->cfg.device));
+    HIPCK(c, crt_launch_resolve(c->dAcc, c->dPixels, c->dTileSums, c->tileFirst, c->tileStride, c->tileCount, (uint32_t)c->tilesX, (uint32_t)c->cfg.width, scale, c->stream));
+    return read_screen(c, hostPixels, energy);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------------------
+// crt_tick: one Renderer::Tick.  A frame's samples depend on its tile, spp, passes, camera, scene, depthLimit and render accelerator — never on the
+// accumulator — so while none of those change, the frames after a Tick can be rendered AHEAD as ordinary render launches (no accumulate; their slab
+// regions stay held) and a later Tick only commits its frame's samples (commit_frame_kernel: accumulate + resolve in one pass) and reads back.
+// The queue is valid for one state epoch (crt_set_camera with new values, crt_update_scene, crt_upload_*, crt_set_render_accel bump it) and the next
+// (spp, passes); any other request discards it and renders its frame as crt_render(spp, 1, passes).  Speculation starts once a Tick follows a Tick of the
+// same epoch with spp = previous + passes, so a camera that moves every Tick renders exactly as before: one launch per Tick, no slab held.
+// Depth: the first launch renders one 64-frame window, each later one twice as many frames as the one before, up to kAheadMaxFrames;
+// at most two launches are queued, on a low-priority stream so that a miss's own launch is dispatched first.
+// ---------------------------------------------------------------------------------------------------------------------------------------------
+static constexpr uint32_t kAheadMaxFrames = 256;
+
+// queues a render-ahead launch whose first frame has spp `sppFirst`
+static int launch_ahead(crt_ctx* c, uint32_t sppFirst, uint32_t passes)
+{
+    if (!c->aheadStream) {
+        int least = 0, greatest = 0;
+        HIPCK(c, hipDeviceGetStreamPriorityRange(&least, &greatest));
+        HIPCK(c, hipStreamCreateWithPriority(&c->aheadStream, hipStreamNonBlocking, least));
+    }
+    uint32_t nf = c->aheadFrames ? std::min(2u * c->aheadFrames, kAheadMaxFrames) : 64u;
+    if (nf > (uint32_t)c->cfg.maxFramesPerLaunch) nf = (uint32_t)c->cfg.maxFramesPerLaunch;
+    const uint32_t poolW = (uint32_t)(c->poolBytes / window_bytes(c, passes));      // the pool as the miss's crt_render sized it: two launches must fit
+    if (nf > poolW / 2u * 64u) nf = poolW / 2u * 64u;
+    if (nf == 0 || c->streams.empty()) return 0;
+    hipStream_t st = hook("CRT_AHEAD_NORMAL_PRIORITY") ? c->streams[(size_t)(c->launchSeq++ % c->streams.size())] : c->aheadStream;   // A/B of the stream priority
+    crt_ctx::Ahead a{};
+    const int r = launch_frames(c, sppFirst, nf, passes, st, &a);
+    if (r < 0) return r;
+    if (r > 0) return 0;                                            // no room in the ring short of a held region: a later hit tries again
+    c->ahead.push_back(a); c->aheadFrames = nf;
+    return 0;
+}
+
+int crt_tick(crt_ctx* c, uint32_t spp, uint32_t passes, uint32_t* hostPixels, float* hostRgba, float* energy)
+{
+    if (!c) return CRT_ERR_INVALID;
+    if (!c->haveScene && !c->havePrim) return c->fail(CRT_ERR_STATE, "crt_tick before crt_upload_scene");
+    if (passes < 1 || passes > 4) return c->fail(CRT_ERR_INVALID, "passes must be 1..4 (the reference's UI range, renderer.cpp:178)");
+    HIPCK(c, hipSetDevice(c->cfg.device));
+    const float scale = 1.0f / (float)(spp + passes);                                          // renderer.cpp:119
+    // statistics contexts (per-tile clocks of ONE launch), the KD-tree / grid path and the PrimitiveScene are served by the plain path only
+    const bool eligible = !c->cfg.collectStats && c->renderAccel == 0 && !c->havePrim && c->tileCount > 0;
+    const bool streak = eligible && c->tickEpoch == c->epoch && spp == c->tickNextSpp && passes == c->tickPasses;
+    c->tickEpoch = c->epoch; c->tickNextSpp = spp + passes; c->tickPasses = passes;
+    const bool hit = !c->ahead.empty() && c->ahead.front().epoch == c->epoch && c->ahead.front().passes == passes &&
+                     spp == c->ahead.front().sppFirst + c->ahead.front().used * passes;
+    int r;
+    if (hit) {
+        crt_ctx::Ahead& a = c->ahead.front();
+        const uint32_t f = a.used++;
+        HIPCK(c, hipStreamWaitEvent(c->stream, a.end, 0));
+        HIPCK(c, crt_launch_commit_frame(a.slab + (size_t)(f / 64u) * sample_bytes_per_window(c, passes), f % 64u, passes, c->dAcc, c->dPixels, c->dTileSums,
+                                         c->tileFirst, c->tileStride, c->tileCount, (uint32_t)c->tilesX, (uint32_t)c->cfg.width, scale, c->stream));
+        if (a.used == a.nf) {                                                                  // the launch's last frame: its region is free behind this commit
+            const crt_ctx::Ahead done = a; c->ahead.pop_front();
+            c->doneEvents.push_back(done.end);
+            if ((r = release_ahead_region(c, done))) return r;
+        }
+        if (c->ahead.size() < 2u) {                                                            // top up while the read-back runs
+            const uint32_t next = c->ahead.empty() ? spp + passes : c->ahead.back().sppFirst + c->ahead.back().nf * passes;
+            if ((r = launch_ahead(c, next, passes))) return r;
+        }
+    } else {
+        if ((r = crt_render(c, spp, 1, passes))) return r;                                     // (discards the queue)
+        HIPCK(c, crt_launch_resolve(c->dAcc, c->dPixels, c->dTileSums, c->tileFirst, c->tileStride, c->tileCount, (uint32_t)c->tilesX, (uint32_t)c->cfg.width, scale, c->stream));
+    }
+    if (hostRgba) HIPCK(c, hipMemcpyAsync(hostRgba, c->dAcc, (size_t)c->cfg.width * c->cfg.height * 16, hipMemcpyDeviceToHost, c->stream));
+    if ((r = read_screen(c, hostPixels, energy))) return r;
+    // a second still Tick in a row: render ahead, after the read-back (the GPU is idle, so a single-window launch takes the latency mode)
+    if (!hit && streak && (r = launch_ahead(c, spp + passes, passes))) return r;
     return CRT_OK;
 }
 
@@ -1567,6 +1727,7 @@ int crt_upload_alt_accel(crt_ctx* c, const crt_alt_accel* a)
     if (!c->haveScene || c->hScene.kind != CRT_SCENE_FILE) return c->fail(CRT_ERR_STATE, "crt_upload_alt_accel needs an uploaded CRT_SCENE_FILE scene (light quad, floor plane, materials)");
     if (a->kind != CRT_ACCEL_KDTREE && a->kind != CRT_ACCEL_GRID) return c->fail(CRT_ERR_INVALID, "unknown accelerator kind %d", a->kind);
     if (!a->triangles || a->triCount == 0) return c->fail(CRT_ERR_INVALID, "accelerator has no triangles");
+    c->epoch++;
     HIPCK(c, hipSetDevice(c->cfg.device));
     const int slot = a->kind == CRT_ACCEL_KDTREE ? 0 : 1;
     uint32_t kdHeight = 0;
@@ -1637,10 +1798,12 @@ int crt_upload_alt_accel(crt_ctx* c, const crt_alt_accel* a)
 int crt_upload_primitive_scene(crt_ctx* c, const crt_primitive_scene* ps)
 {
     if (!c || !ps) return CRT_ERR_INVALID;
+    c->epoch++;
     HIPCK(c, hipSetDevice(c->cfg.device));
     for (const crt_texture* t : {&ps->red, &ps->blue})
         if (t->pixels && (t->width != 512 || t->height != 512)) return c->fail(CRT_ERR_INVALID, "PrimitiveScene wall images are 512 x 512 (Plane::GetAlbedo masks the texel coordinates with 511)");
     for (auto st : c->streams) HIPCK(c, hipStreamSynchronize(st));
+    if (c->aheadStream) HIPCK(c, hipStreamSynchronize(c->aheadStream));
     HIPCK(c, hipStreamSynchronize(c->stream));
     c->freeScene();
     crt::PrimDev& p = c->prim; p = crt::PrimDev{};
@@ -1665,7 +1828,7 @@ int crt_set_render_accel(crt_ctx* c, int kind)
     if (kind != 0 && kind != CRT_ACCEL_KDTREE && kind != CRT_ACCEL_GRID) return c->fail(CRT_ERR_INVALID, "crt_set_render_accel: unknown accelerator kind %d", kind);
     if ((kind == CRT_ACCEL_KDTREE && !c->haveKd) || (kind == CRT_ACCEL_GRID && !c->haveGrid)) return c->fail(CRT_ERR_STATE, "crt_set_render_accel: no such accelerator uploaded (kind %d)", kind);
     if (kind != 0 && (c->alt.kdStack * 2u + 15u) * 64u * 4u * 4u > 64u * 1024u) return c->fail(CRT_ERR_UNSUPPORTED, "KD-tree height %u exceeds the render kernel's LDS stack", c->alt.kdStack);
-    c->renderAccel = kind;
+    c->renderAccel = kind; c->epoch++;
     return CRT_OK;
 }
 
@@ -1715,6 +1878,7 @@ int crt_get_timing(crt_ctx* c, crt_timing* out)
     HIPCK(c, hipSetDevice(c->cfg.device));
     HIPCK(c, hipStreamSynchronize(c->stream));
     for (auto st : c->streams) HIPCK(c, hipStreamSynchronize(st));
+    if (c->aheadStream) HIPCK(c, hipStreamSynchronize(c->aheadStream));
     harvest_tuning(c);                                         // the latency mode's stage timings, before the pairs are recycled
     memset(out, 0, sizeof(*out));
     out->render_kernel_ms = (float)c->foldedRenderMs; out->resolve_kernel_ms = (float)c->foldedAccMs;

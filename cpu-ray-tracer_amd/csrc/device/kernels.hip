@@ -16,6 +16,7 @@
 //   find_nearest_kernel   scene.FindNearest for a ray buffer (parity / query entry).
 //   whitted_kernel        the Whitted-style integrator ("2. WhittedStyle/renderer.cpp":21-157), one thread per pixel.
 //   resolve_kernel        screen pixels + per-tile energy sums (renderer.cpp:119,127-129).
+//   commit_frame_kernel   crt_tick: one rendered-ahead frame's samples into the accumulator + the screen, in one pass.
 //
 // Numerics: compiled with -ffp-contract=off; only IEEE + - * / sqrt, so results are bit-identical with a scalar
 // CPU evaluation of the same expressions.  min/max follow the reference's std::min/std::max operand order.
@@ -928,6 +929,40 @@ __global__ __launch_bounds__(64) void resolve_kernel(const float4* __restrict__ 
     tileSums[tile] = sum;
 }
 
+// ------------------------------------------------------------------------------------------------------------
+// commit_frame_kernel: crt_tick's hit — ONE rendered-ahead frame into the accumulator, then the screen: accumulate_kernel for that frame
+// followed by resolve_kernel, in one pass.  Block = one owned tile, thread = pixel (v * 16 + u, the slab's pixel order).  Each channel gets the
+// frame's `passes` samples in pass order (accumulate_kernel's chain of adds); the pixel is formed from the new value as resolve_kernel forms it.
+// The tile's energy is summed by one lane over the 256 parked values in ProcessTile (v, u) order, so it is bit-exact (renderer.cpp:119,127-129).
+// slabWindow = the launch's window that holds the frame ([tileLocal][pixel][frame * passes + pass]).
+// ------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void commit_frame_kernel(const float4* __restrict__ slabWindow, uint32_t frameInWindow, uint32_t passes,
+                                                            float4* __restrict__ acc, uint32_t* __restrict__ pixels, float* __restrict__ tileSums,
+                                                            uint32_t tileFirst, uint32_t tileStride, uint32_t tileCount, uint32_t tilesX,
+                                                            uint32_t W, float scale)
+{
+    __shared__ float tileE[256];
+    const uint32_t tl = blockIdx.x, pix = threadIdx.x;
+    if (tl >= tileCount) return;
+    const uint32_t tile = tileFirst + tl * tileStride;
+    const uint32_t x0 = (tile % tilesX) * 16u, y0 = (tile / tilesX) * 16u;
+    const size_t i = (x0 + (pix & 15u)) + (size_t)(y0 + (pix >> 4)) * W;
+    const float4* __restrict__ s = slabWindow + ((size_t)tl * 256u + pix) * (64u * passes) + frameInWindow * passes;
+    float4 a = acc[i];
+    for (uint32_t p = 0; p < passes; p++) { const float4 t = s[p]; a.x += t.x; a.y += t.y; a.z += t.z; a.w += t.w; }
+    acc[i] = a;
+    const float px = a.x * scale, py = a.y * scale, pz = a.z * scale;
+    tileE[pix] = px + py + pz;
+    const uint32_t r = (uint32_t)(255.0f * min_std(1.0f, px)), g = (uint32_t)(255.0f * min_std(1.0f, py)), bb = (uint32_t)(255.0f * min_std(1.0f, pz));
+    pixels[i] = (r << 16) + (g << 8) + bb;
+    __syncthreads();
+    if (pix == 0) {
+        float sum = 0;
+        for (uint32_t k = 0; k < 256u; k++) sum += tileE[k];
+        tileSums[tile] = sum;
+    }
+}
+
 } // namespace crt
 
 // ------------------------------------------------------------------------------------------------------------
@@ -1029,5 +1064,15 @@ extern "C" hipError_t crt_launch_resolve(const void* acc, uint32_t* pixels, floa
     if (tileCount == 0) return hipSuccess;
     dim3 grid((tileCount + 63u) / 64u), block(64);
     hipLaunchKernelGGL(crt::resolve_kernel, grid, block, 0, stream, (const float4*)acc, pixels, tileSums, tileFirst, tileStride, tileCount, tilesX, W, scale);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t crt_launch_commit_frame(const void* slabWindow, uint32_t frameInWindow, uint32_t passes, void* acc, uint32_t* pixels, float* tileSums,
+                                              uint32_t tileFirst, uint32_t tileStride, uint32_t tileCount, uint32_t tilesX, uint32_t W, float scale, hipStream_t stream)
+{
+    if (tileCount == 0) return hipSuccess;
+    if (frameInWindow >= 64u || passes < 1u || passes > 4u) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(crt::commit_frame_kernel, dim3(tileCount), dim3(256), 0, stream, (const float4*)slabWindow, frameInWindow, passes, (float4*)acc, pixels, tileSums,
+                       tileFirst, tileStride, tileCount, tilesX, W, scale);
     return hipGetLastError();
 }

@@ -242,9 +242,14 @@ void Renderer::TickWhitted()
 
 void Renderer::Tick(float deltaTime)   // renderer.cpp:144-168
 {
-    if (animating) anim_time += deltaTime * 0.002f;                                              // :147 (Render applies SetTime + ClearAccumulator)
+    if (animating) anim_time += deltaTime * 0.002f;                                              // :147
     const auto t0 = std::chrono::steady_clock::now();
-    Render(1);                                                                                  // the tile jobs (:149-153) + energy (:155-157)
+    if (!ctx) throw std::runtime_error("Renderer::Tick before Init");
+    if (animating) { scene->SetTime(anim_time); ClearAccumulator(); }
+    PushCamera();
+    // the tile jobs (:149-153) + energy (:155-157): Render(1) in one call, which serves a run of still Ticks from frames rendered ahead
+    check(ctx, crt_tick(ctx, (uint32_t)spp, (uint32_t)passes, screen ? screen->pixels.data() : nullptr, accumulator, &energy), "crt_tick");
+    spp += passes;
     // performance report - running average - ms, frames/s, primary rays per ms (:159-161; the UI labels the last one "Mrays/s")
     const float ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
     m_avg = (1 - m_alpha) * m_avg + m_alpha * ms;

@@ -173,6 +173,16 @@ int  crt_read_accumulator(crt_ctx* ctx, float* host_rgba /* float4[width*height]
 /* screen->pixels and Renderer::energy as ProcessTile/Tick leave them (renderer.cpp:119,127-129,155-157):
  * pixel = accumulator * scale, scale = 1/(spp+passes) of the LAST rendered frame.  Either output may be NULL. */
 int  crt_resolve_screen(crt_ctx* ctx, float scale, uint32_t* host_pixels /* width*height */, float* energy);
+/* One Renderer::Tick (renderer.cpp:144-168): exactly crt_render(ctx, spp, 1, passes), then crt_read_accumulator(ctx, host_rgba) if host_rgba != NULL,
+ * then crt_resolve_screen(ctx, 1/(spp+passes), host_pixels, energy) — bit for bit the same accumulator, screen pixels, energy and untouched non-owned
+ * tiles.  Synchronous; any output may be NULL.  Argument checks and error codes are crt_render's.
+ * Render-ahead: a frame's samples do not depend on the accumulator, so once a Tick follows a Tick with spp = previous spp + passes and nothing the
+ * samples depend on has changed in between (crt_set_camera with different values, crt_update_scene, any crt_upload_*, crt_set_render_accel), the
+ * following frames are rendered ahead in multi-frame launches and a later Tick of that sequence only adds its frame's samples, resolves and reads
+ * back.  Any other call order is served as above (crt_render and crt_reserve drop the frames rendered ahead; crt_clear and crt_bind_accumulator keep
+ * them).  The counters and crt_get_timing include every frame rendered ahead, also those later dropped.  Contexts with collectStats, the KD-tree /
+ * grid path (crt_set_render_accel != 0) and the PrimitiveScene never render ahead. */
+int  crt_tick(crt_ctx* ctx, uint32_t spp, uint32_t passes, uint32_t* host_pixels /* width*height */, float* host_rgba /* float4[width*height] */, float* energy);
 
 /* ---- Whitted-style integrator ("2. WhittedStyle/renderer.cpp":21-157): one deterministic Tick -------------------
  * Every pixel of the image (rows are not tile-truncated in this renderer) gets accumulator = float4(Trace(primary), 0)
