@@ -75,9 +75,10 @@ NODE_DTYPE = np.dtype([("aabbMin", "<f4", 3), ("aabbMax", "<f4", 3), ("leftFirst
 TLAS_DTYPE = np.dtype([("aabbMin", "<f4", 3), ("leftRight", "<u4"), ("aabbMax", "<f4", 3), ("BLAS", "<u4")])
 RAY_DTYPE = np.dtype([("O", "<f4", 3), ("D", "<f4", 3), ("inside", "<i4")])
 HIT_DTYPE = np.dtype([("t", "<f4"), ("u", "<f4"), ("v", "<f4"), ("objIdx", "<i4"), ("triIdx", "<i4"), ("traversed", "<i4"), ("tested", "<i4")])
+SHADOW_RAY_DTYPE = np.dtype([("O", "<f4", 3), ("D", "<f4", 3), ("t", "<f4")])     # crt_shadow_ray: the argument of IsOccluded
 
 # every symbol include/crt_abi.h and include/crt_host.h declare (tests check the library exports all of them)
-ABI_SYMBOLS = ["crt_upload_primitive_scene", "crt_set_render_accel", "crt_upload_alt_accel", "crt_find_nearest_alt", "crt_update_scene", "crt_abi_version", "crt_device_count", "crt_create", "crt_destroy", "crt_last_error", "crt_upload_scene", "crt_set_camera",
+ABI_SYMBOLS = ["crt_is_occluded", "crt_find_nearest_device", "crt_is_occluded_device", "crt_upload_primitive_scene", "crt_set_render_accel", "crt_upload_alt_accel", "crt_find_nearest_alt", "crt_update_scene", "crt_abi_version", "crt_device_count", "crt_create", "crt_destroy", "crt_last_error", "crt_upload_scene", "crt_set_camera",
                "crt_render", "crt_tick", "crt_reserve", "crt_whitted_tick", "crt_sync", "crt_clear", "crt_read_accumulator", "crt_resolve_screen", "crt_find_nearest", "crt_get_counters",
                "crt_reset_counters", "crt_get_timing", "crt_get_tile_clocks", "crt_bind_accumulator", "crt_accumulator_device_ptr"]
 HOST_SYMBOLS = ["crt_host_primitive_scene_create", "crt_host_primitive_scene_free", "crt_host_primitive_scene_set_time", "crt_host_primitive_scene_desc", "crt_host_primitive_scene_upload", "crt_host_scene_build_alt", "crt_host_scene_upload_alt", "crt_host_scene_alt_info", "crt_host_scene_alt_copy", "crt_host_scene_set_transform", "crt_host_scene_update", "crt_host_math_probe", "crt_host_vertex_dedup", "crt_host_last_error", "crt_host_scene_load", "crt_host_scene_free", "crt_host_scene_upload", "crt_host_scene_kind",
@@ -154,14 +155,16 @@ class Context:
             raise CrtError(rc, self.L.crt_last_error(None).decode())
         self.h = h
         self.W, self.H = width, height
+        self.device = device
         self._owned = True
 
     @classmethod
-    def borrow(cls, handle, width, height):
+    def borrow(cls, handle, width, height, device=0):
         o = cls.__new__(cls)
         o.L = lib()
         o.h = C.c_void_p(handle)
         o.W, o.H = width, height
+        o.device = device
         o._owned = False
         return o
 
@@ -289,6 +292,94 @@ class Context:
         self._ck(self.L.crt_find_nearest(self.h, _p(rays), _p(hits), C.c_size_t(O.shape[0])))
         return hits
 
+    def is_occluded(self, O, D, t, accel=0):
+        """scene.IsOccluded per ray (crt_is_occluded, host buffers, synchronous): the light quad bounded by t, then the BVH / TLAS (accel 0) or the uploaded
+        KD-tree / grid (ACCEL_KDTREE / ACCEL_GRID) over the whole ray.  t: one value or one per ray.  Returns a bool array."""
+        O = np.asarray(O, np.float32).reshape(-1, 3)
+        D = np.asarray(D, np.float32).reshape(-1, 3)
+        rays = np.zeros(O.shape[0], SHADOW_RAY_DTYPE)
+        rays["O"], rays["D"] = O, D
+        rays["t"] = np.broadcast_to(np.asarray(t, np.float32).reshape(-1), (O.shape[0],))
+        out = np.zeros(O.shape[0], np.int32)
+        self._ck(self.L.crt_is_occluded(self.h, int(accel), _p(rays), _p(out), C.c_size_t(O.shape[0])))
+        return out != 0
+
+    # ---- the queries on device buffers (torch tensors; torch is imported only here) ----
+    def _records(self, rays, O, D, last, last_is_int, what):
+        """the [N, 7] 28-byte records (crt_ray / crt_shadow_ray) on the context's device: `rays` as given, or built from O, D and the last column"""
+        import torch
+        dev = torch.device("cuda", self.device)
+
+        def on_device(x, name):
+            if not isinstance(x, torch.Tensor) or x.device != dev:
+                raise ValueError("%s: %s must be a torch tensor on %s" % (what, name, dev))
+            if not x.is_contiguous():
+                raise ValueError("%s: %s must be contiguous" % (what, name))
+            return x
+
+        if rays is not None:
+            if O is not None or D is not None:
+                raise ValueError("%s: pass either rays or O / D" % what)
+            on_device(rays, "rays")
+            if rays.dim() != 2 or rays.shape[1] != 7 or rays.dtype not in (torch.float32, torch.int32):
+                raise ValueError("%s: rays must be [N, 7] float32 / int32 records" % what)
+            return rays
+        O, D = on_device(O, "O"), on_device(D, "D")
+        if O.dtype != torch.float32 or D.dtype != torch.float32 or O.dim() != 2 or O.shape[1] != 3 or D.shape != O.shape:
+            raise ValueError("%s: O and D must be [N, 3] float32" % what)
+        n = O.shape[0]
+        if last_is_int:                                                       # crt_ray.inside: an int32 bit pattern in the float32 record
+            col = torch.zeros(n, dtype=torch.int32, device=dev) if last is None else torch.as_tensor(last, device=dev).to(torch.int32).expand(n)
+            col = col.contiguous().view(torch.float32)
+        else:                                                                 # crt_shadow_ray.t
+            col = torch.as_tensor(last, dtype=torch.float32, device=dev).reshape(-1).expand(n)
+        return torch.cat([O, D, col.reshape(n, 1)], 1).contiguous()
+
+    def find_nearest_device(self, rays=None, O=None, D=None, inside=None, accel=0, stream=None):
+        """crt_find_nearest_device: scene.FindNearest for rays that live on the GPU, enqueued on `stream` (default torch.cuda.current_stream()) without a host wait.
+        rays = [N, 7] crt_ray records, or O / D = [N, 3] float32 (+ inside).  accel: 0 = BVH / TLAS / PrimitiveScene, ACCEL_KDTREE / ACCEL_GRID.
+        Returns the [N, 7] float32 tensor of crt_hit records (hit_fields() splits it)."""
+        import torch
+
+        def run(st):
+            r = self._records(rays, O, D, inside, True, "find_nearest_device")
+            hits = torch.empty((r.shape[0], 7), dtype=torch.float32, device=r.device)
+            self._ck(self.L.crt_find_nearest_device(self.h, int(accel), C.c_void_p(r.data_ptr()), C.c_void_p(hits.data_ptr()), C.c_size_t(r.shape[0]), C.c_void_p(st.cuda_stream)))
+            return hits
+        return self._enqueue(stream, run)
+
+    def is_occluded_device(self, rays=None, O=None, D=None, t=None, accel=0, stream=None):
+        """crt_is_occluded_device: scene.IsOccluded for rays on the GPU, enqueued on `stream` (default torch.cuda.current_stream()) without a host wait.
+        rays = [N, 7] crt_shadow_ray records, or O / D = [N, 3] float32 + t (one value or [N]).  Returns an [N] int32 tensor of 1 / 0."""
+        import torch
+        if rays is None and t is None:
+            raise ValueError("is_occluded_device: t is required with O / D")
+
+        def run(st):
+            r = self._records(rays, O, D, t, False, "is_occluded_device")
+            occ = torch.empty(r.shape[0], dtype=torch.int32, device=r.device)
+            self._ck(self.L.crt_is_occluded_device(self.h, int(accel), C.c_void_p(r.data_ptr()), C.c_void_p(occ.data_ptr()), C.c_size_t(r.shape[0]), C.c_void_p(st.cuda_stream)))
+            return occ
+        return self._enqueue(stream, run)
+
+    def _enqueue(self, stream, run):
+        """run(st) on the torch stream `stream` (default: the current one).  Torch's default stream has the handle 0, which the ABI reads as the context's own
+        stream: on it the query runs on a side stream that waits for it and that it waits for in turn (events, no host wait)."""
+        import torch
+        st = stream if stream is not None else torch.cuda.current_stream(self.device)
+        if st.cuda_stream != 0:
+            with torch.cuda.stream(st):
+                return run(st)
+        side = getattr(self, "_side_stream", None)
+        if side is None:
+            side = self._side_stream = torch.cuda.Stream(device=self.device)
+        side.wait_stream(st)
+        with torch.cuda.stream(side):
+            out = run(side)
+        st.wait_stream(side)
+        out.record_stream(st)                                                 # allocated on the side stream, consumed on st
+        return out
+
     def counters(self):
         c = CountersS()
         self._ck(self.L.crt_get_counters(self.h, C.byref(c)))
@@ -314,6 +405,12 @@ class Context:
         p = C.c_void_p()
         self._ck(self.L.crt_accumulator_device_ptr(self.h, C.byref(p)))
         return p.value
+
+def hit_fields(hits):
+    """the seven crt_hit fields of an [N, 7] record tensor from find_nearest_device, as views: t / u / v float32, objIdx / triIdx / traversed / tested int32"""
+    import torch
+    i = hits.view(torch.int32)
+    return dict(t=hits[:, 0], u=hits[:, 1], v=hits[:, 2], objIdx=i[:, 3], triIdx=i[:, 4], traversed=i[:, 5], tested=i[:, 6])
 
 
 class HostScene:

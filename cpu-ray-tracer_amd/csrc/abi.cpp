@@ -57,6 +57,9 @@ extern "C" hipError_t crt_launch_find_nearest_prim(const crt::PrimDev*, const vo
 extern "C" hipError_t crt_launch_render_prim(const crt::Scene*, const crt::PrimDev*, void*, crt::Counters*, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, hipStream_t);
 extern "C" hipError_t crt_launch_check_reciprocals(unsigned long long*, hipStream_t);
 extern "C" hipError_t crt_launch_find_nearest_alt(int, const crt::Scene*, const crt::AltAccelDev*, const void*, void*, uint32_t, uint32_t*, hipStream_t);
+extern "C" hipError_t crt_launch_is_occluded(const crt::Scene*, const void*, int32_t*, uint32_t, uint32_t, uint32_t*, hipStream_t);
+extern "C" hipError_t crt_launch_is_occluded_alt(int, const crt::Scene*, const crt::AltAccelDev*, const void*, int32_t*, uint32_t, uint32_t*, hipStream_t);
+static_assert(sizeof(crt_shadow_ray) == 28 && sizeof(crt_ray) == 28 && sizeof(crt_hit) == 28, "query records");
 
 namespace {
 
@@ -119,6 +122,14 @@ struct crt_ctx {
     int renderAccel = 0;                  // crt_set_render_accel: 0 = the scene's BVH / TLAS, CRT_ACCEL_KDTREE / CRT_ACCEL_GRID = Sample and Trace go through that structure
     crt::AltAccelDev alt{}; bool haveKd = false, haveGrid = false; std::vector<void*> altAllocs[2]; void* altTris = nullptr; uint32_t altTriCount = 0;   // KD-tree [0] / grid [1] buffers
     void* dQueryRays = nullptr; void* dQueryHits = nullptr; size_t queryCap = 0;      // crt_find_nearest staging (rays)
+    // Device-buffer queries (crt_find_nearest_device / crt_is_occluded_device) on callers' streams: each launch draws its rays from a cursor word of its own
+    // (slot k at dQuerySlots + 16k, one cache line each), handed out as a ring; `done` is recorded on the caller's stream behind the launch, and a slot is
+    // reused only after its event has completed.  The same events order later scene writes behind the queries still in flight (order_behind_queries).
+    static constexpr int kQuerySlots = 64;
+    uint32_t* dQuerySlots = nullptr;
+    struct QuerySlot { hipEvent_t done = nullptr; bool pending = false; } qslot[kQuerySlots];
+    int qslotNext = 0;
+    hipEvent_t altReady = nullptr;        // recorded behind the last crt_upload_alt_accel's copies (device queries on other streams wait for it)
     // Latency mode of single-window launches (render_tiles_kernel's block table), driven by measurement — see next_block_table.  Stage 0 = the table solved from the cost probe's
     // estimates (one wavefront per tile when there was no probe); stages 1 .. kLatStages = tables solved from the tile costs the stage before measured; afterwards the fastest stage is used
     // (HIP event durations of the launches themselves; identical pixels whatever the table).
@@ -218,6 +229,27 @@ int bvh_height(crt_ctx* c, const crt_bvh& b, uint32_t* heightOut)
     return 0;
 }
 
+// device queries on callers' streams that may still read the scene / accelerator buffers: the host waits for them (before buffers are freed or rewritten
+// by a synchronous copy) ...
+int wait_queries(crt_ctx* c)
+{
+    for (auto& q : c->qslot) if (q.pending) { HIPCK(c, hipEventSynchronize(q.done)); q.pending = false; }
+    return 0;
+}
+
+// ... or the main stream does (before an in-place copy on it): no host wait, as order_behind_ahead for render-ahead launches
+int order_behind_queries(crt_ctx* c)
+{
+    for (auto& q : c->qslot) {
+        if (!q.pending) continue;
+        const hipError_t e = hipEventQuery(q.done);
+        if (e == hipSuccess) { q.pending = false; continue; }
+        if (e != hipErrorNotReady) return c->hip(e, "hipEventQuery(query)");
+        HIPCK(c, hipStreamWaitEvent(c->stream, q.done, 0));
+    }
+    return 0;
+}
+
 } // namespace
 
 extern "C" {
@@ -288,6 +320,7 @@ int crt_create(crt_ctx** out, const crt_config* cfg)
     if ((e = hipMalloc((void**)&c->dCounters, sizeof(crt::Counters))) != hipSuccess) return bail(e, "hipMalloc(counters)");
     if ((e = hipMemsetAsync(c->dCounters, 0, sizeof(crt::Counters), c->stream)) != hipSuccess) return bail(e, "hipMemset(counters)");
     if ((e = hipMalloc((void**)&c->dQueryCursor, 64)) != hipSuccess) return bail(e, "hipMalloc(query cursor)");
+    if ((e = hipMalloc((void**)&c->dQuerySlots, crt_ctx::kQuerySlots * 64)) != hipSuccess) return bail(e, "hipMalloc(query cursor slots)");
     if (c->cfg.collectStats && count > 0) {
         if ((e = hipMalloc((void**)&c->dTileClocks, (size_t)count * 144)) != hipSuccess) return bail(e, "hipMalloc(tileClocks)");
         if ((e = hipMemsetAsync(c->dTileClocks, 0, (size_t)count * 144, c->stream)) != hipSuccess) return bail(e, "hipMemset(tileClocks)");
@@ -314,6 +347,9 @@ void crt_destroy(crt_ctx* c)
     for (auto st : c->streams) (void)hipStreamSynchronize(st);
     if (c->aheadStream) (void)hipStreamSynchronize(c->aheadStream);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
+    for (auto& q : c->qslot) if (q.done) { if (q.pending) (void)hipEventSynchronize(q.done); (void)hipEventDestroy(q.done); }   // device queries on callers' streams
+    if (c->dQuerySlots) (void)hipFree(c->dQuerySlots);
+    if (c->altReady) (void)hipEventDestroy(c->altReady);
     c->freeScene();
     for (auto& a : c->ahead) (void)hipEventDestroy(a.end);
     if (c->aheadStream) (void)hipStreamDestroy(c->aheadStream);
@@ -539,6 +575,7 @@ int crt_upload_scene(crt_ctx* c, const crt_scene_desc* sd)
     for (auto st : c->streams) HIPCK(c, hipStreamSynchronize(st));
     if (c->aheadStream) HIPCK(c, hipStreamSynchronize(c->aheadStream));
     HIPCK(c, hipStreamSynchronize(c->stream));
+    { const int r = wait_queries(c); if (r) return r; }
     c->freeScene();
     uint32_t* dTexels = nullptr;
     HIPCK(c, hipMalloc((void**)&dTexels, (size_t)texels * 4)); c->sceneAllocs.push_back(dTexels);
@@ -761,6 +798,7 @@ int crt_update_scene(crt_ctx* c, const crt_scene_desc* sd, uint32_t what)
     } else HIPCK(c, hipEventSynchronize(c->stageCopied[k]));
     memcpy(c->hStage[k], f.geom.data() + lo, bytes);
     { const int r = order_behind_ahead(c); if (r) return r; }
+    { const int r = order_behind_queries(c); if (r) return r; }
     HIPCK(c, hipMemcpyAsync(const_cast<char*>(c->hScene.geom) + lo, c->hStage[k], bytes, hipMemcpyHostToDevice, c->stream));
     HIPCK(c, hipEventRecord(c->stageCopied[k], c->stream));
     c->sceneReady = c->stageCopied[k];
@@ -1755,6 +1793,7 @@ int crt_upload_alt_accel(crt_ctx* c, const crt_alt_accel* a)
         for (uint32_t i = 0; i < a->gridCellTriCount; i++) if (a->gridCellTris[i] < 0 || (uint32_t)a->gridCellTris[i] >= a->triCount) return c->fail(CRT_ERR_INVALID, "gridCellTris[%u] out of range", i);
     }
     HIPCK(c, hipStreamSynchronize(c->stream));                            // queries of the previous structure
+    { const int r = wait_queries(c); if (r) return r; }                  // ... also those on callers' streams
     for (void* p : c->altAllocs[slot]) (void)hipFree(p);
     c->altAllocs[slot].clear();
     if (slot == 0) c->haveKd = false; else c->haveGrid = false;
@@ -1792,6 +1831,8 @@ int crt_upload_alt_accel(crt_ctx* c, const crt_alt_accel* a)
         for (int k = 0; k < 3; k++) { c->alt.res[k] = a->gridResolution[k]; c->alt.cell[k] = a->gridCellSize[k]; c->alt.lo[k] = a->gridMin[k]; c->alt.hi[k] = a->gridMax[k]; }
         c->haveGrid = true;
     }
+    if (!c->altReady) HIPCK(c, hipEventCreateWithFlags(&c->altReady, hipEventDisableTiming));
+    HIPCK(c, hipEventRecord(c->altReady, nullptr));                       // behind the copies above (null stream): device queries on other streams wait for it
     return CRT_OK;
 }
 
@@ -1805,6 +1846,7 @@ int crt_upload_primitive_scene(crt_ctx* c, const crt_primitive_scene* ps)
     for (auto st : c->streams) HIPCK(c, hipStreamSynchronize(st));
     if (c->aheadStream) HIPCK(c, hipStreamSynchronize(c->aheadStream));
     HIPCK(c, hipStreamSynchronize(c->stream));
+    { const int r = wait_queries(c); if (r) return r; }
     c->freeScene();
     crt::PrimDev& p = c->prim; p = crt::PrimDev{};
     memcpy(p.quadInvT, ps->quadInvT, 48); p.quadNrm[0] = -ps->quadT[1]; p.quadNrm[1] = -ps->quadT[5]; p.quadNrm[2] = -ps->quadT[9]; p.quadSize = ps->quadSize;   // Quad::GetNormal, primitives.h:363-367
@@ -1851,6 +1893,132 @@ int crt_find_nearest_alt(crt_ctx* c, int kind, const crt_ray* rays, crt_hit* hit
     HIPCK(c, hipMemcpyAsync(c->dQueryRays, rays, n * sizeof(crt_ray), hipMemcpyHostToDevice, c->stream));
     HIPCK(c, crt_launch_find_nearest_alt(kind, &c->hScene, &c->alt, c->dQueryRays, c->dQueryHits, (uint32_t)n, c->dQueryCursor, c->stream));
     HIPCK(c, hipMemcpyAsync(hits, c->dQueryHits, n * sizeof(crt_hit), hipMemcpyDeviceToHost, c->stream));
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    return CRT_OK;
+}
+
+// ---- scene queries: IsOccluded on host buffers, FindNearest / IsOccluded on device buffers (crt_abi.h "scene queries") ----
+// what every query entry checks, before n == 0 returns (as crt_find_nearest / crt_find_nearest_alt): a known accelerator, a scene that has it, at most 2^31-1 rays
+static int query_check(crt_ctx* c, int accel, bool occl, size_t n, const char* what)
+{
+    if (accel != 0 && accel != CRT_ACCEL_KDTREE && accel != CRT_ACCEL_GRID) return c->fail(CRT_ERR_INVALID, "%s: unknown accelerator kind %d", what, accel);
+    if (accel == 0) {
+        if (occl && c->havePrim) return c->fail(CRT_ERR_UNSUPPORTED, "%s: IsOccluded over the PrimitiveScene is not supported (crt_whitted_tick refuses it too)", what);
+        if (!c->haveScene && !c->havePrim) return c->fail(CRT_ERR_STATE, "%s before crt_upload_scene", what);
+    } else if (!((accel == CRT_ACCEL_KDTREE && c->haveKd) || (accel == CRT_ACCEL_GRID && c->haveGrid))) {
+        return c->fail(CRT_ERR_STATE, "%s: no such accelerator uploaded (kind %d)", what, accel);
+    }
+    if (n > 0x7fffffffull) return c->fail(CRT_ERR_UNSUPPORTED, "%s: at most 2^31-1 rays per call", what);
+    return 0;
+}
+
+// a caller's buffer of `bytes` bytes must be device (or managed) memory of cfg.device, first and last byte alike, and 4-byte aligned
+static int check_device_buffer(crt_ctx* c, const void* p, size_t bytes, const char* what)
+{
+    if (!p) return c->fail(CRT_ERR_INVALID, "%s: NULL buffer", what);
+    if (reinterpret_cast<uintptr_t>(p) & 3u) return c->fail(CRT_ERR_INVALID, "%s: buffer %p is not 4-byte aligned", what, p);
+    const char* ends[2] = {static_cast<const char*>(p), static_cast<const char*>(p) + bytes - 1};
+    for (const char* q : ends) {
+        hipPointerAttribute_t a{};
+        const hipError_t e = hipPointerGetAttributes(&a, q);
+        if (e != hipSuccess) { (void)hipGetLastError(); return c->fail(CRT_ERR_INVALID, "%s: %p is not device memory (%s)", what, (const void*)q, hipGetErrorString(e)); }
+        if (!(a.type == hipMemoryTypeDevice || a.isManaged)) return c->fail(CRT_ERR_INVALID, "%s: %p is not device memory (a host pointer: use the host entry)", what, (const void*)q);
+        if (a.device != c->cfg.device) return c->fail(CRT_ERR_INVALID, "%s: %p lives on device %d, the context on device %d", what, (const void*)q, a.device, c->cfg.device);
+    }
+    return 0;
+}
+
+// a cursor slot whose previous launch has completed (all 64 in flight: the host waits for the next one in ring order)
+static int take_query_slot(crt_ctx* c, int* out)
+{
+    for (int i = 0; i < crt_ctx::kQuerySlots; i++) {
+        const int k = (c->qslotNext + i) % crt_ctx::kQuerySlots;
+        crt_ctx::QuerySlot& q = c->qslot[k];
+        if (q.pending) {
+            const hipError_t e = hipEventQuery(q.done);
+            if (e == hipErrorNotReady) continue;
+            if (e != hipSuccess) return c->hip(e, "hipEventQuery(query)");
+            q.pending = false;
+        }
+        if (!q.done) HIPCK(c, hipEventCreateWithFlags(&q.done, hipEventDisableTiming));
+        c->qslotNext = (k + 1) % crt_ctx::kQuerySlots; *out = k;
+        return 0;
+    }
+    const int k = c->qslotNext;
+    HIPCK(c, hipEventSynchronize(c->qslot[k].done)); c->qslot[k].pending = false;
+    c->qslotNext = (k + 1) % crt_ctx::kQuerySlots; *out = k;
+    return 0;
+}
+
+static int query_device(crt_ctx* c, bool occl, int accel, const void* dRays, void* dOut, size_t n, void* stream, const char* what)
+{
+    int r;
+    if ((r = query_check(c, accel, occl, n, what))) return r;
+    if (n == 0) return CRT_OK;
+    HIPCK(c, hipSetDevice(c->cfg.device));
+    if ((r = check_device_buffer(c, dRays, n * 28, what)) || (r = check_device_buffer(c, dOut, n * (occl ? 4 : 28), what))) return r;
+    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : c->stream;
+    if (stream) {
+        hipDevice_t dev = -1;
+        HIPCK(c, hipStreamGetDevice(st, &dev));
+        if (dev != c->cfg.device) return c->fail(CRT_ERR_INVALID, "%s: the stream belongs to device %d, the context to device %d", what, dev, c->cfg.device);
+    }
+    // the scene as of the last upload / update: in-place updates are copies on the main stream (sceneReady), the accelerators' copies ran on the null stream
+    if (c->sceneReady) HIPCK(c, hipStreamWaitEvent(st, c->sceneReady, 0));
+    if (accel != 0 && c->altReady) HIPCK(c, hipStreamWaitEvent(st, c->altReady, 0));
+    int k = 0;
+    if ((r = take_query_slot(c, &k))) return r;
+    uint32_t* cursor = c->dQuerySlots + 16 * k;
+    if (occl) {
+        if (accel == 0) HIPCK(c, crt_launch_is_occluded(&c->hScene, dRays, static_cast<int32_t*>(dOut), (uint32_t)n, c->ldsBytes, cursor, st));
+        else HIPCK(c, crt_launch_is_occluded_alt(accel, &c->hScene, &c->alt, dRays, static_cast<int32_t*>(dOut), (uint32_t)n, cursor, st));
+    } else if (accel != 0) {
+        HIPCK(c, crt_launch_find_nearest_alt(accel, &c->hScene, &c->alt, dRays, dOut, (uint32_t)n, cursor, st));
+    } else if (c->havePrim) {
+        HIPCK(c, crt_launch_find_nearest_prim(&c->prim, dRays, dOut, (uint32_t)n, st));
+    } else {
+        HIPCK(c, crt_launch_find_nearest(&c->hScene, dRays, dOut, (uint32_t)n, c->dCounters, c->ldsBytes, cursor, st));
+    }
+    // later scene writes wait for this event (order_behind_queries / wait_queries); so does the slot's next use
+    HIPCK(c, hipEventRecord(c->qslot[k].done, st));
+    c->qslot[k].pending = true;
+    return CRT_OK;
+}
+
+int crt_find_nearest_device(crt_ctx* c, int accel, const crt_ray* d_rays, crt_hit* d_hits, size_t n, void* stream)
+{
+    if (!c) return CRT_ERR_INVALID;
+    return query_device(c, false, accel, d_rays, d_hits, n, stream, "crt_find_nearest_device");
+}
+
+int crt_is_occluded_device(crt_ctx* c, int accel, const crt_shadow_ray* d_rays, int32_t* d_occluded, size_t n, void* stream)
+{
+    if (!c) return CRT_ERR_INVALID;
+    return query_device(c, true, accel, d_rays, d_occluded, n, stream, "crt_is_occluded_device");
+}
+
+int crt_is_occluded(crt_ctx* c, int accel, const crt_shadow_ray* rays, int32_t* occluded, size_t n)
+{
+    if (!c) return CRT_ERR_INVALID;
+    int r;
+    if ((r = query_check(c, accel, true, n, "crt_is_occluded"))) return r;
+    if (n == 0) return CRT_OK;
+    if (!rays || !occluded) return c->fail(CRT_ERR_INVALID, "crt_is_occluded: NULL buffer");
+    HIPCK(c, hipSetDevice(c->cfg.device));
+    if (n > c->queryCap) {                                                // the staging buffers of crt_find_nearest (a shadow ray is as large as a ray)
+        HIPCK(c, hipStreamSynchronize(c->stream));
+        if (c->dQueryRays) (void)hipFree(c->dQueryRays);
+        if (c->dQueryHits) (void)hipFree(c->dQueryHits);
+        c->dQueryRays = c->dQueryHits = nullptr; c->queryCap = 0;
+        HIPCK(c, hipMalloc(&c->dQueryRays, n * sizeof(crt_ray)));
+        HIPCK(c, hipMalloc(&c->dQueryHits, n * sizeof(crt_hit)));
+        c->queryCap = n;
+    }
+    HIPCK(c, hipMemcpyAsync(c->dQueryRays, rays, n * sizeof(crt_shadow_ray), hipMemcpyHostToDevice, c->stream));
+    int32_t* dOut = static_cast<int32_t*>(c->dQueryHits);
+    if (accel == 0) HIPCK(c, crt_launch_is_occluded(&c->hScene, c->dQueryRays, dOut, (uint32_t)n, c->ldsBytes, c->dQueryCursor, c->stream));
+    else HIPCK(c, crt_launch_is_occluded_alt(accel, &c->hScene, &c->alt, c->dQueryRays, dOut, (uint32_t)n, c->dQueryCursor, c->stream));
+    HIPCK(c, hipMemcpyAsync(occluded, dOut, n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     HIPCK(c, hipStreamSynchronize(c->stream));
     return CRT_OK;
 }

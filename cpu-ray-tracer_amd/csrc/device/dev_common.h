@@ -274,6 +274,24 @@ __device__ __forceinline__ void hit_light_floor(const Scene& sc, f3 O, f3 D, Hit
     hit_light_floor(lf, O, D, h);
 }
 
+// Quad::IsOccluded, primitives.h:347-362: the light quad bounded by the shadow ray's t (the general expressions, operation for operation as
+// whitted_occluded in kernels.hip); the scene queries' is_occluded kernels test it before any walk
+__device__ __forceinline__ bool quad_occluded(const Scene& sc, f3 O, f3 D, float tmax)
+{
+    const float* c = sc.lightInvT;
+    const float Oy = c[4] * O.x + c[5] * O.y + c[6] * O.z + c[7];
+    const float Dy = c[4] * D.x + c[5] * D.y + c[6] * D.z;
+    const float t = Oy / -Dy;
+    if (!(t < tmax && t > 0)) return false;
+    const float Ox = c[0] * O.x + c[1] * O.y + c[2] * O.z + c[3];
+    const float Oz = c[8] * O.x + c[9] * O.y + c[10] * O.z + c[11];
+    const float Dx = c[0] * D.x + c[1] * D.y + c[2] * D.z;
+    const float Dz = c[8] * D.x + c[9] * D.y + c[10] * D.z;
+    const float Ix = Ox + t * Dx, Iz = Oz + t * Dz;
+    const float size = sc.lightSize;
+    return Ix > -size && Ix < size && Iz > -size && Iz < size;
+}
+
 // Scene fields that only the shading passes need (the root's child pair, the camera, the light quad / floor plane: 50 dwords) are NOT held in scalar registers
 // across the render kernels' loops — with them render_pool_kernel spills ~50 SGPRs into VGPR lanes and pays v_readlane / v_writelane around every pass.  The passes re-read them from the
 // kernel-argument segment instead (the Scene block is the kernel's first argument: offset 0), through a pointer the optimiser cannot hoist: a few s_load_dwordx8/x16

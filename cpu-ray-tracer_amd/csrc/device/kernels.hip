@@ -690,6 +690,106 @@ __global__ __launch_bounds__(64) void find_nearest_kernel(const Scene sc, const 
 }
 
 // ------------------------------------------------------------------------------------------------------------
+// is_occluded_kernel: scene.IsOccluded for a buffer of shadow rays (file_scene.cpp:177-187, tlas_file_scene.cpp:208-218) over the BVH / TLAS, in
+// find_nearest_kernel's persistent-wave form.  The light quad bounded by the ray's t first (a lane whose ray it occludes is done without a walk), then the
+// reference's walk over the whole ray (shadow.t = 1e34f, no floor) in its order, STOPPED at the first successful triangle test: until that test the
+// reference's nearest-hit walk has ray.t == 1e34f, so every box decision up to it is this walk's; after it objIdx > -1 for good (DESIGN.md "Scene queries").
+// Counts nothing (the reference's IsOccluded does not count on its copy of the ray).
+// ------------------------------------------------------------------------------------------------------------
+struct ShadowRayIn { float O[3]; float D[3]; float t; };
+
+__global__ __launch_bounds__(64) void is_occluded_kernel(const Scene sc, const ShadowRayIn* __restrict__ rays, int32_t* __restrict__ occluded, uint32_t n,
+                                                          uint32_t* __restrict__ cursor)
+{
+    extern __shared__ uint32_t lds[];
+    const uint32_t lane = threadIdx.x;
+    const char* __restrict__ g = sc.geom;
+    uint32_t* stk = lds + lane;                                           // as find_nearest_kernel: BVH entries of this lane's column, TLAS entries above them
+    uint32_t* tstk = stk + sc.bvhStack * 64;
+    uint32_t mode = 0u;                                                   // 0 idle, 1 at a BVH reference, 2 inside a leaf, 3 at a TLAS reference, 4 finished
+    uint32_t idx = 0; f3 O = mk3(0, 0, 0), D = O, rD = O, Oo = O, Do = O, rDo = O;
+    Hit h; h.t = 1e34f; h.u = 0; h.v = 0; h.objIdx = -1; h.triIdx = -1;
+    uint32_t cur = 0, sp = 0, tcur = 0, tsp = 0, leafAt = 0;
+    bool more = true;
+    for (;;) {
+        const uint64_t mIdle = __builtin_amdgcn_ballot_w64(mode == 0u);
+        const uint32_t nIdle = (uint32_t)__popcll(mIdle);
+        if (more && nIdle >= kQueryRefill) {
+            uint32_t base = 0;
+            if (lane == 0) base = atomicAdd(cursor, nIdle);
+            base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
+            more = base + nIdle < n;
+            const uint32_t my = base + (uint32_t)__builtin_amdgcn_mbcnt_hi((uint32_t)(mIdle >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mIdle, 0u));
+            if (mode == 0u && my < n) {
+                idx = my;
+                const ShadowRayIn r = rays[idx];
+                O = mk3(r.O[0], r.O[1], r.O[2]); D = mk3(r.D[0], r.D[1], r.D[2]);
+                if (quad_occluded(sc, O, D, r.t)) occluded[idx] = 1;      // the lane stays idle
+                else {
+                    rD = mk3(1 / D.x, 1 / D.y, 1 / D.z);                  // Ray shadow(O, D) ctor, template/ray.h:15-24
+                    h.t = 1e34f; h.objIdx = -1;
+                    if (sc.kind == 0) { Oo = O; Do = D; rDo = rD; cur = sc.rootRef; sp = 0; mode = 1u; }
+                    else { tcur = sc.rootRef; tsp = 0; mode = 3u; }
+                }
+            }
+        }
+        if (__builtin_amdgcn_ballot_w64(mode != 0u) == 0ull) {
+            if (!more) break;
+            continue;                                                     // every drawn ray was quad-occluded: draw again
+        }
+        // ---------------- TLAS step (tlas_bvh.cpp:83-111) ----------------
+        if (mode == 3u) {
+            bool pop = false;
+            if ((tcur & kRefTlasLeaf) == kRefTlasLeaf) {
+                const uint32_t io = sc.instOff + (tcur & 0xffffu) * 128u;
+                const rec4 r0 = ldg(g, io), r1 = ldg(g, io + 16), r2 = ldg(g, io + 32), ids = ldg(g, io + 48);
+                to_object_space(r0, r1, r2, O, D, Oo, Do, rDo);
+                cur = asu(ids.z); sp = 0; mode = 1u;
+            } else {
+                const uint32_t o1 = sc.tlasOff + (tcur & 0x7fffu) * 32u, o2 = sc.tlasOff + ((tcur >> 15) & 0x7fffu) * 32u;
+                const rec4 alo = ldg(g, o1), ahi = ldg(g, o1 + 16), blo = ldg(g, o2), bhi = ldg(g, o2 + 16);
+                float d1 = box_exact(alo, ahi, O, rD, h.t), d2 = box_exact(blo, bhi, O, rD, h.t);
+                uint32_t r1 = asu(alo.w), r2 = asu(blo.w);
+                if (d1 > d2) { float td = d1; d1 = d2; d2 = td; uint32_t tr = r1; r1 = r2; r2 = tr; }
+                if (d1 == 1e30f) pop = true;
+                else { tcur = r1; if (d2 != 1e30f) { tstk[tsp * 64] = r2; tsp++; } }
+            }
+            if (pop) { if (tsp == 0) mode = 4u; else tcur = tstk[(--tsp) * 64]; }
+        }
+        // ---------------- BVH step (bvh.cpp:224-258) ----------------
+        bool back = false;
+        if (mode == 1u) {
+            const uint32_t off = (cur & kRefOffsetMask) << 4;
+            if (cur & kRefInterior) {
+                const rec4 alo = ldg(g, off), ahi = ldg(g, off + 16), blo = ldg(g, off + 32), bhi = ldg(g, off + 48);
+                float d1 = box_exact(alo, ahi, Oo, rDo, h.t), d2 = box_exact(blo, bhi, Oo, rDo, h.t);
+                uint32_t r1 = asu(alo.w), r2 = asu(blo.w);
+                if (d1 > d2) { float td = d1; d1 = d2; d2 = td; uint32_t tr = r1; r1 = r2; r2 = tr; }
+                if (d1 == 1e30f) back = true;
+                else { cur = r1; if (d2 != 1e30f) { stk[sp * 64] = r2; sp++; } }
+            } else { leafAt = off; mode = 2u; }
+        }
+        // ---------------- one triangle of the leaf (bvh.cpp:232-243); the first success ends the walk ----------------
+        if (mode == 2u) {
+            const rec4 a = ldg(g, leafAt), b = ldg(g, leafAt + 16), c = ldg(g, leafAt + 32);
+            hit_tri(a, b, c, Oo, Do, h);
+            if (h.objIdx > -1) mode = 4u;
+            else if (asu(c.w) <= 1u) { back = true; mode = 1u; } else leafAt += 48;
+        }
+        if (back) {
+            if (sp != 0) cur = stk[(--sp) * 64];
+            else if (sc.kind == 0) mode = 4u;
+            else if (tsp == 0) mode = 4u;
+            else { tcur = tstk[(--tsp) * 64]; mode = 3u; }
+        }
+        if (mode == 4u) {
+            occluded[idx] = h.objIdx > -1 ? 1 : 0;
+            mode = 0u;
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------
 // whitted_kernel: the reference's second front-end ("2. WhittedStyle/renderer.cpp":21-157) behind the same boundary.
 // Deterministic (no RNG), so one thread per pixel.  Trace()'s recursion (a dielectric spawns a refracted AND a
 // reflected ray) runs on an explicit frame stack in post-order, so every float sum and product happens in the
@@ -1045,6 +1145,18 @@ extern "C" hipError_t crt_launch_find_nearest(const crt::Scene* sc, const void* 
     const uint32_t need = (n + 63u) / 64u, fill = 256u * perCu;          // persistent wavefronts: the device full once, never more than the rays need
     dim3 grid(need < fill ? need : fill), block(64);
     hipLaunchKernelGGL(crt::find_nearest_kernel, grid, block, ldsBytes, stream, *sc, (const crt::RayIn*)rays, (crt::HitOut*)hits, n, counters, cursor);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t crt_launch_is_occluded(const crt::Scene* sc, const void* rays, int32_t* occluded, uint32_t n, uint32_t ldsBytes, uint32_t* cursor, hipStream_t stream)
+{
+    if (n == 0) return hipSuccess;
+    if (!cursor) return hipErrorInvalidValue;
+    if (hipMemsetAsync(cursor, 0, 4, stream) != hipSuccess) return hipGetLastError();
+    uint32_t perCu = ldsBytes ? (160u * 1024u) / ldsBytes : 16u; if (perCu > 16u) perCu = 16u; if (perCu < 4u) perCu = 4u;      // as crt_launch_find_nearest
+    const uint32_t need = (n + 63u) / 64u, fill = 256u * perCu;
+    dim3 grid(need < fill ? need : fill), block(64);
+    hipLaunchKernelGGL(crt::is_occluded_kernel, grid, block, ldsBytes, stream, *sc, (const crt::ShadowRayIn*)rays, occluded, n, cursor);
     return hipGetLastError();
 }
 

@@ -109,6 +109,15 @@ void BaseScene::FindNearest(Ray& ray)
     ray.traversed += h.traversed; ray.tested += h.tested;
 }
 
+bool BaseScene::IsOccluded(const Ray& ray)
+{
+    if (!bound) throw std::runtime_error("IsOccluded: scene not uploaded to a device context");
+    crt_shadow_ray r; int32_t occluded = 0;
+    r.O[0] = ray.O.x; r.O[1] = ray.O.y; r.O[2] = ray.O.z; r.D[0] = ray.D.x; r.D[1] = ray.D.y; r.D[2] = ray.D.z; r.t = ray.t;
+    check(bound, crt_is_occluded(bound, 0, &r, &occluded, 1), "crt_is_occluded");
+    return occluded != 0;
+}
+
 // ---- FileScene ---------------------------------------------------------------------------------------
 FileScene::FileScene(const std::string& filePath, const std::string& baseDir)
 {

@@ -42,6 +42,8 @@ public:
     int Update(crt_ctx* ctx, uint32_t what);
     // scene.FindNearest(ray): one ray through crt_find_nearest (use the batch ABI for many)
     void FindNearest(Ray& ray);
+    // scene.IsOccluded(ray): one shadow ray {O, D, t} through crt_is_occluded (light quad bounded by t, then the BVH / TLAS over the whole ray)
+    bool IsOccluded(const Ray& ray);
     float3 GetLightPos() const;
     float3 GetLightColor() const { return float3(24, 24, 22); }
     virtual int GetTriangleCount() const = 0;

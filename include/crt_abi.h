@@ -224,6 +224,33 @@ int  crt_find_nearest_alt(crt_ctx* ctx, int kind, const crt_ray* rays, crt_hit* 
  * exactly 0 (kdtree.cpp:161-201).  The sequential form (one wavefront per tile and 64-frame window); reset by crt_upload_scene / crt_upload_alt_accel of the kind. */
 int  crt_set_render_accel(crt_ctx* ctx, int kind);
 
+/* ---- scene queries: BaseScene::IsOccluded, and both queries on device buffers (base_scene.h:16-32) ------------------------------------------------
+ * accel: 0 = the scene's own structure (BVH / TLAS; for the nearest-hit query also the PrimitiveScene), CRT_ACCEL_KDTREE / CRT_ACCEL_GRID = the uploaded
+ * alternative accelerator (FileScene built with USE_KDTree / USE_Grid).
+ *
+ * IsOccluded (FileScene::IsOccluded / TLASFileScene::IsOccluded, file_scene.cpp:177-187, tlas_file_scene.cpp:208-218), bug-compatible: the light quad is tested
+ * bounded by ray.t (Quad::IsOccluded, primitives.h:347-362); then the acceleration structure is intersected over the WHOLE ray (shadow.t = 1e34f, not clipped at
+ * ray.t); the floor plane is not tested.  occluded[i] = 1 or 0.  The walk stops at the first successful triangle test, which gives exactly the answer of the
+ * reference's full nearest-hit walk (DESIGN.md "Scene queries").  A binding implements `bool IsOccluded(const Ray& ray)` as one crt_shadow_ray {ray.O, ray.D,
+ * ray.t} through crt_is_occluded.  The occlusion entries count nothing in crt_counters (the reference's IsOccluded never touches the caller's ray counters);
+ * PrimitiveScene: CRT_ERR_UNSUPPORTED.
+ *
+ * Device entries: d_* are device pointers on cfg.device (checked; a host or other-device pointer is CRT_ERR_INVALID); `stream` is a hipStream_t of that device
+ * (void* here, as this header takes no HIP types), NULL = the ctx's own stream.  They return once the work is enqueued and never wait on the host (except that
+ * a call which finds 64 device queries of this ctx still running waits for the oldest).  crt_find_nearest_device writes bit for bit the records of
+ * crt_find_nearest / crt_find_nearest_alt and counts into crt_counters as they do.
+ * Ordering contract of the device entries:
+ *   - a query sees the scene as of the last crt_upload_* / crt_update_scene call made before it (the caller's stream waits for those copies);
+ *   - a later crt_update_scene, crt_upload_scene / crt_upload_primitive_scene, crt_upload_alt_accel or crt_destroy does not rewrite or free memory that an
+ *     enqueued query still reads: crt_update_scene orders its copy behind every query in flight (no host wait), the others wait for them on the host;
+ *   - queries may be in flight on several streams at once (each launch draws its rays from a cursor of its own);
+ *   - the outputs are ready in stream order on `stream`: the caller orders its consumers (a kernel on the same stream needs no host synchronisation).
+ * All entries: n == 0 is a no-op; n > 2^31-1 is CRT_ERR_UNSUPPORTED; no scene, or an accelerator that was not uploaded, is CRT_ERR_STATE. */
+typedef struct crt_shadow_ray { float O[3]; float D[3]; float t; } crt_shadow_ray;   /* Ray with ray.t = t: the argument of IsOccluded (28 bytes, as crt_ray) */
+int  crt_is_occluded(crt_ctx* ctx, int accel, const crt_shadow_ray* rays, int32_t* occluded, size_t n);                       /* host pointers, synchronous */
+int  crt_find_nearest_device(crt_ctx* ctx, int accel, const crt_ray* d_rays, crt_hit* d_hits, size_t n, void* stream);
+int  crt_is_occluded_device(crt_ctx* ctx, int accel, const crt_shadow_ray* d_rays, int32_t* d_occluded, size_t n, void* stream);
+
 /* ---- PrimitiveScene (second half): infra/scene/primitive_scene.cpp — the reference's hard-coded demo room (six walls, swinging light quad,
  * bouncing mirror ball, "rounded corners" sphere, spinning glass cube, glass torus; template/primitives.h Sphere :31, Cube :187, Quad :321, Torus :380; the
  * SPEEDTRIX / single-light configuration its headers select).  The binding passes the scene as its constructor + SetTime(t) leave it: the members below.
