@@ -60,6 +60,25 @@ class SceneDescS(C.Structure):
                 ("floorN", C.c_float * 3), ("floorD", C.c_float), ("floorInvto", C.c_float)]
 
 
+class AltAccelS(C.Structure):
+    """crt_alt_accel: one KD-tree / grid description (pointers into numpy arrays the caller keeps alive)"""
+    _fields_ = [("kind", C.c_int32), ("triangles", C.c_void_p), ("triCount", C.c_uint32), ("kdNodes", C.c_void_p), ("kdNodeCount", C.c_uint32),
+                ("kdTriIndices", C.c_void_p), ("kdTriIndexCount", C.c_uint32), ("gridResolution", C.c_int32 * 3), ("gridCellSize", C.c_float * 3),
+                ("gridMin", C.c_float * 3), ("gridMax", C.c_float * 3), ("gridCellStart", C.c_void_p), ("gridCellTris", C.c_void_p), ("gridCellTriCount", C.c_uint32)]
+
+
+def alt_desc(kind, tris, s):
+    """AltAccelS for a structure `s` in the layout HostScene.build_alt / blas_alt return (kind = ACCEL_KDTREE / ACCEL_GRID, tris = its TRI_DTYPE array)"""
+    a = AltAccelS(); a.kind = int(kind); a.triangles = tris.ctypes.data; a.triCount = len(tris)
+    if kind == ACCEL_KDTREE:
+        a.kdNodes = s["nodes"].ctypes.data; a.kdNodeCount = len(s["nodes"]); a.kdTriIndices = s["refs"].ctypes.data if len(s["refs"]) else None; a.kdTriIndexCount = len(s["refs"])
+    else:
+        for k in range(3):
+            a.gridResolution[k] = int(s["resolution"][k]); a.gridCellSize[k] = float(s["cellSize"][k]); a.gridMin[k] = float(s["boundsMin"][k]); a.gridMax[k] = float(s["boundsMax"][k])
+        a.gridCellStart = s["cellStart"].ctypes.data; a.gridCellTris = s["refs"].ctypes.data if len(s["refs"]) else None; a.gridCellTriCount = len(s["refs"])
+    return a
+
+
 class CountersS(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("rays", "primary", "interior_iters", "leaf_iters", "tri_tests", "tlas_iters", "blas_visits", "mesh_hits")]
 
@@ -78,10 +97,10 @@ HIT_DTYPE = np.dtype([("t", "<f4"), ("u", "<f4"), ("v", "<f4"), ("objIdx", "<i4"
 SHADOW_RAY_DTYPE = np.dtype([("O", "<f4", 3), ("D", "<f4", 3), ("t", "<f4")])     # crt_shadow_ray: the argument of IsOccluded
 
 # every symbol include/crt_abi.h and include/crt_host.h declare (tests check the library exports all of them)
-ABI_SYMBOLS = ["crt_is_occluded", "crt_find_nearest_device", "crt_is_occluded_device", "crt_upload_primitive_scene", "crt_set_render_accel", "crt_upload_alt_accel", "crt_find_nearest_alt", "crt_update_scene", "crt_abi_version", "crt_device_count", "crt_create", "crt_destroy", "crt_last_error", "crt_upload_scene", "crt_set_camera",
+ABI_SYMBOLS = ["crt_upload_blas_accel", "crt_is_occluded", "crt_find_nearest_device", "crt_is_occluded_device", "crt_upload_primitive_scene", "crt_set_render_accel", "crt_upload_alt_accel", "crt_find_nearest_alt", "crt_update_scene", "crt_abi_version", "crt_device_count", "crt_create", "crt_destroy", "crt_last_error", "crt_upload_scene", "crt_set_camera",
                "crt_render", "crt_tick", "crt_reserve", "crt_whitted_tick", "crt_sync", "crt_clear", "crt_read_accumulator", "crt_resolve_screen", "crt_find_nearest", "crt_get_counters",
                "crt_reset_counters", "crt_get_timing", "crt_get_tile_clocks", "crt_bind_accumulator", "crt_accumulator_device_ptr"]
-HOST_SYMBOLS = ["crt_host_primitive_scene_create", "crt_host_primitive_scene_free", "crt_host_primitive_scene_set_time", "crt_host_primitive_scene_desc", "crt_host_primitive_scene_upload", "crt_host_scene_build_alt", "crt_host_scene_upload_alt", "crt_host_scene_alt_info", "crt_host_scene_alt_copy", "crt_host_scene_set_transform", "crt_host_scene_update", "crt_host_math_probe", "crt_host_vertex_dedup", "crt_host_last_error", "crt_host_scene_load", "crt_host_scene_free", "crt_host_scene_upload", "crt_host_scene_kind",
+HOST_SYMBOLS = ["crt_host_scene_blas_alt_info", "crt_host_scene_blas_alt_copy", "crt_host_primitive_scene_create", "crt_host_primitive_scene_free", "crt_host_primitive_scene_set_time", "crt_host_primitive_scene_desc", "crt_host_primitive_scene_upload", "crt_host_scene_build_alt", "crt_host_scene_upload_alt", "crt_host_scene_alt_info", "crt_host_scene_alt_copy", "crt_host_scene_set_transform", "crt_host_scene_update", "crt_host_math_probe", "crt_host_vertex_dedup", "crt_host_last_error", "crt_host_scene_load", "crt_host_scene_free", "crt_host_scene_upload", "crt_host_scene_kind",
                 "crt_host_scene_triangle_count", "crt_host_scene_bvh_count", "crt_host_scene_bvh_info", "crt_host_scene_bvh_copy",
                 "crt_host_scene_bvh_move_and_refit", "crt_host_scene_blas_transform", "crt_host_scene_tlas_copy", "crt_host_camera_state", "crt_host_renderer_create",
                 "crt_host_renderer_destroy", "crt_host_renderer_init", "crt_host_renderer_set_camera", "crt_host_renderer_set_passes",
@@ -241,6 +260,14 @@ class Context:
         hits = np.zeros(O.shape[0], HIT_DTYPE)
         self._ck(self.L.crt_find_nearest_alt(self.h, int(kind), _p(rays), _p(hits), C.c_size_t(O.shape[0])))
         return hits
+
+    def upload_blas_accel(self, kind, structs, tris):
+        """crt_upload_blas_accel: a two-level scene's BLASKDTree / BLASGrid set; structs[i] as HostScene.blas_alt returns them, tris[i] BLAS i's TRI_DTYPE array"""
+        keep = [(np.ascontiguousarray(t), {k: (np.ascontiguousarray(v) if isinstance(v, np.ndarray) else v) for k, v in st.items()}) for t, st in zip(tris, structs)]
+        arr = (AltAccelS * max(len(keep), 1))()
+        for i, (t, st) in enumerate(keep):
+            arr[i] = alt_desc(kind, t, st)
+        self._ck(self.L.crt_upload_blas_accel(self.h, int(kind), arr, C.c_uint32(len(keep))))
 
     def upload_desc(self, kind, bvhs, textures, floor_texture, sky_texture, materials, light_T, light_invT, light_size=0.5,
                     floor_n=(0, 1, 0), floor_d=1.0, floor_invto=None, obj_mat_idx=None, tlas_nodes=None, update_what=None):
@@ -464,17 +491,29 @@ class HostScene:
         self._ck(self.L.crt_host_scene_bvh_move_and_refit(self.h, int(i), _p(positions), C.c_uint32(positions.shape[0])))
 
     def build_alt(self, kind):
-        """KDTree::Build / Grid::Build over the FileScene's triangles on the host; returns the flattened structure (the layout crt_upload_alt_accel takes)"""
+        """KDTree::Build / Grid::Build over the FileScene's triangles on the host; returns the flattened structure (the layout crt_upload_alt_accel takes).
+        TLAS scene: BLASKDTree / BLASGrid per BLAS over its own triangles; returns the list of blas_alt(kind, i)."""
         self._ck(self.L.crt_host_scene_build_alt(self.h, int(kind)))
+        if self.kind == 1:
+            return [self.blas_alt(kind, i) for i in range(self.bvh_count())]
+        return self._alt(kind, lambda info: self.L.crt_host_scene_alt_info(self.h, int(kind), info),
+                         lambda a, b, c: self.L.crt_host_scene_alt_copy(self.h, int(kind), a, b, c))
+
+    def blas_alt(self, kind, i):
+        """BLAS i's BLASKDTree / BLASGrid of a TLAS scene (after build_alt), in build_alt's layout"""
+        return self._alt(kind, lambda info: self.L.crt_host_scene_blas_alt_info(self.h, int(kind), int(i), info),
+                         lambda a, b, c: self.L.crt_host_scene_blas_alt_copy(self.h, int(kind), int(i), a, b, c))
+
+    def _alt(self, kind, info_fn, copy_fn):
         info = (C.c_uint32 * 4)()
-        self._ck(self.L.crt_host_scene_alt_info(self.h, int(kind), info))
+        self._ck(info_fn(info))
         if kind == ACCEL_KDTREE:
             nodes = np.zeros(info[0], KD_NODE_DTYPE); refs = np.zeros(max(info[1], 1), np.uint32)
-            self._ck(self.L.crt_host_scene_alt_copy(self.h, int(kind), _p(nodes), _p(refs), None))
+            self._ck(copy_fn(_p(nodes), _p(refs), None))
             return dict(nodes=nodes, refs=refs[:info[1]], maxDepth=int(info[2]), nodesUsed=int(info[3]))
         res = np.array([info[0], info[1], info[2]], np.int32)
         start = np.zeros(int(res.prod()) + 1, np.uint32); refs = np.zeros(max(info[3], 1), np.int32); f = np.zeros(9, np.float32)
-        self._ck(self.L.crt_host_scene_alt_copy(self.h, int(kind), _p(start), _p(refs), _p(f)))
+        self._ck(copy_fn(_p(start), _p(refs), _p(f)))
         return dict(resolution=res, cellSize=f[0:3].copy(), boundsMin=f[3:6].copy(), boundsMax=f[6:9].copy(), cellStart=start, refs=refs[:info[3]])
 
     def upload_alt(self, ctx, kind):

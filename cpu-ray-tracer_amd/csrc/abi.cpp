@@ -28,8 +28,8 @@ extern "C" hipError_t crt_launch_probe(const crt::Scene*, uint32_t, uint32_t, ui
 extern "C" hipError_t crt_launch_accumulate(const void*, void*, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, hipStream_t);
 extern "C" hipError_t crt_launch_find_nearest(const crt::Scene*, const void*, void*, uint32_t, crt::Counters*, uint32_t, uint32_t*, hipStream_t);
 namespace crt { struct AltAccelDev; }
-extern "C" hipError_t crt_launch_whitted(const crt::Scene*, int, const crt::AltAccelDev*, void*, uint32_t*, crt::Counters*, uint32_t, hipStream_t);
-extern "C" hipError_t crt_launch_render_alt(int, const crt::Scene*, const crt::AltAccelDev*, void*, crt::Counters*, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, hipStream_t);
+extern "C" hipError_t crt_launch_whitted(const crt::Scene*, int, const crt::AltAccelDev*, const crt::TlasAltDev*, void*, uint32_t*, crt::Counters*, uint32_t, hipStream_t);
+extern "C" hipError_t crt_launch_render_alt(int, const crt::Scene*, const crt::AltAccelDev*, const crt::TlasAltDev*, void*, crt::Counters*, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, hipStream_t);
 extern "C" hipError_t crt_launch_resolve(const void*, uint32_t*, float*, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, float, hipStream_t);
 extern "C" hipError_t crt_launch_commit_frame(const void*, uint32_t, uint32_t, void*, uint32_t*, float*, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, float, hipStream_t);
 
@@ -59,6 +59,8 @@ extern "C" hipError_t crt_launch_check_reciprocals(unsigned long long*, hipStrea
 extern "C" hipError_t crt_launch_find_nearest_alt(int, const crt::Scene*, const crt::AltAccelDev*, const void*, void*, uint32_t, uint32_t*, hipStream_t);
 extern "C" hipError_t crt_launch_is_occluded(const crt::Scene*, const void*, int32_t*, uint32_t, uint32_t, uint32_t*, hipStream_t);
 extern "C" hipError_t crt_launch_is_occluded_alt(int, const crt::Scene*, const crt::AltAccelDev*, const void*, int32_t*, uint32_t, uint32_t*, hipStream_t);
+extern "C" hipError_t crt_launch_tlas_alt_query(int, bool, const crt::Scene*, const crt::TlasAltDev*, const void*, void*, uint32_t, uint32_t*, hipStream_t);
+static_assert(sizeof(crt::BlasAltDesc) == 72, "BLAS descriptor");
 static_assert(sizeof(crt_shadow_ray) == 28 && sizeof(crt_ray) == 28 && sizeof(crt_hit) == 28, "query records");
 
 namespace {
@@ -115,12 +117,17 @@ struct crt_ctx {
     bool haveScene = false;
     // what crt_update_scene needs of the last upload: a host mirror of the geometry buffer and where each BVH's records start
     struct Flat { int32_t kind = 0; uint64_t leafOff = 0, tlasOff = 0, tlasPairOff = 0, instOff = 0, shadeOff = 0; uint32_t tlasNodeCount = 0, maxHeight = 0;
-                  std::vector<uint64_t> pairBase, triBase; std::vector<uint32_t> nodesUsed, triCount; std::vector<char> geom; } flat;
+                  std::vector<uint64_t> pairBase, triBase; std::vector<uint32_t> nodesUsed, triCount; std::vector<char> geom;
+                  std::vector<float> rootBox; } flat;     // rootBox: every BVH's node 0 box (min xyz, max xyz), what crt_upload_blas_accel checks the BLAS structures against
     char* hStage[2] = {nullptr, nullptr}; size_t stageBytes[2] = {0, 0}; hipEvent_t stageCopied[2] = {nullptr, nullptr}; int stageFlip = 0;
     hipEvent_t sceneReady = nullptr;      // recorded behind the last in-place scene update; render launches wait for it on their stream
     bool havePrim = false; crt::PrimDev prim{}; uint32_t* dPrimTex = nullptr;       // crt_upload_primitive_scene: PrimitiveScene instead of a triangle scene
     int renderAccel = 0;                  // crt_set_render_accel: 0 = the scene's BVH / TLAS, CRT_ACCEL_KDTREE / CRT_ACCEL_GRID = Sample and Trace go through that structure
     crt::AltAccelDev alt{}; bool haveKd = false, haveGrid = false; std::vector<void*> altAllocs[2]; void* altTris = nullptr; uint32_t altTriCount = 0;   // KD-tree [0] / grid [1] buffers
+    // crt_upload_blas_accel: a two-level scene's BLASKDTree [0] / BLASGrid [1] set.  haveBlas is cleared by CRT_UPDATE_BOUNDS without a host wait; the buffers
+    // go with the next upload of the kind or of a scene, which wait for the queries first
+    crt::TlasAltDev blasAlt[2]{}; bool haveBlas[2] = {false, false}; std::vector<void*> blasAllocs[2];
+    bool hasAlt(int kind) const { return (kind == CRT_ACCEL_KDTREE && (haveKd || haveBlas[0])) || (kind == CRT_ACCEL_GRID && (haveGrid || haveBlas[1])); }
     void* dQueryRays = nullptr; void* dQueryHits = nullptr; size_t queryCap = 0;      // crt_find_nearest staging (rays)
     // Device-buffer queries (crt_find_nearest_device / crt_is_occluded_device) on callers' streams: each launch draws its rays from a cursor word of its own
     // (slot k at dQuerySlots + 16k, one cache line each), handed out as a ring; `done` is recorded on the caller's stream behind the launch, and a slot is
@@ -183,6 +190,7 @@ struct crt_ctx {
         for (auto& v : altAllocs) { for (void* p : v) (void)hipFree(p); v.clear(); }
         if (altTris) (void)hipFree(altTris);
         altTris = nullptr; altTriCount = 0; haveKd = haveGrid = false; alt = crt::AltAccelDev{}; renderAccel = 0;
+        for (int k = 0; k < 2; k++) { for (void* p : blasAllocs[k]) (void)hipFree(p); blasAllocs[k].clear(); haveBlas[k] = false; blasAlt[k] = crt::TlasAltDev{}; }
     }
     void freeScene()
     {
@@ -647,7 +655,8 @@ int crt_upload_scene(crt_ctx* c, const crt_scene_desc* sd)
         crt_ctx::Flat& f = c->flat;
         f.kind = sd->kind; f.leafOff = leafOffB; f.tlasOff = tlasOffB; f.tlasPairOff = tlasPairOffB; f.instOff = instOffB; f.shadeOff = shadeOffB;
         f.tlasNodeCount = (sd->kind == CRT_SCENE_TLAS) ? sd->tlasNodeCount : 0; f.maxHeight = maxHeight;
-        f.pairBase.clear(); f.triBase.clear(); f.nodesUsed.clear(); f.triCount.clear();
+        f.pairBase.clear(); f.triBase.clear(); f.nodesUsed.clear(); f.triCount.clear(); f.rootBox.clear();
+        for (uint32_t bi = 0; bi < sd->bvhCount; bi++) { const crt_bvh_node& r = sd->bvhs[bi].nodes[0]; f.rootBox.insert(f.rootBox.end(), r.aabbMin, r.aabbMin + 3); f.rootBox.insert(f.rootBox.end(), r.aabbMax, r.aabbMax + 3); }
         uint64_t pb = 0, tb = 0;
         for (uint32_t bi = 0; bi < sd->bvhCount; bi++) { f.pairBase.push_back(pb); f.triBase.push_back(tb); f.nodesUsed.push_back(sd->bvhs[bi].nodesUsed); f.triCount.push_back(sd->bvhs[bi].triCount); pb += sd->bvhs[bi].nodesUsed / 2; tb += sd->bvhs[bi].triCount; }
         f.geom.swap(geom);
@@ -772,6 +781,9 @@ int crt_update_scene(crt_ctx* c, const crt_scene_desc* sd, uint32_t what)
             }
         }
         touch(0, (size_t)f.tlasOff);
+        for (uint32_t bi = 0; bi < sd->bvhCount; bi++) { memcpy(&f.rootBox[6 * bi], sd->bvhs[bi].nodes[0].aabbMin, 12); memcpy(&f.rootBox[6 * bi + 3], sd->bvhs[bi].nodes[0].aabbMax, 12); }
+        // the reference has no Refit for BLASKDTree / BLASGrid: a refit drops the two-level KD-tree / grid sets (their buffers are freed by the next upload)
+        for (int k = 0; k < 2; k++) if (c->haveBlas[k]) { c->haveBlas[k] = false; if (c->renderAccel == k + 1) c->renderAccel = 0; }
     }
     if (f.kind == CRT_SCENE_TLAS) {
         if (what & CRT_UPDATE_TRANSFORMS) {
@@ -1582,7 +1594,7 @@ int crt_render(crt_ctx* c, uint32_t spp_first, uint32_t frames, uint32_t passes)
             if (c->sceneReady) HIPCK(c, hipStreamWaitEvent(c->stream, c->sceneReady, 0));
             void* slab = c->pool + off;
             if (c->havePrim) HIPCK(c, crt_launch_render_prim(&c->hScene, &c->prim, slab, c->dCounters, c->tileFirst, c->tileStride, c->tileCount, (uint32_t)c->tilesX, spp_first + f0 * passes, nf, passes, c->stream));
-            else HIPCK(c, crt_launch_render_alt(c->renderAccel, &c->hScene, &c->alt, slab, c->dCounters, c->tileFirst, c->tileStride, c->tileCount, (uint32_t)c->tilesX, spp_first + f0 * passes, nf, passes, c->stream));
+            else HIPCK(c, crt_launch_render_alt(c->renderAccel, &c->hScene, &c->alt, &c->blasAlt[c->renderAccel - 1], slab, c->dCounters, c->tileFirst, c->tileStride, c->tileCount, (uint32_t)c->tilesX, spp_first + f0 * passes, nf, passes, c->stream));
             HIPCK(c, crt_launch_accumulate(slab, c->dAcc, c->tileFirst, c->tileStride, c->tileCount, (uint32_t)c->tilesX, (uint32_t)c->cfg.width, nf, passes, c->stream));
             crt_ctx::Region reg; reg.off = off; reg.bytes = (size_t)((nf + 63u) / 64u) * windowBytes;
             if (c->freeEvents.empty()) HIPCK(c, hipEventCreateWithFlags(&reg.freed, hipEventDisableTiming));
@@ -1726,7 +1738,7 @@ int crt_whitted_tick(crt_ctx* c, uint32_t* hostPixels)
     if (!c) return CRT_ERR_INVALID;
     if (!c->haveScene) return c->fail(CRT_ERR_STATE, "crt_whitted_tick before crt_upload_scene");
     HIPCK(c, hipSetDevice(c->cfg.device));
-    HIPCK(c, crt_launch_whitted(&c->hScene, c->renderAccel, &c->alt, c->dAcc, c->dPixels, c->dCounters, c->ldsBytes, c->stream));
+    HIPCK(c, crt_launch_whitted(&c->hScene, c->renderAccel, &c->alt, c->renderAccel ? &c->blasAlt[c->renderAccel - 1] : nullptr, c->dAcc, c->dPixels, c->dCounters, c->ldsBytes, c->stream));
     if (hostPixels) HIPCK(c, hipMemcpyAsync(hostPixels, c->dPixels, (size_t)c->cfg.width * c->cfg.height * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCK(c, hipStreamSynchronize(c->stream));
     return CRT_OK;
@@ -1758,16 +1770,11 @@ int crt_find_nearest(crt_ctx* c, const crt_ray* rays, crt_hit* hits, size_t n)
     return CRT_OK;
 }
 
-// FileScene's KD-tree / uniform grid over the scene's triangles, for crt_find_nearest_alt
-int crt_upload_alt_accel(crt_ctx* c, const crt_alt_accel* a)
+// the checks of one KD-tree / grid description (crt_upload_alt_accel, and every BLAS's of crt_upload_blas_accel); kdHeight: the KD-tree's height
+static int check_alt_accel(crt_ctx* c, const crt_alt_accel* a, uint32_t* kdHeightOut)
 {
-    if (!c || !a) return CRT_ERR_INVALID;
-    if (!c->haveScene || c->hScene.kind != CRT_SCENE_FILE) return c->fail(CRT_ERR_STATE, "crt_upload_alt_accel needs an uploaded CRT_SCENE_FILE scene (light quad, floor plane, materials)");
     if (a->kind != CRT_ACCEL_KDTREE && a->kind != CRT_ACCEL_GRID) return c->fail(CRT_ERR_INVALID, "unknown accelerator kind %d", a->kind);
     if (!a->triangles || a->triCount == 0) return c->fail(CRT_ERR_INVALID, "accelerator has no triangles");
-    c->epoch++;
-    HIPCK(c, hipSetDevice(c->cfg.device));
-    const int slot = a->kind == CRT_ACCEL_KDTREE ? 0 : 1;
     uint32_t kdHeight = 0;
     if (a->kind == CRT_ACCEL_KDTREE) {
         if (!a->kdNodes || a->kdNodeCount == 0 || (a->kdTriIndexCount && !a->kdTriIndices)) return c->fail(CRT_ERR_INVALID, "KD-tree arrays missing");
@@ -1792,6 +1799,20 @@ int crt_upload_alt_accel(crt_ctx* c, const crt_alt_accel* a)
         for (uint64_t i = 0; i < cells; i++) if (a->gridCellStart[i] > a->gridCellStart[i + 1]) return c->fail(CRT_ERR_INVALID, "gridCellStart is not monotone at cell %llu", (unsigned long long)i);
         for (uint32_t i = 0; i < a->gridCellTriCount; i++) if (a->gridCellTris[i] < 0 || (uint32_t)a->gridCellTris[i] >= a->triCount) return c->fail(CRT_ERR_INVALID, "gridCellTris[%u] out of range", i);
     }
+    *kdHeightOut = kdHeight;
+    return 0;
+}
+
+// FileScene's KD-tree / uniform grid over the scene's triangles, for crt_find_nearest_alt
+int crt_upload_alt_accel(crt_ctx* c, const crt_alt_accel* a)
+{
+    if (!c || !a) return CRT_ERR_INVALID;
+    if (!c->haveScene || c->hScene.kind != CRT_SCENE_FILE) return c->fail(CRT_ERR_STATE, "crt_upload_alt_accel needs an uploaded CRT_SCENE_FILE scene (light quad, floor plane, materials)");
+    uint32_t kdHeight = 0;
+    { const int r = check_alt_accel(c, a, &kdHeight); if (r) return r; }
+    c->epoch++;
+    HIPCK(c, hipSetDevice(c->cfg.device));
+    const int slot = a->kind == CRT_ACCEL_KDTREE ? 0 : 1;
     HIPCK(c, hipStreamSynchronize(c->stream));                            // queries of the previous structure
     { const int r = wait_queries(c); if (r) return r; }                  // ... also those on callers' streams
     for (void* p : c->altAllocs[slot]) (void)hipFree(p);
@@ -1836,6 +1857,95 @@ int crt_upload_alt_accel(crt_ctx* c, const crt_alt_accel* a)
     return CRT_OK;
 }
 
+// TLASFileScene built with TLAS_USE_KDTree / TLAS_USE_Grid: one BLASKDTree / BLASGrid per BLAS of the uploaded two-level scene, for the queries and the render path
+int crt_upload_blas_accel(crt_ctx* c, int kind, const crt_alt_accel* blas, uint32_t blasCount)
+{
+    if (!c) return CRT_ERR_INVALID;
+    if (!c->haveScene || c->hScene.kind != CRT_SCENE_TLAS) return c->fail(CRT_ERR_STATE, "crt_upload_blas_accel needs an uploaded CRT_SCENE_TLAS scene");
+    if (kind != CRT_ACCEL_KDTREE && kind != CRT_ACCEL_GRID) return c->fail(CRT_ERR_INVALID, "unknown accelerator kind %d", kind);
+    const crt_ctx::Flat& f = c->flat;
+    if (!blas || blasCount != (uint32_t)f.triCount.size()) return c->fail(CRT_ERR_INVALID, "crt_upload_blas_accel: %u structures for a scene of %zu BLAS", blasCount, f.triCount.size());
+    // ---- every check first: a refused upload leaves the previous set answering ----
+    const crt::Instance* inst = reinterpret_cast<const crt::Instance*>(f.geom.data() + f.instOff);
+    uint32_t maxKd = 0; uint64_t nNodes = 0, nRefs = 0, nTris = 0, nCells = 0, nCellRefs = 0;
+    for (uint32_t b = 0; b < blasCount; b++) {
+        const crt_alt_accel& a = blas[b];
+        if (a.kind != kind) return c->fail(CRT_ERR_INVALID, "BLAS %u: structure of kind %d in a set of kind %d", b, a.kind, kind);
+        uint32_t h = 0;
+        { const int r = check_alt_accel(c, &a, &h); if (r) return r; }
+        if (a.triCount != f.triCount[b]) return c->fail(CRT_ERR_INVALID, "BLAS %u: %u triangles, the uploaded BLAS has %u", b, a.triCount, f.triCount[b]);
+        for (uint32_t t = 0; t < a.triCount; t++)
+            if (a.triangles[t].objIdx != inst[b].objIdx) return c->fail(CRT_ERR_INVALID, "BLAS %u: triangle %u has objIdx %d, the BLAS %d", b, t, a.triangles[t].objIdx, inst[b].objIdx);
+        // SetTransform takes the world bounds from this box (blas_kdtree.cpp:407-418, blas_grid.cpp:267-278): the shared TLAS is the variant's only if it is the BVH's
+        float box[6];
+        if (kind == CRT_ACCEL_KDTREE) { memcpy(box, a.kdNodes[0].aabbMin, 12); memcpy(box + 3, a.kdNodes[0].aabbMax, 12); }
+        else { memcpy(box, a.gridMin, 12); memcpy(box + 3, a.gridMax, 12); }
+        if (memcmp(box, &f.rootBox[6 * b], 24) != 0) return c->fail(CRT_ERR_INVALID, "BLAS %u: root box differs from the BLAS's BVH root box (the TLAS is shared)", b);
+        if (kind == CRT_ACCEL_KDTREE) { if (h + 1 > maxKd) maxKd = h + 1; nNodes += a.kdNodeCount; nRefs += a.kdTriIndexCount; }
+        else { nCells += (uint64_t)a.gridResolution[0] * a.gridResolution[1] * a.gridResolution[2] + 1; nCellRefs += a.gridCellTriCount; }
+        nTris += a.triCount;
+    }
+    const uint32_t words = maxKd * 2u + (c->hScene.stackDepth - c->hScene.bvhStack);      // KD stack + TLAS entries + the return marker, per lane
+    if (words * 64u * 4u > 64u * 1024u) return c->fail(CRT_ERR_UNSUPPORTED, "TLAS + KD-tree traversal stack of %u dwords per lane exceeds the LDS budget", words);
+    if (nNodes > 0xffffffffull || nRefs > 0xffffffffull || nTris > 0xffffffffull || nCells > 0xffffffffull || nCellRefs > 0xffffffffull) return c->fail(CRT_ERR_UNSUPPORTED, "BLAS set too large");
+    // ---- flatten: concatenated arrays + one descriptor per BLAS ----
+    std::vector<crt::BlasAltDesc> desc(blasCount);
+    std::vector<crt_kd_node> nodes; std::vector<uint32_t> refs, cellStart; std::vector<int32_t> cellRefs; std::vector<float> tris((size_t)nTris * 12);
+    uint32_t tb = 0;
+    for (uint32_t b = 0; b < blasCount; b++) {
+        const crt_alt_accel& a = blas[b];
+        crt::BlasAltDesc& d = desc[b]; memset(&d, 0, sizeof(d));
+        d.nodeBase = (uint32_t)nodes.size(); d.refBase = (uint32_t)refs.size(); d.triBase = tb; d.cellBase = (uint32_t)cellStart.size(); d.cellRefBase = (uint32_t)cellRefs.size();
+        d.objIdx = inst[b].objIdx;
+        if (kind == CRT_ACCEL_KDTREE) { nodes.insert(nodes.end(), a.kdNodes, a.kdNodes + a.kdNodeCount); refs.insert(refs.end(), a.kdTriIndices, a.kdTriIndices + a.kdTriIndexCount); }
+        else {
+            const uint64_t cells = (uint64_t)a.gridResolution[0] * a.gridResolution[1] * a.gridResolution[2];
+            cellStart.insert(cellStart.end(), a.gridCellStart, a.gridCellStart + cells + 1); cellRefs.insert(cellRefs.end(), a.gridCellTris, a.gridCellTris + a.gridCellTriCount);
+            for (int k = 0; k < 3; k++) { d.res[k] = a.gridResolution[k]; d.cell[k] = a.gridCellSize[k]; d.lo[k] = a.gridMin[k]; d.hi[k] = a.gridMax[k]; }
+        }
+        for (uint32_t i = 0; i < a.triCount; i++) {                      // AltTri: Möller–Trumbore operands, triIdx = the global shade index (shadeBase + BLAS-local index)
+            const crt_tri& t = a.triangles[i]; float* o = &tris[(size_t)(tb + i) * 12];
+            for (int k = 0; k < 3; k++) { o[k] = t.vertex0[k]; o[4 + k] = t.vertex1[k] - t.vertex0[k]; o[8 + k] = t.vertex2[k] - t.vertex0[k]; }
+            const uint32_t shade = inst[b].shadeBase + i; memcpy(&o[3], &shade, 4); memcpy(&o[7], &t.objIdx, 4); o[11] = 0;
+        }
+        tb += a.triCount;
+    }
+    // ---- replace the set of this kind (synchronous): queries and render launches that read the previous one finish first ----
+    HIPCK(c, hipSetDevice(c->cfg.device));
+    for (auto st : c->streams) HIPCK(c, hipStreamSynchronize(st));
+    if (c->aheadStream) HIPCK(c, hipStreamSynchronize(c->aheadStream));
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    { const int r = wait_queries(c); if (r) return r; }
+    // the new set goes into buffers of its own; only once every copy has succeeded does it replace the previous one (a failed allocation or copy keeps that)
+    std::vector<void*> allocs;
+    crt::TlasAltDev tl{};
+    auto up = [&](const void* src, size_t bytes, const void** out) -> int {
+        *out = nullptr; if (!bytes) return 0;
+        void* d = nullptr; HIPCK(c, hipMalloc(&d, bytes)); allocs.push_back(d);
+        HIPCK(c, hipMemcpy(d, src, bytes, hipMemcpyHostToDevice)); *out = d; return 0;
+    };
+    auto flatten = [&]() -> int {
+        const void* p = nullptr; int r;
+        if ((r = up(desc.data(), desc.size() * sizeof(crt::BlasAltDesc), &p))) return r; tl.desc = (const crt::BlasAltDesc*)p;
+        if ((r = up(tris.data(), tris.size() * 4, &tl.tris))) return r;
+        if ((r = up(nodes.data(), nodes.size() * sizeof(crt_kd_node), &tl.kdNodes))) return r;
+        if ((r = up(refs.data(), refs.size() * 4, &p))) return r; tl.kdRefs = (const uint32_t*)p;
+        if ((r = up(cellStart.data(), cellStart.size() * 4, &p))) return r; tl.cellStart = (const uint32_t*)p;
+        if ((r = up(cellRefs.data(), cellRefs.size() * 4, &p))) return r; tl.cellRefs = (const int32_t*)p;
+        return 0;
+    };
+    if (const int r = flatten()) { for (void* p : allocs) (void)hipFree(p); return r; }
+    tl.kdStack = maxKd;
+    const int slot = kind - 1;
+    c->epoch++;
+    for (void* p : c->blasAllocs[slot]) (void)hipFree(p);
+    c->blasAllocs[slot].swap(allocs); c->blasAlt[slot] = tl; c->haveBlas[slot] = true;
+    if (c->renderAccel == kind) c->renderAccel = 0;                       // as crt_upload_alt_accel: the render goes back to the BVH until crt_set_render_accel
+    if (!c->altReady) HIPCK(c, hipEventCreateWithFlags(&c->altReady, hipEventDisableTiming));
+    HIPCK(c, hipEventRecord(c->altReady, nullptr));                       // behind the copies above: device queries on other streams wait for it
+    return CRT_OK;
+}
+
 int crt_upload_primitive_scene(crt_ctx* c, const crt_primitive_scene* ps)
 {
     if (!c || !ps) return CRT_ERR_INVALID;
@@ -1868,16 +1978,27 @@ int crt_set_render_accel(crt_ctx* c, int kind)
 {
     if (!c) return CRT_ERR_INVALID;
     if (kind != 0 && kind != CRT_ACCEL_KDTREE && kind != CRT_ACCEL_GRID) return c->fail(CRT_ERR_INVALID, "crt_set_render_accel: unknown accelerator kind %d", kind);
-    if ((kind == CRT_ACCEL_KDTREE && !c->haveKd) || (kind == CRT_ACCEL_GRID && !c->haveGrid)) return c->fail(CRT_ERR_STATE, "crt_set_render_accel: no such accelerator uploaded (kind %d)", kind);
-    if (kind != 0 && (c->alt.kdStack * 2u + 15u) * 64u * 4u * 4u > 64u * 1024u) return c->fail(CRT_ERR_UNSUPPORTED, "KD-tree height %u exceeds the render kernel's LDS stack", c->alt.kdStack);
+    if (kind != 0 && !c->hasAlt(kind)) return c->fail(CRT_ERR_STATE, "crt_set_render_accel: no such accelerator uploaded (kind %d)", kind);
+    if (kind != 0 && c->hScene.kind == CRT_SCENE_TLAS) {
+        const uint32_t words = c->blasAlt[kind - 1].kdStack * 2u + (c->hScene.stackDepth - c->hScene.bvhStack);
+        if ((words + 15u) * 64u * 4u * 4u > 64u * 1024u) return c->fail(CRT_ERR_UNSUPPORTED, "TLAS + KD-tree stack of %u dwords exceeds the render kernel's LDS stack", words);
+    } else if (kind != 0 && (c->alt.kdStack * 2u + 15u) * 64u * 4u * 4u > 64u * 1024u) return c->fail(CRT_ERR_UNSUPPORTED, "KD-tree height %u exceeds the render kernel's LDS stack", c->alt.kdStack);
     c->renderAccel = kind; c->epoch++;
     return CRT_OK;
+}
+
+// FindNearest / IsOccluded through an alternative accelerator: FileScene's structure, or a two-level scene's BLAS set
+static hipError_t launch_alt_query(crt_ctx* c, int kind, bool occl, const void* rays, void* out, uint32_t n, uint32_t* cursor, hipStream_t st)
+{
+    if (c->hScene.kind == CRT_SCENE_TLAS) return crt_launch_tlas_alt_query(kind, occl, &c->hScene, &c->blasAlt[kind - 1], rays, out, n, cursor, st);
+    if (occl) return crt_launch_is_occluded_alt(kind, &c->hScene, &c->alt, rays, static_cast<int32_t*>(out), n, cursor, st);
+    return crt_launch_find_nearest_alt(kind, &c->hScene, &c->alt, rays, out, n, cursor, st);
 }
 
 int crt_find_nearest_alt(crt_ctx* c, int kind, const crt_ray* rays, crt_hit* hits, size_t n)
 {
     if (!c || (n && (!rays || !hits))) return CRT_ERR_INVALID;
-    if (!((kind == CRT_ACCEL_KDTREE && c->haveKd) || (kind == CRT_ACCEL_GRID && c->haveGrid))) return c->fail(CRT_ERR_STATE, "crt_find_nearest_alt: no such accelerator uploaded (kind %d)", kind);
+    if (!c->hasAlt(kind)) return c->fail(CRT_ERR_STATE, "crt_find_nearest_alt: no such accelerator uploaded (kind %d)", kind);
     if (n == 0) return CRT_OK;
     if (n > 0x7fffffffull) return c->fail(CRT_ERR_UNSUPPORTED, "at most 2^31-1 rays per call");
     HIPCK(c, hipSetDevice(c->cfg.device));
@@ -1891,7 +2012,7 @@ int crt_find_nearest_alt(crt_ctx* c, int kind, const crt_ray* rays, crt_hit* hit
         c->queryCap = n;
     }
     HIPCK(c, hipMemcpyAsync(c->dQueryRays, rays, n * sizeof(crt_ray), hipMemcpyHostToDevice, c->stream));
-    HIPCK(c, crt_launch_find_nearest_alt(kind, &c->hScene, &c->alt, c->dQueryRays, c->dQueryHits, (uint32_t)n, c->dQueryCursor, c->stream));
+    HIPCK(c, launch_alt_query(c, kind, false, c->dQueryRays, c->dQueryHits, (uint32_t)n, c->dQueryCursor, c->stream));
     HIPCK(c, hipMemcpyAsync(hits, c->dQueryHits, n * sizeof(crt_hit), hipMemcpyDeviceToHost, c->stream));
     HIPCK(c, hipStreamSynchronize(c->stream));
     return CRT_OK;
@@ -1905,7 +2026,7 @@ static int query_check(crt_ctx* c, int accel, bool occl, size_t n, const char* w
     if (accel == 0) {
         if (occl && c->havePrim) return c->fail(CRT_ERR_UNSUPPORTED, "%s: IsOccluded over the PrimitiveScene is not supported (crt_whitted_tick refuses it too)", what);
         if (!c->haveScene && !c->havePrim) return c->fail(CRT_ERR_STATE, "%s before crt_upload_scene", what);
-    } else if (!((accel == CRT_ACCEL_KDTREE && c->haveKd) || (accel == CRT_ACCEL_GRID && c->haveGrid))) {
+    } else if (!c->hasAlt(accel)) {
         return c->fail(CRT_ERR_STATE, "%s: no such accelerator uploaded (kind %d)", what, accel);
     }
     if (n > 0x7fffffffull) return c->fail(CRT_ERR_UNSUPPORTED, "%s: at most 2^31-1 rays per call", what);
@@ -1971,9 +2092,9 @@ static int query_device(crt_ctx* c, bool occl, int accel, const void* dRays, voi
     uint32_t* cursor = c->dQuerySlots + 16 * k;
     if (occl) {
         if (accel == 0) HIPCK(c, crt_launch_is_occluded(&c->hScene, dRays, static_cast<int32_t*>(dOut), (uint32_t)n, c->ldsBytes, cursor, st));
-        else HIPCK(c, crt_launch_is_occluded_alt(accel, &c->hScene, &c->alt, dRays, static_cast<int32_t*>(dOut), (uint32_t)n, cursor, st));
+        else HIPCK(c, launch_alt_query(c, accel, true, dRays, dOut, (uint32_t)n, cursor, st));
     } else if (accel != 0) {
-        HIPCK(c, crt_launch_find_nearest_alt(accel, &c->hScene, &c->alt, dRays, dOut, (uint32_t)n, cursor, st));
+        HIPCK(c, launch_alt_query(c, accel, false, dRays, dOut, (uint32_t)n, cursor, st));
     } else if (c->havePrim) {
         HIPCK(c, crt_launch_find_nearest_prim(&c->prim, dRays, dOut, (uint32_t)n, st));
     } else {
@@ -2017,7 +2138,7 @@ int crt_is_occluded(crt_ctx* c, int accel, const crt_shadow_ray* rays, int32_t* 
     HIPCK(c, hipMemcpyAsync(c->dQueryRays, rays, n * sizeof(crt_shadow_ray), hipMemcpyHostToDevice, c->stream));
     int32_t* dOut = static_cast<int32_t*>(c->dQueryHits);
     if (accel == 0) HIPCK(c, crt_launch_is_occluded(&c->hScene, c->dQueryRays, dOut, (uint32_t)n, c->ldsBytes, c->dQueryCursor, c->stream));
-    else HIPCK(c, crt_launch_is_occluded_alt(accel, &c->hScene, &c->alt, c->dQueryRays, dOut, (uint32_t)n, c->dQueryCursor, c->stream));
+    else HIPCK(c, launch_alt_query(c, accel, true, c->dQueryRays, dOut, (uint32_t)n, c->dQueryCursor, c->stream));
     HIPCK(c, hipMemcpyAsync(occluded, dOut, n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     HIPCK(c, hipStreamSynchronize(c->stream));
     return CRT_OK;

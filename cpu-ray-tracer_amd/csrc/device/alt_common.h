@@ -37,8 +37,11 @@ __device__ __forceinline__ void alt_tri(const AltTri* __restrict__ tris, uint32_
 __device__ __forceinline__ float comp(f3 v, int a) { return a == 0 ? v.x : (a == 1 ? v.y : v.z); }
 
 // KDTree::Intersect: IntersectKDTree(ray, root) with the recursion turned into a stack of (far child, plane distance) in this lane's LDS column:
-// node index at stk[k * 128], its plane distance at stk[k * 128 + 64]; the `if (ray.t < t) return` of the caller frame is applied at pop time
-__device__ __forceinline__ void kd_intersect(const AltAccelDev& acc, f3 O, f3 D, f3 rD, Hit& h, uint32_t* stkNode, int& traversed, int& tested)
+// node index at stk[k * 128], its plane distance at stk[k * 128 + 64]; the `if (ray.t < t) return` of the caller frame is applied at pop time.
+// BLAS = true is BLASKDTree::IntersectKDTree (infra/blas_kdtree.cpp:336-398), whose caller frame returns only if the nearest hit so far is its own BLAS's:
+// `if (ray.objIdx == objIdx && ray.t < t) return;` (:377, :396) — "rule 1".  ANY = true stops at the first successful triangle test (IsOccluded).
+template <bool BLAS = false, bool ANY = false>
+__device__ __forceinline__ void kd_intersect(const AltAccelDev& acc, f3 O, f3 D, f3 rD, Hit& h, uint32_t* stkNode, int& traversed, int& tested, int objIdx = 0)
 {
     uint32_t sp = 0; int32_t node = 0;
     for (;;) {
@@ -49,7 +52,7 @@ __device__ __forceinline__ void kd_intersect(const AltAccelDev& acc, f3 O, f3 D,
         float tmin, tmax;
         if (alt_box(nd.lo, nd.hi, O, rD, h.t, tmin, tmax)) {
             if (nd.left < 0) {
-                for (uint32_t k = 0; k < nd.triCount; k++) { alt_tri(acc.tris, acc.kdRefs[nd.firstTri + k], O, D, h); tested++; }
+                for (uint32_t k = 0; k < nd.triCount; k++) { alt_tri(acc.tris, acc.kdRefs[nd.firstTri + k], O, D, h); tested++; if (ANY && h.objIdx > -1) return; }
             } else {
                 const int axis = nd.splitAxis;
                 const float splitPos = nd.lo[axis] + nd.splitDistance;
@@ -68,14 +71,16 @@ __device__ __forceinline__ void kd_intersect(const AltAccelDev& acc, f3 O, f3 D,
         while (sp > 0) {
             sp--;
             const float t = asf(stkNode[sp * 128u + 64u]);
-            if (h.t < t) continue;
+            if (BLAS ? (h.objIdx == objIdx && h.t < t) : (h.t < t)) continue;
             node = (int32_t)stkNode[sp * 128u]; found = true; break;
         }
         if (!found) break;
     }
 }
 
-// Grid::Intersect: IntersectGrid, grid.cpp:89-153 (3D-DDA over the cells the ray crosses)
+// Grid::Intersect: IntersectGrid, grid.cpp:89-153 (3D-DDA over the cells the ray crosses).  BLASGrid::IntersectGrid (blas_grid.cpp:180-231) is the same walk;
+// its hit ids come with the triangle records.  ANY = true stops at the first successful triangle test (IsOccluded).
+template <bool ANY = false>
 __device__ __forceinline__ void grid_intersect(const AltAccelDev& acc, f3 O, f3 D, f3 rD, Hit& h, int& traversed, int& tested)
 {
     float tmn, tmx;
@@ -92,7 +97,7 @@ __device__ __forceinline__ void grid_intersect(const AltAccelDev& acc, f3 O, f3 
         traversed++;
         const uint32_t index = (uint32_t)c[0] + (uint32_t)c[1] * (uint32_t)acc.res[0] + (uint32_t)c[2] * (uint32_t)acc.res[0] * (uint32_t)acc.res[1];
         const uint32_t e = acc.cellStart[index + 1];
-        for (uint32_t k = acc.cellStart[index]; k < e; k++) { tested++; alt_tri(acc.tris, (uint32_t)acc.cellRefs[k], O, D, h); }
+        for (uint32_t k = acc.cellStart[index]; k < e; k++) { tested++; alt_tri(acc.tris, (uint32_t)acc.cellRefs[k], O, D, h); if (ANY && h.objIdx > -1) return; }
         const uint32_t k = ((uint32_t)(next[0] < next[1]) << 2) + ((uint32_t)(next[0] < next[2]) << 1) + (uint32_t)(next[1] < next[2]);
         const int axis = (0x00221212u >> (4u * k)) & 0xfu;                 // map[8] = {2, 1, 2, 1, 2, 2, 0, 0}, grid.cpp:141
         const float nx = axis == 0 ? next[0] : (axis == 1 ? next[1] : next[2]);
@@ -103,6 +108,48 @@ __device__ __forceinline__ void grid_intersect(const AltAccelDev& acc, f3 O, f3 
         else { c[2] += step[2]; out = c[2] == exitc[2]; next[2] += deltaT[2]; }
         if (out) break;
     }
+}
+
+// ---- two-level scenes: TLASKDTree / TLASGrid over BLASKDTree / BLASGrid (tlas_file_scene.cpp:40-90 with TLAS_USE_KDTree / TLAS_USE_Grid) ----
+// BLAS b of a set as the FileScene walks above see a structure: its slices of the concatenated arrays
+__device__ __forceinline__ AltAccelDev blas_alt(const TlasAltDev& tl, uint32_t b)
+{
+    const BlasAltDesc& d = tl.desc[b];
+    AltAccelDev a;
+    a.kdNodes = reinterpret_cast<const KdNode*>(tl.kdNodes) + d.nodeBase; a.kdRefs = tl.kdRefs + d.refBase; a.kdStack = tl.kdStack;
+    a.tris = reinterpret_cast<const AltTri*>(tl.tris) + d.triBase;
+    a.cellStart = tl.cellStart + d.cellBase; a.cellRefs = tl.cellRefs + d.cellRefBase;
+#pragma unroll
+    for (int k = 0; k < 3; k++) { a.res[k] = d.res[k]; a.cell[k] = d.cell[k]; a.lo[k] = d.lo[k]; a.hi[k] = d.hi[k]; }
+    return a;
+}
+// TLASKDTree::Intersect (ACCEL 1) / TLASGrid::Intersect (ACCEL 2): the TLAS walk of find_nearest_seq, and at an instance BLASKDTree::Intersect (rule 1, with the
+// BLAS's objIdx = Instance::objIdx) / BLASGrid::Intersect on the object-space ray.  Ray::traversed counts the TLAS steps and every BLAS's steps (Ray(const Ray&)
+// copies it, template/ray.h:10-14).  Lane column: the KD stack (two words per entry) first, the TLAS entries above it.  ANY: IsOccluded's first hit ends the walk.
+template <int ACCEL, bool ANY = false>
+__device__ __forceinline__ void tlas_alt_intersect(const Scene& sc, const TlasAltDev& tl, f3 O, f3 D, f3 rD, Hit& h, uint32_t* stk, int& traversed, int& tested)
+{
+    Cnt cn; cn.rays = cn.primary = cn.interior = cn.leaf = cn.tri = cn.tlas = cn.visits = cn.meshhits = 0;
+    tlas_walk<ANY>(sc, O, D, rD, h, stk + tl.kdStack * 128u, cn, traversed, [&](uint32_t b, rec4 ids, f3 Oo, f3 Do, f3 rDo) __attribute__((always_inline)) {
+        const AltAccelDev acc = blas_alt(tl, b);
+        if (ACCEL == 1) kd_intersect<true, ANY>(acc, Oo, Do, rDo, h, stk, traversed, tested, (int)asu(ids.w));
+        else grid_intersect<ANY>(acc, Oo, Do, rDo, h, traversed, tested);
+        return ANY && h.objIdx > -1;
+    });
+}
+// dwords per lane of the traversal stack of tlas_alt_intersect: the KD part + the TLAS part of the scene's stack (TLAS height + 1)
+__device__ __host__ __forceinline__ uint32_t tlas_alt_stack_words(const Scene& sc, const TlasAltDev& tl) { return tl.kdStack * 2u + (sc.stackDepth - sc.bvhStack); }
+
+// the accelerator walk of FindNearest / IsOccluded with an alternative structure: FileScene's (AltAccelDev) or a two-level scene's set (TlasAltDev)
+template <int ACCEL, bool ANY = false>
+__device__ __forceinline__ void alt_walk(const Scene&, const AltAccelDev& acc, f3 O, f3 D, f3 rD, Hit& h, uint32_t* stk, int& traversed, int& tested)
+{
+    if (ACCEL == 1) kd_intersect<false, ANY>(acc, O, D, rD, h, stk, traversed, tested); else grid_intersect<ANY>(acc, O, D, rD, h, traversed, tested);
+}
+template <int ACCEL, bool ANY = false>
+__device__ __forceinline__ void alt_walk(const Scene& sc, const TlasAltDev& tl, f3 O, f3 D, f3 rD, Hit& h, uint32_t* stk, int& traversed, int& tested)
+{
+    tlas_alt_intersect<ACCEL, ANY>(sc, tl, O, D, rD, h, stk, traversed, tested);
 }
 
 } // namespace crt

@@ -356,36 +356,48 @@ __device__ __forceinline__ void traverse_bvh_seq(const Scene& sc, uint32_t rootR
     }
 }
 
-__device__ __forceinline__ void find_nearest_seq(const Scene& sc, f3 O, f3 D, f3 rD, Hit& h, uint32_t* stk, Cnt& cn, int& traversed, int& tested)
+// TLASBVH::Intersect's loop (infra/tlas_bvh.cpp:83-111; tlas_kdtree.cpp / tlas_grid.cpp are the same text) with the BLAS walk as a parameter:
+// at a leaf the ray goes to object space (BLASBVH::Intersect's transform, blas_bvh.cpp:376-381, repeated by blas_kdtree.cpp:420-433 and blas_grid.cpp:233-248)
+// and `blas(instance, ids, Oo, Do, rDo)` walks that BLAS; with STOP it returns true to end the whole walk (IsOccluded's first hit).  TLAS entries at tstk[k * 64].
+template <bool STOP = false, class BlasWalk>
+__device__ __forceinline__ void tlas_walk(const Scene& sc, f3 O, f3 D, f3 rD, Hit& h, uint32_t* tstk, Cnt& cn, int& traversed, BlasWalk&& blas)
 {
     const char* __restrict__ g = sc.geom;
+    uint32_t cur = sc.rootRef, sp = 0;
+    for (;;) {
+        traversed++; cn.tlas++;
+        if ((cur & kRefTlasLeaf) == kRefTlasLeaf) {
+            cn.visits++;
+            const uint32_t io = sc.instOff + (cur & 0xffffu) * 128u;
+            const rec4 r0 = ldg(g, io), r1 = ldg(g, io + 16), r2 = ldg(g, io + 32), ids = ldg(g, io + 48);
+            f3 Oo, Do, rDo; to_object_space(r0, r1, r2, O, D, Oo, Do, rDo);
+            if constexpr (STOP) { if (blas(cur & 0xffffu, ids, Oo, Do, rDo)) break; }
+            else blas(cur & 0xffffu, ids, Oo, Do, rDo);
+            if (sp == 0) break;
+            cur = tstk[(--sp) * 64];
+        } else {
+            const uint32_t o1 = sc.tlasOff + (cur & 0x7fffu) * 32u, o2 = sc.tlasOff + ((cur >> 15) & 0x7fffu) * 32u;
+            const rec4 alo = ldg(g, o1), ahi = ldg(g, o1 + 16), blo = ldg(g, o2), bhi = ldg(g, o2 + 16);
+            float d1 = box_exact(alo, ahi, O, rD, h.t), d2 = box_exact(blo, bhi, O, rD, h.t);
+            uint32_t r1 = asu(alo.w), r2 = asu(blo.w);
+            if (d1 > d2) { float td = d1; d1 = d2; d2 = td; uint32_t tr = r1; r1 = r2; r2 = tr; }
+            if (d1 == 1e30f) { if (sp == 0) break; cur = tstk[(--sp) * 64]; }
+            else { cur = r1; if (d2 != 1e30f) { tstk[sp * 64] = r2; sp++; } }
+        }
+    }
+}
+
+__device__ __forceinline__ void find_nearest_seq(const Scene& sc, f3 O, f3 D, f3 rD, Hit& h, uint32_t* stk, Cnt& cn, int& traversed, int& tested)
+{
     cn.rays++;
     hit_light_floor(sc, O, D, h);
     if (sc.kind == 0) {
         traverse_bvh_seq(sc, sc.rootRef, O, D, rD, h, stk, cn, traversed, tested);
     } else {
-        uint32_t* tstk = stk + sc.bvhStack * 64;     // TLAS entries live above the BVH part of this lane's column
-        uint32_t cur = sc.rootRef, sp = 0;
-        for (;;) {
-            traversed++; cn.tlas++;
-            if ((cur & kRefTlasLeaf) == kRefTlasLeaf) {
-                cn.visits++;
-                const uint32_t io = sc.instOff + (cur & 0xffffu) * 128u;
-                const rec4 r0 = ldg(g, io), r1 = ldg(g, io + 16), r2 = ldg(g, io + 32), ids = ldg(g, io + 48);
-                f3 Oo, Do, rDo; to_object_space(r0, r1, r2, O, D, Oo, Do, rDo);
-                traverse_bvh_seq(sc, asu(ids.z), Oo, Do, rDo, h, stk, cn, traversed, tested);
-                if (sp == 0) break;
-                cur = tstk[(--sp) * 64];
-            } else {
-                const uint32_t o1 = sc.tlasOff + (cur & 0x7fffu) * 32u, o2 = sc.tlasOff + ((cur >> 15) & 0x7fffu) * 32u;
-                const rec4 alo = ldg(g, o1), ahi = ldg(g, o1 + 16), blo = ldg(g, o2), bhi = ldg(g, o2 + 16);
-                float d1 = box_exact(alo, ahi, O, rD, h.t), d2 = box_exact(blo, bhi, O, rD, h.t);
-                uint32_t r1 = asu(alo.w), r2 = asu(blo.w);
-                if (d1 > d2) { float td = d1; d1 = d2; d2 = td; uint32_t tr = r1; r1 = r2; r2 = tr; }
-                if (d1 == 1e30f) { if (sp == 0) break; cur = tstk[(--sp) * 64]; }
-                else { cur = r1; if (d2 != 1e30f) { tstk[sp * 64] = r2; sp++; } }
-            }
-        }
+        // TLAS entries live above the BVH part of this lane's column
+        tlas_walk(sc, O, D, rD, h, stk + sc.bvhStack * 64, cn, traversed, [&](uint32_t, rec4 ids, f3 Oo, f3 Do, f3 rDo) __attribute__((always_inline)) {
+            traverse_bvh_seq(sc, asu(ids.z), Oo, Do, rDo, h, stk, cn, traversed, tested);
+        });
     }
     if (h.objIdx >= 2) cn.meshhits++;
 }

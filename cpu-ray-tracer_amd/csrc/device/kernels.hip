@@ -798,8 +798,8 @@ __global__ __launch_bounds__(64) void is_occluded_kernel(const Scene sc, const S
 struct WFrame { f3 cA, cB, C, medium, out, bO, bD; int flags; };     // flags: 1 hasA, 2 hasB, 4 hasC, 8 b.inside, 16 waiting for B
 constexpr int kWhittedMaxDepth = 7;
 
-template <int ACCEL>
-__device__ __forceinline__ bool whitted_occluded(const Scene& sc, const AltAccelDev& alt, f3 O, f3 D, float tmax, uint32_t* stk, Cnt& cn)   // FileScene::IsOccluded, file_scene.cpp:177-187
+template <int ACCEL, class ALT>
+__device__ __forceinline__ bool whitted_occluded(const Scene& sc, const ALT& alt, f3 O, f3 D, float tmax, uint32_t* stk, Cnt& cn)   // FileScene::IsOccluded, file_scene.cpp:177-187
 {
     {   // Quad::IsOccluded, primitives.h:347-362
         const float* c = sc.lightInvT;
@@ -821,8 +821,7 @@ __device__ __forceinline__ bool whitted_occluded(const Scene& sc, const AltAccel
     const f3 rD = mk3(1 / D.x, 1 / D.y, 1 / D.z);
     int traversed = 0, tested = 0;
     cn.rays++;
-    if (ACCEL == 1) kd_intersect(alt, O, D, rD, h, stk, traversed, tested);          // (stk: this lane's column, two words per entry)
-    else if (ACCEL == 2) grid_intersect(alt, O, D, rD, h, traversed, tested);
+    if constexpr (ACCEL != 0) alt_walk<ACCEL>(sc, alt, O, D, rD, h, stk, traversed, tested);   // (stk: this lane's column, two words per KD entry)
     else if (sc.kind == 0) traverse_bvh_seq(sc, sc.rootRef, O, D, rD, h, stk, cn, traversed, tested);
     else {
         Hit hh = h; Cnt dummy = cn;
@@ -855,9 +854,10 @@ __device__ __forceinline__ bool whitted_occluded(const Scene& sc, const AltAccel
     return h.objIdx > -1;
 }
 
-// ACCEL: 0 = the scene's BVH / TLAS, 1 / 2 = FileScene's KD-tree / uniform grid (crt_set_render_accel) for both the nearest-hit and the shadow queries
-template <int ACCEL>
-__global__ __launch_bounds__(64) void whitted_kernel(const Scene sc, const AltAccelDev alt, float4* __restrict__ acc, uint32_t* __restrict__ pixels, Counters* __restrict__ counters)
+// ACCEL: 0 = the scene's BVH / TLAS, 1 / 2 = the KD-tree / uniform grid (crt_set_render_accel) for both the nearest-hit and the shadow queries: FileScene's
+// (ALT = AltAccelDev) or a two-level scene's BLASKDTree / BLASGrid set (ALT = TlasAltDev)
+template <int ACCEL, class ALT = AltAccelDev>
+__global__ __launch_bounds__(64) void whitted_kernel(const Scene sc, const ALT alt, float4* __restrict__ acc, uint32_t* __restrict__ pixels, Counters* __restrict__ counters)
 {
     extern __shared__ uint32_t lds[];
     const uint32_t lane = threadIdx.x;
@@ -892,7 +892,7 @@ __global__ __launch_bounds__(64) void whitted_kernel(const Scene sc, const AltAc
                     else {
                         cn.rays++;
                         hit_light_floor(sc, O, D, h);
-                        if (ACCEL == 1) kd_intersect(alt, O, D, rD, h, stk, traversed, tested); else grid_intersect(alt, O, D, rD, h, traversed, tested);
+                        alt_walk<ACCEL>(sc, alt, O, D, rD, h, stk, traversed, tested);
                         if (h.objIdx >= 2) cn.meshhits++;
                     }
                     if (h.objIdx == -1) res = sky_color(sc, D);
@@ -1160,10 +1160,18 @@ extern "C" hipError_t crt_launch_is_occluded(const crt::Scene* sc, const void* r
     return hipGetLastError();
 }
 
-extern "C" hipError_t crt_launch_whitted(const crt::Scene* sc, int accel, const crt::AltAccelDev* alt, void* acc, uint32_t* pixels, crt::Counters* counters, uint32_t ldsBytes, hipStream_t stream)
+extern "C" hipError_t crt_launch_whitted(const crt::Scene* sc, int accel, const crt::AltAccelDev* alt, const crt::TlasAltDev* tl, void* acc, uint32_t* pixels, crt::Counters* counters, uint32_t ldsBytes,
+                                         hipStream_t stream)
 {
     const uint32_t n = (uint32_t)sc->W * (uint32_t)sc->H;
     dim3 grid((n + 63u) / 64u), block(64);
+    if (accel != 0 && sc->kind != 0) {                                    // a two-level scene's BLASKDTree / BLASGrid set (crt_upload_blas_accel)
+        const uint32_t bytes = crt::tlas_alt_stack_words(*sc, *tl) * 64u * 4u;
+        if (bytes > 64u * 1024u) return hipErrorInvalidValue;
+        if (accel == 1) hipLaunchKernelGGL((crt::whitted_kernel<1, crt::TlasAltDev>), grid, block, bytes, stream, *sc, *tl, (float4*)acc, pixels, counters);
+        else hipLaunchKernelGGL((crt::whitted_kernel<2, crt::TlasAltDev>), grid, block, bytes, stream, *sc, *tl, (float4*)acc, pixels, counters);
+        return hipGetLastError();
+    }
     if (accel == 1) hipLaunchKernelGGL(crt::whitted_kernel<1>, grid, block, alt->kdStack * 128u * 4u, stream, *sc, *alt, (float4*)acc, pixels, counters);
     else if (accel == 2) hipLaunchKernelGGL(crt::whitted_kernel<2>, grid, block, 256u, stream, *sc, *alt, (float4*)acc, pixels, counters);
     else { const crt::AltAccelDev none{}; hipLaunchKernelGGL(crt::whitted_kernel<0>, grid, block, ldsBytes, stream, *sc, none, (float4*)acc, pixels, counters); }

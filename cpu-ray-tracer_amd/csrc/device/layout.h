@@ -102,4 +102,19 @@ struct Scene {                            // passed to the kernels BY VALUE (ker
 
 struct Counters { unsigned long long v[8]; };   // order = crt_counters
 
+// A two-level scene's set of BLASKDTree / BLASGrid structures (crt_upload_blas_accel): every BLAS's arrays are concatenated, a descriptor per BLAS
+// says where its part starts.  Triangle records are alt_common.h's AltTri (triIdx = the GLOBAL shade index, objIdx = the BLAS's), in each BLAS's order.
+struct BlasAltDesc {                      // 72 B, indexed by the BLAS (= Instance) index
+    uint32_t nodeBase, refBase, triBase;  // KD: first node, first leaf reference; first triangle record (references inside a BLAS are BLAS-local)
+    uint32_t cellBase, cellRefBase;       // grid: first cellStart entry, first cell reference
+    int32_t objIdx;                       // BLASKDTree::objIdx / BLASGrid::objIdx
+    int32_t res[3]; float cell[3]; float lo[3], hi[3];   // grid: resolution, cellSize, localBounds
+};
+struct TlasAltDev {                       // passed by value, like AltAccelDev
+    const BlasAltDesc* desc;
+    const void* kdNodes; const uint32_t* kdRefs; const void* tris;
+    const uint32_t* cellStart; const int32_t* cellRefs;
+    uint32_t kdStack;                     // KD stack entries per lane: the deepest KD-tree's height + 1 (0 for a grid set)
+};
+
 } // namespace crt

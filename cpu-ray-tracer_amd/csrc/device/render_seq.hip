@@ -3,6 +3,8 @@
 //                    the latency mode's cost probe
 //   KdWorld          FindNearest through FileScene's KD-tree (kd_intersect) — the accelerator the reference's shipped FileScene traces through (file_scene.h:10-12)
 //   GridWorld        ... through its uniform grid (grid_intersect)
+//   TlasKdWorld      TLASFileScene::FindNearest built with TLAS_USE_KDTree (TLASKDTree over BLASKDTree: tlas_alt_intersect<1>)
+//   TlasGridWorld    ... with TLAS_USE_Grid (TLASGrid over BLASGrid: tlas_alt_intersect<2>)
 // The issue-bound renders of these scenes are render_pool_kernel / render_tiles_kernel; this form exists for the probe and for parity with the alternative
 // accelerators (crt_set_render_accel).
 //
@@ -96,6 +98,23 @@ struct GridWorld : FileSurface<0> {
     }
 };
 
+// TLASFileScene::FindNearest (tlas_file_scene.cpp:201-206) built with TLAS_USE_KDTree / TLAS_USE_Grid: light quad, floor plane, then TLASKDTree / TLASGrid over
+// the BLAS set of crt_upload_blas_accel; shading is the BVH variant's (GetHitInfo, :236-253: triangle records carry the global shade index)
+template <int ACCEL>
+struct TlasAltWorld : FileSurface<1> {
+    TlasAltDev tl;
+    __device__ __host__ uint32_t stack_words(const Scene& sc) const { return tlas_alt_stack_words(sc, tl); }
+    __device__ __forceinline__ uint32_t trace(const Scene& sc, f3 O, f3 D, f3 rD, Hit& h, uint32_t* stk) const
+    {
+        int traversed = 0, tested = 0;
+        hit_light_floor(sc, O, D, h);
+        tlas_alt_intersect<ACCEL>(sc, tl, O, D, rD, h, stk, traversed, tested);
+        return 0u;
+    }
+};
+using TlasKdWorld = TlasAltWorld<1>;
+using TlasGridWorld = TlasAltWorld<2>;
+
 } // namespace crt
 
 // the latency mode's cost probe: kProbeWaves wavefronts per owned tile, 64 paths each, step counts summed into tileCost[tile]
@@ -112,14 +131,20 @@ extern "C" hipError_t crt_launch_probe(const crt::Scene* sc, uint32_t tileFirst,
     return hipGetLastError();
 }
 
-// Renderer::Sample through FileScene's KD-tree (accel 1) or uniform grid (accel 2): one wavefront per (owned tile, 64-frame window) of the launch, lane = frame
-extern "C" hipError_t crt_launch_render_alt(int accel, const crt::Scene* sc, const crt::AltAccelDev* acc, void* slab, crt::Counters* counters, uint32_t tileFirst, uint32_t tileStride, uint32_t tileCount,
-                                            uint32_t tilesX, uint32_t sppFirst, uint32_t frames, uint32_t passes, hipStream_t stream)
+// Renderer::Sample through the KD-tree (accel 1) or uniform grid (accel 2) — FileScene's (acc), or a two-level scene's BLAS set (tl): one wavefront per (owned tile,
+// 64-frame window) of the launch, lane = frame
+extern "C" hipError_t crt_launch_render_alt(int accel, const crt::Scene* sc, const crt::AltAccelDev* acc, const crt::TlasAltDev* tl, void* slab, crt::Counters* counters, uint32_t tileFirst,
+                                            uint32_t tileStride, uint32_t tileCount, uint32_t tilesX, uint32_t sppFirst, uint32_t frames, uint32_t passes, hipStream_t stream)
 {
     if (tileCount == 0 || frames == 0) return hipSuccess;
-    if (sc->kind != 0 || (accel != 1 && accel != 2)) return hipErrorInvalidValue;
+    if (accel != 1 && accel != 2) return hipErrorInvalidValue;
     const uint32_t windows = (frames + 63u) / 64u;
     if ((unsigned long long)tileCount * windows > 0x7fffffffull || tileCount > 0x10000u || windows > 64u) return hipErrorInvalidValue;
+    if (sc->kind != 0) {
+        if (crt::seq_lds_bytes(crt::tlas_alt_stack_words(*sc, *tl)) > 64u * 1024u) return hipErrorInvalidValue;
+        if (accel == 1) return crt::launch_render_seq(sc, crt::TlasKdWorld{{}, *tl}, slab, counters, tileFirst, tileStride, tileCount, tilesX, sppFirst, frames, passes, stream);
+        return crt::launch_render_seq(sc, crt::TlasGridWorld{{}, *tl}, slab, counters, tileFirst, tileStride, tileCount, tilesX, sppFirst, frames, passes, stream);
+    }
     if (accel == 1) {
         const crt::KdWorld kd{{}, *acc};
         if (crt::seq_lds_bytes(kd.stack_words(*sc)) > 64u * 1024u) return hipErrorInvalidValue;

@@ -33,4 +33,9 @@ public:
     std::vector<int32_t> cellTris;
 };
 
+// TLASFileScene's BLAS structures with TLAS_USE_KDTree / TLAS_USE_Grid (infra/blas_kdtree.h, blas_grid.h): the builds are KDTree's / Grid's (KD_SAH and
+// GRID_MAILBOXING off, blas_kdtree.h:3) over the BLAS's object-space triangle array (the one BLASBVH has); objIdx is the BLAS's.  Intersect lives on the GPU.
+class BLASKDTree : public KDTree { public: int objIdx = 0; };
+class BLASGrid : public Grid { public: int objIdx = 0; };
+
 } // namespace crt

@@ -10,7 +10,8 @@ using namespace crt;
 
 namespace { thread_local std::string g_err; }
 
-struct crt_host_scene { BaseScene* scene = nullptr; FileScene* file = nullptr; TLASFileScene* tlas = nullptr; KDTree* kd = nullptr; Grid* grid = nullptr; };
+struct crt_host_scene { BaseScene* scene = nullptr; FileScene* file = nullptr; TLASFileScene* tlas = nullptr; KDTree* kd = nullptr; Grid* grid = nullptr;
+                        std::vector<BLASKDTree> blasKd; std::vector<BLASGrid> blasGrid; };   // TLAS scene: one structure per BLAS
 struct crt_host_renderer { Renderer* r = nullptr; };
 
 #define GUARD_BEGIN try {
@@ -198,27 +199,39 @@ int crt_host_image_load(const char* path, int* w, int* h, uint32_t** pixels)
 }
 void crt_host_free(void* p) { free(p); }
 
-// FileScene's alternative accelerators (file_scene.h:10-12: USE_KDTree is what the reference ships): built over the scene's triangle array on the host
+// FileScene's alternative accelerators (file_scene.h:10-12: USE_KDTree is what the reference ships): built over the scene's triangle array on the host.
+// TLASFileScene with TLAS_USE_KDTree / TLAS_USE_Grid (tlas_file_scene.cpp:40-90): BLASKDTree / BLASGrid per BLAS over its own triangle array.
 int crt_host_scene_build_alt(crt_host_scene* s, int kind)
 {
-    if (!s || !s->file) { g_err = "alternative accelerators belong to a FileScene"; return CRT_ERR_INVALID; }
+    if (!s) { g_err = "null argument"; return CRT_ERR_INVALID; }
     GUARD_BEGIN
+    if (s->tlas) {
+        const std::vector<BLASBVH*>& bl = s->tlas->tlas.blas;
+        if (kind == CRT_ACCEL_KDTREE) {
+            s->blasKd.assign(bl.size(), BLASKDTree());
+            for (size_t i = 0; i < bl.size(); i++) { s->blasKd[i].objIdx = bl[i]->objIdx; s->blasKd[i].triangles = bl[i]->triangles; s->blasKd[i].Build(); }
+        } else if (kind == CRT_ACCEL_GRID) {
+            s->blasGrid.assign(bl.size(), BLASGrid());
+            for (size_t i = 0; i < bl.size(); i++) { s->blasGrid[i].objIdx = bl[i]->objIdx; s->blasGrid[i].triangles = bl[i]->triangles; s->blasGrid[i].Build(); }
+        } else { g_err = "unknown accelerator kind"; return CRT_ERR_INVALID; }
+        return CRT_OK;
+    }
     if (kind == CRT_ACCEL_KDTREE) { delete s->kd; s->kd = new KDTree(); s->kd->triangles = s->file->acc.triangles; s->kd->Build(); }
     else if (kind == CRT_ACCEL_GRID) { delete s->grid; s->grid = new Grid(); s->grid->triangles = s->file->acc.triangles; s->grid->Build(); }
     else { g_err = "unknown accelerator kind"; return CRT_ERR_INVALID; }
     return CRT_OK;
     GUARD_END(CRT_ERR_INVALID)
 }
-static int describe_alt(crt_host_scene* s, int kind, crt_alt_accel& a)
+static int describe_alt(const KDTree* kd, const Grid* grid, int kind, crt_alt_accel& a)
 {
     memset(&a, 0, sizeof(a)); a.kind = kind;
-    if (kind == CRT_ACCEL_KDTREE && s->kd) {
-        a.triangles = s->kd->triangles.data(); a.triCount = (uint32_t)s->kd->triangles.size();
-        a.kdNodes = s->kd->nodes.data(); a.kdNodeCount = (uint32_t)s->kd->nodes.size(); a.kdTriIndices = s->kd->leafTriIndices.data(); a.kdTriIndexCount = (uint32_t)s->kd->leafTriIndices.size();
+    if (kind == CRT_ACCEL_KDTREE && kd) {
+        a.triangles = kd->triangles.data(); a.triCount = (uint32_t)kd->triangles.size();
+        a.kdNodes = kd->nodes.data(); a.kdNodeCount = (uint32_t)kd->nodes.size(); a.kdTriIndices = kd->leafTriIndices.data(); a.kdTriIndexCount = (uint32_t)kd->leafTriIndices.size();
         return CRT_OK;
     }
-    if (kind == CRT_ACCEL_GRID && s->grid) {
-        const Grid& g = *s->grid;
+    if (kind == CRT_ACCEL_GRID && grid) {
+        const Grid& g = *grid;
         a.triangles = g.triangles.data(); a.triCount = (uint32_t)g.triangles.size();
         for (int k = 0; k < 3; k++) { a.gridResolution[k] = g.resolution[k]; a.gridCellSize[k] = g.cellSize[k]; a.gridMin[k] = g.localBounds.bmin3[k]; a.gridMax[k] = g.localBounds.bmax3[k]; }
         a.gridCellStart = g.cellStart.data(); a.gridCellTris = g.cellTris.data(); a.gridCellTriCount = (uint32_t)g.cellTris.size();
@@ -226,15 +239,42 @@ static int describe_alt(crt_host_scene* s, int kind, crt_alt_accel& a)
     }
     g_err = "accelerator not built (crt_host_scene_build_alt)"; return CRT_ERR_STATE;
 }
+static int describe_alt(crt_host_scene* s, int kind, crt_alt_accel& a) { return describe_alt(s->kd, s->grid, kind, a); }
+// BLAS `i` of a TLAS scene's set
+static int describe_blas_alt(crt_host_scene* s, int kind, int i, crt_alt_accel& a)
+{
+    if (!s->tlas || i < 0 || i >= (int)s->tlas->tlas.blas.size()) { g_err = "not a TLAS scene / BLAS index out of range"; return CRT_ERR_INVALID; }
+    if ((kind == CRT_ACCEL_KDTREE && s->blasKd.empty()) || (kind == CRT_ACCEL_GRID && s->blasGrid.empty())) { g_err = "accelerator not built (crt_host_scene_build_alt)"; return CRT_ERR_STATE; }
+    return describe_alt(kind == CRT_ACCEL_KDTREE ? &s->blasKd[(size_t)i] : nullptr, kind == CRT_ACCEL_GRID ? &s->blasGrid[(size_t)i] : nullptr, kind, a);
+}
 int crt_host_scene_upload_alt(crt_host_scene* s, crt_ctx* ctx, int kind)
 {
     if (!s || !ctx) { g_err = "null argument"; return CRT_ERR_INVALID; }
+    if (s->tlas) {
+        std::vector<crt_alt_accel> set(s->tlas->tlas.blas.size());
+        for (size_t i = 0; i < set.size(); i++) { const int rc = describe_blas_alt(s, kind, (int)i, set[i]); if (rc) return rc; }
+        const int rc = crt_upload_blas_accel(ctx, kind, set.data(), (uint32_t)set.size());
+        if (rc != CRT_OK) g_err = crt_last_error(ctx);
+        return rc;
+    }
     crt_alt_accel a; int rc = describe_alt(s, kind, a); if (rc) return rc;
     rc = crt_upload_alt_accel(ctx, &a);
     if (rc != CRT_OK) g_err = crt_last_error(ctx);
     return rc;
 }
 // sizes: KD-tree -> {nodes, leaf triangle indices, maxDepth, nodesUsed}; grid -> {rx, ry, rz, cell triangle references}
+static void alt_info(const KDTree* kd, int kind, const crt_alt_accel& a, uint32_t out[4])
+{
+    if (kind == CRT_ACCEL_KDTREE) { out[0] = a.kdNodeCount; out[1] = a.kdTriIndexCount; out[2] = kd->maxDepth; out[3] = kd->nodesUsed; }
+    else { out[0] = (uint32_t)a.gridResolution[0]; out[1] = (uint32_t)a.gridResolution[1]; out[2] = (uint32_t)a.gridResolution[2]; out[3] = a.gridCellTriCount; }
+}
+int crt_host_scene_blas_alt_info(crt_host_scene* s, int kind, int blas, uint32_t out[4])
+{
+    if (!s || !out) { g_err = "null argument"; return CRT_ERR_INVALID; }
+    crt_alt_accel a; int rc = describe_blas_alt(s, kind, blas, a); if (rc) return rc;
+    alt_info(kind == CRT_ACCEL_KDTREE ? &s->blasKd[(size_t)blas] : nullptr, kind, a, out);
+    return CRT_OK;
+}
 int crt_host_scene_alt_info(crt_host_scene* s, int kind, uint32_t out[4])
 {
     if (!s || !out) { g_err = "null argument"; return CRT_ERR_INVALID; }
@@ -244,17 +284,29 @@ int crt_host_scene_alt_info(crt_host_scene* s, int kind, uint32_t out[4])
     return CRT_OK;
 }
 // copies: KD-tree -> nodes (48 B each) + leaf triangle indices; grid -> f[0..2] cellSize, f[3..5] bounds min, f[6..8] bounds max, cellStart (cells + 1), cell triangle references
+static void alt_copy(int kind, const crt_alt_accel& a, void* nodesOrCellStart, void* refs, float* f9);
+int crt_host_scene_blas_alt_copy(crt_host_scene* s, int kind, int blas, void* nodesOrCellStart, void* refs, float* f9)
+{
+    if (!s) { g_err = "null argument"; return CRT_ERR_INVALID; }
+    crt_alt_accel a; int rc = describe_blas_alt(s, kind, blas, a); if (rc) return rc;
+    alt_copy(kind, a, nodesOrCellStart, refs, f9);
+    return CRT_OK;
+}
 int crt_host_scene_alt_copy(crt_host_scene* s, int kind, void* nodesOrCellStart, void* refs, float* f9)
 {
     if (!s) { g_err = "null argument"; return CRT_ERR_INVALID; }
     crt_alt_accel a; int rc = describe_alt(s, kind, a); if (rc) return rc;
+    alt_copy(kind, a, nodesOrCellStart, refs, f9);
+    return CRT_OK;
+}
+static void alt_copy(int kind, const crt_alt_accel& a, void* nodesOrCellStart, void* refs, float* f9)
+{
     if (kind == CRT_ACCEL_KDTREE) { if (nodesOrCellStart) memcpy(nodesOrCellStart, a.kdNodes, (size_t)a.kdNodeCount * 48); if (refs) memcpy(refs, a.kdTriIndices, (size_t)a.kdTriIndexCount * 4); }
     else {
         const size_t cells = (size_t)a.gridResolution[0] * a.gridResolution[1] * a.gridResolution[2];
         if (nodesOrCellStart) memcpy(nodesOrCellStart, a.gridCellStart, (cells + 1) * 4); if (refs) memcpy(refs, a.gridCellTris, (size_t)a.gridCellTriCount * 4);
         if (f9) for (int k = 0; k < 3; k++) { f9[k] = a.gridCellSize[k]; f9[3 + k] = a.gridMin[k]; f9[6 + k] = a.gridMax[k]; }
     }
-    return CRT_OK;
 }
 
 // test entries: the host front's restatements of the tmplmath.h inlines / the Vertex table, same layout as the real-reference harness's probes (tests/golden/make_golden.py)

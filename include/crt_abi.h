@@ -181,7 +181,7 @@ int  crt_resolve_screen(crt_ctx* ctx, float scale, uint32_t* host_pixels /* widt
  * following frames are rendered ahead in multi-frame launches and a later Tick of that sequence only adds its frame's samples, resolves and reads
  * back.  Any other call order is served as above (crt_render and crt_reserve drop the frames rendered ahead; crt_clear and crt_bind_accumulator keep
  * them).  The counters and crt_get_timing include every frame rendered ahead, also those later dropped.  Contexts with collectStats, the KD-tree /
- * grid path (crt_set_render_accel != 0) and the PrimitiveScene never render ahead. */
+ * grid path (crt_set_render_accel != 0, FileScene's and a two-level scene's BLAS set alike) and the PrimitiveScene never render ahead. */
 int  crt_tick(crt_ctx* ctx, uint32_t spp, uint32_t passes, uint32_t* host_pixels /* width*height */, float* host_rgba /* float4[width*height] */, float* energy);
 
 /* ---- Whitted-style integrator ("2. WhittedStyle/renderer.cpp":21-157): one deterministic Tick -------------------
@@ -221,12 +221,28 @@ int  crt_find_nearest_alt(crt_ctx* ctx, int kind, const crt_ray* rays, crt_hit* 
 /* ABI 3: which structure crt_render (Renderer::Sample) and crt_whitted_tick (Renderer::Trace, incl. its shadow rays) trace through: 0 = the scene's BVH / TLAS
  * (default), CRT_ACCEL_KDTREE / CRT_ACCEL_GRID = the uploaded alternative accelerator — what the reference's FileScene does when built with USE_KDTree (its shipped
  * setting, infra/scene/file_scene.h:10-12, file_scene.cpp:170-187) / USE_Grid.  Bug-compatible: the KD traversal loses hits for rays with a direction component of
- * exactly 0 (kdtree.cpp:161-201).  The sequential form (one wavefront per tile and 64-frame window); reset by crt_upload_scene / crt_upload_alt_accel of the kind. */
+ * exactly 0 (kdtree.cpp:161-201).  The sequential form (one wavefront per tile and 64-frame window); reset by crt_upload_scene / crt_upload_alt_accel /
+ * crt_upload_blas_accel of the kind, and by a CRT_UPDATE_BOUNDS update that drops a two-level scene's set. */
 int  crt_set_render_accel(crt_ctx* ctx, int kind);
+/* Two-level scenes built with TLAS_USE_KDTree / TLAS_USE_Grid (tlas_file_scene.cpp:40-90): TLASKDTree over BLASKDTree / TLASGrid over BLASGrid.  After
+ * crt_upload_scene of a CRT_SCENE_TLAS scene, blas[i] is BLAS i's KD-tree / grid over its own object-space triangle array (BLASKDTree::Build = KDTree's build,
+ * BLASGrid::Build = Grid's; blasCount = the scene's bvhCount).  Checked as crt_upload_alt_accel checks one structure, and also: the triangle count and every
+ * triangle's objIdx are BLAS i's, and the root box (KD nodes[0], grid gridMin / gridMax) equals BLAS i's BVH root box bit for bit — the TLAS and the instance
+ * records of the BVH variant are shared (SetTransform takes the world bounds from that box) — else CRT_ERR_INVALID; a traversal stack (TLAS height + deepest
+ * KD-tree + 1) beyond the LDS budget is CRT_ERR_UNSUPPORTED.  A failed call changes nothing (a refused description, and also a failed device allocation or
+ * copy: the new set is built in buffers of its own and replaces the previous one only once complete).  One set per kind is kept; the call is synchronous (it
+ * waits for the queries and render launches that read the previous set); a successful call resets crt_set_render_accel to 0 if it named this kind.  Then accel = CRT_ACCEL_KDTREE / CRT_ACCEL_GRID works on the TLAS scene in
+ * crt_find_nearest_alt, crt_is_occluded, the device query entries and crt_set_render_accel (crt_render, crt_whitted_tick); records as the TLAS-BVH path's
+ * (objIdx >= 2 = the BLAS's, triIdx BLAS-local, traversed = TLAS steps + every BLAS's steps, tested over the query).  The KD walk keeps BLASKDTree's early
+ * return `if (ray.objIdx == objIdx && ray.t < t) return;` (blas_kdtree.cpp:377, 396), so `traversed` differs from FileScene's KD-tree for rays that hit something
+ * else first.  CRT_UPDATE_TRANSFORMS keeps the set (it lives in object space); CRT_UPDATE_BOUNDS drops it (the reference has no Refit for these structures:
+ * the render goes back to the BVH, a query with that accel is CRT_ERR_STATE); crt_upload_scene / crt_upload_primitive_scene drop it; crt_upload_alt_accel on
+ * a TLAS scene stays CRT_ERR_STATE. */
+int  crt_upload_blas_accel(crt_ctx* ctx, int kind, const crt_alt_accel* blas, uint32_t blasCount);
 
 /* ---- scene queries: BaseScene::IsOccluded, and both queries on device buffers (base_scene.h:16-32) ------------------------------------------------
  * accel: 0 = the scene's own structure (BVH / TLAS; for the nearest-hit query also the PrimitiveScene), CRT_ACCEL_KDTREE / CRT_ACCEL_GRID = the uploaded
- * alternative accelerator (FileScene built with USE_KDTree / USE_Grid).
+ * alternative accelerator (FileScene built with USE_KDTree / USE_Grid; a TLASFileScene built with TLAS_USE_KDTree / TLAS_USE_Grid: crt_upload_blas_accel).
  *
  * IsOccluded (FileScene::IsOccluded / TLASFileScene::IsOccluded, file_scene.cpp:177-187, tlas_file_scene.cpp:208-218), bug-compatible: the light quad is tested
  * bounded by ray.t (Quad::IsOccluded, primitives.h:347-362); then the acceleration structure is intersected over the WHOLE ray (shadow.t = 1e34f, not clipped at
@@ -246,6 +262,9 @@ int  crt_set_render_accel(crt_ctx* ctx, int kind);
  *   - queries may be in flight on several streams at once (each launch draws its rays from a cursor of its own);
  *   - the outputs are ready in stream order on `stream`: the caller orders its consumers (a kernel on the same stream needs no host synchronisation).
  * All entries: n == 0 is a no-op; n > 2^31-1 is CRT_ERR_UNSUPPORTED; no scene, or an accelerator that was not uploaded, is CRT_ERR_STATE. */
+/* A crt_shadow_ray carries no objIdx: IsOccluded is defined for a ray whose objIdx is -1, as Ray(O, D, t) builds it.  (On a two-level scene's KD-tree set a
+ * caller ray with objIdx >= 2 could differ: BLASKDTree's early return compares ray.objIdx — only where that instance's object-space direction has a component
+ * that is exactly 0.) */
 typedef struct crt_shadow_ray { float O[3]; float D[3]; float t; } crt_shadow_ray;   /* Ray with ray.t = t: the argument of IsOccluded (28 bytes, as crt_ray) */
 int  crt_is_occluded(crt_ctx* ctx, int accel, const crt_shadow_ray* rays, int32_t* occluded, size_t n);                       /* host pointers, synchronous */
 int  crt_find_nearest_device(crt_ctx* ctx, int accel, const crt_ray* d_rays, crt_hit* d_hits, size_t n, void* stream);

@@ -48,6 +48,11 @@ int  crt_host_scene_build_alt(crt_host_scene* scene, int kind);
 int  crt_host_scene_upload_alt(crt_host_scene* scene, crt_ctx* ctx, int kind);
 int  crt_host_scene_alt_info(crt_host_scene* scene, int kind, uint32_t out[4]);   /* KD: nodes, leaf indices, maxDepth, nodesUsed; grid: rx, ry, rz, cell references */
 int  crt_host_scene_alt_copy(crt_host_scene* scene, int kind, void* nodesOrCellStart, void* refs, float* gridCellMinMax9);
+/* For a TLAS scene crt_host_scene_build_alt builds one BLASKDTree / BLASGrid per BLAS (blas_kdtree.cpp:82-104, blas_grid.cpp:82-131: KDTree's / Grid's build
+ * over the BLAS's object-space triangle array) and crt_host_scene_upload_alt uploads the set through crt_upload_blas_accel.  BLAS `blas`'s structure, in the
+ * formats of crt_host_scene_alt_info / _alt_copy: */
+int  crt_host_scene_blas_alt_info(crt_host_scene* scene, int kind, int blas, uint32_t out[4]);
+int  crt_host_scene_blas_alt_copy(crt_host_scene* scene, int kind, int blas, void* nodesOrCellStart, void* refs, float* gridCellMinMax9);
 /* instance motion: BLASBVH::SetTransform(T) of BLAS `bvh` (infra/blas_bvh.cpp:363-374) + TLASBVH::Build (infra/tlas_bvh.cpp:17-55) on the host ... */
 int  crt_host_scene_set_transform(crt_host_scene* scene, int bvh, const float T[16]);
 /* ... and the in-place device update for it (what = CRT_UPDATE_TRANSFORMS) or for crt_host_scene_bvh_move_and_refit (what = CRT_UPDATE_BOUNDS): crt_update_scene */
