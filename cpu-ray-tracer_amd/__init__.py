@@ -83,6 +83,17 @@ class CountersS(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("rays", "primary", "interior_iters", "leaf_iters", "tri_tests", "tlas_iters", "blas_visits", "mesh_hits")]
 
 
+class WhittedMetricsS(C.Structure):
+    """crt_whitted_metrics"""
+    _fields_ = [("rayHitCount", C.c_uint64), ("totalTraversal", C.c_uint64), ("totalTests", C.c_uint64), ("peakTraversal", C.c_int32), ("peakTests", C.c_int32)]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+INSPECT_NONE, INSPECT_TRAVERSAL, INSPECT_TESTS = 0, 1, 2      # crt_whitted_tick_inspect modes
+
+
 class TimingS(C.Structure):
     _fields_ = [("render_kernel_ms", C.c_float), ("resolve_kernel_ms", C.c_float), ("render_launches", C.c_uint32), ("pool_launches", C.c_uint32), ("split_launches", C.c_uint32), ("reserved", C.c_uint32)]
 
@@ -98,13 +109,13 @@ SHADOW_RAY_DTYPE = np.dtype([("O", "<f4", 3), ("D", "<f4", 3), ("t", "<f4")])   
 
 # every symbol include/crt_abi.h and include/crt_host.h declare (tests check the library exports all of them)
 ABI_SYMBOLS = ["crt_upload_blas_accel", "crt_is_occluded", "crt_find_nearest_device", "crt_is_occluded_device", "crt_upload_primitive_scene", "crt_set_render_accel", "crt_upload_alt_accel", "crt_find_nearest_alt", "crt_update_scene", "crt_abi_version", "crt_device_count", "crt_create", "crt_destroy", "crt_last_error", "crt_upload_scene", "crt_set_camera",
-               "crt_render", "crt_tick", "crt_reserve", "crt_whitted_tick", "crt_sync", "crt_clear", "crt_read_accumulator", "crt_resolve_screen", "crt_find_nearest", "crt_get_counters",
+               "crt_render", "crt_tick", "crt_reserve", "crt_whitted_tick", "crt_whitted_tick_inspect", "crt_sync", "crt_clear", "crt_read_accumulator", "crt_resolve_screen", "crt_find_nearest", "crt_get_counters",
                "crt_reset_counters", "crt_get_timing", "crt_get_tile_clocks", "crt_bind_accumulator", "crt_accumulator_device_ptr"]
 HOST_SYMBOLS = ["crt_host_scene_blas_alt_info", "crt_host_scene_blas_alt_copy", "crt_host_primitive_scene_create", "crt_host_primitive_scene_free", "crt_host_primitive_scene_set_time", "crt_host_primitive_scene_desc", "crt_host_primitive_scene_upload", "crt_host_scene_build_alt", "crt_host_scene_upload_alt", "crt_host_scene_alt_info", "crt_host_scene_alt_copy", "crt_host_scene_set_transform", "crt_host_scene_update", "crt_host_math_probe", "crt_host_vertex_dedup", "crt_host_last_error", "crt_host_scene_load", "crt_host_scene_free", "crt_host_scene_upload", "crt_host_scene_kind",
                 "crt_host_scene_triangle_count", "crt_host_scene_bvh_count", "crt_host_scene_bvh_info", "crt_host_scene_bvh_copy",
                 "crt_host_scene_bvh_move_and_refit", "crt_host_scene_blas_transform", "crt_host_scene_tlas_copy", "crt_host_camera_state", "crt_host_renderer_create",
                 "crt_host_renderer_destroy", "crt_host_renderer_init", "crt_host_renderer_set_camera", "crt_host_renderer_set_passes",
-                "crt_host_renderer_clear", "crt_host_renderer_tick", "crt_host_renderer_render", "crt_host_renderer_tick_whitted", "crt_host_renderer_spp",
+                "crt_host_renderer_clear", "crt_host_renderer_tick", "crt_host_renderer_render", "crt_host_renderer_tick_whitted", "crt_host_renderer_set_inspect", "crt_host_renderer_whitted_metrics", "crt_host_renderer_spp",
                 "crt_host_renderer_energy", "crt_host_renderer_accumulator", "crt_host_renderer_screen", "crt_host_renderer_ctx",
                 "crt_host_obj_load", "crt_host_image_load", "crt_host_free"]
 
@@ -231,6 +242,16 @@ class Context:
         px = np.empty((self.H, self.W), np.uint32)
         self._ck(self.L.crt_whitted_tick(self.h, _p(px)))
         return px
+
+    def whitted_tick_inspect(self, inspect=0, peak_traversal=0, peak_tests=0, counts=False):
+        """crt_whitted_tick_inspect: one Whitted Tick in mode `inspect` (INSPECT_NONE / _TRAVERSAL / _TESTS) with the peaks carried in.  Returns (pixels, metrics dict)
+        or, with counts=True, (pixels, metrics dict, traversed (H, W) int32, tested (H, W) int32) of the primary rays."""
+        px = np.empty((self.H, self.W), np.uint32)
+        tr = np.empty((self.H, self.W), np.int32) if counts else None
+        te = np.empty((self.H, self.W), np.int32) if counts else None
+        m = WhittedMetricsS()
+        self._ck(self.L.crt_whitted_tick_inspect(self.h, C.c_int(inspect), C.c_int32(peak_traversal), C.c_int32(peak_tests), _p(px), _p(tr) if counts else None, _p(te) if counts else None, C.byref(m)))
+        return (px, m.as_dict(), tr, te) if counts else (px, m.as_dict())
 
     def sync(self):
         self._ck(self.L.crt_sync(self.h))
@@ -630,6 +651,17 @@ class HostRenderer:
 
     def tick_whitted(self):
         self._ck(self.L.crt_host_renderer_tick_whitted(self.h))
+
+    def set_inspect(self, traversal=False, tests=False):
+        """the Whitted Renderer's m_inspectTraversal / m_inspectIntersectionTest (traversal wins if both are set)"""
+        self._ck(self.L.crt_host_renderer_set_inspect(self.h, int(bool(traversal)), int(bool(tests))))
+
+    def whitted_metrics(self):
+        """the report of the last tick_whitted: crt_whitted_metrics' fields (peaks as carried so far) + averageTraversal / averageTests (float32)"""
+        m = WhittedMetricsS(); a, b = C.c_float(), C.c_float()
+        self._ck(self.L.crt_host_renderer_whitted_metrics(self.h, C.byref(m), C.byref(a), C.byref(b)))
+        d = m.as_dict(); d["averageTraversal"] = np.float32(a.value); d["averageTests"] = np.float32(b.value)
+        return d
 
     @property
     def spp(self):

@@ -29,6 +29,9 @@ extern "C" hipError_t crt_launch_accumulate(const void*, void*, uint32_t, uint32
 extern "C" hipError_t crt_launch_find_nearest(const crt::Scene*, const void*, void*, uint32_t, crt::Counters*, uint32_t, uint32_t*, hipStream_t);
 namespace crt { struct AltAccelDev; }
 extern "C" hipError_t crt_launch_whitted(const crt::Scene*, int, const crt::AltAccelDev*, const crt::TlasAltDev*, void*, uint32_t*, crt::Counters*, uint32_t, hipStream_t);
+extern "C" hipError_t crt_launch_whitted_inspect(const crt::Scene*, int, const crt::AltAccelDev*, const crt::TlasAltDev*, int, int32_t, void*, uint32_t*, crt::Counters*, int32_t*, int32_t*, void*, uint32_t,
+                                                 hipStream_t);
+extern "C" size_t crt_whitted_inspect_work_bytes(uint32_t);
 extern "C" hipError_t crt_launch_render_alt(int, const crt::Scene*, const crt::AltAccelDev*, const crt::TlasAltDev*, void*, crt::Counters*, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, hipStream_t);
 extern "C" hipError_t crt_launch_resolve(const void*, uint32_t*, float*, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, float, hipStream_t);
 extern "C" hipError_t crt_launch_commit_frame(const void*, uint32_t, uint32_t, void*, uint32_t*, float*, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, float, hipStream_t);
@@ -107,6 +110,8 @@ struct crt_ctx {
     crt::Scene hScene{};
     crt::Counters* dCounters = nullptr;
     uint32_t* dQueryCursor = nullptr;      // the ray cursor of the persistent query kernels (zeroed by each launch)
+    // crt_whitted_tick_inspect: the primary rays' traversed / tested images (two int32 per pixel) and the metrics record + per-block maxima; allocated by the first call
+    int32_t* dInspectCounts = nullptr; void* dInspectWork = nullptr; size_t inspectCap = 0;
     uint32_t* dPixels = nullptr; float* dTileSums = nullptr;
     unsigned long long* dTileClocks = nullptr;
     std::vector<void*> sceneAllocs;
@@ -375,6 +380,8 @@ void crt_destroy(crt_ctx* c)
     if (c->dTileSums) (void)hipFree(c->dTileSums);
     if (c->dCounters) (void)hipFree(c->dCounters);
     if (c->dQueryCursor) (void)hipFree(c->dQueryCursor);
+    if (c->dInspectCounts) (void)hipFree(c->dInspectCounts);
+    if (c->dInspectWork) (void)hipFree(c->dInspectWork);
     if (c->dTileClocks) (void)hipFree(c->dTileClocks);
     if (c->dTileOrder) (void)hipFree(c->dTileOrder);
     if (c->dTileCost) (void)hipFree(c->dTileCost);
@@ -1741,6 +1748,41 @@ int crt_whitted_tick(crt_ctx* c, uint32_t* hostPixels)
     HIPCK(c, crt_launch_whitted(&c->hScene, c->renderAccel, &c->alt, c->renderAccel ? &c->blasAlt[c->renderAccel - 1] : nullptr, c->dAcc, c->dPixels, c->dCounters, c->ldsBytes, c->stream));
     if (hostPixels) HIPCK(c, hipMemcpyAsync(hostPixels, c->dPixels, (size_t)c->cfg.width * c->cfg.height * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCK(c, hipStreamSynchronize(c->stream));
+    return CRT_OK;
+}
+
+int crt_whitted_tick_inspect(crt_ctx* c, int inspect, int32_t peakTraversalIn, int32_t peakTestsIn, uint32_t* hostPixels, int32_t* hostTraversed, int32_t* hostTested, crt_whitted_metrics* metrics)
+{
+    if (!c) return CRT_ERR_INVALID;
+    if (inspect < CRT_INSPECT_NONE || inspect > CRT_INSPECT_TESTS) return c->fail(CRT_ERR_INVALID, "crt_whitted_tick_inspect: inspect must be CRT_INSPECT_NONE, _TRAVERSAL or _TESTS");
+    if (peakTraversalIn < 0 || peakTestsIn < 0) return c->fail(CRT_ERR_INVALID, "crt_whitted_tick_inspect: a peak cannot be negative");
+    if (!c->haveScene) return c->fail(CRT_ERR_STATE, "crt_whitted_tick_inspect before crt_upload_scene");
+    HIPCK(c, hipSetDevice(c->cfg.device));
+    const size_t n = (size_t)c->cfg.width * c->cfg.height;
+    if (n > c->inspectCap) {                                               // first use (the image size is the context's): kept until crt_destroy
+        HIPCK(c, hipStreamSynchronize(c->stream));
+        if (c->dInspectCounts) (void)hipFree(c->dInspectCounts);
+        if (c->dInspectWork) (void)hipFree(c->dInspectWork);
+        c->dInspectCounts = nullptr; c->dInspectWork = nullptr; c->inspectCap = 0;
+        HIPCK(c, hipMalloc((void**)&c->dInspectCounts, n * 2 * sizeof(int32_t)));
+        HIPCK(c, hipMalloc(&c->dInspectWork, crt_whitted_inspect_work_bytes((uint32_t)n)));
+        c->inspectCap = n;
+    }
+    int32_t* dTrav = c->dInspectCounts; int32_t* dTested = c->dInspectCounts + n;
+    HIPCK(c, crt_launch_whitted_inspect(&c->hScene, c->renderAccel, &c->alt, c->renderAccel ? &c->blasAlt[c->renderAccel - 1] : nullptr, inspect,
+                                        inspect == CRT_INSPECT_TESTS ? peakTestsIn : peakTraversalIn, c->dAcc, c->dPixels, c->dCounters, dTrav, dTested, c->dInspectWork, c->ldsBytes, c->stream));
+    static_assert(sizeof(crt_whitted_metrics) == 32, "crt::InspectSums (kernels.hip) is read back into this record");
+    crt_whitted_metrics m;                                                 // the device record has this layout, with this Tick's maxima in the peaks
+    if (hostPixels) HIPCK(c, hipMemcpyAsync(hostPixels, c->dPixels, n * 4, hipMemcpyDeviceToHost, c->stream));
+    if (hostTraversed) HIPCK(c, hipMemcpyAsync(hostTraversed, dTrav, n * 4, hipMemcpyDeviceToHost, c->stream));
+    if (hostTested) HIPCK(c, hipMemcpyAsync(hostTested, dTested, n * 4, hipMemcpyDeviceToHost, c->stream));
+    if (metrics) HIPCK(c, hipMemcpyAsync(&m, c->dInspectWork, sizeof(m), hipMemcpyDeviceToHost, c->stream));
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    if (metrics) {
+        if (m.peakTraversal < peakTraversalIn) m.peakTraversal = peakTraversalIn;
+        if (m.peakTests < peakTestsIn) m.peakTests = peakTestsIn;
+        *metrics = m;
+    }
     return CRT_OK;
 }
 

@@ -15,6 +15,8 @@
 //                         atomics anywhere.
 //   find_nearest_kernel   scene.FindNearest for a ray buffer (parity / query entry).
 //   whitted_kernel        the Whitted-style integrator ("2. WhittedStyle/renderer.cpp":21-157), one thread per pixel.
+//   inspect_primary_kernel / inspect_color_kernel   the Whitted renderer's traversal / intersection heat maps and per-Tick metrics
+//                         (renderer.cpp:38-39, 147-152): primary rays' counts + metrics, then exclusive prefix maximum + colour.
 //   resolve_kernel        screen pixels + per-tile energy sums (renderer.cpp:119,127-129).
 //   commit_frame_kernel   crt_tick: one rendered-ahead frame's samples into the accumulator + the screen, in one pass.
 //
@@ -856,10 +858,41 @@ __device__ __forceinline__ bool whitted_occluded(const Scene& sc, const ALT& alt
 
 // ACCEL: 0 = the scene's BVH / TLAS, 1 / 2 = the KD-tree / uniform grid (crt_set_render_accel) for both the nearest-hit and the shadow queries: FileScene's
 // (ALT = AltAccelDev) or a two-level scene's BLASKDTree / BLASGrid set (ALT = TlasAltDev)
-template <int ACCEL, class ALT = AltAccelDev>
-__global__ __launch_bounds__(64) void whitted_kernel(const Scene sc, const ALT alt, float4* __restrict__ acc, uint32_t* __restrict__ pixels, Counters* __restrict__ counters)
+// One Tick's metrics over the primary rays ("2. WhittedStyle/renderer.cpp":147-152) as the device collects them: exact integer sums and this Tick's maxima
+// (crt_whitted_metrics' layout; the host raises the maxima by the peaks passed in).  Zeroed before every launch.
+struct InspectSums { unsigned long long hits, traversal, tests; int32_t maxTraversal, maxTests; };
+static_assert(sizeof(InspectSums) == 32, "crt_whitted_metrics is read back from this record");
+
+__device__ __forceinline__ int32_t wave_max(int32_t v)
 {
+    for (int o = 32; o > 0; o >>= 1) { const int32_t t = __shfl_xor(v, o, 64); v = t > v ? t : v; }
+    return v;
+}
+// the primary ray's record into the per-pixel count images and, one atomic per wavefront and figure, into the Tick's metrics (every lane of the wavefront calls
+// this; lanes beyond the image pass zeros).  Integer add / max only: the result does not depend on the order the wavefronts arrive in.
+__device__ __forceinline__ void inspect_reduce(uint32_t lane, int32_t traversed, int32_t tested, InspectSums* __restrict__ sums)
+{
+    const uint32_t hits = wave_sum(traversed > 0 ? 1u : 0u), st = wave_sum((uint32_t)traversed), ss = wave_sum((uint32_t)tested);
+    const int32_t mt = wave_max(traversed), ms = wave_max(tested);
+    if (lane == 0) {
+        if (hits) atomicAdd(&sums->hits, (unsigned long long)hits);
+        if (st) atomicAdd(&sums->traversal, (unsigned long long)st);
+        if (ss) atomicAdd(&sums->tests, (unsigned long long)ss);
+        if (mt) atomicMax(&sums->maxTraversal, mt);
+        if (ms) atomicMax(&sums->maxTests, ms);
+    }
+}
+
+// EXTRA: nothing (crt_whitted_tick), or one InspectOut (crt_whitted_tick_inspect, CRT_INSPECT_NONE): the same Tick, and the depth-0 ray's traversed / tested go to
+// the count images and the metrics.  A parameter pack so that the instantiations without it keep their parameter list and their code.
+struct InspectOut { int32_t* traversed; int32_t* tested; InspectSums* sums; };
+__device__ __forceinline__ const InspectOut& inspect_out(const InspectOut& o) { return o; }
+template <int ACCEL, class ALT = AltAccelDev, class... EXTRA>
+__global__ __launch_bounds__(64) void whitted_kernel(const Scene sc, const ALT alt, float4* __restrict__ acc, uint32_t* __restrict__ pixels, Counters* __restrict__ counters, const EXTRA... extra)
+{
+    constexpr bool COUNTS = sizeof...(EXTRA) != 0;
     extern __shared__ uint32_t lds[];
+    [[maybe_unused]] int32_t primTraversed = 0, primTested = 0;
     const uint32_t lane = threadIdx.x;
     const uint32_t idx = blockIdx.x * 64u + lane;
     const uint32_t W = (uint32_t)sc.W, H = (uint32_t)sc.H;
@@ -895,6 +928,7 @@ __global__ __launch_bounds__(64) void whitted_kernel(const Scene sc, const ALT a
                         alt_walk<ACCEL>(sc, alt, O, D, rD, h, stk, traversed, tested);
                         if (h.objIdx >= 2) cn.meshhits++;
                     }
+                    if constexpr (COUNTS) { if (sp == 0) { primTraversed = traversed; primTested = tested; } }
                     if (h.objIdx == -1) res = sky_color(sc, D);
                     else if (h.objIdx == 0) res = mk3(24, 24, 22);
                     else {
@@ -996,12 +1030,117 @@ __global__ __launch_bounds__(64) void whitted_kernel(const Scene sc, const ALT a
         acc[idx] = make_float4(res.x, res.y, res.z, 0.0f);
         const uint32_t r = (uint32_t)(255.0f * min_std(1.0f, res.x)), g = (uint32_t)(255.0f * min_std(1.0f, res.y)), bb = (uint32_t)(255.0f * min_std(1.0f, res.z));
         pixels[idx] = (r << 16) + (g << 8) + bb;
+        if constexpr (COUNTS) { const InspectOut& o = inspect_out(extra...); o.traversed[idx] = primTraversed; o.tested[idx] = primTested; }
     }
     uint32_t vals[8] = {cn.rays, cn.primary, cn.interior, cn.leaf, cn.tri, cn.tlas, cn.visits, cn.meshhits};
 #pragma unroll
     for (int k = 0; k < 8; k++) {
         uint32_t s = wave_sum(vals[k]);
         if (lane == 0 && s) atomicAdd(&counters->v[k], (unsigned long long)s);
+    }
+    if constexpr (COUNTS) inspect_reduce(lane, primTraversed, primTested, inspect_out(extra...).sums);
+}
+
+// ------------------------------------------------------------------------------------------------------------
+// The Whitted renderer's "Inspect traversal" / "Inspect intersection" views (renderer.cpp:38-39, infra/helper.h:104-120): Trace returns
+// GetTraverseCountColor(count, peak) for a primary ray that hits anything, the sky colour otherwise, with `peak` as the pixels before it in row-major order left it:
+//     peakIn(i) = max(peak carried into the Tick, max over j < i of count(j)),  i = x + y * W
+// Two launches, no host round trip: inspect_primary_kernel traces one ray per pixel and leaves the counts, the metrics and one maximum per kInspectBlock pixels;
+// inspect_color_kernel forms the exclusive prefix maximum (carry-in from the earlier blocks' maxima, scan in the block) and colours.
+// ------------------------------------------------------------------------------------------------------------
+constexpr uint32_t kInspectBlock = 1024;            // pixels per block of inspect_color_kernel (= per entry of blockMax)
+constexpr uint32_t kInspectPending = 0xff000000u;   // screen value of a hit pixel between the two passes (a finished pixel is below 2^24)
+
+template <int ACCEL, class ALT = AltAccelDev>
+__global__ __launch_bounds__(64) void inspect_primary_kernel(const Scene sc, const ALT alt, float4* __restrict__ acc, uint32_t* __restrict__ pixels, Counters* __restrict__ counters,
+                                                             int32_t* __restrict__ travOut, int32_t* __restrict__ testedOut, InspectSums* __restrict__ sums,
+                                                             int32_t* __restrict__ blockMax, int useTested)
+{
+    extern __shared__ uint32_t lds[];
+    const uint32_t lane = threadIdx.x;
+    const uint32_t idx = blockIdx.x * 64u + lane;
+    const uint32_t W = (uint32_t)sc.W, H = (uint32_t)sc.H;
+    uint32_t* stk = lds + lane;
+    Cnt cn; cn.rays = cn.primary = cn.interior = cn.leaf = cn.tri = cn.tlas = cn.visits = cn.meshhits = 0;
+    int traversed = 0, tested = 0;
+    if (idx < W * H) {
+        const uint32_t x = idx % W, y = idx / W;
+        const f3 camPos = mk3(sc.camPos[0], sc.camPos[1], sc.camPos[2]);
+        const f3 TL = mk3(sc.topLeft[0], sc.topLeft[1], sc.topLeft[2]);
+        const f3 TR = mk3(sc.topRight[0], sc.topRight[1], sc.topRight[2]);
+        const f3 BL = mk3(sc.bottomLeft[0], sc.bottomLeft[1], sc.bottomLeft[2]);
+        const float u = (float)x * sc.invW, v = (float)y * sc.invH;                   // whitted_kernel's primary ray
+        const f3 P = TL + u * (TR - TL) + v * (BL - TL);
+        const f3 O = camPos, D = normalize3(P - camPos);
+        cn.primary++;
+        Hit h; h.t = 1e34f; h.u = 0; h.v = 0; h.objIdx = -1; h.triIdx = -1;
+        const f3 rD = mk3(1 / D.x, 1 / D.y, 1 / D.z);
+        if (ACCEL == 0) find_nearest_seq(sc, O, D, rD, h, stk, cn, traversed, tested);
+        else {
+            cn.rays++;
+            hit_light_floor(sc, O, D, h);
+            alt_walk<ACCEL>(sc, alt, O, D, rD, h, stk, traversed, tested);
+            if (h.objIdx >= 2) cn.meshhits++;
+        }
+        travOut[idx] = traversed; testedOut[idx] = tested;
+        if (h.objIdx == -1) {                                                          // a miss is the sky in every mode (renderer.cpp:27): finished here
+            const f3 res = sky_color(sc, D);
+            acc[idx] = make_float4(res.x, res.y, res.z, 0.0f);
+            const uint32_t r = (uint32_t)(255.0f * min_std(1.0f, res.x)), g = (uint32_t)(255.0f * min_std(1.0f, res.y)), bb = (uint32_t)(255.0f * min_std(1.0f, res.z));
+            pixels[idx] = (r << 16) + (g << 8) + bb;
+        } else pixels[idx] = kInspectPending;
+    }
+    uint32_t vals[8] = {cn.rays, cn.primary, cn.interior, cn.leaf, cn.tri, cn.tlas, cn.visits, cn.meshhits};
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+        uint32_t s = wave_sum(vals[k]);
+        if (lane == 0 && s) atomicAdd(&counters->v[k], (unsigned long long)s);
+    }
+    inspect_reduce(lane, traversed, tested, sums);
+    const int32_t m = wave_max(useTested ? tested : traversed);                        // 64 | kInspectBlock: a wavefront's pixels lie in one block of the scan
+    if (lane == 0 && m) atomicMax(&blockMax[idx / kInspectBlock], m);
+}
+
+// GetTraverseCountColor (infra/helper.h:104-120), operation for operation in float32: a true division, separate multiply and add (the tree builds with -ffp-contract=off)
+__device__ __forceinline__ f3 traverse_count_color(int32_t traversed, int32_t peak)
+{
+    const float invMax = 1 / 255.f;
+    const f3 green = mk3(179 * invMax, 255 * invMax, 174 * invMax);
+    const f3 red = mk3(255 * invMax, 50 * invMax, 50 * invMax);
+    if (peak < 10) return green;
+    traversed = traversed < 0 ? 0 : (traversed > peak ? peak : traversed);
+    const float blend = traversed / (float)peak;
+    return mk3(green.x + blend * (red.x - green.x), green.y + blend * (red.y - green.y), green.z + blend * (red.z - green.z));
+}
+
+__global__ __launch_bounds__(1024) void inspect_color_kernel(const int32_t* __restrict__ count, const int32_t* __restrict__ blockMax, int32_t peakIn, uint32_t n,
+                                                             float4* __restrict__ acc, uint32_t* __restrict__ pixels)
+{
+    __shared__ int32_t carryPart[16], waveMax[16];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint32_t idx = blockIdx.x * kInspectBlock + tid;
+    // carry-in: the peak passed in, raised by every earlier block
+    int32_t c = peakIn;
+    for (uint32_t j = tid; j < blockIdx.x; j += kInspectBlock) { const int32_t t = blockMax[j]; c = t > c ? t : c; }
+    c = wave_max(c);
+    // inclusive maximum over the wavefront's pixels up to this lane
+    const int32_t own = idx < n ? count[idx] : 0;
+    int32_t incl = own;
+    for (int o = 1; o < 64; o <<= 1) { const int32_t t = __shfl_up(incl, o, 64); if (lane >= (uint32_t)o && t > incl) incl = t; }
+    if (lane == 0) carryPart[wave] = c;
+    if (lane == 63) waveMax[wave] = incl;
+    __syncthreads();
+    int32_t peak = carryPart[0];
+#pragma unroll
+    for (uint32_t w = 1; w < 16; w++) { const int32_t t = carryPart[w]; peak = t > peak ? t : peak; }
+    for (uint32_t w = 0; w < wave; w++) { const int32_t t = waveMax[w]; peak = t > peak ? t : peak; }
+    const int32_t before = __shfl_up(incl, 1, 64);                                     // exclusive: the lanes before this one
+    if (lane > 0 && before > peak) peak = before;
+    if (idx < n && pixels[idx] == kInspectPending) {
+        const f3 res = traverse_count_color(own, peak);
+        acc[idx] = make_float4(res.x, res.y, res.z, 0.0f);
+        const uint32_t r = (uint32_t)(255.0f * min_std(1.0f, res.x)), g = (uint32_t)(255.0f * min_std(1.0f, res.y)), bb = (uint32_t)(255.0f * min_std(1.0f, res.z));
+        pixels[idx] = (r << 16) + (g << 8) + bb;
     }
 }
 
@@ -1176,6 +1315,52 @@ extern "C" hipError_t crt_launch_whitted(const crt::Scene* sc, int accel, const 
     else if (accel == 2) hipLaunchKernelGGL(crt::whitted_kernel<2>, grid, block, 256u, stream, *sc, *alt, (float4*)acc, pixels, counters);
     else { const crt::AltAccelDev none{}; hipLaunchKernelGGL(crt::whitted_kernel<0>, grid, block, ldsBytes, stream, *sc, none, (float4*)acc, pixels, counters); }
     return hipGetLastError();
+}
+
+// crt_whitted_tick_inspect.  work = InspectSums followed by one int32 per kInspectBlock pixels; zeroed here, on the stream.  inspect 0: whitted_kernel's Tick with the
+// counts (one launch); 1 / 2: the primary pass and the scan + colour pass.
+template <int ACCEL, class ALT>
+static hipError_t launch_whitted_inspect(const crt::Scene& sc, const ALT& alt, uint32_t ldsBytes, int inspect, int32_t peakIn, float4* acc, uint32_t* pixels, crt::Counters* counters,
+                                         int32_t* trav, int32_t* tested, crt::InspectSums* sums, int32_t* blockMax, hipStream_t stream)
+{
+    const uint32_t n = (uint32_t)sc.W * (uint32_t)sc.H;
+    dim3 grid((n + 63u) / 64u), block(64);
+    if (inspect == 0) {
+        const crt::InspectOut out{trav, tested, sums};
+        hipLaunchKernelGGL((crt::whitted_kernel<ACCEL, ALT, crt::InspectOut>), grid, block, ldsBytes, stream, sc, alt, acc, pixels, counters, out);
+        return hipGetLastError();
+    }
+    hipLaunchKernelGGL((crt::inspect_primary_kernel<ACCEL, ALT>), grid, block, ldsBytes, stream, sc, alt, acc, pixels, counters, trav, tested, sums, blockMax, inspect == 2 ? 1 : 0);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(crt::inspect_color_kernel, dim3((n + crt::kInspectBlock - 1u) / crt::kInspectBlock), dim3(crt::kInspectBlock), 0, stream,
+                       inspect == 2 ? tested : trav, blockMax, peakIn, n, acc, pixels);
+    return hipGetLastError();
+}
+
+extern "C" size_t crt_whitted_inspect_work_bytes(uint32_t pixelCount) { return sizeof(crt::InspectSums) + (size_t)((pixelCount + crt::kInspectBlock - 1u) / crt::kInspectBlock) * 4u; }
+
+extern "C" hipError_t crt_launch_whitted_inspect(const crt::Scene* sc, int accel, const crt::AltAccelDev* alt, const crt::TlasAltDev* tl, int inspect, int32_t peakIn, void* acc, uint32_t* pixels,
+                                                 crt::Counters* counters, int32_t* trav, int32_t* tested, void* work, uint32_t ldsBytes, hipStream_t stream)
+{
+    if (inspect < 0 || inspect > 2 || peakIn < 0 || !trav || !tested || !work) return hipErrorInvalidValue;
+    const uint32_t n = (uint32_t)sc->W * (uint32_t)sc->H;
+    uint32_t bytes = 0;
+    if (accel != 0 && sc->kind != 0) {                                    // the stack check of crt_launch_whitted, before anything is written
+        bytes = crt::tlas_alt_stack_words(*sc, *tl) * 64u * 4u;
+        if (bytes > 64u * 1024u) return hipErrorInvalidValue;
+    }
+    if (hipMemsetAsync(work, 0, crt_whitted_inspect_work_bytes(n), stream) != hipSuccess) return hipGetLastError();
+    crt::InspectSums* sums = (crt::InspectSums*)work;
+    int32_t* blockMax = (int32_t*)(sums + 1);
+    if (accel != 0 && sc->kind != 0) {
+        if (accel == 1) return launch_whitted_inspect<1>(*sc, *tl, bytes, inspect, peakIn, (float4*)acc, pixels, counters, trav, tested, sums, blockMax, stream);
+        return launch_whitted_inspect<2>(*sc, *tl, bytes, inspect, peakIn, (float4*)acc, pixels, counters, trav, tested, sums, blockMax, stream);
+    }
+    if (accel == 1) return launch_whitted_inspect<1>(*sc, *alt, alt->kdStack * 128u * 4u, inspect, peakIn, (float4*)acc, pixels, counters, trav, tested, sums, blockMax, stream);
+    if (accel == 2) return launch_whitted_inspect<2>(*sc, *alt, 256u, inspect, peakIn, (float4*)acc, pixels, counters, trav, tested, sums, blockMax, stream);
+    const crt::AltAccelDev none{};
+    return launch_whitted_inspect<0>(*sc, none, ldsBytes, inspect, peakIn, (float4*)acc, pixels, counters, trav, tested, sums, blockMax, stream);
 }
 
 extern "C" hipError_t crt_launch_resolve(const void* acc, uint32_t* pixels, float* tileSums, uint32_t tileFirst, uint32_t tileStride,

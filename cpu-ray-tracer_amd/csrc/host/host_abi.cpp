@@ -161,12 +161,28 @@ int crt_host_renderer_set_camera(crt_host_renderer* r, const float p[3], const f
 {
     if (!r || !p || !t) return CRT_ERR_INVALID;
     r->r->camera.SetCameraState(float3(p[0], p[1], p[2]), float3(t[0], t[1], t[2]));
+    r->r->ResetWhittedPeaks();                                                          // "2. WhittedStyle/renderer.cpp":180-186, 206-212
     return CRT_OK;
 }
 int crt_host_renderer_set_passes(crt_host_renderer* r, int passes) { if (!r || passes < 1 || passes > 4) { g_err = "passes must be 1..4"; return CRT_ERR_INVALID; } r->r->passes = passes; return CRT_OK; }
 int crt_host_renderer_clear(crt_host_renderer* r) { if (!r) return CRT_ERR_INVALID; GUARD_BEGIN r->r->ClearAccumulator(); return CRT_OK; GUARD_END(CRT_ERR_DEVICE) }
 int crt_host_renderer_tick(crt_host_renderer* r, float dt) { if (!r) return CRT_ERR_INVALID; GUARD_BEGIN r->r->Tick(dt); return CRT_OK; GUARD_END(CRT_ERR_DEVICE) }
 int crt_host_renderer_tick_whitted(crt_host_renderer* r) { if (!r) return CRT_ERR_INVALID; GUARD_BEGIN r->r->TickWhitted(); return CRT_OK; GUARD_END(CRT_ERR_DEVICE) }
+int crt_host_renderer_set_inspect(crt_host_renderer* r, int traversal, int tests)
+{
+    if (!r) return CRT_ERR_INVALID;
+    r->r->m_inspectTraversal = traversal != 0; r->r->m_inspectIntersectionTest = tests != 0;
+    return CRT_OK;
+}
+int crt_host_renderer_whitted_metrics(crt_host_renderer* r, crt_whitted_metrics* out, float* averageTraversal, float* averageTests)
+{
+    if (!r) return CRT_ERR_INVALID;
+    const Renderer& R = *r->r;
+    if (out) { out->rayHitCount = R.m_rayHitCount; out->totalTraversal = R.m_totalTraversal; out->totalTests = R.m_totalTests; out->peakTraversal = R.m_peakTraversal; out->peakTests = R.m_peakTests; }
+    if (averageTraversal) *averageTraversal = R.m_averageTraversal;
+    if (averageTests) *averageTests = R.m_averageTests;
+    return CRT_OK;
+}
 int crt_host_renderer_render(crt_host_renderer* r, int frames) { if (!r) return CRT_ERR_INVALID; GUARD_BEGIN r->r->Render(frames); return CRT_OK; GUARD_END(CRT_ERR_DEVICE) }
 int crt_host_renderer_spp(crt_host_renderer* r) { return r ? r->r->spp : CRT_ERR_INVALID; }
 float crt_host_renderer_energy(crt_host_renderer* r) { return r ? r->r->energy : 0.0f; }

@@ -245,7 +245,12 @@ void Renderer::TickWhitted()
 {
     if (!ctx) throw std::runtime_error("Renderer::TickWhitted before Init");
     PushCamera();
-    check(ctx, crt_whitted_tick(ctx, screen ? screen->pixels.data() : nullptr), "crt_whitted_tick");
+    const int inspect = m_inspectTraversal ? CRT_INSPECT_TRAVERSAL : m_inspectIntersectionTest ? CRT_INSPECT_TESTS : CRT_INSPECT_NONE;   // renderer.cpp:38-39: traversal first
+    crt_whitted_metrics m;
+    check(ctx, crt_whitted_tick_inspect(ctx, inspect, m_peakTraversal, m_peakTests, screen ? screen->pixels.data() : nullptr, nullptr, nullptr, &m), "crt_whitted_tick_inspect");
+    m_rayHitCount = m.rayHitCount; m_totalTraversal = m.totalTraversal; m_totalTests = m.totalTests;                                      // :147-152
+    m_peakTraversal = m.peakTraversal; m_peakTests = m.peakTests;
+    if (m_rayHitCount > 0) { m_averageTraversal = (float)m_totalTraversal / (float)m_rayHitCount; m_averageTests = (float)m_totalTests / (float)m_rayHitCount; }   // :164-168
     check(ctx, crt_read_accumulator(ctx, accumulator), "crt_read_accumulator");
 }
 

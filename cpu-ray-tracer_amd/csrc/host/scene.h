@@ -112,6 +112,7 @@ public:
     void Tick(float deltaTime);
     void Render(int frames);       // `frames` Ticks in one submission (no per-frame read-back)
     void TickWhitted();            // one Tick of the Whitted-style renderer ("2. WhittedStyle/renderer.cpp":131-157): accumulator = Trace(primary)
+    void ResetWhittedPeaks() { m_averageTraversal = m_averageTests = 0; m_peakTraversal = m_peakTests = 0; }   // what a camera change does ("2. WhittedStyle/renderer.cpp":180-186, 206-212)
     void Shutdown() {}
     // data members the shell / UI reads (renderer.h:46-53)
     std::vector<float> accumulatorStorage; float* accumulator = nullptr;   // float4[W*H], refreshed by Tick
@@ -122,6 +123,12 @@ public:
     float energy = 0, anim_time = 0;
     // performance report of Tick (renderer.cpp:159-161): running average of the frame time in ms, frames per second, primary rays per ms
     float m_avg = 10, m_fps = 0, m_rps = 0, m_alpha = 1;
+    // the Whitted renderer's inspection switches and metrics ("2. WhittedStyle/renderer.h":25-33); hit count and totals are the last TickWhitted's, as exact integers
+    // (the reference sums them in float), the peaks are carried from Tick to Tick until the camera changes
+    bool m_inspectTraversal = false, m_inspectIntersectionTest = false;
+    uint64_t m_rayHitCount = 0, m_totalTraversal = 0, m_totalTests = 0;
+    float m_averageTraversal = 0, m_averageTests = 0;
+    int m_peakTraversal = 0, m_peakTests = 0;
     int depthLimit = 5;
     Surface* screen = nullptr; Surface ownScreen;
     crt_ctx* ctx = nullptr;

@@ -188,6 +188,34 @@ int  crt_tick(crt_ctx* ctx, uint32_t spp, uint32_t passes, uint32_t* host_pixels
  * Every pixel of the image (rows are not tile-truncated in this renderer) gets accumulator = float4(Trace(primary), 0)
  * and screen pixel = RGBF32_to_RGB8 of it; host_pixels may be NULL.  Synchronous. */
 int  crt_whitted_tick(crt_ctx* ctx, uint32_t* host_pixels /* width*height or NULL */);
+/* The Whitted renderer's traversal inspection and per-Tick metrics (renderer.cpp:38-39, 147-152, 164-189; infra/helper.h:104-120 GetTraverseCountColor).
+ * One Tick as crt_whitted_tick's, which also reports, over the W*H PRIMARY rays, Ray::traversed / Ray::tested per pixel and the Tick's metrics.  In an inspect
+ * mode Trace returns, for a primary ray that hits anything (light quad and floor included; before the isLight test and any recursion, so exactly one ray per
+ * pixel is traced), GetTraverseCountColor(count, peak) with count = traversed / tested and `peak` the renderer's m_peakTraversal / m_peakTests AS IT STANDS
+ * WHEN THAT PIXEL IS TRACED; a miss is the sky colour in every mode.  The reference raises the peaks from unsynchronised OpenMP threads, so only its
+ * single-threaded order defines a picture; that order is served:
+ *     peakIn(i) = max(peak passed in, max over pixels j < i of count(j)),  i = x + y * width   (an exclusive prefix maximum in row-major order)
+ *     pixel(i)  = hit ? GetTraverseCountColor(count(i), peakIn(i)) : sky;   peak < 10 gives green, else green + (count clamped to [0, peak]) / (float)peak * (red - green)
+ * in float32 operation for operation (true division, no fused multiply-add).  The peaks are the caller's state (the reference resets them when the camera
+ * changes, not per Tick): passed in, returned raised.  The context keeps none, so the call is a function of scene, camera, crt_set_render_accel and its arguments.
+ * Every mode writes accumulator = float4(colour, 0) and the screen pixel for all W*H pixels; CRT_INSPECT_NONE leaves exactly crt_whitted_tick's.  Works through
+ * whatever crt_set_render_accel selects.  Synchronous; any output may be NULL.  CRT_ERR_INVALID for a mode outside 0..2 or a negative peak; without a triangle
+ * scene as crt_whitted_tick; a failed call writes nothing.  crt_counters: an inspect mode counts its one ray per pixel, CRT_INSPECT_NONE what crt_whitted_tick counts.
+ * Deviations: `tested` is crt_hit.tested (tests over the whole query, as everywhere in this ABI); the reference keeps its totals in float and adds ray by ray,
+ * which is order-dependent beyond 2^24 — the totals here are the exact integers (average = (float)total / (float)rayHitCount).
+ * Device scratch (two int32 per pixel, one int32 per 1024 pixels) is allocated by the first call and freed by crt_destroy. */
+#define CRT_INSPECT_NONE      0   /* the shaded image of crt_whitted_tick, plus the metrics          */
+#define CRT_INSPECT_TRAVERSAL 1   /* m_inspectTraversal:        heat map of Ray::traversed           */
+#define CRT_INSPECT_TESTS     2   /* m_inspectIntersectionTest: heat map of Ray::tested              */
+typedef struct crt_whitted_metrics {
+    uint64_t rayHitCount;                 /* primary rays with traversed > 0                          */
+    uint64_t totalTraversal, totalTests;  /* exact sums over all W*H primary rays                     */
+    int32_t  peakTraversal, peakTests;    /* max(value passed in, this Tick's maximum)                */
+} crt_whitted_metrics;
+int  crt_whitted_tick_inspect(crt_ctx* ctx, int inspect, int32_t peakTraversalIn, int32_t peakTestsIn,
+                              uint32_t* host_pixels   /* W*H or NULL */,
+                              int32_t* host_traversed /* W*H or NULL */, int32_t* host_tested /* W*H or NULL */,
+                              crt_whitted_metrics* metrics /* or NULL */);
 
 /* ---- query entry = scene.FindNearest(ray) ------------------------------------------------------------ */
 int  crt_find_nearest(crt_ctx* ctx, const crt_ray* rays, crt_hit* hits, size_t n);

@@ -74,6 +74,10 @@ int  crt_host_renderer_clear(crt_host_renderer* r);                             
 int  crt_host_renderer_tick(crt_host_renderer* r, float deltaTime);                 /* Renderer::Tick                */
 int  crt_host_renderer_render(crt_host_renderer* r, int frames);                    /* `frames` Ticks, one submission */
 int  crt_host_renderer_tick_whitted(crt_host_renderer* r);                          /* Tick of the Whitted-style Renderer */
+/* the Whitted Renderer's "Inspect traversal" / "Inspect intersection" check boxes (m_inspectTraversal wins if both are set) and its console report after a
+ * tick_whitted: the Tick's hit count, totals and the peaks carried so far (set_camera resets peaks and averages), and m_averageTraversal / m_averageTests */
+int  crt_host_renderer_set_inspect(crt_host_renderer* r, int traversal, int tests);
+int  crt_host_renderer_whitted_metrics(crt_host_renderer* r, crt_whitted_metrics* out, float* averageTraversal, float* averageTests);
 int  crt_host_renderer_spp(crt_host_renderer* r);
 float crt_host_renderer_energy(crt_host_renderer* r);
 const float* crt_host_renderer_accumulator(crt_host_renderer* r);                   /* float4[width*height]          */
