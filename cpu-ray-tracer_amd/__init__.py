@@ -106,9 +106,11 @@ TLAS_DTYPE = np.dtype([("aabbMin", "<f4", 3), ("leftRight", "<u4"), ("aabbMax", 
 RAY_DTYPE = np.dtype([("O", "<f4", 3), ("D", "<f4", 3), ("inside", "<i4")])
 HIT_DTYPE = np.dtype([("t", "<f4"), ("u", "<f4"), ("v", "<f4"), ("objIdx", "<i4"), ("triIdx", "<i4"), ("traversed", "<i4"), ("tested", "<i4")])
 SHADOW_RAY_DTYPE = np.dtype([("O", "<f4", 3), ("D", "<f4", 3), ("t", "<f4")])     # crt_shadow_ray: the argument of IsOccluded
+HIT_INFO_DTYPE = np.dtype([("I", "<f4", 3), ("material", "<i4"), ("N", "<f4", 3), ("u", "<f4"), ("albedo", "<f4", 3), ("v", "<f4")])   # crt_hit_info (48 bytes)
+MATERIAL_MISS, MATERIAL_INVALID = -1, -2       # crt_hit_info.material of a miss / of a record whose objIdx or triIdx the scene does not have
 
 # every symbol include/crt_abi.h and include/crt_host.h declare (tests check the library exports all of them)
-ABI_SYMBOLS = ["crt_upload_blas_accel", "crt_is_occluded", "crt_find_nearest_device", "crt_is_occluded_device", "crt_upload_primitive_scene", "crt_set_render_accel", "crt_upload_alt_accel", "crt_find_nearest_alt", "crt_update_scene", "crt_abi_version", "crt_device_count", "crt_create", "crt_destroy", "crt_last_error", "crt_upload_scene", "crt_set_camera",
+ABI_SYMBOLS = ["crt_get_hit_info", "crt_get_hit_info_device", "crt_get_sky_color", "crt_get_sky_color_device", "crt_get_light", "crt_upload_blas_accel", "crt_is_occluded", "crt_find_nearest_device", "crt_is_occluded_device", "crt_upload_primitive_scene", "crt_set_render_accel", "crt_upload_alt_accel", "crt_find_nearest_alt", "crt_update_scene", "crt_abi_version", "crt_device_count", "crt_create", "crt_destroy", "crt_last_error", "crt_upload_scene", "crt_set_camera",
                "crt_render", "crt_tick", "crt_reserve", "crt_whitted_tick", "crt_whitted_tick_inspect", "crt_sync", "crt_clear", "crt_read_accumulator", "crt_resolve_screen", "crt_find_nearest", "crt_get_counters",
                "crt_reset_counters", "crt_get_timing", "crt_get_tile_clocks", "crt_bind_accumulator", "crt_accumulator_device_ptr"]
 HOST_SYMBOLS = ["crt_host_scene_blas_alt_info", "crt_host_scene_blas_alt_copy", "crt_host_primitive_scene_create", "crt_host_primitive_scene_free", "crt_host_primitive_scene_set_time", "crt_host_primitive_scene_desc", "crt_host_primitive_scene_upload", "crt_host_scene_build_alt", "crt_host_scene_upload_alt", "crt_host_scene_alt_info", "crt_host_scene_alt_copy", "crt_host_scene_set_transform", "crt_host_scene_update", "crt_host_math_probe", "crt_host_vertex_dedup", "crt_host_last_error", "crt_host_scene_load", "crt_host_scene_free", "crt_host_scene_upload", "crt_host_scene_kind",
@@ -352,6 +354,35 @@ class Context:
         self._ck(self.L.crt_is_occluded(self.h, int(accel), _p(rays), _p(out), C.c_size_t(O.shape[0])))
         return out != 0
 
+    def get_hit_info(self, O, D, hits):
+        """scene.GetHitInfo + material->GetAlbedo per ray (crt_get_hit_info, host buffers, synchronous): O / D = [N, 3], hits = HIT_DTYPE records of any
+        find-nearest entry.  Returns HIT_INFO_DTYPE records; a miss carries the sky colour as albedo and material MATERIAL_MISS."""
+        O = np.asarray(O, np.float32).reshape(-1, 3)
+        D = np.asarray(D, np.float32).reshape(-1, 3)
+        rays = np.zeros(O.shape[0], RAY_DTYPE)
+        rays["O"], rays["D"] = O, D
+        hits = np.ascontiguousarray(hits, HIT_DTYPE).reshape(-1)
+        if hits.shape[0] != O.shape[0]:
+            raise ValueError("get_hit_info: one hit record per ray")
+        out = np.zeros(O.shape[0], HIT_INFO_DTYPE)
+        self._ck(self.L.crt_get_hit_info(self.h, _p(rays), _p(hits), _p(out), C.c_size_t(O.shape[0])))
+        return out
+
+    def get_sky_color(self, D):
+        """scene.GetSkyColor per direction (crt_get_sky_color, host buffers, synchronous).  Returns [N, 3] float32."""
+        D = np.asarray(D, np.float32).reshape(-1, 3)
+        rays = np.zeros(D.shape[0], RAY_DTYPE)
+        rays["D"] = D
+        rgb = np.zeros((D.shape[0], 3), np.float32)
+        self._ck(self.L.crt_get_sky_color(self.h, _p(rays), _p(rgb), C.c_size_t(D.shape[0])))
+        return rgb
+
+    def get_light(self):
+        """(GetLightPos(), GetLightColor()) of the uploaded triangle scene, two float32 [3] arrays"""
+        pos, col = (C.c_float * 3)(), (C.c_float * 3)()
+        self._ck(self.L.crt_get_light(self.h, pos, col))
+        return np.array(pos[:], np.float32), np.array(col[:], np.float32)
+
     # ---- the queries on device buffers (torch tensors; torch is imported only here) ----
     def _records(self, rays, O, D, last, last_is_int, what):
         """the [N, 7] 28-byte records (crt_ray / crt_shadow_ray) on the context's device: `rays` as given, or built from O, D and the last column"""
@@ -410,6 +441,34 @@ class Context:
             return occ
         return self._enqueue(stream, run)
 
+    def get_hit_info_device(self, rays, hits, stream=None):
+        """crt_get_hit_info_device: GetHitInfo + GetAlbedo for rays and hit records that live on the GPU ([N, 7] crt_ray records and the [N, 7] crt_hit records a
+        find_nearest_device call returned), enqueued on `stream` (default torch.cuda.current_stream()) without a host wait.  Returns the [N, 12] float32 tensor of
+        crt_hit_info records (hit_info_fields() splits it)."""
+        import torch
+
+        def run(st):
+            r = self._records(rays, None, None, None, True, "get_hit_info_device")
+            h = self._records(hits, None, None, None, True, "get_hit_info_device")
+            if h.shape[0] != r.shape[0]:
+                raise ValueError("get_hit_info_device: one hit record per ray")
+            out = torch.empty((r.shape[0], 12), dtype=torch.float32, device=r.device)
+            self._ck(self.L.crt_get_hit_info_device(self.h, C.c_void_p(r.data_ptr()), C.c_void_p(h.data_ptr()), C.c_void_p(out.data_ptr()), C.c_size_t(r.shape[0]), C.c_void_p(st.cuda_stream)))
+            return out
+        return self._enqueue(stream, run)
+
+    def get_sky_color_device(self, rays=None, O=None, D=None, stream=None):
+        """crt_get_sky_color_device: GetSkyColor for rays on the GPU ([N, 7] crt_ray records, or O / D = [N, 3] float32; only D is read), enqueued on `stream`.
+        Returns an [N, 3] float32 tensor."""
+        import torch
+
+        def run(st):
+            r = self._records(rays, O, D, None, True, "get_sky_color_device")
+            rgb = torch.empty((r.shape[0], 3), dtype=torch.float32, device=r.device)
+            self._ck(self.L.crt_get_sky_color_device(self.h, C.c_void_p(r.data_ptr()), C.c_void_p(rgb.data_ptr()), C.c_size_t(r.shape[0]), C.c_void_p(st.cuda_stream)))
+            return rgb
+        return self._enqueue(stream, run)
+
     def _enqueue(self, stream, run):
         """run(st) on the torch stream `stream` (default: the current one).  Torch's default stream has the handle 0, which the ABI reads as the context's own
         stream: on it the query runs on a side stream that waits for it and that it waits for in turn (events, no host wait)."""
@@ -459,6 +518,12 @@ def hit_fields(hits):
     import torch
     i = hits.view(torch.int32)
     return dict(t=hits[:, 0], u=hits[:, 1], v=hits[:, 2], objIdx=i[:, 3], triIdx=i[:, 4], traversed=i[:, 5], tested=i[:, 6])
+
+
+def hit_info_fields(info):
+    """the fields of an [N, 12] crt_hit_info record tensor from get_hit_info_device, as views: I / N / albedo [N, 3] float32, u / v float32, material int32"""
+    import torch
+    return dict(I=info[:, 0:3], material=info.view(torch.int32)[:, 3], N=info[:, 4:7], u=info[:, 7], albedo=info[:, 8:11], v=info[:, 11])
 
 
 class HostScene:

@@ -62,9 +62,13 @@ extern "C" hipError_t crt_launch_check_reciprocals(unsigned long long*, hipStrea
 extern "C" hipError_t crt_launch_find_nearest_alt(int, const crt::Scene*, const crt::AltAccelDev*, const void*, void*, uint32_t, uint32_t*, hipStream_t);
 extern "C" hipError_t crt_launch_is_occluded(const crt::Scene*, const void*, int32_t*, uint32_t, uint32_t, uint32_t*, hipStream_t);
 extern "C" hipError_t crt_launch_is_occluded_alt(int, const crt::Scene*, const crt::AltAccelDev*, const void*, int32_t*, uint32_t, uint32_t*, hipStream_t);
+extern "C" hipError_t crt_launch_hit_info(const crt::Scene*, const void*, const void*, void*, uint32_t, uint32_t, uint32_t, hipStream_t);
+extern "C" hipError_t crt_launch_sky_color(const crt::Scene*, const void*, float*, uint32_t, hipStream_t);
 extern "C" hipError_t crt_launch_tlas_alt_query(int, bool, const crt::Scene*, const crt::TlasAltDev*, const void*, void*, uint32_t, uint32_t*, hipStream_t);
 static_assert(sizeof(crt::BlasAltDesc) == 72, "BLAS descriptor");
 static_assert(sizeof(crt_shadow_ray) == 28 && sizeof(crt_ray) == 28 && sizeof(crt_hit) == 28, "query records");
+static_assert(sizeof(crt_hit_info) == 48 && offsetof(crt_hit_info, material) == 12 && offsetof(crt_hit_info, N) == 16 && offsetof(crt_hit_info, albedo) == 32 && offsetof(crt_hit_info, v) == 44, "crt_hit_info: three 16-byte pieces");
+static_assert(sizeof(crt::Instance) == 128 && offsetof(crt::Instance, triCount) == 112, "Instance record");
 
 namespace {
 
@@ -122,6 +126,7 @@ struct crt_ctx {
     bool haveScene = false;
     // what crt_update_scene needs of the last upload: a host mirror of the geometry buffer and where each BVH's records start
     struct Flat { int32_t kind = 0; uint64_t leafOff = 0, tlasOff = 0, tlasPairOff = 0, instOff = 0, shadeOff = 0; uint32_t tlasNodeCount = 0, maxHeight = 0;
+                  uint32_t objects = 0;           // objCount (FileScene) / bvhCount (two-level): the objIdx a hit record may carry is below 2 + objects
                   std::vector<uint64_t> pairBase, triBase; std::vector<uint32_t> nodesUsed, triCount; std::vector<char> geom;
                   std::vector<float> rootBox; } flat;     // rootBox: every BVH's node 0 box (min xyz, max xyz), what crt_upload_blas_accel checks the BLAS structures against
     char* hStage[2] = {nullptr, nullptr}; size_t stageBytes[2] = {0, 0}; hipEvent_t stageCopied[2] = {nullptr, nullptr}; int stageFlip = 0;
@@ -134,6 +139,7 @@ struct crt_ctx {
     crt::TlasAltDev blasAlt[2]{}; bool haveBlas[2] = {false, false}; std::vector<void*> blasAllocs[2];
     bool hasAlt(int kind) const { return (kind == CRT_ACCEL_KDTREE && (haveKd || haveBlas[0])) || (kind == CRT_ACCEL_GRID && (haveGrid || haveBlas[1])); }
     void* dQueryRays = nullptr; void* dQueryHits = nullptr; size_t queryCap = 0;      // crt_find_nearest staging (rays)
+    void* dShadeStage = nullptr; size_t shadeStageBytes = 0;                          // crt_get_hit_info / crt_get_sky_color staging (output, rays, hits)
     // Device-buffer queries (crt_find_nearest_device / crt_is_occluded_device) on callers' streams: each launch draws its rays from a cursor word of its own
     // (slot k at dQuerySlots + 16k, one cache line each), handed out as a ring; `done` is recorded on the caller's stream behind the launch, and a slot is
     // reused only after its event has completed.  The same events order later scene writes behind the queries still in flight (order_behind_queries).
@@ -399,6 +405,7 @@ void crt_destroy(crt_ctx* c)
     if (c->descReady) (void)hipEventDestroy(c->descReady);
     if (c->dQueryRays) (void)hipFree(c->dQueryRays);
     if (c->dQueryHits) (void)hipFree(c->dQueryHits);
+    if (c->dShadeStage) (void)hipFree(c->dShadeStage);
     for (int k = 0; k < 2; k++) { if (c->hTileOrder[k]) (void)hipHostFree(c->hTileOrder[k]); if (c->orderCopied[k]) (void)hipEventDestroy(c->orderCopied[k]); }
     for (int k = 0; k < 2; k++) { if (c->hStage[k]) (void)hipHostFree(c->hStage[k]); if (c->stageCopied[k]) (void)hipEventDestroy(c->stageCopied[k]); }
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -530,7 +537,7 @@ int crt_upload_scene(crt_ctx* c, const crt_scene_desc* sd)
         if (sd->kind == CRT_SCENE_TLAS) {
             crt::Instance& in = inst[bi];
             memcpy(in.invT, b.invT, 48); memcpy(in.T, b.T, 48);
-            in.shadeBase = (uint32_t)triBase; in.rootRef16 = rootRef16; in.rootRef = rootRef; in.objIdx = b.objIdx;
+            in.shadeBase = (uint32_t)triBase; in.rootRef16 = rootRef16; in.rootRef = rootRef; in.objIdx = b.objIdx; in.triCount = b.triCount;
         } else { rootRef0 = rootRef; rootRef0_16 = rootRef16; }
         pairBase += b.nodesUsed / 2; triBase += b.triCount;
     }
@@ -662,6 +669,7 @@ int crt_upload_scene(crt_ctx* c, const crt_scene_desc* sd)
         crt_ctx::Flat& f = c->flat;
         f.kind = sd->kind; f.leafOff = leafOffB; f.tlasOff = tlasOffB; f.tlasPairOff = tlasPairOffB; f.instOff = instOffB; f.shadeOff = shadeOffB;
         f.tlasNodeCount = (sd->kind == CRT_SCENE_TLAS) ? sd->tlasNodeCount : 0; f.maxHeight = maxHeight;
+        f.objects = (sd->kind == CRT_SCENE_TLAS) ? sd->bvhCount : sd->objCount;
         f.pairBase.clear(); f.triBase.clear(); f.nodesUsed.clear(); f.triCount.clear(); f.rootBox.clear();
         for (uint32_t bi = 0; bi < sd->bvhCount; bi++) { const crt_bvh_node& r = sd->bvhs[bi].nodes[0]; f.rootBox.insert(f.rootBox.end(), r.aabbMin, r.aabbMin + 3); f.rootBox.insert(f.rootBox.end(), r.aabbMax, r.aabbMax + 3); }
         uint64_t pb = 0, tb = 0;
@@ -2113,6 +2121,30 @@ static int take_query_slot(crt_ctx* c, int* out)
     return 0;
 }
 
+// what every device query shares: the caller's stream (checked; NULL = the ctx's own), ordered behind the scene's last in-place update, and a slot of the ring for
+// the event that later scene writes wait for ...
+static int begin_device_query(crt_ctx* c, void* stream, const char* what, hipStream_t* stOut, int* slotOut)
+{
+    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : c->stream;
+    if (stream) {
+        hipDevice_t dev = -1;
+        HIPCK(c, hipStreamGetDevice(st, &dev));
+        if (dev != c->cfg.device) return c->fail(CRT_ERR_INVALID, "%s: the stream belongs to device %d, the context to device %d", what, dev, c->cfg.device);
+    }
+    // the scene as of the last upload / update: in-place updates are copies on the main stream (sceneReady)
+    if (c->sceneReady) HIPCK(c, hipStreamWaitEvent(st, c->sceneReady, 0));
+    *stOut = st;
+    return take_query_slot(c, slotOut);
+}
+
+// ... recorded behind the launch (order_behind_queries / wait_queries look at it; so does the slot's next use)
+static int end_device_query(crt_ctx* c, int k, hipStream_t st)
+{
+    HIPCK(c, hipEventRecord(c->qslot[k].done, st));
+    c->qslot[k].pending = true;
+    return CRT_OK;
+}
+
 static int query_device(crt_ctx* c, bool occl, int accel, const void* dRays, void* dOut, size_t n, void* stream, const char* what)
 {
     int r;
@@ -2120,17 +2152,9 @@ static int query_device(crt_ctx* c, bool occl, int accel, const void* dRays, voi
     if (n == 0) return CRT_OK;
     HIPCK(c, hipSetDevice(c->cfg.device));
     if ((r = check_device_buffer(c, dRays, n * 28, what)) || (r = check_device_buffer(c, dOut, n * (occl ? 4 : 28), what))) return r;
-    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : c->stream;
-    if (stream) {
-        hipDevice_t dev = -1;
-        HIPCK(c, hipStreamGetDevice(st, &dev));
-        if (dev != c->cfg.device) return c->fail(CRT_ERR_INVALID, "%s: the stream belongs to device %d, the context to device %d", what, dev, c->cfg.device);
-    }
-    // the scene as of the last upload / update: in-place updates are copies on the main stream (sceneReady), the accelerators' copies ran on the null stream
-    if (c->sceneReady) HIPCK(c, hipStreamWaitEvent(st, c->sceneReady, 0));
-    if (accel != 0 && c->altReady) HIPCK(c, hipStreamWaitEvent(st, c->altReady, 0));
-    int k = 0;
-    if ((r = take_query_slot(c, &k))) return r;
+    hipStream_t st = nullptr; int k = 0;
+    if ((r = begin_device_query(c, stream, what, &st, &k))) return r;
+    if (accel != 0 && c->altReady) HIPCK(c, hipStreamWaitEvent(st, c->altReady, 0));     // the accelerators' copies ran on the null stream
     uint32_t* cursor = c->dQuerySlots + 16 * k;
     if (occl) {
         if (accel == 0) HIPCK(c, crt_launch_is_occluded(&c->hScene, dRays, static_cast<int32_t*>(dOut), (uint32_t)n, c->ldsBytes, cursor, st));
@@ -2142,10 +2166,7 @@ static int query_device(crt_ctx* c, bool occl, int accel, const void* dRays, voi
     } else {
         HIPCK(c, crt_launch_find_nearest(&c->hScene, dRays, dOut, (uint32_t)n, c->dCounters, c->ldsBytes, cursor, st));
     }
-    // later scene writes wait for this event (order_behind_queries / wait_queries); so does the slot's next use
-    HIPCK(c, hipEventRecord(c->qslot[k].done, st));
-    c->qslot[k].pending = true;
-    return CRT_OK;
+    return end_device_query(c, k, st);
 }
 
 int crt_find_nearest_device(crt_ctx* c, int accel, const crt_ray* d_rays, crt_hit* d_hits, size_t n, void* stream)
@@ -2183,6 +2204,112 @@ int crt_is_occluded(crt_ctx* c, int accel, const crt_shadow_ray* rays, int32_t* 
     else HIPCK(c, launch_alt_query(c, accel, true, c->dQueryRays, dOut, (uint32_t)n, c->dQueryCursor, c->stream));
     HIPCK(c, hipMemcpyAsync(occluded, dOut, n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     HIPCK(c, hipStreamSynchronize(c->stream));
+    return CRT_OK;
+}
+
+// ---- shading queries: GetHitInfo + GetAlbedo, GetSkyColor, GetLightPos / GetLightColor (crt_abi.h "scene queries") ----
+// query_check's checks for them (the scene's own records: accel 0); the PrimitiveScene has a sky (black) and no hit info
+static int shade_check(crt_ctx* c, bool hitInfo, size_t n, const char* what)
+{
+    if (hitInfo && c->havePrim) return c->fail(CRT_ERR_UNSUPPORTED, "%s: GetHitInfo of the PrimitiveScene is not served (crt_abi.h)", what);
+    return query_check(c, 0, false, n, what);
+}
+
+// hit_record_ok's bounds for the uploaded scene
+static uint32_t file_tri_count(const crt_ctx* c) { return c->flat.kind == CRT_SCENE_FILE ? c->flat.triCount[0] : 0u; }
+
+// the host entries' device staging, grown to the high-water mark (hipMalloc'ed: 16-byte aligned)
+static int shade_stage(crt_ctx* c, size_t bytes)
+{
+    if (bytes <= c->shadeStageBytes) return 0;
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    if (c->dShadeStage) (void)hipFree(c->dShadeStage);
+    c->dShadeStage = nullptr; c->shadeStageBytes = 0;
+    HIPCK(c, hipMalloc(&c->dShadeStage, bytes));
+    c->shadeStageBytes = bytes;
+    return 0;
+}
+
+int crt_get_hit_info(crt_ctx* c, const crt_ray* rays, const crt_hit* hits, crt_hit_info* out, size_t n)
+{
+    if (!c) return CRT_ERR_INVALID;
+    int r;
+    if ((r = shade_check(c, true, n, "crt_get_hit_info"))) return r;
+    if (n == 0) return CRT_OK;
+    if (!rays || !hits || !out) return c->fail(CRT_ERR_INVALID, "crt_get_hit_info: NULL buffer");
+    // objIdx / triIdx index device memory: every record is checked here, before anything is copied or launched (the kernel applies the same predicate per lane)
+    const crt_ctx::Flat& f = c->flat;
+    for (size_t i = 0; i < n; i++)
+        if (!crt::hit_record_ok(hits[i].objIdx, hits[i].triIdx, f.objects, [&](uint32_t k) { return f.triCount[f.kind == CRT_SCENE_TLAS ? k : 0]; }))
+            return c->fail(CRT_ERR_INVALID, "crt_get_hit_info: record %zu names objIdx %d, triIdx %d; the scene has objects -1 .. %u and that object's BVH fewer triangles", i, hits[i].objIdx, hits[i].triIdx, f.objects + 1);
+    HIPCK(c, hipSetDevice(c->cfg.device));
+    if ((r = shade_stage(c, n * (sizeof(crt_hit_info) + sizeof(crt_ray) + sizeof(crt_hit))))) return r;
+    char* dOut = static_cast<char*>(c->dShadeStage); char* dRays = dOut + n * sizeof(crt_hit_info); char* dHits = dRays + n * sizeof(crt_ray);
+    HIPCK(c, hipMemcpyAsync(dRays, rays, n * sizeof(crt_ray), hipMemcpyHostToDevice, c->stream));
+    HIPCK(c, hipMemcpyAsync(dHits, hits, n * sizeof(crt_hit), hipMemcpyHostToDevice, c->stream));
+    HIPCK(c, crt_launch_hit_info(&c->hScene, dRays, dHits, dOut, (uint32_t)n, f.objects, file_tri_count(c), c->stream));
+    HIPCK(c, hipMemcpyAsync(out, dOut, n * sizeof(crt_hit_info), hipMemcpyDeviceToHost, c->stream));
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    return CRT_OK;
+}
+
+int crt_get_hit_info_device(crt_ctx* c, const crt_ray* d_rays, const crt_hit* d_hits, crt_hit_info* d_out, size_t n, void* stream)
+{
+    if (!c) return CRT_ERR_INVALID;
+    const char* what = "crt_get_hit_info_device";
+    int r;
+    if ((r = shade_check(c, true, n, what))) return r;
+    if (n == 0) return CRT_OK;
+    HIPCK(c, hipSetDevice(c->cfg.device));
+    if ((r = check_device_buffer(c, d_rays, n * sizeof(crt_ray), what)) || (r = check_device_buffer(c, d_hits, n * sizeof(crt_hit), what)) ||
+        (r = check_device_buffer(c, d_out, n * sizeof(crt_hit_info), what))) return r;
+    if (reinterpret_cast<uintptr_t>(d_out) & 15u) return c->fail(CRT_ERR_INVALID, "%s: the output buffer %p is not 16-byte aligned", what, (void*)d_out);
+    hipStream_t st = nullptr; int k = 0;
+    if ((r = begin_device_query(c, stream, what, &st, &k))) return r;       // the slot's cursor word is unused: a record per lane, nothing to draw
+    HIPCK(c, crt_launch_hit_info(&c->hScene, d_rays, d_hits, d_out, (uint32_t)n, c->flat.objects, file_tri_count(c), st));
+    return end_device_query(c, k, st);
+}
+
+int crt_get_sky_color(crt_ctx* c, const crt_ray* rays, float* rgb, size_t n)
+{
+    if (!c) return CRT_ERR_INVALID;
+    int r;
+    if ((r = shade_check(c, false, n, "crt_get_sky_color"))) return r;
+    if (n == 0) return CRT_OK;
+    if (!rays || !rgb) return c->fail(CRT_ERR_INVALID, "crt_get_sky_color: NULL buffer");
+    if (c->havePrim) { memset(rgb, 0, n * 12); return CRT_OK; }                // PrimitiveScene::GetSkyColor
+    HIPCK(c, hipSetDevice(c->cfg.device));
+    if ((r = shade_stage(c, n * (12 + sizeof(crt_ray))))) return r;
+    float* dOut = static_cast<float*>(c->dShadeStage); char* dRays = static_cast<char*>(c->dShadeStage) + n * 12;
+    HIPCK(c, hipMemcpyAsync(dRays, rays, n * sizeof(crt_ray), hipMemcpyHostToDevice, c->stream));
+    HIPCK(c, crt_launch_sky_color(&c->hScene, dRays, dOut, (uint32_t)n, c->stream));
+    HIPCK(c, hipMemcpyAsync(rgb, dOut, n * 12, hipMemcpyDeviceToHost, c->stream));
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    return CRT_OK;
+}
+
+int crt_get_sky_color_device(crt_ctx* c, const crt_ray* d_rays, float* d_rgb, size_t n, void* stream)
+{
+    if (!c) return CRT_ERR_INVALID;
+    const char* what = "crt_get_sky_color_device";
+    int r;
+    if ((r = shade_check(c, false, n, what))) return r;
+    if (n == 0) return CRT_OK;
+    HIPCK(c, hipSetDevice(c->cfg.device));
+    if ((r = check_device_buffer(c, d_rays, n * sizeof(crt_ray), what)) || (r = check_device_buffer(c, d_rgb, n * 12, what))) return r;
+    hipStream_t st = nullptr; int k = 0;
+    if ((r = begin_device_query(c, stream, what, &st, &k))) return r;
+    if (c->havePrim) HIPCK(c, hipMemsetAsync(d_rgb, 0, n * 12, st));          // PrimitiveScene::GetSkyColor
+    else HIPCK(c, crt_launch_sky_color(&c->hScene, d_rays, d_rgb, (uint32_t)n, st));
+    return end_device_query(c, k, st);
+}
+
+int crt_get_light(crt_ctx* c, float pos[3], float color[3])
+{
+    if (!c || !pos || !color) return CRT_ERR_INVALID;
+    if (!c->haveScene) return c->fail(c->havePrim ? CRT_ERR_UNSUPPORTED : CRT_ERR_STATE, "crt_get_light needs a triangle scene (crt_upload_scene)");
+    memcpy(pos, c->hScene.lightPos, 12);
+    color[0] = 24.0f; color[1] = 24.0f; color[2] = 22.0f;                      // GetLightColor, file_scene.cpp:164-168
     return CRT_OK;
 }
 

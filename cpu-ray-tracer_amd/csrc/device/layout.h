@@ -62,7 +62,8 @@ struct alignas(16) Instance {             // 128 B
     uint32_t rootRef;                     // packed reference of the BLAS's node 0
     int32_t objIdx;
     float T[12];                          // rows 0..2 of BLASBVH::T    (normal -> world space)
-    uint32_t pad[4];
+    uint32_t triCount;                    // triangles of this BLAS: the bound of a BLAS-local triIdx (hit_record_ok)
+    uint32_t pad[3];
 };
 
 struct alignas(16) Material {             // 32 B: material + its texture descriptor in one record
@@ -101,6 +102,22 @@ struct Scene {                            // passed to the kernels BY VALUE (ker
 };
 
 struct Counters { unsigned long long v[8]; };   // order = crt_counters
+
+// Whether a crt_hit's indices may be used as addresses by the hit-info query (shade_query.hip): ONE predicate for the host entry, which refuses the call, and for
+// the kernel, which writes CRT_MATERIAL_INVALID for the lane.  objects = crt_scene_desc.objCount (FileScene) / bvhCount (two-level); triCountOf(k) = triangles of
+// the BVH that object 2 + k's triIdx indexes (FileScene: its one BVH; two-level: BLAS k), asked only for an object that exists.
+#if defined(__HIPCC__)
+#define CRT_HOST_DEVICE __host__ __device__
+#else
+#define CRT_HOST_DEVICE
+#endif
+template <class TriCountOf>
+CRT_HOST_DEVICE inline bool hit_record_ok(int32_t objIdx, int32_t triIdx, uint32_t objects, TriCountOf&& triCountOf)
+{
+    if (objIdx < 2) return objIdx >= -1;                                  // miss, light quad, floor plane: triIdx is not looked at
+    if ((uint32_t)(objIdx - 2) >= objects) return false;
+    return triIdx >= 0 && (uint32_t)triIdx < triCountOf((uint32_t)(objIdx - 2));
+}
 
 // A two-level scene's set of BLASKDTree / BLASGrid structures (crt_upload_blas_accel): every BLAS's arrays are concatenated, a descriptor per BLAS
 // says where its part starts.  Triangle records are alt_common.h's AltTri (triIdx = the GLOBAL shade index, objIdx = the BLAS's), in each BLAS's order.

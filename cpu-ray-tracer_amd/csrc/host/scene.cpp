@@ -27,6 +27,8 @@ void BaseScene::LoadCommon(const SceneData& sd, const std::string& baseDir)
     textures.clear();
     textures.push_back(LoadImage(resolve(baseDir, sd.planeTextureLocation)));      // primitiveMaterials[1].textureDiffuse
     textures.push_back(LoadImage(resolve(baseDir, sd.skydomeLocation)));           // skydome
+    primitiveMaterials[0] = Material(); primitiveMaterials[0].isLight = true;
+    primitiveMaterials[1] = Material(); primitiveMaterials[1].texture = 0;
     objIdUsed = 2;
     lightSize = 1 * 0.5f;                                                            // Quad(0, 1): size = s * 0.5f
     floorN = float3(0, 1, 0); floorD = 1;
@@ -116,6 +118,30 @@ bool BaseScene::IsOccluded(const Ray& ray)
     r.O[0] = ray.O.x; r.O[1] = ray.O.y; r.O[2] = ray.O.z; r.D[0] = ray.D.x; r.D[1] = ray.D.y; r.D[2] = ray.D.z; r.t = ray.t;
     check(bound, crt_is_occluded(bound, 0, &r, &occluded, 1), "crt_is_occluded");
     return occluded != 0;
+}
+
+HitInfo BaseScene::GetHitInfo(const Ray& ray, const float3& I)
+{
+    if (!bound) throw std::runtime_error("GetHitInfo: scene not uploaded to a device context");
+    if (ray.objIdx < 0) throw std::runtime_error("GetHitInfo: the ray has no hit (objIdx -1): ask GetSkyColor");
+    crt_ray r; crt_hit h; crt_hit_info o;
+    r.O[0] = ray.O.x; r.O[1] = ray.O.y; r.O[2] = ray.O.z; r.D[0] = ray.D.x; r.D[1] = ray.D.y; r.D[2] = ray.D.z; r.inside = ray.inside;
+    h.t = ray.t; h.u = ray.barycentric.x; h.v = ray.barycentric.y; h.objIdx = ray.objIdx; h.triIdx = ray.triIdx; h.traversed = h.tested = 0;
+    check(bound, crt_get_hit_info(bound, &r, &h, &o, 1), "crt_get_hit_info");
+    (void)I;                                                             // the query forms I = O + t * D itself, as every caller of the reference does
+    HitInfo hi;
+    hi.normal = float3(o.N[0], o.N[1], o.N[2]); hi.uv.x = o.u; hi.uv.y = o.v; hi.albedo = float3(o.albedo[0], o.albedo[1], o.albedo[2]);
+    hi.material = o.material < 2 ? &primitiveMaterials[o.material] : materials[(size_t)o.material - 2];
+    return hi;
+}
+
+float3 BaseScene::GetSkyColor(const Ray& ray)
+{
+    if (!bound) throw std::runtime_error("GetSkyColor: scene not uploaded to a device context");
+    crt_ray r; float rgb[3];
+    r.O[0] = ray.O.x; r.O[1] = ray.O.y; r.O[2] = ray.O.z; r.D[0] = ray.D.x; r.D[1] = ray.D.y; r.D[2] = ray.D.z; r.inside = ray.inside;
+    check(bound, crt_get_sky_color(bound, &r, rgb, 1), "crt_get_sky_color");
+    return float3(rgb[0], rgb[1], rgb[2]);
 }
 
 // ---- FileScene ---------------------------------------------------------------------------------------

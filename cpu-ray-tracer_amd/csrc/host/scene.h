@@ -33,6 +33,13 @@ struct Material {                  // template/material.h
     int texture = -1;              // index into BaseScene::textures (the reference owns a Texture through unique_ptr)
 };
 
+struct HitInfo {                   // infra/hit_info.h, plus the albedo the same query computes
+    float3 normal;                 // already flipped to face the ray
+    float2 uv;
+    Material* material = nullptr;  // &primitiveMaterials[0 / 1] or materials[k]
+    float3 albedo;                 // material->GetAlbedo(uv) (template/material.h: the material's texture at uv, or 1)
+};
+
 class BaseScene {                  // infra/scene/base_scene.h
 public:
     virtual ~BaseScene() = default;
@@ -44,6 +51,10 @@ public:
     void FindNearest(Ray& ray);
     // scene.IsOccluded(ray): one shadow ray {O, D, t} through crt_is_occluded (light quad bounded by t, then the BVH / TLAS over the whole ray)
     bool IsOccluded(const Ray& ray);
+    // scene.GetHitInfo(ray, I) for a ray FindNearest has hit (objIdx >= 0): one record through crt_get_hit_info
+    HitInfo GetHitInfo(const Ray& ray, const float3& I);
+    // scene.GetSkyColor(ray): one ray through crt_get_sky_color
+    float3 GetSkyColor(const Ray& ray);
     float3 GetLightPos() const;
     float3 GetLightColor() const { return float3(24, 24, 22); }
     virtual int GetTriangleCount() const = 0;
@@ -52,6 +63,7 @@ public:
     std::string sceneName;
     std::vector<Image> textures;   // [0] floor, [1] skydome, then material textures
     std::vector<Material*> materials;
+    Material primitiveMaterials[2];                          // [0] the light (isLight), [1] the floor (texture 0): file_scene.cpp:10-12
     int objCount = 0, materialCount = 0, objIdUsed = 2;
     mat4 lightT, lightInvT; float lightSize = 0.5f;          // Quad light(0, 1)
     float3 floorN{0, 1, 0}; float floorD = 1, floorInvto = 1; // Plane floor(1, (0,1,0), 1, texW/100)

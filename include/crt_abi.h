@@ -298,6 +298,49 @@ int  crt_is_occluded(crt_ctx* ctx, int accel, const crt_shadow_ray* rays, int32_
 int  crt_find_nearest_device(crt_ctx* ctx, int accel, const crt_ray* d_rays, crt_hit* d_hits, size_t n, void* stream);
 int  crt_is_occluded_device(crt_ctx* ctx, int accel, const crt_shadow_ray* d_rays, int32_t* d_occluded, size_t n, void* stream);
 
+/* The shading queries of BaseScene (base_scene.h:16-32): GetHitInfo + Material::GetAlbedo, GetSkyColor, GetLightPos / GetLightColor.  With FindNearest and
+ * IsOccluded above they are what every integrator of the reference begins with (FindNearest; miss -> GetSkyColor; I = O + t * D; GetHitInfo; GetAlbedo —
+ * "2. WhittedStyle/renderer.cpp":24-32, "3. PathTracer/renderer.cpp":52-61), so a caller can write Trace / Sample outside the library, on device buffers.
+ * ABI version 3 still: the entries are additions, detected by symbol (as crt_whitted_tick_inspect).
+ *
+ * crt_get_hit_info: out[i] from rays[i] (O, D) and hits[i] (t, u, v, objIdx, triIdx), by hits[i].objIdx (file_scene.cpp:189-214, tlas_file_scene.cpp:220-260):
+ *     -1 (miss)             I = N = 0, u = v = 0, material = CRT_MATERIAL_MISS, albedo = GetSkyColor(ray): what Trace / Sample return for a miss
+ *      0 (light quad)       N = Quad::GetNormal = (-T[1], -T[5], -T[9]) (primitives.h:363-367), u = v = 0, material 0, albedo (1, 1, 1) (primitiveMaterials[0], no texture)
+ *      1 (floor plane)      N = floor.N, uv = Plane::GetUV(I) (primitives.h:116-133, with its N.y == 1 test), material 1, albedo = the floor texture at uv (texture.h:61-96)
+ *      >= 2, FileScene      N = normalize((1-u-v) n0 + u n1 + v n2) of triangle triIdx (bvh.cpp:290-305), uv by the same weights, material 2 + models[tri.objIdx-2]->matIdx
+ *      >= 2, TLASFileScene  the same in BLAS objIdx-2 with the BLAS-LOCAL triIdx that crt_hit reports, then N = normalize(TransformVector(N, T)) (blas_bvh.cpp:391-398),
+ *                           material 2 + blas->matIdx
+ * albedo = material->GetAlbedo(uv): the material's texture at uv, or (1, 1, 1); then `if (dot(N, ray.D) > 0) N = -N`, so N faces the ray.  I = ray.O + t * ray.D for
+ * every hit.  t, u, v come from the hit record: a record of ANY find-nearest entry (BVH, KD-tree, grid, the two-level variants) can be fed straight in, and the
+ * query depends neither on crt_set_render_accel nor on the accelerator that produced the hit.  The arithmetic is the render kernels' (the same device functions):
+ * bit for bit what Sample and Trace shade with.
+ * Bad records do not become bad addresses.  objIdx must lie in -1 .. objects + 1 (objects = objCount of a FileScene, bvhCount of a two-level scene) and, for
+ * objIdx >= 2, triIdx in 0 .. the triangle count of that object's BVH - 1.  The host entry checks every record first and returns CRT_ERR_INVALID (the message names
+ * the first bad record) with nothing written; the device entry cannot, so the kernel applies the same test per record and writes material =
+ * CRT_MATERIAL_INVALID, every other field 0, without reading the scene for it.  NaN or out-of-range t, u, v are arithmetic only and pass through: Texture::Sample
+ * clamps uv with clamp(f, 0, 1) = max(0, min(f, 1)), whose comparisons are false for a NaN, so min gives 1, the clamp 1, and a NaN u reads the last column /
+ * a NaN v (1 - 1 = 0) row 0 — a texel inside the texture; the float -> int conversions only ever see values in [0, width] / [0, height].
+ * crt_get_sky_color: rgb[3i .. 3i+2] = GetSkyColor(rays[i]) (file_scene.cpp:142-154; only D is read) for rays without a hit record.
+ * crt_get_light: GetLightPos() (file_scene.cpp:156-162) and GetLightColor() = (24, 24, 22) of the uploaded triangle scene.
+ * Host entries: host pointers, synchronous.  Device entries: as the device entries above (pointers checked, `stream`, the ordering contract — a later
+ * crt_update_scene is ordered behind them, freeing / re-uploading calls wait for them); d_out of crt_get_hit_info_device must also be 16-byte aligned (three
+ * 16-byte stores per record).  n == 0 is a no-op; n > 2^31-1 is CRT_ERR_UNSUPPORTED; no scene is CRT_ERR_STATE.  Nothing is counted in crt_counters and crt_tick's
+ * render-ahead is not disturbed.  PrimitiveScene: crt_get_sky_color* gives 0 (PrimitiveScene::GetSkyColor, primitive_scene.cpp:82-85); crt_get_hit_info* and
+ * crt_get_light are CRT_ERR_UNSUPPORTED — the repo's oracle exports neither the normals nor the albedo overrides of that scene, so nothing could check them. */
+#define CRT_MATERIAL_MISS    (-1)
+#define CRT_MATERIAL_INVALID (-2)
+typedef struct crt_hit_info {          /* 48 bytes; arrays of it 16-byte aligned: three 16-byte stores per record */
+    float I[3];      int32_t material; /* I = ray.O + ray.t * ray.D.  material: 0 = light (primitiveMaterials[0], isLight), 1 = floor
+                                          (primitiveMaterials[1]), 2 + k = crt_scene_desc.materials[k], or one of the two values above */
+    float N[3];      float u;          /* GetHitInfo's normal, already flipped to face the ray; HitInfo::uv.x                          */
+    float albedo[3]; float v;          /* material->GetAlbedo(uv); HitInfo::uv.y                                                        */
+} crt_hit_info;
+int  crt_get_hit_info(crt_ctx* ctx, const crt_ray* rays, const crt_hit* hits, crt_hit_info* out, size_t n);                   /* host pointers, synchronous */
+int  crt_get_hit_info_device(crt_ctx* ctx, const crt_ray* d_rays, const crt_hit* d_hits, crt_hit_info* d_out, size_t n, void* stream);
+int  crt_get_sky_color(crt_ctx* ctx, const crt_ray* rays, float* rgb /* 3 * n */, size_t n);                                  /* host pointers, synchronous */
+int  crt_get_sky_color_device(crt_ctx* ctx, const crt_ray* d_rays, float* d_rgb /* 3 * n */, size_t n, void* stream);
+int  crt_get_light(crt_ctx* ctx, float pos[3], float color[3]);
+
 /* ---- PrimitiveScene (second half): infra/scene/primitive_scene.cpp — the reference's hard-coded demo room (six walls, swinging light quad,
  * bouncing mirror ball, "rounded corners" sphere, spinning glass cube, glass torus; template/primitives.h Sphere :31, Cube :187, Quad :321, Torus :380; the
  * SPEEDTRIX / single-light configuration its headers select).  The binding passes the scene as its constructor + SetTime(t) leave it: the members below.
