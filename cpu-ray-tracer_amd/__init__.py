@@ -110,10 +110,10 @@ HIT_INFO_DTYPE = np.dtype([("I", "<f4", 3), ("material", "<i4"), ("N", "<f4", 3)
 MATERIAL_MISS, MATERIAL_INVALID = -1, -2       # crt_hit_info.material of a miss / of a record whose objIdx or triIdx the scene does not have
 
 # every symbol include/crt_abi.h and include/crt_host.h declare (tests check the library exports all of them)
-ABI_SYMBOLS = ["crt_get_hit_info", "crt_get_hit_info_device", "crt_get_sky_color", "crt_get_sky_color_device", "crt_get_light", "crt_upload_blas_accel", "crt_is_occluded", "crt_find_nearest_device", "crt_is_occluded_device", "crt_upload_primitive_scene", "crt_set_render_accel", "crt_upload_alt_accel", "crt_find_nearest_alt", "crt_update_scene", "crt_abi_version", "crt_device_count", "crt_create", "crt_destroy", "crt_last_error", "crt_upload_scene", "crt_set_camera",
+ABI_SYMBOLS = ["crt_refit_device", "crt_get_hit_info", "crt_get_hit_info_device", "crt_get_sky_color", "crt_get_sky_color_device", "crt_get_light", "crt_upload_blas_accel", "crt_is_occluded", "crt_find_nearest_device", "crt_is_occluded_device", "crt_upload_primitive_scene", "crt_set_render_accel", "crt_upload_alt_accel", "crt_find_nearest_alt", "crt_update_scene", "crt_abi_version", "crt_device_count", "crt_create", "crt_destroy", "crt_last_error", "crt_upload_scene", "crt_set_camera",
                "crt_render", "crt_tick", "crt_reserve", "crt_whitted_tick", "crt_whitted_tick_inspect", "crt_sync", "crt_clear", "crt_read_accumulator", "crt_resolve_screen", "crt_find_nearest", "crt_get_counters",
                "crt_reset_counters", "crt_get_timing", "crt_get_tile_clocks", "crt_bind_accumulator", "crt_accumulator_device_ptr"]
-HOST_SYMBOLS = ["crt_host_scene_blas_alt_info", "crt_host_scene_blas_alt_copy", "crt_host_primitive_scene_create", "crt_host_primitive_scene_free", "crt_host_primitive_scene_set_time", "crt_host_primitive_scene_desc", "crt_host_primitive_scene_upload", "crt_host_scene_build_alt", "crt_host_scene_upload_alt", "crt_host_scene_alt_info", "crt_host_scene_alt_copy", "crt_host_scene_set_transform", "crt_host_scene_update", "crt_host_math_probe", "crt_host_vertex_dedup", "crt_host_last_error", "crt_host_scene_load", "crt_host_scene_free", "crt_host_scene_upload", "crt_host_scene_kind",
+HOST_SYMBOLS = ["crt_host_scene_bvh_refit_device", "crt_host_scene_blas_alt_info", "crt_host_scene_blas_alt_copy", "crt_host_primitive_scene_create", "crt_host_primitive_scene_free", "crt_host_primitive_scene_set_time", "crt_host_primitive_scene_desc", "crt_host_primitive_scene_upload", "crt_host_scene_build_alt", "crt_host_scene_upload_alt", "crt_host_scene_alt_info", "crt_host_scene_alt_copy", "crt_host_scene_set_transform", "crt_host_scene_update", "crt_host_math_probe", "crt_host_vertex_dedup", "crt_host_last_error", "crt_host_scene_load", "crt_host_scene_free", "crt_host_scene_upload", "crt_host_scene_kind",
                 "crt_host_scene_triangle_count", "crt_host_scene_bvh_count", "crt_host_scene_bvh_info", "crt_host_scene_bvh_copy",
                 "crt_host_scene_bvh_move_and_refit", "crt_host_scene_blas_transform", "crt_host_scene_tlas_copy", "crt_host_camera_state", "crt_host_renderer_create",
                 "crt_host_renderer_destroy", "crt_host_renderer_init", "crt_host_renderer_set_camera", "crt_host_renderer_set_passes",
@@ -469,6 +469,26 @@ class Context:
             return rgb
         return self._enqueue(stream, run)
 
+    def _positions(self, positions, what):
+        """the device pointer and triangle count of a refit's positions: a contiguous float32 tensor [triCount, 3, 3] or [triCount, 9] on the context's device"""
+        import torch
+        if not isinstance(positions, torch.Tensor) or positions.device != torch.device("cuda", self.device):
+            raise ValueError("%s: positions must be a torch tensor on cuda:%d" % (what, self.device))
+        if positions.dtype != torch.float32 or not positions.is_contiguous() or positions.dim() < 2 or tuple(positions.shape[1:]) not in ((3, 3), (9,)):
+            raise ValueError("%s: positions must be a contiguous float32 tensor of shape [triCount, 3, 3] or [triCount, 9]" % what)
+        return C.c_void_p(positions.data_ptr()), C.c_uint32(positions.shape[0])
+
+    def refit_device(self, bvh, positions, stream=None, root_box=True):
+        """crt_refit_device: BVH::Refit of uploaded BVH `bvh` on the GPU from `positions` (vertex0, vertex1, vertex2 per triangle, the reference's triangle order),
+        enqueued on `stream` (default torch.cuda.current_stream()); returns once the refitted root has been read back.  Returns node 0's box as a [2, 3] float32
+        array (aabbMin, aabbMax), or None with root_box=False.  Two-level scenes: the TLAS is the caller's to rebuild (HostScene.refit_device does it)."""
+        def run(st):
+            ptr, n = self._positions(positions, "refit_device")
+            box = (C.c_float * 6)()
+            self._ck(self.L.crt_refit_device(self.h, C.c_uint32(bvh), ptr, n, C.c_void_p(st.cuda_stream), box if root_box else None))
+            return np.array(box[:], np.float32).reshape(2, 3) if root_box else None
+        return self._enqueue(stream, run)
+
     def _enqueue(self, stream, run):
         """run(st) on the torch stream `stream` (default: the current one).  Torch's default stream has the handle 0, which the ABI reads as the context's own
         stream: on it the query runs on a side stream that waits for it and that it waits for in turn (events, no host wait)."""
@@ -484,7 +504,8 @@ class Context:
         with torch.cuda.stream(side):
             out = run(side)
         st.wait_stream(side)
-        out.record_stream(st)                                                 # allocated on the side stream, consumed on st
+        if isinstance(out, torch.Tensor):
+            out.record_stream(st)                                             # allocated on the side stream, consumed on st
         return out
 
     def counters(self):
@@ -575,6 +596,15 @@ class HostScene:
         """BVH::Refit for moved vertices: positions = (triCount, 3, 3) floats in the reference's triangle order; upload() again afterwards"""
         positions = np.ascontiguousarray(positions, np.float32)
         self._ck(self.L.crt_host_scene_bvh_move_and_refit(self.h, int(i), _p(positions), C.c_uint32(positions.shape[0])))
+
+    def refit_device(self, ctx, i, positions, stream=None):
+        """crt_host_scene_bvh_refit_device: Refit of BVH i on the GPU from a positions tensor (Context.refit_device's), then node 0's new box on the host and, for a
+        two-level scene, SetTransform + TLASBVH::Build + update(UPDATE_TRANSFORMS).  The host arrays of BVH i are stale afterwards: upload / update(UPDATE_BOUNDS)
+        raise until move_and_refit(i, ...) brings positions to the host again."""
+        def run(st):
+            ptr, n = ctx._positions(positions, "refit_device")
+            self._ck(self.L.crt_host_scene_bvh_refit_device(self.h, ctx.h, int(i), ptr, n, C.c_void_p(st.cuda_stream)))
+        return ctx._enqueue(stream, run)
 
     def build_alt(self, kind):
         """KDTree::Build / Grid::Build over the FileScene's triangles on the host; returns the flattened structure (the layout crt_upload_alt_accel takes).

@@ -65,6 +65,7 @@ extern "C" hipError_t crt_launch_is_occluded_alt(int, const crt::Scene*, const c
 extern "C" hipError_t crt_launch_hit_info(const crt::Scene*, const void*, const void*, void*, uint32_t, uint32_t, uint32_t, hipStream_t);
 extern "C" hipError_t crt_launch_sky_color(const crt::Scene*, const void*, float*, uint32_t, hipStream_t);
 extern "C" hipError_t crt_launch_tlas_alt_query(int, bool, const crt::Scene*, const crt::TlasAltDev*, const void*, void*, uint32_t, uint32_t*, hipStream_t);
+extern "C" hipError_t crt_launch_refit(char*, uint32_t, uint32_t, uint32_t, uint32_t, const float*, const void*, const uint32_t*, uint32_t, uint32_t, float*, hipStream_t);
 static_assert(sizeof(crt::BlasAltDesc) == 72, "BLAS descriptor");
 static_assert(sizeof(crt_shadow_ray) == 28 && sizeof(crt_ray) == 28 && sizeof(crt_hit) == 28, "query records");
 static_assert(sizeof(crt_hit_info) == 48 && offsetof(crt_hit_info, material) == 12 && offsetof(crt_hit_info, N) == 16 && offsetof(crt_hit_info, albedo) == 32 && offsetof(crt_hit_info, v) == 44, "crt_hit_info: three 16-byte pieces");
@@ -147,6 +148,11 @@ struct crt_ctx {
     uint32_t* dQuerySlots = nullptr;
     struct QuerySlot { hipEvent_t done = nullptr; bool pending = false; } qslot[kQuerySlots];
     int qslotNext = 0;
+    // crt_refit_device: per BVH the bottom-up plan of refit_box_kernel (device/refit.hip), built from the mirror's references by the first refit of that BVH and
+    // freed with the scene; the root's pair + node 0's box come back through `hRefitBack` (pinned) behind the kernels, and `refitDone` is what sceneReady then names
+    struct RefitPlan { void* dPlan = nullptr; uint32_t* dLevelOff = nullptr; uint32_t levels = 0, rootCode = 0; bool built = false; };
+    std::vector<RefitPlan> refitPlans; std::vector<void*> refitAllocs;
+    float* dRefitBack = nullptr; float* hRefitBack = nullptr; hipEvent_t refitFence = nullptr, refitDone = nullptr;
     hipEvent_t altReady = nullptr;        // recorded behind the last crt_upload_alt_accel's copies (device queries on other streams wait for it)
     // Latency mode of single-window launches (render_tiles_kernel's block table), driven by measurement — see next_block_table.  Stage 0 = the table solved from the cost probe's
     // estimates (one wavefront per tile when there was no probe); stages 1 .. kLatStages = tables solved from the tile costs the stage before measured; afterwards the fastest stage is used
@@ -207,6 +213,8 @@ struct crt_ctx {
     {
         for (void* p : sceneAllocs) (void)hipFree(p);
         sceneAllocs.clear(); haveScene = false;
+        for (void* p : refitAllocs) (void)hipFree(p);
+        refitAllocs.clear(); refitPlans.clear();
         if (dPrimTex) { (void)hipFree(dPrimTex); dPrimTex = nullptr; }
         havePrim = false;
         freeAlt();                        // the alternative accelerators index the scene's triangles
@@ -369,6 +377,10 @@ void crt_destroy(crt_ctx* c)
     for (auto& q : c->qslot) if (q.done) { if (q.pending) (void)hipEventSynchronize(q.done); (void)hipEventDestroy(q.done); }   // device queries on callers' streams
     if (c->dQuerySlots) (void)hipFree(c->dQuerySlots);
     if (c->altReady) (void)hipEventDestroy(c->altReady);
+    if (c->refitFence) (void)hipEventDestroy(c->refitFence);
+    if (c->refitDone) (void)hipEventDestroy(c->refitDone);
+    if (c->dRefitBack) (void)hipFree(c->dRefitBack);
+    if (c->hRefitBack) (void)hipHostFree(c->hRefitBack);
     c->freeScene();
     for (auto& a : c->ahead) (void)hipEventDestroy(a.end);
     if (c->aheadStream) (void)hipStreamDestroy(c->aheadStream);
@@ -739,6 +751,13 @@ static void set_root(crt_ctx* c, int kind, const float* lo, const float* hi)
     memcpy(c->meshLo, lo, 12); memcpy(c->meshHi, hi, 12); c->orderDirty = true;
 }
 
+// the reference has no Refit for BLASKDTree / BLASGrid: a refit (CRT_UPDATE_BOUNDS, crt_refit_device) drops the two-level KD-tree / grid sets (their buffers are
+// freed by the next upload)
+static void drop_blas_sets(crt_ctx* c)
+{
+    for (int k = 0; k < 2; k++) if (c->haveBlas[k]) { c->haveBlas[k] = false; if (c->renderAccel == k + 1) c->renderAccel = 0; }
+}
+
 int crt_update_scene(crt_ctx* c, const crt_scene_desc* sd, uint32_t what)
 {
     if (!c || !sd) return CRT_ERR_INVALID;
@@ -797,8 +816,7 @@ int crt_update_scene(crt_ctx* c, const crt_scene_desc* sd, uint32_t what)
         }
         touch(0, (size_t)f.tlasOff);
         for (uint32_t bi = 0; bi < sd->bvhCount; bi++) { memcpy(&f.rootBox[6 * bi], sd->bvhs[bi].nodes[0].aabbMin, 12); memcpy(&f.rootBox[6 * bi + 3], sd->bvhs[bi].nodes[0].aabbMax, 12); }
-        // the reference has no Refit for BLASKDTree / BLASGrid: a refit drops the two-level KD-tree / grid sets (their buffers are freed by the next upload)
-        for (int k = 0; k < 2; k++) if (c->haveBlas[k]) { c->haveBlas[k] = false; if (c->renderAccel == k + 1) c->renderAccel = 0; }
+        drop_blas_sets(c);
     }
     if (f.kind == CRT_SCENE_TLAS) {
         if (what & CRT_UPDATE_TRANSFORMS) {
@@ -2099,6 +2117,18 @@ static int check_device_buffer(crt_ctx* c, const void* p, size_t bytes, const ch
     return 0;
 }
 
+// the stream a device entry was given: a hipStream_t of the context's device (checked), NULL = the ctx's own
+static int caller_stream(crt_ctx* c, void* stream, const char* what, hipStream_t* stOut)
+{
+    *stOut = stream ? static_cast<hipStream_t>(stream) : c->stream;
+    if (stream) {
+        hipDevice_t dev = -1;
+        HIPCK(c, hipStreamGetDevice(*stOut, &dev));
+        if (dev != c->cfg.device) return c->fail(CRT_ERR_INVALID, "%s: the stream belongs to device %d, the context to device %d", what, dev, c->cfg.device);
+    }
+    return 0;
+}
+
 // a cursor slot whose previous launch has completed (all 64 in flight: the host waits for the next one in ring order)
 static int take_query_slot(crt_ctx* c, int* out)
 {
@@ -2125,12 +2155,8 @@ static int take_query_slot(crt_ctx* c, int* out)
 // the event that later scene writes wait for ...
 static int begin_device_query(crt_ctx* c, void* stream, const char* what, hipStream_t* stOut, int* slotOut)
 {
-    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : c->stream;
-    if (stream) {
-        hipDevice_t dev = -1;
-        HIPCK(c, hipStreamGetDevice(st, &dev));
-        if (dev != c->cfg.device) return c->fail(CRT_ERR_INVALID, "%s: the stream belongs to device %d, the context to device %d", what, dev, c->cfg.device);
-    }
+    hipStream_t st = nullptr;
+    { const int r = caller_stream(c, stream, what, &st); if (r) return r; }
     // the scene as of the last upload / update: in-place updates are copies on the main stream (sceneReady)
     if (c->sceneReady) HIPCK(c, hipStreamWaitEvent(st, c->sceneReady, 0));
     *stOut = st;
@@ -2179,6 +2205,97 @@ int crt_is_occluded_device(crt_ctx* c, int accel, const crt_shadow_ray* d_rays, 
 {
     if (!c) return CRT_ERR_INVALID;
     return query_device(c, true, accel, d_rays, d_occluded, n, stream, "crt_is_occluded_device");
+}
+
+// ---- crt_refit_device: BVH::Refit / BLASBVH::Refit of one BVH on the device, from positions in device memory (device/refit.hip) ----
+// the bottom-up plan of BVH `b`, from the mirror's references (which no update ever changes): every node pair with what its two children are, sorted deepest first
+static int build_refit_plan(crt_ctx* c, uint32_t b)
+{
+    const crt_ctx::Flat& f = c->flat;
+    const uint32_t np = f.nodesUsed[b] / 2, nt = f.triCount[b];
+    const crt::NodePair* pairs = reinterpret_cast<const crt::NodePair*>(f.geom.data()) + f.pairBase[b];
+    const uint32_t rootRef = (f.kind == CRT_SCENE_TLAS) ? reinterpret_cast<const crt::Instance*>(f.geom.data() + f.instOff)[b].rootRef : c->hScene.rootRef;
+    bool bad = false;
+    auto code_of = [&](uint32_t ref) -> uint32_t {
+        const uint64_t off = (uint64_t)(ref & crt::kRefOffsetMask) << 4;
+        if (ref & crt::kRefInterior) { const uint64_t i = off / 64u - f.pairBase[b]; if (i >= np) bad = true; return crt::kPlanInterior | (uint32_t)i; }
+        const uint64_t j = (off - f.leafOff) / 48u - f.triBase[b]; if (j >= nt) bad = true;
+        return (uint32_t)j;
+    };
+    crt_ctx::RefitPlan P;
+    P.rootCode = code_of(rootRef);
+    std::vector<uint32_t> depth(np, 0u), count;
+    std::vector<std::pair<uint32_t, uint32_t>> st; size_t visited = 0;
+    if (P.rootCode & crt::kPlanInterior) st.push_back({P.rootCode & ~crt::kPlanInterior, 0u});
+    while (!st.empty() && !bad) {
+        auto [p, d] = st.back(); st.pop_back();
+        if (++visited > np) { bad = true; break; }
+        depth[p] = d; if (count.size() <= d) count.resize(d + 1, 0u);
+        count[d]++;
+        for (int k = 0; k < 2; k++) { const uint32_t cc = code_of(pairs[p].c[k].ref); if (!bad && (cc & crt::kPlanInterior)) st.push_back({cc & ~crt::kPlanInterior, d + 1}); }
+    }
+    if (bad || visited != np) return c->fail(CRT_ERR_INVALID, "crt_refit_device: the references of BVH %u do not form its tree", b);
+    P.levels = (uint32_t)count.size();
+    std::vector<uint32_t> levelOff(P.levels + 1, 0u);                         // level 0 of the plan = the deepest pairs
+    for (uint32_t l = 0; l < P.levels; l++) levelOff[l + 1] = levelOff[l] + count[P.levels - 1 - l];
+    std::vector<crt::RefitPlanRec> recs(np); std::vector<uint32_t> fill(levelOff.begin(), levelOff.end() - 1);
+    for (uint32_t p = 0; p < np; p++) recs[fill[P.levels - 1 - depth[p]]++] = crt::RefitPlanRec{p, {code_of(pairs[p].c[0].ref), code_of(pairs[p].c[1].ref)}, 0u};
+    if (np) {
+        HIPCK(c, hipMalloc(&P.dPlan, (size_t)np * sizeof(crt::RefitPlanRec))); c->refitAllocs.push_back(P.dPlan);
+        HIPCK(c, hipMalloc((void**)&P.dLevelOff, levelOff.size() * 4)); c->refitAllocs.push_back(P.dLevelOff);
+        HIPCK(c, hipMemcpy(P.dPlan, recs.data(), (size_t)np * sizeof(crt::RefitPlanRec), hipMemcpyHostToDevice));
+        HIPCK(c, hipMemcpy(P.dLevelOff, levelOff.data(), levelOff.size() * 4, hipMemcpyHostToDevice));
+    }
+    P.built = true;
+    c->refitPlans[b] = P;
+    return 0;
+}
+
+int crt_refit_device(crt_ctx* c, uint32_t bvh, const float* d_positions, uint32_t triCount, void* stream, float rootBox[6])
+{
+    if (!c) return CRT_ERR_INVALID;
+    if (c->havePrim) return c->fail(CRT_ERR_UNSUPPORTED, "crt_refit_device: the PrimitiveScene has no BVH to refit");
+    if (!c->haveScene) return c->fail(CRT_ERR_STATE, "crt_refit_device before crt_upload_scene");
+    crt_ctx::Flat& f = c->flat;
+    if (bvh >= f.triCount.size()) return c->fail(CRT_ERR_INVALID, "crt_refit_device: BVH %u of a scene with %zu", bvh, f.triCount.size());
+    if (triCount != f.triCount[bvh]) return c->fail(CRT_ERR_INVALID, "crt_refit_device: %u triangles, the uploaded BVH %u has %u (Refit keeps the topology)", triCount, bvh, f.triCount[bvh]);
+    HIPCK(c, hipSetDevice(c->cfg.device));
+    int r;
+    if ((r = check_device_buffer(c, d_positions, (size_t)triCount * 36u, "crt_refit_device"))) return r;
+    hipStream_t st = nullptr;
+    if ((r = caller_stream(c, stream, "crt_refit_device", &st))) return r;
+    if (c->refitPlans.size() != f.triCount.size()) c->refitPlans.assign(f.triCount.size(), crt_ctx::RefitPlan{});
+    if (!c->refitPlans[bvh].built && (r = build_refit_plan(c, bvh))) return r;
+    const crt_ctx::RefitPlan& P = c->refitPlans[bvh];
+    if (!c->dRefitBack) HIPCK(c, hipMalloc((void**)&c->dRefitBack, 128));
+    if (!c->hRefitBack) HIPCK(c, hipHostMalloc((void**)&c->hRefitBack, 128, hipHostMallocDefault));
+    if (!c->refitFence) HIPCK(c, hipEventCreateWithFlags(&c->refitFence, hipEventDisableTiming));
+    if (!c->refitDone) HIPCK(c, hipEventCreateWithFlags(&c->refitDone, hipEventDisableTiming));
+    // In place, as crt_update_scene: the kernels run behind every earlier launch that reads the geometry.  The main stream is ordered behind crt_render's launches
+    // (it waits for each before that launch's accumulate) and carries the host-buffer queries and earlier updates; it is made to wait for the render-ahead launches
+    // and for the device queries in flight, and the caller's stream waits for the main stream up to here (and for an earlier refit on another stream).
+    if ((r = order_behind_ahead(c)) || (r = order_behind_queries(c))) return r;
+    if (st != c->stream) {
+        HIPCK(c, hipEventRecord(c->refitFence, c->stream));
+        HIPCK(c, hipStreamWaitEvent(st, c->refitFence, 0));
+        if (c->sceneReady) HIPCK(c, hipStreamWaitEvent(st, c->sceneReady, 0));
+    }
+    c->epoch++;                                                           // frames rendered ahead by crt_tick are of the old scene
+    HIPCK(c, crt_launch_refit(const_cast<char*>(c->hScene.geom), (uint32_t)f.leafOff, (uint32_t)f.pairBase[bvh], (uint32_t)f.triBase[bvh], triCount, d_positions,
+                              P.dPlan, P.dLevelOff, P.levels, P.rootCode, c->dRefitBack, st));
+    HIPCK(c, hipMemcpyAsync(c->hRefitBack, c->dRefitBack, 88, hipMemcpyDeviceToHost, st));
+    HIPCK(c, hipEventRecord(c->refitDone, st));
+    c->sceneReady = c->refitDone;                                         // launches submitted later wait for it on their own stream; the main stream's own consumers here
+    if (st != c->stream) HIPCK(c, hipStreamWaitEvent(c->stream, c->refitDone, 0));
+    // the one host wait: Scene::rootPair travels in the kernel arguments of every later launch, so the refitted pair has to be on the host before this call returns
+    HIPCK(c, hipEventSynchronize(c->refitDone));
+    const float* back = c->hRefitBack;
+    memcpy(&f.rootBox[6 * (size_t)bvh], back + 16, 24);
+    if (P.rootCode & crt::kPlanInterior) memcpy(f.geom.data() + (size_t)(f.pairBase[bvh] + (P.rootCode & ~crt::kPlanInterior)) * 64u, back, 64);   // the mirror's copy of the root's pair
+    if (f.kind == CRT_SCENE_FILE) set_root(c, CRT_SCENE_FILE, back + 16, back + 19);      // rootPair from the mirror, dispatch-order bounds; a BLAS's box reaches the TLAS through the caller
+    drop_blas_sets(c);
+    if (rootBox) memcpy(rootBox, back + 16, 24);
+    return CRT_OK;
 }
 
 int crt_is_occluded(crt_ctx* c, int accel, const crt_shadow_ray* rays, int32_t* occluded, size_t n)

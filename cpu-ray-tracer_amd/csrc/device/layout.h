@@ -103,6 +103,11 @@ struct Scene {                            // passed to the kernels BY VALUE (ker
 
 struct Counters { unsigned long long v[8]; };   // order = crt_counters
 
+// crt_refit_device's bottom-up plan of one BVH (refit.hip): one record per node pair, sorted by depth, deepest level first.  A child code is kPlanInterior | the
+// BVH-local index of the child's own pair, or the BVH-local leaf slot of a leaf child's first triangle (its triangle count is that LeafTri's `remain`).
+struct alignas(16) RefitPlanRec { uint32_t pair, child[2], pad; };
+constexpr uint32_t kPlanInterior = 0x80000000u;
+
 // Whether a crt_hit's indices may be used as addresses by the hit-info query (shade_query.hip): ONE predicate for the host entry, which refuses the call, and for
 // the kernel, which writes CRT_MATERIAL_INVALID for the lane.  objects = crt_scene_desc.objCount (FileScene) / bvhCount (two-level); triCountOf(k) = triangles of
 // the BVH that object 2 + k's triIdx indexes (FileScene: its one BVH; two-level: BLAS k), asked only for an object that exists.

@@ -14,6 +14,16 @@ struct crt_host_scene { BaseScene* scene = nullptr; FileScene* file = nullptr; T
                         std::vector<BLASKDTree> blasKd; std::vector<BLASGrid> blasGrid; };   // TLAS scene: one structure per BLAS
 struct crt_host_renderer { Renderer* r = nullptr; };
 
+// a BVH whose host arrays are stale (refitted on the device only): the calls that would send those arrays are refused
+static bool refuse_stale(crt_host_scene* s, const char* what)
+{
+    const int i = s->scene->FirstStaleBvh();
+    if (i < 0) return false;
+    g_err = std::string(what) + ": BVH " + std::to_string(i) + " was refitted on the device (crt_host_scene_bvh_refit_device), its host triangles and nodes are stale; "
+            "crt_host_scene_bvh_move_and_refit brings the positions to the host again";
+    return true;
+}
+
 #define GUARD_BEGIN try {
 #define GUARD_END(code) } catch (const std::exception& e) { g_err = e.what(); return code; } catch (...) { g_err = "unknown exception"; return code; }
 
@@ -42,6 +52,7 @@ void crt_host_scene_free(crt_host_scene* s) { if (s) { delete s->scene; delete s
 int crt_host_scene_upload(crt_host_scene* s, crt_ctx* ctx)
 {
     if (!s || !ctx) { g_err = "null argument"; return CRT_ERR_INVALID; }
+    if (refuse_stale(s, "crt_host_scene_upload")) return CRT_ERR_STATE;
     GUARD_BEGIN
     const int rc = s->scene->Upload(ctx);
     if (rc != CRT_OK) g_err = crt_last_error(ctx);
@@ -91,8 +102,30 @@ int crt_host_scene_bvh_move_and_refit(crt_host_scene* s, int i, const float* pos
     }
     if (s->file) s->file->acc.Refit();
     else { blas->Refit(); blas->SetTransform(blas->T); s->tlas->tlas.Build(); }      // world bounds + TLAS follow the refitted BLAS, as a per-frame animation loop does
+    if ((size_t)i < s->scene->staleBvh.size()) s->scene->staleBvh[(size_t)i] = 0;    // the host arrays are current again
     return CRT_OK;
     GUARD_END(CRT_ERR_INVALID)
+}
+int crt_host_scene_bvh_refit_device(crt_host_scene* s, crt_ctx* ctx, int i, const float* d_positions, uint32_t triCount, void* stream)
+{
+    if (!s || !ctx) { g_err = "null argument"; return CRT_ERR_INVALID; }
+    GUARD_BEGIN
+    const int count = s->file ? 1 : (int)s->tlas->tlas.blas.size();
+    if (i < 0 || i >= count) { g_err = "bvh index out of range"; return CRT_ERR_INVALID; }
+    float box[6];
+    int rc = crt_refit_device(ctx, (uint32_t)i, d_positions, triCount, stream, box);
+    if (rc != CRT_OK) { g_err = crt_last_error(ctx); return rc; }
+    BVHNode& root = s->file ? s->file->acc.bvhNodes[0] : s->tlas->tlas.blas[(size_t)i]->bvhNodes[0];
+    memcpy(root.aabbMin, box, 12); memcpy(root.aabbMax, box + 3, 12);
+    s->scene->staleBvh.resize((size_t)count, 0); s->scene->staleBvh[(size_t)i] = 1;
+    if (s->tlas) {                                                                   // as after BLASBVH::Refit: world bounds from the new root box, TLAS rebuilt, both sent
+        BLASBVH* blas = s->tlas->tlas.blas[(size_t)i];
+        blas->SetTransform(blas->T); s->tlas->tlas.Build();
+        rc = s->scene->Update(ctx, CRT_UPDATE_TRANSFORMS);
+        if (rc != CRT_OK) g_err = crt_last_error(ctx);
+    }
+    return rc;
+    GUARD_END(CRT_ERR_DEVICE)
 }
 // BLASBVH::SetTransform(T) of instance i (blas_bvh.cpp:363-374: T, invT = FastInvertedTransformNoScale, world bounds of the 8 root-box corners)
 // followed by TLASBVH::Build (tlas_bvh.cpp:17-55), as an animation loop does per frame; crt_host_scene_update then moves it to the device
@@ -110,6 +143,7 @@ int crt_host_scene_set_transform(crt_host_scene* s, int i, const float T[16])
 int crt_host_scene_update(crt_host_scene* s, crt_ctx* ctx, uint32_t what)
 {
     if (!s || !ctx) { g_err = "null argument"; return CRT_ERR_INVALID; }
+    if ((what & CRT_UPDATE_BOUNDS) && refuse_stale(s, "crt_host_scene_update(CRT_UPDATE_BOUNDS)")) return CRT_ERR_STATE;
     GUARD_BEGIN
     const int rc = s->scene->Update(ctx, what);
     if (rc != CRT_OK) g_err = crt_last_error(ctx);

@@ -85,6 +85,7 @@ void BaseScene::BuildDesc(crt_scene_desc& d, DescKeep& k)
 
 int BaseScene::Upload(crt_ctx* ctx)
 {
+    if (FirstStaleBvh() >= 0) return CRT_ERR_STATE;
     crt_scene_desc d; DescKeep k;
     BuildDesc(d, k);
     const int rc = crt_upload_scene(ctx, &d);
@@ -95,6 +96,7 @@ int BaseScene::Upload(crt_ctx* ctx)
 // after BLASBVH::SetTransform + TLASBVH::Build (CRT_UPDATE_TRANSFORMS) or Refit (CRT_UPDATE_BOUNDS): rewrites only those sections on the device
 int BaseScene::Update(crt_ctx* ctx, uint32_t what)
 {
+    if ((what & CRT_UPDATE_BOUNDS) && FirstStaleBvh() >= 0) return CRT_ERR_STATE;
     crt_scene_desc d; DescKeep k;
     BuildDesc(d, k);
     return crt_update_scene(ctx, &d, what);

@@ -69,6 +69,10 @@ public:
     float3 floorN{0, 1, 0}; float floorD = 1, floorInvto = 1; // Plane floor(1, (0,1,0), 1, texW/100)
     float animTime = 0;
     void SetTime(float t) { animTime = t; }
+    // BVHs refitted on the device only (crt_host_scene_bvh_refit_device): their host triangles / nodes are stale, so Upload and Update(CRT_UPDATE_BOUNDS), which
+    // would send them, return CRT_ERR_STATE while one is marked
+    std::vector<uint8_t> staleBvh;
+    int FirstStaleBvh() const { for (size_t i = 0; i < staleBvh.size(); i++) if (staleBvh[i]) return (int)i; return -1; }
 protected:
     void LoadCommon(const SceneData& sd, const std::string& baseDir);
     virtual void Describe(crt_scene_desc& d, std::vector<crt_bvh>& bvhs, std::vector<int32_t>& objMat) = 0;

@@ -154,6 +154,27 @@ int  crt_upload_scene(crt_ctx* ctx, const crt_scene_desc* scene);   /* flattens 
 #define CRT_UPDATE_TRANSFORMS 1u
 #define CRT_UPDATE_BOUNDS     2u
 int  crt_update_scene(crt_ctx* ctx, const crt_scene_desc* scene, uint32_t what);
+/* BVH::Refit / BLASBVH::Refit (bvh.cpp:26-61) of ONE uploaded BVH on the device, from vertex positions that already live in device memory (skinning, a cloth step,
+ * an optimiser over vertices): no copy of the positions to the host, no CPU refit, no staging of the geometry sections.  ABI version 3 still: an addition,
+ * detected by symbol.  d_positions = vertex0, vertex1, vertex2 of every triangle in the reference's triangles[] order (9 floats each; the array
+ * crt_host_scene_bvh_move_and_refit takes), device memory of cfg.device (checked as the device query entries check theirs); `stream` as there, NULL = the ctx's.
+ * Works on CRT_SCENE_FILE (bvh = 0) and on every BLAS of a CRT_SCENE_TLAS scene.  What it leaves on the device is exactly what Refit followed by
+ * crt_update_scene(CRT_UPDATE_BOUNDS) leaves for that BVH, bit for bit: every leaf triangle gets vertex0, vertex1 - vertex0, vertex2 - vertex0; every node box is
+ * what the reference's backward loop gives, INCLUDING ITS QUIRK that node 1 is skipped (`if (i != 1)`, bvh.cpp:28): the root's left child keeps the box it had,
+ * and that stale box still feeds node 0's.  Normals, uvs, materials, references and the leaf order stay (Refit touches none of them).
+ * rootBox (may be NULL) receives node 0's refitted aabbMin, aabbMax.  Two-level scenes: the call does NOT rebuild the TLAS (neither does BLASBVH::Refit); the caller
+ * puts rootBox into its BLAS's node 0, runs SetTransform + TLASBVH::Build as after any Refit and sends the result with crt_update_scene(CRT_UPDATE_TRANSFORMS) —
+ * rootBox is what makes that possible without reading the device.  (crt_host_scene_bvh_refit_device does all of it.)
+ * Ordering, as crt_update_scene and the device queries: the refit kernels run on `stream` behind every launch submitted earlier that reads the geometry (renders,
+ * frames rendered ahead, queries on any stream), so earlier renders still see the old scene; every launch submitted later waits for the refit.  THE ONE HOST WAIT:
+ * the root's child pair travels in the kernel arguments of the render launches, so the call reads that pair and node 0's box back (88 bytes, pinned) and returns
+ * once they have landed — it waits for `stream` up to the refit (and so for the earlier readers the refit is ordered behind), for nothing submitted later.
+ * Like CRT_UPDATE_BOUNDS it drops a two-level scene's KD-tree / grid sets and the frames crt_tick rendered ahead.
+ * Refused with nothing modified: no scene (CRT_ERR_STATE), a PrimitiveScene (CRT_ERR_UNSUPPORTED), bvh out of range, triCount different from the uploaded BVH's,
+ * d_positions NULL / a host pointer / memory of another device, a stream of another device (CRT_ERR_INVALID).  The caller's host arrays of that BVH (and a later
+ * CRT_UPDATE_BOUNDS built from them) are its own business: an update rewrites both sections from whatever it is given. */
+int  crt_refit_device(crt_ctx* ctx, uint32_t bvh, const float* d_positions /* 9 * triCount, device */, uint32_t triCount, void* stream,
+                      float rootBox[6] /* out: node 0's aabbMin, aabbMax; may be NULL */);
 int  crt_set_camera(crt_ctx* ctx, const float camPos[3], const float topLeft[3], const float topRight[3], const float bottomLeft[3]);
                                                                 /* Camera members used by GetPrimaryRay (camera.h:23-30) */
 

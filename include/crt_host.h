@@ -57,6 +57,12 @@ int  crt_host_scene_blas_alt_copy(crt_host_scene* scene, int kind, int blas, voi
 int  crt_host_scene_set_transform(crt_host_scene* scene, int bvh, const float T[16]);
 /* ... and the in-place device update for it (what = CRT_UPDATE_TRANSFORMS) or for crt_host_scene_bvh_move_and_refit (what = CRT_UPDATE_BOUNDS): crt_update_scene */
 int  crt_host_scene_update(crt_host_scene* scene, crt_ctx* ctx, uint32_t what);
+/* The same refit on the device, from positions in device memory (crt_refit_device; d_positions, triCount, stream as there): node 0 of BVH `bvh` takes the refitted
+ * root box the call returns and, for a TLAS scene, BLASBVH::SetTransform(T) + TLASBVH::Build run on the host and crt_update_scene(CRT_UPDATE_TRANSFORMS) follows.
+ * The host triangles and the other nodes of that BVH never saw the new positions: the BVH is marked stale, and while any BVH of the scene is,
+ * crt_host_scene_upload and crt_host_scene_update(.., CRT_UPDATE_BOUNDS) — which would send those arrays — are refused with CRT_ERR_STATE.
+ * crt_host_scene_bvh_move_and_refit on that BVH (the positions on the host again) clears its mark. */
+int  crt_host_scene_bvh_refit_device(crt_host_scene* scene, crt_ctx* ctx, int bvh, const float* d_positions, uint32_t triCount, void* stream);
 int  crt_host_scene_blas_transform(crt_host_scene* scene, int bvh, float T[16], float invT[16], float worldMin[3], float worldMax[3]);
 int  crt_host_scene_tlas_copy(crt_host_scene* scene, crt_tlas_node* nodes /* 2*blasCount */, uint32_t* nodesUsed);
 
