@@ -693,6 +693,25 @@ class HostPrimitiveScene:
         if r != 0:
             raise CrtError(r, self.L.crt_last_error(ctx.h).decode())
 
+    def desc_with_state(self, state):
+        """desc() with the 108 floats of state() overwritten (tests: arbitrary matrices, e.g. identity cube / torus transforms); the wall images stay this scene's"""
+        st = np.ascontiguousarray(state, np.float32).reshape(108)
+        d = self.desc()
+        for k, name in enumerate(("quadT", "quadInvT", "cubeM", "cubeInvM", "torusT", "torusInvT")):
+            getattr(d, name)[:] = [float(v) for v in st[16 * k:16 * k + 16]]
+        d.spherePos[:] = [float(v) for v in st[96:99]]
+        d.torusRt2, d.torusRc2, d.torusR2 = float(st[99]), float(st[100]), float(st[101])
+        d.cubeMin[:] = [float(v) for v in st[102:105]]
+        d.cubeMax[:] = [float(v) for v in st[105:108]]
+        return d
+
+    def upload_desc(self, ctx, d):
+        """crt_upload_primitive_scene with a description the caller has edited (the C ABI accepts any); this scene must outlive the call (it owns the wall images)"""
+        self.L.crt_upload_primitive_scene.argtypes = [C.c_void_p, C.POINTER(PrimitiveSceneS)]
+        r = self.L.crt_upload_primitive_scene(ctx.h, C.byref(d))
+        if r != 0:
+            raise CrtError(r, self.L.crt_last_error(ctx.h).decode())
+
     def close(self):
         if self.h:
             self.L.crt_host_primitive_scene_free(self.h); self.h = None

@@ -59,6 +59,8 @@ struct PrimDev {                          // = device/render_prim.hip
 extern "C" hipError_t crt_launch_find_nearest_prim(const crt::PrimDev*, const void*, void*, uint32_t, hipStream_t);
 extern "C" hipError_t crt_launch_render_prim(const crt::Scene*, const crt::PrimDev*, void*, crt::Counters*, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, hipStream_t);
 extern "C" hipError_t crt_launch_check_reciprocals(unsigned long long*, hipStream_t);
+extern "C" hipError_t crt_launch_probe_f32(int, const void*, void*, uint32_t, hipStream_t);
+extern "C" hipError_t crt_launch_probe_f64(int, const void*, void*, uint32_t, hipStream_t);
 extern "C" hipError_t crt_launch_find_nearest_alt(int, const crt::Scene*, const crt::AltAccelDev*, const void*, void*, uint32_t, uint32_t*, hipStream_t);
 extern "C" hipError_t crt_launch_is_occluded(const crt::Scene*, const void*, int32_t*, uint32_t, uint32_t, uint32_t*, hipStream_t);
 extern "C" hipError_t crt_launch_is_occluded_alt(int, const crt::Scene*, const crt::AltAccelDev*, const void*, int32_t*, uint32_t, uint32_t*, hipStream_t);
@@ -2492,6 +2494,26 @@ extern "C" int crt_debug_check_reciprocals(crt_ctx* c, uint64_t* out)
     hipError_t e = hipMemsetAsync(d, 0, 32, c->stream);
     if (e == hipSuccess) e = crt_launch_check_reciprocals(d, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(out, d, 32, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    (void)hipFree(d);
+    HIPCK(c, e);
+    return CRT_OK;
+}
+
+// tests: dev_common.h's fp32 building blocks (device/probe.hip) and the torus' fp64 ones (end of device/render_prim.hip) on the device at hand, one element per
+// thread: host buffers in and out, one launch.  Ops and record layouts: the table at the top of device/probe.hip.  n <= 2^25 records per call.
+extern "C" int crt_debug_device_probe(crt_ctx* c, int op, const void* in, void* out, uint32_t n)
+{
+    static const uint8_t words[17][2] = {{1, 1}, {1, 1}, {2, 1}, {1, 1}, {2, 1}, {6, 7}, {1, 18}, {4, 1}, {5, 3}, {13, 2}, {16, 4}, {2, 2}, {2, 2}, {2, 2}, {2, 2}, {4, 2}, {2, 1}};
+    if (!c || !in || !out || op < 0 || op > 16 || n > (1u << 25)) return CRT_ERR_INVALID;
+    if (n == 0) return CRT_OK;
+    const size_t inBytes = (size_t)n * words[op][0] * 4, outBytes = (size_t)n * words[op][1] * 4;
+    HIPCK(c, hipSetDevice(c->cfg.device));
+    char* d = nullptr;
+    HIPCK(c, hipMalloc((void**)&d, inBytes + outBytes));               // inBytes is a multiple of 8 for the fp64 ops: both halves stay aligned
+    hipError_t e = hipMemcpyAsync(d, in, inBytes, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = (op <= 10) ? crt_launch_probe_f32(op, d, d + inBytes, n, c->stream) : crt_launch_probe_f64(op, d, d + inBytes, n, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(out, d + inBytes, outBytes, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     (void)hipFree(d);
     HIPCK(c, e);

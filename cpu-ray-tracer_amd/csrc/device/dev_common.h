@@ -74,6 +74,7 @@ __device__ __forceinline__ uint32_t asu(float f) { return __float_as_uint(f); }
 #define CRT_EPS 0.001f
 
 // deterministic exp / atan2 / acos: same formulas, same operation order as the checker's restatement (DESIGN.md "numerics")
+// (checked on the device by themselves, like the other building blocks of this header, by tests/test_gpu_device_probe.py through probe.hip)
 static __device__ float crt_expf(float x)
 {
     if (x != x) return x;

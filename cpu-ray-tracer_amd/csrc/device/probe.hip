@@ -1,0 +1,106 @@
+// probe.hip — diagnostics: the fp32 building blocks of dev_common.h, one element per thread, for crt_debug_device_probe (abi.cpp; tests/test_gpu_device_probe.py).
+// The render and query kernels' bit-exact parity rests on "only IEEE + - * / sqrt, so results are bit-identical with a scalar CPU evaluation of the same
+// expressions" (dev_common.h); the renders check that sentence through whole paths, this unit checks each block by itself at the inputs where it can go wrong.
+// It is a translation unit of its own, built with the library's flags: it compiles ITS OWN copy of the inline functions (the copies inlined into the render
+// kernels are still checked by the renders), and the timed kernels' sources do not change.
+//
+// Straight-line code: plain loads and stores, no LDS, no traversal, no loop (the two 8-draw RNG sequences are unrolled).  Every input ends in a stored result;
+// NaN, inf and zero operands are data.
+//
+// Record layouts (32-bit words; op numbers shared with abi.cpp's table and, for 11 .. 16, with the fp64 probe at the end of render_prim.hip):
+//   op  name      in (words)                                          out (words)
+//    0  EXPF      x                                              1    crt_expf(x)                                                        1
+//    1  ACOSF     x                                              1    crt_acosf(x)                                                       1
+//    2  ATAN2F    y, x                                           2    crt_atan2f(y, x)                                                   1
+//    3  SQRTF     x                                              1    __builtin_sqrtf(x)                                                 1
+//    4  DIVF      a, b                                           2    a / b                                                              1
+//    5  VEC3      a.xyz, b.xyz                                   6    normalize3(a).xyz, cross3(a, b).xyz, dot3(a, b)                    7
+//    6  RNG       base (u32)                                     1    init_seed(base) (u32), 8 x rnd, 8 x rnd_pm1, final state (u32)    18
+//    7  TEX       u, v, w (i32), h (i32)                         4    tex_index(0, w, h, u, v) (u32)                                     1
+//    8  SKY       D.xyz, w (i32), h (i32)                        5    phi, theta, tex_index(0, w, h, phi / 2pi, theta / pi) (u32)        3
+//    9  BOX       lo.xyz, hi.xyz, O.xyz, rD.xyz, tray           13    box_exact, box_fast                                                2
+//   10  TRI       v0.xyz, e1.xyz, e2.xyz, O.xyz, D.xyz, t_in    16    t, u, v, accepted (u32 0 / 1); a rejected record keeps t_in, 0, 0  4
+//   11  ACOS64    x (double)                                     2    det_acos(x) (double)                                               2
+//   12  COS64     x (double)                                     2    det_cos(x) (double)                                                2
+//   13  CBRT64    x (double)                                     2    cbrt_fast(x) (double)                                              2
+//   14  SQRT64    x (double)                                     2    __builtin_sqrt(x) (double)                                         2
+//   15  DIV64     a, b (doubles)                                 4    a / b (double)                                                     2
+//   16  F64TOF32  x (double)                                     2    (float)x                                                           1
+#include "dev_common.h"
+
+namespace crt {
+
+__global__ __launch_bounds__(256) void probe_f32_kernel(int op, const uint32_t* __restrict__ in, uint32_t* __restrict__ out, uint32_t n)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    switch (op) {
+    case 0: out[i] = asu(crt_expf(asf(in[i]))); break;
+    case 1: out[i] = asu(crt_acosf(asf(in[i]))); break;
+    case 2: out[i] = asu(crt_atan2f(asf(in[2 * (size_t)i]), asf(in[2 * (size_t)i + 1]))); break;
+    case 3: out[i] = asu(__builtin_sqrtf(asf(in[i]))); break;
+    case 4: out[i] = asu(asf(in[2 * (size_t)i]) / asf(in[2 * (size_t)i + 1])); break;
+    case 5: {
+        const uint32_t* p = in + 6 * (size_t)i; uint32_t* o = out + 7 * (size_t)i;
+        const f3 a = mk3(asf(p[0]), asf(p[1]), asf(p[2])), b = mk3(asf(p[3]), asf(p[4]), asf(p[5]));
+        const f3 nn = normalize3(a), cr = cross3(a, b);
+        o[0] = asu(nn.x); o[1] = asu(nn.y); o[2] = asu(nn.z); o[3] = asu(cr.x); o[4] = asu(cr.y); o[5] = asu(cr.z); o[6] = asu(dot3(a, b));
+        break;
+    }
+    case 6: {
+        uint32_t* o = out + 18 * (size_t)i;
+        uint32_t s = init_seed(in[i]);
+        o[0] = s;
+#pragma unroll
+        for (int k = 0; k < 8; k++) o[1 + k] = asu(rnd(s));
+#pragma unroll
+        for (int k = 0; k < 8; k++) o[9 + k] = asu(rnd_pm1(s));
+        o[17] = s;
+        break;
+    }
+    case 7: {
+        const uint32_t* p = in + 4 * (size_t)i;
+        out[i] = tex_index(0u, (int)p[2], (int)p[3], asf(p[0]), asf(p[1]));
+        break;
+    }
+    case 8: {   // sky_color's lookup (file_scene.cpp:142-154) up to the texel fetch
+        const uint32_t* p = in + 5 * (size_t)i; uint32_t* o = out + 3 * (size_t)i;
+        const f3 D = mk3(asf(p[0]), asf(p[1]), asf(p[2]));
+        const float phi = crt_atan2f(-D.z, D.x) + CRT_PI;
+        const float theta = crt_acosf(-D.y);
+        o[0] = asu(phi); o[1] = asu(theta); o[2] = tex_index(0u, (int)p[3], (int)p[4], phi * CRT_INV2PI, theta * CRT_INVPI);
+        break;
+    }
+    case 9: {
+        const uint32_t* p = in + 13 * (size_t)i;
+        rec4 lo, hi; lo.x = asf(p[0]); lo.y = asf(p[1]); lo.z = asf(p[2]); lo.w = 0.0f; hi.x = asf(p[3]); hi.y = asf(p[4]); hi.z = asf(p[5]); hi.w = 0.0f;
+        const f3 O = mk3(asf(p[6]), asf(p[7]), asf(p[8])), rD = mk3(asf(p[9]), asf(p[10]), asf(p[11]));
+        const float tray = asf(p[12]);
+        out[2 * (size_t)i] = asu(box_exact(lo, hi, O, rD, tray)); out[2 * (size_t)i + 1] = asu(box_fast(lo, hi, O, rD, tray));
+        break;
+    }
+    case 10: {
+        const uint32_t* p = in + 16 * (size_t)i; uint32_t* o = out + 4 * (size_t)i;
+        rec4 a, b, c;
+        a.x = asf(p[0]); a.y = asf(p[1]); a.z = asf(p[2]); a.w = asf(7u);            // shadeIdx 7: the mark of an accepted hit
+        b.x = asf(p[3]); b.y = asf(p[4]); b.z = asf(p[5]); b.w = asf(2u);
+        c.x = asf(p[6]); c.y = asf(p[7]); c.z = asf(p[8]); c.w = asf(1u);
+        const f3 O = mk3(asf(p[9]), asf(p[10]), asf(p[11])), D = mk3(asf(p[12]), asf(p[13]), asf(p[14]));
+        Hit h; h.t = asf(p[15]); h.u = 0.0f; h.v = 0.0f; h.objIdx = -1; h.triIdx = -1;
+        hit_tri(a, b, c, O, D, h);
+        o[0] = asu(h.t); o[1] = asu(h.u); o[2] = asu(h.v); o[3] = (h.triIdx == 7) ? 1u : 0u;
+        break;
+    }
+    default: break;
+    }
+}
+
+} // namespace crt
+
+extern "C" hipError_t crt_launch_probe_f32(int op, const void* in, void* out, uint32_t n, hipStream_t stream)
+{
+    if (n == 0) return hipSuccess;
+    if (op < 0 || op > 10) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(crt::probe_f32_kernel, dim3((n + 255u) / 256u), dim3(256), 0, stream, op, (const uint32_t*)in, (uint32_t*)out, n);
+    return hipGetLastError();
+}

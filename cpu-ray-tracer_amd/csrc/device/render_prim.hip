@@ -299,3 +299,31 @@ extern "C" hipError_t crt_launch_render_prim(const crt::Scene* sc, const crt::Pr
     if ((unsigned long long)tileCount * windows > 0x7fffffffull) return hipErrorInvalidValue;
     return crt::launch_render_seq(sc, crt::PrimWorld{*p}, slab, counters, tileFirst, tileStride, tileCount, tilesX, sppFirst, frames, passes, stream);
 }
+
+// diagnostics (crt_debug_device_probe, abi.cpp; record layouts in probe.hip): the torus' fp64 building blocks, one element per thread.  The functions are
+// static in this unit, so the probe lives here; straight-line code except cbrt_fast's own loop (at most 100 turns).
+namespace crt {
+__global__ __launch_bounds__(256) void probe_f64_kernel(int op, const double* __restrict__ in, void* __restrict__ out, uint32_t n)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    double* o = (double*)out;
+    switch (op) {
+    case 11: o[i] = det_acos(in[i]); break;
+    case 12: o[i] = det_cos(in[i]); break;
+    case 13: o[i] = cbrt_fast(in[i]); break;
+    case 14: o[i] = __builtin_sqrt(in[i]); break;
+    case 15: o[i] = in[2 * (size_t)i] / in[2 * (size_t)i + 1]; break;
+    case 16: ((float*)out)[i] = (float)in[i]; break;
+    default: break;
+    }
+}
+} // namespace crt
+
+extern "C" hipError_t crt_launch_probe_f64(int op, const void* in, void* out, uint32_t n, hipStream_t stream)
+{
+    if (n == 0) return hipSuccess;
+    if (op < 11 || op > 16) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(crt::probe_f64_kernel, dim3((n + 255u) / 256u), dim3(256), 0, stream, op, (const double*)in, out, n);
+    return hipGetLastError();
+}

@@ -125,6 +125,16 @@ int orc_set_render_accel(orc_ctx*, int kind, void* h);
 int orc_prim_setup(orc_ctx*, const uint32_t* red512, const uint32_t* blue512);
 int orc_prim_set_time(orc_ctx*, float t);
 int orc_prim_state(orc_ctx*, float* out108);
+int orc_prim_set_state(orc_ctx*, const float* in108);           /* exactly what orc_prim_state returns */
+/* exact branch counts of PrimScene::find_nearest / Torus::Intersect since the last reset (process-wide); out may be NULL.  Order: v < 0 return; swapped
+ * coefficients (po = -1); h < 0 with det_acos on |x| < 0.5, x <= -0.5, x >= 0.5; h < 0 with det_cos on x <= pi / 4, x > pi / 4; h >= 0 (cbrt_fast);
+ * fabs(d1) < 1e-8; d1 < 0 return; first root pair with po > 0, po < 0; second root pair with po > 0, po < 0; torus nearest with po > 0, po < 0; cube entered
+ * from outside; cube left from inside; cube slab with a NaN tmin or tmax; NaN t in the returned hit */
+#define ORC_PRIM_COV_COUNT 20
+int orc_prim_coverage(orc_ctx*, uint64_t* out, int reset);
+/* expected results of the product's device probe (same ops and record layouts as crt_debug_device_probe, cpu-ray-tracer_amd/csrc/device/probe.hip; TRI takes
+ * v0, v1, v2 where the device record holds v0, e1, e2) */
+int orc_probe_expected(int op, const void* in, void* out, size_t n);
 double orc_det_acos(double x);
 double orc_det_cos(double x);
 void orc_math_probe(const float* in12, uint32_t n, float* out120);

@@ -631,6 +631,46 @@ def prim_state(o):
     return out
 
 
+def prim_set_state(o, state):
+    """the inverse of prim_state: the 108 floats, e.g. with identity cube / torus transforms"""
+    st = np.ascontiguousarray(state, np.float32).reshape(108)
+    if o.L.orc_prim_set_state(o.h, _fp(st)) != 0:
+        raise RuntimeError("orc_prim_set_state refused")
+
+
+PRIM_COVERAGE = ("v_neg", "swapped", "acos_small", "acos_neg", "acos_pos", "cos_kernel", "cos_reduced", "cbrt", "d1_tiny", "d1_neg", "pair1_po_pos", "pair1_po_neg",
+                 "pair2_po_pos", "pair2_po_neg", "torus_nearest_po_pos", "torus_nearest_po_neg", "cube_entered", "cube_left", "cube_nan", "t_nan")
+
+
+def prim_coverage(o, reset=False):
+    """exact branch counts of PrimScene::find_nearest / Torus::Intersect since the last reset (process-wide): {name: count}"""
+    out = np.zeros(len(PRIM_COVERAGE), np.uint64)
+    if o.L.orc_prim_coverage(o.h, _fp(out), C.c_int(1 if reset else 0)) != 0:
+        raise RuntimeError("orc_prim_coverage refused")
+    return {k: int(v) for k, v in zip(PRIM_COVERAGE, out)}
+
+
+# ops of the device probe (crt_debug_device_probe; layouts in cpu-ray-tracer_amd/csrc/device/probe.hip): name -> (number, input words, output words)
+PROBE_OPS = {"EXPF": (0, 1, 1), "ACOSF": (1, 1, 1), "ATAN2F": (2, 2, 1), "SQRTF": (3, 1, 1), "DIVF": (4, 2, 1), "VEC3": (5, 6, 7), "RNG": (6, 1, 18), "TEX": (7, 4, 1),
+             "SKY": (8, 5, 3), "BOX": (9, 13, 2), "TRI": (10, 16, 4), "ACOS64": (11, 2, 2), "COS64": (12, 2, 2), "CBRT64": (13, 2, 2), "SQRT64": (14, 2, 2),
+             "DIV64": (15, 4, 2), "F64TOF32": (16, 2, 1)}
+
+
+def probe_expected(op, inputs):
+    """orc_probe_expected: `inputs` = [n, input words] of a 4-byte type (or [n, words / 2] float64); returns [n, output words] uint32 (view it as the op's type).
+    TRI takes v0, v1, v2 where the device record holds v0, e1, e2."""
+    num, wi, wo = PROBE_OPS[op]
+    a = np.ascontiguousarray(inputs)
+    n = a.shape[0] if a.ndim > 1 else (len(a) if wi * 4 == a.itemsize else len(a) * a.itemsize // (4 * wi))
+    assert a.nbytes == n * wi * 4, (op, a.shape, a.dtype)
+    out = np.zeros((n, wo), np.uint32)
+    L = lib()
+    L.orc_probe_expected.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_size_t]
+    if L.orc_probe_expected(num, _fp(a), _fp(out), n) != 0:
+        raise RuntimeError("orc_probe_expected refused")
+    return out
+
+
 def det_acos_cos():
     L = lib()
     L.orc_det_acos.restype = C.c_double; L.orc_det_acos.argtypes = [C.c_double]

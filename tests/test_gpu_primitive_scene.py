@@ -4,6 +4,7 @@ bit for bit against the oracle's restatement (oracle/crt_oracle.cpp PrimScene), 
 import numpy as np
 import pytest
 
+import probe_inputs as pi
 from conftest import ASSETS
 
 pytestmark = pytest.mark.gpu
@@ -55,3 +56,27 @@ def test_path_tracer_over_the_primitive_scene_is_bit_exact(crt, orc, t, W, H, fr
     hs = crt.HostScene(ASSETS + "/scenes/cube_scene.xml", 0, ASSETS); hs.upload(ctx)
     ctx.clear(); ctx.render(1, 1, 1); ctx.sync()
     assert ctx.accumulator()[..., :3].max() > 0
+
+
+@pytest.mark.parametrize("t", [0.0, 1.3])
+def test_degenerate_rays_through_identity_transforms(crt, orc, t):
+    """The scene as SetTime builds it rotates cube and torus, so no ray has an exact-zero direction component in object space and the edge inputs of the cube,
+    the torus' quartic and the walls cannot occur.  Here oracle and device get the same edited description (identity cube / torus transforms) and the ray families
+    of probe_inputs.prim_families; test_device_probe_cpu.py asserts that they take every branch (fabs(d1) < 1e-8, NaN slabs, NaN t, ...) at least 100 times."""
+    ps = crt.HostPrimitiveScene(ASSETS); ps.set_time(t)
+    o = orc.primitive_scene(ASSETS, t)
+    state = pi.identity_transforms(ps.state())
+    orc.prim_set_state(o, state)
+    d = ps.desc_with_state(state)
+    ctx = crt.Context(64, 64); ps.upload_desc(ctx, d)
+    assert np.array_equal(orc.prim_state(o).view(np.uint32), state.view(np.uint32))
+    O, D = pi.prim_rays()
+    orc.prim_coverage(o, reset=True)
+    h = ctx.find_nearest(O, D); g = o.find_nearest(O, D)
+    cov = orc.prim_coverage(o)
+    assert cov["d1_tiny"] > 100 and cov["cube_nan"] > 100 and cov["t_nan"] > 100 and cov["swapped"] > 100, cov
+    tbad = np.zeros(len(O), bool); tbad[pi.differing(h["t"], g["t"])] = True          # bit equality, any NaN equals any NaN
+    bad = np.flatnonzero((h["objIdx"] != g["objIdx"]) | tbad)
+    assert len(bad) == 0, "first differing rays: %s" % [(int(i), O[i].tolist(), D[i].tolist(), int(h["objIdx"][i]), int(g["objIdx"][i]),
+                                                        "%08x" % h["t"].view(np.uint32)[i], "%08x" % g["t"].view(np.uint32)[i]) for i in bad[:6]]
+    assert np.isnan(g["t"]).sum() == cov["t_nan"] and np.array_equal(np.isnan(h["t"]), np.isnan(g["t"]))        # the NaN t of family (h), in the same rays

@@ -385,10 +385,7 @@ MATH_FIELDS = [("normalize", 0, 3), ("reflect", 3, 6), ("cross", 6, 9), ("dot", 
                ("aabb::Grow(float3) / Area", 106, 113), ("aabb::Grow(aabb) / Area", 113, 120)]
 
 
-def _same_bits(a, b):
-    a = np.ascontiguousarray(a, np.float32).view(np.uint32); b = np.ascontiguousarray(b, np.float32).view(np.uint32)
-    nan = lambda x: (x & 0x7fffffff) > 0x7f800000                      # any NaN matches any NaN (payload / sign of an invalid operation are not specified)
-    return bool(np.all((a == b) | (nan(a) & nan(b))))
+from probe_inputs import same_bits as _same_bits          # bit equality, any NaN matches any NaN: one definition for every bit-exact test
 
 
 @pytest.mark.parametrize("who", ["oracle", "host_front"])
