@@ -110,7 +110,7 @@ HIT_INFO_DTYPE = np.dtype([("I", "<f4", 3), ("material", "<i4"), ("N", "<f4", 3)
 MATERIAL_MISS, MATERIAL_INVALID = -1, -2       # crt_hit_info.material of a miss / of a record whose objIdx or triIdx the scene does not have
 
 # every symbol include/crt_abi.h and include/crt_host.h declare (tests check the library exports all of them)
-ABI_SYMBOLS = ["crt_refit_device", "crt_get_hit_info", "crt_get_hit_info_device", "crt_get_sky_color", "crt_get_sky_color_device", "crt_get_light", "crt_upload_blas_accel", "crt_is_occluded", "crt_find_nearest_device", "crt_is_occluded_device", "crt_upload_primitive_scene", "crt_set_render_accel", "crt_upload_alt_accel", "crt_find_nearest_alt", "crt_update_scene", "crt_abi_version", "crt_device_count", "crt_create", "crt_destroy", "crt_last_error", "crt_upload_scene", "crt_set_camera",
+ABI_SYMBOLS = ["crt_sample", "crt_sample_device", "crt_refit_device", "crt_get_hit_info", "crt_get_hit_info_device", "crt_get_sky_color", "crt_get_sky_color_device", "crt_get_light", "crt_upload_blas_accel", "crt_is_occluded", "crt_find_nearest_device", "crt_is_occluded_device", "crt_upload_primitive_scene", "crt_set_render_accel", "crt_upload_alt_accel", "crt_find_nearest_alt", "crt_update_scene", "crt_abi_version", "crt_device_count", "crt_create", "crt_destroy", "crt_last_error", "crt_upload_scene", "crt_set_camera",
                "crt_render", "crt_tick", "crt_reserve", "crt_whitted_tick", "crt_whitted_tick_inspect", "crt_sync", "crt_clear", "crt_read_accumulator", "crt_resolve_screen", "crt_find_nearest", "crt_get_counters",
                "crt_reset_counters", "crt_get_timing", "crt_get_tile_clocks", "crt_bind_accumulator", "crt_accumulator_device_ptr"]
 HOST_SYMBOLS = ["crt_host_scene_bvh_refit_device", "crt_host_scene_blas_alt_info", "crt_host_scene_blas_alt_copy", "crt_host_primitive_scene_create", "crt_host_primitive_scene_free", "crt_host_primitive_scene_set_time", "crt_host_primitive_scene_desc", "crt_host_primitive_scene_upload", "crt_host_scene_build_alt", "crt_host_scene_upload_alt", "crt_host_scene_alt_info", "crt_host_scene_alt_copy", "crt_host_scene_set_transform", "crt_host_scene_update", "crt_host_math_probe", "crt_host_vertex_dedup", "crt_host_last_error", "crt_host_scene_load", "crt_host_scene_free", "crt_host_scene_upload", "crt_host_scene_kind",
@@ -469,6 +469,49 @@ class Context:
             return rgb
         return self._enqueue(stream, run)
 
+    def sample(self, O, D, seeds, inside=None, accel=0):
+        """Renderer::Sample(ray, seed, 0) per ray (crt_sample, host buffers, synchronous): O / D = [N, 3] (D is used as given: hand in unit directions), seeds = [N]
+        uint32 xorshift32 states, inside = None / one value / [N].  accel: 0 = BVH / TLAS / PrimitiveScene, ACCEL_KDTREE / ACCEL_GRID.
+        Returns (rgb [N, 3] float32, seeds_out [N] uint32); a ray with seed 0, a non-finite component or D = 0 is not traced: NaN, its seed unchanged."""
+        O = np.asarray(O, np.float32).reshape(-1, 3)
+        D = np.asarray(D, np.float32).reshape(-1, 3)
+        rays = np.zeros(O.shape[0], RAY_DTYPE)
+        rays["O"], rays["D"] = O, D
+        if inside is not None:
+            rays["inside"] = inside
+        s = np.array(seeds, dtype=np.uint32).reshape(-1)                        # a copy: the C entry updates it in place
+        if s.shape[0] != O.shape[0]:
+            raise ValueError("sample: one seed per ray")
+        rgb = np.zeros((O.shape[0], 3), np.float32)
+        self._ck(self.L.crt_sample(self.h, int(accel), _p(rays), _p(s), _p(rgb), C.c_size_t(O.shape[0])))
+        return rgb, s
+
+    def sample_device(self, rays=None, O=None, D=None, inside=None, seeds=None, accel=0, stream=None):
+        """crt_sample_device: Renderer::Sample(ray, seed, 0) for rays that live on the GPU, enqueued on `stream` (default torch.cuda.current_stream()) without a host
+        wait.  rays = [N, 7] crt_ray records, or O / D = [N, 3] float32 (+ inside); seeds = [N] int32 tensor on the context's device carrying the uint32 xorshift32
+        states (the convention of the records' `inside` column).  Returns (rgb [N, 3] float32, seeds_out [N] int32) as new tensors; `seeds` is not modified."""
+        import torch
+        if not isinstance(seeds, torch.Tensor) or seeds.device != torch.device("cuda", self.device):
+            raise ValueError("sample_device: seeds must be a torch tensor on cuda:%d" % self.device)
+        if seeds.dtype != torch.int32 or seeds.dim() != 1 or not seeds.is_contiguous():
+            raise ValueError("sample_device: seeds must be a contiguous [N] int32 tensor (the uint32 bit patterns)")
+
+        def run(st):
+            r = self._records(rays, O, D, inside, True, "sample_device")
+            if seeds.shape[0] != r.shape[0]:
+                raise ValueError("sample_device: one seed per ray")
+            s = seeds.clone()                                                 # on the stream: the in/out argument
+            rgb = torch.empty((r.shape[0], 3), dtype=torch.float32, device=r.device)
+            self._ck(self.L.crt_sample_device(self.h, int(accel), C.c_void_p(r.data_ptr()), C.c_void_p(s.data_ptr()), C.c_void_p(rgb.data_ptr()), C.c_size_t(r.shape[0]), C.c_void_p(st.cuda_stream)))
+            return rgb, s
+        return self._enqueue(stream, run)
+
+    def sample_resident_lanes(self, accel=0):
+        """the lanes a full crt_sample launch over this scene holds at once (tools / tests: an n above it makes every wavefront draw from the cursor again)"""
+        n = C.c_uint32()
+        self._ck(self.L.crt_debug_sample_resident_lanes(self.h, int(accel), C.byref(n)))
+        return int(n.value)
+
     def _positions(self, positions, what):
         """the device pointer and triangle count of a refit's positions: a contiguous float32 tensor [triCount, 3, 3] or [triCount, 9] on the context's device"""
         import torch
@@ -504,8 +547,9 @@ class Context:
         with torch.cuda.stream(side):
             out = run(side)
         st.wait_stream(side)
-        if isinstance(out, torch.Tensor):
-            out.record_stream(st)                                             # allocated on the side stream, consumed on st
+        for t in (out if isinstance(out, tuple) else (out,)):
+            if isinstance(t, torch.Tensor):
+                t.record_stream(st)                                           # allocated on the side stream, consumed on st
         return out
 
     def counters(self):

@@ -33,6 +33,7 @@ extern "C" hipError_t crt_launch_whitted_inspect(const crt::Scene*, int, const c
                                                  hipStream_t);
 extern "C" size_t crt_whitted_inspect_work_bytes(uint32_t);
 extern "C" hipError_t crt_launch_render_alt(int, const crt::Scene*, const crt::AltAccelDev*, const crt::TlasAltDev*, void*, crt::Counters*, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, hipStream_t);
+extern "C" hipError_t crt_launch_sample_query(int, const crt::Scene*, const crt::AltAccelDev*, const crt::TlasAltDev*, const void*, uint32_t*, float*, uint32_t, crt::Counters*, uint32_t*, uint32_t*, hipStream_t);
 extern "C" hipError_t crt_launch_resolve(const void*, uint32_t*, float*, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, float, hipStream_t);
 extern "C" hipError_t crt_launch_commit_frame(const void*, uint32_t, uint32_t, void*, uint32_t*, float*, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, float, hipStream_t);
 
@@ -58,6 +59,7 @@ struct PrimDev {                          // = device/render_prim.hip
 }
 extern "C" hipError_t crt_launch_find_nearest_prim(const crt::PrimDev*, const void*, void*, uint32_t, hipStream_t);
 extern "C" hipError_t crt_launch_render_prim(const crt::Scene*, const crt::PrimDev*, void*, crt::Counters*, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, hipStream_t);
+extern "C" hipError_t crt_launch_sample_query_prim(const crt::Scene*, const crt::PrimDev*, const void*, uint32_t*, float*, uint32_t, crt::Counters*, uint32_t*, uint32_t*, hipStream_t);
 extern "C" hipError_t crt_launch_check_reciprocals(unsigned long long*, hipStream_t);
 extern "C" hipError_t crt_launch_probe_f32(int, const void*, void*, uint32_t, hipStream_t);
 extern "C" hipError_t crt_launch_probe_f64(int, const void*, void*, uint32_t, hipStream_t);
@@ -2421,6 +2423,73 @@ int crt_get_sky_color_device(crt_ctx* c, const crt_ray* d_rays, float* d_rgb, si
     if (c->havePrim) HIPCK(c, hipMemsetAsync(d_rgb, 0, n * 12, st));          // PrimitiveScene::GetSkyColor
     else HIPCK(c, crt_launch_sky_color(&c->hScene, d_rays, d_rgb, (uint32_t)n, st));
     return end_device_query(c, k, st);
+}
+
+// ---- crt_sample / crt_sample_device: Renderer::Sample(ray, seed, 0) per ray of a buffer (device/sample_query.h) ----
+// query_check's checks + the world's LDS columns (traversal stack + 15 throughput factors per lane, four wavefronts per workgroup), as crt_set_render_accel refuses them
+static int sample_check(crt_ctx* c, int accel, size_t n, const char* what)
+{
+    int r;
+    if ((r = query_check(c, accel, false, n, what))) return r;
+    uint32_t words = 0;
+    if (c->havePrim) words = 0;
+    else if (accel == 0) words = c->hScene.stackDepth;
+    else if (c->hScene.kind == CRT_SCENE_TLAS) words = c->blasAlt[accel - 1].kdStack * 2u + (c->hScene.stackDepth - c->hScene.bvhStack);
+    else if (accel == CRT_ACCEL_KDTREE) words = c->alt.kdStack * 2u;
+    if (((uint64_t)words + 15u) * 64u * 4u * 4u > 64u * 1024u) return c->fail(CRT_ERR_UNSUPPORTED, "%s: a traversal stack of %u dwords per lane exceeds the kernel's LDS", what, words);
+    return 0;
+}
+
+static hipError_t launch_sample(crt_ctx* c, int accel, const void* rays, uint32_t* seeds, float* rgb, uint32_t n, uint32_t* cursor, uint32_t* residentLanes, hipStream_t st)
+{
+    if (c->havePrim) return crt_launch_sample_query_prim(&c->hScene, &c->prim, rays, seeds, rgb, n, c->dCounters, cursor, residentLanes, st);
+    return crt_launch_sample_query(accel, &c->hScene, &c->alt, accel ? &c->blasAlt[accel - 1] : nullptr, rays, seeds, rgb, n, c->dCounters, cursor, residentLanes, st);
+}
+
+int crt_sample(crt_ctx* c, int accel, const crt_ray* rays, uint32_t* seeds, float* rgb, size_t n)
+{
+    if (!c) return CRT_ERR_INVALID;
+    int r;
+    if ((r = sample_check(c, accel, n, "crt_sample"))) return r;
+    if (n == 0) return CRT_OK;
+    if (!rays || !seeds || !rgb) return c->fail(CRT_ERR_INVALID, "crt_sample: NULL buffer");
+    HIPCK(c, hipSetDevice(c->cfg.device));
+    if ((r = shade_stage(c, n * (12 + sizeof(crt_ray) + 4)))) return r;
+    float* dRgb = static_cast<float*>(c->dShadeStage); char* dRays = static_cast<char*>(c->dShadeStage) + n * 12; uint32_t* dSeeds = reinterpret_cast<uint32_t*>(dRays + n * sizeof(crt_ray));
+    HIPCK(c, hipMemcpyAsync(dRays, rays, n * sizeof(crt_ray), hipMemcpyHostToDevice, c->stream));
+    HIPCK(c, hipMemcpyAsync(dSeeds, seeds, n * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCK(c, launch_sample(c, accel, dRays, dSeeds, dRgb, (uint32_t)n, c->dQueryCursor, nullptr, c->stream));
+    HIPCK(c, hipMemcpyAsync(rgb, dRgb, n * 12, hipMemcpyDeviceToHost, c->stream));
+    HIPCK(c, hipMemcpyAsync(seeds, dSeeds, n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    return CRT_OK;
+}
+
+int crt_sample_device(crt_ctx* c, int accel, const crt_ray* d_rays, uint32_t* d_seeds, float* d_rgb, size_t n, void* stream)
+{
+    if (!c) return CRT_ERR_INVALID;
+    const char* what = "crt_sample_device";
+    int r;
+    if ((r = sample_check(c, accel, n, what))) return r;
+    if (n == 0) return CRT_OK;
+    HIPCK(c, hipSetDevice(c->cfg.device));
+    if ((r = check_device_buffer(c, d_rays, n * sizeof(crt_ray), what)) || (r = check_device_buffer(c, d_seeds, n * 4, what)) || (r = check_device_buffer(c, d_rgb, n * 12, what))) return r;
+    hipStream_t st = nullptr; int k = 0;
+    if ((r = begin_device_query(c, stream, what, &st, &k))) return r;
+    if (accel != 0 && c->altReady) HIPCK(c, hipStreamWaitEvent(st, c->altReady, 0));     // the accelerators' copies ran on the null stream
+    HIPCK(c, launch_sample(c, accel, d_rays, d_seeds, d_rgb, (uint32_t)n, c->dQuerySlots + 16 * k, nullptr, st));
+    return end_device_query(c, k, st);
+}
+
+// tools / tests: the lanes a full sample-query launch of this scene and accelerator holds at once (the grid is that many lanes, or fewer when the rays need fewer)
+extern "C" int crt_debug_sample_resident_lanes(crt_ctx* c, int accel, uint32_t* out)
+{
+    if (!c || !out) return CRT_ERR_INVALID;
+    int r;
+    if ((r = sample_check(c, accel, 0, "crt_debug_sample_resident_lanes"))) return r;
+    HIPCK(c, hipSetDevice(c->cfg.device));
+    HIPCK(c, launch_sample(c, accel, nullptr, nullptr, nullptr, 0u, nullptr, out, c->stream));
+    return CRT_OK;
 }
 
 int crt_get_light(crt_ctx* c, float pos[3], float color[3])

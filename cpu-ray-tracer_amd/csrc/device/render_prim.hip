@@ -1,6 +1,7 @@
 // render_prim.hip — PrimitiveScene (second half: infra/scene/primitive_scene.cpp + template/primitives.h Sphere :31, Cube :187, Quad :321, Torus :380)
 // behind the same two seams as the triangle scenes: scene.FindNearest for a ray buffer (find_nearest_prim_kernel) and Renderer::Sample per tile
-// (render_seq_kernel<PrimWorld>: seq_sample.h's sequential form — one wavefront per (tile, 64-frame window), lane = frame, a plain per-lane path loop).
+// (render_seq_kernel<PrimWorld>: seq_sample.h's sequential form — one wavefront per (tile, 64-frame window), lane = frame, a plain per-lane path loop) and per
+// ray of a buffer (sample_query_kernel<PrimWorld>, sample_query.h).
 // The scene is the reference's hard-coded demo room: six walls, the swinging light quad, the bouncing mirror ball, the "rounded corners" sphere, the spinning
 // glass cube and the glass torus, in the SPEEDTRIX / single-light configuration its headers select.  No acceleration structure: every ray tests all eleven.
 //
@@ -10,7 +11,7 @@
 // IEEE double + - * / sqrt), so oracle and kernel agree exactly; against a Windows build of the reference the torus' hit distances can differ in the last place.
 //
 // Numerics: -ffp-contract=off; fp32 as everywhere, fp64 only inside the torus test.  No MFMA.
-#include "seq_sample.h"
+#include "sample_query.h"
 
 namespace crt {
 
@@ -298,6 +299,13 @@ extern "C" hipError_t crt_launch_render_prim(const crt::Scene* sc, const crt::Pr
     const uint32_t windows = (frames + 63u) / 64u;
     if ((unsigned long long)tileCount * windows > 0x7fffffffull) return hipErrorInvalidValue;
     return crt::launch_render_seq(sc, crt::PrimWorld{*p}, slab, counters, tileFirst, tileStride, tileCount, tilesX, sppFirst, frames, passes, stream);
+}
+
+// Renderer::Sample over the eleven primitives for a buffer of rays with a seed each (crt_sample / crt_sample_device; sample_query.h)
+extern "C" hipError_t crt_launch_sample_query_prim(const crt::Scene* sc, const crt::PrimDev* p, const void* rays, uint32_t* seeds, float* rgb, uint32_t n, crt::Counters* counters,
+                                                   uint32_t* cursor, uint32_t* residentLanes, hipStream_t stream)
+{
+    return crt::launch_sample_query(sc, crt::PrimWorld{*p}, rays, seeds, rgb, n, counters, cursor, residentLanes, stream);
 }
 
 // diagnostics (crt_debug_device_probe, abi.cpp; record layouts in probe.hip): the torus' fp64 building blocks, one element per thread.  The functions are

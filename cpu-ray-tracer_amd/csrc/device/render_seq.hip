@@ -6,11 +6,12 @@
 //   TlasKdWorld      TLASFileScene::FindNearest built with TLAS_USE_KDTree (TLASKDTree over BLASKDTree: tlas_alt_intersect<1>)
 //   TlasGridWorld    ... with TLAS_USE_Grid (TLASGrid over BLASGrid: tlas_alt_intersect<2>)
 // The issue-bound renders of these scenes are render_pool_kernel / render_tiles_kernel; this form exists for the probe and for parity with the alternative
-// accelerators (crt_set_render_accel).
+// accelerators (crt_set_render_accel).  The same worlds serve sample_query_kernel (sample_query.h): Renderer::Sample for a caller's rays and seeds.
 //
 // Numerics: -ffp-contract=off, IEEE + - * / sqrt only (dev_common.h).  No MFMA: pointer chasing + slab / Möller–Trumbore tests.
 #include "alt_common.h"
 #include "file_surface.h"
+#include "sample_query.h"
 
 namespace crt {
 
@@ -103,4 +104,23 @@ extern "C" hipError_t crt_launch_render_alt(int accel, const crt::Scene* sc, con
         return crt::launch_render_seq(sc, kd, slab, counters, tileFirst, tileStride, tileCount, tilesX, sppFirst, frames, passes, stream);
     }
     return crt::launch_render_seq(sc, crt::GridWorld{{}, *acc}, slab, counters, tileFirst, tileStride, tileCount, tilesX, sppFirst, frames, passes, stream);
+}
+
+// Renderer::Sample for a buffer of rays with a seed each (crt_sample / crt_sample_device): accel 0 = the scene's BVH / TLAS, 1 / 2 = the KD-tree / grid (FileScene's
+// `acc`, or a two-level scene's BLAS set `tl`).  A world whose LDS columns exceed 64 KB per workgroup is refused (hipErrorInvalidValue), as crt_launch_render_alt does.
+// residentLanes != null: only report the lanes a full launch holds.
+extern "C" hipError_t crt_launch_sample_query(int accel, const crt::Scene* sc, const crt::AltAccelDev* acc, const crt::TlasAltDev* tl, const void* rays, uint32_t* seeds, float* rgb,
+                                              uint32_t n, crt::Counters* counters, uint32_t* cursor, uint32_t* residentLanes, hipStream_t stream)
+{
+    if (accel < 0 || accel > 2) return hipErrorInvalidValue;
+    if (accel == 0) {
+        if (sc->kind == 0) return crt::launch_sample_query(sc, crt::BvhWorld<0>{}, rays, seeds, rgb, n, counters, cursor, residentLanes, stream);
+        return crt::launch_sample_query(sc, crt::BvhWorld<1>{}, rays, seeds, rgb, n, counters, cursor, residentLanes, stream);
+    }
+    if (sc->kind != 0) {
+        if (accel == 1) return crt::launch_sample_query(sc, crt::TlasKdWorld{{}, *tl}, rays, seeds, rgb, n, counters, cursor, residentLanes, stream);
+        return crt::launch_sample_query(sc, crt::TlasGridWorld{{}, *tl}, rays, seeds, rgb, n, counters, cursor, residentLanes, stream);
+    }
+    if (accel == 1) return crt::launch_sample_query(sc, crt::KdWorld{{}, *acc}, rays, seeds, rgb, n, counters, cursor, residentLanes, stream);
+    return crt::launch_sample_query(sc, crt::GridWorld{{}, *acc}, rays, seeds, rgb, n, counters, cursor, residentLanes, stream);
 }

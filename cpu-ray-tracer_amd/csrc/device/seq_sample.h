@@ -3,6 +3,8 @@
 //   * the latency mode's cost probe (PROBE: render_seq.hip, abi.cpp probe_tile_costs);
 //   * Sample through FileScene's KD-tree / uniform grid (crt_set_render_accel; render_seq.hip);
 //   * Sample over the PrimitiveScene (render_prim.hip).
+// The per-path part (sample_step: one FindNearest + the Sample branch + the factor store; sample_unwind: the return path) is also what sample_query_kernel
+// (sample_query.h: Sample for a caller's rays and seeds) runs — there is one Sample body.
 // What differs between them is the "world" the loop runs in, a small policy class:
 //   uint32_t trace(sc, O, D, rD, h, stk)   scene.FindNearest into `h`; returns the traversal steps the probe counts (interior + triangle + TLAS steps; 0 where never probed)
 //   Surf surface(sc, h, I, D)              normal (already facing the ray), albedo, reflectivity, refractivity and absorption at the hit
@@ -22,6 +24,79 @@ constexpr uint32_t kSeqWaves = 4u;                         // wavefronts per wor
 constexpr uint32_t kProbeWaves = 8u;                       // cost probe: wavefronts (of 64 one-path lanes) per tile
 
 __device__ __host__ __forceinline__ uint32_t seq_lds_bytes(uint32_t stackWords) { return kSeqWaves * (stackWords + 15u) * 64u * 4u; }   // traversal stack + 15 throughput factors per lane
+
+// One trip of Renderer::Sample's recursion (renderer.cpp:50-100) for the path this lane holds: scene.FindNearest for the ray (O, D), then the branch.  Returns true when
+// the path has ended (L = the radiance of its last ray: sky, light, or black at the depth limit); otherwise the bounce's throughput factor is stored in this lane's
+// factor column `fst` (slot `depth`), depth is advanced and (O, D, inside) is the next ray.  Shared by render_seq_kernel and sample_query_kernel (sample_query.h): the
+// rnd draws in the reference's order and every float expression as written there.  `steps`: the cost probe's traversal + weighted shading steps (PROBE only).
+template <class World, bool PROBE>
+__device__ __forceinline__ bool sample_step(const Scene& sc, const World& world, uint32_t* stk, float* fst, f3& O, f3& D, bool& inside, int& depth, uint32_t& seed, f3& L,
+                                            uint32_t& nRays, uint32_t& nMesh, uint32_t& steps)
+{
+    const f3 rD = rcp_exact3(D);
+    Hit h; h.t = 1e34f; h.u = 0; h.v = 0; h.objIdx = -1; h.triIdx = -1;
+    nRays++;
+    const uint32_t traceSteps = world.trace(sc, O, D, rD, h, stk);
+    if (PROBE) steps += traceSteps + 3u;                                          // a shading step weighs about three traversal steps
+    if (World::kMeshHits && h.objIdx >= 2) nMesh++;
+    // ---------------- Renderer::Sample (renderer.cpp:50-100) ----------------
+    if (h.objIdx == -1) { L = world.miss(sc, D); return true; }
+    if (depth >= sc.depthLimit) { L = mk3(0, 0, 0); return true; }
+    if (h.objIdx == 0) { L = mk3(24, 24, 22); return true; }                       // the light
+    const f3 I = O + h.t * D;
+    const Surf s = world.surface(sc, h, I, D);
+    const f3 N = s.N, c = s.c;
+    f3 medium = mk3(1, 1, 1);
+    if (inside) {
+        const f3 ab = s.absorb * -h.t;
+        medium = mk3(crt_expf(ab.x), crt_expf(ab.y), crt_expf(ab.z));
+    }
+    f3 nv, factor; bool newInside = false;
+    const float r = rnd(seed);
+    if (r < s.refl) {                                                              // HandleMirror, renderer.cpp:20-25
+        nv = D - 2.0f * N * dot3(N, D);
+        factor = c * medium;
+    } else if (r < s.refl + s.refr) {                                              // HandleDielectric, renderer.cpp:27-45
+        nv = D - 2.0f * N * dot3(N, D);
+        const float n1 = inside ? 1.2f : 1, n2 = inside ? 1 : 1.2f;
+        const float eta = n1 / n2, cosi = dot3(-D, N);
+        const float cost2 = 1.0f - eta * eta * (1 - cosi * cosi);
+        if (cost2 > 0) {
+            const float a = n1 - n2, b2 = n1 + n2, R0 = (a * a) / (b2 * b2), cc = 1 - cosi;
+            const float Fr = R0 + (1 - R0) * (cc * cc * cc * cc * cc);
+            const f3 T = eta * D + ((eta * cosi - __builtin_sqrtf(__builtin_fabsf(cost2))) * N);
+            if (rnd(seed) > Fr) { nv = T; newInside = !inside; }
+        }
+        factor = c * medium;
+    } else {                                                                       // diffuse, renderer.cpp:93-99; diffusereflection tmplmath.h:535-544
+        f3 Rr;
+        do {
+            const float rz = rnd_pm1(seed);                                        // draw order pinned z, y, x
+            const float ry = rnd_pm1(seed);
+            const float rx = rnd_pm1(seed);
+            Rr = mk3(rx, ry, rz);
+        } while (dot3(Rr, Rr) > 1);
+        if (dot3(Rr, N) < 0) Rr = Rr * -1.0f;
+        nv = Rr * rcp_exact(__builtin_sqrtf(dot3(Rr, Rr)));                        // normalize(R)
+        const f3 brdf = c * CRT_INVPI;
+        const f3 pre = medium * brdf * 2.0f * CRT_PI;
+        factor = pre * dot3(nv, N);
+    }
+    // the bounce's throughput factor (albedo*medium*... multiplies on return: depth <= 4 here)
+    float* fd = fst + (uint32_t)(3 * depth) * 64u;
+    fd[0] = factor.x; fd[64] = factor.y; fd[128] = factor.z;
+    depth++;
+    O = I + nv * CRT_EPS; D = nv; inside = newInside;
+    return false;
+}
+
+// the recursion's return path: the factors of the `depth` bounces multiply the radiance innermost first (depth <= 5)
+__device__ __forceinline__ void sample_unwind(const float* fst, int depth, f3& L)
+{
+#pragma unroll
+    for (int k = 4; k >= 0; k--)
+        if (depth > k) { const float* fd = fst + (uint32_t)(3 * k) * 64u; L = mk3(fd[0], fd[64], fd[128]) * L; }
+}
 
 // entry = tile rank * windows + window.  PROBE = true is the cost probe of the latency mode: kProbeWaves entries per tile, lane l of entry q traces ONE path through
 // pixel (4 l + q) % 256 of the tile with a seed of its own (256 paths per tile per four entries), nothing is stored, and every wavefront adds the number of traversal /
@@ -74,66 +149,8 @@ __global__ __launch_bounds__(256, 4) void render_seq_kernel(const Scene sc, cons
         bool inside = false; int depth = 0;
         nPrimary++;
         f3 L = mk3(0, 0, 0);
-        for (;;) {
-            const f3 rD = rcp_exact3(D);
-            Hit h; h.t = 1e34f; h.u = 0; h.v = 0; h.objIdx = -1; h.triIdx = -1;
-            nRays++;
-            const uint32_t traceSteps = world.trace(sc, O, D, rD, h, stk);
-            if (PROBE) steps += traceSteps + 3u;                                  // a shading step weighs about three traversal steps
-            if (World::kMeshHits && h.objIdx >= 2) nMesh++;
-            // ---------------- Renderer::Sample (renderer.cpp:50-100) ----------------
-            if (h.objIdx == -1) { L = world.miss(sc, D); break; }
-            if (depth >= sc.depthLimit) { L = mk3(0, 0, 0); break; }
-            if (h.objIdx == 0) { L = mk3(24, 24, 22); break; }                     // the light
-            const f3 I = O + h.t * D;
-            const Surf s = world.surface(sc, h, I, D);
-            const f3 N = s.N, c = s.c;
-            f3 medium = mk3(1, 1, 1);
-            if (inside) {
-                const f3 ab = s.absorb * -h.t;
-                medium = mk3(crt_expf(ab.x), crt_expf(ab.y), crt_expf(ab.z));
-            }
-            f3 nv, factor; bool newInside = false;
-            const float r = rnd(seed);
-            if (r < s.refl) {                                                      // HandleMirror, renderer.cpp:20-25
-                nv = D - 2.0f * N * dot3(N, D);
-                factor = c * medium;
-            } else if (r < s.refl + s.refr) {                                      // HandleDielectric, renderer.cpp:27-45
-                nv = D - 2.0f * N * dot3(N, D);
-                const float n1 = inside ? 1.2f : 1, n2 = inside ? 1 : 1.2f;
-                const float eta = n1 / n2, cosi = dot3(-D, N);
-                const float cost2 = 1.0f - eta * eta * (1 - cosi * cosi);
-                if (cost2 > 0) {
-                    const float a = n1 - n2, b2 = n1 + n2, R0 = (a * a) / (b2 * b2), cc = 1 - cosi;
-                    const float Fr = R0 + (1 - R0) * (cc * cc * cc * cc * cc);
-                    const f3 T = eta * D + ((eta * cosi - __builtin_sqrtf(__builtin_fabsf(cost2))) * N);
-                    if (rnd(seed) > Fr) { nv = T; newInside = !inside; }
-                }
-                factor = c * medium;
-            } else {                                                               // diffuse, renderer.cpp:93-99; diffusereflection tmplmath.h:535-544
-                f3 Rr;
-                do {
-                    const float rz = rnd_pm1(seed);                                // draw order pinned z, y, x
-                    const float ry = rnd_pm1(seed);
-                    const float rx = rnd_pm1(seed);
-                    Rr = mk3(rx, ry, rz);
-                } while (dot3(Rr, Rr) > 1);
-                if (dot3(Rr, N) < 0) Rr = Rr * -1.0f;
-                nv = Rr * rcp_exact(__builtin_sqrtf(dot3(Rr, Rr)));                // normalize(R)
-                const f3 brdf = c * CRT_INVPI;
-                const f3 pre = medium * brdf * 2.0f * CRT_PI;
-                factor = pre * dot3(nv, N);
-            }
-            // the bounce's throughput factor (albedo*medium*... multiplies on return: depth <= 4 here)
-            float* fd = fst + (uint32_t)(3 * depth) * 64u;
-            fd[0] = factor.x; fd[64] = factor.y; fd[128] = factor.z;
-            depth++;
-            O = I + nv * CRT_EPS; D = nv; inside = newInside;
-        }
-        // unwind the recursion (innermost factor first), store the sample
-#pragma unroll
-        for (int k = 4; k >= 0; k--)
-            if (depth > k) { const float* fd = fst + (uint32_t)(3 * k) * 64u; L = mk3(fd[0], fd[64], fd[128]) * L; }
+        while (!sample_step<World, PROBE>(sc, world, stk, fst, O, D, inside, depth, seed, L, nRays, nMesh, steps)) {}
+        sample_unwind(fst, depth, L);                                             // unwind the recursion, store the sample
         if (!PROBE) {
             uint32_t pass = 0;
             if (passes != 1u) pass = item - pix * passes;

@@ -362,6 +362,28 @@ int  crt_get_sky_color(crt_ctx* ctx, const crt_ray* rays, float* rgb /* 3 * n */
 int  crt_get_sky_color_device(crt_ctx* ctx, const crt_ray* d_rays, float* d_rgb /* 3 * n */, size_t n, void* stream);
 int  crt_get_light(crt_ctx* ctx, float pos[3], float color[3]);
 
+/* Renderer::Sample(ray, seed, 0) — the path tracer's integrator ("3. PathTracer/renderer.cpp":50-100) — for n rays of the caller's with a seed each: light
+ * probes, irradiance baking, a camera of the caller's own, importance-sampled pixels, training sets.  ABI version 3 still: an addition, detected by symbol.
+ * rgb[3i .. 3i+2] = the radiance of the path that starts with rays[i]; seeds[i] is in/out: the xorshift32 state before / after the path, so a caller can chain
+ * paths exactly as Renderer::ProcessTile does (draw the y jitter, then the x jitter, build the primary ray, Sample).
+ * Per ray: O, D and inside are used as given — D is NOT normalised (the reference hands Sample unit directions; so should the caller), rD = 1 / D per component,
+ * depth starts at 0, depthLimit is crt_config's, every rnd draw is made in the reference's order and the throughput factors multiply innermost first: radiance and
+ * returned seed are bit for bit what the render entries compute for the same ray and seed.
+ * accel: as for crt_find_nearest_device — 0 = the BVH of a CRT_SCENE_FILE scene, the TLAS of a CRT_SCENE_TLAS scene, or the PrimitiveScene; CRT_ACCEL_KDTREE /
+ * CRT_ACCEL_GRID = the uploaded alternative structure (a two-level scene's per-BLAS sets included).  crt_set_render_accel is not consulted: the argument decides.
+ * Rays that are NOT traced come back as quiet NaN in all three channels, their seed untouched, and affect no other ray: a seed of 0 (xorshift32 maps 0 to 0, every
+ * draw would be 0 and the diffuse bounce's rejection loop would never end; a non-zero state never becomes 0), a non-finite component of O or D, or D = (0, 0, 0).
+ * The host entry applies the same rule per ray; it does not refuse the call.
+ * Counters: crt_counters.rays grows by the FindNearest calls made (mesh_hits as the render entries count it); `primary` is not touched.
+ * crt_sample_device: as the device entries above — d_rays (28 n bytes), d_seeds (4 n) and d_rgb (12 n) are device pointers on cfg.device, 4-byte aligned (NULL,
+ * misaligned, host or other-device memory: CRT_ERR_INVALID), `stream` a hipStream_t of that device or NULL; the ordering contract is theirs (a later
+ * crt_update_scene / crt_refit_device is ordered behind the launch).  crt_sample: host pointers, synchronous, through staging buffers the context keeps.
+ * Refusals (nothing is modified, crt_last_error says why): no scene or no such accelerator CRT_ERR_STATE; unknown accel CRT_ERR_INVALID; n > 2^31-1
+ * CRT_ERR_UNSUPPORTED; a structure whose traversal stack does not fit the kernel's LDS CRT_ERR_UNSUPPORTED (as crt_set_render_accel).  n == 0 is a no-op after
+ * the checks that need no buffer. */
+int  crt_sample(crt_ctx* ctx, int accel, const crt_ray* rays, uint32_t* seeds, float* rgb /* 3 * n */, size_t n);                          /* host pointers, synchronous */
+int  crt_sample_device(crt_ctx* ctx, int accel, const crt_ray* d_rays, uint32_t* d_seeds, float* d_rgb /* 3 * n */, size_t n, void* stream); /* device pointers, no host wait */
+
 /* ---- PrimitiveScene (second half): infra/scene/primitive_scene.cpp — the reference's hard-coded demo room (six walls, swinging light quad,
  * bouncing mirror ball, "rounded corners" sphere, spinning glass cube, glass torus; template/primitives.h Sphere :31, Cube :187, Quad :321, Torus :380; the
  * SPEEDTRIX / single-light configuration its headers select).  The binding passes the scene as its constructor + SetTime(t) leave it: the members below.
