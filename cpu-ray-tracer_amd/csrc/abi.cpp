@@ -89,6 +89,16 @@ struct EventPair { hipEvent_t a, b; int mode = -1; bool seen = false; };   // mo
 
 } // namespace
 
+// CRT_DEBUG_QUERY_GRID=<k>, k >= 1: every persistent query launch (find-nearest, is-occluded, their KD-tree / grid and two-level forms, Sample) uses at most k
+// workgroups, so a few thousand rays are enough for every lane to take ray after ray from the cursor (tests/test_gpu_query_lane_reuse.py).  Read on every launch
+// by the wrappers in device/*.hip (layout.h bounded_query_grid); unset or 0: the launch's own grid.  crt_debug_sample_resident_lanes is not a launch and ignores it.
+extern "C" uint32_t crt_debug_query_grid(void)
+{
+    const char* e = hook("CRT_DEBUG_QUERY_GRID");
+    const long k = e ? strtol(e, nullptr, 10) : 0;
+    return k > 0 ? (uint32_t)(k > 0x7fffffffL ? 0x7fffffffL : k) : 0u;
+}
+
 struct crt_ctx {
     crt_config cfg{};
     std::string err;

@@ -281,7 +281,7 @@ __global__ __launch_bounds__(64) void is_occluded_alt_kernel(const Scene sc, con
 static uint32_t query_waves(uint32_t n, uint32_t ldsBytes)
 {
     uint32_t perCu = ldsBytes ? (160u * 1024u) / ldsBytes : 16u; if (perCu > 16u) perCu = 16u; if (perCu < 4u) perCu = 4u;      // 4 wavefronts per SIMD, LDS stacks permitting (measured: 8 per SIMD is no faster for the grid and 17 % slower for the BVH)
-    const uint32_t need = (n + 63u) / 64u, fill = 256u * perCu; return need < fill ? need : fill;
+    const uint32_t need = (n + 63u) / 64u, fill = 256u * perCu; return crt::bounded_query_grid(need < fill ? need : fill);
 }
 
 extern "C" hipError_t crt_launch_find_nearest_alt(int kind, const crt::Scene* sc, const crt::AltAccelDev* acc, const void* rays, void* hits, uint32_t n, uint32_t* cursor, hipStream_t stream)

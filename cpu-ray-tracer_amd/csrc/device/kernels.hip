@@ -1282,7 +1282,7 @@ extern "C" hipError_t crt_launch_find_nearest(const crt::Scene* sc, const void* 
     if (hipMemsetAsync(cursor, 0, 4, stream) != hipSuccess) return hipGetLastError();
     uint32_t perCu = ldsBytes ? (160u * 1024u) / ldsBytes : 16u; if (perCu > 16u) perCu = 16u; if (perCu < 4u) perCu = 4u;      // 4 wavefronts per SIMD, LDS stacks permitting (measured: 8 per SIMD is no faster for the grid and 17 % slower for the BVH)
     const uint32_t need = (n + 63u) / 64u, fill = 256u * perCu;          // persistent wavefronts: the device full once, never more than the rays need
-    dim3 grid(need < fill ? need : fill), block(64);
+    dim3 grid(crt::bounded_query_grid(need < fill ? need : fill)), block(64);
     hipLaunchKernelGGL(crt::find_nearest_kernel, grid, block, ldsBytes, stream, *sc, (const crt::RayIn*)rays, (crt::HitOut*)hits, n, counters, cursor);
     return hipGetLastError();
 }
@@ -1294,7 +1294,7 @@ extern "C" hipError_t crt_launch_is_occluded(const crt::Scene* sc, const void* r
     if (hipMemsetAsync(cursor, 0, 4, stream) != hipSuccess) return hipGetLastError();
     uint32_t perCu = ldsBytes ? (160u * 1024u) / ldsBytes : 16u; if (perCu > 16u) perCu = 16u; if (perCu < 4u) perCu = 4u;      // as crt_launch_find_nearest
     const uint32_t need = (n + 63u) / 64u, fill = 256u * perCu;
-    dim3 grid(need < fill ? need : fill), block(64);
+    dim3 grid(crt::bounded_query_grid(need < fill ? need : fill)), block(64);
     hipLaunchKernelGGL(crt::is_occluded_kernel, grid, block, ldsBytes, stream, *sc, (const crt::ShadowRayIn*)rays, occluded, n, cursor);
     return hipGetLastError();
 }

@@ -140,3 +140,10 @@ struct TlasAltDev {                       // passed by value, like AltAccelDev
 };
 
 } // namespace crt
+
+// CRT_DEBUG_QUERY_GRID=<k> (a test switch, abi.cpp; 0 when unset, or when the process has not enabled the switches): an upper bound on the workgroups of a
+// persistent query launch, so that a launch of a few thousand rays reuses every lane many times.  Host side only: each launch wrapper passes its grid through it.
+extern "C" uint32_t crt_debug_query_grid(void);
+namespace crt {
+inline uint32_t bounded_query_grid(uint32_t grid) { const uint32_t k = crt_debug_query_grid(); return (k != 0u && k < grid) ? k : grid; }
+} // namespace crt

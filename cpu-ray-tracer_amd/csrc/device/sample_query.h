@@ -108,7 +108,7 @@ hipError_t launch_sample_query(const Scene* sc, const World& world, const void* 
     if (!cursor || !counters) return hipErrorInvalidValue;
     if (hipMemsetAsync(cursor, 0, 4, stream) != hipSuccess) return hipGetLastError();
     const uint32_t need = (n + 64u * kSeqWaves - 1u) / (64u * kSeqWaves);
-    hipLaunchKernelGGL((sample_query_kernel<World>), dim3(need < resident ? need : resident), dim3(64u * kSeqWaves), ldsBytes, stream, *sc, world,
+    hipLaunchKernelGGL((sample_query_kernel<World>), dim3(bounded_query_grid(need < resident ? need : resident)), dim3(64u * kSeqWaves), ldsBytes, stream, *sc, world,
                        (const SampleRay*)rays, seeds, rgb, n, counters, cursor);
     return hipGetLastError();
 }

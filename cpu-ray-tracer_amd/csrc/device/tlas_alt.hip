@@ -209,7 +209,7 @@ __global__ __launch_bounds__(64) void tlas_alt_query_kernel(const Scene sc, cons
 static uint32_t tlas_query_waves(uint32_t n, uint32_t ldsBytes)
 {
     uint32_t perCu = ldsBytes ? (160u * 1024u) / ldsBytes : 16u; if (perCu > 16u) perCu = 16u; if (perCu < 4u) perCu = 4u;
-    const uint32_t need = (n + 63u) / 64u, fill = 256u * perCu; return need < fill ? need : fill;
+    const uint32_t need = (n + 63u) / 64u, fill = 256u * perCu; return crt::bounded_query_grid(need < fill ? need : fill);
 }
 
 extern "C" hipError_t crt_launch_tlas_alt_query(int kind, bool occl, const crt::Scene* sc, const crt::TlasAltDev* tl, const void* rays, void* out, uint32_t n, uint32_t* cursor,

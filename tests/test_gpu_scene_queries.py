@@ -171,6 +171,7 @@ def test_find_nearest_device_equals_host_entry(crt, orc, bunny_file, scene):
         assert_hits_equal(hits_np(crt, h), host, (scene, n))
         if c_host is not None:
             assert ctx.counters() == c_host, (scene, n)                   # the same counting as crt_find_nearest
+    big = hits_np(crt, h)                                                 # the 2^20-ray launch: every wavefront refills from the cursor, under real contention
     # the O / D form builds the same records
     h2 = ctx.find_nearest_device(O=torch.from_numpy(O[:3000]).to(dev()), D=torch.from_numpy(D[:3000]).to(dev()),
                                  inside=torch.from_numpy(inside[:3000]).to(dev()), accel=accel)
@@ -187,6 +188,29 @@ def test_find_nearest_device_equals_host_entry(crt, orc, bunny_file, scene):
         got = hits_np(crt, ctx.find_nearest_device(rays[:4000]))
         for fld in ("t", "u", "v", "objIdx", "triIdx"):
             assert np.array_equal(got[fld].view(np.uint32), w[fld].view(np.uint32)), (scene, fld)
+    # ... and the 2^20-ray launch, where every lane takes ray after ray, on a strided subset of 8 192 (tests/test_gpu_query_lane_reuse.py: the same with the
+    # launch bounded to a few workgroups and the rays in adversarial orders)
+    n = 1 << 20
+    sub = np.arange(8192) * (n // 8192)
+    if scene in ("file", "tlas", "prim"):
+        w = o.find_nearest(O[sub], D[sub], inside[sub])
+        for fld in (("t", "u", "v", "objIdx", "triIdx") if scene == "prim" else FIELDS):          # (PrimitiveScene counts no traversal steps)
+            assert np.array_equal(big[fld][sub].view(np.uint32), w[fld].view(np.uint32)), (scene, "2^20", fld)
+    else:
+        # the oracle's restatement of the accelerator alone: the whole record where the device reports a miss, the same hit where it reports the mesh
+        # (test_gpu_alt_accel.test_alt_accel_edge_cases_and_errors), and the oracle's BVH answer on rays without a zero direction component
+        a = orc.alt_accel(scene, hs.bvh(0)["tris"]); w = a.intersect(O[sub], D[sub]); a.close()
+        got = big[sub]
+        miss, mesh, general = got["objIdx"] == -1, got["objIdx"] >= 2, np.all(D[sub] != 0, axis=1)
+        assert miss.sum() > 100 and mesh.sum() > 100
+        for fld in FIELDS:
+            assert np.array_equal(got[fld][miss].view(np.uint32), w[fld][miss].view(np.uint32)), (scene, "2^20 miss", fld)
+        for fld in ("t", "u", "v", "triIdx"):
+            assert np.array_equal(got[fld][mesh].view(np.uint32), w[fld][mesh].view(np.uint32)), (scene, "2^20 mesh", fld)
+        ob, _ = orc.load_scene(xml, 0, ASSETS)
+        wb = ob.find_nearest(O[sub], D[sub], inside[sub])
+        for fld in ("t", "u", "v", "objIdx", "triIdx"):
+            assert np.array_equal(got[fld][general].view(np.uint32), wb[fld][general].view(np.uint32)), (scene, "2^20 BVH answer", fld)
     if own is not None:
         own.close()
 
