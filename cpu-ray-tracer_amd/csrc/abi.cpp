@@ -1,10 +1,8 @@
 // abi.cpp — implementation of include/crt_abi.h: context, scene flattening + upload, launches, read-back.
-// Host-only logic; the kernels live in device/kernels.hip.  There is NO CPU rendering path in this library:
-// without a HIP device crt_create fails with CRT_ERR_NO_DEVICE.
+// Host-only logic; the kernels live in device/*.hip, behind the launch wrappers that device/launch.h declares, and take the structs of device/layout.h.
+// There is NO CPU rendering path in this library: without a HIP device crt_create fails with CRT_ERR_NO_DEVICE.
 #include "../../include/crt_abi.h"
-#include "device/layout.h"
-
-#include <hip/hip_runtime.h>
+#include "device/launch.h"
 
 #include <cmath>
 #include <cstdarg>
@@ -18,58 +16,12 @@
 #include <vector>
 #include <chrono>
 
-extern "C" uint32_t crt_render_resident_waves(int, int, uint32_t);
-extern "C" uint32_t crt_probe_paths();
-extern "C" hipError_t crt_launch_render(const crt::Scene*, void*, crt::Counters*, unsigned long long*, const uint32_t*, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, int, const uint32_t*, uint32_t, uint32_t*, uint32_t, unsigned long long*, hipStream_t);
-extern "C" size_t crt_pool_scratch_bytes_per_window(uint32_t);
-extern "C" hipError_t crt_launch_render_pool(const crt::Scene*, void*, void*, crt::Counters*, unsigned long long*, const uint32_t*, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, int, uint32_t, uint32_t*, unsigned long long*, hipStream_t);
-extern "C" uint32_t crt_pool_streams(uint32_t frames);
-extern "C" hipError_t crt_launch_probe(const crt::Scene*, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t*, hipStream_t);
-extern "C" hipError_t crt_launch_accumulate(const void*, void*, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, hipStream_t);
-extern "C" hipError_t crt_launch_find_nearest(const crt::Scene*, const void*, void*, uint32_t, crt::Counters*, uint32_t, uint32_t*, hipStream_t);
-namespace crt { struct AltAccelDev; }
-extern "C" hipError_t crt_launch_whitted(const crt::Scene*, int, const crt::AltAccelDev*, const crt::TlasAltDev*, void*, uint32_t*, crt::Counters*, uint32_t, hipStream_t);
-extern "C" hipError_t crt_launch_whitted_inspect(const crt::Scene*, int, const crt::AltAccelDev*, const crt::TlasAltDev*, int, int32_t, void*, uint32_t*, crt::Counters*, int32_t*, int32_t*, void*, uint32_t,
-                                                 hipStream_t);
-extern "C" size_t crt_whitted_inspect_work_bytes(uint32_t);
-extern "C" hipError_t crt_launch_render_alt(int, const crt::Scene*, const crt::AltAccelDev*, const crt::TlasAltDev*, void*, crt::Counters*, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, hipStream_t);
-extern "C" hipError_t crt_launch_sample_query(int, const crt::Scene*, const crt::AltAccelDev*, const crt::TlasAltDev*, const void*, uint32_t*, float*, uint32_t, crt::Counters*, uint32_t*, uint32_t*, hipStream_t);
-extern "C" hipError_t crt_launch_resolve(const void*, uint32_t*, float*, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, float, hipStream_t);
-extern "C" hipError_t crt_launch_commit_frame(const void*, uint32_t, uint32_t, void*, uint32_t*, float*, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, float, hipStream_t);
-
 static_assert(sizeof(crt_bvh_node) == 32 && sizeof(crt_tri) == 112 && sizeof(crt_tlas_node) == 32, "reference layouts");
 static_assert(sizeof(crt::NodePair) == 64 && sizeof(crt::LeafTri) == 48 && sizeof(crt::ShadeTri) == 64 && sizeof(crt::TlasNode) == 32 &&
               sizeof(crt::Instance) == 128 && sizeof(crt::Material) == 32 && offsetof(crt::Instance, T) == 64, "device layouts");
 static_assert(sizeof(crt_counters) == sizeof(crt::Counters), "counter layout");
-static_assert(sizeof(crt_kd_node) == 48, "flat KD node");
-// device view of the alternative accelerators (device/alt_accel.hip)
-namespace crt {
-struct KdNode; struct AltTri;
-struct AltAccelDev {
-    const void* kdNodes; const uint32_t* kdRefs; uint32_t kdStack;
-    const void* tris;
-    int32_t res[3]; float cell[3]; float lo[3], hi[3]; const uint32_t* cellStart; const int32_t* cellRefs;
-};
-}
-namespace crt {
-struct PrimDev {                          // = device/render_prim.hip
-    float quadInvT[12], quadNrm[3], quadSize; float spherePos[3], pad0; float cubeInvM[12], cubeM[12], cubeMin[3], cubeMax[3];
-    float torusInvT[12], torusT[12], rt2, rc2, r2, pad1; float refl[11], refr[11], absorb[33]; float pad2; const uint32_t* red; const uint32_t* blue;
-};
-}
-extern "C" hipError_t crt_launch_find_nearest_prim(const crt::PrimDev*, const void*, void*, uint32_t, hipStream_t);
-extern "C" hipError_t crt_launch_render_prim(const crt::Scene*, const crt::PrimDev*, void*, crt::Counters*, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, hipStream_t);
-extern "C" hipError_t crt_launch_sample_query_prim(const crt::Scene*, const crt::PrimDev*, const void*, uint32_t*, float*, uint32_t, crt::Counters*, uint32_t*, uint32_t*, hipStream_t);
-extern "C" hipError_t crt_launch_check_reciprocals(unsigned long long*, hipStream_t);
-extern "C" hipError_t crt_launch_probe_f32(int, const void*, void*, uint32_t, hipStream_t);
-extern "C" hipError_t crt_launch_probe_f64(int, const void*, void*, uint32_t, hipStream_t);
-extern "C" hipError_t crt_launch_find_nearest_alt(int, const crt::Scene*, const crt::AltAccelDev*, const void*, void*, uint32_t, uint32_t*, hipStream_t);
-extern "C" hipError_t crt_launch_is_occluded(const crt::Scene*, const void*, int32_t*, uint32_t, uint32_t, uint32_t*, hipStream_t);
-extern "C" hipError_t crt_launch_is_occluded_alt(int, const crt::Scene*, const crt::AltAccelDev*, const void*, int32_t*, uint32_t, uint32_t*, hipStream_t);
-extern "C" hipError_t crt_launch_hit_info(const crt::Scene*, const void*, const void*, void*, uint32_t, uint32_t, uint32_t, hipStream_t);
-extern "C" hipError_t crt_launch_sky_color(const crt::Scene*, const void*, float*, uint32_t, hipStream_t);
-extern "C" hipError_t crt_launch_tlas_alt_query(int, bool, const crt::Scene*, const crt::TlasAltDev*, const void*, void*, uint32_t, uint32_t*, hipStream_t);
-extern "C" hipError_t crt_launch_refit(char*, uint32_t, uint32_t, uint32_t, uint32_t, const float*, const void*, const uint32_t*, uint32_t, uint32_t, float*, hipStream_t);
+static_assert(sizeof(crt_kd_node) == 48 && sizeof(crt::KdNode) == sizeof(crt_kd_node) && sizeof(crt::AltTri) == 48, "flat KD node (uploaded as it comes), alternative accelerators' triangle record");
+static_assert(offsetof(crt::PrimDev, red) == 536 && sizeof(crt::PrimDev) == 552, "PrimDev: 134 floats, then the two texel pointers");
 static_assert(sizeof(crt::BlasAltDesc) == 72, "BLAS descriptor");
 static_assert(sizeof(crt_shadow_ray) == 28 && sizeof(crt_ray) == 28 && sizeof(crt_hit) == 28, "query records");
 static_assert(sizeof(crt_hit_info) == 48 && offsetof(crt_hit_info, material) == 12 && offsetof(crt_hit_info, N) == 16 && offsetof(crt_hit_info, albedo) == 32 && offsetof(crt_hit_info, v) == 44, "crt_hit_info: three 16-byte pieces");
@@ -91,7 +43,7 @@ struct EventPair { hipEvent_t a, b; int mode = -1; bool seen = false; };   // mo
 
 // CRT_DEBUG_QUERY_GRID=<k>, k >= 1: every persistent query launch (find-nearest, is-occluded, their KD-tree / grid and two-level forms, Sample) uses at most k
 // workgroups, so a few thousand rays are enough for every lane to take ray after ray from the cursor (tests/test_gpu_query_lane_reuse.py).  Read on every launch
-// by the wrappers in device/*.hip (layout.h bounded_query_grid); unset or 0: the launch's own grid.  crt_debug_sample_resident_lanes is not a launch and ignores it.
+// by the wrappers in device/*.hip (launch.h bounded_query_grid); unset or 0: the launch's own grid.  crt_debug_sample_resident_lanes is not a launch and ignores it.
 extern "C" uint32_t crt_debug_query_grid(void)
 {
     const char* e = hook("CRT_DEBUG_QUERY_GRID");
@@ -148,13 +100,12 @@ struct crt_ctx {
     hipEvent_t sceneReady = nullptr;      // recorded behind the last in-place scene update; render launches wait for it on their stream
     bool havePrim = false; crt::PrimDev prim{}; uint32_t* dPrimTex = nullptr;       // crt_upload_primitive_scene: PrimitiveScene instead of a triangle scene
     int renderAccel = 0;                  // crt_set_render_accel: 0 = the scene's BVH / TLAS, CRT_ACCEL_KDTREE / CRT_ACCEL_GRID = Sample and Trace go through that structure
-    crt::AltAccelDev alt{}; bool haveKd = false, haveGrid = false; std::vector<void*> altAllocs[2]; void* altTris = nullptr; uint32_t altTriCount = 0;   // KD-tree [0] / grid [1] buffers
+    crt::AltAccelDev alt{}; bool haveKd = false, haveGrid = false; std::vector<void*> altAllocs[2]; crt::AltTri* altTris = nullptr; uint32_t altTriCount = 0;   // KD-tree [0] / grid [1] buffers
     // crt_upload_blas_accel: a two-level scene's BLASKDTree [0] / BLASGrid [1] set.  haveBlas is cleared by CRT_UPDATE_BOUNDS without a host wait; the buffers
     // go with the next upload of the kind or of a scene, which wait for the queries first
     crt::TlasAltDev blasAlt[2]{}; bool haveBlas[2] = {false, false}; std::vector<void*> blasAllocs[2];
     bool hasAlt(int kind) const { return (kind == CRT_ACCEL_KDTREE && (haveKd || haveBlas[0])) || (kind == CRT_ACCEL_GRID && (haveGrid || haveBlas[1])); }
-    void* dQueryRays = nullptr; void* dQueryHits = nullptr; size_t queryCap = 0;      // crt_find_nearest staging (rays)
-    void* dShadeStage = nullptr; size_t shadeStageBytes = 0;                          // crt_get_hit_info / crt_get_sky_color staging (output, rays, hits)
+    char* dStage = nullptr; size_t stageCap = 0;   // device staging of the host-buffer query entries (stage()): one call's records in and out, then the call synchronises
     // Device-buffer queries (crt_find_nearest_device / crt_is_occluded_device) on callers' streams: each launch draws its rays from a cursor word of its own
     // (slot k at dQuerySlots + 16k, one cache line each), handed out as a ring; `done` is recorded on the caller's stream behind the launch, and a slot is
     // reused only after its event has completed.  The same events order later scene writes behind the queries still in flight (order_behind_queries).
@@ -253,6 +204,15 @@ int upload(crt_ctx* c, const std::vector<T>& v, const T** out)
     return 0;
 }
 
+// one array of an accelerator: a device allocation of its own, noted in `allocs`, filled by a synchronous copy; *out = the view's typed pointer (null: empty array)
+template <class T>
+int upload_array(crt_ctx* c, std::vector<void*>& allocs, const void* src, size_t bytes, const T** out)
+{
+    *out = nullptr; if (!bytes) return 0;
+    void* d = nullptr; HIPCK(c, hipMalloc(&d, bytes)); allocs.push_back(d);
+    HIPCK(c, hipMemcpy(d, src, bytes, hipMemcpyHostToDevice)); *out = static_cast<const T*>(d); return 0;
+}
+
 // height of the tree below node 0 in pushes: the ordered traversal pushes at most one sibling per interior level
 int bvh_height(crt_ctx* c, const crt_bvh& b, uint32_t* heightOut)
 {
@@ -289,6 +249,15 @@ int order_behind_queries(crt_ctx* c)
         HIPCK(c, hipStreamWaitEvent(c->stream, q.done, 0));
     }
     return 0;
+}
+
+// before the scene's or an accelerator set's buffers are freed: every launch that may still read them has finished (render streams first: the main stream's accumulates wait on them)
+int drain_all(crt_ctx* c)
+{
+    for (auto st : c->streams) HIPCK(c, hipStreamSynchronize(st));
+    if (c->aheadStream) HIPCK(c, hipStreamSynchronize(c->aheadStream));
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    return wait_queries(c);
 }
 
 } // namespace
@@ -429,9 +398,7 @@ void crt_destroy(crt_ctx* c)
     if (c->dBlockDesc) (void)hipFree(c->dBlockDesc);
     if (c->hBlockDesc) (void)hipHostFree(c->hBlockDesc);
     if (c->descReady) (void)hipEventDestroy(c->descReady);
-    if (c->dQueryRays) (void)hipFree(c->dQueryRays);
-    if (c->dQueryHits) (void)hipFree(c->dQueryHits);
-    if (c->dShadeStage) (void)hipFree(c->dShadeStage);
+    if (c->dStage) (void)hipFree(c->dStage);
     for (int k = 0; k < 2; k++) { if (c->hTileOrder[k]) (void)hipHostFree(c->hTileOrder[k]); if (c->orderCopied[k]) (void)hipEventDestroy(c->orderCopied[k]); }
     for (int k = 0; k < 2; k++) { if (c->hStage[k]) (void)hipHostFree(c->hStage[k]); if (c->stageCopied[k]) (void)hipEventDestroy(c->stageCopied[k]); }
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -619,11 +586,7 @@ int crt_upload_scene(crt_ctx* c, const crt_scene_desc* sd)
         bindTex(m, sd->materials[i].texture);
     }
 
-    // launches still in flight read the previous scene's buffers (render streams first: the main stream's accumulates wait on them)
-    for (auto st : c->streams) HIPCK(c, hipStreamSynchronize(st));
-    if (c->aheadStream) HIPCK(c, hipStreamSynchronize(c->aheadStream));
-    HIPCK(c, hipStreamSynchronize(c->stream));
-    { const int r = wait_queries(c); if (r) return r; }
+    { const int r = drain_all(c); if (r) return r; }                     // launches still in flight read the previous scene's buffers
     c->freeScene();
     uint32_t* dTexels = nullptr;
     HIPCK(c, hipMalloc((void**)&dTexels, (size_t)texels * 4)); c->sceneAllocs.push_back(dTexels);
@@ -1826,31 +1789,67 @@ int crt_whitted_tick_inspect(crt_ctx* c, int inspect, int32_t peakTraversalIn, i
     return CRT_OK;
 }
 
+// ---- the host-buffer query entries: records in, one launch on the main stream, records out, synchronise.  Their device staging is ONE allocation, grown to the high-water
+// mark (hipMalloc synchronises the device; 16-byte aligned and more); every entry returns only after hipStreamSynchronize, so each lays its sub-buffers out from offset 0 ----
+static int stage(crt_ctx* c, size_t bytes)
+{
+    if (bytes <= c->stageCap) return 0;
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    if (c->dStage) (void)hipFree(c->dStage);
+    c->dStage = nullptr; c->stageCap = 0;
+    HIPCK(c, hipMalloc((void**)&c->dStage, bytes));
+    c->stageCap = bytes;
+    return 0;
+}
+
+// FindNearest (crt_hit records) / IsOccluded (occl: int32 flags) for n rays in device memory: THE choice of launcher, for host and device entries, after their checks.  accel 0 = the
+// scene's own structure (BVH / TLAS, or the PrimitiveScene's eleven primitives), else the uploaded KD-tree / grid: FileScene's structure, or a two-level scene's BLAS set.
+static hipError_t launch_query(crt_ctx* c, bool occl, int accel, const void* rays, void* out, uint32_t n, uint32_t* cursor, hipStream_t st)
+{
+    if (accel != 0) {
+        if (c->hScene.kind == CRT_SCENE_TLAS) return crt_launch_tlas_alt_query(accel, occl, &c->hScene, &c->blasAlt[accel - 1], rays, out, n, cursor, st);
+        if (occl) return crt_launch_is_occluded_alt(accel, &c->hScene, &c->alt, rays, static_cast<int32_t*>(out), n, cursor, st);
+        return crt_launch_find_nearest_alt(accel, &c->hScene, &c->alt, rays, out, n, cursor, st);
+    }
+    if (occl) return crt_launch_is_occluded(&c->hScene, rays, static_cast<int32_t*>(out), n, c->ldsBytes, cursor, st);
+    if (c->havePrim) return crt_launch_find_nearest_prim(&c->prim, rays, out, n, st);
+    return crt_launch_find_nearest(&c->hScene, rays, out, n, c->dCounters, c->ldsBytes, cursor, st);
+}
+
+// crt_find_nearest / crt_find_nearest_alt / crt_is_occluded after their own checks (n >= 1): a ray and a shadow ray are 28 bytes alike
+static int query_host(crt_ctx* c, bool occl, int accel, const void* rays, void* out, size_t n)
+{
+    const size_t outSize = occl ? sizeof(int32_t) : sizeof(crt_hit);
+    HIPCK(c, hipSetDevice(c->cfg.device));
+    if (const int r = stage(c, n * (sizeof(crt_ray) + outSize))) return r;
+    char* dRays = c->dStage; char* dOut = dRays + n * sizeof(crt_ray);
+    HIPCK(c, hipMemcpyAsync(dRays, rays, n * sizeof(crt_ray), hipMemcpyHostToDevice, c->stream));
+    HIPCK(c, launch_query(c, occl, accel, dRays, dOut, (uint32_t)n, c->dQueryCursor, c->stream));
+    HIPCK(c, hipMemcpyAsync(out, dOut, n * outSize, hipMemcpyDeviceToHost, c->stream));
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    return CRT_OK;
+}
+
 int crt_find_nearest(crt_ctx* c, const crt_ray* rays, crt_hit* hits, size_t n)
 {
     if (!c || (n && (!rays || !hits))) return CRT_ERR_INVALID;
     if (!c->haveScene && !c->havePrim) return c->fail(CRT_ERR_STATE, "crt_find_nearest before crt_upload_scene");
     if (n == 0) return CRT_OK;
     if (n > 0x7fffffffull) return c->fail(CRT_ERR_UNSUPPORTED, "at most 2^31-1 rays per call");
-    HIPCK(c, hipSetDevice(c->cfg.device));
-    // query buffers are kept and grown to the high-water mark (hipMalloc synchronises the device)
-    if (n > c->queryCap) {
-        HIPCK(c, hipStreamSynchronize(c->stream));
-        if (c->dQueryRays) (void)hipFree(c->dQueryRays);
-        if (c->dQueryHits) (void)hipFree(c->dQueryHits);
-        c->dQueryRays = c->dQueryHits = nullptr; c->queryCap = 0;
-        HIPCK(c, hipMalloc(&c->dQueryRays, n * sizeof(crt_ray)));
-        HIPCK(c, hipMalloc(&c->dQueryHits, n * sizeof(crt_hit)));
-        c->queryCap = n;
-    }
-    void *dR = c->dQueryRays, *dH = c->dQueryHits;
-    HIPCK(c, hipMemcpyAsync(dR, rays, n * sizeof(crt_ray), hipMemcpyHostToDevice, c->stream));
-    if (c->havePrim) HIPCK(c, crt_launch_find_nearest_prim(&c->prim, dR, dH, (uint32_t)n, c->stream));
-    else HIPCK(c, crt_launch_find_nearest(&c->hScene, dR, dH, (uint32_t)n, c->dCounters, c->ldsBytes, c->dQueryCursor, c->stream));
-    HIPCK(c, hipMemcpyAsync(hits, dH, n * sizeof(crt_hit), hipMemcpyDeviceToHost, c->stream));
-    HIPCK(c, hipStreamSynchronize(c->stream));
-    return CRT_OK;
+    return query_host(c, false, 0, rays, hits, n);
 }
+
+// the alternative accelerators' triangle record.  triIdx = what a hit reports: the triangle's index (crt_upload_alt_accel) / its global shade index, shadeBase + BLAS-local index (_blas_accel)
+static crt::AltTri alt_tri(const crt_tri& t, uint32_t triIdx)
+{
+    crt::AltTri o{};                                                       // pad = 0
+    for (int k = 0; k < 3; k++) { o.v0[k] = t.vertex0[k]; o.e1[k] = t.vertex1[k] - t.vertex0[k]; o.e2[k] = t.vertex2[k] - t.vertex0[k]; }
+    o.triIdx = triIdx; o.objIdx = t.objIdx;
+    return o;
+}
+
+// LDS of the single-wavefront kernels (the find-nearest / is-occluded queries, Whitted): `words` dwords of traversal stack per lane must fit one workgroup's 64 KiB
+static bool wave_stack_fits(uint64_t words) { return words * 64u * 4u <= 64u * 1024u; }
 
 // the checks of one KD-tree / grid description (crt_upload_alt_accel, and every BLAS's of crt_upload_blas_accel); kdHeight: the KD-tree's height
 static int check_alt_accel(crt_ctx* c, const crt_alt_accel* a, uint32_t* kdHeightOut)
@@ -1872,7 +1871,7 @@ static int check_alt_accel(crt_ctx* c, const crt_alt_accel* a, uint32_t* kdHeigh
             st.push_back({(uint32_t)nd.left, d + 1}); st.push_back({(uint32_t)nd.right, d + 1});
         }
         for (uint32_t i = 0; i < a->kdTriIndexCount; i++) if (a->kdTriIndices[i] >= a->triCount) return c->fail(CRT_ERR_INVALID, "kdTriIndices[%u] out of range", i);
-        if ((kdHeight + 1) * 128u * 4u > 64u * 1024u) return c->fail(CRT_ERR_UNSUPPORTED, "KD-tree height %u exceeds the LDS traversal stack", kdHeight);
+        if (!wave_stack_fits((uint64_t)(kdHeight + 1) * 2u)) return c->fail(CRT_ERR_UNSUPPORTED, "KD-tree height %u exceeds the LDS traversal stack", kdHeight);
     } else {
         uint64_t cells = 1;
         for (int k = 0; k < 3; k++) { if (a->gridResolution[k] < 1 || a->gridResolution[k] > 128) return c->fail(CRT_ERR_INVALID, "grid resolution must be 1..128 per axis (grid.cpp:22)"); cells *= (uint64_t)a->gridResolution[k]; }
@@ -1897,40 +1896,31 @@ int crt_upload_alt_accel(crt_ctx* c, const crt_alt_accel* a)
     const int slot = a->kind == CRT_ACCEL_KDTREE ? 0 : 1;
     HIPCK(c, hipStreamSynchronize(c->stream));                            // queries of the previous structure
     { const int r = wait_queries(c); if (r) return r; }                  // ... also those on callers' streams
-    for (void* p : c->altAllocs[slot]) (void)hipFree(p);
-    c->altAllocs[slot].clear();
+    std::vector<void*>& allocs = c->altAllocs[slot];
+    for (void* p : allocs) (void)hipFree(p);
+    allocs.clear();
     if (slot == 0) c->haveKd = false; else c->haveGrid = false;
     if (c->renderAccel == a->kind) c->renderAccel = 0;
-    auto up = [&](const void* src, size_t bytes, const void** out) -> int {
-        *out = nullptr; if (!bytes) return 0;
-        void* d = nullptr; HIPCK(c, hipMalloc(&d, bytes)); c->altAllocs[slot].push_back(d);
-        HIPCK(c, hipMemcpy(d, src, bytes, hipMemcpyHostToDevice)); *out = d; return 0;
-    };
     int r;
     // Möller–Trumbore operands in the reference's triangle order (one array shared by both structures)
     if (!c->altTris || c->altTriCount != a->triCount) {
         if (c->altTris) { (void)hipFree(c->altTris); c->altTris = nullptr; }
-        HIPCK(c, hipMalloc(&c->altTris, (size_t)a->triCount * 48)); c->altTriCount = a->triCount;
+        HIPCK(c, hipMalloc((void**)&c->altTris, (size_t)a->triCount * sizeof(crt::AltTri))); c->altTriCount = a->triCount;
     }
     {
-        std::vector<float> rec((size_t)a->triCount * 12);
-        for (uint32_t i = 0; i < a->triCount; i++) {
-            const crt_tri& t = a->triangles[i]; float* o = &rec[(size_t)i * 12];
-            for (int k = 0; k < 3; k++) { o[k] = t.vertex0[k]; o[4 + k] = t.vertex1[k] - t.vertex0[k]; o[8 + k] = t.vertex2[k] - t.vertex0[k]; }
-            memcpy(&o[3], &i, 4); memcpy(&o[7], &t.objIdx, 4); o[11] = 0;
-        }
-        HIPCK(c, hipMemcpy(c->altTris, rec.data(), rec.size() * 4, hipMemcpyHostToDevice));
+        std::vector<crt::AltTri> rec(a->triCount);
+        for (uint32_t i = 0; i < a->triCount; i++) rec[i] = alt_tri(a->triangles[i], i);
+        HIPCK(c, hipMemcpy(c->altTris, rec.data(), rec.size() * sizeof(crt::AltTri), hipMemcpyHostToDevice));
         c->alt.tris = c->altTris;
     }
     if (slot == 0) {
-        if ((r = up(a->kdNodes, (size_t)a->kdNodeCount * 48, &c->alt.kdNodes))) return r;
-        const void* p = nullptr; if ((r = up(a->kdTriIndices, (size_t)a->kdTriIndexCount * 4, &p))) return r;
-        c->alt.kdRefs = (const uint32_t*)p; c->alt.kdStack = kdHeight + 1; c->haveKd = true;
+        if ((r = upload_array(c, allocs, a->kdNodes, (size_t)a->kdNodeCount * sizeof(crt::KdNode), &c->alt.kdNodes))) return r;
+        if ((r = upload_array(c, allocs, a->kdTriIndices, (size_t)a->kdTriIndexCount * 4, &c->alt.kdRefs))) return r;
+        c->alt.kdStack = kdHeight + 1; c->haveKd = true;
     } else {
         uint64_t cells = (uint64_t)a->gridResolution[0] * a->gridResolution[1] * a->gridResolution[2];
-        const void* p = nullptr;
-        if ((r = up(a->gridCellStart, (size_t)(cells + 1) * 4, &p))) return r; c->alt.cellStart = (const uint32_t*)p;
-        if ((r = up(a->gridCellTris, (size_t)a->gridCellTriCount * 4, &p))) return r; c->alt.cellRefs = (const int32_t*)p;
+        if ((r = upload_array(c, allocs, a->gridCellStart, (size_t)(cells + 1) * 4, &c->alt.cellStart))) return r;
+        if ((r = upload_array(c, allocs, a->gridCellTris, (size_t)a->gridCellTriCount * 4, &c->alt.cellRefs))) return r;
         for (int k = 0; k < 3; k++) { c->alt.res[k] = a->gridResolution[k]; c->alt.cell[k] = a->gridCellSize[k]; c->alt.lo[k] = a->gridMin[k]; c->alt.hi[k] = a->gridMax[k]; }
         c->haveGrid = true;
     }
@@ -1968,11 +1958,11 @@ int crt_upload_blas_accel(crt_ctx* c, int kind, const crt_alt_accel* blas, uint3
         nTris += a.triCount;
     }
     const uint32_t words = maxKd * 2u + (c->hScene.stackDepth - c->hScene.bvhStack);      // KD stack + TLAS entries + the return marker, per lane
-    if (words * 64u * 4u > 64u * 1024u) return c->fail(CRT_ERR_UNSUPPORTED, "TLAS + KD-tree traversal stack of %u dwords per lane exceeds the LDS budget", words);
+    if (!wave_stack_fits(words)) return c->fail(CRT_ERR_UNSUPPORTED, "TLAS + KD-tree traversal stack of %u dwords per lane exceeds the LDS budget", words);
     if (nNodes > 0xffffffffull || nRefs > 0xffffffffull || nTris > 0xffffffffull || nCells > 0xffffffffull || nCellRefs > 0xffffffffull) return c->fail(CRT_ERR_UNSUPPORTED, "BLAS set too large");
     // ---- flatten: concatenated arrays + one descriptor per BLAS ----
     std::vector<crt::BlasAltDesc> desc(blasCount);
-    std::vector<crt_kd_node> nodes; std::vector<uint32_t> refs, cellStart; std::vector<int32_t> cellRefs; std::vector<float> tris((size_t)nTris * 12);
+    std::vector<crt_kd_node> nodes; std::vector<uint32_t> refs, cellStart; std::vector<int32_t> cellRefs; std::vector<crt::AltTri> tris((size_t)nTris);
     uint32_t tb = 0;
     for (uint32_t b = 0; b < blasCount; b++) {
         const crt_alt_accel& a = blas[b];
@@ -1985,38 +1975,22 @@ int crt_upload_blas_accel(crt_ctx* c, int kind, const crt_alt_accel* blas, uint3
             cellStart.insert(cellStart.end(), a.gridCellStart, a.gridCellStart + cells + 1); cellRefs.insert(cellRefs.end(), a.gridCellTris, a.gridCellTris + a.gridCellTriCount);
             for (int k = 0; k < 3; k++) { d.res[k] = a.gridResolution[k]; d.cell[k] = a.gridCellSize[k]; d.lo[k] = a.gridMin[k]; d.hi[k] = a.gridMax[k]; }
         }
-        for (uint32_t i = 0; i < a.triCount; i++) {                      // AltTri: Möller–Trumbore operands, triIdx = the global shade index (shadeBase + BLAS-local index)
-            const crt_tri& t = a.triangles[i]; float* o = &tris[(size_t)(tb + i) * 12];
-            for (int k = 0; k < 3; k++) { o[k] = t.vertex0[k]; o[4 + k] = t.vertex1[k] - t.vertex0[k]; o[8 + k] = t.vertex2[k] - t.vertex0[k]; }
-            const uint32_t shade = inst[b].shadeBase + i; memcpy(&o[3], &shade, 4); memcpy(&o[7], &t.objIdx, 4); o[11] = 0;
-        }
+        for (uint32_t i = 0; i < a.triCount; i++) tris[(size_t)tb + i] = alt_tri(a.triangles[i], inst[b].shadeBase + i);
         tb += a.triCount;
     }
     // ---- replace the set of this kind (synchronous): queries and render launches that read the previous one finish first ----
     HIPCK(c, hipSetDevice(c->cfg.device));
-    for (auto st : c->streams) HIPCK(c, hipStreamSynchronize(st));
-    if (c->aheadStream) HIPCK(c, hipStreamSynchronize(c->aheadStream));
-    HIPCK(c, hipStreamSynchronize(c->stream));
-    { const int r = wait_queries(c); if (r) return r; }
+    { const int r = drain_all(c); if (r) return r; }
     // the new set goes into buffers of its own; only once every copy has succeeded does it replace the previous one (a failed allocation or copy keeps that)
     std::vector<void*> allocs;
     crt::TlasAltDev tl{};
-    auto up = [&](const void* src, size_t bytes, const void** out) -> int {
-        *out = nullptr; if (!bytes) return 0;
-        void* d = nullptr; HIPCK(c, hipMalloc(&d, bytes)); allocs.push_back(d);
-        HIPCK(c, hipMemcpy(d, src, bytes, hipMemcpyHostToDevice)); *out = d; return 0;
-    };
-    auto flatten = [&]() -> int {
-        const void* p = nullptr; int r;
-        if ((r = up(desc.data(), desc.size() * sizeof(crt::BlasAltDesc), &p))) return r; tl.desc = (const crt::BlasAltDesc*)p;
-        if ((r = up(tris.data(), tris.size() * 4, &tl.tris))) return r;
-        if ((r = up(nodes.data(), nodes.size() * sizeof(crt_kd_node), &tl.kdNodes))) return r;
-        if ((r = up(refs.data(), refs.size() * 4, &p))) return r; tl.kdRefs = (const uint32_t*)p;
-        if ((r = up(cellStart.data(), cellStart.size() * 4, &p))) return r; tl.cellStart = (const uint32_t*)p;
-        if ((r = up(cellRefs.data(), cellRefs.size() * 4, &p))) return r; tl.cellRefs = (const int32_t*)p;
-        return 0;
-    };
-    if (const int r = flatten()) { for (void* p : allocs) (void)hipFree(p); return r; }
+    int r;
+    if ((r = upload_array(c, allocs, desc.data(), desc.size() * sizeof(crt::BlasAltDesc), &tl.desc)) || (r = upload_array(c, allocs, tris.data(), tris.size() * sizeof(crt::AltTri), &tl.tris)) ||
+        (r = upload_array(c, allocs, nodes.data(), nodes.size() * sizeof(crt_kd_node), &tl.kdNodes)) || (r = upload_array(c, allocs, refs.data(), refs.size() * 4, &tl.kdRefs)) ||
+        (r = upload_array(c, allocs, cellStart.data(), cellStart.size() * 4, &tl.cellStart)) || (r = upload_array(c, allocs, cellRefs.data(), cellRefs.size() * 4, &tl.cellRefs))) {
+        for (void* p : allocs) (void)hipFree(p);
+        return r;
+    }
     tl.kdStack = maxKd;
     const int slot = kind - 1;
     c->epoch++;
@@ -2035,10 +2009,7 @@ int crt_upload_primitive_scene(crt_ctx* c, const crt_primitive_scene* ps)
     HIPCK(c, hipSetDevice(c->cfg.device));
     for (const crt_texture* t : {&ps->red, &ps->blue})
         if (t->pixels && (t->width != 512 || t->height != 512)) return c->fail(CRT_ERR_INVALID, "PrimitiveScene wall images are 512 x 512 (Plane::GetAlbedo masks the texel coordinates with 511)");
-    for (auto st : c->streams) HIPCK(c, hipStreamSynchronize(st));
-    if (c->aheadStream) HIPCK(c, hipStreamSynchronize(c->aheadStream));
-    HIPCK(c, hipStreamSynchronize(c->stream));
-    { const int r = wait_queries(c); if (r) return r; }
+    { const int r = drain_all(c); if (r) return r; }
     c->freeScene();
     crt::PrimDev& p = c->prim; p = crt::PrimDev{};
     memcpy(p.quadInvT, ps->quadInvT, 48); p.quadNrm[0] = -ps->quadT[1]; p.quadNrm[1] = -ps->quadT[5]; p.quadNrm[2] = -ps->quadT[9]; p.quadSize = ps->quadSize;   // Quad::GetNormal, primitives.h:363-367
@@ -2056,25 +2027,30 @@ int crt_upload_primitive_scene(crt_ctx* c, const crt_primitive_scene* ps)
     return CRT_OK;
 }
 
+// the sequential Sample kernels' LDS columns (render_seq_kernel, sample_query_kernel: device/seq_sample.h seq_lds_bytes).  Dwords of traversal stack per lane when Sample traces
+// through `accel`: 0 = the scene's BVH / TLAS (none for the PrimitiveScene), else the uploaded KD-tree / grid
+static uint32_t sample_stack_words(const crt_ctx* c, int accel)
+{
+    if (c->havePrim) return 0u;
+    if (accel == 0) return c->hScene.stackDepth;
+    if (c->hScene.kind == CRT_SCENE_TLAS) return c->blasAlt[accel - 1].kdStack * 2u + (c->hScene.stackDepth - c->hScene.bvhStack);
+    return accel == CRT_ACCEL_KDTREE ? c->alt.kdStack * 2u : 0u;
+}
+// the stack + 15 throughput factors per lane, four wavefronts per workgroup, within a workgroup's 64 KiB
+static bool sample_lds_fits(uint32_t words) { return ((uint64_t)words + 15u) * 64u * 4u * 4u <= 64u * 1024u; }
+
 int crt_set_render_accel(crt_ctx* c, int kind)
 {
     if (!c) return CRT_ERR_INVALID;
     if (kind != 0 && kind != CRT_ACCEL_KDTREE && kind != CRT_ACCEL_GRID) return c->fail(CRT_ERR_INVALID, "crt_set_render_accel: unknown accelerator kind %d", kind);
     if (kind != 0 && !c->hasAlt(kind)) return c->fail(CRT_ERR_STATE, "crt_set_render_accel: no such accelerator uploaded (kind %d)", kind);
     if (kind != 0 && c->hScene.kind == CRT_SCENE_TLAS) {
-        const uint32_t words = c->blasAlt[kind - 1].kdStack * 2u + (c->hScene.stackDepth - c->hScene.bvhStack);
-        if ((words + 15u) * 64u * 4u * 4u > 64u * 1024u) return c->fail(CRT_ERR_UNSUPPORTED, "TLAS + KD-tree stack of %u dwords exceeds the render kernel's LDS stack", words);
-    } else if (kind != 0 && (c->alt.kdStack * 2u + 15u) * 64u * 4u * 4u > 64u * 1024u) return c->fail(CRT_ERR_UNSUPPORTED, "KD-tree height %u exceeds the render kernel's LDS stack", c->alt.kdStack);
+        const uint32_t words = sample_stack_words(c, kind);
+        if (!sample_lds_fits(words)) return c->fail(CRT_ERR_UNSUPPORTED, "TLAS + KD-tree stack of %u dwords exceeds the render kernel's LDS stack", words);
+    } else if (kind != 0 && !sample_lds_fits(sample_stack_words(c, CRT_ACCEL_KDTREE)))        // a FileScene's grid is held to its KD-tree's stack too, as it always was
+        return c->fail(CRT_ERR_UNSUPPORTED, "KD-tree height %u exceeds the render kernel's LDS stack", c->alt.kdStack);
     c->renderAccel = kind; c->epoch++;
     return CRT_OK;
-}
-
-// FindNearest / IsOccluded through an alternative accelerator: FileScene's structure, or a two-level scene's BLAS set
-static hipError_t launch_alt_query(crt_ctx* c, int kind, bool occl, const void* rays, void* out, uint32_t n, uint32_t* cursor, hipStream_t st)
-{
-    if (c->hScene.kind == CRT_SCENE_TLAS) return crt_launch_tlas_alt_query(kind, occl, &c->hScene, &c->blasAlt[kind - 1], rays, out, n, cursor, st);
-    if (occl) return crt_launch_is_occluded_alt(kind, &c->hScene, &c->alt, rays, static_cast<int32_t*>(out), n, cursor, st);
-    return crt_launch_find_nearest_alt(kind, &c->hScene, &c->alt, rays, out, n, cursor, st);
 }
 
 int crt_find_nearest_alt(crt_ctx* c, int kind, const crt_ray* rays, crt_hit* hits, size_t n)
@@ -2083,21 +2059,7 @@ int crt_find_nearest_alt(crt_ctx* c, int kind, const crt_ray* rays, crt_hit* hit
     if (!c->hasAlt(kind)) return c->fail(CRT_ERR_STATE, "crt_find_nearest_alt: no such accelerator uploaded (kind %d)", kind);
     if (n == 0) return CRT_OK;
     if (n > 0x7fffffffull) return c->fail(CRT_ERR_UNSUPPORTED, "at most 2^31-1 rays per call");
-    HIPCK(c, hipSetDevice(c->cfg.device));
-    if (n > c->queryCap) {
-        HIPCK(c, hipStreamSynchronize(c->stream));
-        if (c->dQueryRays) (void)hipFree(c->dQueryRays);
-        if (c->dQueryHits) (void)hipFree(c->dQueryHits);
-        c->dQueryRays = c->dQueryHits = nullptr; c->queryCap = 0;
-        HIPCK(c, hipMalloc(&c->dQueryRays, n * sizeof(crt_ray)));
-        HIPCK(c, hipMalloc(&c->dQueryHits, n * sizeof(crt_hit)));
-        c->queryCap = n;
-    }
-    HIPCK(c, hipMemcpyAsync(c->dQueryRays, rays, n * sizeof(crt_ray), hipMemcpyHostToDevice, c->stream));
-    HIPCK(c, launch_alt_query(c, kind, false, c->dQueryRays, c->dQueryHits, (uint32_t)n, c->dQueryCursor, c->stream));
-    HIPCK(c, hipMemcpyAsync(hits, c->dQueryHits, n * sizeof(crt_hit), hipMemcpyDeviceToHost, c->stream));
-    HIPCK(c, hipStreamSynchronize(c->stream));
-    return CRT_OK;
+    return query_host(c, false, kind, rays, hits, n);
 }
 
 // ---- scene queries: IsOccluded on host buffers, FindNearest / IsOccluded on device buffers (crt_abi.h "scene queries") ----
@@ -2195,17 +2157,7 @@ static int query_device(crt_ctx* c, bool occl, int accel, const void* dRays, voi
     hipStream_t st = nullptr; int k = 0;
     if ((r = begin_device_query(c, stream, what, &st, &k))) return r;
     if (accel != 0 && c->altReady) HIPCK(c, hipStreamWaitEvent(st, c->altReady, 0));     // the accelerators' copies ran on the null stream
-    uint32_t* cursor = c->dQuerySlots + 16 * k;
-    if (occl) {
-        if (accel == 0) HIPCK(c, crt_launch_is_occluded(&c->hScene, dRays, static_cast<int32_t*>(dOut), (uint32_t)n, c->ldsBytes, cursor, st));
-        else HIPCK(c, launch_alt_query(c, accel, true, dRays, dOut, (uint32_t)n, cursor, st));
-    } else if (accel != 0) {
-        HIPCK(c, launch_alt_query(c, accel, false, dRays, dOut, (uint32_t)n, cursor, st));
-    } else if (c->havePrim) {
-        HIPCK(c, crt_launch_find_nearest_prim(&c->prim, dRays, dOut, (uint32_t)n, st));
-    } else {
-        HIPCK(c, crt_launch_find_nearest(&c->hScene, dRays, dOut, (uint32_t)n, c->dCounters, c->ldsBytes, cursor, st));
-    }
+    HIPCK(c, launch_query(c, occl, accel, dRays, dOut, (uint32_t)n, c->dQuerySlots + 16 * k, st));
     return end_device_query(c, k, st);
 }
 
@@ -2319,23 +2271,7 @@ int crt_is_occluded(crt_ctx* c, int accel, const crt_shadow_ray* rays, int32_t* 
     if ((r = query_check(c, accel, true, n, "crt_is_occluded"))) return r;
     if (n == 0) return CRT_OK;
     if (!rays || !occluded) return c->fail(CRT_ERR_INVALID, "crt_is_occluded: NULL buffer");
-    HIPCK(c, hipSetDevice(c->cfg.device));
-    if (n > c->queryCap) {                                                // the staging buffers of crt_find_nearest (a shadow ray is as large as a ray)
-        HIPCK(c, hipStreamSynchronize(c->stream));
-        if (c->dQueryRays) (void)hipFree(c->dQueryRays);
-        if (c->dQueryHits) (void)hipFree(c->dQueryHits);
-        c->dQueryRays = c->dQueryHits = nullptr; c->queryCap = 0;
-        HIPCK(c, hipMalloc(&c->dQueryRays, n * sizeof(crt_ray)));
-        HIPCK(c, hipMalloc(&c->dQueryHits, n * sizeof(crt_hit)));
-        c->queryCap = n;
-    }
-    HIPCK(c, hipMemcpyAsync(c->dQueryRays, rays, n * sizeof(crt_shadow_ray), hipMemcpyHostToDevice, c->stream));
-    int32_t* dOut = static_cast<int32_t*>(c->dQueryHits);
-    if (accel == 0) HIPCK(c, crt_launch_is_occluded(&c->hScene, c->dQueryRays, dOut, (uint32_t)n, c->ldsBytes, c->dQueryCursor, c->stream));
-    else HIPCK(c, launch_alt_query(c, accel, true, c->dQueryRays, dOut, (uint32_t)n, c->dQueryCursor, c->stream));
-    HIPCK(c, hipMemcpyAsync(occluded, dOut, n * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    HIPCK(c, hipStreamSynchronize(c->stream));
-    return CRT_OK;
+    return query_host(c, true, accel, rays, occluded, n);
 }
 
 // ---- shading queries: GetHitInfo + GetAlbedo, GetSkyColor, GetLightPos / GetLightColor (crt_abi.h "scene queries") ----
@@ -2348,18 +2284,6 @@ static int shade_check(crt_ctx* c, bool hitInfo, size_t n, const char* what)
 
 // hit_record_ok's bounds for the uploaded scene
 static uint32_t file_tri_count(const crt_ctx* c) { return c->flat.kind == CRT_SCENE_FILE ? c->flat.triCount[0] : 0u; }
-
-// the host entries' device staging, grown to the high-water mark (hipMalloc'ed: 16-byte aligned)
-static int shade_stage(crt_ctx* c, size_t bytes)
-{
-    if (bytes <= c->shadeStageBytes) return 0;
-    HIPCK(c, hipStreamSynchronize(c->stream));
-    if (c->dShadeStage) (void)hipFree(c->dShadeStage);
-    c->dShadeStage = nullptr; c->shadeStageBytes = 0;
-    HIPCK(c, hipMalloc(&c->dShadeStage, bytes));
-    c->shadeStageBytes = bytes;
-    return 0;
-}
 
 int crt_get_hit_info(crt_ctx* c, const crt_ray* rays, const crt_hit* hits, crt_hit_info* out, size_t n)
 {
@@ -2374,8 +2298,8 @@ int crt_get_hit_info(crt_ctx* c, const crt_ray* rays, const crt_hit* hits, crt_h
         if (!crt::hit_record_ok(hits[i].objIdx, hits[i].triIdx, f.objects, [&](uint32_t k) { return f.triCount[f.kind == CRT_SCENE_TLAS ? k : 0]; }))
             return c->fail(CRT_ERR_INVALID, "crt_get_hit_info: record %zu names objIdx %d, triIdx %d; the scene has objects -1 .. %u and that object's BVH fewer triangles", i, hits[i].objIdx, hits[i].triIdx, f.objects + 1);
     HIPCK(c, hipSetDevice(c->cfg.device));
-    if ((r = shade_stage(c, n * (sizeof(crt_hit_info) + sizeof(crt_ray) + sizeof(crt_hit))))) return r;
-    char* dOut = static_cast<char*>(c->dShadeStage); char* dRays = dOut + n * sizeof(crt_hit_info); char* dHits = dRays + n * sizeof(crt_ray);
+    if ((r = stage(c, n * (sizeof(crt_hit_info) + sizeof(crt_ray) + sizeof(crt_hit))))) return r;
+    char* dOut = c->dStage; char* dRays = dOut + n * sizeof(crt_hit_info); char* dHits = dRays + n * sizeof(crt_ray);
     HIPCK(c, hipMemcpyAsync(dRays, rays, n * sizeof(crt_ray), hipMemcpyHostToDevice, c->stream));
     HIPCK(c, hipMemcpyAsync(dHits, hits, n * sizeof(crt_hit), hipMemcpyHostToDevice, c->stream));
     HIPCK(c, crt_launch_hit_info(&c->hScene, dRays, dHits, dOut, (uint32_t)n, f.objects, file_tri_count(c), c->stream));
@@ -2410,8 +2334,8 @@ int crt_get_sky_color(crt_ctx* c, const crt_ray* rays, float* rgb, size_t n)
     if (!rays || !rgb) return c->fail(CRT_ERR_INVALID, "crt_get_sky_color: NULL buffer");
     if (c->havePrim) { memset(rgb, 0, n * 12); return CRT_OK; }                // PrimitiveScene::GetSkyColor
     HIPCK(c, hipSetDevice(c->cfg.device));
-    if ((r = shade_stage(c, n * (12 + sizeof(crt_ray))))) return r;
-    float* dOut = static_cast<float*>(c->dShadeStage); char* dRays = static_cast<char*>(c->dShadeStage) + n * 12;
+    if ((r = stage(c, n * (12 + sizeof(crt_ray))))) return r;
+    float* dOut = reinterpret_cast<float*>(c->dStage); char* dRays = c->dStage + n * 12;
     HIPCK(c, hipMemcpyAsync(dRays, rays, n * sizeof(crt_ray), hipMemcpyHostToDevice, c->stream));
     HIPCK(c, crt_launch_sky_color(&c->hScene, dRays, dOut, (uint32_t)n, c->stream));
     HIPCK(c, hipMemcpyAsync(rgb, dOut, n * 12, hipMemcpyDeviceToHost, c->stream));
@@ -2441,12 +2365,8 @@ static int sample_check(crt_ctx* c, int accel, size_t n, const char* what)
 {
     int r;
     if ((r = query_check(c, accel, false, n, what))) return r;
-    uint32_t words = 0;
-    if (c->havePrim) words = 0;
-    else if (accel == 0) words = c->hScene.stackDepth;
-    else if (c->hScene.kind == CRT_SCENE_TLAS) words = c->blasAlt[accel - 1].kdStack * 2u + (c->hScene.stackDepth - c->hScene.bvhStack);
-    else if (accel == CRT_ACCEL_KDTREE) words = c->alt.kdStack * 2u;
-    if (((uint64_t)words + 15u) * 64u * 4u * 4u > 64u * 1024u) return c->fail(CRT_ERR_UNSUPPORTED, "%s: a traversal stack of %u dwords per lane exceeds the kernel's LDS", what, words);
+    const uint32_t words = sample_stack_words(c, accel);
+    if (!sample_lds_fits(words)) return c->fail(CRT_ERR_UNSUPPORTED, "%s: a traversal stack of %u dwords per lane exceeds the kernel's LDS", what, words);
     return 0;
 }
 
@@ -2464,8 +2384,8 @@ int crt_sample(crt_ctx* c, int accel, const crt_ray* rays, uint32_t* seeds, floa
     if (n == 0) return CRT_OK;
     if (!rays || !seeds || !rgb) return c->fail(CRT_ERR_INVALID, "crt_sample: NULL buffer");
     HIPCK(c, hipSetDevice(c->cfg.device));
-    if ((r = shade_stage(c, n * (12 + sizeof(crt_ray) + 4)))) return r;
-    float* dRgb = static_cast<float*>(c->dShadeStage); char* dRays = static_cast<char*>(c->dShadeStage) + n * 12; uint32_t* dSeeds = reinterpret_cast<uint32_t*>(dRays + n * sizeof(crt_ray));
+    if ((r = stage(c, n * (12 + sizeof(crt_ray) + 4)))) return r;
+    float* dRgb = reinterpret_cast<float*>(c->dStage); char* dRays = c->dStage + n * 12; uint32_t* dSeeds = reinterpret_cast<uint32_t*>(dRays + n * sizeof(crt_ray));
     HIPCK(c, hipMemcpyAsync(dRays, rays, n * sizeof(crt_ray), hipMemcpyHostToDevice, c->stream));
     HIPCK(c, hipMemcpyAsync(dSeeds, seeds, n * 4, hipMemcpyHostToDevice, c->stream));
     HIPCK(c, launch_sample(c, accel, dRays, dSeeds, dRgb, (uint32_t)n, c->dQueryCursor, nullptr, c->stream));

@@ -12,6 +12,7 @@
 // Per ray nothing changes: the same nodes, cells and triangles in the same order with the same arithmetic (the result records are compared bit for bit with the real
 // kdtree.cpp / grid.cpp, tests/golden/ref_alt_rays.npz).
 #include "alt_common.h"
+#include "launch.h"
 
 namespace crt {
 
@@ -277,20 +278,11 @@ __global__ __launch_bounds__(64) void is_occluded_alt_kernel(const Scene sc, con
 
 } // namespace crt
 
-// wavefronts of a persistent query launch: enough to fill the device several times over (they hide each other's fetch latency), never more than the rays need
-static uint32_t query_waves(uint32_t n, uint32_t ldsBytes)
-{
-    uint32_t perCu = ldsBytes ? (160u * 1024u) / ldsBytes : 16u; if (perCu > 16u) perCu = 16u; if (perCu < 4u) perCu = 4u;      // 4 wavefronts per SIMD, LDS stacks permitting (measured: 8 per SIMD is no faster for the grid and 17 % slower for the BVH)
-    const uint32_t need = (n + 63u) / 64u, fill = 256u * perCu; return crt::bounded_query_grid(need < fill ? need : fill);
-}
-
 extern "C" hipError_t crt_launch_find_nearest_alt(int kind, const crt::Scene* sc, const crt::AltAccelDev* acc, const void* rays, void* hits, uint32_t n, uint32_t* cursor, hipStream_t stream)
 {
-    if (n == 0) return hipSuccess;
-    if (!cursor) return hipErrorInvalidValue;
-    if (hipMemsetAsync(cursor, 0, 4, stream) != hipSuccess) return hipGetLastError();
+    hipError_t e; if (!crt::query_launch_begin(n, cursor, stream, &e)) return e;       // no rays: nothing to do; the cursor zeroed on the stream (launch.h)
     const uint32_t ldsBytes = kind == 1 ? acc->kdStack * 128u * 4u : 0u;
-    dim3 grid(query_waves(n, ldsBytes)), block(64);
+    dim3 grid(crt::query_grid(n, ldsBytes)), block(64);
     if (kind == 1) hipLaunchKernelGGL(crt::find_nearest_alt_kernel<1>, grid, block, ldsBytes, stream, *sc, *acc, (const crt::RayIn*)rays, (crt::HitOut*)hits, n, cursor);
     else hipLaunchKernelGGL(crt::find_nearest_alt_kernel<2>, grid, block, 0, stream, *sc, *acc, (const crt::RayIn*)rays, (crt::HitOut*)hits, n, cursor);
     return hipGetLastError();
@@ -298,11 +290,9 @@ extern "C" hipError_t crt_launch_find_nearest_alt(int kind, const crt::Scene* sc
 
 extern "C" hipError_t crt_launch_is_occluded_alt(int kind, const crt::Scene* sc, const crt::AltAccelDev* acc, const void* rays, int32_t* occluded, uint32_t n, uint32_t* cursor, hipStream_t stream)
 {
-    if (n == 0) return hipSuccess;
-    if (!cursor) return hipErrorInvalidValue;
-    if (hipMemsetAsync(cursor, 0, 4, stream) != hipSuccess) return hipGetLastError();
+    hipError_t e; if (!crt::query_launch_begin(n, cursor, stream, &e)) return e;       // no rays: nothing to do; the cursor zeroed on the stream (launch.h)
     const uint32_t ldsBytes = kind == 1 ? acc->kdStack * 128u * 4u : 0u;
-    dim3 grid(query_waves(n, ldsBytes)), block(64);
+    dim3 grid(crt::query_grid(n, ldsBytes)), block(64);
     if (kind == 1) hipLaunchKernelGGL(crt::is_occluded_alt_kernel<1>, grid, block, ldsBytes, stream, *sc, *acc, (const crt::ShadowRayIn*)rays, occluded, n, cursor);
     else hipLaunchKernelGGL(crt::is_occluded_alt_kernel<2>, grid, block, 0, stream, *sc, *acc, (const crt::ShadowRayIn*)rays, occluded, n, cursor);
     return hipGetLastError();

@@ -4,18 +4,11 @@
 //   grid_intersect   Grid::Intersect     (infra/grid.cpp:89-161, 3D-DDA)
 // Both report Ray::traversed / Ray::tested as the reference counts them.  Numerics as everywhere: -ffp-contract=off, IEEE + - * / only, std::min / std::max operand
 // order; the two `double` comparisons of the KD traversal (`t < tmin + 0.001` mixes a float with a double literal) are evaluated in double like the reference.
+// The records these walks read (KdNode, AltTri) and the structs the kernels take by value (AltAccelDev, TlasAltDev) are layout.h's: the host fills the same types.
 #pragma once
 #include "dev_common.h"
 
 namespace crt {
-
-struct KdNode { float lo[3]; int32_t left; float hi[3]; int32_t right; float splitDistance; int32_t splitAxis; uint32_t firstTri, triCount; };   // = crt_kd_node, 48 B; left < 0: leaf
-struct AltTri { float v0[3]; uint32_t triIdx; float e1[3]; int32_t objIdx; float e2[3]; uint32_t pad; };                                          // Möller–Trumbore operands, reference triangle order
-struct AltAccelDev {
-    const KdNode* kdNodes; const uint32_t* kdRefs; uint32_t kdStack;         // kdStack: entries per lane (tree height + 1)
-    const AltTri* tris;
-    int32_t res[3]; float cell[3]; float lo[3], hi[3]; const uint32_t* cellStart; const int32_t* cellRefs;
-};
 
 // IntersectAABB of kdtree.cpp:109-120 / grid.cpp:52-61: the slab test that also hands tmin / tmax out
 __device__ __forceinline__ bool alt_box(const float* lo, const float* hi, f3 O, f3 rD, float tray, float& tminOut, float& tmaxOut)

@@ -24,6 +24,7 @@
 // CPU evaluation of the same expressions.  min/max follow the reference's std::min/std::max operand order.
 // No MFMA: the path is pointer chasing + slab / Möller–Trumbore tests.
 #include "alt_common.h"
+#include "launch.h"
 
 namespace crt {
 
@@ -1277,24 +1278,16 @@ extern "C" hipError_t crt_launch_accumulate(const void* slab, void* acc, uint32_
 extern "C" hipError_t crt_launch_find_nearest(const crt::Scene* sc, const void* rays, void* hits, uint32_t n, crt::Counters* counters,
                                               uint32_t ldsBytes, uint32_t* cursor, hipStream_t stream)
 {
-    if (n == 0) return hipSuccess;
-    if (!cursor) return hipErrorInvalidValue;
-    if (hipMemsetAsync(cursor, 0, 4, stream) != hipSuccess) return hipGetLastError();
-    uint32_t perCu = ldsBytes ? (160u * 1024u) / ldsBytes : 16u; if (perCu > 16u) perCu = 16u; if (perCu < 4u) perCu = 4u;      // 4 wavefronts per SIMD, LDS stacks permitting (measured: 8 per SIMD is no faster for the grid and 17 % slower for the BVH)
-    const uint32_t need = (n + 63u) / 64u, fill = 256u * perCu;          // persistent wavefronts: the device full once, never more than the rays need
-    dim3 grid(crt::bounded_query_grid(need < fill ? need : fill)), block(64);
+    hipError_t e; if (!crt::query_launch_begin(n, cursor, stream, &e)) return e;       // no rays: nothing to do; the cursor zeroed on the stream (launch.h)
+    dim3 grid(crt::query_grid(n, ldsBytes)), block(64);                 // persistent wavefronts (launch.h)
     hipLaunchKernelGGL(crt::find_nearest_kernel, grid, block, ldsBytes, stream, *sc, (const crt::RayIn*)rays, (crt::HitOut*)hits, n, counters, cursor);
     return hipGetLastError();
 }
 
 extern "C" hipError_t crt_launch_is_occluded(const crt::Scene* sc, const void* rays, int32_t* occluded, uint32_t n, uint32_t ldsBytes, uint32_t* cursor, hipStream_t stream)
 {
-    if (n == 0) return hipSuccess;
-    if (!cursor) return hipErrorInvalidValue;
-    if (hipMemsetAsync(cursor, 0, 4, stream) != hipSuccess) return hipGetLastError();
-    uint32_t perCu = ldsBytes ? (160u * 1024u) / ldsBytes : 16u; if (perCu > 16u) perCu = 16u; if (perCu < 4u) perCu = 4u;      // as crt_launch_find_nearest
-    const uint32_t need = (n + 63u) / 64u, fill = 256u * perCu;
-    dim3 grid(crt::bounded_query_grid(need < fill ? need : fill)), block(64);
+    hipError_t e; if (!crt::query_launch_begin(n, cursor, stream, &e)) return e;       // no rays: nothing to do; the cursor zeroed on the stream (launch.h)
+    dim3 grid(crt::query_grid(n, ldsBytes)), block(64);
     hipLaunchKernelGGL(crt::is_occluded_kernel, grid, block, ldsBytes, stream, *sc, (const crt::ShadowRayIn*)rays, occluded, n, cursor);
     return hipGetLastError();
 }

@@ -1,0 +1,100 @@
+// launch.h — the seam between the host (abi.cpp) and the device units (device/*.hip): every extern "C" launch wrapper and sizing helper a .hip file defines and
+// abi.cpp calls, declared ONCE.  abi.cpp includes this header and so does every .hip file that defines one of these functions, so a definition that drifts from
+// its declaration is a compile error ("conflicting types") instead of a transposed argument at run time; extern "C" symbols carry no types for the linker to check.
+// Host-includable: no device code.  The by-value kernel argument structs (Scene, AltAccelDev, TlasAltDev, PrimDev) are layout.h's.
+#pragma once
+#include "layout.h"
+
+#include <hip/hip_runtime.h>
+
+extern "C" {
+
+// ---- kernels.hip ----
+hipError_t crt_launch_check_reciprocals(unsigned long long* out, hipStream_t stream);
+hipError_t crt_launch_render(const crt::Scene* sc, void* slab, crt::Counters* counters, unsigned long long* tileClocks, const uint32_t* tileOrder, uint32_t tileFirst, uint32_t tileStride,
+    uint32_t tileCount, uint32_t tilesX, uint32_t sppFirst, uint32_t frames, uint32_t passes, uint32_t ldsBytes, int collectStats, const uint32_t* blockDesc, uint32_t nBlocks, uint32_t* tileCost,
+    uint32_t rankCount, unsigned long long* launchClk, hipStream_t stream);
+uint32_t crt_render_resident_waves(int device, int kind, uint32_t ldsBytes);
+hipError_t crt_launch_accumulate(const void* slab, void* acc, uint32_t tileFirst, uint32_t tileStride, uint32_t tileCount, uint32_t tilesX, uint32_t W, uint32_t frames, uint32_t passes,
+    hipStream_t stream);
+hipError_t crt_launch_find_nearest(const crt::Scene* sc, const void* rays, void* hits, uint32_t n, crt::Counters* counters, uint32_t ldsBytes, uint32_t* cursor, hipStream_t stream);
+hipError_t crt_launch_is_occluded(const crt::Scene* sc, const void* rays, int32_t* occluded, uint32_t n, uint32_t ldsBytes, uint32_t* cursor, hipStream_t stream);
+hipError_t crt_launch_whitted(const crt::Scene* sc, int accel, const crt::AltAccelDev* alt, const crt::TlasAltDev* tl, void* acc, uint32_t* pixels, crt::Counters* counters, uint32_t ldsBytes,
+    hipStream_t stream);
+size_t crt_whitted_inspect_work_bytes(uint32_t pixelCount);
+hipError_t crt_launch_whitted_inspect(const crt::Scene* sc, int accel, const crt::AltAccelDev* alt, const crt::TlasAltDev* tl, int inspect, int32_t peakIn, void* acc, uint32_t* pixels,
+    crt::Counters* counters, int32_t* trav, int32_t* tested, void* work, uint32_t ldsBytes, hipStream_t stream);
+hipError_t crt_launch_resolve(const void* acc, uint32_t* pixels, float* tileSums, uint32_t tileFirst, uint32_t tileStride, uint32_t tileCount, uint32_t tilesX, uint32_t W, float scale,
+    hipStream_t stream);
+hipError_t crt_launch_commit_frame(const void* slabWindow, uint32_t frameInWindow, uint32_t passes, void* acc, uint32_t* pixels, float* tileSums, uint32_t tileFirst, uint32_t tileStride,
+    uint32_t tileCount, uint32_t tilesX, uint32_t W, float scale, hipStream_t stream);
+
+// ---- render_pool.hip (the crt_debug_pool_* entries exist only in builds with CRT_POOL_STAMPS / _DENS / _TIMELINE; the tools look them up by name) ----
+uint32_t crt_pool_streams(uint32_t frames);
+size_t crt_pool_scratch_bytes_per_window(uint32_t tileCount);
+hipError_t crt_launch_render_pool(const crt::Scene* sc, void* slab, void* facScratch, crt::Counters* counters, unsigned long long* tileClocks, const uint32_t* tileOrder, uint32_t tileFirst,
+    uint32_t tileStride, uint32_t tileCount, uint32_t tilesX, uint32_t sppFirst, uint32_t frames, uint32_t passes, int collectStats, uint32_t rankFirst, uint32_t* tileCost,
+    unsigned long long* launchClk, hipStream_t stream);
+int crt_debug_pool_stamps(unsigned long long* out, int reset);
+int crt_debug_pool_density(unsigned long long* out, int reset);
+size_t crt_debug_pool_timeline(unsigned long long* out, size_t cap);
+
+// ---- render_seq.hip ----
+uint32_t crt_probe_paths(void);
+hipError_t crt_launch_probe(const crt::Scene* sc, uint32_t tileFirst, uint32_t tileStride, uint32_t tileCount, uint32_t tilesX, uint32_t* tileCost, hipStream_t stream);
+hipError_t crt_launch_render_alt(int accel, const crt::Scene* sc, const crt::AltAccelDev* acc, const crt::TlasAltDev* tl, void* slab, crt::Counters* counters, uint32_t tileFirst, uint32_t tileStride,
+    uint32_t tileCount, uint32_t tilesX, uint32_t sppFirst, uint32_t frames, uint32_t passes, hipStream_t stream);
+hipError_t crt_launch_sample_query(int accel, const crt::Scene* sc, const crt::AltAccelDev* acc, const crt::TlasAltDev* tl, const void* rays, uint32_t* seeds, float* rgb, uint32_t n,
+    crt::Counters* counters, uint32_t* cursor, uint32_t* residentLanes, hipStream_t stream);
+
+// ---- render_prim.hip ----
+hipError_t crt_launch_find_nearest_prim(const crt::PrimDev* p, const void* rays, void* hits, uint32_t n, hipStream_t stream);
+hipError_t crt_launch_render_prim(const crt::Scene* sc, const crt::PrimDev* p, void* slab, crt::Counters* counters, uint32_t tileFirst, uint32_t tileStride, uint32_t tileCount, uint32_t tilesX,
+    uint32_t sppFirst, uint32_t frames, uint32_t passes, hipStream_t stream);
+hipError_t crt_launch_sample_query_prim(const crt::Scene* sc, const crt::PrimDev* p, const void* rays, uint32_t* seeds, float* rgb, uint32_t n, crt::Counters* counters, uint32_t* cursor,
+    uint32_t* residentLanes, hipStream_t stream);
+hipError_t crt_launch_probe_f64(int op, const void* in, void* out, uint32_t n, hipStream_t stream);
+
+// ---- alt_accel.hip, tlas_alt.hip ----
+hipError_t crt_launch_find_nearest_alt(int kind, const crt::Scene* sc, const crt::AltAccelDev* acc, const void* rays, void* hits, uint32_t n, uint32_t* cursor, hipStream_t stream);
+hipError_t crt_launch_is_occluded_alt(int kind, const crt::Scene* sc, const crt::AltAccelDev* acc, const void* rays, int32_t* occluded, uint32_t n, uint32_t* cursor, hipStream_t stream);
+hipError_t crt_launch_tlas_alt_query(int kind, bool occl, const crt::Scene* sc, const crt::TlasAltDev* tl, const void* rays, void* out, uint32_t n, uint32_t* cursor, hipStream_t stream);
+
+// ---- shade_query.hip, refit.hip, probe.hip ----
+hipError_t crt_launch_hit_info(const crt::Scene* sc, const void* rays, const void* hits, void* out, uint32_t n, uint32_t objects, uint32_t fileTris, hipStream_t stream);
+hipError_t crt_launch_sky_color(const crt::Scene* sc, const void* rays, float* rgb, uint32_t n, hipStream_t stream);
+hipError_t crt_launch_refit(char* geom, uint32_t leafOff, uint32_t pairBase, uint32_t triBase, uint32_t triCount, const float* pos, const void* plan, const uint32_t* levelOff, uint32_t levels,
+    uint32_t rootCode, float* out, hipStream_t stream);
+hipError_t crt_launch_probe_f32(int op, const void* in, void* out, uint32_t n, hipStream_t stream);
+
+// abi.cpp's test switch CRT_DEBUG_QUERY_GRID=<k>: an upper bound on the workgroups of a persistent query launch (0: none).  Host side only: each wrapper passes its grid through it.
+uint32_t crt_debug_query_grid(void);
+
+} // extern "C"
+
+namespace crt {
+
+inline uint32_t bounded_query_grid(uint32_t grid) { const uint32_t k = crt_debug_query_grid(); return (k != 0u && k < grid) ? k : grid; }
+
+// ---- the launch geometry of the persistent find-nearest / is-occluded kernels (kernels.hip, alt_accel.hip, tlas_alt.hip), one wavefront per workgroup ----
+// Workgroups of a launch over n rays whose wavefronts take ldsBytes of LDS each: the device filled several times over (they hide each other's fetch latency), never more than the rays need.
+// 4 wavefronts per SIMD, LDS stacks permitting (measured: 8 per SIMD is no faster for the grid and 17 % slower for the BVH), on the MI355X's 256 CUs.
+inline uint32_t query_grid(uint32_t n, uint32_t ldsBytes)
+{
+    uint32_t perCu = ldsBytes ? (160u * 1024u) / ldsBytes : 16u; if (perCu > 16u) perCu = 16u; if (perCu < 4u) perCu = 4u;
+    const uint32_t need = (n + 63u) / 64u, fill = 256u * perCu;
+    return bounded_query_grid(need < fill ? need : fill);
+}
+
+// What the wrappers do before such a launch: nothing for no rays; the ray cursor the lanes draw from must exist and is zeroed on the stream, ahead of the kernel.
+// true: launch.  false: return *status (hipSuccess for n == 0).
+inline bool query_launch_begin(uint32_t n, uint32_t* cursor, hipStream_t stream, hipError_t* status)
+{
+    *status = hipSuccess;
+    if (n == 0) return false;
+    if (!cursor) { *status = hipErrorInvalidValue; return false; }
+    if (hipMemsetAsync(cursor, 0, 4, stream) != hipSuccess) { *status = hipGetLastError(); return false; }
+    return true;
+}
+
+} // namespace crt

@@ -1,4 +1,5 @@
-// layout.h — device-side (HBM) scene layout shared by the uploader (host) and the kernels.
+// layout.h — device-side (HBM) scene layout shared by the uploader (host) and the kernels: the records of the geometry buffer, and every struct handed to a kernel by value (Scene,
+// AltAccelDev, TlasAltDev, PrimDev), each defined HERE ONLY: the host that fills one and the kernel that reads it cannot disagree.  No device code; the launch wrappers are launch.h's.
 //
 // ONE geometry buffer holds every record the traversal touches, so a record address is `geom + 32-bit byte offset`
 // (scalar base register + per-lane offset: no 64-bit address arithmetic in the hot loop).  Records are sized and
@@ -124,8 +125,18 @@ CRT_HOST_DEVICE inline bool hit_record_ok(int32_t objIdx, int32_t triIdx, uint32
     return triIdx >= 0 && (uint32_t)triIdx < triCountOf((uint32_t)(objIdx - 2));
 }
 
+// FileScene's alternative acceleration structures (crt_upload_alt_accel; traversal in alt_common.h): the flat KD-tree's nodes, the triangle records both structures
+// index, and the view of one uploaded KD-tree + uniform grid that the kernels take by value
+struct KdNode { float lo[3]; int32_t left; float hi[3]; int32_t right; float splitDistance; int32_t splitAxis; uint32_t firstTri, triCount; };   // = crt_kd_node, 48 B; left < 0: leaf
+struct AltTri { float v0[3]; uint32_t triIdx; float e1[3]; int32_t objIdx; float e2[3]; uint32_t pad; };                                          // 48 B: Möller–Trumbore operands, reference triangle order
+struct AltAccelDev {
+    const KdNode* kdNodes; const uint32_t* kdRefs; uint32_t kdStack;         // kdStack: entries per lane (tree height + 1)
+    const AltTri* tris;
+    int32_t res[3]; float cell[3]; float lo[3], hi[3]; const uint32_t* cellStart; const int32_t* cellRefs;
+};
+
 // A two-level scene's set of BLASKDTree / BLASGrid structures (crt_upload_blas_accel): every BLAS's arrays are concatenated, a descriptor per BLAS
-// says where its part starts.  Triangle records are alt_common.h's AltTri (triIdx = the GLOBAL shade index, objIdx = the BLAS's), in each BLAS's order.
+// says where its part starts.  Triangle records are AltTri (triIdx = the GLOBAL shade index, objIdx = the BLAS's), in each BLAS's order.
 struct BlasAltDesc {                      // 72 B, indexed by the BLAS (= Instance) index
     uint32_t nodeBase, refBase, triBase;  // KD: first node, first leaf reference; first triangle record (references inside a BLAS are BLAS-local)
     uint32_t cellBase, cellRefBase;       // grid: first cellStart entry, first cell reference
@@ -139,11 +150,15 @@ struct TlasAltDev {                       // passed by value, like AltAccelDev
     uint32_t kdStack;                     // KD stack entries per lane: the deepest KD-tree's height + 1 (0 for a grid set)
 };
 
-} // namespace crt
+// PrimitiveScene at one animation time (crt_primitive_scene flattened by crt_upload_primitive_scene; kernels in render_prim.hip), passed to the kernels by value
+struct PrimDev {
+    float quadInvT[12], quadNrm[3], quadSize;
+    float spherePos[3], pad0;
+    float cubeInvM[12], cubeM[12], cubeMin[3], cubeMax[3];
+    float torusInvT[12], torusT[12], rt2, rc2, r2, pad1;
+    float refl[11], refr[11], absorb[33];
+    float pad2;
+    const uint32_t* red; const uint32_t* blue;     // 512 x 512 texels 0x00RRGGBB (the left / right wall's albedo override), may be null (black)
+};
 
-// CRT_DEBUG_QUERY_GRID=<k> (a test switch, abi.cpp; 0 when unset, or when the process has not enabled the switches): an upper bound on the workgroups of a
-// persistent query launch, so that a launch of a few thousand rays reuses every lane many times.  Host side only: each launch wrapper passes its grid through it.
-extern "C" uint32_t crt_debug_query_grid(void);
-namespace crt {
-inline uint32_t bounded_query_grid(uint32_t grid) { const uint32_t k = crt_debug_query_grid(); return (k != 0u && k < grid) ? k : grid; }
 } // namespace crt

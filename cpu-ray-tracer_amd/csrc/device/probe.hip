@@ -27,6 +27,7 @@
 //   15  DIV64     a, b (doubles)                                 4    a / b (double)                                                     2
 //   16  F64TOF32  x (double)                                     2    (float)x                                                           1
 #include "dev_common.h"
+#include "launch.h"
 
 namespace crt {
 

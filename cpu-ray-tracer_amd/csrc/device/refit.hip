@@ -11,9 +11,7 @@
 // positions — never from v0 + e1, which rounds), an interior node's box is min / max of its children, both as `a < b ? a : b` / `a > b ? a : b` in the
 // reference's operand order (tmplmath.h:122-123; fminf / fmaxf and the min / max instructions differ on NaN and on +-0), and NODE 1 IS SKIPPED
 // (bvh.cpp:28 `if (i != 1)`): the root's left child keeps the box it had, and that stale box still feeds node 0's.  -ffp-contract=off as everywhere.
-#include "layout.h"
-
-#include <hip/hip_runtime.h>
+#include "launch.h"
 
 namespace crt {
 

@@ -21,6 +21,7 @@
 //
 // Numerics: -ffp-contract=off, IEEE + - * / sqrt only (dev_common.h).  No MFMA: pointer chasing + slab / Möller–Trumbore tests.
 #include "dev_common.h"
+#include "launch.h"
 
 namespace crt {
 

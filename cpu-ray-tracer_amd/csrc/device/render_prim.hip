@@ -11,19 +11,10 @@
 // IEEE double + - * / sqrt), so oracle and kernel agree exactly; against a Windows build of the reference the torus' hit distances can differ in the last place.
 //
 // Numerics: -ffp-contract=off; fp32 as everywhere, fp64 only inside the torus test.  No MFMA.
+#include "launch.h"
 #include "sample_query.h"
 
 namespace crt {
-
-struct PrimDev {                          // the scene at one animation time (crt_primitive_scene flattened), passed to the kernels by value
-    float quadInvT[12], quadNrm[3], quadSize;
-    float spherePos[3], pad0;
-    float cubeInvM[12], cubeM[12], cubeMin[3], cubeMax[3];
-    float torusInvT[12], torusT[12], rt2, rc2, r2, pad1;
-    float refl[11], refr[11], absorb[33];
-    float pad2;
-    const uint32_t* red; const uint32_t* blue;     // 512 x 512 texels 0x00RRGGBB (the left / right wall's albedo override), may be null (black)
-};
 
 __device__ __forceinline__ uint32_t hi_word(double x) { return (uint32_t)__double2hiint(x); }
 __device__ __forceinline__ double with_words(uint32_t hi, uint32_t lo) { return __hiloint2double((int)hi, (int)lo); }

@@ -11,6 +11,7 @@
 // Numerics: -ffp-contract=off, IEEE + - * / sqrt only (dev_common.h).  No MFMA: pointer chasing + slab / Möller–Trumbore tests.
 #include "alt_common.h"
 #include "file_surface.h"
+#include "launch.h"
 #include "sample_query.h"
 
 namespace crt {

@@ -12,6 +12,7 @@
 //
 // Numerics: seq_sample.h's (-ffp-contract=off, IEEE + - * / sqrt, crt_expf / crt_atan2f / crt_acosf).  No MFMA.
 #pragma once
+#include "launch.h"
 #include "seq_sample.h"
 
 namespace crt {

@@ -8,6 +8,7 @@
 //
 // Numerics: -ffp-contract=off, IEEE + - * / sqrt only (dev_common.h).
 #include "file_surface.h"
+#include "launch.h"
 
 namespace crt {
 

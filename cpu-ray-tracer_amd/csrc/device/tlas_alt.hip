@@ -9,6 +9,7 @@
 // triangle test, return to the caller frame or DDA advance, return to the TLAS.  Per ray these are the steps of alt_common.h's tlas_alt_intersect (the render and
 // Whitted kernels' walk) in the same order with the same arithmetic: the same nodes, cells and triangles (tests/tlas_alt_restate.py, compared field for field).
 #include "alt_common.h"
+#include "launch.h"
 
 namespace crt {
 
@@ -205,22 +206,15 @@ __global__ __launch_bounds__(64) void tlas_alt_query_kernel(const Scene sc, cons
 
 } // namespace crt
 
-// wavefronts of a launch: the device filled several times over (LDS stacks permitting), never more than the rays need (as alt_accel.hip query_waves)
-static uint32_t tlas_query_waves(uint32_t n, uint32_t ldsBytes)
-{
-    uint32_t perCu = ldsBytes ? (160u * 1024u) / ldsBytes : 16u; if (perCu > 16u) perCu = 16u; if (perCu < 4u) perCu = 4u;
-    const uint32_t need = (n + 63u) / 64u, fill = 256u * perCu; return crt::bounded_query_grid(need < fill ? need : fill);
-}
-
 extern "C" hipError_t crt_launch_tlas_alt_query(int kind, bool occl, const crt::Scene* sc, const crt::TlasAltDev* tl, const void* rays, void* out, uint32_t n, uint32_t* cursor,
                                                 hipStream_t stream)
 {
     if (n == 0) return hipSuccess;
-    if (!cursor || sc->kind == 0 || (kind != 1 && kind != 2)) return hipErrorInvalidValue;
+    if (sc->kind == 0 || (kind != 1 && kind != 2)) return hipErrorInvalidValue;
     const uint32_t ldsBytes = crt::tlas_alt_stack_words(*sc, *tl) * 64u * 4u;
     if (ldsBytes > 64u * 1024u) return hipErrorInvalidValue;
-    if (hipMemsetAsync(cursor, 0, 4, stream) != hipSuccess) return hipGetLastError();
-    dim3 grid(tlas_query_waves(n, ldsBytes)), block(64);
+    hipError_t e; if (!crt::query_launch_begin(n, cursor, stream, &e)) return e;       // no rays: nothing to do; the cursor zeroed on the stream (launch.h)
+    dim3 grid(crt::query_grid(n, ldsBytes)), block(64);
     if (occl) {
         if (kind == 1) hipLaunchKernelGGL((crt::tlas_alt_query_kernel<1, true>), grid, block, ldsBytes, stream, *sc, *tl, rays, out, n, cursor);
         else hipLaunchKernelGGL((crt::tlas_alt_query_kernel<2, true>), grid, block, ldsBytes, stream, *sc, *tl, rays, out, n, cursor);

@@ -402,7 +402,49 @@ def test_refusals(crt, bunny_file):
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------------------
-# 6. one HIP runtime in the process (stream handles are only meaningful then)
+# 6. the host entries' device staging: one context serving entry after entry == a fresh context per call (agreement check)
+# ---------------------------------------------------------------------------------------------------------------------------------------------------
+def test_host_entries_in_sequence_equal_fresh_contexts(crt):
+    """The host-buffer entries stage their records in device memory that the context keeps and grows.  Seven calls on ONE context, whose record sizes and counts
+    differ (28-byte rays and hits, 48-byte hit infos, 4-byte flags and seeds, 12-byte colours; 63 / 64 / 65 rays = one wavefront less one, exact, plus one, and
+    130 = two plus two), each answer bit-equal to the same call on a context that has done nothing else; the last repeats the first."""
+    hs = crt.HostScene(scene_path("cube_scene.xml"), 0, ASSETS)
+    hs.build_alt(crt.ACCEL_KDTREE)
+
+    def context():
+        ctx = crt.Context(64, 64)
+        hs.upload(ctx); hs.upload_alt(ctx, crt.ACCEL_KDTREE)
+        return ctx
+
+    O, D = camera_rays(130, 5)
+    inside = (np.arange(130) % 5 == 3).astype(np.int32)
+    seeds = (np.arange(130, dtype=np.uint32) * np.uint32(2654435761) + np.uint32(12345)) | np.uint32(1)
+    tq = quad_occluded(O, D, np.full(130, 1e34, np.float32), LIGHT)[1]
+    calls = [
+        ("find_nearest 64", lambda c, first: c.find_nearest(O[:64], D[:64], inside[:64])),
+        ("get_hit_info 64", lambda c, first: c.get_hit_info(O[:64], D[:64], first)),
+        ("is_occluded 65", lambda c, first: c.is_occluded(O[:65], D[:65], pick_t(tq)[:65])),
+        ("sample 130", lambda c, first: np.concatenate([a.view(np.uint32).reshape(130, -1) for a in c.sample(O, D, seeds, inside)], axis=1)),
+        ("get_sky_color 63", lambda c, first: c.get_sky_color(D[:63])),
+        ("find_nearest_alt 65", lambda c, first: c.find_nearest_alt(crt.ACCEL_KDTREE, O[:65], D[:65])),
+        ("find_nearest 64 again", lambda c, first: c.find_nearest(O[:64], D[:64], inside[:64])),
+    ]
+    shared = context()
+    got = []
+    for what, call in calls:
+        got.append(call(shared, got[0] if got else None))
+        fresh = context()
+        want = call(fresh, got[0])
+        fresh.close()
+        assert got[-1].dtype == want.dtype and got[-1].shape == want.shape and got[-1].tobytes() == want.tobytes(), what
+    shared.close()
+    assert got[-1].tobytes() == got[0].tobytes()
+    obj = got[0]["objIdx"]
+    assert (obj >= 2).any() and (obj == 1).any() and (obj == -1).any()          # the rays see the cube, the floor and the sky: the records differ
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------------------
+# 7. one HIP runtime in the process (stream handles are only meaningful then)
 # ---------------------------------------------------------------------------------------------------------------------------------------------------
 def test_one_hip_runtime_is_loaded(crt):
     torch.cuda.init()
