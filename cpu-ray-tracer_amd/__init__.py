@@ -110,10 +110,10 @@ HIT_INFO_DTYPE = np.dtype([("I", "<f4", 3), ("material", "<i4"), ("N", "<f4", 3)
 MATERIAL_MISS, MATERIAL_INVALID = -1, -2       # crt_hit_info.material of a miss / of a record whose objIdx or triIdx the scene does not have
 
 # every symbol include/crt_abi.h and include/crt_host.h declare (tests check the library exports all of them)
-ABI_SYMBOLS = ["crt_sample", "crt_sample_device", "crt_refit_device", "crt_get_hit_info", "crt_get_hit_info_device", "crt_get_sky_color", "crt_get_sky_color_device", "crt_get_light", "crt_upload_blas_accel", "crt_is_occluded", "crt_find_nearest_device", "crt_is_occluded_device", "crt_upload_primitive_scene", "crt_set_render_accel", "crt_upload_alt_accel", "crt_find_nearest_alt", "crt_update_scene", "crt_abi_version", "crt_device_count", "crt_create", "crt_destroy", "crt_last_error", "crt_upload_scene", "crt_set_camera",
+ABI_SYMBOLS = ["crt_update_transforms_device", "crt_sample", "crt_sample_device", "crt_refit_device", "crt_get_hit_info", "crt_get_hit_info_device", "crt_get_sky_color", "crt_get_sky_color_device", "crt_get_light", "crt_upload_blas_accel", "crt_is_occluded", "crt_find_nearest_device", "crt_is_occluded_device", "crt_upload_primitive_scene", "crt_set_render_accel", "crt_upload_alt_accel", "crt_find_nearest_alt", "crt_update_scene", "crt_abi_version", "crt_device_count", "crt_create", "crt_destroy", "crt_last_error", "crt_upload_scene", "crt_set_camera",
                "crt_render", "crt_tick", "crt_reserve", "crt_whitted_tick", "crt_whitted_tick_inspect", "crt_sync", "crt_clear", "crt_read_accumulator", "crt_resolve_screen", "crt_find_nearest", "crt_get_counters",
                "crt_reset_counters", "crt_get_timing", "crt_get_tile_clocks", "crt_bind_accumulator", "crt_accumulator_device_ptr"]
-HOST_SYMBOLS = ["crt_host_scene_bvh_refit_device", "crt_host_scene_blas_alt_info", "crt_host_scene_blas_alt_copy", "crt_host_primitive_scene_create", "crt_host_primitive_scene_free", "crt_host_primitive_scene_set_time", "crt_host_primitive_scene_desc", "crt_host_primitive_scene_upload", "crt_host_scene_build_alt", "crt_host_scene_upload_alt", "crt_host_scene_alt_info", "crt_host_scene_alt_copy", "crt_host_scene_set_transform", "crt_host_scene_update", "crt_host_math_probe", "crt_host_vertex_dedup", "crt_host_last_error", "crt_host_scene_load", "crt_host_scene_free", "crt_host_scene_upload", "crt_host_scene_kind",
+HOST_SYMBOLS = ["crt_host_scene_update_transforms_device", "crt_host_scene_bvh_refit_device", "crt_host_scene_blas_alt_info", "crt_host_scene_blas_alt_copy", "crt_host_primitive_scene_create", "crt_host_primitive_scene_free", "crt_host_primitive_scene_set_time", "crt_host_primitive_scene_desc", "crt_host_primitive_scene_upload", "crt_host_scene_build_alt", "crt_host_scene_upload_alt", "crt_host_scene_alt_info", "crt_host_scene_alt_copy", "crt_host_scene_set_transform", "crt_host_scene_update", "crt_host_math_probe", "crt_host_vertex_dedup", "crt_host_last_error", "crt_host_scene_load", "crt_host_scene_free", "crt_host_scene_upload", "crt_host_scene_kind",
                 "crt_host_scene_triangle_count", "crt_host_scene_bvh_count", "crt_host_scene_bvh_info", "crt_host_scene_bvh_copy",
                 "crt_host_scene_bvh_move_and_refit", "crt_host_scene_blas_transform", "crt_host_scene_tlas_copy", "crt_host_camera_state", "crt_host_renderer_create",
                 "crt_host_renderer_destroy", "crt_host_renderer_init", "crt_host_renderer_set_camera", "crt_host_renderer_set_passes",
@@ -532,6 +532,26 @@ class Context:
             return np.array(box[:], np.float32).reshape(2, 3) if root_box else None
         return self._enqueue(stream, run)
 
+    def _transforms(self, T, what):
+        """the device pointer and instance count of a set of transforms: a contiguous float32 tensor [N, 16] or [N, 4, 4] (row-major mat4s) on the context's device"""
+        import torch
+        if not isinstance(T, torch.Tensor) or T.device != torch.device("cuda", self.device):
+            raise ValueError("%s: the transforms must be a torch tensor on cuda:%d" % (what, self.device))
+        if T.dtype != torch.float32 or not T.is_contiguous() or T.dim() < 2 or tuple(T.shape[1:]) not in ((16,), (4, 4)):
+            raise ValueError("%s: the transforms must be a contiguous float32 tensor of shape [N, 16] or [N, 4, 4]" % what)
+        return C.c_void_p(T.data_ptr()), C.c_uint32(T.shape[0])
+
+    def update_transforms_device(self, T, stream=None):
+        """crt_update_transforms_device: BLASBVH::SetTransform(T[i]) of every instance of a two-level scene + TLASBVH::Build on the GPU, from a tensor of row-major
+        mat4s ([N, 16] or [N, 4, 4], rigid), enqueued on `stream` (default torch.cuda.current_stream()); returns once the build has been read back.  Returns the
+        rebuilt TLASBVH::tlasNode array (TLAS_DTYPE, 2 N records)."""
+        def run(st):
+            ptr, n = self._transforms(T, "update_transforms_device")
+            nodes = np.zeros(2 * n.value, TLAS_DTYPE)
+            self._ck(self.L.crt_update_transforms_device(self.h, ptr, n, C.c_void_p(st.cuda_stream), _p(nodes)))
+            return nodes
+        return self._enqueue(stream, run)
+
     def _enqueue(self, stream, run):
         """run(st) on the torch stream `stream` (default: the current one).  Torch's default stream has the handle 0, which the ABI reads as the context's own
         stream: on it the query runs on a side stream that waits for it and that it waits for in turn (events, no host wait)."""
@@ -648,6 +668,16 @@ class HostScene:
         def run(st):
             ptr, n = ctx._positions(positions, "refit_device")
             self._ck(self.L.crt_host_scene_bvh_refit_device(self.h, ctx.h, int(i), ptr, n, C.c_void_p(st.cuda_stream)))
+        return ctx._enqueue(stream, run)
+
+    def set_transforms_device(self, ctx, T, stream=None):
+        """crt_host_scene_update_transforms_device: every instance's transform from a tensor on the GPU (Context.update_transforms_device's), the TLAS rebuilt there;
+        the host scene's T, invT, world bounds and TLAS follow (blas_transform(i), tlas()), so no update(ctx, UPDATE_TRANSFORMS) is needed."""
+        def run(st):
+            ptr, n = ctx._transforms(T, "set_transforms_device")
+            if n.value != self.bvh_count():
+                raise ValueError("set_transforms_device: %d transforms for %d instances" % (n.value, self.bvh_count()))
+            self._ck(self.L.crt_host_scene_update_transforms_device(self.h, ctx.h, ptr, C.c_void_p(st.cuda_stream)))
         return ctx._enqueue(stream, run)
 
     def build_alt(self, kind):

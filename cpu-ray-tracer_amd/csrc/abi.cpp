@@ -118,6 +118,12 @@ struct crt_ctx {
     struct RefitPlan { void* dPlan = nullptr; uint32_t* dLevelOff = nullptr; uint32_t levels = 0, rootCode = 0; bool built = false; };
     std::vector<RefitPlan> refitPlans; std::vector<void*> refitAllocs;
     float* dRefitBack = nullptr; float* hRefitBack = nullptr; hipEvent_t refitFence = nullptr, refitDone = nullptr;
+    // crt_update_transforms_device (device/tlas_build.hip): every BLAS's node-0 box on the device (6 floats each; written at upload, by CRT_UPDATE_BOUNDS and by
+    // crt_refit_device on its stream, freed with the scene), the kernel's result block and its pinned copy (TlasBuildHeader + an image of [tlasOff, shadeOff)),
+    // and the events: `tlasBack` behind the read-back (the one host wait), `tlasDone` behind the copy into the geometry buffer (what sceneReady then names)
+    float* dRootBox = nullptr;
+    char* dTlasBuild = nullptr; char* hTlasBack = nullptr; size_t tlasBuildBytes = 0;
+    hipEvent_t tlasFence = nullptr, tlasBack = nullptr, tlasDone = nullptr, tlasT0 = nullptr, tlasT1 = nullptr; bool tlasTimed = false;
     hipEvent_t altReady = nullptr;        // recorded behind the last crt_upload_alt_accel's copies (device queries on other streams wait for it)
     // Latency mode of single-window launches (render_tiles_kernel's block table), driven by measurement — see next_block_table.  Stage 0 = the table solved from the cost probe's
     // estimates (one wavefront per tile when there was no probe); stages 1 .. kLatStages = tables solved from the tile costs the stage before measured; afterwards the fastest stage is used
@@ -177,7 +183,7 @@ struct crt_ctx {
     void freeScene()
     {
         for (void* p : sceneAllocs) (void)hipFree(p);
-        sceneAllocs.clear(); haveScene = false;
+        sceneAllocs.clear(); haveScene = false; dRootBox = nullptr;
         for (void* p : refitAllocs) (void)hipFree(p);
         refitAllocs.clear(); refitPlans.clear();
         if (dPrimTex) { (void)hipFree(dPrimTex); dPrimTex = nullptr; }
@@ -364,6 +370,9 @@ void crt_destroy(crt_ctx* c)
     if (c->refitDone) (void)hipEventDestroy(c->refitDone);
     if (c->dRefitBack) (void)hipFree(c->dRefitBack);
     if (c->hRefitBack) (void)hipHostFree(c->hRefitBack);
+    for (hipEvent_t e : {c->tlasFence, c->tlasBack, c->tlasDone, c->tlasT0, c->tlasT1}) if (e) (void)hipEventDestroy(e);
+    if (c->dTlasBuild) (void)hipFree(c->dTlasBuild);
+    if (c->hTlasBack) (void)hipHostFree(c->hTlasBack);
     c->freeScene();
     for (auto& a : c->ahead) (void)hipEventDestroy(a.end);
     if (c->aheadStream) (void)hipStreamDestroy(c->aheadStream);
@@ -625,6 +634,13 @@ int crt_upload_scene(crt_ctx* c, const crt_scene_desc* sd)
     s.rootRef16 = (sd->kind == CRT_SCENE_TLAS) ? tlasRoot16 : rootRef0_16;
     s.ref16ok = (ref16ok && !hook("CRT_DEBUG_NO_REF16")) ? 1u : 0u;
     if ((r = upload(c, mats, &s.mats))) return r;
+    if (sd->kind == CRT_SCENE_TLAS) {                                     // every BLAS's node-0 box, where crt_update_transforms_device takes SetTransform's corners from
+        std::vector<float> boxes;
+        for (uint32_t bi = 0; bi < sd->bvhCount; bi++) { const crt_bvh_node& n0 = sd->bvhs[bi].nodes[0]; boxes.insert(boxes.end(), n0.aabbMin, n0.aabbMin + 3); boxes.insert(boxes.end(), n0.aabbMax, n0.aabbMax + 3); }
+        const float* d = nullptr;
+        if ((r = upload(c, boxes, &d))) return r;
+        c->dRootBox = const_cast<float*>(d);
+    }
     s.rootRef = (sd->kind == CRT_SCENE_TLAS) ? tlasRoot : rootRef0;
     // Traversal stack entries (LDS is what limits the waves per SIMD, so no slack): the ordered traversal keeps at most one pending sibling per level
     // below the root, i.e. <= height entries, and its dead store (the far child is written to slot sp before the push is decided) happens at an
@@ -728,6 +744,24 @@ static void set_root(crt_ctx* c, int kind, const float* lo, const float* hi)
     memcpy(c->meshLo, lo, 12); memcpy(c->meshHi, hi, 12); c->orderDirty = true;
 }
 
+// a TLAS of this height on top of the scene's BLASes: does the traversal stack (BVH part + TLAS pushes + the return marker) fit the LDS budget of the render kernels?
+static int check_tlas_height(crt_ctx* c, uint32_t tlasHeight)
+{
+    if ((c->hScene.bvhStack + tlasHeight + 1) * 64u * 4u + 15u * 256u > 64u * 1024u)
+        return c->fail(CRT_ERR_UNSUPPORTED, "TLAS height %u needs %u bytes of LDS traversal stack per wave (> 64 KiB)", tlasHeight, (c->hScene.bvhStack + tlasHeight + 1) * 256u);
+    return 0;
+}
+
+// what a rebuilt TLAS changes in the context besides the geometry buffer (crt_update_scene, crt_update_transforms_device), once the mirror holds the new TLAS
+// sections: the stack depth and its LDS, the root reference and pair in the kernel arguments, the dispatch-order bounds (node 0's box)
+static void adopt_tlas(crt_ctx* c, uint32_t tlasHeight, const float* lo, const float* hi)
+{
+    crt::Scene& s = c->hScene;
+    s.stackDepth = s.bvhStack + tlasHeight + 1;
+    c->ldsBytes = s.stackDepth * 64u * 4u; c->latSlots = 0;
+    set_root(c, CRT_SCENE_TLAS, lo, hi);
+}
+
 // the reference has no Refit for BLASKDTree / BLASGrid: a refit (CRT_UPDATE_BOUNDS, crt_refit_device) drops the two-level KD-tree / grid sets (their buffers are
 // freed by the next upload)
 static void drop_blas_sets(crt_ctx* c)
@@ -767,9 +801,7 @@ int crt_update_scene(crt_ctx* c, const crt_scene_desc* sd, uint32_t what)
         tlasImage.assign((size_t)(f.instOff - f.tlasOff), 0);
         int r = flatten_tlas(c, sd->tlasNodes, sd->tlasNodeCount, sd->bvhCount, reinterpret_cast<crt::TlasNode*>(tlasImage.data()),
                              reinterpret_cast<crt::NodePair*>(tlasImage.data() + (f.tlasPairOff - f.tlasOff)), &tlasHeight);
-        if (r) return r;
-        if ((c->hScene.bvhStack + tlasHeight + 1) * 64u * 4u + 15u * 256u > 64u * 1024u)
-            return c->fail(CRT_ERR_UNSUPPORTED, "TLAS height %u needs %u bytes of LDS traversal stack per wave (> 64 KiB)", tlasHeight, (c->hScene.bvhStack + tlasHeight + 1) * 256u);
+        if (r || (r = check_tlas_height(c, tlasHeight))) return r;
     }
     // ---- apply ----
     c->epoch++;
@@ -803,30 +835,29 @@ int crt_update_scene(crt_ctx* c, const crt_scene_desc* sd, uint32_t what)
         // TLASBVH::Build (tlas_bvh.cpp:17-55) ran on the host after SetTransform / Refit: new node array of the same size
         memcpy(f.geom.data() + f.tlasOff, tlasImage.data(), tlasImage.size());
         touch((size_t)f.tlasOff, (size_t)f.shadeOff);
-        crt::Scene& s = c->hScene;
-        s.stackDepth = s.bvhStack + tlasHeight + 1;
-        c->ldsBytes = s.stackDepth * 64u * 4u; c->latSlots = 0;
     }
     if (lo >= hi) return CRT_OK;
     // In-place rewrite, no allocation of device memory and no host wait for the GPU: the copy runs on the main stream, which is ordered behind every
     // render launch submitted so far (it waits for each launch's end event before that launch's accumulate); launches submitted later wait
     // for `sceneReady` on their own stream.  Pinned staging buffers alternate and grow on demand; one is reused only after its own copy.
     const int k = c->stageFlip ^= 1;
-    const size_t bytes = hi - lo;
+    const size_t boxBytes = ((what & CRT_UPDATE_BOUNDS) && c->dRootBox) ? f.rootBox.size() * 4u : 0u;   // the device copy of the node-0 boxes rides behind the range
+    const size_t geomBytes = hi - lo, bytes = geomBytes + boxBytes;
     if (c->stageBytes[k] < bytes) {
         if (c->hStage[k]) { HIPCK(c, hipEventSynchronize(c->stageCopied[k])); HIPCK(c, hipHostFree(c->hStage[k])); c->hStage[k] = nullptr; }
         HIPCK(c, hipHostMalloc((void**)&c->hStage[k], bytes, hipHostMallocDefault)); c->stageBytes[k] = bytes;
         if (!c->stageCopied[k]) HIPCK(c, hipEventCreateWithFlags(&c->stageCopied[k], hipEventDisableTiming));
     } else HIPCK(c, hipEventSynchronize(c->stageCopied[k]));
-    memcpy(c->hStage[k], f.geom.data() + lo, bytes);
+    memcpy(c->hStage[k], f.geom.data() + lo, geomBytes);
+    if (boxBytes) memcpy(c->hStage[k] + geomBytes, f.rootBox.data(), boxBytes);
     { const int r = order_behind_ahead(c); if (r) return r; }
     { const int r = order_behind_queries(c); if (r) return r; }
-    HIPCK(c, hipMemcpyAsync(const_cast<char*>(c->hScene.geom) + lo, c->hStage[k], bytes, hipMemcpyHostToDevice, c->stream));
+    HIPCK(c, hipMemcpyAsync(const_cast<char*>(c->hScene.geom) + lo, c->hStage[k], geomBytes, hipMemcpyHostToDevice, c->stream));
+    if (boxBytes) HIPCK(c, hipMemcpyAsync(c->dRootBox, c->hStage[k] + geomBytes, boxBytes, hipMemcpyHostToDevice, c->stream));
     HIPCK(c, hipEventRecord(c->stageCopied[k], c->stream));
     c->sceneReady = c->stageCopied[k];
-    const float* blo = (f.kind == CRT_SCENE_TLAS) ? sd->tlasNodes[0].aabbMin : sd->bvhs[0].nodes[0].aabbMin;
-    const float* bhi = (f.kind == CRT_SCENE_TLAS) ? sd->tlasNodes[0].aabbMax : sd->bvhs[0].nodes[0].aabbMax;
-    set_root(c, f.kind, blo, bhi);
+    if (f.kind == CRT_SCENE_TLAS) adopt_tlas(c, tlasHeight, sd->tlasNodes[0].aabbMin, sd->tlasNodes[0].aabbMax);
+    else set_root(c, f.kind, sd->bvhs[0].nodes[0].aabbMin, sd->bvhs[0].nodes[0].aabbMax);
     return CRT_OK;
 }
 
@@ -2250,6 +2281,7 @@ int crt_refit_device(crt_ctx* c, uint32_t bvh, const float* d_positions, uint32_
     HIPCK(c, crt_launch_refit(const_cast<char*>(c->hScene.geom), (uint32_t)f.leafOff, (uint32_t)f.pairBase[bvh], (uint32_t)f.triBase[bvh], triCount, d_positions,
                               P.dPlan, P.dLevelOff, P.levels, P.rootCode, c->dRefitBack, st));
     HIPCK(c, hipMemcpyAsync(c->hRefitBack, c->dRefitBack, 88, hipMemcpyDeviceToHost, st));
+    if (c->dRootBox) HIPCK(c, hipMemcpyAsync(c->dRootBox + 6 * (size_t)bvh, c->dRefitBack + 16, 24, hipMemcpyDeviceToDevice, st));   // the box pass's node-0 box, for crt_update_transforms_device
     HIPCK(c, hipEventRecord(c->refitDone, st));
     c->sceneReady = c->refitDone;                                         // launches submitted later wait for it on their own stream; the main stream's own consumers here
     if (st != c->stream) HIPCK(c, hipStreamWaitEvent(c->stream, c->refitDone, 0));
@@ -2261,6 +2293,98 @@ int crt_refit_device(crt_ctx* c, uint32_t bvh, const float* d_positions, uint32_
     if (f.kind == CRT_SCENE_FILE) set_root(c, CRT_SCENE_FILE, back + 16, back + 19);      // rootPair from the mirror, dispatch-order bounds; a BLAS's box reaches the TLAS through the caller
     drop_blas_sets(c);
     if (rootBox) memcpy(rootBox, back + 16, 24);
+    return CRT_OK;
+}
+
+// ---- crt_update_transforms_device: SetTransform of every BLAS + TLASBVH::Build on the device, from transforms in device memory (device/tlas_build.hip) ----
+int crt_update_transforms_device(crt_ctx* c, const float* d_T, uint32_t blasCount, void* stream, crt_tlas_node* tlasOut)
+{
+    if (!c) return CRT_ERR_INVALID;
+    if (c->havePrim) return c->fail(CRT_ERR_UNSUPPORTED, "crt_update_transforms_device: the PrimitiveScene has no instances");
+    if (!c->haveScene) return c->fail(CRT_ERR_STATE, "crt_update_transforms_device before crt_upload_scene");
+    crt_ctx::Flat& f = c->flat;
+    if (f.kind != CRT_SCENE_TLAS) return c->fail(CRT_ERR_INVALID, "crt_update_transforms_device applies to two-level scenes (a FileScene bakes its transforms into the triangles)");
+    const uint32_t N = (uint32_t)f.triCount.size();
+    if (blasCount != N) return c->fail(CRT_ERR_INVALID, "crt_update_transforms_device: %u transforms, the uploaded scene has %u BLAS", blasCount, N);
+    if (f.tlasNodeCount != 2u * N) return c->fail(CRT_ERR_UNSUPPORTED, "crt_update_transforms_device: the scene was uploaded with %u TLAS nodes, TLASBVH::Build makes %u", f.tlasNodeCount, 2u * N);
+    HIPCK(c, hipSetDevice(c->cfg.device));
+    int r;
+    if ((r = check_device_buffer(c, d_T, (size_t)N * 64u, "crt_update_transforms_device"))) return r;
+    hipStream_t st = nullptr;
+    if ((r = caller_stream(c, stream, "crt_update_transforms_device", &st))) return r;
+    const size_t imageBytes = (size_t)(f.shadeOff - f.tlasOff), backBytes = sizeof(crt::TlasBuildHeader) + imageBytes;
+    if (c->tlasBuildBytes < backBytes) {                                    // a larger scene than the last one: nothing of an earlier call is in flight in these (see below)
+        if (c->tlasDone) HIPCK(c, hipEventSynchronize(c->tlasDone));
+        if (c->dTlasBuild) { HIPCK(c, hipFree(c->dTlasBuild)); c->dTlasBuild = nullptr; }
+        if (c->hTlasBack) { HIPCK(c, hipHostFree(c->hTlasBack)); c->hTlasBack = nullptr; }
+        c->tlasBuildBytes = 0;
+        HIPCK(c, hipMalloc((void**)&c->dTlasBuild, backBytes));
+        HIPCK(c, hipHostMalloc((void**)&c->hTlasBack, backBytes, hipHostMallocDefault));
+        HIPCK(c, hipMemset(c->dTlasBuild, 0, backBytes));                   // the padding between the image's sections stays zero, as in the host's image: the kernel writes records only
+        c->tlasBuildBytes = backBytes;
+    }
+    for (hipEvent_t* e : {&c->tlasFence, &c->tlasBack, &c->tlasDone}) if (!*e) HIPCK(c, hipEventCreateWithFlags(e, hipEventDisableTiming));
+    if (g_hooks) for (hipEvent_t* e : {&c->tlasT0, &c->tlasT1}) if (!*e) HIPCK(c, hipEventCreate(e));
+    // The build reads the Instance records and the node-0 boxes as the last update / refit left them and writes only the context's result block, which the copy
+    // of an earlier call may still be reading on another stream: both are behind sceneReady.  Earlier renders and queries are not waited for yet.
+    if (c->sceneReady) HIPCK(c, hipStreamWaitEvent(st, c->sceneReady, 0));
+    if (g_hooks) HIPCK(c, hipEventRecord(c->tlasT0, st));
+    HIPCK(c, crt_launch_tlas_build(c->hScene.geom, (uint32_t)f.instOff, d_T, c->dRootBox, N, (uint32_t)(f.tlasPairOff - f.tlasOff), (uint32_t)(f.instOff - f.tlasOff), c->dTlasBuild, st));
+    if (g_hooks) { HIPCK(c, hipEventRecord(c->tlasT1, st)); c->tlasTimed = true; }
+    HIPCK(c, hipMemcpyAsync(c->hTlasBack, c->dTlasBuild, backBytes, hipMemcpyDeviceToHost, st));
+    HIPCK(c, hipEventRecord(c->tlasBack, st));
+    // the one host wait: the root's pair and the stack depth travel in the kernel arguments of every later launch, and only a build that passed is committed
+    HIPCK(c, hipEventSynchronize(c->tlasBack));
+    const crt::TlasBuildHeader& h = *reinterpret_cast<const crt::TlasBuildHeader*>(c->hTlasBack);
+    const char* image = c->hTlasBack + sizeof(crt::TlasBuildHeader);
+    if (h.status == crt::kTlasBuildNoCandidate)
+        return c->fail(CRT_ERR_INVALID, "crt_update_transforms_device: FindBestMatch call %u found no partner while more than one node was open (a non-finite transform or box, or areas >= 1e30; the reference reads list[-1] there)", h.step);
+    if (h.status != crt::kTlasBuildOk) return c->fail(CRT_ERR_INVALID, "crt_update_transforms_device: the build had not ended after %u FindBestMatch calls", h.step);
+    if ((r = check_tlas_height(c, h.height))) return r;
+    // ---- commit: in place, behind every earlier launch that reads the geometry (as crt_refit_device), on the caller's stream ----
+    if ((r = order_behind_ahead(c)) || (r = order_behind_queries(c))) return r;
+    if (st != c->stream) {
+        HIPCK(c, hipEventRecord(c->tlasFence, c->stream));
+        HIPCK(c, hipStreamWaitEvent(st, c->tlasFence, 0));
+    }
+    HIPCK(c, hipMemcpyAsync(const_cast<char*>(c->hScene.geom) + f.tlasOff, c->dTlasBuild + sizeof(crt::TlasBuildHeader), imageBytes, hipMemcpyDeviceToDevice, st));
+    HIPCK(c, hipEventRecord(c->tlasDone, st));
+    c->sceneReady = c->tlasDone;                                           // launches submitted later wait for it on their own stream
+    if (st != c->stream) HIPCK(c, hipStreamWaitEvent(c->stream, c->tlasDone, 0));
+    c->epoch++;                                                           // frames rendered ahead by crt_tick are of the old scene
+    memcpy(f.geom.data() + f.tlasOff, image, imageBytes);                  // the mirror: a later CRT_UPDATE_BOUNDS rewrites [tlasOff, shadeOff) from it
+    const crt::TlasNode* nodes = reinterpret_cast<const crt::TlasNode*>(image);
+    adopt_tlas(c, h.height, nodes[0].lo, nodes[0].hi);
+    if (tlasOut)
+        for (uint32_t i = 0; i < 2u * N; i++) {                            // the reference layout again: leftRight / BLAS from the packed reference
+            const crt::TlasNode& n = nodes[i]; crt_tlas_node& o = tlasOut[i];
+            memcpy(o.aabbMin, n.lo, 12); memcpy(o.aabbMax, n.hi, 12);
+            const bool leaf = (n.ref & 0xC0000000u) == crt::kRefTlasLeaf;
+            o.leftRight = leaf ? 0u : ((n.ref & 0x7fffu) | (((n.ref >> 15) & 0x7fffu) << 16));
+            o.BLAS = leaf ? (n.ref & 0xffffu) : 0u;
+        }
+    return CRT_OK;
+}
+
+// the host front's read of a caller's device buffer (host_abi.cpp, which includes no HIP header): behind everything `stream` holds, synchronous
+extern "C" int crt_internal_read_device(crt_ctx* c, void* dst, const void* d_src, size_t bytes, void* stream)
+{
+    if (!c || !dst) return CRT_ERR_INVALID;
+    HIPCK(c, hipSetDevice(c->cfg.device));
+    int r; hipStream_t st = nullptr;
+    if ((r = check_device_buffer(c, d_src, bytes, "crt_internal_read_device")) || (r = caller_stream(c, stream, "crt_internal_read_device", &st))) return r;
+    HIPCK(c, hipMemcpyAsync(dst, d_src, bytes, hipMemcpyDeviceToHost, st));
+    HIPCK(c, hipStreamSynchronize(st));
+    return CRT_OK;
+}
+
+// tools/tlas_device_cost.py: the duration of the last crt_update_transforms_device's kernel (HIP events on its stream; debug hooks only)
+extern "C" int crt_debug_tlas_build_ms(crt_ctx* c, float* ms)
+{
+    if (!c || !ms) return CRT_ERR_INVALID;
+    if (!c->tlasTimed) return c->fail(CRT_ERR_STATE, "crt_debug_tlas_build_ms: no timed crt_update_transforms_device (debug hooks off?)");
+    HIPCK(c, hipEventSynchronize(c->tlasT1));
+    HIPCK(c, hipEventElapsedTime(ms, c->tlasT0, c->tlasT1));
     return CRT_OK;
 }
 

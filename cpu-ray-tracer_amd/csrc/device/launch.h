@@ -67,6 +67,10 @@ hipError_t crt_launch_refit(char* geom, uint32_t leafOff, uint32_t pairBase, uin
     uint32_t rootCode, float* out, hipStream_t stream);
 hipError_t crt_launch_probe_f32(int op, const void* in, void* out, uint32_t n, hipStream_t stream);
 
+// ---- tlas_build.hip ----
+hipError_t crt_launch_tlas_build(const char* geom, uint32_t instOff, const float* T, const float* rootBox, uint32_t blasCount, uint32_t pairRel, uint32_t instRel, void* out,
+    hipStream_t stream);
+
 // abi.cpp's test switch CRT_DEBUG_QUERY_GRID=<k>: an upper bound on the workgroups of a persistent query launch (0: none).  Host side only: each wrapper passes its grid through it.
 uint32_t crt_debug_query_grid(void);
 

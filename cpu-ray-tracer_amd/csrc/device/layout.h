@@ -109,6 +109,19 @@ struct Counters { unsigned long long v[8]; };   // order = crt_counters
 struct alignas(16) RefitPlanRec { uint32_t pair, child[2], pad; };
 constexpr uint32_t kPlanInterior = 0x80000000u;
 
+// crt_update_transforms_device's result block (tlas_build.hip): this header, then an image of the geometry buffer's [tlasOff, shadeOff) — TLAS nodes, TLAS child
+// pairs, Instance records, at the same relative offsets — which the host reads back, checks and only then copies into the geometry buffer.
+struct alignas(64) TlasBuildHeader {
+    uint32_t status;                      // kTlasBuild*
+    uint32_t step;                        // the FindBestMatch call (counted from 1) that found no candidate / at which the bound was hit
+    uint32_t height;                      // deepest leaf below node 0, in edges: what flatten_tlas reports
+    uint32_t searches;                    // FindBestMatch calls made
+    uint32_t staleA;                      // merges after which A lay outside the list (tlas_bvh.cpp's list[B] = list[N-1]; --N with A == N-1)
+    uint32_t pad[11];
+};
+constexpr uint32_t kTlasBuildOk = 0u, kTlasBuildNoCandidate = 1u, kTlasBuildNoEnd = 2u;
+constexpr uint32_t kTlasMaxBlas = 256u;   // tlas_bvh.cpp:21 (nodeIdx[256])
+
 // Whether a crt_hit's indices may be used as addresses by the hit-info query (shade_query.hip): ONE predicate for the host entry, which refuses the call, and for
 // the kernel, which writes CRT_MATERIAL_INVALID for the lane.  objects = crt_scene_desc.objCount (FileScene) / bvhCount (two-level); triCountOf(k) = triangles of
 // the BVH that object 2 + k's triIdx indexes (FileScene: its one BVH; two-level: BLAS k), asked only for an object that exists.

@@ -5,6 +5,7 @@
 
 #include <cstdlib>
 #include <string>
+#include <vector>
 
 using namespace crt;
 
@@ -26,6 +27,9 @@ static bool refuse_stale(crt_host_scene* s, const char* what)
 
 #define GUARD_BEGIN try {
 #define GUARD_END(code) } catch (const std::exception& e) { g_err = e.what(); return code; } catch (...) { g_err = "unknown exception"; return code; }
+
+// abi.cpp's, for this file only (the host front includes no HIP header): a synchronous copy of device memory to the host behind what `stream` holds
+extern "C" int crt_internal_read_device(crt_ctx* ctx, void* dst, const void* d_src, size_t bytes, void* stream);
 
 extern "C" {
 
@@ -125,6 +129,32 @@ int crt_host_scene_bvh_refit_device(crt_host_scene* s, crt_ctx* ctx, int i, cons
         if (rc != CRT_OK) g_err = crt_last_error(ctx);
     }
     return rc;
+    GUARD_END(CRT_ERR_DEVICE)
+}
+int crt_host_scene_update_transforms_device(crt_host_scene* s, crt_ctx* ctx, const float* d_T, void* stream)
+{
+    if (!s || !ctx) { g_err = "null argument"; return CRT_ERR_INVALID; }
+    if (!s->tlas) { g_err = "not a TLAS scene (a FileScene bakes its transforms into the triangles)"; return CRT_ERR_INVALID; }
+    GUARD_BEGIN
+    TLASBVH& tl = s->tlas->tlas;
+    const size_t n = tl.blas.size();
+    std::vector<float> T(16 * n);                                                    // first, so that the copy waits for d_T's producers only, not for the entry's commit
+    const int rb = crt_internal_read_device(ctx, T.data(), d_T, T.size() * 4, stream);
+    if (rb != CRT_OK) { g_err = crt_last_error(ctx); return rb; }
+    std::vector<crt_tlas_node> nodes(2 * n);
+    const int rc = crt_update_transforms_device(ctx, d_T, (uint32_t)n, stream, nodes.data());
+    if (rc != CRT_OK) { g_err = crt_last_error(ctx); return rc; }
+    for (size_t i = 0; i < n; i++) {                                                 // BLASBVH::SetTransform's results; the world box is TLAS leaf 1 + i's
+        BLASBVH* b = tl.blas[i];
+        memcpy(b->T.cell, &T[16 * i], 64);
+        b->invT = b->T.FastInvertedTransformNoScale();
+        b->worldBounds.bmin3 = float3(nodes[1 + i].aabbMin[0], nodes[1 + i].aabbMin[1], nodes[1 + i].aabbMin[2]);
+        b->worldBounds.bmax3 = float3(nodes[1 + i].aabbMax[0], nodes[1 + i].aabbMax[1], nodes[1 + i].aabbMax[2]);
+    }
+    tl.tlasNode.resize(2 * n);
+    memcpy(tl.tlasNode.data(), nodes.data(), sizeof(crt_tlas_node) * 2 * n);
+    tl.nodesUsed = (uint32_t)(2 * n);
+    return CRT_OK;
     GUARD_END(CRT_ERR_DEVICE)
 }
 // BLASBVH::SetTransform(T) of instance i (blas_bvh.cpp:363-374: T, invT = FastInvertedTransformNoScale, world bounds of the 8 root-box corners)

@@ -163,8 +163,10 @@ int  crt_update_scene(crt_ctx* ctx, const crt_scene_desc* scene, uint32_t what);
  * what the reference's backward loop gives, INCLUDING ITS QUIRK that node 1 is skipped (`if (i != 1)`, bvh.cpp:28): the root's left child keeps the box it had,
  * and that stale box still feeds node 0's.  Normals, uvs, materials, references and the leaf order stay (Refit touches none of them).
  * rootBox (may be NULL) receives node 0's refitted aabbMin, aabbMax.  Two-level scenes: the call does NOT rebuild the TLAS (neither does BLASBVH::Refit); the caller
- * puts rootBox into its BLAS's node 0, runs SetTransform + TLASBVH::Build as after any Refit and sends the result with crt_update_scene(CRT_UPDATE_TRANSFORMS) —
- * rootBox is what makes that possible without reading the device.  (crt_host_scene_bvh_refit_device does all of it.)
+ * either
+ * calls crt_update_transforms_device next, which rebuilds the TLAS on the device from the refitted node-0 box with nothing from the host in between, or puts rootBox
+ * into its BLAS's node 0, runs SetTransform + TLASBVH::Build on the host as after any Refit and sends the result with crt_update_scene(CRT_UPDATE_TRANSFORMS) —
+ * rootBox is what makes the host route possible without reading the device.  (crt_host_scene_bvh_refit_device takes the host route.)
  * Ordering, as crt_update_scene and the device queries: the refit kernels run on `stream` behind every launch submitted earlier that reads the geometry (renders,
  * frames rendered ahead, queries on any stream), so earlier renders still see the old scene; every launch submitted later waits for the refit.  THE ONE HOST WAIT:
  * the root's child pair travels in the kernel arguments of the render launches, so the call reads that pair and node 0's box back (88 bytes, pinned) and returns
@@ -175,6 +177,28 @@ int  crt_update_scene(crt_ctx* ctx, const crt_scene_desc* scene, uint32_t what);
  * CRT_UPDATE_BOUNDS built from them) are its own business: an update rewrites both sections from whatever it is given. */
 int  crt_refit_device(crt_ctx* ctx, uint32_t bvh, const float* d_positions /* 9 * triCount, device */, uint32_t triCount, void* stream,
                       float rootBox[6] /* out: node 0's aabbMin, aabbMax; may be NULL */);
+/* Instance motion of a two-level scene from transforms that already live in device memory (a physics step, an optimiser over poses): BLASBVH::SetTransform for
+ * EVERY BLAS (blas_bvh.cpp:363-374) and the TLASBVH::Build that follows (tlas_bvh.cpp:17-70), on the device, in one kernel launch.  ABI version 3 still: an
+ * addition, detected by symbol.  d_T[16 i .. 16 i + 15] = BLASBVH::T of BLAS i, a row-major mat4 as crt_bvh.T; only cells 0..11 are read; no scale (as
+ * FastInvertedTransformNoScale assumes); device memory of cfg.device, 4-byte aligned, checked as the device query entries check theirs; `stream` as there.
+ * What the call leaves on the device is exactly what crt_host_scene_set_transform for every BLAS followed by crt_update_scene(CRT_UPDATE_TRANSFORMS) leaves, byte
+ * for byte: the Instance records' T / invT rows, the TLAS nodes, the TLAS child pairs, the root reference and pair, the stack depth.  The world box of BLAS i is
+ * grown from the node-0 box of BLAS i AS THE DEVICE HOLDS IT: the one uploaded, sent by the last CRT_UPDATE_BOUNDS, or refitted by crt_refit_device — so
+ * crt_refit_device followed by this call needs no value from the host in between.  The build keeps the reference's quirks (FindBestMatch's first strict minimum
+ * below 1e30f; the list shortened before the search that follows a merge, so that the new node can meet its own copy).
+ * tlasOut (may be NULL) receives TLASBVH::tlasNode[0 .. 2 * blasCount) in the reference layout, byte for byte.
+ * Ordering: the build runs on `stream` into scratch of the context's.  THE ONE HOST WAIT, as crt_refit_device's: the root's pair and the stack depth travel in the
+ * kernel arguments of later launches, so the call reads the result back (status, height, the TLAS and Instance sections: 64 KB at most, pinned) and returns once
+ * that has landed.  Only a build that passed every check is then copied into the geometry buffer, on `stream`, behind every launch submitted earlier that reads
+ * the geometry (renders, frames rendered ahead, queries on any stream: they still see the old scene); every launch submitted later waits for the copy.
+ * Otherwise as CRT_UPDATE_TRANSFORMS: frames crt_tick rendered ahead are dropped, KD-tree / grid BLAS sets are kept (they live in object space).
+ * Refused with nothing modified: no scene (CRT_ERR_STATE); a CRT_SCENE_FILE scene (CRT_ERR_INVALID); a PrimitiveScene (CRT_ERR_UNSUPPORTED); blasCount different
+ * from the uploaded bvhCount, d_T NULL / misaligned / a host pointer / memory of another device, a stream of another device (CRT_ERR_INVALID); a TLAS whose
+ * traversal stack exceeds the LDS budget (CRT_ERR_UNSUPPORTED, as crt_update_scene); a build in which FindBestMatch finds no candidate while more than one node is
+ * open — the reference's list[-1], reached with non-finite transforms or boxes of area >= 1e30 (CRT_ERR_INVALID; crt_last_error names the FindBestMatch call);
+ * a scene uploaded with more than 2 * bvhCount TLAS nodes (CRT_ERR_UNSUPPORTED). */
+int  crt_update_transforms_device(crt_ctx* ctx, const float* d_T /* 16 * blasCount, device */, uint32_t blasCount, void* stream,
+                                  crt_tlas_node* tlasOut /* host, 2 * blasCount; may be NULL */);
 int  crt_set_camera(crt_ctx* ctx, const float camPos[3], const float topLeft[3], const float topRight[3], const float bottomLeft[3]);
                                                                 /* Camera members used by GetPrimaryRay (camera.h:23-30) */
 

@@ -63,6 +63,10 @@ int  crt_host_scene_update(crt_host_scene* scene, crt_ctx* ctx, uint32_t what);
  * crt_host_scene_upload and crt_host_scene_update(.., CRT_UPDATE_BOUNDS) — which would send those arrays — are refused with CRT_ERR_STATE.
  * crt_host_scene_bvh_move_and_refit on that BVH (the positions on the host again) clears its mark. */
 int  crt_host_scene_bvh_refit_device(crt_host_scene* scene, crt_ctx* ctx, int bvh, const float* d_positions, uint32_t triCount, void* stream);
+/* Instance motion on the device (crt_update_transforms_device; d_T = 16 floats per BLAS in device memory, stream as there): runs the entry, copies the transforms
+ * back and leaves the host scene's T, invT, worldBounds and tlasNode as crt_host_scene_set_transform for every BLAS would have left them (the world boxes and the
+ * node array are the device's own: identical, and right also after crt_host_scene_bvh_refit_device).  No crt_host_scene_update is needed afterwards. */
+int  crt_host_scene_update_transforms_device(crt_host_scene* scene, crt_ctx* ctx, const float* d_T, void* stream);
 int  crt_host_scene_blas_transform(crt_host_scene* scene, int bvh, float T[16], float invT[16], float worldMin[3], float worldMax[3]);
 int  crt_host_scene_tlas_copy(crt_host_scene* scene, crt_tlas_node* nodes /* 2*blasCount */, uint32_t* nodesUsed);
 
