@@ -152,6 +152,9 @@ struct crt_ctx {
     uint32_t* dJobDesc = nullptr; uint32_t* hJobDesc = nullptr; uint32_t jobDescCap = 0, jobBlocks = 0, jobHead = 0; hipEvent_t jobDescReady = nullptr;
     uint32_t planWindows = 0, planFrames = 0; bool planPool = false, planValid = false;       // what the table on the device was planned for
     double jobTrialMs[2] = {0, 0};          // this plan's shape timed [0] plain (cost-ordered, no table) and [1] planned: the faster one is kept (planner_prepare)
+    // the plan's pool launch: frames per wavefront by tile rank (pool_wave_plan), behind the block table in dJobDesc — jobWaveBlocks wavefronts (0: every wavefront S frames,
+    // no table), jobLongWaves of them with more than S frames; lastLongWaves: what the last pool launch had of those (crt_debug_pool_long_waves)
+    uint32_t jobWaveOff = 0, jobWaveBlocks = 0, jobLongFrames = 0, jobLongWaves = 0, lastLongWaves = 0;
     std::vector<hipEvent_t> splitEvents;    // end events of the second kernel of split launches (recycled round-robin)
     size_t splitSeq = 0; uint32_t splitLaunches = 0;
     uint64_t poolMinWaves = 65000; // launches of fewer (tile, 64-frame window) pairs run render_tiles_kernel: see crt_render
@@ -1340,6 +1343,80 @@ static void plan_job(const crt_ctx* c, uint32_t windows, uint32_t frames, bool p
     *head = pool ? h : 0u;
 }
 
+// Frames per pool wavefront, by tile rank.  A wavefront that owns S frames of a tile spends the last part of its life with its population falling from S to 0; one that
+// owns more refills its slots (render_pool_kernel) and pays that ramp-down once per range instead of once per S frames.  But a launch ends on its last wavefront, a
+// range of S 2^k frames lasts 2^k times as long, and fewer, longer wavefronts pack the launch's end worse.  So the launch has two parts.  The LONG part renders the frames
+// [0, longFrames) of every tile, longFrames = the whole multiples of 8 S frames within `share` of the job: the tile at rank r (dispatch order: most expensive first) is
+// expected to start when the machine has worked off the long part of the tiles before it — startTicks + the sum of their machine time, longFrames / 64 x cost x perCost —
+// and its wavefronts last poolLong x cost x frames / 128 (plan_job's term: 2.4 = 2 x the 1.2 under load); it gets the largest k <= 3 for which  start + safety x duration <= aim
+// (the job's makespan aim: the machine time of everything).  The SHORT part renders the remaining frames of every tile with S frames per wavefront, as a launch without
+// refill does, dispatched behind the long part in the same tile order: its many short wavefronts fill the launch's end, and a tile's last wavefront takes the remainder.
+// Nothing is lengthened when costs are unknown (cost == nullptr), or when the launch would keep fewer than guard x resident wavefronts — the chip must stay oversubscribed
+// for the dispatch order to fill the tail: k is capped lower until it does.  Measured: a 64-window 720p plan that keeps 14 x 4096 wavefronts gains 2 %, a 20-window plan
+// that kept 6 x 4096 lost 37 % (it grew the tail the split had removed); the guard is 12.  Needs no GPU (tests:
+// crt_debug_pool_wave_plan).  Returns the wavefronts of the launch; wf[r] = frames per wavefront of rank r in the long part, start[r] its expected start; *longFrames = 0:
+// every wavefront owns S frames.
+struct PoolWaveTerms { double poolLong = 2.4, load = 1.0, safety = 1.0, guard = 12.0, share = 1.0; };   // (poolLong is the duration UNDER LOAD: it holds the 1.2, plan_job)
+static uint64_t pool_wave_plan(const uint32_t* cost, uint32_t nr, uint32_t frames, uint32_t S, double perCost, double startTicks, uint32_t resident, const PoolWaveTerms& tm,
+                               std::vector<uint32_t>& wf, uint32_t* longFrames, std::vector<double>* start, double* aimOut)
+{
+    wf.assign(nr, S); *longFrames = 0;
+    if (start) start->assign(nr, 0.0);
+    if (aimOut) *aimOut = 0;
+    const uint64_t perTile = (frames + S - 1u) / S, plain = (uint64_t)nr * perTile;
+    if (!cost || S <= 64u || nr == 0u) return plain;
+    const uint32_t F1 = (uint32_t)((double)frames * std::min(tm.share, 1.0)) / (8u * S) * (8u * S);
+    if (F1 == 0u) return plain;
+    double aim = startTicks, m = startTicks;
+    std::vector<double> st(nr);
+    for (uint32_t r = 0; r < nr; r++) { st[r] = m; m += (double)(F1 / 64u) * (double)cost[r] * perCost; aim += (double)((frames + 63u) / 64u) * (double)cost[r] * perCost; }
+    if (start) *start = st;
+    if (aimOut) *aimOut = aim;
+    if ((double)plain < tm.guard * (double)resident) return plain;
+    const uint64_t shortWaves = (uint64_t)nr * ((frames - F1 + S - 1u) / S);
+    for (int kMax = 3; kMax >= 1; kMax--) {
+        uint64_t waves = shortWaves; bool any = false;
+        for (uint32_t r = 0; r < nr; r++) {
+            int k = kMax;
+            while (k > 0 && st[r] + tm.safety * tm.poolLong * tm.load * (double)cost[r] * (double)((uint64_t)S << k) / 128.0 > aim) k--;
+            wf[r] = S << k; any = any || k > 0;
+            waves += F1 / wf[r];
+        }
+        if (!any) break;
+        if ((double)waves >= tm.guard * (double)resident) { *longFrames = F1; return waves; }
+    }
+    wf.assign(nr, S);
+    return plain;
+}
+// the table of the long part of such a launch: first block and frames per wavefront of every rank (render_pool_kernel's waveTab); returns its wavefronts
+static uint32_t pool_wave_table(const std::vector<uint32_t>& wf, uint32_t longFrames, uint32_t S, std::vector<uint32_t>& tab, uint32_t* longWaves)
+{
+    tab.resize(2 * wf.size()); uint32_t b = 0, lw = 0;
+    for (size_t r = 0; r < wf.size(); r++) {
+        tab[2 * r] = b; tab[2 * r + 1] = wf[r];
+        b += longFrames / wf[r];
+        if (wf[r] > S) lw += longFrames / wf[r];
+    }
+    if (longWaves) *longWaves = lw;
+    return b;
+}
+static bool pool_wave_terms(PoolWaveTerms& tm)
+{
+    if (const char* e = hook("CRT_POOL_REFILL_SAFETY")) { const double v = atof(e); if (v > 0) tm.safety = v; }
+    if (const char* e = hook("CRT_POOL_REFILL_GUARD")) { const double v = atof(e); if (v > 0) tm.guard = v; }
+    if (const char* e = hook("CRT_POOL_REFILL_SHARE")) { const double v = atof(e); if (v > 0) tm.share = v; }
+    return !hook("CRT_POOL_REFILL_OFF");
+}
+// tests / A-B runs: CRT_POOL_WAVE_FRAMES=<n> forces n frames per pool wavefront for every tile (rounded down to whole groups of S; n = 128 is the launch without refill)
+static uint32_t forced_wave_frames(uint32_t S)
+{
+    const char* e = hook("CRT_POOL_WAVE_FRAMES");
+    if (!e) return 0u;
+    const long v = atol(e);
+    if (v < (long)S) return S;
+    return (uint32_t)std::min<long>(v, 8192) / S * S;
+}
+
 // ... and its table on the device (cached for launches of the same shape)
 static int install_job_plan(crt_ctx* c, uint32_t windows, uint32_t frames, bool pool)
 {
@@ -1348,6 +1425,34 @@ static int install_job_plan(crt_ctx* c, uint32_t windows, uint32_t frames, bool 
     plan_job(c, windows, frames, pool, table, &head);
     c->planValid = true; c->planWindows = windows; c->planFrames = frames; c->planPool = pool; c->jobHead = head; c->jobBlocks = (uint32_t)table.size();
     c->jobTrialMs[0] = c->jobTrialMs[1] = 0;
+    c->jobWaveOff = c->jobWaveBlocks = c->jobLongFrames = c->jobLongWaves = 0;
+    PoolWaveTerms terms;
+    const uint32_t S = crt_pool_streams(frames);
+    if (pool && c->jobCostValid && !c->cfg.collectStats && head < c->tileCount && pool_wave_terms(terms) && !forced_wave_frames(S)) {
+        // the pool launch's ranks: the order from `head` on; the head's tiles (block table, dispatched first) are machine time spent before them
+        const uint32_t nr = c->tileCount - head;
+        std::vector<uint32_t> cost(nr), wf, tab;
+        double costSum = 0; for (uint32_t v : c->jobCost) costSum += (double)v;
+        const double perCost = (c->poolWindowTicks > 0 && costSum > 0) ? c->poolWindowTicks / costSum : 1.0 / 4096.0;
+        double startTicks = 0;
+        for (uint32_t r = 0; r < head; r++) startTicks += (double)windows * 1.2 * (double)c->jobCost[c->jobOrder[r]] * perCost;      // (one stream per lane: 1.2 x the pool's machine time)
+        for (uint32_t r = 0; r < nr; r++) cost[r] = c->jobCost[c->jobOrder[head + r]];
+        double aim = 0; uint32_t F1 = 0, lw = 0, blocks = 0;
+        pool_wave_plan(cost.data(), nr, frames, S, perCost, startTicks, 4096u, terms, wf, &F1, nullptr, &aim);
+        if (F1) blocks = pool_wave_table(wf, F1, S, tab, &lw);
+        if (lw) {
+            c->jobWaveOff = (uint32_t)table.size(); c->jobWaveBlocks = blocks; c->jobLongFrames = F1; c->jobLongWaves = lw;
+            table.insert(table.end(), tab.begin(), tab.end());
+        }
+        if (hook("CRT_LAT_VERBOSE")) {
+            uint32_t cnt[4] = {0, 0, 0, 0}; double share[4] = {0, 0, 0, 0}, sum = 0;
+            for (uint32_t r = 0; r < nr; r++) { int k = 0; while ((S << k) < wf[r]) k++; cnt[k]++; share[k] += cost[r]; sum += cost[r]; }
+            fprintf(stderr, "[crt] pool launch of %u ranks x %u frames: aim %.1f ms, most expensive tile %.2f ms, long part %u frames in %u wavefronts, %u of them own more than %u frames (safety %.2f, guard %.1f x 4096, share %.2f); tiles by frames per wavefront (share of the cost):",
+                    nr, frames, aim * 1e-5, nr ? cost[0] * 1e-5 : 0.0, F1, blocks, lw, S, terms.safety, terms.guard, terms.share);
+            for (int k = 0; k < 4; k++) fprintf(stderr, " %u: %u (%.3f)", S << k, cnt[k], sum > 0 ? share[k] / sum : 0.0);
+            fprintf(stderr, "\n");
+        }
+    }
     if (table.empty()) return 0;
     if (c->jobDescCap < table.size()) {
         if (c->dJobDesc) (void)hipFree(c->dJobDesc);
@@ -1377,6 +1482,7 @@ struct Launch {
     const uint32_t* blockDesc = nullptr; uint32_t nBlocks = 0;      // the latency mode's table (single-window launch), or none
     bool wantCost = false, wantJobCost = false, pool = false;
     uint32_t head = 0, jobBlocks = 0; unsigned long long* jobClk = nullptr;      // a planned job: table blocks + first tile rank of the pool launch
+    uint32_t waveFrames = 0, waveBlocks = 0, longFrames = 0, longWaves = 0; const uint32_t* waveTab = nullptr;   // the pool launch's frames per wavefront: one for all (0: S), or per rank (table of waveBlocks wavefronts)
 };
 
 static int next_block_table(crt_ctx* c);
@@ -1440,18 +1546,23 @@ static int planner_prepare(crt_ctx* c, Launch& L)
         // shape runs planned, the second plain (same kernel choice, cost-ordered, no table), and whichever was faster is kept: "planned is never slower than the
         // plain launch" holds by construction from the third launch on (tags 100 / 101 of the timing pairs, harvest_tuning).
         int use = 1;                                                           // 1 planned, 0 plain
-        if (c->jobBlocks && !hook("CRT_PLAN_NO_TRIAL")) {
+        if ((c->jobBlocks || c->jobLongWaves) && !hook("CRT_PLAN_NO_TRIAL")) {
             if (c->jobTrialMs[1] > 0 && c->jobTrialMs[0] > 0) use = c->jobTrialMs[1] <= c->jobTrialMs[0] ? 1 : 0;
             else if (c->jobTrialMs[1] > 0 && c->jobTrialMs[0] == 0) use = 0;   // the planned launch has been timed: time the plain one
             c->evRender.back().mode = 100 + use;
         }
-        if (use) { L.head = c->jobHead; L.jobBlocks = c->jobBlocks; }
+        if (use) { L.head = c->jobHead; L.jobBlocks = c->jobBlocks; if (L.pool && c->jobLongWaves) { L.waveTab = c->dJobDesc + c->jobWaveOff; L.waveBlocks = c->jobWaveBlocks; L.longFrames = c->jobLongFrames; L.longWaves = c->jobLongWaves; } }
     }
-    if (L.jobBlocks) HIPCK(c, hipStreamWaitEvent(L.st, c->jobDescReady, 0));
+    if (L.pool) if (const uint32_t S = crt_pool_streams(L.nf); const uint32_t n = forced_wave_frames(S)) {
+        L.waveFrames = n; L.waveTab = nullptr; L.waveBlocks = 0;
+        L.longWaves = n > S ? (c->tileCount - L.head) * (L.nf / n + ((L.nf % n) > S ? 1u : 0u)) : 0u;
+    }
+    if (L.jobBlocks || L.waveTab) HIPCK(c, hipStreamWaitEvent(L.st, c->jobDescReady, 0));
     if (L.wantJobCost) {                                                 // what adopt_job_costs needs to know about the measuring launch
         L.jobClk = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(c->dJobCost) + job_cost_clk_offset(c));
         c->recPool = L.pool; c->recWindows = L.windows;
-        c->recWaves = L.pool ? c->tileCount * ((L.nf + crt_pool_streams(L.nf) - 1u) / crt_pool_streams(L.nf)) : c->tileCount * L.windows;
+        const uint32_t perWave = L.pool ? std::max(crt_pool_streams(L.nf), L.waveFrames) : 64u;
+        c->recWaves = L.pool ? c->tileCount * ((L.nf + perWave - 1u) / perWave) : c->tileCount * L.windows;
         c->recResident = L.pool ? 4096u : 5120u;                            // 4 / 5 wavefronts per SIMD (render_pool_kernel / render_tiles_kernel)
     }
     return 0;
@@ -1485,7 +1596,9 @@ static hipError_t launch_render_kernels(crt_ctx* c, const Launch& L)
         }
         if (le == hipSuccess)
             le = crt_launch_render_pool(&c->hScene, L.slab, scratch, c->dCounters, c->dTileClocks, c->dTileOrder, c->tileFirst, c->tileStride, c->tileCount, (uint32_t)c->tilesX,
-                                        L.sppFirst, L.nf, L.passes, c->cfg.collectStats, L.jobBlocks ? L.head : 0u, L.wantJobCost ? c->dJobCost : nullptr, L.jobClk, st2);
+                                        L.sppFirst, L.nf, L.passes, c->cfg.collectStats, L.jobBlocks ? L.head : 0u, L.waveFrames, L.waveTab, L.waveBlocks, L.longFrames,
+                                        L.wantJobCost ? c->dJobCost : nullptr, L.jobClk, st2);
+        if (le == hipSuccess) c->lastLongWaves = L.longWaves;
         if (L.jobBlocks && le == hipSuccess) le = join(st2);
     } else if (L.jobBlocks) {
         le = launch_table(c->dJobDesc, L.jobBlocks, nullptr);
@@ -2664,6 +2777,25 @@ extern "C" int crt_debug_plan_job(const uint32_t* cost, uint32_t n, uint32_t win
     memcpy(table, t.data(), t.size() * 4); memcpy(order, c.jobOrder.data(), (size_t)n * 4); *head = h;
     return (int)t.size();
 }
+
+// tests (no GPU needed): pool_wave_plan for tile costs given in dispatch order (cost == nullptr: unknown).  wf[nr] receives the frames per wavefront of every rank in the
+// long part [0, *longFrames) of the launch (the rest of the frames: S per wavefront), start[nr] (optional) its expected start and *aim (optional) the makespan aim, both in
+// the cost's ticks; safety / guard / share <= 0: the built-in terms.  Returns the launch's wavefronts.
+extern "C" long long crt_debug_pool_wave_plan(const uint32_t* cost, uint32_t nr, uint32_t frames, double perCost, double startTicks, uint32_t resident, double safety, double guard,
+                                              double share, uint32_t* wf, uint32_t* longFrames, double* start, double* aim)
+{
+    if (!nr || !frames || !wf || !longFrames) return CRT_ERR_INVALID;
+    PoolWaveTerms tm; if (safety > 0) tm.safety = safety; if (guard > 0) tm.guard = guard; if (share > 0) tm.share = share;
+    std::vector<uint32_t> w; std::vector<double> st;
+    const uint64_t waves = pool_wave_plan(cost, nr, frames, crt_pool_streams(frames), perCost, startTicks, resident, tm, w, longFrames, &st, aim);
+    memcpy(wf, w.data(), (size_t)nr * 4);
+    if (start) memcpy(start, st.data(), (size_t)nr * 8);
+    return (long long)waves;
+}
+// tests: wavefronts of the last render_pool_kernel launch that owned more than S frames (and so refilled their slots)
+extern "C" int crt_debug_pool_long_waves(crt_ctx* c) { return c ? (int)c->lastLongWaves : -1; }
+// the built-in terms of pool_wave_plan: {poolLong, load, safety, guard, share}
+extern "C" void crt_debug_pool_wave_terms(double* out) { const PoolWaveTerms tm; out[0] = tm.poolLong; out[1] = tm.load; out[2] = tm.safety; out[3] = tm.guard; out[4] = tm.share; }
 
 // diagnostics (tools/latency_probe.py): the tile costs the last recording single-window launch left on the device (100 MHz ticks, longest wavefront per tile)
 extern "C" int crt_debug_tile_costs(crt_ctx* c, uint32_t* out)

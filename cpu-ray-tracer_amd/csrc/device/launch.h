@@ -33,8 +33,9 @@ hipError_t crt_launch_commit_frame(const void* slabWindow, uint32_t frameInWindo
 uint32_t crt_pool_streams(uint32_t frames);
 size_t crt_pool_scratch_bytes_per_window(uint32_t tileCount);
 hipError_t crt_launch_render_pool(const crt::Scene* sc, void* slab, void* facScratch, crt::Counters* counters, unsigned long long* tileClocks, const uint32_t* tileOrder, uint32_t tileFirst,
-    uint32_t tileStride, uint32_t tileCount, uint32_t tilesX, uint32_t sppFirst, uint32_t frames, uint32_t passes, int collectStats, uint32_t rankFirst, uint32_t* tileCost,
-    unsigned long long* launchClk, hipStream_t stream);
+    uint32_t tileStride, uint32_t tileCount, uint32_t tilesX, uint32_t sppFirst, uint32_t frames, uint32_t passes, int collectStats, uint32_t rankFirst, uint32_t waveFrames,
+    const uint32_t* waveTab, uint32_t tabBlocks, uint32_t longFrames, uint32_t* tileCost, unsigned long long* launchClk, hipStream_t stream);
+uint32_t crt_pool_lds_bytes(uint32_t stackDepth, uint32_t streams);
 int crt_debug_pool_stamps(unsigned long long* out, int reset);
 int crt_debug_pool_density(unsigned long long* out, int reset);
 size_t crt_debug_pool_timeline(unsigned long long* out, size_t cap);

@@ -2,8 +2,10 @@
 // FindNearest infra/scene/file_scene.cpp:170-175 / tlas_file_scene.cpp:201-206, IntersectBVH infra/bvh.cpp:224-258) as a STREAM POOL.
 //
 // The unit of work is the reference's RNG stream: one xorshift32 stream per (tile, frame), consumed serially over the tile's 256
-// pixels (renderer.cpp:120-126).  A wavefront owns S > 64 such streams of one tile (S consecutive frames) but has only 64 lanes, and
-// a stream is not tied to a lane:
+// pixels (renderer.cpp:120-126).  A wavefront has S > 64 stream SLOTS and owns a range [frame0, frame0 + n) of one tile's frames: the first min(n, S) streams
+// start in the slots, and a slot whose stream has rendered its 256 pixels takes the range's next frame (REFILL, in the END pass), so the wavefront's population stays
+// at S until the range runs out instead of falling from S to 0 over the last part of every 128 frames.  Which slot renders a stream has no influence on its samples:
+// the seed and the slab position depend on the frame alone.  A wavefront has only 64 lanes, and a stream is not tied to a lane:
 //   * a stream that is WALKING the acceleration structure is resident in a lane: its ray, nearest hit, node reference and
 //     pre-loaded node / triangle record live in that lane's registers, its traversal stack in the lane's LDS column;
 //   * a stream that WAITS for shading is parked in LDS (ray, hit, RNG state, pixel counter, the path's throughput factors —
@@ -72,9 +74,12 @@ __device__ unsigned long long g_poolStamps[16];
 #endif
 #ifdef CRT_POOL_DENS
 // diagnostic build only (-DCRT_POOL_DENS, tools/pool_density.py): how often every section of the loop runs and with how many lanes, summed over all waves
-__device__ unsigned long long g_poolDens[32];
+// [32 + 4 * k + b]: by the wave's LIVE streams (slots whose stream has not yet rendered its 256 pixels; bucket b: 0 = >= 112, 1 = 96..111, 2 = 64..95, 3 = < 64)
+//   k = 0 trips, 1 END passes, 2 BOUNCE passes, 3 wall-clock ticks (100 MHz) of the wave's life
+__device__ unsigned long long g_poolDens[48];
 #define CRT_DENS(i, v) (dens[i] += (uint32_t)(v))
 #define CRT_DENS_MASK(i, pred) (dens[i] += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(pred)))
+#define CRT_LIVE_BUCKET(n) ((n) >= 112u ? 0u : (n) >= 96u ? 1u : (n) >= 64u ? 2u : 3u)
 #else
 #define CRT_DENS(i, v)
 #define CRT_DENS_MASK(i, pred)
@@ -98,7 +103,8 @@ template <int KIND, bool COUNT, int S>
 __global__ __launch_bounds__(64, CRT_POOL_MIN_WAVES) void render_pool_kernel(const Scene sc, float4* __restrict__ slab, float* __restrict__ facScratch, Counters* __restrict__ counters,
                                                              unsigned long long* __restrict__ tileClocks, const uint32_t* __restrict__ tileOrder,
                                                              uint32_t tileFirst, uint32_t tileStride, uint32_t tileCount, uint32_t tilesX,
-                                                             uint32_t sppFirst, uint32_t frames, uint32_t passes, uint32_t groups, uint32_t rankFirst, uint32_t* __restrict__ tileCost, unsigned long long* __restrict__ launchClk)
+                                                             uint32_t sppFirst, uint32_t frames, uint32_t passes, uint32_t groups, uint32_t waveFrames, const uint32_t* __restrict__ waveTab, uint32_t tabBlocks, uint32_t longFrames,
+                                                             uint32_t rankFirst, uint32_t* __restrict__ tileCost, unsigned long long* __restrict__ launchClk)
 {
     extern __shared__ uint32_t lds[];
     const uint32_t lane = threadIdx.x;
@@ -107,13 +113,27 @@ __global__ __launch_bounds__(64, CRT_POOL_MIN_WAVES) void render_pool_kernel(con
 #endif
     const unsigned long long clk0 = (COUNT || tileCost) ? wall_clock64() : 0ull;
     if (launchClk && lane == 0) { atomicMax(&launchClk[0], ~clk0); atomicMax(&launchClk[1], clk0); }     // first / last wavefront start of a measuring job (abi.cpp adopt_job_costs)
-    // block -> (tile rank, group of S frames), rank-major: all groups of the expensive tiles (listed first by the host) are dispatched first;
-    // rankFirst > 0: the tiles before it in the order are rendered by a concurrent render_tiles_kernel launch (a split job, abi.cpp)
-    const uint32_t rank0 = blockIdx.x / groups, grp = blockIdx.x - rank0 * groups, rank = rank0 + rankFirst;
+    // block -> (tile rank, frame range), rank-major: all wavefronts of the expensive tiles (listed first by the host) are dispatched first;
+    // rankFirst > 0: the tiles before it in the order are rendered by a concurrent render_tiles_kernel launch (a split job, abi.cpp).
+    // Every tile the same range length (waveFrames, `groups` wavefronts per tile), or a plan (abi.cpp pool_wave_plan) in two parts.  The first tabBlocks wavefronts render
+    // the frames [0, longFrames) of every tile with a range length per rank: waveTab[2 r] = first block and waveTab[2 r + 1] = range length of rank rankFirst + r (a
+    // divisor of longFrames) — searched once per wavefront, on the scalar unit (the block index is wave-uniform).  The wavefronts behind them render the frames
+    // [longFrames, frames) with S frames each, `groups` per tile, rank-major again: the short wavefronts that fill the launch's end.
+    uint32_t rank0, grp, wf = waveFrames, first = 0u, limit = frames;
+    if (waveTab) {
+        if (blockIdx.x < tabBlocks) {
+            uint32_t lo = 0u, hi = tileCount - rankFirst;                         // the last rank whose first block is <= this block
+            while (hi - lo > 1u) { const uint32_t mid = (lo + hi) >> 1; if (waveTab[2u * mid] <= blockIdx.x) lo = mid; else hi = mid; }
+            rank0 = lo; grp = blockIdx.x - waveTab[2u * lo]; wf = waveTab[2u * lo + 1u]; limit = longFrames;
+        } else { const uint32_t b = blockIdx.x - tabBlocks; rank0 = b / groups; grp = b - rank0 * groups; wf = (uint32_t)S; first = longFrames; }
+    } else { rank0 = blockIdx.x / groups; grp = blockIdx.x - rank0 * groups; }
+    const uint32_t rank = rank0 + rankFirst;
     if (rank >= tileCount) return;
     const uint32_t tl = tileOrder ? tileOrder[rank] : rank;
-    const uint32_t frame0 = grp * (uint32_t)S;                                   // first frame (of the launch) of this wave's streams
-    const uint32_t nStreams = (frames - frame0 < (uint32_t)S) ? frames - frame0 : (uint32_t)S;
+    const uint32_t frame0 = first + grp * wf;                                    // first frame (of the launch) of this wave's range
+    if (frame0 >= limit) return;
+    const uint32_t nOwn = (limit - frame0 < wf) ? limit - frame0 : wf;           // frames of the range
+    const uint32_t nStreams = nOwn < (uint32_t)S ? nOwn : (uint32_t)S;           // ... of which this many start now, one per slot
     const uint32_t tile = tileFirst + tl * tileStride;
     const uint32_t tx = tile % tilesX, ty = tile / tilesX;
     const char* __restrict__ geom = sc.geom;
@@ -129,13 +149,15 @@ __global__ __launch_bounds__(64, CRT_POOL_MIN_WAVES) void render_pool_kernel(con
     float* stf = reinterpret_cast<float*>(st);
     uint8_t* qEnd = reinterpret_cast<uint8_t*>(st + F_COUNT * S);
     uint8_t* qBnc = qEnd + 128, * qRdy = qEnd + 256;
+    uint16_t* slotFrame = reinterpret_cast<uint16_t*>(qEnd + 384);               // S > 64 only: frame (relative to frame0) of the stream in each slot
     auto stk_top = [&](uint32_t at) -> uint32_t { return *reinterpret_cast<const uint16_t*>(ldsB + at); };
     auto stk_put = [&](uint32_t at, uint32_t v) { *reinterpret_cast<uint16_t*>(ldsB + at) = (uint16_t)v; };
 
     Cnt cn; cn.rays = cn.primary = cn.interior = cn.leaf = cn.tri = cn.tlas = cn.visits = cn.meshhits = 0;
     uint32_t trips = 0;
 #ifdef CRT_POOL_DENS
-    uint32_t dens[32]; for (int i = 0; i < 32; i++) dens[i] = 0;
+    uint32_t dens[48]; for (int i = 0; i < 48; i++) dens[i] = 0;
+    uint32_t live = nStreams; unsigned long long liveClk = wall_clock64();
 #endif
     const uint32_t items = 256u * passes;                                        // (pixel, pass) pairs in stream order
     const uint32_t rowLen = 64u * passes;                                        // float4 per pixel row of the slab
@@ -146,7 +168,9 @@ __global__ __launch_bounds__(64, CRT_POOL_MIN_WAVES) void render_pool_kernel(con
         st[F_SEED * S + s] = init_seed(tx + ty * (uint32_t)sc.W + (sppFirst + (frame0 + s) * passes) * 1799u);   // renderer.cpp:120
         st[F_META * S + s] = kMetaFresh;
         qEnd[s] = (uint8_t)s;
+        if (S > 64) slotFrame[s] = (uint16_t)s;
     }
+    uint32_t nextFrame = nStreams;                                               // the range's next frame (relative to frame0) without a slot (wave-uniform; only grows)
     uint32_t endH = 0, endT = nStreams, bncH = 0, bncT = 0, rdyH = 0, rdyT = 0;  // queue heads / tails (wave-uniform)
 
     // The stream resident in this lane (if any: mRes).  Invariant at the top of a trip: a resident stream is walking (cur != done) — streams whose walk ended
@@ -367,6 +391,9 @@ __global__ __launch_bounds__(64, CRT_POOL_MIN_WAVES) void render_pool_kernel(con
         }
         if (COUNT) trips++;
         CRT_DENS(0, 1);
+#ifdef CRT_POOL_DENS
+        dens[32u + CRT_LIVE_BUCKET(live)]++;
+#endif
         // ---------------- C. swap in: free lanes take the next READY streams; E. the record loads (consumed by the next trip's walk) ----
         {
             const uint32_t nRdy = rdyT - rdyH;
@@ -429,6 +456,9 @@ __global__ __launch_bounds__(64, CRT_POOL_MIN_WAVES) void render_pool_kernel(con
                 const int depth = (int)((meta >> kMetaDepthShift) & 7u);
                 uint32_t item = meta & kMetaItemMask;
                 const bool ended = act && !first, miss = ended && obj == -1;
+#ifdef CRT_POOL_DENS
+                dens[36u + CRT_LIVE_BUCKET(live)]++;
+#endif
                 CRT_DENS(9, 1); CRT_DENS(10, n); CRT_DENS_MASK(11, miss); CRT_DENS_MASK(13, act && first); CRT_DENS_MASK(25, ended && depth > 0); CRT_DENS_MASK(26, ended && depth > 1); CRT_DENS_MASK(27, ended && depth > 2);
                 if (ended && obj >= 2) cn.meshhits++;
                 // the path's throughput factors: fetched now (device-scope loads: they were written by this wave's BOUNCE passes, possibly from
@@ -455,11 +485,32 @@ __global__ __launch_bounds__(64, CRT_POOL_MIN_WAVES) void render_pool_kernel(con
                 if (ended) {
                     uint32_t pix = item, pass = 0;
                     if (passes != 1u) { pix = item / passes; pass = item - pix * passes; }
-                    const uint32_t fr = frame0 + s;                                // frame of the launch -> (64-frame window, sample row position)
+                    const uint32_t fr = frame0 + (S > 64 ? (uint32_t)slotFrame[s] : s);   // frame of the launch -> (64-frame window, sample row position)
                     sampleAt = (((size_t)(fr >> 6) * tileCount + tl) * 256u + pix) * rowLen + ((fr & 63u) * passes + pass);
                     item++;
                     gen = item < items;                                            // else: the stream has rendered its 256 pixels
                 }
+                // REFILL: the slots whose stream has just rendered its last pixel take the range's next frames (none left: the slot stays empty and the population
+                // falls).  The finished path's sample position is computed above, from the old frame; its radiance is stored below as for every ended path.
+                if (S > 64) if (nextFrame < nOwn) {
+                    const uint64_t mDone = __builtin_amdgcn_ballot_w64(ended) & ~__builtin_amdgcn_ballot_w64(gen);
+                    if (mDone != 0ull) {
+                        const uint32_t f = nextFrame + rank_in(mDone);
+                        const uint64_t mTake = mDone & __builtin_amdgcn_ballot_w64(f < nOwn);
+                        if (lane_in(mTake)) {
+                            slotFrame[s] = (uint16_t)f;
+                            seed = init_seed(tx + ty * (uint32_t)sc.W + (sppFirst + (frame0 + f) * passes) * 1799u);   // renderer.cpp:120, as at the wave's start
+                            item = 0u; gen = true;
+                        }
+                        nextFrame += (uint32_t)__popcll(mTake);
+                    }
+                }
+#ifdef CRT_POOL_DENS
+                {
+                    const uint32_t gone = (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(ended) & ~__builtin_amdgcn_ballot_w64(gen));
+                    if (gone) { const unsigned long long now = wall_clock64(); dens[44u + CRT_LIVE_BUCKET(live)] += (uint32_t)(now - liveClk); liveClk = now; live -= gone; }
+                }
+#endif
                 // the camera (camPos, topLeft, topRight, bottomLeft: 12 floats of the Scene block) is read here, not held in registers across the loop
                 const kernarg_f cam = scene_floats(offsetof(Scene, camPos));
                 const f3 camPos = mk3(cam[0], cam[1], cam[2]);
@@ -512,6 +563,9 @@ __global__ __launch_bounds__(64, CRT_POOL_MIN_WAVES) void render_pool_kernel(con
                     seed = st[F_SEED * S + s]; meta = st[F_META * S + s]; obj = (int)(meta >> kMetaObjShift) - 1;
                 }
                 const bool mesh = act && obj >= 2;
+#ifdef CRT_POOL_DENS
+                dens[40u + CRT_LIVE_BUCKET(live)]++;
+#endif
                 CRT_DENS(14, 1); CRT_DENS(15, n); CRT_DENS_MASK(16, mesh);
                 rec4 s0 = {0, 0, 0, 0}, s1 = s0, s2 = s0, s3 = s0;                 // the hit triangle's ShadeTri
                 if (mesh) { const uint32_t so = sc.shadeOff + tri * 64u; s0 = ldg(geom, so); s1 = ldg(geom, so + 16u); s2 = ldg(geom, so + 32u); s3 = ldg(geom, so + 48u); cn.meshhits++; }
@@ -626,18 +680,19 @@ __global__ __launch_bounds__(64, CRT_POOL_MIN_WAVES) void render_pool_kernel(con
     if (lane == 0) for (int i = 0; i < 12; i++) atomicAdd(&g_poolStamps[i], pst[i]);
 #endif
 #ifdef CRT_POOL_DENS
-    if (lane == 0) for (int i = 0; i < 32; i++) if (dens[i]) atomicAdd(&g_poolDens[i], (unsigned long long)dens[i]);
+    dens[44u + CRT_LIVE_BUCKET(live)] += (uint32_t)(wall_clock64() - liveClk);
+    if (lane == 0) for (int i = 0; i < 48; i++) if (dens[i]) atomicAdd(&g_poolDens[i], (unsigned long long)dens[i]);
 #endif
 
 #ifdef CRT_POOL_TIMELINE
     if (lane == 0 && g_poolTimeline) { uint32_t hw; asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw)); g_poolTimeline[3 * (size_t)blockIdx.x] = tl0; g_poolTimeline[3 * (size_t)blockIdx.x + 1] = wall_clock64(); g_poolTimeline[3 * (size_t)blockIdx.x + 2] = hw; }
 #endif
     // what this tile costs (100 MHz ticks): this wavefront's duration per 64 streams (close to what the tile's one-stream-per-lane wavefront takes on an idle chip);
-    // full groups only — a wavefront with fewer streams than S runs them less densely.  The host orders and plans later jobs with it (abi.cpp plan_job).
-    if (tileCost && lane == 0 && nStreams == (uint32_t)S) atomicMax(&tileCost[tl], (uint32_t)((wall_clock64() - clk0) * 64ull / (uint32_t)S));
+    // wavefronts of exactly S frames only — one with fewer runs them less densely, one with more (refill) more densely.  The host orders and plans later jobs with it (abi.cpp plan_job).
+    if (tileCost && lane == 0 && nOwn == (uint32_t)S) atomicMax(&tileCost[tl], (uint32_t)((wall_clock64() - clk0) * 64ull / (uint32_t)S));
     // ... and how much of this wavefront ran after the launch's last wavefront had started (the launch's drain: abi.cpp adopt_job_costs)
     if (launchClk && lane == 0) { const unsigned long long now = wall_clock64(), last = __hip_atomic_load(&launchClk[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), from = last > clk0 ? last : clk0; if (now > from) atomicAdd(&launchClk[2], now - from); }
-    if (COUNT && tileClocks && lane == 0 && groups == 1u) {                     // instrumentation: per-tile wall time + loop trips (one group per tile only)
+    if (COUNT && tileClocks && lane == 0 && nOwn == frames) {                   // instrumentation: per-tile wall time + loop trips (one wavefront per tile only)
         tileClocks[2 * tl] = wall_clock64() - clk0;        // 100 MHz constant clock
         tileClocks[2 * tl + 1] = trips;
     }
@@ -661,7 +716,8 @@ extern "C" uint32_t crt_pool_streams(uint32_t frames) { return frames > 64u ? (u
 #define CRT_POOL_EXTRA_LDS 0       // occupancy experiments only: unused LDS bytes per wavefront
 #endif
 // LDS of one wavefront: traversal stacks ((stackDepth + 1 dummy) two-byte entries per lane) + parked stream state + the three one-byte ring queues
-extern "C" uint32_t crt_pool_lds_bytes(uint32_t stackDepth, uint32_t streams) { return (stackDepth + 1u) * 64u * 2u + crt::F_COUNT * streams * 4u + 3u * 128u + (uint32_t)CRT_POOL_EXTRA_LDS; }
+// + (more slots than lanes: wavefronts that may refill) the two-byte frame of every slot.  128 slots at a stack depth of <= 17: <= 10 240 bytes, 16 wavefronts per CU.
+extern "C" uint32_t crt_pool_lds_bytes(uint32_t stackDepth, uint32_t streams) { return (stackDepth + 1u) * 64u * 2u + crt::F_COUNT * streams * 4u + 3u * 128u + (streams > 64u ? 2u * streams : 0u) + (uint32_t)CRT_POOL_EXTRA_LDS; }
 // bytes of throughput-factor scratch a launch of `windows` 64-frame windows needs behind its sample slab (15 floats per stream; a wave's
 // group of streams may reach past the last window, hence 128 stream slots per window)
 extern "C" size_t crt_pool_scratch_bytes_per_window(uint32_t tileCount) { return (size_t)tileCount * 128u * 15u * 4u; }
@@ -675,10 +731,10 @@ extern "C" int crt_debug_pool_stamps(unsigned long long* out, int reset)       /
 }
 #endif
 #ifdef CRT_POOL_DENS
-extern "C" int crt_debug_pool_density(unsigned long long* out, int reset)      // after a sync: the 32 section counters summed over every pool wave since the last reset
+extern "C" int crt_debug_pool_density(unsigned long long* out, int reset)      // after a sync: the 48 section counters summed over every pool wave since the last reset
 {
-    if (out && hipMemcpyFromSymbol(out, HIP_SYMBOL(crt::g_poolDens), 256) != hipSuccess) return -1;
-    if (reset) { unsigned long long z[32] = {}; if (hipMemcpyToSymbol(HIP_SYMBOL(crt::g_poolDens), z, 256) != hipSuccess) return -1; }
+    if (out && hipMemcpyFromSymbol(out, HIP_SYMBOL(crt::g_poolDens), 384) != hipSuccess) return -1;
+    if (reset) { unsigned long long z[48] = {}; if (hipMemcpyToSymbol(HIP_SYMBOL(crt::g_poolDens), z, 384) != hipSuccess) return -1; }
     return 0;
 }
 #endif
@@ -693,22 +749,29 @@ extern "C" size_t crt_debug_pool_timeline(unsigned long long* out, size_t cap)  
 #endif
 extern "C" hipError_t crt_launch_render_pool(const crt::Scene* sc, void* slab, void* facScratch, crt::Counters* counters, unsigned long long* tileClocks, const uint32_t* tileOrder,
                                              uint32_t tileFirst, uint32_t tileStride, uint32_t tileCount, uint32_t tilesX, uint32_t sppFirst,
-                                             uint32_t frames, uint32_t passes, int collectStats, uint32_t rankFirst, uint32_t* tileCost, unsigned long long* launchClk, hipStream_t stream)
+                                             uint32_t frames, uint32_t passes, int collectStats, uint32_t rankFirst, uint32_t waveFrames, const uint32_t* waveTab, uint32_t tabBlocks, uint32_t longFrames,
+                                             uint32_t* tileCost, unsigned long long* launchClk, hipStream_t stream)
 {
     if (tileCount == 0 || frames == 0) return hipSuccess;
     if (!sc->ref16ok) return hipErrorInvalidValue;                              // the host launches render_tiles_kernel for such scenes
     const uint32_t S = crt_pool_streams(frames);
-    const uint32_t groups = (frames + S - 1u) / S;
-    if ((unsigned long long)tileCount * groups > 0x7fffffffull) return hipErrorInvalidValue;
+    // frames per wavefront: S (waveFrames == 0), or a multiple of S, at most 0xff80 (the slots' 16-bit frames) — one for all tiles; or per rank from waveTab for the
+    // frames [0, longFrames) (tabBlocks wavefronts in all) and S for the rest
+    const uint32_t wf = (S == 64u || waveFrames < S) ? S : waveFrames;
+    if (wf % S != 0u || wf > 0xff80u) return hipErrorInvalidValue;
+    if (S == 64u) waveTab = nullptr;
+    if (waveTab && (tabBlocks == 0u || longFrames == 0u || longFrames > frames)) return hipErrorInvalidValue;
+    const uint32_t groups = waveTab ? (frames - longFrames + S - 1u) / S : (frames + wf - 1u) / wf;
+    if ((unsigned long long)tileCount * ((frames + S - 1u) / S) > 0x7fffffffull) return hipErrorInvalidValue;
     if (rankFirst >= tileCount) return hipSuccess;
-    dim3 grid((tileCount - rankFirst) * groups), block(64);
+    dim3 grid(waveTab ? tabBlocks + (tileCount - rankFirst) * groups : (tileCount - rankFirst) * groups), block(64);
 #ifdef CRT_POOL_TIMELINE
     { static unsigned long long* buf = nullptr; static size_t cap = 0;
       if (cap < (size_t)grid.x) { if (buf) (void)hipFree(buf); (void)hipMalloc((void**)&buf, (size_t)grid.x * 24); cap = grid.x; (void)hipMemcpyToSymbol(HIP_SYMBOL(crt::g_poolTimeline), &buf, sizeof(buf)); }
       (void)hipMemsetAsync(buf, 0, (size_t)grid.x * 24, stream); g_timelineHost = buf; g_timelineCount = grid.x; }
 #endif
     const uint32_t ldsBytes = crt_pool_lds_bytes(sc->stackDepth, S);
-#define CRT_LAUNCH(K, C, SS) hipLaunchKernelGGL((crt::render_pool_kernel<K, C, SS>), grid, block, ldsBytes, stream, *sc, (float4*)slab, (float*)facScratch, counters, tileClocks, tileOrder, tileFirst, tileStride, tileCount, tilesX, sppFirst, frames, passes, groups, rankFirst, tileCost, launchClk)
+#define CRT_LAUNCH(K, C, SS) hipLaunchKernelGGL((crt::render_pool_kernel<K, C, SS>), grid, block, ldsBytes, stream, *sc, (float4*)slab, (float*)facScratch, counters, tileClocks, tileOrder, tileFirst, tileStride, tileCount, tilesX, sppFirst, frames, passes, groups, wf, waveTab, tabBlocks, longFrames, rankFirst, tileCost, launchClk)
 #define CRT_LAUNCH_S(K, C) do { if (S == 64u) CRT_LAUNCH(K, C, 64); else CRT_LAUNCH(K, C, CRT_POOL_STREAMS); } while (0)
     if (sc->kind == 0) { if (collectStats) CRT_LAUNCH_S(0, true); else CRT_LAUNCH_S(0, false); }
     else { if (collectStats) CRT_LAUNCH_S(1, true); else CRT_LAUNCH_S(1, false); }

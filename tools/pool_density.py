@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Diagnostic (-DCRT_POOL_DENS build, CRT_LIB_PATH=...): how often every section of render_pool_kernel's loop runs and with how many of
-its 64 lanes, for one pool-only job (default 32 windows of the bunny scene at 1280x720).  Prints one JSON line.
+its 64 lanes, for one pool-only job (default 32 windows of the bunny scene at 1280x720), and the shares of trips, shading passes and wave time by the number of
+LIVE streams of the wave (slots whose stream has not yet rendered its 256 pixels): what the ramp-down at the end of a wavefront's frame range costs, with or without
+refill (CRT_POOL_WAVE_FRAMES=<n>; 128 = no refill).  Prints one JSON line.
     python tools/pool_density.py [scene.xml kind [windows [W H]]]"""
 import ctypes as C, importlib.util, json, os, sys, time
 os.environ.setdefault("CRT_ENABLE_DEBUG_HOOKS", "1")      # the library reads its diagnostic environment switches only for processes that opt in
@@ -17,7 +19,7 @@ sc = crt.HostScene(os.path.join(A, "scenes", xml), kind, A)
 ctx = crt.Context(W, H); sc.upload(ctx); ctx.reserve(64 * K, 1)
 ctx.render(1, 64 * K, 1); ctx.sync(); ctx.timing()
 L = crt.lib()
-buf = (C.c_uint64 * 32)()
+buf = (C.c_uint64 * 48)()
 has = hasattr(L, "crt_debug_pool_density")
 if has: L.crt_debug_pool_density(buf, 1)
 ctx.reset_counters(); ctx.clear(); ctx.sync()
@@ -39,4 +41,8 @@ if has:
         "bounce_passes_per_window_M": round(d[14] / K / 1e6, 3), "bounce_lanes_per_pass": per(15, 14), "bounce_mesh_lanes_per_pass": per(16, 14),
         "rejection_wave_iterations_per_pass": per(17, 14), "rejection_lanes_per_iteration": per(18, 17),
         "new_ray_lanes_M_per_window": round(d[20] / K / 1e6, 3), "new_ray_walk_fraction": per(19, 20), "raw": d}
+    share = lambda k: [round(d[32 + 4 * k + b] / max(1, sum(d[32 + 4 * k:36 + 4 * k])), 4) for b in range(4)]
+    out["wave_frames_hook"] = os.environ.get("CRT_POOL_WAVE_FRAMES")
+    out["live_streams"] = {"buckets": [">=112", "96-111", "64-95", "<64"], "trips": share(0), "end_passes": share(1), "bounce_passes": share(2), "wave_time": share(3),
+                           "trips_below_96": round(sum(share(0)[2:]), 4), "wave_time_below_96": round(sum(share(3)[2:]), 4)}
 print(json.dumps(out))
