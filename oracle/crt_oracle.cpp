@@ -15,7 +15,8 @@
  *   - PARITY UNPINNED (restated line by line from the cited reference lines, no executable reference
  *     and no reference-held golden vector exists: the reference has no tests and is MSVC/Windows-only):
  *       Renderer::Sample/ProcessTile/Tick, RNG, Quad/Plane, TLAS build + traversal,
- *       BLAS instance transforms, GetHitInfo, skydome lookup, scene assembly.
+ *       BLAS instance transforms, GetHitInfo, skydome lookup, scene assembly,
+ *       the two-level KD-tree / grid walk (orc_set_blas_accel; held bit for bit to the independent numpy restatement tests/tlas_alt_restate.py).
  *
  * Conventions pinned here (reference leaves them to the compiler; DESIGN.md "pinned choices"):
  *   - argument evaluation order = MSVC's right-to-left: in GetPrimaryRay(x+rnd, y+rnd) the FIRST draw is the
@@ -944,6 +945,9 @@ struct orc_ctx {
 
     void (*accelFn)(void*, Ray&) = nullptr;     // (set by orc_set_render_accel, where KdTree / UGrid are defined)
     int accel = 0; void* accelH = nullptr;      // orc_set_render_accel: 0 = BVH / TLAS, 1 = KD-tree, 2 = grid (a FileScene's `acc`; handle of orc_kd_build / orc_grid_build)
+    // TLASFileScene built with TLAS_USE_KDTree / TLAS_USE_Grid (tlas_file_scene.h:11-13): orc_set_blas_accel, one orc_kd_build / orc_grid_build handle per BLAS
+    int blasAccel = 0; std::vector<void*> blasAccelH;
+    void (*blasAccelFn)(const orc_ctx*, Ray&) = nullptr;
 
     ~orc_ctx() { for (Bvh* b : bvhs) delete b; }
 
@@ -951,6 +955,7 @@ struct orc_ctx {
     void accel_intersect(Ray& r, Counters& cn) const   // acc.Intersect(ray): file_scene.cpp:174, 183
     {
         if (kind == 0 && accel != 0) accelFn(accelH, r);
+        else if (kind == 1 && blasAccel != 0) blasAccelFn(this, r);   // tlas.Intersect(ray) of the KD-tree / grid variant, tlas_file_scene.cpp:205, 214
         else if (kind == 0) bvhs[0]->traverse(r, cn); else tlas.traverse(r, cn);
     }
     void find_nearest(Ray& r, Counters& cn) const // file_scene.cpp:170-175, tlas_file_scene.cpp:201-206; primitive_scene.cpp:92-175
@@ -1304,6 +1309,7 @@ int orc_bvh_move_and_refit(orc_ctx* c, int i, const float* positions, uint32_t t
         memcpy(b->tris[t].vertex2, positions + 9 * (size_t)t + 6, 12);
     }
     b->refit();
+    c->blasAccel = 0; c->blasAccelH.clear();                    // the reference has no Refit for BLASKDTree / BLASGrid: a refitted scene is the TLAS-BVH one again
     if (c->kind == 1) { b->set_transform(b->T); if (!c->tlas.build(c->err)) return -1; }
     return 0;
 }
@@ -1618,7 +1624,7 @@ int orc_png_unfilter(const uint8_t* raw, uint8_t* out, int stride, int h, int fb
 // ------------------------------------------------------------------------------------------------
 namespace {
 // Möller–Trumbore of kdtree.cpp:122-141 / grid.cpp:63-82 (the same arithmetic as bvh.cpp:203-222)
-static inline void alt_hit_tri(Ray& r, const Tri& tri, uint ti)
+static inline void alt_hit_tri(Ray& r, const Tri& tri, uint ti, int objIdx)   // objIdx: tri.objIdx (KDTree / Grid) or the BLAS's own (blas_kdtree.cpp:333, blas_grid.cpp:161)
 {
     V3 v0 = ld3(tri.vertex0);
     V3 e1 = ld3(tri.vertex1) - v0, e2 = ld3(tri.vertex2) - v0;
@@ -1633,7 +1639,7 @@ static inline void alt_hit_tri(Ray& r, const Tri& tri, uint ti)
     float v = f * dot(r.D, q);
     if (v < 0 || u + v > 1) return;
     float t = f * dot(e2, q);
-    if (t > 0.0001f) { if (t < r.t) { r.t = smin_(r.t, t); r.objIdx = tri.objIdx; r.triIdx = (int)ti; r.bu = u; r.bv = v; } }
+    if (t > 0.0001f) { if (t < r.t) { r.t = smin_(r.t, t); r.objIdx = objIdx; r.triIdx = (int)ti; r.bu = u; r.bv = v; } }
 }
 static inline bool alt_hit_aabb(const Ray& r, V3 lo, V3 hi, float& tminOut, float& tmaxOut)   // kdtree.cpp:109-120, grid.cpp:52-61
 {
@@ -1700,7 +1706,7 @@ struct KdTree {
         float tmin, tmax;
         r.traversed++;
         if (!alt_hit_aabb(r, ld3(n.aabbMin), ld3(n.aabbMax), tmin, tmax)) return;
-        if (n.left < 0) { for (uint i = 0; i < n.triCount; i++) { uint ti = refs[n.firstTri + i]; alt_hit_tri(r, tris[ti], ti); r.tested++; } return; }
+        if (n.left < 0) { for (uint i = 0; i < n.triCount; i++) { uint ti = refs[n.firstTri + i]; alt_hit_tri(r, tris[ti], ti, tris[ti].objIdx); r.tested++; } return; }
         const int axis = n.splitAxis;
         const float splitPos = n.aabbMin[axis] + n.splitDistance;
         const float t = (splitPos - comp(r.O, axis)) / comp(r.D, axis);
@@ -1751,7 +1757,7 @@ struct UGrid {
         for (;;) {
             r.traversed++;
             const uint32_t index = (uint32_t)c[0] + (uint32_t)c[1] * res[0] + (uint32_t)c[2] * res[0] * res[1];
-            for (uint32_t k = cellStart[index]; k < cellStart[index + 1]; k++) { r.tested++; alt_hit_tri(r, tris[refs[k]], (uint)refs[k]); }
+            for (uint32_t k = cellStart[index]; k < cellStart[index + 1]; k++) { r.tested++; alt_hit_tri(r, tris[refs[k]], (uint)refs[k], tris[refs[k]].objIdx); }
             const uint k = ((next[0] < next[1]) << 2) + ((next[0] < next[2]) << 1) + ((next[1] < next[2]));
             static const uint8_t map[8] = {2, 1, 2, 1, 2, 2, 0, 0};
             const uint8_t axis = map[k];
@@ -1769,6 +1775,137 @@ int orc_set_render_accel(orc_ctx* c, int kind, void* h)      // kind 1: h = orc_
     if (!c || kind < 0 || kind > 2 || (kind != 0 && (!h || c->kind != 0))) return -1;
     c->accel = kind; c->accelH = kind ? h : nullptr;
     c->accelFn = kind == 1 ? +[](void* p, Ray& r) { ((KdTree*)p)->intersect(r, 0); } : +[](void* p, Ray& r) { ((UGrid*)p)->intersect(r); };
+    return 0;
+}
+// ------------------------------------------------------------------------------------------------
+// TLASFileScene built with TLAS_USE_KDTree / TLAS_USE_Grid (infra/scene/tlas_file_scene.h:11-13, tlas_file_scene.cpp:40-90): TLASKDTree over BLASKDTree, TLASGrid over
+// BLASGrid.  The per-BLAS structures are the KdTree / UGrid above over the BLAS's object-space triangles (BLASKDTree::Build / Subdivide, blas_kdtree.cpp:82-301, and
+// BLASGrid::Build, blas_grid.cpp:82-131, are kdtree.cpp's / grid.cpp's builds); their root box is the BVH's root box, so SetTransform (blas_kdtree.cpp:407-418,
+// blas_grid.cpp's twin) gives the world bounds the BVH variant has and TLASKDTree::Build / TLASGrid::Build (tlas_kdtree.cpp:17-70) the node array of Tlas::build.
+// What differs from the BVH variant is the walk inside an instance, restated here.  PARITY UNPINNED against the reference (no executable two-level reference);
+// pinned against the independent numpy restatement tests/tlas_alt_restate.py (tests/test_tlas_alt_cpu.py).
+// ------------------------------------------------------------------------------------------------
+namespace {
+// BLASKDTree::IntersectKDTree, blas_kdtree.cpp:337-400.  Unlike KDTree::Intersect (kdtree.cpp:143-202) the early return after the near child asks that the nearest
+// hit so far is THIS instance's ("rule 1", :377, :396): a hit carried in from the floor, the light or another instance does not end the walk.
+static void blas_kd_walk(const KdTree& k, int objIdx, Ray& r, int ni)
+{
+    const orc_kd_node& n = k.nodes[ni];
+    float tmin, tmax;
+    r.traversed++;                                                                                       // :341
+    if (!alt_hit_aabb(r, ld3(n.aabbMin), ld3(n.aabbMax), tmin, tmax)) return;                            // :342 (IntersectAABB :303-314)
+    if (n.left < 0) {                                                                                    // :343-353
+        for (uint i = 0; i < n.triCount; i++) { const uint ti = k.refs[n.firstTri + i]; alt_hit_tri(r, k.tris[ti], ti, objIdx); r.tested++; }
+        return;
+    }
+    const int axis = n.splitAxis;
+    const float splitPos = n.aabbMin[axis] + n.splitDistance;                                            // :356
+    const float t = (splitPos - comp(r.O, axis)) / comp(r.D, axis);                                      // :357
+    const bool pos = comp(r.D, axis) > 0;                                                                // :362
+    const int nearC = pos ? n.left : n.right, farC = pos ? n.right : n.left;
+    if ((double)t < (double)tmin + 0.001) blas_kd_walk(k, objIdx, r, farC);                              // :365, :384 — `tmin + 0.001` is a double expression
+    else if ((double)t > (double)tmax - 0.001) blas_kd_walk(k, objIdx, r, nearC);                        // :370, :389
+    else {
+        blas_kd_walk(k, objIdx, r, nearC);
+        if (r.objIdx == objIdx && r.t < t) return;                                                       // :377, :396
+        blas_kd_walk(k, objIdx, r, farC);
+    }
+}
+// BLASGrid::IntersectGrid, blas_grid.cpp:172-231 (GRID_MAILBOXING is not defined: every reference of a cell is tested)
+static void blas_grid_walk(const UGrid& g, int objIdx, Ray& r)
+{
+    float tmn, tmx;
+    if (!alt_hit_aabb(r, g.bounds.lo, g.bounds.hi, tmn, tmx)) return;                                    // :175 (IntersectAABB :133-142)
+    int exitc[3], step[3], cell[3]; float deltaT[3], nextT[3];
+    for (int i = 0; i < 3; ++i) {                                                                        // :180-198
+        const float rayOrigCell = comp(r.O, i) - comp(g.bounds.lo, i), cs = comp(g.cell, i);
+        cell[i] = UGrid::clampi((int)floorf(rayOrigCell / cs), 0, g.res[i] - 1);
+        if (comp(r.D, i) < 0) { deltaT[i] = -cs * comp(r.rD, i); nextT[i] = (cell[i] * cs - rayOrigCell) * comp(r.rD, i); exitc[i] = -1; step[i] = -1; }
+        else { deltaT[i] = cs * comp(r.rD, i); nextT[i] = ((cell[i] + 1) * cs - rayOrigCell) * comp(r.rD, i); exitc[i] = g.res[i]; step[i] = 1; }
+    }
+    static const uint8_t map[8] = {2, 1, 2, 1, 2, 2, 0, 0};                                              // :223
+    for (;;) {                                                                                           // :200-230
+        r.traversed++;
+        const uint32_t index = (uint32_t)cell[0] + (uint32_t)cell[1] * g.res[0] + (uint32_t)cell[2] * g.res[0] * g.res[1];
+        for (uint32_t q = g.cellStart[index]; q < g.cellStart[index + 1]; q++) { r.tested++; alt_hit_tri(r, g.tris[g.refs[q]], (uint)g.refs[q], objIdx); }
+        const uint sel = ((nextT[0] < nextT[1]) << 2) + ((nextT[0] < nextT[2]) << 1) + ((nextT[1] < nextT[2]));
+        const int axis = map[sel];
+        if (r.t < nextT[axis]) break;
+        cell[axis] += step[axis];
+        if (cell[axis] == exitc[axis]) break;
+        nextT[axis] += deltaT[axis];
+    }
+}
+// BLASKDTree::Intersect (blas_kdtree.cpp:420-433) / BLASGrid::Intersect (blas_grid.cpp:233-248): Ray(const Ray&) carries t, objIdx, triIdx, the barycentrics,
+// traversed and inside over (ray.h:10-14) — so rule 1 and every `t < ray.t` see the hits of the instances before this one; O, D, rD come back afterwards
+static void blas_alt_intersect(const orc_ctx* c, int accel, int i, Ray& r)
+{
+    const Bvh* b = c->bvhs[(size_t)i];
+    Ray tr = r;
+    tr.tested = 0;                                                                                       // the copy constructor leaves `tested` at its default
+    tr.O = transform_position_sse(r.O, b->invT);
+    tr.D = transform_vector_sse(r.D, b->invT);
+    tr.rD = v3(1 / tr.D.x, 1 / tr.D.y, 1 / tr.D.z);
+    if (accel == 1) blas_kd_walk(*(const KdTree*)c->blasAccelH[(size_t)i], b->blasObjIdx, tr, 0);
+    else blas_grid_walk(*(const UGrid*)c->blasAccelH[(size_t)i], b->blasObjIdx, tr);
+    tr.O = r.O; tr.D = r.D; tr.rD = r.rD;
+    const int testedTotal = r.tested + tr.tested;
+    r = tr;
+    r.tested = testedTotal;                // the per-query total, as Bvh::intersect_instance keeps it (documented deviation from the reference's reset)
+}
+// TLASKDTree::Intersect (tlas_kdtree.cpp:83-111) / TLASGrid::Intersect: TLASBVH::Intersect's loop (tlas_bvh.cpp:83-111) over the same node array
+static void tlas_alt_walk(const orc_ctx* c, Ray& r)
+{
+    const std::vector<orc_tlas_node>& nodes = c->tlas.nodes;
+    uint node = 0, stack[64]; uint sp = 0;
+    while (1) {
+        r.traversed++;
+        const orc_tlas_node& n = nodes[node];
+        if (n.leftRight == 0) {
+            blas_alt_intersect(c, c->blasAccel, (int)n.BLAS, r);
+            if (sp == 0) break; else node = stack[--sp];
+            continue;
+        }
+        uint c1 = n.leftRight & 0xffff, c2 = n.leftRight >> 16;
+        float d1 = Bvh::hit_aabb(r, nodes[c1].aabbMin, nodes[c1].aabbMax);                               // IntersectAABB, tlas_kdtree.cpp:72-81
+        float d2 = Bvh::hit_aabb(r, nodes[c2].aabbMin, nodes[c2].aabbMax);
+        if (d1 > d2) { float td = d1; d1 = d2; d2 = td; uint tc = c1; c1 = c2; c2 = tc; }
+        if (d1 == 1e30f) { if (sp == 0) break; else node = stack[--sp]; }
+        else { node = c1; if (d2 != 1e30f) stack[sp++] = c2; }
+    }
+}
+} // namespace
+
+// kind 1: handles[i] = orc_kd_build(..), 2: orc_grid_build(..) over BLAS i's triangle array (orc_bvh_copy order), n = orc_bvh_count; 0: the TLAS-BVH again.
+// The handles stay the caller's and must outlive the set.  The statistics counters count rays and mesh hits through a set, no structure steps.
+int orc_set_blas_accel(orc_ctx* c, int kind, void* const* handles, int n)
+{
+    if (!c || kind < 0 || kind > 2) return -1;
+    if (kind == 0) { c->blasAccel = 0; c->blasAccelH.clear(); return 0; }
+    if (!c->built || c->kind != 1 || !handles || n != (int)c->bvhs.size()) { c->err = "orc_set_blas_accel: a built TLAS scene and one handle per BLAS"; return -1; }
+    for (int i = 0; i < n; i++) {
+        if (!handles[i]) { c->err = "orc_set_blas_accel: null handle"; return -1; }
+        const size_t have = kind == 1 ? ((KdTree*)handles[i])->tris.size() : ((UGrid*)handles[i])->tris.size();
+        if (have != c->bvhs[(size_t)i]->tris.size()) { c->err = "orc_set_blas_accel: a structure over another triangle array"; return -1; }
+    }
+    c->blasAccelH.assign(handles, handles + n);
+    c->blasAccel = kind;
+    c->blasAccelFn = &tlas_alt_walk;
+    return 0;
+}
+// FileScene::IsOccluded / TLASFileScene::IsOccluded (file_scene.cpp:177-187, tlas_file_scene.cpp:208-218) for Ray(O, D, t): the light quad bounded by t, then the
+// structure with shadow.t = 1e34f; the floor is skipped
+int orc_is_occluded(orc_ctx* c, const float* O, const float* D, const float* t, int32_t* out, size_t n)
+{
+    if (!c || !c->built || c->kind == 2) { if (c) c->err = "orc_is_occluded: a built FileScene / TLASFileScene"; return -1; }
+    Counters cn;
+    for (size_t i = 0; i < n; i++) {
+        Ray r = make_ray(ld3(O + 3 * i), ld3(D + 3 * i)); r.t = t[i];
+        if (c->light.occluded(r)) { out[i] = 1; continue; }
+        Ray sh = r; sh.t = 1e34f;
+        c->accel_intersect(sh, cn);
+        out[i] = sh.objIdx > -1 ? 1 : 0;
+    }
     return 0;
 }
 void* orc_kd_build(const orc_tri* tris, uint32_t n) { KdTree* k = new KdTree(); k->tris.assign(tris, tris + n); k->build(); return k; }

@@ -121,6 +121,12 @@ void orc_grid_intersect(void* h, const float* O, const float* D, uint32_t n, orc
 void orc_grid_free(void* h);
 /* Sample / Trace through the KD-tree (1) or grid (2) of a FileScene instead of its BVH (file_scene.h:10-12): h = the structure built over the scene's triangles */
 int orc_set_render_accel(orc_ctx*, int kind, void* h);
+/* TLASFileScene built with TLAS_USE_KDTree (1) / TLAS_USE_Grid (2) (tlas_file_scene.h:11-13): handles[i] = the structure built over BLAS i's triangles
+   (orc_bvh_copy order), n = orc_bvh_count; every query, Sample, Tick and the Whitted integrator then walk TLASKDTree / TLASGrid.  0: the TLAS-BVH again.
+   orc_set_blas_transform keeps the set (invT is read per query); orc_bvh_move_and_refit drops it (the reference has no Refit for these structures). */
+int orc_set_blas_accel(orc_ctx*, int kind, void* const* handles, int n);
+/* scene.IsOccluded(Ray(O, D, t)): 1 / 0 per ray */
+int orc_is_occluded(orc_ctx*, const float* O, const float* D, const float* t, int32_t* out, size_t n);
 /* PrimitiveScene: orc_create(2); the wall images; animation time; state dump (6 matrices, sphere position, torus radii, cube box: 108 floats) */
 int orc_prim_setup(orc_ctx*, const uint32_t* red512, const uint32_t* blue512);
 int orc_prim_set_time(orc_ctx*, float t);

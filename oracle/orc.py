@@ -261,6 +261,14 @@ class Oracle:
         self._ck(self.L.orc_find_nearest(self.h, _fp(rays), _fp(hits), C.c_size_t(O.shape[0])))
         return hits
 
+    def is_occluded(self, O, D, t):
+        """scene.IsOccluded(Ray(O, D, t)) per ray: the light quad bounded by t, then the structure with shadow.t = 1e34f (through the set of set_blas_accel, if any)"""
+        O = np.ascontiguousarray(O, np.float32).reshape(-1, 3); D = np.ascontiguousarray(D, np.float32).reshape(-1, 3)
+        t = np.ascontiguousarray(np.broadcast_to(np.asarray(t, np.float32), (O.shape[0],)))
+        out = np.zeros(O.shape[0], np.int32)
+        self._ck(self.L.orc_is_occluded(self.h, _fp(O), _fp(D), _fp(t), _fp(out), C.c_size_t(O.shape[0])))
+        return out
+
     def sample(self, O, D, seed, inside=0):
         r = np.zeros(1, RAY_DTYPE)
         r["O"], r["D"], r["inside"] = O, D, inside
@@ -684,6 +692,29 @@ def set_render_accel(scene, accel):
     r = L.orc_set_render_accel(scene.h, C.c_int(0 if accel is None else (1 if accel.kind == "kd" else 2)), None if accel is None else accel.h)
     if r != 0:
         raise RuntimeError("orc_set_render_accel refused")
+
+
+def set_blas_accel(scene, accels):
+    """scene: an oracle TLAS scene (load_scene(.., 1)); accels: None (the TLAS-BVH again) or one AltAccel of the oracle per BLAS, built over scene.bvh(i)["tris"] —
+    FindNearest / IsOccluded / Sample / Tick / Whitted then walk TLASKDTree / TLASGrid.  The scene keeps the list alive."""
+    L = lib()
+    if accels is None:
+        r = L.orc_set_blas_accel(scene.h, C.c_int(0), None, C.c_int(0))
+    else:
+        accels = list(accels)
+        kinds = {a.kind for a in accels}
+        if len(kinds) != 1 or any(not a.p.startswith("orc_") for a in accels):
+            raise ValueError("set_blas_accel: oracle structures of one kind")
+        arr = (C.c_void_p * len(accels))(*[a.h for a in accels])
+        r = L.orc_set_blas_accel(scene.h, C.c_int(1 if kinds.pop() == "kd" else 2), arr, C.c_int(len(accels)))
+    if r != 0:
+        raise RuntimeError("orc_set_blas_accel refused: " + L.orc_last_error(scene.h).decode())
+    scene._blas_accels = accels
+
+
+def blas_accels(scene, kind):
+    """one oracle KDTree ("kd") / Grid ("grid") per BLAS of `scene`, over its object-space triangles in reference order"""
+    return [alt_accel(kind, scene.bvh(i)["tris"]) for i in range(scene.bvh_count())]
 
 
 def alt_accel(kind, tris):

@@ -275,10 +275,10 @@ def occlusion_pool(lo, hi, light, kmax=3, ordinary=None):
     return pool
 
 
-def sample_pool(o, prim, lo=None, hi=None, kmax=3):
+def sample_pool(o, prim, lo=None, hi=None, kmax=3, extra=None):
     """Sample rays of one world (`o`: its oracle, renderer_init done): sample_query_inputs' ray set at the size the launches need, a share of its directions
     axis-parallel; idlers that end in their first trip (triangle scenes: up and away from everything, the sky; the primitive scene's closed room: at the light);
-    leading: refused rays.  pool.seeds holds the seeds; pool.want = (rgb, seeds out) per pool ray by the oracle, the refused rays' by the rule itself."""
+    leading: refused rays.  extra: (O, D, inside, seeds) put in place of ordinary rays at evenly spaced positions, as they are.  pool.seeds holds the seeds; pool.want = (rgb, seeds out) per pool ray by the oracle, the refused rays' by the rule itself."""
     import sample_query_inputs as si
     m = base_size(kmax, True) + max(TAILS)
     g = base_size(kmax, True) // WAVE
@@ -302,6 +302,9 @@ def sample_pool(o, prim, lo=None, hi=None, kmax=3):
         Oi, Di = idler_rays(lo, hi, ni, 13, up=True)
     D, axis = zero_components(D, 16, 12)
     si_seeds = si.seeds_for(m + ni + nl)
+    if extra is not None:
+        at = (np.arange(len(extra[0])) * m) // len(extra[0])
+        O[at], D[at], inside[at], si_seeds[at], axis[at] = extra[0], extra[1], extra[2], extra[3], False
     Ol, Dl, sl = refused_sample_rays(O[:nl], D[:nl], si_seeds[m + ni:])
     pool = Pool([("ordinary", O, D, inside), ("idlers", Oi, Di, np.zeros(ni, np.int32)), ("leading", Ol, Dl, inside[:nl])], kmax, sample=True)
     pool.seeds = np.concatenate([si_seeds[:m + ni], sl]).astype(np.uint32)
@@ -408,10 +411,16 @@ def tlas_alt_cases(orc, xml, kind, assets, light):
 
 
 def sample_case(o, name):
-    """sample_query_kernel in world `name` of tests/test_gpu_sample_query.py (`o`: its oracle): rgb and the returned seed by the oracle's Sample; cost = draws"""
+    """sample_query_kernel in world `name` of tests/test_gpu_sample_query.py (`o`: its oracle): rgb and the returned seed by the oracle's Sample; cost = draws.
+    The two-level worlds (tlas_kd, tlas_grid: `o` walks the structure, orc.set_blas_accel) also hold the committed rays of alt_disagreement.py, spread through
+    the ordinary rays."""
     prim = name == "prim"
     lo, hi = (None, None) if prim else scene_box(o, 1 if name.startswith("tlas") else 0)
-    pool = sample_pool(o, prim, lo, hi)
+    extra = None
+    if name in ("tlas_kd", "tlas_grid"):
+        import alt_disagreement as ad
+        extra = ad.load(name[5:])[:4]
+    pool = sample_pool(o, prim, lo, hi, extra=extra)
     c = Case()
     c.pool, c.want, c.cost, c.o = pool, pool.want, pool.cost, o
     return c

@@ -96,6 +96,14 @@ def triangle_rays(o, n=N_RAYS, seed=5):
     return O[perm], D[perm], inside[perm], seeds_for(n)
 
 
+def two_level_rays(o, kind):
+    """the ray set of a two-level world ("kd" / "grid"): triangle_rays plus the committed rays on which tlas_scene.xml's structures disagree (alt_disagreement.py)"""
+    import alt_disagreement as ad
+    O, D, inside, seeds = triangle_rays(o)
+    Oa, Da, ia, sa, _ = ad.load(kind)
+    return np.concatenate([O, Oa]), np.concatenate([D, Da]), np.concatenate([inside, ia]).astype(np.int32), np.concatenate([seeds, sa]).astype(np.uint32)
+
+
 def prim_rays(n=N_RAYS, seed=7):
     """rays inside the PrimitiveScene's room, half of them aimed at the small objects; every fourth with inside = 1"""
     rng = np.random.default_rng(seed)

@@ -6,13 +6,15 @@ deterministic schedule; k = 3: wavefronts also contend for the cursor — so tha
 of tests/query_schedules.py, which tests/test_query_schedules_cpu.py checks without a GPU.
 
 Expected values never depend on the order: they are the per-ray answers of the oracle (oracle/orc.py), of its restatements of the KD-tree / grid, of
-tests/tlas_alt_restate.py and of test_gpu_scene_queries.quad_occluded, indexed by the order.  Floats are compared as bit patterns (any NaN equals any NaN), counters
-exactly.  Two comparisons are AGREEMENT checks between two runs of the product and say so where they stand: the switch test's bounded against unbounded launch, and
-the two-level KD-tree / grid Sample worlds, for which no oracle Sample exists."""
+tests/tlas_alt_restate.py and of test_gpu_scene_queries.quad_occluded, indexed by the order; the two-level KD-tree / grid Sample worlds' are orc_sample through the
+same structure (orc.set_blas_accel).  Floats are compared as bit patterns (any NaN equals any NaN), counters exactly.  One comparison is an AGREEMENT check between
+two runs of the product and says so where it stands: the switch test's bounded against unbounded launch."""
 import numpy as np
 import pytest
 
+import alt_disagreement as ad
 import query_schedules as qs
+import sample_query_inputs as si
 from conftest import ASSETS, scene_path
 from probe_inputs import differing
 from test_gpu_golden_and_edges import write_scene
@@ -266,17 +268,59 @@ def test_sample_lane_reuse(crt, cases, worlds, monkeypatch, world, k):
 @pytest.mark.parametrize("k", [1, 3])
 @pytest.mark.parametrize("world", ["tlas_kd", "tlas_grid"])
 def test_sample_two_level_alt_bounded_equals_unbounded(crt, cases, worlds, monkeypatch, world, k):
-    """AGREEMENT check, not an oracle check: the oracle has no Sample through the two-level KD-tree / grid, so the bounded launch (every lane reused) is compared
-    with the same world's unbounded launch of the same rays (a workgroup per 256 rays: hardly a lane reused), bit for bit, the counters' growth included."""
+    """the two-level KD-tree / grid Sample worlds against orc_sample through the same structure: the bounded launch (every lane reused) and the same world's
+    unbounded launch of the same rays (a workgroup per 256 rays: hardly a lane reused) both give the oracle's radiance, seeds and counter growth, bit for bit"""
     w = worlds.get(world)
-    t = worlds.get("tlas")
-    pool = cases(("sample", "tlas"), lambda: qs.sample_case(t.o, "tlas")).pool
-    for name, order in launches(pool, k, pool.cost):
+    case = cases(("sample", world), lambda: qs.sample_case(w.o, world))
+    pool = case.pool
+    for name, order in launches(pool, k, case.cost):
+        counted = {c: int(pool.counted[c][order].sum()) for c in ("rays", "mesh_hits")}
         monkeypatch.delenv(SWITCH, raising=False)
         free = list(sample_both(crt, w.ctx, pool, order, w.accel))
         monkeypatch.setenv(SWITCH, str(k))
         for (entry, rgb, s, grown), (_, rgb0, s0, grown0) in zip(sample_both(crt, w.ctx, pool, order, w.accel), free):
             what = (world, k, name, entry)
             assert len(differing(rgb, rgb0)) == 0 and np.array_equal(s, s0) and grown == grown0, what
+            bad = differing(rgb, case.want[0][order])
+            assert len(bad) == 0, (what, "rgb", len(bad), bad[:8].tolist())
+            bad = np.flatnonzero(s != case.want[1][order])
+            assert len(bad) == 0, (what, "seeds", len(bad), bad[:8].tolist())
+            assert grown == counted, what
             lead = qs.refused(pool.O[order], pool.D[order], pool.seeds[order])
             assert np.isnan(rgb[lead]).all() and np.isfinite(rgb[~lead]).all() and np.array_equal(s[lead], pool.seeds[order][lead]), what
+
+
+@pytest.mark.parametrize("k", [1, 3])
+@pytest.mark.parametrize("kind", ["kd", "grid"])
+def test_sample_lane_reuse_on_the_disagreement_rays(crt, orc, cases, monkeypatch, kind, k):
+    """tlas_scene.xml through the two-level structure, k workgroups, 8 rays a lane: primary rays of the default camera with the committed rays on which the
+    structures disagree spread evenly among them, so a reused lane carries a path that parts from the TLAS-BVH's path next to ordinary ones.  Against orc_sample
+    through the same structure; the premise (through the TLAS-BVH most of those paths end elsewhere) is asserted on the oracle's two answers."""
+    xml = scene_path("tlas_scene.xml"); code = crt.ACCEL_KDTREE if kind == "kd" else crt.ACCEL_GRID
+
+    def make():
+        b, a = ad.scene_pair(orc, xml, ASSETS, kind)
+        a.renderer_init(64, 64)
+        n = 256 * 8 * 3
+        rng = np.random.default_rng(31)
+        O, D = a.primary_rays(np.stack([rng.uniform(0, 64, n), rng.uniform(0, 64, n)], 1).astype(np.float32))
+        inside = np.zeros(n, np.int32); seeds = si.seeds_for(n)
+        Oa, Da, ia, sa, _ = ad.load(kind)
+        at = (np.arange(len(Oa)) * n) // len(Oa)
+        O[at], D[at], inside[at], seeds[at] = Oa, Da, ia, sa
+        want = si.oracle_sample(a, O, D, inside, seeds)
+        bvh = si.oracle_sample(b, O[at], D[at], inside[at], seeds[at])
+        assert (want[1][at] != bvh[1]).sum() >= 50
+        return O, D, inside, seeds, want
+    O, D, inside, seeds, want = cases(("sample disagreement", kind), make)
+    n = 256 * 8 * k                                                          # a prefix: a third of the spread rays for k = 1, all of them for k = 3
+    hs, ctx = start(crt, xml, 1, (code,))
+    monkeypatch.setenv(SWITCH, str(k))
+    for r in (0, 17):
+        m = n - r
+        rgb, s = ctx.sample(O[:m], D[:m], seeds[:m], inside[:m], accel=code)
+        assert len(differing(rgb, want[0][:m])) == 0 and np.array_equal(s, want[1][:m]), (kind, k, r, "host")
+        rgb, s = ctx.sample_device(rays=records(crt, O[:m], D[:m], inside[:m]), seeds=seeds_t(seeds[:m]), accel=code)
+        torch.cuda.synchronize()
+        assert len(differing(rgb.cpu().numpy(), want[0][:m])) == 0 and np.array_equal(seeds_np(s), want[1][:m]), (kind, k, r, "device")
+    ctx.close(); hs.close()

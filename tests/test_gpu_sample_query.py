@@ -1,14 +1,17 @@
 """crt_sample / crt_sample_device: Renderer::Sample(ray, seed, 0) ("3. PathTracer/renderer.cpp":50-100) for arrays of rays with a seed each, on host buffers and
 on device buffers enqueued on a caller's stream (device/sample_query.h).  Radiance, returned seed and the ray counter are compared with the CPU oracle's
-orc_sample bit for bit, per world: FileScene through BVH / KD-tree / grid, TLASFileScene, PrimitiveScene.  The ray sets come from tests/sample_query_inputs.py;
-tests/test_sample_query_cpu.py asserts without a GPU that they reach every branch of Sample."""
+orc_sample bit for bit, per world: FileScene through BVH / KD-tree / grid, TLASFileScene through TLAS-BVH / two-level KD-tree / two-level grid (the oracle walks
+them through orc.set_blas_accel), PrimitiveScene.  The ray sets come from tests/sample_query_inputs.py; tests/test_sample_query_cpu.py asserts without a GPU that
+they reach every branch of Sample.  The two-level worlds also take the committed rays on which the structures disagree (tests/alt_disagreement.py); those come
+from assets/scenes/tlas_scene.xml and disagree there, so they are sampled in that scene too (test_sample_on_the_disagreement_rays)."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
+import alt_disagreement as ad
 import sample_query_inputs as si
-from conftest import ASSETS
+from conftest import ASSETS, scene_path
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
@@ -81,10 +84,13 @@ class Worlds:
             w.o, _ = orc.load_scene(self.xml, kind, ASSETS)
             if name in ("kd", "grid"):
                 w.acc = orc.alt_accel(name, w.o.bvh(0)["tris"]); orc.set_render_accel(w.o, w.acc)
-            # the oracle has no Sample through the two-level KD-tree / grid: those worlds serve the Tick test only (w.o gives the camera)
-            w.rays = si.triangle_rays(w.o) if name in ("bvh", "kd", "grid", "tlas") else None
+            if name in ("tlas_kd", "tlas_grid"):
+                orc.set_blas_accel(w.o, orc.blas_accels(w.o, name[5:]))
+                w.rays = si.two_level_rays(w.o, name[5:])
+            else:
+                w.rays = si.triangle_rays(w.o)
         w.o.renderer_init(W, H)
-        w.want = si.oracle_sample(w.o, *w.rays) if w.rays is not None else None
+        w.want = si.oracle_sample(w.o, *w.rays)
         self.cache[name] = w
         return w
 
@@ -100,7 +106,7 @@ def worlds(crt, orc, tmp_path_factory):
 # ---------------------------------------------------------------------------------------------------------------------------------------------------
 # 1 + 2. oracle parity in every world, on inputs that reach every branch
 # ---------------------------------------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("world", ["bvh", "kd", "grid", "tlas", "prim"])
+@pytest.mark.parametrize("world", ["bvh", "kd", "grid", "tlas", "tlas_kd", "tlas_grid", "prim"])
 def test_sample_equals_the_oracle(crt, worlds, world):
     w = worlds.get(world); ctx = w.ctx
     O, D, inside, seeds = w.rays
@@ -131,6 +137,34 @@ def test_sample_equals_the_oracle(crt, worlds, world):
     else:
         k = si.draws(seeds, seeds_np(s_d))
         assert (k == 0).sum() >= 100 and (k > 10).sum() >= 100
+
+
+@pytest.mark.parametrize("kind", ["kd", "grid"])
+def test_sample_on_the_disagreement_rays(crt, orc, kind):
+    """tlas_scene.xml through the two-level structure, on the committed rays whose nearest hit there is not the TLAS-BVH's (primary rays, rays kEPS off a surface,
+    rays inside the dielectric): radiance, returned seed and the counters equal orc_sample through the same structure.  The premise is asserted on the oracle's two
+    answers: through the BVH most of these paths end elsewhere, so a Sample world that walked the TLAS-BVH instead would fail here."""
+    xml = scene_path("tlas_scene.xml"); code = crt.ACCEL_KDTREE if kind == "kd" else crt.ACCEL_GRID
+    b, a = ad.scene_pair(orc, xml, ASSETS, kind)
+    O, D, inside, seeds, _ = ad.load(kind)
+    want_rgb, want_seeds, cnt = si.oracle_sample(a, O, D, inside, seeds)
+    bvh_rgb, bvh_seeds, _ = si.oracle_sample(b, O, D, inside, seeds)
+    n_diff = len(set(differing(want_rgb, bvh_rgb)) | set(np.flatnonzero(want_seeds != bvh_seeds)))
+    assert n_diff >= 50, n_diff                                            # of 180: 177 (KD-tree), 180 (grid)
+    hs = crt.HostScene(xml, 1, ASSETS); hs.build_alt(code)
+    ctx = crt.Context(W, H); hs.upload(ctx); hs.upload_alt(ctx, code)
+    counted = ("rays", "mesh_hits", "primary")
+    c0 = ctx.counters()
+    rgb, s = ctx.sample(O, D, seeds, inside, accel=code)
+    c1 = ctx.counters()
+    assert_same(rgb, s, want_rgb, want_seeds, "crt_sample")
+    assert {k: c1[k] - c0[k] for k in counted} == {k: cnt[k] for k in counted}
+    rgb_d, s_d = ctx.sample_device(rays=records(crt, O, D, inside), seeds=seeds_t(seeds), accel=code)
+    torch.cuda.synchronize()
+    assert_same(rgb_d.cpu().numpy(), seeds_np(s_d), want_rgb, want_seeds, "crt_sample_device")
+    c2 = ctx.counters()
+    assert {k: c2[k] - c1[k] for k in counted} == {k: cnt[k] for k in counted}
+    ctx.close(); hs.close()
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------------------
@@ -195,8 +229,8 @@ def test_shapes_and_independence_of_position(crt, worlds):
 def test_tick_rebuilt_outside_the_library(crt, worlds, world):
     """ProcessTile (renderer.cpp:117-131) on the host: per 16 x 16 tile seed = InitSeed(tx + ty * W + spp * 1799); per pixel in order the y jitter, then the x jitter,
     the primary ray, Sample — Sample through sample_device with one ray per tile and the returned seed carried to the next pixel.  Two frames summed in frame order
-    must be crt_render(1, 2)'s accumulator bit for bit.  For the two-level KD-tree and grid (the oracle has no Sample through them) this is an AGREEMENT check with
-    crt_render, not an oracle check; the other worlds' crt_render is itself pinned to the oracle elsewhere."""
+    must be crt_render(1, 2)'s accumulator bit for bit.  crt_render is itself pinned to the oracle elsewhere (through the two-level KD-tree and grid:
+    test_gpu_tlas_alt.py::test_render_through_the_structure_equals_the_oracle_through_it)."""
     w = worlds.get(world); ctx = w.ctx
     ctx.set_render_accel(w.accel)
     ctx.clear(); ctx.render(1, 2, 1)

@@ -1,6 +1,8 @@
 """TLASFileScene built with TLAS_USE_KDTree / TLAS_USE_Grid (tlas_file_scene.cpp:40-90) on the GPU: TLASKDTree over BLASKDTree and TLASGrid over BLASGrid,
 uploaded with crt_upload_blas_accel.  Every query record is compared field for field with the CPU restatement (tests/tlas_alt_restate.py), Ray::traversed and
-Ray::tested included; renders with the oracle's TLAS-BVH render (the structures return the same nearest hits, and the path tracer draws the same numbers)."""
+Ray::tested included, and at size (2^16 rays) with the C++ oracle's two-level walk (orc.set_blas_accel, pinned to the restatement by tests/test_tlas_alt_cpu.py).
+Renders and Whitted frames are compared with the oracle through the same structure, over frame counts at which that differs from the oracle's TLAS-BVH render,
+and (test_render_and_whitted_equal_the_oracle) with the TLAS-BVH render itself on a camera whose paths meet no ray on which the structures disagree."""
 import numpy as np
 import pytest
 import torch
@@ -8,6 +10,7 @@ import torch
 from conftest import ASSETS, scene_path
 from test_gpu_scene_queries import light_of, quad_occluded, pick_t, ray_records, shadow_records, hits_np, tlas_up_rays
 from test_tlas_alt_cpu import second_scene
+import alt_disagreement as ad
 import tlas_alt_restate as R
 
 pytestmark = pytest.mark.gpu
@@ -115,6 +118,105 @@ def test_render_and_whitted_equal_the_oracle(crt, orc, tmp_path, kind, code):
         ctx.reset_counters(); ctx.whitted_tick()
         assert ctx.counters()["tlas_iters"] > 0
         ctx.close(); hs.close()
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------------------
+# Against the oracle THROUGH THE SAME STRUCTURE (orc.set_blas_accel), on frames where that is not the TLAS-BVH answer
+# ---------------------------------------------------------------------------------------------------------------------------------------------------
+# (kind, scene state, passes) -> (frames, differing tiles): at 96 x 64 with tlas_scene.xml's default camera, the smallest frame count for which the oracle's
+# accumulator through the structure differs from the oracle's accumulator through the TLAS-BVH, and in how many 16 x 16 tiles it then differs.  Found with the
+# oracle; the test asserts both numbers on the oracle's two images (one frame fewer: no tile differs), so a comparison that says nothing new cannot pass unnoticed.
+# "moved": instance 2 (the teapot) rotated and shifted, as in test_instance_motion_keeps_the_set.
+STRUCTURE_FRAMES = {("kd", "built", 1): (2, 1), ("kd", "built", 2): (3, 1), ("kd", "moved", 1): (9, 1),
+                    ("grid", "built", 1): (20, 1), ("grid", "built", 2): (24, 1), ("grid", "moved", 1): (20, 1)}
+RW, RH = 96, 64
+
+
+def differing_tiles(a, b):
+    d = (a.view(np.uint32) != b.view(np.uint32)).any(axis=2)
+    return int(d.reshape(RH // 16, 16, RW // 16, 16).any(axis=(1, 3)).sum())
+
+
+def moved_transform(T):
+    T = T.reshape(4, 4).copy()
+    c, s = np.float32(np.cos(np.float32(0.7))), np.float32(np.sin(np.float32(0.7)))
+    T[0, 0], T[0, 2], T[2, 0], T[2, 2] = c, s, -s, c
+    T[:3, 3] += np.array([-0.4, 0.1, 0.3], np.float32)
+    return T
+
+
+def structure_context(crt, xml, code):
+    hs = crt.HostScene(xml, 1, ASSETS); hs.build_alt(code)
+    ctx = crt.Context(RW, RH, collect_stats=True); hs.upload(ctx); hs.upload_alt(ctx, code)
+    ctx.set_render_accel(code)
+    return hs, ctx
+
+
+def render_and_whitted_against(ctx, a, b, frames, tiles, passes, what):
+    """crt_render x frames and one Whitted Tick of `ctx` against oracle `a` (through the structure); `b` (through the TLAS-BVH) only states the premise"""
+    for o in (a, b):
+        o.set_params(5, passes); o.clear(); o.reset_counters()
+        o.render(frames - 1, 8)
+    assert differing_tiles(a.accumulator(), b.accumulator()) == 0, what     # `frames` is the smallest such count
+    a.render(1, 8); b.render(1, 8)
+    assert differing_tiles(a.accumulator(), b.accumulator()) == tiles >= 1, what
+    ctx.clear(); ctx.reset_counters()
+    ctx.render(1, frames, passes)
+    assert np.array_equal(ctx.accumulator().view(np.uint32), a.accumulator().view(np.uint32)), what
+    c, oc = ctx.counters(), a.counters()
+    assert c["rays"] == oc["rays"] and c["mesh_hits"] == oc["mesh_hits"] and c["tlas_iters"] == 0, (what, c, oc)
+    ctx.reset_counters()
+    px = ctx.whitted_tick(); a.whitted(8)                                   # its shadow rays take the ANY form of the walk
+    assert np.array_equal(px, a.screen()) and np.array_equal(ctx.accumulator().view(np.uint32), a.accumulator().view(np.uint32)), what
+    assert ctx.counters()["tlas_iters"] == 0
+
+
+@pytest.mark.parametrize("passes", [1, 2])
+@pytest.mark.parametrize("kind,code", KINDS)
+def test_render_through_the_structure_equals_the_oracle_through_it(crt, orc, kind, code, passes):
+    xml = scene_path("tlas_scene.xml")
+    b, a = ad.scene_pair(orc, xml, ASSETS, kind)
+    for o in (a, b):
+        o.renderer_init(RW, RH)
+    hs, ctx = structure_context(crt, xml, code)
+    render_and_whitted_against(ctx, a, b, *STRUCTURE_FRAMES[(kind, "built", passes)], passes, (kind, "built", passes))
+    if passes == 1:
+        # one instance moves: set_transform + UPDATE_TRANSFORMS keeps the uploaded set (invT is read per query), and so does the device route with the same matrices
+        T = moved_transform(hs.blas_transform(2)[0])
+        hs.set_transform(2, T); a.set_transform(2, T); b.set_transform(2, T)
+        hs.update(ctx, crt.UPDATE_TRANSFORMS)
+        frames, tiles = STRUCTURE_FRAMES[(kind, "moved", 1)]
+        render_and_whitted_against(ctx, a, b, frames, tiles, 1, (kind, "set_transform + UPDATE_TRANSFORMS"))
+        hs2, ctx2 = structure_context(crt, xml, code)
+        allT = np.stack([hs.blas_transform(i)[0].reshape(16) for i in range(hs.bvh_count())]).astype(np.float32)
+        ctx2.update_transforms_device(torch.from_numpy(allT).cuda())
+        render_and_whitted_against(ctx2, a, b, frames, tiles, 1, (kind, "update_transforms_device"))
+        ctx2.close(); hs2.close()
+    ctx.close(); hs.close()
+
+
+@pytest.mark.parametrize("kind,code", KINDS)
+def test_queries_at_size_equal_the_oracle(crt, orc, kind, code):
+    """2^16 rays of R.query_rays plus the committed rays on which the structures disagree: a launch of many workgroups (2 000 rays are a workgroup per 64 rays),
+    both FindNearest entries and both occlusion entries against the C++ oracle's two-level walk, all seven fields as bits"""
+    xml = scene_path("tlas_scene.xml"); light = light_of(xml)
+    hs, ctx, o = setup(crt, orc, xml, code)
+    orc.set_blas_accel(o, orc.blas_accels(o, kind))
+    O, D = R.query_rays(o, light, n=65536)
+    Oa, Da, _, _, _ = ad.load(kind)
+    at = np.linspace(0, len(O), len(Oa), endpoint=False).astype(np.int64)   # spread through the launch
+    O = np.insert(O, at, Oa, axis=0); D = np.insert(D, at, Da, axis=0)
+    want = o.find_nearest(O, D)
+    assert (want["objIdx"] == 1).sum() > 3000 and (want["objIdx"] >= 2).sum() > 10000 and (want["objIdx"] == 0).sum() > 100 and (D == 0).any(axis=1).sum() > 5000
+    assert_records(ctx.find_nearest_alt(code, O, D), want, "host entry")
+    assert_records(hits_np(crt, ctx.find_nearest_device(ray_records(O, D), accel=code)), want, "device entry")
+    _, tq = quad_occluded(O, D, np.full(len(O), 1e34, np.float32), light)
+    t = pick_t(tq)
+    occ = o.is_occluded(O, D, t)
+    assert 1000 < occ.sum() < len(occ) - 1000
+    assert np.array_equal(ctx.is_occluded(O, D, t, accel=code), occ != 0)
+    assert np.array_equal(ctx.is_occluded_device(shadow_records(O, D, t), accel=code).cpu().numpy(), occ)
+    ctx.close(); hs.close()
 
 
 @pytest.mark.parametrize("kind,code", KINDS)

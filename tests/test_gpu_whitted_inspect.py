@@ -1,6 +1,7 @@
 """The Whitted renderer's traversal inspection and per-Tick metrics on the GPU (crt_whitted_tick_inspect, Renderer::TickWhitted with the two inspect flags).
 Expected values never come from the library: per-pixel Ray::traversed / Ray::tested from the CPU oracle's FindNearest on the pixel grid's primary rays (through
-its own KD-tree / grid for FileScene, through tests/tlas_alt_restate.py for the two-level KD-tree / grid), sky pixels and the shaded image from Oracle.whitted(),
+its own KD-tree / grid for FileScene; for the two-level KD-tree / grid through tests/tlas_alt_restate.py at 64 x 48 and through the oracle's own two-level walk,
+orc.set_blas_accel, at 320 x 192), sky pixels and the shaded image from Oracle.whitted() (at 320 x 192 through the same two-level structure),
 the running peak and GetTraverseCountColor from tests/inspect_restate.py (itself pinned to the reference's helper.h by test_whitted_inspect_cpu.py).
 Everything is compared with np.array_equal, floats as bits."""
 import re
@@ -25,7 +26,7 @@ def bits(a):
     return np.ascontiguousarray(a).view(np.uint32)
 
 
-def expected(crt, orc, xml, kind, accel, W, H, camera=None):
+def expected(crt, orc, xml, kind, accel, W, H, camera=None, two_level="restatement"):
     """the primary rays' records of the oracle, in row-major pixel order: traversed, tested (H, W) int32, hit (H, W) bool, and the oracle's Whitted
     accumulator / screen / counters of the same Tick (sky pixels, the shaded image)"""
     path = scene_path(xml)
@@ -41,6 +42,9 @@ def expected(crt, orc, xml, kind, accel, W, H, camera=None):
     elif kind == 0:
         keep = orc.alt_accel(NAME[accel], o.bvh(0)["tris"])
         orc.set_render_accel(o, keep)
+        h = o.find_nearest(O, D)
+    elif two_level == "oracle":                                                           # the C++ oracle walks TLASKDTree / TLASGrid: counts and Whitted image through it
+        orc.set_blas_accel(o, orc.blas_accels(o, NAME[accel]))
         h = o.find_nearest(O, D)
     else:
         h = TR.Scene(orc, o, NAME[accel], light_of(path)).find_nearest_many(O, D, crt.HIT_DTYPE)
@@ -96,14 +100,15 @@ def check_mode(ctx, e, mode, pt, ps, sky):
 
 CONFIGS = [("bunny_scene.xml", 0, 0, 320, 192, (57, 18)), ("bunny_scene.xml", 0, 1, 320, 192, (202, 75)), ("bunny_scene.xml", 0, 2, 320, 192, (57, 153)),
            ("tlas_scene.xml", 1, 0, 320, 192, (128, 62)), ("tower_scene.xml", 0, 0, 200, 120, (188, 98)),
-           ("tlas_scene.xml", 1, 1, 64, 48, (392, 232)), ("tlas_scene.xml", 1, 2, 64, 48, (101, 382))]
+           ("tlas_scene.xml", 1, 1, 64, 48, (392, 232)), ("tlas_scene.xml", 1, 2, 64, 48, (101, 382)),
+           ("tlas_scene.xml", 1, 1, 320, 192, (442, 690)), ("tlas_scene.xml", 1, 2, 320, 192, (104, 557))]
 
 
 @pytest.mark.parametrize("xml,kind,accel,W,H,peaks", CONFIGS)
 def test_counts_metrics_and_heat_maps(crt, orc, xml, kind, accel, W, H, peaks):
     """per-pixel traversed / tested, hit count, totals and peaks in modes 0 / 1 / 2; the heat maps of a first Tick (peaks 0 / 0), of a second Tick with the
     peaks the first returned (every hit pixel scaled by the global maximum) and of a Tick with carried-in peaks larger than the frame's maxima"""
-    e = expected(crt, orc, xml, kind, accel, W, H)
+    e = expected(crt, orc, xml, kind, accel, W, H, two_level="restatement" if (W, H) == (64, 48) else "oracle")
     assert (int(e["traversed"].max()), int(e["tested"].max())) == peaks                   # the reference values this case was chosen for
     guards(e, xml == "tlas_scene.xml")
     if (xml, accel) == ("bunny_scene.xml", 0):

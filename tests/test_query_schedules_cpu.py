@@ -108,14 +108,16 @@ def test_tlas_alt_orders(orc, kind):
     check_orders(oc, (1,), "tlas_alt is_occluded %s" % kind)
 
 
-@pytest.mark.parametrize("world", ["bvh", "kd", "grid", "tlas", "prim"])
+@pytest.mark.parametrize("world", ["bvh", "kd", "grid", "tlas", "tlas_kd", "tlas_grid", "prim"])
 def test_sample_orders(orc, tmp_path, world):
     if world == "prim":
         o = orc.primitive_scene(ASSETS, 1.3)
     else:
-        o, _ = orc.load_scene(si.scene_xml(tmp_path), 1 if world == "tlas" else 0, ASSETS)
+        o, _ = orc.load_scene(si.scene_xml(tmp_path), 1 if world.startswith("tlas") else 0, ASSETS)
         if world in ("kd", "grid"):
             orc.set_render_accel(o, orc.alt_accel(world, o.bvh(0)["tris"]))
+        if world in ("tlas_kd", "tlas_grid"):
+            orc.set_blas_accel(o, orc.blas_accels(o, world[5:]))
     o.renderer_init(W, H)
     case = qs.sample_case(o, world)
     pool = case.pool
@@ -123,3 +125,11 @@ def test_sample_orders(orc, tmp_path, world):
     assert np.array_equal(case.want[1][pool.idlers], pool.seeds[pool.idlers]) and np.isfinite(case.want[0][pool.idlers]).all()
     assert np.isnan(case.want[0][pool.leading]).all() and np.array_equal(case.want[1][pool.leading], pool.seeds[pool.leading])
     check_orders(case, (1, 3), "sample %s" % world, idler_hits=False)
+    if world in ("tlas_kd", "tlas_grid"):                                   # the committed disagreement rays sit among the ordinary rays of every launch, as they are
+        import alt_disagreement as ad
+        Oa, Da, _, sa, _ = ad.load(world[5:])
+        held = {(O.tobytes(), D.tobytes(), int(s)) for O, D, s in zip(pool.O[pool.ordinary], pool.D[pool.ordinary], pool.seeds[pool.ordinary])}
+        assert all((O.tobytes(), D.tobytes(), int(s)) in held for O, D, s in zip(Oa, Da, sa))
+        for k in (1, 3):
+            first = {(O.tobytes(), D.tobytes()) for O, D in zip(pool.O[pool.ordinary[:pool.n0(k)]], pool.D[pool.ordinary[:pool.n0(k)]])}
+            assert sum((O.tobytes(), D.tobytes()) in first for O, D in zip(Oa, Da)) >= len(Oa) * k // 3 - 1

@@ -8,15 +8,21 @@ import sample_query_inputs as si
 from conftest import ASSETS
 
 
-@pytest.mark.parametrize("world", ["bvh", "kd", "grid", "tlas"])
+@pytest.mark.parametrize("world", ["bvh", "kd", "grid", "tlas", "tlas_kd", "tlas_grid"])
 def test_triangle_ray_sets_reach_every_branch(orc, tmp_path, world):
     xml = si.scene_xml(tmp_path)
-    o, _ = orc.load_scene(xml, 1 if world == "tlas" else 0, ASSETS)
+    o, _ = orc.load_scene(xml, 1 if world.startswith("tlas") else 0, ASSETS)
     acc = None
     if world in ("kd", "grid"):
         acc = orc.alt_accel(world, o.bvh(0)["tris"]); orc.set_render_accel(o, acc)
-    O, D, inside, seeds = si.triangle_rays(o)
-    assert len(O) == si.N_RAYS and (seeds != 0).all() and (seeds >> 31).sum() > 100
+    if world in ("tlas_kd", "tlas_grid"):
+        orc.set_blas_accel(o, orc.blas_accels(o, world[5:]))
+        O, D, inside, seeds = si.two_level_rays(o, world[5:])
+        assert len(O) == si.N_RAYS + 180
+    else:
+        O, D, inside, seeds = si.triangle_rays(o)
+        assert len(O) == si.N_RAYS
+    assert (seeds != 0).all() and (seeds >> 31).sum() > 100
     _, out, cnt = si.oracle_sample(o, O, D, inside, seeds)
     c, k = si.assert_branches(o, O, D, inside, seeds, out)
     assert cnt["rays"] > len(O) and cnt["primary"] == 0                                                   # paths longer than one ray

@@ -1,6 +1,7 @@
 """A CPU restatement of TLASFileScene::FindNearest / IsOccluded built with TLAS_USE_KDTree or TLAS_USE_Grid (infra/scene/tlas_file_scene.cpp:40-90, 201-218):
-TLASKDTree / TLASGrid over BLASKDTree / BLASGrid.  The oracle has no two-level KD-tree / grid; this module restates them in float32, one ray at a time, operation
-for operation, so the GPU's records can be compared field for field, Ray::traversed and Ray::tested included.
+TLASKDTree / TLASGrid over BLASKDTree / BLASGrid.  This module restates them in float32, one ray at a time, operation for operation, so the GPU's records can be
+compared field for field, Ray::traversed and Ray::tested included.  The C++ oracle has its own two-level walk (orc.set_blas_accel, written later and from the
+reference text, not from this file); tests/test_tlas_alt_cpu.py holds the two to each other bit for bit, which is what pins the oracle's walk.
 
 Its data come from the oracle only: o.tlas() (the TLAS the BVH variant built; the KD / grid variants' SetTransform takes the same world bounds from the same root
 box), o.blas_transform(i) (invT), o.bvh(i)["tris"] (BLAS i's object-space triangles, reference order), orc.alt_accel(kind, tris).dump() (the structure KDTree /
