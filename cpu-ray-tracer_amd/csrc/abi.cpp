@@ -3,6 +3,7 @@
 // There is NO CPU rendering path in this library: without a HIP device crt_create fails with CRT_ERR_NO_DEVICE.
 #include "../../include/crt_abi.h"
 #include "device/launch.h"
+#include "host/grid_resolution.h"
 
 #include <cmath>
 #include <cstdarg>
@@ -124,6 +125,21 @@ struct crt_ctx {
     float* dRootBox = nullptr;
     char* dTlasBuild = nullptr; char* hTlasBack = nullptr; size_t tlasBuildBytes = 0;
     hipEvent_t tlasFence = nullptr, tlasBack = nullptr, tlasDone = nullptr, tlasT0 = nullptr, tlasT1 = nullptr; bool tlasTimed = false;
+    // crt_build_grid_device (device/grid_build.hip): the kernels' state block and its pinned copy, scratch (the scan's chunk sums, the fill's cursors and unsorted
+    // references, grown on demand), and the events: `gridBack` behind each of the two read-backs (the two host waits), `gridDone` behind the build (what sceneReady
+    // then names).  A grid the build replaces may still be read by launches enqueued earlier: its buffers go to `retired` with an event recorded on the main stream
+    // once that is ordered behind those launches, and are freed by a later call that finds the event complete (or with the scene, which drains first).
+    crt::GridBuildState* dGridState = nullptr; crt::GridBuildState* hGridState = nullptr;
+    unsigned long long* dGridChunks = nullptr; uint32_t* dGridCursor = nullptr; int32_t* dGridUnsorted = nullptr; size_t gridCursorCap = 0, gridUnsortedCap = 0;
+    hipEvent_t gridBack = nullptr, gridDone = nullptr, gridT0 = nullptr, gridT1 = nullptr; bool gridBuilt = false, gridTimed = false; uint32_t gridBlocks = 0;
+    double gridWaitMs[2] = {0, 0};        // wall time of the last call's two host waits (crt_debug_grid_build_ms)
+    struct Retired { std::vector<void*> ptrs; void* pinned = nullptr; hipEvent_t unread = nullptr; };
+    std::deque<Retired> retired; std::vector<hipEvent_t> retiredEvents;
+    uint32_t gridRefCount = 0;            // references of the FileScene's live grid (uploaded or built on the device)
+    // the two-level grid set as the device holds it, uploaded or rebuilt per BLAS: descriptors, cells and references per BLAS, and whether BLAS i's part is of its
+    // current vertices (an upload sets all, CRT_UPDATE_BOUNDS clears all, crt_refit_device clears its BLAS's, crt_build_grid_device sets its BLAS's): the set is live
+    // (haveBlas[1]) iff every flag is set.  Kept while the set is dropped: the buffers are still held, and a rebuild carries the other BLASes' parts over.
+    struct BlasGrid { std::vector<crt::BlasAltDesc> desc; std::vector<uint32_t> cells, refs; std::vector<uint8_t> current; bool held = false; } blasGrid;
     hipEvent_t altReady = nullptr;        // recorded behind the last crt_upload_alt_accel's copies (device queries on other streams wait for it)
     // Latency mode of single-window launches (render_tiles_kernel's block table), driven by measurement — see next_block_table.  Stage 0 = the table solved from the cost probe's
     // estimates (one wavefront per tile when there was no probe); stages 1 .. kLatStages = tables solved from the tile costs the stage before measured; afterwards the fastest stage is used
@@ -182,6 +198,18 @@ struct crt_ctx {
         if (altTris) (void)hipFree(altTris);
         altTris = nullptr; altTriCount = 0; haveKd = haveGrid = false; alt = crt::AltAccelDev{}; renderAccel = 0;
         for (int k = 0; k < 2; k++) { for (void* p : blasAllocs[k]) (void)hipFree(p); blasAllocs[k].clear(); haveBlas[k] = false; blasAlt[k] = crt::TlasAltDev{}; }
+        blasGrid = BlasGrid{}; gridRefCount = 0;
+        freeRetired(true);                // the callers have drained every stream
+    }
+    void freeRetired(bool all)
+    {
+        while (!retired.empty()) {
+            Retired& r = retired.front();
+            if (!all && hipEventQuery(r.unread) != hipSuccess) { (void)hipGetLastError(); break; }     // oldest first: the events complete in order on the main stream
+            for (void* p : r.ptrs) (void)hipFree(p);
+            if (r.pinned) (void)hipHostFree(r.pinned);
+            retiredEvents.push_back(r.unread); retired.pop_front();
+        }
     }
     void freeScene()
     {
@@ -377,6 +405,10 @@ void crt_destroy(crt_ctx* c)
     if (c->dTlasBuild) (void)hipFree(c->dTlasBuild);
     if (c->hTlasBack) (void)hipHostFree(c->hTlasBack);
     c->freeScene();
+    for (hipEvent_t e : {c->gridBack, c->gridDone, c->gridT0, c->gridT1}) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : c->retiredEvents) (void)hipEventDestroy(e);
+    for (void* p : {(void*)c->dGridState, (void*)c->dGridChunks, (void*)c->dGridCursor, (void*)c->dGridUnsorted}) if (p) (void)hipFree(p);
+    if (c->hGridState) (void)hipHostFree(c->hGridState);
     for (auto& a : c->ahead) (void)hipEventDestroy(a.end);
     if (c->aheadStream) (void)hipStreamDestroy(c->aheadStream);
     for (auto& ev : c->evPool) { (void)hipEventDestroy(ev.a); (void)hipEventDestroy(ev.b); }
@@ -828,6 +860,7 @@ int crt_update_scene(crt_ctx* c, const crt_scene_desc* sd, uint32_t what)
         }
         touch(0, (size_t)f.tlasOff);
         for (uint32_t bi = 0; bi < sd->bvhCount; bi++) { memcpy(&f.rootBox[6 * bi], sd->bvhs[bi].nodes[0].aabbMin, 12); memcpy(&f.rootBox[6 * bi + 3], sd->bvhs[bi].nodes[0].aabbMax, 12); }
+        std::fill(c->blasGrid.current.begin(), c->blasGrid.current.end(), (uint8_t)0);   // every BLAS's grid is of the old vertices
         drop_blas_sets(c);
     }
     if (f.kind == CRT_SCENE_TLAS) {
@@ -2066,7 +2099,7 @@ int crt_upload_alt_accel(crt_ctx* c, const crt_alt_accel* a)
         if ((r = upload_array(c, allocs, a->gridCellStart, (size_t)(cells + 1) * 4, &c->alt.cellStart))) return r;
         if ((r = upload_array(c, allocs, a->gridCellTris, (size_t)a->gridCellTriCount * 4, &c->alt.cellRefs))) return r;
         for (int k = 0; k < 3; k++) { c->alt.res[k] = a->gridResolution[k]; c->alt.cell[k] = a->gridCellSize[k]; c->alt.lo[k] = a->gridMin[k]; c->alt.hi[k] = a->gridMax[k]; }
-        c->haveGrid = true;
+        c->haveGrid = true; c->gridRefCount = a->gridCellTriCount;
     }
     if (!c->altReady) HIPCK(c, hipEventCreateWithFlags(&c->altReady, hipEventDisableTiming));
     HIPCK(c, hipEventRecord(c->altReady, nullptr));                       // behind the copies above (null stream): device queries on other streams wait for it
@@ -2140,6 +2173,11 @@ int crt_upload_blas_accel(crt_ctx* c, int kind, const crt_alt_accel* blas, uint3
     c->epoch++;
     for (void* p : c->blasAllocs[slot]) (void)hipFree(p);
     c->blasAllocs[slot].swap(allocs); c->blasAlt[slot] = tl; c->haveBlas[slot] = true;
+    if (kind == CRT_ACCEL_GRID) {                                         // what crt_build_grid_device / crt_get_grid need of the set
+        crt_ctx::BlasGrid& g = c->blasGrid;
+        g.desc = desc; g.cells.resize(blasCount); g.refs.resize(blasCount); g.current.assign(blasCount, (uint8_t)1); g.held = true;
+        for (uint32_t b = 0; b < blasCount; b++) { g.cells[b] = (uint32_t)blas[b].gridResolution[0] * (uint32_t)blas[b].gridResolution[1] * (uint32_t)blas[b].gridResolution[2]; g.refs[b] = blas[b].gridCellTriCount; }
+    }
     if (c->renderAccel == kind) c->renderAccel = 0;                       // as crt_upload_alt_accel: the render goes back to the BVH until crt_set_render_accel
     if (!c->altReady) HIPCK(c, hipEventCreateWithFlags(&c->altReady, hipEventDisableTiming));
     HIPCK(c, hipEventRecord(c->altReady, nullptr));                       // behind the copies above: device queries on other streams wait for it
@@ -2404,6 +2442,7 @@ int crt_refit_device(crt_ctx* c, uint32_t bvh, const float* d_positions, uint32_
     memcpy(&f.rootBox[6 * (size_t)bvh], back + 16, 24);
     if (P.rootCode & crt::kPlanInterior) memcpy(f.geom.data() + (size_t)(f.pairBase[bvh] + (P.rootCode & ~crt::kPlanInterior)) * 64u, back, 64);   // the mirror's copy of the root's pair
     if (f.kind == CRT_SCENE_FILE) set_root(c, CRT_SCENE_FILE, back + 16, back + 19);      // rootPair from the mirror, dispatch-order bounds; a BLAS's box reaches the TLAS through the caller
+    if (bvh < c->blasGrid.current.size()) c->blasGrid.current[bvh] = 0;    // crt_build_grid_device(bvh) makes it current again
     drop_blas_sets(c);
     if (rootBox) memcpy(rootBox, back + 16, 24);
     return CRT_OK;
@@ -2476,6 +2515,224 @@ int crt_update_transforms_device(crt_ctx* c, const float* d_T, uint32_t blasCoun
             o.leftRight = leaf ? 0u : ((n.ref & 0x7fffu) | (((n.ref >> 15) & 0x7fffu) << 16));
             o.BLAS = leaf ? (n.ref & 0xffffu) : 0u;
         }
+    return CRT_OK;
+}
+
+// ---- crt_build_grid_device: Grid::Build / BLASGrid::Build of one BVH's triangles on the device, from positions in device memory (device/grid_build.hip) ----
+// one bound from its key (grid_build.hip): the ordered value back to the float's bits, the sign of a zero from the low bit
+static float grid_bound_of(unsigned long long key)
+{
+    const uint32_t ord = (uint32_t)(key >> 32);
+    uint32_t bits = (ord & 0x80000000u) ? (ord & 0x7fffffffu) : ~ord;
+    if (bits == 0u && (key & 1ull)) bits = 0x80000000u;
+    float v; memcpy(&v, &bits, 4);
+    return v;
+}
+
+// scratch of the build that grows on demand; the previous build may still be using it, so the host waits for that build first (earlier work only)
+static int grow_grid_scratch(crt_ctx* c, void** p, size_t* cap, size_t need /* 4-byte words */)
+{
+    if (need <= *cap) return 0;
+    if (c->gridBuilt) HIPCK(c, hipEventSynchronize(c->gridDone));
+    if (*p) { (void)hipFree(*p); *p = nullptr; *cap = 0; }
+    HIPCK(c, hipMalloc(p, need * 4u));
+    *cap = need;
+    return 0;
+}
+
+int crt_build_grid_device(crt_ctx* c, uint32_t bvh, const float* d_positions, uint32_t triCount, void* stream)
+{
+    const char* const me = "crt_build_grid_device";
+    if (!c) return CRT_ERR_INVALID;
+    if (c->havePrim) return c->fail(CRT_ERR_UNSUPPORTED, "%s: the PrimitiveScene has no triangles", me);
+    if (!c->haveScene) return c->fail(CRT_ERR_STATE, "%s before crt_upload_scene", me);
+    crt_ctx::Flat& f = c->flat;
+    const bool tlas = f.kind == CRT_SCENE_TLAS;
+    const uint32_t N = (uint32_t)f.triCount.size();
+    if (bvh >= N) return c->fail(CRT_ERR_INVALID, "%s: BVH %u of a scene with %u", me, bvh, N);
+    if (triCount != f.triCount[bvh]) return c->fail(CRT_ERR_INVALID, "%s: %u triangles, the uploaded BVH %u has %u", me, triCount, bvh, f.triCount[bvh]);
+    if (triCount == 0 || triCount > 0x7fffffffu / 3u) return c->fail(CRT_ERR_UNSUPPORTED, "%s: 1 .. (2^31-1)/3 triangles", me);
+    crt_ctx::BlasGrid& bg = c->blasGrid;
+    if (tlas && (!bg.held || bg.desc.size() != N)) return c->fail(CRT_ERR_STATE, "%s: a two-level scene needs a grid set uploaded earlier (crt_upload_blas_accel(CRT_ACCEL_GRID)): the other BLASes' parts are carried over", me);
+    HIPCK(c, hipSetDevice(c->cfg.device));
+    int r;
+    if ((r = check_device_buffer(c, d_positions, (size_t)triCount * 36u, me))) return r;
+    hipStream_t st = nullptr;
+    if ((r = caller_stream(c, stream, me, &st))) return r;
+    // ---- what the context keeps for the build ----
+    c->freeRetired(false);
+    if (!c->gridBlocks && !(c->gridBlocks = crt_grid_build_blocks(c->cfg.device))) return c->fail(CRT_ERR_DEVICE, "%s: the device's compute units / occupancy could not be asked", me);
+    if (!c->dGridState) HIPCK(c, hipMalloc((void**)&c->dGridState, sizeof(crt::GridBuildState)));
+    if (!c->hGridState) HIPCK(c, hipHostMalloc((void**)&c->hGridState, sizeof(crt::GridBuildState), hipHostMallocDefault));
+    if (!c->dGridChunks) HIPCK(c, hipMalloc((void**)&c->dGridChunks, crt_grid_scan_chunks(128u * 128u * 128u) * 8u));
+    for (hipEvent_t* e : {&c->gridBack, &c->gridDone}) if (!*e) HIPCK(c, hipEventCreateWithFlags(e, hipEventDisableTiming));
+    if (g_hooks) for (hipEvent_t* e : {&c->gridT0, &c->gridT1}) if (!*e) HIPCK(c, hipEventCreate(e));
+    // The build reads the caller's positions and the LeafTri id words (which no update changes) and writes buffers of its own, so it is ordered behind nothing but
+    // the scene's last in-place update and the previous build (whose scratch it reuses); earlier renders and queries are not waited for.
+    if (c->sceneReady) HIPCK(c, hipStreamWaitEvent(st, c->sceneReady, 0));
+    if (c->gridBuilt) HIPCK(c, hipStreamWaitEvent(st, c->gridDone, 0));
+    if (g_hooks) HIPCK(c, hipEventRecord(c->gridT0, st));
+    // ---- a. bounds + finiteness; THE FIRST HOST WAIT: the resolution is computed on the host from the bounds ----
+    HIPCK(c, crt_launch_grid_bounds(d_positions, triCount, c->dGridState, c->gridBlocks, st));
+    HIPCK(c, hipMemcpyAsync(c->hGridState, c->dGridState, sizeof(crt::GridBuildState), hipMemcpyDeviceToHost, st));
+    HIPCK(c, hipEventRecord(c->gridBack, st));
+    auto t0 = std::chrono::steady_clock::now();
+    HIPCK(c, hipEventSynchronize(c->gridBack));
+    c->gridWaitMs[0] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (c->hGridState->nonFinite) return c->fail(CRT_ERR_INVALID, "%s: a position component is not finite", me);
+    // ---- b. localBounds as aabb::Grow folds them from +-1e34, then the resolution lines shared with the host build ----
+    crt::GridParams gp{}; float hi[3], size[3], cell[3]; int res[3];
+    for (int k = 0; k < 3; k++) {
+        const float lo = grid_bound_of(c->hGridState->key[k]), up = grid_bound_of(c->hGridState->key[3 + k]);
+        gp.lo[k] = 1e34f < lo ? 1e34f : lo; hi[k] = -1e34f > up ? -1e34f : up;
+        size[k] = hi[k] - gp.lo[k];
+    }
+    crt::grid_resolution(size, (int)triCount, res, cell);
+    for (int k = 0; k < 3; k++) { gp.res[k] = res[k]; gp.cell[k] = cell[k]; }
+    const uint32_t cells = (uint32_t)res[0] * (uint32_t)res[1] * (uint32_t)res[2];
+    // ---- the new grid's buffers: a FileScene's own arrays, or the set's concatenated arrays with this BLAS's part at its re-based place ----
+    uint64_t cellBase = 0, allCells = (uint64_t)cells + 1u;
+    if (tlas) { allCells = 0; for (uint32_t b = 0; b < N; b++) { if (b == bvh) cellBase = allCells; allCells += (uint64_t)(b == bvh ? cells : bg.cells[b]) + 1u; } }
+    if (allCells > 0xffffffffull) return c->fail(CRT_ERR_UNSUPPORTED, "%s: the grid set has too many cells", me);
+    std::vector<void*> fresh; void* pinned = nullptr;
+    auto undo = [&]() { (void)hipStreamSynchronize(st); for (void* p : fresh) (void)hipFree(p); if (pinned) (void)hipHostFree(pinned); };
+    auto alloc = [&](size_t bytes, void** out) -> int {
+        *out = nullptr; if (!bytes) return 0;
+        const hipError_t e = hipMalloc(out, bytes);
+        if (e != hipSuccess) { (void)hipGetLastError(); *out = nullptr; return c->fail(CRT_ERR_DEVICE, "%s: hipMalloc(%zu): %s", me, bytes, hipGetErrorString(e)); }
+        fresh.push_back(*out); return 0;
+    };
+#define GRIDCK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { undo(); return c->hip(e_, #call); } } while (0)
+    uint32_t* newStart = nullptr;
+    if ((r = alloc((size_t)allCells * 4u, (void**)&newStart))) { undo(); return r; }
+    // ---- c, d. count + exclusive scan; THE SECOND HOST WAIT: cellRefs is sized from the total ----
+    GRIDCK(crt_launch_grid_count(d_positions, triCount, &gp, cells, newStart + cellBase, c->dGridChunks, c->dGridState, c->gridBlocks, st));
+    GRIDCK(hipMemcpyAsync(c->hGridState, c->dGridState, sizeof(crt::GridBuildState), hipMemcpyDeviceToHost, st));
+    GRIDCK(hipEventRecord(c->gridBack, st));
+    t0 = std::chrono::steady_clock::now();
+    GRIDCK(hipEventSynchronize(c->gridBack));
+    c->gridWaitMs[1] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    const unsigned long long total64 = c->hGridState->total;
+    uint64_t refBase = 0, allRefs = total64, triOff = 0, allTris = triCount;
+    if (tlas) {
+        allRefs = 0; allTris = 0;
+        for (uint32_t b = 0; b < N; b++) { if (b == bvh) { refBase = allRefs; triOff = allTris; } allRefs += b == bvh ? total64 : bg.refs[b]; allTris += f.triCount[b]; }
+    }
+    if (total64 > 0x7fffffffull || allRefs > 0xffffffffull) { undo(); return c->fail(CRT_ERR_UNSUPPORTED, "%s: %llu cell references (at most 2^31-1)", me, total64); }
+    const uint32_t total = (uint32_t)total64;
+    int32_t* newRefs = nullptr; crt::AltTri* newTris = nullptr; crt::BlasAltDesc* newDesc = nullptr;
+    if ((r = alloc((size_t)allRefs * 4u, (void**)&newRefs)) || (r = alloc((size_t)allTris * sizeof(crt::AltTri), (void**)&newTris)) ||
+        (r = grow_grid_scratch(c, (void**)&c->dGridCursor, &c->gridCursorCap, (size_t)cells)) || (r = grow_grid_scratch(c, (void**)&c->dGridUnsorted, &c->gridUnsortedCap, (size_t)total))) { undo(); return r; }
+    std::vector<crt::BlasAltDesc> desc;
+    if (tlas) {
+        // the other BLASes' parts, device to device, and the descriptors re-based for the new sizes
+        const crt::TlasAltDev& old = c->blasAlt[1];
+        desc = bg.desc;
+        uint64_t cb = 0, rb = 0, tb = 0;
+        for (uint32_t b = 0; b < N; b++) {
+            const crt::BlasAltDesc& od = bg.desc[b]; crt::BlasAltDesc& nd = desc[b];
+            const uint64_t nc = (uint64_t)(b == bvh ? cells : bg.cells[b]) + 1u, nr = b == bvh ? total : bg.refs[b], nt = f.triCount[b];
+            nd.cellBase = (uint32_t)cb; nd.cellRefBase = (uint32_t)rb; nd.triBase = (uint32_t)tb;
+            if (b == bvh) { for (int k = 0; k < 3; k++) { nd.res[k] = res[k]; nd.cell[k] = cell[k]; nd.lo[k] = gp.lo[k]; nd.hi[k] = hi[k]; } }
+            else {
+                GRIDCK(hipMemcpyAsync(newStart + cb, old.cellStart + od.cellBase, (size_t)nc * 4u, hipMemcpyDeviceToDevice, st));
+                if (nr) GRIDCK(hipMemcpyAsync(newRefs + rb, old.cellRefs + od.cellRefBase, (size_t)nr * 4u, hipMemcpyDeviceToDevice, st));
+                GRIDCK(hipMemcpyAsync(newTris + tb, static_cast<const crt::AltTri*>(old.tris) + od.triBase, (size_t)nt * sizeof(crt::AltTri), hipMemcpyDeviceToDevice, st));
+            }
+            cb += nc; rb += nr; tb += nt;
+        }
+        if ((r = alloc(desc.size() * sizeof(crt::BlasAltDesc), (void**)&newDesc))) { undo(); return r; }
+        GRIDCK(hipHostMalloc(&pinned, desc.size() * sizeof(crt::BlasAltDesc), hipHostMallocDefault));      // read by the copy below after this call has returned: retired with the old set
+        memcpy(pinned, desc.data(), desc.size() * sizeof(crt::BlasAltDesc));
+        GRIDCK(hipMemcpyAsync(newDesc, pinned, desc.size() * sizeof(crt::BlasAltDesc), hipMemcpyHostToDevice, st));
+    }
+    // ---- e, f. fill, sort every cell ascending, the AltTri records ----
+    GRIDCK(crt_launch_grid_fill(d_positions, triCount, &gp, cells, newStart + cellBase, c->dGridCursor, c->dGridUnsorted, newRefs ? newRefs + refBase : nullptr, total, c->hScene.geom,
+                                (uint32_t)f.leafOff, (uint32_t)f.triBase[bvh], tlas ? 1 : 0, newTris + triOff, c->gridBlocks, st));
+    if (g_hooks) { GRIDCK(hipEventRecord(c->gridT1, st)); c->gridTimed = true; }
+    GRIDCK(hipEventRecord(c->gridDone, st));
+    c->gridBuilt = true;
+    // ---- the grid it replaces: still read by launches enqueued earlier, on any stream, and by this build's own copies.  The main stream is ordered behind all of them
+    // (as for an in-place update; behind the build through gridDone) and an event on it says when the old buffers are unread; everything submitted later waits for the build and takes the new pointers ----
+    crt_ctx::Retired old;
+    if (c->retiredEvents.empty()) { hipEvent_t e = nullptr; GRIDCK(hipEventCreateWithFlags(&e, hipEventDisableTiming)); c->retiredEvents.push_back(e); }
+    old.unread = c->retiredEvents.back(); c->retiredEvents.pop_back();
+    if ((r = order_behind_ahead(c)) || (r = order_behind_queries(c))) { c->retiredEvents.push_back(old.unread); undo(); return r; }
+    {
+        // ... and behind the build itself, which reads the old set on `st` (the other BLASes' parts, the pinned descriptors)
+        hipError_t e = st != c->stream ? hipStreamWaitEvent(c->stream, c->gridDone, 0) : hipSuccess;
+        if (e == hipSuccess) e = hipEventRecord(old.unread, c->stream);
+        if (e != hipSuccess) { c->retiredEvents.push_back(old.unread); undo(); return c->hip(e, "hipEventRecord(retired)"); }
+    }
+#undef GRIDCK
+    old.pinned = pinned;
+    if (tlas) {
+        old.ptrs.swap(c->blasAllocs[1]); c->blasAllocs[1] = fresh;
+        crt::TlasAltDev& tl = c->blasAlt[1];
+        tl.desc = newDesc; tl.tris = newTris; tl.cellStart = newStart; tl.cellRefs = newRefs; tl.kdNodes = nullptr; tl.kdRefs = nullptr; tl.kdStack = 0;
+        bg.desc = desc; bg.cells[bvh] = cells; bg.refs[bvh] = total; bg.current[bvh] = 1;
+        bool all = true; for (uint8_t k : bg.current) all = all && k;
+        c->haveBlas[1] = all;                                              // live again once every BLAS's part is of its current vertices
+    } else {
+        old.ptrs.swap(c->altAllocs[1]);
+        for (void* p : fresh) if (p != (void*)newTris) c->altAllocs[1].push_back(p);             // (newTris is not an accelerator array: it becomes altTris)
+        if (c->altTris) old.ptrs.push_back(c->altTris);
+        c->altTris = newTris; c->altTriCount = triCount;
+        crt::AltAccelDev& a = c->alt;
+        a.tris = newTris; a.cellStart = newStart; a.cellRefs = newRefs;
+        for (int k = 0; k < 3; k++) { a.res[k] = res[k]; a.cell[k] = cell[k]; a.lo[k] = gp.lo[k]; a.hi[k] = hi[k]; }
+        c->haveGrid = true; c->gridRefCount = total;
+        // the KD-tree shares altTris and its boxes are of the old positions: absent, as a refit marks a two-level set (its arrays go with the next KD-tree upload)
+        c->haveKd = false; a.kdNodes = nullptr; a.kdRefs = nullptr; a.kdStack = 0;
+        if (c->renderAccel == CRT_ACCEL_KDTREE) c->renderAccel = 0;
+    }
+    c->retired.push_back(std::move(old));
+    c->sceneReady = c->gridDone;                                           // launches submitted later wait for the build on their own stream
+    c->epoch++;                                                            // (the main stream already waits for the build: see the retired set's event above)
+    return CRT_OK;
+}
+
+int crt_get_grid(crt_ctx* c, uint32_t bvh, int32_t res[3], float cellSize[3], float gridMin[3], float gridMax[3], uint32_t* cellCount, uint32_t* refCount, uint32_t* cellStart, int32_t* cellRefs)
+{
+    if (!c) return CRT_ERR_INVALID;
+    if (!c->haveScene) return c->fail(CRT_ERR_STATE, "crt_get_grid before crt_upload_scene");
+    const crt_ctx::Flat& f = c->flat;
+    if (bvh >= f.triCount.size()) return c->fail(CRT_ERR_INVALID, "crt_get_grid: BVH %u of a scene with %zu", bvh, f.triCount.size());
+    const bool tlas = f.kind == CRT_SCENE_TLAS;
+    if (tlas ? !(c->haveBlas[1] && c->blasGrid.held) : !c->haveGrid) return c->fail(CRT_ERR_STATE, "crt_get_grid: no live grid (not uploaded, or dropped by a refit and not rebuilt)");
+    const int32_t* r; const float *cs, *lo, *hi; uint32_t cells, refs; const uint32_t* dStart; const int32_t* dRefs;
+    if (tlas) {
+        const crt::BlasAltDesc& d = c->blasGrid.desc[bvh];
+        r = d.res; cs = d.cell; lo = d.lo; hi = d.hi; cells = c->blasGrid.cells[bvh]; refs = c->blasGrid.refs[bvh];
+        dStart = c->blasAlt[1].cellStart + d.cellBase; dRefs = c->blasAlt[1].cellRefs ? c->blasAlt[1].cellRefs + d.cellRefBase : nullptr;
+    } else {
+        const crt::AltAccelDev& a = c->alt;
+        r = a.res; cs = a.cell; lo = a.lo; hi = a.hi; cells = (uint32_t)a.res[0] * (uint32_t)a.res[1] * (uint32_t)a.res[2]; refs = c->gridRefCount;
+        dStart = a.cellStart; dRefs = a.cellRefs;
+    }
+    for (int k = 0; k < 3; k++) { if (res) res[k] = r[k]; if (cellSize) cellSize[k] = cs[k]; if (gridMin) gridMin[k] = lo[k]; if (gridMax) gridMax[k] = hi[k]; }
+    if (cellCount) *cellCount = cells;
+    if (refCount) *refCount = refs;
+    if (!cellStart && !cellRefs) return CRT_OK;
+    HIPCK(c, hipSetDevice(c->cfg.device));
+    if (c->gridBuilt) HIPCK(c, hipEventSynchronize(c->gridDone));          // a device build still running (an uploaded grid's copies were synchronous)
+    if (cellStart) HIPCK(c, hipMemcpy(cellStart, dStart, ((size_t)cells + 1u) * 4u, hipMemcpyDeviceToHost));
+    if (cellRefs && refs) HIPCK(c, hipMemcpy(cellRefs, dRefs, (size_t)refs * 4u, hipMemcpyDeviceToHost));
+    return CRT_OK;
+}
+
+// tests: what crt_set_render_accel last selected, after the calls that reset it (an upload of the kind, a refit that drops a set, a grid rebuild that marks the KD-tree absent)
+extern "C" int crt_debug_render_accel(crt_ctx* c) { return c ? c->renderAccel : CRT_ERR_INVALID; }
+
+// tools/grid_device_cost.py: the last crt_build_grid_device's duration on its stream (HIP events, first launch to last; it includes the two host round trips in
+// between) and the wall time of its two host waits (debug hooks only)
+extern "C" int crt_debug_grid_build_ms(crt_ctx* c, float* streamMs, double waitMs[2])
+{
+    if (!c || !streamMs || !waitMs) return CRT_ERR_INVALID;
+    if (!c->gridTimed) return c->fail(CRT_ERR_STATE, "crt_debug_grid_build_ms: no timed crt_build_grid_device (debug hooks off?)");
+    HIPCK(c, hipEventSynchronize(c->gridT1));
+    HIPCK(c, hipEventElapsedTime(streamMs, c->gridT0, c->gridT1));
+    waitMs[0] = c->gridWaitMs[0]; waitMs[1] = c->gridWaitMs[1];
     return CRT_OK;
 }
 

@@ -68,6 +68,15 @@ hipError_t crt_launch_refit(char* geom, uint32_t leafOff, uint32_t pairBase, uin
     uint32_t rootCode, float* out, hipStream_t stream);
 hipError_t crt_launch_probe_f32(int op, const void* in, void* out, uint32_t n, hipStream_t stream);
 
+// ---- grid_build.hip ----
+uint32_t crt_grid_build_blocks(int device);
+size_t crt_grid_scan_chunks(uint32_t cells);
+hipError_t crt_launch_grid_bounds(const float* pos, uint32_t triCount, crt::GridBuildState* state, uint32_t maxBlocks, hipStream_t stream);
+hipError_t crt_launch_grid_count(const float* pos, uint32_t triCount, const crt::GridParams* g, uint32_t cells, uint32_t* counts, unsigned long long* chunkSums, crt::GridBuildState* state,
+    uint32_t maxBlocks, hipStream_t stream);
+hipError_t crt_launch_grid_fill(const float* pos, uint32_t triCount, const crt::GridParams* g, uint32_t cells, const uint32_t* cellStart, uint32_t* cursor, int32_t* unsorted, int32_t* refs,
+    uint32_t total, const char* geom, uint32_t leafOff, uint32_t triBase, int globalIdx, crt::AltTri* tris, uint32_t maxBlocks, hipStream_t stream);
+
 // ---- tlas_build.hip ----
 hipError_t crt_launch_tlas_build(const char* geom, uint32_t instOff, const float* T, const float* rootBox, uint32_t blasCount, uint32_t pairRel, uint32_t instRel, void* out,
     hipStream_t stream);

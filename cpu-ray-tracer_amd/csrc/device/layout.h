@@ -163,6 +163,11 @@ struct TlasAltDev {                       // passed by value, like AltAccelDev
     uint32_t kdStack;                     // KD stack entries per lane: the deepest KD-tree's height + 1 (0 for a grid set)
 };
 
+// crt_build_grid_device (grid_build.hip): the grid the host derived from the bounds, handed to the count / fill kernels by value, and the block the kernels report
+// through: the six bound keys (min x y z, max x y z: ordered value << 32 | position << 1 | sign of a zero), the non-finite flag, the reference count.
+struct GridParams { int32_t res[3]; float cell[3]; float lo[3]; };
+struct alignas(16) GridBuildState { unsigned long long key[6]; unsigned long long total; uint32_t nonFinite; uint32_t pad; };
+
 // PrimitiveScene at one animation time (crt_primitive_scene flattened by crt_upload_primitive_scene; kernels in render_prim.hip), passed to the kernels by value
 struct PrimDev {
     float quadInvT[12], quadNrm[3], quadSize;

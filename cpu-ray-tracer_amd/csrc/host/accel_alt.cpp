@@ -1,6 +1,7 @@
 // accel_alt.cpp — host builds of KDTree and Grid (see accel_alt.h).  The node order / cell contents must equal the reference's because
 // Ray::traversed / Ray::tested and, through the visiting order, ties between equal hits depend on them.
 #include "accel_alt.h"
+#include "grid_resolution.h"
 
 #include <cmath>
 
@@ -85,13 +86,10 @@ void Grid::Build()
 {
     for (const Tri& t : triangles) localBounds.Grow(tri_bounds(t));
     const float3 gridSize = localBounds.bmax3 - localBounds.bmin3;
-    const float cubeRoot = powf(5 * GetTriangleCount() / (gridSize.x * gridSize.y * gridSize.z), 1 / 3.f);
-    for (int i = 0; i < 3; i++) {
-        int r = static_cast<int>(floorf(gridSize[i] * cubeRoot));
-        r = r < 128 ? r : 128;                                                  // max(1, min(r, 128))
-        resolution[i] = r > 1 ? r : 1;
-    }
-    cellSize = float3(gridSize.x / resolution[0], gridSize.y / resolution[1], gridSize.z / resolution[2]);
+    const float size3[3] = {gridSize.x, gridSize.y, gridSize.z};
+    float cell3[3];
+    grid_resolution(size3, GetTriangleCount(), resolution, cell3);             // grid.cpp:14-26, shared with crt_build_grid_device
+    cellSize = float3(cell3[0], cell3[1], cell3[2]);
     const size_t cells = (size_t)resolution[0] * resolution[1] * resolution[2];
     // two passes instead of a std::vector per cell: count, prefix, fill — triangles are visited in index order in both, so every cell lists them
     // in the reference's push_back order

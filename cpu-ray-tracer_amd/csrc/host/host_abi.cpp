@@ -12,7 +12,9 @@ using namespace crt;
 namespace { thread_local std::string g_err; }
 
 struct crt_host_scene { BaseScene* scene = nullptr; FileScene* file = nullptr; TLASFileScene* tlas = nullptr; KDTree* kd = nullptr; Grid* grid = nullptr;
-                        std::vector<BLASKDTree> blasKd; std::vector<BLASGrid> blasGrid; };   // TLAS scene: one structure per BLAS
+                        std::vector<BLASKDTree> blasKd; std::vector<BLASGrid> blasGrid;               // TLAS scene: one structure per BLAS
+                        std::vector<uint8_t> gridPending;
+                        bool gridDeviceBuilt = false; };                                               // the grid mirror's cells are the device's, its triangles still the host's old ones                                            // BVHs whose grid was rebuilt on the device and is not mirrored yet
 struct crt_host_renderer { Renderer* r = nullptr; };
 
 // a BVH whose host arrays are stale (refitted on the device only): the calls that would send those arrays are refused
@@ -157,6 +159,64 @@ int crt_host_scene_update_transforms_device(crt_host_scene* s, crt_ctx* ctx, con
     return CRT_OK;
     GUARD_END(CRT_ERR_DEVICE)
 }
+// the mirror of one grid from the device's (crt_get_grid); false: no live grid (a two-level set still dropped)
+static bool mirror_grid(crt_ctx* ctx, uint32_t bvh, Grid& g, int* rc)
+{
+    int32_t res[3]; float cs[3], lo[3], hi[3]; uint32_t cells = 0, refs = 0;
+    *rc = crt_get_grid(ctx, bvh, res, cs, lo, hi, &cells, &refs, nullptr, nullptr);
+    if (*rc == CRT_ERR_STATE) { *rc = CRT_OK; return false; }
+    if (*rc != CRT_OK) return false;
+    g.cellStart.assign((size_t)cells + 1, 0u); g.cellTris.assign(refs, 0);
+    *rc = crt_get_grid(ctx, bvh, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, g.cellStart.data(), refs ? g.cellTris.data() : nullptr);
+    if (*rc != CRT_OK) return false;
+    for (int k = 0; k < 3; k++) g.resolution[k] = res[k];
+    g.cellSize = float3(cs[0], cs[1], cs[2]); g.localBounds.bmin3 = float3(lo[0], lo[1], lo[2]); g.localBounds.bmax3 = float3(hi[0], hi[1], hi[2]);
+    return true;
+}
+int crt_host_scene_build_grid_device(crt_host_scene* s, crt_ctx* ctx, int i, const float* d_positions, uint32_t triCount, void* stream)
+{
+    if (!s || !ctx) { g_err = "null argument"; return CRT_ERR_INVALID; }
+    GUARD_BEGIN
+    const int count = s->file ? 1 : (int)s->tlas->tlas.blas.size();
+    if (i < 0 || i >= count) { g_err = "bvh index out of range"; return CRT_ERR_INVALID; }
+    int rc = crt_build_grid_device(ctx, (uint32_t)i, d_positions, triCount, stream);
+    if (rc != CRT_OK) { g_err = crt_last_error(ctx); return rc; }
+    s->gridDeviceBuilt = true;
+    if (s->file) {
+        if (!s->grid) { s->grid = new Grid(); s->grid->triangles = s->file->acc.triangles; }
+        mirror_grid(ctx, 0, *s->grid, &rc);
+    } else {
+        const std::vector<BLASBVH*>& bl = s->tlas->tlas.blas;
+        s->gridPending.resize(bl.size(), 0);
+        if (s->blasGrid.size() != bl.size()) {                                       // the set came through crt_upload_blas_accel directly: mirror every BLAS
+            s->blasGrid.assign(bl.size(), BLASGrid());
+            for (size_t k = 0; k < bl.size(); k++) { s->blasGrid[k].objIdx = bl[k]->objIdx; s->blasGrid[k].triangles = bl[k]->triangles; s->gridPending[k] = 1; }
+        }
+        s->gridPending[(size_t)i] = 1;
+        for (size_t k = 0; k < bl.size() && rc == CRT_OK; k++)
+            if (s->gridPending[k] && mirror_grid(ctx, (uint32_t)k, s->blasGrid[k], &rc)) s->gridPending[k] = 0;
+    }
+    if (rc != CRT_OK) g_err = crt_last_error(ctx);
+    return rc;
+    GUARD_END(CRT_ERR_DEVICE)
+}
+int crt_host_grid_build(const float* positions, uint32_t triCount, int32_t res[3], float f9[9], uint32_t* refCount, uint32_t* cellStart, int32_t* cellRefs)
+{
+    if (!positions || !triCount) { g_err = "null argument"; return CRT_ERR_INVALID; }
+    GUARD_BEGIN
+    Grid g; g.triangles.resize(triCount);
+    for (uint32_t t = 0; t < triCount; t++) {
+        Tri& tr = g.triangles[t]; memset(&tr, 0, sizeof(Tri));
+        memcpy(tr.vertex0, positions + 9 * (size_t)t, 12); memcpy(tr.vertex1, positions + 9 * (size_t)t + 3, 12); memcpy(tr.vertex2, positions + 9 * (size_t)t + 6, 12);
+    }
+    g.Build();
+    for (int k = 0; k < 3; k++) { if (res) res[k] = g.resolution[k]; if (f9) { f9[k] = g.cellSize[k]; f9[3 + k] = g.localBounds.bmin3[k]; f9[6 + k] = g.localBounds.bmax3[k]; } }
+    if (refCount) *refCount = (uint32_t)g.cellTris.size();
+    if (cellStart) memcpy(cellStart, g.cellStart.data(), g.cellStart.size() * 4);
+    if (cellRefs && !g.cellTris.empty()) memcpy(cellRefs, g.cellTris.data(), g.cellTris.size() * 4);
+    return CRT_OK;
+    GUARD_END(CRT_ERR_INVALID)
+}
 // BLASBVH::SetTransform(T) of instance i (blas_bvh.cpp:363-374: T, invT = FastInvertedTransformNoScale, world bounds of the 8 root-box corners)
 // followed by TLASBVH::Build (tlas_bvh.cpp:17-55), as an animation loop does per frame; crt_host_scene_update then moves it to the device
 int crt_host_scene_set_transform(crt_host_scene* s, int i, const float T[16])
@@ -285,6 +345,7 @@ int crt_host_scene_build_alt(crt_host_scene* s, int kind)
 {
     if (!s) { g_err = "null argument"; return CRT_ERR_INVALID; }
     GUARD_BEGIN
+    if (kind == CRT_ACCEL_GRID) s->gridDeviceBuilt = false;                          // cells and triangles are both the host's again
     if (s->tlas) {
         const std::vector<BLASBVH*>& bl = s->tlas->tlas.blas;
         if (kind == CRT_ACCEL_KDTREE) {
@@ -330,6 +391,11 @@ static int describe_blas_alt(crt_host_scene* s, int kind, int i, crt_alt_accel& 
 int crt_host_scene_upload_alt(crt_host_scene* s, crt_ctx* ctx, int kind)
 {
     if (!s || !ctx) { g_err = "null argument"; return CRT_ERR_INVALID; }
+    if (kind == CRT_ACCEL_GRID && s->gridDeviceBuilt) {
+        g_err = "crt_host_scene_upload_alt: the grid mirror was refreshed from a device build (crt_host_scene_build_grid_device): its cells are of positions the host triangles never "
+                "saw, so the upload would pair new cells with old vertices; crt_host_scene_build_alt(CRT_ACCEL_GRID) builds it from the host's triangles again";
+        return CRT_ERR_STATE;
+    }
     if (s->tlas) {
         std::vector<crt_alt_accel> set(s->tlas->tlas.blas.size());
         for (size_t i = 0; i < set.size(); i++) { const int rc = describe_blas_alt(s, kind, (int)i, set[i]); if (rc) return rc; }

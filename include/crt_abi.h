@@ -199,6 +199,42 @@ int  crt_refit_device(crt_ctx* ctx, uint32_t bvh, const float* d_positions /* 9 
  * a scene uploaded with more than 2 * bvhCount TLAS nodes (CRT_ERR_UNSUPPORTED). */
 int  crt_update_transforms_device(crt_ctx* ctx, const float* d_T /* 16 * blasCount, device */, uint32_t blasCount, void* stream,
                                   crt_tlas_node* tlasOut /* host, 2 * blasCount; may be NULL */);
+/* Grid::Build / BLASGrid::Build (infra/grid.cpp:4-50) for ONE uploaded BVH's triangle array on the device, from vertex positions that already live in device memory:
+ * the uniform grid rebuilt from scratch, so that the structures that have no Refit follow deforming geometry without a host round trip.  ABI version 3 still: both
+ * entries are additions, detected by symbol.  d_positions is the array crt_refit_device takes (vertex0, vertex1, vertex2 per triangle, the reference's triangles[]
+ * order); the pointer and `stream` are checked as there.  What the call leaves on the device equals, byte for byte, what Grid::Build over those triangles followed by
+ * crt_upload_alt_accel / crt_upload_blas_accel would leave: resolution, cellSize, gridMin / gridMax (signed zeros as the reference's _mm_min_ps / _mm_max_ps fold
+ * leaves them: of -0 and +0 tying for an extreme, the last in (triangle, vertex) order), cellStart (x-major cells, prefix array), cellRefs with every cell's triangle
+ * indices ascending, and the triangle records (v0, v1 - v0, v2 - v0; the ids a hit reports are the uploaded scene's).  A rebuilt grid has the quality of a fresh build.
+ * CRT_SCENE_FILE (bvh = 0): works with or without an earlier crt_upload_alt_accel(CRT_ACCEL_GRID); the grid becomes the scene's CRT_ACCEL_GRID structure and
+ * crt_set_render_accel(CRT_ACCEL_GRID) stays selected (the per-frame loop is refit, rebuild, render).  The KD-tree shares the triangle records and its boxes belong to
+ * the old positions, so a successful call marks it absent: a query with CRT_ACCEL_KDTREE is CRT_ERR_STATE, crt_set_render_accel goes back to 0 if it named the KD-tree.
+ * CRT_SCENE_TLAS (bvh = a BLAS): needs a grid set uploaded earlier through crt_upload_blas_accel(CRT_ACCEL_GRID, ..), else CRT_ERR_STATE (its buffers are still held
+ * after a refit dropped the set; the other BLASes' parts are carried over device to device, the descriptors re-based).  The context keeps a "grid current" flag per
+ * BLAS: an upload sets all, CRT_UPDATE_BOUNDS clears all, crt_refit_device(b) clears b's, this call sets b's; the grid set is live iff every flag is set.  So after a
+ * refit of BLAS b the set is dropped exactly as before, and is live again (queries; crt_set_render_accel must be called again) once crt_build_grid_device(b) has run.
+ * The KD set stays dropped.  The test of crt_upload_blas_accel that the grid's bounds equal the BVH root box is not applied: after Refit node 0's box legitimately
+ * differs from the true bounds (node 1 is skipped).  THE CALL TOUCHES NEITHER THE BVH, THE INSTANCES NOR THE TLAS: on a two-level scene the caller runs
+ * crt_refit_device (+ crt_update_transforms_device) for the same positions, otherwise the TLAS boxes cull for the old geometry.
+ * Ordering, as crt_refit_device / crt_update_transforms_device: the build runs on `stream` into buffers of its own; the grid it replaces keeps answering for
+ * everything enqueued earlier, on any stream, and everything submitted later sees the new one.  Retired buffers are freed by a later call, once an event recorded
+ * behind their last readers (the earlier launches and this build's own copies out of the old set) has completed.  Freeing them, and growing the build's scratch for
+ * a larger grid than any before, goes through hipFree, which may synchronise the whole device: such a call can also wait for work submitted after the earlier build.
+ * The promise "nothing submitted later is waited for" is that of the two waits below.  THE TWO HOST WAITS: the call reads the bounds back (the host computes resolution / cellSize from them, with the code the
+ * host build uses) and then the total reference count (the host sizes cellRefs from it); each waits for `stream` up to that point, for nothing submitted later.
+ * Refused with nothing modified, the previous grid still answering: no scene (CRT_ERR_STATE); a PrimitiveScene (CRT_ERR_UNSUPPORTED); bvh out of range, triCount
+ * different from the uploaded BVH's, d_positions NULL / a host pointer / memory of another device, a stream of another device, a non-finite position component
+ * (found by the bounds pass) (CRT_ERR_INVALID); more than 2^31-1 cell references (CRT_ERR_UNSUPPORTED); a failed device allocation (CRT_ERR_DEVICE).
+ * Cost: a cell's references are sorted by rank, quadratic in the cell's length, one wavefront per cell of more than 32.  A FLAT mesh (cloth at rest, a ground plane: an
+ * extent of 0 on an axis) gets resolution (1, 1, 1) from Grid::Build, so ALL its triangles are one cell: about n^2 / 64 steps per lane of a single wavefront — 10 k
+ * triangles a few milliseconds, 100 k about 1.6e8 steps (seconds), 1 M minutes of one kernel.  Such a grid is useless for traversal too (every ray tests every
+ * triangle); build those on the host or keep them on the BVH.  Meshes with volume have about 5 references per cell and do not meet this. */
+int  crt_build_grid_device(crt_ctx* ctx, uint32_t bvh, const float* d_positions /* 9 * triCount, device */, uint32_t triCount, void* stream);
+/* The live grid of a FileScene (bvh = 0) or of one BLAS of a two-level scene's set, uploaded or device-built: sizes first (any output may be NULL), then the arrays
+ * where the pointers are non-NULL (cellStart: cellCount + 1 entries, cellRefs: refCount).  Synchronous (it waits for a device build still running).  CRT_ERR_STATE
+ * when there is no live grid; bvh out of range is CRT_ERR_INVALID.  What lets a caller keep a host mirror of a device-built grid. */
+int  crt_get_grid(crt_ctx* ctx, uint32_t bvh, int32_t res[3], float cellSize[3], float gridMin[3], float gridMax[3], uint32_t* cellCount, uint32_t* refCount,
+                  uint32_t* cellStart /* cellCount + 1, or NULL */, int32_t* cellRefs /* refCount, or NULL */);
 int  crt_set_camera(crt_ctx* ctx, const float camPos[3], const float topLeft[3], const float topRight[3], const float bottomLeft[3]);
                                                                 /* Camera members used by GetPrimaryRay (camera.h:23-30) */
 

@@ -67,6 +67,16 @@ int  crt_host_scene_bvh_refit_device(crt_host_scene* scene, crt_ctx* ctx, int bv
  * back and leaves the host scene's T, invT, worldBounds and tlasNode as crt_host_scene_set_transform for every BLAS would have left them (the world boxes and the
  * node array are the device's own: identical, and right also after crt_host_scene_bvh_refit_device).  No crt_host_scene_update is needed afterwards. */
 int  crt_host_scene_update_transforms_device(crt_host_scene* scene, crt_ctx* ctx, const float* d_T, void* stream);
+/* The uniform grid of BVH `bvh` rebuilt on the device from positions in device memory (crt_build_grid_device; d_positions, triCount, stream as there), then the host
+ * scene's grid mirror refreshed through crt_get_grid: crt_host_scene_alt_info / _alt_copy (FileScene) and crt_host_scene_blas_alt_info / _blas_alt_copy (a two-level
+ * scene's BLAS) with CRT_ACCEL_GRID then describe the live grid.  While a two-level scene's set is still dropped (another BLAS was refitted and not rebuilt) the
+ * mirror of the rebuilt BLASes is refreshed by the call that makes the set live.  The mirror's triangle array stays the host scene's, which never saw the new
+ * positions: the mirror is for reading (alt_info / alt_copy), and crt_host_scene_upload_alt(CRT_ACCEL_GRID) — which would pair the new cells with triangle records of
+ * the old vertices — is refused with CRT_ERR_STATE until crt_host_scene_build_alt(CRT_ACCEL_GRID) has built the grid from the host's triangles again. */
+int  crt_host_scene_build_grid_device(crt_host_scene* scene, crt_ctx* ctx, int bvh, const float* d_positions, uint32_t triCount, void* stream);
+/* Grid::Build (infra/grid.cpp:4-50) on the host over bare positions (9 floats per triangle): what crt_build_grid_device is compared with for meshes that are no
+ * scene.  Sizes first (res, f9 = cellSize, bounds min, bounds max, refCount), the arrays where the pointers are non-NULL (cellStart: rx * ry * rz + 1, cellRefs: refCount). */
+int  crt_host_grid_build(const float* positions, uint32_t triCount, int32_t res[3], float f9[9], uint32_t* refCount, uint32_t* cellStart, int32_t* cellRefs);
 int  crt_host_scene_blas_transform(crt_host_scene* scene, int bvh, float T[16], float invT[16], float worldMin[3], float worldMax[3]);
 int  crt_host_scene_tlas_copy(crt_host_scene* scene, crt_tlas_node* nodes /* 2*blasCount */, uint32_t* nodesUsed);
 
