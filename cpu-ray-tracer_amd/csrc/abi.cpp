@@ -98,7 +98,7 @@ struct crt_ctx {
                   std::vector<uint64_t> pairBase, triBase; std::vector<uint32_t> nodesUsed, triCount; std::vector<char> geom;
                   std::vector<float> rootBox; } flat;     // rootBox: every BVH's node 0 box (min xyz, max xyz), what crt_upload_blas_accel checks the BLAS structures against
     char* hStage[2] = {nullptr, nullptr}; size_t stageBytes[2] = {0, 0}; hipEvent_t stageCopied[2] = {nullptr, nullptr}; int stageFlip = 0;
-    hipEvent_t sceneReady = nullptr;      // recorded behind the last in-place scene update; render launches wait for it on their stream
+    hipEvent_t sceneReady = nullptr, writeFence = nullptr;   // the scene-write protocol (begin_scene_write): the last write's `done` event, the protocol's own fence
     bool havePrim = false; crt::PrimDev prim{}; uint32_t* dPrimTex = nullptr;       // crt_upload_primitive_scene: PrimitiveScene instead of a triangle scene
     int renderAccel = 0;                  // crt_set_render_accel: 0 = the scene's BVH / TLAS, CRT_ACCEL_KDTREE / CRT_ACCEL_GRID = Sample and Trace go through that structure
     crt::AltAccelDev alt{}; bool haveKd = false, haveGrid = false; std::vector<void*> altAllocs[2]; crt::AltTri* altTris = nullptr; uint32_t altTriCount = 0;   // KD-tree [0] / grid [1] buffers
@@ -115,24 +115,33 @@ struct crt_ctx {
     struct QuerySlot { hipEvent_t done = nullptr; bool pending = false; } qslot[kQuerySlots];
     int qslotNext = 0;
     // crt_refit_device: per BVH the bottom-up plan of refit_box_kernel (device/refit.hip), built from the mirror's references by the first refit of that BVH and
-    // freed with the scene; the root's pair + node 0's box come back through `hRefitBack` (pinned) behind the kernels, and `refitDone` is what sceneReady then names
+    // freed with the scene; the root's pair + node 0's box come back through `hBack` (pinned) behind the kernels, and `done` is what sceneReady then names
     struct RefitPlan { void* dPlan = nullptr; uint32_t* dLevelOff = nullptr; uint32_t levels = 0, rootCode = 0; bool built = false; };
     std::vector<RefitPlan> refitPlans; std::vector<void*> refitAllocs;
-    float* dRefitBack = nullptr; float* hRefitBack = nullptr; hipEvent_t refitFence = nullptr, refitDone = nullptr;
+    struct Refit {
+        float* dBack = nullptr; float* hBack = nullptr; hipEvent_t done = nullptr;
+        void release() { if (done) (void)hipEventDestroy(done); (void)hipFree(dBack); (void)hipHostFree(hBack); *this = Refit{}; }
+    } refit;
     // crt_update_transforms_device (device/tlas_build.hip): every BLAS's node-0 box on the device (6 floats each; written at upload, by CRT_UPDATE_BOUNDS and by
     // crt_refit_device on its stream, freed with the scene), the kernel's result block and its pinned copy (TlasBuildHeader + an image of [tlasOff, shadeOff)),
-    // and the events: `tlasBack` behind the read-back (the one host wait), `tlasDone` behind the copy into the geometry buffer (what sceneReady then names)
+    // and the events: `back` behind the read-back (the one host wait), `done` behind the copy into the geometry buffer (what sceneReady then names)
     float* dRootBox = nullptr;
-    char* dTlasBuild = nullptr; char* hTlasBack = nullptr; size_t tlasBuildBytes = 0;
-    hipEvent_t tlasFence = nullptr, tlasBack = nullptr, tlasDone = nullptr, tlasT0 = nullptr, tlasT1 = nullptr; bool tlasTimed = false;
+    struct TlasBuild {
+        char* dBuild = nullptr; char* hBack = nullptr; size_t bytes = 0;
+        hipEvent_t back = nullptr, done = nullptr, t0 = nullptr, t1 = nullptr; bool timed = false;
+        void release() { for (hipEvent_t e : {back, done, t0, t1}) if (e) (void)hipEventDestroy(e); (void)hipFree(dBuild); (void)hipHostFree(hBack); *this = TlasBuild{}; }
+    } tlasBuild;
     // crt_build_grid_device (device/grid_build.hip): the kernels' state block and its pinned copy, scratch (the scan's chunk sums, the fill's cursors and unsorted
-    // references, grown on demand), and the events: `gridBack` behind each of the two read-backs (the two host waits), `gridDone` behind the build (what sceneReady
-    // then names).  A grid the build replaces may still be read by launches enqueued earlier: its buffers go to `retired` with an event recorded on the main stream
+    // references, grown on demand), and the events: `back` behind each of the two read-backs (the two host waits), `done` behind the build (sceneReady names it)
+    struct GridBuild {
+        crt::GridBuildState* dState = nullptr; crt::GridBuildState* hState = nullptr;
+        unsigned long long* dChunks = nullptr; uint32_t* dCursor = nullptr; int32_t* dUnsorted = nullptr; size_t cursorCap = 0, unsortedCap = 0;
+        hipEvent_t back = nullptr, done = nullptr, t0 = nullptr, t1 = nullptr; bool built = false, timed = false; uint32_t blocks = 0;
+        double waitMs[2] = {0, 0};        // wall time of the last call's two host waits (crt_debug_grid_build_ms)
+        void release() { for (hipEvent_t e : {back, done, t0, t1}) if (e) (void)hipEventDestroy(e); for (void* p : {(void*)dState, (void*)dChunks, (void*)dCursor, (void*)dUnsorted}) (void)hipFree(p); (void)hipHostFree(hState); *this = GridBuild{}; }
+    } gridBuild;
+    // A grid the build replaces may still be read by launches enqueued earlier: its buffers go to `retired` with an event recorded on the main stream
     // once that is ordered behind those launches, and are freed by a later call that finds the event complete (or with the scene, which drains first).
-    crt::GridBuildState* dGridState = nullptr; crt::GridBuildState* hGridState = nullptr;
-    unsigned long long* dGridChunks = nullptr; uint32_t* dGridCursor = nullptr; int32_t* dGridUnsorted = nullptr; size_t gridCursorCap = 0, gridUnsortedCap = 0;
-    hipEvent_t gridBack = nullptr, gridDone = nullptr, gridT0 = nullptr, gridT1 = nullptr; bool gridBuilt = false, gridTimed = false; uint32_t gridBlocks = 0;
-    double gridWaitMs[2] = {0, 0};        // wall time of the last call's two host waits (crt_debug_grid_build_ms)
     struct Retired { std::vector<void*> ptrs; void* pinned = nullptr; hipEvent_t unread = nullptr; };
     std::deque<Retired> retired; std::vector<hipEvent_t> retiredEvents;
     uint32_t gridRefCount = 0;            // references of the FileScene's live grid (uploaded or built on the device)
@@ -268,25 +277,15 @@ int bvh_height(crt_ctx* c, const crt_bvh& b, uint32_t* heightOut)
 }
 
 // device queries on callers' streams that may still read the scene / accelerator buffers: the host waits for them (before buffers are freed or rewritten
-// by a synchronous copy) ...
+// by a synchronous copy); an in-place write makes the main stream wait instead (order_behind_queries)
 int wait_queries(crt_ctx* c)
 {
     for (auto& q : c->qslot) if (q.pending) { HIPCK(c, hipEventSynchronize(q.done)); q.pending = false; }
     return 0;
 }
 
-// ... or the main stream does (before an in-place copy on it): no host wait, as order_behind_ahead for render-ahead launches
-int order_behind_queries(crt_ctx* c)
-{
-    for (auto& q : c->qslot) {
-        if (!q.pending) continue;
-        const hipError_t e = hipEventQuery(q.done);
-        if (e == hipSuccess) { q.pending = false; continue; }
-        if (e != hipErrorNotReady) return c->hip(e, "hipEventQuery(query)");
-        HIPCK(c, hipStreamWaitEvent(c->stream, q.done, 0));
-    }
-    return 0;
-}
+// an event field that is created by its first use
+hipError_t ensure_event(hipEvent_t* e, unsigned flags = hipEventDisableTiming) { return *e ? hipSuccess : hipEventCreateWithFlags(e, flags); }
 
 // before the scene's or an accelerator set's buffers are freed: every launch that may still read them has finished (render streams first: the main stream's accumulates wait on them)
 int drain_all(crt_ctx* c)
@@ -397,18 +396,11 @@ void crt_destroy(crt_ctx* c)
     for (auto& q : c->qslot) if (q.done) { if (q.pending) (void)hipEventSynchronize(q.done); (void)hipEventDestroy(q.done); }   // device queries on callers' streams
     if (c->dQuerySlots) (void)hipFree(c->dQuerySlots);
     if (c->altReady) (void)hipEventDestroy(c->altReady);
-    if (c->refitFence) (void)hipEventDestroy(c->refitFence);
-    if (c->refitDone) (void)hipEventDestroy(c->refitDone);
-    if (c->dRefitBack) (void)hipFree(c->dRefitBack);
-    if (c->hRefitBack) (void)hipHostFree(c->hRefitBack);
-    for (hipEvent_t e : {c->tlasFence, c->tlasBack, c->tlasDone, c->tlasT0, c->tlasT1}) if (e) (void)hipEventDestroy(e);
-    if (c->dTlasBuild) (void)hipFree(c->dTlasBuild);
-    if (c->hTlasBack) (void)hipHostFree(c->hTlasBack);
+    if (c->writeFence) (void)hipEventDestroy(c->writeFence);
+    c->refit.release(); c->tlasBuild.release();
     c->freeScene();
-    for (hipEvent_t e : {c->gridBack, c->gridDone, c->gridT0, c->gridT1}) if (e) (void)hipEventDestroy(e);
+    c->gridBuild.release();
     for (hipEvent_t e : c->retiredEvents) (void)hipEventDestroy(e);
-    for (void* p : {(void*)c->dGridState, (void*)c->dGridChunks, (void*)c->dGridCursor, (void*)c->dGridUnsorted}) if (p) (void)hipFree(p);
-    if (c->hGridState) (void)hipHostFree(c->hGridState);
     for (auto& a : c->ahead) (void)hipEventDestroy(a.end);
     if (c->aheadStream) (void)hipStreamDestroy(c->aheadStream);
     for (auto& ev : c->evPool) { (void)hipEventDestroy(ev.a); (void)hipEventDestroy(ev.b); }
@@ -720,13 +712,75 @@ int crt_upload_scene(crt_ctx* c, const crt_scene_desc* sd)
     return CRT_OK;
 }
 
-// Writes on the main stream of data the render kernels read (tile order, block tables, job plans, in-place scene updates) assume the main stream is ordered
-// behind every render launch submitted so far — true for crt_render's launches (each one's accumulate waits for it there), not for crt_tick's render-ahead
-// launches, which nothing on the main stream waits for until their frames are committed: the main stream waits for them here first.
+// ---- the scene-write protocol ----
+// The geometry buffer, the node-0 boxes and the accelerator sets are read by launches on many streams and rewritten without a host wait for any of them.
+//   A WRITER brackets what it enqueues on its stream `st` with begin_scene_write(c, st) ... end_scene_write(c, st, done): begin orders the write behind everything
+//   submitted so far that may read the old bytes, end records `done` behind it and publishes it.  (crt_build_grid_device replaces buffers instead: it builds as a
+//   reader, then order_behind_readers, publish_scene_write, and the old buffers are retired behind an event recorded on the main stream after that.)
+//   A READER calls wait_scene(c, st) before it enqueues anything on `st` that reads the scene.
+// `sceneReady` names the `done` event of the last write; every write is ordered behind the one before it, so waiting for the last is waiting for all.  The main
+// stream is the meeting point: it is already behind every crt_render launch (each launch's accumulate waits for it there) and carries the host-buffer queries, so a
+// writer starts from it (`writeFence`) and hands back to it, and its own consumers see the write without a wait of their own.
+
+// Writes on the main stream of data the render kernels read (tile order, block tables, job plans, scene writes) assume it is ordered behind every render launch
+// submitted so far — not true for crt_tick's render-ahead launches, which nothing on it waits for until their frames are committed: it waits for them here first.
 static int order_behind_ahead(crt_ctx* c)
 {
     for (const auto& a : c->ahead) HIPCK(c, hipStreamWaitEvent(c->stream, a.end, 0));
     return 0;
+}
+
+// ... and for the device queries still in flight on callers' streams (no host wait; wait_queries is the host's form)
+static int order_behind_queries(crt_ctx* c)
+{
+    for (auto& q : c->qslot) {
+        if (!q.pending) continue;
+        const hipError_t e = hipEventQuery(q.done);
+        if (e == hipSuccess) { q.pending = false; continue; }
+        if (e != hipErrorNotReady) return c->hip(e, "hipEventQuery(query)");
+        HIPCK(c, hipStreamWaitEvent(c->stream, q.done, 0));
+    }
+    return 0;
+}
+
+static int wait_scene(crt_ctx* c, hipStream_t st)
+{
+    if (c->sceneReady) HIPCK(c, hipStreamWaitEvent(st, c->sceneReady, 0));
+    return 0;
+}
+
+// The main stream behind every launch submitted so far that may read the scene.  The epoch is bumped HERE, the one place every writer passes before its first byte
+// changes: an entry that fails later has already invalidated crt_tick's rendered-ahead frames, and a write refused after this point costs those frames only.
+static int order_behind_readers(crt_ctx* c)
+{
+    int r;
+    if ((r = order_behind_ahead(c)) || (r = order_behind_queries(c))) return r;
+    c->epoch++;
+    return 0;
+}
+
+static int begin_scene_write(crt_ctx* c, hipStream_t st)
+{
+    const int r = order_behind_readers(c);
+    if (r || st == c->stream) return r;                                    // (the main stream is behind the previous write already)
+    HIPCK(c, ensure_event(&c->writeFence));
+    HIPCK(c, hipEventRecord(c->writeFence, c->stream));                    // a wait takes the event as recorded at the call: one fence serves every write
+    HIPCK(c, hipStreamWaitEvent(st, c->writeFence, 0));
+    return wait_scene(c, st);
+}
+
+// `done`, recorded on `st` behind the write, is what readers wait for from now on, and the main stream follows
+static int publish_scene_write(crt_ctx* c, hipStream_t st, hipEvent_t done)
+{
+    c->sceneReady = done;
+    if (st != c->stream) HIPCK(c, hipStreamWaitEvent(c->stream, done, 0));
+    return 0;
+}
+
+static int end_scene_write(crt_ctx* c, hipStream_t st, hipEvent_t done)
+{
+    HIPCK(c, hipEventRecord(done, st));
+    return publish_scene_write(c, st, done);
 }
 
 // fills the TLAS sections of a host geometry image from the reference's TLASBVHNode array: per-node records with both reference forms, and the child
@@ -839,7 +893,6 @@ int crt_update_scene(crt_ctx* c, const crt_scene_desc* sd, uint32_t what)
         if (r || (r = check_tlas_height(c, tlasHeight))) return r;
     }
     // ---- apply ----
-    c->epoch++;
     size_t lo = SIZE_MAX, hi = 0;                                         // byte range of the geometry buffer to rewrite
     auto touch = [&](size_t a, size_t b) { if (a < lo) lo = a; if (b > hi) hi = b; };
     if (what & CRT_UPDATE_BOUNDS) {
@@ -860,8 +913,6 @@ int crt_update_scene(crt_ctx* c, const crt_scene_desc* sd, uint32_t what)
         }
         touch(0, (size_t)f.tlasOff);
         for (uint32_t bi = 0; bi < sd->bvhCount; bi++) { memcpy(&f.rootBox[6 * bi], sd->bvhs[bi].nodes[0].aabbMin, 12); memcpy(&f.rootBox[6 * bi + 3], sd->bvhs[bi].nodes[0].aabbMax, 12); }
-        std::fill(c->blasGrid.current.begin(), c->blasGrid.current.end(), (uint8_t)0);   // every BLAS's grid is of the old vertices
-        drop_blas_sets(c);
     }
     if (f.kind == CRT_SCENE_TLAS) {
         if (what & CRT_UPDATE_TRANSFORMS) {
@@ -873,25 +924,26 @@ int crt_update_scene(crt_ctx* c, const crt_scene_desc* sd, uint32_t what)
         touch((size_t)f.tlasOff, (size_t)f.shadeOff);
     }
     if (lo >= hi) return CRT_OK;
-    // In-place rewrite, no allocation of device memory and no host wait for the GPU: the copy runs on the main stream, which is ordered behind every
-    // render launch submitted so far (it waits for each launch's end event before that launch's accumulate); launches submitted later wait
-    // for `sceneReady` on their own stream.  Pinned staging buffers alternate and grow on demand; one is reused only after its own copy.
+    // In-place rewrite on the main stream (the scene-write protocol), no allocation of device memory and no host wait for the GPU.  Pinned staging buffers alternate
+    // and grow on demand; one is reused only after its own copy.
     const int k = c->stageFlip ^= 1;
     const size_t boxBytes = ((what & CRT_UPDATE_BOUNDS) && c->dRootBox) ? f.rootBox.size() * 4u : 0u;   // the device copy of the node-0 boxes rides behind the range
     const size_t geomBytes = hi - lo, bytes = geomBytes + boxBytes;
     if (c->stageBytes[k] < bytes) {
         if (c->hStage[k]) { HIPCK(c, hipEventSynchronize(c->stageCopied[k])); HIPCK(c, hipHostFree(c->hStage[k])); c->hStage[k] = nullptr; }
         HIPCK(c, hipHostMalloc((void**)&c->hStage[k], bytes, hipHostMallocDefault)); c->stageBytes[k] = bytes;
-        if (!c->stageCopied[k]) HIPCK(c, hipEventCreateWithFlags(&c->stageCopied[k], hipEventDisableTiming));
+        HIPCK(c, ensure_event(&c->stageCopied[k]));
     } else HIPCK(c, hipEventSynchronize(c->stageCopied[k]));
     memcpy(c->hStage[k], f.geom.data() + lo, geomBytes);
     if (boxBytes) memcpy(c->hStage[k] + geomBytes, f.rootBox.data(), boxBytes);
-    { const int r = order_behind_ahead(c); if (r) return r; }
-    { const int r = order_behind_queries(c); if (r) return r; }
+    { const int r = begin_scene_write(c, c->stream); if (r) return r; }
+    if (what & CRT_UPDATE_BOUNDS) {
+        std::fill(c->blasGrid.current.begin(), c->blasGrid.current.end(), (uint8_t)0);   // every BLAS's grid is of the old vertices
+        drop_blas_sets(c);                                                 // (may reset renderAccel: behind the epoch's bump)
+    }
     HIPCK(c, hipMemcpyAsync(const_cast<char*>(c->hScene.geom) + lo, c->hStage[k], geomBytes, hipMemcpyHostToDevice, c->stream));
     if (boxBytes) HIPCK(c, hipMemcpyAsync(c->dRootBox, c->hStage[k] + geomBytes, boxBytes, hipMemcpyHostToDevice, c->stream));
-    HIPCK(c, hipEventRecord(c->stageCopied[k], c->stream));
-    c->sceneReady = c->stageCopied[k];
+    { const int r = end_scene_write(c, c->stream, c->stageCopied[k]); if (r) return r; }
     if (f.kind == CRT_SCENE_TLAS) adopt_tlas(c, tlasHeight, sd->tlasNodes[0].aabbMin, sd->tlasNodes[0].aabbMax);
     else set_root(c, f.kind, sd->bvhs[0].nodes[0].aabbMin, sd->bvhs[0].nodes[0].aabbMax);
     return CRT_OK;
@@ -918,7 +970,7 @@ static int upload_tile_order(crt_ctx* c, const std::vector<uint32_t>& order)
     const int k = c->orderFlip ^= 1;
     if (!c->hTileOrder[k]) {
         HIPCK(c, hipHostMalloc((void**)&c->hTileOrder[k], (size_t)c->tileCount * 4, hipHostMallocDefault));
-        HIPCK(c, hipEventCreateWithFlags(&c->orderCopied[k], hipEventDisableTiming));
+        HIPCK(c, ensure_event(&c->orderCopied[k]));
     } else HIPCK(c, hipEventSynchronize(c->orderCopied[k]));
     memcpy(c->hTileOrder[k], order.data(), order.size() * 4);
     HIPCK(c, hipMemcpyAsync(c->dTileOrder, c->hTileOrder[k], order.size() * 4, hipMemcpyHostToDevice, c->stream));
@@ -1069,7 +1121,7 @@ static int upload_block_table(crt_ctx* c, const std::vector<uint8_t>& lanes, con
         HIPCK(c, hipHostMalloc((void**)&c->hBlockDesc, cap * 4, hipHostMallocDefault));
         c->descCap = (uint32_t)cap;
     } else if (c->descReady) HIPCK(c, hipEventSynchronize(c->descReady));     // the staging buffer's previous copy (long done)
-    if (!c->descReady) HIPCK(c, hipEventCreateWithFlags(&c->descReady, hipEventDisableTiming));
+    HIPCK(c, ensure_event(&c->descReady));
     memcpy(c->hBlockDesc, table.data(), table.size() * 4);
     { const int r = order_behind_ahead(c); if (r) return r; }
     // on the main stream: ordered behind every launch submitted so far (each launch's accumulate waits for it there), so the previous table is no longer read
@@ -1496,7 +1548,7 @@ static int install_job_plan(crt_ctx* c, uint32_t windows, uint32_t frames, bool 
         HIPCK(c, hipHostMalloc((void**)&c->hJobDesc, cap * 4, hipHostMallocDefault));
         c->jobDescCap = (uint32_t)cap;
     } else if (c->jobDescReady) HIPCK(c, hipEventSynchronize(c->jobDescReady));
-    if (!c->jobDescReady) HIPCK(c, hipEventCreateWithFlags(&c->jobDescReady, hipEventDisableTiming));
+    HIPCK(c, ensure_event(&c->jobDescReady));
     memcpy(c->hJobDesc, table.data(), table.size() * 4);
     { const int r = order_behind_ahead(c); if (r) return r; }
     HIPCK(c, hipMemcpyAsync(c->dJobDesc, c->hJobDesc, table.size() * 4, hipMemcpyHostToDevice, c->stream));      // main stream: behind every launch submitted so far
@@ -1540,7 +1592,7 @@ static int tuner_prepare(crt_ctx* c, Launch& L)
         if (!c->dTileCost) {
             HIPCK(c, hipMalloc((void**)&c->dTileCost, (size_t)c->tileCount * 4));
             HIPCK(c, hipHostMalloc((void**)&c->hTileCost, (size_t)c->tileCount * 4, hipHostMallocDefault));
-            HIPCK(c, hipEventCreateWithFlags(&c->costCopied, hipEventDisableTiming));
+            HIPCK(c, ensure_event(&c->costCopied));
         }
         else HIPCK(c, hipStreamWaitEvent(L.st, c->costCopied, 0));          // behind an earlier measurement (possibly on another stream) that a camera change abandoned
         HIPCK(c, hipMemsetAsync(c->dTileCost, 0, (size_t)c->tileCount * 4, L.st));
@@ -1559,7 +1611,7 @@ static int planner_prepare(crt_ctx* c, Launch& L)
             if (!c->dJobCost) {
                 HIPCK(c, hipMalloc((void**)&c->dJobCost, job_cost_bytes(c)));
                 HIPCK(c, hipHostMalloc((void**)&c->hJobCost, job_cost_bytes(c), hipHostMallocDefault));
-                HIPCK(c, hipEventCreateWithFlags(&c->jobCostCopied, hipEventDisableTiming));
+                HIPCK(c, ensure_event(&c->jobCostCopied));
             } else HIPCK(c, hipStreamWaitEvent(L.st, c->jobCostCopied, 0));      // behind an earlier measurement that a camera change abandoned
             HIPCK(c, hipMemsetAsync(c->dJobCost, 0, job_cost_bytes(c), L.st));
         }
@@ -1655,7 +1707,7 @@ static int probe_tile_costs(crt_ctx* c, hipStream_t st)
     if (!c->dTileCost) {
         HIPCK(c, hipMalloc((void**)&c->dTileCost, (size_t)n * 4));
         HIPCK(c, hipHostMalloc((void**)&c->hTileCost, (size_t)n * 4, hipHostMallocDefault));
-        HIPCK(c, hipEventCreateWithFlags(&c->costCopied, hipEventDisableTiming));
+        HIPCK(c, ensure_event(&c->costCopied));
     } else HIPCK(c, hipEventSynchronize(c->costCopied));                   // an earlier measurement that a camera change abandoned
     const auto tp0 = std::chrono::steady_clock::now();
     HIPCK(c, crt_launch_probe(&c->hScene, c->tileFirst, c->tileStride, n, (uint32_t)c->tilesX, c->dTileCost, st));
@@ -1691,7 +1743,7 @@ static int launch_frames(crt_ctx* c, uint32_t sppFirst, uint32_t nf, uint32_t pa
     size_t off = 0; int r;
     if ((r = take_region(c, (size_t)((nf + 63u) / 64u) * windowBytes, st, &off))) return r;
     if (c->orderReady) HIPCK(c, hipStreamWaitEvent(st, c->orderReady, 0));
-    if (c->sceneReady) HIPCK(c, hipStreamWaitEvent(st, c->sceneReady, 0));
+    if ((r = wait_scene(c, st))) return r;
     void* slab = c->pool + off;
     EventPair ev;
     harvest_tuning(c);
@@ -1778,7 +1830,7 @@ int crt_render(crt_ctx* c, uint32_t spp_first, uint32_t frames, uint32_t passes)
             const uint32_t nf = (frames - f0 < maxF) ? frames - f0 : maxF;
             size_t off = 0; int r;
             if ((r = take_region(c, (size_t)((nf + 63u) / 64u) * windowBytes, c->stream, &off))) return r;
-            if (c->sceneReady) HIPCK(c, hipStreamWaitEvent(c->stream, c->sceneReady, 0));
+            if ((r = wait_scene(c, c->stream))) return r;
             void* slab = c->pool + off;
             if (c->havePrim) HIPCK(c, crt_launch_render_prim(&c->hScene, &c->prim, slab, c->dCounters, c->tileFirst, c->tileStride, c->tileCount, (uint32_t)c->tilesX, spp_first + f0 * passes, nf, passes, c->stream));
             else HIPCK(c, crt_launch_render_alt(c->renderAccel, &c->hScene, &c->alt, &c->blasAlt[c->renderAccel - 1], slab, c->dCounters, c->tileFirst, c->tileStride, c->tileCount, (uint32_t)c->tilesX, spp_first + f0 * passes, nf, passes, c->stream));
@@ -2101,7 +2153,7 @@ int crt_upload_alt_accel(crt_ctx* c, const crt_alt_accel* a)
         for (int k = 0; k < 3; k++) { c->alt.res[k] = a->gridResolution[k]; c->alt.cell[k] = a->gridCellSize[k]; c->alt.lo[k] = a->gridMin[k]; c->alt.hi[k] = a->gridMax[k]; }
         c->haveGrid = true; c->gridRefCount = a->gridCellTriCount;
     }
-    if (!c->altReady) HIPCK(c, hipEventCreateWithFlags(&c->altReady, hipEventDisableTiming));
+    HIPCK(c, ensure_event(&c->altReady));
     HIPCK(c, hipEventRecord(c->altReady, nullptr));                       // behind the copies above (null stream): device queries on other streams wait for it
     return CRT_OK;
 }
@@ -2179,7 +2231,7 @@ int crt_upload_blas_accel(crt_ctx* c, int kind, const crt_alt_accel* blas, uint3
         for (uint32_t b = 0; b < blasCount; b++) { g.cells[b] = (uint32_t)blas[b].gridResolution[0] * (uint32_t)blas[b].gridResolution[1] * (uint32_t)blas[b].gridResolution[2]; g.refs[b] = blas[b].gridCellTriCount; }
     }
     if (c->renderAccel == kind) c->renderAccel = 0;                       // as crt_upload_alt_accel: the render goes back to the BVH until crt_set_render_accel
-    if (!c->altReady) HIPCK(c, hipEventCreateWithFlags(&c->altReady, hipEventDisableTiming));
+    HIPCK(c, ensure_event(&c->altReady));
     HIPCK(c, hipEventRecord(c->altReady, nullptr));                       // behind the copies above: device queries on other streams wait for it
     return CRT_OK;
 }
@@ -2287,6 +2339,36 @@ static int caller_stream(crt_ctx* c, void* stream, const char* what, hipStream_t
     return 0;
 }
 
+// what every entry on device buffers starts with, once its arguments are known to fit the scene: the context's device, every buffer checked, the stream
+static int device_entry(crt_ctx* c, const char* what, std::initializer_list<std::pair<const void*, size_t>> bufs, void* stream, hipStream_t* stOut)
+{
+    HIPCK(c, hipSetDevice(c->cfg.device));
+    for (const auto& b : bufs) { const int r = check_device_buffer(c, b.first, b.second, what); if (r) return r; }
+    return caller_stream(c, stream, what, stOut);
+}
+
+// `bytes` of device memory to the host behind everything on `st`, and the host waits for them (`ev` is recorded behind the copy; *waitMs: the wall time of the wait)
+static int read_back(crt_ctx* c, hipStream_t st, hipEvent_t ev, void* dst, const void* src, size_t bytes, double* waitMs = nullptr)
+{
+    HIPCK(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, st));
+    HIPCK(c, hipEventRecord(ev, st));
+    const auto t0 = std::chrono::steady_clock::now();
+    HIPCK(c, hipEventSynchronize(ev));
+    if (waitMs) *waitMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return 0;
+}
+
+// what crt_refit_device and crt_build_grid_device ask of their arguments: a triangle scene, `bvh` one of its BVHs, of `triCount` triangles (tail: the entry's own words)
+static int check_bvh_arg(crt_ctx* c, const char* me, const char* primLacks, uint32_t bvh, uint32_t triCount, const char* tail)
+{
+    if (c->havePrim) return c->fail(CRT_ERR_UNSUPPORTED, "%s: the PrimitiveScene has no %s", me, primLacks);
+    if (!c->haveScene) return c->fail(CRT_ERR_STATE, "%s before crt_upload_scene", me);
+    const std::vector<uint32_t>& tc = c->flat.triCount;
+    if (bvh >= tc.size()) return c->fail(CRT_ERR_INVALID, "%s: BVH %u of a scene with %zu", me, bvh, tc.size());
+    if (triCount != tc[bvh]) return c->fail(CRT_ERR_INVALID, "%s: %u triangles, the uploaded BVH %u has %u%s", me, triCount, bvh, tc[bvh], tail);
+    return 0;
+}
+
 // a cursor slot whose previous launch has completed (all 64 in flight: the host waits for the next one in ring order)
 static int take_query_slot(crt_ctx* c, int* out)
 {
@@ -2299,7 +2381,7 @@ static int take_query_slot(crt_ctx* c, int* out)
             if (e != hipSuccess) return c->hip(e, "hipEventQuery(query)");
             q.pending = false;
         }
-        if (!q.done) HIPCK(c, hipEventCreateWithFlags(&q.done, hipEventDisableTiming));
+        HIPCK(c, ensure_event(&q.done));
         c->qslotNext = (k + 1) % crt_ctx::kQuerySlots; *out = k;
         return 0;
     }
@@ -2309,18 +2391,7 @@ static int take_query_slot(crt_ctx* c, int* out)
     return 0;
 }
 
-// what every device query shares: the caller's stream (checked; NULL = the ctx's own), ordered behind the scene's last in-place update, and a slot of the ring for
-// the event that later scene writes wait for ...
-static int begin_device_query(crt_ctx* c, void* stream, const char* what, hipStream_t* stOut, int* slotOut)
-{
-    hipStream_t st = nullptr;
-    { const int r = caller_stream(c, stream, what, &st); if (r) return r; }
-    // the scene as of the last upload / update: in-place updates are copies on the main stream (sceneReady)
-    if (c->sceneReady) HIPCK(c, hipStreamWaitEvent(st, c->sceneReady, 0));
-    *stOut = st;
-    return take_query_slot(c, slotOut);
-}
-
+// what every device query shares behind its stream: wait_scene (a reader of the scene-write protocol), a slot of the ring (take_query_slot), and the slot's event
 // ... recorded behind the launch (order_behind_queries / wait_queries look at it; so does the slot's next use)
 static int end_device_query(crt_ctx* c, int k, hipStream_t st)
 {
@@ -2334,10 +2405,8 @@ static int query_device(crt_ctx* c, bool occl, int accel, const void* dRays, voi
     int r;
     if ((r = query_check(c, accel, occl, n, what))) return r;
     if (n == 0) return CRT_OK;
-    HIPCK(c, hipSetDevice(c->cfg.device));
-    if ((r = check_device_buffer(c, dRays, n * 28, what)) || (r = check_device_buffer(c, dOut, n * (occl ? 4 : 28), what))) return r;
     hipStream_t st = nullptr; int k = 0;
-    if ((r = begin_device_query(c, stream, what, &st, &k))) return r;
+    if ((r = device_entry(c, what, {{dRays, n * 28}, {dOut, n * (occl ? 4u : 28u)}}, stream, &st)) || (r = wait_scene(c, st)) || (r = take_query_slot(c, &k))) return r;
     if (accel != 0 && c->altReady) HIPCK(c, hipStreamWaitEvent(st, c->altReady, 0));     // the accelerators' copies ran on the null stream
     HIPCK(c, launch_query(c, occl, accel, dRays, dOut, (uint32_t)n, c->dQuerySlots + 16 * k, st));
     return end_device_query(c, k, st);
@@ -2401,44 +2470,30 @@ static int build_refit_plan(crt_ctx* c, uint32_t b)
 
 int crt_refit_device(crt_ctx* c, uint32_t bvh, const float* d_positions, uint32_t triCount, void* stream, float rootBox[6])
 {
+    const char* const me = "crt_refit_device";
     if (!c) return CRT_ERR_INVALID;
-    if (c->havePrim) return c->fail(CRT_ERR_UNSUPPORTED, "crt_refit_device: the PrimitiveScene has no BVH to refit");
-    if (!c->haveScene) return c->fail(CRT_ERR_STATE, "crt_refit_device before crt_upload_scene");
-    crt_ctx::Flat& f = c->flat;
-    if (bvh >= f.triCount.size()) return c->fail(CRT_ERR_INVALID, "crt_refit_device: BVH %u of a scene with %zu", bvh, f.triCount.size());
-    if (triCount != f.triCount[bvh]) return c->fail(CRT_ERR_INVALID, "crt_refit_device: %u triangles, the uploaded BVH %u has %u (Refit keeps the topology)", triCount, bvh, f.triCount[bvh]);
-    HIPCK(c, hipSetDevice(c->cfg.device));
     int r;
-    if ((r = check_device_buffer(c, d_positions, (size_t)triCount * 36u, "crt_refit_device"))) return r;
+    if ((r = check_bvh_arg(c, me, "BVH to refit", bvh, triCount, " (Refit keeps the topology)"))) return r;
+    crt_ctx::Flat& f = c->flat; crt_ctx::Refit& R = c->refit;
     hipStream_t st = nullptr;
-    if ((r = caller_stream(c, stream, "crt_refit_device", &st))) return r;
+    if ((r = device_entry(c, me, {{d_positions, (size_t)triCount * 36u}}, stream, &st))) return r;
     if (c->refitPlans.size() != f.triCount.size()) c->refitPlans.assign(f.triCount.size(), crt_ctx::RefitPlan{});
     if (!c->refitPlans[bvh].built && (r = build_refit_plan(c, bvh))) return r;
     const crt_ctx::RefitPlan& P = c->refitPlans[bvh];
-    if (!c->dRefitBack) HIPCK(c, hipMalloc((void**)&c->dRefitBack, 128));
-    if (!c->hRefitBack) HIPCK(c, hipHostMalloc((void**)&c->hRefitBack, 128, hipHostMallocDefault));
-    if (!c->refitFence) HIPCK(c, hipEventCreateWithFlags(&c->refitFence, hipEventDisableTiming));
-    if (!c->refitDone) HIPCK(c, hipEventCreateWithFlags(&c->refitDone, hipEventDisableTiming));
-    // In place, as crt_update_scene: the kernels run behind every earlier launch that reads the geometry.  The main stream is ordered behind crt_render's launches
-    // (it waits for each before that launch's accumulate) and carries the host-buffer queries and earlier updates; it is made to wait for the render-ahead launches
-    // and for the device queries in flight, and the caller's stream waits for the main stream up to here (and for an earlier refit on another stream).
-    if ((r = order_behind_ahead(c)) || (r = order_behind_queries(c))) return r;
-    if (st != c->stream) {
-        HIPCK(c, hipEventRecord(c->refitFence, c->stream));
-        HIPCK(c, hipStreamWaitEvent(st, c->refitFence, 0));
-        if (c->sceneReady) HIPCK(c, hipStreamWaitEvent(st, c->sceneReady, 0));
-    }
-    c->epoch++;                                                           // frames rendered ahead by crt_tick are of the old scene
+    if (!R.dBack) HIPCK(c, hipMalloc((void**)&R.dBack, 128));
+    if (!R.hBack) HIPCK(c, hipHostMalloc((void**)&R.hBack, 128, hipHostMallocDefault));
+    HIPCK(c, ensure_event(&R.done));
+    // In place, on the caller's stream: a write of the scene-write protocol.  The read-back rides inside it (`done` is recorded behind both copies), so the entry's
+    // one host wait is for the event that end_scene_write has just published.
+    if ((r = begin_scene_write(c, st))) return r;
     HIPCK(c, crt_launch_refit(const_cast<char*>(c->hScene.geom), (uint32_t)f.leafOff, (uint32_t)f.pairBase[bvh], (uint32_t)f.triBase[bvh], triCount, d_positions,
-                              P.dPlan, P.dLevelOff, P.levels, P.rootCode, c->dRefitBack, st));
-    HIPCK(c, hipMemcpyAsync(c->hRefitBack, c->dRefitBack, 88, hipMemcpyDeviceToHost, st));
-    if (c->dRootBox) HIPCK(c, hipMemcpyAsync(c->dRootBox + 6 * (size_t)bvh, c->dRefitBack + 16, 24, hipMemcpyDeviceToDevice, st));   // the box pass's node-0 box, for crt_update_transforms_device
-    HIPCK(c, hipEventRecord(c->refitDone, st));
-    c->sceneReady = c->refitDone;                                         // launches submitted later wait for it on their own stream; the main stream's own consumers here
-    if (st != c->stream) HIPCK(c, hipStreamWaitEvent(c->stream, c->refitDone, 0));
+                              P.dPlan, P.dLevelOff, P.levels, P.rootCode, R.dBack, st));
+    HIPCK(c, hipMemcpyAsync(R.hBack, R.dBack, 88, hipMemcpyDeviceToHost, st));
+    if (c->dRootBox) HIPCK(c, hipMemcpyAsync(c->dRootBox + 6 * (size_t)bvh, R.dBack + 16, 24, hipMemcpyDeviceToDevice, st));   // the box pass's node-0 box, for crt_update_transforms_device
+    if ((r = end_scene_write(c, st, R.done))) return r;
     // the one host wait: Scene::rootPair travels in the kernel arguments of every later launch, so the refitted pair has to be on the host before this call returns
-    HIPCK(c, hipEventSynchronize(c->refitDone));
-    const float* back = c->hRefitBack;
+    HIPCK(c, hipEventSynchronize(R.done));
+    const float* back = R.hBack;
     memcpy(&f.rootBox[6 * (size_t)bvh], back + 16, 24);
     if (P.rootCode & crt::kPlanInterior) memcpy(f.geom.data() + (size_t)(f.pairBase[bvh] + (P.rootCode & ~crt::kPlanInterior)) * 64u, back, 64);   // the mirror's copy of the root's pair
     if (f.kind == CRT_SCENE_FILE) set_root(c, CRT_SCENE_FILE, back + 16, back + 19);      // rootPair from the mirror, dispatch-order bounds; a BLAS's box reaches the TLAS through the caller
@@ -2451,59 +2506,48 @@ int crt_refit_device(crt_ctx* c, uint32_t bvh, const float* d_positions, uint32_
 // ---- crt_update_transforms_device: SetTransform of every BLAS + TLASBVH::Build on the device, from transforms in device memory (device/tlas_build.hip) ----
 int crt_update_transforms_device(crt_ctx* c, const float* d_T, uint32_t blasCount, void* stream, crt_tlas_node* tlasOut)
 {
+    const char* const me = "crt_update_transforms_device";
     if (!c) return CRT_ERR_INVALID;
-    if (c->havePrim) return c->fail(CRT_ERR_UNSUPPORTED, "crt_update_transforms_device: the PrimitiveScene has no instances");
-    if (!c->haveScene) return c->fail(CRT_ERR_STATE, "crt_update_transforms_device before crt_upload_scene");
-    crt_ctx::Flat& f = c->flat;
+    if (c->havePrim) return c->fail(CRT_ERR_UNSUPPORTED, "%s: the PrimitiveScene has no instances", me);
+    if (!c->haveScene) return c->fail(CRT_ERR_STATE, "%s before crt_upload_scene", me);
+    crt_ctx::Flat& f = c->flat; crt_ctx::TlasBuild& B = c->tlasBuild; int r;
     if (f.kind != CRT_SCENE_TLAS) return c->fail(CRT_ERR_INVALID, "crt_update_transforms_device applies to two-level scenes (a FileScene bakes its transforms into the triangles)");
     const uint32_t N = (uint32_t)f.triCount.size();
     if (blasCount != N) return c->fail(CRT_ERR_INVALID, "crt_update_transforms_device: %u transforms, the uploaded scene has %u BLAS", blasCount, N);
     if (f.tlasNodeCount != 2u * N) return c->fail(CRT_ERR_UNSUPPORTED, "crt_update_transforms_device: the scene was uploaded with %u TLAS nodes, TLASBVH::Build makes %u", f.tlasNodeCount, 2u * N);
-    HIPCK(c, hipSetDevice(c->cfg.device));
-    int r;
-    if ((r = check_device_buffer(c, d_T, (size_t)N * 64u, "crt_update_transforms_device"))) return r;
     hipStream_t st = nullptr;
-    if ((r = caller_stream(c, stream, "crt_update_transforms_device", &st))) return r;
+    if ((r = device_entry(c, me, {{d_T, (size_t)N * 64u}}, stream, &st))) return r;
     const size_t imageBytes = (size_t)(f.shadeOff - f.tlasOff), backBytes = sizeof(crt::TlasBuildHeader) + imageBytes;
-    if (c->tlasBuildBytes < backBytes) {                                    // a larger scene than the last one: nothing of an earlier call is in flight in these (see below)
-        if (c->tlasDone) HIPCK(c, hipEventSynchronize(c->tlasDone));
-        if (c->dTlasBuild) { HIPCK(c, hipFree(c->dTlasBuild)); c->dTlasBuild = nullptr; }
-        if (c->hTlasBack) { HIPCK(c, hipHostFree(c->hTlasBack)); c->hTlasBack = nullptr; }
-        c->tlasBuildBytes = 0;
-        HIPCK(c, hipMalloc((void**)&c->dTlasBuild, backBytes));
-        HIPCK(c, hipHostMalloc((void**)&c->hTlasBack, backBytes, hipHostMallocDefault));
-        HIPCK(c, hipMemset(c->dTlasBuild, 0, backBytes));                   // the padding between the image's sections stays zero, as in the host's image: the kernel writes records only
-        c->tlasBuildBytes = backBytes;
+    if (B.bytes < backBytes) {                                              // a larger scene than the last one: nothing of an earlier call is in flight in these (see below)
+        if (B.done) HIPCK(c, hipEventSynchronize(B.done));
+        if (B.dBuild) { HIPCK(c, hipFree(B.dBuild)); B.dBuild = nullptr; }
+        if (B.hBack) { HIPCK(c, hipHostFree(B.hBack)); B.hBack = nullptr; }
+        B.bytes = 0;
+        HIPCK(c, hipMalloc((void**)&B.dBuild, backBytes));
+        HIPCK(c, hipHostMalloc((void**)&B.hBack, backBytes, hipHostMallocDefault));
+        HIPCK(c, hipMemset(B.dBuild, 0, backBytes));                        // the padding between the image's sections stays zero, as in the host's image: the kernel writes records only
+        B.bytes = backBytes;
     }
-    for (hipEvent_t* e : {&c->tlasFence, &c->tlasBack, &c->tlasDone}) if (!*e) HIPCK(c, hipEventCreateWithFlags(e, hipEventDisableTiming));
-    if (g_hooks) for (hipEvent_t* e : {&c->tlasT0, &c->tlasT1}) if (!*e) HIPCK(c, hipEventCreate(e));
-    // The build reads the Instance records and the node-0 boxes as the last update / refit left them and writes only the context's result block, which the copy
-    // of an earlier call may still be reading on another stream: both are behind sceneReady.  Earlier renders and queries are not waited for yet.
-    if (c->sceneReady) HIPCK(c, hipStreamWaitEvent(st, c->sceneReady, 0));
-    if (g_hooks) HIPCK(c, hipEventRecord(c->tlasT0, st));
-    HIPCK(c, crt_launch_tlas_build(c->hScene.geom, (uint32_t)f.instOff, d_T, c->dRootBox, N, (uint32_t)(f.tlasPairOff - f.tlasOff), (uint32_t)(f.instOff - f.tlasOff), c->dTlasBuild, st));
-    if (g_hooks) { HIPCK(c, hipEventRecord(c->tlasT1, st)); c->tlasTimed = true; }
-    HIPCK(c, hipMemcpyAsync(c->hTlasBack, c->dTlasBuild, backBytes, hipMemcpyDeviceToHost, st));
-    HIPCK(c, hipEventRecord(c->tlasBack, st));
+    for (hipEvent_t* e : {&B.back, &B.done}) HIPCK(c, ensure_event(e));
+    if (g_hooks) for (hipEvent_t* e : {&B.t0, &B.t1}) HIPCK(c, ensure_event(e, hipEventDefault));
+    // The build is a reader: it reads only the Instance records and the node-0 boxes as the last write left them, and writes only the context's result block, which
+    // the commit copy of an earlier call may still be reading on another stream — all behind sceneReady, so it waits for that alone, not for earlier renders or queries.
+    if ((r = wait_scene(c, st))) return r;
+    if (g_hooks) HIPCK(c, hipEventRecord(B.t0, st));
+    HIPCK(c, crt_launch_tlas_build(c->hScene.geom, (uint32_t)f.instOff, d_T, c->dRootBox, N, (uint32_t)(f.tlasPairOff - f.tlasOff), (uint32_t)(f.instOff - f.tlasOff), B.dBuild, st));
+    if (g_hooks) { HIPCK(c, hipEventRecord(B.t1, st)); B.timed = true; }
     // the one host wait: the root's pair and the stack depth travel in the kernel arguments of every later launch, and only a build that passed is committed
-    HIPCK(c, hipEventSynchronize(c->tlasBack));
-    const crt::TlasBuildHeader& h = *reinterpret_cast<const crt::TlasBuildHeader*>(c->hTlasBack);
-    const char* image = c->hTlasBack + sizeof(crt::TlasBuildHeader);
+    if ((r = read_back(c, st, B.back, B.hBack, B.dBuild, backBytes))) return r;
+    const crt::TlasBuildHeader& h = *reinterpret_cast<const crt::TlasBuildHeader*>(B.hBack);
+    const char* image = B.hBack + sizeof(crt::TlasBuildHeader);
     if (h.status == crt::kTlasBuildNoCandidate)
         return c->fail(CRT_ERR_INVALID, "crt_update_transforms_device: FindBestMatch call %u found no partner while more than one node was open (a non-finite transform or box, or areas >= 1e30; the reference reads list[-1] there)", h.step);
     if (h.status != crt::kTlasBuildOk) return c->fail(CRT_ERR_INVALID, "crt_update_transforms_device: the build had not ended after %u FindBestMatch calls", h.step);
     if ((r = check_tlas_height(c, h.height))) return r;
-    // ---- commit: in place, behind every earlier launch that reads the geometry (as crt_refit_device), on the caller's stream ----
-    if ((r = order_behind_ahead(c)) || (r = order_behind_queries(c))) return r;
-    if (st != c->stream) {
-        HIPCK(c, hipEventRecord(c->tlasFence, c->stream));
-        HIPCK(c, hipStreamWaitEvent(st, c->tlasFence, 0));
-    }
-    HIPCK(c, hipMemcpyAsync(const_cast<char*>(c->hScene.geom) + f.tlasOff, c->dTlasBuild + sizeof(crt::TlasBuildHeader), imageBytes, hipMemcpyDeviceToDevice, st));
-    HIPCK(c, hipEventRecord(c->tlasDone, st));
-    c->sceneReady = c->tlasDone;                                           // launches submitted later wait for it on their own stream
-    if (st != c->stream) HIPCK(c, hipStreamWaitEvent(c->stream, c->tlasDone, 0));
-    c->epoch++;                                                           // frames rendered ahead by crt_tick are of the old scene
+    // ---- commit: the write proper, in place on the caller's stream ----
+    if ((r = begin_scene_write(c, st))) return r;
+    HIPCK(c, hipMemcpyAsync(const_cast<char*>(c->hScene.geom) + f.tlasOff, B.dBuild + sizeof(crt::TlasBuildHeader), imageBytes, hipMemcpyDeviceToDevice, st));
+    if ((r = end_scene_write(c, st, B.done))) return r;
     memcpy(f.geom.data() + f.tlasOff, image, imageBytes);                  // the mirror: a later CRT_UPDATE_BOUNDS rewrites [tlasOff, shadeOff) from it
     const crt::TlasNode* nodes = reinterpret_cast<const crt::TlasNode*>(image);
     adopt_tlas(c, h.height, nodes[0].lo, nodes[0].hi);
@@ -2533,7 +2577,7 @@ static float grid_bound_of(unsigned long long key)
 static int grow_grid_scratch(crt_ctx* c, void** p, size_t* cap, size_t need /* 4-byte words */)
 {
     if (need <= *cap) return 0;
-    if (c->gridBuilt) HIPCK(c, hipEventSynchronize(c->gridDone));
+    if (c->gridBuild.built) HIPCK(c, hipEventSynchronize(c->gridBuild.done));
     if (*p) { (void)hipFree(*p); *p = nullptr; *cap = 0; }
     HIPCK(c, hipMalloc(p, need * 4u));
     *cap = need;
@@ -2544,46 +2588,37 @@ int crt_build_grid_device(crt_ctx* c, uint32_t bvh, const float* d_positions, ui
 {
     const char* const me = "crt_build_grid_device";
     if (!c) return CRT_ERR_INVALID;
-    if (c->havePrim) return c->fail(CRT_ERR_UNSUPPORTED, "%s: the PrimitiveScene has no triangles", me);
-    if (!c->haveScene) return c->fail(CRT_ERR_STATE, "%s before crt_upload_scene", me);
-    crt_ctx::Flat& f = c->flat;
+    int r;
+    if ((r = check_bvh_arg(c, me, "triangles", bvh, triCount, ""))) return r;
+    crt_ctx::Flat& f = c->flat; crt_ctx::GridBuild& G = c->gridBuild;
     const bool tlas = f.kind == CRT_SCENE_TLAS;
     const uint32_t N = (uint32_t)f.triCount.size();
-    if (bvh >= N) return c->fail(CRT_ERR_INVALID, "%s: BVH %u of a scene with %u", me, bvh, N);
-    if (triCount != f.triCount[bvh]) return c->fail(CRT_ERR_INVALID, "%s: %u triangles, the uploaded BVH %u has %u", me, triCount, bvh, f.triCount[bvh]);
     if (triCount == 0 || triCount > 0x7fffffffu / 3u) return c->fail(CRT_ERR_UNSUPPORTED, "%s: 1 .. (2^31-1)/3 triangles", me);
     crt_ctx::BlasGrid& bg = c->blasGrid;
     if (tlas && (!bg.held || bg.desc.size() != N)) return c->fail(CRT_ERR_STATE, "%s: a two-level scene needs a grid set uploaded earlier (crt_upload_blas_accel(CRT_ACCEL_GRID)): the other BLASes' parts are carried over", me);
-    HIPCK(c, hipSetDevice(c->cfg.device));
-    int r;
-    if ((r = check_device_buffer(c, d_positions, (size_t)triCount * 36u, me))) return r;
     hipStream_t st = nullptr;
-    if ((r = caller_stream(c, stream, me, &st))) return r;
+    if ((r = device_entry(c, me, {{d_positions, (size_t)triCount * 36u}}, stream, &st))) return r;
     // ---- what the context keeps for the build ----
     c->freeRetired(false);
-    if (!c->gridBlocks && !(c->gridBlocks = crt_grid_build_blocks(c->cfg.device))) return c->fail(CRT_ERR_DEVICE, "%s: the device's compute units / occupancy could not be asked", me);
-    if (!c->dGridState) HIPCK(c, hipMalloc((void**)&c->dGridState, sizeof(crt::GridBuildState)));
-    if (!c->hGridState) HIPCK(c, hipHostMalloc((void**)&c->hGridState, sizeof(crt::GridBuildState), hipHostMallocDefault));
-    if (!c->dGridChunks) HIPCK(c, hipMalloc((void**)&c->dGridChunks, crt_grid_scan_chunks(128u * 128u * 128u) * 8u));
-    for (hipEvent_t* e : {&c->gridBack, &c->gridDone}) if (!*e) HIPCK(c, hipEventCreateWithFlags(e, hipEventDisableTiming));
-    if (g_hooks) for (hipEvent_t* e : {&c->gridT0, &c->gridT1}) if (!*e) HIPCK(c, hipEventCreate(e));
-    // The build reads the caller's positions and the LeafTri id words (which no update changes) and writes buffers of its own, so it is ordered behind nothing but
-    // the scene's last in-place update and the previous build (whose scratch it reuses); earlier renders and queries are not waited for.
-    if (c->sceneReady) HIPCK(c, hipStreamWaitEvent(st, c->sceneReady, 0));
-    if (c->gridBuilt) HIPCK(c, hipStreamWaitEvent(st, c->gridDone, 0));
-    if (g_hooks) HIPCK(c, hipEventRecord(c->gridT0, st));
+    if (!G.blocks && !(G.blocks = crt_grid_build_blocks(c->cfg.device))) return c->fail(CRT_ERR_DEVICE, "%s: the device's compute units / occupancy could not be asked", me);
+    if (!G.dState) HIPCK(c, hipMalloc((void**)&G.dState, sizeof(crt::GridBuildState)));
+    if (!G.hState) HIPCK(c, hipHostMalloc((void**)&G.hState, sizeof(crt::GridBuildState), hipHostMallocDefault));
+    if (!G.dChunks) HIPCK(c, hipMalloc((void**)&G.dChunks, crt_grid_scan_chunks(128u * 128u * 128u) * 8u));
+    for (hipEvent_t* e : {&G.back, &G.done}) HIPCK(c, ensure_event(e));
+    if (g_hooks) for (hipEvent_t* e : {&G.t0, &G.t1}) HIPCK(c, ensure_event(e, hipEventDefault));
+    // Fresh buffers, so the build is a reader: it reads the caller's positions and the LeafTri id words (which no write changes) and waits for the last scene write
+    // and for the previous build (whose scratch it reuses).  Earlier renders and queries are not waited for until the old set is retired.
+    if ((r = wait_scene(c, st))) return r;
+    if (G.built) HIPCK(c, hipStreamWaitEvent(st, G.done, 0));
+    if (g_hooks) HIPCK(c, hipEventRecord(G.t0, st));
     // ---- a. bounds + finiteness; THE FIRST HOST WAIT: the resolution is computed on the host from the bounds ----
-    HIPCK(c, crt_launch_grid_bounds(d_positions, triCount, c->dGridState, c->gridBlocks, st));
-    HIPCK(c, hipMemcpyAsync(c->hGridState, c->dGridState, sizeof(crt::GridBuildState), hipMemcpyDeviceToHost, st));
-    HIPCK(c, hipEventRecord(c->gridBack, st));
-    auto t0 = std::chrono::steady_clock::now();
-    HIPCK(c, hipEventSynchronize(c->gridBack));
-    c->gridWaitMs[0] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    if (c->hGridState->nonFinite) return c->fail(CRT_ERR_INVALID, "%s: a position component is not finite", me);
+    HIPCK(c, crt_launch_grid_bounds(d_positions, triCount, G.dState, G.blocks, st));
+    if ((r = read_back(c, st, G.back, G.hState, G.dState, sizeof(crt::GridBuildState), &G.waitMs[0]))) return r;
+    if (G.hState->nonFinite) return c->fail(CRT_ERR_INVALID, "%s: a position component is not finite", me);
     // ---- b. localBounds as aabb::Grow folds them from +-1e34, then the resolution lines shared with the host build ----
     crt::GridParams gp{}; float hi[3], size[3], cell[3]; int res[3];
     for (int k = 0; k < 3; k++) {
-        const float lo = grid_bound_of(c->hGridState->key[k]), up = grid_bound_of(c->hGridState->key[3 + k]);
+        const float lo = grid_bound_of(G.hState->key[k]), up = grid_bound_of(G.hState->key[3 + k]);
         gp.lo[k] = 1e34f < lo ? 1e34f : lo; hi[k] = -1e34f > up ? -1e34f : up;
         size[k] = hi[k] - gp.lo[k];
     }
@@ -2606,13 +2641,9 @@ int crt_build_grid_device(crt_ctx* c, uint32_t bvh, const float* d_positions, ui
     uint32_t* newStart = nullptr;
     if ((r = alloc((size_t)allCells * 4u, (void**)&newStart))) { undo(); return r; }
     // ---- c, d. count + exclusive scan; THE SECOND HOST WAIT: cellRefs is sized from the total ----
-    GRIDCK(crt_launch_grid_count(d_positions, triCount, &gp, cells, newStart + cellBase, c->dGridChunks, c->dGridState, c->gridBlocks, st));
-    GRIDCK(hipMemcpyAsync(c->hGridState, c->dGridState, sizeof(crt::GridBuildState), hipMemcpyDeviceToHost, st));
-    GRIDCK(hipEventRecord(c->gridBack, st));
-    t0 = std::chrono::steady_clock::now();
-    GRIDCK(hipEventSynchronize(c->gridBack));
-    c->gridWaitMs[1] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    const unsigned long long total64 = c->hGridState->total;
+    GRIDCK(crt_launch_grid_count(d_positions, triCount, &gp, cells, newStart + cellBase, G.dChunks, G.dState, G.blocks, st));
+    if ((r = read_back(c, st, G.back, G.hState, G.dState, sizeof(crt::GridBuildState), &G.waitMs[1]))) { undo(); return r; }
+    const unsigned long long total64 = G.hState->total;
     uint64_t refBase = 0, allRefs = total64, triOff = 0, allTris = triCount;
     if (tlas) {
         allRefs = 0; allTris = 0;
@@ -2622,7 +2653,7 @@ int crt_build_grid_device(crt_ctx* c, uint32_t bvh, const float* d_positions, ui
     const uint32_t total = (uint32_t)total64;
     int32_t* newRefs = nullptr; crt::AltTri* newTris = nullptr; crt::BlasAltDesc* newDesc = nullptr;
     if ((r = alloc((size_t)allRefs * 4u, (void**)&newRefs)) || (r = alloc((size_t)allTris * sizeof(crt::AltTri), (void**)&newTris)) ||
-        (r = grow_grid_scratch(c, (void**)&c->dGridCursor, &c->gridCursorCap, (size_t)cells)) || (r = grow_grid_scratch(c, (void**)&c->dGridUnsorted, &c->gridUnsortedCap, (size_t)total))) { undo(); return r; }
+        (r = grow_grid_scratch(c, (void**)&G.dCursor, &G.cursorCap, (size_t)cells)) || (r = grow_grid_scratch(c, (void**)&G.dUnsorted, &G.unsortedCap, (size_t)total))) { undo(); return r; }
     std::vector<crt::BlasAltDesc> desc;
     if (tlas) {
         // the other BLASes' parts, device to device, and the descriptors re-based for the new sizes
@@ -2647,22 +2678,18 @@ int crt_build_grid_device(crt_ctx* c, uint32_t bvh, const float* d_positions, ui
         GRIDCK(hipMemcpyAsync(newDesc, pinned, desc.size() * sizeof(crt::BlasAltDesc), hipMemcpyHostToDevice, st));
     }
     // ---- e, f. fill, sort every cell ascending, the AltTri records ----
-    GRIDCK(crt_launch_grid_fill(d_positions, triCount, &gp, cells, newStart + cellBase, c->dGridCursor, c->dGridUnsorted, newRefs ? newRefs + refBase : nullptr, total, c->hScene.geom,
-                                (uint32_t)f.leafOff, (uint32_t)f.triBase[bvh], tlas ? 1 : 0, newTris + triOff, c->gridBlocks, st));
-    if (g_hooks) { GRIDCK(hipEventRecord(c->gridT1, st)); c->gridTimed = true; }
-    GRIDCK(hipEventRecord(c->gridDone, st));
-    c->gridBuilt = true;
-    // ---- the grid it replaces: still read by launches enqueued earlier, on any stream, and by this build's own copies.  The main stream is ordered behind all of them
-    // (as for an in-place update; behind the build through gridDone) and an event on it says when the old buffers are unread; everything submitted later waits for the build and takes the new pointers ----
+    GRIDCK(crt_launch_grid_fill(d_positions, triCount, &gp, cells, newStart + cellBase, G.dCursor, G.dUnsorted, newRefs ? newRefs + refBase : nullptr, total, c->hScene.geom,
+                                (uint32_t)f.leafOff, (uint32_t)f.triBase[bvh], tlas ? 1 : 0, newTris + triOff, G.blocks, st));
+    if (g_hooks) { GRIDCK(hipEventRecord(G.t1, st)); G.timed = true; }
+    GRIDCK(hipEventRecord(G.done, st));
+    G.built = true;
+    // ---- the grid it replaces: still read by launches enqueued earlier, on any stream, and by this build's own copies (the other BLASes' parts, the pinned descriptors).
+    // The main stream behind all those readers and behind the build (`done` published), and an event on it then says when the old buffers are unread ----
     crt_ctx::Retired old;
     if (c->retiredEvents.empty()) { hipEvent_t e = nullptr; GRIDCK(hipEventCreateWithFlags(&e, hipEventDisableTiming)); c->retiredEvents.push_back(e); }
     old.unread = c->retiredEvents.back(); c->retiredEvents.pop_back();
-    if ((r = order_behind_ahead(c)) || (r = order_behind_queries(c))) { c->retiredEvents.push_back(old.unread); undo(); return r; }
-    {
-        // ... and behind the build itself, which reads the old set on `st` (the other BLASes' parts, the pinned descriptors)
-        hipError_t e = st != c->stream ? hipStreamWaitEvent(c->stream, c->gridDone, 0) : hipSuccess;
-        if (e == hipSuccess) e = hipEventRecord(old.unread, c->stream);
-        if (e != hipSuccess) { c->retiredEvents.push_back(old.unread); undo(); return c->hip(e, "hipEventRecord(retired)"); }
+    if ((r = order_behind_readers(c)) || (r = publish_scene_write(c, st, G.done)) || (r = c->hip(hipEventRecord(old.unread, c->stream), "hipEventRecord(retired)"))) {
+        c->retiredEvents.push_back(old.unread); undo(); return r;
     }
 #undef GRIDCK
     old.pinned = pinned;
@@ -2687,8 +2714,6 @@ int crt_build_grid_device(crt_ctx* c, uint32_t bvh, const float* d_positions, ui
         if (c->renderAccel == CRT_ACCEL_KDTREE) c->renderAccel = 0;
     }
     c->retired.push_back(std::move(old));
-    c->sceneReady = c->gridDone;                                           // launches submitted later wait for the build on their own stream
-    c->epoch++;                                                            // (the main stream already waits for the build: see the retired set's event above)
     return CRT_OK;
 }
 
@@ -2715,7 +2740,7 @@ int crt_get_grid(crt_ctx* c, uint32_t bvh, int32_t res[3], float cellSize[3], fl
     if (refCount) *refCount = refs;
     if (!cellStart && !cellRefs) return CRT_OK;
     HIPCK(c, hipSetDevice(c->cfg.device));
-    if (c->gridBuilt) HIPCK(c, hipEventSynchronize(c->gridDone));          // a device build still running (an uploaded grid's copies were synchronous)
+    if (c->gridBuild.built) HIPCK(c, hipEventSynchronize(c->gridBuild.done));   // a device build still running (an uploaded grid's copies were synchronous)
     if (cellStart) HIPCK(c, hipMemcpy(cellStart, dStart, ((size_t)cells + 1u) * 4u, hipMemcpyDeviceToHost));
     if (cellRefs && refs) HIPCK(c, hipMemcpy(cellRefs, dRefs, (size_t)refs * 4u, hipMemcpyDeviceToHost));
     return CRT_OK;
@@ -2729,10 +2754,11 @@ extern "C" int crt_debug_render_accel(crt_ctx* c) { return c ? c->renderAccel : 
 extern "C" int crt_debug_grid_build_ms(crt_ctx* c, float* streamMs, double waitMs[2])
 {
     if (!c || !streamMs || !waitMs) return CRT_ERR_INVALID;
-    if (!c->gridTimed) return c->fail(CRT_ERR_STATE, "crt_debug_grid_build_ms: no timed crt_build_grid_device (debug hooks off?)");
-    HIPCK(c, hipEventSynchronize(c->gridT1));
-    HIPCK(c, hipEventElapsedTime(streamMs, c->gridT0, c->gridT1));
-    waitMs[0] = c->gridWaitMs[0]; waitMs[1] = c->gridWaitMs[1];
+    const crt_ctx::GridBuild& G = c->gridBuild;
+    if (!G.timed) return c->fail(CRT_ERR_STATE, "crt_debug_grid_build_ms: no timed crt_build_grid_device (debug hooks off?)");
+    HIPCK(c, hipEventSynchronize(G.t1));
+    HIPCK(c, hipEventElapsedTime(streamMs, G.t0, G.t1));
+    waitMs[0] = G.waitMs[0]; waitMs[1] = G.waitMs[1];
     return CRT_OK;
 }
 
@@ -2740,9 +2766,8 @@ extern "C" int crt_debug_grid_build_ms(crt_ctx* c, float* streamMs, double waitM
 extern "C" int crt_internal_read_device(crt_ctx* c, void* dst, const void* d_src, size_t bytes, void* stream)
 {
     if (!c || !dst) return CRT_ERR_INVALID;
-    HIPCK(c, hipSetDevice(c->cfg.device));
     int r; hipStream_t st = nullptr;
-    if ((r = check_device_buffer(c, d_src, bytes, "crt_internal_read_device")) || (r = caller_stream(c, stream, "crt_internal_read_device", &st))) return r;
+    if ((r = device_entry(c, "crt_internal_read_device", {{d_src, bytes}}, stream, &st))) return r;
     HIPCK(c, hipMemcpyAsync(dst, d_src, bytes, hipMemcpyDeviceToHost, st));
     HIPCK(c, hipStreamSynchronize(st));
     return CRT_OK;
@@ -2752,9 +2777,9 @@ extern "C" int crt_internal_read_device(crt_ctx* c, void* dst, const void* d_src
 extern "C" int crt_debug_tlas_build_ms(crt_ctx* c, float* ms)
 {
     if (!c || !ms) return CRT_ERR_INVALID;
-    if (!c->tlasTimed) return c->fail(CRT_ERR_STATE, "crt_debug_tlas_build_ms: no timed crt_update_transforms_device (debug hooks off?)");
-    HIPCK(c, hipEventSynchronize(c->tlasT1));
-    HIPCK(c, hipEventElapsedTime(ms, c->tlasT0, c->tlasT1));
+    if (!c->tlasBuild.timed) return c->fail(CRT_ERR_STATE, "crt_debug_tlas_build_ms: no timed crt_update_transforms_device (debug hooks off?)");
+    HIPCK(c, hipEventSynchronize(c->tlasBuild.t1));
+    HIPCK(c, hipEventElapsedTime(ms, c->tlasBuild.t0, c->tlasBuild.t1));
     return CRT_OK;
 }
 
@@ -2813,8 +2838,8 @@ int crt_get_hit_info_device(crt_ctx* c, const crt_ray* d_rays, const crt_hit* d_
     if ((r = check_device_buffer(c, d_rays, n * sizeof(crt_ray), what)) || (r = check_device_buffer(c, d_hits, n * sizeof(crt_hit), what)) ||
         (r = check_device_buffer(c, d_out, n * sizeof(crt_hit_info), what))) return r;
     if (reinterpret_cast<uintptr_t>(d_out) & 15u) return c->fail(CRT_ERR_INVALID, "%s: the output buffer %p is not 16-byte aligned", what, (void*)d_out);
-    hipStream_t st = nullptr; int k = 0;
-    if ((r = begin_device_query(c, stream, what, &st, &k))) return r;       // the slot's cursor word is unused: a record per lane, nothing to draw
+    hipStream_t st = nullptr; int k = 0;                                    // (device_entry's steps by hand: the refusal above comes before the stream's)
+    if ((r = caller_stream(c, stream, what, &st)) || (r = wait_scene(c, st)) || (r = take_query_slot(c, &k))) return r;       // the slot's cursor word is unused: a record per lane, nothing to draw
     HIPCK(c, crt_launch_hit_info(&c->hScene, d_rays, d_hits, d_out, (uint32_t)n, c->flat.objects, file_tri_count(c), st));
     return end_device_query(c, k, st);
 }
@@ -2844,10 +2869,8 @@ int crt_get_sky_color_device(crt_ctx* c, const crt_ray* d_rays, float* d_rgb, si
     int r;
     if ((r = shade_check(c, false, n, what))) return r;
     if (n == 0) return CRT_OK;
-    HIPCK(c, hipSetDevice(c->cfg.device));
-    if ((r = check_device_buffer(c, d_rays, n * sizeof(crt_ray), what)) || (r = check_device_buffer(c, d_rgb, n * 12, what))) return r;
     hipStream_t st = nullptr; int k = 0;
-    if ((r = begin_device_query(c, stream, what, &st, &k))) return r;
+    if ((r = device_entry(c, what, {{d_rays, n * sizeof(crt_ray)}, {d_rgb, n * 12}}, stream, &st)) || (r = wait_scene(c, st)) || (r = take_query_slot(c, &k))) return r;
     if (c->havePrim) HIPCK(c, hipMemsetAsync(d_rgb, 0, n * 12, st));          // PrimitiveScene::GetSkyColor
     else HIPCK(c, crt_launch_sky_color(&c->hScene, d_rays, d_rgb, (uint32_t)n, st));
     return end_device_query(c, k, st);
@@ -2896,10 +2919,8 @@ int crt_sample_device(crt_ctx* c, int accel, const crt_ray* d_rays, uint32_t* d_
     int r;
     if ((r = sample_check(c, accel, n, what))) return r;
     if (n == 0) return CRT_OK;
-    HIPCK(c, hipSetDevice(c->cfg.device));
-    if ((r = check_device_buffer(c, d_rays, n * sizeof(crt_ray), what)) || (r = check_device_buffer(c, d_seeds, n * 4, what)) || (r = check_device_buffer(c, d_rgb, n * 12, what))) return r;
     hipStream_t st = nullptr; int k = 0;
-    if ((r = begin_device_query(c, stream, what, &st, &k))) return r;
+    if ((r = device_entry(c, what, {{d_rays, n * sizeof(crt_ray)}, {d_seeds, n * 4}, {d_rgb, n * 12}}, stream, &st)) || (r = wait_scene(c, st)) || (r = take_query_slot(c, &k))) return r;
     if (accel != 0 && c->altReady) HIPCK(c, hipStreamWaitEvent(st, c->altReady, 0));     // the accelerators' copies ran on the null stream
     HIPCK(c, launch_sample(c, accel, d_rays, d_seeds, d_rgb, (uint32_t)n, c->dQuerySlots + 16 * k, nullptr, st));
     return end_device_query(c, k, st);

@@ -286,6 +286,43 @@ def test_two_level_set_follows_a_moved_blas(crt, orc):
         a.close()
 
 
+# 6b. the three device writers chained on three streams, queries in flight on a fourth, a render behind them: no host synchronisation until the end
+def test_refit_transforms_and_grid_chain_on_separate_streams(crt, orc):
+    W = H = 32
+    xml = scene_path("tlas_scene.xml")
+    hs = crt.HostScene(xml, 1, ASSETS); hs.build_alt(GRID)
+    n = hs.bvh_count(); assert n == 3
+    ctx = crt.Context(W, H); hs.upload(ctx); hs.upload_alt(ctx, GRID)
+    o, _ = orc.load_scene(xml, 1, ASSETS); o.renderer_init(W, H)
+    O, D = pixel_rays(o, W, H, 64); rays = ray_records(crt, O, D)
+    moved = G.wobble(positions(hs.bvh(1))); t1 = to_dev(moved)
+    T = to_dev(np.stack([hs.blas_transform(i)[0] for i in range(n)]))
+    s_q, s1, s2, s3 = (torch.cuda.Stream(device=dev()) for _ in range(4))
+    old = ctx.find_nearest_device(rays, stream=s_q)
+    ctx.refit_device(1, t1, stream=s1)
+    ctx.update_transforms_device(T, stream=s2)
+    ctx.build_grid_device(1, t1, stream=s3)
+    new_bvh = ctx.find_nearest_device(rays, stream=s_q)
+    new_grid = ctx.find_nearest_device(rays, accel=GRID, stream=s_q)
+    px, acc, energy = ctx.tick(1)
+    torch.cuda.synchronize()
+    want_old = o.find_nearest(O, D)
+    o.move_and_refit(1, moved)
+    want_bvh = o.find_nearest(O, D)
+    o.render(1, 4)
+    accels = orc.blas_accels(o, "grid"); orc.set_blas_accel(o, accels)
+    want_grid = o.find_nearest(O, D)
+    orc.set_blas_accel(o, None)
+    for a in accels:
+        a.close()
+    old, new_bvh = hits_np(crt, old), hits_np(crt, new_bvh)
+    assert any((old[f] != new_bvh[f]).any() for f in ("t", "triIdx")), "the second query never saw the update"
+    assert_hits_equal(old, want_old, "in flight before the chain: the unmoved scene")
+    assert_hits_equal(new_bvh, want_bvh, "behind the chain: the refitted BVH under the rebuilt TLAS")
+    assert_hits_equal(hits_np(crt, new_grid), want_grid, "behind the chain: the rebuilt grid set")
+    assert np.array_equal(acc, o.accumulator()), "the Tick behind the chain: one frame of the moved scene"
+
+
 # 7. refusals: the named status, and the previous grid keeps answering bit-identically
 def test_refusals_leave_the_previous_grid(crt, bunny):
     C = crt.C
