@@ -381,6 +381,7 @@ int crt_create(crt_ctx** out, const crt_config* cfg)
     s.bottomLeft[0] = -aspect; s.bottomLeft[1] = -1; s.bottomLeft[2] = 0;
     s.W = cfg->width; s.H = cfg->height; s.invW = 1.0f / cfg->width; s.invH = 1.0f / cfg->height;
     s.depthLimit = c->cfg.depthLimit;
+    crt::set_primary(s);
     if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) return bail(e, "hipStreamSynchronize");
     *out = c;
     return CRT_OK;
@@ -685,6 +686,7 @@ int crt_upload_scene(crt_ctx* c, const crt_scene_desc* sd)
         s.rootIsPair = 1;
     }
     if (hook("CRT_DEBUG_NO_ROOTPAIR")) s.rootIsPair = 0;                            // tests: every ray starts at the root reference instead
+    crt::set_primary(s);                                                            // new light / floor block and rootPair: the camera-relative block follows
     s.stackDepth = s.bvhStack + ((sd->kind == CRT_SCENE_TLAS) ? tlasHeight + 1 : 0);   // + TLAS pushes + the return marker
     c->ldsBytes = s.stackDepth * 64u * 4u; c->latSlots = 0;
     if (const char* e = hook("CRT_DEBUG_EXTRA_LDS")) c->ldsBytes += (uint32_t)atoi(e);   // occupancy experiments only
@@ -830,6 +832,7 @@ static void set_root(crt_ctx* c, int kind, const float* lo, const float* hi)
         s.rootIsPair = 1;
     }
     if (hook("CRT_DEBUG_NO_ROOTPAIR")) s.rootIsPair = 0;
+    crt::set_primary(s);
     memcpy(c->meshLo, lo, 12); memcpy(c->meshHi, hi, 12); c->orderDirty = true;
 }
 
@@ -956,6 +959,7 @@ int crt_set_camera(crt_ctx* c, const float camPos[3], const float tl[3], const f
     crt::Scene& s = c->hScene;
     if (!memcmp(s.camPos, camPos, 12) && !memcmp(s.topLeft, tl, 12) && !memcmp(s.topRight, tr, 12) && !memcmp(s.bottomLeft, bl, 12)) return CRT_OK;   // unchanged (a per-frame PushCamera)
     memcpy(s.camPos, camPos, 12); memcpy(s.topLeft, tl, 12); memcpy(s.topRight, tr, 12); memcpy(s.bottomLeft, bl, 12);
+    crt::set_primary(s);
     c->orderDirty = true; c->epoch++;
     return CRT_OK;      // the Scene block travels by value in every launch's kernel arguments
 }
@@ -3014,25 +3018,74 @@ extern "C" int crt_debug_check_reciprocals(crt_ctx* c, uint64_t* out)
     return CRT_OK;
 }
 
+// tests: the device's short square root (dev_common.h sqrt_exact) against the compiler's IEEE sequence over all 2^32 inputs; out[2] = {inputs, differences}
+extern "C" int crt_debug_check_sqrt(crt_ctx* c, uint64_t* out)
+{
+    if (!c || !out) return CRT_ERR_INVALID;
+    HIPCK(c, hipSetDevice(c->cfg.device));
+    unsigned long long* d = nullptr;
+    HIPCK(c, hipMalloc(&d, 16));
+    hipError_t e = hipMemsetAsync(d, 0, 16, c->stream);
+    if (e == hipSuccess) e = crt_launch_check_sqrt(d, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(out, d, 16, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    (void)hipFree(d);
+    HIPCK(c, e);
+    return CRT_OK;
+}
+
+// tests: what the context's Scene block holds for primary rays: out[16 + kPrimFloats] = rootPair, then the camera-relative block (layout.h set_primary); the
+// optional others: camera[12] = camPos, topLeft, topRight, bottomLeft; lightFloor[4] = lightInvT[7], [3], [11], floorD
+extern "C" int crt_debug_primary_block(crt_ctx* c, float* out, float* camera, float* lightFloor)
+{
+    if (!c || !out) return CRT_ERR_INVALID;
+    const crt::Scene& s = c->hScene;
+    static_assert(offsetof(crt::Scene, primRoot) == offsetof(crt::Scene, rootPair) + 64 && offsetof(crt::Scene, primDown) + 12 == offsetof(crt::Scene, rootPair) + 64 + 4 * crt::kPrimFloats, "primary block");
+    memcpy(out, s.rootPair, 64 + 4 * crt::kPrimFloats);
+    if (camera) memcpy(camera, s.camPos, 48);
+    if (lightFloor) { lightFloor[0] = s.lightInvT[7]; lightFloor[1] = s.lightInvT[3]; lightFloor[2] = s.lightInvT[11]; lightFloor[3] = s.floorD; }
+    return CRT_OK;
+}
+// tests (no GPU needed): the same on a context that holds nothing but a Scene block, through the block's writers in the order of a session.  op 0 = a new context's
+// defaults, then upload's light / floor block and root pair (in = lightInvT[12], floorD, rootPair[16]); op 1 = the camera setter's part (in = camPos, topLeft,
+// topRight, bottomLeft); op 2 = a rebuilt root pair (in = rootPair[16]), what set_root does after a refit / TLAS rebuild.  out as crt_debug_primary_block's.
+extern "C" int crt_debug_primary_block_host(int op, const float* in, float* out)
+{
+    static crt::Scene s{};
+    if (!in || !out || op < 0 || op > 2) return CRT_ERR_INVALID;
+    if (op == 0) {
+        s = crt::Scene{};
+        s.camPos[2] = -2; s.topLeft[0] = -1; s.topLeft[1] = 1; s.topRight[0] = 1; s.topRight[1] = 1; s.bottomLeft[0] = -1; s.bottomLeft[1] = -1;
+        memcpy(s.lightInvT, in, 48); s.floorD = in[12]; memcpy(s.rootPair, in + 13, 64); s.rootIsPair = 1;
+    } else if (op == 1) { memcpy(s.camPos, in, 12); memcpy(s.topLeft, in + 3, 12); memcpy(s.topRight, in + 6, 12); memcpy(s.bottomLeft, in + 9, 12); }
+    else memcpy(s.rootPair, in, 64);
+    crt::set_primary(s);
+    memcpy(out, s.rootPair, 64 + 4 * crt::kPrimFloats);
+    return CRT_OK;
+}
+
 // tests: dev_common.h's fp32 building blocks (device/probe.hip) and the torus' fp64 ones (end of device/render_prim.hip) on the device at hand, one element per
 // thread: host buffers in and out, one launch.  Ops and record layouts: the table at the top of device/probe.hip.  n <= 2^25 records per call.
-extern "C" int crt_debug_device_probe(crt_ctx* c, int op, const void* in, void* out, uint32_t n)
+static int device_probe(crt_ctx* c, int op, const void* in, void* out, uint32_t n)
 {
-    static const uint8_t words[17][2] = {{1, 1}, {1, 1}, {2, 1}, {1, 1}, {2, 1}, {6, 7}, {1, 18}, {4, 1}, {5, 3}, {13, 2}, {16, 4}, {2, 2}, {2, 2}, {2, 2}, {2, 2}, {4, 2}, {2, 1}};
-    if (!c || !in || !out || op < 0 || op > 16 || n > (1u << 25)) return CRT_ERR_INVALID;
+    static const uint8_t words[18][2] = {{1, 1}, {1, 1}, {2, 1}, {1, 1}, {2, 1}, {6, 7}, {1, 18}, {4, 1}, {5, 3}, {13, 2}, {16, 4}, {2, 2}, {2, 2}, {2, 2}, {2, 2}, {4, 2}, {2, 1}, {5, 3}};
+    if (!c || !in || !out || op < 0 || op > 17 || n > (1u << 25)) return CRT_ERR_INVALID;
     if (n == 0) return CRT_OK;
     const size_t inBytes = (size_t)n * words[op][0] * 4, outBytes = (size_t)n * words[op][1] * 4;
     HIPCK(c, hipSetDevice(c->cfg.device));
     char* d = nullptr;
     HIPCK(c, hipMalloc((void**)&d, inBytes + outBytes));               // inBytes is a multiple of 8 for the fp64 ops: both halves stay aligned
     hipError_t e = hipMemcpyAsync(d, in, inBytes, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = (op <= 10) ? crt_launch_probe_f32(op, d, d + inBytes, n, c->stream) : crt_launch_probe_f64(op, d, d + inBytes, n, c->stream);
+    if (e == hipSuccess) e = (op <= 10 || op == 17) ? crt_launch_probe_f32(op, d, d + inBytes, n, c->stream) : crt_launch_probe_f64(op, d, d + inBytes, n, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(out, d + inBytes, outBytes, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     (void)hipFree(d);
     HIPCK(c, e);
     return CRT_OK;
 }
+extern "C" int crt_debug_device_probe(crt_ctx* c, int op, const void* in, void* out, uint32_t n) { return (op > 16) ? CRT_ERR_INVALID : device_probe(c, op, in, out, n); }
+// tests: op 8's lookup through sky_angles, the guarded form the render kernels and the sky query call (probe.hip op 17; records as op 8's)
+extern "C" int crt_debug_sky_probe(crt_ctx* c, const void* in, void* out, uint32_t n) { return device_probe(c, 17, in, out, n); }
 
 // tests (no GPU needed): the planner's decision for given tile costs — plan_job on a context that holds nothing but the costs.  table[] receives the block
 // descriptors (tile | first frame << 16 | log2(lanes) << 22 | window << 25), order[] the dispatch order, *head the number of leading tiles of it that go to the table

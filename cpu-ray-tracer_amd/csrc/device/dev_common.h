@@ -58,7 +58,27 @@ __device__ __forceinline__ f3 rcp_exact3(f3 v)
     if (__builtin_expect(__builtin_amdgcn_ballot_w64(!okay) != 0, 0)) r = mk3(1.0f / v.x, 1.0f / v.y, 1.0f / v.z);
     return r;
 }
-__device__ __forceinline__ f3 normalize3(f3 v) { float inv = rcp_exact(__builtin_sqrtf(dot3(v, v))); return v * inv; }
+// sqrtf(x) in nine instructions instead of the twenty-one issue slots of the compiler's IEEE expansion.  That expansion is: scale x by 2^32 if x < 2^-96; s = v_sqrt_f32
+// (1 ulp); the rounding decision between s and its two neighbours by the signs of the residuals fma(-(s - 1 ulp), s, x) <= 0 and fma(-(s + 1 ulp), s, x) > 0; scale back;
+// return x itself for +-0 and +inf.  For 2^-96 <= x < inf neither scaling nor the zero / infinity select does anything, and what is left is the sequence below, operation
+// for operation: the same bits by construction, and compared with __builtin_sqrtf over all 2^32 inputs on the device (crt_debug_check_sqrt, tests/test_gpu_pool_diet.py).
+// If any active lane of the wave holds another input (< 2^-96, zero, negative, inf, NaN) the wave takes the compiler's sequence instead (a scalar branch, as rcp_exact's).
+// (-DCRT_DIET_NO_SQRT builds the compiler's sequence everywhere)
+__device__ __forceinline__ float sqrt_exact(float x)
+{
+#ifdef CRT_DIET_NO_SQRT
+    return __builtin_sqrtf(x);
+#else
+    const float s = __builtin_amdgcn_sqrtf(x);
+    const float dn = __uint_as_float(__float_as_uint(s) - 1u), up = __uint_as_float(__float_as_uint(s) + 1u);
+    const float rdn = __builtin_fmaf(-dn, s, x), rup = __builtin_fmaf(-up, s, x);
+    float r = (rdn <= 0.0f) ? dn : s;
+    r = (rup > 0.0f) ? up : r;
+    if (__builtin_expect(__builtin_amdgcn_ballot_w64(__float_as_uint(x) - 0x0f800000u >= 0x70000000u) != 0, 0)) r = __builtin_sqrtf(x);   // !(2^-96 <= x < inf), as bit patterns: 0x0f800000 .. 0x7f7fffff
+    return r;
+#endif
+}
+__device__ __forceinline__ f3 normalize3(f3 v) { float inv = rcp_exact(sqrt_exact(dot3(v, v))); return v * inv; }
 __device__ __forceinline__ float min_std(float a, float b) { return (b < a) ? b : a; }   // std::min(a,b)
 __device__ __forceinline__ float max_std(float a, float b) { return (a < b) ? b : a; }   // std::max(a,b)
 __device__ __forceinline__ float min_tm(float a, float b) { return a < b ? a : b; }       // tmplmath fminf
@@ -141,11 +161,48 @@ __device__ __forceinline__ float crt_asin_small(float x)
 __device__ __forceinline__ float crt_acosf(float x)
 {
     const bool hi = x > 0.5f, lo = x < -0.5f;
-    const float s = __builtin_sqrtf(0.5f * (1.0f - __builtin_fabsf(x)));
+    const float s = sqrt_exact(0.5f * (1.0f - __builtin_fabsf(x)));
     const float p = crt_asin_small((hi || lo) ? s : x);
     float r = hi ? 2.0f * p : (lo ? CRT_PI - 2.0f * p : 1.5707963267948966f - p);
     if (x > 1.0f || x < -1.0f) r = asf(0x7fc00000u);
     return (x != x) ? x : r;
+}
+// The two functions without the selects of their special cases, for operands that have none.  Every other expression is the one above, in the same order, so for
+// such operands the bits are those of crt_atan2f / crt_acosf.  Callers establish the precondition for a whole wave at once (sky_angles).
+//   crt_atan2f_plain(y, x), x and y finite and non-zero.  Left out:  `ax == inf && ay == inf` (no operand is infinite);  `ax == 0` and `ay == 0` (no operand is a
+//   zero: x == -0 in particular must stay out, the general expression gives pi - pi/2 there and the select pi/2);  the NaN return (no operand is a NaN).  A
+//   quotient ay / ax that overflows to inf or underflows to 0 is not a special case of crt_atan2f either: crt_atan_pos takes it as it is, here as there.
+//   crt_acosf_plain(x), |x| <= 1.  Left out:  the NaN of |x| > 1 and the NaN return (|x| <= 1 is false for a NaN).
+__device__ __forceinline__ float crt_atan2f_plain(float y, float x)
+{
+    const uint32_t sy = asu(y) & 0x80000000u, sx = asu(x) & 0x80000000u;
+    const float ax = __builtin_fabsf(x), ay = __builtin_fabsf(y);
+    const float a = crt_atan_pos(ay / ax);
+    const float r = sx ? (CRT_PI - a) : a;
+    return asf(asu(r) | sy);
+}
+__device__ __forceinline__ float crt_acosf_plain(float x)
+{
+    const bool hi = x > 0.5f, lo = x < -0.5f;
+    const float s = sqrt_exact(0.5f * (1.0f - __builtin_fabsf(x)));
+    const float p = crt_asin_small((hi || lo) ? s : x);
+    return hi ? 2.0f * p : (lo ? CRT_PI - 2.0f * p : 1.5707963267948966f - p);
+}
+// GetSkyColor's angles of a direction (file_scene.cpp:142-154): phi = atan2(-D.z, D.x) + pi, theta = acos(-D.y).  A normalised finite direction almost never has a
+// component that is exactly zero, so the special-case selects of the two functions (compare + select pairs, half rate) sit behind ONE wave-uniform guard: the plain
+// forms when no active lane holds a special operand, the general functions for the whole wave otherwise (a scalar branch, as rcp_exact's).
+// (-DCRT_DIET_NO_SKY builds the general functions everywhere)
+__device__ __forceinline__ void sky_angles(f3 D, float& phi, float& theta)
+{
+    const float y = -D.z, x = D.x, c = -D.y;
+#ifndef CRT_DIET_NO_SKY
+    // a zero, an infinity or a NaN, as ONE unsigned compare of the bit pattern: (bits << 1) - 1 drops the sign and wraps +-0 to the top, so everything from inf
+    // (0xff000000 - 1) upwards is special.  (The compare builtin returns the lane mask itself; the ballot of a v_cmp_class result goes through a VGPR.)
+    const uint64_t special = __builtin_amdgcn_uicmp((asu(x) << 1) - 1u, 0xfeffffffu, 35 /* unsigned >= */) | __builtin_amdgcn_uicmp((asu(y) << 1) - 1u, 0xfeffffffu, 35)
+                           | __builtin_amdgcn_ballot_w64(!(__builtin_fabsf(c) <= 1.0f));
+    if (__builtin_expect(special == 0, 1)) { phi = crt_atan2f_plain(y, x) + CRT_PI; theta = crt_acosf_plain(c); return; }
+#endif
+    phi = crt_atan2f(y, x) + CRT_PI; theta = crt_acosf(c);
 }
 
 // RNG: WangHash seed + xorshift32 (template/tmplmath.cpp:5-16, 27-34)
@@ -176,6 +233,18 @@ typedef float rec4 __attribute__((ext_vector_type(4)));     // a fetched 16-byte
 __device__ __forceinline__ rec4 ld4(const void* p) { return *reinterpret_cast<const rec4*>(p); }
 // record fetch: scalar base + 32-bit per-lane byte offset (global_load_dwordx4 v, v_off, s[base:base+1])
 __device__ __forceinline__ rec4 ldg(const char* __restrict__ base, uint32_t byteOff) { return *reinterpret_cast<const rec4*>(base + byteOff); }
+// Piece PIECE (16 bytes) of the 64-byte record at byteOff, with the piece's constant distance in the load's immediate field (global_load_dwordx4 v, v_off, s[base:base+1]
+// offset:16) instead of a v_add_u32 per piece.  `byteOff + 16u` is 32-bit unsigned arithmetic that may wrap, which is what keeps the compiler from folding the constant;
+// it cannot wrap here, and the compiler is told so: every record is fetched as 64 bytes inside a buffer of at most kMaxGeomBytes = 2^32 bytes, so byteOff + 63 < 2^32.
+// (-DCRT_DIET_NO_RECPTR leaves the assumption out)
+static_assert(kMaxGeomBytes == (1ull << 32), "ldp: byteOff + 63 < 2^32");
+template <uint32_t PIECE> __device__ __forceinline__ rec4 ldp(const char* __restrict__ base, uint32_t byteOff)
+{
+#ifndef CRT_DIET_NO_RECPTR
+    __builtin_assume(byteOff <= 0xffffffffu - 63u);
+#endif
+    return ldg(base, byteOff + 16u * PIECE);
+}
 __device__ __forceinline__ bool finite3(f3 v)
 {
     const uint32_t m = 0x7f800000u;
@@ -183,15 +252,21 @@ __device__ __forceinline__ bool finite3(f3 v)
 }
 
 // slab test, infra/bvh.cpp:181-190, with the reference's std::min / std::max operand order (NaN-exact)
-__device__ __forceinline__ float box_exact(rec4 lo, rec4 hi, f3 O, f3 rD, float tray)
+// (the `_rel` forms take the box relative to the ray's origin, lo - O and hi - O: the differences are the first operation of the test, and for primary rays they are
+// the same for every ray — Scene::primRoot holds them, formed on the host)
+__device__ __forceinline__ float box_exact_rel(f3 lo, f3 hi, f3 rD, float tray)
 {
-    float tx1 = (lo.x - O.x) * rD.x, tx2 = (hi.x - O.x) * rD.x;
+    float tx1 = lo.x * rD.x, tx2 = hi.x * rD.x;
     float tmin = min_std(tx1, tx2), tmax = max_std(tx1, tx2);
-    float ty1 = (lo.y - O.y) * rD.y, ty2 = (hi.y - O.y) * rD.y;
+    float ty1 = lo.y * rD.y, ty2 = hi.y * rD.y;
     tmin = max_std(tmin, min_std(ty1, ty2)); tmax = min_std(tmax, max_std(ty1, ty2));
-    float tz1 = (lo.z - O.z) * rD.z, tz2 = (hi.z - O.z) * rD.z;
+    float tz1 = lo.z * rD.z, tz2 = hi.z * rD.z;
     tmin = max_std(tmin, min_std(tz1, tz2)); tmax = min_std(tmax, max_std(tz1, tz2));
     return (tmax >= tmin && tmin < tray && tmax > 0) ? tmin : 1e30f;
+}
+__device__ __forceinline__ float box_exact(rec4 lo, rec4 hi, f3 O, f3 rD, float tray)
+{
+    return box_exact_rel(mk3(lo.x - O.x, lo.y - O.y, lo.z - O.z), mk3(hi.x - O.x, hi.y - O.y, hi.z - O.z), rD, tray);
 }
 // same test with v_min/v_max(3): identical decisions whenever no product is NaN, i.e. whenever all three rD are
 // finite (0 * inf is the only NaN source); the sign of a zero result never reaches a comparison that can tell.
@@ -199,14 +274,18 @@ __device__ __forceinline__ float vmin(float a, float b) { float r; asm("v_min_f3
 __device__ __forceinline__ float vmax(float a, float b) { float r; asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
 __device__ __forceinline__ float vmin3(float a, float b, float c) { float r; asm("v_min3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c)); return r; }
 __device__ __forceinline__ float vmax3(float a, float b, float c) { float r; asm("v_max3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c)); return r; }
-__device__ __forceinline__ float box_fast(rec4 lo, rec4 hi, f3 O, f3 rD, float tray)
+__device__ __forceinline__ float box_fast_rel(f3 lo, f3 hi, f3 rD, float tray)
 {
-    float tx1 = (lo.x - O.x) * rD.x, tx2 = (hi.x - O.x) * rD.x;
-    float ty1 = (lo.y - O.y) * rD.y, ty2 = (hi.y - O.y) * rD.y;
-    float tz1 = (lo.z - O.z) * rD.z, tz2 = (hi.z - O.z) * rD.z;
+    float tx1 = lo.x * rD.x, tx2 = hi.x * rD.x;
+    float ty1 = lo.y * rD.y, ty2 = hi.y * rD.y;
+    float tz1 = lo.z * rD.z, tz2 = hi.z * rD.z;
     float tmin = vmax3(vmin(tx1, tx2), vmin(ty1, ty2), vmin(tz1, tz2));
     float tmax = vmin3(vmax(tx1, tx2), vmax(ty1, ty2), vmax(tz1, tz2));
     return (tmax >= tmin && tmin < tray && tmax > 0) ? tmin : 1e30f;
+}
+__device__ __forceinline__ float box_fast(rec4 lo, rec4 hi, f3 O, f3 rD, float tray)
+{
+    return box_fast_rel(mk3(lo.x - O.x, lo.y - O.y, lo.z - O.z), mk3(hi.x - O.x, hi.y - O.y, hi.z - O.z), rD, tray);
 }
 
 // Möller–Trumbore on a fetched LeafTri {a = v0|shadeIdx, b = e1|objIdx, c = e2|remain}, infra/bvh.cpp:203-222
@@ -229,7 +308,10 @@ __device__ __forceinline__ void hit_tri(rec4 a, rec4 b, rec4 c, f3 O, f3 D, Hit&
 // Quad::Intersect + Plane::Intersect (template/primitives.h:331-346, 107-111): the two analytic primitives FindNearest
 // tests before the acceleration structure (file_scene.cpp:170-175)
 // (the operands as values: render_pool_kernel reads them from the kernel-argument segment inside its passes instead of holding them in scalar registers)
-struct LightFloor { float lightInvT[12]; float lightSize; uint32_t lightAxis, floorAxisY; float floorN[3]; float floorD; };
+// (PRE: the ray starts at the camera and `pre` holds the sums of the short expressions that involve only O — Scene::primLight / primFloor, formed on the host; the general
+// expressions are evaluated as always)
+struct LightFloor { float lightInvT[12]; float lightSize; uint32_t lightAxis, floorAxisY; float floorN[3]; float floorD; float preOy, preOx, preOz, preNum; };
+template <bool PRE = false>
 __device__ __forceinline__ void hit_light_floor(const LightFloor& sc, f3 O, f3 D, Hit& h)
 {
     // Scene::lightAxis / floorAxisY (set at upload): the quad's invT has an identity rotation block / the plane's normal is exactly
@@ -239,12 +321,12 @@ __device__ __forceinline__ void hit_light_floor(const LightFloor& sc, f3 O, f3 D
     {
         const float* c = sc.lightInvT;
         float Oy, Dy;
-        if (sc.lightAxis) { Oy = O.y + c[7]; Dy = D.y; }
+        if (sc.lightAxis) { Oy = PRE ? sc.preOy : O.y + c[7]; Dy = D.y; }
         else { Oy = c[4] * O.x + c[5] * O.y + c[6] * O.z + c[7]; Dy = c[4] * D.x + c[5] * D.y + c[6] * D.z; }
         const float t = Oy / -Dy;
         if (t < h.t && t > 0) {
             float Ox, Oz, Dx, Dz;
-            if (sc.lightAxis) { Ox = O.x + c[3]; Oz = O.z + c[11]; Dx = D.x; Dz = D.z; }
+            if (sc.lightAxis) { Ox = PRE ? sc.preOx : O.x + c[3]; Oz = PRE ? sc.preOz : O.z + c[11]; Dx = D.x; Dz = D.z; }
             else {
                 Ox = c[0] * O.x + c[1] * O.y + c[2] * O.z + c[3];
                 Oz = c[8] * O.x + c[9] * O.y + c[10] * O.z + c[11];
@@ -258,7 +340,7 @@ __device__ __forceinline__ void hit_light_floor(const LightFloor& sc, f3 O, f3 D
     }
     {
         float num, den;
-        if (sc.floorAxisY) { num = O.y + sc.floorD; den = D.y; }
+        if (sc.floorAxisY) { num = PRE ? sc.preNum : O.y + sc.floorD; den = D.y; }
         else { const f3 N = mk3(sc.floorN[0], sc.floorN[1], sc.floorN[2]); num = dot3(O, N) + sc.floorD; den = dot3(D, N); }
         const float t = -num / den;
         if (t < h.t && t > 0) { h.t = t; h.objIdx = 1; }
@@ -272,6 +354,7 @@ __device__ __forceinline__ void hit_light_floor(const Scene& sc, f3 O, f3 D, Hit
     for (int i = 0; i < 12; i++) lf.lightInvT[i] = sc.lightInvT[i];
     lf.lightSize = sc.lightSize; lf.lightAxis = sc.lightAxis; lf.floorAxisY = sc.floorAxisY;
     lf.floorN[0] = sc.floorN[0]; lf.floorN[1] = sc.floorN[1]; lf.floorN[2] = sc.floorN[2]; lf.floorD = sc.floorD;
+    lf.preOy = lf.preOx = lf.preOz = lf.preNum = 0.0f;
     hit_light_floor(lf, O, D, h);
 }
 
@@ -300,6 +383,7 @@ __device__ __forceinline__ bool quad_occluded(const Scene& sc, f3 O, f3 D, float
 static_assert(offsetof(Scene, topLeft) == offsetof(Scene, camPos) + 12 && offsetof(Scene, bottomLeft) == offsetof(Scene, camPos) + 36 && offsetof(Scene, invW) == offsetof(Scene, camPos) + 48 && offsetof(Scene, invH) == offsetof(Scene, camPos) + 52, "camera block");
 static_assert(offsetof(Scene, lightSize) == offsetof(Scene, lightInvT) + 60 && offsetof(Scene, floorN) == offsetof(Scene, lightInvT) + 76 && offsetof(Scene, floorD) == offsetof(Scene, lightInvT) + 88 && offsetof(Scene, floorInvto) == offsetof(Scene, floorN) + 16, "light / floor block");
 static_assert(offsetof(Scene, floorAxisY) == offsetof(Scene, lightAxis) + 4 && offsetof(Scene, skyW) == offsetof(Scene, skyOffset) + 4 && offsetof(Scene, skyH) == offsetof(Scene, skyOffset) + 8, "flag / sky words");
+static_assert(offsetof(Scene, primRoot) == offsetof(Scene, rootPair) + 64 && offsetof(Scene, primFloor) == offsetof(Scene, primLight) + 12 && offsetof(Scene, primDown) == offsetof(Scene, primRight) + 12, "camera-relative block");
 static_assert(offsetof(Material, absorption) == 8 && offsetof(Material, texOffset) == 20 && offsetof(Material, texW) == 24 && offsetof(Material, texH) == 28, "Material words");
 typedef const float __attribute__((address_space(4)))* kernarg_f;
 __device__ __forceinline__ kernarg_f scene_floats(size_t byteOffset)
@@ -425,8 +509,8 @@ __device__ __forceinline__ f3 tex_sample(const Scene& sc, uint32_t offset, int w
 // GetSkyColor, infra/scene/file_scene.cpp:142-154
 __device__ __forceinline__ f3 sky_color(const Scene& sc, f3 D)
 {
-    float phi = crt_atan2f(-D.z, D.x) + CRT_PI;
-    float theta = crt_acosf(-D.y);
+    float phi, theta;
+    sky_angles(D, phi, theta);
     return tex_sample(sc, sc.skyOffset, sc.skyW, sc.skyH, phi * CRT_INV2PI, theta * CRT_INVPI);
 }
 

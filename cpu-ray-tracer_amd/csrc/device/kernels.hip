@@ -1236,6 +1236,28 @@ extern "C" hipError_t crt_launch_check_reciprocals(unsigned long long* out, hipS
     return hipGetLastError();
 }
 
+// the same self-check for dev_common.h's short square root (tests/test_gpu_pool_diet.py through crt_debug_check_sqrt): every one of the 2^32 float bit patterns
+// through sqrt_exact against __builtin_sqrtf, bit for bit (two NaNs count as equal).  Consecutive bit patterns share a wavefront, so most wavefronts take the short
+// form and the ones at the edges of its range (and all of the negative half) the compiler's.  out = {inputs, differences}
+namespace crt {
+__global__ __launch_bounds__(256) void check_sqrt_kernel(unsigned long long* out)
+{
+    const uint32_t tid = blockIdx.x * 256u + threadIdx.x, nthreads = gridDim.x * 256u;
+    unsigned long long n = 0, bad = 0;
+    for (uint64_t b = tid; b < (1ull << 32); b += nthreads) {
+        const float x = asf((uint32_t)b);
+        n++;
+        if (!same_bits(sqrt_exact(x), __builtin_sqrtf(x))) bad++;
+    }
+    atomicAdd(&out[0], n); atomicAdd(&out[1], bad);
+}
+} // namespace crt
+extern "C" hipError_t crt_launch_check_sqrt(unsigned long long* out, hipStream_t stream)
+{
+    hipLaunchKernelGGL(crt::check_sqrt_kernel, dim3(4096), dim3(256), 0, stream, out);
+    return hipGetLastError();
+}
+
 // blockDesc / nBlocks: block table (see the kernel; the launch renders exactly the table's blocks), else nullptr / 0; tileCost: nullptr or one uint32 per tile, atomicMax'ed
 extern "C" hipError_t crt_launch_render(const crt::Scene* sc, void* slab, crt::Counters* counters, unsigned long long* tileClocks, const uint32_t* tileOrder,
                                         uint32_t tileFirst, uint32_t tileStride, uint32_t tileCount, uint32_t tilesX, uint32_t sppFirst,

@@ -11,6 +11,7 @@ extern "C" {
 
 // ---- kernels.hip ----
 hipError_t crt_launch_check_reciprocals(unsigned long long* out, hipStream_t stream);
+hipError_t crt_launch_check_sqrt(unsigned long long* out, hipStream_t stream);
 hipError_t crt_launch_render(const crt::Scene* sc, void* slab, crt::Counters* counters, unsigned long long* tileClocks, const uint32_t* tileOrder, uint32_t tileFirst, uint32_t tileStride,
     uint32_t tileCount, uint32_t tilesX, uint32_t sppFirst, uint32_t frames, uint32_t passes, uint32_t ldsBytes, int collectStats, const uint32_t* blockDesc, uint32_t nBlocks, uint32_t* tileCost,
     uint32_t rankCount, unsigned long long* launchClk, hipStream_t stream);

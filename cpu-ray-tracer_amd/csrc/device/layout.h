@@ -100,7 +100,31 @@ struct Scene {                            // passed to the kernels BY VALUE (ker
     uint32_t lightAxis, floorAxisY;       // 1: light invT has an identity rotation block / floor normal is exactly (0,1,0): short quad / plane tests (kernels.hip)
     uint32_t rootIsPair;                  // 1: rootPair holds the root's two children (always, unless the root itself is a leaf)
     float rootPair[16];                   // NodePair of the root (BVH: its child pair; TLAS: its two child TlasNodes, same 2 x {lo, ref, hi, -} layout)
+    // Camera-relative operands of PRIMARY rays, directly behind rootPair (one block for the kernel's scalar loads).  Every primary ray starts at camPos, so these
+    // differences and sums are the same for all lanes and all pixels; the device has no scalar float unit and would recompute them per lane and per ray.  The host
+    // computes them with the same single-rounded float operation (set_primary, below: the ONLY writer), whenever the camera, the light / floor block or rootPair
+    // changes; render_pool_kernel's END pass uses them (new_ray's primary form).
+    float primRoot[12];                   // child 1: lo - camPos, hi - camPos; child 2: lo - camPos, hi - camPos
+    float primLight[3];                   // camPos.y + lightInvT[7], camPos.x + lightInvT[3], camPos.z + lightInvT[11]   (the lightAxis expressions)
+    float primFloor;                      // camPos.y + floorD                                                            (the floorAxisY expression)
+    float primRight[3], primDown[3];      // topRight - topLeft, bottomLeft - topLeft
 };
+constexpr uint32_t kPrimFloats = 22u;     // primRoot .. primDown
+
+// Scene's camera-relative block from its camera, light / floor block and rootPair: each value ONE float operation, the one the kernels perform (host code is
+// built with -ffp-contract=off as well)
+inline void set_primary(Scene& s)
+{
+    const float* O = s.camPos;
+    for (int c = 0; c < 2; c++)
+        for (int k = 0; k < 3; k++) {
+            s.primRoot[6 * c + k] = s.rootPair[8 * c + k] - O[k];
+            s.primRoot[6 * c + 3 + k] = s.rootPair[8 * c + 4 + k] - O[k];
+        }
+    s.primLight[0] = O[1] + s.lightInvT[7]; s.primLight[1] = O[0] + s.lightInvT[3]; s.primLight[2] = O[2] + s.lightInvT[11];
+    s.primFloor = O[1] + s.floorD;
+    for (int k = 0; k < 3; k++) { s.primRight[k] = s.topRight[k] - s.topLeft[k]; s.primDown[k] = s.bottomLeft[k] - s.topLeft[k]; }
+}
 
 struct Counters { unsigned long long v[8]; };   // order = crt_counters
 

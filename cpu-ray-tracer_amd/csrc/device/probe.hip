@@ -26,6 +26,7 @@
 //   14  SQRT64    x (double)                                     2    __builtin_sqrt(x) (double)                                         2
 //   15  DIV64     a, b (doubles)                                 4    a / b (double)                                                     2
 //   16  F64TOF32  x (double)                                     2    (float)x                                                           1
+//   17  SKYFAST   D.xyz, w (i32), h (i32)                        5    as op 8, through sky_angles: the guarded lookup as the render kernels call it  3
 #include "dev_common.h"
 #include "launch.h"
 
@@ -72,6 +73,13 @@ __global__ __launch_bounds__(256) void probe_f32_kernel(int op, const uint32_t* 
         o[0] = asu(phi); o[1] = asu(theta); o[2] = tex_index(0u, (int)p[3], (int)p[4], phi * CRT_INV2PI, theta * CRT_INVPI);
         break;
     }
+    case 17: {  // the same lookup as the render kernels and the sky query make it: sky_angles' plain forms unless a lane of the wavefront holds a special operand
+        const uint32_t* p = in + 5 * (size_t)i; uint32_t* o = out + 3 * (size_t)i;
+        float phi, theta;
+        sky_angles(mk3(asf(p[0]), asf(p[1]), asf(p[2])), phi, theta);
+        o[0] = asu(phi); o[1] = asu(theta); o[2] = tex_index(0u, (int)p[3], (int)p[4], phi * CRT_INV2PI, theta * CRT_INVPI);
+        break;
+    }
     case 9: {
         const uint32_t* p = in + 13 * (size_t)i;
         rec4 lo, hi; lo.x = asf(p[0]); lo.y = asf(p[1]); lo.z = asf(p[2]); lo.w = 0.0f; hi.x = asf(p[3]); hi.y = asf(p[4]); hi.z = asf(p[5]); hi.w = 0.0f;
@@ -101,7 +109,7 @@ __global__ __launch_bounds__(256) void probe_f32_kernel(int op, const uint32_t* 
 extern "C" hipError_t crt_launch_probe_f32(int op, const void* in, void* out, uint32_t n, hipStream_t stream)
 {
     if (n == 0) return hipSuccess;
-    if (op < 0 || op > 10) return hipErrorInvalidValue;
+    if ((op < 0 || op > 10) && op != 17) return hipErrorInvalidValue;
     hipLaunchKernelGGL(crt::probe_f32_kernel, dim3((n + 255u) / 256u), dim3(256), 0, stream, op, (const uint32_t*)in, (uint32_t*)out, n);
     return hipGetLastError();
 }

@@ -22,6 +22,7 @@
 // written there, so the image is bit-identical to render_tiles_kernel's and to the CPU oracle's.
 //
 // Numerics: -ffp-contract=off, IEEE + - * / sqrt only (dev_common.h).  No MFMA: pointer chasing + slab / Möller–Trumbore tests.
+#include <type_traits>
 #include "dev_common.h"
 #include "launch.h"
 
@@ -92,10 +93,18 @@ __device__ unsigned long long* g_poolTimeline = nullptr;
 // per-lane predicate is `lane_in(mask)` = the mask used directly as the execution / select mask (amdgcn inverse ballot): no v_cndmask + v_cmp round trip per
 // ballot, and `resident` never has to be re-derived from lane state.
 __device__ __forceinline__ bool lane_in(uint64_t m) { return __builtin_amdgcn_inverse_ballot_w64(m); }
-__device__ __forceinline__ uint64_t finite3_mask(f3 v)          // lanes whose three components are all finite: three compares straight into scalar masks
+// lanes (of the active ones) whose three components are all finite: three compares straight into scalar masks.  |x| < inf is false for inf and NaN alike, i.e. it is
+// finite3's "exponent not all ones"; the compare builtin returns the lane mask itself, where the ballot of a bool goes through a VGPR (v_cndmask 0 / 1 + v_cmp_ne).
+// (-DCRT_DIET_NO_MASKS builds the ballots)
+__device__ __forceinline__ uint64_t finite3_mask(f3 v)
 {
+#ifdef CRT_DIET_NO_MASKS
     const uint32_t m = 0x7f800000u;
     return __builtin_amdgcn_ballot_w64((asu(v.x) & m) != m) & __builtin_amdgcn_ballot_w64((asu(v.y) & m) != m) & __builtin_amdgcn_ballot_w64((asu(v.z) & m) != m);
+#else
+    const float inf = __builtin_inff();
+    return __builtin_amdgcn_fcmpf(__builtin_fabsf(v.x), inf, 4) & __builtin_amdgcn_fcmpf(__builtin_fabsf(v.y), inf, 4) & __builtin_amdgcn_fcmpf(__builtin_fabsf(v.z), inf, 4);   // 4 = ordered and less than
+#endif
 }
 __device__ __forceinline__ uint32_t rank_in(uint64_t m) { return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u)); }   // set bits below this lane
 
@@ -184,11 +193,18 @@ __global__ __launch_bounds__(64, CRT_POOL_MIN_WAVES) void render_pool_kernel(con
 
     // ---- the start of a stream's next scene.FindNearest, shared by both shading passes: normalise, reciprocal direction, light quad,
     // floor plane, root step; parks the new ray and queues the stream (READY, or END / BOUNCE when the ray never enters the tree)
-    auto new_ray = [&](bool act, uint32_t s, f3 v, bool norm, f3 O, uint32_t seed, uint32_t meta) {
+    // `primary` (a compile-time tag): the ray starts at the camera (the END pass), and the operands that depend on the origin alone come from the Scene's
+    // camera-relative block (layout.h: primRoot, primLight, primFloor, formed on the host) instead of being recomputed by every lane (-DCRT_DIET_NO_CAMREL: never)
+    auto new_ray = [&](auto primary, bool act, uint32_t s, f3 v, bool norm, f3 O, uint32_t seed, uint32_t meta) {
+#ifdef CRT_DIET_NO_CAMREL
+        constexpr bool PRIM = false;
+#else
+        constexpr bool PRIM = decltype(primary)::value;
+#endif
         f3 D = v, rD = v; Hit nh; nh.t = 1e34f; nh.u = 0; nh.v = 0; nh.objIdx = -1; nh.triIdx = -1;
         uint32_t ncur = kRefDone, pend = 0u;
         if (act) {
-            const float inv = rcp_exact(__builtin_sqrtf(dot3(v, v)));           // normalize(): v * (1 / sqrtf(dot(v, v)))
+            const float inv = rcp_exact(sqrt_exact(dot3(v, v)));                  // normalize(): v * (1 / sqrtf(dot(v, v)))
             D = norm ? v * inv : v;
             rD = rcp_exact3(D);
             cn.rays++;
@@ -200,7 +216,12 @@ __global__ __launch_bounds__(64, CRT_POOL_MIN_WAVES) void render_pool_kernel(con
                 for (int i = 0; i < 12; i++) lf.lightInvT[i] = lp[i];
                 lf.lightSize = lp[15]; lf.floorN[0] = lp[19]; lf.floorN[1] = lp[20]; lf.floorN[2] = lp[21]; lf.floorD = lp[22];
                 lf.lightAxis = asu(ax[0]); lf.floorAxisY = asu(ax[1]);
-                hit_light_floor(lf, O, D, nh);
+                lf.preOy = lf.preOx = lf.preOz = lf.preNum = 0.0f;
+                if constexpr (PRIM) {
+                    constexpr size_t pl = (offsetof(Scene, primLight) - offsetof(Scene, lightInvT)) / 4;   // primLight[3], primFloor: the same Scene block, further on
+                    lf.preOy = lp[pl]; lf.preOx = lp[pl + 1]; lf.preOz = lp[pl + 2]; lf.preNum = lp[pl + 3];
+                }
+                hit_light_floor<PRIM>(lf, O, D, nh);
             }
             if (sc.rootIsPair) {
                 // bvh.cpp:244-257 / tlas_bvh.cpp:96-110 at the root with an empty stack, from the child pair in the kernel arguments
@@ -208,7 +229,13 @@ __global__ __launch_bounds__(64, CRT_POOL_MIN_WAVES) void render_pool_kernel(con
                 const rec4 a0 = {rp[0], rp[1], rp[2], rp[3]}, a1 = {rp[4], rp[5], rp[6], rp[7]};
                 const rec4 b0 = {rp[8], rp[9], rp[10], rp[11]}, b1 = {rp[12], rp[13], rp[14], rp[15]};
                 float d1, d2;
-                if (__builtin_amdgcn_ballot_w64(!finite3(rD)) == 0ull) { d1 = box_fast(a0, a1, O, rD, nh.t); d2 = box_fast(b0, b1, O, rD, nh.t); }
+                const bool allFinite = (__builtin_amdgcn_ballot_w64(true) & ~finite3_mask(rD)) == 0ull;
+                if constexpr (PRIM) {
+                    // rp[16 ..]: primRoot, the four corners minus the camera position (behind rootPair in the Scene)
+                    const f3 ra0 = mk3(rp[16], rp[17], rp[18]), ra1 = mk3(rp[19], rp[20], rp[21]), rb0 = mk3(rp[22], rp[23], rp[24]), rb1 = mk3(rp[25], rp[26], rp[27]);
+                    if (allFinite) { d1 = box_fast_rel(ra0, ra1, rD, nh.t); d2 = box_fast_rel(rb0, rb1, rD, nh.t); }
+                    else { d1 = box_exact_rel(ra0, ra1, rD, nh.t); d2 = box_exact_rel(rb0, rb1, rD, nh.t); }
+                } else if (allFinite) { d1 = box_fast(a0, a1, O, rD, nh.t); d2 = box_fast(b0, b1, O, rD, nh.t); }
                 else { d1 = box_exact(a0, a1, O, rD, nh.t); d2 = box_exact(b0, b1, O, rD, nh.t); }
                 const bool sw = d1 > d2;
                 const float dn = sw ? d2 : d1, df = sw ? d1 : d2;
@@ -274,7 +301,7 @@ __global__ __launch_bounds__(64, CRT_POOL_MIN_WAVES) void render_pool_kernel(con
         uint32_t oa = idx * (inter ? 64u : 48u) + (inter ? 0u : sc.leafOff - 48u);             // NodePair | LeafTri (one multiply-add on selected operands: no divergent arms)
         if (KIND == 1 && (cur & kRef16TlasBit) != 0u)
             oa = (cur & kRef16Interior) ? sc.instOff + idx * 128u : sc.tlasPairOff + idx * 64u;   // TLAS leaf: Instance {invT rows, ids} | TLAS interior: its child pair
-        if (lane_in(m)) { q0 = ldg(geom, oa); q1 = ldg(geom, oa + 16u); q2 = ldg(geom, oa + 32u); q3 = ldg(geom, oa + 48u); }
+        if (lane_in(m)) { q0 = ldp<0>(geom, oa); q1 = ldp<1>(geom, oa); q2 = ldp<2>(geom, oa); q3 = ldp<3>(geom, oa); }
     };
 
     // ---------------- TRI step of the lanes in m: one triangle of the current leaf (infra/bvh.cpp:203-222, 232-243), on the pre-loaded LeafTri ----------------
@@ -428,7 +455,7 @@ __global__ __launch_bounds__(64, CRT_POOL_MIN_WAVES) void render_pool_kernel(con
                 if (KIND == 1 && (cur & kRef16TlasBit) != 0u)
                     oa = (cur & kRef16Interior) ? sc.instOff + idx * 128u : sc.tlasPairOff + idx * 64u;   // TLAS leaf: Instance {invT rows, ids} | TLAS interior: its child pair
                 if (!lane_in(mRes)) oa = 0u;
-                q0 = ldg(geom, oa); q1 = ldg(geom, oa + 16u); q2 = ldg(geom, oa + 32u); q3 = ldg(geom, oa + 48u);
+                q0 = ldp<0>(geom, oa); q1 = ldp<1>(geom, oa); q2 = ldp<2>(geom, oa); q3 = ldp<3>(geom, oa);
             }
         }
         asm volatile("" ::: "memory");
@@ -476,7 +503,7 @@ __global__ __launch_bounds__(64, CRT_POOL_MIN_WAVES) void render_pool_kernel(con
                 // larger than the caches, and the (long) latency of this one load is then covered by the arithmetic of ray generation and new_ray
                 uint32_t skyTexel = 0u;
                 if (miss) {
-                    const float phi = crt_atan2f(-D.z, D.x) + CRT_PI, theta = crt_acosf(-D.y);
+                    float phi, theta; sky_angles(D, phi, theta);
                     const kernarg_f sk = scene_floats(offsetof(Scene, skyOffset));   // skyOffset, skyW, skyH
                     skyTexel = sc.texels[tex_index(asu(sk[0]), (int)asu(sk[1]), (int)asu(sk[2]), phi * CRT_INV2PI, theta * CRT_INVPI)];
                 }
@@ -521,14 +548,21 @@ __global__ __launch_bounds__(64, CRT_POOL_MIN_WAVES) void render_pool_kernel(con
                     const float jy = rnd(seed);                                    // pinned: first draw is the y jitter
                     const float jx = rnd(seed);
                     const float u = ((float)x + jx) * cam[12], vv = ((float)y + jy) * cam[13];     // invW, invH follow the camera in the Scene block
-                    const f3 TL = mk3(cam[3], cam[4], cam[5]), TR = mk3(cam[6], cam[7], cam[8]), BL = mk3(cam[9], cam[10], cam[11]);
-                    const f3 P = TL + u * (TR - TL) + vv * (BL - TL);
+                    const f3 TL = mk3(cam[3], cam[4], cam[5]);
+#ifdef CRT_DIET_NO_CAMREL
+                    const f3 TR = mk3(cam[6], cam[7], cam[8]), BL = mk3(cam[9], cam[10], cam[11]);
+                    const f3 right = TR - TL, down = BL - TL;
+#else
+                    constexpr size_t pc = (offsetof(Scene, primRight) - offsetof(Scene, camPos)) / 4;   // primRight[3], primDown[3]: TR - TL and BL - TL, formed on the host
+                    const f3 right = mk3(cam[pc], cam[pc + 1], cam[pc + 2]), down = mk3(cam[pc + 3], cam[pc + 4], cam[pc + 5]);
+#endif
+                    const f3 P = TL + u * right + vv * down;
                     v = P - camPos;
                     cn.primary++;
                 }
                 CRT_DENS_MASK(12, gen);
                 CRT_PSTAMP(e1); CRT_PACC(2, p2b, e1);
-                new_ray(gen, s, v, true, camPos, seed, item);                      // depth 0, outside, not fresh
+                new_ray(std::true_type{}, gen, s, v, true, camPos, seed, item);                      // depth 0, outside, not fresh
                 CRT_PSTAMP(e2); CRT_PACC(3, e1, e2);
                 if (ended) {
                     // the finished path's radiance: sky colour / light (24,24,22) / 0 at the depth limit (renderer.cpp:54-55, 69; GetLightColor file_scene.cpp:164-167), times the
@@ -568,7 +602,7 @@ __global__ __launch_bounds__(64, CRT_POOL_MIN_WAVES) void render_pool_kernel(con
 #endif
                 CRT_DENS(14, 1); CRT_DENS(15, n); CRT_DENS_MASK(16, mesh);
                 rec4 s0 = {0, 0, 0, 0}, s1 = s0, s2 = s0, s3 = s0;                 // the hit triangle's ShadeTri
-                if (mesh) { const uint32_t so = sc.shadeOff + tri * 64u; s0 = ldg(geom, so); s1 = ldg(geom, so + 16u); s2 = ldg(geom, so + 32u); s3 = ldg(geom, so + 48u); cn.meshhits++; }
+                if (mesh) { const uint32_t so = sc.shadeOff + tri * 64u; s0 = ldp<0>(geom, so); s1 = ldp<1>(geom, so); s2 = ldp<2>(geom, so); s3 = ldp<3>(geom, so); cn.meshhits++; }
                 const bool inside = (meta & kMetaInside) != 0u;
                 const int depth = (int)((meta >> kMetaDepthShift) & 7u);
                 const uint32_t item = meta & kMetaItemMask;
@@ -603,7 +637,7 @@ __global__ __launch_bounds__(64, CRT_POOL_MIN_WAVES) void render_pool_kernel(con
                             N = normalize3(Nn);
                         } else {
                             const uint32_t io = sc.instOff + (uint32_t)(obj - 2) * 128u + 64u;   // Instance::T rows
-                            const rec4 r0 = ldg(geom, io), r1 = ldg(geom, io + 16), r2 = ldg(geom, io + 32);
+                            const rec4 r0 = ldp<0>(geom, io), r1 = ldp<1>(geom, io), r2 = ldp<2>(geom, io);
                             N = normalize3(mk3(r0.x * Nn.x + r0.y * Nn.y + r0.z * Nn.z + r0.w * 0.0f,
                                                r1.x * Nn.x + r1.y * Nn.y + r1.z * Nn.z + r1.w * 0.0f,
                                                r2.x * Nn.x + r2.y * Nn.y + r2.z * Nn.z + r2.w * 0.0f));
@@ -631,7 +665,7 @@ __global__ __launch_bounds__(64, CRT_POOL_MIN_WAVES) void render_pool_kernel(con
                         if (cost2 > 0) {
                             const float a = n1 - n2, b2 = n1 + n2, R0 = (a * a) / (b2 * b2), cc = 1 - cosi;
                             const float Fr = R0 + (1 - R0) * (cc * cc * cc * cc * cc);
-                            const f3 T = eta * D + ((eta * cosi - __builtin_sqrtf(__builtin_fabsf(cost2))) * N);
+                            const f3 T = eta * D + ((eta * cosi - sqrt_exact(__builtin_fabsf(cost2))) * N);
                             if (rnd(seed) > Fr) { v = T; newInside = !inside; }
                         }
                     } else {                                                       // diffuse, renderer.cpp:93-99; diffusereflection tmplmath.h:535-544
@@ -653,7 +687,7 @@ __global__ __launch_bounds__(64, CRT_POOL_MIN_WAVES) void render_pool_kernel(con
                     } else pre = c * medium;
                     CRT_PSTAMP(b2); CRT_PACC(6, b1, b2);
                     // normalize(R) of the diffuse branch; the bounce's throughput factor and the new origin use the normalised direction
-                    const float inv = rcp_exact(__builtin_sqrtf(dot3(v, v)));
+                    const float inv = rcp_exact(sqrt_exact(dot3(v, v)));
                     const f3 nv = norm ? v * inv : v;
                     v = nv;
                     const f3 factor = diffuse ? pre * dot3(nv, N) : pre;
@@ -665,7 +699,7 @@ __global__ __launch_bounds__(64, CRT_POOL_MIN_WAVES) void render_pool_kernel(con
                     CRT_PSTAMP(b3); CRT_PACC(7, b2, b3);
                 }
                 CRT_PSTAMP(b4);
-                new_ray(act, s, v, false, O, seed, item | ((uint32_t)(depth + 1) << kMetaDepthShift) | (newInside ? kMetaInside : 0u));
+                new_ray(std::false_type{}, act, s, v, false, O, seed, item | ((uint32_t)(depth + 1) << kMetaDepthShift) | (newInside ? kMetaInside : 0u));
 #ifdef CRT_POOL_STAMPS
                 { CRT_PSTAMP(b5); CRT_PACC(8, b4, b5); pst[11]++; }
 #endif
