@@ -604,6 +604,20 @@ class Context:
         self._ck(self.L.crt_get_timing(self.h, C.byref(t)))
         return dict(render_kernel_ms=t.render_kernel_ms, resolve_kernel_ms=t.resolve_kernel_ms, render_launches=t.render_launches, pool_launches=t.pool_launches, split_launches=t.split_launches)
 
+    def tile_classes(self):
+        """crt_debug_tile_classes: the pool kernel's tile classes as the device holds them, one byte per owned tile (TILE_NO_LIGHT | TILE_NO_FLOOR | TILE_NO_TREE)"""
+        self.L.crt_debug_tile_classes.restype = C.c_int
+        self.L.crt_debug_tile_classes.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+        n = self.L.crt_debug_tile_classes(self.h, None, 0)
+        if n < 0:
+            self._ck(n)
+        out = np.zeros(n, np.uint8)
+        if n:
+            rc = self.L.crt_debug_tile_classes(self.h, _p(out), n)
+            if rc < 0:
+                self._ck(rc)
+        return out
+
     def tile_clocks(self, tile_count):
         a = np.zeros((tile_count, 2), np.uint64)
         self._ck(self.L.crt_get_tile_clocks(self.h, _p(a)))
@@ -977,6 +991,27 @@ def tile_partition(rank, world, n_tiles):
     all-reduce of the accumulators reproduces the single-GPU image exactly."""
     count = (n_tiles - rank + world - 1) // world if rank < n_tiles else 0
     return rank, world, count
+
+
+TILE_NO_LIGHT, TILE_NO_FLOOR, TILE_NO_TREE = 1, 2, 4      # layout.h kTileNo*: tests no primary ray of a tile can pass
+TILE_SKY = 7
+
+
+def tile_classes_host(camera, light_offsets, light_size, floor_d, root_pair, width, height, tile_first=0, tile_stride=1, tile_count=-1, flags=7):
+    """crt_debug_tile_classes_host (no GPU): the tile classes of a bare Scene block.  camera = camPos, topLeft, topRight, bottomLeft (12 floats); light_offsets =
+    lightInvT[3], [7], [11]; root_pair = the root's NodePair (16 floats); flags: 1 lightAxis, 2 floorAxisY, 4 rootIsPair."""
+    if tile_count < 0:
+        tile_first, tile_stride, tile_count = 0, 1, (width // 16) * (height // 16)
+    v = np.concatenate([np.asarray(camera, np.float32).reshape(12), np.asarray(light_offsets, np.float32).reshape(3), np.array([light_size, floor_d], np.float32),
+                        np.asarray(root_pair, np.float32).reshape(16)]).astype(np.float32)
+    out = np.zeros(tile_count, np.uint8)
+    L = lib()
+    L.crt_debug_tile_classes_host.restype = C.c_int
+    L.crt_debug_tile_classes_host.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
+    rc = L.crt_debug_tile_classes_host(_p(v), flags, width, height, tile_first, tile_stride, tile_count, _p(out))
+    if rc != 0:
+        raise CrtError(rc, "crt_debug_tile_classes_host: invalid argument")
+    return out
 
 
 def reduce_accumulator(tensor, dist, dst=0):

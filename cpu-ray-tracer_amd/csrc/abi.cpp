@@ -3,6 +3,7 @@
 // There is NO CPU rendering path in this library: without a HIP device crt_create fails with CRT_ERR_NO_DEVICE.
 #include "../../include/crt_abi.h"
 #include "device/launch.h"
+#include "device/tile_class.h"
 #include "host/grid_resolution.h"
 
 #include <cmath>
@@ -91,6 +92,11 @@ struct crt_ctx {
     float meshLo[3] = {0, 0, 0}, meshHi[3] = {0, 0, 0}; bool orderDirty = true;
     uint32_t* dTileOrder = nullptr;
     uint32_t* hTileOrder[2] = {nullptr, nullptr}; hipEvent_t orderCopied[2] = {nullptr, nullptr}; hipEvent_t orderReady = nullptr; int orderFlip = 0;
+    // render_pool_kernel's tile classes (device/tile_class.h): one byte per owned tile, stale from every write of the Scene's camera-relative block (primary_changed)
+    // until the next crt_render classifies again (update_tile_class); a launch never sees a stale table (launch_render_kernels passes none)
+    bool classDirty = true;
+    uint8_t* dTileClass = nullptr;
+    uint8_t* hTileClass[2] = {nullptr, nullptr}; hipEvent_t classCopied[2] = {nullptr, nullptr}; int classFlip = 0;
     bool haveScene = false;
     // what crt_update_scene needs of the last upload: a host mirror of the geometry buffer and where each BVH's records start
     struct Flat { int32_t kind = 0; uint64_t leafOff = 0, tlasOff = 0, tlasPairOff = 0, instOff = 0, shadeOff = 0; uint32_t tlasNodeCount = 0, maxHeight = 0;
@@ -304,6 +310,10 @@ int crt_abi_version(void) { return CRT_ABI_VERSION; }
 
 void crt_debug_enable_hooks(int on) { g_hooks = on != 0; }
 
+// Every write of a context's camera-relative block goes through here: what a tile's primary rays can hit depends on exactly the values set_primary reads (camera,
+// light / floor block, root pair), so the tile classes are stale from the same moment.
+static void primary_changed(crt_ctx* c) { crt::set_primary(c->hScene); c->classDirty = true; }
+
 int crt_device_count(void)
 {
     int n = 0;
@@ -381,7 +391,7 @@ int crt_create(crt_ctx** out, const crt_config* cfg)
     s.bottomLeft[0] = -aspect; s.bottomLeft[1] = -1; s.bottomLeft[2] = 0;
     s.W = cfg->width; s.H = cfg->height; s.invW = 1.0f / cfg->width; s.invH = 1.0f / cfg->height;
     s.depthLimit = c->cfg.depthLimit;
-    crt::set_primary(s);
+    primary_changed(c);
     if ((e = hipStreamSynchronize(c->stream)) != hipSuccess) return bail(e, "hipStreamSynchronize");
     *out = c;
     return CRT_OK;
@@ -422,6 +432,7 @@ void crt_destroy(crt_ctx* c)
     if (c->dInspectWork) (void)hipFree(c->dInspectWork);
     if (c->dTileClocks) (void)hipFree(c->dTileClocks);
     if (c->dTileOrder) (void)hipFree(c->dTileOrder);
+    if (c->dTileClass) (void)hipFree(c->dTileClass);
     if (c->dTileCost) (void)hipFree(c->dTileCost);
     if (c->dJobCost) (void)hipFree(c->dJobCost);
     if (c->dJobDesc) (void)hipFree(c->dJobDesc);
@@ -437,6 +448,7 @@ void crt_destroy(crt_ctx* c)
     if (c->descReady) (void)hipEventDestroy(c->descReady);
     if (c->dStage) (void)hipFree(c->dStage);
     for (int k = 0; k < 2; k++) { if (c->hTileOrder[k]) (void)hipHostFree(c->hTileOrder[k]); if (c->orderCopied[k]) (void)hipEventDestroy(c->orderCopied[k]); }
+    for (int k = 0; k < 2; k++) { if (c->hTileClass[k]) (void)hipHostFree(c->hTileClass[k]); if (c->classCopied[k]) (void)hipEventDestroy(c->classCopied[k]); }
     for (int k = 0; k < 2; k++) { if (c->hStage[k]) (void)hipHostFree(c->hStage[k]); if (c->stageCopied[k]) (void)hipEventDestroy(c->stageCopied[k]); }
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
@@ -686,7 +698,7 @@ int crt_upload_scene(crt_ctx* c, const crt_scene_desc* sd)
         s.rootIsPair = 1;
     }
     if (hook("CRT_DEBUG_NO_ROOTPAIR")) s.rootIsPair = 0;                            // tests: every ray starts at the root reference instead
-    crt::set_primary(s);                                                            // new light / floor block and rootPair: the camera-relative block follows
+    primary_changed(c);                                                             // new light / floor block and rootPair: the camera-relative block follows
     s.stackDepth = s.bvhStack + ((sd->kind == CRT_SCENE_TLAS) ? tlasHeight + 1 : 0);   // + TLAS pushes + the return marker
     c->ldsBytes = s.stackDepth * 64u * 4u; c->latSlots = 0;
     if (const char* e = hook("CRT_DEBUG_EXTRA_LDS")) c->ldsBytes += (uint32_t)atoi(e);   // occupancy experiments only
@@ -832,7 +844,7 @@ static void set_root(crt_ctx* c, int kind, const float* lo, const float* hi)
         s.rootIsPair = 1;
     }
     if (hook("CRT_DEBUG_NO_ROOTPAIR")) s.rootIsPair = 0;
-    crt::set_primary(s);
+    primary_changed(c);
     memcpy(c->meshLo, lo, 12); memcpy(c->meshHi, hi, 12); c->orderDirty = true;
 }
 
@@ -959,7 +971,7 @@ int crt_set_camera(crt_ctx* c, const float camPos[3], const float tl[3], const f
     crt::Scene& s = c->hScene;
     if (!memcmp(s.camPos, camPos, 12) && !memcmp(s.topLeft, tl, 12) && !memcmp(s.topRight, tr, 12) && !memcmp(s.bottomLeft, bl, 12)) return CRT_OK;   // unchanged (a per-frame PushCamera)
     memcpy(s.camPos, camPos, 12); memcpy(s.topLeft, tl, 12); memcpy(s.topRight, tr, 12); memcpy(s.bottomLeft, bl, 12);
-    crt::set_primary(s);
+    primary_changed(c);
     c->orderDirty = true; c->epoch++;
     return CRT_OK;      // the Scene block travels by value in every launch's kernel arguments
 }
@@ -1031,6 +1043,27 @@ static int update_tile_order(crt_ctx* c)
     c->jobCostValid = false; c->jobCostPending = false; c->planValid = false;
     { const int r = upload_tile_order(c, first); if (r) return r; }
     c->orderDirty = false;
+    return 0;
+}
+
+// The tile classes of the Scene block as it stands (device/tile_class.h), to the device under the tile order's protocol (upload_tile_order): the copy runs on the
+// main stream behind every render launch submitted so far, so a launch in flight keeps reading the table it was launched with; later launches wait for
+// `orderReady`, which names the newest of the two tables' copies (one stream: behind it, both have landed).
+static int update_tile_class(crt_ctx* c)
+{
+    if (!c->classDirty || c->tileCount == 0) return 0;
+    if (!c->dTileClass) HIPCK(c, hipMalloc((void**)&c->dTileClass, (size_t)c->tileCount));
+    { const int r = order_behind_ahead(c); if (r) return r; }
+    const int k = c->classFlip ^= 1;
+    if (!c->hTileClass[k]) {
+        HIPCK(c, hipHostMalloc((void**)&c->hTileClass[k], (size_t)c->tileCount, hipHostMallocDefault));
+        HIPCK(c, ensure_event(&c->classCopied[k]));
+    } else HIPCK(c, hipEventSynchronize(c->classCopied[k]));
+    crt::classify_tiles(c->hScene, c->cfg.width, c->cfg.height, (uint32_t)c->tilesX, c->tileFirst, c->tileStride, c->tileCount, c->hTileClass[k]);
+    HIPCK(c, hipMemcpyAsync(c->dTileClass, c->hTileClass[k], (size_t)c->tileCount, hipMemcpyHostToDevice, c->stream));
+    HIPCK(c, hipEventRecord(c->classCopied[k], c->stream));
+    c->orderReady = c->classCopied[k];
+    c->classDirty = false;
     return 0;
 }
 
@@ -1686,7 +1719,8 @@ static hipError_t launch_render_kernels(crt_ctx* c, const Launch& L)
         if (le == hipSuccess)
             le = crt_launch_render_pool(&c->hScene, L.slab, scratch, c->dCounters, c->dTileClocks, c->dTileOrder, c->tileFirst, c->tileStride, c->tileCount, (uint32_t)c->tilesX,
                                         L.sppFirst, L.nf, L.passes, c->cfg.collectStats, L.jobBlocks ? L.head : 0u, L.waveFrames, L.waveTab, L.waveBlocks, L.longFrames,
-                                        L.wantJobCost ? c->dJobCost : nullptr, L.jobClk, st2);
+                                        L.wantJobCost ? c->dJobCost : nullptr, L.jobClk,
+                                        (c->classDirty || hook("CRT_DEBUG_NO_TILE_CLASS")) ? nullptr : c->dTileClass /* tests / A-B: the kernel without the table */, st2);
         if (le == hipSuccess) c->lastLongWaves = L.longWaves;
         if (L.jobBlocks && le == hipSuccess) le = join(st2);
     } else if (L.jobBlocks) {
@@ -1815,6 +1849,7 @@ int crt_render(crt_ctx* c, uint32_t spp_first, uint32_t frames, uint32_t passes)
     { int r = discard_ahead(c); if (r) return r; }                 // (a held region must never be handed out again: see take_region)
     if (c->tileCount == 0 || frames == 0) return CRT_OK;
     { int r = update_tile_order(c); if (r) return r; }
+    { int r = update_tile_class(c); if (r) return r; }
     if (c->streams.empty()) {
         int n = c->cfg.renderStreams;
         if (n <= 0) n = 7;
@@ -3061,6 +3096,39 @@ extern "C" int crt_debug_primary_block_host(int op, const float* in, float* out)
     else memcpy(s.rootPair, in, 64);
     crt::set_primary(s);
     memcpy(out, s.rootPair, 64 + 4 * crt::kPrimFloats);
+    return CRT_OK;
+}
+
+// tests / tools: the context's tile classes as the device holds them, out[min(cap, tiles owned)] (classified first if the Scene block changed since the last
+// crt_render).  Returns the number of owned tiles, or a negative error code.
+extern "C" int crt_debug_tile_classes(crt_ctx* c, uint8_t* out, uint32_t cap)
+{
+    if (!c || (!out && cap)) return CRT_ERR_INVALID;
+    HIPCK(c, hipSetDevice(c->cfg.device));
+    { const int r = update_tile_class(c); if (r) return r; }
+    const uint32_t n = cap < c->tileCount ? cap : c->tileCount;
+    if (n) {
+        HIPCK(c, hipMemcpyAsync(out, c->dTileClass, n, hipMemcpyDeviceToHost, c->stream));
+        HIPCK(c, hipStreamSynchronize(c->stream));
+    }
+    return (int)c->tileCount;
+}
+// tests (no GPU needed): classify_tiles on a bare Scene block filled the way a session fills it.  in[33] = camPos, topLeft, topRight, bottomLeft; lightInvT[3], [7],
+// [11]; lightSize; floorD; rootPair[16].  flags: 1 = lightAxis, 2 = floorAxisY, 4 = rootIsPair.  out[tileCount], the tiles tileFirst + i * tileStride of a W x H image.
+extern "C" int crt_debug_tile_classes_host(const float* in, uint32_t flags, int W, int H, uint32_t tileFirst, uint32_t tileStride, uint32_t tileCount, uint8_t* out)
+{
+    if (!in || !out || W < 16 || H < 16 || tileStride == 0) return CRT_ERR_INVALID;
+    const uint32_t tilesX = (uint32_t)(W / 16), tiles = tilesX * (uint32_t)(H / 16);
+    if (tileCount && (unsigned long long)tileFirst + (unsigned long long)(tileCount - 1) * tileStride >= tiles) return CRT_ERR_INVALID;
+    crt::Scene s{};
+    memcpy(s.camPos, in, 12); memcpy(s.topLeft, in + 3, 12); memcpy(s.topRight, in + 6, 12); memcpy(s.bottomLeft, in + 9, 12);
+    s.W = W; s.H = H; s.invW = 1.0f / W; s.invH = 1.0f / H;
+    s.lightInvT[0] = s.lightInvT[5] = s.lightInvT[10] = 1.0f; s.lightInvT[3] = in[12]; s.lightInvT[7] = in[13]; s.lightInvT[11] = in[14];
+    s.lightSize = in[15]; s.floorN[1] = 1.0f; s.floorD = in[16];
+    memcpy(s.rootPair, in + 17, 64);
+    s.lightAxis = flags & 1u; s.floorAxisY = (flags >> 1) & 1u; s.rootIsPair = (flags >> 2) & 1u;
+    crt::set_primary(s);
+    crt::classify_tiles(s, W, H, tilesX, tileFirst, tileStride, tileCount, out);
     return CRT_OK;
 }
 

@@ -311,14 +311,15 @@ __device__ __forceinline__ void hit_tri(rec4 a, rec4 b, rec4 c, f3 O, f3 D, Hit&
 // (PRE: the ray starts at the camera and `pre` holds the sums of the short expressions that involve only O — Scene::primLight / primFloor, formed on the host; the general
 // expressions are evaluated as always)
 struct LightFloor { float lightInvT[12]; float lightSize; uint32_t lightAxis, floorAxisY; float floorN[3]; float floorD; float preOy, preOx, preOz, preNum; };
+// (skipLight / skipFloor: wave-uniform; the caller has a proof that no ray of the wavefront passes that half's test — render_pool_kernel's tile class, tile_class.h)
 template <bool PRE = false>
-__device__ __forceinline__ void hit_light_floor(const LightFloor& sc, f3 O, f3 D, Hit& h)
+__device__ __forceinline__ void hit_light_floor(const LightFloor& sc, f3 O, f3 D, Hit& h, bool skipLight = false, bool skipFloor = false)
 {
     // Scene::lightAxis / floorAxisY (set at upload): the quad's invT has an identity rotation block / the plane's normal is exactly
     // (0,1,0) — what FileScene and TLASFileScene always build (file_scene.cpp:15-19).  Then 1*x == x and the 0*x terms only add
     // zeros, so the general expressions reduce to the short ones below; the two can differ in the SIGN OF A ZERO only, which no
     // comparison here can see and which never reaches an accepted t (accepted hits have a non-zero numerator and denominator).
-    {
+    if (!skipLight) {
         const float* c = sc.lightInvT;
         float Oy, Dy;
         if (sc.lightAxis) { Oy = PRE ? sc.preOy : O.y + c[7]; Dy = D.y; }
@@ -338,7 +339,7 @@ __device__ __forceinline__ void hit_light_floor(const LightFloor& sc, f3 O, f3 D
             if (Ix > -size && Ix < size && Iz > -size && Iz < size) { h.t = t; h.objIdx = 0; }
         }
     }
-    {
+    if (!skipFloor) {
         float num, den;
         if (sc.floorAxisY) { num = PRE ? sc.preNum : O.y + sc.floorD; den = D.y; }
         else { const f3 N = mk3(sc.floorN[0], sc.floorN[1], sc.floorN[2]); num = dot3(O, N) + sc.floorD; den = dot3(D, N); }

@@ -35,7 +35,8 @@ uint32_t crt_pool_streams(uint32_t frames);
 size_t crt_pool_scratch_bytes_per_window(uint32_t tileCount);
 hipError_t crt_launch_render_pool(const crt::Scene* sc, void* slab, void* facScratch, crt::Counters* counters, unsigned long long* tileClocks, const uint32_t* tileOrder, uint32_t tileFirst,
     uint32_t tileStride, uint32_t tileCount, uint32_t tilesX, uint32_t sppFirst, uint32_t frames, uint32_t passes, int collectStats, uint32_t rankFirst, uint32_t waveFrames,
-    const uint32_t* waveTab, uint32_t tabBlocks, uint32_t longFrames, uint32_t* tileCost, unsigned long long* launchClk, hipStream_t stream);
+    const uint32_t* waveTab, uint32_t tabBlocks, uint32_t longFrames, uint32_t* tileCost, unsigned long long* launchClk,
+    const uint8_t* tileClass /* one byte per local tile (layout.h kTileNo*), or nullptr: every test runs */, hipStream_t stream);
 uint32_t crt_pool_lds_bytes(uint32_t stackDepth, uint32_t streams);
 int crt_debug_pool_stamps(unsigned long long* out, int reset);
 int crt_debug_pool_density(unsigned long long* out, int reset);

@@ -126,6 +126,11 @@ inline void set_primary(Scene& s)
     for (int k = 0; k < 3; k++) { s.primRight[k] = s.topRight[k] - s.topLeft[k]; s.primDown[k] = s.bottomLeft[k] - s.topLeft[k]; }
 }
 
+// render_pool_kernel's tile class, one byte per local tile (tile_class.h classify_tiles, on the host): tests that NO primary ray of the tile can pass.  A set bit
+// is a proof; 0 is always correct.
+constexpr uint32_t kTileNoLight = 1u, kTileNoFloor = 2u, kTileNoTree = 4u;    // the light quad's test, the floor plane's, the slab tests of the root's two children
+constexpr uint32_t kTileSky = kTileNoLight | kTileNoFloor | kTileNoTree;      // all three: every path of the tile ends at depth 0 in the sky lookup
+
 struct Counters { unsigned long long v[8]; };   // order = crt_counters
 
 // crt_refit_device's bottom-up plan of one BVH (refit.hip): one record per node pair, sorted by depth, deepest level first.  A child code is kPlanInterior | the

@@ -113,7 +113,7 @@ __global__ __launch_bounds__(64, CRT_POOL_MIN_WAVES) void render_pool_kernel(con
                                                              unsigned long long* __restrict__ tileClocks, const uint32_t* __restrict__ tileOrder,
                                                              uint32_t tileFirst, uint32_t tileStride, uint32_t tileCount, uint32_t tilesX,
                                                              uint32_t sppFirst, uint32_t frames, uint32_t passes, uint32_t groups, uint32_t waveFrames, const uint32_t* __restrict__ waveTab, uint32_t tabBlocks, uint32_t longFrames,
-                                                             uint32_t rankFirst, uint32_t* __restrict__ tileCost, unsigned long long* __restrict__ launchClk)
+                                                             uint32_t rankFirst, uint32_t* __restrict__ tileCost, unsigned long long* __restrict__ launchClk, const uint8_t* __restrict__ tileClass)
 {
     extern __shared__ uint32_t lds[];
     const uint32_t lane = threadIdx.x;
@@ -145,6 +145,14 @@ __global__ __launch_bounds__(64, CRT_POOL_MIN_WAVES) void render_pool_kernel(con
     const uint32_t nStreams = nOwn < (uint32_t)S ? nOwn : (uint32_t)S;           // ... of which this many start now, one per slot
     const uint32_t tile = tileFirst + tl * tileStride;
     const uint32_t tx = tile % tilesX, ty = tile / tilesX;
+    // what the tile's primary rays cannot hit (layout.h kTileNo*, proven on the host: tile_class.h), one scalar for the wavefront's life; 0 = every test runs.
+    // Only new_ray's primary form and the END pass look at it, and only to skip, under a scalar branch, a test whose outcome is known (-DCRT_NO_TILE_CLASS: never)
+#ifdef CRT_NO_TILE_CLASS
+    constexpr uint32_t tcls = 0u;
+#else
+    const uint32_t tcls = tileClass ? __builtin_amdgcn_readfirstlane((uint32_t)tileClass[tl]) : 0u;
+#endif
+    const bool skyTile = tcls == kTileSky;
     const char* __restrict__ geom = sc.geom;
     float* __restrict__ fac = facScratch + (size_t)blockIdx.x * (15u * (uint32_t)S);
 
@@ -201,14 +209,20 @@ __global__ __launch_bounds__(64, CRT_POOL_MIN_WAVES) void render_pool_kernel(con
 #else
         constexpr bool PRIM = decltype(primary)::value;
 #endif
+        // the tile class applies to rays from the camera only (also under -DCRT_DIET_NO_CAMREL, which only recomputes their operands)
+        constexpr bool FROM_CAM = decltype(primary)::value;
+        // a sky tile (all three bits): the ray misses light, floor and tree, so FindNearest is over before it starts and the stream goes straight back to the END queue.
+        // Parked is only what that pass reads of a missed path: the direction (sky lookup), the RNG state, meta with depth 0 and object field 0 (= miss).
+        const bool sky = FROM_CAM && skyTile;
+        const bool noLight = FROM_CAM && (tcls & kTileNoLight) != 0u, noFloor = FROM_CAM && (tcls & kTileNoFloor) != 0u, noTree = FROM_CAM && (tcls & kTileNoTree) != 0u;
         f3 D = v, rD = v; Hit nh; nh.t = 1e34f; nh.u = 0; nh.v = 0; nh.objIdx = -1; nh.triIdx = -1;
         uint32_t ncur = kRefDone, pend = 0u;
         if (act) {
             const float inv = rcp_exact(sqrt_exact(dot3(v, v)));                  // normalize(): v * (1 / sqrtf(dot(v, v)))
             D = norm ? v * inv : v;
-            rD = rcp_exact3(D);
             cn.rays++;
-            {
+            if (!sky) {
+                rD = rcp_exact3(D);
                 const kernarg_f lp = scene_floats(offsetof(Scene, lightInvT));      // lightInvT[12] lightNrm[3] lightSize lightPos[3] floorN[3] floorD: one block of the Scene
                 const kernarg_f ax = scene_floats(offsetof(Scene, lightAxis));      // lightAxis, floorAxisY
                 LightFloor lf;
@@ -221,9 +235,12 @@ __global__ __launch_bounds__(64, CRT_POOL_MIN_WAVES) void render_pool_kernel(con
                     constexpr size_t pl = (offsetof(Scene, primLight) - offsetof(Scene, lightInvT)) / 4;   // primLight[3], primFloor: the same Scene block, further on
                     lf.preOy = lp[pl]; lf.preOx = lp[pl + 1]; lf.preOz = lp[pl + 2]; lf.preNum = lp[pl + 3];
                 }
-                hit_light_floor<PRIM>(lf, O, D, nh);
+                hit_light_floor<PRIM>(lf, O, D, nh, noLight, noFloor);
             }
-            if (sc.rootIsPair) {
+            if (noTree) {
+                // both slab tests are known to fail: ncur = done, nothing pending; the reference's root step is still counted
+                if (COUNT) { if (KIND == 0) cn.interior++; else cn.tlas++; }
+            } else if (sc.rootIsPair) {
                 // bvh.cpp:244-257 / tlas_bvh.cpp:96-110 at the root with an empty stack, from the child pair in the kernel arguments
                 const kernarg_f rp = scene_floats(offsetof(Scene, rootPair));
                 const rec4 a0 = {rp[0], rp[1], rp[2], rp[3]}, a1 = {rp[4], rp[5], rp[6], rp[7]};
@@ -246,25 +263,33 @@ __global__ __launch_bounds__(64, CRT_POOL_MIN_WAVES) void render_pool_kernel(con
                 if (COUNT) { if (KIND == 0) cn.interior++; else cn.tlas++; }
             } else ncur = sc.rootRef16;
             if (COUNT && KIND == 0 && (ncur & kRef16TagMask) == 0u && ncur != kRefDone) cn.leaf++;
-            stf[F_OX * S + s] = O.x; stf[F_OY * S + s] = O.y; stf[F_OZ * S + s] = O.z;
+            if (!sky) {
+                stf[F_OX * S + s] = O.x; stf[F_OY * S + s] = O.y; stf[F_OZ * S + s] = O.z;
+                stf[F_RX * S + s] = rD.x; stf[F_RY * S + s] = rD.y; stf[F_RZ * S + s] = rD.z;
+                stf[F_T * S + s] = nh.t;
+                st[F_CUR * S + s] = ncur; st[F_PEND * S + s] = pend;
+            }
             stf[F_DX * S + s] = D.x; stf[F_DY * S + s] = D.y; stf[F_DZ * S + s] = D.z;
-            stf[F_RX * S + s] = rD.x; stf[F_RY * S + s] = rD.y; stf[F_RZ * S + s] = rD.z;
-            stf[F_T * S + s] = nh.t;
             st[F_SEED * S + s] = seed; st[F_META * S + s] = meta | ((uint32_t)(nh.objIdx + 1) << kMetaObjShift);
-            st[F_CUR * S + s] = ncur; st[F_PEND * S + s] = pend;
         }
-        // queue: the walk is needed only when the ray enters the tree; otherwise FindNearest is already over (renderer.cpp:52-55, 69).  Every set is the ballot of ONE
-        // comparison combined with scalar logic.
-        const uint32_t depth = (meta >> kMetaDepthShift) & 7u;
         const uint64_t mAct = __builtin_amdgcn_ballot_w64(act);
-        const uint64_t mW = mAct & __builtin_amdgcn_ballot_w64(ncur != kRefDone);
-        const uint64_t mStop = __builtin_amdgcn_ballot_w64((uint32_t)(nh.objIdx + 1) <= 1u) | __builtin_amdgcn_ballot_w64((int)depth >= sc.depthLimit);   // miss, light, or depth limit
-        const uint64_t mE = mAct & ~mW & mStop, mB = mAct & ~mW & ~mStop;
+        // queue: the walk is needed only when the ray enters the tree; otherwise FindNearest is already over (renderer.cpp:52-55, 69).  Every set is the ballot of ONE
+        // comparison combined with scalar logic.  (A sky tile: every new ray is a finished path — one set, no further ballots.)
+        uint64_t mW = 0ull, mE = mAct, mB = 0ull;
+        if (!sky) {
+            const uint32_t depth = (meta >> kMetaDepthShift) & 7u;
+            mW = mAct & __builtin_amdgcn_ballot_w64(ncur != kRefDone);
+            const uint64_t mStop = __builtin_amdgcn_ballot_w64((uint32_t)(nh.objIdx + 1) <= 1u) | __builtin_amdgcn_ballot_w64((int)depth >= sc.depthLimit);   // miss, light, or depth limit
+            mE = mAct & ~mW & mStop; mB = mAct & ~mW & ~mStop;
+        }
         CRT_DENS(20, __popcll(mAct)); CRT_DENS(19, __popcll(mW));
-        if (lane_in(mW)) qRdy[(rdyT + rank_in(mW)) & kQueueMask] = (uint8_t)s;
+        if (!sky) {
+            if (lane_in(mW)) qRdy[(rdyT + rank_in(mW)) & kQueueMask] = (uint8_t)s;
+            if (lane_in(mB)) qBnc[(bncT + rank_in(mB)) & kQueueMask] = (uint8_t)s;
+            rdyT += (uint32_t)__popcll(mW); bncT += (uint32_t)__popcll(mB);
+        }
         if (lane_in(mE)) qEnd[(endT + rank_in(mE)) & kQueueMask] = (uint8_t)s;
-        if (lane_in(mB)) qBnc[(bncT + rank_in(mB)) & kQueueMask] = (uint8_t)s;
-        rdyT += (uint32_t)__popcll(mW); endT += (uint32_t)__popcll(mE); bncT += (uint32_t)__popcll(mB);
+        endT += (uint32_t)__popcll(mE);
     };
     // back to the world-space ray when a BLAS is finished (two-level scenes): the parked copy is the world-space ray
     auto world_ray = [&]() {
@@ -490,11 +515,12 @@ __global__ __launch_bounds__(64, CRT_POOL_MIN_WAVES) void render_pool_kernel(con
                 if (ended && obj >= 2) cn.meshhits++;
                 // the path's throughput factors: fetched now (device-scope loads: they were written by this wave's BOUNCE passes, possibly from
                 // another lane), needed after the sky lookup; most paths end at depth 0..2 and a level is fetched only by the lanes that deep
+                // (a sky tile's paths all end at depth 0: no factor was ever written, the fetch and the unwind below are skipped as a whole)
                 float fk[15];
 #pragma unroll
                 for (int k = 0; k < 5; k++) {
                     fk[3 * k] = fk[3 * k + 1] = fk[3 * k + 2] = 0.0f;
-                    if (ended && depth > k) {
+                    if (!skyTile) if (ended && depth > k) {
 #pragma unroll
                         for (int j = 0; j < 3; j++) fk[3 * k + j] = __hip_atomic_load(fac + (3 * k + j) * S + s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                     }
@@ -568,9 +594,11 @@ __global__ __launch_bounds__(64, CRT_POOL_MIN_WAVES) void render_pool_kernel(con
                     // the finished path's radiance: sky colour / light (24,24,22) / 0 at the depth limit (renderer.cpp:54-55, 69; GetLightColor file_scene.cpp:164-167), times the
                     // throughput factors in recursion order (innermost first: albedo*medium*Sample(...) multiplies on return)
                     f3 L = miss ? tex_unpack(skyTexel) : ((depth >= sc.depthLimit) ? mk3(0, 0, 0) : mk3(24, 24, 22));
+                    if (!skyTile) {
 #pragma unroll
-                    for (int k = 4; k >= 0; k--)
-                        if (depth > k) L = mk3(fk[3 * k], fk[3 * k + 1], fk[3 * k + 2]) * L;
+                        for (int k = 4; k >= 0; k--)
+                            if (depth > k) L = mk3(fk[3 * k], fk[3 * k + 1], fk[3 * k + 2]) * L;
+                    }
                     slab[sampleAt] = make_float4(L.x, L.y, L.z, 0.0f);
                 }
                 // every load of this pass is named as consumed here, at its end, on every path: the registers they wrote are re-used by the next sections, and a load
@@ -784,7 +812,7 @@ extern "C" size_t crt_debug_pool_timeline(unsigned long long* out, size_t cap)  
 extern "C" hipError_t crt_launch_render_pool(const crt::Scene* sc, void* slab, void* facScratch, crt::Counters* counters, unsigned long long* tileClocks, const uint32_t* tileOrder,
                                              uint32_t tileFirst, uint32_t tileStride, uint32_t tileCount, uint32_t tilesX, uint32_t sppFirst,
                                              uint32_t frames, uint32_t passes, int collectStats, uint32_t rankFirst, uint32_t waveFrames, const uint32_t* waveTab, uint32_t tabBlocks, uint32_t longFrames,
-                                             uint32_t* tileCost, unsigned long long* launchClk, hipStream_t stream)
+                                             uint32_t* tileCost, unsigned long long* launchClk, const uint8_t* tileClass, hipStream_t stream)
 {
     if (tileCount == 0 || frames == 0) return hipSuccess;
     if (!sc->ref16ok) return hipErrorInvalidValue;                              // the host launches render_tiles_kernel for such scenes
@@ -805,7 +833,7 @@ extern "C" hipError_t crt_launch_render_pool(const crt::Scene* sc, void* slab, v
       (void)hipMemsetAsync(buf, 0, (size_t)grid.x * 24, stream); g_timelineHost = buf; g_timelineCount = grid.x; }
 #endif
     const uint32_t ldsBytes = crt_pool_lds_bytes(sc->stackDepth, S);
-#define CRT_LAUNCH(K, C, SS) hipLaunchKernelGGL((crt::render_pool_kernel<K, C, SS>), grid, block, ldsBytes, stream, *sc, (float4*)slab, (float*)facScratch, counters, tileClocks, tileOrder, tileFirst, tileStride, tileCount, tilesX, sppFirst, frames, passes, groups, wf, waveTab, tabBlocks, longFrames, rankFirst, tileCost, launchClk)
+#define CRT_LAUNCH(K, C, SS) hipLaunchKernelGGL((crt::render_pool_kernel<K, C, SS>), grid, block, ldsBytes, stream, *sc, (float4*)slab, (float*)facScratch, counters, tileClocks, tileOrder, tileFirst, tileStride, tileCount, tilesX, sppFirst, frames, passes, groups, wf, waveTab, tabBlocks, longFrames, rankFirst, tileCost, launchClk, tileClass)
 #define CRT_LAUNCH_S(K, C) do { if (S == 64u) CRT_LAUNCH(K, C, 64); else CRT_LAUNCH(K, C, CRT_POOL_STREAMS); } while (0)
     if (sc->kind == 0) { if (collectStats) CRT_LAUNCH_S(0, true); else CRT_LAUNCH_S(0, false); }
     else { if (collectStats) CRT_LAUNCH_S(1, true); else CRT_LAUNCH_S(1, false); }
