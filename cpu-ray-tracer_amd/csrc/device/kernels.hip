@@ -23,8 +23,13 @@
 // Numerics: compiled with -ffp-contract=off; only IEEE + - * / sqrt, so results are bit-identical with a scalar
 // CPU evaluation of the same expressions.  min/max follow the reference's std::min/std::max operand order.
 // No MFMA: the path is pointer chasing + slab / Möller–Trumbore tests.
+// render_tiles_kernel's Sample body — the surface of a hit, medium, the bounce and its factor, the primary ray, the return path, the light / floor operands, the
+// ordered two-child step — and whitted_kernel's surface are sample_body.h's: the functions render_pool_kernel and the sequential kernels shade with, not a copy.
+// One repeat stays written out in render_tiles_kernel: its second NODE step.  The two steps as one local lambda called twice took its latency mode (one render
+// of 64 frames) from 20.09 to 20.74 ms, past the parent's 20.29 + 0.07 (profiles/sample_body.json, tiles_kernel_pieces).
 #include "alt_common.h"
 #include "launch.h"
+#include "sample_body.h"
 
 namespace crt {
 
@@ -147,6 +152,24 @@ __global__ __launch_bounds__(64, CRT_MIN_WAVES) void render_tiles_kernel(const S
     // triangle arithmetic runs), a push always stores to slot sp (a dead store when the far child was missed) and
     // only the pointer moves under a select.
 #define CRT_TOP() (stk[(sp ? sp - 1u : 0u) * 64u])
+    // where the 64-byte record a lane fetches next lies in geom, as two 32-byte halves: the hit's ShadeTri (`shade`: the walk is over) | NodePair / LeafTri of `cur` |
+    // TLAS leaf: Instance {invT rows, ids} | TLAS interior: its two child nodes
+    auto record_offsets = [&](bool shade, uint32_t& oa, uint32_t& ob) {
+        oa = shade ? sc.shadeOff + (uint32_t)h.triIdx * 64u : (cur & kRefOffsetMask) << 4; ob = oa + 32u;
+        if (KIND == 1 && !shade && (cur & kRefTlasBit) != 0u) {
+            if (cur & kRefInterior) { oa = sc.instOff + (cur & 0xffffu) * 128u; ob = oa + 32u; }
+            else { oa = sc.tlasOff + (cur & 0x7fffu) * 32u; ob = sc.tlasOff + ((cur >> 15) & 0x7fffu) * 32u; }
+        }
+    };
+    // two-level scenes: a popped return marker — the BLAS is finished: back to the world-space ray, pop the TLAS entry below
+    auto leave_blas = [&](uint32_t next) -> uint32_t {
+        if (KIND == 1 && next == kRefReturn) {
+            tO = O; tD = D; trD = rD; rayFinite = finite3(rD);
+            const bool pop = sp != 0u; const uint32_t top = CRT_TOP();
+            next = pop ? top : kRefDone; sp -= pop ? 1u : 0u;
+        }
+        return next;
+    };
 
     for (;;) {
         // state ballots: the compares write their lane masks straight into scalar registers; `liveMask` (maintained below) removes
@@ -210,91 +233,33 @@ __global__ __launch_bounds__(64, CRT_MIN_WAVES) void render_tiles_kernel(const S
             }
             if (surf) {
                 I = O + h.t * D;
-                if (h.objIdx == 1) {                                              // floor: Plane::GetNormal / GetUV (primitives.h:112-133)
+                SurfPoint p;
+                if (h.objIdx == 1) {
                     const kernarg_f fl = scene_floats(offsetof(Scene, floorN));     // floorN[3], floorD, floorInvto
                     const kernarg_f fm = scene_floats(offsetof(Scene, floorMat));   // Material: reflectivity, refractivity, absorption[3], texOffset, texW, texH
-                    N = mk3(fl[0], fl[1], fl[2]);
-                    if (N.y == 1) {
-                        float u = I.x, v = I.z;
-                        u *= fl[4]; v *= fl[4];
-                        tu = u - __builtin_floorf(u); tv = v - __builtin_floorf(v);
-                    }
-                    refl = fm[0]; refr = fm[1];
-                    absorb = mk3(fm[2], fm[3], fm[4]);
-                    tOff = asu(fm[5]); tW = (int)asu(fm[6]); tH = (int)asu(fm[7]);
-                } else {                                                          // mesh: GetNormal / GetUV (bvh.cpp:290-305, blas_bvh.cpp:391-406)
-                    const f3 n0 = mk3(q0.x, q0.y, q0.z), n1 = mk3(q0.w, q1.x, q1.y), n2 = mk3(q1.z, q1.w, q2.x);   // (q0..q3) = the hit's ShadeTri
-                    const float w = 1 - h.u - h.v;
-                    const f3 Nn = w * n0 + h.u * n1 + h.v * n2;
-                    tu = w * q2.y + h.u * q2.w + h.v * q3.y;
-                    tv = w * q2.z + h.u * q3.x + h.v * q3.z;
-                    const rec4* mp = reinterpret_cast<const rec4*>(sc.mats + (int)asu(q3.w));
-                    const rec4 m0 = mp[0], m1 = mp[1];
-                    refl = m0.x; refr = m0.y; absorb = mk3(m0.z, m0.w, m1.x);
-                    tOff = asu(m1.y); tW = (int)asu(m1.z); tH = (int)asu(m1.w);
-                    if (KIND == 0) {
-                        N = normalize3(Nn);
-                    } else {
-                        const uint32_t io = sc.instOff + (uint32_t)(h.objIdx - 2) * 128u + 64u;   // Instance::T rows
-                        const rec4 r0 = ldg(geom, io), r1 = ldg(geom, io + 16), r2 = ldg(geom, io + 32);
-                        N = normalize3(mk3(r0.x * Nn.x + r0.y * Nn.y + r0.z * Nn.z + r0.w * 0.0f,
-                                           r1.x * Nn.x + r1.y * Nn.y + r1.z * Nn.z + r1.w * 0.0f,
-                                           r2.x * Nn.x + r2.y * Nn.y + r2.z * Nn.z + r2.w * 0.0f));
-                    }
-                }
-                if (dot3(N, D) > 0) N = -N;
+                    const rec4 m0 = {fm[0], fm[1], fm[2], fm[3]}, m1 = {fm[4], fm[5], fm[6], fm[7]};
+                    p = floor_point(mk3(fl[0], fl[1], fl[2]), fl[4], m0, m1, I);
+                } else p = mesh_point<KIND>(q0, q1, q2, q3, h.u, h.v, h.objIdx, geom, sc.instOff, sc.mats);   // (q0..q3) = the hit's ShadeTri
+                N = face_ray(p.N, D);
+                tu = p.tu; tv = p.tv; refl = p.refl; refr = p.refr; absorb = p.absorb; tOff = p.tOff; tW = p.tW; tH = p.tH;
             }
             // stage 3: the one texel fetch (Texture::Sample) — sky colour of a miss, albedo of a textured surface
             f3 c = mk3(1.0f, 1.0f, 1.0f);
             if (miss || (surf && tW > 0)) c = tex_sample(sc, tOff, tW, tH, tu, tv);
-            // stage 4a: the bounce (renderer.cpp:76-99).  `v` = outgoing direction (a diffuse one still to be normalised), `pre` = the
-            // throughput factor without the cosine term of the diffuse branch
-            f3 v = O, pre = O; bool norm = false, diffuse = false, newInside = false;
+            // stage 4a: the bounce (renderer.cpp:76-99).  `v` = outgoing direction (a diffuse one still to be normalised); its throughput factor
+            // follows in stage 5, once the direction is normalised
+            f3 v = O, medium = O; bool norm = false, newInside = false; Branch branch = kMirror;
             if (surf) {
-                f3 medium = mk3(1, 1, 1);
-                if (inside) {
-                    const f3 ab = absorb * -h.t;
-                    medium = mk3(crt_expf(ab.x), crt_expf(ab.y), crt_expf(ab.z));
-                }
-                const float r = rnd(seed);
-                if (r < refl) {                                                   // HandleMirror, renderer.cpp:20-25
-                    v = D - 2.0f * N * dot3(N, D);
-                    pre = c * medium;
-                } else if (r < refl + refr) {                                     // HandleDielectric, renderer.cpp:27-45
-                    v = D - 2.0f * N * dot3(N, D);
-                    const float n1 = inside ? 1.2f : 1, n2 = inside ? 1 : 1.2f;
-                    const float eta = n1 / n2, cosi = dot3(-D, N);
-                    const float cost2 = 1.0f - eta * eta * (1 - cosi * cosi);
-                    if (cost2 > 0) {
-                        const float a = n1 - n2, b2 = n1 + n2, R0 = (a * a) / (b2 * b2), cc = 1 - cosi;
-                        const float Fr = R0 + (1 - R0) * (cc * cc * cc * cc * cc);
-                        const f3 T = eta * D + ((eta * cosi - __builtin_sqrtf(__builtin_fabsf(cost2))) * N);
-                        if (rnd(seed) > Fr) { v = T; newInside = !inside; }
-                    }
-                    pre = c * medium;
-                } else {                                                          // diffuse, renderer.cpp:93-99; diffusereflection tmplmath.h:535-544
-                    f3 Rr;
-                    do {
-                        const float rz = rnd_pm1(seed);                           // draw order pinned z, y, x
-                        const float ry = rnd_pm1(seed);
-                        const float rx = rnd_pm1(seed);
-                        Rr = mk3(rx, ry, rz);
-                    } while (dot3(Rr, Rr) > 1);
-                    if (dot3(Rr, N) < 0) Rr = Rr * -1.0f;
-                    v = Rr; norm = true; diffuse = true;
-                    const f3 brdf = c * CRT_INVPI;
-                    pre = medium * brdf * 2.0f * CRT_PI;                          // ... * dot(R, N) once R is normalised (stage 5)
-                }
+                medium = medium_of(inside, absorb, h.t);
+                const Bounce b = draw_bounce(seed, D, N, inside, refl, refr);
+                v = b.v; branch = b.branch; newInside = b.newInside; norm = b.branch == kDiffuse;
             }
             // stage 4b: the path ended: unwind the recursion (innermost factor first: albedo*medium*Sample(...) multiplies on return),
             // store the sample, move on to the stream's next pixel
             bool gen = first;
             if (miss || stop) {
                 f3 L = miss ? c : ((depth >= sc.depthLimit) ? mk3(0, 0, 0) : mk3(24, 24, 22));   // GetLightColor, file_scene.cpp:164-167
-                // most paths end at depth 0..2: a level is read (and multiplied) only when some lane of the wave is that deep
-#pragma unroll
-                for (int k = 4; k >= 0; k--)
-                    if (depth > k) L = mk3(fst[(3 * k) * 64], fst[(3 * k + 1) * 64], fst[(3 * k + 2) * 64]) * L;
+                sample_unwind(fst, depth, L);                                     // most paths end at depth 0..2: a level is read only when some lane of the wave is that deep
                 uint32_t pix = item, pass = 0;
                 if (passes != 1u) { pix = item / passes; pass = item - pix * passes; }
                 slab[((size_t)tl * 256u + pix) * (64u * passes) + ((laneBase + lane) * passes + pass)] = make_float4(L.x, L.y, L.z, 0.0f);
@@ -304,22 +269,17 @@ __global__ __launch_bounds__(64, CRT_MIN_WAVES) void render_tiles_kernel(const S
             }
             if (gen) {                                                            // ProcessTile + Camera::GetPrimaryRay (renderer.cpp:125-126, camera.h:23-30)
                 const uint32_t pix = (passes == 1u) ? item : item / passes;
-                const int x = (int)(tx * 16u + (pix & 15u)), y = (int)(ty * 16u + (pix >> 4));
-                const float jy = rnd(seed);                                       // pinned: first draw is the y jitter
-                const float jx = rnd(seed);
                 const f3 TL = mk3(cam[3], cam[4], cam[5]), TR = mk3(cam[6], cam[7], cam[8]), BL = mk3(cam[9], cam[10], cam[11]);
-                const float u = ((float)x + jx) * cam[12], vv = ((float)y + jy) * cam[13];
-                const f3 P = TL + u * (TR - TL) + vv * (BL - TL);
-                v = P - camPos; norm = true;
+                v = primary_target(camPos, TL, TR - TL, BL - TL, cam[12], cam[13], tx, ty, pix, seed); norm = true;
                 inside = false; depth = 0; fresh = false;
                 cn.primary++;
             }
             // stage 5: the new ray (bounce or primary) and the start of its scene.FindNearest: light quad, floor plane, root step
             if (live) {
-                const float inv = rcp_exact(__builtin_sqrtf(dot3(v, v)));         // normalize(): v * (1 / sqrtf(dot(v, v)))
+                const float inv = rcp_exact(sqrt_exact(dot3(v, v)));              // normalize(): v * (1 / sqrtf(dot(v, v)))
                 const f3 nv = norm ? v * inv : v;
                 if (surf) {
-                    const f3 factor = diffuse ? pre * dot3(nv, N) : pre;
+                    const f3 factor = bounce_factor(branch, c, medium, nv, N);
                     float* fd = fst + depth * 192;                                // depth <= 4 here: a surface hit at depth >= depthLimit (<= 5) ended the path
                     fd[0] = factor.x; fd[64] = factor.y; fd[128] = factor.z;
                     depth++;
@@ -328,16 +288,7 @@ __global__ __launch_bounds__(64, CRT_MIN_WAVES) void render_tiles_kernel(const S
                 D = nv; rD = rcp_exact3(nv);
                 cn.rays++;
                 h.t = 1e34f; h.u = 0; h.v = 0; h.objIdx = -1; h.triIdx = -1;
-                {
-                    const kernarg_f lp = scene_floats(offsetof(Scene, lightInvT));   // lightInvT[12] lightNrm[3] lightSize lightPos[3] floorN[3] floorD
-                    const kernarg_f ax = scene_floats(offsetof(Scene, lightAxis));   // lightAxis, floorAxisY
-                    LightFloor lf;
-#pragma unroll
-                    for (int i = 0; i < 12; i++) lf.lightInvT[i] = lp[i];
-                    lf.lightSize = lp[15]; lf.floorN[0] = lp[19]; lf.floorN[1] = lp[20]; lf.floorN[2] = lp[21]; lf.floorD = lp[22];
-                    lf.lightAxis = asu(ax[0]); lf.floorAxisY = asu(ax[1]);
-                    hit_light_floor(lf, O, D, h);
-                }
+                hit_light_floor(light_floor_from_kernarg<false>(), O, D, h);
                 tO = O; tD = D; trD = rD; rayFinite = finite3(rD);
                 sp = 0;
                 if (sc.rootIsPair) {
@@ -350,13 +301,10 @@ __global__ __launch_bounds__(64, CRT_MIN_WAVES) void render_tiles_kernel(const S
                     float d1, d2;
                     if (__builtin_amdgcn_ballot_w64(!rayFinite) == 0ull) { d1 = box_fast(a0, a1, O, rD, h.t); d2 = box_fast(b0, b1, O, rD, h.t); }
                     else { d1 = box_exact(a0, a1, O, rD, h.t); d2 = box_exact(b0, b1, O, rD, h.t); }
-                    const bool sw = d1 > d2;
-                    const float dn = sw ? d2 : d1, df = sw ? d1 : d2;
-                    const uint32_t rn = sw ? asu(b0.w) : asu(a0.w), rf = sw ? asu(a0.w) : asu(b0.w);
-                    stk[0] = rf;                                                  // dead store unless pushed
-                    const bool hitN = dn != 1e30f;
-                    sp = (hitN && df != 1e30f) ? 1u : 0u;
-                    cur = hitN ? rn : kRefDone;
+                    const Ordered o = ordered_step(d1, d2, asu(a0.w), asu(b0.w));
+                    stk[0] = o.farRef;                                            // dead store unless pushed
+                    sp = o.push ? 1u : 0u;
+                    cur = o.hitN ? o.nearRef : kRefDone;
                     if (COUNT) { if (KIND == 0) cn.interior++; else cn.tlas++; }
                 } else cur = sc.rootRef;
                 if (COUNT && KIND == 0 && (cur & 0xC0000000u) == 0u && cur != kRefDone) cn.leaf++;
@@ -389,19 +337,12 @@ __global__ __launch_bounds__(64, CRT_MIN_WAVES) void render_tiles_kernel(const S
                 float d1, d2;
                 if (allFinite) { d1 = box_fast(q0, q1, tO, trD, h.t); d2 = box_fast(q2, q3, tO, trD, h.t); }
                 else { d1 = box_exact(q0, q1, tO, trD, h.t); d2 = box_exact(q2, q3, tO, trD, h.t); }
-                const bool sw = d1 > d2;                                             // near child first (strict >: ties keep child 1)
-                const float dn = sw ? d2 : d1, df = sw ? d1 : d2;
-                const uint32_t rn = sw ? asu(q2.w) : asu(q0.w), rf = sw ? asu(q0.w) : asu(q2.w);
-                stk[sp * 64u] = rf;                                                  // dead store unless `push`
-                const bool hitN = dn != 1e30f, push = hitN && df != 1e30f;
-                bool pop = !hitN && sp != 0u;
-                uint32_t next = hitN ? rn : (pop ? top : kRefDone);
-                sp = sp + (push ? 1u : 0u) - (pop ? 1u : 0u);
-                if (KIND == 1 && next == kRefReturn) {                               // BLAS finished: back to the world-space ray, pop the TLAS entry below
-                    tO = O; tD = D; trD = rD; rayFinite = finite3(rD);
-                    pop = sp != 0u; top = CRT_TOP();
-                    next = pop ? top : kRefDone; sp -= pop ? 1u : 0u;
-                }
+                const Ordered o = ordered_step(d1, d2, asu(q0.w), asu(q2.w));             // near child first
+                stk[sp * 64u] = o.farRef;                                             // dead store unless `push`
+                bool pop = !o.hitN && sp != 0u;
+                uint32_t next = o.hitN ? o.nearRef : (pop ? top : kRefDone);
+                sp = sp + (o.push ? 1u : 0u) - (pop ? 1u : 0u);
+                next = leave_blas(next);
                 if (COUNT && (next & 0xC0000000u) == 0u && next != kRefDone) cn.leaf++;
                 cur = next;
             }
@@ -417,8 +358,7 @@ __global__ __launch_bounds__(64, CRT_MIN_WAVES) void render_tiles_kernel(const S
             const uint64_t mNode2 = __builtin_amdgcn_ballot_w64(node2);
             if (mNode2 != 0ull) {
                 if (node2 || leaf2) {
-                    uint32_t oa = (cur & kRefOffsetMask) << 4, ob = oa + 32u;                  // NodePair / LeafTri
-                    if (KIND == 1 && (cur & kRefTlasBit) != 0u) { oa = sc.tlasOff + (cur & 0x7fffu) * 32u; ob = sc.tlasOff + ((cur >> 15) & 0x7fffu) * 32u; }   // TLAS interior: the two child nodes
+                    uint32_t oa, ob; record_offsets(false, oa, ob);
                     q0 = ldg(geom, oa); q1 = ldg(geom, oa + 16u); q2 = ldg(geom, ob); q3 = ldg(geom, ob + 16u);
                 }
                 triNow = isTri || leaf2;
@@ -429,19 +369,12 @@ __global__ __launch_bounds__(64, CRT_MIN_WAVES) void render_tiles_kernel(const S
                     float d1, d2;
                     if (allFinite2) { d1 = box_fast(q0, q1, tO, trD, h.t); d2 = box_fast(q2, q3, tO, trD, h.t); }
                     else { d1 = box_exact(q0, q1, tO, trD, h.t); d2 = box_exact(q2, q3, tO, trD, h.t); }
-                    const bool sw = d1 > d2;
-                    const float dn = sw ? d2 : d1, df = sw ? d1 : d2;
-                    const uint32_t rn = sw ? asu(q2.w) : asu(q0.w), rf = sw ? asu(q0.w) : asu(q2.w);
-                    stk[sp * 64u] = rf;
-                    const bool hitN = dn != 1e30f, push = hitN && df != 1e30f;
-                    bool pop = !hitN && sp != 0u;
-                    uint32_t next = hitN ? rn : (pop ? top : kRefDone);
-                    sp = sp + (push ? 1u : 0u) - (pop ? 1u : 0u);
-                    if (KIND == 1 && next == kRefReturn) {
-                        tO = O; tD = D; trD = rD; rayFinite = finite3(rD);
-                        pop = sp != 0u; top = CRT_TOP();
-                        next = pop ? top : kRefDone; sp -= pop ? 1u : 0u;
-                    }
+                    const Ordered o = ordered_step(d1, d2, asu(q0.w), asu(q2.w));             // near child first
+                    stk[sp * 64u] = o.farRef;
+                    bool pop = !o.hitN && sp != 0u;
+                    uint32_t next = o.hitN ? o.nearRef : (pop ? top : kRefDone);
+                    sp = sp + (o.push ? 1u : 0u) - (pop ? 1u : 0u);
+                    next = leave_blas(next);
                     if (COUNT && (next & 0xC0000000u) == 0u && next != kRefDone) cn.leaf++;
                     cur = next;
                 }
@@ -460,11 +393,7 @@ __global__ __launch_bounds__(64, CRT_MIN_WAVES) void render_tiles_kernel(const S
             bool pop = !more && sp != 0u;
             uint32_t next = more ? cur + 3u : (pop ? top : kRefDone);
             sp -= pop ? 1u : 0u;
-            if (KIND == 1 && next == kRefReturn) {
-                tO = O; tD = D; trD = rD; rayFinite = finite3(rD);
-                pop = sp != 0u; top = CRT_TOP();
-                next = pop ? top : kRefDone; sp -= pop ? 1u : 0u;
-            }
+            next = leave_blas(next);
             if (COUNT && !more && (next & 0xC0000000u) == 0u && next != kRefDone) cn.leaf++;
             cur = next;
         }
@@ -474,12 +403,7 @@ __global__ __launch_bounds__(64, CRT_MIN_WAVES) void render_tiles_kernel(const S
         // ---------------- issue the record loads of every lane that moved (consumed by a later trip) ---------------
         {
             const bool doneNow = cur == kRefDone;
-            uint32_t oa = doneNow ? sc.shadeOff + (uint32_t)h.triIdx * 64u : (cur & kRefOffsetMask) << 4;   // ShadeTri of the hit | NodePair / LeafTri
-            uint32_t ob = oa + 32u;
-            if (KIND == 1 && !doneNow && (cur & kRefTlasBit) != 0u) {
-                if (cur & kRefInterior) { oa = sc.instOff + (cur & 0xffffu) * 128u; ob = oa + 32u; }                // TLAS leaf: Instance {invT rows, ids}
-                else { oa = sc.tlasOff + (cur & 0x7fffu) * 32u; ob = sc.tlasOff + ((cur >> 15) & 0x7fffu) * 32u; } // TLAS interior: the two child nodes
-            }
+            uint32_t oa, ob; record_offsets(doneNow, oa, ob);
             // unconditional per lane on purpose: a lane that did not move re-fetches its record (an L1 hit) and a lane with nothing to
             // fetch reads record 0, so q0..q3 are plain loop-carried load results and nothing has to wait for them here.  Only when NO
             // lane of the wave has a record to fetch (tiles that see only sky and floor: every ray ends at the root step) the loads —
@@ -934,37 +858,19 @@ __global__ __launch_bounds__(64) void whitted_kernel(const Scene sc, const ALT a
                     else if (h.objIdx == 0) res = mk3(24, 24, 22);
                     else {
                         const f3 I = O + h.t * D;
-                        f3 N; float tu = 0, tv = 0; Material m;
-                        if (h.objIdx == 1) {
-                            N = mk3(sc.floorN[0], sc.floorN[1], sc.floorN[2]);
-                            if (N.y == 1) { float fu = I.x, fv = I.z; fu *= sc.floorInvto; fv *= sc.floorInvto; tu = fu - __builtin_floorf(fu); tv = fv - __builtin_floorf(fv); }
-                            m = sc.floorMat;
-                        } else {
+                        SurfPoint p;
+                        if (h.objIdx == 1) p = floor_point(mk3(sc.floorN[0], sc.floorN[1], sc.floorN[2]), sc.floorInvto, sc.floorMat, I);
+                        else {
                             const uint32_t so = sc.shadeOff + (uint32_t)h.triIdx * 64u;
                             const rec4 s0 = ldg(sc.geom, so), s1 = ldg(sc.geom, so + 16), s2 = ldg(sc.geom, so + 32), s3 = ldg(sc.geom, so + 48);
-                            const f3 n0 = mk3(s0.x, s0.y, s0.z), n1 = mk3(s0.w, s1.x, s1.y), n2 = mk3(s1.z, s1.w, s2.x);
-                            const float w = 1 - h.u - h.v;
-                            const f3 Nn = w * n0 + h.u * n1 + h.v * n2;
-                            tu = w * s2.y + h.u * s2.w + h.v * s3.y;
-                            tv = w * s2.z + h.u * s3.x + h.v * s3.z;
-                            const rec4* mp = reinterpret_cast<const rec4*>(sc.mats + (int)asu(s3.w));
-                            const rec4 m0 = mp[0], m1 = mp[1];
-                            m.reflectivity = m0.x; m.refractivity = m0.y; m.absorption[0] = m0.z; m.absorption[1] = m0.w; m.absorption[2] = m1.x;
-                            m.texOffset = asu(m1.y); m.texW = (int)asu(m1.z); m.texH = (int)asu(m1.w);
-                            if (sc.kind == 0) N = normalize3(Nn);
-                            else {
-                                const uint32_t io = sc.instOff + (uint32_t)(h.objIdx - 2) * 128u + 64u;
-                                const rec4 r0 = ldg(sc.geom, io), r1 = ldg(sc.geom, io + 16), r2 = ldg(sc.geom, io + 32);
-                                N = normalize3(mk3(r0.x * Nn.x + r0.y * Nn.y + r0.z * Nn.z + r0.w * 0.0f,
-                                                   r1.x * Nn.x + r1.y * Nn.y + r1.z * Nn.z + r1.w * 0.0f,
-                                                   r2.x * Nn.x + r2.y * Nn.y + r2.z * Nn.z + r2.w * 0.0f));
-                            }
+                            p = sc.kind == 0 ? mesh_point<0>(s0, s1, s2, s3, h.u, h.v, h.objIdx, sc.geom, sc.instOff, sc.mats)
+                                             : mesh_point<1>(s0, s1, s2, s3, h.u, h.v, h.objIdx, sc.geom, sc.instOff, sc.mats);
                         }
-                        if (dot3(N, D) > 0) N = -N;
-                        const f3 albedo = (m.texW > 0) ? tex_sample(sc, m.texOffset, m.texW, m.texH, tu, tv) : mk3(1.0f, 1.0f, 1.0f);
+                        const f3 N = face_ray(p.N, D);
+                        const f3 albedo = (p.tW > 0) ? tex_sample(sc, p.tOff, p.tW, p.tH, p.tu, p.tv) : mk3(1.0f, 1.0f, 1.0f);
                         WFrame& f = fr[sp];
                         f.flags = 0; f.out = mk3(0, 0, 0);
-                        const float refl = m.reflectivity, refr = m.refractivity;
+                        const float refl = p.refl, refr = p.refr;
                         const float diffuseness = 1 - (refl + refr);
                         f3 aO = O, aD = D; bool aInside = false;
                         if (refl > 0.0f) {                                               // renderer.cpp:49-54
@@ -1002,8 +908,7 @@ __global__ __launch_bounds__(64) void whitted_kernel(const Scene sc, const ALT a
                             const f3 brdf = albedo * CRT_INVPI;
                             f.C = diffuseness * brdf * (irr + mk3(0.3f, 0.3f, 0.3f)); f.flags |= 4;
                         }
-                        f.medium = mk3(1, 1, 1);
-                        if (inside) f.medium = mk3(crt_expf(m.absorption[0] * -h.t), crt_expf(m.absorption[1] * -h.t), crt_expf(m.absorption[2] * -h.t));
+                        f.medium = medium_of(inside, p.absorb, h.t);
                         terminal = false;
                         if (f.flags & 1) { O = aO; D = aD; inside = aInside; sp++; }                      // trace child A next
                         else if (f.flags & 2) { O = f.bO; D = f.bD; inside = false; f.flags |= 16; sp++; } // (not reachable in the reference: B only exists with refr > 0)

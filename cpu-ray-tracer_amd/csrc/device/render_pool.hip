@@ -21,10 +21,12 @@
 // nothing changes: every ray visits the reference's nodes in the reference's order and every float expression is evaluated as
 // written there, so the image is bit-identical to render_tiles_kernel's and to the CPU oracle's.
 //
+// The Sample body — the surface of a hit, medium, the bounce and its factor, the primary ray, the ordered two-child step — is sample_body.h's: the functions
+// render_tiles_kernel and the sequential kernels shade with, not a copy.  This file decides where the operands come from and when their loads are issued.
 // Numerics: -ffp-contract=off, IEEE + - * / sqrt only (dev_common.h).  No MFMA: pointer chasing + slab / Möller–Trumbore tests.
 #include <type_traits>
-#include "dev_common.h"
 #include "launch.h"
+#include "sample_body.h"
 
 namespace crt {
 
@@ -223,19 +225,7 @@ __global__ __launch_bounds__(64, CRT_POOL_MIN_WAVES) void render_pool_kernel(con
             cn.rays++;
             if (!sky) {
                 rD = rcp_exact3(D);
-                const kernarg_f lp = scene_floats(offsetof(Scene, lightInvT));      // lightInvT[12] lightNrm[3] lightSize lightPos[3] floorN[3] floorD: one block of the Scene
-                const kernarg_f ax = scene_floats(offsetof(Scene, lightAxis));      // lightAxis, floorAxisY
-                LightFloor lf;
-#pragma unroll
-                for (int i = 0; i < 12; i++) lf.lightInvT[i] = lp[i];
-                lf.lightSize = lp[15]; lf.floorN[0] = lp[19]; lf.floorN[1] = lp[20]; lf.floorN[2] = lp[21]; lf.floorD = lp[22];
-                lf.lightAxis = asu(ax[0]); lf.floorAxisY = asu(ax[1]);
-                lf.preOy = lf.preOx = lf.preOz = lf.preNum = 0.0f;
-                if constexpr (PRIM) {
-                    constexpr size_t pl = (offsetof(Scene, primLight) - offsetof(Scene, lightInvT)) / 4;   // primLight[3], primFloor: the same Scene block, further on
-                    lf.preOy = lp[pl]; lf.preOx = lp[pl + 1]; lf.preOz = lp[pl + 2]; lf.preNum = lp[pl + 3];
-                }
-                hit_light_floor<PRIM>(lf, O, D, nh, noLight, noFloor);
+                hit_light_floor<PRIM>(light_floor_from_kernarg<PRIM>(), O, D, nh, noLight, noFloor);
             }
             if (noTree) {
                 // both slab tests are known to fail: ncur = done, nothing pending; the reference's root step is still counted
@@ -254,12 +244,9 @@ __global__ __launch_bounds__(64, CRT_POOL_MIN_WAVES) void render_pool_kernel(con
                     else { d1 = box_exact_rel(ra0, ra1, rD, nh.t); d2 = box_exact_rel(rb0, rb1, rD, nh.t); }
                 } else if (allFinite) { d1 = box_fast(a0, a1, O, rD, nh.t); d2 = box_fast(b0, b1, O, rD, nh.t); }
                 else { d1 = box_exact(a0, a1, O, rD, nh.t); d2 = box_exact(b0, b1, O, rD, nh.t); }
-                const bool sw = d1 > d2;
-                const float dn = sw ? d2 : d1, df = sw ? d1 : d2;
-                const uint32_t rn = sw ? asu(b1.w) : asu(a1.w), rf = sw ? asu(a1.w) : asu(b1.w);   // the children's ref16
-                const bool hitN = dn != 1e30f;
-                pend = (hitN && df != 1e30f) ? rf : 0u;
-                ncur = hitN ? rn : kRefDone;
+                const Ordered o = ordered_step(d1, d2, asu(a1.w), asu(b1.w));        // the children's ref16
+                pend = o.push ? o.farRef : 0u;
+                ncur = o.hitN ? o.nearRef : kRefDone;
                 if (COUNT) { if (KIND == 0) cn.interior++; else cn.tlas++; }
             } else ncur = sc.rootRef16;
             if (COUNT && KIND == 0 && (ncur & kRef16TagMask) == 0u && ncur != kRefDone) cn.leaf++;
@@ -308,24 +295,26 @@ __global__ __launch_bounds__(64, CRT_POOL_MIN_WAVES) void render_pool_kernel(con
             float d1, d2;
             if (__builtin_expect(allFinite, 1)) { d1 = box_fast(q0, q1, tO, trD, h.t); d2 = box_fast(q2, q3, tO, trD, h.t); }
             else { d1 = box_exact(q0, q1, tO, trD, h.t); d2 = box_exact(q2, q3, tO, trD, h.t); }
-            const bool sw = d1 > d2;                                         // near child first (strict >: ties keep child 1)
-            const float dn = sw ? d2 : d1, df = sw ? d1 : d2;
-            const uint32_t rn = sw ? asu(q3.w) : asu(q1.w), rf = sw ? asu(q1.w) : asu(q3.w);   // the children's ref16
-            stk_put(spB + 128u, rf);                                         // dead store unless `push`
-            const bool hitN = dn != 1e30f, push = hitN && df != 1e30f;
-            const bool pop = !hitN && spB != laneB;
-            cur = hitN ? rn : (pop ? top : kRefDone);
-            spB = spB + (push ? 128u : 0u) - (pop ? 128u : 0u);
+            const Ordered o = ordered_step(d1, d2, asu(q1.w), asu(q3.w));    // the children's ref16
+            stk_put(spB + 128u, o.farRef);                                   // dead store unless `push`
+            const bool pop = !o.hitN && spB != laneB;
+            cur = o.hitN ? o.nearRef : (pop ? top : kRefDone);
+            spB = spB + (o.push ? 128u : 0u) - (pop ? 128u : 0u);
             if (COUNT && (cur & kRef16TagMask) == 0u && cur != kRefDone) cn.leaf++;
         }
     };
-    // the record of `cur` into q0..q3 for the lanes in m (the others keep theirs): record offset of a 16-bit reference = index * record size + section base (layout.h)
-    auto load_records = [&](uint64_t m) {
+    // where the record of `cur` lies in geom: record offset of a 16-bit reference = index * record size + section base (layout.h)
+    auto record_offset = [&]() -> uint32_t {
         const uint32_t idx = cur & kRef16IndexMask;
         const bool inter = (cur & kRef16Interior) != 0u;
         uint32_t oa = idx * (inter ? 64u : 48u) + (inter ? 0u : sc.leafOff - 48u);             // NodePair | LeafTri (one multiply-add on selected operands: no divergent arms)
         if (KIND == 1 && (cur & kRef16TlasBit) != 0u)
             oa = (cur & kRef16Interior) ? sc.instOff + idx * 128u : sc.tlasPairOff + idx * 64u;   // TLAS leaf: Instance {invT rows, ids} | TLAS interior: its child pair
+        return oa;
+    };
+    // the record of `cur` into q0..q3 for the lanes in m (the others keep theirs)
+    auto load_records = [&](uint64_t m) {
+        const uint32_t oa = record_offset();
         if (lane_in(m)) { q0 = ldp<0>(geom, oa); q1 = ldp<1>(geom, oa); q2 = ldp<2>(geom, oa); q3 = ldp<3>(geom, oa); }
     };
 
@@ -473,13 +462,8 @@ __global__ __launch_bounds__(64, CRT_POOL_MIN_WAVES) void render_pool_kernel(con
             }
             if (mRes != 0ull) {
                 CRT_DENS(21, 1);
-                // record offset of a 16-bit reference: index * record size + section base (layout.h); lanes without a stream re-read record 0
-                const uint32_t idx = cur & kRef16IndexMask;
-                const bool inter = (cur & kRef16Interior) != 0u;
-                uint32_t oa = idx * (inter ? 64u : 48u) + (inter ? 0u : sc.leafOff - 48u);             // NodePair | LeafTri (one multiply-add on selected operands: no divergent arms)
-                if (KIND == 1 && (cur & kRef16TlasBit) != 0u)
-                    oa = (cur & kRef16Interior) ? sc.instOff + idx * 128u : sc.tlasPairOff + idx * 64u;   // TLAS leaf: Instance {invT rows, ids} | TLAS interior: its child pair
-                if (!lane_in(mRes)) oa = 0u;
+                uint32_t oa = record_offset();
+                if (!lane_in(mRes)) oa = 0u;                                         // lanes without a stream re-read record 0
                 q0 = ldp<0>(geom, oa); q1 = ldp<1>(geom, oa); q2 = ldp<2>(geom, oa); q3 = ldp<3>(geom, oa);
             }
         }
@@ -570,10 +554,6 @@ __global__ __launch_bounds__(64, CRT_POOL_MIN_WAVES) void render_pool_kernel(con
                 f3 v = camPos;
                 if (gen) {                                                         // ProcessTile + Camera::GetPrimaryRay (renderer.cpp:125-126, camera.h:23-30)
                     const uint32_t pix = (passes == 1u) ? item : item / passes;
-                    const int x = (int)(tx * 16u + (pix & 15u)), y = (int)(ty * 16u + (pix >> 4));
-                    const float jy = rnd(seed);                                    // pinned: first draw is the y jitter
-                    const float jx = rnd(seed);
-                    const float u = ((float)x + jx) * cam[12], vv = ((float)y + jy) * cam[13];     // invW, invH follow the camera in the Scene block
                     const f3 TL = mk3(cam[3], cam[4], cam[5]);
 #ifdef CRT_DIET_NO_CAMREL
                     const f3 TR = mk3(cam[6], cam[7], cam[8]), BL = mk3(cam[9], cam[10], cam[11]);
@@ -582,8 +562,7 @@ __global__ __launch_bounds__(64, CRT_POOL_MIN_WAVES) void render_pool_kernel(con
                     constexpr size_t pc = (offsetof(Scene, primRight) - offsetof(Scene, camPos)) / 4;   // primRight[3], primDown[3]: TR - TL and BL - TL, formed on the host
                     const f3 right = mk3(cam[pc], cam[pc + 1], cam[pc + 2]), down = mk3(cam[pc + 3], cam[pc + 4], cam[pc + 5]);
 #endif
-                    const f3 P = TL + u * right + vv * down;
-                    v = P - camPos;
+                    v = primary_target(camPos, TL, right, down, cam[12], cam[13], tx, ty, pix, seed);   // invW, invH follow the camera in the Scene block
                     cn.primary++;
                 }
                 CRT_DENS_MASK(12, gen);
@@ -634,91 +613,32 @@ __global__ __launch_bounds__(64, CRT_POOL_MIN_WAVES) void render_pool_kernel(con
                 const bool inside = (meta & kMetaInside) != 0u;
                 const int depth = (int)((meta >> kMetaDepthShift) & 7u);
                 const uint32_t item = meta & kMetaItemMask;
-                float tu = 0, tv = 0; uint32_t tOff = 0; int tW = 0, tH = 0;
-                f3 I = O, N = O, absorb = O; float refl = 0, refr = 0;
-                f3 v = O, pre = O; bool norm = false, diffuse = false, newInside = false;
+                f3 v = O; bool newInside = false;
                 if (act) {
-                    I = O + ht * D;
-                    if (obj == 1) {                                                // floor: Plane::GetNormal / GetUV (primitives.h:112-133)
+                    const f3 I = O + ht * D;
+                    SurfPoint p;
+                    if (obj == 1) {
                         const kernarg_f fl = scene_floats(offsetof(Scene, floorN));      // floorN[3], floorD, floorInvto
                         const kernarg_f fm = scene_floats(offsetof(Scene, floorMat));    // Material: reflectivity, refractivity, absorption[3], texOffset, texW, texH
-                        N = mk3(fl[0], fl[1], fl[2]);
-                        if (N.y == 1) {
-                            float u = I.x, vv = I.z;
-                            u *= fl[4]; vv *= fl[4];
-                            tu = u - __builtin_floorf(u); tv = vv - __builtin_floorf(vv);
-                        }
-                        refl = fm[0]; refr = fm[1];
-                        absorb = mk3(fm[2], fm[3], fm[4]);
-                        tOff = asu(fm[5]); tW = (int)asu(fm[6]); tH = (int)asu(fm[7]);
-                    } else {                                                       // mesh: GetNormal / GetUV (bvh.cpp:290-305, blas_bvh.cpp:391-406)
-                        const f3 n0 = mk3(s0.x, s0.y, s0.z), n1 = mk3(s0.w, s1.x, s1.y), n2 = mk3(s1.z, s1.w, s2.x);
-                        const float w = 1 - hu - hv;
-                        const f3 Nn = w * n0 + hu * n1 + hv * n2;
-                        tu = w * s2.y + hu * s2.w + hv * s3.y;
-                        tv = w * s2.z + hu * s3.x + hv * s3.z;
-                        const rec4* mp = reinterpret_cast<const rec4*>(sc.mats + (int)asu(s3.w));
-                        const rec4 m0 = mp[0], m1 = mp[1];
-                        refl = m0.x; refr = m0.y; absorb = mk3(m0.z, m0.w, m1.x);
-                        tOff = asu(m1.y); tW = (int)asu(m1.z); tH = (int)asu(m1.w);
-                        if (KIND == 0) {
-                            N = normalize3(Nn);
-                        } else {
-                            const uint32_t io = sc.instOff + (uint32_t)(obj - 2) * 128u + 64u;   // Instance::T rows
-                            const rec4 r0 = ldp<0>(geom, io), r1 = ldp<1>(geom, io), r2 = ldp<2>(geom, io);
-                            N = normalize3(mk3(r0.x * Nn.x + r0.y * Nn.y + r0.z * Nn.z + r0.w * 0.0f,
-                                               r1.x * Nn.x + r1.y * Nn.y + r1.z * Nn.z + r1.w * 0.0f,
-                                               r2.x * Nn.x + r2.y * Nn.y + r2.z * Nn.z + r2.w * 0.0f));
-                        }
-                    }
-                    if (dot3(N, D) > 0) N = -N;
+                        const rec4 m0 = {fm[0], fm[1], fm[2], fm[3]}, m1 = {fm[4], fm[5], fm[6], fm[7]};
+                        p = floor_point(mk3(fl[0], fl[1], fl[2]), fl[4], m0, m1, I);
+                    } else p = mesh_point<KIND>(s0, s1, s2, s3, hu, hv, obj, geom, sc.instOff, sc.mats);
+                    const f3 N = face_ray(p.N, D);
                     // Material::GetAlbedo: the texel fetch is issued here and consumed after the direction has been drawn (its latency hides behind the rejection loop)
                     uint32_t texel = 0x00ffffffu;
-                    if (tW > 0) texel = sc.texels[tex_index(tOff, tW, tH, tu, tv)];
-                    f3 medium = mk3(1, 1, 1);
-                    if (inside) {
-                        const f3 ab = absorb * -ht;
-                        medium = mk3(crt_expf(ab.x), crt_expf(ab.y), crt_expf(ab.z));
-                    }
+                    if (p.tW > 0) texel = sc.texels[tex_index(p.tOff, p.tW, p.tH, p.tu, p.tv)];
+                    const f3 medium = medium_of(inside, p.absorb, ht);
                     CRT_PSTAMP(b1); CRT_PACC(5, p3, b1);
-                    const float r = rnd(seed);
-                    const bool mirror = r < refl, dielectric = !mirror && r < refl + refr;
-                    if (mirror) {                                                  // HandleMirror, renderer.cpp:20-25
-                        v = D - 2.0f * N * dot3(N, D);
-                    } else if (dielectric) {                                       // HandleDielectric, renderer.cpp:27-45
-                        v = D - 2.0f * N * dot3(N, D);
-                        const float n1 = inside ? 1.2f : 1, n2 = inside ? 1 : 1.2f;
-                        const float eta = n1 / n2, cosi = dot3(-D, N);
-                        const float cost2 = 1.0f - eta * eta * (1 - cosi * cosi);
-                        if (cost2 > 0) {
-                            const float a = n1 - n2, b2 = n1 + n2, R0 = (a * a) / (b2 * b2), cc = 1 - cosi;
-                            const float Fr = R0 + (1 - R0) * (cc * cc * cc * cc * cc);
-                            const f3 T = eta * D + ((eta * cosi - sqrt_exact(__builtin_fabsf(cost2))) * N);
-                            if (rnd(seed) > Fr) { v = T; newInside = !inside; }
-                        }
-                    } else {                                                       // diffuse, renderer.cpp:93-99; diffusereflection tmplmath.h:535-544
-                        f3 Rr;
-                        do {
-                            const float rz = rnd_pm1(seed);                        // draw order pinned z, y, x
-                            const float ry = rnd_pm1(seed);
-                            const float rx = rnd_pm1(seed);
-                            Rr = mk3(rx, ry, rz);
-                        } while (dot3(Rr, Rr) > 1);
-                        if (dot3(Rr, N) < 0) Rr = Rr * -1.0f;
-                        v = Rr; norm = true; diffuse = true;
-                    }
-                    // albedo (1,1,1 untextured: 0xffffff * (1/255) == 1 exactly) and the factor without the cosine term of the diffuse branch
-                    const f3 c = (tW > 0) ? tex_unpack(texel) : mk3(1.0f, 1.0f, 1.0f);
-                    if (diffuse) {
-                        const f3 brdf = c * CRT_INVPI;
-                        pre = medium * brdf * 2.0f * CRT_PI;                       // ... * dot(R, N) once R is normalised
-                    } else pre = c * medium;
+                    const Bounce b = draw_bounce(seed, D, N, inside, p.refl, p.refr);
+                    newInside = b.newInside;
+                    // albedo (1,1,1 untextured: 0xffffff * (1/255) == 1 exactly)
+                    const f3 c = (p.tW > 0) ? tex_unpack(texel) : mk3(1.0f, 1.0f, 1.0f);
                     CRT_PSTAMP(b2); CRT_PACC(6, b1, b2);
                     // normalize(R) of the diffuse branch; the bounce's throughput factor and the new origin use the normalised direction
-                    const float inv = rcp_exact(sqrt_exact(dot3(v, v)));
-                    const f3 nv = norm ? v * inv : v;
+                    const float inv = rcp_exact(sqrt_exact(dot3(b.v, b.v)));
+                    const f3 nv = b.branch == kDiffuse ? b.v * inv : b.v;
                     v = nv;
-                    const f3 factor = diffuse ? pre * dot3(nv, N) : pre;
+                    const f3 factor = bounce_factor(b.branch, c, medium, nv, N);
                     float* fd = fac + (3 * depth) * S + s;                         // depth <= 4 here
                     __hip_atomic_store(fd, factor.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                     __hip_atomic_store(fd + S, factor.y, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

@@ -4,7 +4,8 @@
 //   * Sample through FileScene's KD-tree / uniform grid (crt_set_render_accel; render_seq.hip);
 //   * Sample over the PrimitiveScene (render_prim.hip).
 // The per-path part (sample_step: one FindNearest + the Sample branch + the factor store; sample_unwind: the return path) is also what sample_query_kernel
-// (sample_query.h: Sample for a caller's rays and seeds) runs — there is one Sample body.
+// (sample_query.h: Sample for a caller's rays and seeds) runs.  The branch itself — medium, the rnd draw, mirror / dielectric / diffuse, the throughput factor, the
+// primary ray, the return path — is sample_body.h's: the functions render_pool_kernel and render_tiles_kernel shade with, not a copy.
 // What differs between them is the "world" the loop runs in, a small policy class:
 //   uint32_t trace(sc, O, D, rD, h, stk)   scene.FindNearest into `h`; returns the traversal steps the probe counts (interior + triangle + TLAS steps; 0 where never probed)
 //   Surf surface(sc, h, I, D)              normal (already facing the ray), albedo, reflectivity, refractivity and absorption at the hit
@@ -14,7 +15,7 @@
 // Per stream everything is the reference's: the rnd draws in its order and every float expression as written there (-ffp-contract=off, dev_common.h), so the
 // samples are bit-identical to render_pool_kernel's, render_tiles_kernel's and the CPU oracle's.
 #pragma once
-#include "dev_common.h"
+#include "sample_body.h"
 
 namespace crt {
 
@@ -46,56 +47,16 @@ __device__ __forceinline__ bool sample_step(const Scene& sc, const World& world,
     const f3 I = O + h.t * D;
     const Surf s = world.surface(sc, h, I, D);
     const f3 N = s.N, c = s.c;
-    f3 medium = mk3(1, 1, 1);
-    if (inside) {
-        const f3 ab = s.absorb * -h.t;
-        medium = mk3(crt_expf(ab.x), crt_expf(ab.y), crt_expf(ab.z));
-    }
-    f3 nv, factor; bool newInside = false;
-    const float r = rnd(seed);
-    if (r < s.refl) {                                                              // HandleMirror, renderer.cpp:20-25
-        nv = D - 2.0f * N * dot3(N, D);
-        factor = c * medium;
-    } else if (r < s.refl + s.refr) {                                              // HandleDielectric, renderer.cpp:27-45
-        nv = D - 2.0f * N * dot3(N, D);
-        const float n1 = inside ? 1.2f : 1, n2 = inside ? 1 : 1.2f;
-        const float eta = n1 / n2, cosi = dot3(-D, N);
-        const float cost2 = 1.0f - eta * eta * (1 - cosi * cosi);
-        if (cost2 > 0) {
-            const float a = n1 - n2, b2 = n1 + n2, R0 = (a * a) / (b2 * b2), cc = 1 - cosi;
-            const float Fr = R0 + (1 - R0) * (cc * cc * cc * cc * cc);
-            const f3 T = eta * D + ((eta * cosi - __builtin_sqrtf(__builtin_fabsf(cost2))) * N);
-            if (rnd(seed) > Fr) { nv = T; newInside = !inside; }
-        }
-        factor = c * medium;
-    } else {                                                                       // diffuse, renderer.cpp:93-99; diffusereflection tmplmath.h:535-544
-        f3 Rr;
-        do {
-            const float rz = rnd_pm1(seed);                                        // draw order pinned z, y, x
-            const float ry = rnd_pm1(seed);
-            const float rx = rnd_pm1(seed);
-            Rr = mk3(rx, ry, rz);
-        } while (dot3(Rr, Rr) > 1);
-        if (dot3(Rr, N) < 0) Rr = Rr * -1.0f;
-        nv = Rr * rcp_exact(__builtin_sqrtf(dot3(Rr, Rr)));                        // normalize(R)
-        const f3 brdf = c * CRT_INVPI;
-        const f3 pre = medium * brdf * 2.0f * CRT_PI;
-        factor = pre * dot3(nv, N);
-    }
+    const f3 medium = medium_of(inside, s.absorb, h.t);
+    const Bounce b = draw_bounce(seed, D, N, inside, s.refl, s.refr);
+    const f3 nv = b.branch == kDiffuse ? b.v * rcp_exact(sqrt_exact(dot3(b.v, b.v))) : b.v;   // normalize(R)
+    const f3 factor = bounce_factor(b.branch, c, medium, nv, N);
     // the bounce's throughput factor (albedo*medium*... multiplies on return: depth <= 4 here)
     float* fd = fst + (uint32_t)(3 * depth) * 64u;
     fd[0] = factor.x; fd[64] = factor.y; fd[128] = factor.z;
     depth++;
-    O = I + nv * CRT_EPS; D = nv; inside = newInside;
+    O = I + nv * CRT_EPS; D = nv; inside = b.newInside;
     return false;
-}
-
-// the recursion's return path: the factors of the `depth` bounces multiply the radiance innermost first (depth <= 5)
-__device__ __forceinline__ void sample_unwind(const float* fst, int depth, f3& L)
-{
-#pragma unroll
-    for (int k = 4; k >= 0; k--)
-        if (depth > k) { const float* fd = fst + (uint32_t)(3 * k) * 64u; L = mk3(fd[0], fd[64], fd[128]) * L; }
 }
 
 // entry = tile rank * windows + window.  PROBE = true is the cost probe of the latency mode: kProbeWaves entries per tile, lane l of entry q traces ONE path through
@@ -139,13 +100,8 @@ __global__ __launch_bounds__(256, 4) void render_seq_kernel(const Scene sc, cons
     for (uint32_t item = 0; item < items; item++) {
         // ---------------- ProcessTile + Camera::GetPrimaryRay (renderer.cpp:125-126, camera.h:23-30) ----------------
         const uint32_t pix = PROBE ? ((lane * 4u + entry % kProbeWaves) & 255u) : ((passes == 1u) ? item : item / passes);
-        const int x = (int)(tx * 16u + (pix & 15u)), y = (int)(ty * 16u + (pix >> 4));
-        const float jy = rnd(seed);                                               // pinned: first draw is the y jitter
-        const float jx = rnd(seed);
-        const float u = ((float)x + jx) * invW, vv = ((float)y + jy) * invH;
-        const f3 P = TL + u * (TR - TL) + vv * (BL - TL);
-        f3 v = P - camPos;
-        f3 O = camPos, D = v * rcp_exact(__builtin_sqrtf(dot3(v, v)));            // normalize()
+        const f3 v = primary_target(camPos, TL, TR - TL, BL - TL, invW, invH, tx, ty, pix, seed);
+        f3 O = camPos, D = v * rcp_exact(sqrt_exact(dot3(v, v)));                 // normalize()
         bool inside = false; int depth = 0;
         nPrimary++;
         f3 L = mk3(0, 0, 0);
