@@ -604,6 +604,16 @@ class Context:
         self._ck(self.L.crt_get_timing(self.h, C.byref(t)))
         return dict(render_kernel_ms=t.render_kernel_ms, resolve_kernel_ms=t.resolve_kernel_ms, render_launches=t.render_launches, pool_launches=t.pool_launches, split_launches=t.split_launches)
 
+    def pool_lds(self, frames):
+        """crt_debug_pool_lds: (LDS bytes one render_pool_kernel wavefront of a launch of `frames` frames on the uploaded scene asks for, the per-workgroup limit
+        the library holds it to, the width of the scene's pool references: 16, 32 or 0 = none)"""
+        self.L.crt_debug_pool_lds.restype = C.c_int
+        self.L.crt_debug_pool_lds.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+        b, lim, bits = C.c_uint32(), C.c_uint32(), C.c_uint32()
+        if self.L.crt_debug_pool_lds(self.h, int(frames), C.byref(b), C.byref(lim), C.byref(bits)) != 0:
+            raise CrtError(-3, "pool_lds: no scene uploaded")
+        return b.value, lim.value, bits.value
+
     def tile_classes(self):
         """crt_debug_tile_classes: the pool kernel's tile classes as the device holds them, one byte per owned tile (TILE_NO_LIGHT | TILE_NO_FLOOR | TILE_NO_TREE)"""
         self.L.crt_debug_tile_classes.restype = C.c_int

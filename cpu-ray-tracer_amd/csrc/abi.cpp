@@ -191,6 +191,8 @@ struct crt_ctx {
     uint64_t poolMinWaves = 65000; // launches of fewer (tile, 64-frame window) pairs run render_tiles_kernel: see crt_render
     bool usePool = true;          // render_pool_kernel (stream pool); CRT_RENDER_KERNEL=tiles selects render_tiles_kernel (one stream per lane)
     uint32_t ldsBytes = 0;
+    uint32_t extraLds = 0;        // CRT_DEBUG_EXTRA_LDS: unused LDS bytes per wavefront (part of ldsBytes; the pool launch adds it to its own need)
+    uint32_t poolLdsLimit = 0;    // crt_pool_lds_limit of the device (0: not asked yet)
     // timing of the last crt_render
     std::vector<EventPair> evPool; size_t evUsedRender = 0, evUsedAcc = 0;
     std::deque<EventPair> evRender, evAcc;                        // launches not yet folded into the totals below (oldest first)
@@ -510,7 +512,12 @@ int crt_upload_scene(crt_ctx* c, const crt_scene_desc* sd)
     crt::LeafTri* leaf = reinterpret_cast<crt::LeafTri*>(geom.data() + leafOffB);
     crt::TlasNode* tlas = reinterpret_cast<crt::TlasNode*>(geom.data() + tlasOffB);
     crt::NodePair* tlasPairs = reinterpret_cast<crt::NodePair*>(geom.data() + tlasPairOffB);
-    bool ref16ok = nPairs <= crt::kRef16MaxIndex && nTris < crt::kRef16MaxIndex;
+    // The width the scene's pool references are written in (layout.h): 16 bits where every index fits, else 32 — whose index limit is what kMaxGeomBytes imposes
+    // on the records anyway (index * 64 and leafOff + index * 48 below 2^32), checked here all the same; a scene beyond it has no pool form (render_tiles_kernel).
+    const bool ref16ok = nPairs <= crt::kRef16MaxIndex && nTris < crt::kRef16MaxIndex && !hook("CRT_DEBUG_NO_REF16");   // (tests: a scene that fits, treated as one that does not)
+    const bool refWideOk = nPairs <= crt::kRefWideMaxIndex && nTris < crt::kRefWideMaxIndex && nPairs * 64 < crt::kMaxGeomBytes && leafOffB + nTris * 48 < crt::kMaxGeomBytes;
+    const uint32_t poolRefBits = ref16ok ? 16u : (refWideOk ? 32u : 0u);
+    const crt::PoolRefForm PR = crt::pool_ref_form(poolRefBits);
     crt::Instance* inst = reinterpret_cast<crt::Instance*>(geom.data() + instOffB);
     crt::ShadeTri* shade = reinterpret_cast<crt::ShadeTri*>(geom.data() + shadeOffB);
 
@@ -529,11 +536,11 @@ int crt_upload_scene(crt_ctx* c, const crt_scene_desc* sd)
             }
             return 0;
         };
-        // the same reference in 16 bits (layout.h): record INDEX instead of offset; only meaningful when ref16ok
+        // the same reference in the pool form (layout.h), in the scene's width: record INDEX instead of offset; only meaningful when poolRefBits != 0
         auto ref16_of = [&](uint32_t n) -> uint32_t {
             const crt_bvh_node& nd = b.nodes[n];
-            if (nd.triCount > 0) return (uint32_t)((triBase + nd.leftFirst + 1) & crt::kRef16IndexMask);
-            return crt::kRef16Interior | (uint32_t)((pairBase + ((nd.leftFirst - 1u) >> 1)) & crt::kRef16IndexMask);
+            if (nd.triCount > 0) return (uint32_t)((triBase + nd.leftFirst + 1) & PR.indexMask);
+            return PR.interior | (uint32_t)((pairBase + ((nd.leftFirst - 1u) >> 1)) & PR.indexMask);
         };
         int r;
         for (uint32_t n = 1; n + 1 < b.nodesUsed; n += 2) {
@@ -592,7 +599,7 @@ int crt_upload_scene(crt_ctx* c, const crt_scene_desc* sd)
             memcpy(tlas[i].lo, nd.aabbMin, 12); memcpy(tlas[i].hi, nd.aabbMax, 12);
             tlas[i].ref = nd.leftRight ? (crt::kRefTlasInterior | (nd.leftRight & 0x7fffu) | (((nd.leftRight >> 16) & 0x7fffu) << 15))
                                        : (crt::kRefTlasLeaf | (nd.BLAS & 0xffffu));
-            tlas[i].ref16 = nd.leftRight ? (crt::kRef16TlasBit | nTlasPairs++) : (crt::kRef16TlasLeaf | (nd.BLAS & crt::kRef16IndexMask));   // interior nodes number their child pairs
+            tlas[i].ref16 = nd.leftRight ? (PR.tlasBit | nTlasPairs++) : (PR.tlasLeaf | (nd.BLAS & PR.indexMask));   // interior nodes number their child pairs
         }
         std::vector<std::pair<uint32_t, uint32_t>> st; st.push_back({0u, 0u}); size_t visited = 0;
         while (!st.empty()) {
@@ -608,7 +615,7 @@ int crt_upload_scene(crt_ctx* c, const crt_scene_desc* sd)
         for (uint32_t i = 0; i < sd->tlasNodeCount; i++) {
             const crt_tlas_node& nd = sd->tlasNodes[i];
             if (nd.leftRight == 0) continue;
-            crt::NodePair& p = tlasPairs[tlas[i].ref16 & crt::kRef16IndexMask];
+            crt::NodePair& p = tlasPairs[tlas[i].ref16 & PR.indexMask];
             memcpy(&p.c[0], &tlas[nd.leftRight & 0xffffu], 32); memcpy(&p.c[1], &tlas[nd.leftRight >> 16], 32);
         }
         tlasRoot = tlas[0].ref; tlasRoot16 = tlas[0].ref16;
@@ -672,7 +679,7 @@ int crt_upload_scene(crt_ctx* c, const crt_scene_desc* sd)
     s.tlasOff = (uint32_t)tlasOffB; s.instOff = (uint32_t)instOffB; s.shadeOff = (uint32_t)shadeOffB;
     s.leafOff = (uint32_t)leafOffB; s.tlasPairOff = (uint32_t)tlasPairOffB;
     s.rootRef16 = (sd->kind == CRT_SCENE_TLAS) ? tlasRoot16 : rootRef0_16;
-    s.ref16ok = (ref16ok && !hook("CRT_DEBUG_NO_REF16")) ? 1u : 0u;
+    s.poolRefBits = poolRefBits;
     if ((r = upload(c, mats, &s.mats))) return r;
     if (sd->kind == CRT_SCENE_TLAS) {                                     // every BLAS's node-0 box, where crt_update_transforms_device takes SetTransform's corners from
         std::vector<float> boxes;
@@ -701,7 +708,8 @@ int crt_upload_scene(crt_ctx* c, const crt_scene_desc* sd)
     primary_changed(c);                                                             // new light / floor block and rootPair: the camera-relative block follows
     s.stackDepth = s.bvhStack + ((sd->kind == CRT_SCENE_TLAS) ? tlasHeight + 1 : 0);   // + TLAS pushes + the return marker
     c->ldsBytes = s.stackDepth * 64u * 4u; c->latSlots = 0;
-    if (const char* e = hook("CRT_DEBUG_EXTRA_LDS")) c->ldsBytes += (uint32_t)atoi(e);   // occupancy experiments only
+    c->extraLds = 0;
+    if (const char* e = hook("CRT_DEBUG_EXTRA_LDS")) { c->extraLds = (uint32_t)atoi(e); c->ldsBytes += c->extraLds; }   // occupancy experiments and tests: unused LDS on top, for every render kernel
     if (c->ldsBytes + 15u * 256u > 64u * 1024u) return c->fail(CRT_ERR_UNSUPPORTED, "tree height %u (+TLAS %u) needs %u bytes of LDS traversal stack per wave (> 64 KiB)", maxHeight, tlasHeight, c->ldsBytes);
     // world-space bounds of all meshes (FileScene: root box of the BVH; TLAS: root box of the TLAS) for the dispatch-order heuristic
     {
@@ -801,13 +809,14 @@ static int end_scene_write(crt_ctx* c, hipStream_t st, hipEvent_t done)
 // pair of every interior node side by side (NodePair layout).  Returns the TLAS height, or a negative status.
 static int flatten_tlas(crt_ctx* c, const crt_tlas_node* nodes, uint32_t count, uint32_t bvhCount, crt::TlasNode* tlas, crt::NodePair* tlasPairs, uint32_t* heightOut)
 {
+    const crt::PoolRefForm PR = crt::pool_ref_form(c->hScene.poolRefBits);      // the pool references stay in the width the scene was uploaded in
     uint32_t nTlasPairs = 0;
     for (uint32_t i = 0; i < count; i++) {      // device copy carries each node's packed reference instead of leftRight / BLAS
         const crt_tlas_node& nd = nodes[i];
         memcpy(tlas[i].lo, nd.aabbMin, 12); memcpy(tlas[i].hi, nd.aabbMax, 12);
         tlas[i].ref = nd.leftRight ? (crt::kRefTlasInterior | (nd.leftRight & 0x7fffu) | (((nd.leftRight >> 16) & 0x7fffu) << 15))
                                    : (crt::kRefTlasLeaf | (nd.BLAS & 0xffffu));
-        tlas[i].ref16 = nd.leftRight ? (crt::kRef16TlasBit | nTlasPairs++) : (crt::kRef16TlasLeaf | (nd.BLAS & crt::kRef16IndexMask));   // interior nodes number their child pairs
+        tlas[i].ref16 = nd.leftRight ? (PR.tlasBit | nTlasPairs++) : (PR.tlasLeaf | (nd.BLAS & PR.indexMask));   // interior nodes number their child pairs
     }
     std::vector<std::pair<uint32_t, uint32_t>> st; st.push_back({0u, 0u}); size_t visited = 0; uint32_t height = 0;
     while (!st.empty()) {
@@ -822,7 +831,7 @@ static int flatten_tlas(crt_ctx* c, const crt_tlas_node* nodes, uint32_t count, 
     for (uint32_t i = 0; i < count; i++) {
         const crt_tlas_node& nd = nodes[i];
         if (nd.leftRight == 0) continue;
-        crt::NodePair& p = tlasPairs[tlas[i].ref16 & crt::kRef16IndexMask];
+        crt::NodePair& p = tlasPairs[tlas[i].ref16 & PR.indexMask];
         memcpy(&p.c[0], &tlas[nd.leftRight & 0xffffu], 32); memcpy(&p.c[1], &tlas[nd.leftRight >> 16], 32);
     }
     *heightOut = height;
@@ -846,6 +855,20 @@ static void set_root(crt_ctx* c, int kind, const float* lo, const float* hi)
     if (hook("CRT_DEBUG_NO_ROOTPAIR")) s.rootIsPair = 0;
     primary_changed(c);
     memcpy(c->meshLo, lo, 12); memcpy(c->meshHi, hi, 12); c->orderDirty = true;
+}
+
+// LDS of one render_pool_kernel wavefront of a launch of `frames` frames on the current scene, CRT_DEBUG_EXTRA_LDS included (crt_launch_render_pool asks for the same)
+static uint32_t pool_lds_need(const crt_ctx* c, uint32_t frames)
+{
+    return crt_pool_lds_bytes(c->hScene.stackDepth, crt_pool_streams(frames), c->hScene.poolRefBits) + c->extraLds;
+}
+// Can render_pool_kernel render the current scene at all: its references have a pool form (16 or 32 bits wide, layout.h) and a wavefront's LDS stays within what the
+// device grants a workgroup.  Otherwise the launch is render_tiles_kernel's, whatever CRT_RENDER_KERNEL says.
+static bool pool_can_run(crt_ctx* c, uint32_t frames)
+{
+    if (c->hScene.poolRefBits == 0u) return false;
+    if (!c->poolLdsLimit) c->poolLdsLimit = crt_pool_lds_limit(c->cfg.device);
+    return pool_lds_need(c, frames) <= c->poolLdsLimit;
 }
 
 // a TLAS of this height on top of the scene's BLASes: does the traversal stack (BVH part + TLAS pushes + the return marker) fit the LDS budget of the render kernels?
@@ -1660,8 +1683,13 @@ static int planner_prepare(crt_ctx* c, Launch& L)
     // threshold sits at the low end of that range.
     // With the tile costs known (most expensive first + split, see plan_job) the pool is never slower than one stream per lane from ~12 windows of 720p on
     // (tools/split_probe.py: bunny 14 windows 57.8 against 59.6 ms, two-level scene 16 windows 79 against 94 ms, watch-tower 1080p 7 windows 155.6 against 161.1 ms).
+    // A scene in the 32-bit pool-reference form (layout.h; 4-byte stack entries: 13 KB of LDS per wavefront at a stack depth of 20, 3 waves per SIMD): the pool did not
+    // beat one stream per lane at any job size measured (14-bunny scene 1280x720, tools/pool_wide_bench.py, profiles/pool_wide.json: 12 / 20 / 64 windows 249.3 /
+    // 413.7 / 1299.9 ms against 245.9 / 407.8 / 1293.1 ms, scatter <= 0.2 %), so by default such a scene is rendered by render_tiles_kernel at every size and the
+    // pool is reached through CRT_RENDER_KERNEL=pool_always alone.  (Scene-dependent: on the 4-bunny scenes the 32-bit pool is 7 - 11 % faster)
+    const bool poolByDefault = c->hScene.poolRefBits == 16u || c->poolMinWaves == 0;
     const uint64_t minWaves = c->poolMinWaves != 65000u ? c->poolMinWaves : (c->jobCostValid ? 43000u : 65000u);
-    L.pool = c->usePool && c->hScene.ref16ok && (uint64_t)c->tileCount * L.windows >= minWaves && (c->poolMinWaves == 0 || L.nf > 64u);
+    L.pool = c->usePool && poolByDefault && pool_can_run(c, L.nf) && (uint64_t)c->tileCount * L.windows >= minWaves && (c->poolMinWaves == 0 || L.nf > 64u);
     if (L.nf > 64u && c->jobCostValid) {
         if ((r = install_job_plan(c, L.windows, L.nf, L.pool))) return r;
         // The plan is a MODEL (machine time within ~15 %): for a job shape that repeats (a progressive render) it is checked by measurement — the first launch of the
@@ -1686,6 +1714,8 @@ static int planner_prepare(crt_ctx* c, Launch& L)
         const uint32_t perWave = L.pool ? std::max(crt_pool_streams(L.nf), L.waveFrames) : 64u;
         c->recWaves = L.pool ? c->tileCount * ((L.nf + perWave - 1u) / perWave) : c->tileCount * L.windows;
         c->recResident = L.pool ? 4096u : 5120u;                            // 4 / 5 wavefronts per SIMD (render_pool_kernel / render_tiles_kernel)
+        if (L.pool && c->hScene.poolRefBits == 32u)                         // the 32-bit-reference form: what its LDS leaves of those 4 (160 KiB per CU of 4 SIMDs)
+            c->recResident = 256u * std::min(16u, (160u * 1024u) / std::max(1u, pool_lds_need(c, L.nf)));
     }
     return 0;
 }
@@ -1720,7 +1750,7 @@ static hipError_t launch_render_kernels(crt_ctx* c, const Launch& L)
             le = crt_launch_render_pool(&c->hScene, L.slab, scratch, c->dCounters, c->dTileClocks, c->dTileOrder, c->tileFirst, c->tileStride, c->tileCount, (uint32_t)c->tilesX,
                                         L.sppFirst, L.nf, L.passes, c->cfg.collectStats, L.jobBlocks ? L.head : 0u, L.waveFrames, L.waveTab, L.waveBlocks, L.longFrames,
                                         L.wantJobCost ? c->dJobCost : nullptr, L.jobClk,
-                                        (c->classDirty || hook("CRT_DEBUG_NO_TILE_CLASS")) ? nullptr : c->dTileClass /* tests / A-B: the kernel without the table */, st2);
+                                        (c->classDirty || hook("CRT_DEBUG_NO_TILE_CLASS")) ? nullptr : c->dTileClass /* tests / A-B: the kernel without the table */, c->extraLds, st2);
         if (le == hipSuccess) c->lastLongWaves = L.longWaves;
         if (L.jobBlocks && le == hipSuccess) le = join(st2);
     } else if (L.jobBlocks) {
@@ -2573,7 +2603,7 @@ int crt_update_transforms_device(crt_ctx* c, const float* d_T, uint32_t blasCoun
     // the commit copy of an earlier call may still be reading on another stream — all behind sceneReady, so it waits for that alone, not for earlier renders or queries.
     if ((r = wait_scene(c, st))) return r;
     if (g_hooks) HIPCK(c, hipEventRecord(B.t0, st));
-    HIPCK(c, crt_launch_tlas_build(c->hScene.geom, (uint32_t)f.instOff, d_T, c->dRootBox, N, (uint32_t)(f.tlasPairOff - f.tlasOff), (uint32_t)(f.instOff - f.tlasOff), B.dBuild, st));
+    HIPCK(c, crt_launch_tlas_build(c->hScene.geom, (uint32_t)f.instOff, d_T, c->dRootBox, N, (uint32_t)(f.tlasPairOff - f.tlasOff), (uint32_t)(f.instOff - f.tlasOff), c->hScene.poolRefBits, B.dBuild, st));
     if (g_hooks) { HIPCK(c, hipEventRecord(B.t1, st)); B.timed = true; }
     // the one host wait: the root's pair and the stack depth travel in the kernel arguments of every later launch, and only a build that passed is committed
     if ((r = read_back(c, st, B.back, B.hBack, B.dBuild, backBytes))) return r;
@@ -3035,6 +3065,17 @@ int crt_get_tile_clocks(crt_ctx* c, uint64_t* out)
 
 // diagnostic builds (-DCRT_STAMPS) only: 16 extra words per tile behind the tile clocks (not part of the public ABI)
 // tests: HIP timing events currently held by the context (bounded: completed launches are folded into totals, see fold_completed)
+// LDS bytes one render_pool_kernel wavefront of a launch of `frames` frames on the current scene asks for, the per-workgroup limit it is held to, and the width of
+// the scene's pool references (0: none).  -1: no context / no scene.
+extern "C" int crt_debug_pool_lds(crt_ctx* c, uint32_t frames, uint32_t* bytes, uint32_t* limit, uint32_t* refBits)
+{
+    if (!c || !c->haveScene) return -1;
+    if (!c->poolLdsLimit) c->poolLdsLimit = crt_pool_lds_limit(c->cfg.device);
+    if (bytes) *bytes = c->hScene.poolRefBits ? pool_lds_need(c, frames) : 0u;
+    if (limit) *limit = c->poolLdsLimit;
+    if (refBits) *refBits = c->hScene.poolRefBits;
+    return 0;
+}
 extern "C" int crt_debug_live_events(crt_ctx* c) { return c ? (int)(2 * (c->evRender.size() + c->evAcc.size() + c->evPool.size())) : -1; }
 
 // tests: the device's short reciprocals (dev_common.h rcp_exact*) against the IEEE division over all 2^32 inputs; out[4] = {inputs, differences x 3}

@@ -36,8 +36,10 @@ size_t crt_pool_scratch_bytes_per_window(uint32_t tileCount);
 hipError_t crt_launch_render_pool(const crt::Scene* sc, void* slab, void* facScratch, crt::Counters* counters, unsigned long long* tileClocks, const uint32_t* tileOrder, uint32_t tileFirst,
     uint32_t tileStride, uint32_t tileCount, uint32_t tilesX, uint32_t sppFirst, uint32_t frames, uint32_t passes, int collectStats, uint32_t rankFirst, uint32_t waveFrames,
     const uint32_t* waveTab, uint32_t tabBlocks, uint32_t longFrames, uint32_t* tileCost, unsigned long long* launchClk,
-    const uint8_t* tileClass /* one byte per local tile (layout.h kTileNo*), or nullptr: every test runs */, hipStream_t stream);
-uint32_t crt_pool_lds_bytes(uint32_t stackDepth, uint32_t streams);
+    const uint8_t* tileClass /* one byte per local tile (layout.h kTileNo*), or nullptr: every test runs */, uint32_t extraLds /* unused LDS bytes per wavefront on top (tests) */,
+    hipStream_t stream);
+uint32_t crt_pool_lds_bytes(uint32_t stackDepth, uint32_t streams, uint32_t refBits /* Scene::poolRefBits: 16 or 32 */);
+uint32_t crt_pool_lds_limit(int device);
 int crt_debug_pool_stamps(unsigned long long* out, int reset);
 int crt_debug_pool_density(unsigned long long* out, int reset);
 size_t crt_debug_pool_timeline(unsigned long long* out, size_t cap);
@@ -80,8 +82,8 @@ hipError_t crt_launch_grid_fill(const float* pos, uint32_t triCount, const crt::
     uint32_t total, const char* geom, uint32_t leafOff, uint32_t triBase, int globalIdx, crt::AltTri* tris, uint32_t maxBlocks, hipStream_t stream);
 
 // ---- tlas_build.hip ----
-hipError_t crt_launch_tlas_build(const char* geom, uint32_t instOff, const float* T, const float* rootBox, uint32_t blasCount, uint32_t pairRel, uint32_t instRel, void* out,
-    hipStream_t stream);
+hipError_t crt_launch_tlas_build(const char* geom, uint32_t instOff, const float* T, const float* rootBox, uint32_t blasCount, uint32_t pairRel, uint32_t instRel, uint32_t poolRefBits,
+    void* out, hipStream_t stream);
 
 // abi.cpp's test switch CRT_DEBUG_QUERY_GRID=<k>: an upper bound on the workgroups of a persistent query launch (0: none).  Host side only: each wrapper passes its grid through it.
 uint32_t crt_debug_query_grid(void);

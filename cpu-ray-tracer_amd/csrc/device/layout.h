@@ -29,17 +29,30 @@ constexpr uint32_t kRefDone = 0u;
 constexpr uint32_t kRefOffsetMask = 0x3fffffffu;
 constexpr uint64_t kMaxGeomBytes = 1ull << 32;     // 32-bit byte offsets
 
-// 16-bit form of the same reference (`ref16`), used by render_pool_kernel for `cur` and for its traversal stack (2 bytes per entry: LDS is
-// what limits the waves per SIMD): the same tags in bits 15..14 and a record INDEX in bits 13..0 instead of an offset
+// Pool form of the same reference, used by render_pool_kernel for `cur` and for its traversal stack: the same tags and a record INDEX instead of an offset.
+// It comes in two widths, and a scene is uploaded in exactly one of them (Scene::poolRefBits); both are stored in the same uint32_t fields (NodeChild::ref16,
+// TlasNode::ref16, Instance::rootRef16, Scene::rootRef16 — the names are the narrow form's).
+//   16-bit form (2 bytes per stack entry: LDS is what limits the waves per SIMD): tag in bits 15..14, index in bits 13..0, return marker 0xFFFF.
+//               Scenes of <= 16383 node pairs and < 16383 triangles over all BVHs.
+//   32-bit form (4 bytes per stack entry): tag in bits 31..30, index in bits 29..0, return marker 0xFFFFFFFF.  Every other scene: an index is bounded by
+//               kMaxGeomBytes (index * 64 and leafOff + index * 48 stay below 2^32), far below 2^30.
+// The tags and what the index counts, in either width:
 //   10 : BVH / BLAS interior, index of its NodePair                 (record at            index * 64)
-//   00 : BVH / BLAS leaf,     index of its first LeafTri + 1; 0 = "traversal done"   (record at leafOff + (index - 1) * 48; the next triangle of the leaf is ref16 + 1)
+//   00 : BVH / BLAS leaf,     index of its first LeafTri + 1; 0 = "traversal done"   (record at leafOff + (index - 1) * 48; the next triangle of the leaf is ref + 1)
 //   01 : TLAS interior,       index of its TLAS child pair         (record at tlasPairOff + index * 64)
-//   11 : TLAS leaf,           BLAS (Instance) index                (record at instOff + index * 128);  0xFFFF = "return to TLAS level" marker
-// Scene::ref16ok tells whether the scene fits (<= 16383 node pairs and < 16383 triangles over all BVHs); otherwise the host launches render_tiles_kernel.
+//   11 : TLAS leaf,           BLAS (Instance) index                (record at instOff + index * 128);  all ones = "return to TLAS level" marker
 constexpr uint32_t kRef16Interior = 0x8000u, kRef16TlasBit = 0x4000u, kRef16TlasLeaf = 0xC000u, kRef16TagMask = 0xC000u, kRef16IndexMask = 0x3fffu;
 constexpr uint32_t kRef16Return = 0xFFFFu, kRef16MaxIndex = 0x3ffeu;
+constexpr uint32_t kRefWideMaxIndex = 0x3ffffffeu;
+// the constants of one width, for the writers of those fields (by the scene's poolRefBits) and for the kernel (by its template parameter)
+struct PoolRefForm { uint32_t interior, tlasBit, tlasLeaf, tagMask, indexMask, ret; };
+constexpr PoolRefForm pool_ref_form(uint32_t bits)
+{
+    return bits == 32u ? PoolRefForm{kRefInterior, kRefTlasBit, kRefTlasLeaf, 0xC0000000u, kRefOffsetMask, kRefReturn}
+                       : PoolRefForm{kRef16Interior, kRef16TlasBit, kRef16TlasLeaf, kRef16TagMask, kRef16IndexMask, kRef16Return};
+}
 
-struct alignas(16) NodeChild { float lo[3]; uint32_t ref; float hi[3]; uint32_t ref16; };   // 32 B; ref / ref16 = the child's packed reference, 32- and 16-bit form
+struct alignas(16) NodeChild { float lo[3]; uint32_t ref; float hi[3]; uint32_t ref16; };   // 32 B; ref / ref16 = the child's packed reference: offset form, pool form
 struct alignas(64) NodePair { NodeChild c[2]; };                                           // 64 B
 
 struct alignas(16) LeafTri {              // 48 B = 3 offset units
@@ -54,12 +67,12 @@ struct alignas(16) ShadeTri {             // 64 B
     int32_t mat;                          // index into Scene::mats ([0] light, [1] floor, 2.. scene materials)
 };
 
-struct alignas(16) TlasNode { float lo[3]; uint32_t ref; float hi[3]; uint32_t ref16; };       // 32 B; ref / ref16 = packed reference of THIS node
+struct alignas(16) TlasNode { float lo[3]; uint32_t ref; float hi[3]; uint32_t ref16; };       // 32 B; ref / ref16 = packed reference of THIS node: offset form, pool form
 
 struct alignas(16) Instance {             // 128 B
     float invT[12];                       // rows 0..2 of BLASBVH::invT (ray -> object space)
     uint32_t shadeBase;                   // first ShadeTri of this BLAS (find_nearest reports triIdx = shadeIdx - shadeBase)
-    uint32_t rootRef16;                   // 16-bit reference of the BLAS's node 0
+    uint32_t rootRef16;                   // pool-form reference of the BLAS's node 0
     uint32_t rootRef;                     // packed reference of the BLAS's node 0
     int32_t objIdx;
     float T[12];                          // rows 0..2 of BLASBVH::T    (normal -> world space)
@@ -91,7 +104,7 @@ struct Scene {                            // passed to the kernels BY VALUE (ker
     const char* geom;                     // pairs | leaf tris | TLAS nodes | instances | shade records
     uint32_t tlasOff, instOff, shadeOff;  // byte offsets of those sections inside geom
     uint32_t leafOff, tlasPairOff;        // ... of the leaf triangles and of the TLAS child pairs (NodePair layout: the two child TlasNodes of every TLAS interior node side by side)
-    uint32_t rootRef16, ref16ok;          // 16-bit form of rootRef; 1: every reference of the scene has a 16-bit form (render_pool_kernel can run)
+    uint32_t rootRef16, poolRefBits;      // pool form of rootRef; the width the scene's pool references are written in: 16, 32, or 0 = none (render_pool_kernel cannot run)
     const uint32_t* texels;
     const Material* mats;
     uint32_t rootRef;                     // packed reference of the root (BVH node 0 / TLAS node 0)

@@ -51,6 +51,9 @@ constexpr uint32_t kQueueMask = 127u;                            // queues are r
 #ifndef CRT_POOL_MIN_WAVES
 #define CRT_POOL_MIN_WAVES 4         // waves per SIMD the register budget must allow (<= 128 VGPRs)
 #endif
+#ifndef CRT_POOL_WIDE_MIN_WAVES
+#define CRT_POOL_WIDE_MIN_WAVES 4    // ... of the 32-bit-reference form (LDS allows 3 - 4: DESIGN.md 3a)
+#endif
 #ifndef CRT_POOL_SHADE_MIN
 #define CRT_POOL_SHADE_MIN 64     // streams a shading pass waits for ...
 #endif
@@ -110,8 +113,9 @@ __device__ __forceinline__ uint64_t finite3_mask(f3 v)
 }
 __device__ __forceinline__ uint32_t rank_in(uint64_t m) { return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u)); }   // set bits below this lane
 
-template <int KIND, bool COUNT, int S>
-__global__ __launch_bounds__(64, CRT_POOL_MIN_WAVES) void render_pool_kernel(const Scene sc, float4* __restrict__ slab, float* __restrict__ facScratch, Counters* __restrict__ counters,
+// REFBITS: the width of the scene's pool references (layout.h: 16 or 32) — of `cur`, of the stack entries and of the constants that classify them
+template <int KIND, bool COUNT, int S, int REFBITS = 16>
+__global__ __launch_bounds__(64, REFBITS == 32 ? CRT_POOL_WIDE_MIN_WAVES : CRT_POOL_MIN_WAVES) void render_pool_kernel(const Scene sc, float4* __restrict__ slab, float* __restrict__ facScratch, Counters* __restrict__ counters,
                                                              unsigned long long* __restrict__ tileClocks, const uint32_t* __restrict__ tileOrder,
                                                              uint32_t tileFirst, uint32_t tileStride, uint32_t tileCount, uint32_t tilesX,
                                                              uint32_t sppFirst, uint32_t frames, uint32_t passes, uint32_t groups, uint32_t waveFrames, const uint32_t* __restrict__ waveTab, uint32_t tabBlocks, uint32_t longFrames,
@@ -158,19 +162,23 @@ __global__ __launch_bounds__(64, CRT_POOL_MIN_WAVES) void render_pool_kernel(con
     const char* __restrict__ geom = sc.geom;
     float* __restrict__ fac = facScratch + (size_t)blockIdx.x * (15u * (uint32_t)S);
 
-    // `cur` and the stack entries of this kernel are 16-bit references (layout.h: ref16 — the children's are stored next to the 32-bit ones in
-    // every NodePair); 2 bytes per stack entry instead of 4 is what lets 128 parked streams + the stacks fit 4 waves per SIMD.
-    // Traversal stack of the stream resident in a lane: entry i (1 .. stackDepth) at LDS byte  2 * lane + 128 * i;  entry 0 is a dummy below the bottom, so the
-    // speculative read of the top and the dead store above it need no bounds logic, and the stack pointer IS the byte address of the top entry (`spB`).
+    // `cur` and the stack entries of this kernel are pool references (layout.h: ref16 — the children's are stored next to the offset form in every
+    // NodePair), REFBITS wide.  A scene that fits the 16-bit form gets 2 bytes per stack entry instead of 4, which is what lets 128 parked streams + the stacks
+    // fit 4 waves per SIMD; every other scene is in the 32-bit form: 4 bytes per entry, a wave per SIMD less on deep trees, the same walk.
+    // Traversal stack of the stream resident in a lane: entry i (1 .. stackDepth) at LDS byte  kEntryB * lane + kLevelB * i;  entry 0 is a dummy below the bottom, so
+    // the speculative read of the top and the dead store above it need no bounds logic, and the stack pointer IS the byte address of the top entry (`spB`).
+    constexpr PoolRefForm R = pool_ref_form((uint32_t)REFBITS);
+    using StackEntry = std::conditional_t<REFBITS == 32, uint32_t, uint16_t>;
+    constexpr uint32_t kEntryB = (uint32_t)sizeof(StackEntry), kLevelB = 64u * kEntryB;   // bytes per entry, per stack level of the wavefront
     char* const ldsB = reinterpret_cast<char*>(lds);
-    const uint32_t laneB = lane * 2u;
-    uint32_t* st = lds + (sc.stackDepth + 1u) * 32u;                             // parked stream state (behind (stackDepth + 1) * 64 two-byte entries)
+    const uint32_t laneB = lane * kEntryB;
+    uint32_t* st = lds + (sc.stackDepth + 1u) * (kLevelB / 4u);                  // parked stream state (behind (stackDepth + 1) * 64 stack entries)
     float* stf = reinterpret_cast<float*>(st);
     uint8_t* qEnd = reinterpret_cast<uint8_t*>(st + F_COUNT * S);
     uint8_t* qBnc = qEnd + 128, * qRdy = qEnd + 256;
     uint16_t* slotFrame = reinterpret_cast<uint16_t*>(qEnd + 384);               // S > 64 only: frame (relative to frame0) of the stream in each slot
-    auto stk_top = [&](uint32_t at) -> uint32_t { return *reinterpret_cast<const uint16_t*>(ldsB + at); };
-    auto stk_put = [&](uint32_t at, uint32_t v) { *reinterpret_cast<uint16_t*>(ldsB + at) = (uint16_t)v; };
+    auto stk_top = [&](uint32_t at) -> uint32_t { return *reinterpret_cast<const StackEntry*>(ldsB + at); };
+    auto stk_put = [&](uint32_t at, uint32_t v) { *reinterpret_cast<StackEntry*>(ldsB + at) = (StackEntry)v; };
 
     Cnt cn; cn.rays = cn.primary = cn.interior = cn.leaf = cn.tri = cn.tlas = cn.visits = cn.meshhits = 0;
     uint32_t trips = 0;
@@ -249,7 +257,7 @@ __global__ __launch_bounds__(64, CRT_POOL_MIN_WAVES) void render_pool_kernel(con
                 ncur = o.hitN ? o.nearRef : kRefDone;
                 if (COUNT) { if (KIND == 0) cn.interior++; else cn.tlas++; }
             } else ncur = sc.rootRef16;
-            if (COUNT && KIND == 0 && (ncur & kRef16TagMask) == 0u && ncur != kRefDone) cn.leaf++;
+            if (COUNT && KIND == 0 && (ncur & R.tagMask) == 0u && ncur != kRefDone) cn.leaf++;
             if (!sky) {
                 stf[F_OX * S + s] = O.x; stf[F_OY * S + s] = O.y; stf[F_OZ * S + s] = O.z;
                 stf[F_RX * S + s] = rD.x; stf[F_RY * S + s] = rD.y; stf[F_RZ * S + s] = rD.z;
@@ -290,26 +298,26 @@ __global__ __launch_bounds__(64, CRT_POOL_MIN_WAVES) void render_pool_kernel(con
     auto node_step = [&](uint64_t m) {
         const bool allFinite = (m & ~mFinite) == 0ull;
         if (lane_in(m)) {
-            if (COUNT) { if (KIND == 1 && (cur & kRef16TlasBit) != 0u) cn.tlas++; else cn.interior++; }
+            if (COUNT) { if (KIND == 1 && (cur & R.tlasBit) != 0u) cn.tlas++; else cn.interior++; }
             const uint32_t top = stk_top(spB);                               // speculative: lands during the slab arithmetic (the dummy entry when the stack is empty)
             float d1, d2;
             if (__builtin_expect(allFinite, 1)) { d1 = box_fast(q0, q1, tO, trD, h.t); d2 = box_fast(q2, q3, tO, trD, h.t); }
             else { d1 = box_exact(q0, q1, tO, trD, h.t); d2 = box_exact(q2, q3, tO, trD, h.t); }
             const Ordered o = ordered_step(d1, d2, asu(q1.w), asu(q3.w));    // the children's ref16
-            stk_put(spB + 128u, o.farRef);                                   // dead store unless `push`
+            stk_put(spB + kLevelB, o.farRef);                                   // dead store unless `push`
             const bool pop = !o.hitN && spB != laneB;
             cur = o.hitN ? o.nearRef : (pop ? top : kRefDone);
-            spB = spB + (o.push ? 128u : 0u) - (pop ? 128u : 0u);
-            if (COUNT && (cur & kRef16TagMask) == 0u && cur != kRefDone) cn.leaf++;
+            spB = spB + (o.push ? kLevelB : 0u) - (pop ? kLevelB : 0u);
+            if (COUNT && (cur & R.tagMask) == 0u && cur != kRefDone) cn.leaf++;
         }
     };
-    // where the record of `cur` lies in geom: record offset of a 16-bit reference = index * record size + section base (layout.h)
+    // where the record of `cur` lies in geom: record offset of a pool reference = index * record size + section base (layout.h)
     auto record_offset = [&]() -> uint32_t {
-        const uint32_t idx = cur & kRef16IndexMask;
-        const bool inter = (cur & kRef16Interior) != 0u;
+        const uint32_t idx = cur & R.indexMask;
+        const bool inter = (cur & R.interior) != 0u;
         uint32_t oa = idx * (inter ? 64u : 48u) + (inter ? 0u : sc.leafOff - 48u);             // NodePair | LeafTri (one multiply-add on selected operands: no divergent arms)
-        if (KIND == 1 && (cur & kRef16TlasBit) != 0u)
-            oa = (cur & kRef16Interior) ? sc.instOff + idx * 128u : sc.tlasPairOff + idx * 64u;   // TLAS leaf: Instance {invT rows, ids} | TLAS interior: its child pair
+        if (KIND == 1 && (cur & R.tlasBit) != 0u)
+            oa = (cur & R.interior) ? sc.instOff + idx * 128u : sc.tlasPairOff + idx * 64u;   // TLAS leaf: Instance {invT rows, ids} | TLAS interior: its child pair
         return oa;
     };
     // the record of `cur` into q0..q3 for the lanes in m (the others keep theirs)
@@ -328,8 +336,8 @@ __global__ __launch_bounds__(64, CRT_POOL_MIN_WAVES) void render_pool_kernel(con
             const bool more = asu(q2.w) > 1u;                                // the leaf's next LeafTri is the next index
             const bool pop = !more && spB != laneB;
             const uint32_t next = more ? cur + 1u : (pop ? top : kRefDone);
-            spB -= pop ? 128u : 0u;
-            if (COUNT && !more && (next & kRef16TagMask) == 0u && next != kRefDone) cn.leaf++;
+            spB -= pop ? kLevelB : 0u;
+            if (COUNT && !more && (next & R.tagMask) == 0u && next != kRefDone) cn.leaf++;
             cur = next;
         }
     };
@@ -341,10 +349,10 @@ __global__ __launch_bounds__(64, CRT_POOL_MIN_WAVES) void render_pool_kernel(con
         CRT_PSTAMP(p0);
         if (mRes != 0ull) {
             // ---------------- D. walk: the phases of the resident streams (TLAS leaf / NODE / TRI), on the records loaded by the previous trip ----------------
-            // what each resident lane is at, from its 16-bit reference: 10 = BVH interior, 00 = leaf triangle (never 0 here), 01 = TLAS interior, 11 = TLAS leaf
+            // what each resident lane is at, from its pool reference: 10 = BVH interior, 00 = leaf triangle (never 0 here), 01 = TLAS interior, 11 = TLAS leaf
             uint64_t mNode, mTlas = 0ull;
-            if (KIND == 0) mNode = mRes & __builtin_amdgcn_ballot_w64(cur > 0x7fffu);
-            else { mTlas = mRes & __builtin_amdgcn_ballot_w64(cur >= kRef16TlasLeaf); mNode = mRes & __builtin_amdgcn_ballot_w64(cur - kRef16TlasBit < 0x8000u); }
+            if (KIND == 0) mNode = mRes & __builtin_amdgcn_ballot_w64(cur > R.interior - 1u);
+            else { mTlas = mRes & __builtin_amdgcn_ballot_w64(cur >= R.tlasLeaf); mNode = mRes & __builtin_amdgcn_ballot_w64(cur - R.tlasBit < R.interior); }
             const uint64_t mTri = mRes & ~(mNode | mTlas);
             // The record loads issued at the end of the previous trip are first needed here.  Naming all four tuples in one
             // empty asm keeps the register allocator from splitting a loaded tuple across the back-edge.
@@ -361,9 +369,9 @@ __global__ __launch_bounds__(64, CRT_POOL_MIN_WAVES) void render_pool_kernel(con
                     const f3 O = mk3(stf[F_OX * S + sid], stf[F_OY * S + sid], stf[F_OZ * S + sid]);
                     const f3 D = mk3(stf[F_DX * S + sid], stf[F_DY * S + sid], stf[F_DZ * S + sid]);
                     to_object_space(q0, q1, q2, O, D, tO, tD, trD);
-                    spB += 128u; stk_put(spB, kRef16Return);
+                    spB += kLevelB; stk_put(spB, R.ret);
                     const uint32_t next = asu(q3.y);                                 // Instance::rootRef16
-                    if (COUNT && (next & kRef16TagMask) == 0u && next != kRefDone) cn.leaf++;
+                    if (COUNT && (next & R.tagMask) == 0u && next != kRefDone) cn.leaf++;
                     cur = next;
                 }
                 mFinite = (mFinite & ~mTlas) | (mTlas & finite3_mask(trD));
@@ -377,9 +385,9 @@ __global__ __launch_bounds__(64, CRT_POOL_MIN_WAVES) void render_pool_kernel(con
 #pragma unroll
             for (int rep = 1; rep < CRT_POOL_NODE_STEPS; rep++) {
                 const uint64_t mStepped = rep == 1 ? mNode : mNode2;
-                mNode2 = mStepped & (KIND == 0 ? __builtin_amdgcn_ballot_w64(cur > 0x7fffu) : __builtin_amdgcn_ballot_w64(cur - kRef16TlasBit < 0x8000u));
+                mNode2 = mStepped & (KIND == 0 ? __builtin_amdgcn_ballot_w64(cur > R.interior - 1u) : __builtin_amdgcn_ballot_w64(cur - R.tlasBit < R.interior));
                 if ((uint32_t)__popcll(mNode2) < (uint32_t)CRT_POOL_NODE2_MIN) { mNode2 = 0ull; break; }
-                const uint64_t mLeaf = mStepped & __builtin_amdgcn_ballot_w64((cur & kRef16TagMask) == 0u) & ~__builtin_amdgcn_ballot_w64(cur == kRefDone);
+                const uint64_t mLeaf = mStepped & __builtin_amdgcn_ballot_w64((cur & R.tagMask) == 0u) & ~__builtin_amdgcn_ballot_w64(cur == kRefDone);
                 load_records(mNode2 | mLeaf);
                 mLeafNow |= mLeaf;
                 CRT_DENS(28, 1); CRT_DENS(29, __popcll(mNode2));
@@ -394,14 +402,14 @@ __global__ __launch_bounds__(64, CRT_POOL_MIN_WAVES) void render_pool_kernel(con
             if (mTriAll != 0ull) tri_step(mTriAll);
             if (KIND == 1) {
                 // a popped return marker: the BLAS is finished — back to the world-space ray, pop the TLAS entry below (rare: once per BLAS visit)
-                mBack = (mNode | mTriRan) & __builtin_amdgcn_ballot_w64(cur == kRef16Return);
+                mBack = (mNode | mTriRan) & __builtin_amdgcn_ballot_w64(cur == R.ret);
                 if (mBack != 0ull) {
                     if (lane_in(mBack)) {
                         world_ray();
                         const bool pop = spB != laneB;
                         const uint32_t top = stk_top(spB);
-                        cur = pop ? top : kRefDone; spB -= pop ? 128u : 0u;
-                        if (COUNT && (cur & kRef16TagMask) == 0u && cur != kRefDone) cn.leaf++;
+                        cur = pop ? top : kRefDone; spB -= pop ? kLevelB : 0u;
+                        if (COUNT && (cur & R.tagMask) == 0u && cur != kRefDone) cn.leaf++;
                     }
                     mFinite = (mFinite & ~mBack) | (mBack & finite3_mask(trD));
                 }
@@ -453,8 +461,8 @@ __global__ __launch_bounds__(64, CRT_POOL_MIN_WAVES) void render_pool_kernel(con
                     metaLo = meta & kMetaLowMask;
                     cur = st[F_CUR * S + sid];
                     const uint32_t pend = st[F_PEND * S + sid];
-                    stk_put(laneB + 128u, pend);                                     // a dead store unless the far root child was hit
-                    spB = laneB + (pend ? 128u : 0u);
+                    stk_put(laneB + kLevelB, pend);                                     // a dead store unless the far root child was hit
+                    spB = laneB + (pend ? kLevelB : 0u);
                 }
                 mFinite = (mFinite & ~mTake) | (mTake & finite3_mask(trD));
                 mRes |= mTake;
@@ -697,9 +705,21 @@ extern "C" uint32_t crt_pool_streams(uint32_t frames) { return frames > 64u ? (u
 #ifndef CRT_POOL_EXTRA_LDS
 #define CRT_POOL_EXTRA_LDS 0       // occupancy experiments only: unused LDS bytes per wavefront
 #endif
-// LDS of one wavefront: traversal stacks ((stackDepth + 1 dummy) two-byte entries per lane) + parked stream state + the three one-byte ring queues
-// + (more slots than lanes: wavefronts that may refill) the two-byte frame of every slot.  128 slots at a stack depth of <= 17: <= 10 240 bytes, 16 wavefronts per CU.
-extern "C" uint32_t crt_pool_lds_bytes(uint32_t stackDepth, uint32_t streams) { return (stackDepth + 1u) * 64u * 2u + crt::F_COUNT * streams * 4u + 3u * 128u + (streams > 64u ? 2u * streams : 0u) + (uint32_t)CRT_POOL_EXTRA_LDS; }
+// LDS of one wavefront: traversal stacks ((stackDepth + 1 dummy) entries of refBits / 8 bytes per lane) + parked stream state + the three one-byte ring queues
+// + (more slots than lanes: wavefronts that may refill) the two-byte frame of every slot.  128 slots, 16-bit references, at a stack depth of <= 17: <= 10 240 bytes,
+// 16 wavefronts per CU; 32-bit references add (stackDepth + 1) * 128 bytes.
+extern "C" uint32_t crt_pool_lds_bytes(uint32_t stackDepth, uint32_t streams, uint32_t refBits) { return (stackDepth + 1u) * 64u * (refBits / 8u) + crt::F_COUNT * streams * 4u + 3u * 128u + (streams > 64u ? 2u * streams : 0u) + (uint32_t)CRT_POOL_EXTRA_LDS; }
+// the most LDS a pool wavefront may ask for: what the device grants one workgroup, and never more than the 64 KiB that bound the other render kernels' stacks (abi.cpp)
+extern "C" uint32_t crt_pool_lds_limit(int device)
+{
+    static uint32_t known[64] = {};                                             // asked once per device (the launch wrapper checks every launch against it)
+    if (device >= 0 && device < 64 && known[device]) return known[device];
+    int v = 0;
+    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, device) != hipSuccess || v <= 0) { (void)hipGetLastError(); return 0u; }
+    const uint32_t limit = (uint32_t)v < 64u * 1024u ? (uint32_t)v : 64u * 1024u;
+    if (device >= 0 && device < 64) known[device] = limit;
+    return limit;
+}
 // bytes of throughput-factor scratch a launch of `windows` 64-frame windows needs behind its sample slab (15 floats per stream; a wave's
 // group of streams may reach past the last window, hence 128 stream slots per window)
 extern "C" size_t crt_pool_scratch_bytes_per_window(uint32_t tileCount) { return (size_t)tileCount * 128u * 15u * 4u; }
@@ -732,10 +752,10 @@ extern "C" size_t crt_debug_pool_timeline(unsigned long long* out, size_t cap)  
 extern "C" hipError_t crt_launch_render_pool(const crt::Scene* sc, void* slab, void* facScratch, crt::Counters* counters, unsigned long long* tileClocks, const uint32_t* tileOrder,
                                              uint32_t tileFirst, uint32_t tileStride, uint32_t tileCount, uint32_t tilesX, uint32_t sppFirst,
                                              uint32_t frames, uint32_t passes, int collectStats, uint32_t rankFirst, uint32_t waveFrames, const uint32_t* waveTab, uint32_t tabBlocks, uint32_t longFrames,
-                                             uint32_t* tileCost, unsigned long long* launchClk, const uint8_t* tileClass, hipStream_t stream)
+                                             uint32_t* tileCost, unsigned long long* launchClk, const uint8_t* tileClass, uint32_t extraLds, hipStream_t stream)
 {
     if (tileCount == 0 || frames == 0) return hipSuccess;
-    if (!sc->ref16ok) return hipErrorInvalidValue;                              // the host launches render_tiles_kernel for such scenes
+    if (sc->poolRefBits != 16u && sc->poolRefBits != 32u) return hipErrorInvalidValue;   // a scene without pool references: the host launches render_tiles_kernel
     const uint32_t S = crt_pool_streams(frames);
     // frames per wavefront: S (waveFrames == 0), or a multiple of S, at most 0xff80 (the slots' 16-bit frames) — one for all tiles; or per rank from waveTab for the
     // frames [0, longFrames) (tabBlocks wavefronts in all) and S for the rest
@@ -752,12 +772,15 @@ extern "C" hipError_t crt_launch_render_pool(const crt::Scene* sc, void* slab, v
       if (cap < (size_t)grid.x) { if (buf) (void)hipFree(buf); (void)hipMalloc((void**)&buf, (size_t)grid.x * 24); cap = grid.x; (void)hipMemcpyToSymbol(HIP_SYMBOL(crt::g_poolTimeline), &buf, sizeof(buf)); }
       (void)hipMemsetAsync(buf, 0, (size_t)grid.x * 24, stream); g_timelineHost = buf; g_timelineCount = grid.x; }
 #endif
-    const uint32_t ldsBytes = crt_pool_lds_bytes(sc->stackDepth, S);
-#define CRT_LAUNCH(K, C, SS) hipLaunchKernelGGL((crt::render_pool_kernel<K, C, SS>), grid, block, ldsBytes, stream, *sc, (float4*)slab, (float*)facScratch, counters, tileClocks, tileOrder, tileFirst, tileStride, tileCount, tilesX, sppFirst, frames, passes, groups, wf, waveTab, tabBlocks, longFrames, rankFirst, tileCost, launchClk, tileClass)
+    const uint32_t ldsBytes = crt_pool_lds_bytes(sc->stackDepth, S, sc->poolRefBits) + extraLds;
+    { int dev = 0; if (hipGetDevice(&dev) != hipSuccess) return hipGetLastError(); if (ldsBytes > crt_pool_lds_limit(dev)) return hipErrorInvalidValue; }   // (the host routes such a scene to render_tiles_kernel)
+#define CRT_LAUNCH(K, C, SS) do { if (sc->poolRefBits == 32u) CRT_LAUNCH_R(K, C, SS, 32); else CRT_LAUNCH_R(K, C, SS, 16); } while (0)
+#define CRT_LAUNCH_R(K, C, SS, RB) hipLaunchKernelGGL((crt::render_pool_kernel<K, C, SS, RB>), grid, block, ldsBytes, stream, *sc, (float4*)slab, (float*)facScratch, counters, tileClocks, tileOrder, tileFirst, tileStride, tileCount, tilesX, sppFirst, frames, passes, groups, wf, waveTab, tabBlocks, longFrames, rankFirst, tileCost, launchClk, tileClass)
 #define CRT_LAUNCH_S(K, C) do { if (S == 64u) CRT_LAUNCH(K, C, 64); else CRT_LAUNCH(K, C, CRT_POOL_STREAMS); } while (0)
     if (sc->kind == 0) { if (collectStats) CRT_LAUNCH_S(0, true); else CRT_LAUNCH_S(0, false); }
     else { if (collectStats) CRT_LAUNCH_S(1, true); else CRT_LAUNCH_S(1, false); }
 #undef CRT_LAUNCH_S
 #undef CRT_LAUNCH
+#undef CRT_LAUNCH_R
     return hipGetLastError();
 }

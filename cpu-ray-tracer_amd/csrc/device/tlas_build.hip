@@ -64,18 +64,18 @@ __device__ __forceinline__ int tlas_partner(const TlasLds& s, int A, int n, uint
 
 // what the geometry buffer holds for TLAS node i (TlasNode / NodeChild layout): box + both forms of the node's reference.  Interior nodes number their child
 // pairs in node-index order, node 0 first (flatten_tlas): the interior nodes are node 0 and nodes n + 1 .. 2n - 1, so node i > 0 owns pair i - n.
-__device__ __forceinline__ void tlas_record(const TlasLds& s, uint32_t i, uint32_t n, row4* lo, row4* hi)
+__device__ __forceinline__ void tlas_record(const TlasLds& s, uint32_t i, uint32_t n, const PoolRefForm R, row4* lo, row4* hi)
 {
     const uint32_t lr = s.leftRight[i], blas = i ? i - 1u : 0u;
     const uint32_t ref = lr ? (kRefTlasInterior | (lr & 0x7fffu) | (((lr >> 16) & 0x7fffu) << 15)) : (kRefTlasLeaf | (blas & 0xffffu));
-    const uint32_t ref16 = lr ? (kRef16TlasBit | (i ? i - n : 0u)) : (kRef16TlasLeaf | (blas & kRef16IndexMask));
+    const uint32_t ref16 = lr ? (R.tlasBit | (i ? i - n : 0u)) : (R.tlasLeaf | (blas & R.indexMask));   // the pool form, in the scene's width
     *lo = row4{s.box[0][i], s.box[1][i], s.box[2][i], __uint_as_float(ref)};
     *hi = row4{s.box[3][i], s.box[4][i], s.box[5][i], __uint_as_float(ref16)};
 }
 
 // out: TlasBuildHeader, then the image (node section at 0, child pairs at pairRel, Instance records at instRel: the geometry buffer's offsets minus tlasOff)
 __global__ __launch_bounds__(kTlasLanes) void tlas_build_kernel(const char* __restrict__ geom, uint32_t instOff, const float* __restrict__ T, const float* __restrict__ rootBox,
-                                                                uint32_t n, uint32_t pairRel, uint32_t instRel, char* __restrict__ out)
+                                                                uint32_t n, uint32_t pairRel, uint32_t instRel, uint32_t poolRefBits, char* __restrict__ out)
 {
     __shared__ TlasLds s;
     const uint32_t lane = threadIdx.x;
@@ -150,24 +150,25 @@ __global__ __launch_bounds__(kTlasLanes) void tlas_build_kernel(const char* __re
     __syncthreads();
     row4* nodes = reinterpret_cast<row4*>(image);
     row4* pairs = reinterpret_cast<row4*>(image + pairRel);
+    const PoolRefForm R = pool_ref_form(poolRefBits);
     for (uint32_t i = lane; i < 2u * n; i += kTlasLanes) {
-        row4 lo, hi; tlas_record(s, i, n, &lo, &hi);
+        row4 lo, hi; tlas_record(s, i, n, R, &lo, &hi);
         nodes[2u * i] = lo; nodes[2u * i + 1u] = hi;
         const uint32_t lr = s.leftRight[i];
         if (!lr) continue;
         row4* p = pairs + 4u * (i ? i - n : 0u);
-        tlas_record(s, lr & 0xffffu, n, &p[0], &p[1]);
-        tlas_record(s, lr >> 16, n, &p[2], &p[3]);
+        tlas_record(s, lr & 0xffffu, n, R, &p[0], &p[1]);
+        tlas_record(s, lr >> 16, n, R, &p[2], &p[3]);
     }
     if (n == 1u && lane < 4u) pairs[lane] = row4{0.0f, 0.0f, 0.0f, 0.0f};        // the one pair slot of a single-instance scene stays empty
 }
 
 } // namespace crt
 
-extern "C" hipError_t crt_launch_tlas_build(const char* geom, uint32_t instOff, const float* T, const float* rootBox, uint32_t blasCount, uint32_t pairRel, uint32_t instRel, void* out,
-                                            hipStream_t stream)
+extern "C" hipError_t crt_launch_tlas_build(const char* geom, uint32_t instOff, const float* T, const float* rootBox, uint32_t blasCount, uint32_t pairRel, uint32_t instRel, uint32_t poolRefBits,
+                                            void* out, hipStream_t stream)
 {
     if (blasCount == 0u || blasCount > crt::kTlasMaxBlas) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(crt::tlas_build_kernel, dim3(1), dim3(crt::kTlasLanes), 0, stream, geom, instOff, T, rootBox, blasCount, pairRel, instRel, static_cast<char*>(out));
+    hipLaunchKernelGGL(crt::tlas_build_kernel, dim3(1), dim3(crt::kTlasLanes), 0, stream, geom, instOff, T, rootBox, blasCount, pairRel, instRel, poolRefBits, static_cast<char*>(out));
     return hipGetLastError();
 }

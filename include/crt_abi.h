@@ -143,7 +143,10 @@ void crt_destroy(crt_ctx* ctx);
 const char* crt_last_error(crt_ctx* ctx);                      /* ctx may be NULL: error of the last failed crt_create on this thread */
 
 /* ---- scene / camera (lower seam) -------------------------------------------------------------------- */
-int  crt_upload_scene(crt_ctx* ctx, const crt_scene_desc* scene);   /* flattens to the device layout and copies; host pointers are not kept */
+/* Flattens to the device layout and copies; host pointers are not kept.  The node references the stream-pool render kernel walks are written 16 bits wide
+ * when the scene has <= 16383 node pairs and < 16383 triangles over all its BVHs, 32 bits wide otherwise; the stream-pool kernel can render the scene either way
+ * (which kernel does: see crt_render), and the in-place writes (crt_update_scene, crt_refit_device, crt_update_transforms_device, crt_build_grid_device) keep the width. */
+int  crt_upload_scene(crt_ctx* ctx, const crt_scene_desc* scene);
 /* In-place update of an uploaded scene for animation (renderer.cpp:147 `animating`), same description as at upload, same topology:
  *   CRT_UPDATE_TRANSFORMS  two-level scenes: every BLAS's T / invT as BLASBVH::SetTransform left them (blas_bvh.cpp:363-374) and the node array of the
  *                          TLASBVH::Build that followed (tlas_bvh.cpp:17-55) — instance motion;
@@ -243,7 +246,13 @@ int  crt_set_camera(crt_ctx* ctx, const float camPos[3], const float topLeft[3],
  * (renderer.cpp:120,167) and adds passes samples per pixel into the accumulator in frame order.
  * Asynchronous: the call is cut into launches of up to cfg.maxFramesPerLaunch frames (one grid covers all their 64-frame windows);
  * launches rotate over cfg.renderStreams HIP streams and overlap with those of earlier crt_render calls; the accumulation order
- * is kept by events.  crt_sync / any read waits for everything. */
+ * is kept by events.  crt_sync / any read waits for everything.
+ * Which kernel renders a launch — same samples either way: a scene with 16-bit node references (crt_upload_scene) gets render_pool_kernel (128 RNG streams per
+ * wavefront) for launches of many windows and render_tiles_kernel (one stream per lane) for smaller ones.  A scene with 32-bit node references gets
+ * render_tiles_kernel at every size: the pool kernel's 32-bit instantiation (4-byte traversal-stack entries, (stack depth + 1) * 128 bytes more LDS per
+ * wavefront) renders it too, but measured no faster on the scene the default was decided on (faster on others: DESIGN.md section 5), and runs only where the diagnostic switch CRT_RENDER_KERNEL=pool_always asks for it.
+ * A scene whose pool wavefront would need more LDS than a workgroup may have is rendered by render_tiles_kernel whatever the switch says.
+ * crt_timing.pool_launches counts pool launches of either width. */
 int  crt_render(crt_ctx* ctx, uint32_t spp_first, uint32_t frames, uint32_t passes);
 int  crt_sync(crt_ctx* ctx);
 /* Optional: sizes the device-side sample-slab pool for an upcoming crt_render(.., frames, passes) now (allocating tens of GB takes
