@@ -30,12 +30,7 @@ __device__ __forceinline__ f3 cross3(f3 a, f3 b) { return mk3(a.y * b.z - a.z * 
 // step r + r * (1 - x * r), two fma, IS the correctly rounded quotient for every 2^-126 <= |x| <= 2^126 — compared with 1.0f / x over all
 // 4 227 858 434 such inputs on gfx950 (tools/microbench/exact_rcp.hip: 0 differences) — so results stay bit-identical.  If any active lane of the
 // wave holds another input (0, denormal, > 2^126, inf, NaN) the wave takes the IEEE division instead (a scalar branch: never if-converted).
-// (-DCRT_IEEE_DIV builds the IEEE sequence everywhere: the A/B switch of tools/ab_bench.py)
-#ifdef CRT_IEEE_DIV
-__device__ __forceinline__ float rcp_nr(float x) { return 1.0f / x; }
-#else
 __device__ __forceinline__ float rcp_nr(float x) { const float r = __builtin_amdgcn_rcpf(x); return __builtin_fmaf(__builtin_fmaf(-x, r, 1.0f), r, r); }
-#endif
 __device__ __forceinline__ float rcp_exact(float x)
 {
     float r = rcp_nr(x);
@@ -63,12 +58,8 @@ __device__ __forceinline__ f3 rcp_exact3(f3 v)
 // return x itself for +-0 and +inf.  For 2^-96 <= x < inf neither scaling nor the zero / infinity select does anything, and what is left is the sequence below, operation
 // for operation: the same bits by construction, and compared with __builtin_sqrtf over all 2^32 inputs on the device (crt_debug_check_sqrt, tests/test_gpu_pool_diet.py).
 // If any active lane of the wave holds another input (< 2^-96, zero, negative, inf, NaN) the wave takes the compiler's sequence instead (a scalar branch, as rcp_exact's).
-// (-DCRT_DIET_NO_SQRT builds the compiler's sequence everywhere)
 __device__ __forceinline__ float sqrt_exact(float x)
 {
-#ifdef CRT_DIET_NO_SQRT
-    return __builtin_sqrtf(x);
-#else
     const float s = __builtin_amdgcn_sqrtf(x);
     const float dn = __uint_as_float(__float_as_uint(s) - 1u), up = __uint_as_float(__float_as_uint(s) + 1u);
     const float rdn = __builtin_fmaf(-dn, s, x), rup = __builtin_fmaf(-up, s, x);
@@ -76,7 +67,6 @@ __device__ __forceinline__ float sqrt_exact(float x)
     r = (rup > 0.0f) ? up : r;
     if (__builtin_expect(__builtin_amdgcn_ballot_w64(__float_as_uint(x) - 0x0f800000u >= 0x70000000u) != 0, 0)) r = __builtin_sqrtf(x);   // !(2^-96 <= x < inf), as bit patterns: 0x0f800000 .. 0x7f7fffff
     return r;
-#endif
 }
 __device__ __forceinline__ f3 normalize3(f3 v) { float inv = rcp_exact(sqrt_exact(dot3(v, v))); return v * inv; }
 __device__ __forceinline__ float min_std(float a, float b) { return (b < a) ? b : a; }   // std::min(a,b)
@@ -191,17 +181,14 @@ __device__ __forceinline__ float crt_acosf_plain(float x)
 // GetSkyColor's angles of a direction (file_scene.cpp:142-154): phi = atan2(-D.z, D.x) + pi, theta = acos(-D.y).  A normalised finite direction almost never has a
 // component that is exactly zero, so the special-case selects of the two functions (compare + select pairs, half rate) sit behind ONE wave-uniform guard: the plain
 // forms when no active lane holds a special operand, the general functions for the whole wave otherwise (a scalar branch, as rcp_exact's).
-// (-DCRT_DIET_NO_SKY builds the general functions everywhere)
 __device__ __forceinline__ void sky_angles(f3 D, float& phi, float& theta)
 {
     const float y = -D.z, x = D.x, c = -D.y;
-#ifndef CRT_DIET_NO_SKY
     // a zero, an infinity or a NaN, as ONE unsigned compare of the bit pattern: (bits << 1) - 1 drops the sign and wraps +-0 to the top, so everything from inf
     // (0xff000000 - 1) upwards is special.  (The compare builtin returns the lane mask itself; the ballot of a v_cmp_class result goes through a VGPR.)
     const uint64_t special = __builtin_amdgcn_uicmp((asu(x) << 1) - 1u, 0xfeffffffu, 35 /* unsigned >= */) | __builtin_amdgcn_uicmp((asu(y) << 1) - 1u, 0xfeffffffu, 35)
                            | __builtin_amdgcn_ballot_w64(!(__builtin_fabsf(c) <= 1.0f));
     if (__builtin_expect(special == 0, 1)) { phi = crt_atan2f_plain(y, x) + CRT_PI; theta = crt_acosf_plain(c); return; }
-#endif
     phi = crt_atan2f(y, x) + CRT_PI; theta = crt_acosf(c);
 }
 
@@ -236,13 +223,10 @@ __device__ __forceinline__ rec4 ldg(const char* __restrict__ base, uint32_t byte
 // Piece PIECE (16 bytes) of the 64-byte record at byteOff, with the piece's constant distance in the load's immediate field (global_load_dwordx4 v, v_off, s[base:base+1]
 // offset:16) instead of a v_add_u32 per piece.  `byteOff + 16u` is 32-bit unsigned arithmetic that may wrap, which is what keeps the compiler from folding the constant;
 // it cannot wrap here, and the compiler is told so: every record is fetched as 64 bytes inside a buffer of at most kMaxGeomBytes = 2^32 bytes, so byteOff + 63 < 2^32.
-// (-DCRT_DIET_NO_RECPTR leaves the assumption out)
 static_assert(kMaxGeomBytes == (1ull << 32), "ldp: byteOff + 63 < 2^32");
 template <uint32_t PIECE> __device__ __forceinline__ rec4 ldp(const char* __restrict__ base, uint32_t byteOff)
 {
-#ifndef CRT_DIET_NO_RECPTR
     __builtin_assume(byteOff <= 0xffffffffu - 63u);
-#endif
     return ldg(base, byteOff + 16u * PIECE);
 }
 __device__ __forceinline__ bool finite3(f3 v)

@@ -54,9 +54,6 @@ constexpr uint32_t kQueueMask = 127u;                            // queues are r
 #ifndef CRT_POOL_WIDE_MIN_WAVES
 #define CRT_POOL_WIDE_MIN_WAVES 4    // ... of the 32-bit-reference form (LDS allows 3 - 4: DESIGN.md 3a)
 #endif
-#ifndef CRT_POOL_SHADE_MIN
-#define CRT_POOL_SHADE_MIN 64     // streams a shading pass waits for ...
-#endif
 #ifndef CRT_POOL_NODE_STEPS
 #define CRT_POOL_NODE_STEPS 2     // NODE steps per trip of the lanes that stay at interior nodes
 #endif
@@ -64,7 +61,7 @@ constexpr uint32_t kQueueMask = 127u;                            // queues are r
 #define CRT_POOL_NODE2_MIN 16     // ... as long as at least this many lanes take the further step
 #endif
 #ifndef CRT_POOL_STARVE
-#define CRT_POOL_STARVE 40        // ... unless fewer than this many streams are walking or ready to walk
+#define CRT_POOL_STARVE 40        // a shading pass waits for a full queue (64 streams) unless fewer than this many streams are walking or ready to walk
 #endif
 
 #ifdef CRT_POOL_STAMPS
@@ -100,34 +97,23 @@ __device__ unsigned long long* g_poolTimeline = nullptr;
 __device__ __forceinline__ bool lane_in(uint64_t m) { return __builtin_amdgcn_inverse_ballot_w64(m); }
 // lanes (of the active ones) whose three components are all finite: three compares straight into scalar masks.  |x| < inf is false for inf and NaN alike, i.e. it is
 // finite3's "exponent not all ones"; the compare builtin returns the lane mask itself, where the ballot of a bool goes through a VGPR (v_cndmask 0 / 1 + v_cmp_ne).
-// (-DCRT_DIET_NO_MASKS builds the ballots)
 __device__ __forceinline__ uint64_t finite3_mask(f3 v)
 {
-#ifdef CRT_DIET_NO_MASKS
-    const uint32_t m = 0x7f800000u;
-    return __builtin_amdgcn_ballot_w64((asu(v.x) & m) != m) & __builtin_amdgcn_ballot_w64((asu(v.y) & m) != m) & __builtin_amdgcn_ballot_w64((asu(v.z) & m) != m);
-#else
     const float inf = __builtin_inff();
     return __builtin_amdgcn_fcmpf(__builtin_fabsf(v.x), inf, 4) & __builtin_amdgcn_fcmpf(__builtin_fabsf(v.y), inf, 4) & __builtin_amdgcn_fcmpf(__builtin_fabsf(v.z), inf, 4);   // 4 = ordered and less than
-#endif
 }
 // The loop's wave-uniform decisions are scalar compares in front of scalar branches: nested `if`s on 32-bit counts, no `bool` carried across a join (the
 // compiler materialises such a flag as a 64-bit lane mask: s_cselect_b64 -1 / 0, s_and / s_or_b64, s_andn2_b64 vcc, exec + s_cbranch_vccnz).  pop32: a mask's
 // population as a 32-bit scalar the compiler cannot widen again; CRT_CTL_SEQ: an empty statement that keeps two nested uniform `if`s from being merged back into
-// one flag expression.  (-DCRT_CTL_NO_DECIDE builds the flag forms)
+// one flag expression.
 #define CRT_CTL_SEQ() asm volatile("")
 __device__ __forceinline__ bool ctl_free(uint64_t mRes) { CRT_CTL_SEQ(); return mRes != ~0ull; }      // any lane without a stream? (as the inner of two nested tests)
 // a launch constant as a value the compiler must compare where it is asked about: a test of it is then s_cmp + s_cbranch_scc at the place of use, not a 64-bit
 // flag formed in front of the loop, kept in (spilled) SGPRs for the wavefront's life and negated through a VGPR (v_cndmask 0 / 1 + v_cmp_ne) where its opposite is wanted
-#ifdef CRT_CTL_NO_DECIDE
-__device__ __forceinline__ uint32_t fresh(uint32_t x) { return x; }
-#else
 __device__ __forceinline__ uint32_t fresh(uint32_t x) { asm("" : "+s"(x)); return x; }
-#endif
 __device__ __forceinline__ uint32_t pop32(uint64_t m) { uint32_t n = (uint32_t)__builtin_popcountll(m); asm("" : "+s"(n)); return n; }
 // Lane sets straight from a compare of values every lane holds (a lane without a stream holds the value that keeps it out of the set): the compare builtins return
 // the lane mask, where the ballot of a `bool` that was assigned under a divergent `if` goes through a VGPR (v_cndmask 0 / 1 + v_cmp_ne, both half rate).
-// (-DCRT_CTL_NO_BALLOT builds the ballots)
 __device__ __forceinline__ uint64_t mask_ne(uint32_t a, uint32_t b) { return __builtin_amdgcn_uicmp(a, b, 33); }    // LLVM's integer predicates: 32 eq, 33 ne,
 __device__ __forceinline__ uint64_t mask_eq(uint32_t a, uint32_t b) { return __builtin_amdgcn_uicmp(a, b, 32); }    // 36 unsigned <, 37 unsigned <=, 39 signed >=
 __device__ __forceinline__ uint64_t mask_ult(uint32_t a, uint32_t b) { return __builtin_amdgcn_uicmp(a, b, 36); }
@@ -174,19 +160,10 @@ __global__ __launch_bounds__(64, REFBITS == 32 ? CRT_POOL_WIDE_MIN_WAVES : CRT_P
     const uint32_t tile = tileFirst + tl * tileStride;
     const uint32_t tx = tile % tilesX, ty = tile / tilesX;
     // what the tile's primary rays cannot hit (layout.h kTileNo*, proven on the host: tile_class.h), one scalar for the wavefront's life; 0 = every test runs.
-    // Only new_ray's primary form and the END pass look at it, and only to skip, under a scalar branch, a test whose outcome is known (-DCRT_NO_TILE_CLASS: never)
-#ifdef CRT_NO_TILE_CLASS
-    constexpr uint32_t tcls = 0u;
-#else
+    // Only new_ray's primary form and the END pass look at it, and only to skip, under a scalar branch, a test whose outcome is known
     const uint32_t tcls = tileClass ? __builtin_amdgcn_readfirstlane((uint32_t)tileClass[tl]) : 0u;
-#endif
-#if defined(CRT_CTL_NO_DECIDE) || defined(CRT_NO_TILE_CLASS)
-    const bool skyTile = tcls == kTileSky;
-    auto not_sky = [&]() -> bool { return !skyTile; };
-#else
     // "not a sky tile" is compared afresh by each test that asks (fresh(), above)
     auto not_sky = [&]() -> bool { return fresh(tcls) != kTileSky; };
-#endif
     const char* __restrict__ geom = sc.geom;
     float* __restrict__ fac = facScratch + (size_t)blockIdx.x * (15u * (uint32_t)S);
 
@@ -225,12 +202,10 @@ __global__ __launch_bounds__(64, REFBITS == 32 ? CRT_POOL_WIDE_MIN_WAVES : CRT_P
         qEnd[s] = (uint8_t)s;
         if (S > 64) slotFrame[s] = (uint16_t)s;
     }
-#ifndef CRT_CTL_NO_DECIDE
     // streams of the wavefront that have not rendered their 256 pixels yet — walking or in a queue; falls only in the END pass, when a stream's last path ends and no
     // frame is left for its slot.  The loop ends when it reaches zero: one scalar compare at the foot of a trip.  (That is the moment the walking lanes and the three
-    // queues are all empty, which -DCRT_CTL_NO_DECIDE tests after every walk, from the queue counters.)
+    // queues are all empty.)
     uint32_t nLive = nStreams;
-#endif
     uint32_t nextFrame = nStreams;                                               // the range's next frame (relative to frame0) without a slot (wave-uniform; only grows)
     uint32_t endH = 0, endT = nStreams, bncH = 0, bncT = 0, rdyH = 0, rdyT = 0;  // queue heads / tails (wave-uniform)
 
@@ -246,26 +221,22 @@ __global__ __launch_bounds__(64, REFBITS == 32 ? CRT_POOL_WIDE_MIN_WAVES : CRT_P
     // ---- the start of a stream's next scene.FindNearest, shared by both shading passes: normalise, reciprocal direction, light quad,
     // floor plane, root step; parks the new ray and queues the stream (READY, or END / BOUNCE when the ray never enters the tree)
     // `primary` (a compile-time tag): the ray starts at the camera (the END pass), and the operands that depend on the origin alone come from the Scene's
-    // camera-relative block (layout.h: primRoot, primLight, primFloor, formed on the host) instead of being recomputed by every lane (-DCRT_DIET_NO_CAMREL: never)
-    // mActIn: the lanes with a new ray, as the caller's scalar mask; act = the same as a per-lane predicate
-    auto new_ray = [&](auto primary, uint64_t mActIn, bool act, uint32_t s, f3 v, bool norm, f3 O, uint32_t seed, uint32_t meta) {
-#ifdef CRT_DIET_NO_CAMREL
-        constexpr bool PRIM = false;
-#else
+    // camera-relative block (layout.h: primRoot, primLight, primFloor, formed on the host) instead of being recomputed by every lane.
+    // The tile class applies to these rays only.
+    // mAct: the lanes with a new ray, as the caller's scalar mask
+    auto new_ray = [&](auto primary, uint64_t mAct, uint32_t s, f3 v, bool norm, f3 O, uint32_t seed, uint32_t meta) {
         constexpr bool PRIM = decltype(primary)::value;
-#endif
-        // the tile class applies to rays from the camera only (also under -DCRT_DIET_NO_CAMREL, which only recomputes their operands)
-        constexpr bool FROM_CAM = decltype(primary)::value;
+        const bool act = lane_in(mAct);
         // a sky tile (all three bits): the ray misses light, floor and tree, so FindNearest is over before it starts and the stream goes straight back to the END queue.
         // Parked is only what that pass reads of a missed path: the direction (sky lookup), the RNG state, meta with depth 0 and object field 0 (= miss).
-        const bool noLight = FROM_CAM && (tcls & kTileNoLight) != 0u, noFloor = FROM_CAM && (tcls & kTileNoFloor) != 0u, noTree = FROM_CAM && (tcls & kTileNoTree) != 0u;
+        const bool noLight = PRIM && (tcls & kTileNoLight) != 0u, noFloor = PRIM && (tcls & kTileNoFloor) != 0u, noTree = PRIM && (tcls & kTileNoTree) != 0u;
         f3 D = v, rD = v; Hit nh; nh.t = 1e34f; nh.u = 0; nh.v = 0; nh.objIdx = -1; nh.triIdx = -1;
         uint32_t ncur = kRefDone, pend = 0u;
         if (act) {
             const float inv = rcp_exact(sqrt_exact(dot3(v, v)));                  // normalize(): v * (1 / sqrtf(dot(v, v)))
             D = norm ? v * inv : v;
             cn.rays++;
-            if (!FROM_CAM || not_sky()) {
+            if (!PRIM || not_sky()) {
                 rD = rcp_exact3(D);
                 hit_light_floor<PRIM>(light_floor_from_kernarg<PRIM>(), O, D, nh, noLight, noFloor);
             }
@@ -292,7 +263,7 @@ __global__ __launch_bounds__(64, REFBITS == 32 ? CRT_POOL_WIDE_MIN_WAVES : CRT_P
                 if (COUNT) { if (KIND == 0) cn.interior++; else cn.tlas++; }
             } else ncur = sc.rootRef16;
             if (COUNT && KIND == 0 && (ncur & R.tagMask) == 0u && ncur != kRefDone) cn.leaf++;
-            if (!FROM_CAM || not_sky()) {
+            if (!PRIM || not_sky()) {
                 stf[F_OX * S + s] = O.x; stf[F_OY * S + s] = O.y; stf[F_OZ * S + s] = O.z;
                 stf[F_RX * S + s] = rD.x; stf[F_RY * S + s] = rD.y; stf[F_RZ * S + s] = rD.z;
                 stf[F_T * S + s] = nh.t;
@@ -301,23 +272,13 @@ __global__ __launch_bounds__(64, REFBITS == 32 ? CRT_POOL_WIDE_MIN_WAVES : CRT_P
             stf[F_DX * S + s] = D.x; stf[F_DY * S + s] = D.y; stf[F_DZ * S + s] = D.z;
             st[F_SEED * S + s] = seed; st[F_META * S + s] = meta | ((uint32_t)(nh.objIdx + 1) << kMetaObjShift);
         }
-#ifdef CRT_CTL_NO_BALLOT
-        const uint64_t mAct = __builtin_amdgcn_ballot_w64(act);
-#else
-        const uint64_t mAct = mActIn;
-#endif
         // queue: the walk is needed only when the ray enters the tree; otherwise FindNearest is already over (renderer.cpp:52-55, 69).  Every set is the ballot of ONE
         // comparison combined with scalar logic.  (A sky tile: every new ray is a finished path — one set, no further ballots.)
         uint64_t mW = 0ull, mE = mAct, mB = 0ull;
-        if (!FROM_CAM || not_sky()) {
+        if (!PRIM || not_sky()) {
             const uint32_t depth = (meta >> kMetaDepthShift) & 7u;
-#ifdef CRT_CTL_NO_BALLOT
-            mW = mAct & __builtin_amdgcn_ballot_w64(ncur != kRefDone);
-            const uint64_t mStop = __builtin_amdgcn_ballot_w64((uint32_t)(nh.objIdx + 1) <= 1u) | __builtin_amdgcn_ballot_w64((int)depth >= sc.depthLimit);   // miss, light, or depth limit
-#else
             mW = mAct & mask_ne(ncur, kRefDone);                               // (ncur, nh.objIdx and depth are defined on every lane)
             const uint64_t mStop = mask_ule((uint32_t)(nh.objIdx + 1), 1u) | mask_sge((int)depth, sc.depthLimit);   // miss, light, or depth limit
-#endif
             mE = mAct & ~mW & mStop; mB = mAct & ~mW & ~mStop;
             if (lane_in(mW)) qRdy[(rdyT + rank_in(mW)) & kQueueMask] = (uint8_t)s;
             if (lane_in(mB)) qBnc[(bncT + rank_in(mB)) & kQueueMask] = (uint8_t)s;
@@ -338,19 +299,15 @@ __global__ __launch_bounds__(64, REFBITS == 32 ? CRT_POOL_WIDE_MIN_WAVES : CRT_P
     // Which slab test the step runs — the v_min / v_max form, exact while every stepping lane's reciprocal direction is finite, or the ordered-compare form — is a
     // property of the trip: the walk tests it once, on the lanes of the first step (mFinite changes in swap-in, at a TLAS leaf and at a BLAS return only, none of which
     // lies between a trip's NODE steps for the lanes that step), and calls the steps with the answer as a compile-time tag.  The exact form is then one out-of-line
-    // region of the loop instead of a uniform branch inside every step's divergent region.  (-DCRT_CTL_NO_FINITE: every step tests its own lanes)
+    // region of the loop instead of a uniform branch inside every step's divergent region.
     uint64_t mNode2 = 0ull;
     auto node_step = [&](auto exactTag, uint64_t m) {
-#ifdef CRT_CTL_NO_FINITE
-        const bool allFinite = (m & ~mFinite) == 0ull;
-#else
         constexpr bool allFinite = !decltype(exactTag)::value;
-#endif
         if (lane_in(m)) {
             if (COUNT) { if (KIND == 1 && (cur & R.tlasBit) != 0u) cn.tlas++; else cn.interior++; }
             const uint32_t top = stk_top(spB);                               // speculative: lands during the slab arithmetic (the dummy entry when the stack is empty)
             float d1, d2;
-            if (__builtin_expect(allFinite, 1)) { d1 = box_fast(q0, q1, tO, trD, h.t); d2 = box_fast(q2, q3, tO, trD, h.t); }
+            if constexpr (allFinite) { d1 = box_fast(q0, q1, tO, trD, h.t); d2 = box_fast(q2, q3, tO, trD, h.t); }
             else { d1 = box_exact(q0, q1, tO, trD, h.t); d2 = box_exact(q2, q3, tO, trD, h.t); }
             const Ordered o = ordered_step(d1, d2, asu(q1.w), asu(q3.w));    // the children's ref16
             stk_put(spB + kLevelB, o.farRef);                                   // dead store unless `push`
@@ -436,11 +393,7 @@ __global__ __launch_bounds__(64, REFBITS == 32 ? CRT_POOL_WIDE_MIN_WAVES : CRT_P
                 for (int rep = 1; rep < CRT_POOL_NODE_STEPS; rep++) {
                     const uint64_t mStepped = rep == 1 ? mNode : mNode2;
                     mNode2 = mStepped & (KIND == 0 ? __builtin_amdgcn_ballot_w64(cur > R.interior - 1u) : __builtin_amdgcn_ballot_w64(cur - R.tlasBit < R.interior));
-#ifdef CRT_CTL_NO_DECIDE
-                    if ((uint32_t)__popcll(mNode2) < (uint32_t)CRT_POOL_NODE2_MIN) { mNode2 = 0ull; break; }
-#else
                     if (pop32(mNode2) < (uint32_t)CRT_POOL_NODE2_MIN) { mNode2 = 0ull; break; }
-#endif
                     const uint64_t mLeaf = mStepped & __builtin_amdgcn_ballot_w64((cur & R.tagMask) == 0u) & ~__builtin_amdgcn_ballot_w64(cur == kRefDone);
                     load_records(mNode2 | mLeaf);
                     mLeafNow |= mLeaf;
@@ -449,9 +402,6 @@ __global__ __launch_bounds__(64, REFBITS == 32 ? CRT_POOL_WIDE_MIN_WAVES : CRT_P
                 }
 #endif
             };
-#ifdef CRT_CTL_NO_FINITE
-            node_phase(std::false_type{});
-#else
             if (mNode != 0ull) {
                 // two `if`s, not if / else: an else arm holding divergent regions comes back as a second, dead branch on a saved flag
                 uint64_t mInf = mNode & ~mFinite, mInf2 = mInf;
@@ -459,13 +409,11 @@ __global__ __launch_bounds__(64, REFBITS == 32 ? CRT_POOL_WIDE_MIN_WAVES : CRT_P
                 if (__builtin_expect(mInf == 0ull, 1)) node_phase(std::false_type{});
                 if (__builtin_expect(mInf2 != 0ull, 0)) node_phase(std::true_type{});
             }
-#endif
             const uint64_t mTriAll = mTri | mLeafNow;
-            const uint64_t mTriRan = mTriAll;
             if (mTriAll != 0ull) tri_step(mTriAll);
             if (KIND == 1) {
                 // a popped return marker: the BLAS is finished — back to the world-space ray, pop the TLAS entry below (rare: once per BLAS visit)
-                mBack = (mNode | mTriRan) & __builtin_amdgcn_ballot_w64(cur == R.ret);
+                mBack = (mNode | mTriAll) & __builtin_amdgcn_ballot_w64(cur == R.ret);
                 if (mBack != 0ull) {
                     if (lane_in(mBack)) {
                         world_ray();
@@ -498,11 +446,6 @@ __global__ __launch_bounds__(64, REFBITS == 32 ? CRT_POOL_WIDE_MIN_WAVES : CRT_P
             asm volatile("" ::: "memory");
         }
         CRT_PSTAMP(p1); CRT_PACC(0, p0, p1);
-#ifdef CRT_CTL_NO_DECIDE
-        if (__builtin_expect(mRes == 0ull, 0)) {
-            if ((endT - endH) + (bncT - bncH) + (rdyT - rdyH) == 0u) break;       // every stream has rendered its 256 pixels
-        }
-#endif
         if (COUNT) trips++;
         CRT_DENS(0, 1);
 #ifdef CRT_POOL_STAMPS
@@ -515,11 +458,7 @@ __global__ __launch_bounds__(64, REFBITS == 32 ? CRT_POOL_WIDE_MIN_WAVES : CRT_P
         {
             const uint32_t nRdy = rdyT - rdyH;
             const uint64_t mFree = ~mRes;
-#ifdef CRT_CTL_NO_DECIDE
-            if (nRdy != 0u) if (mFree != 0ull) {
-#else
             if (nRdy != 0u) if (ctl_free(mRes)) {
-#endif
                 const uint32_t myRank = rank_in(mFree);
                 const uint64_t mTake = mFree & __builtin_amdgcn_ballot_w64(myRank < nRdy);      // the first min(nRdy, free) free lanes
                 CRT_DENS(7, 1); CRT_DENS(8, __popcll(mTake));
@@ -551,21 +490,10 @@ __global__ __launch_bounds__(64, REFBITS == 32 ? CRT_POOL_WIDE_MIN_WAVES : CRT_P
         // ---------------- B. shading passes (their latency-free arithmetic also covers the record loads just issued) --------------------
         const uint32_t nEnd = endT - endH, nBnc = bncT - bncH;
         // a shading pass waits for a full wavefront of streams unless the walking side runs dry
-#ifdef CRT_CTL_NO_DECIDE
-        {
-            const uint32_t nRdy = rdyT - rdyH, nRes = (uint32_t)__popcll(mRes);
-            const bool starving = nRes + nRdy < (uint32_t)CRT_POOL_STARVE;
-            bool runEnd = false, runBnc = false;
-            if ((nEnd | nBnc) >= (uint32_t)CRT_POOL_SHADE_MIN || starving) {      // (64 is a power of two: either count >= 64 <=> the OR is; rings hold <= 128)
-                runEnd = nEnd >= (uint32_t)CRT_POOL_SHADE_MIN || (starving && nEnd > 0u && nEnd >= nBnc);
-                runBnc = nBnc >= (uint32_t)CRT_POOL_SHADE_MIN || (starving && nBnc > nEnd);
-            }
-#else
         // "A queue is full, or the wave is starving" is ONE scalar compare in front of ONE branch round both passes: the walking side's population, replaced by 0 when
         // a queue is full (64 is a power of two: either count >= 64 <=> the OR is), against the starving threshold.  No pass due — the common case — costs ten scalar
         // instructions, the branch included.  (The loop holds divergent regions, so the compiler structurises it as a whole, and every further early way out of this
         // section — nested tests, a `continue` — comes back as a saved 64-bit flag and a second branch.)
-        static_assert(CRT_POOL_SHADE_MIN == 64, "the pass decision's shifts assume a threshold of 64");
         uint32_t walking = pop32(mRes) + (rdyT - rdyH), fullest = nEnd | nBnc;
         asm("" : "+s"(walking));                                                  // (a select of two values at hand, not a branch round the sum)
         walking = fullest >= 64u ? 0u : walking;
@@ -576,32 +504,22 @@ __global__ __launch_bounds__(64, REFBITS == 32 ? CRT_POOL_WIDE_MIN_WAVES : CRT_P
             // tie, none when both are empty (nEnd < 64 fits the byte).
             const uint32_t run = fullest >= 64u ? (nEnd >> 6) | ((nBnc >> 6) << 8) : (nEnd >= nBnc ? nEnd : nBnc << 8);
             const uint32_t runEnd = run & 0xffu, runBnc = run >> 8;
-#endif
 
             CRT_PSTAMP(p2b); CRT_PACC(1, p1, p2b);
             if (runEnd != 0u) {
                 // ---------------- B1. END pass: the path of each stream ended (renderer.cpp:54-55, 69) or has not begun ----------------
                 const uint32_t n = nEnd < 64u ? nEnd : 64u;
-#ifdef CRT_CTL_NO_BALLOT
-                const bool act = lane < n;
-#else
                 const uint64_t mActE = mask_ult(lane, n);
                 const bool act = lane_in(mActE);
-#endif
                 const uint32_t s = act ? qEnd[(endH + lane) & kQueueMask] : 0u;
                 endH += n;
                 uint32_t meta = 0, seed = 0; int obj = -1; f3 D = nil3;
                 if (act) { meta = st[F_META * S + s]; seed = st[F_SEED * S + s]; obj = (int)(meta >> kMetaObjShift) - 1; D = mk3(stf[F_DX * S + s], stf[F_DY * S + s], stf[F_DZ * S + s]); }
                 const int depth = (int)((meta >> kMetaDepthShift) & 7u);
                 uint32_t item = meta & kMetaItemMask;
-#ifdef CRT_CTL_NO_BALLOT
-                const bool first = (meta & kMetaFresh) != 0u;
-                const bool ended = act && !first, miss = ended && obj == -1;
-#else
                 // the pass's lane sets as scalar masks (meta is 0 on a lane without a stream: neither fresh nor a hit)
                 const uint64_t mFirst = mask_ne(meta & kMetaFresh, 0u), mEnded = mActE & ~mFirst, mMiss = mEnded & mask_eq(meta >> kMetaObjShift, 0u);
                 const bool first = lane_in(mFirst), ended = lane_in(mEnded), miss = lane_in(mMiss);
-#endif
 #ifdef CRT_POOL_DENS
                 dens[36u + CRT_LIVE_BUCKET(live)]++;
 #endif
@@ -639,25 +557,6 @@ __global__ __launch_bounds__(64, REFBITS == 32 ? CRT_POOL_WIDE_MIN_WAVES : CRT_P
                 }
                 // REFILL: the slots whose stream has just rendered its last pixel take the range's next frames (none left: the slot stays empty and the population
                 // falls).  The finished path's sample position is computed above, from the old frame; its radiance is stored below as for every ended path.
-#ifdef CRT_CTL_NO_BALLOT
-                if (S > 64) if (nextFrame < nOwn) {
-                    const uint64_t mDone = __builtin_amdgcn_ballot_w64(ended) & ~__builtin_amdgcn_ballot_w64(gen);
-                    if (mDone != 0ull) {
-                        const uint32_t f = nextFrame + rank_in(mDone);
-                        const uint64_t mTake = mDone & __builtin_amdgcn_ballot_w64(f < nOwn);
-                        if (lane_in(mTake)) {
-                            slotFrame[s] = (uint16_t)f;
-                            seed = init_seed(tx + ty * (uint32_t)sc.W + (sppFirst + (frame0 + f) * passes) * 1799u);   // renderer.cpp:120, as at the wave's start
-                            item = 0u; gen = true;
-                        }
-                        nextFrame += (uint32_t)__popcll(mTake);
-                    }
-                }
-                const uint64_t mGen = __builtin_amdgcn_ballot_w64(gen);
-#ifndef CRT_CTL_NO_DECIDE
-                { const uint64_t mGone = __builtin_amdgcn_ballot_w64(ended) & ~mGen; if (mGone != 0ull) nLive -= pop32(mGone); }
-#endif
-#else
                 // (the set of lanes that generate a ray is one mask: the fresh streams, the ended ones with pixels left — `item` was stepped on those lanes only —
                 // and, below, the refilled slots.  A stream renders its last pixel once per 256 paths, so the test of mDone skips all of it nearly always.)
                 uint64_t mGen = mFirst | (mEnded & mask_ult(item, items));
@@ -675,12 +574,9 @@ __global__ __launch_bounds__(64, REFBITS == 32 ? CRT_POOL_WIDE_MIN_WAVES : CRT_P
                         nextFrame += pop32(mTake);
                         mGen |= mTake;
                     }
-#ifndef CRT_CTL_NO_DECIDE
                     nLive -= pop32(mDone & ~mTake);
-#endif
                 }
                 gen = lane_in(mGen);
-#endif
 #ifdef CRT_POOL_DENS
                 {
                     const uint32_t gone = (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(ended) & ~__builtin_amdgcn_ballot_w64(gen));
@@ -694,19 +590,14 @@ __global__ __launch_bounds__(64, REFBITS == 32 ? CRT_POOL_WIDE_MIN_WAVES : CRT_P
                 if (gen) {                                                         // ProcessTile + Camera::GetPrimaryRay (renderer.cpp:125-126, camera.h:23-30)
                     const uint32_t pix = (fresh(passes) == 1u) ? item : item / passes;
                     const f3 TL = mk3(cam[3], cam[4], cam[5]);
-#ifdef CRT_DIET_NO_CAMREL
-                    const f3 TR = mk3(cam[6], cam[7], cam[8]), BL = mk3(cam[9], cam[10], cam[11]);
-                    const f3 right = TR - TL, down = BL - TL;
-#else
                     constexpr size_t pc = (offsetof(Scene, primRight) - offsetof(Scene, camPos)) / 4;   // primRight[3], primDown[3]: TR - TL and BL - TL, formed on the host
                     const f3 right = mk3(cam[pc], cam[pc + 1], cam[pc + 2]), down = mk3(cam[pc + 3], cam[pc + 4], cam[pc + 5]);
-#endif
                     v = primary_target(camPos, TL, right, down, cam[12], cam[13], tx, ty, pix, seed);   // invW, invH follow the camera in the Scene block
                     cn.primary++;
                 }
                 CRT_DENS_MASK(12, gen);
                 CRT_PSTAMP(e1); CRT_PACC(2, p2b, e1);
-                new_ray(std::true_type{}, mGen, gen, s, v, true, camPos, seed, item);                      // depth 0, outside, not fresh
+                new_ray(std::true_type{}, mGen, s, v, true, camPos, seed, item);                      // depth 0, outside, not fresh
                 CRT_PSTAMP(e2); CRT_PACC(3, e1, e2);
                 if (ended) {
                     // the finished path's radiance: sky colour / light (24,24,22) / 0 at the depth limit (renderer.cpp:54-55, 69; GetLightColor file_scene.cpp:164-167), times the
@@ -731,13 +622,8 @@ __global__ __launch_bounds__(64, REFBITS == 32 ? CRT_POOL_WIDE_MIN_WAVES : CRT_P
             if (runBnc != 0u) {
                 // ---------------- B2. BOUNCE pass: surface hit (floor or mesh) below the depth limit (renderer.cpp:56-99) ----------------
                 const uint32_t n = nBnc < 64u ? nBnc : 64u;
-#ifdef CRT_CTL_NO_BALLOT
-                const bool act = lane < n;
-                const uint64_t mActB = 0ull;
-#else
                 const uint64_t mActB = mask_ult(lane, n);
                 const bool act = lane_in(mActB);
-#endif
                 const uint32_t s = act ? qBnc[(bncH + lane) & kQueueMask] : 0u;
                 bncH += n;
                 f3 O = nil3, D = nil3; float ht = 0, hu = 0, hv = 0; int obj = 1; uint32_t tri = 0, seed = 0, meta = 0;
@@ -792,16 +678,14 @@ __global__ __launch_bounds__(64, REFBITS == 32 ? CRT_POOL_WIDE_MIN_WAVES : CRT_P
                     CRT_PSTAMP(b3); CRT_PACC(7, b2, b3);
                 }
                 CRT_PSTAMP(b4);
-                new_ray(std::false_type{}, mActB, act, s, v, false, O, seed, item | ((uint32_t)(depth + 1) << kMetaDepthShift) | (newInside ? kMetaInside : 0u));
+                new_ray(std::false_type{}, mActB, s, v, false, O, seed, item | ((uint32_t)(depth + 1) << kMetaDepthShift) | (newInside ? kMetaInside : 0u));
 #ifdef CRT_POOL_STAMPS
                 { CRT_PSTAMP(b5); CRT_PACC(8, b4, b5); pst[11]++; }
 #endif
                 asm volatile("" :: "v"(s0), "v"(s1), "v"(s2), "v"(s3));            // (as at the end of the END pass)
             }
         }
-#ifndef CRT_CTL_NO_DECIDE
         if (nLive == 0u) break;                                                   // every stream has rendered its 256 pixels
-#endif
     }
 #ifdef CRT_POOL_STAMPS
     if (lane == 0) for (int i = 0; i < 12; i++) atomicAdd(&g_poolStamps[i], pst[i]);
@@ -839,13 +723,10 @@ __global__ __launch_bounds__(64, REFBITS == 32 ? CRT_POOL_WIDE_MIN_WAVES : CRT_P
 #define CRT_POOL_STREAMS 128
 #endif
 extern "C" uint32_t crt_pool_streams(uint32_t frames) { return frames > 64u ? (uint32_t)CRT_POOL_STREAMS : 64u; }
-#ifndef CRT_POOL_EXTRA_LDS
-#define CRT_POOL_EXTRA_LDS 0       // occupancy experiments only: unused LDS bytes per wavefront
-#endif
 // LDS of one wavefront: traversal stacks ((stackDepth + 1 dummy) entries of refBits / 8 bytes per lane) + parked stream state + the three one-byte ring queues
 // + (more slots than lanes: wavefronts that may refill) the two-byte frame of every slot.  128 slots, 16-bit references, at a stack depth of <= 17: <= 10 240 bytes,
 // 16 wavefronts per CU; 32-bit references add (stackDepth + 1) * 128 bytes.
-extern "C" uint32_t crt_pool_lds_bytes(uint32_t stackDepth, uint32_t streams, uint32_t refBits) { return (stackDepth + 1u) * 64u * (refBits / 8u) + crt::F_COUNT * streams * 4u + 3u * 128u + (streams > 64u ? 2u * streams : 0u) + (uint32_t)CRT_POOL_EXTRA_LDS; }
+extern "C" uint32_t crt_pool_lds_bytes(uint32_t stackDepth, uint32_t streams, uint32_t refBits) { return (stackDepth + 1u) * 64u * (refBits / 8u) + crt::F_COUNT * streams * 4u + 3u * 128u + (streams > 64u ? 2u * streams : 0u); }
 // the most LDS a pool wavefront may ask for: what the device grants one workgroup, and never more than the 64 KiB that bound the other render kernels' stacks (abi.cpp)
 extern "C" uint32_t crt_pool_lds_limit(int device)
 {
