@@ -80,6 +80,7 @@ struct crt_ctx {
     uint64_t tickEpoch = 0; uint32_t tickNextSpp = 0, tickPasses = 0;   // the previous crt_tick: its epoch (0: none), spp + passes, passes
     uint32_t aheadFrames = 0;             // frames of the newest render-ahead launch (doubles while Ticks hit)
     hipStream_t aheadStream = nullptr;    // low-priority stream of the render-ahead launches
+    hipStream_t skyStream = nullptr;      // low-priority stream of the sky launches submitted behind their job's pool launch (launch_render_kernels)
     crt::Scene hScene{};
     crt::Counters* dCounters = nullptr;
     uint32_t* dQueryCursor = nullptr;      // the ray cursor of the persistent query kernels (zeroed by each launch)
@@ -97,6 +98,10 @@ struct crt_ctx {
     bool classDirty = true;
     uint8_t* dTileClass = nullptr;
     uint8_t* hTileClass[2] = {nullptr, nullptr}; hipEvent_t classCopied[2] = {nullptr, nullptr}; int classFlip = 0;
+    // The kTileSky tiles of that table (hostClass: the host's copy of it; skyTiles of them) are the TAIL of every tile order (sky_to_tail), and a pool launch that has
+    // the table leaves that tail to one render_sky_kernel launch of the same job (sky_split, launch_render_kernels).  skyLaunches: those launches so far
+    // (crt_debug_sky_launches); skyWindowTicks: what one window of them took in the measuring job (adopt_job_costs; 0: unknown)
+    std::vector<uint8_t> hostClass; uint32_t skyTiles = 0, skyLaunches = 0; double skyWindowTicks = 0;
     bool haveScene = false;
     // what crt_update_scene needs of the last upload: a host mirror of the geometry buffer and where each BVH's records start
     struct Flat { int32_t kind = 0; uint64_t leafOff = 0, tlasOff = 0, tlasPairOff = 0, instOff = 0, shadeOff = 0; uint32_t tlasNodeCount = 0, maxHeight = 0;
@@ -181,7 +186,7 @@ struct crt_ctx {
     std::vector<uint32_t> jobCost;          // per local tile, 100 MHz ticks; sorted view = the tile order on the device once jobCostValid
     std::vector<uint32_t> jobOrder;
     uint32_t* dJobDesc = nullptr; uint32_t* hJobDesc = nullptr; uint32_t jobDescCap = 0, jobBlocks = 0, jobHead = 0; hipEvent_t jobDescReady = nullptr;
-    uint32_t planWindows = 0, planFrames = 0; bool planPool = false, planValid = false;       // what the table on the device was planned for
+    uint32_t planWindows = 0, planFrames = 0, planSky = 0, planSkyAsked = 0; bool planPool = false, planValid = false;       // what the table on the device was planned for (planSky: sky ranks left out)
     double jobTrialMs[2] = {0, 0};          // this plan's shape timed [0] plain (cost-ordered, no table) and [1] planned: the faster one is kept (planner_prepare)
     // the plan's pool launch: frames per wavefront by tile rank (pool_wave_plan), behind the block table in dJobDesc — jobWaveBlocks wavefronts (0: every wavefront S frames,
     // no table), jobLongWaves of them with more than S frames; lastLongWaves: what the last pool launch had of those (crt_debug_pool_long_waves)
@@ -416,6 +421,7 @@ void crt_destroy(crt_ctx* c)
     for (hipEvent_t e : c->retiredEvents) (void)hipEventDestroy(e);
     for (auto& a : c->ahead) (void)hipEventDestroy(a.end);
     if (c->aheadStream) (void)hipStreamDestroy(c->aheadStream);
+    if (c->skyStream) (void)hipStreamDestroy(c->skyStream);          // (every sky launch was joined into a render stream: nothing of its own to wait for)
     for (auto& ev : c->evPool) { (void)hipEventDestroy(ev.a); (void)hipEventDestroy(ev.b); }
     for (auto& ev : c->evRender) { (void)hipEventDestroy(ev.a); (void)hipEventDestroy(ev.b); }
     for (auto& ev : c->evAcc) { (void)hipEventDestroy(ev.a); (void)hipEventDestroy(ev.b); }
@@ -1018,6 +1024,15 @@ static int upload_tile_order(crt_ctx* c, const std::vector<uint32_t>& order)
     return 0;
 }
 
+// Every tile order ends with the tiles whose CURRENT class is kTileSky (cls: one byte per local tile, or none known), in the relative order they had: the ranks in
+// front of that tail are what a pool launch with a sky launch beside it renders (sky_split).  Returns the tail's length.
+static uint32_t sky_to_tail(const std::vector<uint8_t>& cls, std::vector<uint32_t>& order)
+{
+    if (cls.size() != order.size()) return 0u;
+    const auto tail = std::stable_partition(order.begin(), order.end(), [&](uint32_t i) { return cls[i] != crt::kTileSky; });
+    return (uint32_t)(order.end() - tail);
+}
+
 // Tiles (local indices 0..tileCount) ordered so that those inside the screen-space bounding rectangle of the meshes' world box come first
 // (the stream-pool kernel and wide launches dispatch in this order).  Pure scheduling heuristic: the projection uses the pin-hole camera of crt_set_camera in double precision and is conservative on failure
 // (a corner behind the eye makes every tile a candidate).
@@ -1063,7 +1078,8 @@ static int update_tile_order(crt_ctx* c)
     for (int k = 0; k <= crt_ctx::kLatStages; k++) { c->tuneCount[k] = 0; c->tuneMs[k] = 0; }
     c->latStage = 0; c->latBest = 0; c->latDone = false; c->latWarm = false; c->latConfirming = false; c->latQueue.clear(); c->costPending = false; c->latProbed = false;
     first.insert(first.end(), rest.begin(), rest.end());
-    c->jobCostValid = false; c->jobCostPending = false; c->planValid = false;
+    (void)sky_to_tail(c->hostClass, first);
+    c->jobCostValid = false; c->jobCostPending = false; c->planValid = false; c->skyWindowTicks = 0;
     { const int r = upload_tile_order(c, first); if (r) return r; }
     c->orderDirty = false;
     return 0;
@@ -1083,6 +1099,15 @@ static int update_tile_class(crt_ctx* c)
         HIPCK(c, ensure_event(&c->classCopied[k]));
     } else HIPCK(c, hipEventSynchronize(c->classCopied[k]));
     crt::classify_tiles(c->hScene, c->cfg.width, c->cfg.height, (uint32_t)c->tilesX, c->tileFirst, c->tileStride, c->tileCount, c->hTileClass[k]);
+    {
+        // a changed set of sky tiles: the order on the device no longer ends with it, so a new one is made before the next launch (crt_render: update_tile_order
+        // runs behind this function) — and with it the costs are measured again, as after a camera change
+        const uint8_t* cls = c->hTileClass[k];
+        bool same = c->hostClass.size() == c->tileCount; uint32_t sky = 0;
+        for (uint32_t i = 0; i < c->tileCount; i++) { const bool s = cls[i] == crt::kTileSky; sky += s ? 1u : 0u; if (same && s != (c->hostClass[i] == crt::kTileSky)) same = false; }
+        c->hostClass.assign(cls, cls + c->tileCount); c->skyTiles = sky;
+        if (!same) c->orderDirty = true;
+    }
     HIPCK(c, hipMemcpyAsync(c->dTileClass, c->hTileClass[k], (size_t)c->tileCount, hipMemcpyHostToDevice, c->stream));
     HIPCK(c, hipEventRecord(c->classCopied[k], c->stream));
     c->orderReady = c->classCopied[k];
@@ -1395,15 +1420,39 @@ static int take_region(crt_ctx* c, size_t need, hipStream_t st, size_t* offOut)
     }
 }
 
-// the job-cost buffer: one uint32 per tile, then (8-byte aligned) three uint64: ~(first wavefront's start clock), last wavefront's start clock, wave time after it
+// the job-cost buffer: one uint32 per tile, then (8-byte aligned) three uint64: ~(first wavefront's start clock), last wavefront's start clock, wave time after it;
+// then two of the job's sky launch (render_sky_kernel): ~(first wavefront's start clock), last wavefront's end clock
 static size_t job_cost_clk_offset(const crt_ctx* c) { return (((size_t)c->tileCount + 1u) & ~(size_t)1u) * 4u; }
-static size_t job_cost_bytes(const crt_ctx* c) { return job_cost_clk_offset(c) + 24u; }
+static size_t job_cost_bytes(const crt_ctx* c) { return job_cost_clk_offset(c) + 40u; }
+
+// How many ranks at the end of the tile order a launch leaves to render_sky_kernel: the order's sky tail, when the launch runs the pool kernel of a non-statistics
+// context (the statistics build counts the root step of every primary ray) and the class table the order was made with is the current one.  0: one kernel renders
+// every tile, as a launch without the table does (stale, or CRT_DEBUG_NO_TILE_CLASS; CRT_DEBUG_NO_SKY_KERNEL keeps the table and drops only the sky launch: A/B runs;
+// CRT_POOL_WAVE_FRAMES, the tests' forced range length, describes a pool launch of every tile and gets one).
+// Where the sky launch goes: on the next stream, submitted behind the pool launch — its many short wavefronts run in that launch's drain (the default: measured
+// faster); CRT_SKY_PLACEMENT=ahead (A/B runs): on the launch's own stream in front of the pool launch.
+static bool sky_behind() { const char* e = hook("CRT_SKY_PLACEMENT"); return !(e && !strcmp(e, "ahead")); }
+static uint32_t sky_split(const crt_ctx* c, bool pool)
+{
+    if (!pool || c->cfg.collectStats || c->classDirty || !c->dTileClass || c->hostClass.size() != c->tileCount) return 0u;
+    if (hook("CRT_DEBUG_NO_TILE_CLASS") || hook("CRT_DEBUG_NO_SKY_KERNEL")) return 0u;
+    if (hook("CRT_POOL_WAVE_FRAMES")) return 0u;                       // (that switch forces a range length "for every tile": the pool launch it describes renders them all)
+    return c->skyTiles;
+}
 
 // A job's tile costs have arrived (hJobCost): dispatch order = most expensive tile first from now on; and what ONE window of this image costs the machine under
 // the pool — the planner's yardstick.  The sum of the wavefront durations is no measure of it (waves that share a SIMD with four others last longer; the
 // expensive tiles' wavefronts, which outlive the crowd, do not), so it comes from the launch's dispatch: a launch that oversubscribes the chip keeps every wavefront
 // slot busy until its last wavefront starts (S0 = last start - first start), and drains afterwards — the wave time spent after S0, summed by the wavefronts
 // themselves, divided by the slots.  One-stream-per-lane launches need 1.2x the pool's machine time (4.24 against 3.52 ms per window on the bunny).
+// (the order itself: most expensive first, ties in index order, the sky tiles behind all others)
+static uint32_t job_order(const std::vector<uint32_t>& cost, const std::vector<uint8_t>& cls, std::vector<uint32_t>& order)
+{
+    order.resize(cost.size());
+    for (uint32_t i = 0; i < (uint32_t)cost.size(); i++) order[i] = i;
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return cost[a] > cost[b]; });
+    return sky_to_tail(cls, order);
+}
 static int adopt_job_costs(crt_ctx* c)
 {
     const uint32_t n = c->tileCount;
@@ -1416,9 +1465,13 @@ static int adopt_job_costs(crt_ctx* c)
         if (c->recWindows && (double)c->recWaves >= 1.5 * (double)c->recResident && s0 > 0) c->poolWindowTicks = (s0 + drain) / (double)c->recWindows / (c->recPool ? 1.0 : 1.2);
         if (hook("CRT_LAT_VERBOSE")) fprintf(stderr, "[crt] measured %u windows with %s: %u wavefronts, last one started %.2f ms after the first, then %.2f ms of drain -> %.3f ms of machine time per window under the pool\n", c->recWindows, c->recPool ? "the pool" : "one stream per lane", c->recWaves, s0 * 1e-5, drain * 1e-5, c->poolWindowTicks * 1e-5);
     }
-    c->jobOrder.resize(n);
-    for (uint32_t i = 0; i < n; i++) c->jobOrder[i] = i;
-    std::stable_sort(c->jobOrder.begin(), c->jobOrder.end(), [&](uint32_t a, uint32_t b) { return c->jobCost[a] > c->jobCost[b]; });
+    {
+        // the job's sky launch, if it had one: its span on the device per window (it shared the machine with the pool launch; the planner adds it to its makespan aim)
+        const unsigned long long* clk = reinterpret_cast<const unsigned long long*>(reinterpret_cast<const char*>(c->hJobCost) + job_cost_clk_offset(c)) + 3;
+        c->skyWindowTicks = (c->recWindows && clk[0] && clk[1] > ~clk[0]) ? (double)(clk[1] - ~clk[0]) / (double)c->recWindows : 0.0;
+        if (hook("CRT_LAT_VERBOSE")) fprintf(stderr, "[crt] the sky launch of the measuring job: %.3f ms per window\n", c->skyWindowTicks * 1e-5);
+    }
+    job_order(c->jobCost, c->hostClass, c->jobOrder);
     c->jobCostValid = true; c->planValid = false;
     return upload_tile_order(c, c->jobOrder);
 }
@@ -1433,11 +1486,14 @@ static int adopt_job_costs(crt_ctx* c)
 // and the machine time of all of them (wave time / wavefronts the chip advances at once) still fits T.  Tiles are sorted by cost, so the classes are contiguous:
 // the first `head` tiles of the order go to a block table (render_tiles_kernel, dispatched first), the rest to the pool launch — or, in a launch without the pool,
 // everything goes to the table as soon as one tile needs narrow wavefronts.  Returns the table's blocks in `table` (empty: no table needed).
-static void plan_job(const crt_ctx* c, uint32_t windows, uint32_t frames, bool pool, std::vector<uint32_t>& table, uint32_t* head)
+// nSky: the last nSky ranks of the order are the job's sky launch (sky_split) — the plan sees the n ranks in front of them only, and skyTicks, that launch's
+// machine time, as time the makespan must hold besides.
+static void plan_job(const crt_ctx* c, uint32_t windows, uint32_t frames, bool pool, std::vector<uint32_t>& table, uint32_t* head, uint32_t nSky = 0u, double skyTicks = 0.0)
 {
     table.clear(); *head = 0;
-    const uint32_t n = c->tileCount;
-    if (!c->jobCostValid || windows < 2u || windows > 64u || n > 0x10000u || c->cfg.collectStats || hook("CRT_SPLIT_OFF")) return;
+    if (nSky >= c->tileCount) return;                                   // an image of sky tiles only: no pool launch, nothing to plan
+    const uint32_t n = c->tileCount - nSky;
+    if (!c->jobCostValid || windows < 2u || windows > 64u || c->tileCount > 0x10000u || c->cfg.collectStats || hook("CRT_SPLIT_OFF")) return;
     if (pool && c->streams.size() < 2) return;
     if (const char* e = hook("CRT_SPLIT_FORCE")) {                      // tests: the first h tiles through the table, alternating wavefront widths
         const uint32_t h = std::min<uint32_t>((uint32_t)atoi(e), pool ? n - 1u : n);
@@ -1461,7 +1517,8 @@ static void plan_job(const crt_ctx* c, uint32_t windows, uint32_t frames, bool p
         int k = 1; while (k < 6 && kLatG[k] * v > T) k++;
         *cls = 2 + k; return K * (64.0 / kLatLanes[k]) * kLatG[k] * v / narrowSlots;
     };
-    auto machine = [&](double T) { double m = 0; int cls; for (uint32_t v : c->jobCost) m += cheapest((double)v, T, &cls); return m; };
+    std::vector<uint8_t> planned(c->tileCount, 0); for (uint32_t r = 0; r < n; r++) planned[c->jobOrder[r]] = 1;      // (summed in tile order, whatever the ranks)
+    auto machine = [&](double T) { double m = 0; int cls; for (uint32_t i = 0; i < c->tileCount; i++) if (planned[i]) m += cheapest((double)c->jobCost[i], T, &cls); return m + skyTicks; };
     const double top = (double)c->jobCost[c->jobOrder[0]];
     double lo = top * kLatG[6], hi = std::max(poolLong * top, machine(1e30)) * 1.01;
     if (machine(lo) <= lo) hi = lo;
@@ -1501,7 +1558,9 @@ static void plan_job(const crt_ctx* c, uint32_t windows, uint32_t frames, bool p
 // that kept 6 x 4096 lost 37 % (it grew the tail the split had removed); the guard is 12.  Needs no GPU (tests:
 // crt_debug_pool_wave_plan).  Returns the wavefronts of the launch; wf[r] = frames per wavefront of rank r in the long part, start[r] its expected start; *longFrames = 0:
 // every wavefront owns S frames.
-struct PoolWaveTerms { double poolLong = 2.4, load = 1.0, safety = 1.0, guard = 12.0, share = 1.0; };   // (poolLong is the duration UNDER LOAD: it holds the 1.2, plan_job)
+// tailTicks / tailWaves: machine time and wavefronts of a launch dispatched BEHIND this one inside the same job (the sky launch: short wavefronts that fill this
+// launch's end as its own short part does) — the time is part of the makespan aim, the wavefronts count towards the guard (in this launch's units: S frames each).
+struct PoolWaveTerms { double poolLong = 2.4, load = 1.0, safety = 1.0, guard = 12.0, share = 1.0, tailTicks = 0.0, tailWaves = 0.0; };   // (poolLong is the duration UNDER LOAD: it holds the 1.2, plan_job)
 static uint64_t pool_wave_plan(const uint32_t* cost, uint32_t nr, uint32_t frames, uint32_t S, double perCost, double startTicks, uint32_t resident, const PoolWaveTerms& tm,
                                std::vector<uint32_t>& wf, uint32_t* longFrames, std::vector<double>* start, double* aimOut)
 {
@@ -1515,9 +1574,10 @@ static uint64_t pool_wave_plan(const uint32_t* cost, uint32_t nr, uint32_t frame
     double aim = startTicks, m = startTicks;
     std::vector<double> st(nr);
     for (uint32_t r = 0; r < nr; r++) { st[r] = m; m += (double)(F1 / 64u) * (double)cost[r] * perCost; aim += (double)((frames + 63u) / 64u) * (double)cost[r] * perCost; }
+    aim += tm.tailTicks;
     if (start) *start = st;
     if (aimOut) *aimOut = aim;
-    if ((double)plain < tm.guard * (double)resident) return plain;
+    if ((double)plain + tm.tailWaves < tm.guard * (double)resident) return plain;
     const uint64_t shortWaves = (uint64_t)nr * ((frames - F1 + S - 1u) / S);
     for (int kMax = 3; kMax >= 1; kMax--) {
         uint64_t waves = shortWaves; bool any = false;
@@ -1528,7 +1588,7 @@ static uint64_t pool_wave_plan(const uint32_t* cost, uint32_t nr, uint32_t frame
             waves += F1 / wf[r];
         }
         if (!any) break;
-        if ((double)waves >= tm.guard * (double)resident) { *longFrames = F1; return waves; }
+        if ((double)waves + tm.tailWaves >= tm.guard * (double)resident) { *longFrames = F1; return waves; }
     }
     wf.assign(nr, S);
     return plain;
@@ -1562,41 +1622,76 @@ static uint32_t forced_wave_frames(uint32_t S)
     return (uint32_t)std::min<long>(v, 8192) / S * S;
 }
 
+// The plan of a job's pool launch: pool_wave_plan for the ranks [head, tileCount - nSky) of the order, the head's tiles (block table, dispatched first) as time spent
+// before them and the sky launch (skyTicks of machine time; the wavefronts its ranks would have in this launch) as the launch's tail — or, when the sky launch is
+// submitted ahead (sky_behind), as time spent before them too.  Appends the wave table to `table` when any wavefront owns
+// more than S frames: one entry per rank from `head` to the END of the order, because the kernel's search runs over all of them — a rank of the sky tail gets
+// `blocks` as its first block, which no wavefront of the long part reaches.
+struct PoolWavePlan { uint32_t off = 0, blocks = 0, longFrames = 0, longWaves = 0, ranks = 0; double aim = 0; };
+static PoolWavePlan plan_pool_waves(const crt_ctx* c, uint32_t windows, uint32_t frames, uint32_t head, uint32_t nSky, double skyTicks, std::vector<uint32_t>& table)
+{
+    PoolWavePlan p;
+    PoolWaveTerms terms;
+    const uint32_t S = crt_pool_streams(frames);
+    if (!c->jobCostValid || c->cfg.collectStats || head + nSky >= c->tileCount || !pool_wave_terms(terms) || forced_wave_frames(S)) return p;
+    const uint32_t nr = c->tileCount - nSky - head;
+    p.ranks = nr;
+    std::vector<uint32_t> cost(nr), wf, tab;
+    double costSum = 0; for (uint32_t v : c->jobCost) costSum += (double)v;
+    const double perCost = (c->poolWindowTicks > 0 && costSum > 0) ? c->poolWindowTicks / costSum : 1.0 / 4096.0;
+    double startTicks = 0;
+    if (sky_behind()) { terms.tailTicks = skyTicks; terms.tailWaves = (double)nSky * (double)((frames + S - 1u) / S); } else startTicks = skyTicks;
+    for (uint32_t r = 0; r < head; r++) startTicks += (double)windows * 1.2 * (double)c->jobCost[c->jobOrder[r]] * perCost;      // (one stream per lane: 1.2 x the pool's machine time)
+    for (uint32_t r = 0; r < nr; r++) cost[r] = c->jobCost[c->jobOrder[head + r]];
+    uint32_t F1 = 0, lw = 0, blocks = 0;
+    pool_wave_plan(cost.data(), nr, frames, S, perCost, startTicks, 4096u, terms, wf, &F1, nullptr, &p.aim);
+    if (F1) blocks = pool_wave_table(wf, F1, S, tab, &lw);
+    if (lw) {
+        for (uint32_t r = 0; r < nSky; r++) { tab.push_back(blocks); tab.push_back(S); }
+        p.off = (uint32_t)table.size(); p.blocks = blocks; p.longFrames = F1; p.longWaves = lw;
+        table.insert(table.end(), tab.begin(), tab.end());
+    }
+    if (hook("CRT_LAT_VERBOSE")) {
+        uint32_t cnt[4] = {0, 0, 0, 0}; double share[4] = {0, 0, 0, 0}, sum = 0;
+        for (uint32_t r = 0; r < nr; r++) { int k = 0; while ((S << k) < wf[r]) k++; cnt[k]++; share[k] += cost[r]; sum += cost[r]; }
+        fprintf(stderr, "[crt] pool launch of %u ranks x %u frames (%u sky ranks behind them: %.2f ms): aim %.1f ms, most expensive tile %.2f ms, long part %u frames in %u wavefronts, %u of them own more than %u frames (safety %.2f, guard %.1f x 4096, share %.2f); tiles by frames per wavefront (share of the cost):",
+                nr, frames, nSky, skyTicks * 1e-5, p.aim * 1e-5, nr ? cost[0] * 1e-5 : 0.0, F1, blocks, lw, S, terms.safety, terms.guard, terms.share);
+        for (int k = 0; k < 4; k++) fprintf(stderr, " %u: %u (%.3f)", S << k, cnt[k], sum > 0 ? share[k] / sum : 0.0);
+        fprintf(stderr, "\n");
+    }
+    return p;
+}
+
+// Machine time of a job's sky launch, for the planner's makespan aim: what the measuring job's sky launch took per window (adopt_job_costs).  0 when that job had
+// none — it ran one stream per lane, below the pool's size: the sky tiles' costs it measured bound the sky launch from above, but an aim raised by them made the plan
+// slower than the parent's, so nothing is assumed about a launch that was not measured.
+static double sky_launch_ticks(const crt_ctx* c, uint32_t windows, uint32_t nSky)
+{
+    return (nSky && c->jobCostValid) ? c->skyWindowTicks * (double)windows : 0.0;
+}
+
 // ... and its table on the device (cached for launches of the same shape)
 static int install_job_plan(crt_ctx* c, uint32_t windows, uint32_t frames, bool pool)
 {
-    if (c->planValid && c->planWindows == windows && c->planFrames == frames && c->planPool == pool) return 0;
+    const uint32_t asked = sky_split(c, pool);
+    if (c->planValid && c->planWindows == windows && c->planFrames == frames && c->planPool == pool && c->planSkyAsked == asked) return 0;
+    uint32_t nSky = asked;
+    double skyTicks = sky_launch_ticks(c, windows, nSky);
     std::vector<uint32_t> table; uint32_t head = 0;
-    plan_job(c, windows, frames, pool, table, &head);
-    c->planValid = true; c->planWindows = windows; c->planFrames = frames; c->planPool = pool; c->jobHead = head; c->jobBlocks = (uint32_t)table.size();
+    plan_job(c, windows, frames, pool, table, &head, nSky, skyTicks);
+    if (head && nSky) {
+        // A job that needs the block table ends on its most expensive tiles' wavefronts, not on machine time, and there a sky launch beside the pool launch was
+        // measured to COST its own duration (20 windows of the bunny: +5 %, whatever its placement or priority): such a job keeps its sky tiles
+        // in the pool launch, at the end of its dispatch order, as before.
+        nSky = 0; skyTicks = 0;
+        plan_job(c, windows, frames, pool, table, &head);
+    }
+    c->planValid = true; c->planWindows = windows; c->planFrames = frames; c->planPool = pool; c->planSkyAsked = asked; c->planSky = nSky; c->jobHead = head; c->jobBlocks = (uint32_t)table.size();
     c->jobTrialMs[0] = c->jobTrialMs[1] = 0;
     c->jobWaveOff = c->jobWaveBlocks = c->jobLongFrames = c->jobLongWaves = 0;
-    PoolWaveTerms terms;
-    const uint32_t S = crt_pool_streams(frames);
-    if (pool && c->jobCostValid && !c->cfg.collectStats && head < c->tileCount && pool_wave_terms(terms) && !forced_wave_frames(S)) {
-        // the pool launch's ranks: the order from `head` on; the head's tiles (block table, dispatched first) are machine time spent before them
-        const uint32_t nr = c->tileCount - head;
-        std::vector<uint32_t> cost(nr), wf, tab;
-        double costSum = 0; for (uint32_t v : c->jobCost) costSum += (double)v;
-        const double perCost = (c->poolWindowTicks > 0 && costSum > 0) ? c->poolWindowTicks / costSum : 1.0 / 4096.0;
-        double startTicks = 0;
-        for (uint32_t r = 0; r < head; r++) startTicks += (double)windows * 1.2 * (double)c->jobCost[c->jobOrder[r]] * perCost;      // (one stream per lane: 1.2 x the pool's machine time)
-        for (uint32_t r = 0; r < nr; r++) cost[r] = c->jobCost[c->jobOrder[head + r]];
-        double aim = 0; uint32_t F1 = 0, lw = 0, blocks = 0;
-        pool_wave_plan(cost.data(), nr, frames, S, perCost, startTicks, 4096u, terms, wf, &F1, nullptr, &aim);
-        if (F1) blocks = pool_wave_table(wf, F1, S, tab, &lw);
-        if (lw) {
-            c->jobWaveOff = (uint32_t)table.size(); c->jobWaveBlocks = blocks; c->jobLongFrames = F1; c->jobLongWaves = lw;
-            table.insert(table.end(), tab.begin(), tab.end());
-        }
-        if (hook("CRT_LAT_VERBOSE")) {
-            uint32_t cnt[4] = {0, 0, 0, 0}; double share[4] = {0, 0, 0, 0}, sum = 0;
-            for (uint32_t r = 0; r < nr; r++) { int k = 0; while ((S << k) < wf[r]) k++; cnt[k]++; share[k] += cost[r]; sum += cost[r]; }
-            fprintf(stderr, "[crt] pool launch of %u ranks x %u frames: aim %.1f ms, most expensive tile %.2f ms, long part %u frames in %u wavefronts, %u of them own more than %u frames (safety %.2f, guard %.1f x 4096, share %.2f); tiles by frames per wavefront (share of the cost):",
-                    nr, frames, aim * 1e-5, nr ? cost[0] * 1e-5 : 0.0, F1, blocks, lw, S, terms.safety, terms.guard, terms.share);
-            for (int k = 0; k < 4; k++) fprintf(stderr, " %u: %u (%.3f)", S << k, cnt[k], sum > 0 ? share[k] / sum : 0.0);
-            fprintf(stderr, "\n");
-        }
+    if (pool) {
+        const PoolWavePlan p = plan_pool_waves(c, windows, frames, head, nSky, skyTicks, table);
+        c->jobWaveOff = p.off; c->jobWaveBlocks = p.blocks; c->jobLongFrames = p.longFrames; c->jobLongWaves = p.longWaves;
     }
     if (table.empty()) return 0;
     if (c->jobDescCap < table.size()) {
@@ -1628,6 +1723,7 @@ struct Launch {
     bool wantCost = false, wantJobCost = false, pool = false;
     uint32_t head = 0, jobBlocks = 0; unsigned long long* jobClk = nullptr;      // a planned job: table blocks + first tile rank of the pool launch
     uint32_t waveFrames = 0, waveBlocks = 0, longFrames = 0, longWaves = 0; const uint32_t* waveTab = nullptr;   // the pool launch's frames per wavefront: one for all (0: S), or per rank (table of waveBlocks wavefronts)
+    uint32_t sky = 0;                                               // ranks at the end of the order that go to render_sky_kernel (sky_split); the pool launch renders the ranks in front of them
 };
 
 static int next_block_table(crt_ctx* c);
@@ -1690,6 +1786,7 @@ static int planner_prepare(crt_ctx* c, Launch& L)
     const bool poolByDefault = c->hScene.poolRefBits == 16u || c->poolMinWaves == 0;
     const uint64_t minWaves = c->poolMinWaves != 65000u ? c->poolMinWaves : (c->jobCostValid ? 43000u : 65000u);
     L.pool = c->usePool && poolByDefault && pool_can_run(c, L.nf) && (uint64_t)c->tileCount * L.windows >= minWaves && (c->poolMinWaves == 0 || L.nf > 64u);
+    L.sky = sky_split(c, L.pool);
     if (L.nf > 64u && c->jobCostValid) {
         if ((r = install_job_plan(c, L.windows, L.nf, L.pool))) return r;
         // The plan is a MODEL (machine time within ~15 %): for a job shape that repeats (a progressive render) it is checked by measurement — the first launch of the
@@ -1701,18 +1798,19 @@ static int planner_prepare(crt_ctx* c, Launch& L)
             else if (c->jobTrialMs[1] > 0 && c->jobTrialMs[0] == 0) use = 0;   // the planned launch has been timed: time the plain one
             c->evRender.back().mode = 100 + use;
         }
+        if (use) L.sky = c->planSky;                                        // (the planned launch: what its table was made for — none beside a block table)
         if (use) { L.head = c->jobHead; L.jobBlocks = c->jobBlocks; if (L.pool && c->jobLongWaves) { L.waveTab = c->dJobDesc + c->jobWaveOff; L.waveBlocks = c->jobWaveBlocks; L.longFrames = c->jobLongFrames; L.longWaves = c->jobLongWaves; } }
     }
     if (L.pool) if (const uint32_t S = crt_pool_streams(L.nf); const uint32_t n = forced_wave_frames(S)) {
         L.waveFrames = n; L.waveTab = nullptr; L.waveBlocks = 0;
-        L.longWaves = n > S ? (c->tileCount - L.head) * (L.nf / n + ((L.nf % n) > S ? 1u : 0u)) : 0u;
+        L.longWaves = n > S ? (c->tileCount - L.sky - L.head) * (L.nf / n + ((L.nf % n) > S ? 1u : 0u)) : 0u;
     }
     if (L.jobBlocks || L.waveTab) HIPCK(c, hipStreamWaitEvent(L.st, c->jobDescReady, 0));
     if (L.wantJobCost) {                                                 // what adopt_job_costs needs to know about the measuring launch
         L.jobClk = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(c->dJobCost) + job_cost_clk_offset(c));
         c->recPool = L.pool; c->recWindows = L.windows;
         const uint32_t perWave = L.pool ? std::max(crt_pool_streams(L.nf), L.waveFrames) : 64u;
-        c->recWaves = L.pool ? c->tileCount * ((L.nf + perWave - 1u) / perWave) : c->tileCount * L.windows;
+        c->recWaves = L.pool ? (c->tileCount - L.sky) * ((L.nf + perWave - 1u) / perWave) : c->tileCount * L.windows;
         c->recResident = L.pool ? 4096u : 5120u;                            // 4 / 5 wavefronts per SIMD (render_pool_kernel / render_tiles_kernel)
         if (L.pool && c->hScene.poolRefBits == 32u)                         // the 32-bit-reference form: what its LDS leaves of those 4 (160 KiB per CU of 4 SIMDs)
             c->recResident = 256u * std::min(16u, (160u * 1024u) / std::max(1u, pool_lds_need(c, L.nf)));
@@ -1740,6 +1838,14 @@ static hipError_t launch_render_kernels(crt_ctx* c, const Launch& L)
     if (L.pool) {
         void* scratch = (char*)L.slab + (size_t)L.windows * sample_bytes_per_window(c, L.passes);
         hipStream_t st2 = st;
+        // The order's sky tail goes to render_sky_kernel, inside the launch's event pair and joined in front of its end event (placement: sky_behind)
+        const bool skyBehind = sky_behind();
+        auto launch_sky = [&](hipStream_t s) -> hipError_t {
+            return crt_launch_render_sky(&c->hScene, L.slab, c->dCounters, c->dTileOrder, c->tileCount - L.sky, L.sky, c->tileFirst, c->tileStride, c->tileCount, (uint32_t)c->tilesX,
+                                         L.sppFirst, L.nf, L.passes, L.jobClk ? L.jobClk + 3 : nullptr, s);
+        };
+        if (L.sky && !skyBehind) { le = launch_sky(st); if (le == hipSuccess) c->skyLaunches++; }
+        if (le != hipSuccess) return le;
         if (L.jobBlocks) {
             // the expensive tiles first, through the block table, on this launch's stream; the pool for the rest on the next stream, released by the same start event
             le = launch_table(c->dJobDesc, L.jobBlocks, nullptr);
@@ -1748,11 +1854,27 @@ static hipError_t launch_render_kernels(crt_ctx* c, const Launch& L)
         }
         if (le == hipSuccess)
             le = crt_launch_render_pool(&c->hScene, L.slab, scratch, c->dCounters, c->dTileClocks, c->dTileOrder, c->tileFirst, c->tileStride, c->tileCount, (uint32_t)c->tilesX,
-                                        L.sppFirst, L.nf, L.passes, c->cfg.collectStats, L.jobBlocks ? L.head : 0u, L.waveFrames, L.waveTab, L.waveBlocks, L.longFrames,
+                                        L.sppFirst, L.nf, L.passes, c->cfg.collectStats, L.jobBlocks ? L.head : 0u, c->tileCount - L.sky, L.waveFrames, L.waveTab, L.waveBlocks, L.longFrames,
                                         L.wantJobCost ? c->dJobCost : nullptr, L.jobClk,
                                         (c->classDirty || hook("CRT_DEBUG_NO_TILE_CLASS")) ? nullptr : c->dTileClass /* tests / A-B: the kernel without the table */, c->extraLds, st2);
         if (le == hipSuccess) c->lastLongWaves = L.longWaves;
         if (L.jobBlocks && le == hipSuccess) le = join(st2);
+        if (L.sky && skyBehind && le == hipSuccess) {
+            // ... on a stream of the lowest priority: "behind" is a dispatch preference, not an order — at equal priority the sky launch's wavefronts are dispatched
+            // beside the pool launch's first ones and a short job, which ends on its most expensive tiles' wavefronts, ends later by the sky launch's whole duration
+            // (CRT_SKY_PRIORITY=normal: the next render stream; the A/B of DESIGN.md section 5)
+            if (!c->skyStream && !hook("CRT_SKY_PRIORITY")) {
+                int least = 0, greatest = 0;
+                le = hipDeviceGetStreamPriorityRange(&least, &greatest);
+                if (le == hipSuccess) le = hipStreamCreateWithPriority(&c->skyStream, hipStreamNonBlocking, least);
+                if (le != hipSuccess) return le;
+            }
+            hipStream_t st3 = c->skyStream;
+            if (hook("CRT_SKY_PRIORITY")) { st3 = c->streams[(size_t)(c->launchSeq++ % c->streams.size())]; if (st3 == st2 && c->streams.size() > 1) st3 = c->streams[(size_t)(c->launchSeq++ % c->streams.size())]; }
+            if (st3 != st) le = hipStreamWaitEvent(st3, L.ev.a, 0);
+            if (le == hipSuccess) le = launch_sky(st3);
+            if (le == hipSuccess) { c->skyLaunches++; le = join(st3); }
+        }
     } else if (L.jobBlocks) {
         le = launch_table(c->dJobDesc, L.jobBlocks, nullptr);
     } else if (L.blockDesc && L.nBlocks) {
@@ -1831,7 +1953,7 @@ static int launch_frames(crt_ctx* c, uint32_t sppFirst, uint32_t nf, uint32_t pa
         // the frames before it are in, this one and the rest are not — and the error is reported
         return c->hip(le, pool ? "launch of render_pool_kernel" : "launch of render_tiles_kernel");
     }
-    if (pool) c->poolLaunches++;
+    if (pool && L.sky < c->tileCount) c->poolLaunches++;           // (an image of sky tiles only: the sky launch was the whole job)
     HIPCK(c, hipEventRecord(ev.b, st));
     pairGuard.armed = false;
     c->lastRenderEnd = ev.b;
@@ -1878,8 +2000,8 @@ int crt_render(crt_ctx* c, uint32_t spp_first, uint32_t frames, uint32_t passes)
     HIPCK(c, hipSetDevice(c->cfg.device));
     { int r = discard_ahead(c); if (r) return r; }                 // (a held region must never be handed out again: see take_region)
     if (c->tileCount == 0 || frames == 0) return CRT_OK;
+    { int r = update_tile_class(c); if (r) return r; }            // (first: the order ends with the table's sky tiles)
     { int r = update_tile_order(c); if (r) return r; }
-    { int r = update_tile_class(c); if (r) return r; }
     if (c->streams.empty()) {
         int n = c->cfg.renderStreams;
         if (n <= 0) n = 7;
@@ -3231,6 +3353,54 @@ extern "C" long long crt_debug_pool_wave_plan(const uint32_t* cost, uint32_t nr,
     memcpy(wf, w.data(), (size_t)nr * 4);
     if (start) memcpy(start, st.data(), (size_t)nr * 8);
     return (long long)waves;
+}
+// tests (no GPU needed): how the host splits a job's ranks between its pool launch and its sky launch, for tile classes cls[n] (layout.h kTileNo* bits) and tile costs
+// cost[n] (nullptr: not measured yet — the order is the tile order with the sky tiles moved behind).  order[n] receives the dispatch order; *skyFirst the first rank of
+// its sky tail (render_sky_kernel renders the ranks [*skyFirst, n)); *head the leading ranks the plan gives to the block table; *planRanks the ranks the pool launch's
+// wave plan covers (they follow the head).  waveTab[2 n] receives that launch's wave table — (first block, frames per wavefront) per rank from *head to n, the kernel's
+// search range — when the plan lengthens wavefronts (*tabBlocks > 0: its wavefronts, *longFrames: the frames of the long part).  Returns the sky tiles.
+// (The split as sky_split asks for it.  install_job_plan plans a job again WITHOUT a sky launch when this plan has a head: *head > 0 here means the job keeps one pool launch.)
+extern "C" int crt_debug_sky_split(const uint32_t* cost, const uint8_t* cls, uint32_t n, uint32_t windows, uint32_t frames, double poolWindowTicks, double skyWindowTicks,
+                                   uint32_t* order, uint32_t* skyFirst, uint32_t* head, uint32_t* planRanks, uint32_t* waveTab, uint32_t* tabBlocks, uint32_t* longFrames)
+{
+    if (!cls || !n || !order || !skyFirst || !head || !planRanks || !waveTab || !tabBlocks || !longFrames) return CRT_ERR_INVALID;
+    crt_ctx c;
+    c.tileCount = n; c.poolWindowTicks = poolWindowTicks; c.skyWindowTicks = skyWindowTicks;
+    c.hostClass.assign(cls, cls + n);
+    *head = *planRanks = *tabBlocks = *longFrames = 0;
+    if (!cost) {
+        c.jobOrder.resize(n); for (uint32_t i = 0; i < n; i++) c.jobOrder[i] = i;
+        c.skyTiles = sky_to_tail(c.hostClass, c.jobOrder);
+    } else {
+        c.jobCost.assign(cost, cost + n); c.jobCostValid = true;
+        c.skyTiles = job_order(c.jobCost, c.hostClass, c.jobOrder);
+        c.streams.assign(2, nullptr);
+        const double skyTicks = c.skyTiles ? skyWindowTicks * (double)windows : 0.0;
+        std::vector<uint32_t> table;
+        plan_job(&c, windows, frames, true, table, head, c.skyTiles, skyTicks);
+        table.clear();
+        const PoolWavePlan p = plan_pool_waves(&c, windows, frames, *head, c.skyTiles, skyTicks, table);
+        c.streams.clear();
+        *planRanks = p.ranks; *tabBlocks = p.blocks; *longFrames = p.longFrames;
+        if (table.size() > 2u * (size_t)n) return CRT_ERR_INVALID;
+        memcpy(waveTab, table.data(), table.size() * 4);
+    }
+    memcpy(order, c.jobOrder.data(), (size_t)n * 4);
+    *skyFirst = n - c.skyTiles;
+    return (int)c.skyTiles;
+}
+// tests: render_sky_kernel launches of this context so far (never reset)
+extern "C" int crt_debug_sky_launches(crt_ctx* c) { return c ? (int)c->skyLaunches : -1; }
+// tools: the tile costs the planner works with (100 MHz ticks per local tile, as the measuring job left them: 0 for a tile its sky launch rendered), and the
+// machine time per window of the measuring job's pool launch and of its sky launch.  CRT_ERR_STATE until a measuring job's costs have been adopted.
+extern "C" int crt_debug_job_costs(crt_ctx* c, uint32_t* out, double* poolWindowTicks, double* skyWindowTicks)
+{
+    if (!c || !out) return CRT_ERR_INVALID;
+    if (!c->jobCostValid || c->jobCost.size() != c->tileCount) return CRT_ERR_STATE;
+    memcpy(out, c->jobCost.data(), (size_t)c->tileCount * 4);
+    if (poolWindowTicks) *poolWindowTicks = c->poolWindowTicks;
+    if (skyWindowTicks) *skyWindowTicks = c->skyWindowTicks;
+    return CRT_OK;
 }
 // tests: wavefronts of the last render_pool_kernel launch that owned more than S frames (and so refilled their slots)
 extern "C" int crt_debug_pool_long_waves(crt_ctx* c) { return c ? (int)c->lastLongWaves : -1; }

@@ -34,8 +34,9 @@ hipError_t crt_launch_commit_frame(const void* slabWindow, uint32_t frameInWindo
 uint32_t crt_pool_streams(uint32_t frames);
 size_t crt_pool_scratch_bytes_per_window(uint32_t tileCount);
 hipError_t crt_launch_render_pool(const crt::Scene* sc, void* slab, void* facScratch, crt::Counters* counters, unsigned long long* tileClocks, const uint32_t* tileOrder, uint32_t tileFirst,
-    uint32_t tileStride, uint32_t tileCount, uint32_t tilesX, uint32_t sppFirst, uint32_t frames, uint32_t passes, int collectStats, uint32_t rankFirst, uint32_t waveFrames,
-    const uint32_t* waveTab, uint32_t tabBlocks, uint32_t longFrames, uint32_t* tileCost, unsigned long long* launchClk,
+    uint32_t tileStride, uint32_t tileCount, uint32_t tilesX, uint32_t sppFirst, uint32_t frames, uint32_t passes, int collectStats, uint32_t rankFirst,
+    uint32_t rankEnd /* the launch renders the ranks [rankFirst, rankEnd) of tileOrder; tileCount stays the slab's */, uint32_t waveFrames,
+    const uint32_t* waveTab /* tileCount - rankFirst entries */, uint32_t tabBlocks, uint32_t longFrames, uint32_t* tileCost, unsigned long long* launchClk,
     const uint8_t* tileClass /* one byte per local tile (layout.h kTileNo*), or nullptr: every test runs */, uint32_t extraLds /* unused LDS bytes per wavefront on top (tests) */,
     hipStream_t stream);
 uint32_t crt_pool_lds_bytes(uint32_t stackDepth, uint32_t streams, uint32_t refBits /* Scene::poolRefBits: 16 or 32 */);
@@ -43,6 +44,11 @@ uint32_t crt_pool_lds_limit(int device);
 int crt_debug_pool_stamps(unsigned long long* out, int reset);
 int crt_debug_pool_density(unsigned long long* out, int reset);
 size_t crt_debug_pool_timeline(unsigned long long* out, size_t cap);
+
+// ---- render_sky.hip: the kTileSky tiles of a job, ranks [rankFirst, rankFirst + skyTiles) of tileOrder, one wavefront per (tile, 64-frame window) ----
+hipError_t crt_launch_render_sky(const crt::Scene* sc, void* slab, crt::Counters* counters, const uint32_t* tileOrder, uint32_t rankFirst, uint32_t skyTiles, uint32_t tileFirst,
+    uint32_t tileStride, uint32_t tileCount /* of the slab: all local tiles */, uint32_t tilesX, uint32_t sppFirst, uint32_t frames, uint32_t passes,
+    unsigned long long* launchClk /* a measuring job: ~first start, last end (100 MHz), or nullptr */, hipStream_t stream);
 
 // ---- render_seq.hip ----
 uint32_t crt_probe_paths(void);

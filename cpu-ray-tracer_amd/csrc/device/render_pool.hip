@@ -197,7 +197,7 @@ __global__ __launch_bounds__(64, REFBITS == 32 ? CRT_POOL_WIDE_MIN_WAVES : CRT_P
 
     // every stream starts in the END queue as "fresh": the pass only generates its first primary ray
     for (uint32_t s = lane; s < nStreams; s += 64u) {
-        st[F_SEED * S + s] = init_seed(tx + ty * (uint32_t)sc.W + (sppFirst + (frame0 + s) * passes) * 1799u);   // renderer.cpp:120
+        st[F_SEED * S + s] = stream_seed(tx, ty, (uint32_t)sc.W, sppFirst, frame0 + s, passes);
         st[F_META * S + s] = kMetaFresh;
         qEnd[s] = (uint8_t)s;
         if (S > 64) slotFrame[s] = (uint16_t)s;
@@ -551,7 +551,7 @@ __global__ __launch_bounds__(64, REFBITS == 32 ? CRT_POOL_WIDE_MIN_WAVES : CRT_P
                     uint32_t pix = item, pass = 0;
                     if (fresh(passes) != 1u) { pix = item / passes; pass = item - pix * passes; }
                     const uint32_t fr = frame0 + (S > 64 ? (uint32_t)slotFrame[s] : s);   // frame of the launch -> (64-frame window, sample row position)
-                    sampleAt = (((size_t)(fr >> 6) * tileCount + tl) * 256u + pix) * rowLen + ((fr & 63u) * passes + pass);
+                    sampleAt = slab_position(fr, tileCount, tl, pix, rowLen, passes, pass);
                     item++;
                     gen = item < items;                                            // else: the stream has rendered its 256 pixels
                 }
@@ -568,7 +568,7 @@ __global__ __launch_bounds__(64, REFBITS == 32 ? CRT_POOL_WIDE_MIN_WAVES : CRT_P
                         mTake = mDone & mask_ult(f, nOwn);
                         if (lane_in(mTake)) {
                             slotFrame[s] = (uint16_t)f;
-                            seed = init_seed(tx + ty * (uint32_t)sc.W + (sppFirst + (frame0 + f) * passes) * 1799u);   // renderer.cpp:120, as at the wave's start
+                            seed = stream_seed(tx, ty, (uint32_t)sc.W, sppFirst, frame0 + f, passes);   // as at the wave's start
                             item = 0u;
                         }
                         nextFrame += pop32(mTake);
@@ -769,7 +769,7 @@ extern "C" size_t crt_debug_pool_timeline(unsigned long long* out, size_t cap)  
 #endif
 extern "C" hipError_t crt_launch_render_pool(const crt::Scene* sc, void* slab, void* facScratch, crt::Counters* counters, unsigned long long* tileClocks, const uint32_t* tileOrder,
                                              uint32_t tileFirst, uint32_t tileStride, uint32_t tileCount, uint32_t tilesX, uint32_t sppFirst,
-                                             uint32_t frames, uint32_t passes, int collectStats, uint32_t rankFirst, uint32_t waveFrames, const uint32_t* waveTab, uint32_t tabBlocks, uint32_t longFrames,
+                                             uint32_t frames, uint32_t passes, int collectStats, uint32_t rankFirst, uint32_t rankEnd, uint32_t waveFrames, const uint32_t* waveTab, uint32_t tabBlocks, uint32_t longFrames,
                                              uint32_t* tileCost, unsigned long long* launchClk, const uint8_t* tileClass, uint32_t extraLds, hipStream_t stream)
 {
     if (tileCount == 0 || frames == 0) return hipSuccess;
@@ -783,8 +783,11 @@ extern "C" hipError_t crt_launch_render_pool(const crt::Scene* sc, void* slab, v
     if (waveTab && (tabBlocks == 0u || longFrames == 0u || longFrames > frames)) return hipErrorInvalidValue;
     const uint32_t groups = waveTab ? (frames - longFrames + S - 1u) / S : (frames + wf - 1u) / wf;
     if ((unsigned long long)tileCount * ((frames + S - 1u) / S) > 0x7fffffffull) return hipErrorInvalidValue;
-    if (rankFirst >= tileCount) return hipSuccess;
-    dim3 grid(waveTab ? tabBlocks + (tileCount - rankFirst) * groups : (tileCount - rankFirst) * groups), block(64);
+    // the ranks [rankFirst, rankEnd) of the order: the grid ends with rankEnd's wavefronts (both parts of the launch are rank-major), and a wave table says of
+    // the ranks behind them that their first block is tabBlocks — the kernel's search, which runs over all tileCount - rankFirst entries, never lands there
+    if (rankEnd > tileCount) return hipErrorInvalidValue;
+    if (rankFirst >= rankEnd) return hipSuccess;
+    dim3 grid(waveTab ? tabBlocks + (rankEnd - rankFirst) * groups : (rankEnd - rankFirst) * groups), block(64);
 #ifdef CRT_POOL_TIMELINE
     { static unsigned long long* buf = nullptr; static size_t cap = 0;
       if (cap < (size_t)grid.x) { if (buf) (void)hipFree(buf); (void)hipMalloc((void**)&buf, (size_t)grid.x * 24); cap = grid.x; (void)hipMemcpyToSymbol(HIP_SYMBOL(crt::g_poolTimeline), &buf, sizeof(buf)); }

@@ -129,6 +129,16 @@ __device__ __forceinline__ void sample_unwind(const float* fst, int depth, f3& L
 // ------------------------------------------------------------------------------------------------------------
 // the ray's start
 // ------------------------------------------------------------------------------------------------------------
+// The RNG stream of frame `frame` (of the launch; `passes` samples per pixel and frame) of tile (tx, ty) of a W-wide image starts here (renderer.cpp:120), and its
+// sample of (pixel, pass) lies here in the launch's slab: [64-frame window][local tile][pixel][64 frames x passes] float4.  render_pool_kernel and render_sky_kernel.
+__device__ __forceinline__ uint32_t stream_seed(uint32_t tx, uint32_t ty, uint32_t W, uint32_t sppFirst, uint32_t frame, uint32_t passes)
+{
+    return init_seed(tx + ty * W + (sppFirst + frame * passes) * 1799u);
+}
+__device__ __forceinline__ size_t slab_position(uint32_t fr, uint32_t tileCount, uint32_t tl, uint32_t pix, uint32_t rowLen, uint32_t passes, uint32_t pass)
+{
+    return (((size_t)(fr >> 6) * tileCount + tl) * 256u + pix) * rowLen + ((fr & 63u) * passes + pass);
+}
 // ProcessTile + Camera::GetPrimaryRay (renderer.cpp:125-126, camera.h:23-30) for pixel `pix` of tile (tx, ty): P - camPos, still to be normalised.
 // right / down = topRight - topLeft / bottomLeft - topLeft
 __device__ __forceinline__ f3 primary_target(f3 camPos, f3 TL, f3 right, f3 down, float invW, float invH, uint32_t tx, uint32_t ty, uint32_t pix, uint32_t& seed)

@@ -35,6 +35,11 @@ for d in sorted(glob.glob(src + "/pmc_*")):
         render = [(did, k) for (did, k) in sorted(per) if ("render_pool_kernel" in k or "render_tiles_kernel" in k or "render_seq_kernel" in k) and "true" not in k.split("<")[-1].split(",")[1:2][0]]
         for (did, k) in render[warm_kernels:]:
             for c, v in per[(did, k)].items(): job[k][c] += v
+        # the job's sky launch (render_sky_kernel, not a template): dispatched beside the timed job's pool launch, so it counts from the first of those on
+        first_timed = render[warm_kernels][0] if len(render) > warm_kernels else None
+        for (did, k) in sorted(per):
+            if "render_sky_kernel" in k and first_timed is not None and did >= first_timed - 1:
+                for c, v in per[(did, k)].items(): job[k][c] += v
         for (did, k) in per:
             if "accumulate_kernel" in k:
                 for c, v in per[(did, k)].items(): acc[c] = max(acc[c], v)
