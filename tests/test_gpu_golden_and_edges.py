@@ -30,8 +30,9 @@ def bits(a):
     return np.asarray(a).view(np.uint32)
 
 
-def write_scene(tmp_path, mesh, name="s.xml", pos=(0.0, -1.0, 2.0), rot=(0.0, 180.0, 0.0), scale=(1.0, 1.0, 1.0), mats=None, extra_objects=()):
-    """scene equivalent to tests/golden/make_golden.py::simple_scene but through the XML loader (floor = pavement, sky = gradient)"""
+def write_scene(tmp_path, mesh, name="s.xml", pos=(0.0, -1.0, 2.0), rot=(0.0, 180.0, 0.0), scale=(1.0, 1.0, 1.0), mats=None, extra_objects=(),
+                light=(0.0, 3.0, 1.0), floor_tex="../assets/textures/Stylized_Pavement_basecolor.png", sky="../assets/sky_gradient.png"):
+    """scene equivalent to tests/golden/make_golden.py::simple_scene but through the XML loader (floor = pavement, sky = gradient unless named)"""
     mats = mats or [(0.0, 0.0, (0.0, 0.0, 0.0), "")]
     objs = [(mesh, 0, pos, rot, scale)] + list(extra_objects)
     o = "".join("<object><model_location>../assets/%s.obj</model_location><material_idx>%d</material_idx><position><x>%r</x><y>%r</y><z>%r</z></position>"
@@ -40,9 +41,9 @@ def write_scene(tmp_path, mesh, name="s.xml", pos=(0.0, -1.0, 2.0), rot=(0.0, 18
     ms = "".join("<material><reflectivity>%r</reflectivity><refractivity>%r</refractivity><absorption><x>%r</x><y>%r</y><z>%r</z></absorption><texture_location>%s</texture_location></material>"
                  % ((a, b) + tuple(c) + (t,)) for a, b, c, t in mats)
     p = tmp_path / name
-    p.write_text("<scene><scene_name>t</scene_name><light_position><x>0.0</x><y>3.0</y><z>1.0</z></light_position>"
-                 "<plane_texture_location>../assets/textures/Stylized_Pavement_basecolor.png</plane_texture_location>"
-                 "<skydome_location>../assets/sky_gradient.png</skydome_location><objects>%s</objects><materials>%s</materials></scene>" % (o, ms))
+    p.write_text("<scene><scene_name>t</scene_name><light_position><x>%r</x><y>%r</y><z>%r</z></light_position>"
+                 "<plane_texture_location>%s</plane_texture_location>"
+                 "<skydome_location>%s</skydome_location><objects>%s</objects><materials>%s</materials></scene>" % (tuple(light) + (floor_tex, sky, o, ms)))
     return str(p)
 
 
