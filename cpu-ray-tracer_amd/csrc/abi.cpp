@@ -1115,9 +1115,10 @@ static int update_tile_class(crt_ctx* c)
     return 0;
 }
 
-// bytes one 64-frame window of a launch takes in the slab pool: its float4 samples + (stream-pool kernel) the throughput-factor scratch.
-// A launch's region = [samples of all its windows][scratch of all its windows].
-static size_t sample_bytes_per_window(const crt_ctx* c, uint32_t passes) { return (size_t)c->tileCount * 256u * 64u * passes * 16u; }
+// bytes one 64-frame window of a launch takes in the slab pool: its 12-byte samples (device/sample_body.h: the kernels' own size function) + (stream-pool
+// kernel) the throughput-factor scratch.  A launch's region = [samples of all its windows][scratch of all its windows]; a window of samples is a multiple of
+// 196 608 bytes, so the scratch behind them stays 4-byte aligned.
+static size_t sample_bytes_per_window(const crt_ctx* c, uint32_t passes) { return crt_slab_window_bytes(c->tileCount, passes); }
 static size_t window_bytes(const crt_ctx* c, uint32_t passes) { return sample_bytes_per_window(c, passes) + (c->usePool ? crt_pool_scratch_bytes_per_window(c->tileCount) : 0); }
 
 // Latency mode: block tables of single-window launches from measured tile costs (100 MHz ticks of a tile's slowest wavefront).  A launch ends on its slowest
@@ -1724,6 +1725,9 @@ struct Launch {
     uint32_t head = 0, jobBlocks = 0; unsigned long long* jobClk = nullptr;      // a planned job: table blocks + first tile rank of the pool launch
     uint32_t waveFrames = 0, waveBlocks = 0, longFrames = 0, longWaves = 0; const uint32_t* waveTab = nullptr;   // the pool launch's frames per wavefront: one for all (0: S), or per rank (table of waveBlocks wavefronts)
     uint32_t sky = 0;                                               // ranks at the end of the order that go to render_sky_kernel (sky_split); the pool launch renders the ranks in front of them
+    // the sky launch writes its tiles' blocks in the texel form (device/sample_body.h) and the launch's accumulate reads the ranks [tileCount - sky, tileCount) as
+    // such: only where that accumulate follows at once (launch_frames) — never a render-ahead launch, whose frames are committed after the order may have changed
+    bool skyTexels = false;
 };
 
 static int next_block_table(crt_ctx* c);
@@ -1842,7 +1846,7 @@ static hipError_t launch_render_kernels(crt_ctx* c, const Launch& L)
         const bool skyBehind = sky_behind();
         auto launch_sky = [&](hipStream_t s) -> hipError_t {
             return crt_launch_render_sky(&c->hScene, L.slab, c->dCounters, c->dTileOrder, c->tileCount - L.sky, L.sky, c->tileFirst, c->tileStride, c->tileCount, (uint32_t)c->tilesX,
-                                         L.sppFirst, L.nf, L.passes, L.jobClk ? L.jobClk + 3 : nullptr, s);
+                                         L.sppFirst, L.nf, L.passes, L.skyTexels ? 1 : 0, L.jobClk ? L.jobClk + 3 : nullptr, s);
         };
         if (L.sky && !skyBehind) { le = launch_sky(st); if (le == hipSuccess) c->skyLaunches++; }
         if (le != hipSuccess) return le;
@@ -1945,6 +1949,7 @@ static int launch_frames(crt_ctx* c, uint32_t sppFirst, uint32_t nf, uint32_t pa
     Launch L; L.st = st; L.ev = ev; L.slab = slab; L.sppFirst = sppFirst; L.nf = nf; L.passes = passes; L.windows = (nf + 63u) / 64u;
     if ((r = tuner_prepare(c, L))) return r;                       // single-window launches: latency mode (block table, tile-cost measurement)
     if ((r = planner_prepare(c, L))) return r;                     // jobs: tile-cost measurement, kernel choice, plan (block table + pool split) or plain launch
+    L.skyTexels = ahead == nullptr;                                // (the accumulate below reads the sky launch's ranks; crt_tick's commits could not tell them later)
     HIPCK(c, hipEventRecord(ev.a, st));
     const bool pool = L.pool, wantCost = L.wantCost, wantJobCost = L.wantJobCost;
     const hipError_t le = hook("CRT_DEBUG_FAIL_LAUNCH") ? hipErrorInvalidConfiguration /* tests: the runtime refuses the launch */ : launch_render_kernels(c, L);
@@ -1981,11 +1986,17 @@ static int launch_frames(crt_ctx* c, uint32_t sppFirst, uint32_t nf, uint32_t pa
         *ahead = crt_ctx::Ahead{end, off, (const char*)slab, c->epoch, sppFirst, nf, passes, 0u};
         return 0;
     }
-    // ordered accumulation on the main stream (frame order = launch order), behind this launch
+    // ordered accumulation on the main stream (frame order = launch order), behind this launch.
+    // Which of the launch's tile blocks hold the texel form is told in RANKS of the tile order: the sky launch's [tileCount - sky, tileCount).  Invariant: this
+    // accumulate reads the order the launch's kernels read.  Every copy to dTileOrder (upload_tile_order, from update_tile_order in crt_render and from
+    // adopt_job_costs in planner_prepare above) is enqueued on the main stream: one made before this point is in front of this accumulate and is the one the
+    // render kernels waited for (orderReady); a later one is enqueued behind this accumulate on the same stream.  The class table (update_tile_class) and the job
+    // table follow the same protocol and are not read here at all.
     HIPCK(c, hipStreamWaitEvent(c->stream, ev.b, 0));
     if ((r = take_event(c, c->evAcc, &ev))) return r;
     HIPCK(c, hipEventRecord(ev.a, c->stream));
-    HIPCK(c, crt_launch_accumulate(slab, c->dAcc, c->tileFirst, c->tileStride, c->tileCount, (uint32_t)c->tilesX, (uint32_t)c->cfg.width, nf, passes, c->stream));
+    const uint32_t texelFirst = (L.pool && L.skyTexels) ? c->tileCount - L.sky : c->tileCount;     // (launch_render_kernels: a sky launch runs beside a pool launch only)
+    HIPCK(c, crt_launch_accumulate(slab, c->dAcc, c->dTileOrder, texelFirst, c->tileFirst, c->tileStride, c->tileCount, (uint32_t)c->tilesX, (uint32_t)c->cfg.width, nf, passes, c->stream));
     HIPCK(c, hipEventRecord(ev.b, c->stream));
     HIPCK(c, hipEventRecord(reg.freed, c->stream));
     c->inflight.push_back(reg);
@@ -2025,7 +2036,7 @@ int crt_render(crt_ctx* c, uint32_t spp_first, uint32_t frames, uint32_t passes)
             void* slab = c->pool + off;
             if (c->havePrim) HIPCK(c, crt_launch_render_prim(&c->hScene, &c->prim, slab, c->dCounters, c->tileFirst, c->tileStride, c->tileCount, (uint32_t)c->tilesX, spp_first + f0 * passes, nf, passes, c->stream));
             else HIPCK(c, crt_launch_render_alt(c->renderAccel, &c->hScene, &c->alt, &c->blasAlt[c->renderAccel - 1], slab, c->dCounters, c->tileFirst, c->tileStride, c->tileCount, (uint32_t)c->tilesX, spp_first + f0 * passes, nf, passes, c->stream));
-            HIPCK(c, crt_launch_accumulate(slab, c->dAcc, c->tileFirst, c->tileStride, c->tileCount, (uint32_t)c->tilesX, (uint32_t)c->cfg.width, nf, passes, c->stream));
+            HIPCK(c, crt_launch_accumulate(slab, c->dAcc, nullptr, c->tileCount, c->tileFirst, c->tileStride, c->tileCount, (uint32_t)c->tilesX, (uint32_t)c->cfg.width, nf, passes, c->stream));
             crt_ctx::Region reg; reg.off = off; reg.bytes = (size_t)((nf + 63u) / 64u) * windowBytes;
             if (c->freeEvents.empty()) HIPCK(c, hipEventCreateWithFlags(&reg.freed, hipEventDisableTiming));
             else { reg.freed = c->freeEvents.back(); c->freeEvents.pop_back(); }
@@ -3391,6 +3402,15 @@ extern "C" int crt_debug_sky_split(const uint32_t* cost, const uint8_t* cls, uin
 }
 // tests: render_sky_kernel launches of this context so far (never reset)
 extern "C" int crt_debug_sky_launches(crt_ctx* c) { return c ? (int)c->skyLaunches : -1; }
+// tests (no device needed): where the kernels put the samples of a launch of `frames` frames over tileCount tiles — device/sample_body.h's own position and size
+// functions, evaluated on the host.  pos[frame][tile][pixel][pass] = byte position in the slab, of the sample form or (texel != 0) of the texel form;
+// sizes = {bytes per window of samples, bytes per tile block}
+extern "C" int crt_debug_slab_layout(int texel, uint32_t frames, uint32_t tileCount, uint32_t passes, unsigned long long* pos, unsigned long long* sizes)
+{
+    if (!pos || !sizes || passes < 1 || passes > 4 || tileCount == 0 || frames == 0) return CRT_ERR_INVALID;
+    crt_slab_layout_probe(texel, frames, tileCount, passes, pos, sizes);
+    return CRT_OK;
+}
 // tools: the tile costs the planner works with (100 MHz ticks per local tile, as the measuring job left them: 0 for a tile its sky launch rendered), and the
 // machine time per window of the measuring job's pool launch and of its sky launch.  CRT_ERR_STATE until a measuring job's costs have been adopted.
 extern "C" int crt_debug_job_costs(crt_ctx* c, uint32_t* out, double* poolWindowTicks, double* skyWindowTicks)

@@ -35,9 +35,9 @@ namespace crt {
 
 // ------------------------------------------------------------------------------------------------------------
 // render_tiles_kernel<KIND, COUNT>: grid = (tiles owned by this ctx) x (64-frame windows of the launch), block = one wavefront (lane = frame).
-// slab layout: float4 [window][tileLocal][pixel 0..255][sample 0..64*passes), sample = frame*passes + pass (a partial last window leaves the
-// tail of its rows unused).  Pixel-major: the lanes of a wave are the consecutive samples of a pixel, so lanes that finish the same pixel
-// write neighbouring 16-byte pieces of one row and the L2 merges them into whole lines before they leave for HBM; accumulate_kernel
+// slab layout (sample_body.h, the 12-byte sample form): [window][tileLocal][pixel 0..255][sample 0..64*passes), sample = frame*passes + pass (a partial
+// last window leaves the tail of its rows unused).  Pixel-major: the lanes of a wave are the consecutive samples of a pixel, so lanes that finish the same
+// pixel write neighbouring 12-byte pieces of one row and the L2 merges them into whole lines before they leave for HBM; accumulate_kernel
 // transposes through LDS on the read side.
 //
 // Per-lane traversal state is ONE packed reference `cur` (layout.h), the 64-byte record it names — already
@@ -74,7 +74,7 @@ namespace crt {
 #define CRT_MIN_WAVES 5      // waves per SIMD the register budget must allow (<= 96 VGPRs)
 #endif
 template <int KIND, bool COUNT>
-__global__ __launch_bounds__(64, CRT_MIN_WAVES) void render_tiles_kernel(const Scene sc, float4* __restrict__ slab,
+__global__ __launch_bounds__(64, CRT_MIN_WAVES) void render_tiles_kernel(const Scene sc, char* __restrict__ slab,
                                                            Counters* __restrict__ counters, unsigned long long* __restrict__ tileClocks,
                                                            const uint32_t* __restrict__ tileOrder,
                                                            uint32_t tileFirst, uint32_t tileStride, uint32_t tileCount, uint32_t tilesX,
@@ -109,7 +109,7 @@ __global__ __launch_bounds__(64, CRT_MIN_WAVES) void render_tiles_kernel(const S
     sppFirst += win * 64u * passes;
     frames = (frames - win * 64u < 64u) ? frames - win * 64u : 64u;               // frames of THIS window (the last one may be partial)
     if (blockDesc) frames = frames > laneBase ? ((frames - laneBase < myLanes) ? frames - laneBase : myLanes) : 0u;
-    slab += (size_t)win * ((size_t)tileCount * 256u * 64u * passes);              // this window's region of the sample slab
+    slab += slab_block_position(win, tileCount, tl, 64u * passes);                 // this tile's block of this window's region of the sample slab
     const uint32_t tile = tileFirst + tl * tileStride;
     const uint32_t tx = tile % tilesX, ty = tile / tilesX;
     uint32_t* stk = lds + lane;
@@ -262,7 +262,7 @@ __global__ __launch_bounds__(64, CRT_MIN_WAVES) void render_tiles_kernel(const S
                 sample_unwind(fst, depth, L);                                     // most paths end at depth 0..2: a level is read only when some lane of the wave is that deep
                 uint32_t pix = item, pass = 0;
                 if (passes != 1u) { pix = item / passes; pass = item - pix * passes; }
-                slab[((size_t)tl * 256u + pix) * (64u * passes) + ((laneBase + lane) * passes + pass)] = make_float4(L.x, L.y, L.z, 0.0f);
+                store_sample(slab, slab_sample_offset(laneBase + lane, pix, 64u * passes, passes, pass), L);   // (`slab`: the tile's block of the window)
                 item++;
                 gen = true;
                 if (item >= items) { live = false; gen = false; }
@@ -444,59 +444,125 @@ __global__ __launch_bounds__(64, CRT_MIN_WAVES) void render_tiles_kernel(const S
 
 // ------------------------------------------------------------------------------------------------------------
 // accumulate_kernel: accumulator[pixel] += the slab's samples in (window, frame, pass) order — the reference's
-// `accumulator[..] +=` order, renderer.cpp:124.  The slab is pixel-major ([tile][pixel][sample]); this kernel streams it with
-// fully coalesced 1 KB loads and transposes through LDS:
+// `accumulator[..] +=` order, renderer.cpp:124.  The slab is pixel-major (sample_body.h: [window][tile][pixel][sample], 12-byte samples); this kernel
+// streams it with fully coalesced 768-byte loads and transposes through LDS:
 //   block = one owned tile, 4 wavefronts; wavefront w owns the tile's image rows 4w .. 4w+3 (16 pixels each) and never talks to the others;
-//   per (row, window, block of 64 samples): lane l fetches sample l of each of the row's 16 pixels (16 loads of 1 KB per wave in flight),
+//   per (row, window, block of 64 samples): lane l fetches sample l of each of the row's 16 pixels (16 loads of 768 bytes per wave in flight),
 //   parks them in the wave's LDS region, then lane (pixel j = l / 4, channel = l % 4) adds its 64 values IN ORDER to its running sum.
 // The running sums of a row are 64 consecutive floats of the accumulator (one 256-byte line).  Every addition of a channel happens
 // in one lane, in frame order; no float atomics anywhere.
+// Blocks [texelFirst, tileCount) — the ranks a render_sky_kernel launch wrote for THIS accumulate, a fact of the launch and uniform over the block — hold the
+// texel form instead: per (row, window) the 16 pixels' passes x 64 packed texels are 4 096 x passes contiguous bytes; they are parked in the order of the
+// additions, and the channel lanes unpack each with tex_unpack — the sample the 12-byte form would have held — and add it in (frame, pass) order.
+// The w channel: a float4 slab carried a 0.0f per sample and the w lanes added it.  x + 0.0f any number of times (>= 1) leaves the bits one such addition leaves
+// (-0.0f becomes +0.0f, a signalling NaN its quiet form, everything else itself), so the w lanes add 0.0f ONCE per row — a launch has at least one sample —
+// and a bound accumulator (crt_bind_accumulator: caller memory, any w) ends with the same bits as before.
 // ------------------------------------------------------------------------------------------------------------
-constexpr uint32_t kAccRowF4 = 65u;                  // float4 per pixel row in LDS: 64 samples + 1 pad (bank spread for the channel-wise reads)
-constexpr uint32_t kAccWaveLds = 16u * kAccRowF4 * 16u;   // bytes per wavefront
-__global__ __launch_bounds__(256) void accumulate_kernel(const float4* __restrict__ slab, float* __restrict__ acc,
+constexpr uint32_t kAccRowW = 64u * 3u + 3u;         // floats per pixel row in LDS, sample form: 64 samples + 1 pad (pixel j, channel c at bank 3j + c: the channel-wise reads spread)
+                                                     // texel form: 64 x passes + 1 dwords per pixel row (pixel j at bank j)
+constexpr uint32_t kAccWaveLds = 64u * 65u * 4u;     // bytes per wavefront: a texel trip's pixel rows (passes 1: 64 x 65 dwords = 16 640; 2: 32 x 129; 3: 16 x 193; 4: 16 x 257); the sample form needs 16 x kAccRowW x 4 = 12 480
+__device__ __forceinline__ float texel_channel(uint32_t texel, uint32_t ch) { const f3 L = tex_unpack(texel); return ch == 1u ? L.y : (ch == 2u ? L.z : L.x); }
+
+// The texel blocks of accumulate_kernel, for one wavefront's four tile rows.  A sky tile's rows are contiguous ([pixel][pass][frame]), so a trip takes G whole rows
+// of the wavefront — 4 with one pass, 2 with two, else 1: 64 (48 with three passes) loads of 256 bytes, 16 KB (12 KB) in flight per wavefront as in the sample form —
+// parks every texel at its pixel's [frame x passes + pass], the order of the additions, and each lane then runs its G rows' chains of additions side by side.
+template <uint32_t PASSES>
+__device__ __forceinline__ void accumulate_texel_rows(const char* __restrict__ slab, float* __restrict__ acc, uint32_t* lds, uint32_t tl, uint32_t tileCount, uint32_t wave, uint32_t lane,
+                                                      uint32_t x0, uint32_t y0, uint32_t W, uint32_t frames, size_t winStride)
+{
+    constexpr uint32_t G = PASSES == 1u ? 4u : (PASSES == 2u ? 2u : 1u), U = 16u * G * PASSES, rowLen = 64u * PASSES, pitch = rowLen + 1u;
+    const uint32_t pj = lane >> 2, ch = lane & 3u;
+    for (uint32_t r = 0; r < 4u; r += G) {
+        const uint32_t v = wave * 4u + r;                                      // first row of the trip
+        float* ap[G]; float a0[G], a[G];
+#pragma unroll
+        for (uint32_t g = 0; g < G; g++) { ap[g] = acc + ((size_t)(x0 + (size_t)(y0 + v + g) * W)) * 4u + lane; a0[g] = a[g] = *ap[g]; }
+        const char* __restrict__ base = slab + slab_texel_position(lane, tileCount, tl, v * 16u, rowLen, PASSES, 0u);   // lane = frame of the window
+        for (uint32_t f0 = 0; f0 < frames; f0 += 64u, base += winStride) {
+            const uint32_t S = ((frames - f0 < 64u) ? frames - f0 : 64u) * PASSES;   // valid texels of this window's rows (a row's tail is inside the block: fetched, never added)
+            uint32_t t[U];
+#pragma unroll
+            for (uint32_t u = 0; u < U; u++) t[u] = load_texel(base, slab_texel_offset(0u, u / PASSES, PASSES, u % PASSES));
+#pragma unroll
+            for (uint32_t u = 0; u < U; u++) lds[(u / PASSES) * pitch + lane * PASSES + u % PASSES] = t[u];
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                 // wave-private region: LDS executes a wave's operations in order
+            const uint32_t* myT = lds + pj * pitch;
+            uint32_t s = 0;
+            for (; s + 4u <= S; s += 4u) {
+                uint32_t x[G][4];
+#pragma unroll
+                for (uint32_t g = 0; g < G; g++)
+#pragma unroll
+                    for (uint32_t k = 0; k < 4u; k++) x[g][k] = myT[g * 16u * pitch + s + k];
+#pragma unroll
+                for (uint32_t k = 0; k < 4u; k++)
+#pragma unroll
+                    for (uint32_t g = 0; g < G; g++) a[g] += texel_channel(x[g][k], ch);
+            }
+            for (; s < S; s++)
+#pragma unroll
+                for (uint32_t g = 0; g < G; g++) a[g] += texel_channel(myT[g * 16u * pitch + s], ch);
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        }
+#pragma unroll
+        for (uint32_t g = 0; g < G; g++) *ap[g] = ch == 3u ? a0[g] + 0.0f : a[g];
+    }
+}
+
+__global__ __launch_bounds__(256) void accumulate_kernel(const char* __restrict__ slab, float* __restrict__ acc, const uint32_t* __restrict__ tileOrder, uint32_t texelFirst,
                                                           uint32_t tileFirst, uint32_t tileStride, uint32_t tileCount, uint32_t tilesX,
                                                           uint32_t W, uint32_t frames, uint32_t passes)
 {
-    extern __shared__ float4 accLds[];
-    const uint32_t tl = blockIdx.x, lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    if (tl >= tileCount) return;
+    extern __shared__ float accLds[];
+    const uint32_t rank = blockIdx.x, lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    if (rank >= tileCount) return;
+    const uint32_t tl = tileOrder ? tileOrder[rank] : rank;
     const uint32_t tile = tileFirst + tl * tileStride;
     const uint32_t x0 = (tile % tilesX) * 16u, y0 = (tile / tilesX) * 16u;
-    const uint32_t rowLen = 64u * passes;                                      // float4 per pixel row of the slab
-    const size_t winStride = (size_t)tileCount * 256u * rowLen;
-    float4* my4 = accLds + wave * (16u * kAccRowF4);
-    const float* myF = reinterpret_cast<const float*>(my4) + (lane >> 2) * (kAccRowF4 * 4u) + (lane & 3u);
+    const uint32_t rowLen = 64u * passes;                                      // samples per pixel row of the slab
+    const size_t winStride = slab_window_bytes(tileCount, passes);
+    float* myLds = accLds + wave * (kAccWaveLds / 4u);
+    if (rank >= texelFirst) {                                                  // (uniform over the block)
+        uint32_t* myU = reinterpret_cast<uint32_t*>(myLds);
+        if (passes == 1u) accumulate_texel_rows<1>(slab, acc, myU, tl, tileCount, wave, lane, x0, y0, W, frames, winStride);
+        else if (passes == 2u) accumulate_texel_rows<2>(slab, acc, myU, tl, tileCount, wave, lane, x0, y0, W, frames, winStride);
+        else if (passes == 3u) accumulate_texel_rows<3>(slab, acc, myU, tl, tileCount, wave, lane, x0, y0, W, frames, winStride);
+        else accumulate_texel_rows<4>(slab, acc, myU, tl, tileCount, wave, lane, x0, y0, W, frames, winStride);
+        return;
+    }
+    const uint32_t pj = lane >> 2, ch = lane & 3u, chR = ch == 3u ? 0u : ch;    // (a w lane reads along with x and drops the sum)
+    const float* myF = myLds + pj * kAccRowW + chR;
     for (uint32_t r = 0; r < 4u; r++) {
         const uint32_t v = wave * 4u + r;                                      // row of the tile
         float* __restrict__ ap = acc + ((size_t)(x0 + (size_t)(y0 + v) * W)) * 4u + lane;   // 16 pixels x 4 channels = 64 consecutive floats
-        float a = *ap;
-        const float4* __restrict__ rowBase = slab + ((size_t)tl * 256u + v * 16u) * rowLen;
+        const float a0 = *ap;
+        float a = a0;
+        const char* __restrict__ rowBase = slab + slab_position(0u, tileCount, tl, v * 16u, rowLen, passes, 0u);
         for (uint32_t f0 = 0; f0 < frames; f0 += 64u, rowBase += winStride) {
             const uint32_t S = ((frames - f0 < 64u) ? frames - f0 : 64u) * passes;   // valid samples of this window's rows
             for (uint32_t b = 0; b < S; b += 64u) {
                 const uint32_t n = (S - b < 64u) ? S - b : 64u;
-                float4 t[16];
+                Sample3 t[16];
                 if (lane < n) {
 #pragma unroll
-                    for (int j = 0; j < 16; j++) t[j] = rowBase[(size_t)j * rowLen + b + lane];
+                    for (uint32_t j = 0; j < 16u; j++) t[j] = load_sample(rowBase, slab_row_offset(j, rowLen, b + lane));
 #pragma unroll
-                    for (int j = 0; j < 16; j++) my4[j * kAccRowF4 + lane] = t[j];
+                    for (uint32_t j = 0; j < 16u; j++) { float* d = myLds + j * kAccRowW + lane * 3u; d[0] = t[j].x; d[1] = t[j].y; d[2] = t[j].z; }
                 }
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");             // wave-private region: LDS executes a wave's operations in order
                 uint32_t s = 0;
                 for (; s + 8u <= n; s += 8u) {
                     float x[8];
 #pragma unroll
-                    for (int k = 0; k < 8; k++) x[k] = myF[(s + k) * 4u];
+                    for (int k = 0; k < 8; k++) x[k] = myF[(s + k) * 3u];
 #pragma unroll
                     for (int k = 0; k < 8; k++) a += x[k];
                 }
-                for (; s < n; s++) a += myF[s * 4u];
+                for (; s < n; s++) a += myF[s * 3u];
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             }
         }
-        *ap = a;
+        *ap = ch == 3u ? a0 + 0.0f : a;
     }
 }
 
@@ -1079,9 +1145,10 @@ __global__ __launch_bounds__(64) void resolve_kernel(const float4* __restrict__ 
 // followed by resolve_kernel, in one pass.  Block = one owned tile, thread = pixel (v * 16 + u, the slab's pixel order).  Each channel gets the
 // frame's `passes` samples in pass order (accumulate_kernel's chain of adds); the pixel is formed from the new value as resolve_kernel forms it.
 // The tile's energy is summed by one lane over the 256 parked values in ProcessTile (v, u) order, so it is bit-exact (renderer.cpp:119,127-129).
-// slabWindow = the launch's window that holds the frame ([tileLocal][pixel][frame * passes + pass]).
+// slabWindow = the launch's window that holds the frame ([tileLocal][pixel][frame * passes + pass], the 12-byte sample form of sample_body.h: a render-ahead
+// launch never writes the texel form — its frames are read here after the tile order may have changed).
 // ------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void commit_frame_kernel(const float4* __restrict__ slabWindow, uint32_t frameInWindow, uint32_t passes,
+__global__ __launch_bounds__(256) void commit_frame_kernel(const char* __restrict__ slabWindow, uint32_t frameInWindow, uint32_t passes,
                                                             float4* __restrict__ acc, uint32_t* __restrict__ pixels, float* __restrict__ tileSums,
                                                             uint32_t tileFirst, uint32_t tileStride, uint32_t tileCount, uint32_t tilesX,
                                                             uint32_t W, float scale)
@@ -1092,9 +1159,10 @@ __global__ __launch_bounds__(256) void commit_frame_kernel(const float4* __restr
     const uint32_t tile = tileFirst + tl * tileStride;
     const uint32_t x0 = (tile % tilesX) * 16u, y0 = (tile / tilesX) * 16u;
     const size_t i = (x0 + (pix & 15u)) + (size_t)(y0 + (pix >> 4)) * W;
-    const float4* __restrict__ s = slabWindow + ((size_t)tl * 256u + pix) * (64u * passes) + frameInWindow * passes;
+    const size_t at = slab_position(frameInWindow, tileCount, tl, pix, 64u * passes, passes, 0u);   // (frame-in-window: the window is in `slabWindow`)
     float4 a = acc[i];
-    for (uint32_t p = 0; p < passes; p++) { const float4 t = s[p]; a.x += t.x; a.y += t.y; a.z += t.z; a.w += t.w; }
+    for (uint32_t p = 0; p < passes; p++) { const Sample3 t = load_sample(slabWindow, at + p * kSampleBytes); a.x += t.x; a.y += t.y; a.z += t.z; }
+    a.w += 0.0f;                                                                // as accumulate_kernel's w lanes: once for the frame's >= 1 samples
     acc[i] = a;
     const float px = a.x * scale, py = a.y * scale, pz = a.z * scale;
     tileE[pix] = px + py + pz;
@@ -1175,7 +1243,7 @@ extern "C" hipError_t crt_launch_render(const crt::Scene* sc, void* slab, crt::C
     if (blockDesc && (tileCount > 0x10000u || windows > 64u)) return hipErrorInvalidValue;
     if (rankCount == 0u || rankCount > tileCount) rankCount = tileCount;          // the first rankCount tiles of the order only (all windows)
     dim3 grid(blockDesc ? nBlocks : rankCount * windows), block(64);
-#define CRT_LAUNCH(K, C) hipLaunchKernelGGL((crt::render_tiles_kernel<K, C>), grid, block, ldsBytes + 15u * 64u * 4u /* throughput-factor columns */, stream, *sc, (float4*)slab, counters, tileClocks, tileOrder, tileFirst, tileStride, tileCount, tilesX, sppFirst, frames, passes, windows, blockDesc, tileCost, rankCount, launchClk)
+#define CRT_LAUNCH(K, C) hipLaunchKernelGGL((crt::render_tiles_kernel<K, C>), grid, block, ldsBytes + 15u * 64u * 4u /* throughput-factor columns */, stream, *sc, (char*)slab, counters, tileClocks, tileOrder, tileFirst, tileStride, tileCount, tilesX, sppFirst, frames, passes, windows, blockDesc, tileCost, rankCount, launchClk)
     if (sc->kind == 0) { if (collectStats) CRT_LAUNCH(0, true); else CRT_LAUNCH(0, false); }
     else { if (collectStats) CRT_LAUNCH(1, true); else CRT_LAUNCH(1, false); }
 #undef CRT_LAUNCH
@@ -1193,12 +1261,27 @@ extern "C" uint32_t crt_render_resident_waves(int device, int kind, uint32_t lds
     return (uint32_t)perCu * (uint32_t)cus;
 }
 
-extern "C" hipError_t crt_launch_accumulate(const void* slab, void* acc, uint32_t tileFirst, uint32_t tileStride, uint32_t tileCount,
+extern "C" size_t crt_slab_window_bytes(uint32_t tileCount, uint32_t passes) { return crt::slab_window_bytes(tileCount, passes); }
+
+extern "C" void crt_slab_layout_probe(int texel, uint32_t frames, uint32_t tileCount, uint32_t passes, unsigned long long* pos, unsigned long long* sizes)
+{
+    for (uint32_t fr = 0; fr < frames; fr++)
+        for (uint32_t tl = 0; tl < tileCount; tl++)
+            for (uint32_t pix = 0; pix < 256u; pix++)
+                for (uint32_t pass = 0; pass < passes; pass++)
+                    *pos++ = texel ? crt::slab_texel_position(fr, tileCount, tl, pix, 64u * passes, passes, pass) : crt::slab_position(fr, tileCount, tl, pix, 64u * passes, passes, pass);
+    sizes[0] = crt::slab_window_bytes(tileCount, passes);
+    sizes[1] = crt::slab_tile_bytes(passes);
+}
+
+extern "C" hipError_t crt_launch_accumulate(const void* slab, void* acc, const uint32_t* tileOrder, uint32_t texelFirst, uint32_t tileFirst, uint32_t tileStride, uint32_t tileCount,
                                             uint32_t tilesX, uint32_t W, uint32_t frames, uint32_t passes, hipStream_t stream)
 {
     if (tileCount == 0 || frames == 0) return hipSuccess;
+    if (passes < 1u || passes > 4u || (texelFirst < tileCount && !tileOrder)) return hipErrorInvalidValue;   // (the LDS region holds 4 passes of texel rows; texel blocks are ranks of an order)
     dim3 grid(tileCount), block(256);
-    hipLaunchKernelGGL(crt::accumulate_kernel, grid, block, 4u * crt::kAccWaveLds, stream, (const float4*)slab, (float*)acc, tileFirst, tileStride, tileCount, tilesX, W, frames, passes);
+    hipLaunchKernelGGL(crt::accumulate_kernel, grid, block, 4u * crt::kAccWaveLds, stream, (const char*)slab, (float*)acc, tileOrder, texelFirst, tileFirst, tileStride, tileCount, tilesX, W, frames,
+                       passes);
     return hipGetLastError();
 }
 
@@ -1297,7 +1380,7 @@ extern "C" hipError_t crt_launch_commit_frame(const void* slabWindow, uint32_t f
 {
     if (tileCount == 0) return hipSuccess;
     if (frameInWindow >= 64u || passes < 1u || passes > 4u) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(crt::commit_frame_kernel, dim3(tileCount), dim3(256), 0, stream, (const float4*)slabWindow, frameInWindow, passes, (float4*)acc, pixels, tileSums,
+    hipLaunchKernelGGL(crt::commit_frame_kernel, dim3(tileCount), dim3(256), 0, stream, (const char*)slabWindow, frameInWindow, passes, (float4*)acc, pixels, tileSums,
                        tileFirst, tileStride, tileCount, tilesX, W, scale);
     return hipGetLastError();
 }

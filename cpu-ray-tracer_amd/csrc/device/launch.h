@@ -16,8 +16,12 @@ hipError_t crt_launch_render(const crt::Scene* sc, void* slab, crt::Counters* co
     uint32_t tileCount, uint32_t tilesX, uint32_t sppFirst, uint32_t frames, uint32_t passes, uint32_t ldsBytes, int collectStats, const uint32_t* blockDesc, uint32_t nBlocks, uint32_t* tileCost,
     uint32_t rankCount, unsigned long long* launchClk, hipStream_t stream);
 uint32_t crt_render_resident_waves(int device, int kind, uint32_t ldsBytes);
-hipError_t crt_launch_accumulate(const void* slab, void* acc, uint32_t tileFirst, uint32_t tileStride, uint32_t tileCount, uint32_t tilesX, uint32_t W, uint32_t frames, uint32_t passes,
-    hipStream_t stream);
+size_t crt_slab_window_bytes(uint32_t tileCount, uint32_t passes);     // one 64-frame window of samples (sample_body.h slab_window_bytes)
+hipError_t crt_launch_accumulate(const void* slab, void* acc, const uint32_t* tileOrder /* block -> local tile, or nullptr: the identity */,
+    uint32_t texelFirst /* the blocks [texelFirst, tileCount) hold the texel form (a sky launch's ranks); tileCount: none */, uint32_t tileFirst, uint32_t tileStride, uint32_t tileCount,
+    uint32_t tilesX, uint32_t W, uint32_t frames, uint32_t passes, hipStream_t stream);
+// the layout test's host-only view of sample_body.h's position functions (crt_debug_slab_layout): pos[frame][tile][pixel][pass], sizes = {window, tile block} bytes
+void crt_slab_layout_probe(int texel, uint32_t frames, uint32_t tileCount, uint32_t passes, unsigned long long* pos, unsigned long long* sizes);
 hipError_t crt_launch_find_nearest(const crt::Scene* sc, const void* rays, void* hits, uint32_t n, crt::Counters* counters, uint32_t ldsBytes, uint32_t* cursor, hipStream_t stream);
 hipError_t crt_launch_is_occluded(const crt::Scene* sc, const void* rays, int32_t* occluded, uint32_t n, uint32_t ldsBytes, uint32_t* cursor, hipStream_t stream);
 hipError_t crt_launch_whitted(const crt::Scene* sc, int accel, const crt::AltAccelDev* alt, const crt::TlasAltDev* tl, void* acc, uint32_t* pixels, crt::Counters* counters, uint32_t ldsBytes,
@@ -48,6 +52,7 @@ size_t crt_debug_pool_timeline(unsigned long long* out, size_t cap);
 // ---- render_sky.hip: the kTileSky tiles of a job, ranks [rankFirst, rankFirst + skyTiles) of tileOrder, one wavefront per (tile, 64-frame window) ----
 hipError_t crt_launch_render_sky(const crt::Scene* sc, void* slab, crt::Counters* counters, const uint32_t* tileOrder, uint32_t rankFirst, uint32_t skyTiles, uint32_t tileFirst,
     uint32_t tileStride, uint32_t tileCount /* of the slab: all local tiles */, uint32_t tilesX, uint32_t sppFirst, uint32_t frames, uint32_t passes,
+    int texels /* the tiles' blocks in the texel form (sample_body.h): the launch's accumulate must be told the same ranks */,
     unsigned long long* launchClk /* a measuring job: ~first start, last end (100 MHz), or nullptr */, hipStream_t stream);
 
 // ---- render_seq.hip ----

@@ -123,7 +123,7 @@ __device__ __forceinline__ uint32_t rank_in(uint64_t m) { return __builtin_amdgc
 
 // REFBITS: the width of the scene's pool references (layout.h: 16 or 32) — of `cur`, of the stack entries and of the constants that classify them
 template <int KIND, bool COUNT, int S, int REFBITS = 16>
-__global__ __launch_bounds__(64, REFBITS == 32 ? CRT_POOL_WIDE_MIN_WAVES : CRT_POOL_MIN_WAVES) void render_pool_kernel(const Scene sc, float4* __restrict__ slab, float* __restrict__ facScratch, Counters* __restrict__ counters,
+__global__ __launch_bounds__(64, REFBITS == 32 ? CRT_POOL_WIDE_MIN_WAVES : CRT_POOL_MIN_WAVES) void render_pool_kernel(const Scene sc, char* __restrict__ slab, float* __restrict__ facScratch, Counters* __restrict__ counters,
                                                              unsigned long long* __restrict__ tileClocks, const uint32_t* __restrict__ tileOrder,
                                                              uint32_t tileFirst, uint32_t tileStride, uint32_t tileCount, uint32_t tilesX,
                                                              uint32_t sppFirst, uint32_t frames, uint32_t passes, uint32_t groups, uint32_t waveFrames, const uint32_t* __restrict__ waveTab, uint32_t tabBlocks, uint32_t longFrames,
@@ -192,7 +192,7 @@ __global__ __launch_bounds__(64, REFBITS == 32 ? CRT_POOL_WIDE_MIN_WAVES : CRT_P
     uint32_t live = nStreams; unsigned long long liveClk = wall_clock64();
 #endif
     const uint32_t items = 256u * passes;                                        // (pixel, pass) pairs in stream order
-    const uint32_t rowLen = 64u * passes;                                        // float4 per pixel row of the slab
+    const uint32_t rowLen = 64u * passes;                                        // samples per pixel row of the slab
     const f3 nil3 = mk3(0.0f, 0.0f, 0.0f);                                       // placeholder of values no lane reads
 
     // every stream starts in the END queue as "fresh": the pass only generates its first primary ray
@@ -608,7 +608,7 @@ __global__ __launch_bounds__(64, REFBITS == 32 ? CRT_POOL_WIDE_MIN_WAVES : CRT_P
                         for (int k = 4; k >= 0; k--)
                             if (depth > k) L = mk3(fk[3 * k], fk[3 * k + 1], fk[3 * k + 2]) * L;
                     }
-                    slab[sampleAt] = make_float4(L.x, L.y, L.z, 0.0f);
+                    store_sample(slab, sampleAt, L);
                 }
                 // every load of this pass is named as consumed here, at its end, on every path: the registers they wrote are re-used by the next sections, and a load
                 // the compiler cannot prove finished would put a wait for ALL outstanding loads — the record loads in flight included — in front of that first re-use
@@ -796,7 +796,7 @@ extern "C" hipError_t crt_launch_render_pool(const crt::Scene* sc, void* slab, v
     const uint32_t ldsBytes = crt_pool_lds_bytes(sc->stackDepth, S, sc->poolRefBits) + extraLds;
     { int dev = 0; if (hipGetDevice(&dev) != hipSuccess) return hipGetLastError(); if (ldsBytes > crt_pool_lds_limit(dev)) return hipErrorInvalidValue; }   // (the host routes such a scene to render_tiles_kernel)
 #define CRT_LAUNCH(K, C, SS) do { if (sc->poolRefBits == 32u) CRT_LAUNCH_R(K, C, SS, 32); else CRT_LAUNCH_R(K, C, SS, 16); } while (0)
-#define CRT_LAUNCH_R(K, C, SS, RB) hipLaunchKernelGGL((crt::render_pool_kernel<K, C, SS, RB>), grid, block, ldsBytes, stream, *sc, (float4*)slab, (float*)facScratch, counters, tileClocks, tileOrder, tileFirst, tileStride, tileCount, tilesX, sppFirst, frames, passes, groups, wf, waveTab, tabBlocks, longFrames, rankFirst, tileCost, launchClk, tileClass)
+#define CRT_LAUNCH_R(K, C, SS, RB) hipLaunchKernelGGL((crt::render_pool_kernel<K, C, SS, RB>), grid, block, ldsBytes, stream, *sc, (char*)slab, (float*)facScratch, counters, tileClocks, tileOrder, tileFirst, tileStride, tileCount, tilesX, sppFirst, frames, passes, groups, wf, waveTab, tabBlocks, longFrames, rankFirst, tileCost, launchClk, tileClass)
 #define CRT_LAUNCH_S(K, C) do { if (S == 64u) CRT_LAUNCH(K, C, 64); else CRT_LAUNCH(K, C, CRT_POOL_STREAMS); } while (0)
     if (sc->kind == 0) { if (collectStats) CRT_LAUNCH_S(0, true); else CRT_LAUNCH_S(0, false); }
     else { if (collectStats) CRT_LAUNCH_S(1, true); else CRT_LAUNCH_S(1, false); }

@@ -80,8 +80,8 @@ extern "C" hipError_t crt_launch_probe(const crt::Scene* sc, uint32_t tileFirst,
     dim3 grid((nProbe + crt::kSeqWaves - 1u) / crt::kSeqWaves), block(64u * crt::kSeqWaves);
     const uint32_t ldsBytes = crt::seq_lds_bytes(sc->stackDepth);
     if (hipMemsetAsync(tileCost, 0, (size_t)tileCount * 4, stream) != hipSuccess) return hipGetLastError();
-    if (sc->kind == 0) hipLaunchKernelGGL((crt::render_seq_kernel<crt::BvhWorld<0>, true>), grid, block, ldsBytes, stream, *sc, crt::BvhWorld<0>{}, (float4*)nullptr, (crt::Counters*)nullptr, tileFirst, tileStride, tileCount, tilesX, 1u, 64u, 1u, nProbe, tileCost);
-    else hipLaunchKernelGGL((crt::render_seq_kernel<crt::BvhWorld<1>, true>), grid, block, ldsBytes, stream, *sc, crt::BvhWorld<1>{}, (float4*)nullptr, (crt::Counters*)nullptr, tileFirst, tileStride, tileCount, tilesX, 1u, 64u, 1u, nProbe, tileCost);
+    if (sc->kind == 0) hipLaunchKernelGGL((crt::render_seq_kernel<crt::BvhWorld<0>, true>), grid, block, ldsBytes, stream, *sc, crt::BvhWorld<0>{}, (char*)nullptr, (crt::Counters*)nullptr, tileFirst, tileStride, tileCount, tilesX, 1u, 64u, 1u, nProbe, tileCost);
+    else hipLaunchKernelGGL((crt::render_seq_kernel<crt::BvhWorld<1>, true>), grid, block, ldsBytes, stream, *sc, crt::BvhWorld<1>{}, (char*)nullptr, (crt::Counters*)nullptr, tileFirst, tileStride, tileCount, tilesX, 1u, 64u, 1u, nProbe, tileCost);
     return hipGetLastError();
 }
 

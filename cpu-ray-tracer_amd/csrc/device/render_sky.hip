@@ -3,8 +3,8 @@
 //
 // Every path of such a tile is Renderer::Sample's first return (renderer.cpp:52-55): two RNG draws, the primary ray, its normalisation, GetSkyColor's one texel.
 // The pool carries these streams through its machinery all the same — parked in LDS, queued on the END ring, popped by a pass at 53 of 64 lanes inside a trip —
-// and its sample store scatters 16 bytes into 1-KB pixel rows.  Here a lane IS a stream: lane l renders frame l of a 64-frame window and walks the tile's 256
-// pixels in registers.  No LDS, no queue, no trip, 64 of 64 lanes, and the 64 lanes' samples of one (pixel, pass) are one contiguous row of the slab.
+// and its sample store scatters 12 bytes into 768-byte pixel rows.  Here a lane IS a stream: lane l renders frame l of a 64-frame window and walks the tile's 256
+// pixels in registers.  No LDS, no queue, no trip, 64 of 64 lanes, and the 64 lanes' texels of one (pixel, pass) are 256 contiguous bytes of the slab.
 //
 // Which slab position and which RNG stream belong to a (tile, frame) is the pool kernel's definition (sample_body.h stream_seed / slab_position), and every step
 // of the path is the function the pool kernel's END pass calls: the accumulator cannot tell which of the two kernels rendered a tile.
@@ -14,9 +14,11 @@
 namespace crt {
 
 // block -> (sky rank, 64-frame window), rank-major; the sky tiles are the ranks [rankFirst, rankFirst + skyTiles) of the tile order (abi.cpp: its tail)
-__global__ __launch_bounds__(64) void render_sky_kernel(const Scene sc, float4* __restrict__ slab, Counters* __restrict__ counters, const uint32_t* __restrict__ tileOrder,
+// texels (the same for the whole launch): the tiles' blocks take the texel form — the sample IS tex_unpack(texel), and the launch's accumulate unpacks it — else
+// the 12-byte sample form (sample_body.h)
+__global__ __launch_bounds__(64) void render_sky_kernel(const Scene sc, char* __restrict__ slab, Counters* __restrict__ counters, const uint32_t* __restrict__ tileOrder,
                                                         uint32_t rankFirst, uint32_t skyTiles, uint32_t tileFirst, uint32_t tileStride, uint32_t tileCount, uint32_t tilesX,
-                                                        uint32_t sppFirst, uint32_t frames, uint32_t passes, uint32_t groups, unsigned long long* __restrict__ launchClk)
+                                                        uint32_t sppFirst, uint32_t frames, uint32_t passes, uint32_t groups, uint32_t texels, unsigned long long* __restrict__ launchClk)
 {
     const uint32_t lane = threadIdx.x;
     const uint32_t r = blockIdx.x / groups, grp = blockIdx.x - r * groups;
@@ -39,8 +41,9 @@ __global__ __launch_bounds__(64) void render_sky_kernel(const Scene sc, float4* 
             const f3 v = primary_target(camPos, TL, right, down, sc.invW, sc.invH, tx, ty, pix, seed);
             const f3 D = v * rcp_exact(sqrt_exact(dot3(v, v)));                  // normalize()
             float phi, theta; sky_angles(D, phi, theta);                         // GetSkyColor (file_scene.cpp:142-154)
-            const f3 L = tex_unpack(sc.texels[tex_index(sc.skyOffset, sc.skyW, sc.skyH, phi * CRT_INV2PI, theta * CRT_INVPI)]);
-            slab[slab_position(fr, tileCount, tl, pix, rowLen, passes, pass)] = make_float4(L.x, L.y, L.z, 0.0f);
+            const uint32_t texel = sc.texels[tex_index(sc.skyOffset, sc.skyW, sc.skyH, phi * CRT_INV2PI, theta * CRT_INVPI)];
+            if (texels) store_texel(slab, slab_texel_position(fr, tileCount, tl, pix, rowLen, passes, pass), texel);
+            else store_sample(slab, slab_position(fr, tileCount, tl, pix, rowLen, passes, pass), tex_unpack(texel));
             if (++pass == passes) { pass = 0; pix++; }
         }
         paths = items;
@@ -54,13 +57,13 @@ __global__ __launch_bounds__(64) void render_sky_kernel(const Scene sc, float4* 
 
 extern "C" hipError_t crt_launch_render_sky(const crt::Scene* sc, void* slab, crt::Counters* counters, const uint32_t* tileOrder, uint32_t rankFirst, uint32_t skyTiles,
                                             uint32_t tileFirst, uint32_t tileStride, uint32_t tileCount, uint32_t tilesX, uint32_t sppFirst, uint32_t frames, uint32_t passes,
-                                            unsigned long long* launchClk, hipStream_t stream)
+                                            int texels, unsigned long long* launchClk, hipStream_t stream)
 {
     if (skyTiles == 0 || frames == 0) return hipSuccess;
     if (!tileOrder || rankFirst > tileCount || skyTiles > tileCount - rankFirst || passes == 0) return hipErrorInvalidValue;
     const uint32_t groups = (frames + 63u) / 64u;
     if ((unsigned long long)skyTiles * groups > 0x7fffffffull) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(crt::render_sky_kernel, dim3(skyTiles * groups), dim3(64), 0, stream, *sc, (float4*)slab, counters, tileOrder, rankFirst, skyTiles, tileFirst, tileStride,
-                       tileCount, tilesX, sppFirst, frames, passes, groups, launchClk);
+    hipLaunchKernelGGL(crt::render_sky_kernel, dim3(skyTiles * groups), dim3(64), 0, stream, *sc, (char*)slab, counters, tileOrder, rankFirst, skyTiles, tileFirst, tileStride,
+                       tileCount, tilesX, sppFirst, frames, passes, groups, texels ? 1u : 0u, launchClk);
     return hipGetLastError();
 }

@@ -129,16 +129,53 @@ __device__ __forceinline__ void sample_unwind(const float* fst, int depth, f3& L
 // ------------------------------------------------------------------------------------------------------------
 // the ray's start
 // ------------------------------------------------------------------------------------------------------------
-// The RNG stream of frame `frame` (of the launch; `passes` samples per pixel and frame) of tile (tx, ty) of a W-wide image starts here (renderer.cpp:120), and its
-// sample of (pixel, pass) lies here in the launch's slab: [64-frame window][local tile][pixel][64 frames x passes] float4.  render_pool_kernel and render_sky_kernel.
+// The RNG stream of frame `frame` (of the launch; `passes` samples per pixel and frame) of tile (tx, ty) of a W-wide image starts here (renderer.cpp:120).
 __device__ __forceinline__ uint32_t stream_seed(uint32_t tx, uint32_t ty, uint32_t W, uint32_t sppFirst, uint32_t frame, uint32_t passes)
 {
     return init_seed(tx + ty * W + (sppFirst + frame * passes) * 1799u);
 }
-__device__ __forceinline__ size_t slab_position(uint32_t fr, uint32_t tileCount, uint32_t tl, uint32_t pix, uint32_t rowLen, uint32_t passes, uint32_t pass)
+
+// ------------------------------------------------------------------------------------------------------------
+// the sample slab of a launch: [64-frame window][local tile] tile blocks of 256 pixel rows of rowLen = 64 x passes samples.  Every writer (render_pool_kernel,
+// render_tiles_kernel, render_sky_kernel, render_seq_kernel) and every reader (accumulate_kernel, commit_frame_kernel) takes its byte positions from here.
+//   sample form  12 bytes: L.x, L.y, L.z.  Sample (frame, pass) of a pixel at [frame-in-window x passes + pass] of the pixel's row: the order they are added in.
+//   texel form    4 bytes: the packed sky texel, before tex_unpack.  Only the tiles of a render_sky_kernel launch whose accumulate follows at once hold it
+//                 (abi.cpp launch_frames).  Its rows lie in the same tile block, [pixel][pass][frame-in-window]: the 64 lanes of one (pixel, pass) of that kernel
+//                 write 256 contiguous bytes, and the tile touches the first third of its block only.
+// Positions are bytes from the slab's start, 4-byte aligned.  (__host__ too: crt_debug_slab_layout evaluates them for the layout test without a device.)
+// ------------------------------------------------------------------------------------------------------------
+constexpr uint32_t kSampleBytes = 12u, kTexelBytes = 4u;
+struct Sample3 { float x, y, z; };
+__host__ __device__ __forceinline__ size_t slab_tile_bytes(uint32_t passes) { return (size_t)(256u * 64u * kSampleBytes) * passes; }
+__host__ __device__ __forceinline__ size_t slab_window_bytes(uint32_t tileCount, uint32_t passes) { return (size_t)tileCount * slab_tile_bytes(passes); }
+// a position = the tile's block of the frame's window + the sample's place inside the block (under 2^20: 32-bit arithmetic).  A kernel whose wavefront stays with
+// one (window, tile) — render_tiles_kernel, render_seq_kernel — adds the block to its slab pointer once and stores at slab_sample_offset.
+__host__ __device__ __forceinline__ size_t slab_block_position(uint32_t window, uint32_t tileCount, uint32_t tl, uint32_t rowLen)
 {
-    return (((size_t)(fr >> 6) * tileCount + tl) * 256u + pix) * rowLen + ((fr & 63u) * passes + pass);
+    return ((size_t)window * tileCount + tl) * (256u * kSampleBytes) * rowLen;
 }
+// (slab_row_offset: by the sample's place in its pixel row, frameInWindow x passes + pass — what a reader that walks rows has in hand)
+__host__ __device__ __forceinline__ uint32_t slab_row_offset(uint32_t pix, uint32_t rowLen, uint32_t sampleInRow) { return (pix * rowLen + sampleInRow) * kSampleBytes; }
+__host__ __device__ __forceinline__ uint32_t slab_sample_offset(uint32_t frameInWindow, uint32_t pix, uint32_t rowLen, uint32_t passes, uint32_t pass)
+{
+    return slab_row_offset(pix, rowLen, frameInWindow * passes + pass);
+}
+__host__ __device__ __forceinline__ uint32_t slab_texel_offset(uint32_t frameInWindow, uint32_t pix, uint32_t passes, uint32_t pass)
+{
+    return ((pix * passes + pass) * 64u + frameInWindow) * kTexelBytes;
+}
+__host__ __device__ __forceinline__ size_t slab_position(uint32_t fr, uint32_t tileCount, uint32_t tl, uint32_t pix, uint32_t rowLen, uint32_t passes, uint32_t pass)
+{
+    return slab_block_position(fr >> 6, tileCount, tl, rowLen) + slab_sample_offset(fr & 63u, pix, rowLen, passes, pass);
+}
+__host__ __device__ __forceinline__ size_t slab_texel_position(uint32_t fr, uint32_t tileCount, uint32_t tl, uint32_t pix, uint32_t rowLen, uint32_t passes, uint32_t pass)
+{
+    return slab_block_position(fr >> 6, tileCount, tl, rowLen) + slab_texel_offset(fr & 63u, pix, passes, pass);
+}
+__device__ __forceinline__ void store_sample(char* __restrict__ slab, size_t at, f3 L) { Sample3 s; s.x = L.x; s.y = L.y; s.z = L.z; *reinterpret_cast<Sample3*>(slab + at) = s; }
+__device__ __forceinline__ Sample3 load_sample(const char* __restrict__ slab, size_t at) { return *reinterpret_cast<const Sample3*>(slab + at); }
+__device__ __forceinline__ void store_texel(char* __restrict__ slab, size_t at, uint32_t texel) { *reinterpret_cast<uint32_t*>(slab + at) = texel; }
+__device__ __forceinline__ uint32_t load_texel(const char* __restrict__ slab, size_t at) { return *reinterpret_cast<const uint32_t*>(slab + at); }
 // ProcessTile + Camera::GetPrimaryRay (renderer.cpp:125-126, camera.h:23-30) for pixel `pix` of tile (tx, ty): P - camPos, still to be normalised.
 // right / down = topRight - topLeft / bottomLeft - topLeft
 __device__ __forceinline__ f3 primary_target(f3 camPos, f3 TL, f3 right, f3 down, float invW, float invH, uint32_t tx, uint32_t ty, uint32_t pix, uint32_t& seed)

@@ -64,7 +64,7 @@ __device__ __forceinline__ bool sample_step(const Scene& sc, const World& world,
 // shading steps its 64 paths took to tileCost[tile] (zeroed by the host) — an estimate of what the tile's streams will cost (a stream = 256 such paths), available well
 // under a millisecond after a camera or scene change instead of after a first full render.
 template <class World, bool PROBE>
-__global__ __launch_bounds__(256, 4) void render_seq_kernel(const Scene sc, const World world, float4* __restrict__ slab, Counters* __restrict__ counters,
+__global__ __launch_bounds__(256, 4) void render_seq_kernel(const Scene sc, const World world, char* __restrict__ slab, Counters* __restrict__ counters,
                                                            uint32_t tileFirst, uint32_t tileStride, uint32_t tileCount, uint32_t tilesX,
                                                            uint32_t sppFirst, uint32_t frames, uint32_t passes, uint32_t nEntries, uint32_t* __restrict__ tileCost)
 {
@@ -78,7 +78,7 @@ __global__ __launch_bounds__(256, 4) void render_seq_kernel(const Scene sc, cons
     sppFirst += win * 64u * passes;
     frames = (frames - win * 64u < 64u) ? frames - win * 64u : 64u;               // frames of THIS window (the last one may be partial)
     if (lane >= frames) return;
-    slab += (size_t)win * ((size_t)tileCount * 256u * 64u * passes);              // this window's region of the sample slab
+    if (!PROBE) slab += slab_block_position(win, tileCount, tl, 64u * passes);     // this tile's block of this window's region of the sample slab
     const uint32_t tile = tileFirst + tl * tileStride;
     const uint32_t tx = tile % tilesX, ty = tile / tilesX;
     // this lane's LDS columns: the traversal stack, then the throughput factors
@@ -110,7 +110,7 @@ __global__ __launch_bounds__(256, 4) void render_seq_kernel(const Scene sc, cons
         if (!PROBE) {
             uint32_t pass = 0;
             if (passes != 1u) pass = item - pix * passes;
-            slab[((size_t)tl * 256u + pix) * (64u * passes) + (lane * passes + pass)] = make_float4(L.x, L.y, L.z, 0.0f);
+            store_sample(slab, slab_sample_offset(lane, pix, 64u * passes, passes, pass), L);   // (`slab`: the tile's block of the window)
         } else if (L.x != L.x) steps++;                                            // (keeps the probe's shading arithmetic alive)
     }
     if (PROBE) { const uint32_t sum = wave_sum(steps); if (lane == 0) atomicAdd(&tileCost[tl], sum); return; }
@@ -126,7 +126,7 @@ hipError_t launch_render_seq(const Scene* sc, const World& world, void* slab, Co
 {
     const uint32_t entries = tileCount * ((frames + 63u) / 64u);
     hipLaunchKernelGGL((render_seq_kernel<World, false>), dim3((entries + kSeqWaves - 1u) / kSeqWaves), dim3(64u * kSeqWaves), seq_lds_bytes(world.stack_words(*sc)), stream,
-                       *sc, world, (float4*)slab, counters, tileFirst, tileStride, tileCount, tilesX, sppFirst, frames, passes, entries, (uint32_t*)nullptr);
+                       *sc, world, (char*)slab, counters, tileFirst, tileStride, tileCount, tilesX, sppFirst, frames, passes, entries, (uint32_t*)nullptr);
     return hipGetLastError();
 }
 
