@@ -110,10 +110,10 @@ HIT_INFO_DTYPE = np.dtype([("I", "<f4", 3), ("material", "<i4"), ("N", "<f4", 3)
 MATERIAL_MISS, MATERIAL_INVALID = -1, -2       # crt_hit_info.material of a miss / of a record whose objIdx or triIdx the scene does not have
 
 # every symbol include/crt_abi.h and include/crt_host.h declare (tests check the library exports all of them)
-ABI_SYMBOLS = ["crt_build_grid_device", "crt_get_grid", "crt_update_transforms_device", "crt_sample", "crt_sample_device", "crt_refit_device", "crt_get_hit_info", "crt_get_hit_info_device", "crt_get_sky_color", "crt_get_sky_color_device", "crt_get_light", "crt_upload_blas_accel", "crt_is_occluded", "crt_find_nearest_device", "crt_is_occluded_device", "crt_upload_primitive_scene", "crt_set_render_accel", "crt_upload_alt_accel", "crt_find_nearest_alt", "crt_update_scene", "crt_abi_version", "crt_device_count", "crt_create", "crt_destroy", "crt_last_error", "crt_upload_scene", "crt_set_camera",
+ABI_SYMBOLS = ["crt_build_kdtree_device", "crt_get_kdtree", "crt_build_grid_device", "crt_get_grid", "crt_update_transforms_device", "crt_sample", "crt_sample_device", "crt_refit_device", "crt_get_hit_info", "crt_get_hit_info_device", "crt_get_sky_color", "crt_get_sky_color_device", "crt_get_light", "crt_upload_blas_accel", "crt_is_occluded", "crt_find_nearest_device", "crt_is_occluded_device", "crt_upload_primitive_scene", "crt_set_render_accel", "crt_upload_alt_accel", "crt_find_nearest_alt", "crt_update_scene", "crt_abi_version", "crt_device_count", "crt_create", "crt_destroy", "crt_last_error", "crt_upload_scene", "crt_set_camera",
                "crt_render", "crt_tick", "crt_reserve", "crt_whitted_tick", "crt_whitted_tick_inspect", "crt_sync", "crt_clear", "crt_read_accumulator", "crt_resolve_screen", "crt_find_nearest", "crt_get_counters",
                "crt_reset_counters", "crt_get_timing", "crt_get_tile_clocks", "crt_bind_accumulator", "crt_accumulator_device_ptr"]
-HOST_SYMBOLS = ["crt_host_scene_build_grid_device", "crt_host_grid_build", "crt_host_scene_update_transforms_device", "crt_host_scene_bvh_refit_device", "crt_host_scene_blas_alt_info", "crt_host_scene_blas_alt_copy", "crt_host_primitive_scene_create", "crt_host_primitive_scene_free", "crt_host_primitive_scene_set_time", "crt_host_primitive_scene_desc", "crt_host_primitive_scene_upload", "crt_host_scene_build_alt", "crt_host_scene_upload_alt", "crt_host_scene_alt_info", "crt_host_scene_alt_copy", "crt_host_scene_set_transform", "crt_host_scene_update", "crt_host_math_probe", "crt_host_vertex_dedup", "crt_host_last_error", "crt_host_scene_load", "crt_host_scene_free", "crt_host_scene_upload", "crt_host_scene_kind",
+HOST_SYMBOLS = ["crt_host_scene_build_kdtree_device", "crt_host_kd_build", "crt_host_scene_build_grid_device", "crt_host_grid_build", "crt_host_scene_update_transforms_device", "crt_host_scene_bvh_refit_device", "crt_host_scene_blas_alt_info", "crt_host_scene_blas_alt_copy", "crt_host_primitive_scene_create", "crt_host_primitive_scene_free", "crt_host_primitive_scene_set_time", "crt_host_primitive_scene_desc", "crt_host_primitive_scene_upload", "crt_host_scene_build_alt", "crt_host_scene_upload_alt", "crt_host_scene_alt_info", "crt_host_scene_alt_copy", "crt_host_scene_set_transform", "crt_host_scene_update", "crt_host_math_probe", "crt_host_vertex_dedup", "crt_host_last_error", "crt_host_scene_load", "crt_host_scene_free", "crt_host_scene_upload", "crt_host_scene_kind",
                 "crt_host_scene_triangle_count", "crt_host_scene_bvh_count", "crt_host_scene_bvh_info", "crt_host_scene_bvh_copy",
                 "crt_host_scene_bvh_move_and_refit", "crt_host_scene_blas_transform", "crt_host_scene_tlas_copy", "crt_host_camera_state", "crt_host_renderer_create",
                 "crt_host_renderer_destroy", "crt_host_renderer_init", "crt_host_renderer_set_camera", "crt_host_renderer_set_passes",
@@ -571,6 +571,24 @@ class Context:
         self._ck(self.L.crt_get_grid(self.h, C.c_uint32(bvh), None, None, None, None, None, None, _p(start), _p(r)))
         return dict(resolution=res, cellSize=f[0:3].copy(), boundsMin=f[3:6].copy(), boundsMax=f[6:9].copy(), cellStart=start, refs=r[:refs.value])
 
+    def build_kdtree_device(self, bvh, positions, stream=None):
+        """crt_build_kdtree_device: KDTree::Build / BLASKDTree::Build of uploaded BVH `bvh` on the GPU from `positions` (refit_device's tensor), enqueued on `stream`
+        (default torch.cuda.current_stream()); returns once the last level's counts have been read back (one host wait per level of the tree).  The tree becomes the
+        FileScene's ACCEL_KDTREE structure (its grid is marked absent), or BLAS `bvh`'s part of a two-level scene's uploaded KD set, which is live again once every
+        refitted BLAS has been rebuilt.  The BVH / TLAS are not touched: refit_device (+ update_transforms_device) with the same positions keeps them in step."""
+        def run(st):
+            ptr, n = self._positions(positions, "build_kdtree_device")
+            self._ck(self.L.crt_build_kdtree_device(self.h, C.c_uint32(bvh), ptr, n, C.c_void_p(st.cuda_stream)))
+        return self._enqueue(stream, run)
+
+    def get_kdtree(self, bvh=0):
+        """crt_get_kdtree: the live KD-tree of a FileScene (bvh 0) or of BLAS `bvh` of a two-level set, uploaded or device-built: dict(nodes, refs, height)"""
+        nn, nr, h = C.c_uint32(), C.c_uint32(), C.c_uint32()
+        self._ck(self.L.crt_get_kdtree(self.h, C.c_uint32(bvh), C.byref(nn), C.byref(nr), C.byref(h), None, None))
+        nodes = np.zeros(nn.value, KD_NODE_DTYPE); r = np.zeros(max(nr.value, 1), np.uint32)
+        self._ck(self.L.crt_get_kdtree(self.h, C.c_uint32(bvh), None, None, None, _p(nodes), _p(r)))
+        return dict(nodes=nodes, refs=r[:nr.value], height=int(h.value))
+
     def _enqueue(self, stream, run):
         """run(st) on the torch stream `stream` (default: the current one).  Torch's default stream has the handle 0, which the ABI reads as the context's own
         stream: on it the query runs on a side stream that waits for it and that it waits for in turn (events, no host wait)."""
@@ -730,6 +748,19 @@ class HostScene:
             ptr, n = ctx._positions(positions, "build_grid_device")
             self._ck(self.L.crt_host_scene_build_grid_device(self.h, ctx.h, int(i), ptr, n, C.c_void_p(st.cuda_stream)))
         return ctx._enqueue(stream, run)
+
+    def build_kdtree_device(self, ctx, i, positions, stream=None):
+        """crt_host_scene_build_kdtree_device: the KD-tree of BVH i rebuilt on the GPU from a positions tensor (Context.build_kdtree_device's), then this scene's KD
+        mirror refreshed from the device: blas_alt(ACCEL_KDTREE, i) / kdtree() describe the live tree."""
+        def run(st):
+            ptr, n = ctx._positions(positions, "build_kdtree_device")
+            self._ck(self.L.crt_host_scene_build_kdtree_device(self.h, ctx.h, int(i), ptr, n, C.c_void_p(st.cuda_stream)))
+        return ctx._enqueue(stream, run)
+
+    def kdtree(self):
+        """the FileScene's KD-tree mirror (after build_alt(ACCEL_KDTREE) or build_kdtree_device), in build_alt's layout"""
+        return self._alt(ACCEL_KDTREE, lambda info: self.L.crt_host_scene_alt_info(self.h, ACCEL_KDTREE, info),
+                         lambda a, b, c: self.L.crt_host_scene_alt_copy(self.h, ACCEL_KDTREE, a, b, c))
 
     def grid(self):
         """the FileScene's grid mirror (after build_alt(ACCEL_GRID) or build_grid_device), in build_alt's layout"""
@@ -978,6 +1009,21 @@ def host_grid_build(positions):
     start = np.zeros(int(res.prod()) + 1, np.uint32); r = np.zeros(max(refs.value, 1), np.int32)
     ck(L.crt_host_grid_build(_p(pos), C.c_uint32(len(pos)), None, None, None, _p(start), _p(r)))
     return dict(resolution=res, cellSize=f[0:3].copy(), boundsMin=f[3:6].copy(), boundsMax=f[6:9].copy(), cellStart=start, refs=r[:refs.value])
+
+
+def host_kd_build(positions):
+    """test / tool entry: the host front's KDTree::Build (csrc/host/accel_alt.cpp) over bare positions ((n, 3, 3) float32), in HostScene.build_alt's layout"""
+    pos = np.ascontiguousarray(positions, np.float32).reshape(-1, 9)
+    L = lib()
+    info = (C.c_uint32 * 4)()
+
+    def ck(rc):
+        if rc != 0:
+            raise CrtError(rc, L.crt_host_last_error().decode())
+    ck(L.crt_host_kd_build(_p(pos), C.c_uint32(len(pos)), info, None, None))
+    nodes = np.zeros(info[0], KD_NODE_DTYPE); r = np.zeros(max(info[1], 1), np.uint32)
+    ck(L.crt_host_kd_build(_p(pos), C.c_uint32(len(pos)), None, _p(nodes), _p(r)))
+    return dict(nodes=nodes, refs=r[:info[1]], maxDepth=int(info[2]), nodesUsed=int(info[3]))
 
 
 def host_vertex_dedup(v8):

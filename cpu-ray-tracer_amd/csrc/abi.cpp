@@ -160,6 +160,28 @@ struct crt_ctx {
     // current vertices (an upload sets all, CRT_UPDATE_BOUNDS clears all, crt_refit_device clears its BLAS's, crt_build_grid_device sets its BLAS's): the set is live
     // (haveBlas[1]) iff every flag is set.  Kept while the set is dropped: the buffers are still held, and a rebuild carries the other BLASes' parts over.
     struct BlasGrid { std::vector<crt::BlasAltDesc> desc; std::vector<uint32_t> cells, refs; std::vector<uint8_t> current; bool held = false; } blasGrid;
+    // crt_build_kdtree_device (device/kd_build.hip): the kernels' state block and its pinned copy; per level the nodes, the references and their owner nodes, kept
+    // until the finalise pass; the triangle boxes, the two scan arrays and the chunk sums — all grown on demand and kept between calls; `back` behind each level's
+    // read-back (the host waits), `done` behind the build (sceneReady names it)
+    struct KdBuild {
+        static constexpr uint32_t kLevels = crt::kKdMaxDepth + 1u;
+        crt::KdBuildState* dState = nullptr; crt::KdBuildState* hState = nullptr;
+        struct Level { void* nodes = nullptr; void* refs = nullptr; void* owner = nullptr; size_t nodeCap = 0, refCap = 0, ownerCap = 0; } lv[kLevels];
+        void* dTriBox = nullptr; void* dNodeItems = nullptr; void* dRefItems = nullptr; void* dChunks = nullptr; size_t triBoxCap = 0, nodeItemCap = 0, refItemCap = 0, chunkCap = 0;
+        hipEvent_t back = nullptr, done = nullptr, t0 = nullptr, t1 = nullptr; bool built = false, timed = false; uint32_t blocks = 0;
+        uint32_t waits = 0, levels = 0; double waitMs = 0;    // the last call's host waits, its levels, the wall time of the waits together (crt_debug_kdtree_build_ms)
+        void release()
+        {
+            for (hipEvent_t e : {back, done, t0, t1}) if (e) (void)hipEventDestroy(e);
+            for (Level& l : lv) for (void* p : {l.nodes, l.refs, l.owner}) (void)hipFree(p);
+            for (void* p : {(void*)dState, dTriBox, dNodeItems, dRefItems, dChunks}) (void)hipFree(p);
+            (void)hipHostFree(hState); *this = KdBuild{};
+        }
+    } kdBuild;
+    uint32_t kdNodeCount = 0, kdRefCount = 0;   // nodes / leaf references of the FileScene's live KD-tree (uploaded or built on the device)
+    // the two-level KD set as the device holds it, the grid set's counterpart: descriptors, nodes / references / height per BLAS, and the "kd current" flags (an
+    // upload sets all, CRT_UPDATE_BOUNDS clears all, crt_refit_device clears its BLAS's, crt_build_kdtree_device sets its BLAS's): live (haveBlas[0]) iff all are set
+    struct BlasKd { std::vector<crt::BlasAltDesc> desc; std::vector<uint32_t> nodes, refs, height; std::vector<uint8_t> current; bool held = false; } blasKd;
     hipEvent_t altReady = nullptr;        // recorded behind the last crt_upload_alt_accel's copies (device queries on other streams wait for it)
     // Latency mode of single-window launches (render_tiles_kernel's block table), driven by measurement — see next_block_table.  Stage 0 = the table solved from the cost probe's
     // estimates (one wavefront per tile when there was no probe); stages 1 .. kLatStages = tables solved from the tile costs the stage before measured; afterwards the fastest stage is used
@@ -220,7 +242,7 @@ struct crt_ctx {
         if (altTris) (void)hipFree(altTris);
         altTris = nullptr; altTriCount = 0; haveKd = haveGrid = false; alt = crt::AltAccelDev{}; renderAccel = 0;
         for (int k = 0; k < 2; k++) { for (void* p : blasAllocs[k]) (void)hipFree(p); blasAllocs[k].clear(); haveBlas[k] = false; blasAlt[k] = crt::TlasAltDev{}; }
-        blasGrid = BlasGrid{}; gridRefCount = 0;
+        blasGrid = BlasGrid{}; gridRefCount = 0; blasKd = BlasKd{}; kdNodeCount = kdRefCount = 0;
         freeRetired(true);                // the callers have drained every stream
     }
     void freeRetired(bool all)
@@ -418,6 +440,7 @@ void crt_destroy(crt_ctx* c)
     c->refit.release(); c->tlasBuild.release();
     c->freeScene();
     c->gridBuild.release();
+    c->kdBuild.release();
     for (hipEvent_t e : c->retiredEvents) (void)hipEventDestroy(e);
     for (auto& a : c->ahead) (void)hipEventDestroy(a.end);
     if (c->aheadStream) (void)hipStreamDestroy(c->aheadStream);
@@ -983,6 +1006,7 @@ int crt_update_scene(crt_ctx* c, const crt_scene_desc* sd, uint32_t what)
     { const int r = begin_scene_write(c, c->stream); if (r) return r; }
     if (what & CRT_UPDATE_BOUNDS) {
         std::fill(c->blasGrid.current.begin(), c->blasGrid.current.end(), (uint8_t)0);   // every BLAS's grid is of the old vertices
+        std::fill(c->blasKd.current.begin(), c->blasKd.current.end(), (uint8_t)0);       // ... and every BLAS's KD-tree
         drop_blas_sets(c);                                                 // (may reset renderAccel: behind the epoch's bump)
     }
     HIPCK(c, hipMemcpyAsync(const_cast<char*>(c->hScene.geom) + lo, c->hStage[k], geomBytes, hipMemcpyHostToDevice, c->stream));
@@ -2347,7 +2371,7 @@ int crt_upload_alt_accel(crt_ctx* c, const crt_alt_accel* a)
     if (slot == 0) {
         if ((r = upload_array(c, allocs, a->kdNodes, (size_t)a->kdNodeCount * sizeof(crt::KdNode), &c->alt.kdNodes))) return r;
         if ((r = upload_array(c, allocs, a->kdTriIndices, (size_t)a->kdTriIndexCount * 4, &c->alt.kdRefs))) return r;
-        c->alt.kdStack = kdHeight + 1; c->haveKd = true;
+        c->alt.kdStack = kdHeight + 1; c->haveKd = true; c->kdNodeCount = a->kdNodeCount; c->kdRefCount = a->kdTriIndexCount;
     } else {
         uint64_t cells = (uint64_t)a->gridResolution[0] * a->gridResolution[1] * a->gridResolution[2];
         if ((r = upload_array(c, allocs, a->gridCellStart, (size_t)(cells + 1) * 4, &c->alt.cellStart))) return r;
@@ -2370,12 +2394,13 @@ int crt_upload_blas_accel(crt_ctx* c, int kind, const crt_alt_accel* blas, uint3
     if (!blas || blasCount != (uint32_t)f.triCount.size()) return c->fail(CRT_ERR_INVALID, "crt_upload_blas_accel: %u structures for a scene of %zu BLAS", blasCount, f.triCount.size());
     // ---- every check first: a refused upload leaves the previous set answering ----
     const crt::Instance* inst = reinterpret_cast<const crt::Instance*>(f.geom.data() + f.instOff);
-    uint32_t maxKd = 0; uint64_t nNodes = 0, nRefs = 0, nTris = 0, nCells = 0, nCellRefs = 0;
+    uint32_t maxKd = 0; uint64_t nNodes = 0, nRefs = 0, nTris = 0, nCells = 0, nCellRefs = 0; std::vector<uint32_t> kdHeights(blasCount, 0u);
     for (uint32_t b = 0; b < blasCount; b++) {
         const crt_alt_accel& a = blas[b];
         if (a.kind != kind) return c->fail(CRT_ERR_INVALID, "BLAS %u: structure of kind %d in a set of kind %d", b, a.kind, kind);
         uint32_t h = 0;
         { const int r = check_alt_accel(c, &a, &h); if (r) return r; }
+        kdHeights[b] = h;
         if (a.triCount != f.triCount[b]) return c->fail(CRT_ERR_INVALID, "BLAS %u: %u triangles, the uploaded BLAS has %u", b, a.triCount, f.triCount[b]);
         for (uint32_t t = 0; t < a.triCount; t++)
             if (a.triangles[t].objIdx != inst[b].objIdx) return c->fail(CRT_ERR_INVALID, "BLAS %u: triangle %u has objIdx %d, the BLAS %d", b, t, a.triangles[t].objIdx, inst[b].objIdx);
@@ -2431,6 +2456,11 @@ int crt_upload_blas_accel(crt_ctx* c, int kind, const crt_alt_accel* blas, uint3
         crt_ctx::BlasGrid& g = c->blasGrid;
         g.desc = desc; g.cells.resize(blasCount); g.refs.resize(blasCount); g.current.assign(blasCount, (uint8_t)1); g.held = true;
         for (uint32_t b = 0; b < blasCount; b++) { g.cells[b] = (uint32_t)blas[b].gridResolution[0] * (uint32_t)blas[b].gridResolution[1] * (uint32_t)blas[b].gridResolution[2]; g.refs[b] = blas[b].gridCellTriCount; }
+    }
+    if (kind == CRT_ACCEL_KDTREE) {                                       // ... and crt_build_kdtree_device / crt_get_kdtree
+        crt_ctx::BlasKd& k = c->blasKd;
+        k.desc = desc; k.nodes.resize(blasCount); k.refs.resize(blasCount); k.height = kdHeights; k.current.assign(blasCount, (uint8_t)1); k.held = true;
+        for (uint32_t b = 0; b < blasCount; b++) { k.nodes[b] = blas[b].kdNodeCount; k.refs[b] = blas[b].kdTriIndexCount; }
     }
     if (c->renderAccel == kind) c->renderAccel = 0;                       // as crt_upload_alt_accel: the render goes back to the BVH until crt_set_render_accel
     HIPCK(c, ensure_event(&c->altReady));
@@ -2700,6 +2730,7 @@ int crt_refit_device(crt_ctx* c, uint32_t bvh, const float* d_positions, uint32_
     if (P.rootCode & crt::kPlanInterior) memcpy(f.geom.data() + (size_t)(f.pairBase[bvh] + (P.rootCode & ~crt::kPlanInterior)) * 64u, back, 64);   // the mirror's copy of the root's pair
     if (f.kind == CRT_SCENE_FILE) set_root(c, CRT_SCENE_FILE, back + 16, back + 19);      // rootPair from the mirror, dispatch-order bounds; a BLAS's box reaches the TLAS through the caller
     if (bvh < c->blasGrid.current.size()) c->blasGrid.current[bvh] = 0;    // crt_build_grid_device(bvh) makes it current again
+    if (bvh < c->blasKd.current.size()) c->blasKd.current[bvh] = 0;        // crt_build_kdtree_device(bvh) likewise
     drop_blas_sets(c);
     if (rootBox) memcpy(rootBox, back + 16, 24);
     return CRT_OK;
@@ -2945,6 +2976,209 @@ int crt_get_grid(crt_ctx* c, uint32_t bvh, int32_t res[3], float cellSize[3], fl
     if (c->gridBuild.built) HIPCK(c, hipEventSynchronize(c->gridBuild.done));   // a device build still running (an uploaded grid's copies were synchronous)
     if (cellStart) HIPCK(c, hipMemcpy(cellStart, dStart, ((size_t)cells + 1u) * 4u, hipMemcpyDeviceToHost));
     if (cellRefs && refs) HIPCK(c, hipMemcpy(cellRefs, dRefs, (size_t)refs * 4u, hipMemcpyDeviceToHost));
+    return CRT_OK;
+}
+
+// ---- crt_build_kdtree_device: KDTree::Build / BLASKDTree::Build of one BVH's triangles on the device, from positions in device memory (device/kd_build.hip) ----
+// scratch of the build that grows on demand (bytes); the previous build may still be using it, so the host waits for that build first (earlier work only)
+static int grow_kd_scratch(crt_ctx* c, void** p, size_t* cap, size_t need)
+{
+    if (need <= *cap) return 0;
+    if (c->kdBuild.built) HIPCK(c, hipEventSynchronize(c->kdBuild.done));
+    if (*p) { (void)hipFree(*p); *p = nullptr; *cap = 0; }
+    const hipError_t e = hipMalloc(p, need);
+    if (e != hipSuccess) { (void)hipGetLastError(); *p = nullptr; return c->fail(CRT_ERR_DEVICE, "crt_build_kdtree_device: hipMalloc(%zu): %s", need, hipGetErrorString(e)); }
+    *cap = need;
+    return 0;
+}
+
+int crt_build_kdtree_device(crt_ctx* c, uint32_t bvh, const float* d_positions, uint32_t triCount, void* stream)
+{
+    const char* const me = "crt_build_kdtree_device";
+    if (!c) return CRT_ERR_INVALID;
+    int r;
+    if ((r = check_bvh_arg(c, me, "triangles", bvh, triCount, ""))) return r;
+    crt_ctx::Flat& f = c->flat; crt_ctx::KdBuild& K = c->kdBuild;
+    const bool tlas = f.kind == CRT_SCENE_TLAS;
+    const uint32_t N = (uint32_t)f.triCount.size();
+    if (triCount == 0 || triCount > 0x7fffffffu / 3u) return c->fail(CRT_ERR_UNSUPPORTED, "%s: 1 .. (2^31-1)/3 triangles", me);
+    crt_ctx::BlasKd& bk = c->blasKd;
+    if (tlas && (!bk.held || bk.desc.size() != N)) return c->fail(CRT_ERR_STATE, "%s: a two-level scene needs a KD set uploaded earlier (crt_upload_blas_accel(CRT_ACCEL_KDTREE)): the other BLASes' parts are carried over", me);
+    hipStream_t st = nullptr;
+    if ((r = device_entry(c, me, {{d_positions, (size_t)triCount * 36u}}, stream, &st))) return r;
+    // ---- what the context keeps for the build ----
+    c->freeRetired(false);
+    if (!K.blocks && !(K.blocks = crt_grid_build_blocks(c->cfg.device))) return c->fail(CRT_ERR_DEVICE, "%s: the device's compute units / occupancy could not be asked", me);
+    if (!K.dState) HIPCK(c, hipMalloc((void**)&K.dState, sizeof(crt::KdBuildState)));
+    if (!K.hState) HIPCK(c, hipHostMalloc((void**)&K.hState, sizeof(crt::KdBuildState), hipHostMallocDefault));
+    for (hipEvent_t* e : {&K.back, &K.done}) HIPCK(c, ensure_event(e));
+    if (g_hooks) for (hipEvent_t* e : {&K.t0, &K.t1}) HIPCK(c, ensure_event(e, hipEventDefault));
+    crt_ctx::KdBuild::Level* lv = K.lv;
+    if ((r = grow_kd_scratch(c, &K.dTriBox, &K.triBoxCap, (size_t)triCount * 24u)) || (r = grow_kd_scratch(c, &lv[0].nodes, &lv[0].nodeCap, sizeof(crt::KdBuildNode))) ||
+        (r = grow_kd_scratch(c, &lv[0].refs, &lv[0].refCap, (size_t)triCount * 4u)) || (r = grow_kd_scratch(c, &lv[0].owner, &lv[0].ownerCap, (size_t)triCount * 4u))) return r;
+    // Fresh buffers for the tree, so the build is a reader: it reads the caller's positions and the LeafTri id words (which no write changes) and waits for the last
+    // scene write and for the previous build (whose scratch it reuses).  Earlier renders and queries are not waited for until the old tree is retired.
+    if ((r = wait_scene(c, st))) return r;
+    if (K.built) HIPCK(c, hipStreamWaitEvent(st, K.done, 0));
+    if (g_hooks) HIPCK(c, hipEventRecord(K.t0, st));
+    K.waits = 0; K.waitMs = 0; K.levels = 0;
+    // ---- a. bounds + finiteness, the triangle boxes, level 0 (no wait of its own: level 0's read-back carries the flag) ----
+    HIPCK(c, crt_launch_kd_begin(d_positions, triCount, K.dState, (float*)K.dTriBox, (crt::KdBuildNode*)lv[0].nodes, (uint32_t*)lv[0].refs, (uint32_t*)lv[0].owner, K.blocks, st));
+    // ---- b. level by level; ONE HOST WAIT PER LEVEL: the next level's node and reference counts size its buffers ----
+    uint32_t nodeCount[crt_ctx::KdBuild::kLevels] = {1u}, refCount[crt_ctx::KdBuild::kLevels] = {triCount};
+    uint32_t levels = 0; uint64_t allNodes64 = 0, leafRefs64 = 0;
+    for (uint32_t d = 0; d < crt_ctx::KdBuild::kLevels; d++) {
+        const uint32_t m = nodeCount[d], t = refCount[d];
+        if ((r = grow_kd_scratch(c, &K.dNodeItems, &K.nodeItemCap, ((size_t)m + 1u) * 8u)) || (r = grow_kd_scratch(c, &K.dRefItems, &K.refItemCap, ((size_t)t + 1u) * 8u)) ||
+            (r = grow_kd_scratch(c, &K.dChunks, &K.chunkCap, crt_kd_scan_chunks(m > t ? m : t) * 8u))) return r;
+        HIPCK(c, crt_launch_kd_level((crt::KdBuildNode*)lv[d].nodes, m, d, (const uint32_t*)lv[d].owner, (const uint32_t*)lv[d].refs, t, (const float*)K.dTriBox,
+                                     (unsigned long long*)K.dNodeItems, (unsigned long long*)K.dRefItems, (unsigned long long*)K.dChunks, K.dState, K.blocks, st));
+        double ms = 0;
+        if ((r = read_back(c, st, K.back, K.hState, K.dState, sizeof(crt::KdBuildState), &ms))) return r;
+        K.waits++; K.waitMs += ms;
+        if (d == 0 && K.hState->bounds.nonFinite) return c->fail(CRT_ERR_INVALID, "%s: a position component is not finite", me);
+        const uint64_t splits = K.hState->nodeTotal & 0xffffffffull, leafRefs = K.hState->nodeTotal >> 32;
+        const uint64_t next = (K.hState->refTotal & 0xffffffffull) + (K.hState->refTotal >> 32);
+        allNodes64 += m; leafRefs64 += leafRefs; levels = d + 1u;
+        if (leafRefs64 > 0x7fffffffull) return c->fail(CRT_ERR_UNSUPPORTED, "%s: more than 2^31-1 leaf references", me);
+        if (splits == 0) break;
+        if (next > 0x7fffffffull) return c->fail(CRT_ERR_UNSUPPORTED, "%s: level %u has %llu references (at most 2^31-1)", me, d + 1u, (unsigned long long)next);
+        if (d + 1u >= crt_ctx::KdBuild::kLevels || splits > m) return c->fail(CRT_ERR_DEVICE, "%s: the level kernels reported %llu split nodes of %u at depth %u", me, (unsigned long long)splits, m, d);
+        nodeCount[d + 1u] = (uint32_t)(2u * splits); refCount[d + 1u] = (uint32_t)next;
+        if ((r = grow_kd_scratch(c, &lv[d + 1u].nodes, &lv[d + 1u].nodeCap, (size_t)nodeCount[d + 1u] * sizeof(crt::KdBuildNode))) ||
+            (r = grow_kd_scratch(c, &lv[d + 1u].refs, &lv[d + 1u].refCap, (size_t)next * 4u)) || (r = grow_kd_scratch(c, &lv[d + 1u].owner, &lv[d + 1u].ownerCap, (size_t)next * 4u))) return r;
+        HIPCK(c, crt_launch_kd_split((crt::KdBuildNode*)lv[d].nodes, m, (const unsigned long long*)K.dNodeItems, (const uint32_t*)lv[d].owner, (const uint32_t*)lv[d].refs, t,
+                                     (const unsigned long long*)K.dRefItems, (crt::KdBuildNode*)lv[d + 1u].nodes, nodeCount[d + 1u], (uint32_t*)lv[d + 1u].refs, (uint32_t*)lv[d + 1u].owner,
+                                     refCount[d + 1u], K.blocks, st));
+    }
+    K.levels = levels;
+    const uint32_t height = levels - 1u, newNodes = (uint32_t)allNodes64, newRefs = (uint32_t)leafRefs64;
+    // ---- the new tree's buffers: a FileScene's own arrays, or the set's concatenated arrays with this BLAS's part at its re-based place ----
+    uint64_t nodeBase = 0, refBase = 0, triOff = 0, allNodes = newNodes, allRefs = newRefs, allTris = triCount; uint32_t maxKd = height + 1u;
+    if (tlas) {
+        allNodes = allRefs = allTris = 0; maxKd = 0;
+        for (uint32_t b = 0; b < N; b++) {
+            if (b == bvh) { nodeBase = allNodes; refBase = allRefs; triOff = allTris; }
+            allNodes += b == bvh ? newNodes : bk.nodes[b]; allRefs += b == bvh ? newRefs : bk.refs[b]; allTris += f.triCount[b];
+            const uint32_t h = (b == bvh ? height : bk.height[b]) + 1u; if (h > maxKd) maxKd = h;
+        }
+        if (allNodes > 0xffffffffull || allRefs > 0xffffffffull || allTris > 0xffffffffull) return c->fail(CRT_ERR_UNSUPPORTED, "%s: the KD set is too large", me);
+        const uint32_t words = maxKd * 2u + (c->hScene.stackDepth - c->hScene.bvhStack);      // as crt_upload_blas_accel
+        if (!wave_stack_fits(words)) return c->fail(CRT_ERR_UNSUPPORTED, "%s: TLAS + KD-tree traversal stack of %u dwords per lane exceeds the LDS budget", me, words);
+    }
+    std::vector<void*> fresh; void* pinned = nullptr;
+    auto undo = [&]() { (void)hipStreamSynchronize(st); for (void* p : fresh) (void)hipFree(p); if (pinned) (void)hipHostFree(pinned); };
+    auto alloc = [&](size_t bytes, void** out) -> int {
+        *out = nullptr; if (!bytes) return 0;
+        const hipError_t e = hipMalloc(out, bytes);
+        if (e != hipSuccess) { (void)hipGetLastError(); *out = nullptr; return c->fail(CRT_ERR_DEVICE, "%s: hipMalloc(%zu): %s", me, bytes, hipGetErrorString(e)); }
+        fresh.push_back(*out); return 0;
+    };
+#define KDCK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { undo(); return c->hip(e_, #call); } } while (0)
+    crt::KdNode* newNodeArr = nullptr; uint32_t* newRefArr = nullptr; crt::AltTri* newTris = nullptr; crt::BlasAltDesc* newDesc = nullptr;
+    if ((r = alloc((size_t)allNodes * sizeof(crt::KdNode), (void**)&newNodeArr)) || (r = alloc((size_t)allRefs * 4u, (void**)&newRefArr)) ||
+        (r = alloc((size_t)allTris * sizeof(crt::AltTri), (void**)&newTris))) { undo(); return r; }
+    std::vector<crt::BlasAltDesc> desc;
+    if (tlas) {
+        // the other BLASes' parts, device to device, and the descriptors re-based for the new sizes
+        const crt::TlasAltDev& old = c->blasAlt[0];
+        desc = bk.desc;
+        uint64_t nb = 0, rb = 0, tb = 0;
+        for (uint32_t b = 0; b < N; b++) {
+            const crt::BlasAltDesc& od = bk.desc[b]; crt::BlasAltDesc& nd = desc[b];
+            const uint64_t nn = b == bvh ? newNodes : bk.nodes[b], nr = b == bvh ? newRefs : bk.refs[b], nt = f.triCount[b];
+            nd.nodeBase = (uint32_t)nb; nd.refBase = (uint32_t)rb; nd.triBase = (uint32_t)tb;
+            if (b != bvh) {
+                KDCK(hipMemcpyAsync(newNodeArr + nb, static_cast<const crt::KdNode*>(old.kdNodes) + od.nodeBase, (size_t)nn * sizeof(crt::KdNode), hipMemcpyDeviceToDevice, st));
+                if (nr) KDCK(hipMemcpyAsync(newRefArr + rb, old.kdRefs + od.refBase, (size_t)nr * 4u, hipMemcpyDeviceToDevice, st));
+                KDCK(hipMemcpyAsync(newTris + tb, static_cast<const crt::AltTri*>(old.tris) + od.triBase, (size_t)nt * sizeof(crt::AltTri), hipMemcpyDeviceToDevice, st));
+            }
+            nb += nn; rb += nr; tb += nt;
+        }
+        if ((r = alloc(desc.size() * sizeof(crt::BlasAltDesc), (void**)&newDesc))) { undo(); return r; }
+        KDCK(hipHostMalloc(&pinned, desc.size() * sizeof(crt::BlasAltDesc), hipHostMallocDefault));      // read by the copy below after this call has returned: retired with the old set
+        memcpy(pinned, desc.data(), desc.size() * sizeof(crt::BlasAltDesc));
+        KDCK(hipMemcpyAsync(newDesc, pinned, desc.size() * sizeof(crt::BlasAltDesc), hipMemcpyHostToDevice, st));
+    }
+    // ---- c. finalise: subtree sizes bottom-up, pre-order places top-down, the records and the leaf references; the AltTri records ----
+    {
+        crt::KdBuildNode* ln[crt_ctx::KdBuild::kLevels]; const uint32_t* lr[crt_ctx::KdBuild::kLevels]; const uint32_t* lo[crt_ctx::KdBuild::kLevels];
+        for (uint32_t d = 0; d < levels; d++) { ln[d] = (crt::KdBuildNode*)lv[d].nodes; lr[d] = (const uint32_t*)lv[d].refs; lo[d] = (const uint32_t*)lv[d].owner; }
+        KDCK(crt_launch_kd_finalise(ln, lr, lo, nodeCount, refCount, levels, newNodeArr + nodeBase, newNodes, newRefArr ? newRefArr + refBase : nullptr, newRefs, K.blocks, st));
+    }
+    KDCK(crt_launch_alt_tris(d_positions, triCount, c->hScene.geom, (uint32_t)f.leafOff, (uint32_t)f.triBase[bvh], tlas ? 1 : 0, newTris + triOff, st));
+    if (g_hooks) { KDCK(hipEventRecord(K.t1, st)); K.timed = true; }
+    KDCK(hipEventRecord(K.done, st));
+    K.built = true;
+    // ---- the tree it replaces: still read by launches enqueued earlier, on any stream, and by this build's own copies; retired as crt_build_grid_device retires a grid ----
+    crt_ctx::Retired old;
+    if (c->retiredEvents.empty()) { hipEvent_t e = nullptr; KDCK(hipEventCreateWithFlags(&e, hipEventDisableTiming)); c->retiredEvents.push_back(e); }
+    old.unread = c->retiredEvents.back(); c->retiredEvents.pop_back();
+    if ((r = order_behind_readers(c)) || (r = publish_scene_write(c, st, K.done)) || (r = c->hip(hipEventRecord(old.unread, c->stream), "hipEventRecord(retired)"))) {
+        c->retiredEvents.push_back(old.unread); undo(); return r;
+    }
+#undef KDCK
+    old.pinned = pinned;
+    if (tlas) {
+        old.ptrs.swap(c->blasAllocs[0]); c->blasAllocs[0] = fresh;
+        crt::TlasAltDev& tl = c->blasAlt[0];
+        tl.desc = newDesc; tl.tris = newTris; tl.kdNodes = newNodeArr; tl.kdRefs = newRefArr; tl.cellStart = nullptr; tl.cellRefs = nullptr; tl.kdStack = maxKd;
+        bk.desc = desc; bk.nodes[bvh] = newNodes; bk.refs[bvh] = newRefs; bk.height[bvh] = height; bk.current[bvh] = 1;
+        bool all = true; for (uint8_t k : bk.current) all = all && k;
+        c->haveBlas[0] = all;                                              // live again once every BLAS's part is of its current vertices
+        if (c->renderAccel == CRT_ACCEL_KDTREE && !sample_lds_fits(sample_stack_words(c, CRT_ACCEL_KDTREE))) c->renderAccel = 0;   // (a set rebuilt while live, now deeper than the render stack)
+    } else {
+        old.ptrs.swap(c->altAllocs[0]);
+        for (void* p : fresh) if (p != (void*)newTris) c->altAllocs[0].push_back(p);             // (newTris is not an accelerator array: it becomes altTris)
+        if (c->altTris) old.ptrs.push_back(c->altTris);
+        c->altTris = newTris; c->altTriCount = triCount;
+        crt::AltAccelDev& a = c->alt;
+        a.tris = newTris; a.kdNodes = newNodeArr; a.kdRefs = newRefArr; a.kdStack = height + 1u;
+        c->haveKd = true; c->kdNodeCount = newNodes; c->kdRefCount = newRefs;
+        // the grid shares altTris and its cells are of the old positions: absent, as crt_build_grid_device marks the KD-tree (its arrays go with the next grid upload or build)
+        c->haveGrid = false; a.cellStart = nullptr; a.cellRefs = nullptr; c->gridRefCount = 0;
+        for (int k = 0; k < 3; k++) { a.res[k] = 0; a.cell[k] = 0.0f; a.lo[k] = 0.0f; a.hi[k] = 0.0f; }
+        if (c->renderAccel == CRT_ACCEL_GRID) c->renderAccel = 0;
+    }
+    c->retired.push_back(std::move(old));
+    return CRT_OK;
+}
+
+int crt_get_kdtree(crt_ctx* c, uint32_t bvh, uint32_t* nodeCount, uint32_t* refCount, uint32_t* height, crt_kd_node* nodes, uint32_t* refs)
+{
+    if (!c) return CRT_ERR_INVALID;
+    if (!c->haveScene) return c->fail(CRT_ERR_STATE, "crt_get_kdtree before crt_upload_scene");
+    const crt_ctx::Flat& f = c->flat;
+    if (bvh >= f.triCount.size()) return c->fail(CRT_ERR_INVALID, "crt_get_kdtree: BVH %u of a scene with %zu", bvh, f.triCount.size());
+    const bool tlas = f.kind == CRT_SCENE_TLAS;
+    if (tlas ? !(c->haveBlas[0] && c->blasKd.held) : !c->haveKd) return c->fail(CRT_ERR_STATE, "crt_get_kdtree: no live KD-tree (not uploaded, or dropped by a refit and not rebuilt)");
+    uint32_t nn, nr, h; const crt::KdNode* dNodes; const uint32_t* dRefs;
+    if (tlas) {
+        const crt::BlasAltDesc& d = c->blasKd.desc[bvh];
+        nn = c->blasKd.nodes[bvh]; nr = c->blasKd.refs[bvh]; h = c->blasKd.height[bvh];
+        dNodes = static_cast<const crt::KdNode*>(c->blasAlt[0].kdNodes) + d.nodeBase; dRefs = c->blasAlt[0].kdRefs ? c->blasAlt[0].kdRefs + d.refBase : nullptr;
+    } else { nn = c->kdNodeCount; nr = c->kdRefCount; h = c->alt.kdStack - 1u; dNodes = c->alt.kdNodes; dRefs = c->alt.kdRefs; }
+    if (nodeCount) *nodeCount = nn;
+    if (refCount) *refCount = nr;
+    if (height) *height = h;
+    if (!nodes && !refs) return CRT_OK;
+    HIPCK(c, hipSetDevice(c->cfg.device));
+    if (c->kdBuild.built) HIPCK(c, hipEventSynchronize(c->kdBuild.done));   // a device build still running (an uploaded tree's copies were synchronous)
+    if (nodes) HIPCK(c, hipMemcpy(nodes, dNodes, (size_t)nn * sizeof(crt::KdNode), hipMemcpyDeviceToHost));
+    if (refs && nr) HIPCK(c, hipMemcpy(refs, dRefs, (size_t)nr * 4u, hipMemcpyDeviceToHost));
+    return CRT_OK;
+}
+
+// tools/kdtree_device_cost.py: the last crt_build_kdtree_device's duration on its stream (HIP events, first launch to last; it includes the host round trips in
+// between), the number of its host waits and their wall time together, and its levels (debug hooks only)
+extern "C" int crt_debug_kdtree_build_ms(crt_ctx* c, float* streamMs, double* waitMs, uint32_t* waits, uint32_t* levels)
+{
+    if (!c || !streamMs || !waitMs || !waits || !levels) return CRT_ERR_INVALID;
+    const crt_ctx::KdBuild& K = c->kdBuild;
+    if (!K.timed) return c->fail(CRT_ERR_STATE, "crt_debug_kdtree_build_ms: no timed crt_build_kdtree_device (debug hooks off?)");
+    HIPCK(c, hipEventSynchronize(K.t1));
+    HIPCK(c, hipEventElapsedTime(streamMs, K.t0, K.t1));
+    *waitMs = K.waitMs; *waits = K.waits; *levels = K.levels;
     return CRT_OK;
 }
 

@@ -279,3 +279,11 @@ extern "C" hipError_t crt_launch_grid_fill(const float* pos, uint32_t triCount, 
                        globalIdx, tris);
     return hipGetLastError();
 }
+
+// the AltTri records alone (crt_build_kdtree_device writes them as the grid build does)
+extern "C" hipError_t crt_launch_alt_tris(const float* pos, uint32_t triCount, const char* geom, uint32_t leafOff, uint32_t triBase, int globalIdx, crt::AltTri* tris, hipStream_t stream)
+{
+    hipLaunchKernelGGL(crt::grid_tris_kernel, dim3((triCount + crt::kGridThreads - 1u) / crt::kGridThreads), dim3(crt::kGridThreads), 0, stream, geom, leafOff, triBase, triCount, pos,
+                       globalIdx, tris);
+    return hipGetLastError();
+}

@@ -91,6 +91,18 @@ hipError_t crt_launch_grid_count(const float* pos, uint32_t triCount, const crt:
     uint32_t maxBlocks, hipStream_t stream);
 hipError_t crt_launch_grid_fill(const float* pos, uint32_t triCount, const crt::GridParams* g, uint32_t cells, const uint32_t* cellStart, uint32_t* cursor, int32_t* unsorted, int32_t* refs,
     uint32_t total, const char* geom, uint32_t leafOff, uint32_t triBase, int globalIdx, crt::AltTri* tris, uint32_t maxBlocks, hipStream_t stream);
+hipError_t crt_launch_alt_tris(const float* pos, uint32_t triCount, const char* geom, uint32_t leafOff, uint32_t triBase, int globalIdx, crt::AltTri* tris, hipStream_t stream);
+
+// ---- kd_build.hip ----
+size_t crt_kd_scan_chunks(uint32_t n);
+hipError_t crt_launch_kd_begin(const float* pos, uint32_t triCount, crt::KdBuildState* state, float* triBox, crt::KdBuildNode* root, uint32_t* refs, uint32_t* owner, uint32_t maxBlocks,
+    hipStream_t stream);
+hipError_t crt_launch_kd_level(crt::KdBuildNode* nodes, uint32_t nodeCount, uint32_t depth, const uint32_t* owner, const uint32_t* refs, uint32_t refCount, const float* triBox,
+    unsigned long long* nodeItems, unsigned long long* refItems, unsigned long long* chunkSums, crt::KdBuildState* state, uint32_t maxBlocks, hipStream_t stream);
+hipError_t crt_launch_kd_split(crt::KdBuildNode* nodes, uint32_t nodeCount, const unsigned long long* nodeScan, const uint32_t* owner, const uint32_t* refs, uint32_t refCount,
+    const unsigned long long* refScan, crt::KdBuildNode* next, uint32_t nextNodes, uint32_t* nextRefs, uint32_t* nextOwner, uint32_t nextRefCount, uint32_t maxBlocks, hipStream_t stream);
+hipError_t crt_launch_kd_finalise(crt::KdBuildNode* const* nodes, const uint32_t* const* refs, const uint32_t* const* owner, const uint32_t* nodeCount, const uint32_t* refCount, uint32_t levels,
+    crt::KdNode* outNodes, uint32_t outNodeCount, uint32_t* outRefs, uint32_t outRefCount, uint32_t maxBlocks, hipStream_t stream);
 
 // ---- tlas_build.hip ----
 hipError_t crt_launch_tlas_build(const char* geom, uint32_t instOff, const float* T, const float* rootBox, uint32_t blasCount, uint32_t pairRel, uint32_t instRel, uint32_t poolRefBits,

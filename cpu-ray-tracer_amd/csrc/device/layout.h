@@ -210,6 +210,20 @@ struct TlasAltDev {                       // passed by value, like AltAccelDev
 struct GridParams { int32_t res[3]; float cell[3]; float lo[3]; };
 struct alignas(16) GridBuildState { unsigned long long key[6]; unsigned long long total; uint32_t nonFinite; uint32_t pad; };
 
+// crt_build_kdtree_device (kd_build.hip): one node of one level of the level-synchronous build, and the block the kernels report through.  A level's nodes are in
+// level order; its references are one concatenated array segmented by node ([first, first + count)).  The finalise passes fill the last four words.
+struct alignas(16) KdBuildNode {
+    float lo[3]; uint32_t first;          // box; first reference of the node in the level's array
+    float hi[3]; uint32_t count;
+    float splitPos, distance; int32_t axis; uint32_t child;    // axis < 0: leaf; child: the left child's index in the next level (the right one follows it)
+    uint32_t subNodes, subRefs;           // nodes / leaf references of the subtree (bottom-up)
+    uint32_t pre, firstRef;               // pre-order index; leaf references that precede the node in pre-order (top-down)
+};
+// the bounds pass's block (the grid build's), then the totals of the level's two scans: nodeTotal = split nodes | leaf references << 32, refTotal = references
+// that go left | references that go right << 32 (each half below 2^32: a level holds at most 2^31 - 1 references)
+struct alignas(16) KdBuildState { GridBuildState bounds; unsigned long long nodeTotal, refTotal; };
+constexpr uint32_t kKdMaxDepth = 20u;     // kdtree.h m_maxBuildDepth: levels 0 .. 20
+
 // PrimitiveScene at one animation time (crt_primitive_scene flattened by crt_upload_primitive_scene; kernels in render_prim.hip), passed to the kernels by value
 struct PrimDev {
     float quadInvT[12], quadNrm[3], quadSize;

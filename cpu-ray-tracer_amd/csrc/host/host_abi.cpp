@@ -13,8 +13,9 @@ namespace { thread_local std::string g_err; }
 
 struct crt_host_scene { BaseScene* scene = nullptr; FileScene* file = nullptr; TLASFileScene* tlas = nullptr; KDTree* kd = nullptr; Grid* grid = nullptr;
                         std::vector<BLASKDTree> blasKd; std::vector<BLASGrid> blasGrid;               // TLAS scene: one structure per BLAS
-                        std::vector<uint8_t> gridPending;
-                        bool gridDeviceBuilt = false; };                                               // the grid mirror's cells are the device's, its triangles still the host's old ones                                            // BVHs whose grid was rebuilt on the device and is not mirrored yet
+                        std::vector<uint8_t> gridPending, kdPending;                                    // BVHs whose grid / KD-tree was rebuilt on the device and is not mirrored yet
+                        bool kdDeviceBuilt = false;                                                   // the KD mirror's nodes are the device's, its triangles still the host's old ones
+                        bool gridDeviceBuilt = false; };                                               // the grid mirror's cells are the device's, its triangles still the host's old ones
 struct crt_host_renderer { Renderer* r = nullptr; };
 
 // a BVH whose host arrays are stale (refitted on the device only): the calls that would send those arrays are refused
@@ -200,6 +201,73 @@ int crt_host_scene_build_grid_device(crt_host_scene* s, crt_ctx* ctx, int i, con
     return rc;
     GUARD_END(CRT_ERR_DEVICE)
 }
+// the mirror of one KD-tree from the device's (crt_get_kdtree); false: no live tree (a two-level set still dropped)
+static bool mirror_kd(crt_ctx* ctx, uint32_t bvh, KDTree& kd, int* rc)
+{
+    uint32_t nodes = 0, refs = 0, height = 0;
+    *rc = crt_get_kdtree(ctx, bvh, &nodes, &refs, &height, nullptr, nullptr);
+    if (*rc == CRT_ERR_STATE) { *rc = CRT_OK; return false; }
+    if (*rc != CRT_OK) return false;
+    kd.nodes.assign(nodes, crt_kd_node{}); kd.leafTriIndices.assign(refs, 0u);
+    *rc = crt_get_kdtree(ctx, bvh, nullptr, nullptr, nullptr, kd.nodes.data(), refs ? kd.leafTriIndices.data() : nullptr);
+    if (*rc != CRT_OK) return false;
+    // KDTree::nodesUsed counts every node; maxDepth is the deepest node Subdivide went on to split (kdtree.cpp:51)
+    kd.nodesUsed = nodes; kd.maxDepth = 0;
+    std::vector<std::pair<uint32_t, uint32_t>> st; st.push_back({0u, 0u});
+    while (!st.empty() && nodes) {
+        const auto [n, d] = st.back(); st.pop_back();
+        const crt_kd_node& nd = kd.nodes[n];
+        if (nd.left < 0 || (uint32_t)nd.left >= nodes || (uint32_t)nd.right >= nodes) continue;
+        if (d > kd.maxDepth) kd.maxDepth = d;
+        st.push_back({(uint32_t)nd.right, d + 1}); st.push_back({(uint32_t)nd.left, d + 1});
+    }
+    kd.localBounds.bmin3 = float3(kd.nodes[0].aabbMin[0], kd.nodes[0].aabbMin[1], kd.nodes[0].aabbMin[2]);
+    kd.localBounds.bmax3 = float3(kd.nodes[0].aabbMax[0], kd.nodes[0].aabbMax[1], kd.nodes[0].aabbMax[2]);
+    return true;
+}
+int crt_host_scene_build_kdtree_device(crt_host_scene* s, crt_ctx* ctx, int i, const float* d_positions, uint32_t triCount, void* stream)
+{
+    if (!s || !ctx) { g_err = "null argument"; return CRT_ERR_INVALID; }
+    GUARD_BEGIN
+    const int count = s->file ? 1 : (int)s->tlas->tlas.blas.size();
+    if (i < 0 || i >= count) { g_err = "bvh index out of range"; return CRT_ERR_INVALID; }
+    int rc = crt_build_kdtree_device(ctx, (uint32_t)i, d_positions, triCount, stream);
+    if (rc != CRT_OK) { g_err = crt_last_error(ctx); return rc; }
+    s->kdDeviceBuilt = true;
+    if (s->file) {
+        if (!s->kd) { s->kd = new KDTree(); s->kd->triangles = s->file->acc.triangles; }
+        mirror_kd(ctx, 0, *s->kd, &rc);
+    } else {
+        const std::vector<BLASBVH*>& bl = s->tlas->tlas.blas;
+        s->kdPending.resize(bl.size(), 0);
+        if (s->blasKd.size() != bl.size()) {                                         // the set came through crt_upload_blas_accel directly: mirror every BLAS
+            s->blasKd.assign(bl.size(), BLASKDTree());
+            for (size_t k = 0; k < bl.size(); k++) { s->blasKd[k].objIdx = bl[k]->objIdx; s->blasKd[k].triangles = bl[k]->triangles; s->kdPending[k] = 1; }
+        }
+        s->kdPending[(size_t)i] = 1;
+        for (size_t k = 0; k < bl.size() && rc == CRT_OK; k++)
+            if (s->kdPending[k] && mirror_kd(ctx, (uint32_t)k, s->blasKd[k], &rc)) s->kdPending[k] = 0;
+    }
+    if (rc != CRT_OK) g_err = crt_last_error(ctx);
+    return rc;
+    GUARD_END(CRT_ERR_DEVICE)
+}
+int crt_host_kd_build(const float* positions, uint32_t triCount, uint32_t info[4], crt_kd_node* nodes, uint32_t* refs)
+{
+    if (!positions || !triCount) { g_err = "null argument"; return CRT_ERR_INVALID; }
+    GUARD_BEGIN
+    KDTree kd; kd.triangles.resize(triCount);
+    for (uint32_t t = 0; t < triCount; t++) {
+        Tri& tr = kd.triangles[t]; memset(&tr, 0, sizeof(Tri));
+        memcpy(tr.vertex0, positions + 9 * (size_t)t, 12); memcpy(tr.vertex1, positions + 9 * (size_t)t + 3, 12); memcpy(tr.vertex2, positions + 9 * (size_t)t + 6, 12);
+    }
+    kd.Build();
+    if (info) { info[0] = (uint32_t)kd.nodes.size(); info[1] = (uint32_t)kd.leafTriIndices.size(); info[2] = kd.maxDepth; info[3] = kd.nodesUsed; }
+    if (nodes) memcpy(nodes, kd.nodes.data(), kd.nodes.size() * sizeof(crt_kd_node));
+    if (refs && !kd.leafTriIndices.empty()) memcpy(refs, kd.leafTriIndices.data(), kd.leafTriIndices.size() * 4);
+    return CRT_OK;
+    GUARD_END(CRT_ERR_INVALID)
+}
 int crt_host_grid_build(const float* positions, uint32_t triCount, int32_t res[3], float f9[9], uint32_t* refCount, uint32_t* cellStart, int32_t* cellRefs)
 {
     if (!positions || !triCount) { g_err = "null argument"; return CRT_ERR_INVALID; }
@@ -346,6 +414,7 @@ int crt_host_scene_build_alt(crt_host_scene* s, int kind)
     if (!s) { g_err = "null argument"; return CRT_ERR_INVALID; }
     GUARD_BEGIN
     if (kind == CRT_ACCEL_GRID) s->gridDeviceBuilt = false;                          // cells and triangles are both the host's again
+    if (kind == CRT_ACCEL_KDTREE) s->kdDeviceBuilt = false;
     if (s->tlas) {
         const std::vector<BLASBVH*>& bl = s->tlas->tlas.blas;
         if (kind == CRT_ACCEL_KDTREE) {
@@ -394,6 +463,11 @@ int crt_host_scene_upload_alt(crt_host_scene* s, crt_ctx* ctx, int kind)
     if (kind == CRT_ACCEL_GRID && s->gridDeviceBuilt) {
         g_err = "crt_host_scene_upload_alt: the grid mirror was refreshed from a device build (crt_host_scene_build_grid_device): its cells are of positions the host triangles never "
                 "saw, so the upload would pair new cells with old vertices; crt_host_scene_build_alt(CRT_ACCEL_GRID) builds it from the host's triangles again";
+        return CRT_ERR_STATE;
+    }
+    if (kind == CRT_ACCEL_KDTREE && s->kdDeviceBuilt) {
+        g_err = "crt_host_scene_upload_alt: the KD-tree mirror was refreshed from a device build (crt_host_scene_build_kdtree_device): its nodes are of positions the host triangles "
+                "never saw, so the upload would pair new nodes with old vertices; crt_host_scene_build_alt(CRT_ACCEL_KDTREE) builds it from the host's triangles again";
         return CRT_ERR_STATE;
     }
     if (s->tlas) {

@@ -174,7 +174,8 @@ int  crt_update_scene(crt_ctx* ctx, const crt_scene_desc* scene, uint32_t what);
  * frames rendered ahead, queries on any stream), so earlier renders still see the old scene; every launch submitted later waits for the refit.  THE ONE HOST WAIT:
  * the root's child pair travels in the kernel arguments of the render launches, so the call reads that pair and node 0's box back (88 bytes, pinned) and returns
  * once they have landed — it waits for `stream` up to the refit (and so for the earlier readers the refit is ordered behind), for nothing submitted later.
- * Like CRT_UPDATE_BOUNDS it drops a two-level scene's KD-tree / grid sets and the frames crt_tick rendered ahead.
+ * Like CRT_UPDATE_BOUNDS it drops a two-level scene's KD-tree / grid sets (crt_build_kdtree_device / crt_build_grid_device of the refitted BLAS bring them back) and
+ * the frames crt_tick rendered ahead.
  * Refused with nothing modified: no scene (CRT_ERR_STATE), a PrimitiveScene (CRT_ERR_UNSUPPORTED), bvh out of range, triCount different from the uploaded BVH's,
  * d_positions NULL / a host pointer / memory of another device, a stream of another device (CRT_ERR_INVALID).  The caller's host arrays of that BVH (and a later
  * CRT_UPDATE_BOUNDS built from them) are its own business: an update rewrites both sections from whatever it is given. */
@@ -216,7 +217,7 @@ int  crt_update_transforms_device(crt_ctx* ctx, const float* d_T /* 16 * blasCou
  * after a refit dropped the set; the other BLASes' parts are carried over device to device, the descriptors re-based).  The context keeps a "grid current" flag per
  * BLAS: an upload sets all, CRT_UPDATE_BOUNDS clears all, crt_refit_device(b) clears b's, this call sets b's; the grid set is live iff every flag is set.  So after a
  * refit of BLAS b the set is dropped exactly as before, and is live again (queries; crt_set_render_accel must be called again) once crt_build_grid_device(b) has run.
- * The KD set stays dropped.  The test of crt_upload_blas_accel that the grid's bounds equal the BVH root box is not applied: after Refit node 0's box legitimately
+ * The KD set has flags of its own and is brought back by crt_build_kdtree_device.  The test of crt_upload_blas_accel that the grid's bounds equal the BVH root box is not applied: after Refit node 0's box legitimately
  * differs from the true bounds (node 1 is skipped).  THE CALL TOUCHES NEITHER THE BVH, THE INSTANCES NOR THE TLAS: on a two-level scene the caller runs
  * crt_refit_device (+ crt_update_transforms_device) for the same positions, otherwise the TLAS boxes cull for the old geometry.
  * Ordering, as crt_refit_device / crt_update_transforms_device: the build runs on `stream` into buffers of its own; the grid it replaces keeps answering for
@@ -357,6 +358,47 @@ int  crt_set_render_accel(crt_ctx* ctx, int kind);
  * the render goes back to the BVH, a query with that accel is CRT_ERR_STATE); crt_upload_scene / crt_upload_primitive_scene drop it; crt_upload_alt_accel on
  * a TLAS scene stays CRT_ERR_STATE. */
 int  crt_upload_blas_accel(crt_ctx* ctx, int kind, const crt_alt_accel* blas, uint32_t blasCount);
+/* KDTree::Build / BLASKDTree::Build (infra/kdtree.cpp:4-108) for ONE uploaded BVH's triangle array on the device, from vertex positions that already live in device
+ * memory: the KD-tree — the accelerator the reference's FileScene ships enabled — rebuilt from scratch without a host round trip, beside crt_refit_device (BVH),
+ * crt_update_transforms_device (TLAS) and crt_build_grid_device (grid).  ABI version 3 still: both entries are additions, detected by symbol.  d_positions, triCount
+ * and `stream` are exactly crt_build_grid_device's (the same array, the same pointer / device / stream checks, NULL = the context's stream).
+ * What the call leaves on the device equals, byte for byte, what KDTree::Build over those triangles followed by crt_upload_alt_accel / crt_upload_blas_accel would
+ * leave: the crt_kd_node records in the host build's pre-order (node, left subtree, right subtree); every box derived from the root box (a child takes its parent's
+ * box with one component replaced by splitPos; the root box's signed zeros as the reference's fold leaves them); left / right -1 on leaves; splitAxis and
+ * splitDistance set on interior nodes, 0 on leaves; firstTri of EVERY node = the leaf references that precede it in pre-order; triCount 0 on interior nodes; the leaf
+ * reference array in pre-order of the leaves, each list in the order the recursion keeps; the triangle records as crt_build_grid_device writes them; the KD stack =
+ * height + 1, as the upload derives it.  The split is the spatial median of the longest axis (not SAH); recursion stops at <= 2 triangles or at depth 20; the
+ * comparison `bmin > splitPos - 0.001` is evaluated in double, as the reference's expression is.  Two runs over the same input give identical bytes.
+ * CRT_SCENE_FILE (bvh = 0): works with or without an earlier crt_upload_alt_accel(CRT_ACCEL_KDTREE); the tree becomes the scene's CRT_ACCEL_KDTREE structure and
+ * crt_set_render_accel(CRT_ACCEL_KDTREE) stays selected (the per-frame loop is refit, rebuild, render).  The build replaces the triangle records, which the grid
+ * shares, and the grid's cells belong to the old positions, so a successful call marks the grid absent — the mirror of what crt_build_grid_device does to the
+ * KD-tree: a query with CRT_ACCEL_GRID is CRT_ERR_STATE, crt_set_render_accel goes back to 0 if it named the grid.  Keeping both live from one set of positions is
+ * not offered.
+ * CRT_SCENE_TLAS (bvh = a BLAS): needs a KD set uploaded earlier through crt_upload_blas_accel(CRT_ACCEL_KDTREE, ..), else CRT_ERR_STATE.  The context keeps a "kd
+ * current" flag per BLAS, next to the grid's: an upload sets all, CRT_UPDATE_BOUNDS clears all, crt_refit_device(b) clears b's, this call sets b's; the set is live
+ * iff every flag is set (crt_set_render_accel must be called again after the set has been dropped).  The other BLASes' parts are carried over device to device and
+ * the descriptors re-based (nodeBase, refBase, triBase); the set's KD stack becomes the deepest tree's height + 1.  The upload's root-box test is not applied, for
+ * the reason given at crt_build_grid_device.  The call touches neither the BVH, the instances nor the TLAS.
+ * Ordering and lifetime are crt_build_grid_device's: the build runs on `stream` into buffers of its own (a reader of the scene-write protocol); the tree it replaces
+ * keeps answering for everything enqueued earlier, on any stream, and is retired once its last readers have completed; a refusal or failure leaves it answering.
+ * THE HOST WAITS: the tree grows level by level (depth 0 .. 20), and the host sizes each level's buffers, so the call makes ONE WAIT PER LEVEL, at most 21: a small
+ * pinned read-back (the level's split-node, leaf-reference and child-reference counts) that waits for `stream` up to that point only, for nothing submitted later.
+ * The first of them also carries the bounds pass's non-finite flag, and the last one (the level without a split) gives the final counts and the height, so there
+ * is no separate wait for either.  Growing the build's scratch beyond any earlier build's goes through hipFree / hipMalloc, as the grid build's.
+ * Refused with nothing modified, the previous tree still answering: no scene, a two-level scene without an uploaded KD set (CRT_ERR_STATE); a PrimitiveScene, a
+ * level or the leaf total with more than 2^31-1 references, a two-level traversal stack beyond the LDS budget (CRT_ERR_UNSUPPORTED); bvh out of range, triCount
+ * different from the uploaded BVH's, d_positions NULL / a host pointer / memory of another device, a stream of another device, a non-finite position component
+ * (found by the bounds pass) (CRT_ERR_INVALID); a failed device allocation (CRT_ERR_DEVICE).
+ * Cost: a triangle that straddles a split plane is referenced on both sides, and where triangles overlap no plane separates them, so they are duplicated down to
+ * the depth limit — the reference's behaviour, not the build's.  Measured (tools/kdtree_device_cost.py, profiles/kdtree_device.json, one MI355X):
+ * the bunny's 4 968 triangles give 154429 nodes and 216127 leaf references in 21 levels, 10.9 ms by the host route (copy, Refit, KDTree::Build, upload) and 1.4 ms by this
+ * call, of which 0.24 ms are its 21 host waits; the eight overlapping triangles of the tests' `zeros` mesh give 247 189 nodes and 383 255 references. */
+int  crt_build_kdtree_device(crt_ctx* ctx, uint32_t bvh, const float* d_positions /* 9 * triCount, device */, uint32_t triCount, void* stream);
+/* The live KD-tree of a FileScene (bvh = 0) or of one BLAS of a two-level scene's set, uploaded or device-built: sizes first (any output may be NULL; height = the
+ * deepest leaf's depth), then the arrays where the pointers are non-NULL (nodes: nodeCount records, refs: refCount leaf references, BLAS-local).  Synchronous (it
+ * waits for a device build still running).  CRT_ERR_STATE when there is no live tree; bvh out of range is CRT_ERR_INVALID. */
+int  crt_get_kdtree(crt_ctx* ctx, uint32_t bvh, uint32_t* nodeCount, uint32_t* refCount, uint32_t* height, crt_kd_node* nodes /* nodeCount, or NULL */,
+                    uint32_t* refs /* refCount, or NULL */);
 
 /* ---- scene queries: BaseScene::IsOccluded, and both queries on device buffers (base_scene.h:16-32) ------------------------------------------------
  * accel: 0 = the scene's own structure (BVH / TLAS; for the nearest-hit query also the PrimitiveScene), CRT_ACCEL_KDTREE / CRT_ACCEL_GRID = the uploaded

@@ -77,6 +77,16 @@ int  crt_host_scene_build_grid_device(crt_host_scene* scene, crt_ctx* ctx, int b
 /* Grid::Build (infra/grid.cpp:4-50) on the host over bare positions (9 floats per triangle): what crt_build_grid_device is compared with for meshes that are no
  * scene.  Sizes first (res, f9 = cellSize, bounds min, bounds max, refCount), the arrays where the pointers are non-NULL (cellStart: rx * ry * rz + 1, cellRefs: refCount). */
 int  crt_host_grid_build(const float* positions, uint32_t triCount, int32_t res[3], float f9[9], uint32_t* refCount, uint32_t* cellStart, int32_t* cellRefs);
+/* The KD-tree of BVH `bvh` rebuilt on the device from positions in device memory (crt_build_kdtree_device; d_positions, triCount, stream as there), then the host
+ * scene's KD mirror refreshed through crt_get_kdtree: crt_host_scene_alt_info / _alt_copy (FileScene) and crt_host_scene_blas_alt_info / _blas_alt_copy (a two-level
+ * scene's BLAS) with CRT_ACCEL_KDTREE then describe the live tree (maxDepth = the deepest interior node's depth, nodesUsed = the node count, both recomputed on the
+ * host).  While a two-level scene's set is still dropped the mirror of the rebuilt BLAS follows with the call that makes the set live.  As for the grid, the mirror's
+ * triangles are the host's old ones: crt_host_scene_upload_alt(CRT_ACCEL_KDTREE) is refused with CRT_ERR_STATE until crt_host_scene_build_alt(CRT_ACCEL_KDTREE) has
+ * built the tree from the host's triangles again. */
+int  crt_host_scene_build_kdtree_device(crt_host_scene* scene, crt_ctx* ctx, int bvh, const float* d_positions, uint32_t triCount, void* stream);
+/* KDTree::Build (infra/kdtree.cpp:4-108) on the host over bare positions (9 floats per triangle): what crt_build_kdtree_device is compared with for meshes that are no
+ * scene.  info (may be NULL) = nodes, leaf references, maxDepth, nodesUsed; nodes / refs (may be NULL) receive the arrays sized by an earlier call. */
+int  crt_host_kd_build(const float* positions, uint32_t triCount, uint32_t info[4], crt_kd_node* nodes, uint32_t* refs);
 int  crt_host_scene_blas_transform(crt_host_scene* scene, int bvh, float T[16], float invT[16], float worldMin[3], float worldMax[3]);
 int  crt_host_scene_tlas_copy(crt_host_scene* scene, crt_tlas_node* nodes /* 2*blasCount */, uint32_t* nodesUsed);
 
