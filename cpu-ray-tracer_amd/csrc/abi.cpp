@@ -4,6 +4,7 @@
 #include "../../include/crt_abi.h"
 #include "device/launch.h"
 #include "device/tile_class.h"
+#include "device/build_common.h"
 #include "host/grid_resolution.h"
 
 #include <cmath>
@@ -142,46 +143,52 @@ struct crt_ctx {
         hipEvent_t back = nullptr, done = nullptr, t0 = nullptr, t1 = nullptr; bool timed = false;
         void release() { for (hipEvent_t e : {back, done, t0, t1}) if (e) (void)hipEventDestroy(e); (void)hipFree(dBuild); (void)hipHostFree(hBack); *this = TlasBuild{}; }
     } tlasBuild;
-    // crt_build_grid_device (device/grid_build.hip): the kernels' state block and its pinned copy, scratch (the scan's chunk sums, the fill's cursors and unsorted
-    // references, grown on demand), and the events: `back` behind each of the two read-backs (the two host waits), `done` behind the build (sceneReady names it)
-    struct GridBuild {
-        crt::GridBuildState* dState = nullptr; crt::GridBuildState* hState = nullptr;
-        unsigned long long* dChunks = nullptr; uint32_t* dCursor = nullptr; int32_t* dUnsorted = nullptr; size_t cursorCap = 0, unsortedCap = 0;
+    // What crt_build_grid_device and crt_build_kdtree_device keep alike between calls: `back` behind each read-back (the host waits), `done` behind the build
+    // (sceneReady names it; the next build of the kind, which reuses the scratch, waits for it), t0 / t1 round the build under the debug hooks, and the workgroups
+    // the device holds at once (crt_grid_build_blocks)
+    struct AccelBuild {
         hipEvent_t back = nullptr, done = nullptr, t0 = nullptr, t1 = nullptr; bool built = false, timed = false; uint32_t blocks = 0;
+        void releaseEvents() { for (hipEvent_t e : {back, done, t0, t1}) if (e) (void)hipEventDestroy(e); }
+    };
+    // crt_build_grid_device (device/grid_build.hip): the kernels' state block and its pinned copy, scratch (the scan's chunk sums, the fill's cursors and unsorted
+    // references, grown on demand; capacities in bytes); two read-backs, so two host waits
+    struct GridBuild : AccelBuild {
+        crt::GridBuildState* dState = nullptr; crt::GridBuildState* hState = nullptr;
+        unsigned long long* dChunks = nullptr; void* dCursor = nullptr; void* dUnsorted = nullptr; size_t cursorCap = 0, unsortedCap = 0;
         double waitMs[2] = {0, 0};        // wall time of the last call's two host waits (crt_debug_grid_build_ms)
-        void release() { for (hipEvent_t e : {back, done, t0, t1}) if (e) (void)hipEventDestroy(e); for (void* p : {(void*)dState, (void*)dChunks, (void*)dCursor, (void*)dUnsorted}) (void)hipFree(p); (void)hipHostFree(hState); *this = GridBuild{}; }
+        void release() { releaseEvents(); for (void* p : {(void*)dState, (void*)dChunks, dCursor, dUnsorted}) (void)hipFree(p); (void)hipHostFree(hState); *this = GridBuild{}; }
     } gridBuild;
-    // A grid the build replaces may still be read by launches enqueued earlier: its buffers go to `retired` with an event recorded on the main stream
+    // A structure the build replaces may still be read by launches enqueued earlier: its buffers go to `retired` with an event recorded on the main stream
     // once that is ordered behind those launches, and are freed by a later call that finds the event complete (or with the scene, which drains first).
     struct Retired { std::vector<void*> ptrs; void* pinned = nullptr; hipEvent_t unread = nullptr; };
     std::deque<Retired> retired; std::vector<hipEvent_t> retiredEvents;
     uint32_t gridRefCount = 0;            // references of the FileScene's live grid (uploaded or built on the device)
-    // the two-level grid set as the device holds it, uploaded or rebuilt per BLAS: descriptors, cells and references per BLAS, and whether BLAS i's part is of its
-    // current vertices (an upload sets all, CRT_UPDATE_BOUNDS clears all, crt_refit_device clears its BLAS's, crt_build_grid_device sets its BLAS's): the set is live
-    // (haveBlas[1]) iff every flag is set.  Kept while the set is dropped: the buffers are still held, and a rebuild carries the other BLASes' parts over.
-    struct BlasGrid { std::vector<crt::BlasAltDesc> desc; std::vector<uint32_t> cells, refs; std::vector<uint8_t> current; bool held = false; } blasGrid;
     // crt_build_kdtree_device (device/kd_build.hip): the kernels' state block and its pinned copy; per level the nodes, the references and their owner nodes, kept
-    // until the finalise pass; the triangle boxes, the two scan arrays and the chunk sums — all grown on demand and kept between calls; `back` behind each level's
-    // read-back (the host waits), `done` behind the build (sceneReady names it)
-    struct KdBuild {
+    // until the finalise pass; the triangle boxes, the two scan arrays and the chunk sums — all grown on demand and kept between calls; one read-back (host wait) per level
+    struct KdBuild : AccelBuild {
         static constexpr uint32_t kLevels = crt::kKdMaxDepth + 1u;
         crt::KdBuildState* dState = nullptr; crt::KdBuildState* hState = nullptr;
         struct Level { void* nodes = nullptr; void* refs = nullptr; void* owner = nullptr; size_t nodeCap = 0, refCap = 0, ownerCap = 0; } lv[kLevels];
         void* dTriBox = nullptr; void* dNodeItems = nullptr; void* dRefItems = nullptr; void* dChunks = nullptr; size_t triBoxCap = 0, nodeItemCap = 0, refItemCap = 0, chunkCap = 0;
-        hipEvent_t back = nullptr, done = nullptr, t0 = nullptr, t1 = nullptr; bool built = false, timed = false; uint32_t blocks = 0;
         uint32_t waits = 0, levels = 0; double waitMs = 0;    // the last call's host waits, its levels, the wall time of the waits together (crt_debug_kdtree_build_ms)
         void release()
         {
-            for (hipEvent_t e : {back, done, t0, t1}) if (e) (void)hipEventDestroy(e);
+            releaseEvents();
             for (Level& l : lv) for (void* p : {l.nodes, l.refs, l.owner}) (void)hipFree(p);
             for (void* p : {(void*)dState, dTriBox, dNodeItems, dRefItems, dChunks}) (void)hipFree(p);
             (void)hipHostFree(hState); *this = KdBuild{};
         }
     } kdBuild;
     uint32_t kdNodeCount = 0, kdRefCount = 0;   // nodes / leaf references of the FileScene's live KD-tree (uploaded or built on the device)
-    // the two-level KD set as the device holds it, the grid set's counterpart: descriptors, nodes / references / height per BLAS, and the "kd current" flags (an
-    // upload sets all, CRT_UPDATE_BOUNDS clears all, crt_refit_device clears its BLAS's, crt_build_kdtree_device sets its BLAS's): live (haveBlas[0]) iff all are set
-    struct BlasKd { std::vector<crt::BlasAltDesc> desc; std::vector<uint32_t> nodes, refs, height; std::vector<uint8_t> current; bool held = false; } blasKd;
+    // The two-level KD [0] / grid [1] set as the device holds it, uploaded or rebuilt per BLAS: the descriptors; per BLAS the elements of its part of the kind's two
+    // arrays (count[0]: KD nodes / cells + 1, count[1]: KD / cell references) and its height (KD only); and whether BLAS i's part is of its current vertices (an
+    // upload sets all, CRT_UPDATE_BOUNDS clears all, crt_refit_device clears its BLAS's, the kind's device build sets its BLAS's): the set is live (haveBlas[k]) iff
+    // every flag is set.  Kept while the set is dropped: the buffers are still held (`held`), and a rebuild carries the other BLASes' parts over.
+    struct BlasSet {
+        std::vector<crt::BlasAltDesc> desc; std::vector<uint32_t> count[2], height; std::vector<uint8_t> current; bool held = false;
+        void stale(uint32_t bvh) { if (bvh < current.size()) current[bvh] = 0; }
+        bool allCurrent() const { for (uint8_t k : current) if (!k) return false; return true; }
+    } blasSet[2];
     hipEvent_t altReady = nullptr;        // recorded behind the last crt_upload_alt_accel's copies (device queries on other streams wait for it)
     // Latency mode of single-window launches (render_tiles_kernel's block table), driven by measurement — see next_block_table.  Stage 0 = the table solved from the cost probe's
     // estimates (one wavefront per tile when there was no probe); stages 1 .. kLatStages = tables solved from the tile costs the stage before measured; afterwards the fastest stage is used
@@ -242,7 +249,8 @@ struct crt_ctx {
         if (altTris) (void)hipFree(altTris);
         altTris = nullptr; altTriCount = 0; haveKd = haveGrid = false; alt = crt::AltAccelDev{}; renderAccel = 0;
         for (int k = 0; k < 2; k++) { for (void* p : blasAllocs[k]) (void)hipFree(p); blasAllocs[k].clear(); haveBlas[k] = false; blasAlt[k] = crt::TlasAltDev{}; }
-        blasGrid = BlasGrid{}; gridRefCount = 0; blasKd = BlasKd{}; kdNodeCount = kdRefCount = 0;
+        for (BlasSet& b : blasSet) b = BlasSet{};
+        gridRefCount = 0; kdNodeCount = kdRefCount = 0;
         freeRetired(true);                // the callers have drained every stream
     }
     void freeRetired(bool all)
@@ -1005,8 +1013,7 @@ int crt_update_scene(crt_ctx* c, const crt_scene_desc* sd, uint32_t what)
     if (boxBytes) memcpy(c->hStage[k] + geomBytes, f.rootBox.data(), boxBytes);
     { const int r = begin_scene_write(c, c->stream); if (r) return r; }
     if (what & CRT_UPDATE_BOUNDS) {
-        std::fill(c->blasGrid.current.begin(), c->blasGrid.current.end(), (uint8_t)0);   // every BLAS's grid is of the old vertices
-        std::fill(c->blasKd.current.begin(), c->blasKd.current.end(), (uint8_t)0);       // ... and every BLAS's KD-tree
+        for (crt_ctx::BlasSet& b : c->blasSet) std::fill(b.current.begin(), b.current.end(), (uint8_t)0);   // every BLAS's KD-tree and grid are of the old vertices
         drop_blas_sets(c);                                                 // (may reset renderAccel: behind the epoch's bump)
     }
     HIPCK(c, hipMemcpyAsync(const_cast<char*>(c->hScene.geom) + lo, c->hStage[k], geomBytes, hipMemcpyHostToDevice, c->stream));
@@ -2452,15 +2459,12 @@ int crt_upload_blas_accel(crt_ctx* c, int kind, const crt_alt_accel* blas, uint3
     c->epoch++;
     for (void* p : c->blasAllocs[slot]) (void)hipFree(p);
     c->blasAllocs[slot].swap(allocs); c->blasAlt[slot] = tl; c->haveBlas[slot] = true;
-    if (kind == CRT_ACCEL_GRID) {                                         // what crt_build_grid_device / crt_get_grid need of the set
-        crt_ctx::BlasGrid& g = c->blasGrid;
-        g.desc = desc; g.cells.resize(blasCount); g.refs.resize(blasCount); g.current.assign(blasCount, (uint8_t)1); g.held = true;
-        for (uint32_t b = 0; b < blasCount; b++) { g.cells[b] = (uint32_t)blas[b].gridResolution[0] * (uint32_t)blas[b].gridResolution[1] * (uint32_t)blas[b].gridResolution[2]; g.refs[b] = blas[b].gridCellTriCount; }
-    }
-    if (kind == CRT_ACCEL_KDTREE) {                                       // ... and crt_build_kdtree_device / crt_get_kdtree
-        crt_ctx::BlasKd& k = c->blasKd;
-        k.desc = desc; k.nodes.resize(blasCount); k.refs.resize(blasCount); k.height = kdHeights; k.current.assign(blasCount, (uint8_t)1); k.held = true;
-        for (uint32_t b = 0; b < blasCount; b++) { k.nodes[b] = blas[b].kdNodeCount; k.refs[b] = blas[b].kdTriIndexCount; }
+    crt_ctx::BlasSet& S = c->blasSet[slot];                               // what the kind's device build and crt_get_kdtree / crt_get_grid need of the set
+    S.desc = desc; S.count[0].resize(blasCount); S.count[1].resize(blasCount); S.height = kdHeights; S.current.assign(blasCount, (uint8_t)1); S.held = true;
+    for (uint32_t b = 0; b < blasCount; b++) {
+        const crt_alt_accel& a = blas[b];
+        S.count[0][b] = slot ? (uint32_t)a.gridResolution[0] * (uint32_t)a.gridResolution[1] * (uint32_t)a.gridResolution[2] + 1u : a.kdNodeCount;
+        S.count[1][b] = slot ? a.gridCellTriCount : a.kdTriIndexCount;
     }
     if (c->renderAccel == kind) c->renderAccel = 0;                       // as crt_upload_alt_accel: the render goes back to the BVH until crt_set_render_accel
     HIPCK(c, ensure_event(&c->altReady));
@@ -2729,8 +2733,7 @@ int crt_refit_device(crt_ctx* c, uint32_t bvh, const float* d_positions, uint32_
     memcpy(&f.rootBox[6 * (size_t)bvh], back + 16, 24);
     if (P.rootCode & crt::kPlanInterior) memcpy(f.geom.data() + (size_t)(f.pairBase[bvh] + (P.rootCode & ~crt::kPlanInterior)) * 64u, back, 64);   // the mirror's copy of the root's pair
     if (f.kind == CRT_SCENE_FILE) set_root(c, CRT_SCENE_FILE, back + 16, back + 19);      // rootPair from the mirror, dispatch-order bounds; a BLAS's box reaches the TLAS through the caller
-    if (bvh < c->blasGrid.current.size()) c->blasGrid.current[bvh] = 0;    // crt_build_grid_device(bvh) makes it current again
-    if (bvh < c->blasKd.current.size()) c->blasKd.current[bvh] = 0;        // crt_build_kdtree_device(bvh) likewise
+    for (crt_ctx::BlasSet& b : c->blasSet) b.stale(bvh);                   // crt_build_kdtree_device(bvh) / crt_build_grid_device(bvh) make it current again
     drop_blas_sets(c);
     if (rootBox) memcpy(rootBox, back + 16, 24);
     return CRT_OK;
@@ -2795,55 +2798,146 @@ int crt_update_transforms_device(crt_ctx* c, const float* d_T, uint32_t blasCoun
     return CRT_OK;
 }
 
-// ---- crt_build_grid_device: Grid::Build / BLASGrid::Build of one BVH's triangles on the device, from positions in device memory (device/grid_build.hip) ----
-// one bound from its key (grid_build.hip): the ordered value back to the float's bits, the sign of a zero from the low bit
-static float grid_bound_of(unsigned long long key)
+// ---- crt_build_grid_device / crt_build_kdtree_device: one BVH's uniform grid / KD-tree rebuilt on the device from positions in device memory, into FRESH buffers
+// that replace the live ones.  The two entries differ in the kernels they launch and in the arrays they name; what surrounds the kernels is AccelReplace ----
+// scratch of a build that grows on demand; the previous build of the kind may still be using it, so the host waits for that build first (earlier work only)
+static int grow_scratch(crt_ctx* c, const crt_ctx::AccelBuild& B, void** p, size_t* cap, size_t bytes)
 {
-    const uint32_t ord = (uint32_t)(key >> 32);
-    uint32_t bits = (ord & 0x80000000u) ? (ord & 0x7fffffffu) : ~ord;
-    if (bits == 0u && (key & 1ull)) bits = 0x80000000u;
-    float v; memcpy(&v, &bits, 4);
-    return v;
-}
-
-// scratch of the build that grows on demand; the previous build may still be using it, so the host waits for that build first (earlier work only)
-static int grow_grid_scratch(crt_ctx* c, void** p, size_t* cap, size_t need /* 4-byte words */)
-{
-    if (need <= *cap) return 0;
-    if (c->gridBuild.built) HIPCK(c, hipEventSynchronize(c->gridBuild.done));
+    if (bytes <= *cap) return 0;
+    if (B.built) HIPCK(c, hipEventSynchronize(B.done));
     if (*p) { (void)hipFree(*p); *p = nullptr; *cap = 0; }
-    HIPCK(c, hipMalloc(p, need * 4u));
-    *cap = need;
+    const hipError_t e = hipMalloc(p, bytes);
+    if (e != hipSuccess) { (void)hipGetLastError(); *p = nullptr; return c->fail(CRT_ERR_DEVICE, "device build scratch: hipMalloc(%zu): %s", bytes, hipGetErrorString(e)); }
+    *cap = bytes;
     return 0;
 }
+
+// One replacement, slot 0: the KD-tree, 1: the grid (as blasAlt / haveBlas / blasAllocs).  The kind's arrays are numbered 0: KD nodes / cellStart, 1: KD references /
+// cellRefs, 2: the AltTri records.  A FileScene's structure is the arrays alone; a two-level scene's is BLAS `bvh`'s part of the set's concatenated arrays, and the
+// other BLASes' parts are carried over.  The entry calls begin, prepare, its kernels up to the sizes it reads back, place + alloc per array, carry, the kernels that
+// write the result, commit — and then names the new arrays in AltAccelDev / TlasAltDev.  After the first alloc every failure frees what the call allocated (undo).
+struct AccelReplace {
+    crt_ctx* c; const char* me; int slot; crt_ctx::AccelBuild& B; uint32_t bvh;
+    hipStream_t st = nullptr; bool tlas = false; uint32_t N = 0;
+    std::vector<void*> fresh; void* pinned = nullptr;
+    uint64_t base[3] = {0, 0, 0}, all[3] = {0, 0, 0}; uint32_t part[3] = {0, 0, 0};     // place(): where the new part starts in array k, the array's elements, the part's
+    std::vector<crt::BlasAltDesc> desc; crt::BlasAltDesc* newDesc = nullptr;          // the set's descriptors re-based by place(); on the device after carry()
+
+    crt_ctx::BlasSet& set() const { return c->blasSet[slot]; }
+    uint32_t crt::BlasAltDesc::* base_of(int k) const
+    {
+        return k == 2 ? &crt::BlasAltDesc::triBase : slot ? (k ? &crt::BlasAltDesc::cellRefBase : &crt::BlasAltDesc::cellBase) : (k ? &crt::BlasAltDesc::refBase : &crt::BlasAltDesc::nodeBase);
+    }
+    const std::vector<uint32_t>& counts(int k) const { return k == 2 ? c->flat.triCount : set().count[k]; }
+    void undo() { (void)hipStreamSynchronize(st); for (void* p : fresh) (void)hipFree(p); if (pinned) (void)hipHostFree(pinned); }
+    int hip(hipError_t e, const char* what) { if (e == hipSuccess) return 0; undo(); return c->hip(e, what); }
+    int drop(int r) { if (r) undo(); return r; }
+#define REPLCK(R, call) do { if (const int r_ = (R).hip((call), #call)) return r_; } while (0)
+
+    // the entry checks, and the buffers retired by earlier calls that are unread by now
+    int begin(const float* d_positions, uint32_t triCount, void* stream)
+    {
+        int r;
+        if ((r = check_bvh_arg(c, me, "triangles", bvh, triCount, ""))) return r;
+        tlas = c->flat.kind == CRT_SCENE_TLAS; N = (uint32_t)c->flat.triCount.size();
+        if (triCount == 0 || triCount > 0x7fffffffu / 3u) return c->fail(CRT_ERR_UNSUPPORTED, "%s: 1 .. (2^31-1)/3 triangles", me);
+        if (tlas && (!set().held || set().desc.size() != N))
+            return c->fail(CRT_ERR_STATE, "%s: a two-level scene needs a %s set uploaded earlier (crt_upload_blas_accel(%s)): the other BLASes' parts are carried over", me,
+                           slot ? "grid" : "KD", slot ? "CRT_ACCEL_GRID" : "CRT_ACCEL_KDTREE");
+        if ((r = device_entry(c, me, {{d_positions, (size_t)triCount * 36u}}, stream, &st))) return r;
+        c->freeRetired(false);
+        if (tlas) desc = set().desc;
+        return 0;
+    }
+    // Fresh buffers, so the build is a reader: it reads the caller's positions and the LeafTri id words (which no write changes) and waits for the last scene write
+    // and for the previous build (whose scratch it reuses).  Earlier renders and queries are not waited for until the old structure is retired.
+    int prepare()
+    {
+        if (!B.blocks && !(B.blocks = crt_grid_build_blocks(c->cfg.device))) return c->fail(CRT_ERR_DEVICE, "%s: the device's compute units / occupancy could not be asked", me);
+        for (hipEvent_t* e : {&B.back, &B.done}) HIPCK(c, ensure_event(e));
+        if (g_hooks) for (hipEvent_t* e : {&B.t0, &B.t1}) HIPCK(c, ensure_event(e, hipEventDefault));
+        if (const int r = wait_scene(c, st)) return r;
+        if (B.built) HIPCK(c, hipStreamWaitEvent(st, B.done, 0));
+        if (g_hooks) HIPCK(c, hipEventRecord(B.t0, st));
+        return 0;
+    }
+    // array k with the new part `count` elements long: the part alone (FileScene), or at its re-based place among the other BLASes' parts
+    void place(int k, uint32_t count)
+    {
+        part[k] = count; base[k] = 0; all[k] = count;
+        if (!tlas) return;
+        all[k] = 0;
+        for (uint32_t b = 0; b < N; b++) { if (b == bvh) base[k] = all[k]; desc[b].*base_of(k) = (uint32_t)all[k]; all[k] += b == bvh ? count : counts(k)[b]; }
+    }
+    int alloc(size_t bytes, void** out)
+    {
+        *out = nullptr; if (!bytes) return 0;
+        const hipError_t e = hipMalloc(out, bytes);
+        if (e != hipSuccess) { (void)hipGetLastError(); *out = nullptr; undo(); return c->fail(CRT_ERR_DEVICE, "%s: hipMalloc(%zu): %s", me, bytes, hipGetErrorString(e)); }
+        fresh.push_back(*out); return 0;
+    }
+    // the other BLASes' parts of the three arrays, device to device (dst: the new arrays, src: the live set's, elem: bytes per element), and the re-based descriptors
+    int carry(void* const dst[3], const void* const src[3], const size_t elem[3])
+    {
+        if (!tlas) return 0;
+        for (uint32_t b = 0; b < N; b++)
+            for (int k = 0; k < 3 && b != bvh; k++) {
+                const size_t n = counts(k)[b], to = desc[b].*base_of(k), from = set().desc[b].*base_of(k);
+                if (n) REPLCK(*this, hipMemcpyAsync((char*)dst[k] + to * elem[k], (const char*)src[k] + from * elem[k], n * elem[k], hipMemcpyDeviceToDevice, st));
+            }
+        if (const int r = alloc(desc.size() * sizeof(crt::BlasAltDesc), (void**)&newDesc)) return r;
+        REPLCK(*this, hipHostMalloc(&pinned, desc.size() * sizeof(crt::BlasAltDesc), hipHostMallocDefault));     // read by the copy below after this call has returned: retired with the old set
+        memcpy(pinned, desc.data(), desc.size() * sizeof(crt::BlasAltDesc));
+        REPLCK(*this, hipMemcpyAsync(newDesc, pinned, desc.size() * sizeof(crt::BlasAltDesc), hipMemcpyHostToDevice, st));
+        return 0;
+    }
+    // `done` behind the build, the structure it replaces retired, the new buffers the context's
+    int commit(crt::AltTri* newTris)
+    {
+        if (g_hooks) { REPLCK(*this, hipEventRecord(B.t1, st)); B.timed = true; }
+        REPLCK(*this, hipEventRecord(B.done, st));
+        B.built = true;
+        // What it replaces is still read by launches enqueued earlier, on any stream, and by this build's own copies (the other BLASes' parts, the pinned descriptors).
+        // The main stream behind all those readers and behind the build (`done` published), and an event on it then says when the old buffers are unread.
+        crt_ctx::Retired old;
+        if (c->retiredEvents.empty()) { hipEvent_t e = nullptr; REPLCK(*this, hipEventCreateWithFlags(&e, hipEventDisableTiming)); c->retiredEvents.push_back(e); }
+        old.unread = c->retiredEvents.back(); c->retiredEvents.pop_back();
+        int r;
+        if ((r = order_behind_readers(c)) || (r = publish_scene_write(c, st, B.done)) || (r = c->hip(hipEventRecord(old.unread, c->stream), "hipEventRecord(retired)"))) {
+            c->retiredEvents.push_back(old.unread); return drop(r);
+        }
+        old.pinned = pinned;
+        if (tlas) {
+            crt_ctx::BlasSet& S = set();
+            old.ptrs.swap(c->blasAllocs[slot]); c->blasAllocs[slot] = fresh;
+            S.desc = desc; S.count[0][bvh] = part[0]; S.count[1][bvh] = part[1]; S.current[bvh] = 1;
+            c->haveBlas[slot] = S.allCurrent();                            // live again once every BLAS's part is of its current vertices
+        } else {
+            old.ptrs.swap(c->altAllocs[slot]);
+            for (void* p : fresh) if (p != (void*)newTris) c->altAllocs[slot].push_back(p);              // (newTris is not an accelerator array: it becomes altTris)
+            if (c->altTris) old.ptrs.push_back(c->altTris);
+            c->altTris = newTris; c->altTriCount = part[2]; c->alt.tris = newTris;
+            // the other structure shares altTris and is of the old positions: the entry marks it absent, as a refit marks a two-level set (its arrays go with its next upload or build)
+            if (c->renderAccel == (slot ? CRT_ACCEL_KDTREE : CRT_ACCEL_GRID)) c->renderAccel = 0;
+        }
+        c->retired.push_back(std::move(old));
+        return 0;
+    }
+};
 
 int crt_build_grid_device(crt_ctx* c, uint32_t bvh, const float* d_positions, uint32_t triCount, void* stream)
 {
     const char* const me = "crt_build_grid_device";
     if (!c) return CRT_ERR_INVALID;
-    int r;
-    if ((r = check_bvh_arg(c, me, "triangles", bvh, triCount, ""))) return r;
     crt_ctx::Flat& f = c->flat; crt_ctx::GridBuild& G = c->gridBuild;
-    const bool tlas = f.kind == CRT_SCENE_TLAS;
-    const uint32_t N = (uint32_t)f.triCount.size();
-    if (triCount == 0 || triCount > 0x7fffffffu / 3u) return c->fail(CRT_ERR_UNSUPPORTED, "%s: 1 .. (2^31-1)/3 triangles", me);
-    crt_ctx::BlasGrid& bg = c->blasGrid;
-    if (tlas && (!bg.held || bg.desc.size() != N)) return c->fail(CRT_ERR_STATE, "%s: a two-level scene needs a grid set uploaded earlier (crt_upload_blas_accel(CRT_ACCEL_GRID)): the other BLASes' parts are carried over", me);
-    hipStream_t st = nullptr;
-    if ((r = device_entry(c, me, {{d_positions, (size_t)triCount * 36u}}, stream, &st))) return r;
-    // ---- what the context keeps for the build ----
-    c->freeRetired(false);
-    if (!G.blocks && !(G.blocks = crt_grid_build_blocks(c->cfg.device))) return c->fail(CRT_ERR_DEVICE, "%s: the device's compute units / occupancy could not be asked", me);
+    AccelReplace R{c, me, 1, G, bvh};
+    int r;
+    if ((r = R.begin(d_positions, triCount, stream))) return r;
+    hipStream_t st = R.st;
     if (!G.dState) HIPCK(c, hipMalloc((void**)&G.dState, sizeof(crt::GridBuildState)));
     if (!G.hState) HIPCK(c, hipHostMalloc((void**)&G.hState, sizeof(crt::GridBuildState), hipHostMallocDefault));
     if (!G.dChunks) HIPCK(c, hipMalloc((void**)&G.dChunks, crt_grid_scan_chunks(128u * 128u * 128u) * 8u));
-    for (hipEvent_t* e : {&G.back, &G.done}) HIPCK(c, ensure_event(e));
-    if (g_hooks) for (hipEvent_t* e : {&G.t0, &G.t1}) HIPCK(c, ensure_event(e, hipEventDefault));
-    // Fresh buffers, so the build is a reader: it reads the caller's positions and the LeafTri id words (which no write changes) and waits for the last scene write
-    // and for the previous build (whose scratch it reuses).  Earlier renders and queries are not waited for until the old set is retired.
-    if ((r = wait_scene(c, st))) return r;
-    if (G.built) HIPCK(c, hipStreamWaitEvent(st, G.done, 0));
-    if (g_hooks) HIPCK(c, hipEventRecord(G.t0, st));
+    if ((r = R.prepare())) return r;
     // ---- a. bounds + finiteness; THE FIRST HOST WAIT: the resolution is computed on the host from the bounds ----
     HIPCK(c, crt_launch_grid_bounds(d_positions, triCount, G.dState, G.blocks, st));
     if ((r = read_back(c, st, G.back, G.hState, G.dState, sizeof(crt::GridBuildState), &G.waitMs[0]))) return r;
@@ -2851,117 +2945,76 @@ int crt_build_grid_device(crt_ctx* c, uint32_t bvh, const float* d_positions, ui
     // ---- b. localBounds as aabb::Grow folds them from +-1e34, then the resolution lines shared with the host build ----
     crt::GridParams gp{}; float hi[3], size[3], cell[3]; int res[3];
     for (int k = 0; k < 3; k++) {
-        const float lo = grid_bound_of(G.hState->key[k]), up = grid_bound_of(G.hState->key[3 + k]);
+        const float lo = crt::bound_of_key(G.hState->key[k]), up = crt::bound_of_key(G.hState->key[3 + k]);
         gp.lo[k] = 1e34f < lo ? 1e34f : lo; hi[k] = -1e34f > up ? -1e34f : up;
         size[k] = hi[k] - gp.lo[k];
     }
     crt::grid_resolution(size, (int)triCount, res, cell);
     for (int k = 0; k < 3; k++) { gp.res[k] = res[k]; gp.cell[k] = cell[k]; }
     const uint32_t cells = (uint32_t)res[0] * (uint32_t)res[1] * (uint32_t)res[2];
-    // ---- the new grid's buffers: a FileScene's own arrays, or the set's concatenated arrays with this BLAS's part at its re-based place ----
-    uint64_t cellBase = 0, allCells = (uint64_t)cells + 1u;
-    if (tlas) { allCells = 0; for (uint32_t b = 0; b < N; b++) { if (b == bvh) cellBase = allCells; allCells += (uint64_t)(b == bvh ? cells : bg.cells[b]) + 1u; } }
-    if (allCells > 0xffffffffull) return c->fail(CRT_ERR_UNSUPPORTED, "%s: the grid set has too many cells", me);
-    std::vector<void*> fresh; void* pinned = nullptr;
-    auto undo = [&]() { (void)hipStreamSynchronize(st); for (void* p : fresh) (void)hipFree(p); if (pinned) (void)hipHostFree(pinned); };
-    auto alloc = [&](size_t bytes, void** out) -> int {
-        *out = nullptr; if (!bytes) return 0;
-        const hipError_t e = hipMalloc(out, bytes);
-        if (e != hipSuccess) { (void)hipGetLastError(); *out = nullptr; return c->fail(CRT_ERR_DEVICE, "%s: hipMalloc(%zu): %s", me, bytes, hipGetErrorString(e)); }
-        fresh.push_back(*out); return 0;
-    };
-#define GRIDCK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { undo(); return c->hip(e_, #call); } } while (0)
+    // ---- cellStart is allocated between the waits: the count kernel writes it ----
+    R.place(0, cells + 1u);
+    if (R.all[0] > 0xffffffffull) return c->fail(CRT_ERR_UNSUPPORTED, "%s: the grid set has too many cells", me);
     uint32_t* newStart = nullptr;
-    if ((r = alloc((size_t)allCells * 4u, (void**)&newStart))) { undo(); return r; }
+    if ((r = R.alloc((size_t)R.all[0] * 4u, (void**)&newStart))) return r;
     // ---- c, d. count + exclusive scan; THE SECOND HOST WAIT: cellRefs is sized from the total ----
-    GRIDCK(crt_launch_grid_count(d_positions, triCount, &gp, cells, newStart + cellBase, G.dChunks, G.dState, G.blocks, st));
-    if ((r = read_back(c, st, G.back, G.hState, G.dState, sizeof(crt::GridBuildState), &G.waitMs[1]))) { undo(); return r; }
+    REPLCK(R, crt_launch_grid_count(d_positions, triCount, &gp, cells, newStart + R.base[0], G.dChunks, G.dState, G.blocks, st));
+    if ((r = R.drop(read_back(c, st, G.back, G.hState, G.dState, sizeof(crt::GridBuildState), &G.waitMs[1])))) return r;
     const unsigned long long total64 = G.hState->total;
-    uint64_t refBase = 0, allRefs = total64, triOff = 0, allTris = triCount;
-    if (tlas) {
-        allRefs = 0; allTris = 0;
-        for (uint32_t b = 0; b < N; b++) { if (b == bvh) { refBase = allRefs; triOff = allTris; } allRefs += b == bvh ? total64 : bg.refs[b]; allTris += f.triCount[b]; }
-    }
-    if (total64 > 0x7fffffffull || allRefs > 0xffffffffull) { undo(); return c->fail(CRT_ERR_UNSUPPORTED, "%s: %llu cell references (at most 2^31-1)", me, total64); }
     const uint32_t total = (uint32_t)total64;
-    int32_t* newRefs = nullptr; crt::AltTri* newTris = nullptr; crt::BlasAltDesc* newDesc = nullptr;
-    if ((r = alloc((size_t)allRefs * 4u, (void**)&newRefs)) || (r = alloc((size_t)allTris * sizeof(crt::AltTri), (void**)&newTris)) ||
-        (r = grow_grid_scratch(c, (void**)&G.dCursor, &G.cursorCap, (size_t)cells)) || (r = grow_grid_scratch(c, (void**)&G.dUnsorted, &G.unsortedCap, (size_t)total))) { undo(); return r; }
-    std::vector<crt::BlasAltDesc> desc;
-    if (tlas) {
-        // the other BLASes' parts, device to device, and the descriptors re-based for the new sizes
-        const crt::TlasAltDev& old = c->blasAlt[1];
-        desc = bg.desc;
-        uint64_t cb = 0, rb = 0, tb = 0;
-        for (uint32_t b = 0; b < N; b++) {
-            const crt::BlasAltDesc& od = bg.desc[b]; crt::BlasAltDesc& nd = desc[b];
-            const uint64_t nc = (uint64_t)(b == bvh ? cells : bg.cells[b]) + 1u, nr = b == bvh ? total : bg.refs[b], nt = f.triCount[b];
-            nd.cellBase = (uint32_t)cb; nd.cellRefBase = (uint32_t)rb; nd.triBase = (uint32_t)tb;
-            if (b == bvh) { for (int k = 0; k < 3; k++) { nd.res[k] = res[k]; nd.cell[k] = cell[k]; nd.lo[k] = gp.lo[k]; nd.hi[k] = hi[k]; } }
-            else {
-                GRIDCK(hipMemcpyAsync(newStart + cb, old.cellStart + od.cellBase, (size_t)nc * 4u, hipMemcpyDeviceToDevice, st));
-                if (nr) GRIDCK(hipMemcpyAsync(newRefs + rb, old.cellRefs + od.cellRefBase, (size_t)nr * 4u, hipMemcpyDeviceToDevice, st));
-                GRIDCK(hipMemcpyAsync(newTris + tb, static_cast<const crt::AltTri*>(old.tris) + od.triBase, (size_t)nt * sizeof(crt::AltTri), hipMemcpyDeviceToDevice, st));
-            }
-            cb += nc; rb += nr; tb += nt;
-        }
-        if ((r = alloc(desc.size() * sizeof(crt::BlasAltDesc), (void**)&newDesc))) { undo(); return r; }
-        GRIDCK(hipHostMalloc(&pinned, desc.size() * sizeof(crt::BlasAltDesc), hipHostMallocDefault));      // read by the copy below after this call has returned: retired with the old set
-        memcpy(pinned, desc.data(), desc.size() * sizeof(crt::BlasAltDesc));
-        GRIDCK(hipMemcpyAsync(newDesc, pinned, desc.size() * sizeof(crt::BlasAltDesc), hipMemcpyHostToDevice, st));
-    }
+    R.place(1, total); R.place(2, triCount);
+    if (total64 > 0x7fffffffull || R.all[1] > 0xffffffffull) { R.undo(); return c->fail(CRT_ERR_UNSUPPORTED, "%s: %llu cell references (at most 2^31-1)", me, total64); }
+    int32_t* newRefs = nullptr; crt::AltTri* newTris = nullptr;
+    if ((r = R.alloc((size_t)R.all[1] * 4u, (void**)&newRefs)) || (r = R.alloc((size_t)R.all[2] * sizeof(crt::AltTri), (void**)&newTris))) return r;
+    if ((r = R.drop(grow_scratch(c, G, &G.dCursor, &G.cursorCap, (size_t)cells * 4u))) || (r = R.drop(grow_scratch(c, G, &G.dUnsorted, &G.unsortedCap, (size_t)total * 4u)))) return r;
+    if (R.tlas) { crt::BlasAltDesc& nd = R.desc[bvh]; for (int k = 0; k < 3; k++) { nd.res[k] = res[k]; nd.cell[k] = cell[k]; nd.lo[k] = gp.lo[k]; nd.hi[k] = hi[k]; } }
+    const crt::TlasAltDev& live = c->blasAlt[1];
+    void* const dst[3] = {newStart, newRefs, newTris}; const void* const src[3] = {live.cellStart, live.cellRefs, live.tris}; const size_t elem[3] = {4u, 4u, sizeof(crt::AltTri)};
+    if ((r = R.carry(dst, src, elem))) return r;
     // ---- e, f. fill, sort every cell ascending, the AltTri records ----
-    GRIDCK(crt_launch_grid_fill(d_positions, triCount, &gp, cells, newStart + cellBase, G.dCursor, G.dUnsorted, newRefs ? newRefs + refBase : nullptr, total, c->hScene.geom,
-                                (uint32_t)f.leafOff, (uint32_t)f.triBase[bvh], tlas ? 1 : 0, newTris + triOff, G.blocks, st));
-    if (g_hooks) { GRIDCK(hipEventRecord(G.t1, st)); G.timed = true; }
-    GRIDCK(hipEventRecord(G.done, st));
-    G.built = true;
-    // ---- the grid it replaces: still read by launches enqueued earlier, on any stream, and by this build's own copies (the other BLASes' parts, the pinned descriptors).
-    // The main stream behind all those readers and behind the build (`done` published), and an event on it then says when the old buffers are unread ----
-    crt_ctx::Retired old;
-    if (c->retiredEvents.empty()) { hipEvent_t e = nullptr; GRIDCK(hipEventCreateWithFlags(&e, hipEventDisableTiming)); c->retiredEvents.push_back(e); }
-    old.unread = c->retiredEvents.back(); c->retiredEvents.pop_back();
-    if ((r = order_behind_readers(c)) || (r = publish_scene_write(c, st, G.done)) || (r = c->hip(hipEventRecord(old.unread, c->stream), "hipEventRecord(retired)"))) {
-        c->retiredEvents.push_back(old.unread); undo(); return r;
-    }
-#undef GRIDCK
-    old.pinned = pinned;
-    if (tlas) {
-        old.ptrs.swap(c->blasAllocs[1]); c->blasAllocs[1] = fresh;
+    REPLCK(R, crt_launch_grid_fill(d_positions, triCount, &gp, cells, newStart + R.base[0], (uint32_t*)G.dCursor, (int32_t*)G.dUnsorted, newRefs ? newRefs + R.base[1] : nullptr, total,
+                                   c->hScene.geom, (uint32_t)f.leafOff, (uint32_t)f.triBase[bvh], R.tlas ? 1 : 0, newTris + R.base[2], G.blocks, st));
+    if ((r = R.commit(newTris))) return r;
+    if (R.tlas) {
         crt::TlasAltDev& tl = c->blasAlt[1];
-        tl.desc = newDesc; tl.tris = newTris; tl.cellStart = newStart; tl.cellRefs = newRefs; tl.kdNodes = nullptr; tl.kdRefs = nullptr; tl.kdStack = 0;
-        bg.desc = desc; bg.cells[bvh] = cells; bg.refs[bvh] = total; bg.current[bvh] = 1;
-        bool all = true; for (uint8_t k : bg.current) all = all && k;
-        c->haveBlas[1] = all;                                              // live again once every BLAS's part is of its current vertices
+        tl.desc = R.newDesc; tl.tris = newTris; tl.cellStart = newStart; tl.cellRefs = newRefs; tl.kdNodes = nullptr; tl.kdRefs = nullptr; tl.kdStack = 0;
     } else {
-        old.ptrs.swap(c->altAllocs[1]);
-        for (void* p : fresh) if (p != (void*)newTris) c->altAllocs[1].push_back(p);             // (newTris is not an accelerator array: it becomes altTris)
-        if (c->altTris) old.ptrs.push_back(c->altTris);
-        c->altTris = newTris; c->altTriCount = triCount;
         crt::AltAccelDev& a = c->alt;
-        a.tris = newTris; a.cellStart = newStart; a.cellRefs = newRefs;
+        a.cellStart = newStart; a.cellRefs = newRefs;
         for (int k = 0; k < 3; k++) { a.res[k] = res[k]; a.cell[k] = cell[k]; a.lo[k] = gp.lo[k]; a.hi[k] = hi[k]; }
         c->haveGrid = true; c->gridRefCount = total;
-        // the KD-tree shares altTris and its boxes are of the old positions: absent, as a refit marks a two-level set (its arrays go with the next KD-tree upload)
-        c->haveKd = false; a.kdNodes = nullptr; a.kdRefs = nullptr; a.kdStack = 0;
-        if (c->renderAccel == CRT_ACCEL_KDTREE) c->renderAccel = 0;
+        c->haveKd = false; a.kdNodes = nullptr; a.kdRefs = nullptr; a.kdStack = 0;       // the KD-tree: absent
     }
-    c->retired.push_back(std::move(old));
     return CRT_OK;
+}
+
+// what crt_get_grid and crt_get_kdtree check first; *tlas: the structure is BLAS bvh's part of a two-level scene's set
+static int get_accel_head(crt_ctx* c, const char* me, int slot, uint32_t bvh, bool* tlas)
+{
+    if (!c) return CRT_ERR_INVALID;
+    if (!c->haveScene) return c->fail(CRT_ERR_STATE, "%s before crt_upload_scene", me);
+    if (bvh >= c->flat.triCount.size()) return c->fail(CRT_ERR_INVALID, "%s: BVH %u of a scene with %zu", me, bvh, c->flat.triCount.size());
+    *tlas = c->flat.kind == CRT_SCENE_TLAS;
+    if (*tlas ? !(c->haveBlas[slot] && c->blasSet[slot].held) : !(slot ? c->haveGrid : c->haveKd))
+        return c->fail(CRT_ERR_STATE, "%s: no live %s (not uploaded, or dropped by a refit and not rebuilt)", me, slot ? "grid" : "KD-tree");
+    return 0;
+}
+// ... and before they copy the arrays: a device build still running (an uploaded structure's copies were synchronous)
+static int get_accel_wait(crt_ctx* c, const crt_ctx::AccelBuild& B)
+{
+    HIPCK(c, hipSetDevice(c->cfg.device));
+    if (B.built) HIPCK(c, hipEventSynchronize(B.done));
+    return 0;
 }
 
 int crt_get_grid(crt_ctx* c, uint32_t bvh, int32_t res[3], float cellSize[3], float gridMin[3], float gridMax[3], uint32_t* cellCount, uint32_t* refCount, uint32_t* cellStart, int32_t* cellRefs)
 {
-    if (!c) return CRT_ERR_INVALID;
-    if (!c->haveScene) return c->fail(CRT_ERR_STATE, "crt_get_grid before crt_upload_scene");
-    const crt_ctx::Flat& f = c->flat;
-    if (bvh >= f.triCount.size()) return c->fail(CRT_ERR_INVALID, "crt_get_grid: BVH %u of a scene with %zu", bvh, f.triCount.size());
-    const bool tlas = f.kind == CRT_SCENE_TLAS;
-    if (tlas ? !(c->haveBlas[1] && c->blasGrid.held) : !c->haveGrid) return c->fail(CRT_ERR_STATE, "crt_get_grid: no live grid (not uploaded, or dropped by a refit and not rebuilt)");
+    bool tlas; int rc;
+    if ((rc = get_accel_head(c, "crt_get_grid", 1, bvh, &tlas))) return rc;
     const int32_t* r; const float *cs, *lo, *hi; uint32_t cells, refs; const uint32_t* dStart; const int32_t* dRefs;
     if (tlas) {
-        const crt::BlasAltDesc& d = c->blasGrid.desc[bvh];
-        r = d.res; cs = d.cell; lo = d.lo; hi = d.hi; cells = c->blasGrid.cells[bvh]; refs = c->blasGrid.refs[bvh];
+        const crt_ctx::BlasSet& S = c->blasSet[1]; const crt::BlasAltDesc& d = S.desc[bvh];
+        r = d.res; cs = d.cell; lo = d.lo; hi = d.hi; cells = S.count[0][bvh] - 1u; refs = S.count[1][bvh];
         dStart = c->blasAlt[1].cellStart + d.cellBase; dRefs = c->blasAlt[1].cellRefs ? c->blasAlt[1].cellRefs + d.cellRefBase : nullptr;
     } else {
         const crt::AltAccelDev& a = c->alt;
@@ -2972,55 +3025,27 @@ int crt_get_grid(crt_ctx* c, uint32_t bvh, int32_t res[3], float cellSize[3], fl
     if (cellCount) *cellCount = cells;
     if (refCount) *refCount = refs;
     if (!cellStart && !cellRefs) return CRT_OK;
-    HIPCK(c, hipSetDevice(c->cfg.device));
-    if (c->gridBuild.built) HIPCK(c, hipEventSynchronize(c->gridBuild.done));   // a device build still running (an uploaded grid's copies were synchronous)
+    if ((rc = get_accel_wait(c, c->gridBuild))) return rc;
     if (cellStart) HIPCK(c, hipMemcpy(cellStart, dStart, ((size_t)cells + 1u) * 4u, hipMemcpyDeviceToHost));
     if (cellRefs && refs) HIPCK(c, hipMemcpy(cellRefs, dRefs, (size_t)refs * 4u, hipMemcpyDeviceToHost));
     return CRT_OK;
-}
-
-// ---- crt_build_kdtree_device: KDTree::Build / BLASKDTree::Build of one BVH's triangles on the device, from positions in device memory (device/kd_build.hip) ----
-// scratch of the build that grows on demand (bytes); the previous build may still be using it, so the host waits for that build first (earlier work only)
-static int grow_kd_scratch(crt_ctx* c, void** p, size_t* cap, size_t need)
-{
-    if (need <= *cap) return 0;
-    if (c->kdBuild.built) HIPCK(c, hipEventSynchronize(c->kdBuild.done));
-    if (*p) { (void)hipFree(*p); *p = nullptr; *cap = 0; }
-    const hipError_t e = hipMalloc(p, need);
-    if (e != hipSuccess) { (void)hipGetLastError(); *p = nullptr; return c->fail(CRT_ERR_DEVICE, "crt_build_kdtree_device: hipMalloc(%zu): %s", need, hipGetErrorString(e)); }
-    *cap = need;
-    return 0;
 }
 
 int crt_build_kdtree_device(crt_ctx* c, uint32_t bvh, const float* d_positions, uint32_t triCount, void* stream)
 {
     const char* const me = "crt_build_kdtree_device";
     if (!c) return CRT_ERR_INVALID;
-    int r;
-    if ((r = check_bvh_arg(c, me, "triangles", bvh, triCount, ""))) return r;
     crt_ctx::Flat& f = c->flat; crt_ctx::KdBuild& K = c->kdBuild;
-    const bool tlas = f.kind == CRT_SCENE_TLAS;
-    const uint32_t N = (uint32_t)f.triCount.size();
-    if (triCount == 0 || triCount > 0x7fffffffu / 3u) return c->fail(CRT_ERR_UNSUPPORTED, "%s: 1 .. (2^31-1)/3 triangles", me);
-    crt_ctx::BlasKd& bk = c->blasKd;
-    if (tlas && (!bk.held || bk.desc.size() != N)) return c->fail(CRT_ERR_STATE, "%s: a two-level scene needs a KD set uploaded earlier (crt_upload_blas_accel(CRT_ACCEL_KDTREE)): the other BLASes' parts are carried over", me);
-    hipStream_t st = nullptr;
-    if ((r = device_entry(c, me, {{d_positions, (size_t)triCount * 36u}}, stream, &st))) return r;
-    // ---- what the context keeps for the build ----
-    c->freeRetired(false);
-    if (!K.blocks && !(K.blocks = crt_grid_build_blocks(c->cfg.device))) return c->fail(CRT_ERR_DEVICE, "%s: the device's compute units / occupancy could not be asked", me);
+    AccelReplace R{c, me, 0, K, bvh};
+    int r;
+    if ((r = R.begin(d_positions, triCount, stream))) return r;
+    hipStream_t st = R.st;
     if (!K.dState) HIPCK(c, hipMalloc((void**)&K.dState, sizeof(crt::KdBuildState)));
     if (!K.hState) HIPCK(c, hipHostMalloc((void**)&K.hState, sizeof(crt::KdBuildState), hipHostMallocDefault));
-    for (hipEvent_t* e : {&K.back, &K.done}) HIPCK(c, ensure_event(e));
-    if (g_hooks) for (hipEvent_t* e : {&K.t0, &K.t1}) HIPCK(c, ensure_event(e, hipEventDefault));
     crt_ctx::KdBuild::Level* lv = K.lv;
-    if ((r = grow_kd_scratch(c, &K.dTriBox, &K.triBoxCap, (size_t)triCount * 24u)) || (r = grow_kd_scratch(c, &lv[0].nodes, &lv[0].nodeCap, sizeof(crt::KdBuildNode))) ||
-        (r = grow_kd_scratch(c, &lv[0].refs, &lv[0].refCap, (size_t)triCount * 4u)) || (r = grow_kd_scratch(c, &lv[0].owner, &lv[0].ownerCap, (size_t)triCount * 4u))) return r;
-    // Fresh buffers for the tree, so the build is a reader: it reads the caller's positions and the LeafTri id words (which no write changes) and waits for the last
-    // scene write and for the previous build (whose scratch it reuses).  Earlier renders and queries are not waited for until the old tree is retired.
-    if ((r = wait_scene(c, st))) return r;
-    if (K.built) HIPCK(c, hipStreamWaitEvent(st, K.done, 0));
-    if (g_hooks) HIPCK(c, hipEventRecord(K.t0, st));
+    if ((r = grow_scratch(c, K, &K.dTriBox, &K.triBoxCap, (size_t)triCount * 24u)) || (r = grow_scratch(c, K, &lv[0].nodes, &lv[0].nodeCap, sizeof(crt::KdBuildNode))) ||
+        (r = grow_scratch(c, K, &lv[0].refs, &lv[0].refCap, (size_t)triCount * 4u)) || (r = grow_scratch(c, K, &lv[0].owner, &lv[0].ownerCap, (size_t)triCount * 4u))) return r;
+    if ((r = R.prepare())) return r;
     K.waits = 0; K.waitMs = 0; K.levels = 0;
     // ---- a. bounds + finiteness, the triangle boxes, level 0 (no wait of its own: level 0's read-back carries the flag) ----
     HIPCK(c, crt_launch_kd_begin(d_positions, triCount, K.dState, (float*)K.dTriBox, (crt::KdBuildNode*)lv[0].nodes, (uint32_t*)lv[0].refs, (uint32_t*)lv[0].owner, K.blocks, st));
@@ -3029,8 +3054,8 @@ int crt_build_kdtree_device(crt_ctx* c, uint32_t bvh, const float* d_positions, 
     uint32_t levels = 0; uint64_t allNodes64 = 0, leafRefs64 = 0;
     for (uint32_t d = 0; d < crt_ctx::KdBuild::kLevels; d++) {
         const uint32_t m = nodeCount[d], t = refCount[d];
-        if ((r = grow_kd_scratch(c, &K.dNodeItems, &K.nodeItemCap, ((size_t)m + 1u) * 8u)) || (r = grow_kd_scratch(c, &K.dRefItems, &K.refItemCap, ((size_t)t + 1u) * 8u)) ||
-            (r = grow_kd_scratch(c, &K.dChunks, &K.chunkCap, crt_kd_scan_chunks(m > t ? m : t) * 8u))) return r;
+        if ((r = grow_scratch(c, K, &K.dNodeItems, &K.nodeItemCap, ((size_t)m + 1u) * 8u)) || (r = grow_scratch(c, K, &K.dRefItems, &K.refItemCap, ((size_t)t + 1u) * 8u)) ||
+            (r = grow_scratch(c, K, &K.dChunks, &K.chunkCap, crt_kd_scan_chunks(m > t ? m : t) * 8u))) return r;
         HIPCK(c, crt_launch_kd_level((crt::KdBuildNode*)lv[d].nodes, m, d, (const uint32_t*)lv[d].owner, (const uint32_t*)lv[d].refs, t, (const float*)K.dTriBox,
                                      (unsigned long long*)K.dNodeItems, (unsigned long long*)K.dRefItems, (unsigned long long*)K.dChunks, K.dState, K.blocks, st));
         double ms = 0;
@@ -3045,125 +3070,69 @@ int crt_build_kdtree_device(crt_ctx* c, uint32_t bvh, const float* d_positions, 
         if (next > 0x7fffffffull) return c->fail(CRT_ERR_UNSUPPORTED, "%s: level %u has %llu references (at most 2^31-1)", me, d + 1u, (unsigned long long)next);
         if (d + 1u >= crt_ctx::KdBuild::kLevels || splits > m) return c->fail(CRT_ERR_DEVICE, "%s: the level kernels reported %llu split nodes of %u at depth %u", me, (unsigned long long)splits, m, d);
         nodeCount[d + 1u] = (uint32_t)(2u * splits); refCount[d + 1u] = (uint32_t)next;
-        if ((r = grow_kd_scratch(c, &lv[d + 1u].nodes, &lv[d + 1u].nodeCap, (size_t)nodeCount[d + 1u] * sizeof(crt::KdBuildNode))) ||
-            (r = grow_kd_scratch(c, &lv[d + 1u].refs, &lv[d + 1u].refCap, (size_t)next * 4u)) || (r = grow_kd_scratch(c, &lv[d + 1u].owner, &lv[d + 1u].ownerCap, (size_t)next * 4u))) return r;
+        if ((r = grow_scratch(c, K, &lv[d + 1u].nodes, &lv[d + 1u].nodeCap, (size_t)nodeCount[d + 1u] * sizeof(crt::KdBuildNode))) ||
+            (r = grow_scratch(c, K, &lv[d + 1u].refs, &lv[d + 1u].refCap, (size_t)next * 4u)) || (r = grow_scratch(c, K, &lv[d + 1u].owner, &lv[d + 1u].ownerCap, (size_t)next * 4u))) return r;
         HIPCK(c, crt_launch_kd_split((crt::KdBuildNode*)lv[d].nodes, m, (const unsigned long long*)K.dNodeItems, (const uint32_t*)lv[d].owner, (const uint32_t*)lv[d].refs, t,
                                      (const unsigned long long*)K.dRefItems, (crt::KdBuildNode*)lv[d + 1u].nodes, nodeCount[d + 1u], (uint32_t*)lv[d + 1u].refs, (uint32_t*)lv[d + 1u].owner,
                                      refCount[d + 1u], K.blocks, st));
     }
     K.levels = levels;
     const uint32_t height = levels - 1u, newNodes = (uint32_t)allNodes64, newRefs = (uint32_t)leafRefs64;
-    // ---- the new tree's buffers: a FileScene's own arrays, or the set's concatenated arrays with this BLAS's part at its re-based place ----
-    uint64_t nodeBase = 0, refBase = 0, triOff = 0, allNodes = newNodes, allRefs = newRefs, allTris = triCount; uint32_t maxKd = height + 1u;
-    if (tlas) {
-        allNodes = allRefs = allTris = 0; maxKd = 0;
-        for (uint32_t b = 0; b < N; b++) {
-            if (b == bvh) { nodeBase = allNodes; refBase = allRefs; triOff = allTris; }
-            allNodes += b == bvh ? newNodes : bk.nodes[b]; allRefs += b == bvh ? newRefs : bk.refs[b]; allTris += f.triCount[b];
-            const uint32_t h = (b == bvh ? height : bk.height[b]) + 1u; if (h > maxKd) maxKd = h;
-        }
-        if (allNodes > 0xffffffffull || allRefs > 0xffffffffull || allTris > 0xffffffffull) return c->fail(CRT_ERR_UNSUPPORTED, "%s: the KD set is too large", me);
+    // ---- the new tree's arrays, allocated after the last wait; a set's deepest tree sizes the traversal stack ----
+    R.place(0, newNodes); R.place(1, newRefs); R.place(2, triCount);
+    uint32_t maxKd = height + 1u;
+    if (R.tlas) {
+        const crt_ctx::BlasSet& S = c->blasSet[0];
+        for (uint32_t b = 0; b < R.N; b++) if (b != bvh && S.height[b] + 1u > maxKd) maxKd = S.height[b] + 1u;
+        if (R.all[0] > 0xffffffffull || R.all[1] > 0xffffffffull || R.all[2] > 0xffffffffull) return c->fail(CRT_ERR_UNSUPPORTED, "%s: the KD set is too large", me);
         const uint32_t words = maxKd * 2u + (c->hScene.stackDepth - c->hScene.bvhStack);      // as crt_upload_blas_accel
         if (!wave_stack_fits(words)) return c->fail(CRT_ERR_UNSUPPORTED, "%s: TLAS + KD-tree traversal stack of %u dwords per lane exceeds the LDS budget", me, words);
     }
-    std::vector<void*> fresh; void* pinned = nullptr;
-    auto undo = [&]() { (void)hipStreamSynchronize(st); for (void* p : fresh) (void)hipFree(p); if (pinned) (void)hipHostFree(pinned); };
-    auto alloc = [&](size_t bytes, void** out) -> int {
-        *out = nullptr; if (!bytes) return 0;
-        const hipError_t e = hipMalloc(out, bytes);
-        if (e != hipSuccess) { (void)hipGetLastError(); *out = nullptr; return c->fail(CRT_ERR_DEVICE, "%s: hipMalloc(%zu): %s", me, bytes, hipGetErrorString(e)); }
-        fresh.push_back(*out); return 0;
-    };
-#define KDCK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { undo(); return c->hip(e_, #call); } } while (0)
-    crt::KdNode* newNodeArr = nullptr; uint32_t* newRefArr = nullptr; crt::AltTri* newTris = nullptr; crt::BlasAltDesc* newDesc = nullptr;
-    if ((r = alloc((size_t)allNodes * sizeof(crt::KdNode), (void**)&newNodeArr)) || (r = alloc((size_t)allRefs * 4u, (void**)&newRefArr)) ||
-        (r = alloc((size_t)allTris * sizeof(crt::AltTri), (void**)&newTris))) { undo(); return r; }
-    std::vector<crt::BlasAltDesc> desc;
-    if (tlas) {
-        // the other BLASes' parts, device to device, and the descriptors re-based for the new sizes
-        const crt::TlasAltDev& old = c->blasAlt[0];
-        desc = bk.desc;
-        uint64_t nb = 0, rb = 0, tb = 0;
-        for (uint32_t b = 0; b < N; b++) {
-            const crt::BlasAltDesc& od = bk.desc[b]; crt::BlasAltDesc& nd = desc[b];
-            const uint64_t nn = b == bvh ? newNodes : bk.nodes[b], nr = b == bvh ? newRefs : bk.refs[b], nt = f.triCount[b];
-            nd.nodeBase = (uint32_t)nb; nd.refBase = (uint32_t)rb; nd.triBase = (uint32_t)tb;
-            if (b != bvh) {
-                KDCK(hipMemcpyAsync(newNodeArr + nb, static_cast<const crt::KdNode*>(old.kdNodes) + od.nodeBase, (size_t)nn * sizeof(crt::KdNode), hipMemcpyDeviceToDevice, st));
-                if (nr) KDCK(hipMemcpyAsync(newRefArr + rb, old.kdRefs + od.refBase, (size_t)nr * 4u, hipMemcpyDeviceToDevice, st));
-                KDCK(hipMemcpyAsync(newTris + tb, static_cast<const crt::AltTri*>(old.tris) + od.triBase, (size_t)nt * sizeof(crt::AltTri), hipMemcpyDeviceToDevice, st));
-            }
-            nb += nn; rb += nr; tb += nt;
-        }
-        if ((r = alloc(desc.size() * sizeof(crt::BlasAltDesc), (void**)&newDesc))) { undo(); return r; }
-        KDCK(hipHostMalloc(&pinned, desc.size() * sizeof(crt::BlasAltDesc), hipHostMallocDefault));      // read by the copy below after this call has returned: retired with the old set
-        memcpy(pinned, desc.data(), desc.size() * sizeof(crt::BlasAltDesc));
-        KDCK(hipMemcpyAsync(newDesc, pinned, desc.size() * sizeof(crt::BlasAltDesc), hipMemcpyHostToDevice, st));
-    }
+    crt::KdNode* newNodeArr = nullptr; uint32_t* newRefArr = nullptr; crt::AltTri* newTris = nullptr;
+    if ((r = R.alloc((size_t)R.all[0] * sizeof(crt::KdNode), (void**)&newNodeArr)) || (r = R.alloc((size_t)R.all[1] * 4u, (void**)&newRefArr)) ||
+        (r = R.alloc((size_t)R.all[2] * sizeof(crt::AltTri), (void**)&newTris))) return r;
+    const crt::TlasAltDev& live = c->blasAlt[0];
+    void* const dst[3] = {newNodeArr, newRefArr, newTris}; const void* const src[3] = {live.kdNodes, live.kdRefs, live.tris}; const size_t elem[3] = {sizeof(crt::KdNode), 4u, sizeof(crt::AltTri)};
+    if ((r = R.carry(dst, src, elem))) return r;
     // ---- c. finalise: subtree sizes bottom-up, pre-order places top-down, the records and the leaf references; the AltTri records ----
     {
         crt::KdBuildNode* ln[crt_ctx::KdBuild::kLevels]; const uint32_t* lr[crt_ctx::KdBuild::kLevels]; const uint32_t* lo[crt_ctx::KdBuild::kLevels];
         for (uint32_t d = 0; d < levels; d++) { ln[d] = (crt::KdBuildNode*)lv[d].nodes; lr[d] = (const uint32_t*)lv[d].refs; lo[d] = (const uint32_t*)lv[d].owner; }
-        KDCK(crt_launch_kd_finalise(ln, lr, lo, nodeCount, refCount, levels, newNodeArr + nodeBase, newNodes, newRefArr ? newRefArr + refBase : nullptr, newRefs, K.blocks, st));
+        REPLCK(R, crt_launch_kd_finalise(ln, lr, lo, nodeCount, refCount, levels, newNodeArr + R.base[0], newNodes, newRefArr ? newRefArr + R.base[1] : nullptr, newRefs, K.blocks, st));
     }
-    KDCK(crt_launch_alt_tris(d_positions, triCount, c->hScene.geom, (uint32_t)f.leafOff, (uint32_t)f.triBase[bvh], tlas ? 1 : 0, newTris + triOff, st));
-    if (g_hooks) { KDCK(hipEventRecord(K.t1, st)); K.timed = true; }
-    KDCK(hipEventRecord(K.done, st));
-    K.built = true;
-    // ---- the tree it replaces: still read by launches enqueued earlier, on any stream, and by this build's own copies; retired as crt_build_grid_device retires a grid ----
-    crt_ctx::Retired old;
-    if (c->retiredEvents.empty()) { hipEvent_t e = nullptr; KDCK(hipEventCreateWithFlags(&e, hipEventDisableTiming)); c->retiredEvents.push_back(e); }
-    old.unread = c->retiredEvents.back(); c->retiredEvents.pop_back();
-    if ((r = order_behind_readers(c)) || (r = publish_scene_write(c, st, K.done)) || (r = c->hip(hipEventRecord(old.unread, c->stream), "hipEventRecord(retired)"))) {
-        c->retiredEvents.push_back(old.unread); undo(); return r;
-    }
-#undef KDCK
-    old.pinned = pinned;
-    if (tlas) {
-        old.ptrs.swap(c->blasAllocs[0]); c->blasAllocs[0] = fresh;
+    REPLCK(R, crt_launch_alt_tris(d_positions, triCount, c->hScene.geom, (uint32_t)f.leafOff, (uint32_t)f.triBase[bvh], R.tlas ? 1 : 0, newTris + R.base[2], st));
+    if ((r = R.commit(newTris))) return r;
+    if (R.tlas) {
         crt::TlasAltDev& tl = c->blasAlt[0];
-        tl.desc = newDesc; tl.tris = newTris; tl.kdNodes = newNodeArr; tl.kdRefs = newRefArr; tl.cellStart = nullptr; tl.cellRefs = nullptr; tl.kdStack = maxKd;
-        bk.desc = desc; bk.nodes[bvh] = newNodes; bk.refs[bvh] = newRefs; bk.height[bvh] = height; bk.current[bvh] = 1;
-        bool all = true; for (uint8_t k : bk.current) all = all && k;
-        c->haveBlas[0] = all;                                              // live again once every BLAS's part is of its current vertices
+        tl.desc = R.newDesc; tl.tris = newTris; tl.kdNodes = newNodeArr; tl.kdRefs = newRefArr; tl.cellStart = nullptr; tl.cellRefs = nullptr; tl.kdStack = maxKd;
+        c->blasSet[0].height[bvh] = height;
         if (c->renderAccel == CRT_ACCEL_KDTREE && !sample_lds_fits(sample_stack_words(c, CRT_ACCEL_KDTREE))) c->renderAccel = 0;   // (a set rebuilt while live, now deeper than the render stack)
     } else {
-        old.ptrs.swap(c->altAllocs[0]);
-        for (void* p : fresh) if (p != (void*)newTris) c->altAllocs[0].push_back(p);             // (newTris is not an accelerator array: it becomes altTris)
-        if (c->altTris) old.ptrs.push_back(c->altTris);
-        c->altTris = newTris; c->altTriCount = triCount;
         crt::AltAccelDev& a = c->alt;
-        a.tris = newTris; a.kdNodes = newNodeArr; a.kdRefs = newRefArr; a.kdStack = height + 1u;
+        a.kdNodes = newNodeArr; a.kdRefs = newRefArr; a.kdStack = height + 1u;
         c->haveKd = true; c->kdNodeCount = newNodes; c->kdRefCount = newRefs;
-        // the grid shares altTris and its cells are of the old positions: absent, as crt_build_grid_device marks the KD-tree (its arrays go with the next grid upload or build)
-        c->haveGrid = false; a.cellStart = nullptr; a.cellRefs = nullptr; c->gridRefCount = 0;
+        c->haveGrid = false; a.cellStart = nullptr; a.cellRefs = nullptr; c->gridRefCount = 0;     // the grid: absent
         for (int k = 0; k < 3; k++) { a.res[k] = 0; a.cell[k] = 0.0f; a.lo[k] = 0.0f; a.hi[k] = 0.0f; }
-        if (c->renderAccel == CRT_ACCEL_GRID) c->renderAccel = 0;
     }
-    c->retired.push_back(std::move(old));
     return CRT_OK;
 }
+#undef REPLCK
 
 int crt_get_kdtree(crt_ctx* c, uint32_t bvh, uint32_t* nodeCount, uint32_t* refCount, uint32_t* height, crt_kd_node* nodes, uint32_t* refs)
 {
-    if (!c) return CRT_ERR_INVALID;
-    if (!c->haveScene) return c->fail(CRT_ERR_STATE, "crt_get_kdtree before crt_upload_scene");
-    const crt_ctx::Flat& f = c->flat;
-    if (bvh >= f.triCount.size()) return c->fail(CRT_ERR_INVALID, "crt_get_kdtree: BVH %u of a scene with %zu", bvh, f.triCount.size());
-    const bool tlas = f.kind == CRT_SCENE_TLAS;
-    if (tlas ? !(c->haveBlas[0] && c->blasKd.held) : !c->haveKd) return c->fail(CRT_ERR_STATE, "crt_get_kdtree: no live KD-tree (not uploaded, or dropped by a refit and not rebuilt)");
+    bool tlas; int rc;
+    if ((rc = get_accel_head(c, "crt_get_kdtree", 0, bvh, &tlas))) return rc;
     uint32_t nn, nr, h; const crt::KdNode* dNodes; const uint32_t* dRefs;
     if (tlas) {
-        const crt::BlasAltDesc& d = c->blasKd.desc[bvh];
-        nn = c->blasKd.nodes[bvh]; nr = c->blasKd.refs[bvh]; h = c->blasKd.height[bvh];
+        const crt_ctx::BlasSet& S = c->blasSet[0]; const crt::BlasAltDesc& d = S.desc[bvh];
+        nn = S.count[0][bvh]; nr = S.count[1][bvh]; h = S.height[bvh];
         dNodes = static_cast<const crt::KdNode*>(c->blasAlt[0].kdNodes) + d.nodeBase; dRefs = c->blasAlt[0].kdRefs ? c->blasAlt[0].kdRefs + d.refBase : nullptr;
     } else { nn = c->kdNodeCount; nr = c->kdRefCount; h = c->alt.kdStack - 1u; dNodes = c->alt.kdNodes; dRefs = c->alt.kdRefs; }
     if (nodeCount) *nodeCount = nn;
     if (refCount) *refCount = nr;
     if (height) *height = h;
     if (!nodes && !refs) return CRT_OK;
-    HIPCK(c, hipSetDevice(c->cfg.device));
-    if (c->kdBuild.built) HIPCK(c, hipEventSynchronize(c->kdBuild.done));   // a device build still running (an uploaded tree's copies were synchronous)
+    if ((rc = get_accel_wait(c, c->kdBuild))) return rc;
     if (nodes) HIPCK(c, hipMemcpy(nodes, dNodes, (size_t)nn * sizeof(crt::KdNode), hipMemcpyDeviceToHost));
     if (refs && nr) HIPCK(c, hipMemcpy(refs, dRefs, (size_t)nr * 4u, hipMemcpyDeviceToHost));
     return CRT_OK;

@@ -11,8 +11,8 @@
 //                            conversion restated as x86's, which gives INT_MIN for NaN and for anything out of range: a NaN quotient — 0 / 0 on a flat axis — ends in
 //                            cell 0 after the clamp, as on the host), then one atomicAdd per covered cell.  A triangle that covers more than 64 cells is spread over
 //                            its wavefront, so one large triangle does not serialise 2 M atomics on one lane.
-//   grid_scan_*_kernel       exclusive prefix over the cells + 1 counters, multi-block (sums per 2048-counter chunk, one block over the chunk sums, apply), 64-bit
-//                            sums: the total goes back to the host, which sizes cellRefs from it and refuses more than 2^31 - 1 references.
+//   scan_*_kernel<uint32_t>  exclusive prefix over the cells + 1 counters (build_common.h: multi-block, 64-bit chunk sums): the total goes back to the host, which
+//                            sizes cellRefs from it and refuses more than 2^31 - 1 references.
 //   grid_fill_kernel         the same ranges again; slots are handed out by atomics, so their order inside a cell is not deterministic ...
 //   grid_sort_kernel         ... and every cell's segment is then put in ascending order, which is the host build's push_back order: indices inside a cell are
 //                            distinct, so out[#smaller] = e is exact.  One lane per cell of up to 32 references, the wavefront together for a longer one.
@@ -20,18 +20,15 @@
 //
 // Integer atomics only; -ffp-contract=off as everywhere.
 #include "launch.h"
+#include "build_common.h"
 
 namespace crt {
 
 typedef float row4 __attribute__((ext_vector_type(4)));
 
-constexpr uint32_t kGridThreads = 256u;
-constexpr uint32_t kScanItems = 8u, kScanChunk = kGridThreads * kScanItems;       // counters per block of the scan kernels
+constexpr uint32_t kGridThreads = kBuildThreads;
 constexpr uint32_t kWaveCells = 64u;                                              // a triangle over more cells than this is spread over the wavefront
 constexpr uint32_t kLaneCellRefs = 32u;                                           // a cell with more references than this is sorted by the wavefront
-
-__device__ __forceinline__ float lesser(float a, float b) { return a < b ? a : b; }     // tmplmath.h:122 / _mm_min_ps operand order
-__device__ __forceinline__ float greater(float a, float b) { return a > b ? a : b; }
 
 // static_cast<int>(float) as the host build's x86 code performs it (cvttss2si): the "integer indefinite" value for NaN and for every value outside int's range
 __device__ __forceinline__ int x86_int(float q) { return (q >= -2147483648.0f && q < 2147483648.0f) ? (int)q : (int)0x80000000; }
@@ -125,50 +122,6 @@ __global__ __launch_bounds__(kGridThreads) void grid_fill_kernel(const float* __
     }
 }
 
-// ---- the exclusive prefix over n = cells + 1 counters (the last one is 0, so counts[cells] ends as the total) ----
-__global__ __launch_bounds__(kGridThreads) void grid_scan_sums_kernel(const uint32_t* __restrict__ counts, uint32_t n, unsigned long long* chunkSums)
-{
-    __shared__ unsigned long long s[kGridThreads];
-    const uint32_t first = blockIdx.x * kScanChunk + threadIdx.x * kScanItems;
-    unsigned long long sum = 0;
-    for (uint32_t i = 0; i < kScanItems; i++) if (first + i < n) sum += counts[first + i];
-    s[threadIdx.x] = sum; __syncthreads();
-    for (uint32_t off = kGridThreads / 2u; off > 0u; off >>= 1) { if (threadIdx.x < off) s[threadIdx.x] += s[threadIdx.x + off]; __syncthreads(); }
-    if (threadIdx.x == 0u) chunkSums[blockIdx.x] = s[0];
-}
-
-// one block: chunkSums becomes its own exclusive prefix, the total goes to the state block
-__global__ __launch_bounds__(kGridThreads) void grid_scan_chunks_kernel(unsigned long long* chunkSums, uint32_t chunks, GridBuildState* st)
-{
-    __shared__ unsigned long long s[2][kGridThreads];
-    const uint32_t per = (chunks + kGridThreads - 1u) / kGridThreads, first = threadIdx.x * per;
-    unsigned long long sum = 0;
-    for (uint32_t i = 0; i < per; i++) if (first + i < chunks) sum += chunkSums[first + i];
-    int in = 0; s[0][threadIdx.x] = sum; __syncthreads();
-    for (uint32_t off = 1u; off < kGridThreads; off <<= 1) {
-        s[1 - in][threadIdx.x] = s[in][threadIdx.x] + (threadIdx.x >= off ? s[in][threadIdx.x - off] : 0ull);
-        __syncthreads(); in = 1 - in;
-    }
-    unsigned long long run = s[in][threadIdx.x] - sum;                                // exclusive
-    for (uint32_t i = 0; i < per; i++) if (first + i < chunks) { const unsigned long long c = chunkSums[first + i]; chunkSums[first + i] = run; run += c; }
-    if (threadIdx.x == kGridThreads - 1u) st->total = s[in][threadIdx.x];
-}
-
-__global__ __launch_bounds__(kGridThreads) void grid_scan_apply_kernel(uint32_t* counts, uint32_t n, const unsigned long long* __restrict__ chunkSums)
-{
-    __shared__ uint32_t s[2][kGridThreads];
-    const uint32_t first = blockIdx.x * kScanChunk + threadIdx.x * kScanItems;
-    uint32_t v[kScanItems]; uint32_t sum = 0;
-    for (uint32_t i = 0; i < kScanItems; i++) { v[i] = first + i < n ? counts[first + i] : 0u; sum += v[i]; }
-    int in = 0; s[0][threadIdx.x] = sum; __syncthreads();
-    for (uint32_t off = 1u; off < kGridThreads; off <<= 1) {
-        s[1 - in][threadIdx.x] = s[in][threadIdx.x] + (threadIdx.x >= off ? s[in][threadIdx.x - off] : 0u);
-        __syncthreads(); in = 1 - in;
-    }
-    uint32_t run = (uint32_t)chunkSums[blockIdx.x] + (s[in][threadIdx.x] - sum);
-    for (uint32_t i = 0; i < kScanItems; i++) if (first + i < n) { counts[first + i] = run; run += v[i]; }
-}
-
 // every cell's segment of `in` in ascending order into `out` (the same offsets)
 __global__ __launch_bounds__(kGridThreads) void grid_sort_kernel(const uint32_t* __restrict__ cellStart, uint32_t cells, uint32_t total, const int32_t* __restrict__ in, int32_t* out)
 {
@@ -217,12 +170,6 @@ __global__ __launch_bounds__(kGridThreads) void grid_tris_kernel(const char* __r
     o[0] = r0; o[1] = r1; o[2] = r2;
 }
 
-static uint32_t blocks_for(uint32_t items, uint32_t maxBlocks)
-{
-    const uint32_t need = (items + kGridThreads - 1u) / kGridThreads;
-    return need < maxBlocks ? (need ? need : 1u) : maxBlocks;
-}
-
 } // namespace crt
 
 // workgroups of 256 lanes the device holds at once for the build's kernels (occupancy of the count kernel x compute units); 0: the device could not be asked
@@ -234,7 +181,7 @@ extern "C" uint32_t crt_grid_build_blocks(int device)
     return (uint32_t)perCu * (uint32_t)cus;
 }
 
-extern "C" size_t crt_grid_scan_chunks(uint32_t cells) { return ((size_t)cells + 1u + crt::kScanChunk - 1u) / crt::kScanChunk; }
+extern "C" size_t crt_grid_scan_chunks(uint32_t cells) { return crt::scan_chunks((size_t)cells + 1u); }
 
 extern "C" hipError_t crt_launch_grid_bounds(const float* pos, uint32_t triCount, crt::GridBuildState* state, uint32_t maxBlocks, hipStream_t stream)
 {
@@ -254,12 +201,7 @@ extern "C" hipError_t crt_launch_grid_count(const float* pos, uint32_t triCount,
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(crt::grid_count_kernel, dim3(crt::blocks_for(triCount, maxBlocks)), dim3(crt::kGridThreads), 0, stream, pos, triCount, *g, counts);
     if ((e = hipGetLastError()) != hipSuccess) return e;
-    hipLaunchKernelGGL(crt::grid_scan_sums_kernel, dim3(chunks), dim3(crt::kGridThreads), 0, stream, counts, n, chunkSums);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    hipLaunchKernelGGL(crt::grid_scan_chunks_kernel, dim3(1), dim3(crt::kGridThreads), 0, stream, chunkSums, chunks, state);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    hipLaunchKernelGGL(crt::grid_scan_apply_kernel, dim3(chunks), dim3(crt::kGridThreads), 0, stream, counts, n, chunkSums);
-    return hipGetLastError();
+    return crt::scan(counts, n, chunks, chunkSums, (uint32_t*)nullptr, &state->total, stream);     // (the last counter is 0, so counts[cells] ends as the total too)
 }
 
 // cursor: cells words of scratch; unsorted: total words of scratch; refs: the total references of the finished grid; tris: the BVH's triCount AltTri records

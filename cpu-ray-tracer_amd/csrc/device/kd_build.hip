@@ -11,8 +11,8 @@
 //                            writes the node's scan item: 1 for a split node | its reference count << 32 for a leaf
 //   kd_classify_kernel       one lane per reference: left (bmax < splitPos), else right ((double)bmin > (double)splitPos - 0.001, kdtree.cpp:71), else both;
 //                            its scan item: goes left | goes right << 32
-//   kd_scan_*_kernel         exclusive prefix of either item array in place, both halves at once (multi-block: sums per 2048-item chunk, one block over the chunk
-//                            sums, apply); the total goes to the state block, which the host reads to size the next level
+//   scan_*_kernel<64-bit>    exclusive prefix of either item array in place, both halves at once (build_common.h: multi-block); the total goes behind the items
+//                            and to the state block, which the host reads to size the next level
 //   kd_split_kernel          one lane per node: the two children (the parent's box with one component replaced by splitPos) at 2 * (split nodes before it) in the next
 //                            level; one lane per reference: its place(s) in the next level's array — [left list][right list] per split node in level order, each list
 //                            in the parent's order — are sums of prefix values, so no atomic's arrival order reaches the output
@@ -25,33 +25,22 @@
 //
 // The height is the index of the last level: the host knows it without a reduction.  No floating-point atomics, no atomics at all; -ffp-contract=off as everywhere.
 #include "launch.h"
+#include "build_common.h"
 
 namespace crt {
 
 typedef float row4 __attribute__((ext_vector_type(4)));
 
-constexpr uint32_t kKdThreads = 256u;
-constexpr uint32_t kKdScanItems = 8u, kKdScanChunk = kKdThreads * kKdScanItems;   // items per block of the scan kernels
+constexpr uint32_t kKdThreads = kBuildThreads;
 
-__device__ __forceinline__ float kd_lesser(float a, float b) { return a < b ? a : b; }       // tmplmath.h:122 / _mm_min_ps operand order
-__device__ __forceinline__ float kd_greater(float a, float b) { return a > b ? a : b; }
 __device__ __forceinline__ float kd_pick(float x, float y, float z, int axis) { return axis == 0 ? x : (axis == 1 ? y : z); }
-
-// one bound from its key (grid_build.hip): the ordered value back to the float's bits, the sign of a zero from the low bit
-__device__ __forceinline__ float kd_bound_of(unsigned long long key)
-{
-    const uint32_t ord = (uint32_t)(key >> 32);
-    uint32_t bits = (ord & 0x80000000u) ? (ord & 0x7fffffffu) : ~ord;
-    if (bits == 0u && (key & 1ull)) bits = 0x80000000u;
-    return __uint_as_float(bits);
-}
 
 __global__ __launch_bounds__(64) void kd_root_kernel(const KdBuildState* __restrict__ st, uint32_t triCount, KdBuildNode* root)
 {
     if (threadIdx.x != 0u || blockIdx.x != 0u) return;
     KdBuildNode n{};
     for (int k = 0; k < 3; k++) {
-        const float lo = kd_bound_of(st->bounds.key[k]), up = kd_bound_of(st->bounds.key[3 + k]);
+        const float lo = bound_of_key(st->bounds.key[k]), up = bound_of_key(st->bounds.key[3 + k]);
         n.lo[k] = 1e34f < lo ? 1e34f : lo; n.hi[k] = -1e34f > up ? -1e34f : up;    // aabb::Grow from +-1e34 (the host's fold of the same bounds)
     }
     n.first = 0u; n.count = triCount; n.axis = -1;
@@ -65,8 +54,8 @@ __global__ __launch_bounds__(kKdThreads) void kd_tri_box_kernel(const float* __r
         const float* v = pos + (size_t)t * 9u;
         float* b = triBox + (size_t)t * 6u;
         for (int k = 0; k < 3; k++) {
-            b[k] = kd_lesser(kd_lesser(kd_lesser(1e34f, v[k]), v[3 + k]), v[6 + k]);
-            b[3 + k] = kd_greater(kd_greater(kd_greater(-1e34f, v[k]), v[3 + k]), v[6 + k]);
+            b[k] = lesser(lesser(lesser(1e34f, v[k]), v[3 + k]), v[6 + k]);
+            b[3 + k] = greater(greater(greater(-1e34f, v[k]), v[3 + k]), v[6 + k]);
         }
         refs[t] = t; owner[t] = 0u;
     }
@@ -115,50 +104,6 @@ __global__ __launch_bounds__(kKdThreads) void kd_classify_kernel(const KdBuildNo
         }
         item[j] = v;
     }
-}
-
-// ---- the exclusive prefix over n 64-bit items, two 32-bit sums side by side (neither half can carry: see KdBuildState); item[n] receives the total ----
-__global__ __launch_bounds__(kKdThreads) void kd_scan_sums_kernel(const unsigned long long* __restrict__ item, uint32_t n, unsigned long long* chunkSums)
-{
-    __shared__ unsigned long long s[kKdThreads];
-    const uint32_t first = blockIdx.x * kKdScanChunk + threadIdx.x * kKdScanItems;
-    unsigned long long sum = 0;
-    for (uint32_t i = 0; i < kKdScanItems; i++) if (first + i < n) sum += item[first + i];
-    s[threadIdx.x] = sum; __syncthreads();
-    for (uint32_t off = kKdThreads / 2u; off > 0u; off >>= 1) { if (threadIdx.x < off) s[threadIdx.x] += s[threadIdx.x + off]; __syncthreads(); }
-    if (threadIdx.x == 0u) chunkSums[blockIdx.x] = s[0];
-}
-
-// one block: chunkSums becomes its own exclusive prefix; the total goes behind the items and to the state block
-__global__ __launch_bounds__(kKdThreads) void kd_scan_chunks_kernel(unsigned long long* chunkSums, uint32_t chunks, unsigned long long* itemEnd, unsigned long long* total)
-{
-    __shared__ unsigned long long s[2][kKdThreads];
-    const uint32_t per = (chunks + kKdThreads - 1u) / kKdThreads, first = threadIdx.x * per;
-    unsigned long long sum = 0;
-    for (uint32_t i = 0; i < per; i++) if (first + i < chunks) sum += chunkSums[first + i];
-    int in = 0; s[0][threadIdx.x] = sum; __syncthreads();
-    for (uint32_t off = 1u; off < kKdThreads; off <<= 1) {
-        s[1 - in][threadIdx.x] = s[in][threadIdx.x] + (threadIdx.x >= off ? s[in][threadIdx.x - off] : 0ull);
-        __syncthreads(); in = 1 - in;
-    }
-    unsigned long long run = s[in][threadIdx.x] - sum;                                // exclusive
-    for (uint32_t i = 0; i < per; i++) if (first + i < chunks) { const unsigned long long c = chunkSums[first + i]; chunkSums[first + i] = run; run += c; }
-    if (threadIdx.x == kKdThreads - 1u) { *itemEnd = s[in][threadIdx.x]; *total = s[in][threadIdx.x]; }
-}
-
-__global__ __launch_bounds__(kKdThreads) void kd_scan_apply_kernel(unsigned long long* item, uint32_t n, const unsigned long long* __restrict__ chunkSums)
-{
-    __shared__ unsigned long long s[2][kKdThreads];
-    const uint32_t first = blockIdx.x * kKdScanChunk + threadIdx.x * kKdScanItems;
-    unsigned long long v[kKdScanItems]; unsigned long long sum = 0;
-    for (uint32_t i = 0; i < kKdScanItems; i++) { v[i] = first + i < n ? item[first + i] : 0ull; sum += v[i]; }
-    int in = 0; s[0][threadIdx.x] = sum; __syncthreads();
-    for (uint32_t off = 1u; off < kKdThreads; off <<= 1) {
-        s[1 - in][threadIdx.x] = s[in][threadIdx.x] + (threadIdx.x >= off ? s[in][threadIdx.x - off] : 0ull);
-        __syncthreads(); in = 1 - in;
-    }
-    unsigned long long run = chunkSums[blockIdx.x] + (s[in][threadIdx.x] - sum);
-    for (uint32_t i = 0; i < kKdScanItems; i++) if (first + i < n) { item[first + i] = run; run += v[i]; }
 }
 
 // Subdivide's tail (kdtree.cpp:82-100) from the two prefixes: nodeScan[i] & 0xffffffff = split nodes before node i; refScan[j] = references before j that go
@@ -259,28 +204,10 @@ __global__ __launch_bounds__(kKdThreads) void kd_emit_kernel(const KdBuildNode* 
     }
 }
 
-static uint32_t kd_blocks_for(uint32_t items, uint32_t maxBlocks)
-{
-    const uint32_t need = (items + kKdThreads - 1u) / kKdThreads;
-    return need < maxBlocks ? (need ? need : 1u) : maxBlocks;
-}
-
-static hipError_t kd_scan(unsigned long long* item, uint32_t n, unsigned long long* chunkSums, unsigned long long* total, hipStream_t stream)
-{
-    const uint32_t chunks = (uint32_t)crt_kd_scan_chunks(n);
-    hipError_t e;
-    hipLaunchKernelGGL(kd_scan_sums_kernel, dim3(chunks), dim3(kKdThreads), 0, stream, item, n, chunkSums);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    hipLaunchKernelGGL(kd_scan_chunks_kernel, dim3(1), dim3(kKdThreads), 0, stream, chunkSums, chunks, item + n, total);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    hipLaunchKernelGGL(kd_scan_apply_kernel, dim3(chunks), dim3(kKdThreads), 0, stream, item, n, chunkSums);
-    return hipGetLastError();
-}
-
 } // namespace crt
 
 // chunk sums the scan of n items needs (64-bit words)
-extern "C" size_t crt_kd_scan_chunks(uint32_t n) { const size_t c = ((size_t)n + crt::kKdScanChunk - 1u) / crt::kKdScanChunk; return c ? c : 1u; }
+extern "C" size_t crt_kd_scan_chunks(uint32_t n) { return crt::scan_chunks(n ? n : 1u); }
 
 // bounds (state->bounds), the triangle boxes (6 floats each), level 0: the root node and the references 0 .. triCount - 1
 extern "C" hipError_t crt_launch_kd_begin(const float* pos, uint32_t triCount, crt::KdBuildState* state, float* triBox, crt::KdBuildNode* root, uint32_t* refs, uint32_t* owner,
@@ -290,23 +217,23 @@ extern "C" hipError_t crt_launch_kd_begin(const float* pos, uint32_t triCount, c
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(crt::kd_root_kernel, dim3(1), dim3(64), 0, stream, state, triCount, root);
     if ((e = hipGetLastError()) != hipSuccess) return e;
-    hipLaunchKernelGGL(crt::kd_tri_box_kernel, dim3(crt::kd_blocks_for(triCount, maxBlocks)), dim3(crt::kKdThreads), 0, stream, pos, triCount, triBox, refs, owner);
+    hipLaunchKernelGGL(crt::kd_tri_box_kernel, dim3(crt::blocks_for(triCount, maxBlocks)), dim3(crt::kKdThreads), 0, stream, pos, triCount, triBox, refs, owner);
     return hipGetLastError();
 }
 
 // One level's decisions: which nodes split and where every reference goes.  nodeItems: nodeCount + 1 words, refItems: refCount + 1 words, both come back as the
-// exclusive prefixes kd_split reads; chunkSums: crt_kd_scan_chunks(max(nodeCount, refCount)) words.  state->nodeTotal / refTotal receive the totals.
+// exclusive prefixes kd_split reads, each with its total behind it; chunkSums: crt_kd_scan_chunks(max(nodeCount, refCount)) words.  state->nodeTotal / refTotal receive the totals.
 extern "C" hipError_t crt_launch_kd_level(crt::KdBuildNode* nodes, uint32_t nodeCount, uint32_t depth, const uint32_t* owner, const uint32_t* refs, uint32_t refCount, const float* triBox,
                                           unsigned long long* nodeItems, unsigned long long* refItems, unsigned long long* chunkSums, crt::KdBuildState* state, uint32_t maxBlocks,
                                           hipStream_t stream)
 {
     hipError_t e;
-    hipLaunchKernelGGL(crt::kd_node_kernel, dim3(crt::kd_blocks_for(nodeCount, maxBlocks)), dim3(crt::kKdThreads), 0, stream, nodes, nodeCount, depth, nodeItems);
+    hipLaunchKernelGGL(crt::kd_node_kernel, dim3(crt::blocks_for(nodeCount, maxBlocks)), dim3(crt::kKdThreads), 0, stream, nodes, nodeCount, depth, nodeItems);
     if ((e = hipGetLastError()) != hipSuccess) return e;
-    if ((e = crt::kd_scan(nodeItems, nodeCount, chunkSums, &state->nodeTotal, stream)) != hipSuccess) return e;
-    hipLaunchKernelGGL(crt::kd_classify_kernel, dim3(crt::kd_blocks_for(refCount, maxBlocks)), dim3(crt::kKdThreads), 0, stream, nodes, owner, refs, triBox, refCount, refItems);
+    if ((e = crt::scan(nodeItems, nodeCount, (uint32_t)crt_kd_scan_chunks(nodeCount), chunkSums, nodeItems + nodeCount, &state->nodeTotal, stream)) != hipSuccess) return e;
+    hipLaunchKernelGGL(crt::kd_classify_kernel, dim3(crt::blocks_for(refCount, maxBlocks)), dim3(crt::kKdThreads), 0, stream, nodes, owner, refs, triBox, refCount, refItems);
     if ((e = hipGetLastError()) != hipSuccess) return e;
-    return crt::kd_scan(refItems, refCount, chunkSums, &state->refTotal, stream);
+    return crt::scan(refItems, refCount, (uint32_t)crt_kd_scan_chunks(refCount), chunkSums, refItems + refCount, &state->refTotal, stream);
 }
 
 // the next level's nodes and references from this level's prefixes
@@ -315,7 +242,7 @@ extern "C" hipError_t crt_launch_kd_split(crt::KdBuildNode* nodes, uint32_t node
                                           uint32_t maxBlocks, hipStream_t stream)
 {
     const uint32_t items = nodeCount > refCount ? nodeCount : refCount;
-    hipLaunchKernelGGL(crt::kd_split_kernel, dim3(crt::kd_blocks_for(items, maxBlocks)), dim3(crt::kKdThreads), 0, stream, nodes, nodeCount, nodeScan, owner, refs, refCount, refScan, next,
+    hipLaunchKernelGGL(crt::kd_split_kernel, dim3(crt::blocks_for(items, maxBlocks)), dim3(crt::kKdThreads), 0, stream, nodes, nodeCount, nodeScan, owner, refs, refCount, refScan, next,
                        nextNodes, nextRefs, nextOwner, nextRefCount);
     return hipGetLastError();
 }
@@ -326,13 +253,13 @@ extern "C" hipError_t crt_launch_kd_finalise(crt::KdBuildNode* const* nodes, con
 {
     hipError_t e;
     for (uint32_t d = levels - 1u; d-- > 0u;) {
-        hipLaunchKernelGGL(crt::kd_sizes_kernel, dim3(crt::kd_blocks_for(nodeCount[d], maxBlocks)), dim3(crt::kKdThreads), 0, stream, nodes[d], nodeCount[d], nodes[d + 1u], nodeCount[d + 1u]);
+        hipLaunchKernelGGL(crt::kd_sizes_kernel, dim3(crt::blocks_for(nodeCount[d], maxBlocks)), dim3(crt::kKdThreads), 0, stream, nodes[d], nodeCount[d], nodes[d + 1u], nodeCount[d + 1u]);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
     for (uint32_t d = 0; d < levels; d++) {
         const bool last = d + 1u == levels;
         const uint32_t items = nodeCount[d] > refCount[d] ? nodeCount[d] : refCount[d];
-        hipLaunchKernelGGL(crt::kd_emit_kernel, dim3(crt::kd_blocks_for(items, maxBlocks)), dim3(crt::kKdThreads), 0, stream, nodes[d], nodeCount[d], last ? nullptr : nodes[d + 1u],
+        hipLaunchKernelGGL(crt::kd_emit_kernel, dim3(crt::blocks_for(items, maxBlocks)), dim3(crt::kKdThreads), 0, stream, nodes[d], nodeCount[d], last ? nullptr : nodes[d + 1u],
                            last ? 0u : nodeCount[d + 1u], owner[d], refs[d], refCount[d], outNodes, outNodeCount, outRefs, outRefCount);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }

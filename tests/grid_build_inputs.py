@@ -46,6 +46,14 @@ def spanner():
     return np.concatenate([big, small]).astype(np.float32)
 
 
+def dense():
+    """120 000 triangles of size <= 0.01 spread over [0, 1]^3: a grid of 84^3 = 592 704 cells, more than 256 x 2048 counters, so the one-block pass of the
+    device's prefix sum over its chunk sums takes more than one chunk per thread"""
+    rng = np.random.default_rng(13)
+    base = rng.uniform(0.0, 0.99, (120000, 1, 3))
+    return (base + rng.uniform(0.0, 0.01, (120000, 3, 3))).astype(np.float32)
+
+
 def zeros(last_negative):
     """The minimum x of the mesh is 0 and the maximum z is 0; the vertices that tie there include some at -0.0 and some at +0.0 (two of them inside one triangle).
     The last tying vertex in (triangle, vertex) order is -0.0 (last_negative) or +0.0, for x and for z alike."""
@@ -80,7 +88,7 @@ def bunny_moved(crt):
     return wobble(scene_positions(crt))
 
 
-GENERATED = {"single": single, "flat": flat, "sliver": sliver, "cluster": cluster, "spanner": spanner,
+GENERATED = {"single": single, "flat": flat, "sliver": sliver, "cluster": cluster, "spanner": spanner, "dense": dense,
              "zeros-neg": lambda: zeros(True), "zeros-pos": lambda: zeros(False)}
 NAMES = list(GENERATED) + ["bunny_moved"]
 

@@ -65,6 +65,7 @@ def test_each_mesh_has_its_shape(crt, built):
     starts, ends = g["cellStart"][:-1], g["cellStart"][1:]
     assert (ends > starts).all() and (g["refs"][starts] == 0).all()          # triangle 0 lies in every cell (ascending: it comes first)
     assert int(g["resolution"].prod()) > 64                                  # ... more cells than one lane takes on its own
+    assert int(built["dense"][1]["resolution"].prod()) + 1 > 256 * 2048      # more chunk sums than the scan's one-block pass has threads
     for name, neg in (("zeros-neg", True), ("zeros-pos", False)):
         p, g, _ = built[name]
         assert p[..., 0].min() == 0 and p[..., 2].max() == 0
