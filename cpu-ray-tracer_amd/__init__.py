@@ -110,10 +110,10 @@ HIT_INFO_DTYPE = np.dtype([("I", "<f4", 3), ("material", "<i4"), ("N", "<f4", 3)
 MATERIAL_MISS, MATERIAL_INVALID = -1, -2       # crt_hit_info.material of a miss / of a record whose objIdx or triIdx the scene does not have
 
 # every symbol include/crt_abi.h and include/crt_host.h declare (tests check the library exports all of them)
-ABI_SYMBOLS = ["crt_build_kdtree_device", "crt_get_kdtree", "crt_build_grid_device", "crt_get_grid", "crt_update_transforms_device", "crt_sample", "crt_sample_device", "crt_refit_device", "crt_get_hit_info", "crt_get_hit_info_device", "crt_get_sky_color", "crt_get_sky_color_device", "crt_get_light", "crt_upload_blas_accel", "crt_is_occluded", "crt_find_nearest_device", "crt_is_occluded_device", "crt_upload_primitive_scene", "crt_set_render_accel", "crt_upload_alt_accel", "crt_find_nearest_alt", "crt_update_scene", "crt_abi_version", "crt_device_count", "crt_create", "crt_destroy", "crt_last_error", "crt_upload_scene", "crt_set_camera",
+ABI_SYMBOLS = ["crt_build_bvh_device", "crt_get_bvh", "crt_build_kdtree_device", "crt_get_kdtree", "crt_build_grid_device", "crt_get_grid", "crt_update_transforms_device", "crt_sample", "crt_sample_device", "crt_refit_device", "crt_get_hit_info", "crt_get_hit_info_device", "crt_get_sky_color", "crt_get_sky_color_device", "crt_get_light", "crt_upload_blas_accel", "crt_is_occluded", "crt_find_nearest_device", "crt_is_occluded_device", "crt_upload_primitive_scene", "crt_set_render_accel", "crt_upload_alt_accel", "crt_find_nearest_alt", "crt_update_scene", "crt_abi_version", "crt_device_count", "crt_create", "crt_destroy", "crt_last_error", "crt_upload_scene", "crt_set_camera",
                "crt_render", "crt_tick", "crt_reserve", "crt_whitted_tick", "crt_whitted_tick_inspect", "crt_sync", "crt_clear", "crt_read_accumulator", "crt_resolve_screen", "crt_find_nearest", "crt_get_counters",
                "crt_reset_counters", "crt_get_timing", "crt_get_tile_clocks", "crt_bind_accumulator", "crt_accumulator_device_ptr"]
-HOST_SYMBOLS = ["crt_host_scene_build_kdtree_device", "crt_host_kd_build", "crt_host_scene_build_grid_device", "crt_host_grid_build", "crt_host_scene_update_transforms_device", "crt_host_scene_bvh_refit_device", "crt_host_scene_blas_alt_info", "crt_host_scene_blas_alt_copy", "crt_host_primitive_scene_create", "crt_host_primitive_scene_free", "crt_host_primitive_scene_set_time", "crt_host_primitive_scene_desc", "crt_host_primitive_scene_upload", "crt_host_scene_build_alt", "crt_host_scene_upload_alt", "crt_host_scene_alt_info", "crt_host_scene_alt_copy", "crt_host_scene_set_transform", "crt_host_scene_update", "crt_host_math_probe", "crt_host_vertex_dedup", "crt_host_last_error", "crt_host_scene_load", "crt_host_scene_free", "crt_host_scene_upload", "crt_host_scene_kind",
+HOST_SYMBOLS = ["crt_host_bvh_build", "crt_host_scene_bvh_move_and_rebuild", "crt_host_scene_build_bvh_device", "crt_host_scene_build_kdtree_device", "crt_host_kd_build", "crt_host_scene_build_grid_device", "crt_host_grid_build", "crt_host_scene_update_transforms_device", "crt_host_scene_bvh_refit_device", "crt_host_scene_blas_alt_info", "crt_host_scene_blas_alt_copy", "crt_host_primitive_scene_create", "crt_host_primitive_scene_free", "crt_host_primitive_scene_set_time", "crt_host_primitive_scene_desc", "crt_host_primitive_scene_upload", "crt_host_scene_build_alt", "crt_host_scene_upload_alt", "crt_host_scene_alt_info", "crt_host_scene_alt_copy", "crt_host_scene_set_transform", "crt_host_scene_update", "crt_host_math_probe", "crt_host_vertex_dedup", "crt_host_last_error", "crt_host_scene_load", "crt_host_scene_free", "crt_host_scene_upload", "crt_host_scene_kind",
                 "crt_host_scene_triangle_count", "crt_host_scene_bvh_count", "crt_host_scene_bvh_info", "crt_host_scene_bvh_copy",
                 "crt_host_scene_bvh_move_and_refit", "crt_host_scene_blas_transform", "crt_host_scene_tlas_copy", "crt_host_camera_state", "crt_host_renderer_create",
                 "crt_host_renderer_destroy", "crt_host_renderer_init", "crt_host_renderer_set_camera", "crt_host_renderer_set_passes",
@@ -589,6 +589,29 @@ class Context:
         self._ck(self.L.crt_get_kdtree(self.h, C.c_uint32(bvh), None, None, None, _p(nodes), _p(r)))
         return dict(nodes=nodes, refs=r[:nr.value], height=int(h.value))
 
+    def build_bvh_device(self, bvh, positions, stream=None, root_box=True):
+        """crt_build_bvh_device: BVH::Build (binned SAH) of uploaded BVH `bvh` on the GPU from `positions` (refit_device's tensor), enqueued on `stream` (default
+        torch.cuda.current_stream()); returns once the new tree has been read back into the context's mirror (one host wait per level of the tree before that).  The
+        scene is then what a fresh upload of the host-rebuilt scene gives.  Returns node 0's box as refit_device does.  Two-level scenes: the TLAS is the caller's to
+        rebuild (update_transforms_device, or HostScene.build_bvh_device)."""
+        def run(st):
+            ptr, n = self._positions(positions, "build_bvh_device")
+            box = (C.c_float * 6)()
+            self._ck(self.L.crt_build_bvh_device(self.h, C.c_uint32(bvh), ptr, n, C.c_void_p(st.cuda_stream), box if root_box else None))
+            return np.array(box[:], np.float32).reshape(2, 3) if root_box else None
+        return self._enqueue(stream, run)
+
+    def get_bvh(self, bvh=0):
+        """crt_get_bvh: BVH `bvh` of the live scene in the reference's form, reconstructed from the device's geometry buffer:
+        dict(nodes (NODE_DTYPE, nodesUsed records), indices, nodesUsed, maxDepth, height)"""
+        used, depth, h = C.c_uint32(), C.c_uint32(), C.c_uint32()
+        self._ck(self.L.crt_get_bvh(self.h, C.c_uint32(bvh), C.byref(used), C.byref(depth), C.byref(h), None, None))
+        nodes = np.zeros(used.value, NODE_DTYPE)
+        self._ck(self.L.crt_get_bvh(self.h, C.c_uint32(bvh), None, None, None, _p(nodes), None))
+        idx = np.zeros(int(nodes["triCount"].sum()), np.uint32)                 # every triangle is in exactly one leaf
+        self._ck(self.L.crt_get_bvh(self.h, C.c_uint32(bvh), None, None, None, None, _p(idx)))
+        return dict(nodes=nodes, indices=idx, nodesUsed=int(used.value), maxDepth=int(depth.value), height=int(h.value))
+
     def _enqueue(self, stream, run):
         """run(st) on the torch stream `stream` (default: the current one).  Torch's default stream has the handle 0, which the ABI reads as the context's own
         stream: on it the query runs on a side stream that waits for it and that it waits for in turn (events, no host wait)."""
@@ -748,6 +771,19 @@ class HostScene:
             ptr, n = ctx._positions(positions, "build_grid_device")
             self._ck(self.L.crt_host_scene_build_grid_device(self.h, ctx.h, int(i), ptr, n, C.c_void_p(st.cuda_stream)))
         return ctx._enqueue(stream, run)
+
+    def build_bvh_device(self, ctx, i, positions, stream=None):
+        """crt_host_scene_build_bvh_device: BVH i rebuilt on the GPU from a positions tensor (Context.build_bvh_device's), this scene's triangles moved and its tree
+        rebuilt on the host alike (the two trees are identical), and a TLAS scene's TLAS rebuilt on the host and sent."""
+        def run(st):
+            ptr, n = ctx._positions(positions, "build_bvh_device")
+            self._ck(self.L.crt_host_scene_build_bvh_device(self.h, ctx.h, int(i), ptr, n, C.c_void_p(st.cuda_stream)))
+        return ctx._enqueue(stream, run)
+
+    def move_and_rebuild(self, i, positions):
+        """crt_host_scene_bvh_move_and_rebuild: new vertex positions ((n, 3, 3) float32) for BVH i, centroids recomputed, BVH::Build on the host (+ TLAS)"""
+        pos = np.ascontiguousarray(positions, np.float32).reshape(-1, 9)
+        self._ck(self.L.crt_host_scene_bvh_move_and_rebuild(self.h, int(i), _p(pos), C.c_uint32(len(pos))))
 
     def build_kdtree_device(self, ctx, i, positions, stream=None):
         """crt_host_scene_build_kdtree_device: the KD-tree of BVH i rebuilt on the GPU from a positions tensor (Context.build_kdtree_device's), then this scene's KD
@@ -1009,6 +1045,18 @@ def host_grid_build(positions):
     start = np.zeros(int(res.prod()) + 1, np.uint32); r = np.zeros(max(refs.value, 1), np.int32)
     ck(L.crt_host_grid_build(_p(pos), C.c_uint32(len(pos)), None, None, None, _p(start), _p(r)))
     return dict(resolution=res, cellSize=f[0:3].copy(), boundsMin=f[3:6].copy(), boundsMax=f[6:9].copy(), cellStart=start, refs=r[:refs.value])
+
+
+def host_bvh_build(positions):
+    """test / tool entry: the host front's BVH::Build (csrc/host/accel.cpp BuildSAH) over bare positions ((n, 3, 3) float32), in Context.get_bvh's layout"""
+    L = lib()
+    pos = np.ascontiguousarray(positions, np.float32).reshape(-1, 9)
+    info = (C.c_uint32 * 3)()
+    nodes = np.zeros(2 * len(pos) - 1, NODE_DTYPE); idx = np.zeros(len(pos), np.uint32)
+    rc = L.crt_host_bvh_build(_p(pos), C.c_uint32(len(pos)), info, _p(nodes), _p(idx))
+    if rc != 0:
+        raise RuntimeError("crt_host_bvh_build: %s" % L.crt_host_last_error().decode())
+    return dict(nodes=nodes[:info[0]].copy(), indices=idx, nodesUsed=int(info[0]), maxDepth=int(info[1]), height=int(info[2]))
 
 
 def host_kd_build(positions):

@@ -107,7 +107,7 @@ struct crt_ctx {
     // what crt_update_scene needs of the last upload: a host mirror of the geometry buffer and where each BVH's records start
     struct Flat { int32_t kind = 0; uint64_t leafOff = 0, tlasOff = 0, tlasPairOff = 0, instOff = 0, shadeOff = 0; uint32_t tlasNodeCount = 0, maxHeight = 0;
                   uint32_t objects = 0;           // objCount (FileScene) / bvhCount (two-level): the objIdx a hit record may carry is below 2 + objects
-                  std::vector<uint64_t> pairBase, triBase; std::vector<uint32_t> nodesUsed, triCount; std::vector<char> geom;
+                  std::vector<uint64_t> pairBase, triBase; std::vector<uint32_t> nodesUsed, triCount, height; std::vector<char> geom;   // height: every BVH's deepest leaf, in edges
                   std::vector<float> rootBox; } flat;     // rootBox: every BVH's node 0 box (min xyz, max xyz), what crt_upload_blas_accel checks the BLAS structures against
     char* hStage[2] = {nullptr, nullptr}; size_t stageBytes[2] = {0, 0}; hipEvent_t stageCopied[2] = {nullptr, nullptr}; int stageFlip = 0;
     hipEvent_t sceneReady = nullptr, writeFence = nullptr;   // the scene-write protocol (begin_scene_write): the last write's `done` event, the protocol's own fence
@@ -179,6 +179,16 @@ struct crt_ctx {
             (void)hipHostFree(hState); *this = KdBuild{};
         }
     } kdBuild;
+    // crt_build_bvh_device (device/bvh_build.hip): the kernels' state block and its pinned copy; the node records and box keys of all levels (at most 2n - 1 nodes),
+    // the centroids, triangleIndices and owners (double-buffered: a level's partition writes the next level's), `remain`, the triangles' objIdx, the two scan arrays,
+    // the chunk sums and one level's bins — grown on demand and kept between calls; one read-back (host wait) per level, and the read-back of the new records
+    struct BvhBuild : AccelBuild {
+        crt::BvhBuildState* dState = nullptr; crt::BvhBuildState* hState = nullptr;
+        static constexpr int kBufs = 13;      // nodes, keys, cen, idx x 2, owner x 2, remain, objOf, leftItems, nodeItems, chunks, bins
+        void* buf[kBufs] = {}; size_t cap[kBufs] = {};
+        uint32_t waits = 0, levels = 0; double waitMs = 0, readBackMs = 0;      // the last call's host waits per level, its levels, the waits' wall time, the mirror read-back's
+        void release() { releaseEvents(); for (void* p : buf) (void)hipFree(p); (void)hipFree(dState); (void)hipHostFree(hState); *this = BvhBuild{}; }
+    } bvhBuild;
     uint32_t kdNodeCount = 0, kdRefCount = 0;   // nodes / leaf references of the FileScene's live KD-tree (uploaded or built on the device)
     // The two-level KD [0] / grid [1] set as the device holds it, uploaded or rebuilt per BLAS: the descriptors; per BLAS the elements of its part of the kind's two
     // arrays (count[0]: KD nodes / cells + 1, count[1]: KD / cell references) and its height (KD only); and whether BLAS i's part is of its current vertices (an
@@ -449,6 +459,7 @@ void crt_destroy(crt_ctx* c)
     c->freeScene();
     c->gridBuild.release();
     c->kdBuild.release();
+    c->bvhBuild.release();
     for (hipEvent_t e : c->retiredEvents) (void)hipEventDestroy(e);
     for (auto& a : c->ahead) (void)hipEventDestroy(a.end);
     if (c->aheadStream) (void)hipStreamDestroy(c->aheadStream);
@@ -519,7 +530,7 @@ int crt_upload_scene(crt_ctx* c, const crt_scene_desc* sd)
 
     // ---- sizes of the sections of the geometry buffer: pairs | leaf tris (+1 pad record) | TLAS nodes | instances | shade records ----
     uint64_t nPairs = 0, nTris = 0;
-    uint32_t maxHeight = 0;
+    uint32_t maxHeight = 0; std::vector<uint32_t> heights;
     for (uint32_t bi = 0; bi < sd->bvhCount; bi++) {
         const crt_bvh& b = sd->bvhs[bi];
         if (!b.nodes || !b.triangles || !b.triangleIndices || b.nodesUsed == 0 || b.triCount == 0) return c->fail(CRT_ERR_INVALID, "BVH %u is empty", bi);
@@ -529,6 +540,7 @@ int crt_upload_scene(crt_ctx* c, const crt_scene_desc* sd)
             return c->fail(CRT_ERR_INVALID, "BLAS %u: objIdx must be %u (TLASFileScene numbers objects from 2, tlas_file_scene.cpp:13,51-53)", bi, bi + 2);
         uint32_t h = 0; int r = bvh_height(c, b, &h); if (r) return r;
         if (h > maxHeight) maxHeight = h;
+        heights.push_back(h);
         nPairs += b.nodesUsed / 2; nTris += b.triCount;
     }
     const uint64_t pairBytes = nPairs ? nPairs * 64 : 64;                   // offset 0 must never be a leaf record (ref 0 = "done")
@@ -765,7 +777,7 @@ int crt_upload_scene(crt_ctx* c, const crt_scene_desc* sd)
         for (uint32_t bi = 0; bi < sd->bvhCount; bi++) { const crt_bvh_node& r = sd->bvhs[bi].nodes[0]; f.rootBox.insert(f.rootBox.end(), r.aabbMin, r.aabbMin + 3); f.rootBox.insert(f.rootBox.end(), r.aabbMax, r.aabbMax + 3); }
         uint64_t pb = 0, tb = 0;
         for (uint32_t bi = 0; bi < sd->bvhCount; bi++) { f.pairBase.push_back(pb); f.triBase.push_back(tb); f.nodesUsed.push_back(sd->bvhs[bi].nodesUsed); f.triCount.push_back(sd->bvhs[bi].triCount); pb += sd->bvhs[bi].nodesUsed / 2; tb += sd->bvhs[bi].triCount; }
-        f.geom.swap(geom);
+        f.geom.swap(geom); f.height.swap(heights);
     }
     c->haveScene = true;
     return CRT_OK;
@@ -2812,6 +2824,20 @@ static int grow_scratch(crt_ctx* c, const crt_ctx::AccelBuild& B, void** p, size
     return 0;
 }
 
+// What a replaced buffer set's retirement takes, once `done` is recorded on `st` behind the build: the replaced buffers are still read by launches enqueued earlier, on
+// any stream, and by the build's own copies.  The main stream goes behind all those readers and behind the build (`done` published: launches enqueued from now on
+// wait for it), and old.unread, recorded on it then, says when the old buffers are unread.  The caller fills old.ptrs and pushes `old` onto c->retired.
+static int retire_behind_readers(crt_ctx* c, hipStream_t st, hipEvent_t done, crt_ctx::Retired& old)
+{
+    if (c->retiredEvents.empty()) { hipEvent_t e = nullptr; HIPCK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming)); c->retiredEvents.push_back(e); }
+    old.unread = c->retiredEvents.back(); c->retiredEvents.pop_back();
+    int r;
+    if ((r = order_behind_readers(c)) || (r = publish_scene_write(c, st, done)) || (r = c->hip(hipEventRecord(old.unread, c->stream), "hipEventRecord(retired)"))) {
+        c->retiredEvents.push_back(old.unread); old.unread = nullptr;
+    }
+    return r;
+}
+
 // One replacement, slot 0: the KD-tree, 1: the grid (as blasAlt / haveBlas / blasAllocs).  The kind's arrays are numbered 0: KD nodes / cellStart, 1: KD references /
 // cellRefs, 2: the AltTri records.  A FileScene's structure is the arrays alone; a two-level scene's is BLAS `bvh`'s part of the set's concatenated arrays, and the
 // other BLASes' parts are carried over.  The entry calls begin, prepare, its kernels up to the sizes it reads back, place + alloc per array, carry, the kernels that
@@ -2897,15 +2923,8 @@ struct AccelReplace {
         if (g_hooks) { REPLCK(*this, hipEventRecord(B.t1, st)); B.timed = true; }
         REPLCK(*this, hipEventRecord(B.done, st));
         B.built = true;
-        // What it replaces is still read by launches enqueued earlier, on any stream, and by this build's own copies (the other BLASes' parts, the pinned descriptors).
-        // The main stream behind all those readers and behind the build (`done` published), and an event on it then says when the old buffers are unread.
-        crt_ctx::Retired old;
-        if (c->retiredEvents.empty()) { hipEvent_t e = nullptr; REPLCK(*this, hipEventCreateWithFlags(&e, hipEventDisableTiming)); c->retiredEvents.push_back(e); }
-        old.unread = c->retiredEvents.back(); c->retiredEvents.pop_back();
-        int r;
-        if ((r = order_behind_readers(c)) || (r = publish_scene_write(c, st, B.done)) || (r = c->hip(hipEventRecord(old.unread, c->stream), "hipEventRecord(retired)"))) {
-            c->retiredEvents.push_back(old.unread); return drop(r);
-        }
+        crt_ctx::Retired old;                                              // (what it replaces is also read by this build's own copies: the other BLASes' parts, the pinned descriptors)
+        if (const int r = retire_behind_readers(c, st, B.done, old)) return drop(r);
         old.pinned = pinned;
         if (tlas) {
             crt_ctx::BlasSet& S = set();
@@ -3148,6 +3167,234 @@ extern "C" int crt_debug_kdtree_build_ms(crt_ctx* c, float* streamMs, double* wa
     HIPCK(c, hipEventSynchronize(K.t1));
     HIPCK(c, hipEventElapsedTime(streamMs, K.t0, K.t1));
     *waitMs = K.waitMs; *waits = K.waits; *levels = K.levels;
+    return CRT_OK;
+}
+
+// ---- crt_build_bvh_device: BVH::Build / BLASBVH::Build of one BVH on the device, from positions in device memory (device/bvh_build.hip).  The tree's size changes, so
+// the pair section does, and every section behind it moves: the result is a FRESH geometry buffer — the rebuilt BVH's pairs and leaf triangles written by the kernels,
+// the other BVHs' pairs re-based, everything else copied device to device — which replaces the live one as crt_build_grid_device replaces a grid ----
+int crt_build_bvh_device(crt_ctx* c, uint32_t bvh, const float* d_positions, uint32_t triCount, void* stream, float rootBox[6])
+{
+    const char* const me = "crt_build_bvh_device";
+    if (!c) return CRT_ERR_INVALID;
+    int r;
+    if ((r = check_bvh_arg(c, me, "BVH to rebuild", bvh, triCount, " (a rebuild keeps the triangles)"))) return r;
+    crt_ctx::Flat& f = c->flat; crt_ctx::BvhBuild& B = c->bvhBuild;
+    const uint32_t n = triCount, N = (uint32_t)f.triCount.size();
+    if (n == 0 || n > 0x7fffffffu / 3u) return c->fail(CRT_ERR_UNSUPPORTED, "%s: 1 .. (2^31-1)/3 triangles", me);
+    hipStream_t st = nullptr;
+    if ((r = device_entry(c, me, {{d_positions, (size_t)n * 36u}}, stream, &st))) return r;
+    c->freeRetired(false);
+    if (!B.dState) HIPCK(c, hipMalloc((void**)&B.dState, sizeof(crt::BvhBuildState)));
+    if (!B.hState) HIPCK(c, hipHostMalloc((void**)&B.hState, sizeof(crt::BvhBuildState), hipHostMallocDefault));
+    enum { kNodes, kKeys, kCen, kIdx0, kIdx1, kOwner0, kOwner1, kRemain, kObj, kLeft, kSplit, kChunks, kBins };
+    const size_t need[crt_ctx::BvhBuild::kBufs - 1] = {2u * (size_t)n * sizeof(crt::BvhBuildNode), 2u * (size_t)n * 48u, (size_t)n * 12u, (size_t)n * 4u, (size_t)n * 4u, (size_t)n * 4u,
+                                                       (size_t)n * 4u, (size_t)n * 4u, (size_t)n * 4u, ((size_t)n + 1u) * 4u, ((size_t)n + 1u) * 4u, crt::scan_chunks((size_t)n + 1u) * 8u};
+    for (int k = 0; k < crt_ctx::BvhBuild::kBufs - 1; k++) if ((r = grow_scratch(c, B, &B.buf[k], &B.cap[k], need[k]))) return r;
+    crt::BvhBuildNode* nodes = (crt::BvhBuildNode*)B.buf[kNodes]; unsigned long long* keys = (unsigned long long*)B.buf[kKeys];
+    uint32_t* idx[2] = {(uint32_t*)B.buf[kIdx0], (uint32_t*)B.buf[kIdx1]}; uint32_t* owner[2] = {(uint32_t*)B.buf[kOwner0], (uint32_t*)B.buf[kOwner1]};
+    // Fresh buffer, so the build is a reader (as AccelReplace::prepare): it reads the caller's positions and the LeafTri id words and waits for the last scene write
+    // and for the previous build, whose scratch it reuses
+    if (!B.blocks && !(B.blocks = crt_grid_build_blocks(c->cfg.device))) return c->fail(CRT_ERR_DEVICE, "%s: the device's compute units / occupancy could not be asked", me);
+    for (hipEvent_t* e : {&B.back, &B.done}) HIPCK(c, ensure_event(e));
+    if (g_hooks) for (hipEvent_t* e : {&B.t0, &B.t1}) HIPCK(c, ensure_event(e, hipEventDefault));
+    if ((r = wait_scene(c, st))) return r;
+    if (B.built) HIPCK(c, hipStreamWaitEvent(st, B.done, 0));
+    if (g_hooks) HIPCK(c, hipEventRecord(B.t0, st));
+    B.waits = 0; B.levels = 0; B.waitMs = 0; B.readBackMs = 0;
+    HIPCK(c, crt_launch_bvh_begin(d_positions, n, c->hScene.geom, (uint32_t)f.leafOff, (uint32_t)f.triBase[bvh], (float*)B.buf[kCen], idx[0], owner[0], (int32_t*)B.buf[kObj], nodes, keys,
+                                  B.dState, B.blocks, st));
+    // ---- level by level; ONE HOST WAIT PER LEVEL: the number of nodes that split sizes the next level.  The bound of the loop is the traversal stack: a level d
+    // with nodes means a leaf at depth >= d, and crt_upload_scene refuses a tree whose stack does not fit the LDS ----
+    const uint32_t tlasPart = c->hScene.stackDepth - c->hScene.bvhStack;          // TLAS pushes + the return marker (0 for a FileScene)
+    uint32_t otherHeight = 0;
+    for (uint32_t b = 0; b < N; b++) if (b != bvh && f.height[b] > otherHeight) otherHeight = f.height[b];
+    auto stack_of = [&](uint32_t h) { const uint32_t m = h > otherHeight ? h : otherHeight; return (m ? m : 1u) + tlasPart; };
+    auto lds_fits = [&](uint32_t h) { return (uint64_t)stack_of(h) * 256u + c->extraLds + 15u * 256u <= 64u * 1024u; };
+    std::vector<uint32_t> levelOff{0u, 1u};
+    uint32_t cur = 0, levels = 0;
+    for (uint32_t d = 0;; d++) {
+        const uint32_t m = levelOff[d + 1u] - levelOff[d];
+        if ((r = grow_scratch(c, B, &B.buf[kBins], &B.cap[kBins], (size_t)m * crt::kBvhNodeBinWords * 4u))) return r;
+        HIPCK(c, crt_launch_bvh_level(d_positions, (const float*)B.buf[kCen], idx[cur], owner[cur], n, nodes + levelOff[d], keys + 6u * (size_t)levelOff[d], m, (uint32_t*)B.buf[kBins],
+                                      (uint32_t*)B.buf[kLeft], (uint32_t*)B.buf[kSplit], (unsigned long long*)B.buf[kChunks], B.dState, d == 0u, B.blocks, st));
+        double ms = 0;
+        if ((r = read_back(c, st, B.back, B.hState, B.dState, sizeof(crt::BvhBuildState), &ms))) return r;
+        B.waits++; B.waitMs += ms; levels = d + 1u;
+        if (d == 0u && B.hState->nonFinite) return c->fail(CRT_ERR_INVALID, "%s: a position component is not finite", me);
+        const uint64_t splits = B.hState->splits;
+        if (splits > m || (uint64_t)levelOff[d + 1u] + 2u * splits > 2u * (uint64_t)n - 1u)
+            return c->fail(CRT_ERR_DEVICE, "%s: the level kernels reported %llu split nodes of %u at depth %u", me, (unsigned long long)splits, m, d);
+        if (splits && !lds_fits(d + 1u))
+            return c->fail(CRT_ERR_UNSUPPORTED, "%s: the tree is taller than %u, its traversal stack (+TLAS %u) exceeds the 64 KiB of LDS per wave", me, d, tlasPart);
+        const uint32_t nextM = (uint32_t)(2u * splits);
+        HIPCK(c, crt_launch_bvh_split(nodes + levelOff[d], m, (const uint32_t*)B.buf[kSplit], owner[cur], idx[cur], (const uint32_t*)B.buf[kLeft], n, nodes + levelOff[d + 1u],
+                                      keys + 6u * (size_t)levelOff[d + 1u], nextM, idx[cur ^ 1u], owner[cur ^ 1u], (uint32_t*)B.buf[kRemain], B.blocks, st));
+        cur ^= 1u;
+        if (!splits) break;
+        levelOff.push_back(levelOff[d + 1u] + nextM);
+    }
+    B.levels = levels;
+    const uint32_t height = levels - 1u, nodesUsed = levelOff.back(), np = nodesUsed / 2u, oldNp = f.nodesUsed[bvh] / 2u;
+    // ---- the new buffer's sections, as crt_upload_scene lays them out ----
+    uint64_t oldPairs = 0; for (uint32_t b = 0; b < N; b++) oldPairs += f.nodesUsed[b] / 2u;
+    const uint64_t nPairs = oldPairs - oldNp + np, nTris = f.triBase[N - 1u] + f.triCount[N - 1u];
+    const bool tlas = f.kind == CRT_SCENE_TLAS;
+    const uint64_t leafOffB = nPairs ? nPairs * 64 : 64, tlasOffB = (leafOffB + (nTris + 1) * 48 + 63) & ~63ull, tlasBytes = tlas ? (uint64_t)f.tlasNodeCount * 32 : 0;
+    const uint64_t tlasPairOffB = (tlasOffB + tlasBytes + 63) & ~63ull, instOffB = (tlasPairOffB + tlasBytes + 127) & ~127ull, instBytes = tlas ? (uint64_t)N * 128 : 0;
+    const uint64_t shadeOffB = (instOffB + instBytes + 63) & ~63ull, total = shadeOffB + nTris * 64;
+    if (total >= crt::kMaxGeomBytes) return c->fail(CRT_ERR_UNSUPPORTED, "%s: scene geometry needs %llu bytes; this build addresses 4 GiB", me, (unsigned long long)total);
+    const uint32_t bits = c->hScene.poolRefBits;                           // pairs <= triangles - 1: the triangle count decided the width at upload, a rebuild cannot change it
+    if ((bits == 16u && nPairs > crt::kRef16MaxIndex) || (bits == 32u && nPairs > crt::kRefWideMaxIndex)) return c->fail(CRT_ERR_DEVICE, "%s: %llu node pairs do not fit the scene's %u-bit pool references", me, (unsigned long long)nPairs, bits);
+    const crt::PoolRefForm PR = crt::pool_ref_form(bits);
+    char* fresh = nullptr;
+    { const hipError_t e = hipMalloc((void**)&fresh, (size_t)total); if (e != hipSuccess) { (void)hipGetLastError(); return c->fail(CRT_ERR_DEVICE, "%s: hipMalloc(%llu): %s", me, (unsigned long long)total, hipGetErrorString(e)); } }
+    std::vector<char> mirror;
+    auto undo = [&](int rc) { (void)hipStreamSynchronize(st); (void)hipFree(fresh); return rc; };
+#define BVHCK(call) do { const hipError_t e_ = (call); if (e_ != hipSuccess) return undo(c->hip(e_, #call)); } while (0)
+    const char* old = c->hScene.geom;
+    const uint64_t pb = f.pairBase[bvh], tb = f.triBase[bvh];
+    BVHCK(hipMemsetAsync(fresh, 0, (size_t)shadeOffB, st));                 // the padding between the sections, and the 64 bytes of a scene without pairs
+    const crt::BvhFlatten F{(uint32_t)pb, np, (uint32_t)tb, (uint32_t)leafOffB, PR.interior, PR.indexMask};
+    BVHCK(crt_launch_bvh_flatten(nodes, levelOff.data(), levels, d_positions, idx[cur], (const uint32_t*)B.buf[kRemain], (const int32_t*)B.buf[kObj], n, &F, fresh, B.blocks, st));
+    auto copy = [&](uint64_t to, uint64_t from, uint64_t bytes) { return bytes ? hipMemcpyAsync(fresh + to, old + from, (size_t)bytes, hipMemcpyDeviceToDevice, st) : hipSuccess; };
+    BVHCK(copy(leafOffB, f.leafOff, tb * 48));                             // the other BVHs' leaf triangles and the pad record
+    BVHCK(copy(leafOffB + (tb + n) * 48, f.leafOff + (tb + n) * 48, (nTris + 1 - tb - n) * 48));
+    BVHCK(copy(tlasOffB, f.tlasOff, tlasBytes)); BVHCK(copy(tlasPairOffB, f.tlasPairOff, tlasBytes)); BVHCK(copy(instOffB, f.instOff, instBytes)); BVHCK(copy(shadeOffB, f.shadeOff, nTris * 64));
+    const crt::BvhRelocate RL{(uint32_t)oldPairs, (uint32_t)pb, oldNp, (int32_t)np - (int32_t)oldNp, (int32_t)(((int64_t)leafOffB - (int64_t)f.leafOff) / 16), PR.interior, PR.indexMask};
+    const bool rootSplits = levels > 1u;
+    const uint32_t newRoot = rootSplits ? (crt::kRefInterior | (uint32_t)((pb * 64) >> 4)) : (uint32_t)((leafOffB + tb * 48) >> 4);
+    const uint32_t newRoot16 = rootSplits ? (PR.interior | ((uint32_t)pb & PR.indexMask)) : ((uint32_t)(tb + 1) & PR.indexMask);
+    BVHCK(crt_launch_bvh_relocate(old, fresh, &RL, (uint32_t)instOffB, tlas ? N : 0u, bvh, newRoot, newRoot16, B.blocks, st));
+    if (g_hooks) { BVHCK(hipEventRecord(B.t1, st)); B.timed = true; }
+    // ---- the host mirror of everything in front of the shade records, read back from the new buffer (the last host wait; the shade records are the old mirror's) ----
+    mirror.resize((size_t)total);
+    {
+        const auto t0 = std::chrono::steady_clock::now();                  // (the whole copy: into pageable memory the call itself blocks, not the wait behind it)
+        if ((r = read_back(c, st, B.back, mirror.data(), fresh, (size_t)shadeOffB))) return undo(r);
+        B.readBackMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    }
+    memcpy(mirror.data() + shadeOffB, f.geom.data() + f.shadeOff, (size_t)(nTris * 64));
+    const float* box = B.hState->rootBox;
+    // ---- commit.  Node 0's box on the device is rewritten in place (crt_update_transforms_device reads it), so that copy is a write of the protocol; the buffer is
+    // replaced: launches enqueued earlier keep the old one, which is retired behind them ----
+    if (c->dRootBox) {
+        if ((r = begin_scene_write(c, st))) return undo(r);
+        BVHCK(hipMemcpyAsync(c->dRootBox + 6 * (size_t)bvh, B.dState->rootBox, 24, hipMemcpyDeviceToDevice, st));
+    }
+    BVHCK(hipEventRecord(B.done, st));
+    B.built = true;
+    crt_ctx::Retired gone;
+    if ((r = retire_behind_readers(c, st, B.done, gone))) return undo(r);
+#undef BVHCK
+    gone.ptrs.push_back(const_cast<char*>(old));
+    for (void*& p : c->sceneAllocs) if (p == (void*)old) p = fresh;
+    if (bvh < c->refitPlans.size() && c->refitPlans[bvh].built) {          // the plan of the old topology goes with the old buffer (a refit enqueued earlier may still read it)
+        for (void* p : {c->refitPlans[bvh].dPlan, (void*)c->refitPlans[bvh].dLevelOff})
+            if (p) { gone.ptrs.push_back(p); c->refitAllocs.erase(std::remove(c->refitAllocs.begin(), c->refitAllocs.end(), p), c->refitAllocs.end()); }
+        c->refitPlans[bvh] = crt_ctx::RefitPlan{};
+    }
+    c->retired.push_back(std::move(gone));
+    f.geom.swap(mirror);
+    f.leafOff = leafOffB; f.tlasOff = tlasOffB; f.tlasPairOff = tlasPairOffB; f.instOff = instOffB; f.shadeOff = shadeOffB;
+    f.nodesUsed[bvh] = nodesUsed; f.height[bvh] = height;
+    { uint64_t p = 0; for (uint32_t b = 0; b < N; b++) { f.pairBase[b] = p; p += f.nodesUsed[b] / 2u; } }
+    f.maxHeight = height > otherHeight ? height : otherHeight;
+    memcpy(&f.rootBox[6 * (size_t)bvh], box, 24);
+    crt::Scene& s = c->hScene;
+    s.geom = fresh; s.leafOff = (uint32_t)leafOffB; s.tlasOff = (uint32_t)tlasOffB; s.tlasPairOff = (uint32_t)tlasPairOffB; s.instOff = (uint32_t)instOffB; s.shadeOff = (uint32_t)shadeOffB;
+    s.bvhStack = f.maxHeight ? f.maxHeight : 1u; s.stackDepth = s.bvhStack + tlasPart;
+    c->ldsBytes = s.stackDepth * 64u * 4u + c->extraLds; c->latSlots = 0;
+    if (tlas) { float lo[3], hi[3]; memcpy(lo, c->meshLo, 12); memcpy(hi, c->meshHi, 12); set_root(c, CRT_SCENE_TLAS, lo, hi); }   // (the TLAS is the caller's next step, as after BLASBVH::Build)
+    else { s.rootRef = newRoot; s.rootRef16 = newRoot16; set_root(c, CRT_SCENE_FILE, box, box + 3); }
+    for (crt_ctx::BlasSet& b : c->blasSet) b.stale(bvh);                   // as crt_refit_device: the KD-tree / grid of this BLAS are of the old vertices
+    drop_blas_sets(c);
+    if (rootBox) memcpy(rootBox, box, 24);
+    return CRT_OK;
+}
+
+// one BVH in the reference's form again, from the live geometry buffer: node 0 from its kept box and the root reference; nodes 2k + 1 and 2k + 2 are pair k's
+// children; a leaf slot's triangle is shadeIdx - shadeBase
+int crt_get_bvh(crt_ctx* c, uint32_t bvh, uint32_t* nodesUsed, uint32_t* maxDepth, uint32_t* height, crt_bvh_node* nodes, uint32_t* triangleIndices)
+{
+    const char* const me = "crt_get_bvh";
+    if (!c) return CRT_ERR_INVALID;
+    if (c->havePrim) return c->fail(CRT_ERR_UNSUPPORTED, "%s: the PrimitiveScene has no BVH", me);
+    if (!c->haveScene) return c->fail(CRT_ERR_STATE, "%s before crt_upload_scene", me);
+    const crt_ctx::Flat& f = c->flat;
+    if (bvh >= f.triCount.size()) return c->fail(CRT_ERR_INVALID, "%s: BVH %u of a scene with %zu", me, bvh, f.triCount.size());
+    const uint32_t used = f.nodesUsed[bvh], np = used / 2u, nt = f.triCount[bvh], h = f.height[bvh];
+    if (nodesUsed) *nodesUsed = used;
+    if (height) *height = h;
+    if (maxDepth) *maxDepth = h ? h - 1u : 0u;                             // the deepest node that split is the deepest leaf's parent
+    if (!nodes && !triangleIndices) return CRT_OK;
+    HIPCK(c, hipSetDevice(c->cfg.device));
+    if (c->sceneReady) HIPCK(c, hipEventSynchronize(c->sceneReady));       // a refit, rebuild or update still running
+    std::vector<crt::NodePair> pairs(np); std::vector<crt::LeafTri> leaf(nt);
+    if (np) HIPCK(c, hipMemcpy(pairs.data(), c->hScene.geom + f.pairBase[bvh] * 64, (size_t)np * 64u, hipMemcpyDeviceToHost));
+    HIPCK(c, hipMemcpy(leaf.data(), c->hScene.geom + f.leafOff + f.triBase[bvh] * 48, (size_t)nt * 48u, hipMemcpyDeviceToHost));
+    if (triangleIndices) for (uint32_t j = 0; j < nt; j++) triangleIndices[j] = leaf[j].shadeIdx - (uint32_t)f.triBase[bvh];
+    if (!nodes) return CRT_OK;
+    bool bad = false;
+    auto fill = [&](crt_bvh_node& o, const float* lo, const float* hi, uint32_t ref) {
+        memcpy(o.aabbMin, lo, 12); memcpy(o.aabbMax, hi, 12);
+        const uint64_t off = (uint64_t)(ref & crt::kRefOffsetMask) << 4;
+        if (ref & crt::kRefInterior) { const uint64_t k = off / 64u - f.pairBase[bvh]; if (k >= np) bad = true; o.leftFirst = (uint32_t)(2u * k + 1u); o.triCount = 0u; }
+        else { const uint64_t j = (off - f.leafOff) / 48u - f.triBase[bvh]; if (j >= nt) { bad = true; return; } o.leftFirst = (uint32_t)j; o.triCount = leaf[j].remain; }
+    };
+    const uint32_t rootRef = f.kind == CRT_SCENE_TLAS ? reinterpret_cast<const crt::Instance*>(f.geom.data() + f.instOff)[bvh].rootRef : c->hScene.rootRef;
+    fill(nodes[0], &f.rootBox[6 * (size_t)bvh], &f.rootBox[6 * (size_t)bvh + 3], rootRef);
+    for (uint32_t k = 0; k < np; k++) for (int i = 0; i < 2; i++) fill(nodes[2u * k + 1u + i], pairs[k].c[i].lo, pairs[k].c[i].hi, pairs[k].c[i].ref);
+    if (bad) return c->fail(CRT_ERR_DEVICE, "%s: the references of BVH %u do not form its tree", me, bvh);
+    return CRT_OK;
+}
+
+// tests: the closed form of the partition loop as bvh_scatter_kernel applies it (bvh_partition_dest, build_common.h: the same lines, compiled for the host) over one
+// segment of n slots; left[p] != 0: slot p's element goes left.  out[dest] = p; returns leftCount, or -1 where two slots map to one place or a place lies outside
+extern "C" int crt_debug_bvh_partition(const uint8_t* left, uint32_t n, uint32_t* out)
+{
+    if (!left || !out || n == 0 || n > (1u << 20)) return -1;
+    std::vector<uint32_t> S((size_t)n + 1u, 0u);
+    for (uint32_t p = 0; p < n; p++) { S[p + 1u] = S[p] + (left[p] ? 1u : 0u); out[p] = 0xffffffffu; }
+    for (uint32_t p = 0; p < n; p++) {
+        const uint32_t d = crt::bvh_partition_dest(S.data(), 0u, n, S[n], p);
+        if (d >= n || out[d] != 0xffffffffu) return -1;
+        out[d] = p;
+    }
+    return (int)S[n];
+}
+
+// tests: the live geometry buffer (every section: pairs, leaf triangles, TLAS nodes and pairs, instances, shade records) and the words of the Scene block that
+// describe it — what a device rebuild must leave exactly as a fresh upload does.  words[24]: leafOff, tlasOff, tlasPairOff, instOff, shadeOff, rootRef, rootRef16,
+// rootIsPair, stackDepth, bvhStack, poolRefBits, ldsBytes, then the 12 box floats of rootPair (lo / hi of both children) as bits.  dst == NULL: *bytes alone.
+extern "C" int crt_debug_geometry(crt_ctx* c, uint32_t words[24], unsigned long long* bytes, void* dst)
+{
+    if (!c || !bytes) return CRT_ERR_INVALID;
+    if (!c->haveScene) return c->fail(CRT_ERR_STATE, "crt_debug_geometry before crt_upload_scene");
+    const crt::Scene& s = c->hScene;
+    *bytes = c->flat.geom.size();
+    if (words) {
+        const uint32_t w[12] = {s.leafOff, s.tlasOff, s.tlasPairOff, s.instOff, s.shadeOff, s.rootRef, s.rootRef16, s.rootIsPair, s.stackDepth, s.bvhStack, s.poolRefBits, c->ldsBytes};
+        memcpy(words, w, sizeof(w));
+        for (int k = 0; k < 2; k++) { memcpy(words + 12 + 6 * k, s.rootPair + 8 * k, 12); memcpy(words + 15 + 6 * k, s.rootPair + 8 * k + 4, 12); }
+    }
+    if (!dst) return CRT_OK;
+    HIPCK(c, hipSetDevice(c->cfg.device));
+    if (c->sceneReady) HIPCK(c, hipEventSynchronize(c->sceneReady));
+    HIPCK(c, hipMemcpy(dst, s.geom, c->flat.geom.size(), hipMemcpyDeviceToHost));
+    return CRT_OK;
+}
+
+// tools/bvh_device_cost.py: the last crt_build_bvh_device's duration on its stream (HIP events, first launch to the last kernel; it includes the host round trips in
+// between), the number of its per-level host waits and their wall time together, its levels, and the wall time of the mirror's read-back (debug hooks only)
+extern "C" int crt_debug_bvh_build_ms(crt_ctx* c, float* streamMs, double* waitMs, uint32_t* waits, uint32_t* levels, double* readBackMs)
+{
+    if (!c || !streamMs || !waitMs || !waits || !levels || !readBackMs) return CRT_ERR_INVALID;
+    const crt_ctx::BvhBuild& B = c->bvhBuild;
+    if (!B.timed) return c->fail(CRT_ERR_STATE, "crt_debug_bvh_build_ms: no timed crt_build_bvh_device (debug hooks off?)");
+    HIPCK(c, hipEventSynchronize(B.t1));
+    HIPCK(c, hipEventElapsedTime(streamMs, B.t0, B.t1));
+    *waitMs = B.waitMs; *waits = B.waits; *levels = B.levels; *readBackMs = B.readBackMs;
     return CRT_OK;
 }
 

@@ -1,4 +1,4 @@
-// build_common.h — what the device builds of the uniform grid (grid_build.hip) and the KD-tree (kd_build.hip) share.  The first part is host-includable (abi.cpp
+// build_common.h — what the device builds of the uniform grid (grid_build.hip), the KD-tree (kd_build.hip) and the BVH (bvh_build.hip) share.  The first part is host-includable (abi.cpp
 // turns the grid's bound keys back into floats with the function the KD-tree's root kernel uses); the kernels below it exist for the .hip files only, and each
 // of them instantiates its own copy for its item type, so no relocatable device code is needed.
 #pragma once
@@ -23,6 +23,33 @@ constexpr uint32_t kScanItems = 8u, kScanChunk = kBuildThreads * kScanItems;    
 // chunk sums the scan of n items needs (64-bit words)
 inline size_t scan_chunks(size_t n) { return (n + kScanChunk - 1u) / kScanChunk; }
 
+// The partition loop `while (i <= j) if (left(idx[i])) i++; else swap(idx[i], idx[j--]);` over a segment of `count` slots, as a map from a slot to where its
+// element ends (tests/test_bvh_device_cpu.py holds these lines to the loop through crt_debug_bvh_partition).  S = leftScan, f = the segment's first slot, nLeft = its left elements.
+//   a left element below nLeft stays;  the left element with k lefts behind it in [nLeft, count) takes the place of the k-th right element of [0, nLeft);
+//   right element number k of [0, nLeft) goes to count - 1 (k = 0) or just below the (k-1)-th left element from the back;
+//   the right element at nLeft goes just below the last paired left element (or to count - 1 when there is no pair);  a right element above nLeft moves down one.
+CRT_HOST_DEVICE inline uint32_t bvh_select_left(const uint32_t* S, uint32_t f, uint32_t count, uint32_t rank)      // the slot of left element `rank` (ascending, from 0)
+{
+    uint32_t lo = f, hi = f + count - 1u;
+    while (lo < hi) { const uint32_t mid = lo + ((hi - lo) >> 1); if (S[mid + 1u] - S[f] >= rank + 1u) hi = mid; else lo = mid + 1u; }
+    return lo;
+}
+CRT_HOST_DEVICE inline uint32_t bvh_select_right(const uint32_t* S, uint32_t f, uint32_t count, uint32_t rank)
+{
+    uint32_t lo = f, hi = f + count - 1u;
+    while (lo < hi) { const uint32_t mid = lo + ((hi - lo) >> 1); if ((mid + 1u - f) - (S[mid + 1u] - S[f]) >= rank + 1u) hi = mid; else lo = mid + 1u; }
+    return lo;
+}
+CRT_HOST_DEVICE inline uint32_t bvh_partition_dest(const uint32_t* S, uint32_t f, uint32_t count, uint32_t nLeft, uint32_t p)
+{
+    const uint32_t q = p - f, lb = S[p] - S[f];
+    if (S[p + 1u] != S[p]) return q < nLeft ? p : bvh_select_right(S, f, count, nLeft - 1u - lb);
+    if (q > nLeft) return p - 1u;
+    if (q < nLeft) { const uint32_t k = q - lb; return k == 0u ? f + count - 1u : bvh_select_left(S, f, count, nLeft - k) - 1u; }
+    const uint32_t pairs = nLeft - (S[f + nLeft] - S[f]);
+    return pairs == 0u ? f + count - 1u : bvh_select_left(S, f, count, nLeft - pairs) - 1u;
+}
+
 } // namespace crt
 
 #if defined(__HIPCC__)
@@ -32,6 +59,21 @@ namespace crt {
 
 __device__ __forceinline__ float lesser(float a, float b) { return a < b ? a : b; }     // tmplmath.h:122 / _mm_min_ps operand order
 __device__ __forceinline__ float greater(float a, float b) { return a > b ? a : b; }
+
+// static_cast<int>(float) as the host builds' x86 code performs it (cvttss2si): the "integer indefinite" value for NaN and for every value outside int's range
+__device__ __forceinline__ int x86_int(float q) { return (q >= -2147483648.0f && q < 2147483648.0f) ? (int)q : (int)0x80000000; }
+
+// The keys of one finite component at position `at` (< 2^31) of a fold `acc = lesser(acc, v)` / `acc = greater(acc, v)`, which keeps the LATER operand on a tie: the
+// value as an ordered integer with -0 and +0 on one key, the position (complemented for the minimum, so that the last tying component wins both), the sign the
+// winner had in the low bit.  Integer min of *kmin and max of *kmax are then the fold in any order; bound_of_key turns either back into the float.
+__device__ __forceinline__ void bound_keys(float v, uint32_t at, unsigned long long* kmin, unsigned long long* kmax)
+{
+    uint32_t b = __float_as_uint(v);
+    const uint32_t sign = b >> 31;
+    if ((b << 1) == 0u) b = 0u;
+    const unsigned long long ord = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+    *kmin = (ord << 32) | ((unsigned long long)(0x7fffffffu - at) << 1) | sign; *kmax = (ord << 32) | ((unsigned long long)at << 1) | sign;
+}
 
 static uint32_t blocks_for(uint32_t items, uint32_t maxBlocks)
 {

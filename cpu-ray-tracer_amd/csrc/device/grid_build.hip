@@ -30,9 +30,6 @@ constexpr uint32_t kGridThreads = kBuildThreads;
 constexpr uint32_t kWaveCells = 64u;                                              // a triangle over more cells than this is spread over the wavefront
 constexpr uint32_t kLaneCellRefs = 32u;                                           // a cell with more references than this is sorted by the wavefront
 
-// static_cast<int>(float) as the host build's x86 code performs it (cvttss2si): the "integer indefinite" value for NaN and for every value outside int's range
-__device__ __forceinline__ int x86_int(float q) { return (q >= -2147483648.0f && q < 2147483648.0f) ? (int)q : (int)0x80000000; }
-
 struct CellRange { int mn[3]; uint32_t nx, ny, n; };                              // first cell per axis, cells along x and y, cells in all (>= 1)
 
 // Tri::GetBounds (aabb from +-1e34, Grow(vertex0), Grow(vertex1), Grow(vertex2)) and the `range` lambda of Grid::Build
@@ -85,12 +82,8 @@ __global__ __launch_bounds__(kGridThreads) void grid_bounds_kernel(const float* 
     for (uint32_t v = blockIdx.x * kGridThreads + threadIdx.x; v < nVerts; v += gridDim.x * kGridThreads) {
         const float* p = pos + (size_t)v * 3u;
         for (int k = 0; k < 3; k++) {
-            uint32_t b = __float_as_uint(p[k]);
-            if ((b & 0x7f800000u) == 0x7f800000u) { bad = true; continue; }
-            const uint32_t sign = b >> 31;
-            if ((b << 1) == 0u) b = 0u;                                            // -0 and +0 tie
-            const unsigned long long ord = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-            const unsigned long long kmin = (ord << 32) | ((unsigned long long)(0x7fffffffu - v) << 1) | sign, kmax = (ord << 32) | ((unsigned long long)v << 1) | sign;
+            if ((__float_as_uint(p[k]) & 0x7f800000u) == 0x7f800000u) { bad = true; continue; }
+            unsigned long long kmin, kmax; bound_keys(p[k], v, &kmin, &kmax);
             mn[k] = kmin < mn[k] ? kmin : mn[k]; mx[k] = kmax > mx[k] ? kmax : mx[k];
         }
     }

@@ -104,6 +104,18 @@ hipError_t crt_launch_kd_split(crt::KdBuildNode* nodes, uint32_t nodeCount, cons
 hipError_t crt_launch_kd_finalise(crt::KdBuildNode* const* nodes, const uint32_t* const* refs, const uint32_t* const* owner, const uint32_t* nodeCount, const uint32_t* refCount, uint32_t levels,
     crt::KdNode* outNodes, uint32_t outNodeCount, uint32_t* outRefs, uint32_t outRefCount, uint32_t maxBlocks, hipStream_t stream);
 
+// ---- bvh_build.hip ----
+hipError_t crt_launch_bvh_begin(const float* pos, uint32_t triCount, const char* geom, uint32_t leafOff, uint32_t triBase, float* cen, uint32_t* idx, uint32_t* owner, int32_t* objOf,
+    crt::BvhBuildNode* root, unsigned long long* rootKeys, crt::BvhBuildState* state, uint32_t maxBlocks, hipStream_t stream);
+hipError_t crt_launch_bvh_level(const float* pos, const float* cen, const uint32_t* idx, const uint32_t* owner, uint32_t triCount, crt::BvhBuildNode* nodes, unsigned long long* keys,
+    uint32_t m, uint32_t* bins, uint32_t* leftItems, uint32_t* nodeItems, unsigned long long* chunkSums, crt::BvhBuildState* state, int isRoot, uint32_t maxBlocks, hipStream_t stream);
+hipError_t crt_launch_bvh_split(crt::BvhBuildNode* nodes, uint32_t m, const uint32_t* splitScan, const uint32_t* owner, const uint32_t* idx, const uint32_t* leftScan, uint32_t triCount,
+    crt::BvhBuildNode* next, unsigned long long* nextKeys, uint32_t nextM, uint32_t* idxOut, uint32_t* ownerOut, uint32_t* remain, uint32_t maxBlocks, hipStream_t stream);
+hipError_t crt_launch_bvh_flatten(crt::BvhBuildNode* nodes, const uint32_t* levelOff, uint32_t levels, const float* pos, const uint32_t* idx, const uint32_t* remain, const int32_t* objOf,
+    uint32_t triCount, const crt::BvhFlatten* F, char* geom, uint32_t maxBlocks, hipStream_t stream);
+hipError_t crt_launch_bvh_relocate(const char* oldGeom, char* geom, const crt::BvhRelocate* R, uint32_t instOff, uint32_t blasCount, uint32_t bvh, uint32_t rootRef, uint32_t rootRef16,
+    uint32_t maxBlocks, hipStream_t stream);
+
 // ---- tlas_build.hip ----
 hipError_t crt_launch_tlas_build(const char* geom, uint32_t instOff, const float* T, const float* rootBox, uint32_t blasCount, uint32_t pairRel, uint32_t instRel, uint32_t poolRefBits,
     void* out, hipStream_t stream);

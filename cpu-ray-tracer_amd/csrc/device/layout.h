@@ -224,6 +224,28 @@ struct alignas(16) KdBuildNode {
 struct alignas(16) KdBuildState { GridBuildState bounds; unsigned long long nodeTotal, refTotal; };
 constexpr uint32_t kKdMaxDepth = 20u;     // kdtree.h m_maxBuildDepth: levels 0 .. 20
 
+// crt_build_bvh_device (bvh_build.hip): one node of one level of the level-synchronous binned-SAH build, and the block the kernels report through.  A level's
+// nodes are in level order over ONE triangleIndices array: node = slots [first, first + count).  Beside the records live 6 box keys per node (the fold of
+// Builder::fit: ordered value << 32 | position << 1 | sign of a zero) and, per level, 3 x 8 bins per node of kBvhBinWords words: count, box min xyz, box max xyz
+// as ordered 32-bit keys.
+struct alignas(16) BvhBuildNode {
+    float lo[3]; uint32_t first;          // box (from the keys, bvh_plane_kernel); first slot
+    float hi[3]; uint32_t count;
+    uint32_t ckey[6];                     // centroid bounds min xyz, max xyz as ordered keys (nodes of more than 2 triangles)
+    float pos; int32_t axis;              // the chosen plane; axis < 0: no plane (<= 2 triangles, or the leaf test held): nothing is partitioned
+    uint32_t nLeft, child;                // leftCount of the partition; the left child's index in the next level (the right one follows it), kBvhNone: a leaf
+    uint32_t subSplits, pair;             // split nodes of the subtree (bottom-up); number of the node's child pair = split nodes before it in pre-order (top-down)
+};
+constexpr uint32_t kBvhNone = 0xffffffffu;
+constexpr uint32_t kBvhBins = 8u, kBvhBinWords = 7u, kBvhNodeBinWords = 3u * kBvhBins * kBvhBinWords;
+// splits / lefts: the totals of the level's two scans (nodes that split; slots that go left); rootBox: node 0's box, written by level 0
+struct alignas(16) BvhBuildState { unsigned long long splits, lefts; float rootBox[6]; uint32_t nonFinite, pad; };
+// where the rebuilt BVH's records go in the new geometry buffer, and how its references are written (the scene's pool reference form)
+struct BvhFlatten { uint32_t pairBase, pairs, triBase, leafOff, interior16, mask16; };
+// the other BVHs' pairs carried into the new buffer: the old buffer's pairs, the rebuilt BVH's old range among them, how far the pairs behind it move, how far
+// (in 16-byte units) every offset-form leaf reference moves
+struct BvhRelocate { uint32_t oldPairs, firstPair, pairCount; int32_t pairDelta, leafDelta16; uint32_t interior16, mask16; };
+
 // PrimitiveScene at one animation time (crt_primitive_scene flattened by crt_upload_primitive_scene; kernels in render_prim.hip), passed to the kernels by value
 struct PrimDev {
     float quadInvT[12], quadNrm[3], quadSize;

@@ -17,15 +17,17 @@ struct Builder {
     std::vector<Tri>& tris; std::vector<BVHNode>& nodes; std::vector<uint32_t>& idx;
     uint32_t used = 1, deepest = 0;
 
-    // tight bounds over a node's triangles (bvh.cpp:45-61); sentinels are 1e30, not the aabb class's 1e34
+    // tight bounds over a node's triangles (bvh.cpp:45-61); sentinels are 1e30, not the aabb class's 1e34.  The fold keeps the EARLIER operand on a tie (which decides
+    // between -0 and +0): bvh.cpp calls fminf / fmaxf, and the in-place build of the reference's bvh.cpp, which the build is held to byte for byte, answers that way
+    //  — so the accumulator is the SECOND operand of lesser / greater here
     void fit(uint32_t n)
     {
         BVHNode& node = nodes[n];
         float3 lo(1e30f), hi(-1e30f);
         for (uint32_t i = 0; i < node.triCount; i++) {
             const Tri& t = tris[idx[node.leftFirst + i]];
-            lo = fminf3(lo, V(t.vertex0)); lo = fminf3(lo, V(t.vertex1)); lo = fminf3(lo, V(t.vertex2));
-            hi = fmaxf3(hi, V(t.vertex0)); hi = fmaxf3(hi, V(t.vertex1)); hi = fmaxf3(hi, V(t.vertex2));
+            lo = fminf3(V(t.vertex0), lo); lo = fminf3(V(t.vertex1), lo); lo = fminf3(V(t.vertex2), lo);
+            hi = fmaxf3(V(t.vertex0), hi); hi = fmaxf3(V(t.vertex1), hi); hi = fmaxf3(V(t.vertex2), hi);
         }
         S(node.aabbMin, lo); S(node.aabbMax, hi);
     }

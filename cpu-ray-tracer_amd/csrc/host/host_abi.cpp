@@ -113,6 +113,45 @@ int crt_host_scene_bvh_move_and_refit(crt_host_scene* s, int i, const float* pos
     return CRT_OK;
     GUARD_END(CRT_ERR_INVALID)
 }
+int crt_host_scene_bvh_move_and_rebuild(crt_host_scene* s, int i, const float* positions, uint32_t triCount)
+{
+    if (!s || !positions) { g_err = "null argument"; return CRT_ERR_INVALID; }
+    GUARD_BEGIN
+    std::vector<Tri>* tris = nullptr;
+    BLASBVH* blas = nullptr;
+    if (s->file) { if (i != 0) { g_err = "bvh index out of range"; return CRT_ERR_INVALID; } tris = &s->file->acc.triangles; }
+    else { if (i < 0 || i >= (int)s->tlas->tlas.blas.size()) { g_err = "bvh index out of range"; return CRT_ERR_INVALID; } blas = s->tlas->tlas.blas[(size_t)i]; tris = &blas->triangles; }
+    if (triCount != tris->size()) { g_err = "triangle count does not match the built BVH (a rebuild keeps the triangles)"; return CRT_ERR_INVALID; }
+    for (uint32_t t = 0; t < triCount; t++) {
+        Tri& tr = (*tris)[t];
+        memcpy(tr.vertex0, positions + 9 * (size_t)t, 12); memcpy(tr.vertex1, positions + 9 * (size_t)t + 3, 12); memcpy(tr.vertex2, positions + 9 * (size_t)t + 6, 12);
+        for (int k = 0; k < 3; k++) tr.centroid[k] = (tr.vertex0[k] + tr.vertex1[k] + tr.vertex2[k]) * 0.3333f;       // model.cpp:77 / blas_bvh.cpp:74
+    }
+    if (s->file) s->file->acc.Build();
+    else { blas->Build(); blas->SetTransform(blas->T); s->tlas->tlas.Build(); }
+    if ((size_t)i < s->scene->staleBvh.size()) s->scene->staleBvh[(size_t)i] = 0;    // the host arrays are current again
+    return CRT_OK;
+    GUARD_END(CRT_ERR_INVALID)
+}
+int crt_host_scene_build_bvh_device(crt_host_scene* s, crt_ctx* ctx, int i, const float* d_positions, uint32_t triCount, void* stream)
+{
+    if (!s || !ctx) { g_err = "null argument"; return CRT_ERR_INVALID; }
+    GUARD_BEGIN
+    const int count = s->file ? 1 : (int)s->tlas->tlas.blas.size();
+    if (i < 0 || i >= count) { g_err = "bvh index out of range"; return CRT_ERR_INVALID; }
+    int rc = crt_build_bvh_device(ctx, (uint32_t)i, d_positions, triCount, stream, nullptr);
+    if (rc != CRT_OK) { g_err = crt_last_error(ctx); return rc; }
+    std::vector<float> pos(9 * (size_t)triCount);
+    rc = crt_internal_read_device(ctx, pos.data(), d_positions, pos.size() * 4, stream);
+    if (rc != CRT_OK) { g_err = crt_last_error(ctx); return rc; }
+    if ((rc = crt_host_scene_bvh_move_and_rebuild(s, i, pos.data(), triCount)) != CRT_OK) return rc;
+    if (s->tlas) {                                                                   // as after BLASBVH::Build: world bounds from the new root box, TLAS rebuilt, both sent
+        rc = s->scene->Update(ctx, CRT_UPDATE_TRANSFORMS);
+        if (rc != CRT_OK) g_err = crt_last_error(ctx);
+    }
+    return rc;
+    GUARD_END(CRT_ERR_DEVICE)
+}
 int crt_host_scene_bvh_refit_device(crt_host_scene* s, crt_ctx* ctx, int i, const float* d_positions, uint32_t triCount, void* stream)
 {
     if (!s || !ctx) { g_err = "null argument"; return CRT_ERR_INVALID; }
@@ -251,6 +290,33 @@ int crt_host_scene_build_kdtree_device(crt_host_scene* s, crt_ctx* ctx, int i, c
     if (rc != CRT_OK) g_err = crt_last_error(ctx);
     return rc;
     GUARD_END(CRT_ERR_DEVICE)
+}
+int crt_host_bvh_build(const float* positions, uint32_t triCount, uint32_t info[3], crt_bvh_node* nodes, uint32_t* triangleIndices)
+{
+    if (!positions || triCount == 0) { g_err = "null argument"; return CRT_ERR_INVALID; }
+    GUARD_BEGIN
+    std::vector<Tri> tris(triCount);
+    for (uint32_t t = 0; t < triCount; t++) {
+        Tri& tr = tris[t]; memset(&tr, 0, sizeof(Tri));
+        memcpy(tr.vertex0, positions + 9 * (size_t)t, 12); memcpy(tr.vertex1, positions + 9 * (size_t)t + 3, 12); memcpy(tr.vertex2, positions + 9 * (size_t)t + 6, 12);
+        for (int k = 0; k < 3; k++) tr.centroid[k] = (tr.vertex0[k] + tr.vertex1[k] + tr.vertex2[k]) * 0.3333f;
+    }
+    std::vector<BVHNode> n; std::vector<uint32_t> idx; uint32_t used = 0, depth = 0;
+    BuildSAH(tris, n, idx, used, depth);
+    if (info) {
+        uint32_t height = 0;
+        std::vector<std::pair<uint32_t, uint32_t>> st; st.push_back({0u, 0u});
+        while (!st.empty()) {
+            const auto [k, d] = st.back(); st.pop_back();
+            if (n[k].triCount > 0) { if (d > height) height = d; continue; }
+            st.push_back({n[k].leftFirst, d + 1}); st.push_back({n[k].leftFirst + 1, d + 1});
+        }
+        info[0] = used; info[1] = depth; info[2] = height;
+    }
+    if (nodes) memcpy(nodes, n.data(), n.size() * sizeof(BVHNode));
+    if (triangleIndices) memcpy(triangleIndices, idx.data(), idx.size() * 4);
+    return CRT_OK;
+    GUARD_END(CRT_ERR_INVALID)
 }
 int crt_host_kd_build(const float* positions, uint32_t triCount, uint32_t info[4], crt_kd_node* nodes, uint32_t* refs)
 {

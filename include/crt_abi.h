@@ -399,6 +399,28 @@ int  crt_build_kdtree_device(crt_ctx* ctx, uint32_t bvh, const float* d_position
  * waits for a device build still running).  CRT_ERR_STATE when there is no live tree; bvh out of range is CRT_ERR_INVALID. */
 int  crt_get_kdtree(crt_ctx* ctx, uint32_t bvh, uint32_t* nodeCount, uint32_t* refCount, uint32_t* height, crt_kd_node* nodes /* nodeCount, or NULL */,
                     uint32_t* refs /* refCount, or NULL */);
+/* BVH::Build / BLASBVH::Build (bvh.cpp:4-24, 63-178: binned SAH, 8 bins) of ONE uploaded BVH on the device, from vertex positions that already live in device memory:
+ * where crt_refit_device keeps the rest pose's topology — boxes overlap more with every frame of a deformation — this call gives the tree a fresh build has.  ABI
+ * version 3 still: an addition, detected by symbol.  d_positions, triCount, `stream`, rootBox as crt_refit_device takes them; CRT_SCENE_FILE (bvh = 0) and every BLAS
+ * of a CRT_SCENE_TLAS scene.  Afterwards the scene is exactly what crt_upload_scene gives for the same description with that BVH rebuilt on the host (triangles moved,
+ * centroids (v0 + v1 + v2) * 0.3333f, Build), byte for byte: node pairs, leaf triangles, both forms of every packed reference, the section offsets (the pair section
+ * changes size, so everything behind it moves), the root reference and pair, the stack depth.  Shade records, materials, textures, the TLAS and the transforms are
+ * untouched.  Like BLASBVH::Build the call does NOT rebuild the TLAS: crt_update_transforms_device next (it reads the new node-0 box on the device), or the host route
+ * through rootBox, as after crt_refit_device.
+ * The build is level-synchronous (device/bvh_build.hip): ONE SHORT HOST WAIT PER LEVEL of the tree for the number of nodes that split, then one read-back of the new
+ * pair and leaf sections into the context's host mirror.  The result is a fresh geometry buffer; the old one is retired behind its readers: launches enqueued earlier
+ * keep the old tree, later ones wait for the new one.  It drops what crt_refit_device drops (a two-level scene's KD-tree / grid sets until their device builds of
+ * this BLAS, the frames crt_tick rendered ahead) and that BVH's refit plan.
+ * Refused with nothing modified, with crt_refit_device's codes; also: a position component that is not finite (CRT_ERR_INVALID), a tree whose traversal stack would
+ * exceed the LDS budget crt_upload_scene enforces, geometry beyond 4 GiB (CRT_ERR_UNSUPPORTED), a failed device allocation (CRT_ERR_DEVICE). */
+int  crt_build_bvh_device(crt_ctx* ctx, uint32_t bvh, const float* d_positions /* 9 * triCount, device */, uint32_t triCount, void* stream,
+                          float rootBox[6] /* out: node 0's aabbMin, aabbMax; may be NULL */);
+/* One BVH of the live scene in the reference's form again, reconstructed from the device's geometry buffer (after an upload, an update, a refit or a device
+ * rebuild): sizes first (any output may be NULL; maxDepth = the deepest depth at which a node split, what BVH::Build reports; height = the deepest leaf, in edges),
+ * then nodes (nodesUsed records: children 2k + 1 and 2k + 2 are pair k's) and triangleIndices (triCount) where the pointers are non-NULL.  Synchronous (it waits for a
+ * scene write still running).  No scene: CRT_ERR_STATE; a PrimitiveScene: CRT_ERR_UNSUPPORTED; bvh out of range: CRT_ERR_INVALID. */
+int  crt_get_bvh(crt_ctx* ctx, uint32_t bvh, uint32_t* nodesUsed, uint32_t* maxDepth, uint32_t* height, crt_bvh_node* nodes /* nodesUsed, or NULL */,
+                 uint32_t* triangleIndices /* triCount, or NULL */);
 
 /* ---- scene queries: BaseScene::IsOccluded, and both queries on device buffers (base_scene.h:16-32) ------------------------------------------------
  * accel: 0 = the scene's own structure (BVH / TLAS; for the nearest-hit query also the PrimitiveScene), CRT_ACCEL_KDTREE / CRT_ACCEL_GRID = the uploaded

@@ -87,6 +87,17 @@ int  crt_host_scene_build_kdtree_device(crt_host_scene* scene, crt_ctx* ctx, int
 /* KDTree::Build (infra/kdtree.cpp:4-108) on the host over bare positions (9 floats per triangle): what crt_build_kdtree_device is compared with for meshes that are no
  * scene.  info (may be NULL) = nodes, leaf references, maxDepth, nodesUsed; nodes / refs (may be NULL) receive the arrays sized by an earlier call. */
 int  crt_host_kd_build(const float* positions, uint32_t triCount, uint32_t info[4], crt_kd_node* nodes, uint32_t* refs);
+/* BVH::Build (infra/bvh.cpp:4-24, 63-178; BuildSAH) on the host over bare positions (9 floats per triangle; centroids (v0 + v1 + v2) * 0.3333f): what
+ * crt_build_bvh_device is compared with for meshes that are no scene.  info (may be NULL) = nodesUsed, maxDepth, height (deepest leaf, in edges); nodes (2 * triCount - 1
+ * records, those behind nodesUsed zero) and triangleIndices (triCount) where the pointers are non-NULL. */
+int  crt_host_bvh_build(const float* positions, uint32_t triCount, uint32_t info[3], crt_bvh_node* nodes, uint32_t* triangleIndices);
+/* BVH::Build / BLASBVH::Build for moved vertices: replaces the vertex positions of BVH `bvh` as crt_host_scene_bvh_move_and_refit does, recomputes the centroids and
+ * BUILDS the tree again; a TLAS scene's world bounds and TLAS follow.  crt_host_scene_upload afterwards sends the rebuilt scene. */
+int  crt_host_scene_bvh_move_and_rebuild(crt_host_scene* scene, int bvh, const float* positions, uint32_t triCount);
+/* The same rebuild on the device, from positions in device memory (crt_build_bvh_device; d_positions, triCount, stream as there), and the host scene kept in step:
+ * the positions are copied back, crt_host_scene_bvh_move_and_rebuild runs on them (the device's tree is that build's, byte for byte), and for a TLAS scene
+ * crt_update_scene(CRT_UPDATE_TRANSFORMS) sends the host's TLAS, as crt_host_scene_bvh_refit_device does.  The host arrays are current afterwards. */
+int  crt_host_scene_build_bvh_device(crt_host_scene* scene, crt_ctx* ctx, int bvh, const float* d_positions, uint32_t triCount, void* stream);
 int  crt_host_scene_blas_transform(crt_host_scene* scene, int bvh, float T[16], float invT[16], float worldMin[3], float worldMax[3]);
 int  crt_host_scene_tlas_copy(crt_host_scene* scene, crt_tlas_node* nodes /* 2*blasCount */, uint32_t* nodesUsed);
 
