@@ -655,16 +655,18 @@ class Context:
             raise CrtError(-3, "pool_lds: no scene uploaded")
         return b.value, lim.value, bits.value
 
-    def tile_classes(self):
-        """crt_debug_tile_classes: the pool kernel's tile classes as the device holds them, one byte per owned tile (TILE_NO_LIGHT | TILE_NO_FLOOR | TILE_NO_TREE)"""
-        self.L.crt_debug_tile_classes.restype = C.c_int
-        self.L.crt_debug_tile_classes.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
-        n = self.L.crt_debug_tile_classes(self.h, None, 0)
+    def tile_classes(self, ex=False):
+        """crt_debug_tile_classes: the pool kernel's tile classes as the device holds them, one byte per owned tile (TILE_NO_LIGHT | TILE_NO_FLOOR | TILE_NO_TREE);
+        ex: crt_debug_tile_classes_ex, the whole byte (TILE_FLOOR_SURE as well)"""
+        f = self.L.crt_debug_tile_classes_ex if ex else self.L.crt_debug_tile_classes
+        f.restype = C.c_int
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+        n = f(self.h, None, 0)
         if n < 0:
             self._ck(n)
         out = np.zeros(n, np.uint8)
         if n:
-            rc = self.L.crt_debug_tile_classes(self.h, _p(out), n)
+            rc = f(self.h, _p(out), n)
             if rc < 0:
                 self._ck(rc)
         return out
@@ -1099,20 +1101,24 @@ def tile_partition(rank, world, n_tiles):
 
 TILE_NO_LIGHT, TILE_NO_FLOOR, TILE_NO_TREE = 1, 2, 4      # layout.h kTileNo*: tests no primary ray of a tile can pass
 TILE_SKY = 7
+TILE_FLOOR_SURE = 8                                       # layout.h kTileFloorSure: the floor plane's test EVERY primary ray of a tile passes (the _ex entries only)
+TILE_FLOOR = TILE_NO_LIGHT | TILE_NO_TREE | TILE_FLOOR_SURE
 
 
-def tile_classes_host(camera, light_offsets, light_size, floor_d, root_pair, width, height, tile_first=0, tile_stride=1, tile_count=-1, flags=7):
+def tile_classes_host(camera, light_offsets, light_size, floor_d, root_pair, width, height, tile_first=0, tile_stride=1, tile_count=-1, flags=7, ex=False):
     """crt_debug_tile_classes_host (no GPU): the tile classes of a bare Scene block.  camera = camPos, topLeft, topRight, bottomLeft (12 floats); light_offsets =
-    lightInvT[3], [7], [11]; root_pair = the root's NodePair (16 floats); flags: 1 lightAxis, 2 floorAxisY, 4 rootIsPair."""
+    lightInvT[3], [7], [11]; root_pair = the root's NodePair (16 floats); flags: 1 lightAxis, 2 floorAxisY, 4 rootIsPair.  ex: crt_debug_tile_classes_host_ex, the
+    whole byte (TILE_FLOOR_SURE as well)."""
     if tile_count < 0:
         tile_first, tile_stride, tile_count = 0, 1, (width // 16) * (height // 16)
     v = np.concatenate([np.asarray(camera, np.float32).reshape(12), np.asarray(light_offsets, np.float32).reshape(3), np.array([light_size, floor_d], np.float32),
                         np.asarray(root_pair, np.float32).reshape(16)]).astype(np.float32)
     out = np.zeros(tile_count, np.uint8)
     L = lib()
-    L.crt_debug_tile_classes_host.restype = C.c_int
-    L.crt_debug_tile_classes_host.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
-    rc = L.crt_debug_tile_classes_host(_p(v), flags, width, height, tile_first, tile_stride, tile_count, _p(out))
+    f = L.crt_debug_tile_classes_host_ex if ex else L.crt_debug_tile_classes_host
+    f.restype = C.c_int
+    f.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
+    rc = f(_p(v), flags, width, height, tile_first, tile_stride, tile_count, _p(out))
     if rc != 0:
         raise CrtError(rc, "crt_debug_tile_classes_host: invalid argument")
     return out

@@ -1142,6 +1142,8 @@ static int update_tile_class(crt_ctx* c)
         HIPCK(c, ensure_event(&c->classCopied[k]));
     } else HIPCK(c, hipEventSynchronize(c->classCopied[k]));
     crt::classify_tiles(c->hScene, c->cfg.width, c->cfg.height, (uint32_t)c->tilesX, c->tileFirst, c->tileStride, c->tileCount, c->hTileClass[k]);
+    if (hook("CRT_DEBUG_NO_FLOOR_CLASS"))                           // tests / A-B: the table as it was before kTileFloorSure (the floor tiles take new_ray's general form)
+        for (uint32_t i = 0; i < c->tileCount; i++) c->hTileClass[k][i] &= (uint8_t)~crt::kTileFloorSure;
     {
         // a changed set of sky tiles: the order on the device no longer ends with it, so a new one is made before the next launch (crt_render: update_tile_order
         // runs behind this function) — and with it the costs are measured again, as after a camera change
@@ -3725,7 +3727,8 @@ extern "C" int crt_debug_primary_block_host(int op, const float* in, float* out)
 
 // tests / tools: the context's tile classes as the device holds them, out[min(cap, tiles owned)] (classified first if the Scene block changed since the last
 // crt_render).  Returns the number of owned tiles, or a negative error code.
-extern "C" int crt_debug_tile_classes(crt_ctx* c, uint8_t* out, uint32_t cap)
+// (_ex: the whole byte, layout.h kTileFloorSure included; the older entry keeps returning the three kTileNo* bits)
+extern "C" int crt_debug_tile_classes_ex(crt_ctx* c, uint8_t* out, uint32_t cap)
 {
     if (!c || (!out && cap)) return CRT_ERR_INVALID;
     HIPCK(c, hipSetDevice(c->cfg.device));
@@ -3737,9 +3740,23 @@ extern "C" int crt_debug_tile_classes(crt_ctx* c, uint8_t* out, uint32_t cap)
     }
     return (int)c->tileCount;
 }
+extern "C" int crt_debug_tile_classes(crt_ctx* c, uint8_t* out, uint32_t cap)
+{
+    const int r = crt_debug_tile_classes_ex(c, out, cap);
+    for (uint32_t i = 0; r > 0 && i < cap && i < (uint32_t)r; i++) out[i] &= (uint8_t)crt::kTileNoMask;
+    return r;
+}
 // tests (no GPU needed): classify_tiles on a bare Scene block filled the way a session fills it.  in[33] = camPos, topLeft, topRight, bottomLeft; lightInvT[3], [7],
 // [11]; lightSize; floorD; rootPair[16].  flags: 1 = lightAxis, 2 = floorAxisY, 4 = rootIsPair.  out[tileCount], the tiles tileFirst + i * tileStride of a W x H image.
+// (_ex: the whole byte, layout.h kTileFloorSure included; the older entry keeps returning the three kTileNo* bits)
+extern "C" int crt_debug_tile_classes_host_ex(const float* in, uint32_t flags, int W, int H, uint32_t tileFirst, uint32_t tileStride, uint32_t tileCount, uint8_t* out);
 extern "C" int crt_debug_tile_classes_host(const float* in, uint32_t flags, int W, int H, uint32_t tileFirst, uint32_t tileStride, uint32_t tileCount, uint8_t* out)
+{
+    const int r = crt_debug_tile_classes_host_ex(in, flags, W, H, tileFirst, tileStride, tileCount, out);
+    for (uint32_t i = 0; r == CRT_OK && i < tileCount; i++) out[i] &= (uint8_t)crt::kTileNoMask;
+    return r;
+}
+extern "C" int crt_debug_tile_classes_host_ex(const float* in, uint32_t flags, int W, int H, uint32_t tileFirst, uint32_t tileStride, uint32_t tileCount, uint8_t* out)
 {
     if (!in || !out || W < 16 || H < 16 || tileStride == 0) return CRT_ERR_INVALID;
     const uint32_t tilesX = (uint32_t)(W / 16), tiles = tilesX * (uint32_t)(H / 16);

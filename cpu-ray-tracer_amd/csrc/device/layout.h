@@ -143,6 +143,11 @@ inline void set_primary(Scene& s)
 // is a proof; 0 is always correct.
 constexpr uint32_t kTileNoLight = 1u, kTileNoFloor = 2u, kTileNoTree = 4u;    // the light quad's test, the floor plane's, the slab tests of the root's two children
 constexpr uint32_t kTileSky = kTileNoLight | kTileNoFloor | kTileNoTree;      // all three: every path of the tile ends at depth 0 in the sky lookup
+// ... and one test that EVERY primary ray of the tile passes: the floor half of hit_light_floor<true> (floorAxisY form), i.e. t = -primFloor / D.y satisfies
+// 0 < t < 1e34.  It excludes kTileNoFloor, so a sky tile never carries it.  The debug entries that predate it return the three bits above only.
+constexpr uint32_t kTileFloorSure = 8u;
+constexpr uint32_t kTileFloor = kTileNoLight | kTileNoTree | kTileFloorSure;  // every primary ray of the tile misses the light and the tree and hits the floor
+constexpr uint32_t kTileNoMask = 7u;                                          // the kTileNo* bits
 
 struct Counters { unsigned long long v[8]; };   // order = crt_counters
 

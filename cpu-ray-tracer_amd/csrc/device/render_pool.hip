@@ -79,6 +79,7 @@ __device__ unsigned long long g_poolStamps[16];
 // diagnostic build only (-DCRT_POOL_DENS, tools/pool_density.py): how often every section of the loop runs and with how many lanes, summed over all waves
 // [32 + 4 * k + b]: by the wave's LIVE streams (slots whose stream has not yet rendered its 256 pixels; bucket b: 0 = >= 112, 1 = 96..111, 2 = 64..95, 3 = < 64)
 //   k = 0 trips, 1 END passes, 2 BOUNCE passes, 3 wall-clock ticks (100 MHz) of the wave's life
+// [30], [31]: the trips and the shading passes (END + BOUNCE) of the wavefronts whose tile carries kTileFloor
 __device__ unsigned long long g_poolDens[48];
 #define CRT_DENS(i, v) (dens[i] += (uint32_t)(v))
 #define CRT_DENS_MASK(i, pred) (dens[i] += (uint32_t)__popcll(__builtin_amdgcn_ballot_w64(pred)))
@@ -161,7 +162,9 @@ __global__ __launch_bounds__(64, REFBITS == 32 ? CRT_POOL_WIDE_MIN_WAVES : CRT_P
     const uint32_t tx = tile % tilesX, ty = tile / tilesX;
     // what the tile's primary rays cannot hit (layout.h kTileNo*, proven on the host: tile_class.h), one scalar for the wavefront's life; 0 = every test runs.
     // Only new_ray's primary form and the END pass look at it, and only to skip, under a scalar branch, a test whose outcome is known
-    const uint32_t tcls = tileClass ? __builtin_amdgcn_readfirstlane((uint32_t)tileClass[tl]) : 0u;
+    // kTileFloorSure (every primary ray hits the floor: floor_ray, below) is dropped here, once, when the depth limit is 0: a floor hit at depth 0 then ends the path
+    // instead of bouncing, which is new_ray's general form
+    const uint32_t tcls = tileClass ? __builtin_amdgcn_readfirstlane((uint32_t)tileClass[tl] & (sc.depthLimit > 0 ? ~0u : ~kTileFloorSure)) : 0u;
     // "not a sky tile" is compared afresh by each test that asks (fresh(), above)
     auto not_sky = [&]() -> bool { return fresh(tcls) != kTileSky; };
     const char* __restrict__ geom = sc.geom;
@@ -287,6 +290,28 @@ __global__ __launch_bounds__(64, REFBITS == 32 ? CRT_POOL_WIDE_MIN_WAVES : CRT_P
         CRT_DENS(20, __popcll(mAct)); CRT_DENS(19, __popcll(mW));
         if (lane_in(mE)) qEnd[(endT + rank_in(mE)) & kQueueMask] = (uint8_t)s;
         endT += (uint32_t)__popcll(mE);
+    };
+    // ---- the primary form of new_ray in a kTileFloor wavefront (layout.h; the host's proof: tile_class.h): every primary ray misses the light quad and both root
+    // children and passes the floor plane's test, and the depth limit is above 0 (tcls, above), so the outcome of new_ray's general form is known for every lane:
+    // nh = {t = -primFloor / D.y (hit_light_floor<true>'s floorAxisY expression), objIdx 1}, ncur = done, and the stream goes to the BOUNCE queue.  What is left is
+    // what that pass reads of a floor hit: O, D, t, the RNG state and meta with the floor's object field.  The reciprocal direction, CUR and PEND (alias F_TRI, F_U,
+    // F_V) feed a root test and a walk that do not happen; the BOUNCE pass loads those slots but uses them for mesh hits only.
+    auto floor_ray = [&](uint64_t mAct, uint32_t s, f3 v, f3 O, uint32_t seed, uint32_t meta) {
+        if (lane_in(mAct)) {
+            const float inv = rcp_exact(sqrt_exact(dot3(v, v)));                  // normalize(): v * (1 / sqrtf(dot(v, v)))
+            const f3 D = v * inv;
+            cn.rays++;
+            if (COUNT) { if (KIND == 0) cn.interior++; else cn.tlas++; }           // the reference's root step is still counted
+            const kernarg_f pf = scene_floats(offsetof(Scene, primFloor));
+            const float t = -pf[0] / D.y;
+            stf[F_OX * S + s] = O.x; stf[F_OY * S + s] = O.y; stf[F_OZ * S + s] = O.z;
+            stf[F_DX * S + s] = D.x; stf[F_DY * S + s] = D.y; stf[F_DZ * S + s] = D.z;
+            stf[F_T * S + s] = t;
+            st[F_SEED * S + s] = seed; st[F_META * S + s] = meta | (2u << kMetaObjShift);
+            qBnc[(bncT + rank_in(mAct)) & kQueueMask] = (uint8_t)s;
+        }
+        CRT_DENS(20, __popcll(mAct));
+        bncT += (uint32_t)__popcll(mAct);
     };
     // back to the world-space ray when a BLAS is finished (two-level scenes): the parked copy is the world-space ray
     auto world_ray = [&]() {
@@ -447,7 +472,7 @@ __global__ __launch_bounds__(64, REFBITS == 32 ? CRT_POOL_WIDE_MIN_WAVES : CRT_P
         }
         CRT_PSTAMP(p1); CRT_PACC(0, p0, p1);
         if (COUNT) trips++;
-        CRT_DENS(0, 1);
+        CRT_DENS(0, 1); CRT_DENS(30, tcls == kTileFloor);
 #ifdef CRT_POOL_STAMPS
         pst[9]++;
 #endif
@@ -523,7 +548,7 @@ __global__ __launch_bounds__(64, REFBITS == 32 ? CRT_POOL_WIDE_MIN_WAVES : CRT_P
 #ifdef CRT_POOL_DENS
                 dens[36u + CRT_LIVE_BUCKET(live)]++;
 #endif
-                CRT_DENS(9, 1); CRT_DENS(10, n); CRT_DENS_MASK(11, miss); CRT_DENS_MASK(13, act && first); CRT_DENS_MASK(25, ended && depth > 0); CRT_DENS_MASK(26, ended && depth > 1); CRT_DENS_MASK(27, ended && depth > 2);
+                CRT_DENS(9, 1); CRT_DENS(31, tcls == kTileFloor); CRT_DENS(10, n); CRT_DENS_MASK(11, miss); CRT_DENS_MASK(13, act && first); CRT_DENS_MASK(25, ended && depth > 0); CRT_DENS_MASK(26, ended && depth > 1); CRT_DENS_MASK(27, ended && depth > 2);
                 if (ended && obj >= 2) cn.meshhits++;
                 // the path's throughput factors: fetched now (device-scope loads: they were written by this wave's BOUNCE passes, possibly from
                 // another lane), needed after the sky lookup; most paths end at depth 0..2 and a level is fetched only by the lanes that deep
@@ -597,7 +622,9 @@ __global__ __launch_bounds__(64, REFBITS == 32 ? CRT_POOL_WIDE_MIN_WAVES : CRT_P
                 }
                 CRT_DENS_MASK(12, gen);
                 CRT_PSTAMP(e1); CRT_PACC(2, p2b, e1);
-                new_ray(std::true_type{}, mGen, s, v, true, camPos, seed, item);                      // depth 0, outside, not fresh
+                // (two `if`s on one scalar, not if / else: as at the walk's node_phase)
+                if (fresh(tcls) != kTileFloor) new_ray(std::true_type{}, mGen, s, v, true, camPos, seed, item);   // depth 0, outside, not fresh
+                if (fresh(tcls) == kTileFloor) floor_ray(mGen, s, v, camPos, seed, item);
                 CRT_PSTAMP(e2); CRT_PACC(3, e1, e2);
                 if (ended) {
                     // the finished path's radiance: sky colour / light (24,24,22) / 0 at the depth limit (renderer.cpp:54-55, 69; GetLightColor file_scene.cpp:164-167), times the
@@ -638,7 +665,7 @@ __global__ __launch_bounds__(64, REFBITS == 32 ? CRT_POOL_WIDE_MIN_WAVES : CRT_P
 #ifdef CRT_POOL_DENS
                 dens[40u + CRT_LIVE_BUCKET(live)]++;
 #endif
-                CRT_DENS(14, 1); CRT_DENS(15, n); CRT_DENS_MASK(16, mesh);
+                CRT_DENS(14, 1); CRT_DENS(31, tcls == kTileFloor); CRT_DENS(15, n); CRT_DENS_MASK(16, mesh);
                 rec4 s0 = {0, 0, 0, 0}, s1 = s0, s2 = s0, s3 = s0;                 // the hit triangle's ShadeTri
                 if (mesh) { const uint32_t so = sc.shadeOff + tri * 64u; s0 = ldp<0>(geom, so); s1 = ldp<1>(geom, so); s2 = ldp<2>(geom, so); s3 = ldp<3>(geom, so); cn.meshhits++; }
                 const bool inside = (meta & kMetaInside) != 0u;

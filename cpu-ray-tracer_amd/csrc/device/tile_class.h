@@ -4,6 +4,8 @@
 // accepted by the light quad's test, the floor plane's test or the slab test of the root's two children is a property of the tile.  classify_tiles decides it
 // conservatively for every local tile: a SET bit is a proof that no primary ray of the tile passes that test as dev_common.h evaluates it in float; a CLEAR bit
 // promises nothing and is always correct.  The kernel skips a test only under a set bit, so the samples do not change.
+// kTileFloorSure is the one bit that proves the opposite: EVERY primary ray of the tile passes the floor plane's test (0 < t < 1e34), so with kTileNoLight and
+// kTileNoTree (kTileFloor) the outcome of the whole primary FindNearest is known: the floor, at t = -primFloor / D.y.
 //
 // All arithmetic is double on the exact floats of the Scene block.  What makes a double result a proof about the kernel's float arithmetic is a guard band:
 //   * the jitter (float)s * 2^-32 can round to 1.0, so a tile's pixel coordinates fill the CLOSED square [16 tx, 16 tx + 16] x [16 ty, 16 ty + 16]; the square is
@@ -20,7 +22,7 @@
 
 namespace crt {
 
-// cls[i] (bits: layout.h kTileNoLight / kTileNoFloor / kTileNoTree) for the local tiles i = 0 .. tileCount - 1 (tile tileFirst + i * tileStride of a tilesX-wide grid) of a W x H image
+// cls[i] (bits: layout.h kTileNoLight / kTileNoFloor / kTileNoTree / kTileFloorSure) for the local tiles i = 0 .. tileCount - 1 (tile tileFirst + i * tileStride of a tilesX-wide grid) of a W x H image
 inline void classify_tiles(const Scene& s, int W, int H, uint32_t tilesX, uint32_t tileFirst, uint32_t tileStride, uint32_t tileCount, uint8_t* cls)
 {
     if (tileCount == 0) return;
@@ -75,6 +77,8 @@ inline void classify_tiles(const Scene& s, int W, int H, uint32_t tilesX, uint32
     // ---- operands of the floor plane's and the light quad's short tests (dev_common.h hit_light_floor<true>) ----
     const double fnum = s.primFloor;                                            // t = -num / D.y, accepted when t > 0
     const bool floorOk = wantFloor && fnum != 0;
+    // kTileFloorSure also bounds t: |num| inside [2^-60, 2^60) and (per tile) |v.y| >= 2^-18 |v|, so |D.y| stays above 2^-19 and t inside (2^-61, 2^80)
+    const bool sureOk = floorOk && std::fabs(fnum) < std::ldexp(1.0, 60) && std::fabs(fnum) >= std::ldexp(1.0, -60);
     const double lOy = s.primLight[0], lOx = s.primLight[1], lOz = s.primLight[2], lsize = s.lightSize;   // t = Oy / -D.y; I = (Ox, Oz) + t (D.x, D.z) inside (-size, size)^2
     const bool lightOk = wantLight && lOy != 0;
 
@@ -90,6 +94,13 @@ inline void classify_tiles(const Scene& s, int W, int H, uint32_t tilesX, uint32
         if (tree && (x1 < bx0 || x0 > bx1 || y1 < by0 || y0 > by1)) b |= kTileNoTree;
         // floor: -num / D.y > 0 needs D.y and num of opposite sign
         if (floorOk && (fnum > 0 ? up : down)) b |= kTileNoFloor;
+        // ... and is positive on the whole square when they are of opposite sign at all four corners (v.y is linear, |v| convex: the extremes are at the corners)
+        if (sureOk && (fnum > 0 ? down : up)) {
+            double vv = 0;
+            for (int j = 0; j < 4; j++) vv = std::fmax(vv, v[j][0] * v[j][0] + v[j][1] * v[j][1] + v[j][2] * v[j][2]);
+            const double vyAbsMin = fnum > 0 ? -vyMax : vyMin;
+            if (std::isfinite(vv) && vyAbsMin >= std::ldexp(std::sqrt(vv), -18)) b |= kTileFloorSure;
+        }
         // light: with q = -v.y / Oy (t = |v| / q), a ray is accepted only if q > 0 and the plane hit (Ox, Oz) + (v.x, v.z) / q lies inside (-size, size)^2, i.e. only if
         //   q > 0,  v.x - (size - Ox) q < 0,  v.x + (size + Ox) q > 0,  v.z - (size - Oz) q < 0,  v.z + (size + Oz) q > 0.
         // Each left side is affine in the pixel coordinates, so one that fails at all four corners fails on the whole square.  The first is "t <= 0 at all four

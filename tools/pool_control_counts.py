@@ -18,7 +18,7 @@ import re
 import sys
 
 NAME = re.compile(r"^(_ZN3crt18render_pool_kernelILi(\d)ELb(\d)ELi(\d+)E(?:Li(\d+)E)?EE\w*):")
-ANCHORS = [("new_ray", "auto new_ray ="), ("world_ray", "auto world_ray ="), ("node_step", "auto node_step ="), ("record_offset", "auto record_offset ="),
+ANCHORS = [("new_ray", "auto new_ray ="), ("floor_ray", "auto floor_ray ="), ("world_ray", "auto world_ray ="), ("node_step", "auto node_step ="), ("record_offset", "auto record_offset ="),
            ("load_records", "auto load_records ="), ("tri_step", "auto tri_step ="), ("walk", "for (;;) {"), ("swap_out", "A. swap out"), ("exit_test", "CRT_PACC(0, p0, p1)"),
            ("swap_in", "C. swap in"), ("decide", "B. shading passes"), ("end_pass", "B1. END pass"), ("bounce_pass", "B2. BOUNCE pass"), ("epilogue", "CRT_POOL_TIMELINE\n    if (lane == 0 && g_poolTimeline)")]
 NAMED = ["s_cselect_b64", "v_cndmask_b32", "v_readlane_b32", "v_writelane_b32", "v_readfirstlane_b32", "s_and_saveexec_b64", "s_nop"]

@@ -40,7 +40,10 @@ if has:
         "end_depth_gt0_per_pass": per(25, 9), "end_depth_gt1_per_pass": per(26, 9), "end_depth_gt2_per_pass": per(27, 9),
         "bounce_passes_per_window_M": round(d[14] / K / 1e6, 3), "bounce_lanes_per_pass": per(15, 14), "bounce_mesh_lanes_per_pass": per(16, 14),
         "rejection_wave_iterations_per_pass": per(17, 14), "rejection_lanes_per_iteration": per(18, 17),
-        "new_ray_lanes_M_per_window": round(d[20] / K / 1e6, 3), "new_ray_walk_fraction": per(19, 20), "raw": d}
+        "new_ray_lanes_M_per_window": round(d[20] / K / 1e6, 3), "new_ray_walk_fraction": per(19, 20),
+        # the wavefronts whose tile carries the floor class (layout.h kTileFloor): their trips, their shading passes (END + BOUNCE), passes per trip
+        "floor_wave_trips_per_window_M": round(d[30] / K / 1e6, 3), "floor_wave_passes_per_window_M": round(d[31] / K / 1e6, 3), "floor_wave_passes_per_trip": per(31, 30),
+        "floor_wave_share_of_trips": per(30, 0), "floor_wave_share_of_passes": round(d[31] / (d[9] + d[14]), 4) if d[9] + d[14] else None, "raw": d}
     share = lambda k: [round(d[32 + 4 * k + b] / max(1, sum(d[32 + 4 * k:36 + 4 * k])), 4) for b in range(4)]
     out["wave_frames_hook"] = os.environ.get("CRT_POOL_WAVE_FRAMES")
     out["live_streams"] = {"buckets": [">=112", "96-111", "64-95", "<64"], "trips": share(0), "end_passes": share(1), "bounce_passes": share(2), "wave_time": share(3),

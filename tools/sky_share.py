@@ -2,7 +2,8 @@
 """What share of a job's summed tile cost belongs to kTileSky tiles?  Renders bench.py's default job shape (bunny 1280x720, 64 windows) twice — the first job
 measures the tile costs, the second adopts them — with ONE pool launch for every tile (CRT_DEBUG_NO_SKY_KERNEL: the launch as it was before render_sky_kernel,
 tile classes on), reads the planner's input back (crt_debug_job_costs) and sums it by class.  Then the same with the sky launch: what is left for the pool and
-what the sky launch itself took in the measuring job.
+what the sky launch itself took in the measuring job.  Also per run: how many tiles carry the floor class (layout.h kTileFloor: every primary ray hits the
+floor; crt_debug_tile_classes_ex) and what share of the summed NON-SKY tile cost they hold — the reach of the END pass's floor_ray.
     python tools/sky_share.py [scene.xml kind W H [windows]]        prints one JSON line"""
 import ctypes as C, importlib.util, json, os, subprocess, sys
 os.environ.setdefault("CRT_ENABLE_DEBUG_HOOKS", "1")      # the library reads its diagnostic environment switches only for processes that opt in
@@ -25,8 +26,13 @@ def measure(xml, kind, W, H, windows):
     rc = f(ctx.h, cost.ctypes.data, C.addressof(pw), C.addressof(sw))
     if rc != 0: sys.exit("crt_debug_job_costs: %d" % rc)
     sky = cls == crt.TILE_SKY
+    floor = (ctx.tile_classes(ex=True) & crt.TILE_FLOOR) == crt.TILE_FLOOR
     total = float(cost.astype(np.float64).sum())
-    return {"tiles": int(len(cls)), "sky_tiles": int(sky.sum()), "cost_sum_ticks": total, "sky_cost_sum_ticks": float(cost[sky].astype(np.float64).sum()),
+    other = float(cost[~sky].astype(np.float64).sum())
+    return {"floor_tiles": int(floor.sum()), "floor_cost_sum_ticks": float(cost[floor].astype(np.float64).sum()), "non_sky_cost_sum_ticks": other,
+            "floor_share_of_non_sky_cost": float(cost[floor].astype(np.float64).sum()) / other if other else 0.0,
+            "median_cost_floor_tile": float(np.median(cost[floor])) if floor.any() else 0.0,
+            "tiles": int(len(cls)), "sky_tiles": int(sky.sum()), "cost_sum_ticks": total, "sky_cost_sum_ticks": float(cost[sky].astype(np.float64).sum()),
             "sky_cost_share": float(cost[sky].astype(np.float64).sum()) / total if total else 0.0,
             "median_cost_sky_tile": float(np.median(cost[sky])) if sky.any() else 0.0, "median_cost_other_tile": float(np.median(cost[~sky])) if (~sky).any() else 0.0,
             "pool_window_ms": pw.value * 1e-5, "sky_window_ms": sw.value * 1e-5}
