@@ -110,7 +110,7 @@ HIT_INFO_DTYPE = np.dtype([("I", "<f4", 3), ("material", "<i4"), ("N", "<f4", 3)
 MATERIAL_MISS, MATERIAL_INVALID = -1, -2       # crt_hit_info.material of a miss / of a record whose objIdx or triIdx the scene does not have
 
 # every symbol include/crt_abi.h and include/crt_host.h declare (tests check the library exports all of them)
-ABI_SYMBOLS = ["crt_build_bvh_device", "crt_get_bvh", "crt_build_kdtree_device", "crt_get_kdtree", "crt_build_grid_device", "crt_get_grid", "crt_update_transforms_device", "crt_sample", "crt_sample_device", "crt_refit_device", "crt_get_hit_info", "crt_get_hit_info_device", "crt_get_sky_color", "crt_get_sky_color_device", "crt_get_light", "crt_upload_blas_accel", "crt_is_occluded", "crt_find_nearest_device", "crt_is_occluded_device", "crt_upload_primitive_scene", "crt_set_render_accel", "crt_upload_alt_accel", "crt_find_nearest_alt", "crt_update_scene", "crt_abi_version", "crt_device_count", "crt_create", "crt_destroy", "crt_last_error", "crt_upload_scene", "crt_set_camera",
+ABI_SYMBOLS = ["crt_trace", "crt_trace_device", "crt_build_bvh_device", "crt_get_bvh", "crt_build_kdtree_device", "crt_get_kdtree", "crt_build_grid_device", "crt_get_grid", "crt_update_transforms_device", "crt_sample", "crt_sample_device", "crt_refit_device", "crt_get_hit_info", "crt_get_hit_info_device", "crt_get_sky_color", "crt_get_sky_color_device", "crt_get_light", "crt_upload_blas_accel", "crt_is_occluded", "crt_find_nearest_device", "crt_is_occluded_device", "crt_upload_primitive_scene", "crt_set_render_accel", "crt_upload_alt_accel", "crt_find_nearest_alt", "crt_update_scene", "crt_abi_version", "crt_device_count", "crt_create", "crt_destroy", "crt_last_error", "crt_upload_scene", "crt_set_camera",
                "crt_render", "crt_tick", "crt_reserve", "crt_whitted_tick", "crt_whitted_tick_inspect", "crt_sync", "crt_clear", "crt_read_accumulator", "crt_resolve_screen", "crt_find_nearest", "crt_get_counters",
                "crt_reset_counters", "crt_get_timing", "crt_get_tile_clocks", "crt_bind_accumulator", "crt_accumulator_device_ptr"]
 HOST_SYMBOLS = ["crt_host_bvh_build", "crt_host_scene_bvh_move_and_rebuild", "crt_host_scene_build_bvh_device", "crt_host_scene_build_kdtree_device", "crt_host_kd_build", "crt_host_scene_build_grid_device", "crt_host_grid_build", "crt_host_scene_update_transforms_device", "crt_host_scene_bvh_refit_device", "crt_host_scene_blas_alt_info", "crt_host_scene_blas_alt_copy", "crt_host_primitive_scene_create", "crt_host_primitive_scene_free", "crt_host_primitive_scene_set_time", "crt_host_primitive_scene_desc", "crt_host_primitive_scene_upload", "crt_host_scene_build_alt", "crt_host_scene_upload_alt", "crt_host_scene_alt_info", "crt_host_scene_alt_copy", "crt_host_scene_set_transform", "crt_host_scene_update", "crt_host_math_probe", "crt_host_vertex_dedup", "crt_host_last_error", "crt_host_scene_load", "crt_host_scene_free", "crt_host_scene_upload", "crt_host_scene_kind",
@@ -510,6 +510,41 @@ class Context:
         """the lanes a full crt_sample launch over this scene holds at once (tools / tests: an n above it makes every wavefront draw from the cursor again)"""
         n = C.c_uint32()
         self._ck(self.L.crt_debug_sample_resident_lanes(self.h, int(accel), C.byref(n)))
+        return int(n.value)
+
+    def trace(self, rays, accel=0, counts=False):
+        """The Whitted Renderer::Trace(ray, 0) per ray (crt_trace, host buffers, synchronous): rays = an [N] RAY_DTYPE array (D is used as given).  accel: 0 = BVH /
+        TLAS, ACCEL_KDTREE / ACCEL_GRID.  Returns rgb [N, 3] float32, or with counts=True (rgb, traversed [N] int32, tested [N] int32): the depth-0 ray's
+        Ray::traversed / Ray::tested.  A ray with a non-finite component or D = 0 is not traced: NaN, and -1 in both counts."""
+        rays = np.ascontiguousarray(rays)
+        if rays.dtype != RAY_DTYPE or rays.ndim != 1:
+            raise ValueError("trace: rays must be a one-dimensional RAY_DTYPE array")
+        n = rays.shape[0]
+        rgb = np.zeros((n, 3), np.float32)
+        trav, tested = (np.zeros(n, np.int32), np.zeros(n, np.int32)) if counts else (None, None)
+        self._ck(self.L.crt_trace(self.h, int(accel), _p(rays), _p(rgb), _p(trav) if counts else None, _p(tested) if counts else None, C.c_size_t(n)))
+        return (rgb, trav, tested) if counts else rgb
+
+    def trace_device(self, rays, accel=0, counts=False, stream=None):
+        """crt_trace_device: the Whitted Renderer::Trace(ray, 0) for rays that live on the GPU ([N, 7] crt_ray records), enqueued on `stream` (default
+        torch.cuda.current_stream()) without a host wait.  Returns rgb [N, 3] float32, or with counts=True (rgb, traversed [N] int32, tested [N] int32), new tensors."""
+        import torch
+
+        def run(st):
+            r = self._records(rays, None, None, None, True, "trace_device")
+            n = r.shape[0]
+            rgb = torch.empty((n, 3), dtype=torch.float32, device=r.device)
+            trav = torch.empty(n, dtype=torch.int32, device=r.device) if counts else None
+            tested = torch.empty(n, dtype=torch.int32, device=r.device) if counts else None
+            self._ck(self.L.crt_trace_device(self.h, int(accel), C.c_void_p(r.data_ptr()), C.c_void_p(rgb.data_ptr()), C.c_void_p(trav.data_ptr()) if counts else None,
+                                             C.c_void_p(tested.data_ptr()) if counts else None, C.c_size_t(n), C.c_void_p(st.cuda_stream)))
+            return (rgb, trav, tested) if counts else rgb
+        return self._enqueue(stream, run)
+
+    def trace_resident_lanes(self, accel=0):
+        """the lanes a full crt_trace launch over this scene holds at once (tools / tests: an n above it makes every wavefront draw from the cursor again)"""
+        n = C.c_uint32()
+        self._ck(self.L.crt_debug_trace_resident_lanes(self.h, int(accel), C.byref(n)))
         return int(n.value)
 
     def _positions(self, positions, what):

@@ -44,9 +44,9 @@ struct EventPair { hipEvent_t a, b; int mode = -1; bool seen = false; };   // mo
 
 } // namespace
 
-// CRT_DEBUG_QUERY_GRID=<k>, k >= 1: every persistent query launch (find-nearest, is-occluded, their KD-tree / grid and two-level forms, Sample) uses at most k
+// CRT_DEBUG_QUERY_GRID=<k>, k >= 1: every persistent query launch (find-nearest, is-occluded, their KD-tree / grid and two-level forms, Sample, Trace) uses at most k
 // workgroups, so a few thousand rays are enough for every lane to take ray after ray from the cursor (tests/test_gpu_query_lane_reuse.py).  Read on every launch
-// by the wrappers in device/*.hip (launch.h bounded_query_grid); unset or 0: the launch's own grid.  crt_debug_sample_resident_lanes is not a launch and ignores it.
+// by the wrappers in device/*.hip (launch.h bounded_query_grid); unset or 0: the launch's own grid.  crt_debug_sample_resident_lanes / crt_debug_trace_resident_lanes are not launches and ignore it.
 extern "C" uint32_t crt_debug_query_grid(void)
 {
     const char* e = hook("CRT_DEBUG_QUERY_GRID");
@@ -3588,6 +3588,72 @@ extern "C" int crt_debug_sample_resident_lanes(crt_ctx* c, int accel, uint32_t* 
     if ((r = sample_check(c, accel, 0, "crt_debug_sample_resident_lanes"))) return r;
     HIPCK(c, hipSetDevice(c->cfg.device));
     HIPCK(c, launch_sample(c, accel, nullptr, nullptr, nullptr, 0u, nullptr, out, c->stream));
+    return CRT_OK;
+}
+
+// ---- crt_trace / crt_trace_device: the Whitted Renderer::Trace(ray, 0) per ray of a buffer (device/trace_query.h) ----
+// query_check's checks, the PrimitiveScene refused as crt_whitted_tick refuses it, and the traversal stack's LDS columns for the four wavefronts of a workgroup
+static int trace_check(crt_ctx* c, int accel, size_t n, const char* what)
+{
+    if (accel != 0 && accel != CRT_ACCEL_KDTREE && accel != CRT_ACCEL_GRID) return c->fail(CRT_ERR_INVALID, "%s: unknown accelerator kind %d", what, accel);
+    if (c->havePrim) return c->fail(CRT_ERR_UNSUPPORTED, "%s: Trace over the PrimitiveScene is not supported (crt_whitted_tick refuses it too)", what);
+    int r;
+    if ((r = query_check(c, accel, false, n, what))) return r;
+    const uint32_t words = crt_trace_query_stack_words(&c->hScene, accel, &c->alt, accel ? &c->blasAlt[accel - 1] : nullptr);
+    if ((uint64_t)words * 64u * 4u * 4u > 64u * 1024u) return c->fail(CRT_ERR_UNSUPPORTED, "%s: a traversal stack of %u dwords per lane exceeds the kernel's LDS", what, words);
+    return 0;
+}
+
+static hipError_t launch_trace(crt_ctx* c, int accel, const void* rays, float* rgb, int32_t* trav, int32_t* tested, uint32_t n, uint32_t* cursor, uint32_t* residentLanes, hipStream_t st)
+{
+    return crt_launch_trace_query(&c->hScene, accel, &c->alt, accel ? &c->blasAlt[accel - 1] : nullptr, rays, rgb, trav, tested, n, c->dCounters, cursor, residentLanes, st);
+}
+
+int crt_trace(crt_ctx* c, int accel, const crt_ray* rays, float* rgb, int32_t* traversed, int32_t* tested, size_t n)
+{
+    if (!c) return CRT_ERR_INVALID;
+    int r;
+    if ((r = trace_check(c, accel, n, "crt_trace"))) return r;
+    if (n == 0) return CRT_OK;
+    if (!rays || !rgb) return c->fail(CRT_ERR_INVALID, "crt_trace: NULL buffer");
+    HIPCK(c, hipSetDevice(c->cfg.device));
+    if ((r = stage(c, n * (12 + sizeof(crt_ray) + 8)))) return r;
+    float* dRgb = reinterpret_cast<float*>(c->dStage); char* dRays = c->dStage + n * 12;
+    int32_t* dTrav = reinterpret_cast<int32_t*>(dRays + n * sizeof(crt_ray)); int32_t* dTested = dTrav + n;
+    HIPCK(c, hipMemcpyAsync(dRays, rays, n * sizeof(crt_ray), hipMemcpyHostToDevice, c->stream));
+    HIPCK(c, launch_trace(c, accel, dRays, dRgb, traversed ? dTrav : nullptr, tested ? dTested : nullptr, (uint32_t)n, c->dQueryCursor, nullptr, c->stream));
+    HIPCK(c, hipMemcpyAsync(rgb, dRgb, n * 12, hipMemcpyDeviceToHost, c->stream));
+    if (traversed) HIPCK(c, hipMemcpyAsync(traversed, dTrav, n * 4, hipMemcpyDeviceToHost, c->stream));
+    if (tested) HIPCK(c, hipMemcpyAsync(tested, dTested, n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    return CRT_OK;
+}
+
+int crt_trace_device(crt_ctx* c, int accel, const crt_ray* d_rays, float* d_rgb, int32_t* d_traversed, int32_t* d_tested, size_t n, void* stream)
+{
+    if (!c) return CRT_ERR_INVALID;
+    const char* what = "crt_trace_device";
+    int r;
+    if ((r = trace_check(c, accel, n, what))) return r;
+    if (n == 0) return CRT_OK;
+    hipStream_t st = nullptr; int k = 0;
+    if ((r = device_entry(c, what, {{d_rays, n * sizeof(crt_ray)}, {d_rgb, n * 12}}, stream, &st))) return r;
+    if (d_traversed && (r = check_device_buffer(c, d_traversed, n * 4, what))) return r;          // the optional outputs: checked where given
+    if (d_tested && (r = check_device_buffer(c, d_tested, n * 4, what))) return r;
+    if ((r = wait_scene(c, st)) || (r = take_query_slot(c, &k))) return r;
+    if (accel != 0 && c->altReady) HIPCK(c, hipStreamWaitEvent(st, c->altReady, 0));     // the accelerators' copies ran on the null stream
+    HIPCK(c, launch_trace(c, accel, d_rays, d_rgb, d_traversed, d_tested, (uint32_t)n, c->dQuerySlots + 16 * k, nullptr, st));
+    return end_device_query(c, k, st);
+}
+
+// tools / tests: the lanes a full trace-query launch of this scene and accelerator holds at once (the grid is that many lanes, or fewer when the rays need fewer)
+extern "C" int crt_debug_trace_resident_lanes(crt_ctx* c, int accel, uint32_t* out)
+{
+    if (!c || !out) return CRT_ERR_INVALID;
+    int r;
+    if ((r = trace_check(c, accel, 0, "crt_debug_trace_resident_lanes"))) return r;
+    HIPCK(c, hipSetDevice(c->cfg.device));
+    HIPCK(c, launch_trace(c, accel, nullptr, nullptr, nullptr, nullptr, 0u, nullptr, out, c->stream));
     return CRT_OK;
 }
 

@@ -499,6 +499,9 @@ __device__ __forceinline__ f3 sky_color(const Scene& sc, f3 D)
     return tex_sample(sc, sc.skyOffset, sc.skyW, sc.skyH, phi * CRT_INV2PI, theta * CRT_INVPI);
 }
 
+// neither an infinity nor a NaN (the ray-array kernels refuse such rays: sample_query.h, trace_query.h)
+__device__ __forceinline__ bool finite_bits(float x) { return (__float_as_uint(x) & 0x7f800000u) != 0x7f800000u; }
+
 __device__ __forceinline__ uint32_t wave_sum(uint32_t v)
 {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

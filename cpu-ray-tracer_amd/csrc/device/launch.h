@@ -29,6 +29,10 @@ hipError_t crt_launch_whitted(const crt::Scene* sc, int accel, const crt::AltAcc
 size_t crt_whitted_inspect_work_bytes(uint32_t pixelCount);
 hipError_t crt_launch_whitted_inspect(const crt::Scene* sc, int accel, const crt::AltAccelDev* alt, const crt::TlasAltDev* tl, int inspect, int32_t peakIn, void* acc, uint32_t* pixels,
     crt::Counters* counters, int32_t* trav, int32_t* tested, void* work, uint32_t ldsBytes, hipStream_t stream);
+uint32_t crt_trace_query_stack_words(const crt::Scene* sc, int accel, const crt::AltAccelDev* alt, const crt::TlasAltDev* tl);   // dwords per lane; four wavefronts share a workgroup's 64 KiB
+hipError_t crt_launch_trace_query(const crt::Scene* sc, int accel, const crt::AltAccelDev* alt, const crt::TlasAltDev* tl, const void* rays, float* rgb, int32_t* trav /* or nullptr */,
+    int32_t* tested /* or nullptr */, uint32_t n, crt::Counters* counters, uint32_t* cursor, uint32_t* residentLanes /* not nullptr: the lanes of a full launch, and no launch */,
+    hipStream_t stream);
 hipError_t crt_launch_resolve(const void* acc, uint32_t* pixels, float* tileSums, uint32_t tileFirst, uint32_t tileStride, uint32_t tileCount, uint32_t tilesX, uint32_t W, float scale,
     hipStream_t stream);
 hipError_t crt_launch_commit_frame(const void* slabWindow, uint32_t frameInWindow, uint32_t passes, void* acc, uint32_t* pixels, float* tileSums, uint32_t tileFirst, uint32_t tileStride,

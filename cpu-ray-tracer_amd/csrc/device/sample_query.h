@@ -19,8 +19,6 @@ namespace crt {
 
 struct SampleRay { float O[3]; float D[3]; int32_t inside; };           // = crt_ray, 28 bytes
 
-__device__ __forceinline__ bool finite_bits(float x) { return (__float_as_uint(x) & 0x7f800000u) != 0x7f800000u; }
-
 template <class World>
 __global__ __launch_bounds__(256, 4) void sample_query_kernel(const Scene sc, const World world, const SampleRay* __restrict__ rays, uint32_t* __restrict__ seeds,
                                                              float* __restrict__ rgb, uint32_t n, Counters* __restrict__ counters, uint32_t* __restrict__ cursor)

@@ -517,6 +517,29 @@ int  crt_get_light(crt_ctx* ctx, float pos[3], float color[3]);
 int  crt_sample(crt_ctx* ctx, int accel, const crt_ray* rays, uint32_t* seeds, float* rgb /* 3 * n */, size_t n);                          /* host pointers, synchronous */
 int  crt_sample_device(crt_ctx* ctx, int accel, const crt_ray* d_rays, uint32_t* d_seeds, float* d_rgb /* 3 * n */, size_t n, void* stream); /* device pointers, no host wait */
 
+/* Renderer::Trace(ray, 0) — the Whitted integrator ("2. WhittedStyle/renderer.cpp":21-91), the deterministic one — for n rays of the caller's: light probes, a second
+ * camera, reflection captures, a training set without noise.  crt_whitted_tick traces the pixel grid of the context's camera with the same body; these entries
+ * serve it for any ray array.  ABI version 3 still: additions, detected by symbol.
+ * rgb[3i .. 3i+2] = Trace's return value for rays[i].  traversed[i] / tested[i] (each may be NULL) = Ray::traversed / Ray::tested of the depth-0 ray after Trace,
+ * the figures Renderer::Tick reads off primaryRay for its metrics — so a caller can rebuild Tick with its metrics outside the library.
+ * Per ray: O, D and inside are used as given — D is NOT normalised, rD = 1 / D per component; depth starts at 0; depthLimit is crt_config's, with the reference's
+ * `depth > depthLimit` test ahead of the trace; the inspection modes are off.  Radiance and counts are bit for bit what crt_whitted_tick[_inspect] computes for the same ray.
+ * accel: as for crt_sample_device — 0 = the BVH / TLAS, CRT_ACCEL_KDTREE / CRT_ACCEL_GRID = the uploaded alternative structure (a two-level scene's per-BLAS sets
+ * included), for the nearest-hit and the shadow queries alike.  crt_set_render_accel is not consulted: the argument decides.
+ * Rays that are NOT traced come back as quiet NaN in all three channels and -1 in both counts, and affect no other ray: a non-finite component of O or D, or
+ * D = (0, 0, 0).  The host entry applies the same rule per ray; it does not refuse the call.
+ * Counters: everything crt_whitted_tick counts for the same rays, except `primary`, which is not touched.  crt_tick's rendered-ahead frames are not disturbed.
+ * crt_trace_device: as the device entries above — d_rays (28 n bytes), d_rgb (12 n) and, where not NULL, d_traversed / d_tested (4 n each) are device pointers on
+ * cfg.device, 4-byte aligned (a NULL d_rays / d_rgb, misaligned, host or other-device memory: CRT_ERR_INVALID), `stream` a hipStream_t of that device or NULL; no
+ * host wait; the ordering contract is theirs (a later crt_update_scene / crt_refit_device / device rebuild is ordered behind the launch).  crt_trace: host
+ * pointers, synchronous, through staging buffers the context keeps.
+ * Refusals (nothing is modified, crt_last_error says why): no scene or no such accelerator CRT_ERR_STATE; unknown accel CRT_ERR_INVALID; the PrimitiveScene
+ * CRT_ERR_UNSUPPORTED (as crt_whitted_tick); n > 2^31-1 CRT_ERR_UNSUPPORTED; a traversal stack of more than 64 dwords per lane (four wavefronts share a
+ * workgroup's 64 KiB of LDS) CRT_ERR_UNSUPPORTED.  n == 0 is a no-op after the checks that need no buffer. */
+int  crt_trace(crt_ctx* ctx, int accel, const crt_ray* rays, float* rgb /* 3 * n */, int32_t* traversed /* n or NULL */, int32_t* tested /* n or NULL */, size_t n);
+int  crt_trace_device(crt_ctx* ctx, int accel, const crt_ray* d_rays, float* d_rgb /* 3 * n */, int32_t* d_traversed /* n or NULL */, int32_t* d_tested /* n or NULL */,
+                      size_t n, void* stream);
+
 /* ---- PrimitiveScene (second half): infra/scene/primitive_scene.cpp — the reference's hard-coded demo room (six walls, swinging light quad,
  * bouncing mirror ball, "rounded corners" sphere, spinning glass cube, glass torus; template/primitives.h Sphere :31, Cube :187, Quad :321, Torus :380; the
  * SPEEDTRIX / single-light configuration its headers select).  The binding passes the scene as its constructor + SetTime(t) leave it: the members below.
