@@ -550,17 +550,27 @@ __global__ __launch_bounds__(64, REFBITS == 32 ? CRT_POOL_WIDE_MIN_WAVES : CRT_P
 #endif
                 CRT_DENS(9, 1); CRT_DENS(31, tcls == kTileFloor); CRT_DENS(10, n); CRT_DENS_MASK(11, miss); CRT_DENS_MASK(13, act && first); CRT_DENS_MASK(25, ended && depth > 0); CRT_DENS_MASK(26, ended && depth > 1); CRT_DENS_MASK(27, ended && depth > 2);
                 if (ended && obj >= 2) cn.meshhits++;
-                // the path's throughput factors: fetched now (device-scope loads: they were written by this wave's BOUNCE passes, possibly from
-                // another lane), needed after the sky lookup; most paths end at depth 0..2 and a level is fetched only by the lanes that deep
-                // (a sky tile's paths all end at depth 0: no factor was ever written, the fetch and the unwind below are skipped as a whole)
+                // the path's throughput factors: fetched now, needed after the sky lookup.  They were written by this wavefront's BOUNCE passes, possibly from another
+                // lane, and by nobody else: a workgroup is this one wavefront and the rows are the block's own.  So the accesses are relaxed atomics of WORKGROUP scope:
+                // LLVM's gfx942 / gfx950 memory model asks for no cache bypass at that scope, because all lanes of a workgroup go through one vector L1 — which holds as
+                // long as the kernel is not built for threadgroup-split mode, and it is not.  (At agent scope every one of these loads and stores carries sc1 and goes
+                // past the L2 of its XCD.)
+                // Level k + 1 is fetched inside level k's region (depth > k + 1 implies depth > k): most paths end at depth 0..2, and the first level no lane reaches
+                // skips all the deeper ones with one branch.  "Not a sky tile" is asked once, round the nest (a sky tile's paths all end at depth 0: no factor was ever
+                // written, the fetch and the unwind below are skipped as a whole).  The 15 registers start as whatever they hold — a definition without an instruction:
+                // a lane reads a level in the unwind only where it loaded it here.
                 float fk[15];
+                asm("" : "=v"(fk[0]), "=v"(fk[1]), "=v"(fk[2]), "=v"(fk[3]), "=v"(fk[4]), "=v"(fk[5]), "=v"(fk[6]), "=v"(fk[7]), "=v"(fk[8]), "=v"(fk[9]), "=v"(fk[10]), "=v"(fk[11]), "=v"(fk[12]), "=v"(fk[13]), "=v"(fk[14]));
+                auto fetch_level = [&](int k) {
 #pragma unroll
-                for (int k = 0; k < 5; k++) {
-                    fk[3 * k] = fk[3 * k + 1] = fk[3 * k + 2] = 0.0f;
-                    if (not_sky()) if (ended && depth > k) {
-#pragma unroll
-                        for (int j = 0; j < 3; j++) fk[3 * k + j] = __hip_atomic_load(fac + (3 * k + j) * S + s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    }
+                    for (int j = 0; j < 3; j++) fk[3 * k + j] = __hip_atomic_load(fac + (3 * k + j) * S + s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                };
+                if (not_sky()) {
+                    if (ended && depth > 0) { fetch_level(0);
+                        if (depth > 1) { fetch_level(1);
+                            if (depth > 2) { fetch_level(2);
+                                if (depth > 3) { fetch_level(3);
+                                    if (depth > 4) fetch_level(4); } } } }
                 }
                 // GetSkyColor (file_scene.cpp:142-154): the texel fetch is issued here and consumed after the next ray has been set up — the skydome is far
                 // larger than the caches, and the (long) latency of this one load is then covered by the arithmetic of ray generation and new_ray
@@ -630,10 +640,18 @@ __global__ __launch_bounds__(64, REFBITS == 32 ? CRT_POOL_WIDE_MIN_WAVES : CRT_P
                     // the finished path's radiance: sky colour / light (24,24,22) / 0 at the depth limit (renderer.cpp:54-55, 69; GetLightColor file_scene.cpp:164-167), times the
                     // throughput factors in recursion order (innermost first: albedo*medium*Sample(...) multiplies on return)
                     f3 L = miss ? tex_unpack(skyTexel) : ((depth >= sc.depthLimit) ? mk3(0, 0, 0) : mk3(24, 24, 22));
+                    // (nested as the fetch is: a lane at depth d multiplies by the factors d - 1 ... 0, in that order, and the first level no lane reaches skips the deeper ones)
+                    auto fk3 = [&](int k) -> f3 { return mk3(fk[3 * k], fk[3 * k + 1], fk[3 * k + 2]); };
                     if (not_sky()) {
-#pragma unroll
-                        for (int k = 4; k >= 0; k--)
-                            if (depth > k) L = mk3(fk[3 * k], fk[3 * k + 1], fk[3 * k + 2]) * L;
+                        if (depth > 0) {
+                            if (depth > 1) {
+                                if (depth > 2) {
+                                    if (depth > 3) {
+                                        if (depth > 4) L = fk3(4) * L;
+                                        L = fk3(3) * L; }
+                                    L = fk3(2) * L; }
+                                L = fk3(1) * L; }
+                            L = fk3(0) * L; }
                     }
                     store_sample(slab, sampleAt, L);
                 }
@@ -697,10 +715,10 @@ __global__ __launch_bounds__(64, REFBITS == 32 ? CRT_POOL_WIDE_MIN_WAVES : CRT_P
                     const f3 nv = b.branch == kDiffuse ? b.v * inv : b.v;
                     v = nv;
                     const f3 factor = bounce_factor(b.branch, c, medium, nv, N);
-                    float* fd = fac + (3 * depth) * S + s;                         // depth <= 4 here
-                    __hip_atomic_store(fd, factor.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    __hip_atomic_store(fd + S, factor.y, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    __hip_atomic_store(fd + 2 * S, factor.z, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    float* fd = fac + (3 * depth) * S + s;                         // depth <= 4 here; workgroup scope: read back by this wavefront alone (the END pass's fetch)
+                    __hip_atomic_store(fd, factor.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    __hip_atomic_store(fd + S, factor.y, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    __hip_atomic_store(fd + 2 * S, factor.z, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                     O = I + nv * CRT_EPS;
                     CRT_PSTAMP(b3); CRT_PACC(7, b2, b3);
                 }

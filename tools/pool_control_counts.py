@@ -9,6 +9,8 @@ v_readlane_b32, v_writelane_b32, s_cbranch_*).  Sections come from the .loc line
 the code, and the listing names the chain of call sites an inlined line came from): the innermost line of that chain that lies inside the kernel selects
 the section whose anchor comment / lambda precedes it in the source, so a header function inlined into new_ray counts as new_ray.  A static count, good
 enough to see where a change landed; the dynamic counts are the SQ counters' (tools/profile_job.sh).
+Two parts of the END pass are sections of their own: factor_fetch (from the declaration of the 15 factor registers to the sky lookup) and unwind (from the
+path's radiance to the sample store); end_pass is the rest of the pass, and the line "end_pass (all)" sums the three.
 With --rpt the compiler's resource report (SGPRs, VGPRs, spills, scratch) of every instantiation is added."""
 import argparse
 import collections
@@ -20,7 +22,8 @@ import sys
 NAME = re.compile(r"^(_ZN3crt18render_pool_kernelILi(\d)ELb(\d)ELi(\d+)E(?:Li(\d+)E)?EE\w*):")
 ANCHORS = [("new_ray", "auto new_ray ="), ("floor_ray", "auto floor_ray ="), ("world_ray", "auto world_ray ="), ("node_step", "auto node_step ="), ("record_offset", "auto record_offset ="),
            ("load_records", "auto load_records ="), ("tri_step", "auto tri_step ="), ("walk", "for (;;) {"), ("swap_out", "A. swap out"), ("exit_test", "CRT_PACC(0, p0, p1)"),
-           ("swap_in", "C. swap in"), ("decide", "B. shading passes"), ("end_pass", "B1. END pass"), ("bounce_pass", "B2. BOUNCE pass"), ("epilogue", "CRT_POOL_TIMELINE\n    if (lane == 0 && g_poolTimeline)")]
+           ("swap_in", "C. swap in"), ("decide", "B. shading passes"), ("end_pass", "B1. END pass"), ("factor_fetch", "float fk[15];"), ("end_pass", "uint32_t skyTexel = 0u;"),
+           ("unwind", "f3 L = miss ?"), ("end_pass", "store_sample(slab, sampleAt, L);"), ("bounce_pass", "B2. BOUNCE pass"), ("epilogue", "CRT_POOL_TIMELINE\n    if (lane == 0 && g_poolTimeline)")]
 NAMED = ["s_cselect_b64", "v_cndmask_b32", "v_readlane_b32", "v_writelane_b32", "v_readfirstlane_b32", "s_and_saveexec_b64", "s_nop"]
 
 
@@ -130,6 +133,10 @@ def main():
     print("%s <%s>: %d instructions  %s  %s" % (a.label, a.inst, res["instructions"], res["by_class"], res["named"]))
     for sec, c in sorted(res["by_section"].items(), key=lambda kv: -kv[1]["total"]):
         print("  %-14s %5d  v %4d  s %4d  ds %3d  global %3d  branch %3d" % (sec, c["total"], c.get("v_", 0), c.get("s_", 0), c.get("ds_", 0), c.get("global_", 0), c.get("branch", 0)))
+    whole = collections.Counter()
+    for sec in ("end_pass", "factor_fetch", "unwind"):
+        whole.update(res["by_section"].get(sec, {}))
+    print("  %-14s %5d  (end_pass + factor_fetch + unwind)" % ("end_pass (all)", whole["total"]))
     if a.rpt:
         for k, r in sorted(res["resources"].items()):
             print("  <%s> %s" % (k, r))
