@@ -110,7 +110,7 @@ HIT_INFO_DTYPE = np.dtype([("I", "<f4", 3), ("material", "<i4"), ("N", "<f4", 3)
 MATERIAL_MISS, MATERIAL_INVALID = -1, -2       # crt_hit_info.material of a miss / of a record whose objIdx or triIdx the scene does not have
 
 # every symbol include/crt_abi.h and include/crt_host.h declare (tests check the library exports all of them)
-ABI_SYMBOLS = ["crt_trace", "crt_trace_device", "crt_build_bvh_device", "crt_get_bvh", "crt_build_kdtree_device", "crt_get_kdtree", "crt_build_grid_device", "crt_get_grid", "crt_update_transforms_device", "crt_sample", "crt_sample_device", "crt_refit_device", "crt_get_hit_info", "crt_get_hit_info_device", "crt_get_sky_color", "crt_get_sky_color_device", "crt_get_light", "crt_upload_blas_accel", "crt_is_occluded", "crt_find_nearest_device", "crt_is_occluded_device", "crt_upload_primitive_scene", "crt_set_render_accel", "crt_upload_alt_accel", "crt_find_nearest_alt", "crt_update_scene", "crt_abi_version", "crt_device_count", "crt_create", "crt_destroy", "crt_last_error", "crt_upload_scene", "crt_set_camera",
+ABI_SYMBOLS = ["crt_render_views", "crt_render_views_device", "crt_trace","crt_trace_device", "crt_build_bvh_device", "crt_get_bvh", "crt_build_kdtree_device", "crt_get_kdtree", "crt_build_grid_device", "crt_get_grid", "crt_update_transforms_device", "crt_sample", "crt_sample_device", "crt_refit_device", "crt_get_hit_info", "crt_get_hit_info_device", "crt_get_sky_color", "crt_get_sky_color_device", "crt_get_light", "crt_upload_blas_accel", "crt_is_occluded", "crt_find_nearest_device", "crt_is_occluded_device", "crt_upload_primitive_scene", "crt_set_render_accel", "crt_upload_alt_accel", "crt_find_nearest_alt", "crt_update_scene", "crt_abi_version", "crt_device_count", "crt_create", "crt_destroy", "crt_last_error", "crt_upload_scene", "crt_set_camera",
                "crt_render", "crt_tick", "crt_reserve", "crt_whitted_tick", "crt_whitted_tick_inspect", "crt_sync", "crt_clear", "crt_read_accumulator", "crt_resolve_screen", "crt_find_nearest", "crt_get_counters",
                "crt_reset_counters", "crt_get_timing", "crt_get_tile_clocks", "crt_bind_accumulator", "crt_accumulator_device_ptr"]
 HOST_SYMBOLS = ["crt_host_bvh_build", "crt_host_scene_bvh_move_and_rebuild", "crt_host_scene_build_bvh_device", "crt_host_scene_build_kdtree_device", "crt_host_kd_build", "crt_host_scene_build_grid_device", "crt_host_grid_build", "crt_host_scene_update_transforms_device", "crt_host_scene_bvh_refit_device", "crt_host_scene_blas_alt_info", "crt_host_scene_blas_alt_copy", "crt_host_primitive_scene_create", "crt_host_primitive_scene_free", "crt_host_primitive_scene_set_time", "crt_host_primitive_scene_desc", "crt_host_primitive_scene_upload", "crt_host_scene_build_alt", "crt_host_scene_upload_alt", "crt_host_scene_alt_info", "crt_host_scene_alt_copy", "crt_host_scene_set_transform", "crt_host_scene_update", "crt_host_math_probe", "crt_host_vertex_dedup", "crt_host_last_error", "crt_host_scene_load", "crt_host_scene_free", "crt_host_scene_upload", "crt_host_scene_kind",
@@ -170,6 +170,19 @@ def _f3(v):
     return (C.c_float * 3)(*[float(x) for x in v])
 
 
+def camera_records(width, height, pairs):
+    """[K, 12] float32 camera records (camPos, topLeft, topRight, bottomLeft: crt_set_camera's arguments, crt_render_views' `cams`) of the reference Camera of a
+    width x height image for each (position, target) pair — crt_host_camera_state, what Context.set_camera_state hands to crt_set_camera."""
+    out = np.zeros((len(pairs), 12), np.float32)
+    for k, (position, target) in enumerate(pairs):
+        a = [(C.c_float * 3)() for _ in range(4)]
+        rc = lib().crt_host_camera_state(int(width), int(height), _f3(position), _f3(target), *a)
+        if rc != 0:
+            raise CrtError(rc, lib().crt_host_last_error().decode())
+        out[k] = [x for v in a for x in v]
+    return out
+
+
 def device_count():
     return int(lib().crt_device_count())
 
@@ -227,6 +240,40 @@ class Context:
 
     def render(self, spp_first, frames, passes=1):
         self._ck(self.L.crt_render(self.h, C.c_uint32(spp_first), C.c_uint32(frames), C.c_uint32(passes)))
+
+    def render_views(self, cameras, spp_first, frames, passes=1, scale=None):
+        """crt_render_views: the frames of K cameras in one job (host buffers, synchronous).  cameras = [K, 12] float32 records (camera_records).  Returns the
+        accumulators [K, H, W, 4] float32 — what set_camera + clear + render(spp_first, frames, passes) + accumulator() leaves per view, on the tiles this context
+        owns; every other pixel is 0 — and, when `scale` is given, (accumulators, pixels [K, H, W] uint32): resolve_screen(scale)'s pixels of them."""
+        cams = np.ascontiguousarray(cameras, np.float32).reshape(-1, 12)
+        k = cams.shape[0]
+        acc = np.zeros((k, self.H, self.W, 4), np.float32)
+        px = np.zeros((k, self.H, self.W), np.uint32) if scale is not None else None
+        self._ck(self.L.crt_render_views(self.h, _p(cams), C.c_uint32(k), C.c_uint32(spp_first), C.c_uint32(frames), C.c_uint32(passes),
+                                         C.c_float(1.0 if scale is None else scale), _p(acc), _p(px) if px is not None else None))
+        return acc if scale is None else (acc, px)
+
+    def render_views_device(self, cams, out, spp_first, frames, passes=1, scale=None, pixels=None, stream=None):
+        """crt_render_views_device: the same job for torch tensors on the context's device, enqueued on `stream` (default torch.cuda.current_stream()) without a host
+        wait.  cams = [K, 12] float32, out = [K, H, W, 4] float32, pixels = None or [K, H, W] int32 (the uint32 bit patterns; needs `scale`), all contiguous; only
+        the pixels of owned tiles are written.  Returns out, or (out, pixels) when pixels is given."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        k = cams.shape[0] if isinstance(cams, torch.Tensor) and cams.dim() == 2 else -1
+        for t, dt, shape, name in ((cams, torch.float32, (k, 12), "cams"), (out, torch.float32, (k, self.H, self.W, 4), "out"), (pixels, torch.int32, (k, self.H, self.W), "pixels")):
+            if t is None and name == "pixels":
+                continue
+            if not isinstance(t, torch.Tensor) or t.device != dev or t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
+                raise ValueError("render_views_device: %s must be a contiguous %s tensor of shape %s on cuda:%d" % (name, dt, shape, self.device))
+        if pixels is not None and scale is None:
+            raise ValueError("render_views_device: pixels need a scale")
+
+        def run(st):
+            self._ck(self.L.crt_render_views_device(self.h, C.c_void_p(cams.data_ptr()), C.c_uint32(k), C.c_uint32(spp_first), C.c_uint32(frames), C.c_uint32(passes),
+                                                    C.c_float(1.0 if scale is None else scale), C.c_void_p(out.data_ptr()),
+                                                    C.c_void_p(pixels.data_ptr()) if pixels is not None else None, C.c_void_p(st.cuda_stream)))
+            return out if pixels is None else (out, pixels)
+        return self._enqueue(stream, run)
 
     def tick(self, spp, passes=1, pixels=True, accumulator=True):
         """crt_tick: one Renderer::Tick at `spp` (crt_render(spp, 1, passes) + read-back + resolve; frames after a run of still Ticks are rendered ahead).

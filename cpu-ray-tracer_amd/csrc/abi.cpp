@@ -126,6 +126,10 @@ struct crt_ctx {
     uint32_t* dQuerySlots = nullptr;
     struct QuerySlot { hipEvent_t done = nullptr; bool pending = false; } qslot[kQuerySlots];
     int qslotNext = 0;
+    // crt_render_views / crt_render_views_device: the sample slab of their launches, scratch of the entries' own (whole windows, grown on demand, kept until
+    // crt_destroy) — the slab pool and crt_tick's held regions are not touched; viewsDone: behind the last call's last accumulate, on that call's stream (the next
+    // call's stream waits for it before it writes the slab again)
+    char* dViewsSlab = nullptr; size_t viewsSlabCap = 0; hipEvent_t viewsDone = nullptr; bool viewsPending = false;
     // crt_refit_device: per BVH the bottom-up plan of refit_box_kernel (device/refit.hip), built from the mirror's references by the first refit of that BVH and
     // freed with the scene; the root's pair + node 0's box come back through `hBack` (pinned) behind the kernels, and `done` is what sceneReady then names
     struct RefitPlan { void* dPlan = nullptr; uint32_t* dLevelOff = nullptr; uint32_t levels = 0, rootCode = 0; bool built = false; };
@@ -453,6 +457,8 @@ void crt_destroy(crt_ctx* c)
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     for (auto& q : c->qslot) if (q.done) { if (q.pending) (void)hipEventSynchronize(q.done); (void)hipEventDestroy(q.done); }   // device queries on callers' streams
     if (c->dQuerySlots) (void)hipFree(c->dQuerySlots);
+    if (c->viewsDone) { if (c->viewsPending) (void)hipEventSynchronize(c->viewsDone); (void)hipEventDestroy(c->viewsDone); }
+    if (c->dViewsSlab) (void)hipFree(c->dViewsSlab);
     if (c->altReady) (void)hipEventDestroy(c->altReady);
     if (c->writeFence) (void)hipEventDestroy(c->writeFence);
     c->refit.release(); c->tlasBuild.release();
@@ -3578,6 +3584,118 @@ int crt_sample_device(crt_ctx* c, int accel, const crt_ray* d_rays, uint32_t* d_
     if (accel != 0 && c->altReady) HIPCK(c, hipStreamWaitEvent(st, c->altReady, 0));     // the accelerators' copies ran on the null stream
     HIPCK(c, launch_sample(c, accel, d_rays, d_seeds, d_rgb, (uint32_t)n, c->dQuerySlots + 16 * k, nullptr, st));
     return end_device_query(c, k, st);
+}
+
+// ---- crt_render_views / crt_render_views_device: the frames of K cameras in one job of K x frames view-frames (device/render_views.h) ----
+// the checks that need no buffer, in the order crt_abi.h lists the refusals
+static int views_check(crt_ctx* c, uint32_t K, uint32_t frames, uint32_t passes, const char* what)
+{
+    if (!c->haveScene && !c->havePrim) return c->fail(CRT_ERR_STATE, "%s before crt_upload_scene", what);
+    if (passes < 1 || passes > 4) return c->fail(CRT_ERR_INVALID, "%s: passes must be 1..4 (the reference's UI range, renderer.cpp:178)", what);
+    if ((uint64_t)K * frames > 0x7fffffffull) return c->fail(CRT_ERR_UNSUPPORTED, "%s: at most 2^31-1 view-frames per call (%u views x %u frames)", what, K, frames);
+    const uint32_t words = sample_stack_words(c, c->renderAccel);
+    if (!sample_lds_fits(words)) return c->fail(CRT_ERR_UNSUPPORTED, "%s: a traversal stack of %u dwords per lane exceeds the kernel's LDS", what, words);
+    return 0;
+}
+
+// windows of 64 view-frames one launch of the job renders: what cfg.maxFramesPerLaunch allows (as crt_render's launches), within 4 GiB of slab, within the scratch —
+// which grows to that here (the one host wait: for the previous call, before its slab is freed) and never beyond half of the free HBM
+static int views_scratch(crt_ctx* c, uint32_t totalWindows, size_t windowBytes, uint32_t* launchWindows)
+{
+    uint32_t wl = c->cfg.maxFramesPerLaunch >= 64 ? (uint32_t)c->cfg.maxFramesPerLaunch / 64u : 1u;
+    const size_t byBytes = ((size_t)4 << 30) / windowBytes;
+    if (wl > byBytes) wl = byBytes ? (uint32_t)byBytes : 1u;
+    if (wl > totalWindows) wl = totalWindows;
+    if ((size_t)wl * windowBytes > c->viewsSlabCap) {
+        if (c->viewsPending) { HIPCK(c, hipEventSynchronize(c->viewsDone)); c->viewsPending = false; }
+        if (c->dViewsSlab) { HIPCK(c, hipFree(c->dViewsSlab)); c->dViewsSlab = nullptr; c->viewsSlabCap = 0; }
+        size_t freeB = 0, totalB = 0;
+        HIPCK(c, hipMemGetInfo(&freeB, &totalB));
+        if (freeB / 2 < windowBytes) return c->fail(CRT_ERR_DEVICE, "not enough free HBM for one 64-view-frame sample slab (%zu bytes needed, %zu free)", windowBytes, freeB);
+        size_t want = (size_t)wl * windowBytes;
+        if (want > freeB / 2) want = freeB / 2 / windowBytes * windowBytes;
+        HIPCK(c, hipMalloc((void**)&c->dViewsSlab, want));
+        c->viewsSlabCap = want;
+    }
+    const size_t fit = c->viewsSlabCap / windowBytes;
+    *launchWindows = wl > fit ? (uint32_t)fit : wl;
+    return 0;
+}
+
+// the job on `st`, after every check: launches of whole windows, each followed by its per-view sums into the caller's images
+static int views_run(crt_ctx* c, const float* dCams, uint32_t K, uint32_t sppFirst, uint32_t frames, uint32_t passes, float scale, float* dRgba, uint32_t* dPixels, hipStream_t st)
+{
+    if (c->tileCount == 0) return 0;
+    const uint32_t total = K * frames, totalWindows = (total + 63u) / 64u;
+    uint32_t wl = 0; int r;
+    if ((r = views_scratch(c, totalWindows, crt_slab_window_bytes(c->tileCount, passes), &wl))) return r;
+    HIPCK(c, ensure_event(&c->viewsDone));
+    if (c->viewsPending) HIPCK(c, hipStreamWaitEvent(st, c->viewsDone, 0));
+    if ((r = wait_scene(c, st))) return r;
+    if (c->renderAccel != 0 && c->altReady) HIPCK(c, hipStreamWaitEvent(st, c->altReady, 0));   // the accelerators' copies ran on the null stream
+    for (uint32_t j0 = 0; j0 < total; j0 += wl * 64u) {
+        const uint32_t nj = (total - j0 < wl * 64u) ? total - j0 : wl * 64u;
+        if (c->havePrim) HIPCK(c, crt_launch_render_views_prim(&c->hScene, &c->prim, dCams, c->dViewsSlab, c->dCounters, c->tileFirst, c->tileStride, c->tileCount, (uint32_t)c->tilesX, sppFirst, frames, passes, j0, nj, st));
+        else HIPCK(c, crt_launch_render_views(c->renderAccel, &c->hScene, &c->alt, c->renderAccel ? &c->blasAlt[c->renderAccel - 1] : nullptr, dCams, c->dViewsSlab, c->dCounters, c->tileFirst,
+                                              c->tileStride, c->tileCount, (uint32_t)c->tilesX, sppFirst, frames, passes, j0, nj, st));
+        HIPCK(c, crt_launch_views_accumulate(c->dViewsSlab, dRgba, dPixels, c->tileFirst, c->tileStride, c->tileCount, (uint32_t)c->tilesX, (uint32_t)c->cfg.width, (uint32_t)c->cfg.height, frames,
+                                             passes, j0, nj, scale, st));
+    }
+    HIPCK(c, hipEventRecord(c->viewsDone, st));
+    c->viewsPending = true;
+    return 0;
+}
+
+int crt_render_views_device(crt_ctx* c, const float* d_cams, uint32_t K, uint32_t spp_first, uint32_t frames, uint32_t passes, float scale, float* d_out_rgba, uint32_t* d_out_pixels, void* stream)
+{
+    if (!c) return CRT_ERR_INVALID;
+    const char* what = "crt_render_views_device";
+    int r;
+    if ((r = views_check(c, K, frames, passes, what))) return r;
+    if (K == 0 || frames == 0) return CRT_OK;
+    const size_t px = (size_t)c->cfg.width * c->cfg.height;
+    if (reinterpret_cast<uintptr_t>(d_out_rgba) & 15u) return c->fail(CRT_ERR_INVALID, "%s: d_out_rgba %p is not 16-byte aligned", what, (void*)d_out_rgba);
+    hipStream_t st = nullptr; int k = 0;
+    if (d_out_pixels) r = device_entry(c, what, {{d_cams, (size_t)K * 48}, {d_out_rgba, K * px * 16}, {d_out_pixels, K * px * 4}}, stream, &st);
+    else r = device_entry(c, what, {{d_cams, (size_t)K * 48}, {d_out_rgba, K * px * 16}}, stream, &st);
+    if (r || (r = take_query_slot(c, &k))) return r;
+    if ((r = views_run(c, d_cams, K, spp_first, frames, passes, scale, d_out_rgba, d_out_pixels, st))) return r;
+    return end_device_query(c, k, st);
+}
+
+int crt_render_views(crt_ctx* c, const float* cams, uint32_t K, uint32_t spp_first, uint32_t frames, uint32_t passes, float scale, float* out_rgba, uint32_t* out_pixels)
+{
+    if (!c) return CRT_ERR_INVALID;
+    int r;
+    if ((r = views_check(c, K, frames, passes, "crt_render_views"))) return r;
+    if (K == 0 || frames == 0) return CRT_OK;
+    if (!cams || !out_rgba) return c->fail(CRT_ERR_INVALID, "crt_render_views: NULL buffer");
+    HIPCK(c, hipSetDevice(c->cfg.device));
+    const size_t W = (size_t)c->cfg.width, px = W * c->cfg.height;
+    const size_t pixOff = K * px * 16, camOff = pixOff + (out_pixels ? K * px * 4 : 0);
+    if ((r = stage(c, camOff + (size_t)K * 48))) return r;
+    float* dRgba = reinterpret_cast<float*>(c->dStage); uint32_t* dPix = out_pixels ? reinterpret_cast<uint32_t*>(c->dStage + pixOff) : nullptr;
+    float* dCams = reinterpret_cast<float*>(c->dStage + camOff);
+    // The call writes the owned tiles' pixels only.  A context that owns every tile of an image whose width the tiling does not truncate writes whole rows — the first
+    // 16 * tilesY of every view — and only those travel back; any other context's staging starts from the caller's images, so every other pixel returns as it came.
+    const bool wholeRows = c->tileFirst == 0 && c->tileStride == 1 && c->tileCount == (uint32_t)(c->tilesX * c->tilesY) && (size_t)c->tilesX * 16u == W;
+    const size_t rowsPx = wholeRows ? W * 16u * (size_t)c->tilesY : px;
+    HIPCK(c, hipMemcpyAsync(dCams, cams, (size_t)K * 48, hipMemcpyHostToDevice, c->stream));
+    if (!wholeRows) {
+        HIPCK(c, hipMemcpyAsync(dRgba, out_rgba, K * px * 16, hipMemcpyHostToDevice, c->stream));
+        if (dPix) HIPCK(c, hipMemcpyAsync(dPix, out_pixels, K * px * 4, hipMemcpyHostToDevice, c->stream));
+    }
+    if ((r = views_run(c, dCams, K, spp_first, frames, passes, scale, dRgba, dPix, c->stream))) return r;
+    if (rowsPx == px) {
+        HIPCK(c, hipMemcpyAsync(out_rgba, dRgba, K * px * 16, hipMemcpyDeviceToHost, c->stream));
+        if (dPix) HIPCK(c, hipMemcpyAsync(out_pixels, dPix, K * px * 4, hipMemcpyDeviceToHost, c->stream));
+    } else for (uint32_t k = 0; k < K; k++) {
+        HIPCK(c, hipMemcpyAsync(out_rgba + k * px * 4, dRgba + k * px * 4, rowsPx * 16, hipMemcpyDeviceToHost, c->stream));
+        if (dPix) HIPCK(c, hipMemcpyAsync(out_pixels + k * px, dPix + k * px, rowsPx * 4, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    c->viewsPending = false;
+    return CRT_OK;
 }
 
 // tools / tests: the lanes a full sample-query launch of this scene and accelerator holds at once (the grid is that many lanes, or fewer when the rays need fewer)

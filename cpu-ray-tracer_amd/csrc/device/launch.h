@@ -66,8 +66,16 @@ hipError_t crt_launch_render_alt(int accel, const crt::Scene* sc, const crt::Alt
     uint32_t tileCount, uint32_t tilesX, uint32_t sppFirst, uint32_t frames, uint32_t passes, hipStream_t stream);
 hipError_t crt_launch_sample_query(int accel, const crt::Scene* sc, const crt::AltAccelDev* acc, const crt::TlasAltDev* tl, const void* rays, uint32_t* seeds, float* rgb, uint32_t n,
     crt::Counters* counters, uint32_t* cursor, uint32_t* residentLanes, hipStream_t stream);
+// crt_render_views (render_views.h): one launch renders the view-frames [jFirst, jFirst + nj) of a job of K x frames (jFirst a multiple of 64) into a slab of
+// ceil(nj / 64) windows, cams = K records of twelve floats; crt_launch_views_accumulate sums that slab per view into the caller's images (outPixels may be nullptr)
+hipError_t crt_launch_render_views(int accel, const crt::Scene* sc, const crt::AltAccelDev* acc, const crt::TlasAltDev* tl, const float* cams, void* slab, crt::Counters* counters,
+    uint32_t tileFirst, uint32_t tileStride, uint32_t tileCount, uint32_t tilesX, uint32_t sppFirst, uint32_t frames, uint32_t passes, uint32_t jFirst, uint32_t nj, hipStream_t stream);
+hipError_t crt_launch_views_accumulate(const void* slab, float* outRgba, uint32_t* outPixels, uint32_t tileFirst, uint32_t tileStride, uint32_t tileCount, uint32_t tilesX, uint32_t W,
+    uint32_t H, uint32_t frames, uint32_t passes, uint32_t jFirst, uint32_t nj, float scale, hipStream_t stream);
 
 // ---- render_prim.hip ----
+hipError_t crt_launch_render_views_prim(const crt::Scene* sc, const crt::PrimDev* p, const float* cams, void* slab, crt::Counters* counters, uint32_t tileFirst, uint32_t tileStride,
+    uint32_t tileCount, uint32_t tilesX, uint32_t sppFirst, uint32_t frames, uint32_t passes, uint32_t jFirst, uint32_t nj, hipStream_t stream);
 hipError_t crt_launch_find_nearest_prim(const crt::PrimDev* p, const void* rays, void* hits, uint32_t n, hipStream_t stream);
 hipError_t crt_launch_render_prim(const crt::Scene* sc, const crt::PrimDev* p, void* slab, crt::Counters* counters, uint32_t tileFirst, uint32_t tileStride, uint32_t tileCount, uint32_t tilesX,
     uint32_t sppFirst, uint32_t frames, uint32_t passes, hipStream_t stream);

@@ -13,6 +13,7 @@
 // Numerics: -ffp-contract=off; fp32 as everywhere, fp64 only inside the torus test.  No MFMA.
 #include "launch.h"
 #include "sample_query.h"
+#include "render_views.h"
 
 namespace crt {
 
@@ -297,6 +298,13 @@ extern "C" hipError_t crt_launch_sample_query_prim(const crt::Scene* sc, const c
                                                    uint32_t* cursor, uint32_t* residentLanes, hipStream_t stream)
 {
     return crt::launch_sample_query(sc, crt::PrimWorld{*p}, rays, seeds, rgb, n, counters, cursor, residentLanes, stream);
+}
+
+// crt_render_views over the eleven primitives: the view-frames [jFirst, jFirst + nj) of a job (render_views.h)
+extern "C" hipError_t crt_launch_render_views_prim(const crt::Scene* sc, const crt::PrimDev* p, const float* cams, void* slab, crt::Counters* counters, uint32_t tileFirst, uint32_t tileStride,
+                                                   uint32_t tileCount, uint32_t tilesX, uint32_t sppFirst, uint32_t frames, uint32_t passes, uint32_t jFirst, uint32_t nj, hipStream_t stream)
+{
+    return crt::launch_render_views(sc, crt::PrimWorld{*p}, cams, slab, counters, tileFirst, tileStride, tileCount, tilesX, sppFirst, frames, passes, jFirst, nj, stream);
 }
 
 // diagnostics (crt_debug_device_probe, abi.cpp; record layouts in probe.hip): the torus' fp64 building blocks, one element per thread.  The functions are

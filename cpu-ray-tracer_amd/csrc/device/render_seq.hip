@@ -6,13 +6,15 @@
 //   TlasKdWorld      TLASFileScene::FindNearest built with TLAS_USE_KDTree (TLASKDTree over BLASKDTree: tlas_alt_intersect<1>)
 //   TlasGridWorld    ... with TLAS_USE_Grid (TLASGrid over BLASGrid: tlas_alt_intersect<2>)
 // The issue-bound renders of these scenes are render_pool_kernel / render_tiles_kernel; this form exists for the probe and for parity with the alternative
-// accelerators (crt_set_render_accel).  The same worlds serve sample_query_kernel (sample_query.h): Renderer::Sample for a caller's rays and seeds.
+// accelerators (crt_set_render_accel).  The same worlds serve sample_query_kernel (sample_query.h): Renderer::Sample for a caller's rays and seeds, and
+// render_views_kernel (render_views.h): the frames of many cameras in one launch (crt_render_views), whose per-view sums views_accumulate_kernel below forms.
 //
 // Numerics: -ffp-contract=off, IEEE + - * / sqrt only (dev_common.h).  No MFMA: pointer chasing + slab / Möller–Trumbore tests.
 #include "alt_common.h"
 #include "file_surface.h"
 #include "launch.h"
 #include "sample_query.h"
+#include "render_views.h"
 
 namespace crt {
 
@@ -69,6 +71,35 @@ struct TlasAltWorld : FileSurface<1> {
 using TlasKdWorld = TlasAltWorld<1>;
 using TlasGridWorld = TlasAltWorld<2>;
 
+// views_accumulate_kernel: for every view with view-frames in [jFirst, jFirst + nj), owned tile and pixel, the view's samples of this launch added channel by channel in
+// frame order, then pass order — accumulate_kernel's chain after crt_clear.  Block = (owned tile, view of the launch), views of a tile side by side (they share the slab's lines), thread = pixel (v * 16 + u, the slab's order).  A
+// view whose first frame lies in this launch starts from +0; one that began in an earlier launch continues from what that launch left in out_rgba.  The sum follows the
+// view across the tile blocks of the windows it straddles (slab_position with the launch's view-frame as the frame).  w: +0 plus 0.0f per launch, so +0.  The screen
+// pixel (rgb8_pixel) is written with the view's last frame.  Every addition of a channel happens in one thread, in order; no atomics.
+__global__ __launch_bounds__(256) void views_accumulate_kernel(const char* __restrict__ slab, float4* __restrict__ outRgba, uint32_t* __restrict__ outPixels, uint32_t tileFirst,
+                                                                uint32_t tileStride, uint32_t tileCount, uint32_t tilesX, uint32_t W, uint32_t H, uint32_t frames, uint32_t passes,
+                                                                uint32_t jFirst, uint32_t nj, uint32_t nViews, float scale)
+{
+    const uint32_t viewFirst = jFirst / frames, view = viewFirst + blockIdx.x % nViews, tl = blockIdx.x / nViews, pix = threadIdx.x;
+    if (tl >= tileCount) return;
+    const unsigned long long vBegin = (unsigned long long)view * frames, vEnd = vBegin + frames, jEnd = (unsigned long long)jFirst + nj;
+    const uint32_t ja = (uint32_t)(vBegin > jFirst ? vBegin : jFirst), jb = (uint32_t)(vEnd < jEnd ? vEnd : jEnd);     // this view's view-frames of the launch
+    if (ja >= jb) return;
+    const uint32_t tile = tileFirst + tl * tileStride;
+    const uint32_t x0 = (tile % tilesX) * 16u, y0 = (tile / tilesX) * 16u;
+    const size_t i = (size_t)view * W * H + (x0 + (pix & 15u)) + (size_t)(y0 + (pix >> 4)) * W;
+    float4 a = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (ja != vBegin) a = outRgba[i];
+    const uint32_t rowLen = 64u * passes;
+    for (uint32_t j = ja; j < jb; j++) {
+        const size_t at = slab_position(j - jFirst, tileCount, tl, pix, rowLen, passes, 0u);
+        for (uint32_t p = 0; p < passes; p++) { const Sample3 t = load_sample(slab, at + p * kSampleBytes); a.x += t.x; a.y += t.y; a.z += t.z; }
+    }
+    a.w += 0.0f;
+    outRgba[i] = a;
+    if (outPixels && jb == vEnd) outPixels[i] = rgb8_pixel(a.x, a.y, a.z, scale);
+}
+
 } // namespace crt
 
 // the latency mode's cost probe: kProbeWaves wavefronts per owned tile, 64 paths each, step counts summed into tileCost[tile]
@@ -124,4 +155,36 @@ extern "C" hipError_t crt_launch_sample_query(int accel, const crt::Scene* sc, c
     }
     if (accel == 1) return crt::launch_sample_query(sc, crt::KdWorld{{}, *acc}, rays, seeds, rgb, n, counters, cursor, residentLanes, stream);
     return crt::launch_sample_query(sc, crt::GridWorld{{}, *acc}, rays, seeds, rgb, n, counters, cursor, residentLanes, stream);
+}
+
+// crt_render_views: the view-frames [jFirst, jFirst + nj) of a job (render_views.h) through accel 0 = the scene's BVH / TLAS, 1 / 2 = the KD-tree / grid (FileScene's
+// `acc`, or a two-level scene's BLAS set `tl`).  A world whose LDS columns exceed 64 KB per workgroup is refused (hipErrorInvalidValue), as crt_launch_render_alt does.
+extern "C" hipError_t crt_launch_render_views(int accel, const crt::Scene* sc, const crt::AltAccelDev* acc, const crt::TlasAltDev* tl, const float* cams, void* slab, crt::Counters* counters,
+                                              uint32_t tileFirst, uint32_t tileStride, uint32_t tileCount, uint32_t tilesX, uint32_t sppFirst, uint32_t frames, uint32_t passes, uint32_t jFirst,
+                                              uint32_t nj, hipStream_t stream)
+{
+    if (accel < 0 || accel > 2) return hipErrorInvalidValue;
+    if (accel == 0) {
+        if (sc->kind == 0) return crt::launch_render_views(sc, crt::BvhWorld<0>{}, cams, slab, counters, tileFirst, tileStride, tileCount, tilesX, sppFirst, frames, passes, jFirst, nj, stream);
+        return crt::launch_render_views(sc, crt::BvhWorld<1>{}, cams, slab, counters, tileFirst, tileStride, tileCount, tilesX, sppFirst, frames, passes, jFirst, nj, stream);
+    }
+    if (sc->kind != 0) {
+        if (accel == 1) return crt::launch_render_views(sc, crt::TlasKdWorld{{}, *tl}, cams, slab, counters, tileFirst, tileStride, tileCount, tilesX, sppFirst, frames, passes, jFirst, nj, stream);
+        return crt::launch_render_views(sc, crt::TlasGridWorld{{}, *tl}, cams, slab, counters, tileFirst, tileStride, tileCount, tilesX, sppFirst, frames, passes, jFirst, nj, stream);
+    }
+    if (accel == 1) return crt::launch_render_views(sc, crt::KdWorld{{}, *acc}, cams, slab, counters, tileFirst, tileStride, tileCount, tilesX, sppFirst, frames, passes, jFirst, nj, stream);
+    return crt::launch_render_views(sc, crt::GridWorld{{}, *acc}, cams, slab, counters, tileFirst, tileStride, tileCount, tilesX, sppFirst, frames, passes, jFirst, nj, stream);
+}
+
+// ... and the per-view sums of that launch's slab into the caller's images (views_accumulate_kernel)
+extern "C" hipError_t crt_launch_views_accumulate(const void* slab, float* outRgba, uint32_t* outPixels, uint32_t tileFirst, uint32_t tileStride, uint32_t tileCount, uint32_t tilesX, uint32_t W,
+                                                  uint32_t H, uint32_t frames, uint32_t passes, uint32_t jFirst, uint32_t nj, float scale, hipStream_t stream)
+{
+    if (tileCount == 0 || nj == 0) return hipSuccess;
+    if (frames == 0) return hipErrorInvalidValue;
+    const uint32_t nViews = (uint32_t)(((unsigned long long)jFirst + nj - 1u) / frames) - jFirst / frames + 1u;
+    if ((unsigned long long)nViews * tileCount > 0x7fffffffull) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(crt::views_accumulate_kernel, dim3(nViews * tileCount), dim3(256), 0, stream, (const char*)slab, (float4*)outRgba, outPixels, tileFirst, tileStride, tileCount, tilesX, W, H,
+                       frames, passes, jFirst, nj, nViews, scale);
+    return hipGetLastError();
 }

@@ -540,6 +540,36 @@ int  crt_trace(crt_ctx* ctx, int accel, const crt_ray* rays, float* rgb /* 3 * n
 int  crt_trace_device(crt_ctx* ctx, int accel, const crt_ray* d_rays, float* d_rgb /* 3 * n */, int32_t* d_traversed /* n or NULL */, int32_t* d_tested /* n or NULL */,
                       size_t n, void* stream);
 
+/* The frames of MANY cameras in one render job: a turntable, a replayed camera path, an offline animation, the views of a training set — whenever the cameras are
+ * known before the frames are needed.  A one-frame crt_render runs a tile's serial RNG stream in one lane of a wavefront; here the other 63 lanes carry the same
+ * tile for other cameras or other frames (device/render_views.h).  ABI version 3 still: additions, detected by symbol.
+ * cams: K records of 12 floats — camPos, topLeft, topRight, bottomLeft, exactly crt_set_camera's arguments.  For every view k and every pixel of a tile this
+ * context owns, out_rgba[k] (W * H float4) is bit for bit what crt_set_camera(cams[k]); crt_clear; crt_render(spp_first, frames, passes); crt_read_accumulator
+ * leaves there, w = 0 included, and out_pixels[k] (W * H, may be NULL) is bit for bit crt_resolve_screen(scale, ..)'s pixel of that accumulator.  No other pixel
+ * of the outputs is touched: not the tiles the context does not own, not the rows and columns the 16-pixel tiling truncates.  The energy is not offered.
+ * The job renders through whatever crt_set_render_accel has selected — the BVH / TLAS, the KD-tree or grid (a two-level scene's BLAS sets included) — or over the
+ * PrimitiveScene, with crt_config's depthLimit and tile ownership.
+ * It does NOT change the context's camera, accumulator (owned or bound), tile order, tuner or planner tables.  crt_tick: the frames rendered ahead SURVIVE — the
+ * job's samples live in scratch of the entries' own (whole windows of 64 view-frames, at most cfg.maxFramesPerLaunch / 64 of them and 4 GiB per launch, kept
+ * until crt_destroy), not in the slab pool — so a crt_tick sequence around the call returns the pixels it returns without it.
+ * Counters: crt_counters.rays, primary and mesh_hits grow as they would for the K renders; the collectStats detail counters and tile clocks are not fed.
+ * crt_render_views_device: d_cams (48 K bytes), d_out_rgba (16 K W H, 16-byte aligned) and, where not NULL, d_out_pixels (4 K W H) are device pointers on
+ * cfg.device, checked as crt_sample_device checks its buffers; `stream` a hipStream_t of that device or NULL; no host wait (except to grow the scratch).  The
+ * launches are readers under the scene-write protocol: a later crt_update_scene, refit or device rebuild is ordered behind them, a freeing call waits for them.
+ * crt_render_views: host pointers, synchronous, through staging the context keeps.
+ * Refusals (nothing is modified, crt_last_error says why): no scene CRT_ERR_STATE; passes outside 1..4 CRT_ERR_INVALID (as crt_render); K * frames > 2^31-1
+ * CRT_ERR_UNSUPPORTED; a traversal stack beyond the sequential kernels' LDS bound CRT_ERR_UNSUPPORTED (crt_set_render_accel's rule); NULL, misaligned, host or
+ * other-device memory, a stream of another device CRT_ERR_INVALID; a failed device allocation CRT_ERR_DEVICE.  K == 0 or frames == 0 is a no-op after the checks
+ * that need no buffer.
+ * When to use it (one MI355X, 1280x720, profiles/render_views.json): with one frame per view, 64 views take 85 ms (bunny) / 232 ms (tlas_scene.xml) against 916 /
+ * 1 982 ms for the loop crt_set_camera, crt_clear, crt_render(1, 1, 1), crt_sync — 10.7x / 8.6x.  The job costs about 0.26 / 0.39 ms per view-frame however they are
+ * split into views, while the loop's renders get cheaper per frame as they grow: at 64 frames per view the entry is still 1.36x / 1.87x faster, at 128 1.05x / 1.57x,
+ * at 256 the loop wins (0.54x / 0.80x: its renders are then jobs of the pool kernel).  So: up to 128 frames per view call this entry; from 256 on, loop crt_render. */
+int  crt_render_views(crt_ctx* ctx, const float* cams, uint32_t K, uint32_t spp_first, uint32_t frames, uint32_t passes, float scale,
+                      float* out_rgba /* K * W*H float4 */, uint32_t* out_pixels /* K * W*H or NULL */);                                    /* host pointers, synchronous */
+int  crt_render_views_device(crt_ctx* ctx, const float* d_cams, uint32_t K, uint32_t spp_first, uint32_t frames, uint32_t passes, float scale,
+                             float* d_out_rgba, uint32_t* d_out_pixels /* or NULL */, void* stream);                                          /* device pointers, no host wait */
+
 /* ---- PrimitiveScene (second half): infra/scene/primitive_scene.cpp — the reference's hard-coded demo room (six walls, swinging light quad,
  * bouncing mirror ball, "rounded corners" sphere, spinning glass cube, glass torus; template/primitives.h Sphere :31, Cube :187, Quad :321, Torus :380; the
  * SPEEDTRIX / single-light configuration its headers select).  The binding passes the scene as its constructor + SetTime(t) leave it: the members below.
