@@ -737,6 +737,19 @@ class Context:
             raise CrtError(-3, "pool_lds: no scene uploaded")
         return b.value, lim.value, bits.value
 
+    def arith_forms(self, what, records=None, n=None, seed=1):
+        """crt_debug_arith_forms: a short arithmetic form of dev_common.h against the form it stands for, on the device (device/probe.hip probe_arith_kernel lists
+        `what` and the record layouts).  records: uint32 [k, words] read first (sweeps: the 4-word header), then generated records up to n in all.  Returns
+        (differing records, index of the lowest or None, its operands [3], old result [2], new result [2]) — the last three as uint32 bit patterns."""
+        f = self.L.crt_debug_arith_forms
+        f.restype = C.c_int
+        f.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
+        r = None if records is None else np.ascontiguousarray(records, np.uint32)
+        n_in = 0 if (r is None or what == 3) else len(r)
+        out = np.zeros(9, np.uint32)
+        self._ck(f(self.h, int(what), None if r is None else _p(r), n_in, n_in if n is None else int(n), int(seed), _p(out)))
+        return int(out[0]), (None if out[0] == 0 else int(out[1])), out[2:5].copy(), out[5:7].copy(), out[7:9].copy()
+
     def tile_classes(self, ex=False):
         """crt_debug_tile_classes: the pool kernel's tile classes as the device holds them, one byte per owned tile (TILE_NO_LIGHT | TILE_NO_FLOOR | TILE_NO_TREE);
         ex: crt_debug_tile_classes_ex, the whole byte (TILE_FLOOR_SURE as well)"""

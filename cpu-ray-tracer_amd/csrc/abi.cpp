@@ -3979,6 +3979,34 @@ static int device_probe(crt_ctx* c, int op, const void* in, void* out, uint32_t 
 extern "C" int crt_debug_device_probe(crt_ctx* c, int op, const void* in, void* out, uint32_t n) { return (op > 16) ? CRT_ERR_INVALID : device_probe(c, op, in, out, n); }
 // tests: op 8's lookup through sky_angles, the guarded form the render kernels and the sky query call (probe.hip op 17; records as op 8's)
 extern "C" int crt_debug_sky_probe(crt_ctx* c, const void* in, void* out, uint32_t n) { return device_probe(c, 17, in, out, n); }
+// tests: the short arithmetic forms of dev_common.h against the forms they stand for, side by side on the device (device/probe.hip probe_arith_kernel: `what`, the
+// record layouts and the generated records are listed there).  in: nIn records (sweeps: their 4-word header); n: records in all, the ones behind nIn generated from
+// `seed`.  out[9] = {differing records, the lowest of them (0xffffffff: none), its operands [3], old result [2], new result [2]}
+extern "C" int crt_debug_arith_forms(crt_ctx* c, int what, const void* in, uint32_t nIn, uint32_t n, uint32_t seed, uint32_t* out)
+{
+    static const uint8_t words[4] = {3, 2, 3, 0};
+    if (!c || !out || what < 0 || what > 3 || nIn > n || (nIn && !in) || (what == 3 && !in)) return CRT_ERR_INVALID;
+    for (int k = 0; k < 9; k++) out[k] = 0u;
+    out[1] = 0xffffffffu;
+    if (n == 0) return CRT_OK;
+    const size_t inBytes = what == 3 ? 16 : (size_t)nIn * words[what] * 4;
+    HIPCK(c, hipSetDevice(c->cfg.device));
+    char* d = nullptr;
+    HIPCK(c, hipMalloc((void**)&d, 64 + inBytes));
+    hipError_t e = hipMemcpyAsync(d, out, 36, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess && inBytes) e = hipMemcpyAsync(d + 64, in, inBytes, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = crt_launch_probe_arith(what, d + 64, nIn, n, seed, 0xffffffffu, d, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(out, d, 8, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess && out[0] != 0u) {                                       // the lowest differing record once more, for its operands and results
+        e = crt_launch_probe_arith(what, d + 64, nIn, n, seed, out[1], d, c->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(out + 2, d + 8, 28, hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    }
+    (void)hipFree(d);
+    HIPCK(c, e);
+    return CRT_OK;
+}
 
 // tests (no GPU needed): the planner's decision for given tile costs — plan_job on a context that holds nothing but the costs.  table[] receives the block
 // descriptors (tile | first frame << 16 | log2(lanes) << 22 | window << 25), order[] the dispatch order, *head the number of leading tiles of it that go to the table

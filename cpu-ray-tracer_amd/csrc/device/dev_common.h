@@ -53,6 +53,23 @@ __device__ __forceinline__ f3 rcp_exact3(f3 v)
     if (__builtin_expect(__builtin_amdgcn_ballot_w64(!okay) != 0, 0)) r = mk3(1.0f / v.x, 1.0f / v.y, 1.0f / v.z);
     return r;
 }
+// a / b without the eleven-instruction IEEE sequence, for TAME operands: magnitude in [2^-40, 2^40] (so no zero, denormal, infinity or NaN).
+//   div_by_rcp(a, b, r), r = RN(1 / b) (rcp_nr's result, or the negation of -b's): q0 = a * r, e = fma(-b, q0, a) — exact —, q = fma(e, r, q0) is the correctly
+//   rounded quotient whenever nothing over- or underflows or is denormal on the way (Markstein).  With tame a and b: |q| in [2^-80, 2^80], |e| >= 2^-40 * 2^-48 or 0.
+//   Three instructions.  div_short(a, b): the same with a reciprocal of its own, six.
+// PRE: a and b are tame on every active lane.  The caller establishes that for the whole wave at once, from the bit patterns (tame_bits: one unsigned compare of
+// the pattern without its sign; a NaN fails it), and a wave with any other operand — a zero numerator among them, so the sign of a zero quotient is never decided
+// here — takes the IEEE division (a scalar branch, as rcp_exact's).  div_guarded is div_short with that guard for its two operands.
+constexpr uint32_t kTameLo = 0x2b800000u, kTameHi = 0x53800000u;                 // 2^-40, 2^40 as bit patterns
+__device__ __forceinline__ bool tame_bits(float x) { return (__float_as_uint(x) & 0x7fffffffu) - kTameLo <= kTameHi - kTameLo; }
+__device__ __forceinline__ float div_by_rcp(float a, float b, float r) { const float q0 = a * r; const float e = __builtin_fmaf(-b, q0, a); return __builtin_fmaf(e, r, q0); }
+__device__ __forceinline__ float div_short(float a, float b) { return div_by_rcp(a, b, rcp_nr(b)); }
+__device__ __forceinline__ float div_guarded(float a, float b)
+{
+    float q = div_short(a, b);
+    if (__builtin_expect(__builtin_amdgcn_ballot_w64(!(tame_bits(a) && tame_bits(b))) != 0, 0)) q = a / b;
+    return q;
+}
 // sqrtf(x) in nine instructions instead of the twenty-one issue slots of the compiler's IEEE expansion.  That expansion is: scale x by 2^32 if x < 2^-96; s = v_sqrt_f32
 // (1 ulp); the rounding decision between s and its two neighbours by the signs of the residuals fma(-(s - 1 ulp), s, x) <= 0 and fma(-(s + 1 ulp), s, x) > 0; scale back;
 // return x itself for +-0 and +inf.  For 2^-96 <= x < inf neither scaling nor the zero / infinity select does anything, and what is left is the sequence below, operation
@@ -109,13 +126,16 @@ static __device__ float crt_expf(float x)
 }
 // The three range reductions of atan share ONE division site and the two of acos ONE square root: -(1/x) == (-1)/x,
 // x/1 == x and 1+x == 1-|x| (x < 0) are exact identities of IEEE arithmetic, so the values are those of the branchy form.
+// (SHORT: the one division as div_short.  PRE: x is tame.  Then num and den are: -1 and x; x - 1 — a multiple of 2^-25 below 2, or +0 for x == 1, which
+// the caller keeps out — and x + 1 in (1.4, 3.5); x and 1.  All tame.)
+template <bool SHORT = false>
 __device__ __forceinline__ float crt_atan_pos(float x)
 {
     const bool big = x > 2.414213562373095f, mid = x > 0.4142135623730950f;
     const float y0 = big ? 1.5707963267948966f : (mid ? 0.7853981633974483f : 0.0f);
     const float num = big ? -1.0f : (mid ? x - 1.0f : x);
     const float den = big ? x : (mid ? x + 1.0f : 1.0f);
-    const float t = num / den;
+    const float t = SHORT ? div_short(num, den) : num / den;
     float z = t * t;
     float p = 8.05374449538e-2f;
     p = p * z - 1.38776856032e-1f;
@@ -159,15 +179,17 @@ __device__ __forceinline__ float crt_acosf(float x)
 }
 // The two functions without the selects of their special cases, for operands that have none.  Every other expression is the one above, in the same order, so for
 // such operands the bits are those of crt_atan2f / crt_acosf.  Callers establish the precondition for a whole wave at once (sky_angles).
-//   crt_atan2f_plain(y, x), x and y finite and non-zero.  Left out:  `ax == inf && ay == inf` (no operand is infinite);  `ax == 0` and `ay == 0` (no operand is a
+//   crt_atan2f_plain(y, x), x and y tame (dev_common.h div_by_rcp: finite, non-zero, normal) and of different magnitude.  Left out:  `ax == inf && ay == inf` (no operand is infinite);  `ax == 0` and `ay == 0` (no operand is a
 //   zero: x == -0 in particular must stay out, the general expression gives pi - pi/2 there and the select pi/2);  the NaN return (no operand is a NaN).  A
 //   quotient ay / ax that overflows to inf or underflows to 0 is not a special case of crt_atan2f either: crt_atan_pos takes it as it is, here as there.
 //   crt_acosf_plain(x), |x| <= 1.  Left out:  the NaN of |x| > 1 and the NaN return (|x| <= 1 is false for a NaN).
+//   Both divisions (ay / ax here, crt_atan_pos's) are div_short.  PRE, beyond the above: x and y are tame and |x| != |y|.  Then ay / ax lies in [2^-80, 2^80] — wider than
+//   tame — so crt_atan_pos's own operands are: big, -1 and a den up to 2^80: q0 = -r, e and q stay normal (|q| >= 2^-80); mid and small: as stated there.
 __device__ __forceinline__ float crt_atan2f_plain(float y, float x)
 {
     const uint32_t sy = asu(y) & 0x80000000u, sx = asu(x) & 0x80000000u;
     const float ax = __builtin_fabsf(x), ay = __builtin_fabsf(y);
-    const float a = crt_atan_pos(ay / ax);
+    const float a = crt_atan_pos<true>(div_short(ay, ax));
     const float r = sx ? (CRT_PI - a) : a;
     return asf(asu(r) | sy);
 }
@@ -184,9 +206,12 @@ __device__ __forceinline__ float crt_acosf_plain(float x)
 __device__ __forceinline__ void sky_angles(f3 D, float& phi, float& theta)
 {
     const float y = -D.z, x = D.x, c = -D.y;
-    // a zero, an infinity or a NaN, as ONE unsigned compare of the bit pattern: (bits << 1) - 1 drops the sign and wraps +-0 to the top, so everything from inf
-    // (0xff000000 - 1) upwards is special.  (The compare builtin returns the lane mask itself; the ballot of a v_cmp_class result goes through a VGPR.)
-    const uint64_t special = __builtin_amdgcn_uicmp((asu(x) << 1) - 1u, 0xfeffffffu, 35 /* unsigned >= */) | __builtin_amdgcn_uicmp((asu(y) << 1) - 1u, 0xfeffffffu, 35)
+    // anything but a tame operand (a zero, a denormal, below 2^-40, an infinity, a NaN), as ONE unsigned compare of the bit pattern: bits << 1 drops the sign, and
+    // minus the lower bound everything outside [2^-40, 2^40] lies above the range's width (what is below the bound wraps to the top).  |x| == |y| joins them: the
+    // quotient 1 makes crt_atan_pos's numerator x - 1 a zero, which the short division does not take.  (The compare builtin returns the lane mask itself; the ballot
+    // of a v_cmp_class result goes through a VGPR.)
+    const uint64_t special = __builtin_amdgcn_uicmp((asu(x) << 1) - (kTameLo << 1), (kTameHi - kTameLo) << 1, 34 /* unsigned > */)
+                           | __builtin_amdgcn_uicmp((asu(y) << 1) - (kTameLo << 1), (kTameHi - kTameLo) << 1, 34) | __builtin_amdgcn_uicmp(asu(x) << 1, asu(y) << 1, 32 /* == */)
                            | __builtin_amdgcn_ballot_w64(!(__builtin_fabsf(c) <= 1.0f));
     if (__builtin_expect(special == 0, 1)) { phi = crt_atan2f_plain(y, x) + CRT_PI; theta = crt_acosf_plain(c); return; }
     phi = crt_atan2f(y, x) + CRT_PI; theta = crt_acosf(c);
@@ -270,6 +295,32 @@ __device__ __forceinline__ float box_fast_rel(f3 lo, f3 hi, f3 rD, float tray)
 __device__ __forceinline__ float box_fast(rec4 lo, rec4 hi, f3 O, f3 rD, float tray)
 {
     return box_fast_rel(mk3(lo.x - O.x, lo.y - O.y, lo.z - O.z), mk3(hi.x - O.x, hi.y - O.y, hi.z - O.z), rD, tray);
+}
+
+// The accept predicate of the fast form in four instructions instead of six (three v_cmp, two s_and_b64, one v_cndmask: the compares and the mask logic issue at
+// half the rate of v_min / v_max).  With dmin = the smallest denormal and pred(tray) = the next float below tray (tray_pred: bit pattern - 1)
+//     tmax >= tmin && tmin < tray && tmax > 0    <=>    max(tmin, dmin) <= min(tmax, pred(tray))
+// because  tmax > 0 <=> tmax >= dmin  (the kernels keep denormals: float_denorm_mode_32 = 3),  tmin < tray <=> tmin <= pred(tray)  (tray > 0),  and
+// dmin <= pred(tray).  PRE: no operand is a NaN (the fast form's own precondition: finite rD) and tray's bit pattern, as a signed integer, is >= 2 (tray_tame), i.e.
+// tray is a positive float above dmin, +inf included.  For tray = dmin the predecessor is +0 and a box with tmin <= 0 < tmax would be refused where the
+// conjunction accepts tmin < dmin; a zero or a negative tray has no predecessor of this form at all.  Such a lane goes with the lanes whose rD is not finite: to
+// box_exact.  (The integer inline constant 1 IS dmin's bit pattern: floating-point instructions take an integer constant's bits as they are.)
+__device__ __forceinline__ float tray_pred(float tray) { return asf(asu(tray) - 1u); }
+__device__ __forceinline__ bool tray_tame(float tray) { return (int32_t)asu(tray) >= 2; }
+__device__ __forceinline__ float vmax_dmin(float a) { float r; asm("v_max_f32 %0, 1, %1" : "=v"(r) : "v"(a)); return r; }
+__device__ __forceinline__ float slab_accept(float tmin, float tmax, float trayPred) { return (vmax_dmin(tmin) <= vmin(tmax, trayPred)) ? tmin : 1e30f; }
+__device__ __forceinline__ float box_short_rel(f3 lo, f3 hi, f3 rD, float trayPred)
+{
+    float tx1 = lo.x * rD.x, tx2 = hi.x * rD.x;
+    float ty1 = lo.y * rD.y, ty2 = hi.y * rD.y;
+    float tz1 = lo.z * rD.z, tz2 = hi.z * rD.z;
+    float tmin = vmax3(vmin(tx1, tx2), vmin(ty1, ty2), vmin(tz1, tz2));
+    float tmax = vmin3(vmax(tx1, tx2), vmax(ty1, ty2), vmax(tz1, tz2));
+    return slab_accept(tmin, tmax, trayPred);
+}
+__device__ __forceinline__ float box_short(rec4 lo, rec4 hi, f3 O, f3 rD, float trayPred)
+{
+    return box_short_rel(mk3(lo.x - O.x, lo.y - O.y, lo.z - O.z), mk3(hi.x - O.x, hi.y - O.y, hi.z - O.z), rD, trayPred);
 }
 
 // Möller–Trumbore on a fetched LeafTri {a = v0|shadeIdx, b = e1|objIdx, c = e2|remain}, infra/bvh.cpp:203-222

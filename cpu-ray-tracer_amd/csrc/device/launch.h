@@ -94,6 +94,7 @@ hipError_t crt_launch_sky_color(const crt::Scene* sc, const void* rays, float* r
 hipError_t crt_launch_refit(char* geom, uint32_t leafOff, uint32_t pairBase, uint32_t triBase, uint32_t triCount, const float* pos, const void* plan, const uint32_t* levelOff, uint32_t levels,
     uint32_t rootCode, float* out, hipStream_t stream);
 hipError_t crt_launch_probe_f32(int op, const void* in, void* out, uint32_t n, hipStream_t stream);
+hipError_t crt_launch_probe_arith(int what, const void* in, uint32_t nIn, uint32_t n, uint32_t seed, uint32_t dumpAt, void* out, hipStream_t stream);
 
 // ---- grid_build.hip ----
 uint32_t crt_grid_build_blocks(int device);

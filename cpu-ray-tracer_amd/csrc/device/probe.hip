@@ -27,6 +27,17 @@
 //   15  DIV64     a, b (doubles)                                 4    a / b (double)                                                     2
 //   16  F64TOF32  x (double)                                     2    (float)x                                                           1
 //   17  SKYFAST   D.xyz, w (i32), h (i32)                        5    as op 8, through sky_angles: the guarded lookup as the render kernels call it  3
+//
+// probe_arith_kernel (crt_debug_arith_forms; tests/test_gpu_arith_forms.py): the short arithmetic forms of dev_common.h next to the forms they stand for, on the
+// device, one record per thread; counted are the records whose two results differ in a bit (two NaNs count as equal), and a second launch writes the operands
+// and both results of the lowest such record.  Records [0, nIn) are read from `in`; the records behind them are generated from (seed, index).
+//   what  name   record (words)        old form                                         new form                                        generated records
+//    0    PRED   tmin, tmax, tray  3   tmax >= tmin && tmin < tray && tmax > 0          slab_accept(tmin, tmax, tray_pred(tray)) where  any non-NaN tmin / tmax, any positive tray, three
+//                                       ? tmin : 1e30f                                  tray_tame(tray) (per lane), else the old form   in four with tmax and / or tray next to tmin
+//    1    DIV    a, b              2   a / b                                            div_guarded(a, b): div_short = div_by_rcp with  tame a and b: every exponent -40 .. 39, any mantissa
+//                                                                                        rcp_nr(b), behind the tame-operand guard
+//    2    SKY    D.xyz             3   crt_atan2f(-D.z, D.x) + pi, crt_acosf(-D.y)      sky_angles(D)                                   normalised random directions
+//    3    DIV sweep:                   in = {b's sign and exponent bits, three numerators}; record i is (numerator i >> 23, b = bits | (i & 0x7fffff)), 3 * 2^23 records
 #include "dev_common.h"
 #include "launch.h"
 
@@ -104,7 +115,69 @@ __global__ __launch_bounds__(256) void probe_f32_kernel(int op, const uint32_t* 
     }
 }
 
+__device__ __forceinline__ uint32_t probe_hash(uint32_t seed, uint32_t i, uint32_t k) { return wang_hash(wang_hash(i * 0x9e3779b9u + seed) + k * 0x85ebca6bu); }
+__device__ __forceinline__ uint32_t probe_no_nan(uint32_t u) { return ((u & 0x7fffffffu) > 0x7f800000u) ? (u & 0xff800000u) : u; }     // a NaN becomes the infinity of its sign
+__device__ __forceinline__ uint32_t probe_tame(uint32_t h) { return (h & 0x807fffffu) | ((87u + ((h >> 23) & 0xffu) % 80u) << 23); }     // 2^-40 <= |x| < 2^40
+__device__ __forceinline__ bool probe_same(float a, float b) { return asu(a) == asu(b) || (a != a && b != b); }
+
+__global__ __launch_bounds__(256) void probe_arith_kernel(int what, const uint32_t* __restrict__ in, uint32_t nIn, uint32_t n, uint32_t seed, uint32_t dumpAt, uint32_t* __restrict__ out)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t j = i - nIn;                                                  // index among the generated records
+    uint32_t op[3] = {0u, 0u, 0u};
+    float was[2] = {0.0f, 0.0f}, is[2] = {0.0f, 0.0f};
+    switch (what) {
+    case 0: {
+        if (i < nIn) { op[0] = in[3 * (size_t)i]; op[1] = in[3 * (size_t)i + 1]; op[2] = in[3 * (size_t)i + 2]; }
+        else {
+            op[0] = probe_no_nan(probe_hash(seed, j, 1u)); op[1] = probe_no_nan(probe_hash(seed, j, 2u)); op[2] = probe_no_nan(probe_hash(seed, j, 3u)) & 0x7fffffffu;
+            if (j & 1u) op[1] = probe_no_nan(op[0] + probe_hash(seed, j, 4u) % 5u - 2u);
+            if (j & 2u) op[2] = probe_no_nan((op[0] & 0x7fffffffu) + probe_hash(seed, j, 5u) % 5u - 2u) & 0x7fffffffu;
+        }
+        const float tmin = asf(op[0]), tmax = asf(op[1]), tray = asf(op[2]);
+        was[0] = (tmax >= tmin && tmin < tray && tmax > 0) ? tmin : 1e30f;
+        is[0] = tray_tame(tray) ? slab_accept(tmin, tmax, tray_pred(tray)) : was[0];
+        break;
+    }
+    case 1: case 3: {
+        if (what == 3) { op[0] = in[1u + (i >> 23)]; op[1] = in[0] | (i & 0x7fffffu); }
+        else if (i < nIn) { op[0] = in[2 * (size_t)i]; op[1] = in[2 * (size_t)i + 1]; }
+        else { op[0] = probe_tame(probe_hash(seed, j, 1u)); op[1] = probe_tame(probe_hash(seed, j, 2u)); }
+        const float a = asf(op[0]), b = asf(op[1]);
+        was[0] = a / b;
+        is[0] = div_guarded(a, b);
+        break;
+    }
+    case 2: {
+        f3 D;
+        if (i < nIn) D = mk3(asf(in[3 * (size_t)i]), asf(in[3 * (size_t)i + 1]), asf(in[3 * (size_t)i + 2]));
+        else {
+            uint32_t s0 = probe_hash(seed, j, 1u) | 1u;
+            const float x = rnd_pm1(s0), y = rnd_pm1(s0), z = rnd_pm1(s0);
+            D = normalize3(mk3(x, y, z));
+        }
+        op[0] = asu(D.x); op[1] = asu(D.y); op[2] = asu(D.z);
+        was[0] = crt_atan2f(-D.z, D.x) + CRT_PI; was[1] = crt_acosf(-D.y);
+        sky_angles(D, is[0], is[1]);
+        break;
+    }
+    default: break;
+    }
+    if (!probe_same(was[0], is[0]) || !probe_same(was[1], is[1])) { atomicAdd(&out[0], 1u); atomicMin(&out[1], i); }
+    if (i == dumpAt) { out[2] = op[0]; out[3] = op[1]; out[4] = op[2]; out[5] = asu(was[0]); out[6] = asu(was[1]); out[7] = asu(is[0]); out[8] = asu(is[1]); }
+}
+
 } // namespace crt
+
+// out: 9 words {differing records, the lowest of them, its operands [3], old result [2], new result [2]}; out[0] = 0 and out[1] = 0xffffffff before the first launch
+extern "C" hipError_t crt_launch_probe_arith(int what, const void* in, uint32_t nIn, uint32_t n, uint32_t seed, uint32_t dumpAt, void* out, hipStream_t stream)
+{
+    if (n == 0) return hipSuccess;
+    if (what < 0 || what > 3 || nIn > n || (what == 3 && (n != 3u << 23 || nIn != 0u || !in)) || (nIn && !in)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(crt::probe_arith_kernel, dim3((n + 255u) / 256u), dim3(256), 0, stream, what, (const uint32_t*)in, nIn, n, seed, dumpAt, (uint32_t*)out);
+    return hipGetLastError();
+}
 
 extern "C" hipError_t crt_launch_probe_f32(int op, const void* in, void* out, uint32_t n, hipStream_t stream)
 {

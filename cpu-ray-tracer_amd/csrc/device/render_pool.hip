@@ -120,6 +120,10 @@ __device__ __forceinline__ uint64_t mask_eq(uint32_t a, uint32_t b) { return __b
 __device__ __forceinline__ uint64_t mask_ult(uint32_t a, uint32_t b) { return __builtin_amdgcn_uicmp(a, b, 36); }
 __device__ __forceinline__ uint64_t mask_ule(uint32_t a, uint32_t b) { return __builtin_amdgcn_uicmp(a, b, 37); }
 __device__ __forceinline__ uint64_t mask_sge(int a, int b) { return __builtin_amdgcn_sicmp(a, b, 39); }
+// lanes (of the active ones) whose walk may run the short slab test (dev_common.h box_short): finite reciprocal direction AND a tray the short accept predicate
+// holds for (tray_tame: bit pattern >= 2 as a signed integer).  A stream's tray is set when it is swapped in and falls only to accepted triangle hits (t > 1e-4),
+// so a lane that is tame when it enters a walk stays tame, and one that is not (a light / floor hit at a denormal t) accepts nothing and stays as it is.
+__device__ __forceinline__ uint64_t short_slab_mask(f3 rD, float tray) { return finite3_mask(rD) & mask_sge((int)asu(tray), 2); }
 __device__ __forceinline__ uint32_t rank_in(uint64_t m) { return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u)); }   // set bits below this lane
 
 // REFBITS: the width of the scene's pool references (layout.h: 16 or 32) — of `cur`, of the stack entries and of the constants that classify them
@@ -215,7 +219,7 @@ __global__ __launch_bounds__(64, REFBITS == 32 ? CRT_POOL_WIDE_MIN_WAVES : CRT_P
     // The stream resident in this lane (if any: mRes).  Invariant at the top of a trip: a resident stream is walking (cur != done) — streams whose walk ended
     // leave their lane in the trip that ended it, and only streams with a walk ahead are ever READY.
     uint64_t mRes = 0ull;                                                        // lanes holding a stream
-    uint64_t mFinite = ~0ull;                                                    // ... whose reciprocal direction is finite in all components (v_min / v_max slab test is exact)
+    uint64_t mFinite = ~0ull;                                                    // ... whose reciprocal direction is finite in all components and whose tray is tame (short_slab_mask: the v_min / v_max slab test is exact)
     uint32_t sid = 0, cur = kRefDone, spB = laneB, metaLo = 0u;
     f3 tO = nil3, tD = nil3, trD = nil3;
     Hit h; h.t = 1e34f; h.u = 0; h.v = 0; h.objIdx = -1; h.triIdx = -1;
@@ -252,13 +256,14 @@ __global__ __launch_bounds__(64, REFBITS == 32 ? CRT_POOL_WIDE_MIN_WAVES : CRT_P
                 const rec4 a0 = {rp[0], rp[1], rp[2], rp[3]}, a1 = {rp[4], rp[5], rp[6], rp[7]};
                 const rec4 b0 = {rp[8], rp[9], rp[10], rp[11]}, b1 = {rp[12], rp[13], rp[14], rp[15]};
                 float d1, d2;
-                const bool allFinite = (__builtin_amdgcn_ballot_w64(true) & ~finite3_mask(rD)) == 0ull;
+                const bool allFinite = (__builtin_amdgcn_ballot_w64(true) & ~short_slab_mask(rD, nh.t)) == 0ull;
+                const float tp = tray_pred(nh.t);
                 if constexpr (PRIM) {
                     // rp[16 ..]: primRoot, the four corners minus the camera position (behind rootPair in the Scene)
                     const f3 ra0 = mk3(rp[16], rp[17], rp[18]), ra1 = mk3(rp[19], rp[20], rp[21]), rb0 = mk3(rp[22], rp[23], rp[24]), rb1 = mk3(rp[25], rp[26], rp[27]);
-                    if (allFinite) { d1 = box_fast_rel(ra0, ra1, rD, nh.t); d2 = box_fast_rel(rb0, rb1, rD, nh.t); }
+                    if (allFinite) { d1 = box_short_rel(ra0, ra1, rD, tp); d2 = box_short_rel(rb0, rb1, rD, tp); }
                     else { d1 = box_exact_rel(ra0, ra1, rD, nh.t); d2 = box_exact_rel(rb0, rb1, rD, nh.t); }
-                } else if (allFinite) { d1 = box_fast(a0, a1, O, rD, nh.t); d2 = box_fast(b0, b1, O, rD, nh.t); }
+                } else if (allFinite) { d1 = box_short(a0, a1, O, rD, tp); d2 = box_short(b0, b1, O, rD, tp); }
                 else { d1 = box_exact(a0, a1, O, rD, nh.t); d2 = box_exact(b0, b1, O, rD, nh.t); }
                 const Ordered o = ordered_step(d1, d2, asu(a1.w), asu(b1.w));        // the children's ref16
                 pend = o.push ? o.farRef : 0u;
@@ -321,7 +326,7 @@ __global__ __launch_bounds__(64, REFBITS == 32 ? CRT_POOL_WIDE_MIN_WAVES : CRT_P
     };
 
     // ---------------- NODE step (infra/bvh.cpp:244-257 / tlas_bvh.cpp:96-110) of the lanes in m, on their pre-loaded NodePair ----------------
-    // Which slab test the step runs — the v_min / v_max form, exact while every stepping lane's reciprocal direction is finite, or the ordered-compare form — is a
+    // Which slab test the step runs — the v_min / v_max form with the short accept predicate (box_short), exact while every stepping lane is in mFinite, or the ordered-compare form — is a
     // property of the trip: the walk tests it once, on the lanes of the first step (mFinite changes in swap-in, at a TLAS leaf and at a BLAS return only, none of which
     // lies between a trip's NODE steps for the lanes that step), and calls the steps with the answer as a compile-time tag.  The exact form is then one out-of-line
     // region of the loop instead of a uniform branch inside every step's divergent region.
@@ -332,7 +337,7 @@ __global__ __launch_bounds__(64, REFBITS == 32 ? CRT_POOL_WIDE_MIN_WAVES : CRT_P
             if (COUNT) { if (KIND == 1 && (cur & R.tlasBit) != 0u) cn.tlas++; else cn.interior++; }
             const uint32_t top = stk_top(spB);                               // speculative: lands during the slab arithmetic (the dummy entry when the stack is empty)
             float d1, d2;
-            if constexpr (allFinite) { d1 = box_fast(q0, q1, tO, trD, h.t); d2 = box_fast(q2, q3, tO, trD, h.t); }
+            if constexpr (allFinite) { const float tp = tray_pred(h.t); d1 = box_short(q0, q1, tO, trD, tp); d2 = box_short(q2, q3, tO, trD, tp); }
             else { d1 = box_exact(q0, q1, tO, trD, h.t); d2 = box_exact(q2, q3, tO, trD, h.t); }
             const Ordered o = ordered_step(d1, d2, asu(q1.w), asu(q3.w));    // the children's ref16
             stk_put(spB + kLevelB, o.farRef);                                   // dead store unless `push`
@@ -405,7 +410,7 @@ __global__ __launch_bounds__(64, REFBITS == 32 ? CRT_POOL_WIDE_MIN_WAVES : CRT_P
                     if (COUNT && (next & R.tagMask) == 0u && next != kRefDone) cn.leaf++;
                     cur = next;
                 }
-                mFinite = (mFinite & ~mTlas) | (mTlas & finite3_mask(trD));
+                mFinite = (mFinite & ~mTlas) | (mTlas & short_slab_mask(trD, h.t));
             }
             uint64_t mLeafNow = 0ull;                                              // lanes that reached a leaf in an earlier step of this trip and have its first triangle loaded
             auto node_phase = [&](auto exactTag) {
@@ -447,7 +452,7 @@ __global__ __launch_bounds__(64, REFBITS == 32 ? CRT_POOL_WIDE_MIN_WAVES : CRT_P
                         cur = pop ? top : kRefDone; spB -= pop ? kLevelB : 0u;
                         if (COUNT && (cur & R.tagMask) == 0u && cur != kRefDone) cn.leaf++;
                     }
-                    mFinite = (mFinite & ~mBack) | (mBack & finite3_mask(trD));
+                    mFinite = (mFinite & ~mBack) | (mBack & short_slab_mask(trD, h.t));
                 }
             }
             asm volatile("" ::: "memory");          // (the sections exchange stream state through LDS across lanes: nothing is carried over in registers)
@@ -500,7 +505,7 @@ __global__ __launch_bounds__(64, REFBITS == 32 ? CRT_POOL_WIDE_MIN_WAVES : CRT_P
                     stk_put(laneB + kLevelB, pend);                                     // a dead store unless the far root child was hit
                     spB = laneB + (pend ? kLevelB : 0u);
                 }
-                mFinite = (mFinite & ~mTake) | (mTake & finite3_mask(trD));
+                mFinite = (mFinite & ~mTake) | (mTake & short_slab_mask(trD, h.t));
                 mRes |= mTake;
                 rdyH += (uint32_t)__popcll(mTake);
             }
