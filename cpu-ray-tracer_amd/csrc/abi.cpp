@@ -130,6 +130,10 @@ struct crt_ctx {
     // crt_destroy) — the slab pool and crt_tick's held regions are not touched; viewsDone: behind the last call's last accumulate, on that call's stream (the next
     // call's stream waits for it before it writes the slab again)
     char* dViewsSlab = nullptr; size_t viewsSlabCap = 0; hipEvent_t viewsDone = nullptr; bool viewsPending = false;
+    // crt_render_poses / crt_render_poses_device: the job's pose table (device/layout.h PoseJobHeader: P build headers, P images of [tlasOff, shadeOff)), scratch of the
+    // entries' own like dViewsSlab and ordered by the same event (the job's launches read it to the end); hPoseBack: the pinned copy of the headers (and, for
+    // tlas_out, of the images' node sections), poseBack: behind that read-back (the entries' one host wait)
+    char* dPoseTable = nullptr; size_t poseTableCap = 0; char* hPoseBack = nullptr; size_t poseBackCap = 0; hipEvent_t poseBack = nullptr;
     // crt_refit_device: per BVH the bottom-up plan of refit_box_kernel (device/refit.hip), built from the mirror's references by the first refit of that BVH and
     // freed with the scene; the root's pair + node 0's box come back through `hBack` (pinned) behind the kernels, and `done` is what sceneReady then names
     struct RefitPlan { void* dPlan = nullptr; uint32_t* dLevelOff = nullptr; uint32_t levels = 0, rootCode = 0; bool built = false; };
@@ -255,6 +259,7 @@ struct crt_ctx {
     int hip(hipError_t e, const char* what)
     {
         if (e == hipSuccess) return 0;
+        (void)hipGetLastError();          // the runtime keeps a failed call's code until it is read: a launch wrapper's hipGetLastError() of a LATER call must not find it
         return fail(CRT_ERR_DEVICE, "%s: %s", what, hipGetErrorString(e));
     }
     void freeAlt()
@@ -459,6 +464,9 @@ void crt_destroy(crt_ctx* c)
     if (c->dQuerySlots) (void)hipFree(c->dQuerySlots);
     if (c->viewsDone) { if (c->viewsPending) (void)hipEventSynchronize(c->viewsDone); (void)hipEventDestroy(c->viewsDone); }
     if (c->dViewsSlab) (void)hipFree(c->dViewsSlab);
+    if (c->poseBack) (void)hipEventDestroy(c->poseBack);
+    if (c->dPoseTable) (void)hipFree(c->dPoseTable);
+    if (c->hPoseBack) (void)hipHostFree(c->hPoseBack);
     if (c->altReady) (void)hipEventDestroy(c->altReady);
     if (c->writeFence) (void)hipEventDestroy(c->writeFence);
     c->refit.release(); c->tlasBuild.release();
@@ -2759,6 +2767,18 @@ int crt_refit_device(crt_ctx* c, uint32_t bvh, const float* d_positions, uint32_
     return CRT_OK;
 }
 
+// a built image's node section in the reference layout again (TLASBVH::tlasNode): leftRight / BLAS from the packed reference
+static void unpack_tlas_nodes(const crt::TlasNode* nodes, uint32_t count, crt_tlas_node* out)
+{
+    for (uint32_t i = 0; i < count; i++) {
+        const crt::TlasNode& n = nodes[i]; crt_tlas_node& o = out[i];
+        memcpy(o.aabbMin, n.lo, 12); memcpy(o.aabbMax, n.hi, 12);
+        const bool leaf = (n.ref & 0xC0000000u) == crt::kRefTlasLeaf;
+        o.leftRight = leaf ? 0u : ((n.ref & 0x7fffu) | (((n.ref >> 15) & 0x7fffu) << 16));
+        o.BLAS = leaf ? (n.ref & 0xffffu) : 0u;
+    }
+}
+
 // ---- crt_update_transforms_device: SetTransform of every BLAS + TLASBVH::Build on the device, from transforms in device memory (device/tlas_build.hip) ----
 int crt_update_transforms_device(crt_ctx* c, const float* d_T, uint32_t blasCount, void* stream, crt_tlas_node* tlasOut)
 {
@@ -2807,14 +2827,7 @@ int crt_update_transforms_device(crt_ctx* c, const float* d_T, uint32_t blasCoun
     memcpy(f.geom.data() + f.tlasOff, image, imageBytes);                  // the mirror: a later CRT_UPDATE_BOUNDS rewrites [tlasOff, shadeOff) from it
     const crt::TlasNode* nodes = reinterpret_cast<const crt::TlasNode*>(image);
     adopt_tlas(c, h.height, nodes[0].lo, nodes[0].hi);
-    if (tlasOut)
-        for (uint32_t i = 0; i < 2u * N; i++) {                            // the reference layout again: leftRight / BLAS from the packed reference
-            const crt::TlasNode& n = nodes[i]; crt_tlas_node& o = tlasOut[i];
-            memcpy(o.aabbMin, n.lo, 12); memcpy(o.aabbMax, n.hi, 12);
-            const bool leaf = (n.ref & 0xC0000000u) == crt::kRefTlasLeaf;
-            o.leftRight = leaf ? 0u : ((n.ref & 0x7fffu) | (((n.ref >> 15) & 0x7fffu) << 16));
-            o.BLAS = leaf ? (n.ref & 0xffffu) : 0u;
-        }
+    if (tlasOut) unpack_tlas_nodes(nodes, 2u * N, tlasOut);
     return CRT_OK;
 }
 
@@ -3623,7 +3636,9 @@ static int views_scratch(crt_ctx* c, uint32_t totalWindows, size_t windowBytes, 
 }
 
 // the job on `st`, after every check: launches of whole windows, each followed by its per-view sums into the caller's images
-static int views_run(crt_ctx* c, const float* dCams, uint32_t K, uint32_t sppFirst, uint32_t frames, uint32_t passes, float scale, float* dRgba, uint32_t* dPixels, hipStream_t st)
+// (poses: crt_render_poses' job — the launches read every lane's TLAS and Instance records from its view's pose in that table, with jobScene's stack depth)
+static int views_run(crt_ctx* c, const float* dCams, uint32_t K, uint32_t sppFirst, uint32_t frames, uint32_t passes, float scale, float* dRgba, uint32_t* dPixels, hipStream_t st,
+                     const crt::Scene* jobScene = nullptr, const crt::PoseTableDev* poses = nullptr)
 {
     if (c->tileCount == 0) return 0;
     const uint32_t total = K * frames, totalWindows = (total + 63u) / 64u;
@@ -3635,7 +3650,8 @@ static int views_run(crt_ctx* c, const float* dCams, uint32_t K, uint32_t sppFir
     if (c->renderAccel != 0 && c->altReady) HIPCK(c, hipStreamWaitEvent(st, c->altReady, 0));   // the accelerators' copies ran on the null stream
     for (uint32_t j0 = 0; j0 < total; j0 += wl * 64u) {
         const uint32_t nj = (total - j0 < wl * 64u) ? total - j0 : wl * 64u;
-        if (c->havePrim) HIPCK(c, crt_launch_render_views_prim(&c->hScene, &c->prim, dCams, c->dViewsSlab, c->dCounters, c->tileFirst, c->tileStride, c->tileCount, (uint32_t)c->tilesX, sppFirst, frames, passes, j0, nj, st));
+        if (poses) HIPCK(c, crt_launch_render_poses(jobScene, poses, dCams, c->dViewsSlab, c->dCounters, c->tileFirst, c->tileStride, c->tileCount, (uint32_t)c->tilesX, sppFirst, frames, passes, j0, nj, st));
+        else if (c->havePrim) HIPCK(c, crt_launch_render_views_prim(&c->hScene, &c->prim, dCams, c->dViewsSlab, c->dCounters, c->tileFirst, c->tileStride, c->tileCount, (uint32_t)c->tilesX, sppFirst, frames, passes, j0, nj, st));
         else HIPCK(c, crt_launch_render_views(c->renderAccel, &c->hScene, &c->alt, c->renderAccel ? &c->blasAlt[c->renderAccel - 1] : nullptr, dCams, c->dViewsSlab, c->dCounters, c->tileFirst,
                                               c->tileStride, c->tileCount, (uint32_t)c->tilesX, sppFirst, frames, passes, j0, nj, st));
         HIPCK(c, crt_launch_views_accumulate(c->dViewsSlab, dRgba, dPixels, c->tileFirst, c->tileStride, c->tileCount, (uint32_t)c->tilesX, (uint32_t)c->cfg.width, (uint32_t)c->cfg.height, frames,
@@ -3644,6 +3660,41 @@ static int views_run(crt_ctx* c, const float* dCams, uint32_t K, uint32_t sppFir
     HIPCK(c, hipEventRecord(c->viewsDone, st));
     c->viewsPending = true;
     return 0;
+}
+
+// The host entries' staging (the context's, stage()): the K images, the K screens where wanted, then `extraBytes` for the entry's inputs (cameras, ...).
+// The job writes the owned tiles' pixels only.  A context that owns every tile of an image whose width the tiling does not truncate writes whole rows — the first
+// 16 * tilesY of every view — and only those travel back; any other context's staging starts from the caller's images, so every other pixel returns as it came.
+struct ViewsStage { float* dRgba; uint32_t* dPix; char* extra; size_t px, rowsPx; };
+static int views_stage_in(crt_ctx* c, uint32_t K, const float* out_rgba, const uint32_t* out_pixels, size_t extraBytes, ViewsStage* S)
+{
+    const size_t W = (size_t)c->cfg.width, px = W * c->cfg.height;
+    const size_t pixOff = K * px * 16, extraOff = pixOff + (out_pixels ? K * px * 4 : 0);
+    int r;
+    if ((r = stage(c, extraOff + extraBytes))) return r;
+    S->dRgba = reinterpret_cast<float*>(c->dStage); S->dPix = out_pixels ? reinterpret_cast<uint32_t*>(c->dStage + pixOff) : nullptr; S->extra = c->dStage + extraOff;
+    const bool wholeRows = c->tileFirst == 0 && c->tileStride == 1 && c->tileCount == (uint32_t)(c->tilesX * c->tilesY) && (size_t)c->tilesX * 16u == W;
+    S->px = px; S->rowsPx = wholeRows ? W * 16u * (size_t)c->tilesY : px;
+    if (!wholeRows) {
+        HIPCK(c, hipMemcpyAsync(S->dRgba, out_rgba, K * px * 16, hipMemcpyHostToDevice, c->stream));
+        if (S->dPix) HIPCK(c, hipMemcpyAsync(S->dPix, out_pixels, K * px * 4, hipMemcpyHostToDevice, c->stream));
+    }
+    return 0;
+}
+// ... and the way back, behind the job on the context's stream; the call synchronises
+static int views_stage_out(crt_ctx* c, uint32_t K, float* out_rgba, uint32_t* out_pixels, const ViewsStage& S)
+{
+    const size_t px = S.px;
+    if (S.rowsPx == px) {
+        HIPCK(c, hipMemcpyAsync(out_rgba, S.dRgba, K * px * 16, hipMemcpyDeviceToHost, c->stream));
+        if (S.dPix) HIPCK(c, hipMemcpyAsync(out_pixels, S.dPix, K * px * 4, hipMemcpyDeviceToHost, c->stream));
+    } else for (uint32_t k = 0; k < K; k++) {
+        HIPCK(c, hipMemcpyAsync(out_rgba + k * px * 4, S.dRgba + k * px * 4, S.rowsPx * 16, hipMemcpyDeviceToHost, c->stream));
+        if (S.dPix) HIPCK(c, hipMemcpyAsync(out_pixels + k * px, S.dPix + k * px, S.rowsPx * 4, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCK(c, hipStreamSynchronize(c->stream));
+    c->viewsPending = false;
+    return CRT_OK;
 }
 
 int crt_render_views_device(crt_ctx* c, const float* d_cams, uint32_t K, uint32_t spp_first, uint32_t frames, uint32_t passes, float scale, float* d_out_rgba, uint32_t* d_out_pixels, void* stream)
@@ -3671,31 +3722,147 @@ int crt_render_views(crt_ctx* c, const float* cams, uint32_t K, uint32_t spp_fir
     if (K == 0 || frames == 0) return CRT_OK;
     if (!cams || !out_rgba) return c->fail(CRT_ERR_INVALID, "crt_render_views: NULL buffer");
     HIPCK(c, hipSetDevice(c->cfg.device));
-    const size_t W = (size_t)c->cfg.width, px = W * c->cfg.height;
-    const size_t pixOff = K * px * 16, camOff = pixOff + (out_pixels ? K * px * 4 : 0);
-    if ((r = stage(c, camOff + (size_t)K * 48))) return r;
-    float* dRgba = reinterpret_cast<float*>(c->dStage); uint32_t* dPix = out_pixels ? reinterpret_cast<uint32_t*>(c->dStage + pixOff) : nullptr;
-    float* dCams = reinterpret_cast<float*>(c->dStage + camOff);
-    // The call writes the owned tiles' pixels only.  A context that owns every tile of an image whose width the tiling does not truncate writes whole rows — the first
-    // 16 * tilesY of every view — and only those travel back; any other context's staging starts from the caller's images, so every other pixel returns as it came.
-    const bool wholeRows = c->tileFirst == 0 && c->tileStride == 1 && c->tileCount == (uint32_t)(c->tilesX * c->tilesY) && (size_t)c->tilesX * 16u == W;
-    const size_t rowsPx = wholeRows ? W * 16u * (size_t)c->tilesY : px;
+    ViewsStage S;
+    if ((r = views_stage_in(c, K, out_rgba, out_pixels, (size_t)K * 48, &S))) return r;
+    float* dCams = reinterpret_cast<float*>(S.extra);
     HIPCK(c, hipMemcpyAsync(dCams, cams, (size_t)K * 48, hipMemcpyHostToDevice, c->stream));
-    if (!wholeRows) {
-        HIPCK(c, hipMemcpyAsync(dRgba, out_rgba, K * px * 16, hipMemcpyHostToDevice, c->stream));
-        if (dPix) HIPCK(c, hipMemcpyAsync(dPix, out_pixels, K * px * 4, hipMemcpyHostToDevice, c->stream));
+    if ((r = views_run(c, dCams, K, spp_first, frames, passes, scale, S.dRgba, S.dPix, c->stream))) return r;
+    return views_stage_out(c, K, out_rgba, out_pixels, S);
+}
+
+// ---- crt_render_poses / crt_render_poses_device: the frames of K cameras over P job-local poses of a two-level scene's instances (device/render_poses.h) ----
+// where a job's pose table keeps what (device/layout.h PoseJobHeader)
+struct PoseLayout {
+    size_t imageBytes, headBytes, tableBytes; uint32_t imagesOff, imageStride;
+    PoseLayout(const crt_ctx::Flat& f, uint32_t P)
+    {
+        imageBytes = (size_t)(f.shadeOff - f.tlasOff);
+        imageStride = (uint32_t)((imageBytes + 127u) & ~(size_t)127u);
+        headBytes = sizeof(crt::PoseJobHeader) + (size_t)P * sizeof(crt::TlasBuildHeader);
+        imagesOff = (uint32_t)((headBytes + 127u) & ~(size_t)127u);        // (poses_check refuses a table beyond 4 GiB before anything uses the 32-bit fields)
+        tableBytes = ((headBytes + 127u) & ~(size_t)127u) + (size_t)P * imageStride;
     }
-    if ((r = views_run(c, dCams, K, spp_first, frames, passes, scale, dRgba, dPix, c->stream))) return r;
-    if (rowsPx == px) {
-        HIPCK(c, hipMemcpyAsync(out_rgba, dRgba, K * px * 16, hipMemcpyDeviceToHost, c->stream));
-        if (dPix) HIPCK(c, hipMemcpyAsync(out_pixels, dPix, K * px * 4, hipMemcpyDeviceToHost, c->stream));
-    } else for (uint32_t k = 0; k < K; k++) {
-        HIPCK(c, hipMemcpyAsync(out_rgba + k * px * 4, dRgba + k * px * 4, rowsPx * 16, hipMemcpyDeviceToHost, c->stream));
-        if (dPix) HIPCK(c, hipMemcpyAsync(out_pixels + k * px, dPix + k * px, rowsPx * 4, hipMemcpyDeviceToHost, c->stream));
+};
+
+// the checks that need no buffer, in the order crt_abi.h lists the refusals
+static int poses_check(crt_ctx* c, uint32_t K, uint32_t P, uint32_t blasCount, bool viewPose, uint32_t frames, uint32_t passes, const char* what)
+{
+    if (!c->haveScene && !c->havePrim) return c->fail(CRT_ERR_STATE, "%s before crt_upload_scene", what);
+    if (c->havePrim) return c->fail(CRT_ERR_UNSUPPORTED, "%s: the PrimitiveScene has no instances", what);
+    const crt_ctx::Flat& f = c->flat;
+    if (f.kind != CRT_SCENE_TLAS) return c->fail(CRT_ERR_INVALID, "%s applies to two-level scenes (a FileScene bakes its transforms into the triangles)", what);
+    const uint32_t N = (uint32_t)f.triCount.size();
+    if (blasCount != N) return c->fail(CRT_ERR_INVALID, "%s: %u transforms per pose, the uploaded scene has %u BLAS", what, blasCount, N);
+    if (f.tlasNodeCount != 2u * N) return c->fail(CRT_ERR_UNSUPPORTED, "%s: the scene was uploaded with %u TLAS nodes, TLASBVH::Build makes %u", what, f.tlasNodeCount, 2u * N);
+    if (passes < 1 || passes > 4) return c->fail(CRT_ERR_INVALID, "%s: passes must be 1..4 (the reference's UI range, renderer.cpp:178)", what);
+    if ((uint64_t)K * frames > 0x7fffffffull) return c->fail(CRT_ERR_UNSUPPORTED, "%s: at most 2^31-1 view-frames per call (%u views x %u frames)", what, K, frames);
+    if (c->renderAccel != 0) return c->fail(CRT_ERR_UNSUPPORTED, "%s: poses of the KD-tree / grid BLAS sets are not supported (crt_set_render_accel(0) first)", what);
+    if (K > 0 && P == 0) return c->fail(CRT_ERR_INVALID, "%s: %u views and no pose", what, K);
+    if (!viewPose && P != K) return c->fail(CRT_ERR_INVALID, "%s: without view_pose view k renders pose k, so P (%u) must equal K (%u)", what, P, K);
+    if (PoseLayout(f, P).tableBytes > crt::kMaxGeomBytes)
+        return c->fail(CRT_ERR_UNSUPPORTED, "%s: %u poses of %zu bytes each exceed the 4 GiB the kernel's 32-bit offsets address; split the job", what, P, PoseLayout(f, P).imageBytes);
+    return 0;
+}
+
+// The job on `st`, after the checks that need no launch: the P builds in one launch, the read-back of their headers and of the view_pose flag (THE host wait),
+// the checks of what came back, tlasOut, then crt_render_views' launches over the table.  dViewPose may be nullptr (view k renders pose k).
+static int poses_run(crt_ctx* c, const float* dCams, uint32_t K, const float* dT, uint32_t P, const int32_t* dViewPose, uint32_t sppFirst, uint32_t frames, uint32_t passes, float scale,
+                     float* dRgba, uint32_t* dPixels, crt_tlas_node* tlasOut, hipStream_t st, const char* what)
+{
+    const crt_ctx::Flat& f = c->flat;
+    const uint32_t N = (uint32_t)f.triCount.size();
+    const PoseLayout L(f, P);
+    const size_t nodeBytes = (size_t)2u * N * sizeof(crt::TlasNode), backBytes = L.headBytes + (tlasOut ? (size_t)P * nodeBytes : 0);
+    // The builds are readers, as crt_update_transforms_device's: the Instance records and the node-0 boxes as the last write left them.
+    int r;
+    if ((r = wait_scene(c, st))) return r;
+    // the table is read by the previous job's launches to their end: viewsDone, on that job's stream
+    HIPCK(c, ensure_event(&c->viewsDone));
+    HIPCK(c, ensure_event(&c->poseBack));
+    if (L.tableBytes > c->poseTableCap) {
+        if (c->viewsPending) { HIPCK(c, hipEventSynchronize(c->viewsDone)); c->viewsPending = false; }
+        if (c->dPoseTable) { HIPCK(c, hipFree(c->dPoseTable)); c->dPoseTable = nullptr; c->poseTableCap = 0; }
+        HIPCK(c, hipMalloc((void**)&c->dPoseTable, L.tableBytes));
+        c->poseTableCap = L.tableBytes;
     }
-    HIPCK(c, hipStreamSynchronize(c->stream));
-    c->viewsPending = false;
-    return CRT_OK;
+    if (backBytes > c->poseBackCap) {                                       // (no copy into it is in flight: every call waits for its own)
+        if (c->hPoseBack) { HIPCK(c, hipHostFree(c->hPoseBack)); c->hPoseBack = nullptr; c->poseBackCap = 0; }
+        HIPCK(c, hipHostMalloc((void**)&c->hPoseBack, backBytes, hipHostMallocDefault));
+        c->poseBackCap = backBytes;
+    }
+    if (c->viewsPending) HIPCK(c, hipStreamWaitEvent(st, c->viewsDone, 0));
+    HIPCK(c, hipMemsetAsync(c->dPoseTable, 0xff, sizeof(uint32_t), st));    // PoseJobHeader::badView = kPoseNoBadView
+    HIPCK(c, crt_launch_tlas_build_poses(c->hScene.geom, (uint32_t)f.instOff, dT, c->dRootBox, N, (uint32_t)(f.tlasPairOff - f.tlasOff), (uint32_t)(f.instOff - f.tlasOff), c->hScene.poolRefBits,
+                                         c->dPoseTable, L.imagesOff, L.imageStride, P, dViewPose, K, st));
+    if (tlasOut) HIPCK(c, hipMemcpy2DAsync(c->hPoseBack + L.headBytes, nodeBytes, c->dPoseTable + L.imagesOff, L.imageStride, nodeBytes, P, hipMemcpyDeviceToHost, st));
+    // the one host wait: the launches' LDS stack is sized by the tallest pose's TLAS, and a job with a failed build or a view_pose entry out of range does not run
+    if ((r = read_back(c, st, c->poseBack, c->hPoseBack, c->dPoseTable, L.headBytes))) return r;
+    const crt::PoseJobHeader& job = *reinterpret_cast<const crt::PoseJobHeader*>(c->hPoseBack);
+    const crt::TlasBuildHeader* heads = reinterpret_cast<const crt::TlasBuildHeader*>(c->hPoseBack + sizeof(crt::PoseJobHeader));
+    if (job.badView != crt::kPoseNoBadView) return c->fail(CRT_ERR_INVALID, "%s: view_pose[%u] lies outside [0, %u)", what, job.badView, P);
+    uint32_t tallest = 0, tallestPose = 0;
+    for (uint32_t p = 0; p < P; p++) {
+        const crt::TlasBuildHeader& h = heads[p];
+        if (h.status == crt::kTlasBuildNoCandidate)
+            return c->fail(CRT_ERR_INVALID, "%s: pose %u: FindBestMatch call %u found no partner while more than one node was open (a non-finite transform or box, or areas >= 1e30; the reference reads list[-1] there)", what, p, h.step);
+        if (h.status != crt::kTlasBuildOk) return c->fail(CRT_ERR_INVALID, "%s: pose %u: the build had not ended after %u FindBestMatch calls", what, p, h.step);
+        if (h.height > tallest) { tallest = h.height; tallestPose = p; }
+    }
+    crt::Scene job_scene = c->hScene;                                       // the launches' by-value Scene: the context's, with the job's stack depth.  c->hScene stays as it is
+    job_scene.stackDepth = job_scene.bvhStack + tallest + 1;
+    if ((r = check_tlas_height(c, tallest))) return r;
+    if (!sample_lds_fits(job_scene.stackDepth))
+        return c->fail(CRT_ERR_UNSUPPORTED, "%s: pose %u: a TLAS of height %u makes the traversal stack %u dwords per lane, which exceeds the kernel's LDS", what, tallestPose, tallest, job_scene.stackDepth);
+    const crt::PoseTableDev pt{c->dPoseTable, dViewPose, L.imagesOff, L.imageStride, (uint32_t)(f.instOff - f.tlasOff)};
+    if ((r = views_run(c, dCams, K, sppFirst, frames, passes, scale, dRgba, dPixels, st, &job_scene, &pt))) return r;
+    // tlasOut last, once nothing can refuse the job any more (the pinned copy is the call's own until it returns): a refused call writes nothing
+    if (tlasOut)
+        for (uint32_t p = 0; p < P; p++) unpack_tlas_nodes(reinterpret_cast<const crt::TlasNode*>(c->hPoseBack + L.headBytes + p * nodeBytes), 2u * N, tlasOut + (size_t)p * 2u * N);
+    return 0;
+}
+
+int crt_render_poses_device(crt_ctx* c, const float* d_cams, uint32_t K, const float* d_T, uint32_t P, uint32_t blasCount, const int32_t* d_view_pose, uint32_t spp_first, uint32_t frames,
+                            uint32_t passes, float scale, float* d_out_rgba, uint32_t* d_out_pixels, crt_tlas_node* tlas_out, void* stream)
+{
+    if (!c) return CRT_ERR_INVALID;
+    const char* what = "crt_render_poses_device";
+    int r;
+    if ((r = poses_check(c, K, P, blasCount, d_view_pose != nullptr, frames, passes, what))) return r;
+    if (K == 0 || frames == 0) return CRT_OK;
+    const size_t px = (size_t)c->cfg.width * c->cfg.height;
+    if (reinterpret_cast<uintptr_t>(d_out_rgba) & 15u) return c->fail(CRT_ERR_INVALID, "%s: d_out_rgba %p is not 16-byte aligned", what, (void*)d_out_rgba);
+    hipStream_t st = nullptr; int k = 0;
+    if ((r = device_entry(c, what, {{d_cams, (size_t)K * 48}, {d_T, (size_t)P * blasCount * 64}, {d_out_rgba, K * px * 16}}, stream, &st))) return r;
+    if (d_out_pixels && (r = check_device_buffer(c, d_out_pixels, K * px * 4, what))) return r;
+    if (d_view_pose && (r = check_device_buffer(c, d_view_pose, (size_t)K * 4, what))) return r;
+    if ((r = take_query_slot(c, &k))) return r;
+    if ((r = poses_run(c, d_cams, K, d_T, P, d_view_pose, spp_first, frames, passes, scale, d_out_rgba, d_out_pixels, tlas_out, st, what))) return r;
+    return end_device_query(c, k, st);
+}
+
+int crt_render_poses(crt_ctx* c, const float* cams, uint32_t K, const float* T, uint32_t P, uint32_t blasCount, const int32_t* view_pose, uint32_t spp_first, uint32_t frames, uint32_t passes,
+                     float scale, float* out_rgba, uint32_t* out_pixels, crt_tlas_node* tlas_out)
+{
+    if (!c) return CRT_ERR_INVALID;
+    const char* what = "crt_render_poses";
+    int r;
+    if ((r = poses_check(c, K, P, blasCount, view_pose != nullptr, frames, passes, what))) return r;
+    if (K == 0 || frames == 0) return CRT_OK;
+    if (!cams || !T || !out_rgba) return c->fail(CRT_ERR_INVALID, "%s: NULL buffer", what);
+    if (view_pose)
+        for (uint32_t k = 0; k < K; k++)
+            if (view_pose[k] < 0 || (uint32_t)view_pose[k] >= P) return c->fail(CRT_ERR_INVALID, "%s: view_pose[%u] = %d lies outside [0, %u)", what, k, view_pose[k], P);
+    HIPCK(c, hipSetDevice(c->cfg.device));
+    const size_t camBytes = (size_t)K * 48, tBytes = (size_t)P * blasCount * 64;
+    ViewsStage S;
+    if ((r = views_stage_in(c, K, out_rgba, out_pixels, camBytes + tBytes + (view_pose ? (size_t)K * 4 : 0), &S))) return r;
+    float* dCams = reinterpret_cast<float*>(S.extra); float* dT = reinterpret_cast<float*>(S.extra + camBytes);
+    int32_t* dViewPose = view_pose ? reinterpret_cast<int32_t*>(S.extra + camBytes + tBytes) : nullptr;
+    HIPCK(c, hipMemcpyAsync(dCams, cams, camBytes, hipMemcpyHostToDevice, c->stream));
+    HIPCK(c, hipMemcpyAsync(dT, T, tBytes, hipMemcpyHostToDevice, c->stream));
+    if (dViewPose) HIPCK(c, hipMemcpyAsync(dViewPose, view_pose, (size_t)K * 4, hipMemcpyHostToDevice, c->stream));
+    if ((r = poses_run(c, dCams, K, dT, P, dViewPose, spp_first, frames, passes, scale, S.dRgba, S.dPix, tlas_out, c->stream, what))) return r;
+    return views_stage_out(c, K, out_rgba, out_pixels, S);
 }
 
 // tools / tests: the lanes a full sample-query launch of this scene and accelerator holds at once (the grid is that many lanes, or fewer when the rays need fewer)

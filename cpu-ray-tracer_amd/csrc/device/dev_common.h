@@ -480,16 +480,22 @@ __device__ __forceinline__ void traverse_bvh_seq(const Scene& sc, uint32_t rootR
 // TLASBVH::Intersect's loop (infra/tlas_bvh.cpp:83-111; tlas_kdtree.cpp / tlas_grid.cpp are the same text) with the BLAS walk as a parameter:
 // at a leaf the ray goes to object space (BLASBVH::Intersect's transform, blas_bvh.cpp:376-381, repeated by blas_kdtree.cpp:420-433 and blas_grid.cpp:233-248)
 // and `blas(instance, ids, Oo, Do, rDo)` walks that BLAS; with STOP it returns true to end the whole walk (IsOccluded's first hit).  TLAS entries at tstk[k * 64].
-template <bool STOP = false, class BlasWalk>
-__device__ __forceinline__ void tlas_walk(const Scene& sc, f3 O, f3 D, f3 rD, Hit& h, uint32_t* tstk, Cnt& cn, int& traversed, BlasWalk&& blas)
+// Where the walk finds its TLAS: tlas_base(t) + tlas_nodes(t) = the TlasNode section, tlas_base(t) + tlas_insts(t) = the Instance records, tlas_root(t) = node 0's
+// reference.  For a Scene the live scene's, below; a job-local pose names its own image of those sections (render_poses.h PoseWorld).
+__device__ __forceinline__ const char* tlas_base(const Scene& sc) { return sc.geom; }
+__device__ __forceinline__ uint32_t tlas_nodes(const Scene& sc) { return sc.tlasOff; }
+__device__ __forceinline__ uint32_t tlas_insts(const Scene& sc) { return sc.instOff; }
+__device__ __forceinline__ uint32_t tlas_root(const Scene& sc) { return sc.rootRef; }
+template <bool STOP = false, class Tlas, class BlasWalk>
+__device__ __forceinline__ void tlas_walk(const Tlas& tlas, f3 O, f3 D, f3 rD, Hit& h, uint32_t* tstk, Cnt& cn, int& traversed, BlasWalk&& blas)
 {
-    const char* __restrict__ g = sc.geom;
-    uint32_t cur = sc.rootRef, sp = 0;
+    const char* __restrict__ g = tlas_base(tlas);
+    uint32_t cur = tlas_root(tlas), sp = 0;
     for (;;) {
         traversed++; cn.tlas++;
         if ((cur & kRefTlasLeaf) == kRefTlasLeaf) {
             cn.visits++;
-            const uint32_t io = sc.instOff + (cur & 0xffffu) * 128u;
+            const uint32_t io = tlas_insts(tlas) + (cur & 0xffffu) * 128u;
             const rec4 r0 = ldg(g, io), r1 = ldg(g, io + 16), r2 = ldg(g, io + 32), ids = ldg(g, io + 48);
             f3 Oo, Do, rDo; to_object_space(r0, r1, r2, O, D, Oo, Do, rDo);
             if constexpr (STOP) { if (blas(cur & 0xffffu, ids, Oo, Do, rDo)) break; }
@@ -497,7 +503,7 @@ __device__ __forceinline__ void tlas_walk(const Scene& sc, f3 O, f3 D, f3 rD, Hi
             if (sp == 0) break;
             cur = tstk[(--sp) * 64];
         } else {
-            const uint32_t o1 = sc.tlasOff + (cur & 0x7fffu) * 32u, o2 = sc.tlasOff + ((cur >> 15) & 0x7fffu) * 32u;
+            const uint32_t o1 = tlas_nodes(tlas) + (cur & 0x7fffu) * 32u, o2 = tlas_nodes(tlas) + ((cur >> 15) & 0x7fffu) * 32u;
             const rec4 alo = ldg(g, o1), ahi = ldg(g, o1 + 16), blo = ldg(g, o2), bhi = ldg(g, o2 + 16);
             float d1 = box_exact(alo, ahi, O, rD, h.t), d2 = box_exact(blo, bhi, O, rD, h.t);
             uint32_t r1 = asu(alo.w), r2 = asu(blo.w);

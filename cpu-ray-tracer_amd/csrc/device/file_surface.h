@@ -15,7 +15,9 @@ struct FileSurface {
     static constexpr bool kMeshHits = true;
     __device__ __forceinline__ f3 miss(const Scene& sc, f3 D) const { return sky_color(sc, D); }        // GetSkyColor, file_scene.cpp:142-154
     // h.triIdx is the GLOBAL shade index (what LeafTri::shadeIdx carries).  x: also HitInfo::uv and the material's index in Scene::mats, for the hit-info query
-    __device__ __forceinline__ Surf surface(const Scene& sc, const Hit& h, f3 I, f3 D, SurfExtra* x = nullptr) const
+    __device__ __forceinline__ Surf surface(const Scene& sc, const Hit& h, f3 I, f3 D, SurfExtra* x = nullptr) const { return surface_of(sc, h, I, D, sc.geom, sc.instOff, x); }
+    // ... with the Instance records (KIND 1: their T rows) at instGeom + instOff: the live scene's (above), or a job-local pose's image of them (render_poses.h)
+    __device__ __forceinline__ Surf surface_of(const Scene& sc, const Hit& h, f3 I, f3 D, const char* instGeom, uint32_t instOff, SurfExtra* x = nullptr) const
     {
         const char* __restrict__ geom = sc.geom;
         SurfPoint p;
@@ -23,7 +25,7 @@ struct FileSurface {
         else {
             const uint32_t so = sc.shadeOff + (uint32_t)h.triIdx * 64u;
             const rec4 s0 = ldg(geom, so), s1 = ldg(geom, so + 16u), s2 = ldg(geom, so + 32u), s3 = ldg(geom, so + 48u);
-            p = mesh_point<KIND>(s0, s1, s2, s3, h.u, h.v, h.objIdx, geom, sc.instOff, sc.mats);
+            p = mesh_point<KIND>(s0, s1, s2, s3, h.u, h.v, h.objIdx, instGeom, instOff, sc.mats);
         }
         Surf s; s.N = face_ray(p.N, D); s.refl = p.refl; s.refr = p.refr; s.absorb = p.absorb;
         s.c = mk3(1.0f, 1.0f, 1.0f);

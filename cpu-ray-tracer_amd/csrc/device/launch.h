@@ -70,6 +70,10 @@ hipError_t crt_launch_sample_query(int accel, const crt::Scene* sc, const crt::A
 // ceil(nj / 64) windows, cams = K records of twelve floats; crt_launch_views_accumulate sums that slab per view into the caller's images (outPixels may be nullptr)
 hipError_t crt_launch_render_views(int accel, const crt::Scene* sc, const crt::AltAccelDev* acc, const crt::TlasAltDev* tl, const float* cams, void* slab, crt::Counters* counters,
     uint32_t tileFirst, uint32_t tileStride, uint32_t tileCount, uint32_t tilesX, uint32_t sppFirst, uint32_t frames, uint32_t passes, uint32_t jFirst, uint32_t nj, hipStream_t stream);
+// crt_render_poses (render_poses.h): crt_launch_render_views' launch with every lane's TLAS and Instance records taken from its view's pose in the table `pt` names;
+// sc->stackDepth is the job's.  The per-view sums are crt_launch_views_accumulate's.
+hipError_t crt_launch_render_poses(const crt::Scene* sc, const crt::PoseTableDev* pt, const float* cams, void* slab, crt::Counters* counters, uint32_t tileFirst, uint32_t tileStride,
+    uint32_t tileCount, uint32_t tilesX, uint32_t sppFirst, uint32_t frames, uint32_t passes, uint32_t jFirst, uint32_t nj, hipStream_t stream);
 hipError_t crt_launch_views_accumulate(const void* slab, float* outRgba, uint32_t* outPixels, uint32_t tileFirst, uint32_t tileStride, uint32_t tileCount, uint32_t tilesX, uint32_t W,
     uint32_t H, uint32_t frames, uint32_t passes, uint32_t jFirst, uint32_t nj, float scale, hipStream_t stream);
 
@@ -132,6 +136,10 @@ hipError_t crt_launch_bvh_relocate(const char* oldGeom, char* geom, const crt::B
 // ---- tlas_build.hip ----
 hipError_t crt_launch_tlas_build(const char* geom, uint32_t instOff, const float* T, const float* rootBox, uint32_t blasCount, uint32_t pairRel, uint32_t instRel, uint32_t poolRefBits,
     void* out, hipStream_t stream);
+// P such builds in one launch, one workgroup each, over T + 16 blasCount p into header p / image p of a pose table (layout.h PoseJobHeader), and the check of the K
+// view -> pose indices (viewPose may be nullptr); the caller sets PoseJobHeader::badView to kPoseNoBadView on the stream first
+hipError_t crt_launch_tlas_build_poses(const char* geom, uint32_t instOff, const float* T, const float* rootBox, uint32_t blasCount, uint32_t pairRel, uint32_t instRel, uint32_t poolRefBits,
+    void* table, uint32_t imagesOff, uint32_t imageStride, uint32_t P, const int32_t* viewPose, uint32_t K, hipStream_t stream);
 
 // abi.cpp's test switch CRT_DEBUG_QUERY_GRID=<k>: an upper bound on the workgroups of a persistent query launch (0: none).  Host side only: each wrapper passes its grid through it.
 uint32_t crt_debug_query_grid(void);

@@ -167,6 +167,20 @@ struct alignas(64) TlasBuildHeader {
     uint32_t pad[11];
 };
 constexpr uint32_t kTlasBuildOk = 0u, kTlasBuildNoCandidate = 1u, kTlasBuildNoEnd = 2u;
+// crt_render_poses' pose table (tlas_build.hip tlas_build_poses_kernel writes it, render_poses.h reads it): this header, P TlasBuildHeaders side by side (one
+// read-back), then — at imagesOff, imageStride apart, both multiples of 128 — the P images of [tlasOff, shadeOff).  The render kernel addresses the table as it
+// addresses the geometry buffer, scalar base + 32-bit byte offset, so the whole table stays within kMaxGeomBytes; an image's Instance records are 128 bytes each
+// and lie wholly inside it, which keeps ldp<>'s assumption (64 bytes from a record half's offset are inside the buffer) true.
+struct alignas(64) PoseJobHeader {
+    uint32_t badView;                     // the lowest view whose view_pose entry lies outside [0, P); kPoseNoBadView: none
+    uint32_t pad[15];
+};
+constexpr uint32_t kPoseNoBadView = 0xffffffffu;
+// what the render kernel takes by value: where the table is and how a view finds its pose in it
+struct PoseTableDev {
+    const char* table; const int32_t* viewPose;   // viewPose == nullptr: view k renders pose k
+    uint32_t imagesOff, imageStride, instRel;     // instRel: the Instance records' offset inside an image (instOff - tlasOff)
+};
 constexpr uint32_t kTlasMaxBlas = 256u;   // tlas_bvh.cpp:21 (nodeIdx[256])
 
 // Whether a crt_hit's indices may be used as addresses by the hit-info query (shade_query.hip): ONE predicate for the host entry, which refuses the call, and for

@@ -8,6 +8,7 @@
 // The issue-bound renders of these scenes are render_pool_kernel / render_tiles_kernel; this form exists for the probe and for parity with the alternative
 // accelerators (crt_set_render_accel).  The same worlds serve sample_query_kernel (sample_query.h): Renderer::Sample for a caller's rays and seeds, and
 // render_views_kernel (render_views.h): the frames of many cameras in one launch (crt_render_views), whose per-view sums views_accumulate_kernel below forms.
+// render_poses_kernel (render_poses.h) is that kernel over job-local poses of a two-level scene's instances (crt_render_poses); it is launched from here too.
 //
 // Numerics: -ffp-contract=off, IEEE + - * / sqrt only (dev_common.h).  No MFMA: pointer chasing + slab / Möller–Trumbore tests.
 #include "alt_common.h"
@@ -15,6 +16,7 @@
 #include "launch.h"
 #include "sample_query.h"
 #include "render_views.h"
+#include "render_poses.h"
 
 namespace crt {
 
@@ -174,6 +176,20 @@ extern "C" hipError_t crt_launch_render_views(int accel, const crt::Scene* sc, c
     }
     if (accel == 1) return crt::launch_render_views(sc, crt::KdWorld{{}, *acc}, cams, slab, counters, tileFirst, tileStride, tileCount, tilesX, sppFirst, frames, passes, jFirst, nj, stream);
     return crt::launch_render_views(sc, crt::GridWorld{{}, *acc}, cams, slab, counters, tileFirst, tileStride, tileCount, tilesX, sppFirst, frames, passes, jFirst, nj, stream);
+}
+
+// crt_render_poses: the same launch over the poses of a pose table (render_poses.h).  sc: the context's Scene with the JOB's stackDepth (the tallest pose's).
+extern "C" hipError_t crt_launch_render_poses(const crt::Scene* sc, const crt::PoseTableDev* pt, const float* cams, void* slab, crt::Counters* counters, uint32_t tileFirst,
+                                              uint32_t tileStride, uint32_t tileCount, uint32_t tilesX, uint32_t sppFirst, uint32_t frames, uint32_t passes, uint32_t jFirst, uint32_t nj,
+                                              hipStream_t stream)
+{
+    const uint32_t ldsBytes = crt::seq_lds_bytes(sc->stackDepth);
+    const unsigned long long entries = (unsigned long long)tileCount * ((nj + 63u) / 64u);
+    if (sc->kind != 1 || ldsBytes > 64u * 1024u || entries > 0x7fffffffull || frames == 0) return hipErrorInvalidValue;
+    if (entries == 0) return hipSuccess;
+    hipLaunchKernelGGL(crt::render_poses_kernel, dim3((uint32_t)((entries + crt::kSeqWaves - 1u) / crt::kSeqWaves)), dim3(64u * crt::kSeqWaves), ldsBytes, stream, *sc, *pt, cams, (char*)slab,
+                       counters, tileFirst, tileStride, tileCount, tilesX, sppFirst, frames, passes, jFirst, nj, (uint32_t)entries);
+    return hipGetLastError();
 }
 
 // ... and the per-view sums of that launch's slab into the caller's images (views_accumulate_kernel)

@@ -1,7 +1,8 @@
 // tlas_build.hip — BLASBVH::SetTransform for every instance (infra/blas_bvh.cpp:363-374) and the TLASBVH::Build that follows (infra/tlas_bvh.cpp:17-70) on the
 // device, from transforms that live in device memory (crt_update_transforms_device).  ONE launch of ONE 64-lane wavefront writes a result block (TlasBuildHeader +
 // an image of the geometry buffer's TLAS node, TLAS child pair and Instance sections); the host reads it back, checks it and copies the image into the geometry
-// buffer.  The kernel never writes the geometry buffer itself.
+// buffer.  The kernel never writes the geometry buffer itself.  crt_render_poses runs the same build for P sets of transforms at once, one workgroup (of that one
+// wavefront) per set, into the P result blocks of a pose table (tlas_build_poses_kernel): such a block is a complete, relocatable pose of the scene's instances.
 //
 //   phase 1  one lane per BLAS (four rounds for 256): invT = T.FastInvertedTransformNoScale(), the world box grown over the eight corners of the BLAS's node-0
 //            box (the context's device array of root boxes) through TransformPosition, the TLAS leaf node, and the Instance record with its T / invT rows renewed.
@@ -73,13 +74,12 @@ __device__ __forceinline__ void tlas_record(const TlasLds& s, uint32_t i, uint32
     *hi = row4{s.box[3][i], s.box[4][i], s.box[5][i], __uint_as_float(ref16)};
 }
 
-// out: TlasBuildHeader, then the image (node section at 0, child pairs at pairRel, Instance records at instRel: the geometry buffer's offsets minus tlasOff)
-__global__ __launch_bounds__(kTlasLanes) void tlas_build_kernel(const char* __restrict__ geom, uint32_t instOff, const float* __restrict__ T, const float* __restrict__ rootBox,
-                                                                uint32_t n, uint32_t pairRel, uint32_t instRel, uint32_t poolRefBits, char* __restrict__ out)
+// The three phases, for the one wavefront of a workgroup: the build over the n transforms at T into `head` and `image` (node section at 0, child pairs at pairRel,
+// Instance records at instRel: the geometry buffer's offsets minus tlasOff).  One definition for the two kernels below.
+__device__ __forceinline__ void tlas_build_pose(TlasLds& s, const char* __restrict__ geom, uint32_t instOff, const float* __restrict__ T, const float* __restrict__ rootBox, uint32_t n,
+                                                uint32_t pairRel, uint32_t instRel, uint32_t poolRefBits, TlasBuildHeader* __restrict__ head, char* __restrict__ image)
 {
-    __shared__ TlasLds s;
     const uint32_t lane = threadIdx.x;
-    char* image = out + sizeof(TlasBuildHeader);
     if (n == 0u || n > kTlasMaxBlas) return;
 
     // ---- phase 1: SetTransform per BLAS, leaf nodes, Instance records ----
@@ -137,7 +137,7 @@ __global__ __launch_bounds__(kTlasLanes) void tlas_build_kernel(const char* __re
         B = tlas_partner(s, A, open, lane); searches++;
     }
     if (lane == 0u) {
-        TlasBuildHeader* h = reinterpret_cast<TlasBuildHeader*>(out);
+        TlasBuildHeader* h = head;
         h->status = status; h->step = step; h->height = (status == kTlasBuildOk) ? s.height[s.list[A]] : 0u; h->searches = searches; h->staleA = staleA;
     }
     if (status != kTlasBuildOk) return;
@@ -163,6 +163,31 @@ __global__ __launch_bounds__(kTlasLanes) void tlas_build_kernel(const char* __re
     if (n == 1u && lane < 4u) pairs[lane] = row4{0.0f, 0.0f, 0.0f, 0.0f};        // the one pair slot of a single-instance scene stays empty
 }
 
+// crt_update_transforms_device.  out: TlasBuildHeader, then the image
+__global__ __launch_bounds__(kTlasLanes) void tlas_build_kernel(const char* __restrict__ geom, uint32_t instOff, const float* __restrict__ T, const float* __restrict__ rootBox,
+                                                                uint32_t n, uint32_t pairRel, uint32_t instRel, uint32_t poolRefBits, char* __restrict__ out)
+{
+    __shared__ TlasLds s;
+    tlas_build_pose(s, geom, instOff, T, rootBox, n, pairRel, instRel, poolRefBits, reinterpret_cast<TlasBuildHeader*>(out), out + sizeof(TlasBuildHeader));
+}
+
+// crt_render_poses: P builds in one launch, workgroup p the build over T + 16 n p into header p and image p of a pose table (layout.h PoseJobHeader).  The chains are
+// independent, so they run side by side on P compute units in the time of one.  The same launch looks at the job's view -> pose indices (viewPose, K of them, or
+// nullptr: the identity): workgroup p takes every P-th group of 64, and an index outside [0, P) lowers PoseJobHeader::badView to its view (atomicMin on the word the
+// host set to kPoseNoBadView: the lowest such view remains).
+__global__ __launch_bounds__(kTlasLanes) void tlas_build_poses_kernel(const char* __restrict__ geom, uint32_t instOff, const float* __restrict__ T, const float* __restrict__ rootBox,
+                                                                      uint32_t n, uint32_t pairRel, uint32_t instRel, uint32_t poolRefBits, char* __restrict__ table, uint32_t imagesOff,
+                                                                      uint32_t imageStride, uint32_t P, const int32_t* __restrict__ viewPose, uint32_t K)
+{
+    __shared__ TlasLds s;
+    const uint32_t p = blockIdx.x;
+    if (viewPose)
+        for (unsigned long long k = (unsigned long long)p * kTlasLanes + threadIdx.x; k < K; k += (unsigned long long)P * kTlasLanes)
+            if ((uint32_t)viewPose[k] >= P) atomicMin(&reinterpret_cast<PoseJobHeader*>(table)->badView, (uint32_t)k);
+    tlas_build_pose(s, geom, instOff, T + (size_t)p * 16u * n, rootBox, n, pairRel, instRel, poolRefBits, reinterpret_cast<TlasBuildHeader*>(table + sizeof(PoseJobHeader)) + p,
+                    table + imagesOff + (size_t)p * imageStride);
+}
+
 } // namespace crt
 
 extern "C" hipError_t crt_launch_tlas_build(const char* geom, uint32_t instOff, const float* T, const float* rootBox, uint32_t blasCount, uint32_t pairRel, uint32_t instRel, uint32_t poolRefBits,
@@ -170,5 +195,16 @@ extern "C" hipError_t crt_launch_tlas_build(const char* geom, uint32_t instOff, 
 {
     if (blasCount == 0u || blasCount > crt::kTlasMaxBlas) return hipErrorInvalidValue;
     hipLaunchKernelGGL(crt::tlas_build_kernel, dim3(1), dim3(crt::kTlasLanes), 0, stream, geom, instOff, T, rootBox, blasCount, pairRel, instRel, poolRefBits, static_cast<char*>(out));
+    return hipGetLastError();
+}
+
+// P builds into a pose table (layout.h PoseJobHeader): one workgroup each.  The caller has set PoseJobHeader::badView to kPoseNoBadView on the stream.
+extern "C" hipError_t crt_launch_tlas_build_poses(const char* geom, uint32_t instOff, const float* T, const float* rootBox, uint32_t blasCount, uint32_t pairRel, uint32_t instRel,
+                                                  uint32_t poolRefBits, void* table, uint32_t imagesOff, uint32_t imageStride, uint32_t P, const int32_t* viewPose, uint32_t K, hipStream_t stream)
+{
+    if (blasCount == 0u || blasCount > crt::kTlasMaxBlas || P == 0u || (imagesOff & 63u) || (imageStride & 127u)) return hipErrorInvalidValue;
+    if ((unsigned long long)imagesOff + (unsigned long long)P * imageStride > crt::kMaxGeomBytes) return hipErrorInvalidValue;     // the render kernel's 32-bit offsets into the table
+    hipLaunchKernelGGL(crt::tlas_build_poses_kernel, dim3(P), dim3(crt::kTlasLanes), 0, stream, geom, instOff, T, rootBox, blasCount, pairRel, instRel, poolRefBits, static_cast<char*>(table),
+                       imagesOff, imageStride, P, viewPose, K);
     return hipGetLastError();
 }

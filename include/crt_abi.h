@@ -570,6 +570,51 @@ int  crt_render_views(crt_ctx* ctx, const float* cams, uint32_t K, uint32_t spp_
 int  crt_render_views_device(crt_ctx* ctx, const float* d_cams, uint32_t K, uint32_t spp_first, uint32_t frames, uint32_t passes, float scale,
                              float* d_out_rgba, uint32_t* d_out_pixels /* or NULL */, void* stream);                                          /* device pointers, no host wait */
 
+/* The frames of MANY cameras over MANY POSES of a two-level scene's instances in one render job: physics playback, a turntable of a moving assembly, a pose
+ * optimiser's candidates, the views of a training set in which the objects move.  crt_render_views renders K cameras over the one live scene; the loop that moves
+ * the instances between views — crt_update_transforms_device (one lone-wavefront build + one host wait per pose), crt_set_camera, crt_clear, crt_render, crt_read_accumulator —
+ * pays the one-frame render and the lone build K times.  Here the P builds run side by side in ONE launch (device/tlas_build.hip), each into a job-local pose: an
+ * image of the TLAS nodes, the TLAS child pairs and the Instance records; and every lane of crt_render_views' launch walks the TLAS of its own view's pose
+ * (device/render_poses.h).  The BLAS trees are shared.  ABI version 3 still: additions, detected by symbol.
+ * cams: K records of 12 floats, crt_set_camera's arguments.  T: P * blasCount row-major mat4s, pose p's at T + 16 * blasCount * p, each exactly what
+ * crt_update_transforms_device takes as d_T (cells 0..11 read, no scale).  view_pose: K indices into the poses, or NULL: view k renders pose k, and P must equal K.
+ * For every view k, with p = view_pose[k], and every pixel of a tile this context owns: out_rgba[k] (W * H float4) is bit for bit what
+ * crt_update_transforms_device(T[p]); crt_set_camera(cams[k]); crt_clear; crt_render(spp_first, frames, passes); crt_read_accumulator leaves there, w = 0
+ * included; out_pixels[k] (W * H, may be NULL) is crt_resolve_screen(scale)'s pixel of that accumulator; tlas_out[p] (host memory in BOTH entries, 2 * blasCount
+ * nodes per pose, may be NULL) is byte for byte the tlasOut of crt_update_transforms_device(T[p]).  No other pixel of the outputs is touched.
+ * THE LIVE SCENE IS NOT CHANGED: the Instance records, the TLAS, the root, the stack depth, the host mirror and the epoch stay as they are, and so do crt_tick's
+ * rendered-ahead frames, the context's camera, the accumulator, the tuner and planner tables.  Poses are job-local: they live in scratch of the entries' own (kept
+ * until crt_destroy, like crt_render_views' slab), at most 4 GiB of it (about 256 * blasCount bytes per pose).
+ * World boxes come from the node-0 boxes as the device holds them — as uploaded, as sent by CRT_UPDATE_BOUNDS, or as refitted by crt_refit_device — so a refit
+ * followed by this call needs nothing from the host.  The builds keep the reference's quirks, as crt_update_transforms_device's.
+ * Counters: crt_counters.rays, primary and mesh_hits grow as they would for the K renders.
+ * Ordering: the call is a reader under the scene-write protocol, exactly like crt_render_views_device: later writes are ordered behind it.  THE ONE HOST WAIT (both
+ * entries; besides growing scratch): the launches' LDS traversal stack is sized by the tallest pose's TLAS, and a job with a failed build or a view_pose entry out
+ * of range must not run — so the call reads the P build headers and the view_pose flag back (64 (P + 1) bytes, pinned; with tlas_out the node sections too) and
+ * returns from that wait before it enqueues the render launches.  crt_render_poses_device: d_cams (48 K bytes), d_T (64 P blasCount), d_view_pose (4 K, or NULL),
+ * d_out_rgba (16 K W H, 16-byte aligned), d_out_pixels (4 K W H, or NULL) are device pointers on cfg.device, checked as crt_render_views_device checks its
+ * buffers; `stream` a hipStream_t of that device or NULL.  crt_render_poses: host pointers, synchronous, through staging the context keeps.
+ * Refusals (nothing is written, crt_last_error says why): no scene CRT_ERR_STATE; a PrimitiveScene CRT_ERR_UNSUPPORTED; a CRT_SCENE_FILE scene CRT_ERR_INVALID;
+ * blasCount different from the uploaded bvhCount CRT_ERR_INVALID; passes outside 1..4 CRT_ERR_INVALID; K * frames > 2^31-1 CRT_ERR_UNSUPPORTED;
+ * crt_set_render_accel != 0 CRT_ERR_UNSUPPORTED (the KD-tree / grid BLAS sets live in object space and could be posed the same way: not built yet); P == 0 with
+ * K > 0, or view_pose NULL with P != K, CRT_ERR_INVALID; a pose table beyond 4 GiB, or a scene uploaded with more than 2 * bvhCount TLAS nodes (as
+ * crt_update_transforms_device), CRT_ERR_UNSUPPORTED; NULL, misaligned, host or other-device memory, a stream
+ * of another device CRT_ERR_INVALID; a view_pose entry outside [0, P) CRT_ERR_INVALID (the host entry looks before anything runs; the device entry checks in the
+ * build launch and learns of it with the headers); a pose whose build has a FindBestMatch without a candidate while more than one node is open CRT_ERR_INVALID
+ * (crt_last_error names the first such pose and the call); a pose whose TLAS height puts the traversal stack beyond the sequential kernels' LDS bound
+ * CRT_ERR_UNSUPPORTED; a failed device allocation CRT_ERR_DEVICE.  K == 0 or frames == 0 is a no-op after the checks that need no buffer.
+ * When to use it (one MI355X, 1280x720, tlas_scene.xml, profiles/render_poses.json): 64 poses of one frame each take 225 ms against 1 983 ms for the loop above (8.8x) and
+ * no longer than crt_render_views takes for the same cameras over a static scene (229 ms); 16 poses x 64 frames take 424 ms against 760 ms (1.79x; static: 400 ms).  The
+ * builds by themselves: 64 poses of 40 / 256 instances cost 0.26 / 0.64 ms inside the entry against 11.7 / 64.9 ms for 64 crt_update_transforms_device calls.  The entry
+ * beat the loop at every shape measured; crt_render_views' rule (from 256 frames per view on, loop crt_render) was not measured again for poses. */
+int  crt_render_poses(crt_ctx* ctx, const float* cams /* K * 12 */, uint32_t K, const float* T /* P * blasCount * 16 */, uint32_t P, uint32_t blasCount,
+                      const int32_t* view_pose /* K, or NULL */, uint32_t spp_first, uint32_t frames, uint32_t passes, float scale,
+                      float* out_rgba /* K * W*H float4 */, uint32_t* out_pixels /* K * W*H or NULL */,
+                      crt_tlas_node* tlas_out /* host, P * 2 * blasCount, or NULL */);                                                       /* host pointers, synchronous */
+int  crt_render_poses_device(crt_ctx* ctx, const float* d_cams, uint32_t K, const float* d_T, uint32_t P, uint32_t blasCount, const int32_t* d_view_pose /* or NULL */,
+                             uint32_t spp_first, uint32_t frames, uint32_t passes, float scale, float* d_out_rgba, uint32_t* d_out_pixels /* or NULL */,
+                             crt_tlas_node* tlas_out /* host, or NULL */, void* stream);                                                      /* device pointers, one host wait */
+
 /* ---- PrimitiveScene (second half): infra/scene/primitive_scene.cpp — the reference's hard-coded demo room (six walls, swinging light quad,
  * bouncing mirror ball, "rounded corners" sphere, spinning glass cube, glass torus; template/primitives.h Sphere :31, Cube :187, Quad :321, Torus :380; the
  * SPEEDTRIX / single-light configuration its headers select).  The binding passes the scene as its constructor + SetTime(t) leave it: the members below.
