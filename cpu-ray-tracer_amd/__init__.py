@@ -202,6 +202,7 @@ class Context:
         self.W, self.H = width, height
         self.device = device
         self._owned = True
+        self.tiles = (width // 16) * (height // 16) if tile_count < 0 else tile_count      # owned tiles
 
     @classmethod
     def borrow(cls, handle, width, height, device=0):
@@ -801,6 +802,33 @@ class Context:
         out = np.zeros(9, np.uint32)
         self._ck(f(self.h, int(what), None if r is None else _p(r), n_in, n_in if n is None else int(n), int(seed), _p(out)))
         return int(out[0]), (None if out[0] == 0 else int(out[1])), out[2:5].copy(), out[5:7].copy(), out[7:9].copy()
+
+    def job_costs(self):
+        """crt_debug_job_costs: (tile costs uint32 [owned tiles], pool window ticks, sky window ticks) as the planner holds them; CrtError (state) until a
+        measuring job's costs have been adopted or set_job_costs has installed some, and again after whatever drops them (camera, scene, accelerator)"""
+        f = self.L.crt_debug_job_costs
+        f.restype = C.c_int
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        n = getattr(self, "tiles", None)
+        if n is None: n = len(self.tile_classes())
+        out = np.zeros(max(1, n), np.uint32)
+        pool, sky = C.c_double(0), C.c_double(0)
+        rc = f(self.h, _p(out), C.byref(pool), C.byref(sky))
+        if rc != 0:
+            raise CrtError(rc, "crt_debug_job_costs: no tile costs held")
+        return out[:n], pool.value, sky.value
+
+    def set_job_costs(self, cost, pool_window_ticks, sky_window_ticks=0.0):
+        """crt_debug_set_job_costs: installs tile costs (one per owned tile, local tile order, 100 MHz ticks) and the machine time of one window of the image under
+        the pool / of its sky launch, as if a measuring job had left them: the next job is planned from them.  cost=None passes NULL (refused)."""
+        f = self.L.crt_debug_set_job_costs
+        f.restype = C.c_int
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_double, C.c_double]
+        c = None if cost is None else np.ascontiguousarray(cost, np.uint32)
+        n = getattr(self, "tiles", None)
+        if c is not None and n is not None and len(c) != n:
+            raise ValueError("set_job_costs: %d costs for %d owned tiles" % (len(c), n))
+        self._ck(f(self.h, None if c is None else _p(c), float(pool_window_ticks), float(sky_window_ticks)))
 
     def tile_classes(self, ex=False):
         """crt_debug_tile_classes: the pool kernel's tile classes as the device holds them, one byte per owned tile (TILE_NO_LIGHT | TILE_NO_FLOOR | TILE_NO_TREE);

@@ -1513,27 +1513,40 @@ static uint32_t job_order(const std::vector<uint32_t>& cost, const std::vector<u
     std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return cost[a] > cost[b]; });
     return sky_to_tail(cls, order);
 }
-static int adopt_job_costs(crt_ctx* c)
+// ... in two steps: what the measuring launch left in hJobCost (the costs, its clocks) as the planner's three inputs, and their installation.  The second step
+// alone is crt_debug_set_job_costs' (tests: a plan from GIVEN costs — the clocks of a small launch never lead to one).
+static void measured_job_costs(const crt_ctx* c, std::vector<uint32_t>& cost, double* poolWindowTicks, double* skyWindowTicks)
 {
     const uint32_t n = c->tileCount;
-    c->jobCost.assign(c->hJobCost, c->hJobCost + n);
+    cost.assign(c->hJobCost, c->hJobCost + n);
     {
         const unsigned long long* clk = reinterpret_cast<const unsigned long long*>(reinterpret_cast<const char*>(c->hJobCost) + job_cost_clk_offset(c));
         const double s0 = (clk[0] && clk[1] && clk[1] > ~clk[0]) ? (double)(clk[1] - ~clk[0]) : 0.0;
         const double drain = (double)clk[2] / (double)(c->recResident ? c->recResident : 1u);
-        c->poolWindowTicks = 0;
-        if (c->recWindows && (double)c->recWaves >= 1.5 * (double)c->recResident && s0 > 0) c->poolWindowTicks = (s0 + drain) / (double)c->recWindows / (c->recPool ? 1.0 : 1.2);
-        if (hook("CRT_LAT_VERBOSE")) fprintf(stderr, "[crt] measured %u windows with %s: %u wavefronts, last one started %.2f ms after the first, then %.2f ms of drain -> %.3f ms of machine time per window under the pool\n", c->recWindows, c->recPool ? "the pool" : "one stream per lane", c->recWaves, s0 * 1e-5, drain * 1e-5, c->poolWindowTicks * 1e-5);
+        *poolWindowTicks = 0;
+        if (c->recWindows && (double)c->recWaves >= 1.5 * (double)c->recResident && s0 > 0) *poolWindowTicks = (s0 + drain) / (double)c->recWindows / (c->recPool ? 1.0 : 1.2);
+        if (hook("CRT_LAT_VERBOSE")) fprintf(stderr, "[crt] measured %u windows with %s: %u wavefronts, last one started %.2f ms after the first, then %.2f ms of drain -> %.3f ms of machine time per window under the pool\n", c->recWindows, c->recPool ? "the pool" : "one stream per lane", c->recWaves, s0 * 1e-5, drain * 1e-5, *poolWindowTicks * 1e-5);
     }
     {
         // the job's sky launch, if it had one: its span on the device per window (it shared the machine with the pool launch; the planner adds it to its makespan aim)
         const unsigned long long* clk = reinterpret_cast<const unsigned long long*>(reinterpret_cast<const char*>(c->hJobCost) + job_cost_clk_offset(c)) + 3;
-        c->skyWindowTicks = (c->recWindows && clk[0] && clk[1] > ~clk[0]) ? (double)(clk[1] - ~clk[0]) / (double)c->recWindows : 0.0;
-        if (hook("CRT_LAT_VERBOSE")) fprintf(stderr, "[crt] the sky launch of the measuring job: %.3f ms per window\n", c->skyWindowTicks * 1e-5);
+        *skyWindowTicks = (c->recWindows && clk[0] && clk[1] > ~clk[0]) ? (double)(clk[1] - ~clk[0]) / (double)c->recWindows : 0.0;
+        if (hook("CRT_LAT_VERBOSE")) fprintf(stderr, "[crt] the sky launch of the measuring job: %.3f ms per window\n", *skyWindowTicks * 1e-5);
     }
+}
+// (the order's copy runs on the main stream behind every launch submitted so far and behind the frames rendered ahead: upload_tile_order)
+static int install_job_costs(crt_ctx* c, std::vector<uint32_t>&& cost, double poolWindowTicks, double skyWindowTicks)
+{
+    c->jobCost = std::move(cost); c->poolWindowTicks = poolWindowTicks; c->skyWindowTicks = skyWindowTicks;
     job_order(c->jobCost, c->hostClass, c->jobOrder);
     c->jobCostValid = true; c->planValid = false;
     return upload_tile_order(c, c->jobOrder);
+}
+static int adopt_job_costs(crt_ctx* c)
+{
+    std::vector<uint32_t> cost; double poolWindowTicks = 0, skyWindowTicks = 0;
+    measured_job_costs(c, cost, &poolWindowTicks, &skyWindowTicks);
+    return install_job_costs(c, std::move(cost), poolWindowTicks, skyWindowTicks);
 }
 
 // Plan of a job (one launch of `windows` windows) once the tile costs are known.  A launch ends on its slowest wavefront, and how long a wavefront runs is set by
@@ -4258,15 +4271,34 @@ extern "C" int crt_debug_slab_layout(int texel, uint32_t frames, uint32_t tileCo
     return CRT_OK;
 }
 // tools: the tile costs the planner works with (100 MHz ticks per local tile, as the measuring job left them: 0 for a tile its sky launch rendered), and the
-// machine time per window of the measuring job's pool launch and of its sky launch.  CRT_ERR_STATE until a measuring job's costs have been adopted.
+// machine time per window of the measuring job's pool launch and of its sky launch.  CRT_ERR_STATE until a measuring job's costs have been adopted (or
+// crt_debug_set_job_costs has installed some), and again once a camera or scene change has condemned them.
 extern "C" int crt_debug_job_costs(crt_ctx* c, uint32_t* out, double* poolWindowTicks, double* skyWindowTicks)
 {
     if (!c || !out) return CRT_ERR_INVALID;
-    if (!c->jobCostValid || c->jobCost.size() != c->tileCount) return CRT_ERR_STATE;
+    if (!c->jobCostValid || c->orderDirty || c->jobCost.size() != c->tileCount) return CRT_ERR_STATE;      // (orderDirty: the next crt_render drops them, update_tile_order)
     memcpy(out, c->jobCost.data(), (size_t)c->tileCount * 4);
     if (poolWindowTicks) *poolWindowTicks = c->poolWindowTicks;
     if (skyWindowTicks) *skyWindowTicks = c->skyWindowTicks;
     return CRT_OK;
+}
+// tests: tile costs (100 MHz ticks per local tile, cost[tileCount]) and the two machine-time figures installed as if a measuring job had left them — the second
+// half of adopt_job_costs, so the planner's whole input can be GIVEN (its own comes from device clocks, and a launch small enough for a test never oversubscribes
+// the chip).  First the context is brought to the state the next crt_render would start from (class table and tile order of the current camera and scene: a change
+// still pending would drop the costs again, as it drops measured ones) and a measurement in flight is settled, so that a late adoption cannot replace what is
+// installed here.  Refused, with nothing written: a context without a scene (CRT_ERR_STATE), a statistics context (CRT_ERR_STATE: it never plans).
+extern "C" int crt_debug_set_job_costs(crt_ctx* c, const uint32_t* cost, double poolWindowTicks, double skyWindowTicks)
+{
+    if (!c || !cost) return CRT_ERR_INVALID;
+    if (!(poolWindowTicks >= 0) || !(skyWindowTicks >= 0)) return c->fail(CRT_ERR_INVALID, "crt_debug_set_job_costs: the window ticks must be >= 0");
+    if (!c->haveScene) return c->fail(CRT_ERR_STATE, "crt_debug_set_job_costs before crt_upload_scene");
+    if (c->cfg.collectStats) return c->fail(CRT_ERR_STATE, "crt_debug_set_job_costs: a statistics context never plans");
+    HIPCK(c, hipSetDevice(c->cfg.device));
+    if (c->tileCount == 0) return CRT_OK;
+    { int r = update_tile_class(c); if (r) return r; }
+    { int r = update_tile_order(c); if (r) return r; }
+    if (c->jobCostPending) { HIPCK(c, hipEventSynchronize(c->jobCostCopied)); c->jobCostPending = false; }
+    return install_job_costs(c, std::vector<uint32_t>(cost, cost + c->tileCount), poolWindowTicks, skyWindowTicks);
 }
 // tests: wavefronts of the last render_pool_kernel launch that owned more than S frames (and so refilled their slots)
 extern "C" int crt_debug_pool_long_waves(crt_ctx* c) { return c ? (int)c->lastLongWaves : -1; }
