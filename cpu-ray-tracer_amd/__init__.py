@@ -110,7 +110,7 @@ HIT_INFO_DTYPE = np.dtype([("I", "<f4", 3), ("material", "<i4"), ("N", "<f4", 3)
 MATERIAL_MISS, MATERIAL_INVALID = -1, -2       # crt_hit_info.material of a miss / of a record whose objIdx or triIdx the scene does not have
 
 # every symbol include/crt_abi.h and include/crt_host.h declare (tests check the library exports all of them)
-ABI_SYMBOLS = ["crt_render_poses", "crt_render_poses_device", "crt_render_views", "crt_render_views_device", "crt_trace","crt_trace_device", "crt_build_bvh_device", "crt_get_bvh", "crt_build_kdtree_device", "crt_get_kdtree", "crt_build_grid_device", "crt_get_grid", "crt_update_transforms_device", "crt_sample", "crt_sample_device", "crt_refit_device", "crt_get_hit_info", "crt_get_hit_info_device", "crt_get_sky_color", "crt_get_sky_color_device", "crt_get_light", "crt_upload_blas_accel", "crt_is_occluded", "crt_find_nearest_device", "crt_is_occluded_device", "crt_upload_primitive_scene", "crt_set_render_accel", "crt_upload_alt_accel", "crt_find_nearest_alt", "crt_update_scene", "crt_abi_version", "crt_device_count", "crt_create", "crt_destroy", "crt_last_error", "crt_upload_scene", "crt_set_camera",
+ABI_SYMBOLS = ["crt_render_shapes", "crt_render_shapes_device", "crt_render_poses", "crt_render_poses_device", "crt_render_views", "crt_render_views_device", "crt_trace","crt_trace_device", "crt_build_bvh_device", "crt_get_bvh", "crt_build_kdtree_device", "crt_get_kdtree", "crt_build_grid_device", "crt_get_grid", "crt_update_transforms_device", "crt_sample", "crt_sample_device", "crt_refit_device", "crt_get_hit_info", "crt_get_hit_info_device", "crt_get_sky_color", "crt_get_sky_color_device", "crt_get_light", "crt_upload_blas_accel", "crt_is_occluded", "crt_find_nearest_device", "crt_is_occluded_device", "crt_upload_primitive_scene", "crt_set_render_accel", "crt_upload_alt_accel", "crt_find_nearest_alt", "crt_update_scene", "crt_abi_version", "crt_device_count", "crt_create", "crt_destroy", "crt_last_error", "crt_upload_scene", "crt_set_camera",
                "crt_render", "crt_tick", "crt_reserve", "crt_whitted_tick", "crt_whitted_tick_inspect", "crt_sync", "crt_clear", "crt_read_accumulator", "crt_resolve_screen", "crt_find_nearest", "crt_get_counters",
                "crt_reset_counters", "crt_get_timing", "crt_get_tile_clocks", "crt_bind_accumulator", "crt_accumulator_device_ptr"]
 HOST_SYMBOLS = ["crt_host_bvh_build", "crt_host_scene_bvh_move_and_rebuild", "crt_host_scene_build_bvh_device", "crt_host_scene_build_kdtree_device", "crt_host_kd_build", "crt_host_scene_build_grid_device", "crt_host_grid_build", "crt_host_scene_update_transforms_device", "crt_host_scene_bvh_refit_device", "crt_host_scene_blas_alt_info", "crt_host_scene_blas_alt_copy", "crt_host_primitive_scene_create", "crt_host_primitive_scene_free", "crt_host_primitive_scene_set_time", "crt_host_primitive_scene_desc", "crt_host_primitive_scene_upload", "crt_host_scene_build_alt", "crt_host_scene_upload_alt", "crt_host_scene_alt_info", "crt_host_scene_alt_copy", "crt_host_scene_set_transform", "crt_host_scene_update", "crt_host_math_probe", "crt_host_vertex_dedup", "crt_host_last_error", "crt_host_scene_load", "crt_host_scene_free", "crt_host_scene_upload", "crt_host_scene_kind",
@@ -325,6 +325,76 @@ class Context:
                                                     C.c_void_p(pixels.data_ptr()) if pixels is not None else None, _p(nodes) if nodes is not None else None,
                                                     C.c_void_p(st.cuda_stream)))
             res = [out] + ([pixels] if pixels is not None else []) + ([nodes] if nodes is not None else [])
+            return res[0] if len(res) == 1 else tuple(res)
+        return self._enqueue(stream, run)
+
+    def render_shapes(self, cameras, bvh, positions, spp_first, frames, passes=1, scale=None, T=None, view_shape=None, want_root_boxes=False, want_tlas=False):
+        """crt_render_shapes: the frames of K cameras over S shapes of uploaded BVH `bvh` in one job (host buffers, synchronous; the live scene is not changed).
+        cameras = [K, 12] float32 (camera_records), positions = [S, triCount, 3, 3] (or [S, triCount, 9]) float32, per shape what refit_device takes, T = None (a
+        FileScene) or [S, blasCount, 16] float32 row-major mat4s (update_transforms_device's, per shape), view_shape = None (view k renders shape k; S == K) or K
+        indices into the shapes.  Returns the accumulators [K, H, W, 4] float32 — per view what refit_device(bvh, positions[s]) (+ update_transforms_device(T[s])) +
+        set_camera + clear + render(spp_first, frames, passes) + accumulator() leaves on the tiles this context owns, every other pixel 0 —, then the pixels
+        [K, H, W] uint32 when `scale` is given, then the TLAS nodes [S, 2 * blasCount] (TLAS_DTYPE) when want_tlas, then node 0's boxes [S, 2, 3] float32 (aabbMin,
+        aabbMax: refit_device's) when want_root_boxes: a tuple when more than one."""
+        cams = np.ascontiguousarray(cameras, np.float32).reshape(-1, 12)
+        pos = np.ascontiguousarray(positions, np.float32)
+        if pos.ndim < 3 or pos.shape[2:] not in ((3, 3), (9,)):
+            raise ValueError("render_shapes: positions must be [S, triCount, 3, 3] or [S, triCount, 9] float32")
+        k, s, tris = cams.shape[0], pos.shape[0], pos.shape[1]
+        t = None if T is None else np.ascontiguousarray(T, np.float32)
+        if t is not None and (t.ndim != 3 or t.shape[2] != 16 or t.shape[0] != s):
+            raise ValueError("render_shapes: T must be [S, blasCount, 16] float32")
+        n = 0 if t is None else t.shape[1]
+        vs = None if view_shape is None else np.ascontiguousarray(view_shape, np.int32).reshape(-1)
+        if vs is not None and vs.shape[0] != k:
+            raise ValueError("render_shapes: view_shape needs one index per camera")
+        if want_tlas and t is None:
+            raise ValueError("render_shapes: a FileScene has no TLAS")
+        acc = np.zeros((k, self.H, self.W, 4), np.float32)
+        px = np.zeros((k, self.H, self.W), np.uint32) if scale is not None else None
+        nodes = np.zeros((s, 2 * n), TLAS_DTYPE) if want_tlas else None
+        boxes = np.zeros((s, 2, 3), np.float32) if want_root_boxes else None
+        self._ck(self.L.crt_render_shapes(self.h, _p(cams), C.c_uint32(k), C.c_uint32(bvh), _p(pos), C.c_uint32(s), C.c_uint32(tris), _p(t) if t is not None else None, C.c_uint32(n),
+                                          _p(vs) if vs is not None else None, C.c_uint32(spp_first), C.c_uint32(frames), C.c_uint32(passes), C.c_float(1.0 if scale is None else scale),
+                                          _p(acc), _p(px) if px is not None else None, _p(boxes) if boxes is not None else None, _p(nodes) if nodes is not None else None))
+        out = [acc] + ([px] if px is not None else []) + ([nodes] if nodes is not None else []) + ([boxes] if boxes is not None else [])
+        return out[0] if len(out) == 1 else tuple(out)
+
+    def render_shapes_device(self, cams, bvh, positions, out, spp_first, frames, passes=1, scale=None, pixels=None, T=None, view_shape=None, want_root_boxes=False, want_tlas=False,
+                             stream=None):
+        """crt_render_shapes_device: the same job for torch tensors on the context's device, enqueued on `stream` (default torch.cuda.current_stream()); one host
+        wait, for the job header (and a two-level scene's build headers).  cams = [K, 12] float32, positions = [S, triCount, 3, 3] or [S, triCount, 9] float32, T =
+        None or [S, blasCount, 16] float32, out = [K, H, W, 4] float32, pixels = None or [K, H, W] int32 (needs `scale`), view_shape = None or [K] int32, all
+        contiguous; only the pixels of owned tiles are written.  Returns out, then pixels when given, then the TLAS nodes [S, 2 * blasCount] (numpy, TLAS_DTYPE) when
+        want_tlas, then node 0's boxes [S, 2, 3] (numpy) when want_root_boxes: a tuple when more than one."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        k = cams.shape[0] if isinstance(cams, torch.Tensor) and cams.dim() == 2 else -1
+        if not isinstance(positions, torch.Tensor) or positions.dim() < 3 or tuple(positions.shape[2:]) not in ((3, 3), (9,)):
+            raise ValueError("render_shapes_device: positions must be a float32 tensor of shape [S, triCount, 3, 3] or [S, triCount, 9] on cuda:%d" % self.device)
+        s, tris = positions.shape[0], positions.shape[1]
+        n = T.shape[1] if isinstance(T, torch.Tensor) and T.dim() == 3 else (0 if T is None else -1)
+        for t, dt, shape, name in ((cams, torch.float32, (k, 12), "cams"), (positions, torch.float32, tuple(positions.shape), "positions"), (T, torch.float32, (s, n, 16), "T"),
+                                   (out, torch.float32, (k, self.H, self.W, 4), "out"), (pixels, torch.int32, (k, self.H, self.W), "pixels"), (view_shape, torch.int32, (k,), "view_shape")):
+            if t is None and name in ("pixels", "view_shape", "T"):
+                continue
+            if not isinstance(t, torch.Tensor) or t.device != dev or t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
+                raise ValueError("render_shapes_device: %s must be a contiguous %s tensor of shape %s on cuda:%d" % (name, dt, shape, self.device))
+        if pixels is not None and scale is None:
+            raise ValueError("render_shapes_device: pixels need a scale")
+        if want_tlas and T is None:
+            raise ValueError("render_shapes_device: a FileScene has no TLAS")
+        nodes = np.zeros((s, 2 * n), TLAS_DTYPE) if want_tlas else None
+        boxes = np.zeros((s, 2, 3), np.float32) if want_root_boxes else None
+
+        def run(st):
+            self._ck(self.L.crt_render_shapes_device(self.h, C.c_void_p(cams.data_ptr()), C.c_uint32(k), C.c_uint32(bvh), C.c_void_p(positions.data_ptr()), C.c_uint32(s), C.c_uint32(tris),
+                                                     C.c_void_p(T.data_ptr()) if T is not None else None, C.c_uint32(n),
+                                                     C.c_void_p(view_shape.data_ptr()) if view_shape is not None else None, C.c_uint32(spp_first), C.c_uint32(frames),
+                                                     C.c_uint32(passes), C.c_float(1.0 if scale is None else scale), C.c_void_p(out.data_ptr()),
+                                                     C.c_void_p(pixels.data_ptr()) if pixels is not None else None, _p(boxes) if boxes is not None else None,
+                                                     _p(nodes) if nodes is not None else None, C.c_void_p(st.cuda_stream)))
+            res = [out] + ([pixels] if pixels is not None else []) + ([nodes] if nodes is not None else []) + ([boxes] if boxes is not None else [])
             return res[0] if len(res) == 1 else tuple(res)
         return self._enqueue(stream, run)
 

@@ -130,6 +130,7 @@ struct crt_ctx {
     // crt_destroy) — the slab pool and crt_tick's held regions are not touched; viewsDone: behind the last call's last accumulate, on that call's stream (the next
     // call's stream waits for it before it writes the slab again)
     char* dViewsSlab = nullptr; size_t viewsSlabCap = 0; hipEvent_t viewsDone = nullptr; bool viewsPending = false;
+    // (crt_render_shapes / crt_render_shapes_device keep their shape table, layout.h ShapeJobHeader, and its pinned copy in the same four: a job-local table either way)
     // crt_render_poses / crt_render_poses_device: the job's pose table (device/layout.h PoseJobHeader: P build headers, P images of [tlasOff, shadeOff)), scratch of the
     // entries' own like dViewsSlab and ordered by the same event (the job's launches read it to the end); hPoseBack: the pinned copy of the headers (and, for
     // tlas_out, of the images' node sections), poseBack: behind that read-back (the entries' one host wait)
@@ -3650,8 +3651,9 @@ static int views_scratch(crt_ctx* c, uint32_t totalWindows, size_t windowBytes, 
 
 // the job on `st`, after every check: launches of whole windows, each followed by its per-view sums into the caller's images
 // (poses: crt_render_poses' job — the launches read every lane's TLAS and Instance records from its view's pose in that table, with jobScene's stack depth)
+// (shapes: crt_render_shapes' job — ... every lane's refitted BVH, and a two-level scene's TLAS and Instance records, from its view's shape in that table)
 static int views_run(crt_ctx* c, const float* dCams, uint32_t K, uint32_t sppFirst, uint32_t frames, uint32_t passes, float scale, float* dRgba, uint32_t* dPixels, hipStream_t st,
-                     const crt::Scene* jobScene = nullptr, const crt::PoseTableDev* poses = nullptr)
+                     const crt::Scene* jobScene = nullptr, const crt::PoseTableDev* poses = nullptr, const crt::ShapeTableDev* shapes = nullptr)
 {
     if (c->tileCount == 0) return 0;
     const uint32_t total = K * frames, totalWindows = (total + 63u) / 64u;
@@ -3663,7 +3665,8 @@ static int views_run(crt_ctx* c, const float* dCams, uint32_t K, uint32_t sppFir
     if (c->renderAccel != 0 && c->altReady) HIPCK(c, hipStreamWaitEvent(st, c->altReady, 0));   // the accelerators' copies ran on the null stream
     for (uint32_t j0 = 0; j0 < total; j0 += wl * 64u) {
         const uint32_t nj = (total - j0 < wl * 64u) ? total - j0 : wl * 64u;
-        if (poses) HIPCK(c, crt_launch_render_poses(jobScene, poses, dCams, c->dViewsSlab, c->dCounters, c->tileFirst, c->tileStride, c->tileCount, (uint32_t)c->tilesX, sppFirst, frames, passes, j0, nj, st));
+        if (shapes) HIPCK(c, crt_launch_render_shapes(jobScene, shapes, dCams, c->dViewsSlab, c->dCounters, c->tileFirst, c->tileStride, c->tileCount, (uint32_t)c->tilesX, sppFirst, frames, passes, j0, nj, st));
+        else if (poses) HIPCK(c, crt_launch_render_poses(jobScene, poses, dCams, c->dViewsSlab, c->dCounters, c->tileFirst, c->tileStride, c->tileCount, (uint32_t)c->tilesX, sppFirst, frames, passes, j0, nj, st));
         else if (c->havePrim) HIPCK(c, crt_launch_render_views_prim(&c->hScene, &c->prim, dCams, c->dViewsSlab, c->dCounters, c->tileFirst, c->tileStride, c->tileCount, (uint32_t)c->tilesX, sppFirst, frames, passes, j0, nj, st));
         else HIPCK(c, crt_launch_render_views(c->renderAccel, &c->hScene, &c->alt, c->renderAccel ? &c->blasAlt[c->renderAccel - 1] : nullptr, dCams, c->dViewsSlab, c->dCounters, c->tileFirst,
                                               c->tileStride, c->tileCount, (uint32_t)c->tilesX, sppFirst, frames, passes, j0, nj, st));
@@ -3876,6 +3879,177 @@ int crt_render_poses(crt_ctx* c, const float* cams, uint32_t K, const float* T, 
     if (dViewPose) HIPCK(c, hipMemcpyAsync(dViewPose, view_pose, (size_t)K * 4, hipMemcpyHostToDevice, c->stream));
     if ((r = poses_run(c, dCams, K, dT, P, dViewPose, spp_first, frames, passes, scale, S.dRgba, S.dPix, tlas_out, c->stream, what))) return r;
     return views_stage_out(c, K, out_rgba, out_pixels, S);
+}
+
+// ---- crt_render_shapes / crt_render_shapes_device: the frames of K cameras over S job-local shapes of one refitted BVH (device/shape_build.hip, render_shapes.h) ----
+// where a job's shape table keeps what (device/layout.h ShapeJobHeader)
+struct ShapeLayout {
+    bool tlas; uint32_t N, rowFloats, pairCount, triCount;
+    size_t headBytes, poseBytes, tableBytes; uint32_t headsOff, rowsOff, imagesOff, imageStride, leafRel, poseRel;
+    ShapeLayout(const crt_ctx::Flat& f, uint32_t bvh, uint32_t S)
+    {
+        tlas = f.kind == CRT_SCENE_TLAS; N = (uint32_t)f.triCount.size();
+        rowFloats = tlas ? 6u * N : 6u;
+        pairCount = f.nodesUsed[bvh] / 2; triCount = f.triCount[bvh];
+        headsOff = (uint32_t)sizeof(crt::ShapeJobHeader);
+        headBytes = headsOff + (tlas ? (size_t)S * sizeof(crt::TlasBuildHeader) : 0);      // what the one host wait reads: the flag and the build headers
+        const size_t rowsAt = headBytes, imagesAt = (rowsAt + (size_t)S * rowFloats * 4u + 127u) & ~(size_t)127u;
+        const size_t leafAt = (size_t)(pairCount ? pairCount : 1u) * 64u, poseAt = (leafAt + (size_t)triCount * 48u + 127u) & ~(size_t)127u;
+        poseBytes = tlas ? (size_t)(f.shadeOff - f.tlasOff) : 0;
+        const size_t stride = (poseAt + poseBytes + 127u) & ~(size_t)127u;
+        tableBytes = imagesAt + (size_t)S * stride + 64u;                   // (+ 64: a fetch of 64 bytes at the last record's last row stays inside)
+        // shapes_check refuses a table beyond 4 GiB before anything uses the 32-bit fields
+        rowsOff = (uint32_t)rowsAt; imagesOff = (uint32_t)imagesAt; imageStride = (uint32_t)stride; leafRel = (uint32_t)leafAt; poseRel = (uint32_t)poseAt;
+    }
+};
+
+// the checks that need no buffer, in the order crt_abi.h lists the refusals
+static int shapes_check(crt_ctx* c, uint32_t K, uint32_t bvh, uint32_t S, uint32_t triCount, bool haveT, uint32_t blasCount, bool viewShape, uint32_t frames, uint32_t passes, const char* what)
+{
+    if (!c->haveScene && !c->havePrim) return c->fail(CRT_ERR_STATE, "%s before crt_upload_scene", what);
+    if (c->havePrim) return c->fail(CRT_ERR_UNSUPPORTED, "%s: the PrimitiveScene has no BVH to refit", what);
+    const crt_ctx::Flat& f = c->flat;
+    const uint32_t N = (uint32_t)f.triCount.size();
+    if (bvh >= N) return c->fail(CRT_ERR_INVALID, "%s: BVH %u of a scene with %u", what, bvh, N);
+    if (triCount != f.triCount[bvh]) return c->fail(CRT_ERR_INVALID, "%s: %u triangles per shape, the uploaded BVH %u has %u (Refit keeps the topology)", what, triCount, bvh, f.triCount[bvh]);
+    if (f.kind != CRT_SCENE_TLAS) {
+        if (haveT || blasCount != 0) return c->fail(CRT_ERR_INVALID, "%s: a FileScene has no instances (T must be NULL and blasCount 0)", what);
+    } else {
+        if (!haveT || blasCount != N) return c->fail(CRT_ERR_INVALID, "%s: %u transforms per shape%s, the uploaded scene has %u BLAS", what, blasCount, haveT ? "" : " (T is NULL)", N);
+        if (f.tlasNodeCount != 2u * N) return c->fail(CRT_ERR_UNSUPPORTED, "%s: the scene was uploaded with %u TLAS nodes, TLASBVH::Build makes %u", what, f.tlasNodeCount, 2u * N);
+    }
+    if (passes < 1 || passes > 4) return c->fail(CRT_ERR_INVALID, "%s: passes must be 1..4 (the reference's UI range, renderer.cpp:178)", what);
+    if ((uint64_t)K * frames > 0x7fffffffull) return c->fail(CRT_ERR_UNSUPPORTED, "%s: at most 2^31-1 view-frames per call (%u views x %u frames)", what, K, frames);
+    if (c->renderAccel != 0) return c->fail(CRT_ERR_UNSUPPORTED, "%s: the KD-tree / grid structures have no refit (crt_set_render_accel(0) first; crt_refit_device drops those sets too)", what);
+    if (K > 0 && S == 0) return c->fail(CRT_ERR_INVALID, "%s: %u views and no shape", what, K);
+    if (!viewShape && S != K) return c->fail(CRT_ERR_INVALID, "%s: without view_shape view k renders shape k, so S (%u) must equal K (%u)", what, S, K);
+    const ShapeLayout L(f, bvh, S);
+    if (L.tableBytes > crt::kMaxGeomBytes)
+        return c->fail(CRT_ERR_UNSUPPORTED, "%s: %u shapes of %u bytes each exceed the 4 GiB the kernel's 32-bit offsets address; split the job", what, S, L.imageStride);
+    return 0;
+}
+
+// The job on `st`, after the checks that need no launch: the S shapes (leaf launch, box launch, for a two-level scene the S TLAS builds), the read-back of the
+// view_shape flag and the build headers (THE host wait; with root_box_out / tlas_out the boxes / node sections too), the checks of what came back, then
+// crt_render_views' launches over the table.  dViewShape may be nullptr (view k renders shape k); dT is nullptr for a FileScene.
+static int shapes_run(crt_ctx* c, const float* dCams, uint32_t K, uint32_t bvh, const float* dPos, uint32_t S, const float* dT, const int32_t* dViewShape, uint32_t sppFirst, uint32_t frames,
+                      uint32_t passes, float scale, float* dRgba, uint32_t* dPixels, float* rootBoxOut, crt_tlas_node* tlasOut, hipStream_t st, const char* what)
+{
+    const crt_ctx::Flat& f = c->flat;
+    const ShapeLayout L(f, bvh, S);
+    const uint32_t N = L.N;
+    int r;
+    if (c->refitPlans.size() != f.triCount.size()) c->refitPlans.assign(f.triCount.size(), crt_ctx::RefitPlan{});
+    if (!c->refitPlans[bvh].built && (r = build_refit_plan(c, bvh))) return r;
+    const crt_ctx::RefitPlan& P = c->refitPlans[bvh];
+    const size_t nodeBytes = (size_t)2u * N * sizeof(crt::TlasNode);
+    const size_t boxesAt = L.headBytes, nodesAt = boxesAt + (rootBoxOut ? (size_t)S * 24u : 0), backBytes = nodesAt + (tlasOut && L.tlas ? (size_t)S * nodeBytes : 0);
+    // The builds are readers, as crt_render_poses': the live pairs, leaf records, Instance records and node-0 boxes as the last write left them.
+    if ((r = wait_scene(c, st))) return r;
+    // the table is read by the previous job's launches to their end: viewsDone, on that job's stream
+    HIPCK(c, ensure_event(&c->viewsDone));
+    HIPCK(c, ensure_event(&c->poseBack));
+    if (L.tableBytes > c->poseTableCap) {
+        if (c->viewsPending) { HIPCK(c, hipEventSynchronize(c->viewsDone)); c->viewsPending = false; }
+        if (c->dPoseTable) { HIPCK(c, hipFree(c->dPoseTable)); c->dPoseTable = nullptr; c->poseTableCap = 0; }
+        HIPCK(c, hipMalloc((void**)&c->dPoseTable, L.tableBytes));
+        c->poseTableCap = L.tableBytes;
+    }
+    if (backBytes > c->poseBackCap) {                                       // (no copy into it is in flight: every call waits for its own)
+        if (c->hPoseBack) { HIPCK(c, hipHostFree(c->hPoseBack)); c->hPoseBack = nullptr; c->poseBackCap = 0; }
+        HIPCK(c, hipHostMalloc((void**)&c->hPoseBack, backBytes, hipHostMallocDefault));
+        c->poseBackCap = backBytes;
+    }
+    if (c->viewsPending) HIPCK(c, hipStreamWaitEvent(st, c->viewsDone, 0));
+    char* table = c->dPoseTable;
+    HIPCK(c, hipMemsetAsync(table, 0xff, sizeof(uint32_t), st));            // ShapeJobHeader::badView = kPoseNoBadView
+    const crt::ShapeBuildDev sb{c->hScene.geom, (uint32_t)f.leafOff, (uint32_t)f.pairBase[bvh], L.pairCount, (uint32_t)f.triBase[bvh], L.triCount, dPos,
+                                L.tlas ? c->dRootBox : nullptr, L.rowFloats, L.tlas ? bvh : 0u, table, L.rowsOff, L.imagesOff, L.imageStride, L.leafRel, S};
+    HIPCK(c, crt_launch_shape_build(&sb, P.dPlan, P.dLevelOff, P.levels, P.rootCode, dViewShape, K, st));
+    if (L.tlas)
+        HIPCK(c, crt_launch_tlas_build_shapes(c->hScene.geom, (uint32_t)f.instOff, dT, reinterpret_cast<const float*>(table + L.rowsOff), N, (uint32_t)(f.tlasPairOff - f.tlasOff),
+                                              (uint32_t)(f.instOff - f.tlasOff), c->hScene.poolRefBits, table, L.headsOff, L.imagesOff + L.poseRel, L.imageStride, S, st));
+    if (rootBoxOut) HIPCK(c, hipMemcpy2DAsync(c->hPoseBack + boxesAt, 24, table + L.rowsOff + (size_t)sb.bvh * 24u, (size_t)L.rowFloats * 4u, 24, S, hipMemcpyDeviceToHost, st));
+    if (tlasOut && L.tlas) HIPCK(c, hipMemcpy2DAsync(c->hPoseBack + nodesAt, nodeBytes, table + L.imagesOff + L.poseRel, L.imageStride, nodeBytes, S, hipMemcpyDeviceToHost, st));
+    // the one host wait: a job with a view_shape entry out of range or a failed build does not run, and the launches' LDS stack is sized by the tallest shape's TLAS
+    if ((r = read_back(c, st, c->poseBack, c->hPoseBack, table, L.headBytes))) return r;
+    const crt::ShapeJobHeader& job = *reinterpret_cast<const crt::ShapeJobHeader*>(c->hPoseBack);
+    if (job.badView != crt::kPoseNoBadView) return c->fail(CRT_ERR_INVALID, "%s: view_shape[%u] lies outside [0, %u)", what, job.badView, S);
+    crt::Scene job_scene = c->hScene;                                       // the launches' by-value Scene: the context's, with the job's stack depth.  c->hScene stays as it is
+    if (L.tlas) {
+        const crt::TlasBuildHeader* heads = reinterpret_cast<const crt::TlasBuildHeader*>(c->hPoseBack + L.headsOff);
+        uint32_t tallest = 0, tallestShape = 0;
+        for (uint32_t s = 0; s < S; s++) {
+            const crt::TlasBuildHeader& h = heads[s];
+            if (h.status == crt::kTlasBuildNoCandidate)
+                return c->fail(CRT_ERR_INVALID, "%s: shape %u: FindBestMatch call %u found no partner while more than one node was open (a non-finite transform, position or box, or areas >= 1e30; the reference reads list[-1] there)", what, s, h.step);
+            if (h.status != crt::kTlasBuildOk) return c->fail(CRT_ERR_INVALID, "%s: shape %u: the build had not ended after %u FindBestMatch calls", what, s, h.step);
+            if (h.height > tallest) { tallest = h.height; tallestShape = s; }
+        }
+        job_scene.stackDepth = job_scene.bvhStack + tallest + 1;
+        if ((r = check_tlas_height(c, tallest))) return r;
+        if (!sample_lds_fits(job_scene.stackDepth))
+            return c->fail(CRT_ERR_UNSUPPORTED, "%s: shape %u: a TLAS of height %u makes the traversal stack %u dwords per lane, which exceeds the kernel's LDS", what, tallestShape, tallest, job_scene.stackDepth);
+    } else if (!sample_lds_fits(job_scene.stackDepth))
+        return c->fail(CRT_ERR_UNSUPPORTED, "%s: a traversal stack of %u dwords per lane exceeds the kernel's LDS", what, job_scene.stackDepth);
+    // node 0 of the refitted BVH as the image names it (shape_build.hip image_ref)
+    const uint32_t rootRef = (P.rootCode & crt::kPlanInterior) ? (crt::kRefInterior | ((P.rootCode & ~crt::kPlanInterior) * 4u)) : ((L.leafRel + P.rootCode * 48u) >> 4);
+    const crt::ShapeTableDev tb{table, dViewShape, L.imagesOff, L.imageStride, rootRef, bvh, L.poseRel, (uint32_t)(f.instOff - f.tlasOff)};
+    if ((r = views_run(c, dCams, K, sppFirst, frames, passes, scale, dRgba, dPixels, st, &job_scene, nullptr, &tb))) return r;
+    // the host outputs last, once nothing can refuse the job any more (the pinned copy is the call's own until it returns): a refused call writes nothing
+    if (rootBoxOut) memcpy(rootBoxOut, c->hPoseBack + boxesAt, (size_t)S * 24u);
+    if (tlasOut && L.tlas)
+        for (uint32_t s = 0; s < S; s++) unpack_tlas_nodes(reinterpret_cast<const crt::TlasNode*>(c->hPoseBack + nodesAt + s * nodeBytes), 2u * N, tlasOut + (size_t)s * 2u * N);
+    return 0;
+}
+
+int crt_render_shapes_device(crt_ctx* c, const float* d_cams, uint32_t K, uint32_t bvh, const float* d_positions, uint32_t S, uint32_t triCount, const float* d_T, uint32_t blasCount,
+                             const int32_t* d_view_shape, uint32_t spp_first, uint32_t frames, uint32_t passes, float scale, float* d_out_rgba, uint32_t* d_out_pixels, float* root_box_out,
+                             crt_tlas_node* tlas_out, void* stream)
+{
+    if (!c) return CRT_ERR_INVALID;
+    const char* what = "crt_render_shapes_device";
+    int r;
+    if ((r = shapes_check(c, K, bvh, S, triCount, d_T != nullptr, blasCount, d_view_shape != nullptr, frames, passes, what))) return r;
+    if (K == 0 || frames == 0) return CRT_OK;
+    const size_t px = (size_t)c->cfg.width * c->cfg.height;
+    if (reinterpret_cast<uintptr_t>(d_out_rgba) & 15u) return c->fail(CRT_ERR_INVALID, "%s: d_out_rgba %p is not 16-byte aligned", what, (void*)d_out_rgba);
+    hipStream_t st = nullptr; int k = 0;
+    if ((r = device_entry(c, what, {{d_cams, (size_t)K * 48}, {d_positions, (size_t)S * triCount * 36}, {d_out_rgba, K * px * 16}}, stream, &st))) return r;
+    if (d_T && (r = check_device_buffer(c, d_T, (size_t)S * blasCount * 64, what))) return r;
+    if (d_out_pixels && (r = check_device_buffer(c, d_out_pixels, K * px * 4, what))) return r;
+    if (d_view_shape && (r = check_device_buffer(c, d_view_shape, (size_t)K * 4, what))) return r;
+    if ((r = take_query_slot(c, &k))) return r;
+    if ((r = shapes_run(c, d_cams, K, bvh, d_positions, S, d_T, d_view_shape, spp_first, frames, passes, scale, d_out_rgba, d_out_pixels, root_box_out, tlas_out, st, what))) return r;
+    return end_device_query(c, k, st);
+}
+
+int crt_render_shapes(crt_ctx* c, const float* cams, uint32_t K, uint32_t bvh, const float* positions, uint32_t S, uint32_t triCount, const float* T, uint32_t blasCount,
+                      const int32_t* view_shape, uint32_t spp_first, uint32_t frames, uint32_t passes, float scale, float* out_rgba, uint32_t* out_pixels, float* root_box_out,
+                      crt_tlas_node* tlas_out)
+{
+    if (!c) return CRT_ERR_INVALID;
+    const char* what = "crt_render_shapes";
+    int r;
+    if ((r = shapes_check(c, K, bvh, S, triCount, T != nullptr, blasCount, view_shape != nullptr, frames, passes, what))) return r;
+    if (K == 0 || frames == 0) return CRT_OK;
+    if (!cams || !positions || !out_rgba) return c->fail(CRT_ERR_INVALID, "%s: NULL buffer", what);
+    if (view_shape)
+        for (uint32_t k = 0; k < K; k++)
+            if (view_shape[k] < 0 || (uint32_t)view_shape[k] >= S) return c->fail(CRT_ERR_INVALID, "%s: view_shape[%u] = %d lies outside [0, %u)", what, k, view_shape[k], S);
+    HIPCK(c, hipSetDevice(c->cfg.device));
+    const size_t camBytes = (size_t)K * 48, posBytes = ((size_t)S * triCount * 36 + 15u) & ~(size_t)15u, tBytes = (size_t)S * blasCount * 64;
+    ViewsStage G;
+    if ((r = views_stage_in(c, K, out_rgba, out_pixels, camBytes + posBytes + tBytes + (view_shape ? (size_t)K * 4 : 0), &G))) return r;
+    float* dCams = reinterpret_cast<float*>(G.extra); float* dPos = reinterpret_cast<float*>(G.extra + camBytes);
+    float* dT = T ? reinterpret_cast<float*>(G.extra + camBytes + posBytes) : nullptr;
+    int32_t* dViewShape = view_shape ? reinterpret_cast<int32_t*>(G.extra + camBytes + posBytes + tBytes) : nullptr;
+    HIPCK(c, hipMemcpyAsync(dCams, cams, camBytes, hipMemcpyHostToDevice, c->stream));
+    HIPCK(c, hipMemcpyAsync(dPos, positions, (size_t)S * triCount * 36, hipMemcpyHostToDevice, c->stream));
+    if (dT) HIPCK(c, hipMemcpyAsync(dT, T, tBytes, hipMemcpyHostToDevice, c->stream));
+    if (dViewShape) HIPCK(c, hipMemcpyAsync(dViewShape, view_shape, (size_t)K * 4, hipMemcpyHostToDevice, c->stream));
+    if ((r = shapes_run(c, dCams, K, bvh, dPos, S, dT, dViewShape, spp_first, frames, passes, scale, G.dRgba, G.dPix, root_box_out, tlas_out, c->stream, what))) return r;
+    return views_stage_out(c, K, out_rgba, out_pixels, G);
 }
 
 // tools / tests: the lanes a full sample-query launch of this scene and accelerator holds at once (the grid is that many lanes, or fewer when the rays need fewer)

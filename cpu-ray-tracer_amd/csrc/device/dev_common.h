@@ -445,14 +445,19 @@ __device__ __forceinline__ void to_object_space(rec4 r0, rec4 r1, rec4 r2, f3 O,
 // sequential reference-order traversal (used by find_nearest_kernel: it reports Ray::traversed / tested, which
 // count loop trips in the reference's order — infra/bvh.cpp:224-258, infra/tlas_bvh.cpp:83-111)
 // ------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void traverse_bvh_seq(const Scene& sc, uint32_t rootRef, f3 O, f3 D, f3 rD, Hit& h, uint32_t* stk, Cnt& cn,
+// Where the walk finds its BVH: bvh_base(w) + bvh_record(w, ref) = the NodePair / first LeafTri a reference names.  For a Scene the geometry buffer and the
+// reference's own offset, below; a job-local shape names its image of one BVH, whose references are image-relative (render_shapes.h ShapeBvh).
+__device__ __forceinline__ const char* bvh_base(const Scene& sc) { return sc.geom; }
+__device__ __forceinline__ uint32_t bvh_record(const Scene&, uint32_t ref) { return (ref & kRefOffsetMask) << 4; }
+template <class Where>
+__device__ __forceinline__ void traverse_bvh_seq(const Where& sc, uint32_t rootRef, f3 O, f3 D, f3 rD, Hit& h, uint32_t* stk, Cnt& cn,
                                                  int& traversed, int& tested)
 {
-    const char* __restrict__ g = sc.geom;
+    const char* __restrict__ g = bvh_base(sc);
     uint32_t cur = rootRef, sp = 0;
     for (;;) {
         traversed++;
-        const uint32_t off = (cur & kRefOffsetMask) << 4;
+        const uint32_t off = bvh_record(sc, cur);
         if (cur & kRefInterior) {
             cn.interior++;
             const rec4 alo = ldg(g, off), ahi = ldg(g, off + 16), blo = ldg(g, off + 32), bhi = ldg(g, off + 48);

@@ -74,6 +74,10 @@ hipError_t crt_launch_render_views(int accel, const crt::Scene* sc, const crt::A
 // sc->stackDepth is the job's.  The per-view sums are crt_launch_views_accumulate's.
 hipError_t crt_launch_render_poses(const crt::Scene* sc, const crt::PoseTableDev* pt, const float* cams, void* slab, crt::Counters* counters, uint32_t tileFirst, uint32_t tileStride,
     uint32_t tileCount, uint32_t tilesX, uint32_t sppFirst, uint32_t frames, uint32_t passes, uint32_t jFirst, uint32_t nj, hipStream_t stream);
+// crt_render_shapes (render_shapes.h, render_shapes.hip): the same launch with every lane's refitted BVH (and, two-level, its TLAS and Instance records) taken from its
+// view's shape in the table `t` names; sc->stackDepth is the job's.  The per-view sums are crt_launch_views_accumulate's.
+hipError_t crt_launch_render_shapes(const crt::Scene* sc, const crt::ShapeTableDev* t, const float* cams, void* slab, crt::Counters* counters, uint32_t tileFirst, uint32_t tileStride,
+    uint32_t tileCount, uint32_t tilesX, uint32_t sppFirst, uint32_t frames, uint32_t passes, uint32_t jFirst, uint32_t nj, hipStream_t stream);
 hipError_t crt_launch_views_accumulate(const void* slab, float* outRgba, uint32_t* outPixels, uint32_t tileFirst, uint32_t tileStride, uint32_t tileCount, uint32_t tilesX, uint32_t W,
     uint32_t H, uint32_t frames, uint32_t passes, uint32_t jFirst, uint32_t nj, float scale, hipStream_t stream);
 
@@ -140,6 +144,15 @@ hipError_t crt_launch_tlas_build(const char* geom, uint32_t instOff, const float
 // view -> pose indices (viewPose may be nullptr); the caller sets PoseJobHeader::badView to kPoseNoBadView on the stream first
 hipError_t crt_launch_tlas_build_poses(const char* geom, uint32_t instOff, const float* T, const float* rootBox, uint32_t blasCount, uint32_t pairRel, uint32_t instRel, uint32_t poolRefBits,
     void* table, uint32_t imagesOff, uint32_t imageStride, uint32_t P, const int32_t* viewPose, uint32_t K, hipStream_t stream);
+// S such builds, each from its own row of node-0 boxes, into the pose images of a shape table (layout.h ShapeJobHeader); posesOff: the first image's pose image
+hipError_t crt_launch_tlas_build_shapes(const char* geom, uint32_t instOff, const float* T, const float* rootBoxRows, uint32_t blasCount, uint32_t pairRel, uint32_t instRel,
+    uint32_t poolRefBits, void* table, uint32_t headsOff, uint32_t posesOff, uint32_t imageStride, uint32_t S, hipStream_t stream);
+
+// ---- shape_build.hip ----
+// crt_render_shapes: BVH::Refit of one BVH for b->S sets of positions into the images of a shape table, the rows of node-0 boxes, and the check of the K view -> shape
+// indices (viewShape may be nullptr); the caller sets ShapeJobHeader::badView to kPoseNoBadView on the stream first.  plan / levelOff / levels / rootCode: crt_launch_refit's
+hipError_t crt_launch_shape_build(const crt::ShapeBuildDev* b, const void* plan, const uint32_t* levelOff, uint32_t levels, uint32_t rootCode, const int32_t* viewShape, uint32_t K,
+    hipStream_t stream);
 
 // abi.cpp's test switch CRT_DEBUG_QUERY_GRID=<k>: an upper bound on the workgroups of a persistent query launch (0: none).  Host side only: each wrapper passes its grid through it.
 uint32_t crt_debug_query_grid(void);

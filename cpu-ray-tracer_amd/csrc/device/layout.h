@@ -181,6 +181,30 @@ struct PoseTableDev {
     const char* table; const int32_t* viewPose;   // viewPose == nullptr: view k renders pose k
     uint32_t imagesOff, imageStride, instRel;     // instRel: the Instance records' offset inside an image (instOff - tlasOff)
 };
+// crt_render_shapes' shape table (shape_build.hip writes it, render_shapes.h reads it): this header, S rows of node-0 boxes (rowFloats each: the live root boxes with
+// the refitted BVH's entry replaced; a FileScene's row is that one box), for a two-level scene S TlasBuildHeaders, then — at imagesOff, imageStride apart, both
+// multiples of 128 — the S images.  An image holds the refitted BVH's NodePairs at 0, its LeafTris at leafRel and, for a two-level scene, a pose image (the build's
+// [tlasOff, shadeOff)) at poseRel.  References inside an image's pairs are IMAGE-RELATIVE 16-byte offsets (the box kernel rewrites them as it copies the pairs), so a
+// lane finds a record at table + (its image's offset + (ref << 4)): one per-lane delta.  leafRel >= 64, so a leaf's reference is never 0 here either.  The whole
+// table stays within kMaxGeomBytes, as the pose table does.
+struct alignas(64) ShapeJobHeader {
+    uint32_t badView;                     // the lowest view whose view_shape entry lies outside [0, S); kPoseNoBadView: none
+    uint32_t pad[15];
+};
+// what the build kernels take by value
+struct ShapeBuildDev {
+    const char* geom; uint32_t leafOff, pairBase, pairCount, triBase, triCount;    // the live BVH: its pairs at 64 pairBase, its leaf slots at leafOff + 48 triBase
+    const float* pos;                                                             // S * triCount * 9
+    const float* liveRootBox; uint32_t rowFloats, bvh;                            // nullptr (FileScene: rowFloats 6, entry 0) or the device's node-0 boxes
+    char* table; uint32_t rowsOff, imagesOff, imageStride, leafRel, S;
+};
+// what the render kernel takes by value: where the table is and how a view finds its shape in it
+struct ShapeTableDev {
+    const char* table; const int32_t* viewShape;  // viewShape == nullptr: view k renders shape k
+    uint32_t imagesOff, imageStride;
+    uint32_t rootRef;                             // the refitted BVH's node 0, image-relative
+    uint32_t bvh, poseRel, instRel;               // two-level: the instance that walks the image; the pose image inside an image; the Instance records inside that
+};
 constexpr uint32_t kTlasMaxBlas = 256u;   // tlas_bvh.cpp:21 (nodeIdx[256])
 
 // Whether a crt_hit's indices may be used as addresses by the hit-info query (shade_query.hip): ONE predicate for the host entry, which refuses the call, and for

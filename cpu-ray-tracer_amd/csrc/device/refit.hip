@@ -7,48 +7,17 @@
 //                      producer and consumer of a box are waves of the same CU, so workgroup scope orders them and no cross-workgroup protocol exists.
 //                      The order comes from a plan the host builds once per BVH from its mirror of the references (RefitPlanRec, 32-bit indices).
 //
+// The comparison forms and a node's box (node_box) are refit_common.h's, shared with shape_build.hip (crt_render_shapes: the same refit into job-local images).
 // Bit for bit the reference's loop: a leaf's box is UpdateNodeBounds (starts from +-1e30, triangles in leaf order, vertices 0, 1, 2, taken from the caller's
 // positions — never from v0 + e1, which rounds), an interior node's box is min / max of its children, both as `a < b ? a : b` / `a > b ? a : b` in the
 // reference's operand order (tmplmath.h:122-123; fminf / fmaxf and the min / max instructions differ on NaN and on +-0), and NODE 1 IS SKIPPED
 // (bvh.cpp:28 `if (i != 1)`): the root's left child keeps the box it had, and that stale box still feeds node 0's.  -ffp-contract=off as everywhere.
 #include "launch.h"
+#include "refit_common.h"
 
 namespace crt {
 
-typedef float row4 __attribute__((ext_vector_type(4)));
-
 constexpr uint32_t kRefitBoxThreads = 1024u;
-
-__device__ __forceinline__ float lesser(float a, float b) { return a < b ? a : b; }
-__device__ __forceinline__ float greater(float a, float b) { return a > b ? a : b; }
-
-struct Box { float lo[3], hi[3]; };
-
-// the box of the node a child code names: UpdateNodeBounds for a leaf, the union of the two children for an interior node (whose pair an earlier level wrote)
-__device__ __forceinline__ Box node_box(const char* geom, uint32_t leafOff, uint32_t pairBase, uint32_t triBase, uint32_t triCount, const float* pos, uint32_t code)
-{
-    Box b;
-    if (code & kPlanInterior) {
-        const row4* p = reinterpret_cast<const row4*>(geom + (size_t)(pairBase + (code & ~kPlanInterior)) * 64u);
-        const row4 llo = p[0], lhi = p[1], rlo = p[2], rhi = p[3];
-        b.lo[0] = lesser(llo.x, rlo.x); b.lo[1] = lesser(llo.y, rlo.y); b.lo[2] = lesser(llo.z, rlo.z);
-        b.hi[0] = greater(lhi.x, rhi.x); b.hi[1] = greater(lhi.y, rhi.y); b.hi[2] = greater(lhi.z, rhi.z);
-        return b;
-    }
-    for (int k = 0; k < 3; k++) { b.lo[k] = 1e30f; b.hi[k] = -1e30f; }
-    if (code >= triCount) return b;
-    const char* leaf = geom + leafOff + (size_t)(triBase + code) * 48u;
-    uint32_t n = reinterpret_cast<const uint32_t*>(leaf)[11];                      // LeafTri::remain of the leaf's first slot
-    if (n > triCount - code) n = triCount - code;                                  // (a plan never names a slot past the BVH; neither does this loop)
-    for (uint32_t i = 0; i < n; i++) {
-        const uint32_t tri = reinterpret_cast<const uint32_t*>(leaf + (size_t)i * 48u)[3] - triBase;   // LeafTri::shadeIdx = triBase + the reference's triangle index
-        if (tri >= triCount) continue;
-        const float* v = pos + (size_t)tri * 9u;
-        for (int c = 0; c < 3; c++) for (int k = 0; k < 3; k++) b.lo[k] = lesser(b.lo[k], v[3 * c + k]);
-        for (int c = 0; c < 3; c++) for (int k = 0; k < 3; k++) b.hi[k] = greater(b.hi[k], v[3 * c + k]);
-    }
-    return b;
-}
 
 __global__ __launch_bounds__(256) void refit_leaf_kernel(char* geom, uint32_t leafOff, uint32_t triBase, uint32_t triCount, const float* __restrict__ pos)
 {
@@ -77,7 +46,7 @@ __global__ __launch_bounds__(kRefitBoxThreads) void refit_box_kernel(char* geom,
             row4* p = reinterpret_cast<row4*>(geom + (size_t)(pairBase + r.pair) * 64u);
             for (uint32_t k = 0; k < 2; k++) {
                 if (r.pair == 0 && k == 0) continue;                               // node 1 = child 0 of the BVH's first pair: bvh.cpp:28
-                const Box b = node_box(geom, leafOff, pairBase, triBase, triCount, pos, r.child[k]);
+                const Box b = node_box(geom, geom, leafOff, pairBase, triBase, triCount, pos, r.child[k]);
                 row4 lo = p[2 * k], hi = p[2 * k + 1];                              // .w: ref / ref16 stay
                 lo.x = b.lo[0]; lo.y = b.lo[1]; lo.z = b.lo[2]; hi.x = b.hi[0]; hi.y = b.hi[1]; hi.z = b.hi[2];
                 p[2 * k] = lo; p[2 * k + 1] = hi;
@@ -86,7 +55,7 @@ __global__ __launch_bounds__(kRefitBoxThreads) void refit_box_kernel(char* geom,
         __syncthreads();                                                           // the next level reads what this one stored (same workgroup, same CU)
     }
     if (threadIdx.x == 0) {
-        const Box b = node_box(geom, leafOff, pairBase, triBase, triCount, pos, rootCode);
+        const Box b = node_box(geom, geom, leafOff, pairBase, triBase, triCount, pos, rootCode);
         row4 z = {0.0f, 0.0f, 0.0f, 0.0f};
         row4* o = reinterpret_cast<row4*>(out);
         const row4* p = reinterpret_cast<const row4*>(geom + (size_t)(pairBase + (rootCode & ~kPlanInterior)) * 64u);

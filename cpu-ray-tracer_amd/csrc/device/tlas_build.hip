@@ -3,6 +3,7 @@
 // an image of the geometry buffer's TLAS node, TLAS child pair and Instance sections); the host reads it back, checks it and copies the image into the geometry
 // buffer.  The kernel never writes the geometry buffer itself.  crt_render_poses runs the same build for P sets of transforms at once, one workgroup (of that one
 // wavefront) per set, into the P result blocks of a pose table (tlas_build_poses_kernel): such a block is a complete, relocatable pose of the scene's instances.
+// crt_render_shapes runs it per SHAPE of a refitted BLAS, each build over its own row of node-0 boxes (tlas_build_shapes_kernel).
 //
 //   phase 1  one lane per BLAS (four rounds for 256): invT = T.FastInvertedTransformNoScale(), the world box grown over the eight corners of the BLAS's node-0
 //            box (the context's device array of root boxes) through TransformPosition, the TLAS leaf node, and the Instance record with its T / invT rows renewed.
@@ -188,6 +189,19 @@ __global__ __launch_bounds__(kTlasLanes) void tlas_build_poses_kernel(const char
                     table + imagesOff + (size_t)p * imageStride);
 }
 
+// crt_render_shapes: S builds in one launch, workgroup s the build over T + 16 n s with ITS OWN row of node-0 boxes (shape_build.hip writes the rows: the live boxes
+// with the refitted BVH's replaced) into header s and the pose image inside image s of a shape table (layout.h ShapeJobHeader).  The view -> shape indices are the
+// box launch's to check.
+__global__ __launch_bounds__(kTlasLanes) void tlas_build_shapes_kernel(const char* __restrict__ geom, uint32_t instOff, const float* __restrict__ T, const float* __restrict__ rootBoxRows,
+                                                                       uint32_t n, uint32_t pairRel, uint32_t instRel, uint32_t poolRefBits, char* __restrict__ table, uint32_t headsOff,
+                                                                       uint32_t posesOff, uint32_t imageStride)
+{
+    __shared__ TlasLds s;
+    const uint32_t p = blockIdx.x;
+    tlas_build_pose(s, geom, instOff, T + (size_t)p * 16u * n, rootBoxRows + (size_t)p * 6u * n, n, pairRel, instRel, poolRefBits, reinterpret_cast<TlasBuildHeader*>(table + headsOff) + p,
+                    table + posesOff + (size_t)p * imageStride);
+}
+
 } // namespace crt
 
 extern "C" hipError_t crt_launch_tlas_build(const char* geom, uint32_t instOff, const float* T, const float* rootBox, uint32_t blasCount, uint32_t pairRel, uint32_t instRel, uint32_t poolRefBits,
@@ -206,5 +220,17 @@ extern "C" hipError_t crt_launch_tlas_build_poses(const char* geom, uint32_t ins
     if ((unsigned long long)imagesOff + (unsigned long long)P * imageStride > crt::kMaxGeomBytes) return hipErrorInvalidValue;     // the render kernel's 32-bit offsets into the table
     hipLaunchKernelGGL(crt::tlas_build_poses_kernel, dim3(P), dim3(crt::kTlasLanes), 0, stream, geom, instOff, T, rootBox, blasCount, pairRel, instRel, poolRefBits, static_cast<char*>(table),
                        imagesOff, imageStride, P, viewPose, K);
+    return hipGetLastError();
+}
+
+// S builds into the pose images of a shape table (layout.h ShapeJobHeader), each from its own row of 6 blasCount node-0 boxes: one workgroup each.  posesOff: the
+// first image's pose image (imagesOff + poseRel).
+extern "C" hipError_t crt_launch_tlas_build_shapes(const char* geom, uint32_t instOff, const float* T, const float* rootBoxRows, uint32_t blasCount, uint32_t pairRel, uint32_t instRel,
+                                                   uint32_t poolRefBits, void* table, uint32_t headsOff, uint32_t posesOff, uint32_t imageStride, uint32_t S, hipStream_t stream)
+{
+    if (blasCount == 0u || blasCount > crt::kTlasMaxBlas || S == 0u || (headsOff & 63u) || (posesOff & 127u) || (imageStride & 127u)) return hipErrorInvalidValue;
+    if ((unsigned long long)posesOff + (unsigned long long)S * imageStride > crt::kMaxGeomBytes) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(crt::tlas_build_shapes_kernel, dim3(S), dim3(crt::kTlasLanes), 0, stream, geom, instOff, T, rootBoxRows, blasCount, pairRel, instRel, poolRefBits, static_cast<char*>(table),
+                       headsOff, posesOff, imageStride);
     return hipGetLastError();
 }

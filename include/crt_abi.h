@@ -615,6 +615,60 @@ int  crt_render_poses_device(crt_ctx* ctx, const float* d_cams, uint32_t K, cons
                              uint32_t spp_first, uint32_t frames, uint32_t passes, float scale, float* d_out_rgba, uint32_t* d_out_pixels /* or NULL */,
                              crt_tlas_node* tlas_out /* host, or NULL */, void* stream);                                                      /* device pointers, one host wait */
 
+/* The frames of MANY cameras over MANY SHAPES of one refitted BVH in one render job: skinning, cloth, the candidates of an optimiser over vertices — callers whose
+ * vertex positions already live in device memory.  crt_render_views renders K cameras over the one live scene and crt_render_poses moves a two-level scene's
+ * instances; the loop that deforms a mesh between views — crt_refit_device (one host wait), for a two-level scene crt_update_transforms_device (another),
+ * crt_set_camera, crt_clear, crt_render, crt_read_accumulator — pays the one-frame render and the waits K times, and can hold only one shape at a time because the
+ * live BVH is refitted in place.  Here the S shapes are built side by side (device/shape_build.hip: a leaf launch over (leaf slot, shape) and a box launch of one
+ * workgroup per shape, then for a two-level scene the S TLAS builds in one launch), each into a job-local image: the refitted node pairs and leaf triangles of BVH
+ * `bvh`, and for a two-level scene a pose as crt_render_poses keeps it; every lane of crt_render_views' launch walks the image of its own view's shape
+ * (device/render_shapes.h).  Shading records, the other BVHs and the textures are shared.  ABI version 3 still: additions, detected by symbol.
+ * cams: K records of 12 floats, crt_set_camera's arguments.  positions: S * triCount * 9 floats, shape s's at positions + 9 * triCount * s, each exactly what
+ * crt_refit_device takes as d_positions (vertex0, vertex1, vertex2 per triangle in the reference's triangle order; not validated, as there).  T: S * blasCount
+ * row-major mat4s, shape s's at T + 16 * blasCount * s, each what crt_update_transforms_device takes; NULL with blasCount 0 for a CRT_SCENE_FILE scene.
+ * view_shape: K indices into the shapes, or NULL: view k renders shape k, and S must equal K.
+ * For every view k, with s = view_shape[k], and every pixel of a tile this context owns: out_rgba[k] (W * H float4) is bit for bit what
+ * crt_refit_device(bvh, positions[s]); for a two-level scene crt_update_transforms_device(T[s]); crt_set_camera(cams[k]); crt_clear; crt_render(spp_first, frames,
+ * passes); crt_read_accumulator leaves there on a context in the same live state, w = 0 included; out_pixels[k] (W * H, may be NULL) is crt_resolve_screen(scale)'s
+ * pixel of that accumulator; root_box_out[s] (host memory in BOTH entries, 6 floats per shape, may be NULL) is crt_refit_device's rootBox; tlas_out[s] (host memory
+ * in both entries, 2 * blasCount nodes per shape, may be NULL; not written for a CRT_SCENE_FILE scene) is byte for byte crt_update_transforms_device's tlasOut.
+ * No other pixel of the outputs is touched.  Refit's quirk is kept: node 1 keeps the box THE LIVE SCENE holds, and that box feeds node 0's.  No refit ever writes
+ * node 1, so the shapes of a job do not depend on each other or on their order.
+ * THE LIVE SCENE IS NOT CHANGED: the geometry, the node-0 boxes, the TLAS, the KD-tree / grid sets, the host mirror and the epoch stay as they are, and so do
+ * crt_tick's rendered-ahead frames, the context's camera and the accumulator.  Shapes are job-local: they live in the scratch crt_render_poses keeps its poses in
+ * (kept until crt_destroy), at most 4 GiB of it (64 bytes per node pair + 48 per triangle, + about 256 * blasCount per shape of a two-level scene).
+ * Counters: crt_counters.rays, primary and mesh_hits grow as they would for the K renders.
+ * Ordering: the call is a reader under the scene-write protocol, exactly like crt_render_poses_device.  THE ONE HOST WAIT (both entries; besides growing scratch
+ * and the BVH's refit plan, built by the first call as crt_refit_device builds it): a job with a view_shape entry out of range or a failed TLAS build must not run,
+ * and the launches' LDS stack is sized by the tallest shape's TLAS — so the call reads the flag and, for a two-level scene, the S build headers back (64 (S + 1)
+ * bytes, pinned; with root_box_out the boxes, with tlas_out the node sections too) and returns from that wait before it enqueues the render launches.
+ * crt_render_shapes_device: d_cams (48 K bytes), d_positions (36 S triCount), d_T (64 S blasCount, or NULL), d_view_shape (4 K, or NULL), d_out_rgba (16 K W H,
+ * 16-byte aligned), d_out_pixels (4 K W H, or NULL) are device pointers on cfg.device, checked as crt_render_views_device checks its buffers; `stream` a
+ * hipStream_t of that device or NULL.  crt_render_shapes: host pointers, synchronous, through staging the context keeps.
+ * Refusals (nothing is written, crt_last_error says why), in this order: no scene CRT_ERR_STATE; a PrimitiveScene CRT_ERR_UNSUPPORTED; `bvh` out of range, or
+ * triCount different from the uploaded BVH's, CRT_ERR_INVALID; a CRT_SCENE_FILE scene with T != NULL or blasCount != 0 CRT_ERR_INVALID; a two-level scene with
+ * T == NULL or blasCount != bvhCount CRT_ERR_INVALID; a two-level scene uploaded with a TLAS node count other than 2 * bvhCount CRT_ERR_UNSUPPORTED; passes outside
+ * 1..4 CRT_ERR_INVALID; K * frames > 2^31-1 CRT_ERR_UNSUPPORTED; crt_set_render_accel != 0 CRT_ERR_UNSUPPORTED (a refit drops those sets anyway); S == 0 with
+ * K > 0, or view_shape NULL with S != K, CRT_ERR_INVALID; a shape table beyond 4 GiB CRT_ERR_UNSUPPORTED; NULL, misaligned, host or other-device memory, a stream of
+ * another device CRT_ERR_INVALID; a view_shape entry outside [0, S) CRT_ERR_INVALID (the host entry looks before anything runs; the device entry checks in the
+ * build launch and learns of it with the header); a shape whose TLAS build has a FindBestMatch without a candidate while more than one node is open
+ * CRT_ERR_INVALID (crt_last_error names the first such shape and the call); a TLAS height that puts the traversal stack beyond the sequential kernels' LDS bound
+ * CRT_ERR_UNSUPPORTED; a failed device allocation CRT_ERR_DEVICE.  K == 0 or frames == 0 is a no-op after the checks that need no buffer.
+ * When to use it (one MI355X, 1280x720, profiles/render_shapes.json): 64 shapes of one frame each take 212 ms against 1 415 ms for the loop above on the bunny
+ * FileScene (6.7x) and 223 ms against 1 986 ms on tlas_scene.xml (8.9x).  The advantage shrinks with the frames per view: 16 shapes x 64 frames 466 against 504 ms
+ * (bunny, 1.08x) and 404 against 758 ms (two-level, 1.88x); at 8 x 128 the loop is the better call on the bunny (380 against 435 ms) and the entry still on the
+ * two-level scene (382 against 606 ms); at 4 x 256 the loop wins on both (190 against 382 ms, 303 against 363 ms).  So: up to 64 frames per view call the entry, from
+ * 256 on loop crt_refit_device + crt_render, in between measure.  The 64 shape builds by themselves cost 0.21 ms (bunny, 4 968 triangles) / 0.20 ms (a BLAS of
+ * 2 992 triangles + 64 TLAS builds) inside the entry against 7.3 / 12.1 ms for 64 crt_refit_device (+ crt_update_transforms_device) calls. */
+int  crt_render_shapes(crt_ctx* ctx, const float* cams /* K * 12 */, uint32_t K, uint32_t bvh, const float* positions /* S * triCount * 9 */, uint32_t S, uint32_t triCount,
+                       const float* T /* S * blasCount * 16; NULL for a CRT_SCENE_FILE scene */, uint32_t blasCount, const int32_t* view_shape /* K, or NULL */,
+                       uint32_t spp_first, uint32_t frames, uint32_t passes, float scale, float* out_rgba /* K * W*H float4 */, uint32_t* out_pixels /* K * W*H or NULL */,
+                       float* root_box_out /* host, S * 6, or NULL */, crt_tlas_node* tlas_out /* host, S * 2 * blasCount, or NULL */);         /* host pointers, synchronous */
+int  crt_render_shapes_device(crt_ctx* ctx, const float* d_cams, uint32_t K, uint32_t bvh, const float* d_positions, uint32_t S, uint32_t triCount, const float* d_T /* or NULL */,
+                              uint32_t blasCount, const int32_t* d_view_shape /* or NULL */, uint32_t spp_first, uint32_t frames, uint32_t passes, float scale, float* d_out_rgba,
+                              uint32_t* d_out_pixels /* or NULL */, float* root_box_out /* host, or NULL */, crt_tlas_node* tlas_out /* host, or NULL */,
+                              void* stream);                                                                                                   /* device pointers, one host wait */
+
 /* ---- PrimitiveScene (second half): infra/scene/primitive_scene.cpp — the reference's hard-coded demo room (six walls, swinging light quad,
  * bouncing mirror ball, "rounded corners" sphere, spinning glass cube, glass torus; template/primitives.h Sphere :31, Cube :187, Quad :321, Torus :380; the
  * SPEEDTRIX / single-light configuration its headers select).  The binding passes the scene as its constructor + SetTime(t) leave it: the members below.
