@@ -110,7 +110,7 @@ HIT_INFO_DTYPE = np.dtype([("I", "<f4", 3), ("material", "<i4"), ("N", "<f4", 3)
 MATERIAL_MISS, MATERIAL_INVALID = -1, -2       # crt_hit_info.material of a miss / of a record whose objIdx or triIdx the scene does not have
 
 # every symbol include/crt_abi.h and include/crt_host.h declare (tests check the library exports all of them)
-ABI_SYMBOLS = ["crt_render_shapes", "crt_render_shapes_device", "crt_render_poses", "crt_render_poses_device", "crt_render_views", "crt_render_views_device", "crt_trace","crt_trace_device", "crt_build_bvh_device", "crt_get_bvh", "crt_build_kdtree_device", "crt_get_kdtree", "crt_build_grid_device", "crt_get_grid", "crt_update_transforms_device", "crt_sample", "crt_sample_device", "crt_refit_device", "crt_get_hit_info", "crt_get_hit_info_device", "crt_get_sky_color", "crt_get_sky_color_device", "crt_get_light", "crt_upload_blas_accel", "crt_is_occluded", "crt_find_nearest_device", "crt_is_occluded_device", "crt_upload_primitive_scene", "crt_set_render_accel", "crt_upload_alt_accel", "crt_find_nearest_alt", "crt_update_scene", "crt_abi_version", "crt_device_count", "crt_create", "crt_destroy", "crt_last_error", "crt_upload_scene", "crt_set_camera",
+ABI_SYMBOLS = ["crt_render_shapes", "crt_render_shapes_device", "crt_render_shape_sets", "crt_render_shape_sets_device", "crt_render_poses", "crt_render_poses_device", "crt_render_views", "crt_render_views_device", "crt_trace","crt_trace_device", "crt_build_bvh_device", "crt_get_bvh", "crt_build_kdtree_device", "crt_get_kdtree", "crt_build_grid_device", "crt_get_grid", "crt_update_transforms_device", "crt_sample", "crt_sample_device", "crt_refit_device", "crt_get_hit_info", "crt_get_hit_info_device", "crt_get_sky_color", "crt_get_sky_color_device", "crt_get_light", "crt_upload_blas_accel", "crt_is_occluded", "crt_find_nearest_device", "crt_is_occluded_device", "crt_upload_primitive_scene", "crt_set_render_accel", "crt_upload_alt_accel", "crt_find_nearest_alt", "crt_update_scene", "crt_abi_version", "crt_device_count", "crt_create", "crt_destroy", "crt_last_error", "crt_upload_scene", "crt_set_camera",
                "crt_render", "crt_tick", "crt_reserve", "crt_whitted_tick", "crt_whitted_tick_inspect", "crt_sync", "crt_clear", "crt_read_accumulator", "crt_resolve_screen", "crt_find_nearest", "crt_get_counters",
                "crt_reset_counters", "crt_get_timing", "crt_get_tile_clocks", "crt_bind_accumulator", "crt_accumulator_device_ptr"]
 HOST_SYMBOLS = ["crt_host_bvh_build", "crt_host_scene_bvh_move_and_rebuild", "crt_host_scene_build_bvh_device", "crt_host_scene_build_kdtree_device", "crt_host_kd_build", "crt_host_scene_build_grid_device", "crt_host_grid_build", "crt_host_scene_update_transforms_device", "crt_host_scene_bvh_refit_device", "crt_host_scene_blas_alt_info", "crt_host_scene_blas_alt_copy", "crt_host_primitive_scene_create", "crt_host_primitive_scene_free", "crt_host_primitive_scene_set_time", "crt_host_primitive_scene_desc", "crt_host_primitive_scene_upload", "crt_host_scene_build_alt", "crt_host_scene_upload_alt", "crt_host_scene_alt_info", "crt_host_scene_alt_copy", "crt_host_scene_set_transform", "crt_host_scene_update", "crt_host_math_probe", "crt_host_vertex_dedup", "crt_host_last_error", "crt_host_scene_load", "crt_host_scene_free", "crt_host_scene_upload", "crt_host_scene_kind",
@@ -394,6 +394,80 @@ class Context:
                                                      C.c_uint32(passes), C.c_float(1.0 if scale is None else scale), C.c_void_p(out.data_ptr()),
                                                      C.c_void_p(pixels.data_ptr()) if pixels is not None else None, _p(boxes) if boxes is not None else None,
                                                      _p(nodes) if nodes is not None else None, C.c_void_p(st.cuda_stream)))
+            res = [out] + ([pixels] if pixels is not None else []) + ([nodes] if nodes is not None else []) + ([boxes] if boxes is not None else [])
+            return res[0] if len(res) == 1 else tuple(res)
+        return self._enqueue(stream, run)
+
+    def render_shape_sets(self, cameras, bvhs, positions, spp_first, frames, passes=1, scale=None, T=None, view_shape=None, want_root_boxes=False, want_tlas=False):
+        """crt_render_shape_sets: the frames of K cameras over S shapes of a two-level scene in which the M uploaded BLASes `bvhs` deform per shape, in one job (host
+        buffers, synchronous; the live scene is not changed).  cameras = [K, 12] float32 (camera_records), bvhs = M distinct BLAS indices, positions = a list of M arrays
+        [S, triCount_m, 3, 3] float32 in the order of bvhs (per shape what refit_device takes for that BVH), or one array [S, setTris, 9] (or [S, setTris, 3, 3]) with
+        the blocks in that order, T = [S, blasCount, 16] float32, view_shape = None (view k renders shape k; S == K) or K indices into the shapes.  Returns what
+        render_shapes returns — per view what refit_device(bvhs[m], ...) for every m + update_transforms_device(T[s]) + set_camera + clear + render + accumulator()
+        leaves —, with node 0's boxes [S, M, 2, 3] float32 when want_root_boxes."""
+        cams = np.ascontiguousarray(cameras, np.float32).reshape(-1, 12)
+        ids = np.ascontiguousarray(bvhs, np.uint32).reshape(-1)
+        if isinstance(positions, (list, tuple)):
+            parts = [np.ascontiguousarray(a, np.float32) for a in positions]
+            if len(parts) != ids.shape[0] or any(a.ndim < 3 or a.shape[0] != parts[0].shape[0] for a in parts):
+                raise ValueError("render_shape_sets: positions must hold one [S, triCount_m, 3, 3] array per BVH of the set")
+            pos = np.ascontiguousarray(np.concatenate([a.reshape(a.shape[0], a.shape[1], 9) for a in parts], axis=1)) if parts else np.zeros((0, 0, 9), np.float32)
+        else:
+            pos = np.ascontiguousarray(positions, np.float32)
+        if pos.ndim < 3 or pos.shape[2:] not in ((3, 3), (9,)):
+            raise ValueError("render_shape_sets: positions must be M arrays [S, triCount_m, 3, 3] or one [S, setTris, 9] float32 array")
+        k, s, tris, m = cams.shape[0], pos.shape[0], pos.shape[1], ids.shape[0]
+        t = None if T is None else np.ascontiguousarray(T, np.float32)
+        if t is not None and (t.ndim != 3 or t.shape[2] != 16 or t.shape[0] != s):
+            raise ValueError("render_shape_sets: T must be [S, blasCount, 16] float32")
+        n = 0 if t is None else t.shape[1]
+        vs = None if view_shape is None else np.ascontiguousarray(view_shape, np.int32).reshape(-1)
+        if vs is not None and vs.shape[0] != k:
+            raise ValueError("render_shape_sets: view_shape needs one index per camera")
+        acc = np.zeros((k, self.H, self.W, 4), np.float32)
+        px = np.zeros((k, self.H, self.W), np.uint32) if scale is not None else None
+        nodes = np.zeros((s, 2 * n), TLAS_DTYPE) if want_tlas else None
+        boxes = np.zeros((s, m, 2, 3), np.float32) if want_root_boxes else None
+        self._ck(self.L.crt_render_shape_sets(self.h, _p(cams), C.c_uint32(k), _p(ids), C.c_uint32(m), _p(pos), C.c_uint32(s), C.c_uint32(tris), _p(t) if t is not None else None,
+                                              C.c_uint32(n), _p(vs) if vs is not None else None, C.c_uint32(spp_first), C.c_uint32(frames), C.c_uint32(passes),
+                                              C.c_float(1.0 if scale is None else scale), _p(acc), _p(px) if px is not None else None, _p(boxes) if boxes is not None else None,
+                                              _p(nodes) if nodes is not None else None))
+        out = [acc] + ([px] if px is not None else []) + ([nodes] if nodes is not None else []) + ([boxes] if boxes is not None else [])
+        return out[0] if len(out) == 1 else tuple(out)
+
+    def render_shape_sets_device(self, cams, bvhs, positions, out, spp_first, frames, passes=1, scale=None, pixels=None, T=None, view_shape=None, want_root_boxes=False,
+                                 want_tlas=False, stream=None):
+        """crt_render_shape_sets_device: the same job for torch tensors on the context's device, enqueued on `stream` (default torch.cuda.current_stream()); one host
+        wait, for the job header and the build headers.  cams = [K, 12] float32, bvhs = M BLAS indices (host), positions = [S, setTris, 3, 3] or [S, setTris, 9]
+        float32 (per shape the BVHs' blocks in the order of bvhs), T = [S, blasCount, 16] float32, out = [K, H, W, 4] float32, pixels = None or [K, H, W] int32 (needs
+        `scale`), view_shape = None or [K] int32, all contiguous; only the pixels of owned tiles are written.  Returns out, then pixels when given, then the TLAS
+        nodes [S, 2 * blasCount] (numpy, TLAS_DTYPE) when want_tlas, then node 0's boxes [S, M, 2, 3] (numpy) when want_root_boxes: a tuple when more than one."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        ids = np.ascontiguousarray(bvhs, np.uint32).reshape(-1)
+        k = cams.shape[0] if isinstance(cams, torch.Tensor) and cams.dim() == 2 else -1
+        if not isinstance(positions, torch.Tensor) or positions.dim() < 3 or tuple(positions.shape[2:]) not in ((3, 3), (9,)):
+            raise ValueError("render_shape_sets_device: positions must be a float32 tensor of shape [S, setTris, 3, 3] or [S, setTris, 9] on cuda:%d" % self.device)
+        s, tris, m = positions.shape[0], positions.shape[1], ids.shape[0]
+        n = T.shape[1] if isinstance(T, torch.Tensor) and T.dim() == 3 else -1
+        for t, dt, shape, name in ((cams, torch.float32, (k, 12), "cams"), (positions, torch.float32, tuple(positions.shape), "positions"), (T, torch.float32, (s, n, 16), "T"),
+                                   (out, torch.float32, (k, self.H, self.W, 4), "out"), (pixels, torch.int32, (k, self.H, self.W), "pixels"), (view_shape, torch.int32, (k,), "view_shape")):
+            if t is None and name in ("pixels", "view_shape"):
+                continue
+            if not isinstance(t, torch.Tensor) or t.device != dev or t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
+                raise ValueError("render_shape_sets_device: %s must be a contiguous %s tensor of shape %s on cuda:%d" % (name, dt, shape, self.device))
+        if pixels is not None and scale is None:
+            raise ValueError("render_shape_sets_device: pixels need a scale")
+        nodes = np.zeros((s, 2 * n), TLAS_DTYPE) if want_tlas else None
+        boxes = np.zeros((s, m, 2, 3), np.float32) if want_root_boxes else None
+
+        def run(st):
+            self._ck(self.L.crt_render_shape_sets_device(self.h, C.c_void_p(cams.data_ptr()), C.c_uint32(k), _p(ids), C.c_uint32(m), C.c_void_p(positions.data_ptr()), C.c_uint32(s),
+                                                         C.c_uint32(tris), C.c_void_p(T.data_ptr()), C.c_uint32(n),
+                                                         C.c_void_p(view_shape.data_ptr()) if view_shape is not None else None, C.c_uint32(spp_first), C.c_uint32(frames),
+                                                         C.c_uint32(passes), C.c_float(1.0 if scale is None else scale), C.c_void_p(out.data_ptr()),
+                                                         C.c_void_p(pixels.data_ptr()) if pixels is not None else None, _p(boxes) if boxes is not None else None,
+                                                         _p(nodes) if nodes is not None else None, C.c_void_p(st.cuda_stream)))
             res = [out] + ([pixels] if pixels is not None else []) + ([nodes] if nodes is not None else []) + ([boxes] if boxes is not None else [])
             return res[0] if len(res) == 1 else tuple(res)
         return self._enqueue(stream, run)

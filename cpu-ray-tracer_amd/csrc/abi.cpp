@@ -3652,8 +3652,9 @@ static int views_scratch(crt_ctx* c, uint32_t totalWindows, size_t windowBytes, 
 // the job on `st`, after every check: launches of whole windows, each followed by its per-view sums into the caller's images
 // (poses: crt_render_poses' job — the launches read every lane's TLAS and Instance records from its view's pose in that table, with jobScene's stack depth)
 // (shapes: crt_render_shapes' job — ... every lane's refitted BVH, and a two-level scene's TLAS and Instance records, from its view's shape in that table)
+// (sets: crt_render_shape_sets' job — ... the refitted BVHs of the set, the TLAS and the Instance records, from its view's shape in that table)
 static int views_run(crt_ctx* c, const float* dCams, uint32_t K, uint32_t sppFirst, uint32_t frames, uint32_t passes, float scale, float* dRgba, uint32_t* dPixels, hipStream_t st,
-                     const crt::Scene* jobScene = nullptr, const crt::PoseTableDev* poses = nullptr, const crt::ShapeTableDev* shapes = nullptr)
+                     const crt::Scene* jobScene = nullptr, const crt::PoseTableDev* poses = nullptr, const crt::ShapeTableDev* shapes = nullptr, const crt::ShapeSetTableDev* sets = nullptr)
 {
     if (c->tileCount == 0) return 0;
     const uint32_t total = K * frames, totalWindows = (total + 63u) / 64u;
@@ -3665,7 +3666,8 @@ static int views_run(crt_ctx* c, const float* dCams, uint32_t K, uint32_t sppFir
     if (c->renderAccel != 0 && c->altReady) HIPCK(c, hipStreamWaitEvent(st, c->altReady, 0));   // the accelerators' copies ran on the null stream
     for (uint32_t j0 = 0; j0 < total; j0 += wl * 64u) {
         const uint32_t nj = (total - j0 < wl * 64u) ? total - j0 : wl * 64u;
-        if (shapes) HIPCK(c, crt_launch_render_shapes(jobScene, shapes, dCams, c->dViewsSlab, c->dCounters, c->tileFirst, c->tileStride, c->tileCount, (uint32_t)c->tilesX, sppFirst, frames, passes, j0, nj, st));
+        if (sets) HIPCK(c, crt_launch_render_shape_sets(jobScene, sets, dCams, c->dViewsSlab, c->dCounters, c->tileFirst, c->tileStride, c->tileCount, (uint32_t)c->tilesX, sppFirst, frames, passes, j0, nj, st));
+        else if (shapes) HIPCK(c, crt_launch_render_shapes(jobScene, shapes, dCams, c->dViewsSlab, c->dCounters, c->tileFirst, c->tileStride, c->tileCount, (uint32_t)c->tilesX, sppFirst, frames, passes, j0, nj, st));
         else if (poses) HIPCK(c, crt_launch_render_poses(jobScene, poses, dCams, c->dViewsSlab, c->dCounters, c->tileFirst, c->tileStride, c->tileCount, (uint32_t)c->tilesX, sppFirst, frames, passes, j0, nj, st));
         else if (c->havePrim) HIPCK(c, crt_launch_render_views_prim(&c->hScene, &c->prim, dCams, c->dViewsSlab, c->dCounters, c->tileFirst, c->tileStride, c->tileCount, (uint32_t)c->tilesX, sppFirst, frames, passes, j0, nj, st));
         else HIPCK(c, crt_launch_render_views(c->renderAccel, &c->hScene, &c->alt, c->renderAccel ? &c->blasAlt[c->renderAccel - 1] : nullptr, dCams, c->dViewsSlab, c->dCounters, c->tileFirst,
@@ -3746,6 +3748,27 @@ int crt_render_views(crt_ctx* c, const float* cams, uint32_t K, uint32_t spp_fir
     return views_stage_out(c, K, out_rgba, out_pixels, S);
 }
 
+// the job table and the pinned copy of what the one host wait reads, each grown when the job needs more, and `st` behind the previous job's launches
+static int job_table(crt_ctx* c, size_t tableBytes, size_t backBytes, hipStream_t st)
+{
+    // the table is read by the previous job's launches to their end: viewsDone, on that job's stream
+    HIPCK(c, ensure_event(&c->viewsDone));
+    HIPCK(c, ensure_event(&c->poseBack));
+    if (tableBytes > c->poseTableCap) {
+        if (c->viewsPending) { HIPCK(c, hipEventSynchronize(c->viewsDone)); c->viewsPending = false; }
+        if (c->dPoseTable) { HIPCK(c, hipFree(c->dPoseTable)); c->dPoseTable = nullptr; c->poseTableCap = 0; }
+        HIPCK(c, hipMalloc((void**)&c->dPoseTable, tableBytes));
+        c->poseTableCap = tableBytes;
+    }
+    if (backBytes > c->poseBackCap) {                                       // (no copy into it is in flight: every call waits for its own)
+        if (c->hPoseBack) { HIPCK(c, hipHostFree(c->hPoseBack)); c->hPoseBack = nullptr; c->poseBackCap = 0; }
+        HIPCK(c, hipHostMalloc((void**)&c->hPoseBack, backBytes, hipHostMallocDefault));
+        c->poseBackCap = backBytes;
+    }
+    if (c->viewsPending) HIPCK(c, hipStreamWaitEvent(st, c->viewsDone, 0));
+    return 0;
+}
+
 // ---- crt_render_poses / crt_render_poses_device: the frames of K cameras over P job-local poses of a two-level scene's instances (device/render_poses.h) ----
 // where a job's pose table keeps what (device/layout.h PoseJobHeader)
 struct PoseLayout {
@@ -3792,21 +3815,7 @@ static int poses_run(crt_ctx* c, const float* dCams, uint32_t K, const float* dT
     // The builds are readers, as crt_update_transforms_device's: the Instance records and the node-0 boxes as the last write left them.
     int r;
     if ((r = wait_scene(c, st))) return r;
-    // the table is read by the previous job's launches to their end: viewsDone, on that job's stream
-    HIPCK(c, ensure_event(&c->viewsDone));
-    HIPCK(c, ensure_event(&c->poseBack));
-    if (L.tableBytes > c->poseTableCap) {
-        if (c->viewsPending) { HIPCK(c, hipEventSynchronize(c->viewsDone)); c->viewsPending = false; }
-        if (c->dPoseTable) { HIPCK(c, hipFree(c->dPoseTable)); c->dPoseTable = nullptr; c->poseTableCap = 0; }
-        HIPCK(c, hipMalloc((void**)&c->dPoseTable, L.tableBytes));
-        c->poseTableCap = L.tableBytes;
-    }
-    if (backBytes > c->poseBackCap) {                                       // (no copy into it is in flight: every call waits for its own)
-        if (c->hPoseBack) { HIPCK(c, hipHostFree(c->hPoseBack)); c->hPoseBack = nullptr; c->poseBackCap = 0; }
-        HIPCK(c, hipHostMalloc((void**)&c->hPoseBack, backBytes, hipHostMallocDefault));
-        c->poseBackCap = backBytes;
-    }
-    if (c->viewsPending) HIPCK(c, hipStreamWaitEvent(st, c->viewsDone, 0));
+    if ((r = job_table(c, L.tableBytes, backBytes, st))) return r;
     HIPCK(c, hipMemsetAsync(c->dPoseTable, 0xff, sizeof(uint32_t), st));    // PoseJobHeader::badView = kPoseNoBadView
     HIPCK(c, crt_launch_tlas_build_poses(c->hScene.geom, (uint32_t)f.instOff, dT, c->dRootBox, N, (uint32_t)(f.tlasPairOff - f.tlasOff), (uint32_t)(f.instOff - f.tlasOff), c->hScene.poolRefBits,
                                          c->dPoseTable, L.imagesOff, L.imageStride, P, dViewPose, K, st));
@@ -3929,6 +3938,24 @@ static int shapes_check(crt_ctx* c, uint32_t K, uint32_t bvh, uint32_t S, uint32
     return 0;
 }
 
+// what the S TLAS builds of a shape job reported: a failed build refuses the job; the tallest TLAS sizes the launches' LDS stack (jobScene->stackDepth)
+static int shape_tlas_heads(crt_ctx* c, const crt::TlasBuildHeader* heads, uint32_t S, crt::Scene* jobScene, const char* what)
+{
+    uint32_t tallest = 0, tallestShape = 0; int r;
+    for (uint32_t s = 0; s < S; s++) {
+        const crt::TlasBuildHeader& h = heads[s];
+        if (h.status == crt::kTlasBuildNoCandidate)
+            return c->fail(CRT_ERR_INVALID, "%s: shape %u: FindBestMatch call %u found no partner while more than one node was open (a non-finite transform, position or box, or areas >= 1e30; the reference reads list[-1] there)", what, s, h.step);
+        if (h.status != crt::kTlasBuildOk) return c->fail(CRT_ERR_INVALID, "%s: shape %u: the build had not ended after %u FindBestMatch calls", what, s, h.step);
+        if (h.height > tallest) { tallest = h.height; tallestShape = s; }
+    }
+    jobScene->stackDepth = jobScene->bvhStack + tallest + 1;
+    if ((r = check_tlas_height(c, tallest))) return r;
+    if (!sample_lds_fits(jobScene->stackDepth))
+        return c->fail(CRT_ERR_UNSUPPORTED, "%s: shape %u: a TLAS of height %u makes the traversal stack %u dwords per lane, which exceeds the kernel's LDS", what, tallestShape, tallest, jobScene->stackDepth);
+    return 0;
+}
+
 // The job on `st`, after the checks that need no launch: the S shapes (leaf launch, box launch, for a two-level scene the S TLAS builds), the read-back of the
 // view_shape flag and the build headers (THE host wait; with root_box_out / tlas_out the boxes / node sections too), the checks of what came back, then
 // crt_render_views' launches over the table.  dViewShape may be nullptr (view k renders shape k); dT is nullptr for a FileScene.
@@ -3946,21 +3973,7 @@ static int shapes_run(crt_ctx* c, const float* dCams, uint32_t K, uint32_t bvh, 
     const size_t boxesAt = L.headBytes, nodesAt = boxesAt + (rootBoxOut ? (size_t)S * 24u : 0), backBytes = nodesAt + (tlasOut && L.tlas ? (size_t)S * nodeBytes : 0);
     // The builds are readers, as crt_render_poses': the live pairs, leaf records, Instance records and node-0 boxes as the last write left them.
     if ((r = wait_scene(c, st))) return r;
-    // the table is read by the previous job's launches to their end: viewsDone, on that job's stream
-    HIPCK(c, ensure_event(&c->viewsDone));
-    HIPCK(c, ensure_event(&c->poseBack));
-    if (L.tableBytes > c->poseTableCap) {
-        if (c->viewsPending) { HIPCK(c, hipEventSynchronize(c->viewsDone)); c->viewsPending = false; }
-        if (c->dPoseTable) { HIPCK(c, hipFree(c->dPoseTable)); c->dPoseTable = nullptr; c->poseTableCap = 0; }
-        HIPCK(c, hipMalloc((void**)&c->dPoseTable, L.tableBytes));
-        c->poseTableCap = L.tableBytes;
-    }
-    if (backBytes > c->poseBackCap) {                                       // (no copy into it is in flight: every call waits for its own)
-        if (c->hPoseBack) { HIPCK(c, hipHostFree(c->hPoseBack)); c->hPoseBack = nullptr; c->poseBackCap = 0; }
-        HIPCK(c, hipHostMalloc((void**)&c->hPoseBack, backBytes, hipHostMallocDefault));
-        c->poseBackCap = backBytes;
-    }
-    if (c->viewsPending) HIPCK(c, hipStreamWaitEvent(st, c->viewsDone, 0));
+    if ((r = job_table(c, L.tableBytes, backBytes, st))) return r;
     char* table = c->dPoseTable;
     HIPCK(c, hipMemsetAsync(table, 0xff, sizeof(uint32_t), st));            // ShapeJobHeader::badView = kPoseNoBadView
     const crt::ShapeBuildDev sb{c->hScene.geom, (uint32_t)f.leafOff, (uint32_t)f.pairBase[bvh], L.pairCount, (uint32_t)f.triBase[bvh], L.triCount, dPos,
@@ -3977,19 +3990,7 @@ static int shapes_run(crt_ctx* c, const float* dCams, uint32_t K, uint32_t bvh, 
     if (job.badView != crt::kPoseNoBadView) return c->fail(CRT_ERR_INVALID, "%s: view_shape[%u] lies outside [0, %u)", what, job.badView, S);
     crt::Scene job_scene = c->hScene;                                       // the launches' by-value Scene: the context's, with the job's stack depth.  c->hScene stays as it is
     if (L.tlas) {
-        const crt::TlasBuildHeader* heads = reinterpret_cast<const crt::TlasBuildHeader*>(c->hPoseBack + L.headsOff);
-        uint32_t tallest = 0, tallestShape = 0;
-        for (uint32_t s = 0; s < S; s++) {
-            const crt::TlasBuildHeader& h = heads[s];
-            if (h.status == crt::kTlasBuildNoCandidate)
-                return c->fail(CRT_ERR_INVALID, "%s: shape %u: FindBestMatch call %u found no partner while more than one node was open (a non-finite transform, position or box, or areas >= 1e30; the reference reads list[-1] there)", what, s, h.step);
-            if (h.status != crt::kTlasBuildOk) return c->fail(CRT_ERR_INVALID, "%s: shape %u: the build had not ended after %u FindBestMatch calls", what, s, h.step);
-            if (h.height > tallest) { tallest = h.height; tallestShape = s; }
-        }
-        job_scene.stackDepth = job_scene.bvhStack + tallest + 1;
-        if ((r = check_tlas_height(c, tallest))) return r;
-        if (!sample_lds_fits(job_scene.stackDepth))
-            return c->fail(CRT_ERR_UNSUPPORTED, "%s: shape %u: a TLAS of height %u makes the traversal stack %u dwords per lane, which exceeds the kernel's LDS", what, tallestShape, tallest, job_scene.stackDepth);
+        if ((r = shape_tlas_heads(c, reinterpret_cast<const crt::TlasBuildHeader*>(c->hPoseBack + L.headsOff), S, &job_scene, what))) return r;
     } else if (!sample_lds_fits(job_scene.stackDepth))
         return c->fail(CRT_ERR_UNSUPPORTED, "%s: a traversal stack of %u dwords per lane exceeds the kernel's LDS", what, job_scene.stackDepth);
     // node 0 of the refitted BVH as the image names it (shape_build.hip image_ref)
@@ -4049,6 +4050,169 @@ int crt_render_shapes(crt_ctx* c, const float* cams, uint32_t K, uint32_t bvh, c
     if (dT) HIPCK(c, hipMemcpyAsync(dT, T, tBytes, hipMemcpyHostToDevice, c->stream));
     if (dViewShape) HIPCK(c, hipMemcpyAsync(dViewShape, view_shape, (size_t)K * 4, hipMemcpyHostToDevice, c->stream));
     if ((r = shapes_run(c, dCams, K, bvh, dPos, S, dT, dViewShape, spp_first, frames, passes, scale, G.dRgba, G.dPix, root_box_out, tlas_out, c->stream, what))) return r;
+    return views_stage_out(c, K, out_rgba, out_pixels, G);
+}
+
+// ---- crt_render_shape_sets / crt_render_shape_sets_device: the same over shapes in which M BLASes of a two-level scene deform (device/render_shape_sets.h) ----
+// where a set job's table keeps what (device/layout.h ShapeSetMesh): ShapeLayout's head and rows, the two tables the kernels read, then the images, each the M
+// sub-images in the order of `bvhs` and the pose image.  With M = 1 an image is ShapeLayout's.
+struct ShapeSetLayout {
+    uint32_t N, rowFloats;
+    size_t headBytes, tableBytes; uint32_t headsOff, rowsOff, meshOff, instRootOff, imagesOff, imageStride, poseRel, setTris;
+    std::vector<crt::ShapeSetMesh> mesh;          // plan, levelOff, levels, rootCode: filled by shape_sets_run
+    ShapeSetLayout(const crt_ctx::Flat& f, const uint32_t* bvhs, uint32_t M, uint32_t S)
+    {
+        N = (uint32_t)f.triCount.size(); rowFloats = 6u * N;
+        headsOff = (uint32_t)sizeof(crt::ShapeJobHeader);
+        headBytes = headsOff + (size_t)S * sizeof(crt::TlasBuildHeader);
+        const size_t meshAt = (headBytes + (size_t)S * rowFloats * 4u + 15u) & ~(size_t)15u, rootsAt = meshAt + (size_t)M * sizeof(crt::ShapeSetMesh);
+        const size_t imagesAt = (rootsAt + (size_t)N * 4u + 127u) & ~(size_t)127u;
+        size_t at = 0, tris = 0;
+        for (uint32_t m = 0; m < M; m++) {
+            crt::ShapeSetMesh d{};
+            d.bvh = bvhs[m]; d.pairBase = (uint32_t)f.pairBase[d.bvh]; d.pairCount = f.nodesUsed[d.bvh] / 2; d.triBase = (uint32_t)f.triBase[d.bvh]; d.triCount = f.triCount[d.bvh];
+            d.triFirst = (uint32_t)tris; d.pairRel = (uint32_t)at; d.leafRel = (uint32_t)(at + (size_t)(d.pairCount ? d.pairCount : 1u) * 64u);
+            at = (d.leafRel + (size_t)d.triCount * 48u + 63u) & ~(size_t)63u;
+            tris += d.triCount;
+            mesh.push_back(d);
+        }
+        const size_t poseAt = (at + 127u) & ~(size_t)127u, stride = (poseAt + (size_t)(f.shadeOff - f.tlasOff) + 127u) & ~(size_t)127u;
+        tableBytes = imagesAt + (size_t)S * stride + 64u;                   // (+ 64: a fetch of 64 bytes at the last record's last row stays inside)
+        // shape_sets_check refuses a table beyond 4 GiB before anything uses the 32-bit fields (one image is below 4 GiB: it is smaller than the geometry buffer)
+        rowsOff = (uint32_t)headBytes; meshOff = (uint32_t)meshAt; instRootOff = (uint32_t)rootsAt; imagesOff = (uint32_t)imagesAt; imageStride = (uint32_t)stride;
+        poseRel = (uint32_t)poseAt; setTris = (uint32_t)tris;
+    }
+};
+
+// the checks that need no buffer, in the order crt_abi.h lists the refusals
+static int shape_sets_check(crt_ctx* c, uint32_t K, const uint32_t* bvhs, uint32_t M, uint32_t S, uint32_t setTris, bool haveT, uint32_t blasCount, bool viewShape, uint32_t frames,
+                            uint32_t passes, const char* what)
+{
+    if (!c->haveScene && !c->havePrim) return c->fail(CRT_ERR_STATE, "%s before crt_upload_scene", what);
+    if (c->havePrim) return c->fail(CRT_ERR_UNSUPPORTED, "%s: the PrimitiveScene has no BVH to refit", what);
+    const crt_ctx::Flat& f = c->flat;
+    if (f.kind != CRT_SCENE_TLAS) return c->fail(CRT_ERR_INVALID, "%s applies to two-level scenes; a FileScene has one BVH (crt_render_shapes)", what);
+    const uint32_t N = (uint32_t)f.triCount.size();
+    if (!bvhs) return c->fail(CRT_ERR_INVALID, "%s: bvhs is NULL", what);
+    if (M == 0 && K > 0) return c->fail(CRT_ERR_INVALID, "%s: %u views and no BVH in the set", what, K);
+    std::vector<uint8_t> named(N, 0);
+    uint64_t tris = 0;
+    for (uint32_t m = 0; m < M; m++) {
+        if (bvhs[m] >= N) return c->fail(CRT_ERR_INVALID, "%s: bvhs[%u] = %u of a scene with %u BLAS", what, m, bvhs[m], N);
+        if (named[bvhs[m]]) return c->fail(CRT_ERR_INVALID, "%s: bvhs[%u] = %u is named twice", what, m, bvhs[m]);
+        named[bvhs[m]] = 1; tris += f.triCount[bvhs[m]];
+    }
+    if (setTris != tris) return c->fail(CRT_ERR_INVALID, "%s: %u triangles per shape, the %u uploaded BVHs of the set have %llu (Refit keeps the topology)", what, setTris, M, (unsigned long long)tris);
+    if (!haveT || blasCount != N) return c->fail(CRT_ERR_INVALID, "%s: %u transforms per shape%s, the uploaded scene has %u BLAS", what, blasCount, haveT ? "" : " (T is NULL)", N);
+    if (f.tlasNodeCount != 2u * N) return c->fail(CRT_ERR_UNSUPPORTED, "%s: the scene was uploaded with %u TLAS nodes, TLASBVH::Build makes %u", what, f.tlasNodeCount, 2u * N);
+    if (passes < 1 || passes > 4) return c->fail(CRT_ERR_INVALID, "%s: passes must be 1..4 (the reference's UI range, renderer.cpp:178)", what);
+    if ((uint64_t)K * frames > 0x7fffffffull) return c->fail(CRT_ERR_UNSUPPORTED, "%s: at most 2^31-1 view-frames per call (%u views x %u frames)", what, K, frames);
+    if (c->renderAccel != 0) return c->fail(CRT_ERR_UNSUPPORTED, "%s: the KD-tree / grid structures have no refit (crt_set_render_accel(0) first; crt_refit_device drops those sets too)", what);
+    if (K > 0 && S == 0) return c->fail(CRT_ERR_INVALID, "%s: %u views and no shape", what, K);
+    if (!viewShape && S != K) return c->fail(CRT_ERR_INVALID, "%s: without view_shape view k renders shape k, so S (%u) must equal K (%u)", what, S, K);
+    const ShapeSetLayout L(f, bvhs, M, S);
+    if (L.tableBytes > crt::kMaxGeomBytes)
+        return c->fail(CRT_ERR_UNSUPPORTED, "%s: %u shapes of %u bytes each exceed the 4 GiB the kernel's 32-bit offsets address; split the job", what, S, L.imageStride);
+    return 0;
+}
+
+// The job on `st`, after the checks that need no launch: shapes_run's with the set's two tables enqueued in front of the ONE leaf launch and the ONE box launch.
+// The tables travel from the tail of the pinned block the read-back uses; the call waits for that read-back, which is behind the copy on `st`.
+static int shape_sets_run(crt_ctx* c, const float* dCams, uint32_t K, const uint32_t* bvhs, uint32_t M, const float* dPos, uint32_t S, const float* dT, const int32_t* dViewShape,
+                          uint32_t sppFirst, uint32_t frames, uint32_t passes, float scale, float* dRgba, uint32_t* dPixels, float* rootBoxOut, crt_tlas_node* tlasOut, hipStream_t st,
+                          const char* what)
+{
+    const crt_ctx::Flat& f = c->flat;
+    ShapeSetLayout L(f, bvhs, M, S);
+    const uint32_t N = L.N;
+    int r;
+    if (c->refitPlans.size() != f.triCount.size()) c->refitPlans.assign(f.triCount.size(), crt_ctx::RefitPlan{});
+    std::vector<uint32_t> instRoot(N, crt::kInstLive);
+    for (crt::ShapeSetMesh& d : L.mesh) {
+        if (!c->refitPlans[d.bvh].built && (r = build_refit_plan(c, d.bvh))) return r;
+        const crt_ctx::RefitPlan& P = c->refitPlans[d.bvh];
+        d.plan = reinterpret_cast<const crt::RefitPlanRec*>(P.dPlan); d.levelOff = P.dLevelOff; d.levels = P.levels; d.rootCode = P.rootCode;
+        // node 0 of the refitted BVH as the image names it (shape_build.hip image_ref)
+        instRoot[d.bvh] = (P.rootCode & crt::kPlanInterior) ? (crt::kRefInterior | ((d.pairRel >> 4) + (P.rootCode & ~crt::kPlanInterior) * 4u)) : ((d.leafRel + P.rootCode * 48u) >> 4);
+    }
+    const size_t nodeBytes = (size_t)2u * N * sizeof(crt::TlasNode), meshBytes = (size_t)M * sizeof(crt::ShapeSetMesh);
+    const size_t boxesAt = L.headBytes, nodesAt = boxesAt + (rootBoxOut ? (size_t)S * M * 24u : 0), tablesAt = (nodesAt + (tlasOut ? (size_t)S * nodeBytes : 0) + 15u) & ~(size_t)15u;
+    const size_t backBytes = tablesAt + meshBytes + (size_t)N * 4u;
+    // The builds are readers, as crt_render_shapes': the live pairs, leaf records, Instance records and node-0 boxes as the last write left them.
+    if ((r = wait_scene(c, st))) return r;
+    if ((r = job_table(c, L.tableBytes, backBytes, st))) return r;
+    char* table = c->dPoseTable;
+    HIPCK(c, hipMemsetAsync(table, 0xff, sizeof(uint32_t), st));            // ShapeJobHeader::badView = kPoseNoBadView
+    memcpy(c->hPoseBack + tablesAt, L.mesh.data(), meshBytes); memcpy(c->hPoseBack + tablesAt + meshBytes, instRoot.data(), (size_t)N * 4u);
+    HIPCK(c, hipMemcpyAsync(table + L.meshOff, c->hPoseBack + tablesAt, meshBytes + (size_t)N * 4u, hipMemcpyHostToDevice, st));      // (instRootOff = meshOff + meshBytes)
+    const crt::ShapeSetBuildDev sb{c->hScene.geom, (uint32_t)f.leafOff, dPos, L.setTris, c->dRootBox, L.rowFloats, table, L.rowsOff, L.meshOff, L.instRootOff, L.imagesOff, L.imageStride, S, M};
+    HIPCK(c, crt_launch_shape_set_build(&sb, L.mesh.data(), instRoot.data(), dViewShape, K, st));
+    HIPCK(c, crt_launch_tlas_build_shapes(c->hScene.geom, (uint32_t)f.instOff, dT, reinterpret_cast<const float*>(table + L.rowsOff), N, (uint32_t)(f.tlasPairOff - f.tlasOff),
+                                          (uint32_t)(f.instOff - f.tlasOff), c->hScene.poolRefBits, table, L.headsOff, L.imagesOff + L.poseRel, L.imageStride, S, st));
+    if (rootBoxOut)
+        for (uint32_t m = 0; m < M; m++)                                    // entry bvhs[m] of every row -> box (s, m)
+            HIPCK(c, hipMemcpy2DAsync(c->hPoseBack + boxesAt + (size_t)m * 24u, (size_t)M * 24u, table + L.rowsOff + (size_t)bvhs[m] * 24u, (size_t)L.rowFloats * 4u, 24, S, hipMemcpyDeviceToHost, st));
+    if (tlasOut) HIPCK(c, hipMemcpy2DAsync(c->hPoseBack + nodesAt, nodeBytes, table + L.imagesOff + L.poseRel, L.imageStride, nodeBytes, S, hipMemcpyDeviceToHost, st));
+    // the one host wait: a job with a view_shape entry out of range or a failed build does not run, and the launches' LDS stack is sized by the tallest shape's TLAS
+    if ((r = read_back(c, st, c->poseBack, c->hPoseBack, table, L.headBytes))) return r;
+    const crt::ShapeJobHeader& job = *reinterpret_cast<const crt::ShapeJobHeader*>(c->hPoseBack);
+    if (job.badView != crt::kPoseNoBadView) return c->fail(CRT_ERR_INVALID, "%s: view_shape[%u] lies outside [0, %u)", what, job.badView, S);
+    crt::Scene job_scene = c->hScene;                                       // the launches' by-value Scene: the context's, with the job's stack depth.  c->hScene stays as it is
+    if ((r = shape_tlas_heads(c, reinterpret_cast<const crt::TlasBuildHeader*>(c->hPoseBack + L.headsOff), S, &job_scene, what))) return r;
+    const crt::ShapeSetTableDev tb{table, dViewShape, L.imagesOff, L.imageStride, L.instRootOff, L.poseRel, (uint32_t)(f.instOff - f.tlasOff)};
+    if ((r = views_run(c, dCams, K, sppFirst, frames, passes, scale, dRgba, dPixels, st, &job_scene, nullptr, nullptr, &tb))) return r;
+    // the host outputs last, once nothing can refuse the job any more (the pinned copy is the call's own until it returns): a refused call writes nothing
+    if (rootBoxOut) memcpy(rootBoxOut, c->hPoseBack + boxesAt, (size_t)S * M * 24u);
+    if (tlasOut)
+        for (uint32_t s = 0; s < S; s++) unpack_tlas_nodes(reinterpret_cast<const crt::TlasNode*>(c->hPoseBack + nodesAt + s * nodeBytes), 2u * N, tlasOut + (size_t)s * 2u * N);
+    return 0;
+}
+
+int crt_render_shape_sets_device(crt_ctx* c, const float* d_cams, uint32_t K, const uint32_t* bvhs, uint32_t M, const float* d_positions, uint32_t S, uint32_t setTris, const float* d_T,
+                                 uint32_t blasCount, const int32_t* d_view_shape, uint32_t spp_first, uint32_t frames, uint32_t passes, float scale, float* d_out_rgba,
+                                 uint32_t* d_out_pixels, float* root_box_out, crt_tlas_node* tlas_out, void* stream)
+{
+    if (!c) return CRT_ERR_INVALID;
+    const char* what = "crt_render_shape_sets_device";
+    int r;
+    if ((r = shape_sets_check(c, K, bvhs, M, S, setTris, d_T != nullptr, blasCount, d_view_shape != nullptr, frames, passes, what))) return r;
+    if (K == 0 || frames == 0) return CRT_OK;
+    const size_t px = (size_t)c->cfg.width * c->cfg.height;
+    if (reinterpret_cast<uintptr_t>(d_out_rgba) & 15u) return c->fail(CRT_ERR_INVALID, "%s: d_out_rgba %p is not 16-byte aligned", what, (void*)d_out_rgba);
+    hipStream_t st = nullptr; int k = 0;
+    if ((r = device_entry(c, what, {{d_cams, (size_t)K * 48}, {d_positions, (size_t)S * setTris * 36}, {d_T, (size_t)S * blasCount * 64}, {d_out_rgba, K * px * 16}}, stream, &st))) return r;
+    if (d_out_pixels && (r = check_device_buffer(c, d_out_pixels, K * px * 4, what))) return r;
+    if (d_view_shape && (r = check_device_buffer(c, d_view_shape, (size_t)K * 4, what))) return r;
+    if ((r = take_query_slot(c, &k))) return r;
+    if ((r = shape_sets_run(c, d_cams, K, bvhs, M, d_positions, S, d_T, d_view_shape, spp_first, frames, passes, scale, d_out_rgba, d_out_pixels, root_box_out, tlas_out, st, what))) return r;
+    return end_device_query(c, k, st);
+}
+
+int crt_render_shape_sets(crt_ctx* c, const float* cams, uint32_t K, const uint32_t* bvhs, uint32_t M, const float* positions, uint32_t S, uint32_t setTris, const float* T, uint32_t blasCount,
+                          const int32_t* view_shape, uint32_t spp_first, uint32_t frames, uint32_t passes, float scale, float* out_rgba, uint32_t* out_pixels, float* root_box_out,
+                          crt_tlas_node* tlas_out)
+{
+    if (!c) return CRT_ERR_INVALID;
+    const char* what = "crt_render_shape_sets";
+    int r;
+    if ((r = shape_sets_check(c, K, bvhs, M, S, setTris, T != nullptr, blasCount, view_shape != nullptr, frames, passes, what))) return r;
+    if (K == 0 || frames == 0) return CRT_OK;
+    if (!cams || !positions || !out_rgba) return c->fail(CRT_ERR_INVALID, "%s: NULL buffer", what);
+    if (view_shape)
+        for (uint32_t k = 0; k < K; k++)
+            if (view_shape[k] < 0 || (uint32_t)view_shape[k] >= S) return c->fail(CRT_ERR_INVALID, "%s: view_shape[%u] = %d lies outside [0, %u)", what, k, view_shape[k], S);
+    HIPCK(c, hipSetDevice(c->cfg.device));
+    const size_t camBytes = (size_t)K * 48, posBytes = ((size_t)S * setTris * 36 + 15u) & ~(size_t)15u, tBytes = (size_t)S * blasCount * 64;
+    ViewsStage G;
+    if ((r = views_stage_in(c, K, out_rgba, out_pixels, camBytes + posBytes + tBytes + (view_shape ? (size_t)K * 4 : 0), &G))) return r;
+    float* dCams = reinterpret_cast<float*>(G.extra); float* dPos = reinterpret_cast<float*>(G.extra + camBytes);
+    float* dT = reinterpret_cast<float*>(G.extra + camBytes + posBytes);
+    int32_t* dViewShape = view_shape ? reinterpret_cast<int32_t*>(G.extra + camBytes + posBytes + tBytes) : nullptr;
+    HIPCK(c, hipMemcpyAsync(dCams, cams, camBytes, hipMemcpyHostToDevice, c->stream));
+    HIPCK(c, hipMemcpyAsync(dPos, positions, (size_t)S * setTris * 36, hipMemcpyHostToDevice, c->stream));
+    HIPCK(c, hipMemcpyAsync(dT, T, tBytes, hipMemcpyHostToDevice, c->stream));
+    if (dViewShape) HIPCK(c, hipMemcpyAsync(dViewShape, view_shape, (size_t)K * 4, hipMemcpyHostToDevice, c->stream));
+    if ((r = shape_sets_run(c, dCams, K, bvhs, M, dPos, S, dT, dViewShape, spp_first, frames, passes, scale, G.dRgba, G.dPix, root_box_out, tlas_out, c->stream, what))) return r;
     return views_stage_out(c, K, out_rgba, out_pixels, G);
 }
 

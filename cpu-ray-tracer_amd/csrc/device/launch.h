@@ -78,6 +78,9 @@ hipError_t crt_launch_render_poses(const crt::Scene* sc, const crt::PoseTableDev
 // view's shape in the table `t` names; sc->stackDepth is the job's.  The per-view sums are crt_launch_views_accumulate's.
 hipError_t crt_launch_render_shapes(const crt::Scene* sc, const crt::ShapeTableDev* t, const float* cams, void* slab, crt::Counters* counters, uint32_t tileFirst, uint32_t tileStride,
     uint32_t tileCount, uint32_t tilesX, uint32_t sppFirst, uint32_t frames, uint32_t passes, uint32_t jFirst, uint32_t nj, hipStream_t stream);
+// crt_render_shape_sets (render_shape_sets.h): the same with the instances that walk the lane's image named by the table's instRoot words; two-level scenes only
+hipError_t crt_launch_render_shape_sets(const crt::Scene* sc, const crt::ShapeSetTableDev* t, const float* cams, void* slab, crt::Counters* counters, uint32_t tileFirst, uint32_t tileStride,
+    uint32_t tileCount, uint32_t tilesX, uint32_t sppFirst, uint32_t frames, uint32_t passes, uint32_t jFirst, uint32_t nj, hipStream_t stream);
 hipError_t crt_launch_views_accumulate(const void* slab, float* outRgba, uint32_t* outPixels, uint32_t tileFirst, uint32_t tileStride, uint32_t tileCount, uint32_t tilesX, uint32_t W,
     uint32_t H, uint32_t frames, uint32_t passes, uint32_t jFirst, uint32_t nj, float scale, hipStream_t stream);
 
@@ -153,6 +156,9 @@ hipError_t crt_launch_tlas_build_shapes(const char* geom, uint32_t instOff, cons
 // indices (viewShape may be nullptr); the caller sets ShapeJobHeader::badView to kPoseNoBadView on the stream first.  plan / levelOff / levels / rootCode: crt_launch_refit's
 hipError_t crt_launch_shape_build(const crt::ShapeBuildDev* b, const void* plan, const uint32_t* levelOff, uint32_t levels, uint32_t rootCode, const int32_t* viewShape, uint32_t K,
     hipStream_t stream);
+// crt_render_shape_sets: the same for b->M BVHs of a two-level scene per shape, in one leaf launch and one box launch of a workgroup per (shape, mesh).  meshes / instRoot:
+// the host's copy of the two tables the caller has enqueued to b->meshOff / b->instRootOff of the table (layout.h ShapeSetMesh)
+hipError_t crt_launch_shape_set_build(const crt::ShapeSetBuildDev* b, const crt::ShapeSetMesh* meshes, const uint32_t* instRoot, const int32_t* viewShape, uint32_t K, hipStream_t stream);
 
 // abi.cpp's test switch CRT_DEBUG_QUERY_GRID=<k>: an upper bound on the workgroups of a persistent query launch (0: none).  Host side only: each wrapper passes its grid through it.
 uint32_t crt_debug_query_grid(void);

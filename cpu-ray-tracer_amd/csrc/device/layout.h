@@ -205,6 +205,36 @@ struct ShapeTableDev {
     uint32_t rootRef;                             // the refitted BVH's node 0, image-relative
     uint32_t bvh, poseRel, instRel;               // two-level: the instance that walks the image; the pose image inside an image; the Instance records inside that
 };
+// crt_render_shape_sets' table: the shape table with M BVHs of a two-level scene deforming per shape.  Behind the S rows of node-0 boxes the header region holds two
+// tables that the kernels read from device memory (M and blasCount are the job's, so neither fits a kernel argument): M ShapeSetMesh descriptors at meshOff and the
+// per-instance words instRoot[blasCount] at instRootOff.  An image holds, for every m, mesh m's NodePairs at pairRel and its LeafTris at leafRel — offsets of its own
+// from the image's first byte —, then the pose image at poseRel.  References inside EVERY sub-image are relative to the image's first byte, not the sub-image's, so
+// the one per-lane delta of ShapeBvh (render_shapes.h) still serves every fetch.  The first sub-image is laid out as a single shape's image: leafRel >= 64 for every m.
+struct alignas(16) ShapeSetMesh {
+    const RefitPlanRec* plan; const uint32_t* levelOff;                           // the BVH's refit plan (refit.hip), its level offsets
+    uint32_t levels, rootCode;                                                    // ... its level count and node 0's child code
+    uint32_t pairBase, pairCount, triBase, triCount;                              // the live BVH, as ShapeBuildDev names it
+    uint32_t bvh;                                                                 // the BLAS (= Instance) index: its entry in a row of node-0 boxes
+    uint32_t triFirst;                                                            // its first triangle in a shape's positions = its first leaf slot of the set
+    uint32_t pairRel, leafRel;                                                    // where its sub-image's pairs and leaves start inside an image
+};
+// instRoot[i]: the image-relative reference of node 0 of instance i's BVH if it deforms, kInstLive if the instance walks Scene::geom.  No image-relative reference is
+// 0: an interior root has kRefInterior set, a leaf root is at least leafRel >> 4 >= 4.
+constexpr uint32_t kInstLive = 0u;
+// what the set's build kernels take by value
+struct ShapeSetBuildDev {
+    const char* geom; uint32_t leafOff;                                           // the live geometry buffer, its leaf section
+    const float* pos; uint32_t setTris;                                           // S * setTris * 9: per shape mesh 0's triangles, then mesh 1's, ...
+    const float* liveRootBox; uint32_t rowFloats;                                 // the device's node-0 boxes, 6 * blasCount floats
+    char* table; uint32_t rowsOff, meshOff, instRootOff, imagesOff, imageStride, S, M;
+};
+// what the set's render kernel takes by value (ShapeTableDev with the instRoot table in place of the one BVH)
+struct ShapeSetTableDev {
+    const char* table; const int32_t* viewShape;  // viewShape == nullptr: view k renders shape k
+    uint32_t imagesOff, imageStride;
+    uint32_t instRootOff;                         // instRoot[blasCount] in the table
+    uint32_t poseRel, instRel;                    // the pose image inside an image; the Instance records inside that
+};
 constexpr uint32_t kTlasMaxBlas = 256u;   // tlas_bvh.cpp:21 (nodeIdx[256])
 
 // Whether a crt_hit's indices may be used as addresses by the hit-info query (shade_query.hip): ONE predicate for the host entry, which refuses the call, and for

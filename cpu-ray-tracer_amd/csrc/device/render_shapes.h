@@ -30,6 +30,7 @@ __device__ __forceinline__ uint32_t bvh_record(const ShapeBvh& w, uint32_t ref) 
 
 template <int KIND>
 struct ShapeWorld : FileSurface<KIND> {
+    static constexpr int kind = KIND;
     const char* table;                    // the shape table (wave-uniform)
     uint32_t image;                       // this lane's shape: its image's offset in the table
     uint32_t rootRef, bvh;                // the refitted BVH's node 0 (image-relative) and, KIND 1, the instance that walks it (both wave-uniform)
@@ -65,11 +66,12 @@ __device__ __forceinline__ uint32_t tlas_insts(const ShapeWorld<1>& w) { return 
 __device__ __forceinline__ uint32_t tlas_root(const ShapeWorld<1>& w) { return w.tlasRoot; }
 
 // the shape of `view`: an index the build launch has found to lie in [0, S) before this kernel is launched
-template <int KIND>
-__device__ __forceinline__ ShapeWorld<KIND> shape_world(const ShapeTableDev& t, uint32_t view)
+template <class WORLD>
+__device__ __forceinline__ WORLD world_of(const ShapeTableDev& t, uint32_t view)
 {
+    constexpr int KIND = WORLD::kind;
     const uint32_t s = t.viewShape ? (uint32_t)t.viewShape[view] : view;
-    ShapeWorld<KIND> w;
+    WORLD w;
     w.table = t.table; w.image = t.imagesOff + s * t.imageStride; w.rootRef = t.rootRef; w.bvh = t.bvh;
     w.tlas = w.image + t.poseRel; w.inst = w.tlas + t.instRel;
     w.tlasRoot = 0u;
@@ -79,10 +81,11 @@ __device__ __forceinline__ ShapeWorld<KIND> shape_world(const ShapeTableDev& t, 
 
 // render_views_kernel's launch shape, slab, seeds and camera handling (render_views.h: entry = tile rank * windows + window, lane = view-frame, the camera read again
 // per pixel); the path itself is sample_step / sample_unwind over the lane's ShapeWorld.
-template <int KIND>
-__global__ __launch_bounds__(256, 4) void render_shapes_kernel(const Scene sc, const ShapeTableDev st, const float* __restrict__ cams, char* __restrict__ slab,
-                                                              Counters* __restrict__ counters, uint32_t tileFirst, uint32_t tileStride, uint32_t tileCount, uint32_t tilesX,
-                                                              uint32_t sppFirst, uint32_t frames, uint32_t passes, uint32_t jFirst, uint32_t nj, uint32_t nEntries)
+// (the body of render_shapes_kernel and of render_shape_sets_kernel, render_shape_sets.h: WORLD is the lane's world, world_of(st, view) makes it)
+template <class WORLD, class TABLE>
+__device__ __forceinline__ void render_shape_lanes(const Scene& sc, const TABLE& st, const float* __restrict__ cams, char* __restrict__ slab, Counters* __restrict__ counters,
+                                                   uint32_t tileFirst, uint32_t tileStride, uint32_t tileCount, uint32_t tilesX, uint32_t sppFirst, uint32_t frames, uint32_t passes,
+                                                   uint32_t jFirst, uint32_t nj, uint32_t nEntries)
 {
     extern __shared__ uint32_t ldsAll[];
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
@@ -97,7 +100,7 @@ __global__ __launch_bounds__(256, 4) void render_shapes_kernel(const Scene sc, c
     slab += slab_block_position(win, tileCount, tl, 64u * passes);                // this tile's block of this window's region of the sample slab
     const uint32_t tile = tileFirst + tl * tileStride;
     const uint32_t tx = tile % tilesX, ty = tile / tilesX;
-    const ShapeWorld<KIND> world = shape_world<KIND>(st, view);
+    const WORLD world = world_of<WORLD>(st, view);
     // this lane's LDS columns: the traversal stack (the job's depth), then the throughput factors
     const uint32_t stackWords = world.stack_words(sc);
     uint32_t* stk = ldsAll + wave * (stackWords + 15u) * 64u + lane;
@@ -119,7 +122,7 @@ __global__ __launch_bounds__(256, 4) void render_shapes_kernel(const Scene sc, c
         bool inside = false; int depth = 0;
         nPrimary++;
         f3 L = mk3(0, 0, 0);
-        while (!sample_step<ShapeWorld<KIND>, false>(sc, world, stk, fst, O, D, inside, depth, seed, L, nRays, nMesh, steps)) {}
+        while (!sample_step<WORLD, false>(sc, world, stk, fst, O, D, inside, depth, seed, L, nRays, nMesh, steps)) {}
         sample_unwind(fst, depth, L);
         uint32_t pass = 0;
         if (passes != 1u) pass = item - pix * passes;
@@ -128,6 +131,14 @@ __global__ __launch_bounds__(256, 4) void render_shapes_kernel(const Scene sc, c
     atomicAdd(&counters->v[0], (unsigned long long)nRays);
     atomicAdd(&counters->v[1], (unsigned long long)nPrimary);
     if (nMesh) atomicAdd(&counters->v[7], (unsigned long long)nMesh);
+}
+
+template <int KIND>
+__global__ __launch_bounds__(256, 4) void render_shapes_kernel(const Scene sc, const ShapeTableDev st, const float* __restrict__ cams, char* __restrict__ slab,
+                                                              Counters* __restrict__ counters, uint32_t tileFirst, uint32_t tileStride, uint32_t tileCount, uint32_t tilesX,
+                                                              uint32_t sppFirst, uint32_t frames, uint32_t passes, uint32_t jFirst, uint32_t nj, uint32_t nEntries)
+{
+    render_shape_lanes<ShapeWorld<KIND>>(sc, st, cams, slab, counters, tileFirst, tileStride, tileCount, tilesX, sppFirst, frames, passes, jFirst, nj, nEntries);
 }
 
 } // namespace crt

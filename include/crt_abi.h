@@ -622,7 +622,8 @@ int  crt_render_poses_device(crt_ctx* ctx, const float* d_cams, uint32_t K, cons
  * live BVH is refitted in place.  Here the S shapes are built side by side (device/shape_build.hip: a leaf launch over (leaf slot, shape) and a box launch of one
  * workgroup per shape, then for a two-level scene the S TLAS builds in one launch), each into a job-local image: the refitted node pairs and leaf triangles of BVH
  * `bvh`, and for a two-level scene a pose as crt_render_poses keeps it; every lane of crt_render_views' launch walks the image of its own view's shape
- * (device/render_shapes.h).  Shading records, the other BVHs and the textures are shared.  ABI version 3 still: additions, detected by symbol.
+ * (device/render_shapes.h).  Shading records, the other BVHs and the textures are shared.  ABI version 3 still: additions, detected by symbol.  ONE BVH deforms
+ * per job here; a two-level scene in which several BLASes deform at the same time goes to crt_render_shape_sets, below.
  * cams: K records of 12 floats, crt_set_camera's arguments.  positions: S * triCount * 9 floats, shape s's at positions + 9 * triCount * s, each exactly what
  * crt_refit_device takes as d_positions (vertex0, vertex1, vertex2 per triangle in the reference's triangle order; not validated, as there).  T: S * blasCount
  * row-major mat4s, shape s's at T + 16 * blasCount * s, each what crt_update_transforms_device takes; NULL with blasCount 0 for a CRT_SCENE_FILE scene.
@@ -668,6 +669,50 @@ int  crt_render_shapes_device(crt_ctx* ctx, const float* d_cams, uint32_t K, uin
                               uint32_t blasCount, const int32_t* d_view_shape /* or NULL */, uint32_t spp_first, uint32_t frames, uint32_t passes, float scale, float* d_out_rgba,
                               uint32_t* d_out_pixels /* or NULL */, float* root_box_out /* host, or NULL */, crt_tlas_node* tlas_out /* host, or NULL */,
                               void* stream);                                                                                                   /* device pointers, one host wait */
+
+/* The same job with SEVERAL deforming meshes: M >= 1 BLASes of a two-level scene deform per shape — two skinned characters, a cloth on a body, an optimiser over the
+ * vertices of more than one object.  A crt_render_shapes job per BLAS cannot put them into one image, and the loop pays crt_refit_device's host wait once per mesh.
+ * bvhs (HOST memory in both entries): M distinct BLAS indices, in any order.  setTris: the sum over m of the uploaded triCount of bvhs[m].  positions: S * setTris * 9
+ * floats, shape s's at positions + 9 * setTris * s: BVH bvhs[0]'s triangles first, then bvhs[1]'s, and so on, each block exactly what crt_refit_device takes for
+ * that BVH.  cams, T, view_shape, spp_first, frames, passes, scale, out_rgba, out_pixels: crt_render_shapes' (T is never NULL: two-level scenes only).
+ * The contract is crt_render_shapes' with "the BVH" replaced by "every BVH of the set": for view k with s = view_shape[k], out_rgba[k] is bit for bit what
+ * crt_refit_device(bvhs[m], its block of positions[s]) for every m (in any order); crt_update_transforms_device(T[s]); crt_set_camera(cams[k]); crt_clear;
+ * crt_render(spp_first, frames, passes); crt_read_accumulator leaves on a context in the same live state; out_pixels[k] is crt_resolve_screen(scale)'s pixel of
+ * that; root_box_out[(s * M + m) * 6 ..] (host, may be NULL) is that refit's rootBox; tlas_out[s] (host, may be NULL) is byte for byte
+ * crt_update_transforms_device's tlasOut.  Refit's skipped node 1 is kept PER BVH: node 1 of each deforming BVH keeps the box the live scene holds.  The live scene,
+ * crt_tick's rendered-ahead frames, the camera and the accumulator are not changed; counters grow as crt_render_shapes' do; the job is a reader under the
+ * scene-write protocol; the one host wait is crt_render_shapes' (the job header plus the S build headers, with the boxes and nodes when asked for; besides growing
+ * scratch and the refit plans of the set's BVHs, each built by the first call that names it).  Scratch is the table crt_render_poses / crt_render_shapes keep, at
+ * most 4 GiB: per shape 64 bytes per node pair and 48 per triangle of every BVH of the set + about 256 * blasCount.  With M = 1 the entry gives bit for bit what
+ * crt_render_shapes gives for the same job.
+ * How: device/shape_build.hip refits the M * S BVHs side by side in ONE leaf launch over (leaf slot of the set, shape) and ONE box launch of a workgroup per
+ * (shape, mesh), whatever M is; workgroup (s, m) writes entry bvhs[m] of shape s's row of node-0 boxes, over which the S TLAS builds run as they do for
+ * crt_render_shapes.  An image holds the M sub-images and the pose; references in every sub-image are relative to the image's first byte, so a lane still needs one
+ * offset.  The render kernel (device/render_shape_sets.h) looks an instance up in a table of blasCount words: the image-relative root of its BVH, or "walk the
+ * live geometry".
+ * Refusals (nothing is written, crt_last_error says why), in this order: no scene CRT_ERR_STATE; a PrimitiveScene CRT_ERR_UNSUPPORTED; a CRT_SCENE_FILE scene
+ * CRT_ERR_INVALID (it has one BVH: crt_render_shapes); bvhs NULL, or M == 0 with K > 0, CRT_ERR_INVALID; a bvhs entry out of range or named twice CRT_ERR_INVALID
+ * (crt_last_error names the entry); setTris different from the sum of the uploaded counts CRT_ERR_INVALID; then the remaining refusals of crt_render_shapes in its
+ * order: T == NULL or blasCount != bvhCount CRT_ERR_INVALID; a TLAS node count other than 2 * bvhCount CRT_ERR_UNSUPPORTED; passes outside 1..4 CRT_ERR_INVALID;
+ * K * frames > 2^31-1 CRT_ERR_UNSUPPORTED; crt_set_render_accel != 0 CRT_ERR_UNSUPPORTED; S == 0 with K > 0, or view_shape NULL with S != K, CRT_ERR_INVALID; a table
+ * beyond 4 GiB CRT_ERR_UNSUPPORTED; NULL, misaligned, host or other-device memory, a stream of another device CRT_ERR_INVALID; a view_shape entry outside [0, S)
+ * CRT_ERR_INVALID; a shape whose TLAS build finds no candidate (non-finite positions of any mesh of the shape among the causes) CRT_ERR_INVALID, crt_last_error
+ * names the shape; a TLAS too tall for the LDS stack CRT_ERR_UNSUPPORTED; a failed device allocation CRT_ERR_DEVICE.  K == 0 or frames == 0 is a no-op after the
+ * checks that need no buffer.
+ * When to use it (one MI355X, 1280x720, tlas_scene.xml with all three BLASes deforming, profiles/render_shape_sets.json): 64 shapes of one frame each take 252 ms against 2 261 ms for the loop
+ * (9.0x: 3 crt_refit_device + crt_update_transforms_device, crt_set_camera, crt_clear, crt_render, crt_sync per shape); 16 shapes x 64 frames 478 against 831 ms (1.74x);
+ * at 4 x 256 the loop wins (338 against 436 ms).  So, as for crt_render_shapes: up to 64 frames per view call the entry, from 256 on loop crt_refit_device + crt_render, in
+ * between measure.  The 64 x 3 shape builds by themselves cost 0.18 ms inside the entry against 26.2 ms for the 64 x 4 calls.  The per-instance lookup is not visible in the
+ * wall time: with M = 1 the entry takes 215.4 ms against 211.0 ms for crt_render_shapes of the parent commit at 64 x 1 (1.02x, each side spreading over 192 - 243 ms) and
+ * 396.9 against 403.4 ms at 16 x 64 (0.98x). */
+int  crt_render_shape_sets(crt_ctx* ctx, const float* cams /* K * 12 */, uint32_t K, const uint32_t* bvhs /* host, M */, uint32_t M, const float* positions /* S * setTris * 9 */,
+                           uint32_t S, uint32_t setTris, const float* T /* S * blasCount * 16 */, uint32_t blasCount, const int32_t* view_shape /* K, or NULL */,
+                           uint32_t spp_first, uint32_t frames, uint32_t passes, float scale, float* out_rgba /* K * W*H float4 */, uint32_t* out_pixels /* K * W*H or NULL */,
+                           float* root_box_out /* host, S * M * 6, or NULL */, crt_tlas_node* tlas_out /* host, S * 2 * blasCount, or NULL */);     /* host pointers, synchronous */
+int  crt_render_shape_sets_device(crt_ctx* ctx, const float* d_cams, uint32_t K, const uint32_t* bvhs /* host, M */, uint32_t M, const float* d_positions, uint32_t S, uint32_t setTris,
+                                  const float* d_T, uint32_t blasCount, const int32_t* d_view_shape /* or NULL */, uint32_t spp_first, uint32_t frames, uint32_t passes, float scale,
+                                  float* d_out_rgba, uint32_t* d_out_pixels /* or NULL */, float* root_box_out /* host, or NULL */, crt_tlas_node* tlas_out /* host, or NULL */,
+                                  void* stream);                                                                                               /* device pointers, one host wait */
 
 /* ---- PrimitiveScene (second half): infra/scene/primitive_scene.cpp — the reference's hard-coded demo room (six walls, swinging light quad,
  * bouncing mirror ball, "rounded corners" sphere, spinning glass cube, glass torus; template/primitives.h Sphere :31, Cube :187, Quad :321, Torus :380; the
