@@ -578,7 +578,7 @@ int crt_upload_scene(crt_ctx* c, const crt_scene_desc* sd)
     crt::NodePair* tlasPairs = reinterpret_cast<crt::NodePair*>(geom.data() + tlasPairOffB);
     // The width the scene's pool references are written in (layout.h): 16 bits where every index fits, else 32 — whose index limit is what kMaxGeomBytes imposes
     // on the records anyway (index * 64 and leafOff + index * 48 below 2^32), checked here all the same; a scene beyond it has no pool form (render_tiles_kernel).
-    const bool ref16ok = nPairs <= crt::kRef16MaxIndex && nTris < crt::kRef16MaxIndex && !hook("CRT_DEBUG_NO_REF16");   // (tests: a scene that fits, treated as one that does not)
+    const bool ref16ok = nPairs <= crt::kRef16MaxIndex && nTris <= crt::kRef16MaxIndex && !hook("CRT_DEBUG_NO_REF16");   // (tests: a scene that fits, treated as one that does not)
     const bool refWideOk = nPairs <= crt::kRefWideMaxIndex && nTris < crt::kRefWideMaxIndex && nPairs * 64 < crt::kMaxGeomBytes && leafOffB + nTris * 48 < crt::kMaxGeomBytes;
     const uint32_t poolRefBits = ref16ok ? 16u : (refWideOk ? 32u : 0u);
     const crt::PoolRefForm PR = crt::pool_ref_form(poolRefBits);

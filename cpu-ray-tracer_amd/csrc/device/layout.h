@@ -33,7 +33,8 @@ constexpr uint64_t kMaxGeomBytes = 1ull << 32;     // 32-bit byte offsets
 // It comes in two widths, and a scene is uploaded in exactly one of them (Scene::poolRefBits); both are stored in the same uint32_t fields (NodeChild::ref16,
 // TlasNode::ref16, Instance::rootRef16, Scene::rootRef16 — the names are the narrow form's).
 //   16-bit form (2 bytes per stack entry: LDS is what limits the waves per SIMD): tag in bits 15..14, index in bits 13..0, return marker 0xFFFF.
-//               Scenes of <= 16383 node pairs and < 16383 triangles over all BVHs.
+//               Scenes of <= 16382 node pairs and <= 16382 triangles over all BVHs (kRef16MaxIndex each: the highest index a reference carries is the last
+//               triangle's, the triangle count itself).
 //   32-bit form (4 bytes per stack entry): tag in bits 31..30, index in bits 29..0, return marker 0xFFFFFFFF.  Every other scene: an index is bounded by
 //               kMaxGeomBytes (index * 64 and leafOff + index * 48 stay below 2^32), far below 2^30.
 // The tags and what the index counts, in either width:

@@ -144,7 +144,7 @@ const char* crt_last_error(crt_ctx* ctx);                      /* ctx may be NUL
 
 /* ---- scene / camera (lower seam) -------------------------------------------------------------------- */
 /* Flattens to the device layout and copies; host pointers are not kept.  The node references the stream-pool render kernel walks are written 16 bits wide
- * when the scene has <= 16383 node pairs and < 16383 triangles over all its BVHs, 32 bits wide otherwise; the stream-pool kernel can render the scene either way
+ * when the scene has <= 16382 node pairs and <= 16382 triangles over all its BVHs, 32 bits wide otherwise; the stream-pool kernel can render the scene either way
  * (which kernel does: see crt_render), and the in-place writes (crt_update_scene, crt_refit_device, crt_update_transforms_device, crt_build_grid_device) keep the width. */
 int  crt_upload_scene(crt_ctx* ctx, const crt_scene_desc* scene);
 /* In-place update of an uploaded scene for animation (renderer.cpp:147 `animating`), same description as at upload, same topology:
