@@ -110,10 +110,10 @@ HIT_INFO_DTYPE = np.dtype([("I", "<f4", 3), ("material", "<i4"), ("N", "<f4", 3)
 MATERIAL_MISS, MATERIAL_INVALID = -1, -2       # crt_hit_info.material of a miss / of a record whose objIdx or triIdx the scene does not have
 
 # every symbol include/crt_abi.h and include/crt_host.h declare (tests check the library exports all of them)
-ABI_SYMBOLS = ["crt_render_shapes", "crt_render_shapes_device", "crt_render_shape_sets", "crt_render_shape_sets_device", "crt_render_poses", "crt_render_poses_device", "crt_render_views", "crt_render_views_device", "crt_trace","crt_trace_device", "crt_build_bvh_device", "crt_get_bvh", "crt_build_kdtree_device", "crt_get_kdtree", "crt_build_grid_device", "crt_get_grid", "crt_update_transforms_device", "crt_sample", "crt_sample_device", "crt_refit_device", "crt_get_hit_info", "crt_get_hit_info_device", "crt_get_sky_color", "crt_get_sky_color_device", "crt_get_light", "crt_upload_blas_accel", "crt_is_occluded", "crt_find_nearest_device", "crt_is_occluded_device", "crt_upload_primitive_scene", "crt_set_render_accel", "crt_upload_alt_accel", "crt_find_nearest_alt", "crt_update_scene", "crt_abi_version", "crt_device_count", "crt_create", "crt_destroy", "crt_last_error", "crt_upload_scene", "crt_set_camera",
+ABI_SYMBOLS = ["crt_look_words", "crt_update_look", "crt_render_looks", "crt_render_looks_device", "crt_render_shapes", "crt_render_shapes_device", "crt_render_shape_sets", "crt_render_shape_sets_device", "crt_render_poses", "crt_render_poses_device", "crt_render_views", "crt_render_views_device", "crt_trace","crt_trace_device", "crt_build_bvh_device", "crt_get_bvh", "crt_build_kdtree_device", "crt_get_kdtree", "crt_build_grid_device", "crt_get_grid", "crt_update_transforms_device", "crt_sample", "crt_sample_device", "crt_refit_device", "crt_get_hit_info", "crt_get_hit_info_device", "crt_get_sky_color", "crt_get_sky_color_device", "crt_get_light", "crt_upload_blas_accel", "crt_is_occluded", "crt_find_nearest_device", "crt_is_occluded_device", "crt_upload_primitive_scene", "crt_set_render_accel", "crt_upload_alt_accel", "crt_find_nearest_alt", "crt_update_scene", "crt_abi_version", "crt_device_count", "crt_create", "crt_destroy", "crt_last_error", "crt_upload_scene", "crt_set_camera",
                "crt_render", "crt_tick", "crt_reserve", "crt_whitted_tick", "crt_whitted_tick_inspect", "crt_sync", "crt_clear", "crt_read_accumulator", "crt_resolve_screen", "crt_find_nearest", "crt_get_counters",
                "crt_reset_counters", "crt_get_timing", "crt_get_tile_clocks", "crt_bind_accumulator", "crt_accumulator_device_ptr"]
-HOST_SYMBOLS = ["crt_host_bvh_build", "crt_host_scene_bvh_move_and_rebuild", "crt_host_scene_build_bvh_device", "crt_host_scene_build_kdtree_device", "crt_host_kd_build", "crt_host_scene_build_grid_device", "crt_host_grid_build", "crt_host_scene_update_transforms_device", "crt_host_scene_bvh_refit_device", "crt_host_scene_blas_alt_info", "crt_host_scene_blas_alt_copy", "crt_host_primitive_scene_create", "crt_host_primitive_scene_free", "crt_host_primitive_scene_set_time", "crt_host_primitive_scene_desc", "crt_host_primitive_scene_upload", "crt_host_scene_build_alt", "crt_host_scene_upload_alt", "crt_host_scene_alt_info", "crt_host_scene_alt_copy", "crt_host_scene_set_transform", "crt_host_scene_update", "crt_host_math_probe", "crt_host_vertex_dedup", "crt_host_last_error", "crt_host_scene_load", "crt_host_scene_free", "crt_host_scene_upload", "crt_host_scene_kind",
+HOST_SYMBOLS = ["crt_host_scene_look", "crt_host_scene_set_look", "crt_host_bvh_build", "crt_host_scene_bvh_move_and_rebuild", "crt_host_scene_build_bvh_device", "crt_host_scene_build_kdtree_device", "crt_host_kd_build", "crt_host_scene_build_grid_device", "crt_host_grid_build", "crt_host_scene_update_transforms_device", "crt_host_scene_bvh_refit_device", "crt_host_scene_blas_alt_info", "crt_host_scene_blas_alt_copy", "crt_host_primitive_scene_create", "crt_host_primitive_scene_free", "crt_host_primitive_scene_set_time", "crt_host_primitive_scene_desc", "crt_host_primitive_scene_upload", "crt_host_scene_build_alt", "crt_host_scene_upload_alt", "crt_host_scene_alt_info", "crt_host_scene_alt_copy", "crt_host_scene_set_transform", "crt_host_scene_update", "crt_host_math_probe", "crt_host_vertex_dedup", "crt_host_last_error", "crt_host_scene_load", "crt_host_scene_free", "crt_host_scene_upload", "crt_host_scene_kind",
                 "crt_host_scene_triangle_count", "crt_host_scene_bvh_count", "crt_host_scene_bvh_info", "crt_host_scene_bvh_copy",
                 "crt_host_scene_bvh_move_and_refit", "crt_host_scene_blas_transform", "crt_host_scene_tlas_copy", "crt_host_camera_state", "crt_host_renderer_create",
                 "crt_host_renderer_destroy", "crt_host_renderer_init", "crt_host_renderer_set_camera", "crt_host_renderer_set_passes",
@@ -181,6 +181,48 @@ def camera_records(width, height, pairs):
             raise CrtError(rc, lib().crt_host_last_error().decode())
         out[k] = [x for v in a for x in v]
     return out
+
+
+LOOK_HEADER_WORDS, LOOK_MATERIAL_WORDS = 36, 6      # crt_abi.h: crt_look_header, crt_material
+
+
+def look_words(material_count):
+    """crt_look_words: the 4-byte words of one look record of a scene with `material_count` materials"""
+    return LOOK_HEADER_WORDS + LOOK_MATERIAL_WORDS * int(material_count)
+
+
+def look_records(looks):
+    """[L, crt_look_words(materialCount)] uint32 look records (crt_update_look's argument, crt_render_looks' `looks`) from dicts with light_T / light_invT (mat4s, 16
+    floats each, invT supplied by the caller as at upload), light_size, floor_texture, sky_texture (indices into the uploaded textures) and materials =
+    (reflectivity, refractivity, absorption[3], texture index or -1) per material of the uploaded scene.  View the result as float32 to read the float words."""
+    looks = list(looks)
+    m = len(looks[0]["materials"]) if looks else 0
+    out = np.zeros((len(looks), look_words(m)), np.uint32)
+    f, i = out.view(np.float32), out.view(np.int32)
+    for k, lk in enumerate(looks):
+        if len(lk["materials"]) != m:
+            raise ValueError("look_records: every look of an array has the scene's material count")
+        f[k, 0:16] = np.asarray(lk["light_T"], np.float32).reshape(16)
+        f[k, 16:32] = np.asarray(lk["light_invT"], np.float32).reshape(16)
+        f[k, 32] = lk["light_size"]
+        i[k, 33], i[k, 34] = int(lk["floor_texture"]), int(lk["sky_texture"])
+        for j, (refl, refr, ab, tex) in enumerate(lk["materials"]):
+            o = LOOK_HEADER_WORDS + LOOK_MATERIAL_WORDS * j
+            f[k, o], f[k, o + 1] = refl, refr
+            f[k, o + 2:o + 5] = np.asarray(ab, np.float32).reshape(3)
+            i[k, o + 5] = int(tex)
+    return out
+
+
+def look_dicts(records):
+    """look_records' inverse: one dict per record (fresh lists and arrays, so a caller can change one field and pack again)"""
+    rec = np.ascontiguousarray(records, np.uint32)
+    rec = rec.reshape(1, -1) if rec.ndim == 1 else rec
+    f, i = rec.view(np.float32), rec.view(np.int32)
+    m = (rec.shape[1] - LOOK_HEADER_WORDS) // LOOK_MATERIAL_WORDS
+    return [dict(light_T=f[k, 0:16].copy(), light_invT=f[k, 16:32].copy(), light_size=float(f[k, 32]), floor_texture=int(i[k, 33]), sky_texture=int(i[k, 34]),
+                 materials=[(float(f[k, o]), float(f[k, o + 1]), tuple(float(x) for x in f[k, o + 2:o + 5]), int(i[k, o + 5]))
+                            for o in (LOOK_HEADER_WORDS + LOOK_MATERIAL_WORDS * j for j in range(m))]) for k in range(rec.shape[0])]
 
 
 def device_count():
@@ -272,6 +314,57 @@ class Context:
         def run(st):
             self._ck(self.L.crt_render_views_device(self.h, C.c_void_p(cams.data_ptr()), C.c_uint32(k), C.c_uint32(spp_first), C.c_uint32(frames), C.c_uint32(passes),
                                                     C.c_float(1.0 if scale is None else scale), C.c_void_p(out.data_ptr()),
+                                                    C.c_void_p(pixels.data_ptr()) if pixels is not None else None, C.c_void_p(st.cuda_stream)))
+            return out if pixels is None else (out, pixels)
+        return self._enqueue(stream, run)
+
+    def update_look(self, look):
+        """crt_update_look: the live scene's look — light quad, floor / skydome texture, materials — changed in place (no re-upload).  look = one record of
+        look_records, [crt_look_words(materialCount)] uint32."""
+        rec = np.ascontiguousarray(look, np.uint32).reshape(-1)
+        self._ck(self.L.crt_update_look(self.h, _p(rec)))
+
+    def render_looks(self, cameras, looks, spp_first, frames, passes=1, scale=None, view_look=None):
+        """crt_render_looks: the frames of K cameras over L looks of the live scene in one job (host buffers, synchronous; the live scene is not changed).
+        cameras = [K, 12] float32 (camera_records), looks = [L, crt_look_words(materialCount)] uint32 (look_records), view_look = None (view k renders look k; L == K)
+        or K indices into the looks.  Returns the accumulators [K, H, W, 4] float32 — per view what update_look(looks[l]) + set_camera + clear + render(spp_first,
+        frames, passes) + accumulator() leaves on the tiles this context owns, every other pixel 0 — and, when `scale` is given, (accumulators, pixels [K, H, W] uint32)."""
+        cams = np.ascontiguousarray(cameras, np.float32).reshape(-1, 12)
+        rec = np.ascontiguousarray(looks, np.uint32)
+        if rec.ndim != 2:
+            raise ValueError("render_looks: looks must be [L, crt_look_words(materialCount)] uint32")
+        k, n = cams.shape[0], rec.shape[0]
+        vl = None if view_look is None else np.ascontiguousarray(view_look, np.int32).reshape(-1)
+        if vl is not None and vl.shape[0] != k:
+            raise ValueError("render_looks: view_look needs one index per camera")
+        acc = np.zeros((k, self.H, self.W, 4), np.float32)
+        px = np.zeros((k, self.H, self.W), np.uint32) if scale is not None else None
+        self._ck(self.L.crt_render_looks(self.h, _p(cams), C.c_uint32(k), _p(rec), C.c_uint32(n), _p(vl) if vl is not None else None, C.c_uint32(spp_first),
+                                         C.c_uint32(frames), C.c_uint32(passes), C.c_float(1.0 if scale is None else scale), _p(acc), _p(px) if px is not None else None))
+        return acc if scale is None else (acc, px)
+
+    def render_looks_device(self, cams, looks, out, spp_first, frames, passes=1, scale=None, pixels=None, view_look=None, stream=None):
+        """crt_render_looks_device: the same job for torch tensors on the context's device, enqueued on `stream` (default torch.cuda.current_stream()); one host
+        wait, for the build's status header.  cams = [K, 12] float32, looks = [L, crt_look_words(materialCount)] int32 (the records' bit patterns), out = [K, H, W, 4]
+        float32, pixels = None or [K, H, W] int32 (needs `scale`), view_look = None or [K] int32, all contiguous; only the pixels of owned tiles are written.
+        Returns out, or (out, pixels) when pixels is given."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        k = cams.shape[0] if isinstance(cams, torch.Tensor) and cams.dim() == 2 else -1
+        n, w = (looks.shape[0], looks.shape[1]) if isinstance(looks, torch.Tensor) and looks.dim() == 2 else (-1, -1)
+        for t, dt, shape, name in ((cams, torch.float32, (k, 12), "cams"), (looks, torch.int32, (n, w), "looks"), (out, torch.float32, (k, self.H, self.W, 4), "out"),
+                                   (pixels, torch.int32, (k, self.H, self.W), "pixels"), (view_look, torch.int32, (k,), "view_look")):
+            if t is None and name in ("pixels", "view_look"):
+                continue
+            if not isinstance(t, torch.Tensor) or t.device != dev or t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
+                raise ValueError("render_looks_device: %s must be a contiguous %s tensor of shape %s on cuda:%d" % (name, dt, shape, self.device))
+        if pixels is not None and scale is None:
+            raise ValueError("render_looks_device: pixels need a scale")
+
+        def run(st):
+            self._ck(self.L.crt_render_looks_device(self.h, C.c_void_p(cams.data_ptr()), C.c_uint32(k), C.c_void_p(looks.data_ptr()), C.c_uint32(n),
+                                                    C.c_void_p(view_look.data_ptr()) if view_look is not None else None, C.c_uint32(spp_first), C.c_uint32(frames),
+                                                    C.c_uint32(passes), C.c_float(1.0 if scale is None else scale), C.c_void_p(out.data_ptr()),
                                                     C.c_void_p(pixels.data_ptr()) if pixels is not None else None, C.c_void_p(st.cuda_stream)))
             return out if pixels is None else (out, pixels)
         return self._enqueue(stream, run)
@@ -1157,6 +1250,22 @@ class HostScene:
         """BLASBVH::SetTransform(T) of instance i (T = 4x4 row-major, rigid) + TLASBVH::Build on the host; update(ctx, UPDATE_TRANSFORMS) moves it to the device"""
         T = np.ascontiguousarray(T, np.float32).reshape(16)
         self._ck(self.L.crt_host_scene_set_transform(self.h, int(i), _p(T)))
+
+    def look(self):
+        """the scene's look as one record of look_records ([crt_look_words(materialCount)] uint32): the file's, or the last set_look's"""
+        n = C.c_uint32()
+        self._ck(self.L.crt_host_scene_look(self.h, None, C.byref(n)))
+        rec = np.zeros(n.value, np.uint32)
+        self._ck(self.L.crt_host_scene_look(self.h, _p(rec), C.byref(n)))
+        return rec
+
+    def set_look(self, look):
+        """takes a look over (light quad, floor / skydome texture index, materials) so that the next upload describes the scene with it; the device is not touched
+        (Context.update_look changes a live scene's look in place)"""
+        rec = np.ascontiguousarray(look, np.uint32).reshape(-1)
+        if rec.shape[0] != self.look().shape[0]:
+            raise ValueError("set_look: the record has %d words, the scene's look %d" % (rec.shape[0], self.look().shape[0]))
+        self._ck(self.L.crt_host_scene_set_look(self.h, _p(rec)))
 
     def update(self, ctx, what):
         """in-place device update (crt_update_scene): UPDATE_TRANSFORMS after set_transform, UPDATE_BOUNDS after move_and_refit; no re-upload"""

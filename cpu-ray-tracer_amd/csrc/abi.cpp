@@ -108,7 +108,9 @@ struct crt_ctx {
     struct Flat { int32_t kind = 0; uint64_t leafOff = 0, tlasOff = 0, tlasPairOff = 0, instOff = 0, shadeOff = 0; uint32_t tlasNodeCount = 0, maxHeight = 0;
                   uint32_t objects = 0;           // objCount (FileScene) / bvhCount (two-level): the objIdx a hit record may carry is below 2 + objects
                   std::vector<uint64_t> pairBase, triBase; std::vector<uint32_t> nodesUsed, triCount, height; std::vector<char> geom;   // height: every BVH's deepest leaf, in edges
-                  std::vector<float> rootBox; } flat;     // rootBox: every BVH's node 0 box (min xyz, max xyz), what crt_upload_blas_accel checks the BLAS structures against
+                  std::vector<float> rootBox;
+                  uint32_t materialCount = 0; std::vector<crt::TexDesc> tex; } flat;   // crt_update_look / crt_render_looks: the scene's material count, its texture table (dTex: the device's copy)
+    const crt::TexDesc* dTex = nullptr;     // rootBox: every BVH's node 0 box (min xyz, max xyz), what crt_upload_blas_accel checks the BLAS structures against
     char* hStage[2] = {nullptr, nullptr}; size_t stageBytes[2] = {0, 0}; hipEvent_t stageCopied[2] = {nullptr, nullptr}; int stageFlip = 0;
     hipEvent_t sceneReady = nullptr, writeFence = nullptr;   // the scene-write protocol (begin_scene_write): the last write's `done` event, the protocol's own fence
     bool havePrim = false; crt::PrimDev prim{}; uint32_t* dPrimTex = nullptr;       // crt_upload_primitive_scene: PrimitiveScene instead of a triangle scene
@@ -286,7 +288,7 @@ struct crt_ctx {
     void freeScene()
     {
         for (void* p : sceneAllocs) (void)hipFree(p);
-        sceneAllocs.clear(); haveScene = false; dRootBox = nullptr;
+        sceneAllocs.clear(); haveScene = false; dRootBox = nullptr; dTex = nullptr;
         for (void* p : refitAllocs) (void)hipFree(p);
         refitAllocs.clear(); refitPlans.clear();
         if (dPrimTex) { (void)hipFree(dPrimTex); dPrimTex = nullptr; }
@@ -519,6 +521,26 @@ void crt_destroy(crt_ctx* c)
     delete c;
 }
 
+// The light block of a Scene from a description's (or a look's) lightT / lightInvT / lightSize: the one writer, for crt_upload_scene and crt_update_look, so the two
+// cannot differ by a bit.
+static void set_light_block(crt::Scene& s, const float* lightT, const float* lightInvT, float lightSize)
+{
+    memcpy(s.lightInvT, lightInvT, 48);
+    s.lightNrm[0] = -lightT[1]; s.lightNrm[1] = -lightT[5]; s.lightNrm[2] = -lightT[9];   // Quad::GetNormal, primitives.h:363-367
+    s.lightSize = lightSize;
+    {   // GetLightPos (file_scene.cpp:156-162): middle of the quad's two corners, 0.01 below; scalar TransformPosition order
+        const float* m = lightT;
+        const float ax = -0.5f, ay = 0.0f, az = -0.5f, bx = 0.5f, by = 0.0f, bz = 0.5f;
+        const float c1[3] = {m[0] * ax + m[1] * ay + m[2] * az + m[3] * 1.0f, m[4] * ax + m[5] * ay + m[6] * az + m[7] * 1.0f, m[8] * ax + m[9] * ay + m[10] * az + m[11] * 1.0f};
+        const float c2[3] = {m[0] * bx + m[1] * by + m[2] * bz + m[3] * 1.0f, m[4] * bx + m[5] * by + m[6] * bz + m[7] * 1.0f, m[8] * bx + m[9] * by + m[10] * bz + m[11] * 1.0f};
+        s.lightPos[0] = (c1[0] + c2[0]) * 0.5f - 0.0f; s.lightPos[1] = (c1[1] + c2[1]) * 0.5f - 0.01f; s.lightPos[2] = (c1[2] + c2[2]) * 0.5f - 0.0f;
+    }
+    // what FileScene / TLASFileScene always build: a translated, unrotated quad
+    const float* m = lightInvT;
+    s.lightAxis = (m[0] == 1.0f && m[1] == 0.0f && m[2] == 0.0f && m[4] == 0.0f && m[5] == 1.0f && m[6] == 0.0f && m[8] == 0.0f && m[9] == 0.0f && m[10] == 1.0f) ? 1u : 0u;
+    if (hook("CRT_DEBUG_GENERAL_PRIMS")) s.lightAxis = 0u;                        // tests: the general quad expressions on the standard scenes
+}
+
 int crt_upload_scene(crt_ctx* c, const crt_scene_desc* sd)
 {
     if (!c || !sd) return CRT_ERR_INVALID;
@@ -716,22 +738,11 @@ int crt_upload_scene(crt_ctx* c, const crt_scene_desc* sd)
 
     crt::Scene& s = c->hScene;
     s.kind = sd->kind;
-    memcpy(s.lightInvT, sd->lightInvT, 48);
-    s.lightNrm[0] = -sd->lightT[1]; s.lightNrm[1] = -sd->lightT[5]; s.lightNrm[2] = -sd->lightT[9];   // Quad::GetNormal, primitives.h:363-367
-    s.lightSize = sd->lightSize;
-    {   // GetLightPos (file_scene.cpp:156-162): middle of the quad's two corners, 0.01 below; scalar TransformPosition order
-        const float* m = sd->lightT;
-        const float ax = -0.5f, ay = 0.0f, az = -0.5f, bx = 0.5f, by = 0.0f, bz = 0.5f;
-        const float c1[3] = {m[0] * ax + m[1] * ay + m[2] * az + m[3] * 1.0f, m[4] * ax + m[5] * ay + m[6] * az + m[7] * 1.0f, m[8] * ax + m[9] * ay + m[10] * az + m[11] * 1.0f};
-        const float c2[3] = {m[0] * bx + m[1] * by + m[2] * bz + m[3] * 1.0f, m[4] * bx + m[5] * by + m[6] * bz + m[7] * 1.0f, m[8] * bx + m[9] * by + m[10] * bz + m[11] * 1.0f};
-        s.lightPos[0] = (c1[0] + c2[0]) * 0.5f - 0.0f; s.lightPos[1] = (c1[1] + c2[1]) * 0.5f - 0.01f; s.lightPos[2] = (c1[2] + c2[2]) * 0.5f - 0.0f;
-    }
+    set_light_block(s, sd->lightT, sd->lightInvT, sd->lightSize);
     memcpy(s.floorN, sd->floorN, 12); s.floorD = sd->floorD; s.floorInvto = sd->floorInvto;
-    {   // what FileScene / TLASFileScene always build: a translated, unrotated quad and the y-up floor plane
-        const float* m = sd->lightInvT;
-        s.lightAxis = (m[0] == 1.0f && m[1] == 0.0f && m[2] == 0.0f && m[4] == 0.0f && m[5] == 1.0f && m[6] == 0.0f && m[8] == 0.0f && m[9] == 0.0f && m[10] == 1.0f) ? 1u : 0u;
+    {   // what FileScene / TLASFileScene always build: the y-up floor plane
         s.floorAxisY = (sd->floorN[0] == 0.0f && sd->floorN[1] == 1.0f && sd->floorN[2] == 0.0f) ? 1u : 0u;
-        if (hook("CRT_DEBUG_GENERAL_PRIMS")) s.lightAxis = s.floorAxisY = 0u;     // tests: the general quad / plane expressions on the standard scenes
+        if (hook("CRT_DEBUG_GENERAL_PRIMS")) s.floorAxisY = 0u;                   // tests: the general quad / plane expressions on the standard scenes (the light's: set_light_block)
     }
     s.floorMat = mats[1];
     s.skyOffset = texOff[sd->skyTexture]; s.skyW = sd->textures[sd->skyTexture].width; s.skyH = sd->textures[sd->skyTexture].height;
@@ -745,6 +756,9 @@ int crt_upload_scene(crt_ctx* c, const crt_scene_desc* sd)
     s.rootRef16 = (sd->kind == CRT_SCENE_TLAS) ? tlasRoot16 : rootRef0_16;
     s.poolRefBits = poolRefBits;
     if ((r = upload(c, mats, &s.mats))) return r;
+    std::vector<crt::TexDesc> texTable(sd->textureCount);                     // what a texture index becomes in a Material: crt_update_look, crt_render_looks' build launch
+    for (uint32_t i = 0; i < sd->textureCount; i++) texTable[i] = crt::TexDesc{texOff[i], sd->textures[i].width, sd->textures[i].height, 0u};
+    if ((r = upload(c, texTable, &c->dTex))) return r;
     if (sd->kind == CRT_SCENE_TLAS) {                                     // every BLAS's node-0 box, where crt_update_transforms_device takes SetTransform's corners from
         std::vector<float> boxes;
         for (uint32_t bi = 0; bi < sd->bvhCount; bi++) { const crt_bvh_node& n0 = sd->bvhs[bi].nodes[0]; boxes.insert(boxes.end(), n0.aabbMin, n0.aabbMin + 3); boxes.insert(boxes.end(), n0.aabbMax, n0.aabbMax + 3); }
@@ -793,6 +807,7 @@ int crt_upload_scene(crt_ctx* c, const crt_scene_desc* sd)
         uint64_t pb = 0, tb = 0;
         for (uint32_t bi = 0; bi < sd->bvhCount; bi++) { f.pairBase.push_back(pb); f.triBase.push_back(tb); f.nodesUsed.push_back(sd->bvhs[bi].nodesUsed); f.triCount.push_back(sd->bvhs[bi].triCount); pb += sd->bvhs[bi].nodesUsed / 2; tb += sd->bvhs[bi].triCount; }
         f.geom.swap(geom); f.height.swap(heights);
+        f.materialCount = sd->materialCount; f.tex.swap(texTable);
     }
     c->haveScene = true;
     return CRT_OK;
@@ -1048,6 +1063,70 @@ int crt_update_scene(crt_ctx* c, const crt_scene_desc* sd, uint32_t what)
     { const int r = end_scene_write(c, c->stream, c->stageCopied[k]); if (r) return r; }
     if (f.kind == CRT_SCENE_TLAS) adopt_tlas(c, tlasHeight, sd->tlasNodes[0].aabbMin, sd->tlasNodes[0].aabbMax);
     else set_root(c, f.kind, sd->bvhs[0].nodes[0].aabbMin, sd->bvhs[0].nodes[0].aabbMax);
+    return CRT_OK;
+}
+
+uint32_t crt_look_words(uint32_t materialCount) { return CRT_LOOK_HEADER_WORDS + CRT_LOOK_MATERIAL_WORDS * materialCount; }
+
+// a look's texture indices against the uploaded texture table (crt_update_look; crt_render_looks' host entry, which names the look): 0, or the refusal
+static int check_look(crt_ctx* c, const uint32_t* look, const char* what, const char* where)
+{
+    const crt_ctx::Flat& f = c->flat;
+    const crt_look_header* h = reinterpret_cast<const crt_look_header*>(look);
+    const int32_t n = (int32_t)f.tex.size();
+    if (h->floorTexture < 0 || h->floorTexture >= n) return c->fail(CRT_ERR_INVALID, "%s: %sfloorTexture %d lies outside [0, %d)", what, where, h->floorTexture, n);
+    if (h->skyTexture < 0 || h->skyTexture >= n) return c->fail(CRT_ERR_INVALID, "%s: %sskyTexture %d lies outside [0, %d)", what, where, h->skyTexture, n);
+    const crt_material* m = reinterpret_cast<const crt_material*>(look + CRT_LOOK_HEADER_WORDS);
+    for (uint32_t i = 0; i < f.materialCount; i++)
+        if (m[i].texture < -1 || m[i].texture >= n) return c->fail(CRT_ERR_INVALID, "%s: %smaterial %u: texture %d lies outside [-1, %d)", what, where, i, m[i].texture, n);
+    return 0;
+}
+
+int crt_update_look(crt_ctx* c, const void* look)
+{
+    if (!c) return CRT_ERR_INVALID;
+    if (c->havePrim) return c->fail(CRT_ERR_UNSUPPORTED, "crt_update_look: the PrimitiveScene's materials are part of its code (primitive_scene.cpp); it has no look");
+    if (!c->haveScene) return c->fail(CRT_ERR_STATE, "crt_update_look before crt_upload_scene");
+    if (!look) return c->fail(CRT_ERR_INVALID, "crt_update_look: NULL look");
+    const crt_ctx::Flat& f = c->flat;
+    const uint32_t* words = static_cast<const uint32_t*>(look);
+    { const int r = check_look(c, words, "crt_update_look", ""); if (r) return r; }
+    HIPCK(c, hipSetDevice(c->cfg.device));
+    const crt_look_header* h = reinterpret_cast<const crt_look_header*>(words);
+    const crt_material* lm = reinterpret_cast<const crt_material*>(words + CRT_LOOK_HEADER_WORDS);
+    // ---- the Material table as crt_upload_scene writes it ([0] light, [1] floor, then the scene's), into a pinned staging buffer (crt_update_scene's pair) ----
+    const size_t bytes = (size_t)(2u + f.materialCount) * sizeof(crt::Material);
+    const int k = c->stageFlip ^= 1;
+    if (c->stageBytes[k] < bytes) {
+        if (c->hStage[k]) { HIPCK(c, hipEventSynchronize(c->stageCopied[k])); HIPCK(c, hipHostFree(c->hStage[k])); c->hStage[k] = nullptr; c->stageBytes[k] = 0; }
+        HIPCK(c, hipHostMalloc((void**)&c->hStage[k], bytes, hipHostMallocDefault)); c->stageBytes[k] = bytes;
+        HIPCK(c, ensure_event(&c->stageCopied[k]));
+    } else HIPCK(c, hipEventSynchronize(c->stageCopied[k]));
+    crt::Material* mats = reinterpret_cast<crt::Material*>(c->hStage[k]);
+    memset(mats, 0, bytes);
+    auto bindTex = [&](crt::Material& m, int t) {
+        if (t < 0) { m.texOffset = 0; m.texW = 0; m.texH = 0; }
+        else { m.texOffset = f.tex[(size_t)t].offset; m.texW = f.tex[(size_t)t].w; m.texH = f.tex[(size_t)t].h; }
+    };
+    bindTex(mats[0], -1);
+    bindTex(mats[1], h->floorTexture);
+    for (uint32_t i = 0; i < f.materialCount; i++) {
+        crt::Material& m = mats[2 + i];
+        m.reflectivity = lm[i].reflectivity; m.refractivity = lm[i].refractivity;
+        memcpy(m.absorption, lm[i].absorption, 12);
+        bindTex(m, lm[i].texture);
+    }
+    // ---- apply: the records in place under the scene-write protocol; the Scene block travels by value with every later launch ----
+    { const int r = begin_scene_write(c, c->stream); if (r) return r; }
+    HIPCK(c, hipMemcpyAsync(const_cast<crt::Material*>(c->hScene.mats), mats, bytes, hipMemcpyHostToDevice, c->stream));
+    { const int r = end_scene_write(c, c->stream, c->stageCopied[k]); if (r) return r; }
+    crt::Scene& s = c->hScene;
+    set_light_block(s, h->lightT, h->lightInvT, h->lightSize);
+    s.floorMat = mats[1];
+    const crt::TexDesc& sky = f.tex[(size_t)h->skyTexture];
+    s.skyOffset = sky.offset; s.skyW = sky.w; s.skyH = sky.h;
+    primary_changed(c);                                                   // new light block: the camera-relative block and the tile classes follow
+    c->orderDirty = true;                                                 // ... and what a camera change invalidates: the dispatch order, the probe and the job costs behind it
     return CRT_OK;
 }
 
@@ -3653,8 +3732,9 @@ static int views_scratch(crt_ctx* c, uint32_t totalWindows, size_t windowBytes, 
 // (poses: crt_render_poses' job — the launches read every lane's TLAS and Instance records from its view's pose in that table, with jobScene's stack depth)
 // (shapes: crt_render_shapes' job — ... every lane's refitted BVH, and a two-level scene's TLAS and Instance records, from its view's shape in that table)
 // (sets: crt_render_shape_sets' job — ... the refitted BVHs of the set, the TLAS and the Instance records, from its view's shape in that table)
+// (looks: crt_render_looks' job — the launches read every lane's light quad, floor material, sky and Material records from its view's look in that table)
 static int views_run(crt_ctx* c, const float* dCams, uint32_t K, uint32_t sppFirst, uint32_t frames, uint32_t passes, float scale, float* dRgba, uint32_t* dPixels, hipStream_t st,
-                     const crt::Scene* jobScene = nullptr, const crt::PoseTableDev* poses = nullptr, const crt::ShapeTableDev* shapes = nullptr, const crt::ShapeSetTableDev* sets = nullptr)
+                     const crt::Scene* jobScene = nullptr, const crt::PoseTableDev* poses = nullptr, const crt::ShapeTableDev* shapes = nullptr, const crt::ShapeSetTableDev* sets = nullptr, const crt::LookTableDev* looks = nullptr)
 {
     if (c->tileCount == 0) return 0;
     const uint32_t total = K * frames, totalWindows = (total + 63u) / 64u;
@@ -3666,7 +3746,8 @@ static int views_run(crt_ctx* c, const float* dCams, uint32_t K, uint32_t sppFir
     if (c->renderAccel != 0 && c->altReady) HIPCK(c, hipStreamWaitEvent(st, c->altReady, 0));   // the accelerators' copies ran on the null stream
     for (uint32_t j0 = 0; j0 < total; j0 += wl * 64u) {
         const uint32_t nj = (total - j0 < wl * 64u) ? total - j0 : wl * 64u;
-        if (sets) HIPCK(c, crt_launch_render_shape_sets(jobScene, sets, dCams, c->dViewsSlab, c->dCounters, c->tileFirst, c->tileStride, c->tileCount, (uint32_t)c->tilesX, sppFirst, frames, passes, j0, nj, st));
+        if (looks) HIPCK(c, crt_launch_render_looks(jobScene, looks, dCams, c->dViewsSlab, c->dCounters, c->tileFirst, c->tileStride, c->tileCount, (uint32_t)c->tilesX, sppFirst, frames, passes, j0, nj, st));
+        else if (sets) HIPCK(c, crt_launch_render_shape_sets(jobScene, sets, dCams, c->dViewsSlab, c->dCounters, c->tileFirst, c->tileStride, c->tileCount, (uint32_t)c->tilesX, sppFirst, frames, passes, j0, nj, st));
         else if (shapes) HIPCK(c, crt_launch_render_shapes(jobScene, shapes, dCams, c->dViewsSlab, c->dCounters, c->tileFirst, c->tileStride, c->tileCount, (uint32_t)c->tilesX, sppFirst, frames, passes, j0, nj, st));
         else if (poses) HIPCK(c, crt_launch_render_poses(jobScene, poses, dCams, c->dViewsSlab, c->dCounters, c->tileFirst, c->tileStride, c->tileCount, (uint32_t)c->tilesX, sppFirst, frames, passes, j0, nj, st));
         else if (c->havePrim) HIPCK(c, crt_launch_render_views_prim(&c->hScene, &c->prim, dCams, c->dViewsSlab, c->dCounters, c->tileFirst, c->tileStride, c->tileCount, (uint32_t)c->tilesX, sppFirst, frames, passes, j0, nj, st));
@@ -3887,6 +3968,112 @@ int crt_render_poses(crt_ctx* c, const float* cams, uint32_t K, const float* T, 
     HIPCK(c, hipMemcpyAsync(dT, T, tBytes, hipMemcpyHostToDevice, c->stream));
     if (dViewPose) HIPCK(c, hipMemcpyAsync(dViewPose, view_pose, (size_t)K * 4, hipMemcpyHostToDevice, c->stream));
     if ((r = poses_run(c, dCams, K, dT, P, dViewPose, spp_first, frames, passes, scale, S.dRgba, S.dPix, tlas_out, c->stream, what))) return r;
+    return views_stage_out(c, K, out_rgba, out_pixels, S);
+}
+
+// ---- crt_render_looks / crt_render_looks_device: the frames of K cameras over L job-local looks of the live scene (device/look_build.hip, render_looks.h) ----
+// where a job's look table keeps what (device/layout.h LookJobHeader, LookDev)
+struct LookLayout {
+    size_t tableBytes; uint32_t looksOff, lookStride, recordWords;
+    LookLayout(const crt_ctx::Flat& f, uint32_t L)
+    {
+        recordWords = crt_look_words(f.materialCount);
+        lookStride = (uint32_t)((sizeof(crt::LookDev) + (size_t)(2u + f.materialCount) * sizeof(crt::Material) + 127u) & ~(size_t)127u);
+        looksOff = 128u;                                                    // behind the LookJobHeader
+        tableBytes = looksOff + (size_t)L * lookStride;
+    }
+};
+
+// the checks that need no buffer, in the order crt_abi.h lists the refusals
+static int looks_check(crt_ctx* c, uint32_t K, uint32_t L, bool viewLook, uint32_t frames, uint32_t passes, const char* what)
+{
+    if (!c->haveScene && !c->havePrim) return c->fail(CRT_ERR_STATE, "%s before crt_upload_scene", what);
+    if (c->havePrim) return c->fail(CRT_ERR_UNSUPPORTED, "%s: the PrimitiveScene's materials are part of its code; it has no look", what);
+    if (passes < 1 || passes > 4) return c->fail(CRT_ERR_INVALID, "%s: passes must be 1..4 (the reference's UI range, renderer.cpp:178)", what);
+    if ((uint64_t)K * frames > 0x7fffffffull) return c->fail(CRT_ERR_UNSUPPORTED, "%s: at most 2^31-1 view-frames per call (%u views x %u frames)", what, K, frames);
+    if (c->renderAccel != 0) return c->fail(CRT_ERR_UNSUPPORTED, "%s: looks through the KD-tree / grid are not supported (crt_set_render_accel(0) first)", what);
+    if (K > 0 && L == 0) return c->fail(CRT_ERR_INVALID, "%s: %u views and no look", what, K);
+    if (!viewLook && L != K) return c->fail(CRT_ERR_INVALID, "%s: without view_look view k renders look k, so L (%u) must equal K (%u)", what, L, K);
+    const LookLayout Y(c->flat, L);
+    if (Y.tableBytes > crt::kMaxGeomBytes || (uint64_t)L * Y.recordWords > 0x3fffffffull)
+        return c->fail(CRT_ERR_UNSUPPORTED, "%s: %u looks of %u bytes each exceed the 4 GiB the kernel's 32-bit offsets address; split the job", what, L, Y.lookStride);
+    if (!sample_lds_fits(c->hScene.stackDepth)) return c->fail(CRT_ERR_UNSUPPORTED, "%s: a traversal stack of %u dwords per lane exceeds the kernel's LDS", what, c->hScene.stackDepth);
+    return 0;
+}
+
+// The job on `st`, after the checks that need no launch: the build launch, the read-back of its status header (THE host wait), the checks of what came back, then
+// crt_render_views' launches over the table.  dViewLook may be nullptr (view k renders look k).
+static int looks_run(crt_ctx* c, const float* dCams, uint32_t K, const void* dLooks, uint32_t L, const int32_t* dViewLook, uint32_t sppFirst, uint32_t frames, uint32_t passes, float scale,
+                     float* dRgba, uint32_t* dPixels, hipStream_t st, const char* what)
+{
+    const crt_ctx::Flat& f = c->flat;
+    const LookLayout Y(f, L);
+    int r;
+    if ((r = wait_scene(c, st))) return r;
+    if ((r = job_table(c, Y.tableBytes, sizeof(crt::LookJobHeader), st))) return r;
+    HIPCK(c, hipMemsetAsync(c->dPoseTable, 0xff, sizeof(crt::LookJobHeader), st));     // badView = kPoseNoBadView, badField = kLookNoBadField
+    const crt::LookBuildDev b{static_cast<const uint32_t*>(dLooks), L, f.materialCount, c->dTex, (uint32_t)f.tex.size(), c->dPoseTable, Y.looksOff, Y.lookStride, dViewLook, K};
+    HIPCK(c, crt_launch_look_build(&b, st));
+    // the one host wait: a job with a texture index or a view_look entry out of range does not run
+    if ((r = read_back(c, st, c->poseBack, c->hPoseBack, c->dPoseTable, sizeof(crt::LookJobHeader)))) return r;
+    const crt::LookJobHeader& job = *reinterpret_cast<const crt::LookJobHeader*>(c->hPoseBack);
+    if (job.badField != crt::kLookNoBadField) {
+        const uint32_t look = (uint32_t)(job.badField >> 32), field = (uint32_t)job.badField;
+        if (field == crt::kLookFieldFloor) return c->fail(CRT_ERR_INVALID, "%s: look %u: floorTexture lies outside [0, %zu)", what, look, f.tex.size());
+        if (field == crt::kLookFieldSky) return c->fail(CRT_ERR_INVALID, "%s: look %u: skyTexture lies outside [0, %zu)", what, look, f.tex.size());
+        return c->fail(CRT_ERR_INVALID, "%s: look %u: material %u: texture lies outside [-1, %zu)", what, look, field - crt::kLookFieldMaterial, f.tex.size());
+    }
+    if (job.badView != crt::kPoseNoBadView) return c->fail(CRT_ERR_INVALID, "%s: view_look[%u] lies outside [0, %u)", what, job.badView, L);
+    const crt::LookTableDev lt{c->dPoseTable, dViewLook, Y.looksOff, Y.lookStride};
+    return views_run(c, dCams, K, sppFirst, frames, passes, scale, dRgba, dPixels, st, &c->hScene, nullptr, nullptr, nullptr, &lt);
+}
+
+int crt_render_looks_device(crt_ctx* c, const float* d_cams, uint32_t K, const void* d_looks, uint32_t L, const int32_t* d_view_look, uint32_t spp_first, uint32_t frames, uint32_t passes,
+                            float scale, float* d_out_rgba, uint32_t* d_out_pixels, void* stream)
+{
+    if (!c) return CRT_ERR_INVALID;
+    const char* what = "crt_render_looks_device";
+    int r;
+    if ((r = looks_check(c, K, L, d_view_look != nullptr, frames, passes, what))) return r;
+    if (K == 0 || frames == 0) return CRT_OK;
+    const size_t px = (size_t)c->cfg.width * c->cfg.height;
+    if (reinterpret_cast<uintptr_t>(d_out_rgba) & 15u) return c->fail(CRT_ERR_INVALID, "%s: d_out_rgba %p is not 16-byte aligned", what, (void*)d_out_rgba);
+    hipStream_t st = nullptr; int k = 0;
+    if ((r = device_entry(c, what, {{d_cams, (size_t)K * 48}, {d_looks, (size_t)L * LookLayout(c->flat, L).recordWords * 4}, {d_out_rgba, K * px * 16}}, stream, &st))) return r;
+    if (d_out_pixels && (r = check_device_buffer(c, d_out_pixels, K * px * 4, what))) return r;
+    if (d_view_look && (r = check_device_buffer(c, d_view_look, (size_t)K * 4, what))) return r;
+    if ((r = take_query_slot(c, &k))) return r;
+    if ((r = looks_run(c, d_cams, K, d_looks, L, d_view_look, spp_first, frames, passes, scale, d_out_rgba, d_out_pixels, st, what))) return r;
+    return end_device_query(c, k, st);
+}
+
+int crt_render_looks(crt_ctx* c, const float* cams, uint32_t K, const void* looks, uint32_t L, const int32_t* view_look, uint32_t spp_first, uint32_t frames, uint32_t passes, float scale,
+                     float* out_rgba, uint32_t* out_pixels)
+{
+    if (!c) return CRT_ERR_INVALID;
+    const char* what = "crt_render_looks";
+    int r;
+    if ((r = looks_check(c, K, L, view_look != nullptr, frames, passes, what))) return r;
+    if (K == 0 || frames == 0) return CRT_OK;
+    if (!cams || !looks || !out_rgba) return c->fail(CRT_ERR_INVALID, "%s: NULL buffer", what);
+    const LookLayout Y(c->flat, L);
+    for (uint32_t l = 0; l < L; l++) {                                      // the build launch's checks, on the host first: nothing is staged for a job that will not run
+        char where[32]; snprintf(where, sizeof(where), "look %u: ", l);
+        if ((r = check_look(c, static_cast<const uint32_t*>(looks) + (size_t)l * Y.recordWords, what, where))) return r;
+    }
+    if (view_look)
+        for (uint32_t k = 0; k < K; k++)
+            if (view_look[k] < 0 || (uint32_t)view_look[k] >= L) return c->fail(CRT_ERR_INVALID, "%s: view_look[%u] = %d lies outside [0, %u)", what, k, view_look[k], L);
+    HIPCK(c, hipSetDevice(c->cfg.device));
+    const size_t camBytes = (size_t)K * 48, lookBytes = (size_t)L * Y.recordWords * 4;
+    ViewsStage S;
+    if ((r = views_stage_in(c, K, out_rgba, out_pixels, camBytes + lookBytes + (view_look ? (size_t)K * 4 : 0), &S))) return r;
+    float* dCams = reinterpret_cast<float*>(S.extra); void* dLooks = S.extra + camBytes;
+    int32_t* dViewLook = view_look ? reinterpret_cast<int32_t*>(S.extra + camBytes + lookBytes) : nullptr;
+    HIPCK(c, hipMemcpyAsync(dCams, cams, camBytes, hipMemcpyHostToDevice, c->stream));
+    HIPCK(c, hipMemcpyAsync(dLooks, looks, lookBytes, hipMemcpyHostToDevice, c->stream));
+    if (dViewLook) HIPCK(c, hipMemcpyAsync(dViewLook, view_look, (size_t)K * 4, hipMemcpyHostToDevice, c->stream));
+    if ((r = looks_run(c, dCams, K, dLooks, L, dViewLook, spp_first, frames, passes, scale, S.dRgba, S.dPix, c->stream, what))) return r;
     return views_stage_out(c, K, out_rgba, out_pixels, S);
 }
 

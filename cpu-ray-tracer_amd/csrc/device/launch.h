@@ -81,6 +81,12 @@ hipError_t crt_launch_render_shapes(const crt::Scene* sc, const crt::ShapeTableD
 // crt_render_shape_sets (render_shape_sets.h): the same with the instances that walk the lane's image named by the table's instRoot words; two-level scenes only
 hipError_t crt_launch_render_shape_sets(const crt::Scene* sc, const crt::ShapeSetTableDev* t, const float* cams, void* slab, crt::Counters* counters, uint32_t tileFirst, uint32_t tileStride,
     uint32_t tileCount, uint32_t tilesX, uint32_t sppFirst, uint32_t frames, uint32_t passes, uint32_t jFirst, uint32_t nj, hipStream_t stream);
+// crt_render_looks (render_looks.h, render_looks.hip): the same launch with every lane's light quad, floor material, sky and Material records taken from its view's look
+// in the table `lt` names (look_build.hip: the build of that table from the job's look records, and the check of the K view -> look indices; the caller sets the
+// table's LookJobHeader to all ones on the stream first).  BVH / TLAS only.
+hipError_t crt_launch_look_build(const crt::LookBuildDev* b, hipStream_t stream);
+hipError_t crt_launch_render_looks(const crt::Scene* sc, const crt::LookTableDev* lt, const float* cams, void* slab, crt::Counters* counters, uint32_t tileFirst, uint32_t tileStride,
+    uint32_t tileCount, uint32_t tilesX, uint32_t sppFirst, uint32_t frames, uint32_t passes, uint32_t jFirst, uint32_t nj, hipStream_t stream);
 hipError_t crt_launch_views_accumulate(const void* slab, float* outRgba, uint32_t* outPixels, uint32_t tileFirst, uint32_t tileStride, uint32_t tileCount, uint32_t tilesX, uint32_t W,
     uint32_t H, uint32_t frames, uint32_t passes, uint32_t jFirst, uint32_t nj, float scale, hipStream_t stream);
 

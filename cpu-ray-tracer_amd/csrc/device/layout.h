@@ -236,6 +236,39 @@ struct ShapeSetTableDev {
     uint32_t instRootOff;                         // instRoot[blasCount] in the table
     uint32_t poseRel, instRel;                    // the pose image inside an image; the Instance records inside that
 };
+// The uploaded texture table as the device keeps it (one record per crt_texture, written at upload and never after): what a texture index becomes in a Material
+// record or in the sky words.  look_build.hip binds a look's indices through it.
+struct alignas(16) TexDesc { uint32_t offset; int32_t w, h; uint32_t pad; };
+// crt_render_looks' look table (look_build.hip writes it, render_looks.h reads it): this header, then — at looksOff, lookStride apart, both multiples of 128 — one
+// block per look: a LookDev (the light quad, the floor material, the sky words), then the look's 2 + materialCount Material records in Scene::mats' order ([0] light,
+// [1] floor, 2.. the scene's), so ShadeTri::mat indexes them as it indexes the live table.  The render kernel addresses the table as the pose table is addressed,
+// scalar base + 32-bit byte offset, so the whole table stays within kMaxGeomBytes.
+struct alignas(64) LookJobHeader {
+    uint32_t badView;                     // the lowest view whose view_look entry lies outside [0, L); kPoseNoBadView: none
+    uint32_t pad0;
+    unsigned long long badField;          // look << 32 | field of the lowest (look, field) whose texture index is out of range; kLookNoBadField: none
+    uint32_t pad[12];
+};
+constexpr unsigned long long kLookNoBadField = ~0ull;
+constexpr uint32_t kLookFieldFloor = 0u, kLookFieldSky = 1u, kLookFieldMaterial = 2u;   // field: floorTexture, skyTexture, 2 + i = materials[i].texture
+struct alignas(128) LookDev {             // 128 B
+    float lightInvT[12]; float lightNrm[3]; float lightSize;      // Scene's light block, rows 0..2 of the look's invT
+    Material floorMat;                                            // Scene::floorMat
+    uint32_t skyOffset; int32_t skyW, skyH; uint32_t pad[5];      // Scene's sky words
+};
+constexpr uint32_t kLookHeaderWords = 36u, kLookMaterialWords = 6u;     // crt_abi.h: crt_look_header, crt_material
+// what the build kernel takes by value
+struct LookBuildDev {
+    const uint32_t* looks; uint32_t L, M;                         // L records of kLookHeaderWords + M * kLookMaterialWords words
+    const TexDesc* tex; uint32_t texCount;
+    char* table; uint32_t looksOff, lookStride;
+    const int32_t* viewLook; uint32_t K;                          // viewLook may be nullptr
+};
+// what the render kernel takes by value: where the table is and how a view finds its look in it
+struct LookTableDev {
+    const char* table; const int32_t* viewLook;   // viewLook == nullptr: view k renders look k
+    uint32_t looksOff, lookStride;
+};
 constexpr uint32_t kTlasMaxBlas = 256u;   // tlas_bvh.cpp:21 (nodeIdx[256])
 
 // Whether a crt_hit's indices may be used as addresses by the hit-info query (shade_query.hip): ONE predicate for the host entry, which refuses the call, and for

@@ -42,8 +42,9 @@ __device__ __forceinline__ SurfPoint floor_point(f3 floorN, float floorInvto, co
 // mesh: GetNormal / GetUV (bvh.cpp:290-305, blas_bvh.cpp:391-406) from the hit's ShadeTri (s0..s3); KIND 1: the normal goes through the instance's T.
 // (The T rows are fetched with ldp<>, whose assumption — 64 bytes from the given offset lie inside the geometry buffer — holds for `io`: it is the second
 // 64-byte half of a 128-byte Instance record.)
-template <int KIND>
-__device__ __forceinline__ SurfPoint mesh_point(rec4 s0, rec4 s1, rec4 s2, rec4 s3, float u, float v, int objIdx, const char* __restrict__ geom, uint32_t instOff, const Material* __restrict__ mats)
+// (materialOf(mat, m0, m1): fetches the two halves of the Material record ShadeTri::mat names — from the live table, below, or from a job-local look, render_looks.h)
+template <int KIND, class MaterialOf>
+__device__ __forceinline__ SurfPoint mesh_point_with(rec4 s0, rec4 s1, rec4 s2, rec4 s3, float u, float v, int objIdx, const char* __restrict__ geom, uint32_t instOff, MaterialOf&& materialOf)
 {
     SurfPoint p;
     const f3 n0 = mk3(s0.x, s0.y, s0.z), n1 = mk3(s0.w, s1.x, s1.y), n2 = mk3(s1.z, s1.w, s2.x);
@@ -52,8 +53,9 @@ __device__ __forceinline__ SurfPoint mesh_point(rec4 s0, rec4 s1, rec4 s2, rec4 
     p.tu = w * s2.y + u * s2.w + v * s3.y;
     p.tv = w * s2.z + u * s3.x + v * s3.z;
     p.mat = (int)asu(s3.w);
-    const rec4* mp = reinterpret_cast<const rec4*>(mats + p.mat);
-    set_material(p, mp[0], mp[1]);
+    rec4 m0, m1;
+    materialOf(p.mat, m0, m1);
+    set_material(p, m0, m1);
     if (KIND == 0) p.N = normalize3(Nn);
     else {
         const uint32_t io = instOff + (uint32_t)(objIdx - 2) * 128u + 64u;       // Instance::T rows
@@ -63,6 +65,14 @@ __device__ __forceinline__ SurfPoint mesh_point(rec4 s0, rec4 s1, rec4 s2, rec4 
                              r2.x * Nn.x + r2.y * Nn.y + r2.z * Nn.z + r2.w * 0.0f));
     }
     return p;
+}
+template <int KIND>
+__device__ __forceinline__ SurfPoint mesh_point(rec4 s0, rec4 s1, rec4 s2, rec4 s3, float u, float v, int objIdx, const char* __restrict__ geom, uint32_t instOff, const Material* __restrict__ mats)
+{
+    return mesh_point_with<KIND>(s0, s1, s2, s3, u, v, objIdx, geom, instOff, [&](int mat, rec4& m0, rec4& m1) __attribute__((always_inline)) {
+        const rec4* mp = reinterpret_cast<const rec4*>(mats + mat);
+        m0 = mp[0]; m1 = mp[1];
+    });
 }
 __device__ __forceinline__ f3 face_ray(f3 N, f3 D) { return (dot3(N, D) > 0) ? -N : N; }
 

@@ -364,6 +364,22 @@ int crt_host_scene_set_transform(crt_host_scene* s, int i, const float T[16])
     return CRT_OK;
     GUARD_END(CRT_ERR_INVALID)
 }
+// the scene's look as a crt_update_look record: *words = crt_look_words(materialCount), the record where `look` is non-NULL
+int crt_host_scene_look(crt_host_scene* s, void* look, uint32_t* words)
+{
+    if (!s || !words) { g_err = "null argument"; return CRT_ERR_INVALID; }
+    *words = crt_look_words((uint32_t)s->scene->materials.size());
+    if (look) s->scene->Look(look);
+    return CRT_OK;
+}
+// ... and a look taken over by the host scene, for the next crt_host_scene_upload; the device is not touched (crt_update_look changes a live scene's look)
+int crt_host_scene_set_look(crt_host_scene* s, const void* look)
+{
+    if (!s || !look) { g_err = "null argument"; return CRT_ERR_INVALID; }
+    const int rc = s->scene->SetLook(look);
+    if (rc != CRT_OK) g_err = "crt_host_scene_set_look: a texture index of the look lies outside the scene's textures";
+    return rc;
+}
 int crt_host_scene_update(crt_host_scene* s, crt_ctx* ctx, uint32_t what)
 {
     if (!s || !ctx) { g_err = "null argument"; return CRT_ERR_INVALID; }

@@ -78,9 +78,40 @@ void BaseScene::BuildDesc(crt_scene_desc& d, DescKeep& k)
     k.tex.resize(textures.size());
     for (size_t i = 0; i < textures.size(); i++) { k.tex[i].pixels = textures[i].pixels.data(); k.tex[i].width = textures[i].width; k.tex[i].height = textures[i].height; }
     d.textures = k.tex.data(); d.textureCount = (uint32_t)k.tex.size();
-    d.floorTexture = 0; d.skyTexture = 1;
+    d.floorTexture = floorTexture; d.skyTexture = skyTexture;
     memcpy(d.lightT, lightT.cell, 64); memcpy(d.lightInvT, lightInvT.cell, 64); d.lightSize = lightSize;
     d.floorN[0] = floorN.x; d.floorN[1] = floorN.y; d.floorN[2] = floorN.z; d.floorD = floorD; d.floorInvto = floorInvto;
+}
+
+void BaseScene::Look(void* out) const
+{
+    crt_look_header h; memset(&h, 0, sizeof(h));
+    memcpy(h.lightT, lightT.cell, 64); memcpy(h.lightInvT, lightInvT.cell, 64); h.lightSize = lightSize;
+    h.floorTexture = floorTexture; h.skyTexture = skyTexture;
+    memcpy(out, &h, sizeof(h));
+    crt_material* m = reinterpret_cast<crt_material*>(static_cast<uint32_t*>(out) + CRT_LOOK_HEADER_WORDS);
+    for (size_t i = 0; i < materials.size(); i++) {
+        m[i].reflectivity = materials[i]->reflectivity; m[i].refractivity = materials[i]->refractivity;
+        m[i].absorption[0] = materials[i]->absorption.x; m[i].absorption[1] = materials[i]->absorption.y; m[i].absorption[2] = materials[i]->absorption.z;
+        m[i].texture = materials[i]->texture;
+    }
+}
+
+int BaseScene::SetLook(const void* look)
+{
+    crt_look_header h; memcpy(&h, look, sizeof(h));
+    const crt_material* m = reinterpret_cast<const crt_material*>(static_cast<const uint32_t*>(look) + CRT_LOOK_HEADER_WORDS);
+    const int n = (int)textures.size();
+    if (h.floorTexture < 0 || h.floorTexture >= n || h.skyTexture < 0 || h.skyTexture >= n) return CRT_ERR_INVALID;
+    for (size_t i = 0; i < materials.size(); i++) if (m[i].texture < -1 || m[i].texture >= n) return CRT_ERR_INVALID;
+    memcpy(lightT.cell, h.lightT, 64); memcpy(lightInvT.cell, h.lightInvT, 64); lightSize = h.lightSize;
+    floorTexture = h.floorTexture; skyTexture = h.skyTexture; primitiveMaterials[1].texture = h.floorTexture;
+    for (size_t i = 0; i < materials.size(); i++) {
+        materials[i]->reflectivity = m[i].reflectivity; materials[i]->refractivity = m[i].refractivity;
+        materials[i]->absorption = float3(m[i].absorption[0], m[i].absorption[1], m[i].absorption[2]);
+        materials[i]->texture = m[i].texture;
+    }
+    return CRT_OK;
 }
 
 int BaseScene::Upload(crt_ctx* ctx)

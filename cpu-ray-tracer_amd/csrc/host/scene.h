@@ -47,6 +47,10 @@ public:
     int Upload(crt_ctx* ctx);
     // in-place device update after instance motion (BLASBVH::SetTransform + TLASBVH::Build) / Refit: crt_update_scene with this scene's description
     int Update(crt_ctx* ctx, uint32_t what);
+    // The scene's look as a crt_update_look record (crt_look_words(materialCount) words): Look writes the current one; SetLook takes one over — the light quad, the
+    // floor / skydome texture indices and the materials — so that Upload describes the scene with that look.  Neither touches a device.
+    void Look(void* out) const;
+    int SetLook(const void* look);
     // scene.FindNearest(ray): one ray through crt_find_nearest (use the batch ABI for many)
     void FindNearest(Ray& ray);
     // scene.IsOccluded(ray): one shadow ray {O, D, t} through crt_is_occluded (light quad bounded by t, then the BVH / TLAS over the whole ray)
@@ -66,6 +70,7 @@ public:
     Material primitiveMaterials[2];                          // [0] the light (isLight), [1] the floor (texture 0): file_scene.cpp:10-12
     int objCount = 0, materialCount = 0, objIdUsed = 2;
     mat4 lightT, lightInvT; float lightSize = 0.5f;          // Quad light(0, 1)
+    int floorTexture = 0, skyTexture = 1;                    // indices into textures (file_scene.cpp:10-19 loads them first)
     float3 floorN{0, 1, 0}; float floorD = 1, floorInvto = 1; // Plane floor(1, (0,1,0), 1, texW/100)
     float animTime = 0;
     void SetTime(float t) { animTime = t; }

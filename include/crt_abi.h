@@ -157,6 +157,27 @@ int  crt_upload_scene(crt_ctx* ctx, const crt_scene_desc* scene);
 #define CRT_UPDATE_TRANSFORMS 1u
 #define CRT_UPDATE_BOUNDS     2u
 int  crt_update_scene(crt_ctx* ctx, const crt_scene_desc* scene, uint32_t what);
+/* A LOOK: everything of an uploaded triangle scene's appearance that can change without touching geometry or texels, as one block of 4-byte words (so it can live in
+ * a host array or in a device tensor): a crt_look_header — the light quad and the floor / skydome texture, the crt_scene_desc members of the same names, same meaning
+ * and units, invT supplied by the caller exactly as at upload — followed by materialCount crt_material records (six words each), materialCount being the uploaded
+ * scene's.  A look SELECTS AMONG THE UPLOADED TEXTURES BY INDEX (materials: -1 = untextured); texels are never part of a look.  crt_look_words(materialCount) is the
+ * stride of an array of looks, in words.  ABI version 3 still: additions, detected by symbol. */
+typedef struct crt_look_header { float lightT[16], lightInvT[16], lightSize; int32_t floorTexture, skyTexture; uint32_t pad; } crt_look_header;
+#define CRT_LOOK_HEADER_WORDS   36u
+#define CRT_LOOK_MATERIAL_WORDS 6u
+uint32_t crt_look_words(uint32_t materialCount);               /* CRT_LOOK_HEADER_WORDS + CRT_LOOK_MATERIAL_WORDS * materialCount */
+/* In-place change of the live scene's look (CRT_SCENE_FILE and CRT_SCENE_TLAS): a material sweep, relighting, a moving light, without the re-flatten, re-allocation and
+ * synchronising copy of crt_upload_scene.  Rewrites the device Material records, the floor material, the sky words and the light block (and what derives from it: the
+ * camera-relative block, the tile classes, the dispatch order and the planner / probe state a camera change also invalidates).  Afterwards every entry that shades —
+ * crt_render through either render kernel and through crt_set_render_accel, crt_tick, crt_whitted_tick, crt_sample*, crt_trace*, crt_get_hit_info*,
+ * crt_get_sky_color*, crt_get_light — gives bit for bit what a fresh crt_upload_scene of the same description with that look gives (followed by the same
+ * alternative-accelerator uploads).  The KD-tree / grid structures are kept: they hold no appearance.  Frames crt_tick rendered ahead are dropped.
+ * Ordering, as crt_update_scene: the Material records are rewritten on the context's stream behind every launch submitted earlier that may read them (renders,
+ * frames rendered ahead, queries on any stream), so those still see the old look, and every launch submitted later sees the new one; no device allocation, no host
+ * wait for the GPU beyond what CRT_UPDATE_TRANSFORMS has (a pinned staging buffer's previous copy).
+ * Refused with nothing modified: no scene CRT_ERR_STATE; a PrimitiveScene CRT_ERR_UNSUPPORTED; look NULL, floorTexture / skyTexture outside [0, textureCount), a
+ * material's texture outside [-1, textureCount) CRT_ERR_INVALID (crt_last_error names the field). */
+int  crt_update_look(crt_ctx* ctx, const void* look /* crt_look_words(materialCount) words, host */);
 /* BVH::Refit / BLASBVH::Refit (bvh.cpp:26-61) of ONE uploaded BVH on the device, from vertex positions that already live in device memory (skinning, a cloth step,
  * an optimiser over vertices): no copy of the positions to the host, no CPU refit, no staging of the geometry sections.  ABI version 3 still: an addition,
  * detected by symbol.  d_positions = vertex0, vertex1, vertex2 of every triangle in the reference's triangles[] order (9 floats each; the array
@@ -614,6 +635,37 @@ int  crt_render_poses(crt_ctx* ctx, const float* cams /* K * 12 */, uint32_t K, 
 int  crt_render_poses_device(crt_ctx* ctx, const float* d_cams, uint32_t K, const float* d_T, uint32_t P, uint32_t blasCount, const int32_t* d_view_pose /* or NULL */,
                              uint32_t spp_first, uint32_t frames, uint32_t passes, float scale, float* d_out_rgba, uint32_t* d_out_pixels /* or NULL */,
                              crt_tlas_node* tlas_out /* host, or NULL */, void* stream);                                                      /* device pointers, one host wait */
+
+/* The frames of MANY cameras over MANY LOOKS of the live scene in one render job: a material sweep, a relighting turntable, a moving light, the candidates of a
+ * derivative-free optimiser over material parameters, a training set with randomised appearance.  The loop that changes the look between views — crt_update_look,
+ * crt_set_camera, crt_clear, crt_render, crt_read_accumulator — renders every variant one lane wide.  Here one build launch (device/look_build.hip) turns the L look
+ * records into a job-local table of device Material records and one light / floor-material / sky block per look, and every lane of crt_render_views' launch shades
+ * with the look of its own view (device/render_looks.h).  Geometry, trees and texels are shared.  ABI version 3 still: additions, detected by symbol.
+ * cams: K records of 12 floats, crt_set_camera's arguments.  looks: L records of crt_look_words(materialCount) words each (crt_update_look's argument).  view_look:
+ * K indices into the looks, or NULL: view k renders look k, and L must equal K.
+ * For every view k, with l = view_look[k], and every pixel of a tile this context owns: out_rgba[k] (W * H float4) is bit for bit what crt_update_look(looks[l]);
+ * crt_set_camera(cams[k]); crt_clear; crt_render(spp_first, frames, passes); crt_read_accumulator leaves there, w = 0 included; out_pixels[k] (W * H, may be NULL) is
+ * crt_resolve_screen(scale)'s pixel of that accumulator.  No other pixel of the outputs is touched.
+ * THE LIVE SCENE IS NOT CHANGED: its look, the context's camera, the accumulator, the epoch and crt_tick's rendered-ahead frames stay as they are.  Looks are
+ * job-local: they live in the scratch crt_render_poses keeps its poses in, at most 4 GiB of it (128 + 32 (2 + materialCount) bytes per look, rounded up to 128).
+ * Counters: crt_counters.rays, primary and mesh_hits grow as they would for the K renders.
+ * Ordering: the call is a reader under the scene-write protocol, exactly like crt_render_views_device.  THE ONE HOST WAIT (both entries; besides growing scratch): a
+ * job with a texture index or a view_look entry out of range must not run, so the call reads the build's 64-byte status header back (pinned) and returns from that
+ * wait before it enqueues the render launches.  crt_render_looks_device: d_cams (48 K bytes), d_looks (4 L crt_look_words bytes), d_view_look (4 K, or NULL),
+ * d_out_rgba (16 K W H, 16-byte aligned), d_out_pixels (4 K W H, or NULL) are device pointers on cfg.device, checked as crt_render_views_device checks its buffers;
+ * the records are never read on the host.  crt_render_looks: host pointers, synchronous, through staging the context keeps; it checks the records on the host first.
+ * Refusals (nothing is written, crt_last_error says why): no scene CRT_ERR_STATE; a PrimitiveScene CRT_ERR_UNSUPPORTED; passes outside 1..4 CRT_ERR_INVALID;
+ * K * frames > 2^31-1 CRT_ERR_UNSUPPORTED; crt_set_render_accel != 0 CRT_ERR_UNSUPPORTED (looks through the KD-tree / grid: not built); L == 0 with K > 0, or
+ * view_look NULL with L != K, CRT_ERR_INVALID; a look table beyond 4 GiB CRT_ERR_UNSUPPORTED; NULL, misaligned, host or other-device memory, a stream of another
+ * device CRT_ERR_INVALID; a view_look entry outside [0, L) CRT_ERR_INVALID; a floorTexture / skyTexture outside [0, textureCount) or a material's texture outside
+ * [-1, textureCount) in ANY look, used by a view or not, CRT_ERR_INVALID (crt_last_error names the lowest such look and its first such field); a failed device
+ * allocation CRT_ERR_DEVICE.  K == 0 or frames == 0 is a no-op after the checks that need no buffer. */
+int  crt_render_looks(crt_ctx* ctx, const float* cams /* K * 12 */, uint32_t K, const void* looks /* L * crt_look_words(materialCount) words */, uint32_t L,
+                      const int32_t* view_look /* K, or NULL */, uint32_t spp_first, uint32_t frames, uint32_t passes, float scale,
+                      float* out_rgba /* K * W*H float4 */, uint32_t* out_pixels /* K * W*H or NULL */);                                     /* host pointers, synchronous */
+int  crt_render_looks_device(crt_ctx* ctx, const float* d_cams, uint32_t K, const void* d_looks, uint32_t L, const int32_t* d_view_look /* or NULL */,
+                             uint32_t spp_first, uint32_t frames, uint32_t passes, float scale, float* d_out_rgba, uint32_t* d_out_pixels /* or NULL */,
+                             void* stream);                                                                                                    /* device pointers, one host wait */
 
 /* The frames of MANY cameras over MANY SHAPES of one refitted BVH in one render job: skinning, cloth, the candidates of an optimiser over vertices — callers whose
  * vertex positions already live in device memory.  crt_render_views renders K cameras over the one live scene and crt_render_poses moves a two-level scene's

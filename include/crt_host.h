@@ -57,6 +57,13 @@ int  crt_host_scene_blas_alt_copy(crt_host_scene* scene, int kind, int blas, voi
 int  crt_host_scene_set_transform(crt_host_scene* scene, int bvh, const float T[16]);
 /* ... and the in-place device update for it (what = CRT_UPDATE_TRANSFORMS) or for crt_host_scene_bvh_move_and_refit (what = CRT_UPDATE_BOUNDS): crt_update_scene */
 int  crt_host_scene_update(crt_host_scene* scene, crt_ctx* ctx, uint32_t what);
+/* The scene's look as a crt_update_look / crt_render_looks record (crt_abi.h crt_look_header + materialCount crt_material): *words = crt_look_words(materialCount),
+ * and the record itself where `look` is non-NULL.  Texture indices are the host scene's: [0] the floor's, [1] the skydome, then the materials' in file order. */
+int  crt_host_scene_look(crt_host_scene* scene, void* look /* or NULL */, uint32_t* words);
+/* ... and a look taken over by the host scene — light quad, floor / skydome texture index, materials — so that the next crt_host_scene_upload describes the scene
+ * with it.  The device is not touched: crt_update_look changes the look of a live scene in place.  CRT_ERR_INVALID with nothing changed for a texture index the
+ * scene does not have. */
+int  crt_host_scene_set_look(crt_host_scene* scene, const void* look);
 /* The same refit on the device, from positions in device memory (crt_refit_device; d_positions, triCount, stream as there): node 0 of BVH `bvh` takes the refitted
  * root box the call returns and, for a TLAS scene, BLASBVH::SetTransform(T) + TLASBVH::Build run on the host and crt_update_scene(CRT_UPDATE_TRANSFORMS) follows.
  * The host triangles and the other nodes of that BVH never saw the new positions: the BVH is marked stale, and while any BVH of the scene is,
