@@ -161,7 +161,8 @@ int  crt_update_scene(crt_ctx* ctx, const crt_scene_desc* scene, uint32_t what);
  * a host array or in a device tensor): a crt_look_header — the light quad and the floor / skydome texture, the crt_scene_desc members of the same names, same meaning
  * and units, invT supplied by the caller exactly as at upload — followed by materialCount crt_material records (six words each), materialCount being the uploaded
  * scene's.  A look SELECTS AMONG THE UPLOADED TEXTURES BY INDEX (materials: -1 = untextured); texels are never part of a look.  crt_look_words(materialCount) is the
- * stride of an array of looks, in words.  ABI version 3 still: additions, detected by symbol. */
+ * stride of an array of looks, in words.  ABI version 3 still: additions, detected by symbol.
+ * lightT must be rigid (rotation and translation) and lightInvT its FastInvertedTransformNoScale, as at upload; anything else is the caller's error. */
 typedef struct crt_look_header { float lightT[16], lightInvT[16], lightSize; int32_t floorTexture, skyTexture; uint32_t pad; } crt_look_header;
 #define CRT_LOOK_HEADER_WORDS   36u
 #define CRT_LOOK_MATERIAL_WORDS 6u

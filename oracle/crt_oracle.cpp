@@ -922,6 +922,8 @@ struct orc_ctx {
     std::string err;
     // scene description
     V3 lightPos = v3(0, 3, 1);
+    bool lightQuadSet = false; M4 lightT = m4_identity(), lightInvT = m4_identity(); float lightSize = 0.5f;   // orc_set_light_quad: instead of Translate(lightPos), Quad(0, 1)
+    bool floorScaleSet = false; float floorInvto = 1.f;                                                        // orc_set_floor_uv_scale: instead of 1 / (width / 100)
     Tex floorTex, sky;
     std::vector<Mat> materials;
     std::vector<ObjDesc> objects;
@@ -1171,6 +1173,22 @@ void orc_destroy(orc_ctx* c) { delete c; }
 const char* orc_last_error(orc_ctx* c) { return c ? c->err.c_str() : "null ctx"; }
 
 int orc_set_light_position(orc_ctx* c, const float p[3]) { c->lightPos = v3(p[0], p[1], p[2]); return 0; }
+// A look's light quad and floor scale (the product's crt_look_header): the quad's two matrices and half size as given, cell for cell, and the floor plane's uv
+// scale, in place of what orc_build derives from lightPos and from the floor texture's width.  Kept across orc_build; applied to a built scene at once.
+static void apply_light_quad(orc_ctx* c) { c->light.T = c->lightT; c->light.invT = c->lightInvT; c->light.size = c->lightSize; }
+int orc_set_light_quad(orc_ctx* c, const float T[16], const float invT[16], float size)
+{
+    if (!T || !invT) { c->err = "orc_set_light_quad: T and invT are required"; return -1; }
+    memcpy(c->lightT.c, T, 64); memcpy(c->lightInvT.c, invT, 64); c->lightSize = size; c->lightQuadSet = true;
+    if (c->built && c->kind != 2) apply_light_quad(c);
+    return 0;
+}
+int orc_set_floor_uv_scale(orc_ctx* c, float invto)
+{
+    c->floorInvto = invto; c->floorScaleSet = true;
+    if (c->built && c->kind != 2) c->floor.invto = invto;
+    return 0;
+}
 static int set_tex(Tex& t, const uint32_t* rgb, int w, int h)
 {
     t.w = w; t.h = h; t.px.assign(rgb, rgb + (size_t)w * h); return 0;
@@ -1210,6 +1228,8 @@ int orc_build(orc_ctx* c)
     c->floor.invto = 1.f / (float)(c->floorTex.w / 100);              // integer division (file_scene.cpp:16)
     M4 M1 = m4_translate(c->lightPos);
     c->light.T = M1; c->light.invT = m4_fast_inverted_noscale(M1);
+    if (c->lightQuadSet) apply_light_quad(c);
+    if (c->floorScaleSet) c->floor.invto = c->floorInvto;
 
     int objId = 2;
     if (c->kind == 0) {
@@ -1571,6 +1591,41 @@ struct Whitted {
 };
 } // namespace
 
+int orc_get_light(orc_ctx* c, float T[16], float invT[16], float* size, float normal[3], float lightPos[3], float* floorInvto)
+{
+    if (!c->built || c->kind == 2) { c->err = "orc_get_light: a built FileScene / TLASFileScene"; return -1; }
+    Whitted w; w.c = c;
+    memcpy(T, c->light.T.c, 64); memcpy(invT, c->light.invT.c, 64); *size = c->light.size; st3(normal, c->light.normal()); st3(lightPos, w.light_pos());
+    *floorInvto = c->floor.invto;
+    return 0;
+}
+// QuadPrim and PlanePrim on their own, for the pin against the reference's classes (tests/test_oracle_pinning.py): per ray Intersect on a fresh Ray (t, objIdx),
+// IsOccluded on Ray(O, D, tmax), GetNormal; the plane's GetUV at I = O + t * D where it is hit
+int orc_quad_probe(const float T[16], const float invT[16], float size, const float* O, const float* D, const float* tmax, size_t n, float* t, int32_t* objIdx,
+                   int32_t* occluded, float normal[3])
+{
+    QuadPrim q; memcpy(q.T.c, T, 64); memcpy(q.invT.c, invT, 64); q.size = size; q.objIdx = 0;
+    for (size_t i = 0; i < n; i++) {
+        Ray r = make_ray(ld3(O + 3 * i), ld3(D + 3 * i));
+        q.intersect(r); t[i] = r.t; objIdx[i] = r.objIdx;
+        Ray s = make_ray(ld3(O + 3 * i), ld3(D + 3 * i)); s.t = tmax[i];
+        occluded[i] = q.occluded(s) ? 1 : 0;
+    }
+    st3(normal, q.normal());
+    return 0;
+}
+int orc_plane_probe(float invto, const float* O, const float* D, size_t n, float* t, int32_t* objIdx, float* uv)
+{
+    PlanePrim p; p.invto = invto;
+    for (size_t i = 0; i < n; i++) {
+        Ray r = make_ray(ld3(O + 3 * i), ld3(D + 3 * i));
+        p.intersect(r); t[i] = r.t; objIdx[i] = r.objIdx;
+        V2 w; w.x = 0; w.y = 0;
+        if (r.objIdx == 1) w = p.uv(r.O + r.t * r.D);
+        uv[2 * i] = w.x; uv[2 * i + 1] = w.y;
+    }
+    return 0;
+}
 int orc_whitted_render(orc_ctx* c, int nThreads)
 {
     if (!c->built || c->W == 0) { c->err = "scene not built or renderer not initialised"; return -1; }

@@ -57,6 +57,17 @@ const char* orc_last_error(orc_ctx*);
 /* scene description (what LoadSceneFile + tinyobj + stb_image hand to the scene ctor) */
 int orc_set_light_position(orc_ctx*, const float pos[3]);
 int orc_set_floor_texture(orc_ctx*, const uint32_t* rgb, int w, int h);   /* 0x00RRGGBB */
+/* what a look of the product may set beyond the scene file: the light quad as Quad(0, 2 * size, T) with T, invT taken cell for cell (rigid T, invT its
+ * FastInvertedTransformNoScale: anything else is the caller's error), and the floor plane's uv scale (Plane::invto).  They override what orc_build derives
+ * from orc_set_light_position and from the floor texture's width / 100, hold across orc_build, and reach a built scene at once.  Unset: as before. */
+int orc_set_light_quad(orc_ctx*, const float T[16], const float invT[16], float size);
+int orc_set_floor_uv_scale(orc_ctx*, float invto);
+/* QuadPrim / PlanePrim alone (the pin against the reference's Quad and Plane): Intersect on Ray(O, D), IsOccluded on Ray(O, D, tmax), GetNormal, GetUV */
+int orc_quad_probe(const float T[16], const float invT[16], float size, const float* O, const float* D, const float* tmax, size_t n, float* t, int32_t* objIdx,
+                   int32_t* occluded, float normal[3]);
+int orc_plane_probe(float invto, const float* O, const float* D, size_t n, float* t, int32_t* objIdx, float* uv);
+/* the built scene's quad (Quad::GetNormal, FileScene::GetLightPos) and floor scale */
+int orc_get_light(orc_ctx*, float T[16], float invT[16], float* size, float normal[3], float lightPos[3], float* floorInvto);
 int orc_set_skydome(orc_ctx*, const uint32_t* rgb, int w, int h);
 int orc_add_material(orc_ctx*, float reflectivity, float refractivity, const float absorption[3],
                      const uint32_t* tex_rgb, int w, int h);              /* tex_rgb NULL = no texture */

@@ -19,14 +19,23 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libcrt_oracle.so")
 REF_LIB_PATH = os.path.join(HERE, "_ref", "libcrt_ref.so")
+# the entry point ref_harness.cpp gained last: whoever adds an export there names it here, or a library kept from before the addition is taken for current
+REF_NEWEST_SYMBOL = b"ref_plane_probe"
 
 
 def build(force=False):
     """Compile the oracle (g++) and, when /root/reference exists, oracle/_ref (the real reference, in place)."""
     if force or not os.path.exists(LIB_PATH) or os.path.getmtime(LIB_PATH) < os.path.getmtime(os.path.join(HERE, "crt_oracle.cpp")):
         subprocess.check_call(["make", "-C", HERE, "libcrt_oracle.so"])
-    if os.path.isdir("/root/reference") and (force or not os.path.exists(REF_LIB_PATH)):
-        subprocess.check_call(["make", "-C", HERE, "ref"])
+    ref_src = [os.path.join(HERE, "ref_build", "ref_harness.cpp"), os.path.join(HERE, "ref_build", "precomp.h"), os.path.join(HERE, "Makefile")]
+    # (a library left by an earlier build of another harness lacks the entry points this one declares: rebuilt whenever a source of it is newer)
+    def stale():
+        if os.path.getmtime(REF_LIB_PATH) < max(os.path.getmtime(f) for f in ref_src):
+            return True
+        with open(REF_LIB_PATH, "rb") as f:                                 # (looked for in the file: a dlopen would pin the old image for this process)
+            return REF_NEWEST_SYMBOL not in f.read()
+    if os.path.isdir("/root/reference") and (force or not os.path.exists(REF_LIB_PATH) or stale()):
+        subprocess.check_call(["make", "-B", "-C", HERE, "ref"])
 
 
 class BvhNode(C.Structure):
@@ -121,6 +130,22 @@ class Oracle:
     # --- scene description -------------------------------------------------------------------
     def set_light_position(self, p):
         self._ck(self.L.orc_set_light_position(self.h, _f3(p)))
+
+    def set_light_quad(self, T, invT, size):
+        """the light as Quad(0, 2 * size, T): both matrices cell for cell (16 float32 each, row-major), instead of Translate(light position) and size 0.5; kept across build()"""
+        T = np.ascontiguousarray(T, np.float32).reshape(16); invT = np.ascontiguousarray(invT, np.float32).reshape(16)
+        self._ck(self.L.orc_set_light_quad(self.h, _fp(T), _fp(invT), C.c_float(size)))
+
+    def set_floor_uv_scale(self, invto):
+        """the floor plane's uv scale (Plane::invto) instead of 1 / (floor texture width // 100); kept across build()"""
+        self._ck(self.L.orc_set_floor_uv_scale(self.h, C.c_float(invto)))
+
+    def light(self):
+        """the built scene's quad and floor scale: dict(T, invT, size, normal = Quad::GetNormal, pos = GetLightPos(), floor_invto)"""
+        T, invT, n, p = np.zeros(16, np.float32), np.zeros(16, np.float32), np.zeros(3, np.float32), np.zeros(3, np.float32)
+        size, invto = C.c_float(), C.c_float()
+        self._ck(self.L.orc_get_light(self.h, _fp(T), _fp(invT), C.byref(size), _fp(n), _fp(p), C.byref(invto)))
+        return dict(T=T.reshape(4, 4), invT=invT.reshape(4, 4), size=np.float32(size.value), normal=n, pos=p, floor_invto=np.float32(invto.value))
 
     def set_floor_texture(self, rgb):
         rgb = np.ascontiguousarray(rgb, dtype=np.uint32)
@@ -742,6 +767,27 @@ def vertex_dedup(v8):
     return idx, uniq[:n].copy()
 
 
+def _ray_arrays(O, D, tmax):
+    O = np.ascontiguousarray(O, np.float32).reshape(-1, 3); D = np.ascontiguousarray(D, np.float32).reshape(-1, 3)
+    return O, D, np.ascontiguousarray(np.broadcast_to(np.asarray(tmax, np.float32), (O.shape[0],))), O.shape[0]
+
+
+def quad_probe(T, invT, size, O, D, tmax):
+    """the oracle's QuadPrim alone (orc_quad_probe): dict(t, objIdx, occluded, normal), as Ref.quad_probe"""
+    T = np.ascontiguousarray(T, np.float32).reshape(16); invT = np.ascontiguousarray(invT, np.float32).reshape(16); O, D, tmax, n = _ray_arrays(O, D, tmax)
+    t, obj, occ, nrm = np.zeros(n, np.float32), np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(3, np.float32)
+    lib().orc_quad_probe(_fp(T), _fp(invT), C.c_float(size), _fp(O), _fp(D), _fp(tmax), C.c_size_t(n), _fp(t), _fp(obj), _fp(occ), _fp(nrm))
+    return dict(t=t, objIdx=obj, occluded=occ, normal=nrm)
+
+
+def plane_probe(invto, O, D):
+    """the oracle's PlanePrim alone (orc_plane_probe): dict(t, objIdx, uv), as Ref.plane_probe"""
+    O, D, _, n = _ray_arrays(O, D, 0.0)
+    t, obj, uv = np.zeros(n, np.float32), np.zeros(n, np.int32), np.zeros((n, 2), np.float32)
+    lib().orc_plane_probe(C.c_float(invto), _fp(O), _fp(D), C.c_size_t(n), _fp(t), _fp(obj), _fp(uv))
+    return dict(t=t, objIdx=obj, uv=uv)
+
+
 class Ref:
     """oracle/_ref: the reference's own bvh.cpp / tinyobj / stb_image compiled in place (authoring container only)."""
 
@@ -754,6 +800,10 @@ class Ref:
         L.ref_image_load.restype = C.POINTER(C.c_ubyte)
         L.ref_texture_load.restype = C.POINTER(C.c_uint32)
         self.L = L
+
+    def has(self, symbol):
+        """whether this build of oracle/_ref exports `symbol` (one kept from an earlier harness, where the reference tree is gone, does not have the later ones)"""
+        return hasattr(self.L, symbol)
 
     def bvh_build(self, tris):
         tris = np.ascontiguousarray(tris)
@@ -840,6 +890,21 @@ class Ref:
         rgb = np.zeros((uv.shape[0], 3), np.float32); alb = np.zeros((uv.shape[0], 3), np.float32)
         self.L.ref_texture_sample(_fp(texels), texels.shape[1], texels.shape[0], _fp(uv), C.c_uint32(uv.shape[0]), _fp(rgb), _fp(alb))
         return rgb, alb
+
+    def quad_probe(self, T, size, O, D, tmax):
+        """the reference's own Quad(0, 2 * size, T): dict(t, objIdx of Intersect on Ray(O, D); occluded = IsOccluded(Ray(O, D, tmax)); invT, size as its constructor
+        left them; normal = GetNormal; pos = FileScene::GetLightPos's expression on its T)"""
+        T = np.ascontiguousarray(T, np.float32).reshape(16); O, D, tmax, n = _ray_arrays(O, D, tmax)
+        t, obj, occ, out = np.zeros(n, np.float32), np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(23, np.float32)
+        self.L.ref_quad_probe(_fp(T), C.c_float(size), _fp(O), _fp(D), _fp(tmax), C.c_uint32(n), _fp(t), _fp(obj), _fp(occ), _fp(out))
+        return dict(t=t, objIdx=obj, occluded=occ, invT=out[:16].reshape(4, 4).copy(), size=out[16], normal=out[17:20].copy(), pos=out[20:23].copy())
+
+    def plane_probe(self, texture_offset, O, D):
+        """the reference's own Plane(1, (0, 1, 0), 1, texture_offset): dict(t, objIdx of Intersect; uv = GetUV(O + t D) where it is hit; invto)"""
+        O, D, _, n = _ray_arrays(O, D, 0.0)
+        t, obj, uv, invto = np.zeros(n, np.float32), np.zeros(n, np.int32), np.zeros((n, 2), np.float32), C.c_float()
+        self.L.ref_plane_probe(C.c_float(texture_offset), _fp(O), _fp(D), C.c_uint32(n), _fp(t), _fp(obj), _fp(uv), C.byref(invto))
+        return dict(t=t, objIdx=obj, uv=uv, invto=np.float32(invto.value))
 
     def image_load(self, path):
         w, h, n = C.c_int(), C.c_int(), C.c_int()

@@ -13,6 +13,11 @@
  *   template/tmplmath.h      -> the inline functions on the path: normalize, reflect, cross, dot, mat4::Translate / RotateX / RotateY / RotateZ / Scale,
  *                               mat4::FastInvertedTransformNoScale, aabb::Grow / Area   (ref_math_probe)
  *   infra/helper.h           -> Vertex::operator== and std::hash<Vertex> inside a real std::unordered_map<Vertex, uint32_t>   (ref_vertex_dedup)
+ *   template/primitives.h    -> class Plane and class Quad (ref_quad_probe, ref_plane_probe).  The header as a whole does not compile here (Sphere and Cube read
+ *                               __m128::m128_f32, an MSVC member), so the Makefile copies the two classes' own lines, unchanged, into _ref/prim_plane_quad.h
+ *                               and checks that the copy begins and ends where the classes do; nothing of it is kept outside _ref.
+ *   template/tmplmath.cpp    -> operator*(mat4, mat4), operator*(float4, mat4), TransformPosition, TransformVector (:109-169), copied likewise into
+ *                               _ref/tmplmath_products.inc: the file includes "precomp.h" from its own directory and so cannot be compiled where it lies.
  * The three headers need three names that template/precomp.h / template/opengl.h declare and that live in translation units this
  * image cannot build (template.cpp, opencl.cpp: <windows.h>, OpenGL, OpenCL): IsKeyDown (precomp.h:143), WindowHasFocus (opengl.h:23)
  * and FatalError (precomp.h:203).  They are DECLARED below exactly as there and never defined: only Camera::HandleInput and the
@@ -40,6 +45,11 @@ void FatalError( const char* fmt, ... ); /* template/precomp.h:203 (declaration 
 #include "camera.h"                    /* /root/reference/template/camera.h */
 #include "texture.h"                   /* /root/reference/template/texture.h */
 #include "material.h"                  /* /root/reference/template/material.h */
+#include "surface.h"                   /* /root/reference/template/surface.h (Plane::GetAlbedo names Surface; never instantiated here) */
+namespace Tmpl8 {
+#include "prim_plane_quad.h"           /* oracle/_ref: template/primitives.h's class Plane and class Quad, verbatim (Makefile) */
+}
+#include "tmplmath_products.inc"       /* oracle/_ref: template/tmplmath.cpp:109-169, verbatim (Makefile) */
 
 #include <stdint.h>
 
@@ -274,6 +284,46 @@ uint32_t ref_vertex_dedup(const float* v8, uint32_t n, uint32_t* idx, float* uni
         u[0] = v.position.x; u[1] = v.position.y; u[2] = v.position.z; u[3] = v.normal.x; u[4] = v.normal.y; u[5] = v.normal.z; u[6] = v.uv.x; u[7] = v.uv.y;
     }
     return (uint32_t)vertices.size();
+}
+
+
+/* Quad as a scene would construct it with a half size and a transform, Quad(0, 2 * size, T) (primitives.h:325-330: size = s * 0.5f, invT = T's
+ * FastInvertedTransformNoScale): Intersect on a fresh Ray(O, D), IsOccluded on Ray(O, D, tmax), GetNormal, and FileScene::GetLightPos's expression
+ * (file_scene.cpp:159-161) on the quad's T.  out = invT[16], size, normal[3], light position[3] */
+void ref_quad_probe(const float* T, float size, const float* O, const float* D, const float* tmax, uint32_t n, float* t, int32_t* objIdx, int32_t* occluded, float* out)
+{
+    mat4 M; memcpy(M.cell, T, 64);
+    const Quad light(0, 2 * size, M);
+    for (uint32_t i = 0; i < n; i++) {
+        const float3 o(O[3 * i], O[3 * i + 1], O[3 * i + 2]), d(D[3 * i], D[3 * i + 1], D[3 * i + 2]);
+        Ray r(o, d);
+        light.Intersect(r);
+        t[i] = r.t; objIdx[i] = r.objIdx;
+        occluded[i] = light.IsOccluded(Ray(o, d, tmax[i])) ? 1 : 0;
+    }
+    memcpy(out, light.invT.cell, 64); out[16] = light.size;
+    const float3 nn = light.GetNormal(float3(0));
+    out[17] = nn.x; out[18] = nn.y; out[19] = nn.z;
+    float3 ends[2];                                        /* the two opposite corners of the unit quad carried by T, their mean, 0.01 lower */
+    for (int k = 0; k < 2; k++) { const float e = k ? 0.5f : -0.5f; ends[k] = TransformPosition(float3(e, 0, e), light.T); }
+    float3 mid = ends[0] + ends[1];
+    mid = mid * 0.5f;
+    mid = mid - float3(0, 0.01f, 0);
+    out[20] = mid.x; out[21] = mid.y; out[22] = mid.z;
+}
+/* Plane(1, (0, 1, 0), 1, textureOffset) as FileScene constructs its floor (file_scene.cpp:16): Intersect, and GetUV at I = O + t * D where it is hit */
+void ref_plane_probe(float textureOffset, const float* O, const float* D, uint32_t n, float* t, int32_t* objIdx, float* uv, float* invto)
+{
+    const Plane floor(1, float3(0, 1, 0), 1, textureOffset);
+    *invto = floor.invto;
+    for (uint32_t i = 0; i < n; i++) {
+        Ray r(float3(O[3 * i], O[3 * i + 1], O[3 * i + 2]), float3(D[3 * i], D[3 * i + 1], D[3 * i + 2]));
+        floor.Intersect(r);
+        t[i] = r.t; objIdx[i] = r.objIdx;
+        float2 w(0);
+        if (r.objIdx == 1) w = floor.GetUV(r.O + r.t * r.D);
+        uv[2 * i] = w.x; uv[2 * i + 1] = w.y;
+    }
 }
 
 } // extern "C"

@@ -5,9 +5,17 @@ here is derived from the reference's lines a third time, as mathematics: the EXP
 analytic nearest hit of the PrimitiveScene's primitives.  Nothing in this module imports the oracle or the library; the test modules hand their results in.
 
 Statistical criterion of every comparison with a mean of N samples:   |mean - want| <= Z * sigma_truth / sqrt(N),   Z = 5,
-with sigma_truth from the SECOND MOMENT OF THE TRUTH (never from the samples).  The two test modules make some 50 distinct comparisons of this kind (the kernels
-return the oracle's bits, so theirs are the same numbers again): a correct estimator fails one with probability < 200 * 5.8e-7 = 1.2e-4, and the seeds are
-fixed, so what passes once passes always.
+with sigma_truth from the SECOND MOMENT OF THE TRUTH (never from the samples).  The two test modules make some 50 distinct comparisons of this kind on the scenes
+as their files give them, and some 100 more under the quad looks below (QUAD_LOOKS: 5 looks x 5 floor points through the BVH — the TLAS returns the same samples —
+and 5 looks x 8 floor tiles x 3 channels share one render per look, counted once per tile: 25 + 40, and the render_looks job's 40 again); the kernels return the
+oracle's bits, so theirs are the same numbers again.  A correct estimator fails one of 150 three-channel comparisons with probability < 450 * 5.8e-7 = 2.7e-4, and the
+seeds are fixed, so what passes once passes always.
+
+THE QUAD.  quad = (centre, half) is the scene files' quad, parallel to the floor; quad = (centre, R, half) a look's (crt_update_look): the square |x|, |z| < half of
+the frame whose axes are R's columns, R[:, 1] its normal's axis.  It emits (24, 24, 22) from BOTH faces (the path tracer returns the light's colour before it
+looks at a normal, renderer.cpp:69), so every integral takes |cos theta'|; the Whitted point light is the centre moved 0.01 down in WORLD y whatever R is
+(file_scene.cpp:156-162: the two corners' mean, minus (0, 0.01, 0)), and its N.L is the floor's normal alone.  Every test quad lies wholly above the floor, which
+the contour formula needs and floor_radiance asserts.
 
 Line numbers: renderer.cpp = "3. PathTracer/renderer.cpp" unless "2. WhittedStyle" is named; the other files are template/ and infra/ of the reference.
 """
@@ -49,9 +57,38 @@ def _quad_edges(P, quad):
     return c[0] - s - P[..., 0], c[0] + s - P[..., 0], c[2] - s - P[..., 2], c[2] + s - P[..., 2], c[1] - P[..., 1]
 
 
+def quad_frame(quad):
+    """(centre, R [3, 3], half) of either form of a quad"""
+    if len(quad) == 2:
+        return np.asarray(quad[0], np.float64), np.eye(3), float(quad[1])
+    return np.asarray(quad[0], np.float64), np.asarray(quad[1], np.float64).reshape(3, 3), float(quad[2])
+
+
+def quad_corners(quad):
+    c, R, h = quad_frame(quad)
+    return np.stack([c + sx * h * R[:, 0] + sz * h * R[:, 2] for sx, sz in ((-1, -1), (1, -1), (1, 1), (-1, 1))])
+
+
+def form_factor_polygon(P, n, corners):
+    """Lambert's contour formula: the form factor from a differential area at P [..., 3] with normal n to the polygon `corners` [k, 3], all of it above P's horizon:
+    1 / 2 pi * sum gamma_i n . (r_i x r_i+1) / |r_i x r_i+1|, gamma_i the angle the edge subtends.  The sign of the sum is the polygon's winding; a quad that emits
+    from both faces counts either way: the absolute value."""
+    P, n, corners = np.asarray(P, np.float64), np.asarray(n, np.float64), np.asarray(corners, np.float64)
+    r = corners - P[..., None, :]
+    assert ((r @ n) > 0).all(), "a corner at or below the horizon"
+    r = r / np.linalg.norm(r, axis=-1, keepdims=True)
+    rn = np.roll(r, -1, axis=-2)
+    cr = np.cross(r, rn); sn = np.linalg.norm(cr, axis=-1)
+    gamma = np.arctan2(sn, (r * rn).sum(-1))
+    return np.abs((gamma * (cr @ n) / sn).sum(-1)) / (2.0 * np.pi)
+
+
 def form_factor(P, quad):
-    """form factor from a horizontal differential area at P [..., 3] (normal +y) to the parallel rectangle quad = (centre, half size) above it: the corner term
-    x / sqrt(x^2 + h^2) atan(z / sqrt(x^2 + h^2)) + z / sqrt(z^2 + h^2) atan(x / sqrt(z^2 + h^2)) over 2 pi, summed with signs over the four corners"""
+    """form factor from a horizontal differential area at P [..., 3] (normal +y) to the quad above it.  quad = (centre, half size), parallel: the corner term
+    x / sqrt(x^2 + h^2) atan(z / sqrt(x^2 + h^2)) + z / sqrt(z^2 + h^2) atan(x / sqrt(z^2 + h^2)) over 2 pi, summed with signs over the four corners;
+    quad = (centre, R, half): form_factor_polygon"""
+    if len(quad) == 3:
+        return form_factor_polygon(P, [0.0, 1.0, 0.0], quad_corners(quad))
     x1, x2, z1, z2, h = _quad_edges(P, quad)
     return _corner(x2, z2, h) - _corner(x1, z2, h) - _corner(x2, z1, h) + _corner(x1, z1, h)
 
@@ -60,7 +97,20 @@ _GL = np.polynomial.legendre.leggauss(12)
 
 
 def cos2_solid_angle(P, quad):
-    """integral of cos^2(theta) d omega over the quad seen from P = integral of h^3 / r^5 dA, by 12 x 12 Gauss-Legendre"""
+    """integral of cos^2(theta) d omega over the quad seen from P (theta from +y), by 12 x 12 Gauss-Legendre over the quad's own parametrisation:
+    d omega = |cos theta'| dA / r^2, so the integrand is (d.y)^2 |d . n'| / r^5 with d the vector to the quad's point and n' = R[:, 1]"""
+    P = np.asarray(P, np.float64)
+    c, R, h = quad_frame(quad)
+    g, w = _GL
+    pts = c + h * g[:, None, None] * R[:, 0] + h * g[None, :, None] * R[:, 2]
+    d = pts - P[..., None, None, :]
+    r2 = (d * d).sum(-1)
+    f = d[..., 1] ** 2 * np.abs(d @ R[:, 1]) / r2 ** 2.5
+    return (f * w[:, None] * w[None, :]).sum(axis=(-1, -2)) * h * h
+
+
+def cos2_solid_angle_parallel(P, quad):
+    """the same for quad = (centre, half), parallel to the floor: integral of h^3 / r^5 dA (what cos2_solid_angle must come to there)"""
     x1, x2, z1, z2, h = _quad_edges(P, quad)
     g, w = _GL
     x = (x1[..., None] + x2[..., None]) / 2 + (x2 - x1)[..., None] / 2 * g
@@ -71,21 +121,32 @@ def cos2_solid_angle(P, quad):
 
 
 def form_factor_quadrature(P, quad, n=400):
-    """brute force: cos(theta) cos(theta') / (pi r^2) over an n x n midpoint grid of the quad (the check of form_factor)"""
+    """brute force: cos(theta) |cos(theta')| / (pi r^2) over an n x n midpoint grid of the quad (the check of form_factor)"""
+    if len(quad) == 3:
+        c, R, h = quad_frame(quad)
+        u = ((np.arange(n) + 0.5) / n * 2.0 - 1.0) * h
+        d = c + u[:, None, None] * R[:, 0] + u[None, :, None] * R[:, 2] - np.asarray(P, np.float64)
+        r2 = (d * d).sum(-1)
+        return float((d[..., 1] * np.abs(d @ R[:, 1]) / (np.pi * r2 * r2)).sum() * (2.0 * h / n) ** 2)
     x1, x2, z1, z2, h = [float(v) for v in _quad_edges(np.asarray(P, np.float64), quad)]
     x = x1 + (np.arange(n) + 0.5) * (x2 - x1) / n; z = z1 + (np.arange(n) + 0.5) * (z2 - z1) / n
     r2 = x[:, None] ** 2 + z[None, :] ** 2 + h * h
     return float((h * h / (np.pi * r2 * r2)).sum() * (x2 - x1) * (z2 - z1) / (n * n))
 
 
-def floor_radiance(P, rho, L_sky, quad):
+def floor_radiance(P, rho, L_sky, quad, one_face=False):
     """(E[X], E[X^2]) [..., 3] of X = Sample(ray that hits the floor at P) when the bounce ray can meet only the light quad or the constant sky.
     renderer.cpp:95-98: R uniform on the hemisphere (tmplmath.h:535-544, pdf 1 / 2 pi), X = albedo * INVPI * 2 * PI * dot(R, N) * Sample(R), and
     Sample(R) = (24, 24, 22) on the quad (:69, both faces, file_scene.cpp:211) or the sky texel (:54).  So
         E[X]   = rho / pi * integral cos L_in d omega    = rho (L_sky (1 - F) + L_light F)
         E[X^2] = rho^2 (2 / pi) integral cos^2 L_in^2 d omega,  integral of cos^2 over the hemisphere = 2 pi / 3"""
     rho, L_sky = np.asarray(rho, np.float64), np.asarray(L_sky, np.float64)
+    assert (quad_corners(quad)[:, 1] > FLOOR_Y).all(), "the quad reaches the floor"
     F = form_factor(P, quad)[..., None]; Q = cos2_solid_angle(P, quad)[..., None]
+    if one_face:                                                           # a WRONG model, for the tests' controls: only the face the normal -R[:, 1] points from emits
+        c, R, _ = quad_frame(quad)
+        seen = (((np.asarray(P, np.float64) - c) @ -R[:, 1]) > 0)[..., None]
+        F, Q = F * seen, Q * seen
     mean = rho * (L_sky * (1.0 - F) + LIGHT * F)
     second = rho * rho * (2.0 / np.pi) * (LIGHT * LIGHT * Q + L_sky * L_sky * (2.0 * np.pi / 3.0 - Q))
     return mean, second
@@ -265,16 +326,26 @@ def light_pixels(camera, W, H, quad, grow=0.5, margin=1e-3):
 # ---------------------------------------------------------------------------------------------------------------------------------------------------
 # Whitted
 # ---------------------------------------------------------------------------------------------------------------------------------------------------
-def whitted_floor(P, rho, quad, boxes=()):
+def whitted_floor(P, rho, quad, boxes=(), along_normal=False):
     """Trace of a primary ray that meets the diffuse floor at P (2. WhittedStyle/renderer.cpp:74-79, 105-126): rho / pi * (L_light cos / d^2 V + 0.3), the light
     point 0.01 under the quad's centre (file_scene.cpp:156-162), V = 0 where a box stands between (file_scene.cpp:177-187; the shadow ray runs from EPSILON to
     d - 2 EPSILON (:117) and the quad itself lies 0.01 / cos beyond its end).  Returns (rgb [..., 3], V)"""
     P = np.asarray(P, np.float64)
-    lp = np.asarray(quad[0], np.float64) - [0.0, 0.01, 0.0]
+    lp = np.asarray(quad[0], np.float64) - [0.0, 0.01, 0.0]                # 0.01 down in world y, whatever the quad's frame and size
+    if along_normal:                                                       # a WRONG model, for the tests' controls: 0.01 along the quad's normal -R[:, 1]
+        lp = np.asarray(quad[0], np.float64) - 0.01 * quad_frame(quad)[1][:, 1]
     Lv = lp - P; d = np.linalg.norm(Lv, axis=-1); Lv = Lv / d[..., None]
     V = np.ones(P.shape[:-1], bool)
     for b in boxes:
         V &= ~b.blocks(P + Lv * EPSILON, Lv, d - 2 * EPSILON)
+    # the quad itself (IsOccluded tests it first, file_scene.cpp:177-187): the light point lies 0.01 under the centre in world y, so a floor point on the far
+    # side of a TILTED quad's plane sees it through the quad, and is dark
+    c, R, half = quad_frame(quad)
+    O = P + Lv * EPSILON
+    with np.errstate(divide="ignore", invalid="ignore"):
+        t = ((c - O) @ R[:, 1]) / (Lv @ R[:, 1])
+    I = O + np.where(np.isfinite(t), t, 0.0)[..., None] * Lv - c
+    V &= ~(np.isfinite(t) & (t > 0) & (t < d - 2 * EPSILON) & (np.abs(I @ R[:, 0]) < half) & (np.abs(I @ R[:, 2]) < half))
     cos = Lv[..., 1]
     return np.asarray(rho, np.float64) / np.pi * (LIGHT * (cos / (d * d) * V)[..., None] + 0.3), V
 
@@ -298,6 +369,8 @@ MIRROR_RGB = (192, 128, 64)
 LIGHT_POS = (1.2, 3.0, 0.5)                        # off-centre: a mirrored or transposed image moves the light's pool of brightness to other tiles
 QUAD = (np.array(LIGHT_POS), LIGHT_HALF)
 FLOOR_POINTS = np.array([[1.2, -1.0, 0.5], [0.3, -1.0, 1.6], [3.0, -1.0, -1.0]])       # under the quad's centre, beside it, far from it
+# under a turned quad: two more, either side of the centre along x (the point under the centre cannot tell R from its transpose)
+QUAD_FLOOR_POINTS = np.array(FLOOR_POINTS.tolist() + [[2.4, -1.0, 0.5], [0.0, -1.0, 0.5]])
 EYE = np.array([0.0, 0.3, -2.0])
 
 
@@ -548,10 +621,13 @@ def check_mean(samples, want, second, what):
     return z
 
 
-def floor_case(k):
-    """floor point k of S0: (O, D float32, E, E2, seeds)"""
-    P = FLOOR_POINTS[k]
-    mean, second = floor_radiance(P, texel_rgb(FLOOR_RGB), texel_rgb(SKY_RGB), QUAD)
+def floor_case(k, quad=None, salt=0):
+    """floor point k of S0: (O, D float32, E, E2, seeds); quad: a look's quad (then k indexes QUAD_FLOOR_POINTS), salt: seeds of its own"""
+    P = (FLOOR_POINTS if quad is None else QUAD_FLOOR_POINTS)[k]
+    mean, second = floor_radiance(P, texel_rgb(FLOOR_RGB), texel_rgb(SKY_RGB), QUAD if quad is None else quad)
+    if quad is not None:
+        assert (Z * np.sqrt(second - mean * mean) / np.sqrt(N_FLOOR) <= 0.03 * mean).all()
+        return EYE.astype(np.float32), _unit32(P - EYE), mean, second, seeds(1000 + 10 * salt + k, N_FLOOR)
     assert (np.sqrt(second - mean * mean) / np.sqrt(N_FLOOR) <= 0.005 * mean).all()
     return EYE.astype(np.float32), _unit32(P - EYE), mean, second, seeds(100 + k, N_FLOOR)
 
@@ -623,17 +699,17 @@ def mirror_case(kind, sky, n=8000):
 _truth_cache = {}
 
 
-def render_truth(sky):
-    """pixel_truth of S0 through the default camera, computed once: (E, E2, sky share)"""
-    if "render" not in _truth_cache:
-        _truth_cache["render"] = pixel_truth(camera_default(W, H), W, H, texel_rgb(FLOOR_RGB), sky, QUAD)
-    return _truth_cache["render"]
+def render_truth(sky, quad=None, key="render"):
+    """pixel_truth of S0 through the default camera, computed once per key: (E, E2, sky share)"""
+    if key not in _truth_cache:
+        _truth_cache[key] = pixel_truth(camera_default(W, H), W, H, texel_rgb(FLOOR_RGB), sky, QUAD if quad is None else quad)
+    return _truth_cache[key]
 
 
-def check_render(acc, frames, sky, what):
+def check_render(acc, frames, sky, what, quad=None, key="render"):
     """an accumulator [H, W, 4] of `frames` frames of S0 through the default camera: sky pixels, floor-tile means (ProcessTile's pixel <-> tile <-> accumulator
     mapping: the quad is off-centre, so a transposed or mirrored image moves the tile means by many sigma)"""
-    E, E2, up = render_truth(sky)
+    E, E2, up = render_truth(sky, quad, key)
     assert np.isfinite(acc).all() and not acc[..., 3].any()
     img = acc[..., :3].astype(np.float64) / frames
     sky_px = up == 1.0; floor_px = up == 0.0
@@ -656,16 +732,28 @@ def check_render(acc, frames, sky, what):
     assert (n_sky, n_floor) == (8, 8)
 
 
-def check_light_pixels(acc, frames, what):
+def check_light_pixels(acc, frames, what, quad=None, beyond=None):
+    """quad: a parallel quad (centre, half) of another size; beyond: only the pixels that lie wholly OUTSIDE this smaller quad's projection (its edge grown by
+    0.05: no corner of the pixel's footprint inside it)"""
     cam = camera_state(LIGHT_CAMERA[0], LIGHT_CAMERA[1], W, H)
-    lit = light_pixels(cam, W, H, QUAD)
+    lit = light_pixels(cam, W, H, QUAD if quad is None else quad)
+    if beyond is not None:
+        touched = np.zeros((H, W), bool)
+        for dx in (0.0, 1.0):
+            for dy in (0.0, 1.0):
+                y, x = np.meshgrid(np.arange(H), np.arange(W), indexing="ij")
+                D = primary_dirs(cam, W, H, x + dx, y + dy)
+                t = (beyond[0][1] - cam[0][1]) / D[..., 1]
+                I = cam[0] + t[..., None] * D
+                touched |= (np.abs(I[..., 0] - beyond[0][0]) < beyond[1] + 0.05) & (np.abs(I[..., 2] - beyond[0][2]) < beyond[1] + 0.05)
+        lit &= ~touched
     assert lit.sum() >= 16, lit.sum()
     want = (LIGHT * frames).astype(np.float32)                             # :69 returns (24, 24, 22) whatever the seed: `frames` exact additions
     assert (acc[lit][:, :3] == want).all(), (what, int(lit.sum()))
     return int(lit.sum())
 
 
-def whitted_truth(boxes=()):
+def whitted_truth(boxes=(), quad=None):
     """the Whitted image of the floor through the default camera (2. WhittedStyle/renderer.cpp:144: rays through integer pixel coordinates): (rgb [H, W, 3],
     checked [H, W] bool = floor pixels away from the shadow's and the boxes' edges, floor [H, W] bool)"""
     cam = camera_default(W, H)
@@ -676,7 +764,7 @@ def whitted_truth(boxes=()):
         down = D[..., 1] < 0
         t = -(cam[0][1] - FLOOR_Y) / np.where(down, D[..., 1], -1.0)
         P = cam[0] + t[..., None] * D
-        rgb, V = whitted_floor(P, texel_rgb(FLOOR_RGB), QUAD, boxes)
+        rgb, V = whitted_floor(P, texel_rgb(FLOOR_RGB), QUAD if quad is None else quad, boxes)
         hit_box = np.zeros(down.shape, bool)
         for b in boxes:
             hit_box |= b.blocks(np.broadcast_to(cam[0], D.shape), D, np.where(down, t, np.inf))
@@ -690,11 +778,48 @@ def whitted_truth(boxes=()):
     return rgb, floor & steady, floor
 
 
-def check_whitted(acc, boxes, what, shadow):
-    rgb, checked, floor = whitted_truth(boxes)
+def check_whitted(acc, boxes, what, shadow, quad=None, tol=1.0 / 255.0):
+    rgb, checked, floor = whitted_truth(boxes, quad)
     left_out = 1.0 - checked.sum() / floor.sum()
     err = np.abs(acc[..., :3].astype(np.float64) - rgb)[checked]
     print("%s: %d floor pixels, %.2f %% left out, largest error %.2e" % (what, floor.sum(), 100 * left_out, err.max()))
     assert floor.sum() >= W * H // 3 and left_out <= 0.03, (what, left_out)
     assert (left_out > 0) == shadow, (what, left_out)
-    assert err.max() <= 1.0 / 255.0, (what, err.max())
+    assert err.max() <= tol, (what, err.max())
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------------------
+# the quad looks on S0 (applied by crt_update_look / in a crt_render_looks job; the oracle: set_light_quad)
+# ---------------------------------------------------------------------------------------------------------------------------------------------------
+def _rot64(axis, deg):
+    a = np.radians(deg); c, s_ = np.cos(a), np.sin(a); R = np.eye(3)
+    i, j = {"x": (1, 2), "y": (2, 0), "z": (0, 1)}[axis]
+    R[i, i], R[i, j], R[j, i], R[j, j] = c, -s_, s_, c
+    return R
+
+
+# name: (rotation block, half size); the transforms are tests/render_looks_inputs.py's about LIGHT_POS
+QUAD_LOOKS = {
+    "zyx": (_rot64("z", 25.0) @ _rot64("y", 30.0) @ _rot64("x", -35.0), 0.5),
+    "z25": (_rot64("z", 25.0), 0.5),
+    "half_x": (np.diag([1.0, -1.0, -1.0]), 0.5),
+    "size_0.9": (np.eye(3), 0.9),
+    "zyx_size_0.9": (_rot64("z", 25.0) @ _rot64("y", 30.0) @ _rot64("x", -35.0), 0.9),
+}
+
+
+# check_whitted's bound under a look: the pixel is some 25 float32 operations on values of at most about 1, each within 2^-24 = 6e-8 relative: 1.5e-6.
+# (The scene files' 1 / 255 was set for an image read back through 8-bit pixels; the accumulator compared here is float32.)
+WHITTED_QUAD_TOL = 2e-6
+
+
+def look_quad(name):
+    R, half = QUAD_LOOKS[name]
+    return (np.array(LIGHT_POS), R.astype(np.float32).astype(np.float64), half)      # (the cells a look carries are float32)
+
+
+def look_cells(name):
+    """(T [16], half) float32 of the look: R | LIGHT_POS"""
+    R, half = QUAD_LOOKS[name]
+    T = np.eye(4, dtype=np.float32); T[:3, :3] = R.astype(np.float32); T[:3, 3] = np.asarray(LIGHT_POS, np.float32)
+    return T.reshape(16), np.float32(half)

@@ -98,7 +98,8 @@ def det_acos(x):
 # the scene as GetHitInfo sees it
 # ---------------------------------------------------------------------------------------------------------------------------------------------------
 class SceneShading:
-    """What GetHitInfo / GetAlbedo / GetSkyColor read of a FileScene (kind 0) or TLASFileScene (kind 1) `o` that orc.load_scene built from the description `sc`."""
+    """What GetHitInfo / GetAlbedo / GetSkyColor read of a FileScene (kind 0) or TLASFileScene (kind 1) `o` that orc.load_scene built from the description `sc`.
+    set_look: the scene under a look of crt_update_look / crt_render_looks instead of the file's own."""
 
     def __init__(self, orc, o, sc, kind, base_dir):
         def rp(p):
@@ -110,6 +111,8 @@ class SceneShading:
         self.materials = sc["materials"]
         self.obj_mat = [ob["material_idx"] for ob in sc["objects"]]          # models[i]->matIdx (FileScene) / blas[i]->matIdx (two-level)
         self.light = f32(sc["light"])
+        self.light_T = np.eye(4, dtype=F)                                    # T = Translate(light position), file_scene.cpp:18
+        self.light_T[0, 3], self.light_T[1, 3], self.light_T[2, 3] = self.light
         self.tris = [o.bvh(i)["tris"] for i in range(o.bvh_count())]
         self.refresh_transforms(o)
         self.floor_n = f32([0, 1, 0])                                        # Plane floor(1, float3(0, 1, 0), 1, texW / 100), file_scene.cpp:16
@@ -119,16 +122,27 @@ class SceneShading:
     def refresh_transforms(self, o):
         self.T = [o.blas_transform(i)[0].reshape(4, 4) for i in range(o.bvh_count())] if self.kind == 1 else None
 
+    def set_look(self, look):
+        """the look's light T, and its floor, sky and material textures by index into the scene's texture list ([0] the file's floor texture, [1] its skydome,
+        then the materials' in file order).  The floor plane's uv scale is NOT part of a look: floor_invto stays the uploaded floor texture's
+        (file_scene.cpp:16 runs once, at construction), whatever width the selected texture has."""
+        if not hasattr(self, "textures"):
+            self.textures = [self.floor_tex, self.sky_tex] + [t for t in self.mat_tex if t is not None]
+        self.light_T = f32(look["light_T"]).reshape(4, 4).copy()
+        self.light = self.light_T[:3, 3].copy()
+        self.floor_tex, self.sky_tex = self.textures[look["floor_texture"]], self.textures[look["sky_texture"]]
+        assert len(look["materials"]) == len(self.materials)
+        self.mat_tex = [self.textures[t] if t >= 0 else None for _, _, _, t in look["materials"]]
+        self.materials = [dict(reflectivity=a, refractivity=b, absorption=c) for a, b, c, _ in look["materials"]]
+
     def light_normal(self):
-        """Quad::GetNormal (primitives.h:363-367): (-T[1], -T[5], -T[9]) of T = Translate(light position)"""
-        T = np.eye(4, dtype=F)
-        T[0, 3], T[1, 3], T[2, 3] = self.light
+        """Quad::GetNormal (primitives.h:363-367): (-T[1], -T[5], -T[9]) of the quad's T"""
+        T = self.light_T
         return f32([-T[0, 1], -T[1, 1], -T[2, 1]])
 
     def light_pos(self):
         """GetLightPos (file_scene.cpp:156-162): (c1 + c2) * 0.5f - (0, 0.01f, 0), the corners through the scalar TransformPosition"""
-        T = np.eye(4, dtype=F)
-        T[0, 3], T[1, 3], T[2, 3] = self.light
+        T = self.light_T                                                     # (the corners are +-0.5 whatever the quad's size, and 0.01 down in WORLD y)
 
         def tp(a):
             return f32([(((T[r, 0] * a[0]).astype(F) + (T[r, 1] * a[1]).astype(F)).astype(F) + (T[r, 2] * a[2]).astype(F)).astype(F) + (T[r, 3] * F(1)).astype(F) for r in range(3)])

@@ -9,10 +9,13 @@ Derived from the reference's lines as mathematics:
                evaluates it in: world space for a FileScene, object space for a BLAS, o = invT O, d = invT D, NOT renormalised (blas_bvh.cpp:376-389), so the
                ray parameter t is the world's.  Conditions: |a| >= 1e-4, 0 <= u, 0 <= v, u + v <= 1, t > 1e-4.  The two absolute thresholds are behaviour.
   floor        Plane(1, (0, 1, 0), 1): t = -(O.N + 1) / D.N, t > 0 (template/primitives.h:107-111)
-  light        Quad(0, 1) under Translate(light position): t = Oy / -Dy in its space, t > 0, |Ix| < 0.5, |Iz| < 0.5 (primitives.h:331-346)
+  light        Quad(0, 2 half, T), T rigid = (R | c): the plane through the centre c with normal R's y column, t > 0, and the hit point's coordinates along R's
+               x and z columns within +-half (primitives.h:321-367 as geometry).  The scene files give T = Translate(light position), half = 0.5; a look
+               (crt_update_look) any rigid T and any half size: World(light_T=, light_half=)
   IsOccluded   the light bounded by the ray's t; then the structure over the WHOLE ray (shadow.t = 1e34f); the floor is skipped (file_scene.cpp:177-187)
   GetHitInfo   N = normalize(w n0 + u n1 + v n2) (bvh.cpp:290-297), carried by T and renormalised for a BLAS (blas_bvh.cpp:391-398), turned towards the ray
-               (file_scene.cpp:211); uv interpolated alike; material 2 + matIdx; the floor's N, uv = frac(I.xz * invto) and the light's N = -T's y column.
+               (file_scene.cpp:211); uv interpolated alike; material 2 + matIdx; the floor's N, uv = frac(I.xz * invto) and the light's N = -(R's y column), turned
+               towards the ray like every other.
 
 THE CRITERION.  float32 arithmetic may decide a borderline condition either way, so every ray gets two candidate sets:
   ROBUST  every condition holds with slack;   SOFT  every condition holds when relaxed by the same slack;
@@ -100,16 +103,22 @@ def tol(name):
 # the world
 # ---------------------------------------------------------------------------------------------------------------------------------------------------
 class World:
-    """kind 0: one BVH in world space.  kind 1: one BLAS per object with its float32 T and invT as the scene holds them.  light: the quad's centre.
+    """kind 0: one BVH in world space.  kind 1: one BLAS per object with its float32 T and invT as the scene holds them.  light: the quad's centre;
+    light_T (the float32 cells, rotation | centre) and light_half: a look's quad instead of Translate(light), 0.5.
     obj_mat: the material index of every object of the scene file.  floor_invto: 1 / (floor texture width // 100) (file_scene.cpp:16)."""
 
-    def __init__(self, kind, tris, T=None, invT=None, light=(0.0, 3.0, 1.0), obj_mat=(0,), floor_invto=1.0):
+    def __init__(self, kind, tris, T=None, invT=None, light=(0.0, 3.0, 1.0), obj_mat=(0,), floor_invto=1.0, light_T=None, light_half=None):
         self.kind = int(kind)
         self.tris = [np.array(t) for t in tris]
         n = len(self.tris)
         self.T = [np.eye(4) if T is None else np.asarray(T[i], np.float32).astype(np.float64).reshape(4, 4) for i in range(n)]
         self.invT = [np.eye(4) if invT is None else np.asarray(invT[i], np.float32).astype(np.float64).reshape(4, 4) for i in range(n)]
         self.light = np.asarray(light, np.float32).astype(np.float64)
+        self.light_R, self.light_half = np.eye(3), float(at.LIGHT_HALF if light_half is None else np.float32(light_half))
+        if light_T is not None:                                             # the look's float32 cells, 3 x 4 or 4 x 4, row-major: rotation | centre
+            M = np.asarray(light_T, np.float32).astype(np.float64).reshape(-1, 4)
+            self.light_R, self.light = M[:3, :3].copy(), M[:3, 3].copy()
+            assert np.abs(self.light_R @ self.light_R.T - np.eye(3)).max() < 1e-6, "a rigid light transform"
         self.obj_mat = list(obj_mat)
         self.floor_invto = float(floor_invto)
         self.v = [np.stack([t["vertex0"], t["vertex1"], t["vertex2"]], 1).astype(np.float64) for t in self.tris]          # [n, 3, 3] per BVH
@@ -128,14 +137,14 @@ class World:
         return out
 
 
-def world_of(scene, kind, light, obj_mat, floor_invto):
+def world_of(scene, kind, light, obj_mat, floor_invto, light_T=None, light_half=None):
     """the plain arrays of anything that answers bvh_count(), bvh(i)["tris"] and blas_transform(i) (the oracle's scene and the host front's alike)"""
     n = scene.bvh_count()
     tris = [scene.bvh(i)["tris"] for i in range(n)]
     if kind == 0:
-        return World(0, tris, light=light, obj_mat=obj_mat, floor_invto=floor_invto)
+        return World(0, tris, light=light, obj_mat=obj_mat, floor_invto=floor_invto, light_T=light_T, light_half=light_half)
     tr = [scene.blas_transform(i) for i in range(n)]
-    return World(1, tris, [t[0] for t in tr], [t[1] for t in tr], light, obj_mat, floor_invto)
+    return World(1, tris, [t[0] for t in tr], [t[1] for t in tr], light, obj_mat, floor_invto, light_T, light_half)
 
 
 def mesh_world(p, light=(0.0, 3.0, 1.0)):
@@ -237,13 +246,14 @@ def floor_candidate(world, O, D, band):
 
 def light_candidate(world, O, D, band):
     """(robust t, soft t) of the light quad"""
+    R = world.light_R
     o = O - world.light
     with np.errstate(all="ignore"):
-        t = o[:, 1] / -D[:, 1]
+        t = (o @ R[:, 1]) / -(D @ R[:, 1])                                  # the plane through the centre with normal R's y column
     t = np.where(np.isfinite(t), t, -INF)
     tt = np.where(np.isfinite(t), t, 0.0)
-    ix, iz = o[:, 0] + tt * D[:, 0], o[:, 2] + tt * D[:, 2]
-    edge = at.LIGHT_HALF - np.maximum(np.abs(ix), np.abs(iz))
+    P = o + tt[:, None] * D
+    edge = world.light_half - np.maximum(np.abs(P @ R[:, 0]), np.abs(P @ R[:, 2]))   # inside the square spanned by R's x and z columns
     return np.where((t > band) & (edge > EPS), t, INF), np.where((t > -band) & (edge > -EPS), t, INF)
 
 
@@ -266,11 +276,13 @@ def nearest_truth(world, O, D, a_min=A_MIN):
     rival = np.where(kind == 2, np.minimum(m["second"], np.minimum(fs, ls)), rival)
     rival = np.where(kind == 1, np.minimum(m["lo"], ls), rival)
     rival = np.where(kind == 0, np.minimum(m["lo"], fs), rival)
-    unique = (kind >= 0) & (rival - t_lo > band)
+    with np.errstate(invalid="ignore"):                                  # (inf - inf where a ray has no candidate at all: NaN compares false)
+        unique = (kind >= 0) & (rival - t_lo > band)
     wide = np.isfinite(t_hi) != np.isfinite(t_lo)
     with np.errstate(invalid="ignore"):
         wide |= np.isfinite(t_hi) & (t_hi - t_lo > band)
-    crowded = (kind == 2) & ~unique & ~m["edge"] & (m["second"] - t_lo <= band)
+    with np.errstate(invalid="ignore"):                                  # (inf - inf where a ray has no candidate at all: NaN compares false)
+        crowded = (kind == 2) & ~unique & ~m["edge"] & (m["second"] - t_lo <= band)
     obj = np.where(kind == 2, world.obj_idx(m["blas"], np.maximum(m["tri"], 0)), kind)
     return dict(t_hi=t_hi, t_lo=t_lo, kind=kind, kind_hi=kind_hi, unique=unique, uninformative=wide | crowded, scale=scale, obj=obj, blas=m["blas"], tri=m["tri"],
                 u=m["u"], v=m["v"], slack=m["slack"], cond=1.0 + np.where(np.isfinite(m["cond"]), m["cond"], 0.0), mesh_hi=m["hi"], mesh_lo=m["lo"], floor=(fr, fs), light=(lr, ls), edge=m["edge"])
@@ -292,7 +304,8 @@ def nearest_violations(tr, hits):
     fs, ls = tr["floor"][1], tr["light"][1]
     bad["floor where the floor is not"] = (obj == 1) & ~(np.abs(t - fs) <= tt)
     bad["light where the light is not"] = (obj == 0) & ~(np.abs(t - ls) <= tt)
-    ident = tr["unique"] & ~miss & (tr["t_hi"] - tr["t_lo"] <= ID_BAND * tr["scale"])
+    with np.errstate(invalid="ignore"):                                  # (inf - inf where a ray has no candidate at all: NaN compares false)
+        ident = tr["unique"] & ~miss & (tr["t_hi"] - tr["t_lo"] <= ID_BAND * tr["scale"])
     bad["another object"] = ident & (obj != tr["obj"])
     mesh = ident & (tr["kind"] == 2) & (obj == tr["obj"])
     bad["another triangle"] = mesh & (tri != tr["tri"])
@@ -313,7 +326,8 @@ def rays_of(viol):
 def nearest_deviation(tr, hits):
     """the observed deviations on rays with a tight interval and a unique identity the answer shares: {quantity: max of |got - truth| / its scale}"""
     t = np.asarray(hits["t"], np.float64); obj = np.asarray(hits["objIdx"]); tri = np.asarray(hits["triIdx"])
-    tight = tr["unique"] & (obj == tr["obj"]) & (tr["t_hi"] - tr["t_lo"] <= 1e-9 * tr["scale"])
+    with np.errstate(invalid="ignore"):                                  # (inf - inf where a ray has no candidate at all: NaN compares false)
+        tight = tr["unique"] & (obj == tr["obj"]) & (tr["t_hi"] - tr["t_lo"] <= 1e-9 * tr["scale"])
     mesh = tight & (tr["kind"] == 2) & (tri == tr["tri"])
     cond = tr["cond"]
     out = dict(t=float((np.abs(t - tr["t_hi"]) / tr["scale"])[tight].max()) if tight.any() else 0.0, n=int(tight.sum()))
@@ -431,12 +445,13 @@ def hit_info_truth(world, O, D, tr, renormalise=True, flip=True):
     cond).  renormalise / flip = False: the doctored forms of the test."""
     O, D = np.asarray(O, np.float64), np.asarray(D, np.float64)
     n = len(O)
-    ok = tr["unique"] & np.isfinite(tr["t_hi"]) & (tr["t_hi"] - tr["t_lo"] <= ID_BAND * tr["scale"])
+    with np.errstate(invalid="ignore"):                                  # (inf - inf where a ray has no candidate at all: NaN compares false)
+        ok = tr["unique"] & np.isfinite(tr["t_hi"]) & (tr["t_hi"] - tr["t_lo"] <= ID_BAND * tr["scale"])
     t = np.where(ok, tr["t_hi"], 0.0)
     I = O + t[:, None] * D
     N = np.zeros((n, 3)); uv = np.zeros((n, 2)); mat = np.full(n, -1, np.int64)
     m = ok & (tr["kind"] == 0)
-    N[m] = [0.0, -1.0, 0.0]; mat[m] = 0                                   # Quad::GetNormal: -(T's y column), T = Translate
+    N[m] = -world.light_R[:, 1]; mat[m] = 0                               # Quad::GetNormal: -(T's y column)
     m = ok & (tr["kind"] == 1)
     N[m] = [0.0, 1.0, 0.0]; mat[m] = 1
     f = I[m][:, [0, 2]] * world.floor_invto
@@ -483,7 +498,8 @@ def hit_info_violations(tr, ti, hits, info):
 
 def hit_info_deviation(tr, ti, hits, info):
     obj = np.asarray(hits["objIdx"]); tri = np.asarray(hits["triIdx"])
-    m = ti["ok"] & ti["sure"] & (obj == tr["obj"]) & ((tr["kind"] != 2) | (tri == tr["tri"])) & (tr["t_hi"] - tr["t_lo"] <= 1e-9 * tr["scale"])
+    with np.errstate(invalid="ignore"):                                  # (inf - inf where a ray has no candidate at all: NaN compares false)
+        m = ti["ok"] & ti["sure"] & (obj == tr["obj"]) & ((tr["kind"] != 2) | (tri == tr["tri"])) & (tr["t_hi"] - tr["t_lo"] <= 1e-9 * tr["scale"])
     if not m.any():
         return dict(I=0.0, N=0.0, uv=0.0)
     uv = np.stack([info["u"], info["v"]], 1).astype(np.float64)

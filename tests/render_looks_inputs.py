@@ -3,12 +3,13 @@ test_render_looks_cpu.py for what they assume of the oracle).  A look is a dict 
 file's look (`base`) in exactly one thing, and "all" changes everything.  Texture indices are the host scene's: [0] the floor's, [1] the skydome, then the
 materials' in file order.  The image is 64 x 48: twelve 16 x 16 tiles.
 
-The oracle builds a scene per look through add_material / set_light_position / set_floor_texture / set_skydome.  It cannot express three of the looks, which are
-held to the fresh-upload comparison only (ORACLE_CANNOT):
-  light_turn   set_light_position is all the oracle has: its quad is never rotated;
-  light_size   the oracle's quad is Quad(0, 1): size 0.5, always;
-  floor        the oracle derives the floor plane's uv scale from the floor texture's width (file_scene.cpp:16), which is geometry, not part of a look: a look that
-               selects another floor texture keeps the uploaded scene's scale.  (No two textures of the test scenes share width // 100.)
+The oracle builds a scene per look through add_material / set_floor_texture / set_skydome and, for what no scene file says, set_light_quad (the look's T, invT
+and half size, cell for cell) and set_floor_uv_scale: the floor plane's uv scale is geometry of the UPLOADED scene (1 / (floor texture width // 100),
+file_scene.cpp:16), so a look that selects another floor texture keeps it.  Every look of both scenes is therefore held to the oracle.
+
+TRANSFORMS are the light quads of tests/light_quad_inputs.py and test_gpu_light_quad.py (name -> 4 x 4 float32 about a centre p); SIZES their half sizes.  All are
+rigid, and invT is inverse_no_scale(T).  A T that is not rigid, or an invT that is not T's FastInvertedTransformNoScale, is the caller's error: the reference's
+Quad would intersect one surface and shade another, no truth is defined for it, and nothing here tests it.
 """
 import math
 import os
@@ -22,7 +23,6 @@ F = np.float32
 SCENES = {"cube": ("cube_scene.xml", 0), "tlas": ("tlas_scene.xml", 1)}
 # the camera looks up from below the light, so that the quad itself, the meshes, the floor and the sky are all in the image
 CAMERAS = {"cube": ((0.0, 0.2, -2.5), (0.0, 1.3, 1.0)), "tlas": ((0.0, 0.4, -2.5), (0.0, 1.4, 1.5))}
-ORACLE_CANNOT = ("light_turn", "light_size", "floor", "all")
 
 
 def translate(p):
@@ -52,6 +52,49 @@ def with_material(look, i, refl=None, refr=None, absorb=None, tex=None):
     return out
 
 
+def rot(axis, deg):
+    """mat4::RotateX / RotateY / RotateZ (tmplmath.h:673-675) in float64"""
+    a = math.radians(deg); c, s = math.cos(a), math.sin(a); R = np.eye(4)
+    i, j = {"x": (1, 2), "y": (2, 0), "z": (0, 1)}[axis]
+    R[i, i], R[i, j], R[j, i], R[j, j] = c, -s, s, c
+    return R
+
+
+def exact(rows):
+    T = np.eye(4, dtype=F); T[:3, :3] = np.asarray(rows, F)
+    return T
+
+
+def transforms(p):
+    """{name: T} about the centre p.  z25: a tilt about z; zyx: no zero cell, no symmetry (R differs from its transpose in every off-diagonal cell); y45: the
+    normal unchanged, the square turned; quarter_z: cells exactly 0 / +-1, local y -> world x (a vertical quad); half_x: cells exactly 1, -1, -1 (face up)"""
+    t = translate(p).astype(np.float64)
+    out = {"z25": (t @ rot("z", 25.0)).astype(F), "zyx": (t @ rot("z", 25.0) @ rot("y", 30.0) @ rot("x", -35.0)).astype(F), "y45": (t @ rot("y", 45.0)).astype(F)}
+    out["quarter_z"] = translate(p) @ exact([[0, 1, 0], [-1, 0, 0], [0, 0, 1]])                  # exact products: one non-zero term each
+    out["half_x"] = translate(p) @ exact([[1, 0, 0], [0, -1, 0], [0, 0, -1]])
+    for T in out.values():
+        R = T[:3, :3].astype(np.float64)
+        assert np.abs(R @ R.T - np.eye(3)).max() < 2e-7 and np.linalg.det(R) > 0.999 and np.array_equal(T[:3, 3], np.asarray(p, F))
+        assert not (np.signbit(T) & (T == 0)).any() and not (np.signbit(inverse_no_scale(T)[:3, :3]) & (inverse_no_scale(T)[:3, :3] == 0)).any()   # no -0.0 cell
+    return out
+
+
+# looking up at the light from close by: the 0.9 quad reaches tiles the 0.5 quad leaves empty (tiles a classifier blind to the size would prove free of the
+# light), and the 0.03125 quad covers a pixel centre (test_render_looks_cpu.py holds both on the oracle)
+QUAD_CAMERAS = {"cube": ((0.3, 0.0, -1.2), (-0.25, 3.0, 1.0)), "tlas": ((0.3, 0.0, -0.6), (-0.25, 3.0, 1.5))}
+SIZES = {"cube": (0.9, 0.03125), "tlas": (0.9, 0.03125, 2.5)}     # 0.03125: about one pixel at the tests' cameras; 2.5: the quad's plane cuts the tlas meshes' boxes
+
+
+def quad_looks(scene, base):
+    """{name: look}: the file look with each transform of `transforms` at half size 0.5, each size of SIZES untransformed, and zyx at 0.9"""
+    p = light_position(base)
+    out = {n: with_light(base, T) for n, T in transforms(p).items()}
+    for s in SIZES[scene]:
+        out["size_%g" % s] = dict(base, light_size=s)
+    out["zyx_size_0.9"] = dict(out["zyx"], light_size=0.9)
+    return out
+
+
 def light_position(look):
     return np.asarray(look["light_T"], F).reshape(4, 4)[:3, 3].copy()
 
@@ -59,8 +102,7 @@ def light_position(look):
 def looks(scene, base):
     """{name: look} of `scene` ('cube' / 'tlas') round its file look `base`"""
     p = light_position(base)
-    turn = np.eye(4, dtype=np.float64); a = math.radians(25.0)
-    turn[:2, :2] = [[math.cos(a), -math.sin(a)], [math.sin(a), math.cos(a)]]                     # about z: the quad tilts, invT's rotation block is no identity
+    turn = rot("z", 25.0)                                                                        # about z: the quad tilts, invT's rotation block is no identity
     out = {"base": base}
     if scene == "cube":                          # one material, untextured diffuse; textures: pavement 512 x 512, sky 1024 x 512
         out["mirror"] = with_material(base, 0, refl=1.0)
@@ -101,15 +143,19 @@ def scene_textures(orc, sc):
     return [_images[p] for p in paths]
 
 
+def floor_invto(tex):
+    """the uploaded scene's floor uv scale: from the FILE's floor texture ([0]), whatever a look selects"""
+    return F(1.0) / F(tex[0].shape[1] // 100)
+
+
 def make_oracle(orc, scene, look, width=W, height=H):
-    """an oracle scene of `scene` with `look` (one of those the oracle can express), its renderer initialised"""
+    """an oracle scene of `scene` with `look`, its renderer initialised"""
     xml, kind = SCENES[scene]
     sc = orc.read_scene_xml(scene_path(xml))
     tex = scene_textures(orc, sc)
-    assert float(look["light_size"]) == 0.5 and np.array_equal(np.asarray(look["light_T"], F).reshape(4, 4)[:3, :3], np.eye(3, dtype=F))
-    assert tex[look["floor_texture"]].shape[1] // 100 == tex[0].shape[1] // 100
     o = orc.Oracle(kind)
-    o.set_light_position([float(x) for x in light_position(look)])
+    o.set_light_quad(look["light_T"], look["light_invT"], look["light_size"])
+    o.set_floor_uv_scale(floor_invto(tex))
     o.set_floor_texture(tex[look["floor_texture"]])
     o.set_skydome(tex[look["sky_texture"]])
     for refl, refr, ab, t in look["materials"]:
@@ -142,6 +188,21 @@ def light_tiles(orc, o, camera, width=W, height=H):
 def tile_slice(t, width=W):
     tx, ty = t % (width // 16), t // (width // 16)
     return slice(16 * ty, 16 * ty + 16), slice(16 * tx, 16 * tx + 16)
+
+
+def floor_rays(invto, n=2048, seed=9):
+    """(O, D) float32 that meet the floor: three quarters spread over the floor round the scene, a quarter aimed next to the lines x = k / invto and z = k / invto,
+    where frac(u) wraps from nearly 1 to 0 (the texel column changes from the last to the first)"""
+    rng = np.random.default_rng(seed)
+    k = n // 4
+    P = np.stack([rng.uniform(-6, 6, n), np.full(n, -1.0), rng.uniform(-4, 8, n)], 1)
+    line = rng.integers(-1, 2, k) / float(invto) + rng.choice([-1.0, 1.0], k) * rng.choice([1e-6, 1e-4, 1e-2], k)
+    axis = np.arange(k) % 2
+    P[:k, 0] = np.where(axis == 0, line, P[:k, 0]); P[:k, 2] = np.where(axis == 1, line, P[:k, 2])
+    O = np.stack([rng.uniform(-1, 1, n), rng.uniform(0.2, 2.0, n), rng.uniform(-2.5, -1.0, n)], 1)
+    D = P - O
+    D /= np.linalg.norm(D, axis=1, keepdims=True)
+    return O.astype(F), D.astype(F)
 
 
 # ---- the jobs ----

@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 import analytic_truth as at
+import render_looks_inputs as li
 from conftest import ASSETS
 from test_gpu_golden_and_edges import write_scene
 from test_gpu_primitive_scene import _rays
@@ -135,3 +136,103 @@ def test_primitive_scene(orc, t):
     tw, iw, margin = at.prim_truth(O, D, t)
     seen = at.prim_check(g["t"], g["objIdx"], tw, iw, margin)
     print("t = %s: %d rays under the margin; observed |dt| %s" % (t, (margin < at.NEAR).sum(), {k: "%.3g" % v for k, v in seen.items()}))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------------------
+# the light quad of a look: turned, resized (analytic_truth.QUAD_LOOKS)
+# ---------------------------------------------------------------------------------------------------------------------------------------------------
+RHO, L_SKY = at.texel_rgb(at.FLOOR_RGB), at.texel_rgb(at.SKY_RGB)
+
+
+def look_oracle(orc, xml, name):
+    o = oracle(orc, xml, 0)
+    T, half = at.look_cells(name)
+    o.set_light_quad(T, li.inverse_no_scale(T), half)
+    return o
+
+
+def test_quad_looks_are_the_look_tests_transforms():
+    tr = li.transforms(np.asarray(at.LIGHT_POS, np.float32))
+    for name, key in (("zyx", "zyx"), ("z25", "z25"), ("half_x", "half_x"), ("zyx_size_0.9", "zyx")):
+        assert np.array_equal(at.look_cells(name)[0].reshape(4, 4), tr[key]), name
+    assert np.array_equal(at.look_cells("size_0.9")[0].reshape(4, 4), li.translate(np.asarray(at.LIGHT_POS, np.float32)))
+
+
+def test_general_quad_truth_checks_itself():
+    """the general forms come to the parallel ones (1e-12), and Lambert's contour formula to the 400 x 400 midpoint quadrature (1e-6), for every look and point"""
+    pts = list(at.QUAD_FLOOR_POINTS) + [[1.2, 2.0, 0.5], [-4.0, -1.0, 6.0]]
+    same = (at.QUAD[0], np.eye(3), at.QUAD[1])
+    for P in pts:
+        P = np.asarray(P)
+        assert abs(float(at.cos2_solid_angle(P, same)) - float(at.cos2_solid_angle_parallel(P, at.QUAD))) <= 1e-12
+        assert abs(float(at.form_factor(P, same)) - float(at.form_factor(P, at.QUAD))) <= 1e-12
+        m1, s1 = at.floor_radiance(P, RHO, L_SKY, same); m0, s0 = at.floor_radiance(P, RHO, L_SKY, at.QUAD)
+        assert np.abs(m1 - m0).max() <= 1e-12 and np.abs(s1 - s0).max() <= 1e-12
+    n = 400; u = ((np.arange(n) + 0.5) / n * 2 - 1)
+    for name in at.QUAD_LOOKS:
+        q = at.look_quad(name); c, R, h = q
+        assert (at.quad_corners(q)[:, 1] > at.FLOOR_Y + 1.0).all()            # wholly above the floor
+        for P in at.QUAD_FLOOR_POINTS:
+            assert abs(float(at.form_factor(P, q)) - at.form_factor_quadrature(P, q)) <= 1e-6, (name, P)
+            d = c + (u * h)[:, None, None] * R[:, 0] + (u * h)[None, :, None] * R[:, 2] - P
+            r2 = (d * d).sum(-1)
+            brute = (d[..., 1] ** 2 * np.abs(d @ R[:, 1]) / r2 ** 2.5).sum() * (2 * h / n) ** 2
+            assert abs(float(at.cos2_solid_angle(P, q)) - brute) <= 1e-6, (name, P)
+    # the figures the cases were chosen by: under zyx the two points either side of the centre tell R from its transpose, the point under it cannot
+    m = [at.floor_radiance(P, RHO, L_SKY, at.look_quad("zyx"))[0][0] for P in at.QUAD_FLOOR_POINTS[[3, 4, 0]]]
+    c, R, h = at.look_quad("zyx")
+    mt = [at.floor_radiance(P, RHO, L_SKY, (c, R.T, h))[0][0] for P in at.QUAD_FLOOR_POINTS[[3, 4, 0]]]
+    assert np.allclose(m, [0.5248, 0.4152, 0.5071], atol=5e-5) and np.allclose(mt, [0.4374, 0.5037, 0.5071], atol=5e-5), (m, mt)
+
+
+def test_wrong_quad_models_lie_outside_the_band():
+    """negative controls: each wrong model's truth lies beyond the right one's Z = 5 band by at least twice the band (three bands from the right mean), on some
+    channel, at two or more floor points of a look that is tested; the Whitted control against check_whitted's bound in the same way"""
+    def far_points(name, wrong):
+        q = at.look_quad(name); k = 0
+        for P in at.QUAD_FLOOR_POINTS:
+            m, s2 = at.floor_radiance(P, RHO, L_SKY, q)
+            band = at.Z * np.sqrt(s2 - m * m) / np.sqrt(at.N_FLOOR)
+            assert (band <= 0.025 * m).all()                                  # 2.4 % of the mean at most
+            k += bool((np.abs(wrong(P, q) - m) >= 3 * band).any())
+        return k
+    transposed = lambda P, q: at.floor_radiance(P, RHO, L_SKY, (q[0], q[1].T, q[2]))[0]      # noqa: E731
+    no_size = lambda P, q: at.floor_radiance(P, RHO, L_SKY, (q[0], q[1], 0.5))[0]            # noqa: E731
+    one_face = lambda P, q: at.floor_radiance(P, RHO, L_SKY, q, one_face=True)[0]            # noqa: E731
+    assert far_points("zyx", transposed) >= 2 and far_points("z25", transposed) >= 2 and far_points("zyx_size_0.9", transposed) >= 2
+    assert far_points("size_0.9", no_size) == 5 and far_points("zyx_size_0.9", no_size) == 5
+    assert far_points("half_x", one_face) == 5
+    for name in ("zyx", "z25", "half_x", "zyx_size_0.9"):
+        q = at.look_quad(name)
+        d = [np.abs(at.whitted_floor(P, RHO, q, along_normal=True)[0] - at.whitted_floor(P, RHO, q)[0]).max() for P in at.QUAD_FLOOR_POINTS]
+        assert sum(x >= 3 * at.WHITTED_QUAD_TOL for x in d) >= 2, (name, d)
+
+
+@pytest.mark.parametrize("name", sorted(at.QUAD_LOOKS))
+def test_floor_points_and_whitted_under_a_quad_look(orc, scenes, name):
+    """the oracle with set_light_quad against the expectation: Sample at the two floor points either side of the centre (the GPU module takes all five), and the
+    Whitted image of the floor"""
+    o = look_oracle(orc, scenes["S0"], name)
+    q = at.look_quad(name)
+    for k in (3, 4):
+        O, D, mean, second, seeds = at.floor_case(k, q, salt=sorted(at.QUAD_LOOKS).index(name))
+        assert o.find_nearest(O, D)["objIdx"][0] == 1
+        at.check_mean(at.oracle_samples(o, O, D, seeds), mean, second, "%s, floor point %d" % (name, k))
+    o.whitted(4)
+    at.check_whitted(o.accumulator(), [], "whitted under %s" % name, shadow=name == "z25", quad=q, tol=at.WHITTED_QUAD_TOL)     # (z25: far floor lies behind the tilted quad's plane)
+
+
+def test_render_and_light_pixels_under_quad_looks(orc, scenes, flat_sky):
+    """ProcessTile's floor-tile means under every look, and the ring of pixels that see the 0.9 quad but not the 0.5 quad: exactly the light's colour"""
+    for name in sorted(at.QUAD_LOOKS):
+        o = look_oracle(orc, scenes["S0"], name)
+        o.render(at.FRAMES, 8)
+        at.check_render(o.accumulator(), at.FRAMES, flat_sky, "render under %s" % name, quad=at.look_quad(name), key=name)
+    o = look_oracle(orc, scenes["S0"], "size_0.9")
+    o.set_camera_state(*at.LIGHT_CAMERA); o.render(at.LIGHT_FRAMES, 8)
+    ring = at.check_light_pixels(o.accumulator(), at.LIGHT_FRAMES, "ring", quad=(at.QUAD[0], 0.9), beyond=at.QUAD)
+    assert ring >= 200
+    plain = oracle(orc, scenes["S0"], 0)
+    plain.set_camera_state(*at.LIGHT_CAMERA); plain.render(at.LIGHT_FRAMES, 8)
+    with pytest.raises(AssertionError):                                     # the 0.5 quad leaves the ring to the sky
+        at.check_light_pixels(plain.accumulator(), at.LIGHT_FRAMES, "ring without the size", quad=(at.QUAD[0], 0.9), beyond=at.QUAD)

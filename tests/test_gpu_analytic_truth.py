@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import analytic_truth as at
+import render_looks_inputs as li
 from conftest import ASSETS
 from test_gpu_golden_and_edges import write_scene
 from test_gpu_primitive_scene import _rays
@@ -161,4 +162,88 @@ def test_primitive_scene(crt, orc, t):
     at.prim_check(h["t"], h["objIdx"], tw, iw, margin)
     g = orc.primitive_scene(ASSETS, t).find_nearest(O, D)
     assert np.array_equal(h["objIdx"], g["objIdx"]) and np.array_equal(bits(h["t"]), bits(g["t"]))
+    ctx.close()
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------------------
+# the light quad of a look, turned and resized (analytic_truth.QUAD_LOOKS), applied by update_look and as one render_looks job
+# ---------------------------------------------------------------------------------------------------------------------------------------------------
+LOOK_NAMES = sorted(at.QUAD_LOOKS)
+
+
+def look_record(crt, hs, name):
+    T, half = at.look_cells(name)
+    return crt.look_records([dict(li.with_light(crt.look_dicts(hs.look())[0], T.reshape(4, 4)), light_size=float(half))])[0]
+
+
+def look_oracle(orc, xml, kind, name):
+    o, _ = orc.load_scene(xml, kind, ASSETS); o.renderer_init(at.W, at.H)
+    T, half = at.look_cells(name)
+    o.set_light_quad(T, li.inverse_no_scale(T), half)
+    return o
+
+
+@pytest.mark.parametrize("world", ["bvh", "tlas"])
+@pytest.mark.parametrize("name", LOOK_NAMES)
+def test_sample_floor_points_under_a_quad_look(crt, orc, scenes, name, world):
+    kind = 1 if world == "tlas" else 0
+    hs = crt.HostScene(scenes["S0"], kind, ASSETS)
+    ctx = crt.Context(at.W, at.H); hs.upload(ctx)
+    ctx.update_look(look_record(crt, hs, name))
+    o = look_oracle(orc, scenes["S0"], kind, name)
+    q = at.look_quad(name)
+    for k in range(len(at.QUAD_FLOOR_POINTS)):
+        O, D, mean, second, seeds = at.floor_case(k, q, salt=LOOK_NAMES.index(name))
+        what = "%s, floor point %d through %s" % (name, k, world)
+        at.check_mean(sample_one_ray(ctx, o, 0, O, D, seeds, what), mean, second, what)
+    ctx.close()
+
+
+@pytest.mark.parametrize("mode", ["tiles", "pool", "pool32"])
+@pytest.mark.parametrize("name", LOOK_NAMES)
+def test_render_of_the_floor_under_quad_looks(crt, orc, scenes, flat_sky, monkeypatch, name, mode):
+    """per look: floor-tile means against the expectation and the oracle's bits; under the 0.9 quad, looking up: every pixel inside its projection and wholly
+    outside the 0.5 quad's is exactly the light's colour (tiles a classifier blind to lightSize would prove free of the light)"""
+    if mode != "tiles":
+        monkeypatch.setenv("CRT_RENDER_KERNEL", "pool_always")
+    if mode == "pool32":
+        monkeypatch.setenv("CRT_DEBUG_NO_REF16", "1")
+    hs = crt.HostScene(scenes["S0"], 0, ASSETS)
+    ctx = crt.Context(at.W, at.H, max_frames_per_launch=64 if mode == "tiles" else 4096); hs.upload(ctx)
+    ctx.update_look(look_record(crt, hs, name))
+    ctx.render(1, at.FRAMES, 1)
+    acc, tm = ctx.accumulator(), ctx.timing()
+    assert (tm["pool_launches"] == 0) == (mode == "tiles"), tm
+    at.check_render(acc, at.FRAMES, flat_sky, "%s under %s" % (mode, name), quad=at.look_quad(name), key=name)
+    o = look_oracle(orc, scenes["S0"], 0, name); o.render(at.FRAMES, 8)
+    assert np.array_equal(acc, o.accumulator()), (mode, name)
+    if name == "size_0.9":
+        ctx.clear(); ctx.set_camera_state(*at.LIGHT_CAMERA); ctx.render(1, at.LIGHT_FRAMES, 1)
+        ring = at.check_light_pixels(ctx.accumulator(), at.LIGHT_FRAMES, mode + ", the ring round the 0.5 quad", quad=(at.QUAD[0], 0.9), beyond=at.QUAD)
+        assert ring >= 200
+    ctx.close()
+
+
+def test_whitted_floor_under_quad_looks(crt, orc, scenes):
+    hs = crt.HostScene(scenes["S0"], 0, ASSETS)
+    ctx = crt.Context(at.W, at.H); hs.upload(ctx)
+    for name in LOOK_NAMES:
+        ctx.update_look(look_record(crt, hs, name))
+        px = ctx.whitted_tick(); acc = ctx.accumulator()
+        at.check_whitted(acc, [], "whitted_tick under %s" % name, shadow=name == "z25", quad=at.look_quad(name), tol=at.WHITTED_QUAD_TOL)
+        o = look_oracle(orc, scenes["S0"], 0, name); o.whitted(4)
+        assert np.array_equal(acc, o.accumulator()) and np.array_equal(px, o.screen()), name
+    ctx.close()
+
+
+def test_one_render_looks_job_of_the_quad_looks(crt, scenes, flat_sky):
+    """the five looks as one job through the default camera: per view the floor-tile means of its own look (the live look stays the file's)"""
+    hs = crt.HostScene(scenes["S0"], 0, ASSETS)
+    ctx = crt.Context(at.W, at.H, max_frames_per_launch=4096); hs.upload(ctx)
+    cams = crt.camera_records(at.W, at.H, [((0.0, 0.0, -2.0), (0.0, 0.0, 0.0))] * len(LOOK_NAMES))          # Camera(): camera.h:14-22
+    acc = ctx.render_looks(cams, np.stack([look_record(crt, hs, n) for n in LOOK_NAMES]), 1, at.FRAMES, 1)
+    for k, name in enumerate(LOOK_NAMES):
+        at.check_render(acc[k], at.FRAMES, flat_sky, "render_looks view %d (%s)" % (k, name), quad=at.look_quad(name), key=name)
+    ctx.clear(); ctx.render(1, at.FRAMES, 1)
+    at.check_render(ctx.accumulator(), at.FRAMES, flat_sky, "the live look after the job")
     ctx.close()

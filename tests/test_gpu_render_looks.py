@@ -2,7 +2,7 @@
 render_looks.h).  Every comparison is bit for bit (np.array_equal on the bit patterns) against
   the update loop   update_look(look) + set_camera_state + clear + render + accumulator per view, on a SECOND context;
   the fresh loop    HostScene.set_look(look) + upload + the same render per view, on a THIRD context: what a scene uploaded with that look renders;
-  the oracle        a scene built with that look (render_looks_inputs.make_oracle), for the looks the oracle can express.
+  the oracle        a scene built with that look (render_looks_inputs.make_oracle).
 The scenes, looks, cameras and cases are tests/render_looks_inputs.py's; tests/test_render_looks_cpu.py holds, without a GPU, that every look changes the image, so
 a lane that shades with the wrong look or ignores one of its fields cannot pass here."""
 import ctypes as C
@@ -88,14 +88,14 @@ class Rig:
         return self._views(c, views, "fresh", render)
 
     def oracle_views(self, c):
-        """{view: accumulator} of the views whose look the oracle can express"""
-        ks = [k for k in range(c.K) if c.look_of(k) not in li.ORACLE_CANNOT]
+        """{view: accumulator} of every view"""
+        ks = list(range(c.K))
 
         def render(name, camera):
             if name not in self._oracles:
                 self._oracles[name] = li.make_oracle(self.orc, self.scene, self.looks[name], self.W, self.H)
             return li.oracle_render(self._oracles[name], camera, c.spp_first, c.frames, c.passes)
-        return dict(zip(ks, self._views(c, ks, "oracle", render))) if ks else {}
+        return dict(zip(ks, self._views(c, ks, "oracle", render)))
 
     def run(self, c, ctx=None, **kw):
         return (ctx or self.ctx).render_looks(self.records(c), self.look_array(c), c.spp_first, c.frames, c.passes, view_look=c.view_look, **kw)
@@ -140,7 +140,7 @@ def test_looks_equal_both_loops_and_the_oracle(rigs, name):
     bad = [v for v in range(c.K) if not same(acc[v], fresh[v])]
     assert not bad, (name, "fresh-upload loop", bad)
     told = r.oracle_views(c)
-    assert len(told) >= 2, name
+    assert len(told) == c.K, name
     bad = [v for v, a in told.items() if not same(acc[v], a)]
     assert not bad, (name, "oracle", bad)
     assert (acc[..., 3].view(np.uint32) == 0).all()                        # w = +0

@@ -1,6 +1,6 @@
 """crt_update_look: the live scene's look — materials, floor texture, skydome, light quad — changed in place.  After the call every entry that shades must give bit
 for bit what a FRESH context gives that uploaded the scene's description with that look (HostScene.set_look + upload, followed by the same alternative-accelerator
-uploads), and what the oracle gives where it can express the look (render_looks_inputs.ORACLE_CANNOT lists the looks it cannot).  The looks are
+uploads), and what the oracle gives for a scene built with that look (render_looks_inputs.make_oracle).  The looks are
 tests/render_looks_inputs.py's; tests/test_render_looks_cpu.py holds, without a GPU, that each of them changes the image."""
 import ctypes as C
 
@@ -56,7 +56,7 @@ def test_render_after_every_look(rigs, scene):
         assert same(got, r.fresh_loop(c)[0]), (scene, name, "fresh upload")
         for a in r.oracle_views(c).values():
             assert same(got, a), (scene, name, "oracle")
-        assert same(got, base) == (name == "base"), (scene, name)            # every look changes the image, the oracle's or not
+        assert same(got, base) == (name == "base"), (scene, name)            # every look changes the image
     r.ctx.update_look(r.rec["base"])
 
 
@@ -75,8 +75,7 @@ def test_pool_kernel_after_a_look(crt, orc, monkeypatch, rigs, scene, name):
         assert t["render_launches"] == 1 and t["pool_launches"] == 1, t
         out.append(ctx.accumulator())
     assert same(out[0], out[1])
-    if name not in li.ORACLE_CANNOT:
-        assert same(out[0], r.oracle_views(one(scene, name, 64))[0])
+    assert same(out[0], r.oracle_views(one(scene, name, 64))[0])
     a.close(); b.close()
 
 
@@ -129,11 +128,10 @@ def test_queries_after_a_look(crt, orc, rigs, scene):
         assert same(a.get_sky_color(D), b.get_sky_color(D)), name
         la, lb = a.get_light(), b.get_light()
         assert same(la[0], lb[0]) and same(la[1], lb[1]) and same(la[0], base_light) == (name != "all")
-        if name not in li.ORACLE_CANNOT:                                     # the oracle's Sample, ray by ray
-            ol = li.make_oracle(orc, scene, r.looks[name])
-            for i in range(0, len(O), 7):
-                want, seed = ol.sample(O[i], D[i], int(seeds[i]))
-                assert same(sa[0][i], want) and int(sa[1][i]) == seed, (name, i)
+        ol = li.make_oracle(orc, scene, r.looks[name])                       # the oracle's Sample, ray by ray
+        for i in range(0, len(O), 7):
+            want, seed = ol.sample(O[i], D[i], int(seeds[i]))
+            assert same(sa[0][i], want) and int(sa[1][i]) == seed, (name, i)
     r.ctx.update_look(r.rec["base"])
 
 

@@ -14,7 +14,9 @@ import pytest
 import alt_disagreement as AD
 import bvh_build_inputs as B
 import hit_info_restate as hr
+import light_quad_inputs as lq
 import mesh_truth as mt
+import render_looks_inputs as li
 from conftest import ASSETS
 from mesh_truth_scenes import SCENES, describe, load, moved_records, report, scene_xml, through
 
@@ -391,3 +393,83 @@ def test_rejects_normals_not_flipped(orc, cases):
         m = flipped & c.ti["ok"] & c.ti["sure"] & (hits["objIdx"] == c.tr["obj"]) & ((c.tr["kind"] != 2) | (hits["triIdx"] == c.tr["tri"]))
         hv, _ = mt.hit_info_violations(c.tr, c.ti, hits, info)
         assert m.sum() >= 50 and np.array_equal(hv.get("N", []), np.flatnonzero(m)), scene     # (a closed mesh turns its normal only for a ray that starts inside)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------------------
+# the light quad of a look: turned, resized (light_quad_inputs.py; the kernels: tests/test_gpu_light_quad.py)
+# ---------------------------------------------------------------------------------------------------------------------------------------------------
+def quad_base(orc, scene):
+    """the file look's light fields, as the library's HostScene.look() gives them (test_render_looks_cpu.py holds that equality)"""
+    T = li.translate(np.asarray(orc.read_scene_xml(li.scene_path(li.SCENES[scene][0]))["light"], np.float32))
+    return dict(light_T=T.reshape(16), light_invT=li.inverse_no_scale(T).reshape(16), light_size=0.5)
+
+
+QUAD_CASES = [(s, n) for s in sorted(li.SCENES) for n in ("z25", "zyx", "y45", "quarter_z", "half_x", "zyx_size_0.9") + tuple("size_%g" % x for x in li.SIZES[s])]
+
+
+@pytest.mark.parametrize("scene,name", QUAD_CASES)
+def test_oracle_meets_the_criterion_under_a_quad_look(orc, scene, name):
+    """the rays of light_quad_inputs meet the caps, and the oracle with set_light_quad meets the float64 truth on them: nearest hit, occlusion, the light's normal
+    from both faces; GetLightPos is the restatement's; on the two quads of exact cells the float32 one-liner predicts the light's t bit for bit"""
+    look = li.quad_looks(scene, quad_base(orc, scene))[name]
+    xml, kind = li.SCENES[scene]
+    o, sc = orc.load_scene(li.scene_path(xml), kind, ASSETS)
+    o.set_light_quad(look["light_T"], look["light_invT"], look["light_size"])
+    c = lq.Case(orc, scene, name, look, o)
+    front, back = c.light_faces()
+    assert front >= 100 and back >= 100, (front, back)
+    for world in (("bvh", "grid") if kind == 0 else ("tlas", "tlas_grid")):
+        hits = through(orc, o, world).find_nearest(c.O, c.D)
+        viol = mt.nearest_violations(c.tr, hits)
+        assert not viol, report("%s under %s through %s" % (scene, name, world), viol, c.O, c.D, hits, c.tr)
+        bad = mt.occluded_violations(c.occ[0], c.occ[1], o.is_occluded(c.O, c.D, c.ts))
+        assert len(bad) == 0, (scene, name, world, "is_occluded", bad[:8].tolist())
+    through(orc, o, "bvh" if kind == 0 else "tlas")
+    sh_cls = c.cls == lq.CLASSES.index("shadow")
+    assert (c.occ[0] & sh_cls).sum() >= 40 and (~c.occ[1] & sh_cls).sum() >= 15         # the lengths just beyond / just short of the quad decide
+    sh = hr.SceneShading(orc, o, sc, kind, ASSETS)
+    full = dict(look, floor_texture=0, sky_texture=1, materials=[(m["reflectivity"], m["refractivity"], tuple(m["absorption"]), -1) for m in sc["materials"]])
+    k = 2
+    for i, m in enumerate(sc["materials"]):                                  # texture indices as the host scene numbers them
+        if m["texture"]:
+            full["materials"][i] = full["materials"][i][:3] + (k,); k += 1
+    sh.set_look(full)
+    info = sh.hit_info(c.O, c.D, hits)
+    hv, n = mt.hit_info_violations(c.tr, c.ti, hits, info)
+    assert n >= 0.7 * len(c.O) and not hv, (scene, name, {k: (len(v), v[:4].tolist()) for k, v in hv.items()})       # (a fifth of these rays are made to miss)
+    q = o.light()
+    assert np.array_equal(q["pos"].view(np.uint32), sh.light_pos().view(np.uint32)) and np.array_equal(q["normal"].view(np.uint32), sh.light_normal().view(np.uint32))
+    T = np.asarray(look["light_T"], np.float32).reshape(4, 4)
+    assert abs(float(q["pos"][1]) - (float(T[1, 3]) - 0.01)) < 1e-6 and np.abs(q["pos"][[0, 2]] - T[[0, 2], 3]).max() < 1e-6       # 0.01 down in WORLD y, whatever the normal
+    if name in ("quarter_z", "half_x"):
+        assert q["normal"].tolist() == {"quarter_z": [-1.0, 0.0, 0.0], "half_x": [0.0, 1.0, 0.0]}[name]
+        cand, t = lq.axis_form(name, T, look["light_size"], c.O, c.D)
+        lit = hits["objIdx"] == 0
+        assert lit.sum() >= 300 and cand[lit].all() and np.array_equal(hits["t"][lit].view(np.uint32), t[lit].view(np.uint32))
+        assert (hits["t"][cand & ~lit] < t[cand & ~lit]).all() and (hits["objIdx"][cand & ~lit] >= 1).all()     # something nearer
+        eO, eD = lq.exact_rays(T, look["light_size"], 5)
+        eh = o.find_nearest(eO, eD)
+        assert not (eh["objIdx"] == 0).any() and not lq.axis_form(name, T, look["light_size"], eO, eD)[0].any()
+
+
+def test_a_wrong_quad_is_rejected(orc):
+    """the criterion has teeth on these rays: the oracle with the rotation transposed, with the size ignored, and with the un-turned quad breaks it.  (y45 is
+    not asked to tell R from its transpose: a square turned by +45 and by -45 degrees about its normal is one square; and half_x, the square turned face up onto itself, is
+    told from the un-turned quad by nothing a query returns, GetHitInfo's normal being turned towards the ray: it is there for the general form with exact cells.)"""
+    scene = "cube"; xml, kind = li.SCENES[scene]
+    looks = li.quad_looks(scene, quad_base(orc, scene))
+    o, _ = orc.load_scene(li.scene_path(xml), kind, ASSETS)
+    for name, wrong in (("zyx", "transposed"), ("z25", "transposed"), ("y45", "unturned"), ("size_0.9", "size"), ("size_0.03125", "size"), ("quarter_z", "unturned")):
+        look = looks[name]
+        c = lq.Case(orc, scene, name, look, o)
+        T = np.asarray(look["light_T"], np.float32).reshape(4, 4).copy(); size = look["light_size"]
+        if wrong == "transposed":
+            T[:3, :3] = T[:3, :3].T.copy()
+        elif wrong == "size":
+            size = 0.5
+        elif wrong == "unturned":
+            T[:3, :3] = np.eye(3)
+        o.set_light_quad(T, li.inverse_no_scale(T), size)
+        hits = o.find_nearest(c.O, c.D)
+        n = mt.count(mt.nearest_violations(c.tr, hits))
+        assert n >= 50, (name, wrong, n)

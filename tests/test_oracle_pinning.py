@@ -518,3 +518,59 @@ def test_alt_accel_live(orc, live):
             live.check("alt %s %s" % (kind, k), np.asarray(db[k]), None if da is None else np.asarray(da[k]))
         for f in hb.dtype.names:
             live.check("alt %s hit %s" % (kind, f), hb[f], None if ha is None else ha[f])
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------------------
+# the light quad and floor plane of a look (orc_set_light_quad / orc_set_floor_uv_scale) against the reference's own Quad and Plane
+# ---------------------------------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("scene", ["cube", "tlas"])
+def test_oracle_quad_and_plane_vs_reference_classes(orc, scene):
+    """Quad(0, 2 * size, T) and Plane(1, (0, 1, 0), 1, width / 100) of the reference, compiled in place, against the oracle's QuadPrim with the cells
+    set_light_quad takes and its PlanePrim with set_floor_uv_scale's factor, bit for bit: Intersect, IsOccluded, GetNormal, GetUV, the constructor's invT and
+    size, and GetLightPos's expression, for every transform and size of render_looks_inputs on the rays of light_quad_inputs (the exact ones included)"""
+    import light_quad_inputs as lq
+    import mesh_truth as mt
+    import mesh_truth_scenes as MC
+    import render_looks_inputs as li
+    try:
+        ref = orc.Ref()
+    except FileNotFoundError:
+        pytest.skip("oracle/_ref is not built (no reference tree on this machine)")
+    if not (ref.has("ref_quad_probe") and ref.has("ref_plane_probe")):
+        pytest.skip("oracle/_ref was built from an earlier harness and the reference tree is gone: nothing to rebuild it from")
+    xml, kind = li.SCENES[scene]
+    o, _ = orc.load_scene(li.scene_path(xml), kind, ASSETS)
+    _, light, obj_mat, invto = MC.describe(orc, li.scene_path(xml))
+    T0 = li.translate(np.asarray(light, np.float32))
+    base = dict(light_T=T0.reshape(16), light_invT=li.inverse_no_scale(T0).reshape(16), light_size=0.5)
+    bits = lambda a: np.ascontiguousarray(a).view(np.uint32)                # noqa: E731
+    looks = dict(li.quad_looks(scene, base), base=base)
+    for name, look in looks.items():
+        T = np.asarray(look["light_T"], np.float32).reshape(4, 4); size = look["light_size"]
+        w = mt.world_of(o, kind, light, obj_mat, invto, light_T=T, light_half=size)
+        O, D, given, cls = lq.make_rays(w, 1024, seed=7)
+        tmax = np.where(np.isnan(given), np.float32(3.0), given).astype(np.float32)
+        if name in ("quarter_z", "half_x"):
+            eO, eD = lq.exact_rays(T, size, 5)
+            O, D, tmax = np.concatenate([O, eO]), np.concatenate([D, eD]), np.concatenate([tmax, np.full(len(eO), 3.0, np.float32)])
+        theirs = ref.quad_probe(T, size, O, D, tmax)
+        assert np.array_equal(bits(theirs["invT"]), bits(li.inverse_no_scale(T))) and theirs["size"] == np.float32(size), name      # what a look's record carries
+        mine = orc.quad_probe(T, look["light_invT"], size, O, D, tmax)
+        for k in ("t", "objIdx", "occluded", "normal"):
+            assert np.array_equal(bits(mine[k]), bits(theirs[k])), (scene, name, k)
+        assert (theirs["objIdx"] == 0).sum() >= 300 and (theirs["objIdx"] == -1).sum() >= 200 and 100 <= theirs["occluded"].sum() <= len(O) - 100, name
+        o.set_light_quad(T, look["light_invT"], size)                       # ... and the scene's own quad is that QuadPrim
+        q = o.light()
+        assert np.array_equal(bits(q["pos"]), bits(theirs["pos"])) and np.array_equal(bits(q["normal"]), bits(theirs["normal"])), (scene, name)
+        lit = o.find_nearest(O, D)
+        m = lit["objIdx"] == 0
+        assert m.sum() >= 250 and (theirs["objIdx"][m] == 0).all() and np.array_equal(bits(lit["t"][m]), bits(theirs["t"][m])), (scene, name)
+    # the floor: the file's own scale, another texture's, and one no texture width gives
+    for offset in (5, 10, 40, 7.5):
+        theirs = ref.plane_probe(offset, O, D)
+        mine = orc.plane_probe(theirs["invto"], O, D)
+        assert theirs["invto"] == np.float32(1.0) / np.float32(offset) and (theirs["objIdx"] == 1).sum() >= 200
+        for k in ("t", "objIdx", "uv"):
+            assert np.array_equal(bits(mine[k]), bits(theirs[k])), (offset, k)
+    o.set_floor_uv_scale(np.float32(1.0) / np.float32(7.5))
+    assert o.light()["floor_invto"] == ref.plane_probe(7.5, O[:1], D[:1])["invto"]
